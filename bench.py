@@ -536,6 +536,68 @@ def lpt_curve(seq_dir, tmp, devices, scale=20, timeout=900, time_field=True):
                     "Unmeasured on more than one physical GPU until an 8-GPU node runs it."}
 
 
+DUMP_PAIRS_PER_SCAN = 4096  # scan points whose final pairing is dumped, per scan of the last batch (all pairings are ~90 MB)
+
+
+def batch_slot(b, K, up):
+    """Batch b of a measurement (0, 1, ...): (buffer set, pairs block, scan set) it runs on.  Buffer sets and pairs blocks
+    alternate; the K batches of a step read the K scan sets in turn."""
+    cur = b & 1
+    return (cur if up else 0), cur, b % K
+
+
+def dump_outputs(out_dir, step_results, pairs, scan_sizes, all_poses):
+    """--dump-outputs: what the timed path handed back in its last step, as DIR/<name>.npy (float64; float32 where the
+    product returns float32).
+
+    Per scan of the step, one row each, batch-major (row = batch * S + job, K batches of S jobs): pose, covariance,
+    quality and the counters that depend on the computation alone (no timings, launch or poll counts).  `gathered_poses`:
+    the poses of the last batch from every rank.
+
+    Final pairings (`pairs_*`): the point-to-point pairings the batch call downloads for the step's last batch (its pairs
+    block; plane pairings of NDT maps are not part of it, and the bench's maps give none).  The sample is a fixed set of
+    scan points, not of positions in the pairing list: DUMP_PAIRS_PER_SCAN local indices per job, drawn from the scan's
+    size with a seed per job, so the rows of two builds line up even when their pair counts differ.
+    `pairs_pose_row` is the scan's row in pose.npy ((K - 1) * S + job), `pairs_local_idx` the scan point, `pairs_paired`
+    1 where that point has a pairing and 0 where not (global index, point and d2 are then NaN)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rs = [r for batch in step_results for r in batch]
+    arrays = {
+        "pose": np.stack([np.asarray(r["T"], np.float64) for r in rs]),
+        "covariance": np.stack([np.asarray(r["cov"], np.float64) for r in rs]),
+        "quality": np.array([r["quality"] for r in rs], np.float64),
+    }
+    for key in ("n_iterations", "termination_reason", "n_final_pairs", "n_final_pairs_pt2pl", "potential_pairings"):
+        arrays[key] = np.array([r[key] for r in rs], np.float64)
+    arrays["gathered_poses"] = np.asarray(all_poses, np.float64)
+    if pairs is not None:
+        first_row = len(rs) - len(pairs)
+        per_scan = min(DUMP_PAIRS_PER_SCAN, (48 << 20) // (48 * max(1, len(pairs))))  # 48 B per sampled point, 64 MB in all
+        cols = {k: [] for k in ("pose_row", "local_idx", "paired", "global_idx", "global_xyz", "d2")}
+        for j, (p, n) in enumerate(zip(pairs, scan_sizes)):
+            m = min(n, per_scan)
+            pts = np.sort(np.random.default_rng(7919 + j).choice(n, m, replace=False)) if m < n else np.arange(n)
+            li = np.asarray(p["local_idx"], np.int64)
+            order = np.argsort(li, kind="stable")  # (ascending already; the first pairing of a point if it has several)
+            pos = np.minimum(np.searchsorted(li[order], pts), max(0, len(li) - 1))
+            hit = (li[order][pos] == pts) if len(li) else np.zeros(m, bool)
+            at = order[pos] if len(li) else np.zeros(m, np.int64)
+            gi = np.where(hit, np.asarray(p["global_idx"], np.float64)[at] if len(li) else 0.0, np.nan)
+            gx = np.where(hit[:, None], np.asarray(p["global_xyz"], np.float32)[at] if len(li) else 0.0, np.nan).astype(np.float32)
+            d2 = np.where(hit, np.asarray(p["d2"], np.float32)[at] if len(li) else 0.0, np.nan).astype(np.float32)
+            cols["pose_row"].append(np.full(m, first_row + j, np.float64))
+            cols["local_idx"].append(pts.astype(np.float64))
+            cols["paired"].append(hit.astype(np.float64))
+            cols["global_idx"].append(gi)
+            cols["global_xyz"].append(gx.reshape(-1, 3))
+            cols["d2"].append(d2)
+        for k, v in cols.items():
+            arrays["pairs_" + k] = np.concatenate(v)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def relaunch_under_torchrun(n):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -579,6 +641,9 @@ def main():
     ap.add_argument("--no-lpt", action="store_true", help="skip the lpt_curve extra (11 sequences with KITTI's length ratios through molahip-lo-cli --devices)")
     ap.add_argument("--lpt-scale", type=float, default=20.0, help="lpt_curve: KITTI sequence lengths divided by this")
     ap.add_argument("--lpt-devices", default=None, help="lpt_curve: device list (default 0..N-1; e.g. 0,0,0,0 exercises four slots on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (poses, covariances, counters, a fixed "
+                         "sample of the final pairings) as DIR/<name>.npy; the inputs depend on the arguments alone")
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, gather their ranks over gloo and print n_gpus (no GPU needed: tests the self-launch)")
     args = ap.parse_args()
@@ -698,10 +763,13 @@ def main():
                     self.worker_error = e
                 self.done.put(item)
 
+        def call_key(self, buf, cur, sset):
+            return (buf, cur if self.dl else -1, sset)
+
         def call_for(self, buf, cur, sset):
             """The marshalled arguments of a batch (capi.BatchCall): built once per (buffer, pairs block, scan set), reused every
             step -- the per-batch host work is the C call."""
-            key = (buf, cur if self.dl else -1, sset)
+            key = self.call_key(buf, cur, sset)
             if key not in self.calls:
                 if self.dl:
                     self.calls[key] = capi.BatchCall(self.maps, self.scans[buf], self.guesses[sset], params,
@@ -717,9 +785,7 @@ def main():
                 r = self.last_call.run()
                 self.k += 1
                 return r[0].match_kernel_ms, int(r[0].n_match_launches)
-            cur = self.k & 1
-            buf = cur if self.up else 0
-            sset = self.k % self.K
+            buf, cur, sset = batch_slot(self.k, self.K, self.up)
             pending = False
             if self.up:  # next batch's scans: asynchronous copies on the OTHER buffer set's stream
                 nxt = (1 - cur, (self.k + 1) % self.K)
@@ -784,6 +850,13 @@ def main():
             cur = (self.k - 1) & 1
             return capi.unpack_pairs_block(self.blocks[cur].numpy(), self.sizes[self.last_set()], results)
 
+        def last_step_results(self):
+            """Result dicts of every batch of the last step, in batch order (one list of S per batch).  The K batches of a
+            step read K different scan sets, so their marshalled calls are distinct and none was overwritten since."""
+            keys = [self.call_key(*batch_slot(b, self.K, self.up)) for b in range(self.k - self.K, self.k)]
+            assert len(set(keys)) == self.K and all(k in self.calls for k in keys), keys
+            return [self.calls[k].results() for k in keys]
+
         def close(self):
             self.sync()
             if self.thread is not None:
@@ -800,6 +873,7 @@ def main():
     main_run = Setup(ws, sets, io)
     KS = main_run.K  # batches (= scan sets) per step
     dt, match_ms, match_launches, last = main_run.run(args.steps, args.warmup)
+    step_results = main_run.last_step_results() if args.dump_outputs and rank == 0 else None
     # outside the timed region: the same kernel with nothing else on the device (S = 1), what rocprofv3 --stats of a
     # one-stream run reports per launch
     iso_ms, iso_launches = 0.0, 0
@@ -818,6 +892,9 @@ def main():
     guesses = main_run.guesses[last_set]     # the inputs of the LAST timed batch: what `last` / `pairs_last` belong to
     last_scans = [st[last_set][0] for st in main_run.job_sets]
     guess0 = main_run.guesses[0][0]
+    if step_results is not None:
+        dump_outputs(args.dump_outputs, step_results, main_run.last_pairs(last) if main_run.dl else None,
+                     main_run.sizes[main_run.last_set()], all_poses)
     main_run.close()
 
     shared = None

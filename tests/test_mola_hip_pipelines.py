@@ -12,8 +12,10 @@ nothing here runs mola-lidar-odometry-cli -- the checks are the ones that failed
   * the MOLA_HIP_* switches the adapter reads (molahip_host/plugin_switches.h, compiled into this repository's host
     layer) parse as documented.
 
-/root/reference exists in the authoring container only; on a box without it the pre-generated files under
-pipelines/generated/ (built by __graft_entry__.build(), git-ignored, shipped with the snapshot) are checked instead.
+The reference's pipeline files are its own sources and are not copied into this repository: the tests that diff against
+them or read what the generator made of them run where those files are installed (make_mola_hip.find_reference_dir(),
+e.g. $MOLA_LO_PIPELINES_DIR) or where build() has already written pipelines/generated/ (git-ignored, so never in a clean
+checkout), and skip elsewhere.
 """
 import difflib
 import importlib.util
@@ -278,9 +280,7 @@ def test_docs_and_tools_point_at_the_generated_files():
     assert "lidar3d-default-mola-hip.yaml" in pin and "make_mola_hip" in pin
 
 
-def test_build_generates_the_pipelines_when_the_reference_is_present():
-    if not mk.find_reference_dir():
-        pytest.skip("no reference pipelines on this box")
+def test_build_runs_the_pipeline_generator_into_an_ignored_directory():
     entry = open(os.path.join(ROOT, "__graft_entry__.py")).read()
     assert "make_mola_hip" in entry
     assert "pipelines/generated/" in open(os.path.join(ROOT, ".gitignore")).read()

@@ -114,11 +114,9 @@ def test_tum_roundtrip_and_metrics(tmp_path):
     assert trajectory.ate_rmse(moved, poses, "se3") < 1e-6 < trajectory.ate_rmse(moved, poses, "none")
     ia, ib = trajectory.associate(stamps[::2] + 0.001, stamps)
     np.testing.assert_array_equal(ib, np.arange(0, n, 2))
-    # the reference's own GT fragment parses (23 poses, starts at identity)
-    ref = "/root/reference/test/rslidar_fragment_gt.tum"
-    if os.path.exists(ref):
-        s, p = trajectory.read_tum(ref)
-        assert len(s) == len(p) > 10 and np.allclose(p[0], np.eye(4), atol=1e-6)
+    # the reference's own GT fragment (stored under tests/golden/) parses (23 poses, starts at identity)
+    s, p = trajectory.read_tum(os.path.join(ROOT, "tests", "golden", "rslidar_fragment_gt.tum"))
+    assert len(s) == len(p) > 10 and np.allclose(p[0], np.eye(4), atol=1e-6)
 
 
 def test_oracle_driver_tracks_synthetic_drive(drive):
