@@ -223,11 +223,10 @@ __global__ __launch_bounds__(kBlock, MH_QUAD_WAVES) void k_match_wave_sparse_b(c
   const BatchJob& j = jobs[blockIdx.y];
   k_match_wave_body<false, false>(j.st, j.sx, j.sy, j.sz, j.perm, j.tile_start, j.n_tiles, j.map, j.pair_q, j.pair_gidx MH_WT_NULL);
 }
-// both launches of the wave matcher on stream s (LDS staging of the dense tiles: MH_WAVE_LDS=1)
-static inline bool wave_lds_env() { static const bool v = getenv("MH_WAVE_LDS") != nullptr; return v; }
-#define MH_LAUNCH_WAVE(S, ST, SC, MV, PQ, PG, WT)                                                                          \
+// both launches of the wave matcher on stream s (LDS staging of the dense tiles: MH_WAVE_LDS=1, Switches::wave_lds)
+#define MH_LAUNCH_WAVE(LDS, S, ST, SC, MV, PQ, PG, WT)                                                                     \
   do {                                                                                                                     \
-    if (wave_lds_env())                                                                                                    \
+    if (LDS)                                                                                                               \
       hipLaunchKernelGGL(k_match_wave_dense<true>, dim3((SC)->n_tiles), dim3(64), 0, S, ST, (SC)->sx, (SC)->sy, (SC)->sz,   \
                          (SC)->perm, (SC)->tile_start, (SC)->n_tiles, MV, PQ, PG WT);                                      \
     else                                                                                                                   \

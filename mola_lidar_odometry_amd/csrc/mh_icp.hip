@@ -26,7 +26,7 @@
 //   k_solve          one workgroup: ordered sum of partials, prior factor, LDL^T, T <- T(+)exp(delta),
 //                    inner/outer loop bookkeeping, stall + hook tests, termination flag, next threshold
 //   k_accum, k_solve (inner Gauss-Newton steps >= 1 on the SAME pairings)
-// Smaller layers take shorter chains (chosen by size in AlignJob::start / enqueue_chunk):
+// Smaller layers take shorter chains (chosen by size in plan_alignment, run by AlignJob):
 //   <= 32 k points   k_match16: a DPP row (16 lanes) per point; up to 12 k points it also accumulates the first step
 //   <= 8 k points    k_step16 x max_inner: search + sums per launch, the Gauss-Newton step carried into the next launch
 //   <= 2560 points   k_icp16: the whole loop in ONE launch (single alignments); lock-step batches of point layers up to 4096
@@ -203,10 +203,8 @@ mh_status compact_pairs(mh_ctx* ctx, size_t n, const mh_pairs_out* out, int32_t 
   return MH_OK;
 }
 
-// One alignment in flight on one context: enqueue / poll state machine shared by mh_icp_align and
-// mh_icp_align_batch.
 std::atomic<unsigned long long> g_loop16_runs{0}, g_loop16_fallbacks{0};  // one-launch loops started / abandoned for the chain (mh_debug_loop_stats)
-uint32_t loop_cu_limit(int device) {
+uint32_t loop_cu_limit(const Switches& sw, int device) {
   static uint32_t cap[64] = {0};
   uint32_t& cu = cap[(unsigned)device % 64u];
   if (!cu) {
@@ -214,8 +212,7 @@ uint32_t loop_cu_limit(int device) {
     if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || v <= 0) v = 64;
     cu = (uint32_t)v;
   }
-  const char* e = getenv("MH_LOOP16_CUS");  // (test knob: the admission limit)
-  return e ? (uint32_t)std::max(0, atoi(e)) : cu;
+  return sw.loop16_cus >= 0 ? (uint32_t)sw.loop16_cus : cu;  // (MH_LOOP16_CUS: test knob of the admission limit)
 }
 // the loops of `callers` alignments of `ng` groups each fit 70 % of the device's CUs side by side (one group per workgroup; shared
 // loops whose workgroups take 2 or 4 groups each were measured for 6 / 8 / 16 callers and lost to lock-step batches: 3100-3550 /
@@ -225,24 +222,166 @@ uint32_t loop_cu_limit(int device) {
 constexpr uint32_t kLoopUnitsPerCu = 2;
 // MH_LOOPW = all | solo | batch | none: where k_icpw / k_icpw_b (plan / scan search, 128 points per workgroup) replace k_icp16 /
 // k_icp16_b (a DPP row per point) on point layers.  (MH_NO_LOOPW=1 = none.)
-bool loop_wave_enabled(bool batch = false) {
-  if (getenv("MH_NO_LOOPW") != nullptr) return false;
-  const char* e = getenv("MH_LOOPW");
-  if (!e) e = MH_LOOPW_DEFAULT;
-  return e[0] == 'a' || (batch ? e[0] == 'b' : e[0] == 's');
+bool loop_wave_enabled(const Switches& sw, bool batch) {
+  return !sw.no_loopw && (sw.loopw == 'a' || sw.loopw == (batch ? 'b' : 's'));
 }
-// what the loop of a layer of `ng` groups holds: with_planes -> k_icp16<true> (the plane matcher rides in the row search)
-uint32_t loop_units(uint32_t ng, bool with_planes) {
-  return (with_planes || !loop_wave_enabled()) ? kLoopUnitsPerCu * ng : (ng + kLwGroups - 1) / kLwGroups;
-}
-bool loops_fit(int device, uint32_t units, uint32_t callers) {
+bool loops_fit(const Switches& sw, int device, uint32_t units, uint32_t callers) {
   // (and never more than MH_SOLO_MAX_CALLERS, 4: beyond, every measurement so far says lock-step batches -- the loops' own
   //  streams share four hardware queues with everything else the callers issue, and a loop holds its queue for 0.5 ms)
-  const char* e = getenv("MH_SOLO_MAX_CALLERS");
-  const uint32_t cap = e ? (uint32_t)std::max(1, atoi(e)) : 4u;
-  return callers <= 1 || (callers <= cap && (uint64_t)callers * units * 10u <= (uint64_t)loop_cu_limit(device) * kLoopUnitsPerCu * 7u);
+  return callers <= 1 || (callers <= sw.solo_max_callers &&
+                          (uint64_t)callers * units * 10u <= (uint64_t)loop_cu_limit(sw, device) * kLoopUnitsPerCu * 7u);
 }
 
+// Admission of one-launch loops: the workgroups of all loops running on a device must be resident together (a loop's
+// workgroups wait for each other), so their sum stays below the CU count less a reserve for what else is running; kernels
+// that merely pass through (other sequences' large layers, map updates) delay a loop's start, they cannot block it.
+std::atomic<uint32_t>& loop_count(int device) {
+  static std::atomic<uint32_t> c[64];
+  return c[(unsigned)device % 64u];
+}
+// arm > 0: a loop was abandoned; arm < 0: a loop ran to its end; 0: true while the hold-off lasts (counts down).  The hold-off
+// doubles with every abandonment in a row (200, 400, ... 12 800 alignments): on a device shared with other processes a loop's
+// workgroups may never run together, and every attempt costs its 20 ms limit (MH_NO_LOOP16=1 is the switch for such
+// a deployment).
+bool loop_holdoff(int device, int arm) {
+  static std::atomic<int> left[64], streak[64];
+  std::atomic<int>& v = left[(unsigned)device % 64u];
+  std::atomic<int>& st = streak[(unsigned)device % 64u];
+  if (arm > 0) {
+    const int k = st.fetch_add(1);
+    v.store(200 << (k < 6 ? k : 6));
+    return true;
+  }
+  if (arm < 0) {
+    st.store(0);
+    return false;
+  }
+  int cur = v.load();
+  while (cur > 0)
+    if (v.compare_exchange_weak(cur, cur - 1)) return true;
+  return false;
+}
+// The units one or several loops hold of a device's admission count, given back by release() or, whatever way the call that
+// took them ends, by the destructor.
+class LoopAdmission {
+ public:
+  LoopAdmission() = default;
+  LoopAdmission(LoopAdmission&& o) noexcept : device_(o.device_), units_(o.units_) { o.units_ = 0; }  // (move-only)
+  ~LoopAdmission() { release(); }
+  // `units` half CUs of `device` (an empty guard only): true once they are held
+  bool admit(const Switches& sw, int device, uint32_t units) {
+    const uint32_t limit = loop_cu_limit(sw, device) * kLoopUnitsPerCu;
+    if (units > limit) return false;
+    // A loop that does not fit now waits for the running ones (each takes a fraction of a millisecond) rather than fall back to
+    // the chain, whose forty-odd launches would queue behind the same loops: eight sequences of the default pipeline keep five
+    // loops on the device at any time.  MH_LOOP16_WAIT_US (2000): how long before the chain is taken after all.
+    std::atomic<uint32_t>& c = loop_count(device);
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t spins = 0;; spins++) {
+      uint32_t cur = c.load();
+      while (cur + units <= limit)
+        if (c.compare_exchange_weak(cur, cur + units)) {
+          device_ = device;
+          units_ = units;
+          return true;
+        }
+      if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() >= sw.loop16_wait_us)
+        return false;
+      if (spins < 64) __builtin_ia32_pause();
+      else std::this_thread::yield();
+    }
+  }
+  void release() {
+    if (units_) loop_count(device_).fetch_sub(units_);
+    units_ = 0;
+  }
+ private:
+  int device_ = 0;
+  uint32_t units_ = 0;
+};
+
+// The correspondence kernel of the fused loop, MH_MATCH=<letter> (all exact, bit-identical pairings).  The numbers go into the
+// graph-cache key and the debug prints.
+enum class Matcher : int {
+  Point = 0,    // "p": one lane per point, branch-and-bound, fused accumulation                            -> k_match<true, 1>
+  Literal = 1,  // "x": one lane per point, the literal 27-voxel scan of the reference (A/B baseline)        -> k_match<true, 0>
+  Quad = 4,     // "q": a DPP quad per scan point, merged candidate scans (the default of rounds 1-4)        -> k_match4 + k_accum
+  Row = 5,      // "s": a DPP row (16 lanes) per point (default up to kRowMaxPoints)                         -> k_match16 + k_accum
+  Tile = 6,     // "t": a workgroup per tile of the spatially sorted scan, map records staged in LDS        -> k_match_tile + k_accum
+  Wave = 7,     // "w": a wave per tile of 64 sorted points, wave-uniform candidates through the scalar path -> k_match_wave + k_accum
+  Ordered = 8,  // "o": "q" over the scan in search order (the sort of "t" / "w", no tiles)                   -> k_match4 + k_accum
+  Flat = 9,     // "f": plan / scan (mh_nn_flat.h; default above kRowMaxPoints): a wave per 64 points, per-point / per-voxel /
+                //      per-record work each on all 64 lanes                                                  -> k_match_flat + k_accum
+};  // ("t", "w", "o": mh_dev_variants.h, the development library only)
+// the one-lane matchers sum the first Gauss-Newton step themselves; every other one leaves it to k_accum (or the row kernel)
+inline bool one_lane(Matcher m) { return m == Matcher::Point || m == Matcher::Literal; }
+// the matchers that search the scan in its sorted order (mh_tile.hip)
+inline bool sorted_scan(Matcher m) { return m == Matcher::Tile || m == Matcher::Wave || m == Matcher::Ordered; }
+
+enum class Loop { None, Icp16, Icpw };  // one-launch loop: k_icp16 (a DPP row per point) | k_icpw (plan / scan search)
+struct AlignPlan {
+  Matcher matcher = Matcher::Row;
+  char dev_matcher = 0;     // MH_MATCH names a matcher of the development library, this one lacks it (start() fails)
+  bool fused16 = false;     // the row kernel accumulates the first Gauss-Newton step itself (layers above the one-workgroup size)
+  bool step_chain = false;  // k_step16 launches (row-kernel layers up to kStepMaxPoints)
+  bool streaming = false;   // run_streaming(): iterations enqueued one by one behind the device's published progress
+  Loop loop = Loop::None;   // the one-launch loop that takes the streaming chain's place if the hold-off and admission allow ...
+  uint32_t loop_units = 0;  // ... and the half CUs it holds meanwhile (0: the layer is too large for it)
+};
+
+// The path of one alignment, from the switches and its shape alone (no HIP call, no admission): AlignJob::start runs it,
+// mh_icp_align_prefers_solo promises it and a batch groups its jobs by it.  `map` null: the map-dependent downgrades are left out
+// (they never touch the row matcher).  `auto_control`: a single alignment with automatic polling on a context with a progress word.
+AlignPlan plan_alignment(const Switches& sw, size_t n, bool pl, uint32_t matched_points, const mh_map* map, bool prof,
+                         bool auto_control) {
+  AlignPlan a;
+  a.matcher = n <= kRowMaxPoints ? Matcher::Row : Matcher::Flat;
+  switch (sw.match) {
+    case 'f': a.matcher = Matcher::Flat; break;
+    case 'q': a.matcher = Matcher::Quad; break;
+    case 's': a.matcher = Matcher::Row; break;
+    case 'p': a.matcher = Matcher::Point; break;
+    case 'x': a.matcher = Matcher::Literal; break;
+#ifdef MH_DEV_VARIANTS
+    case 't': a.matcher = Matcher::Tile; break;
+    case 'w': a.matcher = Matcher::Wave; break;
+    case 'o': a.matcher = Matcher::Ordered; break;
+#else
+    case 't': case 'w': case 'o': a.dev_matcher = sw.match; a.matcher = Matcher::Flat; break;
+#endif
+  }
+  if (map && a.matcher == Matcher::Literal && map->view(sw).ndt) a.matcher = Matcher::Point;  // "x" walks contiguous z-runs; NDT maps interleave statistics records
+  // MH_MATCHED_POINTS_SKIP (U12): the point matcher has to know the plane matcher's verdict for the same point -- the row
+  // kernel runs both in one launch (k_match16<true>), whatever the layer's size
+  if (pl && matched_points == MH_MATCHED_POINTS_SKIP) a.matcher = Matcher::Row;
+  if (map && a.matcher == Matcher::Flat && map->pts.bytes / sizeof(float4) >= kFlatMaxRecords) a.matcher = Matcher::Quad;  // (the chunk word holds 30 bits of record index)
+  // (measured per iteration, fused vs k_accum: 31.0 vs 33.8 us at 4 k points, 33.2 vs 35.0 at 8 k, equal at 16 k,
+  //  45.9 vs 41.8 at 32 k -- one partial row per 16 points makes the solve's reduction the longer pole there)
+  a.fused16 = a.matcher == Matcher::Row && !pl && n <= kFused16MaxPoints && !sw.no_fuse16;
+  // profiled jobs time the match kernel alone: they, and MH_NO_STEP_CHAIN=1, take the chains with a match kernel of its own
+  a.step_chain = a.matcher == Matcher::Row && n <= kStepMaxPoints && !prof && !sw.no_step_chain;
+  // Streaming loop control (single alignments with automatic polling): instead of a predicted chunk of iterations whose
+  // unused tail idles on the stream (27.8 iterations' worth of kernels enqueued for 21 executed on the city drive, plus
+  // 0.64 extra host round trips per scan), the host follows the progress word the solve kernels publish and keeps
+  // kStreamLead (2) iterations queued ahead.  Not for lock-step batches, profiled jobs, or when switched off (MH_NO_STREAM=1).
+  a.streaming = auto_control && !prof && !sw.no_stream;
+  // k_icp16: where the streaming chain would run and the layer has at most kLoopMaxGroups groups (k_icpw: kLwMaxGroups)
+  if (a.streaming && a.step_chain && !sw.no_loop16) {
+    const bool wave = !pl && loop_wave_enabled(sw, false);
+    const uint32_t ng = (uint32_t)((n + kStepPoints - 1) / kStepPoints);
+    a.loop = wave ? Loop::Icpw : Loop::Icp16;
+    if (ng <= (wave ? kLwMaxGroups : kLoopMaxGroups)) a.loop_units = wave ? (ng + kLwGroups - 1) / kLwGroups : kLoopUnitsPerCu * ng;
+  }
+  return a;
+}
+
+// Loop control constants (MH_STREAM_LEAD, MH_CHUNK_MARGIN and MH_CHUNK_NEXT were their A/B switches)
+constexpr uint32_t kStreamLead = 2;   // iterations a streaming alignment keeps queued ahead of the device's published one
+constexpr uint32_t kChunkMargin = 2;  // iterations the first chunk adds to the expected count
+constexpr uint32_t kChunkNext = 6;    // iterations of the chunks after the first (automatic polling)
+
+// One alignment in flight on one context: enqueue / poll state machine shared by mh_icp_align and
+// mh_icp_align_batch.
 struct AlignJob {
   const mh_map* map = nullptr;
   const mh_scan* scan = nullptr;
@@ -259,24 +398,23 @@ struct AlignJob {
   // 0 / 1 = the ping-pong pair) and the half of the partials it reads
   uint32_t step_src = 2, step_ppar = 0;
   bool auto_chunk = false;
-  bool fused16 = false;  // row kernel accumulates the first Gauss-Newton step itself (layers above the one-workgroup size)
   bool defer_upload = false;   // batches: the pinned mirrors are filled, the copies are issued by the batch (staged) or flush()
   size_t nsched_pending = 0;
   size_t inline_sched = 0;  // doubles of the schedules that ride behind the parameter block (single alignments; 0: their own copy)
-  int variant = 0;
+  const Switches* sw = nullptr;  // the snapshot of the entry point that runs this job
+  AlignPlan plan{};
   bool finished = false, trivial = false;
   bool prof = false;  // time this job's match kernels with events (then it cannot use the graph path)
   bool pl = false;    // Matcher_Point2Plane runs before the point matcher (lidar3d-ndt.yaml:195-210)
   bool streaming = false;  // run_streaming(): iterations are enqueued one by one behind the device's published progress
   bool skip_tail = false;  // ... and the covariance kernels + state read-back only once the loop has ended
-  bool loop16 = false;         // run_loop16(): the whole loop of a small layer in ONE launch (k_icp16 / k_icpw)
-  bool loopw = false;          // ... as k_icpw (plan / scan search, 128 points per workgroup; needs the map's sub-voxel index)
+  bool loop16 = false;         // run_loop16(): the whole loop of a small layer in ONE launch (plan.loop: k_icp16 / k_icpw)
   bool forbid_loop16 = false;  // ... not for this job: the second attempt after a loop whose workgroups gave up
-  uint32_t loop_wgs = 0;       // workgroups this job holds of the device's admission count while its loop runs
+  LoopAdmission loop_adm;      // what this job holds of the device's admission count while its loop runs
 
-  mh_status start(const mh_map* m, const mh_scan* sc, const mh_icp_params* prm, const double* T0, const mh_prior* prior,
-                  mh_icp_result* r, mh_icp_iter* tr, size_t batch_index = 0) {
-    map = m; scan = sc; ctx = sc->ctx; p = prm; res = r; trace = tr;
+  mh_status start(const Switches& switches, const mh_map* m, const mh_scan* sc, const mh_icp_params* prm, const double* T0,
+                  const mh_prior* prior, mh_icp_result* r, mh_icp_iter* tr, size_t batch_index = 0) {
+    sw = &switches; map = m; scan = sc; ctx = sc->ctx; p = prm; res = r; trace = tr;
     prof = prm->profile == 1 || (prm->profile == 2 && batch_index == 0);
     pl = prm->pt2pl_threshold != nullptr;
     memset(res, 0, sizeof(*res));
@@ -296,7 +434,7 @@ struct AlignJob {
     MH_TRY(map_ready_on(map, s));  // a key-frame update still running on the map's side stream (mh_map_insert)
     const size_t mi = p->max_iterations;
     if (pl) {
-      if (!map->view().ndt)
+      if (!map->view(*sw).ndt)
         return fail(MH_ERR_INVALID_ARGUMENT, "pt2pl_threshold given but the map carries no NDT statistics "
                                              "(build it with ndt_max_eigen_ratio > 0)");
       MH_TRY(ensure_pl_buffers(ctx, scan->n));
@@ -374,96 +512,48 @@ struct AlignJob {
     sk.gn_trace = nullptr;
     sk.cov_hx = p->cov_findif_xyz;
     sk.cov_ha = p->cov_findif_ang;
-    // Streaming loop control (single alignments with automatic polling): instead of a predicted chunk of iterations whose
-    // unused tail idles on the stream (27.8 iterations' worth of kernels enqueued for 21 executed on the city drive, plus
-    // 0.64 extra host round trips per scan), the host follows the progress word the solve kernels publish and keeps
-    // MH_STREAM_LEAD (2) iterations queued ahead.  Not for lock-step batches (defer_upload), profiled jobs, or when switched
-    // off (MH_NO_STREAM=1).
-    streaming = p->poll_every == 0 && !defer_upload && !prof && ctx->d_progress != nullptr && getenv("MH_NO_STREAM") == nullptr;
+    plan = plan_alignment(*sw, scan->n, pl, p->matched_points, map, prof,
+                          p->poll_every == 0 && !defer_upload && ctx->d_progress != nullptr);
+    if (plan.dev_matcher)
+      return fail(MH_ERR_INVALID_ARGUMENT, "MH_MATCH=%c names a development matcher: build tools/variants/libmolahip_dev.so (tools/build_variants.sh)", plan.dev_matcher);
+    const Matcher mt = plan.matcher;
+    streaming = plan.streaming;
     sk.host_progress = streaming ? ctx->d_progress : nullptr;
     nb = nblk(scan->n);
-    {  // MH_MATCH selects the correspondence kernel of the fused loop (all exact, bit-identical pairings):
-       //   "q"            a DPP quad per scan point, merged candidate scans (the default of rounds 1-4) -> k_match4 + k_accum
-       //   "p"            one lane per point, branch-and-bound, fused accumulation   -> k_match<true, 1>
-       //   "x"            one lane per point, the literal 27-voxel scan of the reference (A/B baseline)
-      //   "s"            a DPP row (16 lanes) per point: what "q" becomes automatically for small layers    -> k_match16 + k_accum
-      //   "t"            a workgroup per tile of the spatially sorted scan, map records staged in LDS      -> k_match_tile + k_accum
-      const char* e = getenv("MH_MATCH");
-      variant = scan->n <= kRowMaxPoints ? 5 : 9;
-      //   "w"            a wave per tile of 64 sorted points, wave-uniform candidates through the scalar path       -> k_match_wave + k_accum
-      //   "o"            "q" over the scan in search order (the sort of "t"/"w", no tiles)                                    -> k_match4 + k_accum
-      //   ("t", "w", "o": mh_dev_variants.h, the development library only)
 #ifdef MH_DEV_VARIANTS
-      if (e && e[0] == 't') variant = 6;
-      if (e && e[0] == 'w') variant = 7;
-      if (e && e[0] == 'o') variant = 8;
-#else
-      if (e && (e[0] == 't' || e[0] == 'w' || e[0] == 'o'))
-        return fail(MH_ERR_INVALID_ARGUMENT, "MH_MATCH=%c names a development matcher: build tools/variants/libmolahip_dev.so (tools/build_variants.sh)", e[0]);
+    if (sorted_scan(mt)) MH_TRY(scan_build_tiles(scan, map->inv_vs, mt == Matcher::Wave ? 64u : 256u));
 #endif
-      if (e && e[0] == 'q') variant = 4;
-      //   "f" (default)  plan / scan (mh_nn_flat.h): a wave per 64 points, per-point / per-voxel / per-record work each on all 64 lanes -> k_match_flat + k_accum
-      if (e && e[0] == 'f') variant = 9;
-      if (e && e[0] == 's') variant = 5;
-      if (e && e[0] == 'p') variant = 0;
-      if (e && e[0] == 'x') variant = 1;
-      if (variant == 1 && map->view().ndt) variant = 0;  // "x" walks contiguous z-runs; NDT maps interleave statistics records
-      // MH_MATCHED_POINTS_SKIP (U12): the point matcher has to know the plane matcher's verdict for the same point -- the row
-      // kernel runs both in one launch (k_match16<true>), whatever the layer's size
-      if (pl && p->matched_points == MH_MATCHED_POINTS_SKIP) variant = 5;
-    }
-    if (variant == 9 && map->pts.bytes / sizeof(float4) >= kFlatMaxRecords) variant = 4;  // (the chunk word holds 30 bits of record index)
-#ifdef MH_DEV_VARIANTS
-    if (variant >= 6 && variant != 9) MH_TRY(scan_build_tiles(scan, map->inv_vs, variant == 7 ? 64u : 256u));
-#endif
-    if (variant == 4 || variant >= 6) {  // nn_search_quad / the plan-scan matcher read the map's sub-voxel index
-      MH_TRY(map_ensure_qidx(map, ctx->stream));
-      if (!map->view().pts_q) return fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (matcher variant %d needs it)", variant);
+    if (mt == Matcher::Quad || mt == Matcher::Flat || sorted_scan(mt)) {  // nn_search_quad / the plan-scan matcher read the map's sub-voxel index
+      MH_TRY(map_ensure_qidx(*sw, map, ctx->stream));
+      if (!map->view(*sw).pts_q) return fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (matcher variant %d needs it)", (int)mt);
     }
     nba = nblk_acc(scan->n);
-    // (measured per iteration, fused vs k_accum: 31.0 vs 33.8 us at 4 k points, 33.2 vs 35.0 at 8 k, equal at 16 k,
-    //  45.9 vs 41.8 at 32 k -- one partial row per 16 points makes the solve's reduction the longer pole there)
-    fused16 = variant == 5 && !pl && scan->n <= kFused16MaxPoints && getenv("MH_NO_FUSE16") == nullptr;
     // who writes the partials of the first Gauss-Newton step: the row kernel (16 points per workgroup), k_accum, or k_match
-    nbm = fused16 ? (uint32_t)((16ull * scan->n + kBlock - 1) / kBlock) : (variant >= 4 ? nba : nb);
+    nbm = plan.fused16 ? (uint32_t)((16ull * scan->n + kBlock - 1) / kBlock) : (one_lane(mt) ? nb : nba);
     MH_TRY(ctx->partials.reserve((size_t)kGenN * (nbm > nb ? nbm : nb) * sizeof(double)));
-    if (variant == 5 && scan->n <= kStepMaxPoints) {  // k_step16: two halves of one column per group of 32 points
+    if (mt == Matcher::Row && scan->n <= kStepMaxPoints) {  // k_step16: two halves of one column per group of 32 points
       const size_t ng = (scan->n + kStepPoints - 1) / kStepPoints;
       MH_TRY(ctx->partials.reserve(2 * (size_t)kStepRowsA * (ng ? ng : 1) * sizeof(double)));
       if (pl) MH_TRY(ctx->partials_b.reserve(2 * (size_t)kStepRowsB * (ng ? ng : 1) * sizeof(double)));
     }
     step_src = 2;
     step_ppar = 0;
-    // k_icp16: where the streaming chain would run (a single alignment under automatic control) and the layer has at most
-    // kLoopMaxGroups groups -- if the workgroups of all loops running on this device still fit its CUs (every workgroup of a
-    // loop has to be resident while it runs); otherwise the chain, bit for bit the same result
-    loop16 = false;
-    // (after a loop had to be abandoned -- somebody else's work kept its workgroups from running together, ~0.1 s lost -- the
-    //  next 200 alignments on the device take the chain before another loop is tried)
-    if (streaming && use_step_chain() && !forbid_loop16 && getenv("MH_NO_LOOP16") == nullptr && !loop_holdoff(ctx->device, 0)) {
-      const uint32_t ng = (uint32_t)((scan->n + kStepPoints - 1) / kStepPoints);
-      loopw = !pl && loop_wave_enabled();
-      if (ng <= (loopw ? kLwMaxGroups : kLoopMaxGroups) && loop_admit(ctx->device, loop_units(ng, pl))) {
-        loop_wgs = loop_units(ng, pl);
-        loop16 = true;
-        streaming = false;
-        sk.host_progress = nullptr;
-        if (loopw) {  // the plan / scan search reads the map's sub-voxel index (built once per map content, on this stream)
-          mh_status qs = map_ensure_qidx(map, ctx->stream);
-          if (qs == MH_OK && !map->view().pts_q) qs = fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (k_icpw needs it)");
-          if (qs != MH_OK) {
-            loop_release();
-            return qs;
-          }
-        }
-        if (ctx->loop_x.bytes < kLoopExchangeBytes) {
-          const mh_status rs = ctx->loop_x.reserve(kLoopExchangeBytes);
-          if (rs != MH_OK) {
-            loop_release();
-            return rs;
-          }
-          (void)hipMemsetAsync(ctx->loop_x.p, 0, kLoopExchangeBytes, s);
-        }
+    // the one-launch loop if the workgroups of all loops running on this device still fit its CUs (every workgroup of a loop
+    // has to be resident while it runs); otherwise the chain, bit for bit the same result.  (After a loop had to be abandoned --
+    // somebody else's work kept its workgroups from running together, ~0.1 s lost -- the next 200 alignments on the device take
+    // the chain before another loop is tried.)
+    loop16 = plan.loop != Loop::None && !forbid_loop16 && !loop_holdoff(ctx->device, 0) && plan.loop_units &&
+             loop_adm.admit(*sw, ctx->device, plan.loop_units);
+    if (loop16) {
+      streaming = false;
+      sk.host_progress = nullptr;
+      if (plan.loop == Loop::Icpw) {  // the plan / scan search reads the map's sub-voxel index (built once per map content, on this stream)
+        MH_TRY(map_ensure_qidx(*sw, map, ctx->stream));
+        if (!map->view(*sw).pts_q) return fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (k_icpw needs it)");
+      }
+      if (ctx->loop_x.bytes < kLoopExchangeBytes) {
+        MH_TRY(ctx->loop_x.reserve(kLoopExchangeBytes));
+        (void)hipMemsetAsync(ctx->loop_x.p, 0, kLoopExchangeBytes, s);
       }
     }
     if (defer_upload) {
@@ -482,8 +572,7 @@ struct AlignJob {
     kind = 0;
     {
       const uint32_t expect = p->expected_iterations ? p->expected_iterations : ctx->predicted_iterations[kind];
-      static const uint32_t margin = getenv("MH_CHUNK_MARGIN") ? (uint32_t)atoi(getenv("MH_CHUNK_MARGIN")) : 2u;
-      chunk = p->poll_every ? p->poll_every : (expect ? (expect + margin > 64 ? 64u : expect + margin) : 10u);
+      chunk = p->poll_every ? p->poll_every : (expect ? (expect + kChunkMargin > 64 ? 64u : expect + kChunkMargin) : 10u);
     }
     polls = 0;
     enqueued = 0;
@@ -515,59 +604,6 @@ struct AlignJob {
     return MH_OK;
   }
 
-  // Admission of one-launch loops: the workgroups of all loops running on a device must be resident together (a loop's
-  // workgroups wait for each other), so their sum stays below the CU count less a reserve for what else is running; kernels
-  // that merely pass through (other sequences' large layers, map updates) delay a loop's start, they cannot block it.
-  static std::atomic<uint32_t>& loop_count(int device) {
-    static std::atomic<uint32_t> c[64];
-    return c[(unsigned)device % 64u];
-  }
-  static bool loop_admit(int device, uint32_t wgs) {  // wgs: in half CUs (loop_units)
-    const uint32_t limit = loop_cu_limit(device) * kLoopUnitsPerCu;
-    if (wgs > limit) return false;
-    // A loop that does not fit now waits for the running ones (each takes a fraction of a millisecond) rather than fall back to
-    // the chain, whose forty-odd launches would queue behind the same loops: eight sequences of the default pipeline keep five
-    // loops on the device at any time.  MH_LOOP16_WAIT_US (2000): how long before the chain is taken after all.
-    static const long wait_us = getenv("MH_LOOP16_WAIT_US") ? atol(getenv("MH_LOOP16_WAIT_US")) : 2000L;
-    std::atomic<uint32_t>& c = loop_count(device);
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spins = 0;; spins++) {
-      uint32_t cur = c.load();
-      while (cur + wgs <= limit)
-        if (c.compare_exchange_weak(cur, cur + wgs)) return true;
-      if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() >= wait_us) return false;
-      if (spins < 64) __builtin_ia32_pause();
-      else std::this_thread::yield();
-    }
-  }
-  // arm > 0: a loop was abandoned; arm < 0: a loop ran to its end; 0: true while the hold-off lasts (counts down).  The hold-off
-  // doubles with every abandonment in a row (200, 400, ... 12 800 alignments): on a device shared with other processes a loop's
-  // workgroups may never run together, and every attempt costs its 20 ms limit (MH_NO_LOOP16=1 is the switch for such
-  // a deployment).
-  static bool loop_holdoff(int device, int arm) {
-    static std::atomic<int> left[64], streak[64];
-    std::atomic<int>& v = left[(unsigned)device % 64u];
-    std::atomic<int>& st = streak[(unsigned)device % 64u];
-    if (arm > 0) {
-      const int k = st.fetch_add(1);
-      v.store(200 << (k < 6 ? k : 6));
-      return true;
-    }
-    if (arm < 0) {
-      st.store(0);
-      return false;
-    }
-    int cur = v.load();
-    while (cur > 0)
-      if (v.compare_exchange_weak(cur, cur - 1)) return true;
-    return false;
-  }
-  void loop_release() {
-    if (loop_wgs) loop_count(ctx->device).fetch_sub(loop_wgs);
-    loop_wgs = 0;
-  }
-  ~AlignJob() { loop_release(); }
-
   // The whole loop in one launch, then the covariance kernels + the state read-back, one event wait.  Leaves `finished`
   // false when the loop did not run to its end (a workgroup gave up waiting for the others): the caller starts over with the
   // launch-by-launch chain.
@@ -577,14 +613,14 @@ struct AlignJob {
     const uint32_t n = (uint32_t)scan->n;
     const uint32_t ngr = (n + kStepPoints - 1) / kStepPoints;
     // (MH_LOOP16_TEST_ABANDON: the loop is cut short as if its workgroups had given up -- the caller's second attempt is what is tested)
-    const uint32_t max_steps = getenv("MH_LOOP16_TEST_ABANDON") ? 1u : p->max_iterations * p->gn.max_inner_iterations + 1u;
+    const uint32_t max_steps = sw->loop16_test_abandon ? 1u : p->max_iterations * p->gn.max_inner_iterations + 1u;
     const uint32_t serial0 = ctx->loop_serial;
     ctx->loop_serial += max_steps + 2u;
     g_loop16_runs.fetch_add(1);
     char* const xa = static_cast<char*>(ctx->loop_x.p);
     char* const xb = xa + 2 * (size_t)kAccN * kLoopRowStride * 16;
-    const MapView mv = map->view();
-    if (loopw)
+    const MapView mv = map->view(*sw);
+    if (plan.loop == Loop::Icpw)
       hipLaunchKernelGGL(k_icpw, dim3((ngr + kLwGroups - 1) / kLwGroups), dim3(kLwThreads), 0, s, ctx->d_state, &ctx->d_params->mk,
                          &ctx->d_params->sk, scan->x, scan->y, scan->z, n, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(),
                          (void*)xa, ngr, serial0, max_steps, p->compute_covariance ? 1u : 0u);
@@ -600,22 +636,16 @@ struct AlignJob {
     skip_tail = false;
     MH_TRY(enqueue_tail(/*cov_prepared=*/true));
     const hipError_t we = mh::wait_event(ctx->ev_poll);
-    loop_release();
+    loop_adm.release();
     MH_HIP(we);
     const IcpDeviceState* h = ctx->h_state;
     if (!h->done || h->handover_timeouts) {
       g_loop16_fallbacks.fetch_add(1);
-      if (getenv("MH_LOOP16_TEST_ABANDON") == nullptr) loop_holdoff(ctx->device, 1);
+      if (!sw->loop16_test_abandon) loop_holdoff(ctx->device, 1);
       return MH_OK;  // (not finished)
     }
     loop_holdoff(ctx->device, -1);
     return poll(true);
-  }
-
-  // row-kernel layers up to kStepMaxPoints: k_step16 launches (profiled jobs time the match kernel alone -- they, and
-  // MH_NO_STEP_CHAIN=1, take the chains with a match kernel of its own)
-  bool use_step_chain() const {
-    return variant == 5 && scan->n <= kStepMaxPoints && !prof && getenv("MH_NO_STEP_CHAIN") == nullptr;
   }
 
   mh_status enqueue_chunk() {
@@ -623,9 +653,10 @@ struct AlignJob {
     MH_TRY(set_device(ctx));
     hipStream_t s = ctx->stream;
     const uint32_t n = (uint32_t)scan->n;
-    const MapView mv = map->view();
+    const MapView mv = map->view(*sw);
+    const Matcher mt = plan.matcher;
 #ifdef MH_DEV_VARIANTS
-    if (variant == 6 || variant == 7) MH_TRY(scan_tiles_ready(scan));  // the launch grid needs the tile count
+    if (mt == Matcher::Tile || mt == Matcher::Wave) MH_TRY(scan_tiles_ready(scan));  // the launch grid needs the tile count
 #endif
     const uint32_t m = (p->max_iterations - enqueued) < chunk ? (p->max_iterations - enqueued) : chunk;
     PoseArg dummy{};
@@ -633,11 +664,11 @@ struct AlignJob {
     const MatchK* dmk = &ctx->d_params->mk;
     const SolveK* dsk = &ctx->d_params->sk;
     // everything a chunk launches, in stream order; used directly (profiling / MH_NO_GRAPH) or under stream capture
-    const bool step_chain = use_step_chain();  // k_step16: every launch over the whole layer, the solve carried into the next launch
+    const bool step_chain = plan.step_chain;  // k_step16: every launch over the whole layer, the solve carried into the next launch
     const uint32_t ngr = n ? (n + kStepPoints - 1) / kStepPoints : 1u;
     const uint32_t nwg = ngr < kStepMaxWorkgroups ? ngr : kStepMaxWorkgroups;
     // (launches whose arguments may be frozen in a captured graph cannot be told their number)
-    const bool counted = prof || streaming || getenv("MH_NO_GRAPH") != nullptr;
+    const bool counted = prof || streaming || sw->no_graph;
     uint32_t chunk_k = 0;  // k_step16 launches of this chunk so far
     auto launch_step = [&](uint32_t close_only) {
       const uint32_t expect = counted ? serial_base + step_launches : chunk_k;  // (replayed: the place in the chunk)
@@ -667,7 +698,7 @@ struct AlignJob {
     };
     auto enqueue_kernels = [&]() -> mh_status {
       double* partb = pl ? ctx->partials_b.as<double>() : nullptr;
-      const bool rows16 = pl && variant == 5;                  // NDT layer handled by the row kernel
+      const bool rows16 = pl && mt == Matcher::Row;              // NDT layer handled by the row kernel
       const uint32_t nB = pl ? (rows16 ? nba : nb) : 0u;       // columns of the point-to-plane partials of the FIRST step
       const uint32_t nBi = pl ? nba : 0u;                      // ... of the inner steps (k_accum_both)
       for (uint32_t j = 0; j < m; j++) {
@@ -675,13 +706,13 @@ struct AlignJob {
           for (uint32_t in = 0; in < p->gn.max_inner_iterations; in++) launch_step(0u);
           continue;
         }
-        const bool both16 = pl && variant == 5;  // small layer: both matchers in one launch (k_match16<true>)
+        const bool both16 = pl && mt == Matcher::Row;  // small layer: both matchers in one launch (k_match16<true>)
         if (pl && !both16)
           hipLaunchKernelGGL(k_match_pl<true>, dim3(nb), dim3(kBlock), 0, s, ctx->d_state, dummy, 0.f, dmk, scan->x, scan->y,
                              scan->z, n, mv, ctx->pl_c.as<float4>(), ctx->pl_n.as<float4>(), partb, nb);
         if (prof) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n], s));
-        if (variant == 5) {
-          if (fused16)
+        if (mt == Matcher::Row) {
+          if (plan.fused16)
             hipLaunchKernelGGL((k_match16<false, true>), dim3(nbm), dim3(kBlock), 0, s, ctx->d_state, dmk, scan->x, scan->y,
                                scan->z, n, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), (float4*)nullptr,
                                (float4*)nullptr, part, nbm);
@@ -698,20 +729,20 @@ struct AlignJob {
             hipLaunchKernelGGL(k_accum_both, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                                ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), ctx->pl_c.as<float4>(),
                                ctx->pl_n.as<float4>(), part, partb, nba);
-          else if (!fused16)
+          else if (!plan.fused16)
             hipLaunchKernelGGL(k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                                ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nbm);
 #ifdef MH_DEV_VARIANTS
-        } else if (variant == 7) {
+        } else if (mt == Matcher::Wave) {
 #ifdef MH_DEBUG_WAVETRACE
-          MH_LAUNCH_WAVE(s, ctx->d_state, scan, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), MH_WT_G);
+          MH_LAUNCH_WAVE(sw->wave_lds, s, ctx->d_state, scan, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), MH_WT_G);
 #else
-          MH_LAUNCH_WAVE(s, ctx->d_state, scan, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), );
+          MH_LAUNCH_WAVE(sw->wave_lds, s, ctx->d_state, scan, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), );
 #endif
           if (prof) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));  // the match kernel alone
           hipLaunchKernelGGL(k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                              ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
-        } else if (variant == 6) {
+        } else if (mt == Matcher::Tile) {
           hipLaunchKernelGGL(k_match_tile, dim3(scan->n_tiles), dim3(kTileThreads), 0, s, ctx->d_state, scan->sx, scan->sy, scan->sz,
                              scan->perm, scan->tile_start, scan->n_tiles, mv, ctx->pair_q.as<float4>(),
                              ctx->pair_gidx.as<uint32_t>()
@@ -723,15 +754,15 @@ struct AlignJob {
           hipLaunchKernelGGL(k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                              ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
 #endif
-        } else if (variant == 9) {
+        } else if (mt == Matcher::Flat) {
           hipLaunchKernelGGL(k_match_flat, dim3(nblk_flat(n)), dim3(kFlatThreads), 0, s, ctx->d_state, scan->x, scan->y, scan->z, n, mv,
                              ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), (const uint32_t*)nullptr);
           if (prof) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));  // the match kernel alone
           hipLaunchKernelGGL(k_accum<true>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                              ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
-        } else if (variant == 4 || variant == 8) {
+        } else if (mt == Matcher::Quad || mt == Matcher::Ordered) {
 #ifdef MH_DEV_VARIANTS
-          const bool ord = variant == 8;  // the scan in search order
+          const bool ord = mt == Matcher::Ordered;  // the scan in search order
 #else
           const bool ord = false;
 #endif
@@ -745,14 +776,14 @@ struct AlignJob {
           if (prof) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));  // the match kernel alone
           hipLaunchKernelGGL(k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                              ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
-        } else if (variant == 1)
+        } else if (mt == Matcher::Literal)
           hipLaunchKernelGGL((k_match<true, 0>), dim3(nb), dim3(kBlock), 0, s, ctx->d_state, dummy, 0.f, 1u, dmk, scan->x,
                              scan->y, scan->z, n, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nbm);
         else
           hipLaunchKernelGGL((k_match<true, 1>), dim3(nb), dim3(kBlock), 0, s, ctx->d_state, dummy, 0.f, 1u, dmk, scan->x,
                              scan->y, scan->z, n, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nbm);
         if (prof) {
-          if (variant < 4) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));
+          if (one_lane(mt)) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));
           prof_n++;
         }
         hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, dsk, part, nbm, nbm,
@@ -763,7 +794,7 @@ struct AlignJob {
                                ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), ctx->pl_c.as<float4>(),
                                ctx->pl_n.as<float4>(), part, partb, nba);
           else
-            hipLaunchKernelGGL(variant == 9 ? k_accum<true> : k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 0u, dmk, scan->x, scan->y, scan->z, n,
+            hipLaunchKernelGGL(mt == Matcher::Flat ? k_accum<true> : k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 0u, dmk, scan->x, scan->y, scan->z, n,
                                ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
           hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, dsk, part, nba, nba,
                              (const double*)partb, nBi, nBi, 0u);
@@ -786,8 +817,7 @@ struct AlignJob {
       MH_HIP(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(IcpDeviceState), hipMemcpyDeviceToHost, s));
       return MH_OK;
     };
-    const bool no_graph = getenv("MH_NO_GRAPH") != nullptr;
-    if (prof || no_graph || streaming) {
+    if (prof || sw->no_graph || streaming) {
       MH_TRY(enqueue_kernels());
       MH_HIP(hipGetLastError());
       if (streaming) {  // (no event per iteration: the progress word is the signal)
@@ -805,19 +835,19 @@ struct AlignJob {
       unsigned long long key[32] = {0};
       uint32_t fb;
       memcpy(&fb, &mv.inv_vs, 4);
-      const unsigned long long kv[] = {n, nb, nbm, (unsigned long long)variant, m, p->gn.max_inner_iterations,
+      const unsigned long long kv[] = {n, nb, nbm, (unsigned long long)mt, m, p->gn.max_inner_iterations,
                                        p->compute_covariance, (unsigned long long)mv.slots, (unsigned long long)mv.pts, mv.mask,
                                        fb, mv.trunc | (mv.ndt << 1) | (mv.no_prev_bound << 2), (unsigned long long)scan->x, (unsigned long long)scan->y,
                                        (unsigned long long)scan->z, (unsigned long long)ctx->pair_q.p,
                                        (unsigned long long)ctx->pair_gidx.p, (unsigned long long)part,
                                        (unsigned long long)ctx->d_state, (unsigned long long)ctx->d_params,
                                        (unsigned long long)ctx->h_state,
-                                       (pl ? 2ull : 1ull) | (fused16 ? 8ull : 0ull) | (step_chain ? 16ull : 0ull),
+                                       (pl ? 2ull : 1ull) | (plan.fused16 ? 8ull : 0ull) | (step_chain ? 16ull : 0ull),
                                        (unsigned long long)(pl ? ctx->pl_c.p : nullptr),
                                        (unsigned long long)(pl ? ctx->pl_n.p : nullptr),
                                        (unsigned long long)(pl ? ctx->partials_b.p : nullptr),
-                                       variant >= 6 && variant != 9 ? (unsigned long long)scan->sx : (unsigned long long)variant,
-                                       variant >= 6 && variant != 9 ? (unsigned long long)scan->n_tiles : 0ull,
+                                       sorted_scan(mt) ? (unsigned long long)scan->sx : (unsigned long long)mt,
+                                       sorted_scan(mt) ? (unsigned long long)scan->n_tiles : 0ull,
                                        (unsigned long long)mv.pts_q};  // (a word each: no XOR folding)
       static_assert(sizeof(kv) <= sizeof(key), "graph key too small");
       memcpy(key, kv, sizeof(kv));
@@ -871,8 +901,7 @@ struct AlignJob {
   // ahead of the iteration the device has published; once it publishes "done" the covariance kernels and the state
   // read-back follow and ONE event wait ends the call.
   mh_status run_streaming() {
-    static const uint32_t lead0 = getenv("MH_STREAM_LEAD") ? (uint32_t)std::max(1, atoi(getenv("MH_STREAM_LEAD"))) : 2u;
-    const uint32_t lead = lead0 + (use_step_chain() ? 1u : 0u);  // (k_step16 publishes an iteration's end from the NEXT launch)
+    const uint32_t lead = kStreamLead + (plan.step_chain ? 1u : 0u);  // (k_step16 publishes an iteration's end from the NEXT launch)
     volatile uint32_t* prog = ctx->h_progress;
     *prog = 0;  // (the previous alignment of this context has been waited for: nothing in flight writes it)
     chunk = 1;
@@ -933,10 +962,7 @@ struct AlignJob {
     if (!already_synced) MH_HIP(mh::wait_event(ctx->ev_poll));
     const IcpDeviceState* h = ctx->h_state;
     if (!h->done && enqueued < p->max_iterations) {
-      if (auto_chunk) {
-        static const uint32_t next = getenv("MH_CHUNK_NEXT") ? (uint32_t)atoi(getenv("MH_CHUNK_NEXT")) : 6u;
-        chunk = next ? next : 6u;
-      }
+      if (auto_chunk) chunk = kChunkNext;
       return MH_OK;
     }
     if (h->handover_timeouts)
@@ -997,22 +1023,17 @@ mh_status check_align_args(const mh_map* map, const mh_scan* scan, const mh_icp_
   return MH_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-mh_status mh_icp_align(const mh_map* map, const mh_scan* scan, const mh_icp_params* params, const double T_guess[12],
-                       const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
-                       int32_t pairs_mem) {
-  MH_TRY(check_align_args(map, scan, params, T_guess, result));
-  MH_REQUIRE(!final_pairs || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
+// mh_icp_align once its arguments are checked
+mh_status align_single(const Switches& sw, const mh_map* map, const mh_scan* scan, const mh_icp_params* params,
+                       const double T_guess[12], const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
+                       const mh_pairs_out* final_pairs, int32_t pairs_mem) {
   AlignJob job;
-  MH_TRY(job.start(map, scan, params, T_guess, prior, result, trace));
+  MH_TRY(job.start(sw, map, scan, params, T_guess, prior, result, trace));
   if (job.loop16 && !job.finished) {
     MH_TRY(job.run_loop16());
     if (!job.finished) {  // the loop's workgroups did not all get to run together: once more, launch by launch
       job.forbid_loop16 = true;
-      MH_TRY(job.start(map, scan, params, T_guess, prior, result, trace));
+      MH_TRY(job.start(sw, map, scan, params, T_guess, prior, result, trace));
     }
   }
   if (job.streaming && !job.finished) MH_TRY(job.run_streaming());
@@ -1030,27 +1051,29 @@ mh_status mh_icp_align(const mh_map* map, const mh_scan* scan, const mh_icp_para
   return MH_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+mh_status mh_icp_align(const mh_map* map, const mh_scan* scan, const mh_icp_params* params, const double T_guess[12],
+                       const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
+                       int32_t pairs_mem) {
+  MH_TRY(check_align_args(map, scan, params, T_guess, result));
+  MH_REQUIRE(!final_pairs || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
+  return align_single(read_switches(), map, scan, params, T_guess, prior, result, trace, final_pairs, pairs_mem);
+}
+
 mh_status mh_icp_align_prefers_solo(const mh_scan* scan, const mh_icp_params* p, uint32_t concurrent_callers, int32_t* yes) {
   MH_REQUIRE(scan && p && yes, "null argument");
-  // what AlignJob::start decides for a single alignment under automatic control: the row matcher's layer sizes (MH_MATCH unset or
-  // "s"; always for MH_MATCHED_POINTS_SKIP), the k_step16 chain's conditions, at most kLoopMaxGroups groups
-  const size_t n = scan->n;
-  const bool pl = p->pt2pl_threshold != nullptr;
-  const char* e = getenv("MH_MATCH");
-  bool row = n <= kRowMaxPoints;
-  if (e && (e[0] == 't' || e[0] == 'w' || e[0] == 'o' || e[0] == 'q' || e[0] == 'f' || e[0] == 'p' || e[0] == 'x')) row = false;
-  if (e && e[0] == 's') row = true;
-  if (pl && p->matched_points == MH_MATCHED_POINTS_SKIP) row = true;
-  const size_t loop_max = (size_t)((!pl && loop_wave_enabled()) ? kLwMaxGroups : kLoopMaxGroups) * kStepPoints;
-  *yes = (n > 0 && p->max_iterations > 0 && row && n <= loop_max && p->poll_every == 0 && p->profile == 0 &&
-          scan->ctx->d_progress != nullptr && getenv("MH_NO_STREAM") == nullptr && getenv("MH_NO_STEP_CHAIN") == nullptr &&
-          getenv("MH_NO_LOOP16") == nullptr)
-             ? 1
-             : 0;
+  // what AlignJob::start decides for a single alignment under automatic control: a one-launch loop ...
+  const Switches sw = read_switches();
+  const AlignPlan a = plan_alignment(sw, scan->n, p->pt2pl_threshold != nullptr, p->matched_points, nullptr, p->profile != 0,
+                                     p->poll_every == 0 && scan->ctx->d_progress != nullptr);
   // ... and the loops of all callers fit the device together: nobody waits for a turn.  (70 % of the CUs: the callers' filters,
   // de-skew and map updates run beside the loops -- five loops of 44 workgroups on 256 CUs measured slower than four, 3780 against
   // 4000-4450 scans/s.)
-  if (*yes && !loops_fit(scan->ctx->device, loop_units((uint32_t)((n + kStepPoints - 1) / kStepPoints), pl), concurrent_callers)) *yes = 0;
+  *yes = (p->max_iterations > 0 && a.loop != Loop::None && a.loop_units &&
+          loops_fit(sw, scan->ctx->device, a.loop_units, concurrent_callers)) ? 1 : 0;
   return MH_OK;
 }
 

@@ -5,22 +5,22 @@ namespace {
 #ifdef MH_DEV_VARIANTS
 // MH_MATCH=t: the matcher-granular entry points run the tile matcher too (the parity tests drive every search kernel
 // through mh_nn_search / mh_nn_search_dense); thr2 = +inf: no threshold
-mh_status launch_tile_search(const mh_map* map, const mh_scan* scan, const double T[12], float thr2, float ang2) {
+mh_status launch_tile_search(const Switches& sw, const mh_map* map, const mh_scan* scan, const double T[12], float thr2, float ang2) {
   mh_ctx* ctx = scan->ctx;
-  const bool wave = tile_points_for_env() == 64u;
+  const bool wave = tile_points(sw) == 64u;
   MH_TRY(scan_build_tiles(scan, map->inv_vs, wave ? 64u : 256u));
   MH_TRY(scan_tiles_ready(scan));
-  MH_TRY(map_ensure_qidx(map, ctx->stream));  // (sparse tiles are searched by quads)
+  MH_TRY(map_ensure_qidx(sw, map, ctx->stream));  // (sparse tiles are searched by quads)
   MH_HIP(mh::wait_stream(ctx->stream));  // the pinned state mirror may still be travelling
   init_state(ctx->h_state, T);
   ctx->h_state->cur_thr2 = thr2;
   ctx->h_state->cur_ang2 = ang2;
   MH_HIP(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(IcpDeviceState), hipMemcpyHostToDevice, ctx->stream));
   if (scan->n_tiles && wave)
-    MH_LAUNCH_WAVE(ctx->stream, ctx->d_state, scan, map->view(), ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), MH_WT_NULL);
+    MH_LAUNCH_WAVE(sw.wave_lds, ctx->stream, ctx->d_state, scan, map->view(sw), ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), MH_WT_NULL);
   else if (scan->n_tiles)
     hipLaunchKernelGGL(k_match_tile, dim3(scan->n_tiles), dim3(kTileThreads), 0, ctx->stream, ctx->d_state, scan->sx, scan->sy,
-                       scan->sz, scan->perm, scan->tile_start, scan->n_tiles, map->view(), ctx->pair_q.as<float4>(),
+                       scan->sz, scan->perm, scan->tile_start, scan->n_tiles, map->view(sw), ctx->pair_q.as<float4>(),
                        ctx->pair_gidx.as<uint32_t>()
 #ifdef MH_DEBUG_WAVETRACE
                        , (unsigned long long*)nullptr
@@ -29,18 +29,16 @@ mh_status launch_tile_search(const mh_map* map, const mh_scan* scan, const doubl
   MH_HIP(hipGetLastError());
   return MH_OK;
 }
-inline bool tile_search_forced() {
-  const char* e = getenv("MH_MATCH");
-  return e && (e[0] == 't' || e[0] == 'w');
-}
+inline bool tile_search_forced(const Switches& sw) { return sw.match == 't' || sw.match == 'w'; }
 #else  // the shipped library: the matcher-granular entry points run k_match<false, 1> whatever MH_MATCH says
-inline bool tile_search_forced() { return false; }
-inline mh_status launch_tile_search(const mh_map*, const mh_scan*, const double*, float, float) { return MH_OK; }
+inline bool tile_search_forced(const Switches&) { return false; }
+inline mh_status launch_tile_search(const Switches&, const mh_map*, const mh_scan*, const double*, float, float) { return MH_OK; }
 #endif
 }  // namespace
 
 mh_status mh_nn_search(const mh_map* map, const mh_scan* scan, const double T[12], double threshold,
                        double threshold_angular_deg, const mh_pairs_out* out, int32_t mem, mh_match_info* info) {
+  const Switches sw = read_switches();
   MH_REQUIRE(map && scan && T, "null argument");
   MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE, "bad mem space");
   MH_REQUIRE(map->ctx->device == scan->ctx->device, "map and scan live on different devices");
@@ -62,11 +60,11 @@ mh_status mh_nn_search(const mh_map* map, const mh_scan* scan, const double T[12
   const double ang = threshold_angular_deg * 3.14159265358979323846 / 180.0;
   mk.ang2 = (float)(ang * ang);
   MH_TRY(upload_params(ctx, mk, sk0));
-  if (tile_search_forced())
-    MH_TRY(launch_tile_search(map, scan, T, (float)(threshold * threshold), mk.ang2));
+  if (tile_search_forced(sw))
+    MH_TRY(launch_tile_search(sw, map, scan, T, (float)(threshold * threshold), mk.ang2));
   else
     hipLaunchKernelGGL((k_match<false, 1>), dim3(nblk(scan->n)), dim3(kBlock), 0, ctx->stream, ctx->d_state, Ta,
-                       (float)(threshold * threshold), 1u, &ctx->d_params->mk, scan->x, scan->y, scan->z, (uint32_t)scan->n, map->view(),
+                       (float)(threshold * threshold), 1u, &ctx->d_params->mk, scan->x, scan->y, scan->z, (uint32_t)scan->n, map->view(sw),
                        ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), (double*)nullptr, 0u);
   MH_HIP(hipGetLastError());
   mh_pairs_out none{};
@@ -86,6 +84,7 @@ mh_status mh_nn_search_k(const mh_map* map, const mh_scan* scan, const double T[
   MH_REQUIRE(pose_ok(T), "non-finite pose");
   MH_REQUIRE((uint64_t)scan->n * pairings_per_point < 0xFFFFFFFFull, "scan size * pairings_per_point does not fit 32 bits");
   if (pairings_per_point == 1) return mh_nn_search(map, scan, T, threshold, threshold_angular_deg, out, mem, info);
+  const Switches sw = read_switches();
   mh_ctx* ctx = scan->ctx;
   MH_TRY(set_device(ctx));
   MH_TRY(map_ready_on(map, ctx->stream));
@@ -101,7 +100,7 @@ mh_status mh_nn_search_k(const mh_map* map, const mh_scan* scan, const double T[
   for (int i = 0; i < 12; i++) Ta.m[i] = T[i];
   const double ang = threshold_angular_deg * 3.14159265358979323846 / 180.0;
   hipLaunchKernelGGL(k_match_kbest, dim3(nblk(scan->n)), dim3(kBlock), 0, ctx->stream, Ta, (float)(threshold * threshold),
-                     (float)(ang * ang), k, scan->x, scan->y, scan->z, (uint32_t)scan->n, map->view(), ctx->pair_q.as<float4>(),
+                     (float)(ang * ang), k, scan->x, scan->y, scan->z, (uint32_t)scan->n, map->view(sw), ctx->pair_q.as<float4>(),
                      ctx->pair_gidx.as<uint32_t>());
   MH_HIP(hipGetLastError());
   mh_pairs_out none{};
@@ -123,6 +122,7 @@ mh_status mh_nn_search_k(const mh_map* map, const mh_scan* scan, const double T[
 
 mh_status mh_nn_search_dense(const mh_map* map, const mh_scan* scan, const double T[12], uint32_t* global_idx, float* gx,
                              float* gy, float* gz, float* d2, int32_t mem) {
+  const Switches sw = read_switches();
   MH_REQUIRE(map && scan && T, "null argument");
   MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE, "bad mem space");
   MH_REQUIRE(map->ctx->device == scan->ctx->device, "map and scan live on different devices");
@@ -140,12 +140,12 @@ mh_status mh_nn_search_dense(const mh_map* map, const mh_scan* scan, const doubl
   SolveK sk0{};
   hipStream_t s = ctx->stream;
   MH_TRY(upload_params(ctx, mk, sk0));
-  if (tile_search_forced())
-    MH_TRY(launch_tile_search(map, scan, T, __builtin_inff(), 0.f));
+  if (tile_search_forced(sw))
+    MH_TRY(launch_tile_search(sw, map, scan, T, __builtin_inff(), 0.f));
   else
     hipLaunchKernelGGL((k_match<false, 1>), dim3(nblk(n)), dim3(kBlock), 0, s, ctx->d_state, Ta, 0.f, 0u,
                        &ctx->d_params->mk, scan->x,
-                       scan->y, scan->z, (uint32_t)n, map->view(), ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(),
+                       scan->y, scan->z, (uint32_t)n, map->view(sw), ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(),
                        (double*)nullptr, 0u);
   uint32_t* o_gi = global_idx;
   float *o_x = gx, *o_y = gy, *o_z = gz, *o_d2 = d2;
@@ -210,13 +210,14 @@ static mh_status compact_pl_pairs(mh_ctx* ctx, size_t n, const mh_pairs_pl_out* 
 
 mh_status mh_nn_search_pt2pl(const mh_map* map, const mh_scan* scan, const double T[12], double distance_threshold,
                              uint32_t mode, const mh_pairs_pl_out* out, int32_t mem, mh_match_info* info) {
+  const Switches sw = read_switches();
   MH_REQUIRE(map && scan && T, "null argument");
   MH_REQUIRE(mode == MH_PT2PL_PLANE_DISTANCE || mode == MH_PT2PL_CENTROID_DISTANCE, "bad pt2pl mode");
   distance_threshold = (mode == MH_PT2PL_CENTROID_DISTANCE ? -1.0 : 1.0) * fabs(distance_threshold);
   MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE, "bad mem space");
   MH_REQUIRE(map->ctx->device == scan->ctx->device, "map and scan live on different devices");
   MH_REQUIRE(pose_ok(T), "non-finite pose");
-  MH_REQUIRE(map->view().ndt, "the map carries no NDT statistics (build it with ndt_max_eigen_ratio > 0)");
+  MH_REQUIRE(map->view(sw).ndt, "the map carries no NDT statistics (build it with ndt_max_eigen_ratio > 0)");
   mh_ctx* ctx = scan->ctx;
   MH_TRY(set_device(ctx));
   MH_TRY(map_ready_on(map, ctx->stream));
@@ -233,7 +234,7 @@ mh_status mh_nn_search_pt2pl(const mh_map* map, const mh_scan* scan, const doubl
   SolveK sk0{};
   MH_TRY(upload_params(ctx, mk, sk0));
   hipLaunchKernelGGL(k_match_pl<false>, dim3(nblk(scan->n)), dim3(kBlock), 0, ctx->stream, ctx->d_state, Ta,
-                     (float)distance_threshold, &ctx->d_params->mk, scan->x, scan->y, scan->z, (uint32_t)scan->n, map->view(),
+                     (float)distance_threshold, &ctx->d_params->mk, scan->x, scan->y, scan->z, (uint32_t)scan->n, map->view(sw),
                      ctx->pl_c.as<float4>(), ctx->pl_n.as<float4>(), (double*)nullptr, 0u);
   MH_HIP(hipGetLastError());
   mh_pairs_pl_out none{};
@@ -245,6 +246,7 @@ mh_status mh_nn_search_pt2pl(const mh_map* map, const mh_scan* scan, const doubl
 
 mh_status mh_nn_search_pt2pl_knn(const mh_map* map, const mh_scan* scan, const double T[12], const mh_pt2pl_knn_params* params,
                                  const mh_pairs_pl_out* out, int32_t mem, mh_match_info* info) {
+  const Switches sw = read_switches();
   MH_REQUIRE(map && scan && T && params, "null argument");
   MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE, "bad mem space");
   MH_REQUIRE(map->ctx->device == scan->ctx->device, "map and scan live on different devices");
@@ -270,7 +272,7 @@ mh_status mh_nn_search_pt2pl_knn(const mh_map* map, const mh_scan* scan, const d
   a.knn = params->knn;
   a.min_pts = params->minimum_plane_points < 3u ? 3u : params->minimum_plane_points;  // (three points span a plane)
   hipLaunchKernelGGL(k_match_pl_knn, dim3(nblk(scan->n)), dim3(kBlock), 0, ctx->stream, Ta, a, scan->x, scan->y, scan->z,
-                     (uint32_t)scan->n, map->view(), ctx->pl_c.as<float4>(), ctx->pl_n.as<float4>());
+                     (uint32_t)scan->n, map->view(sw), ctx->pl_c.as<float4>(), ctx->pl_n.as<float4>());
   MH_HIP(hipGetLastError());
   mh_pairs_pl_out none{};
   uint64_t np = 0;

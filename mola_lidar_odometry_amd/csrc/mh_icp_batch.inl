@@ -16,7 +16,7 @@ void fill_batch_desc(const AlignJob& j, BatchJob& d) {
   d.nb = j.nb;
   d.nba = j.nba;
   d.nbm = j.nbm;
-  d.map = j.map->view();
+  d.map = j.map->view(*j.sw);
   d.pair_q = j.ctx->pair_q.as<float4>();
   d.pair_gidx = j.ctx->pair_gidx.as<uint32_t>();
   d.part = j.ctx->partials.as<double>();
@@ -27,7 +27,7 @@ void fill_batch_desc(const AlignJob& j, BatchJob& d) {
   }
   d.sched_dst = j.ctx->sched.as<uint32_t>();
   d.sched_dwords = (uint32_t)(2 * j.nsched_pending);
-  if (j.variant >= 6 && j.variant != 9) {
+  if (sorted_scan(j.plan.matcher)) {
     d.sx = j.scan->sx; d.sy = j.scan->sy; d.sz = j.scan->sz;
     d.perm = j.scan->perm;
     d.tile_start = j.scan->tile_start;
@@ -127,20 +127,21 @@ mh_status finish_pairs(mh_ctx* lead, hipStream_t s, const PairsPlan& pp, const B
 }
 }  // namespace
 
-static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const mh_scan* const* scans,
+static mh_status align_batch_run(const Switches& sw, size_t n_jobs, const mh_map* const* maps, const mh_scan* const* scans,
                                  const mh_icp_params* params, int32_t params_per_job, const double* T_guesses,
                                  const mh_prior* const* priors, mh_icp_result* results, void* pairs_block, int32_t pairs_mem);
 
 mh_status mh_icp_align_batch(size_t n_jobs, const mh_map* const* maps, const mh_scan* const* scans,
                              const mh_icp_params* params, int32_t params_per_job, const double* T_guesses,
                              const mh_prior* const* priors, mh_icp_result* results, void* pairs_block, int32_t pairs_mem) {
-  const mh_status st = align_batch_run(n_jobs, maps, scans, params, params_per_job, T_guesses, priors, results, pairs_block, pairs_mem);
+  const Switches sw = read_switches();
+  const mh_status st = align_batch_run(sw, n_jobs, maps, scans, params, params_per_job, T_guesses, priors, results, pairs_block, pairs_mem);
   // MH_DEBUG_VERIFY_BATCH=1 (development): every job once more as a single alignment -- a batch has to give the same bits
-  if (st == MH_OK && n_jobs && getenv("MH_DEBUG_VERIFY_BATCH") != nullptr && !pairs_block) {
+  if (st == MH_OK && n_jobs && sw.debug_verify_batch && !pairs_block) {
     for (size_t i = 0; i < n_jobs; i++) {
       mh_icp_result r2;
       const mh_icp_params* q = params_per_job ? &params[i] : params;
-      if (mh_icp_align(maps[i], scans[i], q, T_guesses + 12 * i, priors ? priors[i] : nullptr, &r2, nullptr, nullptr, MH_MEM_HOST) != MH_OK) continue;
+      if (align_single(sw, maps[i], scans[i], q, T_guesses + 12 * i, priors ? priors[i] : nullptr, &r2, nullptr, nullptr, MH_MEM_HOST) != MH_OK) continue;
       if (memcmp(r2.T, results[i].T, sizeof(r2.T)) != 0 || r2.n_iterations != results[i].n_iterations) {
         double md = 0;
         for (int k = 0; k < 12; k++) md = fmax(md, fabs(r2.T[k] - results[i].T[k]));
@@ -151,9 +152,9 @@ mh_status mh_icp_align_batch(size_t n_jobs, const mh_map* const* maps, const mh_
         fprintf(stderr, "\n");
         // which of the two is unstable?  the batch once more, the single once more
         std::vector<mh_icp_result> again(n_jobs);
-        if (align_batch_run(n_jobs, maps, scans, params, params_per_job, T_guesses, priors, again.data(), nullptr, pairs_mem) == MH_OK) {
+        if (align_batch_run(sw, n_jobs, maps, scans, params, params_per_job, T_guesses, priors, again.data(), nullptr, pairs_mem) == MH_OK) {
           mh_icp_result r3;
-          (void)mh_icp_align(maps[i], scans[i], q, T_guesses + 12 * i, priors ? priors[i] : nullptr, &r3, nullptr, nullptr, MH_MEM_HOST);
+          (void)align_single(sw, maps[i], scans[i], q, T_guesses + 12 * i, priors ? priors[i] : nullptr, &r3, nullptr, nullptr, MH_MEM_HOST);
           fprintf(stderr, "[MH_DEBUG_VERIFY_BATCH]    second batch == first batch: %d, second batch == single: %d, second single == first single: %d (iterations %u / %u / %u / %u)\n",
                   memcmp(again[i].T, results[i].T, sizeof(r2.T)) == 0, memcmp(again[i].T, r2.T, sizeof(r2.T)) == 0,
                   memcmp(r3.T, r2.T, sizeof(r2.T)) == 0, results[i].n_iterations, again[i].n_iterations, r2.n_iterations, r3.n_iterations);
@@ -164,7 +165,7 @@ mh_status mh_icp_align_batch(size_t n_jobs, const mh_map* const* maps, const mh_
   return st;
 }
 
-static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const mh_scan* const* scans,
+static mh_status align_batch_run(const Switches& sw, size_t n_jobs, const mh_map* const* maps, const mh_scan* const* scans,
                                  const mh_icp_params* params, int32_t params_per_job, const double* T_guesses,
                                  const mh_prior* const* priors, mh_icp_result* results, void* pairs_block, int32_t pairs_mem) {
   MH_REQUIRE(n_jobs == 0 || (maps && scans && params && T_guesses && results), "null argument");
@@ -179,7 +180,7 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
       MH_REQUIRE(scans[j]->ctx != scans[i]->ctx, "each job of a batch needs its own context");
     MH_REQUIRE(!pairs_block || scans[i]->ctx->device == scans[0]->ctx->device, "a pairs block needs all jobs on one device");
     jobs[i].defer_upload = n_jobs >= 2;  // a lock-step group uploads its jobs' blocks in one staged copy
-    MH_TRY(jobs[i].start(maps[i], scans[i], P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr, &results[i],
+    MH_TRY(jobs[i].start(sw, maps[i], scans[i], P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr, &results[i],
                          nullptr, i));
   }
   mh_ctx* lead0 = scans[0]->ctx;
@@ -195,23 +196,19 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
   // each job keeps its own parameters (iteration budget, schedules, hook check point, prior), state block, termination
   // flag and iteration count.  Jobs whose chain has no lock-step form (or that are alone in their group) take the
   // per-stream path below.
-  enum Kind { K_NONE = 0, K_QUAD, K_TILE, K_WAVE, K_ORD, K_ROWF, K_STEP, K_STEP_PL, K_FLAT };
-  const bool no_lockstep = getenv("MH_NO_LOCKSTEP") != nullptr;
-  const bool batch_prof = !jobs.empty() && jobs[0].prof && !no_lockstep;  // (profile == 2 times job 0's share of a match kernel)
+  // (the kinds of the matcher chains are their matchers' numbers: K_ROWF = the row matcher with the fused first accumulation)
+  enum Kind { K_NONE = -1, K_QUAD = (int)Matcher::Quad, K_ROWF = (int)Matcher::Row, K_TILE = (int)Matcher::Tile,
+              K_WAVE = (int)Matcher::Wave, K_ORD = (int)Matcher::Ordered, K_FLAT = (int)Matcher::Flat, K_STEP = 16, K_STEP_PL };
+  const bool batch_prof = !jobs.empty() && jobs[0].prof && !sw.no_lockstep;  // (profile == 2 times job 0's share of a match kernel)
   auto kind_of = [&](const AlignJob& j) -> int {
-    if (j.finished || no_lockstep || j.trace || j.prof) return K_NONE;
+    if (j.finished || sw.no_lockstep || j.trace || j.prof) return K_NONE;
     // row-kernel layers up to 8 k points: k_step16_b, the chain of a single alignment with the jobs' workgroups side by side -- the
     // same sums in the same order, hence the same bits.  (Round 4 also kept the one-workgroup accumulate-and-solve of round 3 for
     // batches, re-ordered to give those bits: 4 / 8 / 16 sequences 3690 / 4920 / 5770 scans/s against 4092 / 5173 / 5510 this
     // way, NDT pipeline 3966 / 4509 / 3939 against 4780 / 5500 / 5600: removed.)
-    if (j.use_step_chain() && !batch_prof) return j.pl ? K_STEP_PL : K_STEP;
-    if (j.variant == 4 && !j.pl) return K_QUAD;
-    if (j.variant == 9 && !j.pl) return K_FLAT;
-    if (j.variant == 6 && !j.pl) return K_TILE;
-    if (j.variant == 7 && !j.pl) return K_WAVE;
-    if (j.variant == 8 && !j.pl) return K_ORD;
-    if (j.variant == 5 && j.fused16 && !j.pl) return K_ROWF;
-    return K_NONE;
+    if (j.plan.step_chain && !batch_prof) return j.pl ? K_STEP_PL : K_STEP;
+    const Matcher m = j.plan.matcher;
+    return (j.pl || one_lane(m) || (m == Matcher::Row && !j.plan.fused16)) ? K_NONE : (int)m;
   };
   struct Group {
     int kind = K_NONE;
@@ -226,22 +223,12 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
     bool loop_wave = false;  // ... as k_icpw_b (point layers): every job its own workgroups
     uint32_t gx_loopw = 1;   // ... whose launch has this many workgroups per job
     bool loop_now = false;   // k_icp16_b: the group's whole loops in ONE launch (decided below; cleared when a job's workgroups gave up)
-    uint32_t loop_wgs = 0;   // ... and what it holds of the device's admission count meanwhile
+    LoopAdmission loop_adm;  // ... and what it holds of the device's admission count meanwhile
     bool step_chain() const { return kind == K_STEP || kind == K_STEP_PL; }
     bool with_planes() const { return kind == K_STEP_PL; }
   };
   std::vector<Group> groups;
-  struct ReleaseLoops {  // whatever way this call ends, the groups' share of the device's loop admission count is given back
-    std::vector<Group>* gs;
-    ~ReleaseLoops() {
-      for (Group& g : *gs)
-        if (g.loop_wgs && g.lead) {
-          AlignJob::loop_count(g.lead->device).fetch_sub(g.loop_wgs);
-          g.loop_wgs = 0;
-        }
-    }
-  } release_loops{&groups};
-  const bool want_prof = !jobs.empty() && jobs[0].prof && !no_lockstep;  // profile == 2: the share of job 0's group
+  const bool want_prof = !jobs.empty() && jobs[0].prof && !sw.no_lockstep;  // profile == 2: the share of job 0's group
   if (want_prof) jobs[0].prof = false;
   for (size_t i = 0; i < n_jobs; i++) {
     const int k = kind_of(jobs[i]);
@@ -273,8 +260,7 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
   }
   {  // a job alone in its group gains nothing from lock step; MH_LOCKSTEP_GROUPS splits the groups further (measured: two
      // groups of the C2 batch overlap one's match launch with the other's short launches for +3 %; default off)
-    uint32_t split = 1;
-    if (const char* e = getenv("MH_LOCKSTEP_GROUPS")) split = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : 1u;
+    const uint32_t split = sw.lockstep_groups;
     std::vector<Group> kept;
     for (Group& g : groups) {
       if (g.jobs.size() < 2) continue;
@@ -282,16 +268,16 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
       if (parts > g.jobs.size() / 2) parts = (uint32_t)(g.jobs.size() / 2);
       if (parts < 1 || pp.want) parts = 1;  // (the pairs block is compacted by one launch over one group's jobs)
       for (uint32_t part = 0; part < parts; part++) {
-        Group h = g;
-        h.jobs.clear();
-        h.index.clear();
+        Group h;  // (g's shape: nothing else is set yet)
+        h.kind = g.kind; h.inner = g.inner; h.cov = g.cov; h.chunk = g.chunk; h.auto_chunk = g.auto_chunk;
+        h.max_iterations = g.max_iterations;
         for (size_t a = 0; a < g.jobs.size(); a++)
           if (a * parts / g.jobs.size() == part) {
             h.jobs.push_back(g.jobs[a]);
             h.index.push_back(g.index[a]);
           }
         h.lead = h.jobs[0]->ctx;
-        kept.push_back(h);
+        kept.push_back(std::move(h));
       }
     }
     groups.swap(kept);
@@ -344,8 +330,7 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
         if (g.kind == K_TILE) bm = d.n_tiles;
         if (g.kind == K_WAVE) bm = d.n_tiles;
         if (g.step_chain()) {  // all jobs' workgroups resident at once: kStepMaxWorkgroups shared between them
-          static const uint32_t cap_env = getenv("MH_STEP_WGS") ? (uint32_t)std::max(1, atoi(getenv("MH_STEP_WGS"))) : 0u;  // (development)
-          const uint32_t cap = cap_env ? cap_env : (kStepMaxWorkgroups / A ? kStepMaxWorkgroups / A : 1u);
+          const uint32_t cap = kStepMaxWorkgroups / A ? kStepMaxWorkgroups / A : 1u;
           const uint32_t ng = (d.n + kStepPoints - 1) / kStepPoints;
           const uint32_t nw = ng < cap ? ng : cap;
           g.gx_step = nw > g.gx_step ? nw : g.gx_step;
@@ -362,12 +347,11 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
       // Small layers: the whole loops of the group's jobs in ONE launch (k_icp16_b) when every job's layer has at most kLoopMaxGroups
       // groups, a workgroup takes at most kLoopGroupsPerWg of them, and the launch's workgroups are admitted (all resident together,
       // beside the one-launch loops of single alignments running on the device).  MH_NO_LOOP16 / MH_NO_LOOP16_BATCH: the chain.
-      if (g.step_chain() && getenv("MH_NO_LOOP16") == nullptr && getenv("MH_NO_LOOP16_BATCH") == nullptr &&
-          !AlignJob::loop_holdoff(lead->device, 0)) {
+      if (g.step_chain() && !sw.no_loop16 && !sw.no_loop16_batch && !loop_holdoff(lead->device, 0)) {
         bool fits = true;
         // k_icpw_b (point layers): every job its own workgroups of 128 points; k_icp16_b (NDT maps, MH_NO_LOOPW): the jobs share
         // kStepMaxWorkgroups workgroups of 32 points, a workgroup taking several groups
-        g.loop_wave = !g.with_planes() && loop_wave_enabled(true);
+        g.loop_wave = !g.with_planes() && loop_wave_enabled(sw, true);
         uint32_t units = 0, gx_w = 1;
         for (uint32_t a = 0; a < A; a++) {
           const uint32_t ng = (h_desc[a].n + kStepPoints - 1) / kStepPoints;
@@ -382,17 +366,16 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
           }
         }
         if (!g.loop_wave) units = kLoopUnitsPerCu * g.gx_step * A;
-        if (fits && AlignJob::loop_admit(lead->device, units)) {
+        if (fits && g.loop_adm.admit(sw, lead->device, units)) {
           g.loop_now = true;
-          g.loop_wgs = units;
           g.gx_loopw = gx_w;
           for (uint32_t a = 0; a < A && g.loop_now; a++) {
             AlignJob& j = *g.jobs[a];
-            if (g.loop_wave && (map_ensure_qidx(j.map, s) != MH_OK || !j.map->view().pts_q)) {  // (s waits for every job's stream: above)
+            if (g.loop_wave && (map_ensure_qidx(sw, j.map, s) != MH_OK || !j.map->view(sw).pts_q)) {  // (s waits for every job's stream: above)
               g.loop_now = false;
               break;
             }
-            if (g.loop_wave) h_desc[a].map = j.map->view();  // (with the sub-voxel index)
+            if (g.loop_wave) h_desc[a].map = j.map->view(sw);  // (with the sub-voxel index)
             if (j.ctx->loop_x.bytes < kLoopExchangeBytes) {
               if (j.ctx->loop_x.reserve(kLoopExchangeBytes) != MH_OK) {
                 g.loop_now = false;
@@ -404,13 +387,10 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
             h_desc[a].loop_xa = j.ctx->loop_x.p;
             h_desc[a].loop_xb = static_cast<char*>(j.ctx->loop_x.p) + 2 * (size_t)kAccN * kLoopRowStride * 16;
             h_desc[a].loop_serial0 = j.ctx->loop_serial;
-            h_desc[a].loop_pad = getenv("MH_LOOP16_TEST_ABANDON") ? 1u : 0u;
+            h_desc[a].loop_pad = sw.loop16_test_abandon ? 1u : 0u;
             j.ctx->loop_serial += max_steps + 2u;
           }
-          if (!g.loop_now) {
-            AlignJob::loop_count(lead->device).fetch_sub(g.loop_wgs);
-            g.loop_wgs = 0;
-          }
+          if (!g.loop_now) g.loop_adm.release();
         }
       }
       // descriptors and staged blocks in ONE copy, then a scatter kernel writes every job's block where it lives
@@ -470,7 +450,7 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
 #ifdef MH_DEV_VARIANTS
             case K_TILE: hipLaunchKernelGGL(k_match_tile_b, dim3(g.gx_match, A), dim3(kTileThreads), 0, s, g.dj); break;
             case K_WAVE:
-              if (wave_lds_env()) hipLaunchKernelGGL(k_match_wave_dense_b<true>, dim3(g.gx_match, A), dim3(64), 0, s, g.dj);
+              if (sw.wave_lds) hipLaunchKernelGGL(k_match_wave_dense_b<true>, dim3(g.gx_match, A), dim3(64), 0, s, g.dj);
               else hipLaunchKernelGGL(k_match_wave_dense_b<false>, dim3(g.gx_match, A), dim3(64), 0, s, g.dj);
               hipLaunchKernelGGL(k_match_wave_sparse_b, dim3(g.gx_match, A), dim3(kBlock), 0, s, g.dj);
               break;
@@ -515,10 +495,7 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
         Group& g = groups[gi];
         if (g.done) continue;
         const hipError_t we = mh::wait_stream(g.lead->stream);
-        if (g.loop_wgs) {
-          AlignJob::loop_count(g.lead->device).fetch_sub(g.loop_wgs);
-          g.loop_wgs = 0;
-        }
+        g.loop_adm.release();
         MH_HIP(we);
         if (g.loop_now) {
           // a job whose workgroups gave up waiting for each other left done == 0 and its canonical state block as uploaded: the
@@ -532,9 +509,9 @@ static mh_status align_batch_run(size_t n_jobs, const mh_map* const* maps, const
             g_loop16_fallbacks.fetch_add(1);
             MH_HIP(hipMemsetAsync(&g.jobs[a]->ctx->d_state->handover_timeouts, 0, sizeof(uint32_t) * 10, g.lead->stream));
           }
-          if (!abandoned) AlignJob::loop_holdoff(g.lead->device, -1);  // (a clean run ends a streak of abandoned loops)
+          if (!abandoned) loop_holdoff(g.lead->device, -1);  // (a clean run ends a streak of abandoned loops)
           if (abandoned) {
-            if (getenv("MH_LOOP16_TEST_ABANDON") == nullptr) AlignJob::loop_holdoff(g.lead->device, 1);
+            if (!sw.loop16_test_abandon) loop_holdoff(g.lead->device, 1);
             for (size_t a = 0; a < g.jobs.size(); a++) {
               AlignJob& j = *g.jobs[a];
               const IcpDeviceState& h = g.h_states[a];

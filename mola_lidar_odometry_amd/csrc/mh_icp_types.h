@@ -3,10 +3,6 @@
 // kernel has to be defined where it is launched).
 #pragma once
 
-#ifndef MH_LOOPW_DEFAULT
-#define MH_LOOPW_DEFAULT "batch"
-#endif
-
 using namespace mh;
 
 constexpr uint32_t kBlock = 256;

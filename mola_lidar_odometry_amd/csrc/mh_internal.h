@@ -11,6 +11,7 @@
 
 #include "../../include/molahip.h"
 #include "mh_se3.h"
+#include "mh_switches.h"
 
 namespace mh {
 
@@ -222,7 +223,7 @@ struct mh_map {
   mutable mh_status deferred_error = MH_OK;  // an insertion's out-of-range verdict, reported by the next call that resolves
   // mh_map_insert's scratch is the map's own
   mh::DevBuf build_a, build_b, build_c, build_d, build_e, sort_tmp;
-  mh::MapView view() const {
+  mh::MapView view(const mh::Switches& sw) const {
     mh::MapView v;
     v.slots = slots.as<mh::MapSlot>();
     v.pts = pts.as<float4>();
@@ -231,10 +232,10 @@ struct mh_map {
     v.vs = 1.0f / inv_vs;
     v.trunc = params.index_mode == MH_INDEX_TRUNC;
     v.ndt = params.ndt_max_eigen_ratio > 0.f ? 1u : 0u;
-    v.no_prev_bound = getenv("MH_NO_PREV_BOUND") != nullptr ? 1u : 0u;
+    v.no_prev_bound = sw.no_prev_bound ? 1u : 0u;
     v.pts_q = qidx_valid ? pts_q.as<float4>() : nullptr;
 #ifdef MH_DEBUG_WAVETRACE
-    v.dbg_stop = getenv("MH_DBG_STOP") ? (uint32_t)atoi(getenv("MH_DBG_STOP")) : 0u;
+    v.dbg_stop = sw.dbg_stop;
 #endif
     return v;
   }
@@ -279,21 +280,21 @@ mh_status scan_alloc(mh_scan* s, size_t n, bool with_t, bool with_src);
 // scan_tiles_ready() waits for the tile count
 #ifdef MH_DEV_VARIANTS  // (mh_tile.hip: the search order of the tile / wave / sorted matchers -- development library only)
 mh_status scan_build_tiles(const mh_scan* s, float inv_vs, uint32_t tile_points);
-uint32_t tile_points_for_env();
+uint32_t tile_points(const Switches& sw);
 mh_status scan_tiles_ready(const mh_scan* s);
 void scan_drop_tiles(mh_scan* s);  // host-side bookkeeping only (the points changed)
 void scan_free_tiles(mh_scan* s);
 #else
 inline mh_status scan_build_tiles(const mh_scan*, float, uint32_t) { return MH_OK; }
-inline uint32_t tile_points_for_env() { return 0; }
+inline uint32_t tile_points(const Switches&) { return 0; }
 inline mh_status scan_tiles_ready(const mh_scan*) { return MH_OK; }
 inline void scan_drop_tiles(mh_scan*) {}
 inline void scan_free_tiles(mh_scan*) {}
 #endif
 // Asynchronous on stream `s` (the context's); scratch from `m`.  Counts / bbox / the
 // out-of-range verdict are resolved lazily (map_resolve).
-mh_status map_build_device(mh_map* m, hipStream_t s, const float* dx, const float* dy, const float* dz, const uint32_t* dsrc,
-                           size_t n, const int* evict, size_t n_stored, bool collected = false);
+mh_status map_build_device(const Switches& sw, mh_map* m, hipStream_t s, const float* dx, const float* dy, const float* dz,
+                           const uint32_t* dsrc, size_t n, const int* evict, size_t n_stored, bool collected = false);
 mh_status map_build_prologue(mh_map* m, hipStream_t s, size_t n, size_t n_stored, uint32_t** counters_out,
                              unsigned long long** keys_out, uint32_t** idx_out);
 // wait (host) for the last (re)build's counters and refresh n_points / n_voxels / n_records / n_planes / bbox; returns the
@@ -303,5 +304,5 @@ mh_status map_resolve(const mh_map* m);
 mh_status map_resolve_counts(const mh_map* m);
 // make stream `s` wait for a (re)build that may still be running on the map's own context stream (no-op when `s` is that stream)
 mh_status map_ready_on(const mh_map* m, hipStream_t s);
-mh_status map_ensure_qidx(const mh_map* m, hipStream_t s);  // before any kernel that runs nn_search_quad (after map_ready_on)
+mh_status map_ensure_qidx(const Switches& sw, const mh_map* m, hipStream_t s);  // before any kernel that runs nn_search_quad (after map_ready_on)
 }  // namespace mh

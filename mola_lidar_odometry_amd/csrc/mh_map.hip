@@ -228,10 +228,8 @@ __global__ __launch_bounds__(kKeepBlock) void k_keep_seq(const float* __restrict
 }
 
 // MH_KEEP_LDS=<n>: a smaller LDS list (the parity tests drive k_keep_seq's overflow path with it)
-inline uint32_t keep_lds_points() {
-  const char* e = getenv("MH_KEEP_LDS");
-  const long x = e ? atol(e) : (long)kKeepLds;
-  return (uint32_t)std::min<long>(std::max<long>(x, 1), (long)kKeepLds);
+inline uint32_t keep_lds_points(const Switches& sw) {
+  return (uint32_t)std::min<long>(std::max<long>(sw.keep_lds, 1), (long)kKeepLds);
 }
 
 __global__ void k_add_ndt_slots(const uint32_t* __restrict__ head, uint32_t n, uint32_t* __restrict__ keep_plus) {
@@ -591,6 +589,7 @@ mh_status mh_map_build(mh_map* m, const float* x, const float* y, const float* z
   MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE, "bad mem space");
   MH_REQUIRE(n == 0 || (x && y && z), "null point arrays");
   MH_REQUIRE(n < 0x7FFFFFF0ull, "too many points");
+  const Switches sw = read_switches();
   mh_ctx* ctx = m->ctx;
   MH_TRY(set_device(ctx));
   hipStream_t s = ctx->stream;
@@ -607,7 +606,7 @@ mh_status mh_map_build(mh_map* m, const float* x, const float* y, const float* z
     dy = (const float*)(ctx->staging.as<char>() + stride);
     dz = (const float*)(ctx->staging.as<char>() + 2 * stride);
   }
-  MH_TRY(map_build_device(m, s, dx, dy, dz, nullptr, n, nullptr, 0));
+  MH_TRY(map_build_device(sw, m, s, dx, dy, dz, nullptr, n, nullptr, 0));
   m->n_offered = n;
   return map_resolve(m);  // a build reports its own verdict (out-of-range points) and leaves nothing in flight
 }
@@ -617,6 +616,7 @@ mh_status mh_map_insert(mh_map* m, const mh_scan* scan, const double T[12], floa
   MH_REQUIRE(m->ctx == scan->ctx, "map and scan belong to different contexts");
   MH_REQUIRE(remove_voxels_farther_than >= 0.f, "negative remove_voxels_farther_than");
   for (int i = 0; i < 12; i++) MH_REQUIRE(isfinite(T[i]), "non-finite pose");
+  const Switches sw = read_switches();
   mh_ctx* ctx = m->ctx;
   MH_TRY(set_device(ctx));
   // the previous update's counts (long complete by now: an align has run in between).  Its out-of-range verdict, if any, is
@@ -643,8 +643,7 @@ mh_status mh_map_insert(mh_map* m, const mh_scan* scan, const double T[12], floa
   // (up to ~0.4 M stored points: beyond, the voxel-by-voxel walk that also writes keys loses to the streaming k_keys --
   // a 10 k-point key-frame into 0.1 / 0.25 / 0.5 / 1 M points completes after 0.117 / 0.139 / 0.180 / 0.272 ms fused and
   // 0.132 / 0.156 / 0.181 / 0.242 ms with the three launches)
-  const bool fused_collect = m->n_voxels && n_new && n_old <= 400000 && getenv("MH_MAP_FULL_SORT") == nullptr &&
-                             getenv("MH_MAP_NO_COLLECT") == nullptr;
+  const bool fused_collect = m->n_voxels && n_new && n_old <= 400000 && !sw.map_full_sort && !sw.map_no_collect;
   if (fused_collect) {
     uint32_t* counters = nullptr;
     unsigned long long* keys = nullptr;
@@ -681,7 +680,7 @@ mh_status mh_map_insert(mh_map* m, const mh_scan* scan, const double T[12], floa
     }
     evict[3] = (int)ceilf(remove_voxels_farther_than * m->inv_vs);
   }
-  MH_TRY(map_build_device(m, s, mx, my, mz, msrc, total, evict, n_old, fused_collect));
+  MH_TRY(map_build_device(sw, m, s, mx, my, mz, msrc, total, evict, n_old, fused_collect));
   m->n_offered += n_new;
   if (prev_out_of_range)  // a status of its own, not a failure (a caller must be able to tell "inserted" from "not inserted")
     return fail(MH_WARN_PREVIOUS_OUT_OF_RANGE, "the PREVIOUS update of this map held points whose voxel index exceeds the +-2^20 range of the "
@@ -745,7 +744,7 @@ mh_status map_resolve(const mh_map* m) {
 // The sub-voxel index of the quad matcher (MapView::pts_q / qidx, k_build_qidx), built on first use after a (re)build, on the
 // stream that is about to search (the caller has ordered that stream behind the map's build: map_ready_on).  Other streams that
 // come later wait for the event; MH_NO_QIDX=1 builds it without boundaries (every voxel scanned whole: the A/B baseline).
-mh_status map_ensure_qidx(const mh_map* mc, hipStream_t s) {
+mh_status map_ensure_qidx(const Switches& sw, const mh_map* mc, hipStream_t s) {
   mh_map* m = const_cast<mh_map*>(mc);
   std::lock_guard<std::mutex> lk(m->qidx_mtx);
   if (m->qidx_valid) {
@@ -759,7 +758,7 @@ mh_status map_ensure_qidx(const mh_map* mc, hipStream_t s) {
   const size_t tsize = m->table_size ? m->table_size : 1;
   MH_TRY(m->pts_q.reserve(m->pts.bytes ? m->pts.bytes : sizeof(float4)));
   if (m->n_voxels && m->d_counters) {
-    const uint32_t no_index = (m->params.index_mode == MH_INDEX_TRUNC || getenv("MH_NO_QIDX") != nullptr) ? 1u : 0u;
+    const uint32_t no_index = (m->params.index_mode == MH_INDEX_TRUNC || sw.no_qidx) ? 1u : 0u;
     hipLaunchKernelGGL(k_build_qidx, dim3(nblk(m->n_voxels, 128)), dim3(128), 0, s, m->pts.as<float4>(),
                        m->vox_keys.as<unsigned long long>(), m->vox_first.as<uint32_t>(), m->vox_count.as<uint32_t>(),
                        m->d_counters + 9, m->slots.as<MapSlot>(), (uint32_t)(tsize - 1), 1.0f / m->inv_vs, no_index,
@@ -789,8 +788,7 @@ mh_status map_ready_on(const mh_map* m, hipStream_t s) {
 // with 4096 keys per workgroup needs one block sort and one or two merge passes; larger layers keep the radix sort.
 static hipError_t sort_new_points(void* tmp, size_t& tmp_bytes, unsigned long long* keys_in, unsigned long long* keys_out,
                                   uint32_t* idx_in, uint32_t* idx_out, size_t n, hipStream_t s) {
-  static const bool radix_only = getenv("MH_MAP_RADIX_SORT_NEW") != nullptr;
-  if (n > 65536 || radix_only) return rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, idx_in, idx_out, n, 0, 64, s);
+  if (n > 65536) return rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, idx_in, idx_out, n, 0, 64, s);
   using cfg = rocprim::merge_sort_config<512, 512, 8>;  // (8192 per workgroup: the block sort alone takes 92 us instead of 22)
   return rocprim::merge_sort<cfg>(tmp, tmp_bytes, keys_in, keys_out, idx_in, idx_out, n, rocprim::less<unsigned long long>(), s);
 }
@@ -832,8 +830,8 @@ mh_status map_build_prologue(mh_map* m, hipStream_t s, size_t n, size_t n_stored
   return MH_OK;
 }
 
-mh_status map_build_device(mh_map* m, hipStream_t s, const float* dx, const float* dy, const float* dz, const uint32_t* dsrc,
-                           size_t n, const int* evict, size_t n_stored, bool collected) {
+mh_status map_build_device(const Switches& sw, mh_map* m, hipStream_t s, const float* dx, const float* dy, const float* dz,
+                           const uint32_t* dsrc, size_t n, const int* evict, size_t n_stored, bool collected) {
   const uint32_t ndt = m->params.ndt_max_eigen_ratio > 0.f ? 1u : 0u;
   const size_t n_vox_ub = n_stored ? std::min<size_t>(n, m->n_voxels + (n - n_stored)) : n;
   const size_t n_rec_ub = n + (ndt ? 2 * n_vox_ub : 0);
@@ -862,7 +860,7 @@ mh_status map_build_device(mh_map* m, hipStream_t s, const float* dx, const floa
     // mh_map_insert hands over [stored points, voxel by voxel in key order | new points]: only the new ones need sorting,
     // one merge puts them in place (stored first among equal keys = insertion order).  MH_MAP_FULL_SORT=1: sort everything.
     const size_t n_new = n - n_stored;
-    const bool merge_path = n_stored > 0 && getenv("MH_MAP_FULL_SORT") == nullptr;
+    const bool merge_path = n_stored > 0 && !sw.map_full_sort;
     MH_TRY(m->build_a.reserve((2 * n + n_new) * sizeof(unsigned long long)));  // keys in | keys sorted | new keys sorted
     MH_TRY(m->build_b.reserve((2 * n + n_new) * sizeof(uint32_t)));            // idx in | idx sorted | new idx sorted
     MH_TRY(m->build_c.reserve(2 * n * sizeof(uint32_t)));            // head | vid1
@@ -919,7 +917,7 @@ mh_status map_build_device(mh_map* m, hipStream_t s, const float* dx, const floa
     if (m->params.min_distance_between_points > 0.f)
       hipLaunchKernelGGL(k_keep_seq, dim3(nblk(n, kKeepBlock)), dim3(kKeepBlock), 0, s, dx, dy, dz, keys_s, idx_s, head, vid1,
                          vstart, N, m->params.max_points_per_voxel, m->params.min_distance_between_points, (uint32_t)n_stored,
-                         keep_lds_points(), keep);
+                         keep_lds_points(sw), keep);
     else
       hipLaunchKernelGGL(k_keep, dim3(nblk(n, B)), dim3(B), 0, s, keys_s, vid1, vstart, N, m->params.max_points_per_voxel,
                          keep);

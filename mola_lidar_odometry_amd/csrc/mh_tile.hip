@@ -66,9 +66,8 @@ __global__ void k_tile_finish(uint32_t* __restrict__ tile_start, const uint32_t*
   *h_count = c;       // pinned host memory
 }
 
-uint32_t tile_points_for_env() {  // MH_MATCH=w (wave matcher): tiles of one wave; t: tiles of one workgroup
-  const char* e = getenv("MH_MATCH");
-  return (e && e[0] == 'w') ? 64u : 256u;
+uint32_t tile_points(const Switches& sw) {  // MH_MATCH=w (wave matcher): tiles of one wave; t: tiles of one workgroup
+  return sw.match == 'w' ? 64u : 256u;
 }
 
 void scan_drop_tiles(mh_scan* s) {
@@ -165,6 +164,6 @@ extern "C" {
 mh_status mh_scan_prepare(const mh_scan* scan, float voxel_size) {
   MH_REQUIRE(scan, "null scan");
   MH_REQUIRE(voxel_size > 0.f, "voxel_size must be > 0");
-  return mh::scan_build_tiles(scan, 1.0f / voxel_size, mh::tile_points_for_env());
+  return mh::scan_build_tiles(scan, 1.0f / voxel_size, mh::tile_points(mh::read_switches()));
 }
 }
