@@ -44,10 +44,10 @@ extern "C" {
 #define MH_VERSION_MINOR 1
 #define MH_VERSION_PATCH 0
 /* The parameter structs of this header carry no size field: they grow at the END, and every growth bumps MH_ABI_VERSION (6:
- * mh_preprocess_params' two decimation-method fields, round 5).  A binder built against this header checks
+ * mh_preprocess_params' two decimation-method fields, round 5; 7: mh_layer_pair and mh_icp_align_layers).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
  * built with) and zero-initialises every struct it passes -- a field the binder does not know then reads as its default. */
-#define MH_ABI_VERSION 6
+#define MH_ABI_VERSION 7
 
 typedef int32_t mh_status;
 enum {
@@ -546,6 +546,41 @@ MH_API mh_status mh_icp_align_batch(size_t n_jobs, const mh_map* const* maps, co
                                     const mh_icp_params* params, int32_t params_per_job, const double* T_guesses,
                                     const mh_prior* const* priors, mh_icp_result* results, void* pairs_block,
                                     int32_t pairs_mem);
+
+/* Fused path over several point-layer pairs.  Replaces mp2p_icp::ICP::align [U] with an ICP block of one or more
+ * Matcher_Points_DistanceThreshold whose pointLayerMatches hold several {global, local, weight} entries and one
+ * Solver_GaussNewton (pipelines/extras/lidar3d-dual-map.yaml:115-132, lidar3d-edges.yaml:120-129; no runFromIteration /
+ * runUpToIteration gates, pairingsPerPoint 1, allowMatchAlreadyMatchedGlobalPoints true).
+ *  - Matching: in every ICP iteration k, pair i runs the matcher of mh_nn_search on (map_i, scan_i): the 27-voxel exact search,
+ *    accepted iff d^2 < (float)(threshold_i[k]^2) + ang_i^2*|p'|^2 with ang_i from threshold_angular_deg_i as in mh_icp_align.
+ *  - Solve: the pairings of ALL pairs go to one robust Gauss-Newton solve; pair i's rows are scaled by weight_i.  Inner steps,
+ *    the kernel-parameter schedule, prior, stall test, device hook, poll_every and expected_iterations behave as in mh_icp_align.
+ *  - Counts: n_final_pairs (and the trace's n_pairs) is the sum over the pairs, potential_pairings = sum of scan_i->n, quality =
+ *    their ratio (PairedRatio); NoPairings when the sum is 0.  The covariance is mh_icp_align's over the union of the final
+ *    pairings.
+ *  - Ignored fields of mh_icp_params: threshold, threshold_angular_deg, gn.weight_pt2pt (every pair carries its own); the trace's
+ *    threshold reports pair 0's.
+ *  - final_pairs[i] (nullable; arrays in pairs_mem of scan_i-size entries) receives pair i's final pairings in ascending local
+ *    index, final_pair_counts[i] (nullable) their number.
+ *  - Pairs may share a map and may share a scan: a shared scan pairs its points again for every pair (MH_MATCHED_POINTS_PAIR_AGAIN).
+ *  - MH_ERR_INVALID_ARGUMENT: n_pairs 0 or above MH_MAX_LAYER_PAIRS, a null map / scan / threshold, maps and scans on more than
+ *    one context, pt2pl_threshold != NULL.  MH_ERR_UNSUPPORTED: matched_points == MH_MATCHED_POINTS_SKIP with a scan shared by
+ *    two pairs, profile != 0, a map of 2^30 or more records.
+ * Per ICP iteration 1 + 2 * gn.max_inner_iterations launches, whatever the number of pairs.  No one-launch loops, streaming control or
+ * lock-step batches on this path. */
+#define MH_MAX_LAYER_PAIRS 8
+typedef struct {
+  const mh_map* map;            /* global layer */
+  const mh_scan* scan;          /* local layer (vehicle frame, untransformed) */
+  const double* threshold;      /* HOST, max_iterations entries: this matcher's threshold per ICP_ITERATION */
+  double threshold_angular_deg;
+  double weight;                /* pointLayerMatches {..., weight} */
+} mh_layer_pair;
+
+MH_API mh_status mh_icp_align_layers(size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params,
+                                     const double T_guess[12], const mh_prior* prior, mh_icp_result* result,
+                                     mh_icp_iter* trace, const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
+                                     uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
 
 #ifdef __cplusplus
 }

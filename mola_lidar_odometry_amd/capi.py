@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -119,6 +119,12 @@ class ICPResult(C.Structure):
                 ("n_host_polls", C.c_uint32), ("n_enqueued_iterations", C.c_uint32)]
 
 
+class LayerPair(C.Structure):
+    """mh_layer_pair: one {global, local} entry of a multi-layer alignment (mh_icp_align_layers)."""
+    _fields_ = [("map", C.c_void_p), ("scan", C.c_void_p), ("threshold", _DP), ("threshold_angular_deg", C.c_double),
+                ("weight", C.c_double)]
+
+
 class PreprocessParams(C.Structure):
     _fields_ = [("decim_map_resolution", C.c_float), ("decim_icp_resolution", C.c_float),
                 ("min_points_to_filter", C.c_uint32), ("index_mode", C.c_int32), ("range_min", C.c_float),
@@ -195,6 +201,9 @@ _SIGNATURES = {
                                        C.c_int32, _DP, C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.c_void_p,
                                        C.c_int32]),
     "mh_pairs_block_bytes": (C.c_size_t, [C.c_size_t]),
+    "mh_icp_align_layers": (C.c_int32, [C.c_size_t, C.POINTER(LayerPair), C.POINTER(ICPParamsC), _DP, C.POINTER(Prior),
+                                        C.POINTER(ICPResult), C.POINTER(ICPIter), C.POINTER(PairsOut),
+                                        C.POINTER(C.c_uint64), C.c_int32]),
 }
 
 _lib = None
@@ -726,6 +735,16 @@ def icp_align_prefers_solo(s: Scan, p: ICPParams, T_guess=None, concurrent_calle
     return bool(yes.value)
 
 
+def _trace_list(out, trace, p: ICPParams):
+    """The executed iterations' records of an ICPIter array (NoPairings / SolverError leave the failing one out)."""
+    n_tr = min(p.max_iterations, out["n_iterations"] + 1)
+    if TERM_NAMES[out["termination_reason"]] in ("NoPairings", "SolverError"):
+        n_tr = out["n_iterations"]
+    return [dict(T=np.array(trace[i].T), n_pairs=int(trace[i].n_pairs), threshold=trace[i].threshold,
+                 kernel_param=trace[i].kernel_param, delta_trans=trace[i].delta_trans,
+                 delta_rot=trace[i].delta_rot) for i in range(n_tr)]
+
+
 def icp_align(m: Map, s: Scan, T_guess, p: ICPParams, prior=None, want_trace=True, want_pairs=False):
     cp, keep = p.c(T_guess)
     T0 = _T12(T_guess)
@@ -743,17 +762,66 @@ def icp_align(m: Map, s: Scan, T_guess, p: ICPParams, prior=None, want_trace=Tru
                             trace, C.byref(po) if po else None, MEM_HOST))
     out = _result_dict(res)
     if want_trace:
-        n_it = out["n_iterations"]
-        n_tr = min(p.max_iterations, n_it + 1)
-        if TERM_NAMES[out["termination_reason"]] in ("NoPairings", "SolverError"):
-            n_tr = n_it
-        out["trace"] = [dict(T=np.array(trace[i].T), n_pairs=int(trace[i].n_pairs), threshold=trace[i].threshold,
-                             kernel_param=trace[i].kernel_param, delta_trans=trace[i].delta_trans,
-                             delta_rot=trace[i].delta_rot) for i in range(n_tr)]
+        out["trace"] = _trace_list(out, trace, p)
     if want_pairs:
         k = out["n_final_pairs"] - out["n_final_pairs_pt2pl"]
         out["pairs"] = dict(local_idx=li[:k].copy(), global_idx=gi[:k].copy(),
                             global_xyz=np.stack([gx[:k], gy[:k], gz[:k]], 1), d2=d2[:k].copy())
+    return out
+
+
+def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, want_pairs=False):
+    """mh_icp_align_layers: one alignment over several (map, scan) point-layer pairs with one Gauss-Newton solve.
+    `pairs`: a sequence of dicts {map, scan, threshold, threshold_angular_deg=0, weight=1} or tuples in that order; a
+    threshold is a scalar or max_iterations values.  p.threshold, p.threshold_angular_deg and p.gn.weight_pt2pt are not used.
+    Returns icp_align's dict plus pair_counts (final pairings per pair) and, with want_pairs, pairs (one dict per pair)."""
+    norm = []
+    for e in pairs:
+        if not isinstance(e, dict):
+            e = dict(zip(("map", "scan", "threshold", "threshold_angular_deg", "weight"), e))
+        norm.append(e)
+    n_pairs = len(norm)
+    p_c = replace(p, threshold=p.threshold if p.threshold is not None else 0.0)
+    cp, keep = p_c.c(T_guess)
+    T0 = _T12(T_guess)
+    arr = (LayerPair * max(1, n_pairs))()
+    thr_keep = []
+    for i, e in enumerate(norm):
+        m, s = e.get("map"), e.get("scan")
+        arr[i].map = m._h if m is not None else None
+        arr[i].scan = s._h if s is not None else None
+        if e.get("threshold") is not None:
+            t = np.ascontiguousarray(np.broadcast_to(np.asarray(e["threshold"], np.float64), (max(1, p.max_iterations),)))
+            thr_keep.append(t)
+            arr[i].threshold = t.ctypes.data_as(_DP)
+        arr[i].threshold_angular_deg = float(e.get("threshold_angular_deg", 0.0) or 0.0)
+        arr[i].weight = float(e.get("weight", 1.0) if e.get("weight") is not None else 1.0)
+    res = ICPResult()
+    trace = (ICPIter * max(1, p.max_iterations))() if want_trace else None
+    pr = _mk_prior(prior)
+    counts = (C.c_uint64 * max(1, n_pairs))()
+    po, bufs = None, []
+    if want_pairs:
+        po = (PairsOut * max(1, n_pairs))()
+        for i, e in enumerate(norm):
+            n = max(e["scan"].n, 1)
+            li, gi = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+            gx, gy, gz, d2 = (np.zeros(n, np.float32) for _ in range(4))
+            po[i] = PairsOut(li.ctypes.data_as(_UP), gi.ctypes.data_as(_UP), gx.ctypes.data_as(_FP), gy.ctypes.data_as(_FP),
+                             gz.ctypes.data_as(_FP), d2.ctypes.data_as(_FP))
+            bufs.append((li, gi, gx, gy, gz, d2))
+    _chk(lib().mh_icp_align_layers(n_pairs, arr, C.byref(cp), T0.ctypes.data_as(_DP), C.byref(pr) if pr else None,
+                                   C.byref(res), trace, po, counts, MEM_HOST))
+    out = _result_dict(res)
+    out["pair_counts"] = [int(counts[i]) for i in range(n_pairs)]
+    if want_trace:
+        out["trace"] = _trace_list(out, trace, p)
+    if want_pairs:
+        out["pairs"] = []
+        for i, (li, gi, gx, gy, gz, d2) in enumerate(bufs):
+            k = out["pair_counts"][i]
+            out["pairs"].append(dict(local_idx=li[:k].copy(), global_idx=gi[:k].copy(),
+                                     global_xyz=np.stack([gx[:k], gy[:k], gz[:k]], 1), d2=d2[:k].copy()))
     return out
 
 

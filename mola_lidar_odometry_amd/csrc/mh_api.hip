@@ -201,6 +201,9 @@ mh_status mh_ctx_destroy(mh_ctx* ctx) {
   if (ctx->h_pp) (void)hipHostFree(ctx->h_pp);
   if (ctx->h_sched) (void)hipHostFree(ctx->h_sched);
   if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+  ctx->layers_pairs.release();
+  ctx->layers_tab.release();
+  if (ctx->h_layers) (void)hipHostFree(ctx->h_layers);
   ctx->batch_desc.release();
   ctx->batch_states.release();  // d_params / h_params point into the state blocks
   if (ctx->ev_poll) (void)hipEventDestroy(ctx->ev_poll);

@@ -57,6 +57,7 @@
 #include "mh_k_step.h"
 #include "mh_k_cov.h"
 #include "mh_k_launch.h"
+#include "mh_k_layers.h"
 #include "mh_k_pairs.h"
 
 // ================================================================================================
@@ -156,8 +157,9 @@ bool pose_ok(const double T[12]) {
   return true;
 }
 
-// compaction of the context's pair buffers into caller arrays; returns the number of pairs
-mh_status compact_pairs(mh_ctx* ctx, size_t n, const mh_pairs_out* out, int32_t mem, uint64_t* n_pairs_out) {
+// compaction of pairing buffers (gidx / q, n entries) into caller arrays; returns the number of pairs
+mh_status compact_pairs_of(mh_ctx* ctx, const uint32_t* gidx, const float4* q, size_t n, const mh_pairs_out* out, int32_t mem,
+                           uint64_t* n_pairs_out) {
   hipStream_t s = ctx->stream;
   const uint32_t nb = nblk(n);
   const size_t n4 = ((n + 63) / 64) * 64;
@@ -182,10 +184,9 @@ mh_status compact_pairs(mh_ctx* ctx, size_t n, const mh_pairs_out* out, int32_t 
   }
   uint32_t h_total = 0;
   if (n) {
-    hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(kBlock), 0, s, ctx->pair_gidx.as<uint32_t>(), (uint32_t)n, counts);
+    hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(kBlock), 0, s, gidx, (uint32_t)n, counts);
     hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, counts, nb, offsets, total);
-    hipLaunchKernelGGL(k_compact, dim3(nb), dim3(kBlock), 0, s, ctx->pair_gidx.as<uint32_t>(), ctx->pair_q.as<float4>(),
-                       (uint32_t)n, offsets, o_li, o_gi, o_x, o_y, o_z, o_d2);
+    hipLaunchKernelGGL(k_compact, dim3(nb), dim3(kBlock), 0, s, gidx, q, (uint32_t)n, offsets, o_li, o_gi, o_x, o_y, o_z, o_d2);
     MH_HIP(hipGetLastError());
     MH_HIP(hipMemcpyAsync(&h_total, total, 4, hipMemcpyDeviceToHost, s));
     MH_HIP(mh::wait_stream(s));
@@ -201,6 +202,10 @@ mh_status compact_pairs(mh_ctx* ctx, size_t n, const mh_pairs_out* out, int32_t 
   }
   if (n_pairs_out) *n_pairs_out = h_total;
   return MH_OK;
+}
+// ... of the context's own pair buffers (a single alignment's)
+mh_status compact_pairs(mh_ctx* ctx, size_t n, const mh_pairs_out* out, int32_t mem, uint64_t* n_pairs_out) {
+  return compact_pairs_of(ctx, ctx->pair_gidx.as<uint32_t>(), ctx->pair_q.as<float4>(), n, out, mem, n_pairs_out);
 }
 
 std::atomic<unsigned long long> g_loop16_runs{0}, g_loop16_fallbacks{0};  // one-launch loops started / abandoned for the chain (mh_debug_loop_stats)
@@ -1051,6 +1056,8 @@ mh_status align_single(const Switches& sw, const mh_map* map, const mh_scan* sca
   return MH_OK;
 }
 
+#include "mh_icp_layers.inl"  // align_layers (mh_icp_align_layers)
+
 }  // namespace
 
 extern "C" {
@@ -1098,5 +1105,33 @@ size_t mh_pairs_block_bytes(size_t n_scan_points) {
 #include "mh_icp_batch.inl"  // mh_icp_align_batch
 
 #include "mh_icp_api.inl"    // mh_nn_search*, mh_gn_solve, mh_covariance
+
+mh_status mh_icp_align_layers(size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params, const double T_guess[12],
+                              const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
+                              uint64_t* final_pair_counts, int32_t pairs_mem) {
+  MH_REQUIRE(n_pairs >= 1 && n_pairs <= MH_MAX_LAYER_PAIRS, "n_pairs must be 1 .. MH_MAX_LAYER_PAIRS");
+  MH_REQUIRE(pairs && params && T_guess && result, "null argument");
+  for (size_t i = 0; i < n_pairs; i++) {
+    MH_REQUIRE(pairs[i].map && pairs[i].scan && pairs[i].threshold, "null map, scan or threshold in a layer pair");
+    MH_REQUIRE(pairs[i].map->ctx == pairs[0].scan->ctx && pairs[i].scan->ctx == pairs[0].scan->ctx,
+               "the maps and scans of a multi-layer alignment live on different contexts");
+  }
+  MH_REQUIRE(params->pt2pl_threshold == nullptr, "Matcher_Point2Plane is not supported with layer pairs");
+  MH_REQUIRE(pose_ok(T_guess), "non-finite initial guess");
+  MH_REQUIRE(params->max_iterations == 0 || params->kernel_param, "kernel_param array is required");
+  MH_REQUIRE(params->gn.max_inner_iterations >= 1, "gn.max_inner_iterations must be >= 1");
+  MH_REQUIRE(params->gn.robust_kernel <= MH_KERNEL_GM_C2, "unknown robust kernel");
+  MH_REQUIRE(params->max_iterations < (1u << 20), "max_iterations too large");
+  MH_REQUIRE(params->matched_points <= MH_MATCHED_POINTS_SKIP, "unknown matched_points mode");
+  MH_REQUIRE(!final_pairs || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
+  if (params->profile != 0) return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: profile is not supported");
+  if (params->matched_points == MH_MATCHED_POINTS_SKIP)
+    for (size_t i = 0; i < n_pairs; i++)
+      for (size_t j = i + 1; j < n_pairs; j++)
+        if (pairs[i].scan == pairs[j].scan)
+          return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: MH_MATCHED_POINTS_SKIP with a scan shared by two pairs");
+  return align_layers(read_switches(), (uint32_t)n_pairs, pairs, params, T_guess, prior, result, trace, final_pairs,
+                      final_pair_counts, pairs_mem);
+}
 
 }  // extern "C"

@@ -1,0 +1,263 @@
+// mh_icp_layers.inl -- mh_icp_align_layers: one ICP alignment over several Matcher_Points_DistanceThreshold (map, scan) pairs
+// (lidar3d-dual-map.yaml, lidar3d-edges.yaml) with one Gauss-Newton solve.  Included by mh_icp.hip inside its anonymous namespace.
+//
+// Per ICP iteration:  k_match_layers -> k_accum_layers(first) -> k_solve -> [k_accum_layers -> k_solve] x (inner - 1)
+// over ALL pairs, whatever their number (mh_k_layers.h); the covariance kernels close the chunk that ends the loop.  Loop
+// control is AlignJob's chunked one: a chunk of iterations is enqueued (replayed from a captured graph once its shape repeats,
+// MH_NO_GRAPH=1: never), the host waits for its event and reads the done flag.
+
+constexpr unsigned long long kLayersGraphTag = 0x4C41594552530000ull;  // "LAYERS": no size of a single alignment's key comes near it
+
+struct LayersLayout {
+  size_t seg_q[MH_MAX_LAYER_PAIRS], seg_g[MH_MAX_LAYER_PAIRS];  // byte offsets of each pair's pairing buffers
+  size_t pair_bytes = 0;
+  uint32_t tot_match = 0, tot_acc = 0, tot_cov = 0;
+};
+
+mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pairs, const mh_icp_params* p, const double T0[12],
+                       const mh_prior* prior, mh_icp_result* res, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
+                       uint64_t* final_pair_counts, int32_t pairs_mem) {
+  mh_ctx* const ctx = pairs[0].scan->ctx;
+  memset(res, 0, sizeof(*res));
+  for (int i = 0; i < 12; i++) res->T[i] = T0[i];
+  for (int i = 0; i < 6; i++) res->cov[i * 7] = 1e6;
+  if (final_pair_counts)
+    for (uint32_t i = 0; i < np; i++) final_pair_counts[i] = 0;
+  size_t total_n = 0;
+  for (uint32_t i = 0; i < np; i++) total_n += pairs[i].scan->n;
+  res->potential_pairings = total_n;  // every pair adds its layer size
+  if (p->max_iterations == 0 || total_n == 0) {
+    res->termination_reason = p->max_iterations == 0 ? MH_TERM_MAX_ITERATIONS : MH_TERM_NO_PAIRINGS;
+    return MH_OK;
+  }
+  MH_TRY(set_device(ctx));
+  MH_TRY(ensure_state(ctx));
+  hipStream_t s = ctx->stream;
+  // every distinct map: its pending key-frame update, its sub-voxel index (the plan / scan search reads it)
+  for (uint32_t i = 0; i < np; i++) {
+    bool seen = false;
+    for (uint32_t j = 0; j < i; j++) seen = seen || pairs[j].map == pairs[i].map;
+    if (seen) continue;
+    const mh_map* m = pairs[i].map;
+    // (n_records: exact once the last (re)build is resolved, an upper bound while it may still run -- never below the truth)
+    if (m->n_records >= kFlatMaxRecords)
+      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: a map of 2^30 or more records");
+    MH_TRY(map_ready_on(m, s));
+    MH_TRY(map_ensure_qidx(sw, m, s));
+    if (!m->view(sw).pts_q) return fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (mh_icp_align_layers needs it)");
+  }
+  // layout: a pairing segment per pair (a scan shared by two pairs is paired again for each), flattened grids
+  LayersLayout L;
+  LayerTable* tab = nullptr;
+  const size_t mi = p->max_iterations;
+  const size_t tab_bytes = (sizeof(LayerTable) + 255) / 256 * 256;
+  const size_t sched_bytes = (1 + (size_t)np) * mi * sizeof(double);  // kernel_param | threshold of pair 0 | ... | pair np-1
+  if (ctx->h_layers_cap < tab_bytes + sched_bytes) {
+    if (ctx->h_layers) (void)hipHostFree(ctx->h_layers);
+    ctx->h_layers = nullptr;
+    ctx->h_layers_cap = 0;
+    MH_HIP(hipHostMalloc(&ctx->h_layers, tab_bytes + sched_bytes, hipHostMallocDefault));
+    ctx->h_layers_cap = tab_bytes + sched_bytes;
+  }
+  MH_TRY(ctx->layers_tab.reserve(tab_bytes + sched_bytes));
+  tab = static_cast<LayerTable*>(ctx->h_layers);
+  memset(tab, 0, sizeof(LayerTable));
+  tab->n_pairs = np;
+  for (uint32_t i = 0; i < np; i++) {
+    const size_t n = pairs[i].scan->n, nn = n ? n : 1;
+    L.seg_q[i] = L.pair_bytes;
+    L.pair_bytes += (nn * sizeof(float4) + 255) / 256 * 256;
+    L.seg_g[i] = L.pair_bytes;
+    L.pair_bytes += (nn * sizeof(uint32_t) + 255) / 256 * 256;
+    tab->blk_match[i] = L.tot_match;
+    tab->blk_acc[i] = L.tot_acc;
+    tab->blk_cov[i] = L.tot_cov;
+    L.tot_match += (uint32_t)((n + kFlatPointsPerBlock - 1) / kFlatPointsPerBlock);
+    L.tot_acc += n ? nblk_acc(n) : 0u;
+    L.tot_cov += n ? nblk(n) : 0u;
+  }
+  tab->blk_match[np] = L.tot_match;
+  tab->blk_acc[np] = L.tot_acc;
+  tab->blk_cov[np] = L.tot_cov;
+  MH_TRY(ctx->layers_pairs.reserve(L.pair_bytes));
+  const uint32_t cols = L.tot_acc > L.tot_cov ? L.tot_acc : L.tot_cov;
+  MH_TRY(ctx->partials.reserve((size_t)kGenN * (cols ? cols : 1) * sizeof(double)));
+  if (trace) MH_TRY(ctx->trace.reserve(mi * sizeof(mh_icp_iter)));
+  double* const h_sched = reinterpret_cast<double*>(static_cast<char*>(ctx->h_layers) + tab_bytes);
+  double* const d_sched = reinterpret_cast<double*>(ctx->layers_tab.as<char>() + tab_bytes);
+  memcpy(h_sched, p->kernel_param, mi * sizeof(double));
+  char* const pb = ctx->layers_pairs.as<char>();
+  const double deg = 3.14159265358979323846 / 180.0;
+  for (uint32_t i = 0; i < np; i++) {
+    LayerDesc& d = tab->d[i];
+    memcpy(h_sched + (1 + i) * mi, pairs[i].threshold, mi * sizeof(double));
+    d.map = pairs[i].map->view(sw);
+    d.lx = pairs[i].scan->x;
+    d.ly = pairs[i].scan->y;
+    d.lz = pairs[i].scan->z;
+    d.n = (uint32_t)pairs[i].scan->n;
+    d.pair_q = reinterpret_cast<float4*>(pb + L.seg_q[i]);
+    d.pair_gidx = reinterpret_cast<uint32_t*>(pb + L.seg_g[i]);
+    const double ang = pairs[i].threshold_angular_deg * deg;  // as mh_icp_align computes it
+    d.mk.thr = d_sched + (1 + i) * mi;
+    d.mk.kparam = d_sched;
+    d.mk.ang2 = (float)(ang * ang);
+    d.mk.kernel = p->gn.robust_kernel;
+    d.mk.w_pt2pt = pairs[i].weight;
+    d.col_off = tab->blk_acc[i];
+    d.cov_off = tab->blk_cov[i];
+  }
+  MH_HIP(hipMemcpyAsync(ctx->layers_tab.p, ctx->h_layers, tab_bytes + sched_bytes, hipMemcpyHostToDevice, s));
+  // the shared state and the solver's parameters: pair 0 stands in where a single value is reported (the trace's threshold)
+  MatchK mk = tab->d[0].mk;
+  SolveK sk;
+  memset(&sk, 0, sizeof(sk));
+  sk.max_iterations = p->max_iterations;
+  sk.disable_stall = p->disable_stall_test;
+  sk.max_inner = p->gn.max_inner_iterations;
+  sk.min_step_trans = p->min_abs_step_trans;
+  sk.min_step_rot = p->min_abs_step_rot;
+  sk.min_delta = p->gn.min_delta;
+  sk.max_cost = p->gn.max_cost;
+  sk.hook_enabled = p->hook_enabled;
+  sk.hook_trans = p->hook_min_trans;
+  sk.hook_rot = p->hook_min_rot;
+  sk.hook_cos_rot = (p->hook_min_rot > 0.0 && p->hook_min_rot < 3.0) ? cos(p->hook_min_rot) : __builtin_nan("");
+  if (p->hook_enabled) {
+    Pose C;
+    for (int i = 0; i < 12; i++) C.m[i] = p->hook_checkpoint[i];
+    const Pose Ci = inverse(C);
+    for (int i = 0; i < 12; i++) sk.hook_chk_inv[i] = Ci.m[i];
+  }
+  fill_prior(sk, prior);
+  sk.thr = mk.thr;
+  sk.kparam = mk.kparam;
+  sk.trace = trace ? ctx->trace.as<mh_icp_iter>() : nullptr;
+  sk.cov_hx = p->cov_findif_xyz;
+  sk.cov_ha = p->cov_findif_ang;
+  ctx->align_serial++;
+  init_state(ctx->h_state, T0);
+  ctx->h_state->serial = ((uint32_t)ctx->align_serial & 0x3FFu) << 22;
+  ctx->h_state->cur_thr2 = (float)(pairs[0].threshold[0] * pairs[0].threshold[0]);
+  ctx->h_state->cur_ang2 = mk.ang2;
+  ctx->h_state->cur_kparam = p->kernel_param[0];
+  MH_TRY(upload_state_and_params(ctx, mk, sk));
+
+  const LayerTable* const dtab = ctx->layers_tab.as<LayerTable>();
+  double* const part = ctx->partials.as<double>();
+  const SolveK* const dsk = &ctx->d_params->sk;
+  const uint32_t inner = p->gn.max_inner_iterations;
+  uint32_t chunk;
+  {
+    const uint32_t expect = p->expected_iterations ? p->expected_iterations : ctx->layers_predicted;
+    chunk = p->poll_every ? p->poll_every : (expect ? (expect + kChunkMargin > 64 ? 64u : expect + kChunkMargin) : 10u);
+  }
+  uint32_t enqueued = 0, polls = 0;
+  for (;;) {
+    const uint32_t m = (p->max_iterations - enqueued) < chunk ? (p->max_iterations - enqueued) : chunk;
+    auto enqueue_kernels = [&]() {
+      for (uint32_t j = 0; j < m; j++) {
+        hipLaunchKernelGGL(k_match_layers, dim3(L.tot_match), dim3(kFlatThreads), 0, s, ctx->d_state, dtab);
+        hipLaunchKernelGGL(k_accum_layers, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 1u, part, L.tot_acc);
+        hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, dsk, (const double*)part, L.tot_acc,
+                           L.tot_acc, (const double*)nullptr, 0u, 0u, 1u);
+        for (uint32_t in = 1; in < inner; in++) {
+          hipLaunchKernelGGL(k_accum_layers, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 0u, part, L.tot_acc);
+          hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, dsk, (const double*)part, L.tot_acc,
+                             L.tot_acc, (const double*)nullptr, 0u, 0u, 0u);
+        }
+      }
+      if (p->compute_covariance) {  // no-ops unless the loop has terminated
+        hipLaunchKernelGGL(k_cov_prepare, dim3(1), dim3(64), 0, s, ctx->d_state, dsk, 0u);
+        hipLaunchKernelGGL(k_cov_accum_layers, dim3(L.tot_cov), dim3(kBlock), 0, s, ctx->d_state, dtab, part, L.tot_cov);
+        hipLaunchKernelGGL(k_cov_finalize, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, 0u, (const double*)part, L.tot_cov,
+                           L.tot_cov, (const double*)nullptr, 0u, 0u);
+      }
+      (void)hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(IcpDeviceState), hipMemcpyDeviceToHost, s);
+    };
+    // the launches depend on the sizes and the buffers only (the per-alignment values sit in device memory): a shape seen in
+    // an earlier alignment is captured once and replayed, as AlignJob::enqueue_chunk does
+    unsigned long long key[32] = {0};
+    const unsigned long long kv[] = {kLayersGraphTag | np, m, inner, p->compute_covariance, L.tot_match, L.tot_acc, L.tot_cov,
+                                     (unsigned long long)dtab, (unsigned long long)part, (unsigned long long)ctx->d_state,
+                                     (unsigned long long)ctx->d_params, (unsigned long long)ctx->h_state};
+    static_assert(sizeof(kv) <= sizeof(key), "graph key too small");
+    memcpy(key, kv, sizeof(kv));
+    const bool cached = !sw.no_graph && ctx->graph_exec && memcmp(key, ctx->graph_key, sizeof(key)) == 0;
+    const bool seen_before = !sw.no_graph && memcmp(key, ctx->graph_candidate, sizeof(key)) == 0 &&
+                             ctx->graph_candidate_align != ctx->align_serial;
+    if (!cached && !seen_before) {
+      if (!sw.no_graph && memcmp(key, ctx->graph_candidate, sizeof(key)) != 0) {
+        memcpy(ctx->graph_candidate, key, sizeof(key));
+        ctx->graph_candidate_align = ctx->align_serial;
+      }
+      enqueue_kernels();
+      MH_HIP(hipGetLastError());
+    } else {
+      if (!cached) {
+        if (ctx->graph_exec) {
+          (void)hipGraphExecDestroy(ctx->graph_exec);
+          ctx->graph_exec = nullptr;
+        }
+        hipGraph_t g = nullptr;
+        MH_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        enqueue_kernels();
+        const hipError_t ce = hipStreamEndCapture(s, &g);
+        if (ce != hipSuccess) {
+          if (g) (void)hipGraphDestroy(g);
+          return fail(MH_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
+        }
+        const hipError_t ie = hipGraphInstantiate(&ctx->graph_exec, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        if (ie != hipSuccess) {
+          ctx->graph_exec = nullptr;
+          return fail(MH_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
+        }
+        memcpy(ctx->graph_key, key, sizeof(key));
+      }
+      MH_HIP(hipGraphLaunch(ctx->graph_exec, s));
+    }
+    enqueued += m;
+    MH_HIP(hipEventRecord(ctx->ev_poll, s));
+    polls++;
+    MH_HIP(mh::wait_event(ctx->ev_poll));
+    if (ctx->h_state->done) break;
+    if (enqueued >= p->max_iterations) return fail(MH_ERR_INTERNAL, "device ICP loop did not terminate after max_iterations");
+    if (p->poll_every == 0) chunk = kChunkNext;
+  }
+  const IcpDeviceState* h = ctx->h_state;
+  if (p->poll_every == 0) ctx->layers_predicted = h->n_iterations + (h->term_reason == MH_TERM_MAX_ITERATIONS ? 0u : 1u);
+  res->n_host_polls = polls;
+  res->n_enqueued_iterations = enqueued;
+  for (int i = 0; i < 12; i++) res->T[i] = h->T[i];
+  if (p->compute_covariance)
+    for (int i = 0; i < 36; i++) res->cov[i] = h->cov[i];
+  res->n_iterations = h->n_iterations;
+  res->termination_reason = h->term_reason;
+  res->n_final_pairs = h->n_pairs;
+  res->quality = h->n_pairs ? (double)h->n_pairs / (double)total_n : 0.0;  // PairedRatio over all pairs
+  if (h->term_reason == MH_TERM_NO_PAIRINGS)
+    for (int i = 0; i < 36; i++) res->cov[i] = (i % 7 == 0) ? 1e6 : 0.0;
+  if (trace) {
+    const uint32_t cnt = h->n_iterations < p->max_iterations ? h->n_iterations + 1 : p->max_iterations;
+    memset(trace, 0, sizeof(mh_icp_iter) * p->max_iterations);
+    const uint32_t valid = (h->term_reason == MH_TERM_NO_PAIRINGS || h->term_reason == MH_TERM_SOLVER_ERROR) ? h->n_iterations : cnt;
+    if (valid) MH_HIP(hipMemcpy(trace, ctx->trace.p, sizeof(mh_icp_iter) * valid, hipMemcpyDeviceToHost));
+  }
+  if ((final_pairs || final_pair_counts) && res->n_final_pairs) {
+    const mh_pairs_out none{};
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < np; i++) {
+      uint64_t c = 0;
+      if (pairs[i].scan->n)
+        MH_TRY(compact_pairs_of(ctx, tab->d[i].pair_gidx, tab->d[i].pair_q, pairs[i].scan->n, final_pairs ? &final_pairs[i] : &none,
+                                final_pairs ? pairs_mem : MH_MEM_DEVICE, &c));
+      if (final_pair_counts) final_pair_counts[i] = c;
+      sum += c;
+    }
+    if (sum != res->n_final_pairs)
+      return fail(MH_ERR_INTERNAL, "pair compaction count mismatch: %llu pairings in the buffers, %u in the last accumulation",
+                  (unsigned long long)sum, res->n_final_pairs);
+  }
+  return MH_OK;
+}

@@ -102,7 +102,7 @@ static_assert(sizeof(MapSlot) == 16, "slot must be one dwordx4");
 constexpr unsigned long long kEmptyKey = ~0ull;
 constexpr int kKeyBias = 1 << 20;
 
-struct MapView {
+struct MapView {  // (k_match_layers, mh_k_layers.h, copies it field by field: keep that copy in step)
   const MapSlot* slots;
   const float4* pts;  // {x,y,z, bit-cast source index}, voxel-contiguous
   uint32_t mask;      // table_size - 1
@@ -187,6 +187,11 @@ struct mh_ctx {
   hipEvent_t ev_pairs_ready = nullptr, ev_pairs_copied = nullptr;
   bool pairs_copy_pending = false;
   mh::DevBuf pairs_stage;  // compacted pairings of all jobs of a batch
+  mh::DevBuf layers_pairs;  // mh_icp_align_layers: a segment of pairing buffers per pair
+  mh::DevBuf layers_tab;    // ... its descriptor table + threshold schedules
+  void* h_layers = nullptr; // ... their pinned mirror
+  size_t h_layers_cap = 0;
+  uint32_t layers_predicted = 0;  // iterations its previous alignment ran (size of the first chunk)
   // profiling events for the match kernel (pairs), created lazily
   hipEvent_t* prof_ev = nullptr;
   uint32_t prof_cap = 0;

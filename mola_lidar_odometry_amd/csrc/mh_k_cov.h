@@ -88,18 +88,18 @@ __device__ __forceinline__ void k_cov_accum_body(const IcpDeviceState* __restric
                                                       const float* __restrict__ lx, const float* __restrict__ ly,
                                                       const float* __restrict__ lz, uint32_t n,
                                                       const uint32_t* __restrict__ pair_gidx,
-                                                      double* __restrict__ partials, uint32_t pstride) {
+                                                      double* __restrict__ partials, uint32_t pstride, uint32_t block_x) {
   __shared__ double sD[72];
   __shared__ BlockSum<kCovN> lds;
   if (!force && (!st->done || st->cov_done)) return;
   if (threadIdx.x < 72) sD[threadIdx.x] = st->covD[threadIdx.x];
   __syncthreads();
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t i = block_x * kBlock + threadIdx.x;
   double v[kCovN];
 #pragma unroll
   for (int j = 0; j < kCovN; j++) v[j] = 0.0;
   if (i < n && pair_gidx[i] != kNoMatch) cov_rows_point(sD, lx[i], ly[i], lz[i], v);
-  block_sum_rows<kCovN>(v, lds, partials, pstride, blockIdx.x);
+  block_sum_rows<kCovN>(v, lds, partials, pstride, block_x);
 }
 
 __global__ __launch_bounds__(kBlock) void k_cov_accum_pl(const IcpDeviceState* __restrict__ st,

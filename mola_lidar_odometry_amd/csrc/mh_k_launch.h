@@ -128,12 +128,12 @@ __global__ __launch_bounds__(kBlock) void k_cov_accum(const IcpDeviceState* __re
                                                       const float* __restrict__ lz, uint32_t n,
                                                       const uint32_t* __restrict__ pair_gidx,
                                                       double* __restrict__ partials, uint32_t pstride) {
-  k_cov_accum_body(st, force, lx, ly, lz, n, pair_gidx, partials, pstride);
+  k_cov_accum_body(st, force, lx, ly, lz, n, pair_gidx, partials, pstride, blockIdx.x);
 }
 __global__ __launch_bounds__(kBlock) void k_cov_accum_b(const BatchJob* __restrict__ jobs) {
   const BatchJob& j = jobs[blockIdx.y];
   if (blockIdx.x >= j.nb) return;
-  k_cov_accum_body(j.st, 0u, j.lx, j.ly, j.lz, j.n, j.pair_gidx, j.part, j.nb);
+  k_cov_accum_body(j.st, 0u, j.lx, j.ly, j.lz, j.n, j.pair_gidx, j.part, j.nb, blockIdx.x);
 }
 __global__ __launch_bounds__(kSolveThreads) void k_cov_finalize(IcpDeviceState* __restrict__ st, uint32_t force,
                                                                 const double* __restrict__ partA, uint32_t nA,

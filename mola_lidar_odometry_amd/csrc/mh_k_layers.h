@@ -1,0 +1,100 @@
+// mh_k_layers.h -- mh_icp_align_layers: one alignment over several (map, scan) point-layer pairs (lidar3d-dual-map.yaml,
+// lidar3d-edges.yaml).  Every pair has a descriptor in a device-resident table; all pairs share ONE IcpDeviceState and their
+// partial sums feed ONE k_solve.  The entry points walk a flattened block range: pair i owns the workgroups
+// [blk_*[i], blk_*[i + 1]) of each launch.  (Chosen over a blockIdx.y grid -- one row of workgroups per pair, sized by the largest
+// pair, the rest exiting at once -- by reasoning, NOT measured: the dual-map scans differ in size several times over, so such a
+// grid launches workgroups that do nothing.)  The bodies are the single alignment's, unchanged:
+//   k_match_layers    match_flat_wave (the plan / scan search of k_match_flat) with the pair's own threshold and angular term
+//   k_accum_layers    k_accum_body<true> with the pair's MatchK (its weight), into its columns of the shared partials
+//   k_cov_accum_layers  k_cov_accum_body over the pair's pairings, into its columns of the covariance partials
+// k_solve / k_cov_prepare / k_cov_finalize are launched as they are over all columns (fixed order: bitwise reproducible).
+#pragma once
+
+struct LayerDesc {
+  MapView map;
+  const float *lx, *ly, *lz;
+  float4* pair_q;       // this pair's segment of the pairing buffers (a shared scan is paired again for every pair)
+  uint32_t* pair_gidx;
+  MatchK mk;            // thr: this pair's threshold schedule; ang2; kernel; w_pt2pt: this pair's weight
+  uint32_t n;
+  uint32_t col_off;     // first column of its k_accum partials
+  uint32_t cov_off;     // first column of its covariance partials
+  uint32_t pad;
+};
+
+struct LayerTable {
+  uint32_t n_pairs, pad;
+  uint32_t blk_match[MH_MAX_LAYER_PAIRS + 1];  // first workgroup of each pair in the flattened grids (+ the total)
+  uint32_t blk_acc[MH_MAX_LAYER_PAIRS + 1];
+  uint32_t blk_cov[MH_MAX_LAYER_PAIRS + 1];
+  LayerDesc d[MH_MAX_LAYER_PAIRS];
+};
+
+typedef const LayerTable __attribute__((address_space(4))) * clayers_ptr;
+
+// the pair that owns workgroup b: the last one whose range starts at or before b (pairs without points own no workgroup)
+__device__ __forceinline__ uint32_t layer_of(const uint32_t __attribute__((address_space(4))) * start, uint32_t np, uint32_t b) {
+  uint32_t li = 0;
+  for (uint32_t k = 1; k < np; k++) li += b >= start[k] ? 1u : 0u;
+  return li;
+}
+
+__global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_layers(const IcpDeviceState* __restrict__ st,
+                                                                               const LayerTable* __restrict__ tab) {
+  __shared__ FlatWave sh[kFlatThreads / 64];
+  typedef const IcpDeviceState __attribute__((address_space(4))) * cstate_ptr;
+  const cstate_ptr cst = (cstate_ptr)uniform_const_ptr(st);
+  if (cst->done) return;  // grid-uniform
+  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
+  const uint32_t li = layer_of(ct->blk_match, ct->n_pairs, blockIdx.x);
+  const uint32_t n = ct->d[li].n;
+  const uint32_t i0 = (blockIdx.x - ct->blk_match[li]) * kFlatPointsPerBlock + (threadIdx.x & ~63u);
+  if (i0 >= n) return;    // whole waves
+  // field by field: scalar loads through the constant-space table (a MapView field added in mh_internal.h has to be added here:
+  // the static_assert below fails until it is)
+#ifdef MH_DEBUG_WAVETRACE
+  static_assert(sizeof(MapView) == 56, "MapView changed: copy the new field in k_match_layers");
+#else
+  static_assert(sizeof(MapView) == 48, "MapView changed: copy the new field in k_match_layers");
+#endif
+  MapView map;
+  map.slots = ct->d[li].map.slots;
+  map.pts = ct->d[li].map.pts;
+  map.mask = ct->d[li].map.mask;
+  map.inv_vs = ct->d[li].map.inv_vs;
+  map.vs = ct->d[li].map.vs;
+  map.trunc = ct->d[li].map.trunc;
+  map.ndt = ct->d[li].map.ndt;
+  map.no_prev_bound = ct->d[li].map.no_prev_bound;
+  map.pts_q = ct->d[li].map.pts_q;
+#ifdef MH_DEBUG_WAVETRACE
+  map.dbg_stop = ct->d[li].map.dbg_stop;
+#endif
+  const uint32_t iter = cst->iter;
+  const bool have_prev = iter > 0 && !map.no_prev_bound;
+  double T[12];
+#pragma unroll
+  for (int k = 0; k < 12; k++) T[k] = cst->T[k];
+  const double thr = G(ct->d[li].mk.thr)[iter];
+  const float thr2 = (float)(thr * thr);  // what k_solve leaves in cur_thr2 for a single alignment
+  match_flat_wave(sh[threadIdx.x >> 6], map, T, thr2, ct->d[li].mk.ang2, have_prev, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz,
+                  n, i0, ct->d[li].pair_q, ct->d[li].pair_gidx, nullptr);
+}
+
+__global__ __launch_bounds__(kBlock, MH_ACCUM_WAVES) void k_accum_layers(const IcpDeviceState* __restrict__ st,
+                                                                         const LayerTable* __restrict__ tab, uint32_t first,
+                                                                         double* __restrict__ partials, uint32_t pstride) {
+  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
+  const uint32_t li = layer_of(ct->blk_acc, ct->n_pairs, blockIdx.x);
+  k_accum_body<true>(st, first, &tab->d[li].mk, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n, ct->d[li].pair_q,
+                     ct->d[li].pair_gidx, partials + ct->d[li].col_off, pstride, blockIdx.x - ct->blk_acc[li]);
+}
+
+__global__ __launch_bounds__(kBlock) void k_cov_accum_layers(const IcpDeviceState* __restrict__ st,
+                                                             const LayerTable* __restrict__ tab, double* __restrict__ partials,
+                                                             uint32_t pstride) {
+  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
+  const uint32_t li = layer_of(ct->blk_cov, ct->n_pairs, blockIdx.x);
+  k_cov_accum_body(st, 0u, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n, ct->d[li].pair_gidx,
+                   partials + ct->d[li].cov_off, pstride, blockIdx.x - ct->blk_cov[li]);
+}

@@ -12,6 +12,7 @@
 #include <mrpt/maps/CPointsMap.h>
 #include <mrpt/poses/CPose3D.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -192,8 +193,9 @@ class DeviceSession
         return mir.map;
     }
 
-    /** The local layer on the device (created on first use, refilled every call: the layer changes every scan). */
-    mh_scan* upload(const mrpt::maps::CPointsMap& local)
+    /** The local layer on the device (created on first use, refilled every call: the layer changes every scan).  `keep`: other
+     *  layers whose scans the caller still holds (a multi-layer alignment uploads several) -- never evicted here. */
+    mh_scan* upload(const mrpt::maps::CPointsMap& local, const std::vector<const mrpt::maps::CPointsMap*>* keep = nullptr)
     {
         const auto& lx = local.getPointsBufferRef_x();  // already SoA [U]
         const auto& ly = local.getPointsBufferRef_y();
@@ -204,7 +206,9 @@ class DeviceSession
         if (scans_.size() > 16)  // host layers come and go (one per observation): keep the table from growing
         {
             for (auto it = scans_.begin(); it != scans_.end();)
-                if (it->first != &local) { mh_scan_destroy(it->second); it = scans_.erase(it); } else ++it;
+                if (it->first != &local && !(keep && std::find(keep->begin(), keep->end(), it->first) != keep->end()))
+                { mh_scan_destroy(it->second); it = scans_.erase(it); }
+                else ++it;
         }
         return scans_[&local];
     }

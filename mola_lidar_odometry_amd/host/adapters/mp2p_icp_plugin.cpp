@@ -26,7 +26,14 @@
 //   lidar3d-default.yaml:184-204   one Solver_GaussNewton, matchers = [Matcher_Points_DistanceThreshold]
 //   lidar3d-ndt.yaml:184-210       one Solver_GaussNewton, matchers = [Matcher_Point2Plane, Matcher_Points_DistanceThreshold]
 // both with one {global, local, weight} entry in pointLayerMatches (yaml :203-204; the point matcher's weight may differ from 1
-// since round 5), pairingsPerPoint 1.
+// since round 5), pairingsPerPoint 1.  And, through mh_icp_align_layers, several point-layer pairs in one solve:
+//   extras/lidar3d-dual-map.yaml:115-132   one Solver_GaussNewton, two Matcher_Points_DistanceThreshold on two layer pairs
+//   extras/lidar3d-edges.yaml:120-129      one Solver_GaussNewton, one Matcher_Points_DistanceThreshold with two entries
+// i.e. only ungated, enabled point matchers (pairingsPerPoint 1, allowMatchAlreadyMatchedGlobalPoints), 2 to MH_MAX_LAYER_PAIRS
+// {global, local} entries in all, each with its own threshold schedule, angular term and weight; pairs in upstream's matching
+// order (matchers in list order, then weight_pt2pt_layers' std::map order: global name, then local name).  A local layer named by
+// two entries is paired again for each unless allowMatchAlreadyMatchedPoints is false and MOLA_HIP_MATCHED_POINTS=skip (then the
+// upstream loop runs).  Gated blocks (extras/lidar3d-near-far.yaml) go to the upstream loop.
 // Global layers read: mola::HashedVoxelPointCloud (yaml:230), mola::NDT (ndt yaml:236) -- through their point / voxel
 // visitors, they are NOT mrpt::maps::CPointsMap --, mola::HashedVoxelPointCloudHIP (device owned, no mirror), and any
 // CPointsMap (pipelines/extras/localmap_definition_pointmap.ini).
@@ -111,6 +118,21 @@ struct Shape
     double ptLayerWeight = 1.0;  // pointLayerMatches {..., weight} of the point matcher (yaml:203-204)
 };
 
+/** The multi-pair shape (mh_icp_align_layers): one entry per {global, local} pair, in upstream's matching order. */
+struct LayerShape
+{
+    struct Entry
+    {
+        const Matcher_Points_DistanceThreshold* m = nullptr;
+        size_t      matcher = 0;  // index into LayerShape::matchers (its threshold schedule)
+        std::string globalLayer, localLayer;
+        double      weight = 1.0;
+    };
+    std::vector<const Matcher_Points_DistanceThreshold*> matchers;
+    const Solver_GaussNewton* gn = nullptr;
+    std::vector<Entry> entries;
+};
+
 template <class M> bool single_unit_layer(const M& m, std::string& g, std::string& l, double* weight_out = nullptr)
 {
     if (m.weight_pt2pt_layers.size() != 1) return false;                     // [U] {global -> {local -> weight}}
@@ -145,6 +167,9 @@ class ICP_HIP : public ICP
         // (set at LidarOdometry.cpp:360-364) itself before it writes the .icplog.
         Shape sh;
         mh_map* dmap = nullptr;
+        LayerShape ls;
+        if (!sw.force_cpu && !p.generateDebugFiles && !recognise(sh) && recognise_layers(ls))
+            return align_layers(ls, pcLocal, pcGlobal, initialGuessLocalWrtGlobal, p, result, prior, outputDebugInfo);
         if (sw.force_cpu || p.generateDebugFiles || !recognise(sh) || !pcLocal.layers.count(sh.localLayer) || !pcGlobal.layers.count(sh.globalLayer))
             return upstream_align(pcLocal, pcGlobal, initialGuessLocalWrtGlobal, p, result, prior, outputDebugInfo);
         if (!dev_) dev_ = std::make_unique<molahip_mrpt::DeviceSession>();
@@ -350,6 +375,186 @@ class ICP_HIP : public ICP
         return single_unit_layer(*sh.pt, sh.globalLayer, sh.localLayer, &sh.ptLayerWeight);
     }
 
+    /** Does the configured pipeline have the multi-pair shape of the file header? */
+    bool recognise_layers(LayerShape& ls) const
+    {
+        if (solvers().size() != 1 || !(ls.gn = dynamic_cast<const Solver_GaussNewton*>(solvers()[0].get()))) return false;
+        bool skip_paired = false;  // some matcher leaves points an earlier one paired out (U12, MOLA_HIP_MATCHED_POINTS=skip)
+        for (const auto& mp : matchers())
+        {
+            const auto* m = dynamic_cast<const Matcher_Points_DistanceThreshold*>(mp.get());
+            if (!m || !m->enabled || m->runFromIteration != 0 || m->runUpToIteration != 0 || m->pairingsPerPoint != 1 ||
+                !m->allowMatchAlreadyMatchedGlobalPoints)
+                return false;
+            if (!m->allowMatchAlreadyMatchedPoints_ && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP)
+                skip_paired = true;
+            ls.matchers.push_back(m);
+            for (const auto& [gname, locals] : m->weight_pt2pt_layers)  // [U] std::map: global name, then local name
+                for (const auto& [lname, w] : locals)
+                {
+                    LayerShape::Entry e;
+                    e.m = m;
+                    e.matcher = ls.matchers.size() - 1;
+                    e.globalLayer = gname;
+                    e.localLayer = lname;
+                    e.weight = w;
+                    ls.entries.push_back(e);
+                }
+        }
+        if (ls.entries.size() < 2 || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
+        for (size_t i = 0; i < ls.entries.size(); i++)
+            for (size_t j = i + 1; j < ls.entries.size(); j++)
+                if (skip_paired && ls.entries[i].localLayer == ls.entries[j].localLayer) return false;
+        return true;
+    }
+
+    /** The multi-pair shape on the device (mh_icp_align_layers); an unreadable layer sends the call to the upstream loop. */
+    void align_layers(const LayerShape& ls, const metric_map_t& pcLocal, const metric_map_t& pcGlobal, const mrpt::math::TPose3D& guess,
+                      const Parameters& p, Results& result, const std::optional<mrpt::poses::CPose3DPDFGaussianInf>& prior,
+                      const mrpt::optional_ref<LogRecord>& outputDebugInfo)
+    {
+        const auto& sw = molahip_host::plugin_switches();
+        for (const auto& e : ls.entries)
+            if (!pcLocal.layers.count(e.localLayer) || !pcGlobal.layers.count(e.globalLayer))
+                return upstream_align(pcLocal, pcGlobal, guess, p, result, prior, outputDebugInfo);
+        if (!dev_) dev_ = std::make_unique<molahip_mrpt::DeviceSession>();
+        const size_t np = ls.entries.size();
+        std::vector<const mrpt::maps::CPointsMap*> locals(np);
+        std::vector<mh_layer_pair> pairs(np);
+        for (size_t i = 0; i < np; i++)
+        {
+            const auto& e = ls.entries[i];
+            mh_map* m = dev_->device_map_of(*pcGlobal.layers.at(e.globalLayer), false);  // every global layer mirrored
+            locals[i] = dynamic_cast<const mrpt::maps::CPointsMap*>(pcLocal.layers.at(e.localLayer).get());
+            if (!m || !locals[i]) return upstream_align(pcLocal, pcGlobal, guess, p, result, prior, outputDebugInfo);
+            pairs[i].map = m;
+            pairs[i].threshold_angular_deg = e.m->thresholdAngularDeg;
+            pairs[i].weight = e.weight;  // Pairings::point_weights [U]: the entry's own weight
+        }
+        for (size_t i = 0; i < np; i++)  // every local layer uploaded (a layer named twice: once)
+        {
+            size_t first = i;
+            for (size_t j = 0; j < i; j++) if (locals[j] == locals[i]) { first = j; break; }
+            pairs[i].scan = first == i ? dev_->upload(*locals[i], &locals) : pairs[first].scan;
+        }
+        mrpt::system::CTimeLoggerEntry tle(profiler(), "align_hip");
+
+        // every matcher's threshold and the solver's kernel parameter per ICP_ITERATION, lazily as in align()
+        std::vector<std::vector<double>> thr(ls.matchers.size());
+        std::vector<double> kp;
+        auto ensure_schedule = [&](uint32_t upto) {
+            for (uint32_t k = static_cast<uint32_t>(kp.size()); k < upto; k++)
+            {
+                for (auto* src : attachedSources()) { src->updateVariable("ICP_ITERATION", k); src->realize(); }  // [U]
+                for (size_t j = 0; j < ls.matchers.size(); j++) thr[j].push_back(ls.matchers[j]->threshold);
+                kp.push_back(ls.gn->robustKernelParam);
+            }
+        };
+        constexpr uint32_t kScheduleFirstStage = 48;
+        mh_icp_params ip{};
+        ip.max_iterations        = p.maxIterations;
+        ip.min_abs_step_trans    = p.minAbsStep_trans;
+        ip.min_abs_step_rot      = p.minAbsStep_rot;
+        ip.matched_points        = MH_MATCHED_POINTS_PAIR_AGAIN;  // (recognise_layers: the skip case stays upstream)
+        ip.gn.max_inner_iterations = ls.gn->maxIterations;
+        const std::string kname = mrpt::typemeta::TEnumType<RobustKernel>::value2name(ls.gn->robustKernel);  // [U]
+        ip.gn.robust_kernel      = molahip_host::kernel_from_upstream_name(kname.c_str(), sw);
+        ip.gn.min_delta          = sw.min_delta;
+        ip.gn.max_cost           = sw.max_cost;
+        ip.compute_covariance    = 1;
+        ip.cov_findif_xyz        = sw.cov_step_xyz;
+        ip.cov_findif_ang        = sw.cov_step_ang;
+        double T0[12];
+        pose_to_T12(mrpt::poses::CPose3D(guess), T0);
+        mh_prior pr;
+        if (prior)
+        {
+            pose_to_T12(prior->mean, pr.mean);
+            for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) pr.info[i * 6 + j] = prior->cov_inv(i, j);
+        }
+        if (layer_pairs_.size() < np) layer_pairs_.resize(np);
+        std::vector<mh_pairs_out> po(np);
+        std::vector<uint64_t> counts(np, 0);
+        size_t n_local = 0;
+        for (size_t i = 0; i < np; i++)
+        {
+            po[i] = layer_pairs_[i].out(locals[i]->getPointsBufferRef_x().size());
+            n_local += locals[i]->getPointsBufferRef_x().size();
+        }
+        auto run_with = [&](uint32_t budget, mh_icp_iter* trace) {
+            ensure_schedule(budget);
+            for (size_t i = 0; i < np; i++) pairs[i].threshold = thr[ls.entries[i].matcher].data();
+            mh_icp_params q = ip;
+            q.max_iterations = budget;
+            q.kernel_param   = kp.data();
+            mh_icp_result rr{};
+            mh_check(mh_icp_align_layers(np, pairs.data(), &q, T0, prior ? &pr : nullptr, &rr, trace, po.data(), counts.data(),
+                                         MH_MEM_HOST), "mh_icp_align_layers");
+            return rr;
+        };
+        auto run = [&](uint32_t budget, mh_icp_iter* trace) {
+            uint32_t stage = kScheduleFirstStage;
+            if (last_iterations_ + 16u > stage) stage = last_iterations_ + 16u;
+            const uint32_t first = budget < stage ? budget : stage;
+            mh_icp_result rr = run_with(first, trace);
+            if (first < budget && rr.termination_reason == MH_TERM_MAX_ITERATIONS) rr = run_with(budget, trace);  // rare
+            return rr;
+        };
+        mh_icp_result r{};
+        if (iteration_hook_)  // the opaque hook, replayed on the traced poses as in align()
+        {
+            auto hook = [&](uint32_t k, const double* T) {
+                mrpt::math::CMatrixDouble44 Mk = mrpt::math::CMatrixDouble44::Identity();
+                for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) Mk(i, j) = T[i * 4 + j];
+                OptimalTF_Result cur;
+                cur.optimalPose = mrpt::poses::CPose3D(Mk);
+                IterationHook_Input in;
+                in.currentIteration = k;
+                in.currentSolution  = &cur;
+                in.pcGlobal = &pcGlobal;
+                in.pcLocal  = &pcLocal;
+                return iteration_hook_(in).request_stop;
+            };
+            r = molahip_host::align_with_replayed_hook(p.maxIterations, run, hook);
+        }
+        else
+            r = run(p.maxIterations, nullptr);
+        last_iterations_ = r.n_iterations;
+        {
+            const uint32_t last_k = r.n_iterations ? r.n_iterations - 1u : 0u;
+            for (auto* src : attachedSources()) { src->updateVariable("ICP_ITERATION", last_k); src->realize(); }  // [U]
+        }
+        mrpt::math::CMatrixDouble44 M = mrpt::math::CMatrixDouble44::Identity();
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 4; j++) M(i, j) = r.T[i * 4 + j];
+        result.optimal_tf.mean = mrpt::poses::CPose3D(M);
+        for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) result.optimal_tf.cov(i, j) = r.cov[i * 6 + j];
+        result.quality           = r.quality;
+        result.nIterations       = r.n_iterations;
+        result.terminationReason = molahip_host::term_reason_to<IterTermReason>(r.termination_reason);
+        result.finalPairings     = Pairings();
+        result.finalPairings.potential_pairings = r.potential_pairings;
+        result.finalPairings.paired_pt2pt.reserve(r.n_final_pairs);
+        for (size_t i = 0; i < np; i++)  // pair by pair, in matching order (each pair's in ascending local index)
+        {
+            const auto& lx = locals[i]->getPointsBufferRef_x();
+            const auto& ly = locals[i]->getPointsBufferRef_y();
+            const auto& lz = locals[i]->getPointsBufferRef_z();
+            const auto& b = layer_pairs_[i];
+            for (uint64_t k = 0; k < counts[i]; k++)
+            {
+                mrpt::tfest::TMatchingPair mp;
+                mp.globalIdx = b.gi[k];
+                mp.localIdx  = b.li[k];
+                mp.global    = {b.gx[k], b.gy[k], b.gz[k]};
+                mp.local     = {lx[b.li[k]], ly[b.li[k]], lz[b.li[k]]};
+                mp.errorSquareAfterTransformation = b.d2[k];
+                result.finalPairings.paired_pt2pt.push_back(mp);
+            }
+        }
+        trace_.row("hip-layers", n_local, result);
+    }
+
+    std::vector<molahip_mrpt::DeviceSession::PairBuffers> layer_pairs_;  // align_layers: result arrays per pair
     std::unique_ptr<molahip_mrpt::DeviceSession> dev_;  // context, map mirrors, staging scan, result buffers
     uint32_t last_iterations_ = 0;  // nIterations of the previous align(): sizes the first stage of the lazy threshold schedule
     AlignTrace trace_;

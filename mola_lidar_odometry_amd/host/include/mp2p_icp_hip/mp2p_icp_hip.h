@@ -207,6 +207,7 @@ class DevicePointCloud : public Layer {
   void setTimestamps(const float* t, size_t n);
   void boundingBox(float mn[3], float mx[3]) const;
   void download(std::vector<float>& x, std::vector<float>& y, std::vector<float>& z) const;
+  const std::shared_ptr<DeviceContext>& context() const { return ctx_; }
 
  private:
   std::shared_ptr<DeviceContext> ctx_;
@@ -254,7 +255,8 @@ struct Pairings {  // mp2p_icp::Pairings::paired_pt2pt as SoA (+ pt2pl)
   std::vector<float> pl_lx, pl_ly, pl_lz, pl_cx, pl_cy, pl_cz, pl_nx, pl_ny, pl_nz;
   size_t potential_pairings = 0;
   // role of Pairings::point_weights [U]: the `weight` of the pointLayerMatches entry that produced the point pairs (yaml:203-204).
-  // The device solver takes ONE weight per kind of pair: layers with different weights in one pairing set are refused.
+  // The device solver takes ONE weight per kind of pair: layers with different weights in one pairing set are refused here
+  // (the matcher-granular path).  The fused multi-layer path (mh_icp_align_layers) takes a weight per pair and accepts them.
   double pt2pt_weight = 1.0, pt2pl_weight = 1.0;
   bool pt2pt_weight_set = false, pt2pl_weight_set = false;
   // role of MatchState::localPairedBitField [U]: per local layer, which points the matchers of THIS iteration have paired so
@@ -540,12 +542,20 @@ class ICP {
   // false: Results::finalPairings stays empty in the fused path (the odometry driver never reads it)
   void setKeepFinalPairings(bool v) { keep_pairings_ = v; }
   void forceGenericPath(bool v) { force_generic_ = v; }
-  // evaluate the per-iteration thresholds of the fused path NOW, on the variables' current values; the next align()
+  // the path align() takes for the configured pipeline (no alignment): "single" (mh_icp_align: lidar3d-default / -ndt shapes),
+  // "layers" (mh_icp_align_layers: several point-layer pairs, lidar3d-dual-map / -edges shapes) or "generic" (matcher by matcher).
+  // "layers" also needs the maps handed to align() to qualify (global layers HashedVoxelPointCloud on one context, local layers
+  // PointCloud / DevicePointCloud); otherwise that call runs the generic loop.
+  std::string alignPath() const;
+  // evaluate the per-iteration thresholds of the fused paths (single or multi-layer) NOW, on the variables' current values; the next align()
   // re-uses them if the variables its formulas read still have these values (anything else: evaluated again, as before)
   void precomputeSchedule(uint32_t n_iterations);
 
  private:
   bool can_fuse() const;
+  bool can_fuse_layers() const;
+  void align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pcGlobal, const CPose3D& guess, const Parameters& p,
+                          Results& result, const std::optional<CPose3DPDFGaussianInf>& prior);
   void align_fused(const PointCloud* local, const DevicePointCloud* dev_local, const HashedVoxelPointCloud& global,
                    const CPose3D& guess, const Parameters& p, Results& result,
                    const std::optional<CPose3DPDFGaussianInf>& prior);
@@ -558,6 +568,13 @@ class ICP {
     std::vector<double> key;  // values of the variables the formulas read (ICP_ITERATION = 0)
     std::vector<double> thr, kp, plthr;
   } sched_;
+  void prepare_layer_schedule(uint32_t n_iterations);  // the same for align_fused_layers: a threshold schedule per matcher
+  struct LayerSchedule {
+    bool valid = false;
+    std::vector<double> key;
+    std::vector<std::vector<double>> thr;  // [matcher][iteration]
+    std::vector<double> kp;
+  } layer_sched_;
 
   std::shared_ptr<DeviceContext> ctx_;
   std::vector<Matcher::Ptr> matchers_;
@@ -571,6 +588,7 @@ class ICP {
   ParameterSource own_source_;
   mh_scan* scan_ = nullptr;                 // staging layer for host point clouds handed to the fused path ...
   std::shared_ptr<DeviceContext> scan_ctx_;  // ... and the (map's) context it lives in, kept alive until ~ICP has destroyed it
+  std::map<std::string, mh_scan*> layer_scans_;  // align_fused_layers: a staging layer per host local layer (in scan_ctx_)
   bool last_fused_ = false, force_generic_ = false, keep_pairings_ = true, hook_replay_ = false;
   std::shared_ptr<AlignBatcher> batcher_;
   const void* batch_owner_ = nullptr;

@@ -337,6 +337,7 @@ void Matcher_Points_DistanceThreshold::impl_match(const metric_map_t& pcGlobal, 
     const HashedVoxelPointCloud& glob = global_layer(pcGlobal, lm.global);
     const size_t n = loc.size();
     out.potential_pairings += n * pairingsPerPoint;
+    // (the fused multi-layer path, ICP::align_fused_layers, takes a weight per pair; this matcher-granular path keeps its refusal)
     if (out.pt2pt_weight_set && out.pt2pt_weight != lm.weight)
       throw std::runtime_error("pointLayerMatches with different weights in one pairing set: not a device input (one weight per kind of pair)");
     out.pt2pt_weight = lm.weight;
@@ -524,6 +525,7 @@ Solver::Ptr create_solver(const std::string& cn) {
 ICP::ICP(std::shared_ptr<DeviceContext> ctx) : ctx_(std::move(ctx)) {}
 ICP::~ICP() {
   if (scan_) mh_scan_destroy(scan_);
+  for (auto& e : layer_scans_) mh_scan_destroy(e.second);
 }
 
 void ICP::setDeviceHook(double min_trans, double min_rot_rad, const CPose3D& checkpoint) {
@@ -588,6 +590,59 @@ bool ICP::can_fuse() const {
     if (a.global != b.global || a.local != b.local) return false;
   }
   return true;
+}
+
+// several point-layer pairs in one solve (lidar3d-dual-map.yaml:115-132, lidar3d-edges.yaml:120-129): one Solver_GaussNewton, only
+// enabled, ungated Matcher_Points_DistanceThreshold with pairingsPerPoint 1 that may match already matched global points, 2 to
+// MH_MAX_LAYER_PAIRS entries in all.  A local layer named by two entries is paired again for each: only under
+// MOLA_HIP_MATCHED_POINTS=again (skip would leave the second entry's points out, which mh_icp_align_layers does not do).
+bool ICP::can_fuse_layers() const {
+  if (force_generic_ || iteration_hook_) return false;
+  if (matchers_.empty() || solvers_.size() != 1 || !std::dynamic_pointer_cast<Solver_GaussNewton>(solvers_[0])) return false;
+  std::vector<std::string> locals;
+  for (const auto& mm : matchers_) {
+    auto m = std::dynamic_pointer_cast<Matcher_Points_DistanceThreshold>(mm);
+    if (!m || !m->enabled || m->runFromIteration || m->runUpToIteration || m->pairingsPerPoint != 1 ||
+        !m->allowMatchAlreadyMatchedGlobalPoints)
+      return false;
+    for (const auto& lm : m->pointLayerMatches) locals.push_back(lm.local);
+  }
+  if (locals.size() < 2 || locals.size() > MH_MAX_LAYER_PAIRS) return false;
+  std::sort(locals.begin(), locals.end());
+  const bool shared = std::adjacent_find(locals.begin(), locals.end()) != locals.end();
+  return !(shared && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP);
+}
+
+std::string ICP::alignPath() const {
+  if (can_fuse()) return "single";
+  if (can_fuse_layers()) return "layers";
+  return "generic";
+}
+
+// the layers align_fused_layers needs: every global one a HashedVoxelPointCloud on the first one's context, every local one a
+// PointCloud or a DevicePointCloud
+static bool layer_inputs_ok(const std::vector<Matcher::Ptr>& matchers, const metric_map_t& pcLocal, const metric_map_t& pcGlobal) {
+  const DeviceContext* ctx = nullptr;
+  for (const auto& mm : matchers)
+    for (const auto& lm : std::static_pointer_cast<Matcher_Points_DistanceThreshold>(mm)->pointLayerMatches) {
+      auto g = pcGlobal.layers.find(lm.global);
+      auto l = pcLocal.layers.find(lm.local);
+      if (g == pcGlobal.layers.end() || l == pcLocal.layers.end()) return false;
+      auto hv = std::dynamic_pointer_cast<HashedVoxelPointCloud>(g->second);
+      if (!hv || (ctx && hv->context().get() != ctx)) return false;
+      ctx = hv->context().get();
+      // mh_icp_align_layers refuses a map of 2^30 or more records (records = points + two per voxel at most)
+      mh_map_info info{};
+      if (mh_map_get_info(hv->handle(), &info) != MH_OK || info.n_points + 2 * info.n_voxels >= (1ull << 30)) return false;
+      if (!std::dynamic_pointer_cast<PointCloud>(l->second) && !std::dynamic_pointer_cast<DevicePointCloud>(l->second)) return false;
+    }
+  // ... and maps and scans on more than one context: a device local layer has to live on the maps' one
+  for (const auto& mm : matchers)
+    for (const auto& lm : std::static_pointer_cast<Matcher_Points_DistanceThreshold>(mm)->pointLayerMatches) {
+      auto dev = std::dynamic_pointer_cast<DevicePointCloud>(pcLocal.layers.find(lm.local)->second);
+      if (dev && dev->context().get() != ctx) return false;
+    }
+  return ctx != nullptr;
 }
 
 // ---------------------------------------------------------------- AlignBatcher
@@ -900,6 +955,9 @@ void ICP::align(const metric_map_t& pcLocal, const metric_map_t& pcGlobal, const
     auto dev = it != pcLocal.layers.end() ? std::dynamic_pointer_cast<DevicePointCloud>(it->second) : nullptr;
     align_fused(dev ? nullptr : &local_layer(pcLocal, lname), dev.get(), global_layer(pcGlobal, m->pointLayerMatches[0].global),
                 g, p, result, prior);
+  } else if (can_fuse_layers() && layer_inputs_ok(matchers_, pcLocal, pcGlobal)) {
+    last_fused_ = true;
+    align_fused_layers(pcLocal, pcGlobal, g, p, result, prior);
   } else {
     last_fused_ = false;
     align_generic(pcLocal, pcGlobal, g, p, result, prior);
@@ -987,9 +1045,49 @@ void ICP::prepare_schedule(uint32_t n_iterations) {
 }
 
 void ICP::precomputeSchedule(uint32_t n_iterations) {
-  if (!can_fuse() || !n_iterations) return;
-  prepare_schedule(n_iterations);
+  if (!n_iterations) return;
+  if (can_fuse())
+    prepare_schedule(n_iterations);
+  else if (can_fuse_layers())
+    prepare_layer_schedule(n_iterations);
+  else
+    return;
   realize_iteration(0);  // (the members the formulas write are left as align() leaves them)
+}
+
+// prepare_schedule for the multi-layer shapes: every matcher's threshold and the solver's kernel parameter, formulas bound once,
+// one realize per iteration; kept with the values of the variables the formulas read
+void ICP::prepare_layer_schedule(uint32_t n_iterations) {
+  auto s = std::static_pointer_cast<Solver_GaussNewton>(solvers_[0]);
+  std::vector<std::shared_ptr<Matcher_Points_DistanceThreshold>> ms;
+  for (const auto& mm : matchers_) ms.push_back(std::static_pointer_cast<Matcher_Points_DistanceThreshold>(mm));
+  std::map<std::string, double> vars = source_ ? source_->getVariableValues() : own_source_.getVariableValues();
+  double& it_var = vars["ICP_ITERATION"];
+  it_var = 0.0;
+  std::vector<Parameterizable::Binding> bm;
+  for (const auto& m : ms) bm.push_back(m->bind(vars));
+  const auto bs = s->bind(vars);
+  std::vector<double> key;
+  for (const Parameterizable::Binding* b : {&bs})
+    for (const auto& item : b->items)
+      for (const double* v : item.second) key.push_back(*v);
+  for (const auto& b : bm)
+    for (const auto& item : b.items)
+      for (const double* v : item.second) key.push_back(*v);
+  key.push_back((double)ms.size());
+  if (layer_sched_.valid && layer_sched_.key == key && layer_sched_.kp.size() >= n_iterations) return;
+  layer_sched_.valid = false;
+  layer_sched_.key = key;
+  layer_sched_.thr.assign(ms.size(), std::vector<double>(n_iterations, 0.0));
+  layer_sched_.kp.assign(n_iterations, 0.0);
+  for (uint32_t k = 0; k < n_iterations; k++) {
+    it_var = (double)k;
+    for (const auto& b : bm) b.realize();
+    bs.realize();
+    for (size_t j = 0; j < ms.size(); j++) layer_sched_.thr[j][k] = ms[j]->threshold;
+    layer_sched_.kp[k] = s->robustKernelParam;
+  }
+  layer_sched_.valid = true;
 }
 
 void ICP::align_fused(const PointCloud* host_local, const DevicePointCloud* dev_local, const HashedVoxelPointCloud& global,
@@ -1117,6 +1215,132 @@ void ICP::align_fused(const PointCloud* host_local, const DevicePointCloud* dev_
     fp.gy.push_back(gy[k]);
     fp.gz.push_back(gz[k]);
     fp.errSq.push_back(d2[k]);
+  }
+}
+
+// The multi-layer shapes on the device loop (mh_icp_align_layers).  Pairs in align_generic's matching order: matchers in list
+// order, entries in pointLayerMatches order.  Solo alignments (not through the AlignBatcher).
+void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pcGlobal, const CPose3D& guess, const Parameters& p,
+                             Results& result, const std::optional<CPose3DPDFGaussianInf>& prior) {
+  const auto t_setup0 = std::chrono::steady_clock::now();
+  auto s = std::static_pointer_cast<Solver_GaussNewton>(solvers_[0]);
+  std::vector<std::shared_ptr<Matcher_Points_DistanceThreshold>> ms;
+  for (const auto& mm : matchers_) ms.push_back(std::static_pointer_cast<Matcher_Points_DistanceThreshold>(mm));
+  // every matcher's threshold schedule and the solver's kernel parameter (a no-op when precomputeSchedule() ran on the same
+  // values of the variables)
+  const uint32_t mi = p.maxIterations;
+  prepare_layer_schedule(mi ? mi : 1);
+  const std::vector<std::vector<double>>& thr = layer_sched_.thr;
+  const std::vector<double>& kp = layer_sched_.kp;
+  if (mi) realize_iteration(0);
+  mh_icp_params ip{};
+  ip.max_iterations = mi;
+  ip.min_abs_step_trans = p.minAbsStep_trans;
+  ip.min_abs_step_rot = p.minAbsStep_rot;
+  ip.threshold = thr[0].data();  // (not read: every pair carries its own)
+  ip.kernel_param = kp.data();
+  ip.gn = gn_params_of(*s);
+  ip.hook_enabled = dev_hook_ ? 1u : 0u;
+  ip.hook_min_trans = dev_hook_trans_;
+  ip.hook_min_rot = dev_hook_rot_;
+  memcpy(ip.hook_checkpoint, dev_hook_chk_.T, sizeof(ip.hook_checkpoint));
+  ip.compute_covariance = 1;
+  ip.cov_findif_xyz = 1e-7;
+  ip.cov_findif_ang = 1e-7;
+  molahip_host::apply_switches(ip, molahip_host::plugin_switches());
+  if (mi > full_budget_) full_budget_ = mi;
+  const int call_kind = mi < full_budget_ ? 1 : 0;
+  ip.expected_iterations = last_iterations_[call_kind];
+  // the pairs; host local layers are staged in the maps' context, once per layer name
+  struct Entry {
+    const PointCloud* host = nullptr;
+    const DevicePointCloud* dev = nullptr;
+  };
+  std::vector<mh_layer_pair> pairs;
+  std::vector<Entry> entries;
+  const auto& ctx0 = global_layer(pcGlobal, ms[0]->pointLayerMatches[0].global).context();
+  if (scan_ctx_ && scan_ctx_ != ctx0) {
+    for (auto& e : layer_scans_) mh_scan_destroy(e.second);
+    layer_scans_.clear();
+    if (scan_) mh_scan_destroy(scan_);
+    scan_ = nullptr;
+  }
+  scan_ctx_ = ctx0;
+  std::map<std::string, bool> staged;
+  for (size_t j = 0; j < ms.size(); j++)
+    for (const auto& lm : ms[j]->pointLayerMatches) {
+      Entry e;
+      auto it = pcLocal.layers.find(lm.local);
+      e.dev = std::dynamic_pointer_cast<DevicePointCloud>(it->second).get();
+      mh_scan* scan = nullptr;
+      if (e.dev) {
+        scan = e.dev->handle();
+      } else {
+        e.host = &local_layer(pcLocal, lm.local);
+        mh_scan*& st = layer_scans_[lm.local];
+        if (!staged[lm.local]) {
+          const PointCloud& hl = *e.host;
+          if (!st)
+            check(mh_scan_create(ctx0->get(), hl.x.data(), hl.y.data(), hl.z.data(), hl.size(), MH_MEM_HOST, &st), "mh_scan_create");
+          else
+            check(mh_scan_update(st, hl.x.data(), hl.y.data(), hl.z.data(), hl.size(), MH_MEM_HOST), "mh_scan_update");
+          staged[lm.local] = true;
+        }
+        scan = st;
+      }
+      mh_layer_pair lp{};
+      lp.map = global_layer(pcGlobal, lm.global).handle();
+      lp.scan = scan;
+      lp.threshold = thr[j].data();
+      lp.threshold_angular_deg = ms[j]->thresholdAngularDeg;
+      lp.weight = lm.weight;
+      pairs.push_back(lp);
+      entries.push_back(e);
+    }
+  mh_prior pr;
+  if (prior) fill_prior(prior, pr);
+  last_setup_seconds_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup0).count();
+  const bool want_pairs = keep_pairings_;
+  std::vector<std::vector<uint32_t>> li(pairs.size()), gi(pairs.size());
+  std::vector<std::vector<float>> gx(pairs.size()), gy(pairs.size()), gz(pairs.size()), d2(pairs.size());
+  std::vector<mh_pairs_out> po(pairs.size());
+  std::vector<uint64_t> counts(pairs.size(), 0);
+  for (size_t i = 0; want_pairs && i < pairs.size(); i++) {
+    const size_t n = entries[i].dev ? entries[i].dev->size() : entries[i].host->size();
+    li[i].resize(n); gi[i].resize(n); gx[i].resize(n); gy[i].resize(n); gz[i].resize(n); d2[i].resize(n);
+    po[i] = mh_pairs_out{li[i].data(), gi[i].data(), gx[i].data(), gy[i].data(), gz[i].data(), d2[i].data()};
+  }
+  mh_icp_result r{};
+  std::vector<mh_icp_iter> trace(p.generateDebugFiles ? mi : 0);
+  check(mh_icp_align_layers(pairs.size(), pairs.data(), &ip, guess.T, prior ? &pr : nullptr, &r, trace.empty() ? nullptr : trace.data(),
+                            want_pairs ? po.data() : nullptr, counts.data(), MH_MEM_HOST), "mh_icp_align_layers");
+  if (p.generateDebugFiles) write_debug_file(p, guess, r, trace, (size_t)r.potential_pairings);
+  last_iterations_[call_kind] = r.n_iterations + (r.termination_reason == MH_TERM_MAX_ITERATIONS ? 0u : 1u);
+  last_polls_ = r.n_host_polls;
+  last_enqueued_ = r.n_enqueued_iterations;
+  memcpy(result.optimal_tf.mean.T, r.T, sizeof(r.T));
+  memcpy(result.optimal_tf.cov, r.cov, sizeof(r.cov));
+  result.quality = r.quality;
+  result.nIterations = r.n_iterations;
+  result.terminationReason = (IterTermReason)r.termination_reason;
+  Pairings& fp = result.finalPairings;
+  fp.potential_pairings = r.potential_pairings;
+  if (!want_pairs) return;
+  for (size_t i = 0; i < pairs.size(); i++) {
+    PointCloud downloaded;
+    if (entries[i].dev && counts[i]) entries[i].dev->download(downloaded.x, downloaded.y, downloaded.z);
+    const PointCloud& local = entries[i].dev ? downloaded : *entries[i].host;
+    for (uint64_t k = 0; k < counts[i]; k++) {
+      fp.localIdx.push_back(li[i][k]);
+      fp.globalIdx.push_back(gi[i][k]);
+      fp.lx.push_back(local.x[li[i][k]]);
+      fp.ly.push_back(local.y[li[i][k]]);
+      fp.lz.push_back(local.z[li[i][k]]);
+      fp.gx.push_back(gx[i][k]);
+      fp.gy.push_back(gy[i][k]);
+      fp.gz.push_back(gz[i][k]);
+      fp.errSq.push_back(d2[i][k]);
+    }
   }
 }
 

@@ -118,6 +118,8 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("setDeviceHook", &ICP::setDeviceHook)
       .def("clearHooks", &ICP::clearHooks)
       .def("forceGenericPath", &ICP::forceGenericPath)
+      .def("alignPath", &ICP::alignPath)
+      .def("precomputeSchedule", &ICP::precomputeSchedule)
       .def("setHookReplay", &ICP::setHookReplay)
       .def("lastAlignUsedFusedPath", &ICP::lastAlignUsedFusedPath)
       .def("setIterationHook", [](ICP& icp, std::function<bool(uint32_t, std::vector<double>)> f) {

@@ -1,0 +1,116 @@
+"""Milliseconds per alignment of a dual-map-shaped ICP block (pipelines/extras/lidar3d-dual-map.yaml:115-132) on three routes:
+
+  fused     mh_icp_align_layers over both pairs (one device loop)
+  generic   the host layer's matcher-by-matcher loop on the same block (ICP::forceGenericPath)
+  single    mh_icp_align on the larger pair alone (for scale)
+
+The shape: the creal scan split by range into two layers (all points | points within 25 m), the full 1 M-point map and a 2x
+subsampled copy of it.  Each route: median of --reps warmed alignments, host clock around synchronised calls.
+
+    python tools/layers_align_bench.py [--reps 200] [--pairs 2|3]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mola_lidar_odometry_amd import capi, synth  # noqa: E402
+
+_YAML_HEAD = """
+class_name: mp2p_icp::ICP
+params:
+  maxIterations: %d
+  minAbsStep_trans: 1e-4
+  minAbsStep_rot: 5e-5
+solvers:
+  - class: mp2p_icp::Solver_GaussNewton
+    params:
+      maxIterations: 2
+      robustKernel: 'RobustKernel::GemanMcClure'
+      robustKernelParam: '0.5*ADAPTIVE_THRESHOLD_SIGMA'
+matchers:
+"""
+_YAML_MATCHER = """  - class: mp2p_icp::Matcher_Points_DistanceThreshold
+    params:
+      threshold: '%s*ADAPTIVE_THRESHOLD_SIGMA'
+      thresholdAngularDeg: 0
+      pairingsPerPoint: 1
+      allowMatchAlreadyMatchedGlobalPoints: true
+      pointLayerMatches:
+        - {global: "%s", local: "%s", weight: 1.0}
+"""
+
+
+def timed(fn, reps, warm=10):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        r = fn()
+        ts.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(ts)), r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--pairs", type=int, default=2, choices=(2, 3))
+    ap.add_argument("--routes", default="fused,generic,single")
+    a = ap.parse_args()
+    w = synth.workload_creal()
+    rng = np.linalg.norm(w.scan_xyz, axis=1)
+    full_l, near_l = w.scan_xyz, w.scan_xyz[rng < 25.0]
+    far_g = w.map_xyz[::2]
+    sigma, n_it = w.sigma, 40
+    thr = {"localmap": 3.0, "localmap_far": 2.0}
+    spec = [("localmap", "decimated_for_icp", 3.0), ("localmap_far", "decimated_for_icp_near", 2.0)]
+    if a.pairs == 3:
+        spec.append(("localmap_far", "decimated_for_icp", 2.5))
+    ctx = capi.Context(0)
+    maps = {"localmap": capi.Map(ctx, 1.0, 20).build(w.map_xyz), "localmap_far": capi.Map(ctx, 2.0, 20).build(far_g)}
+    scans = {"decimated_for_icp": capi.Scan(ctx, full_l), "decimated_for_icp_near": capi.Scan(ctx, near_l)}
+    kp = np.full(n_it, 0.5 * sigma)
+    p = capi.ICPParams(max_iterations=n_it, threshold=thr["localmap"] * sigma, kernel_param=kp)
+    pairs = [dict(map=maps[g], scan=scans[l], threshold=np.full(n_it, f * sigma)) for g, l, f in spec]
+    print("layers: %s; scan points %d / %d; map points %d / %d" % (
+        ", ".join("%s<-%s" % (g, l) for g, l, _ in spec), len(full_l), len(near_l), len(w.map_xyz), len(far_g)))
+    routes = a.routes.split(",")
+    if "fused" in routes:
+        ms, r = timed(lambda: capi.icp_align_layers(pairs, w.T_guess, p, want_trace=False), a.reps)
+        print("fused   %.3f ms / alignment  (%d iterations, %s, %d pairs, %d host polls)" % (
+            ms, r["n_iterations"], capi.TERM_NAMES[r["termination_reason"]], r["n_final_pairs"], r["n_host_polls"]))
+    if "generic" in routes:
+        from mola_lidar_odometry_amd import _mp2p_icp_hip as hl
+        text = _YAML_HEAD % n_it + "".join(_YAML_MATCHER % (f, g, l) for g, l, f in spec)
+        icp, params = hl.icp_pipeline_from_yaml(hl.Config.FromYamlText(text))
+        src = hl.ParameterSource()
+        src.updateVariable("ADAPTIVE_THRESHOLD_SIGMA", sigma)
+        src.updateVariable("ICP_ITERATION", 0)
+        icp.attachToParameterSource(src)
+        src.realize()
+        icp.forceGenericPath(True)
+        g = hl.metric_map_t()
+        for name, pts, vs in (("localmap", w.map_xyz, 1.0), ("localmap_far", far_g, 2.0)):
+            hv = hl.HashedVoxelPointCloud(vs, 20)
+            hv.setPoints(pts)
+            g.set_layer(name, hv)
+        loc = hl.metric_map_t()
+        loc.set_layer("decimated_for_icp", hl.PointCloud(full_l))
+        loc.set_layer("decimated_for_icp_near", hl.PointCloud(near_l))
+        guess = hl.TPose3D(*w.guess_ypr)
+        ms, r = timed(lambda: icp.align(loc, g, guess, params), a.reps, warm=3)
+        print("generic %.3f ms / alignment  (%d iterations, %s, %d pairs)" % (ms, r.nIterations, r.terminationReason.name,
+                                                                             r.n_pairs()))
+    if "single" in routes:
+        ms, r = timed(lambda: capi.icp_align(maps["localmap"], scans["decimated_for_icp"], w.T_guess, p, want_trace=False), a.reps)
+        print("single  %.3f ms / alignment  (%d iterations, %s, %d pairs; larger pair alone)" % (
+            ms, r["n_iterations"], capi.TERM_NAMES[r["termination_reason"]], r["n_final_pairs"]))
+
+
+if __name__ == "__main__":
+    main()
