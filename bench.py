@@ -18,22 +18,28 @@ second number.
 each rank runs the same per-GPU batch on its own GPU (weak scaling, no data-path collective), the only collective is
 the gather of the resulting poses (RCCL all_gather of 12 doubles per scan).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints ONE JSON line on rank 0 (contract in the
+task statement), including
   "roofline":     the match kernel (k_match_flat_b, one launch over all S scans of a batch): compulsory bytes per launch / its
-                  HIP-event duration vs the 8 TB/s HBM peak (frac <= 1 by construction), the PMC-measured HBM traffic of
-                  that kernel (profiles/) and the views that say what the kernel really waits for, each a counter of the
-                  timed kernel over its clock cycles: vector-instruction issue with the measured mix, texture addresser /
-                  data return, L1 tag rate and pending-line stalls, LDS, waves parked, and two sensitivity slopes;
+                  HIP-event duration in the timed steps vs the 8 TB/s HBM peak (frac <= 1 by construction), the PMC-measured
+                  HBM traffic of that kernel (profiles/) and the views that say what the kernel really waits for, each a
+                  counter of the timed kernel over its clock cycles: vector-instruction issue with the measured mix, texture
+                  addresser / data return, L1 tag rate and pending-line stalls, LDS, waves parked, and two sensitivity slopes.
+--full also measures, outside `value` and after the timed steps (the extras' city drive is cast before them):
+  "shared_map":   the second, shared-map measurement (--no-shared-run skips it);
+  "roofline":     + avg_kernel_ms_alone, the match kernel with nothing else on the device;
   "cpu_baseline": the CPU oracle (a port of the reference algorithm, not the reference binary) timed on this box's
-                  host cores on a bounded sample of the same workload (thread count used AND the box's logical cores);
-and, at N = 1, labelled extras OUTSIDE `value` (--no-extras skips them):
+                  host cores on a bounded sample of the same workload (thread count used AND the box's logical cores),
+                  and "parity_vs_cpu" of the last timed step (--no-cpu-baseline skips both);
+and, at N = 1, labelled extras (--no-extras skips them):
   "single_sequence":     the config-3 proxy -- molahip-lo-cli (C++) on a 1000-sweep synthetic CITY drive (cross streets, houses,
                          cars, poles, trees; ~118 k raw points per sweep, skewed, per-point time stamps): whole-run and
                          steady scans/s, ICP-layer and local-map sizes, per-stage milliseconds, ATE against the generator's
                          ground truth, and the CPU oracle driver on the same scans (with its Python share taken out);
   "single_sequence_ndt": the config-5 proxy -- the same drive through pipelines/lidar3d-ndt-hip.yaml, with its CPU driver;
   "creal":               the 6 k-point layer, 32 in lock step, with its CPU figure;
-  "multi_sequence":      N = 1, 2, 4, 8, 16 copies of the drive's first 400 scans through one molahip-lo-cli process.
+  "multi_sequence":      N = 1, 2, 4, 8, 16 copies of the drive's first 400 scans through one molahip-lo-cli process;
+and, at any N, "lpt_curve": eleven sequences with KITTI's length ratios over the N devices (--no-lpt skips it).
 """
 import argparse
 import glob
@@ -609,7 +615,7 @@ def relaunch_under_torchrun(n):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -629,6 +635,9 @@ def main():
     ap.add_argument("--shared-stream", type=int, default=1, help="1: the contexts of a buffer set share one stream; 0: a stream per context")
     ap.add_argument("--upload-thread", type=int, default=1, help="1: the next step's uploads are queued by a second host thread while "
                     "the current step's batch call blocks; 0: by the main thread before the call")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the shared-map measurement, the match kernel alone, the CPU baseline with "
+                         "parity against the oracle and the labelled extras (each --no-* option below skips its part)")
     ap.add_argument("--no-shared-run", action="store_true", help="skip the second, shared-map measurement")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline budget (bounded sample)")
@@ -646,7 +655,32 @@ def main():
                          "sample of the final pairings) as DIR/<name>.npy; the inputs depend on the arguments alone")
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, gather their ranks over gloo and print n_gpus (no GPU needed: tests the self-launch)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def extra_parts(args, world, rank):
+    """What this rank measures besides the headline: nothing in a plain run, which sets up, warms up, times the steps,
+    writes --dump-outputs and prints the result line.  --full adds every part its --no-* options leave."""
+    if not args.full:
+        return set()
+    sequence_workload = args.workload == "c2" and args.maps == "distinct"
+    parts = set()
+    if args.maps == "distinct" and not args.no_shared_run and args.streams > 1:
+        parts.add("shared_map")
+    if rank == 0 and not args.no_profile:
+        parts.add("kernel_alone")
+    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+        parts.add("cpu_baseline")  # + parity of the last timed step
+    if world == 1 and not args.no_extras and sequence_workload:
+        parts.add("extras")
+    # the KITTI-length LPT curve (SURVEY 8e) is the one extra that also runs at N > 1: rank 0 starts molahip-lo-cli over all N devices
+    if not args.no_extras and not args.no_lpt and sequence_workload:
+        parts.add("lpt_curve")
+    return parts
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(args.gpus)
@@ -670,9 +704,8 @@ def main():
     S = args.streams
     n_var = 1 if args.maps == "shared" else S
     # inputs first (worker processes, before the HIP runtime exists in this one); ranks draw different variants
-    want_extras = world == 1 and not args.no_extras and args.workload == "c2" and args.maps == "distinct"
-    # the KITTI-length LPT curve is the one extra that also runs at N > 1: rank 0 starts molahip-lo-cli over all N devices
-    want_lpt = not args.no_extras and not args.no_lpt and args.workload == "c2" and args.maps == "distinct"
+    parts = extra_parts(args, world, rank)
+    want_extras, want_lpt, want_cpu = "extras" in parts, "lpt_curve" in parts, "cpu_baseline" in parts
     lpt_scans = int(round(max(__import__("mola_lidar_odometry_amd.dist", fromlist=["x"]).KITTI_SEQ_LENGTHS) / float(args.lpt_scale))) + 1
     city = start_city_drive(args.extras_scans if want_extras else lpt_scans) if (want_extras or want_lpt) and rank == 0 else None
     K = max(1, args.scan_sets)
@@ -877,7 +910,7 @@ def main():
     # outside the timed region: the same kernel with nothing else on the device (S = 1), what rocprofv3 --stats of a
     # one-stream run reports per launch
     iso_ms, iso_launches = 0.0, 0
-    if prof and rank == 0:
+    if "kernel_alone" in parts:
         for _ in range(3):
             for r in capi.icp_align_batch(main_run.maps[:1], main_run.scans[0][:1], main_run.guesses[0][:1], params):
                 iso_ms += r["match_kernel_ms"]
@@ -885,7 +918,7 @@ def main():
     # the trivial result gather: poses of the last step from every rank, RCCL all_gather
     gathered = mdist.gather_poses(np.stack([r["T"] for r in last]), device="cuda" if distributed else None)
     all_poses = np.stack(gathered)
-    pairs_last = main_run.last_pairs(last) if main_run.dl else None
+    pairs_last = main_run.last_pairs(last) if want_cpu and main_run.dl else None
     if pairs_last is not None:
         pairs_last = [dict(local_idx=p["local_idx"].copy(), global_idx=p["global_idx"].copy(), d2=p["d2"].copy()) for p in pairs_last]
     last_set = main_run.last_set()
@@ -898,7 +931,7 @@ def main():
     main_run.close()
 
     shared = None
-    if args.maps == "distinct" and not args.no_shared_run and S > 1:
+    if "shared_map" in parts:
         sh = Setup(ws[:1], [sets[0][:1]], io)
         sdt, sms, sl, _ = sh.run(max(2, args.steps // 2), 1)
         shared = {"value": world * max(2, args.steps // 2) * S / sdt, "unit": "scans/sec",
@@ -1008,7 +1041,7 @@ def main():
         # ---- CPU baseline: the oracle (a port), bounded sample, N=1 only ------------------------
         p_bar = None
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if want_cpu:
             from oracle import oracle_c
             op = oracle_c.ICPParams(max_iterations=w.n_iters, disable_stall_test=True, threshold=w.threshold,
                                     kernel_param=w.kernel_param, compute_covariance=True)
