@@ -44,7 +44,9 @@ extern "C" {
 #define MH_VERSION_MINOR 1
 #define MH_VERSION_PATCH 0
 /* The parameter structs of this header carry no size field: they grow at the END, and every growth bumps MH_ABI_VERSION (6:
- * mh_preprocess_params' two decimation-method fields, round 5; 7: mh_layer_pair and mh_icp_align_layers).  A binder built against this header checks
+ * mh_preprocess_params' two decimation-method fields, round 5; 7: mh_layer_pair and mh_icp_align_layers, later also
+ * mh_curvature_params and mh_scan_curvature: new structs and entry points change no existing layout, and a binder that lacks
+ * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
  * built with) and zero-initialises every struct it passes -- a field the binder does not know then reads as its default. */
 #define MH_ABI_VERSION 7
@@ -284,6 +286,29 @@ MH_API mh_status mh_scan_deskew_pair(const mh_scan* in_a, const mh_scan* in_b, c
 /* Axis-aligned bounding box of the finite points (CPointsMap::boundingBox [U], used by the sensor-range estimate at
  * LidarOdometry.cpp:1503-1508, 1517-1534).  n_finite (nullable) = number of finite points; zeros for an empty scan. */
 MH_API mh_status mh_scan_bbox(const mh_scan* scan, float bb_min[3], float bb_max[3], uint64_t* n_finite);
+/* FilterCurvature [U] (extras/lidar3d-edges.yaml:252-259): splits a layer into points of larger and smaller curvature and
+ * the rest.  Upstream's source is not vendored, so this is a restatement; parity with it is unpinned.  The layer carries no
+ * ring channel: it is read in storage order (the synthetic sweeps and KITTI / MulRan rows are ring-major).  For a layer of
+ * N points p_0..p_{N-1}, in float, unfused, in the order written, every point i in [1, N-2]:
+ *   a = p_i - p_{i-1}, b = p_{i+1} - p_i (component-wise);  na = (a.x*a.x + a.y*a.y) + a.z*a.z, nb the same from b;
+ *   gap2 = max_gap*max_gap, clr2 = min_clearance*min_clearance;
+ *   na > gap2 || nb > gap2             -> other
+ *   else na < clr2 || nb < clr2        -> other
+ *   else c = ((a.x*b.x + a.y*b.y) + a.z*b.z) / (sqrtf(na) * sqrtf(nb))   (correctly rounded divide and square root)
+ *        c < max_cosine                -> larger (output_layer_larger_curvature)
+ *        otherwise                     -> smaller (output_layer_smaller_curvature)
+ * IEEE comparisons decide as written (a NaN neighbour difference lands in `smaller`).  Points 0 and N-1 are in no output.
+ * Each output keeps the input order, carries the input's time stamps when it has them, and src_idx = the input's src_idx[i]
+ * when it has one, else i.  Any output may be NULL, not all of them; the outputs differ from `in` and from each other; all
+ * scans belong to one context.  Layers of up to 2^21 - 1 points (three 21-bit counters share one 64-bit scan word; larger:
+ * MH_ERR_INVALID_ARGUMENT).  Queued on the context's stream; one read-back of the three counts ends the call. */
+typedef struct {
+  float max_cosine;     /* cosine of the angle between a and b below which a point is a curvature point */
+  float min_clearance;  /* [m] a neighbour closer than this: other */
+  float max_gap;        /* [m] a neighbour farther than this: other */
+} mh_curvature_params;
+MH_API mh_status mh_scan_curvature(const mh_scan* in, const mh_curvature_params* p, mh_scan* out_larger, mh_scan* out_smaller,
+                                   mh_scan* out_other);
 /* Copy a scan to HOST arrays (any may be NULL; t / src_idx are zero-filled when the scan has none). */
 MH_API mh_status mh_scan_download(const mh_scan* scan, float* x, float* y, float* z, float* t, uint32_t* src_idx);
 

@@ -133,6 +133,10 @@ class PreprocessParams(C.Structure):
                 ("time_offset", C.c_float), ("decim_map_method", C.c_int32), ("decim_icp_method", C.c_int32)]
 
 
+class CurvatureParams(C.Structure):
+    _fields_ = [("max_cosine", C.c_float), ("min_clearance", C.c_float), ("max_gap", C.c_float)]
+
+
 TS_NONE, TS_MIDDLE_IS_ZERO, TS_EARLIEST_IS_ZERO = 0, 1, 2
 DECIMATE_FIRST_POINT, DECIMATE_CLOSEST_TO_AVERAGE = 0, 1
 BBOX_OFF, BBOX_KEEP_OUTSIDE, BBOX_KEEP_INSIDE = 0, 1, 2
@@ -175,6 +179,7 @@ _SIGNATURES = {
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "mh_scan_deskew": (C.c_int32, [C.c_void_p, _DP, C.c_void_p]),
     "mh_scan_deskew_pair": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_void_p, C.c_void_p, _FP, _FP, C.POINTER(C.c_uint64)]),
+    "mh_scan_curvature": (C.c_int32, [C.c_void_p, C.POINTER(CurvatureParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mh_host_alloc_pinned": (C.c_int32, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "mh_host_free_pinned": (C.c_int32, [C.c_void_p]),
     "mh_scan_download": (C.c_int32, [C.c_void_p, _FP, _FP, _FP, _FP, _UP]),
@@ -445,6 +450,11 @@ class Scan:
         tw = None if twist is None else np.ascontiguousarray(twist, dtype=np.float64)
         _chk(lib().mh_scan_deskew(self._h, tw.ctypes.data_as(_DP) if tw is not None else None, out._h))
         return out
+
+    def curvature(self, params: "CurvatureParams", out_larger: "Scan | None", out_smaller: "Scan | None" = None,
+                  out_other: "Scan | None" = None):
+        """FilterCurvature on the device (mh_scan_curvature): self = the input layer; any output may be None."""
+        return scan_curvature(self, params, out_larger, out_smaller, out_other)
 
     def bbox(self):
         mn, mx = np.zeros(3, np.float32), np.zeros(3, np.float32)
@@ -907,6 +917,20 @@ def preprocess_batch(raws, params, out_maps, out_icps=None):
     hs = lambda scans: (C.c_void_p * n)(*[(sc._h if sc is not None else None) for sc in scans])
     _chk(lib().mh_scan_preprocess_batch(n, hs(raws), arr, C.sizeof(PreprocessParams) if per_job else 0, hs(out_maps),
                                         hs(out_icps) if out_icps is not None else None))
+
+
+def scan_curvature(scan: "Scan", params: "CurvatureParams", out_larger: "Scan | None", out_smaller: "Scan | None" = None,
+                   out_other: "Scan | None" = None):
+    """mh_scan_curvature: split `scan` into its larger-curvature, smaller-curvature and other points (molahip.h states
+    the rule).  Returns the three outputs (None where none was given)."""
+    h = lambda sc: sc._h if sc is not None else None
+    _chk(lib().mh_scan_curvature(scan._h, C.byref(params), h(out_larger), h(out_smaller), h(out_other)))
+    return out_larger, out_smaller, out_other
+
+
+def curvature_params(max_cosine=0.4, min_clearance=0.20, max_gap=1.0) -> CurvatureParams:
+    """Defaults: the values of extras/lidar3d-edges.yaml's FilterCurvature."""
+    return CurvatureParams(float(max_cosine), float(min_clearance), float(max_gap))
 
 
 def preprocess_params(decim_map_resolution, decim_icp_resolution, min_points_to_filter=2000, index_mode=INDEX_FLOOR,

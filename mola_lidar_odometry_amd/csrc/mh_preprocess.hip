@@ -8,6 +8,7 @@
 //   FilterByRange / FilterBoundingBox -> per-point predicates fused into the same flag pass
 //   (flags) -> exclusive scan -> order-preserving compaction (survivors keep the raw order)
 //   FilterDeskew            -> p' = Exp_SO3(w t_i) p + v t_i, fp64, rounded to float
+//   FilterCurvature         -> three-point stencil, one scan of packed class counters, three-way compaction (mh_k_curv.h)
 // All of it is HBM-bound byte/index work: coalesced SoA streams, one pass per stage, atomics only on the
 // (L2-resident) decimation table.
 #include <string.h>
@@ -16,6 +17,7 @@
 
 #include "mh_internal.h"
 #include "mh_nn_device.h"
+#include "mh_k_curv.h"
 
 using namespace mh;
 
@@ -976,6 +978,62 @@ mh_status mh_scan_deskew(const mh_scan* in, const double twist[6], mh_scan* out)
     MH_HIP(hipMemcpyAsync((void*)out->y, in->y, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     MH_HIP(hipMemcpyAsync((void*)out->z, in->z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   }
+  return MH_OK;
+}
+
+mh_status mh_scan_curvature(const mh_scan* in, const mh_curvature_params* p, mh_scan* out_larger, mh_scan* out_smaller,
+                            mh_scan* out_other) {
+  MH_REQUIRE(in && p, "null argument");
+  mh_scan* outs[3] = {out_larger, out_smaller, out_other};
+  MH_REQUIRE(out_larger || out_smaller || out_other, "all outputs are NULL");
+  for (int k = 0; k < 3; k++) {
+    if (!outs[k]) continue;
+    MH_REQUIRE(outs[k] != in, "an output is the input scan");
+    MH_REQUIRE(outs[k]->ctx == in->ctx, "scans belong to different contexts");
+    for (int q = 0; q < k; q++) MH_REQUIRE(outs[k] != outs[q], "outputs must be distinct scans");
+  }
+  MH_REQUIRE(in->n <= kCurvMaxPoints, "layer above 2^21 - 1 points (the three packed 21-bit counters of the scan)");
+  mh_ctx* ctx = in->ctx;
+  MH_TRY(set_device(ctx));
+  hipStream_t s = ctx->stream;
+  const size_t n = in->n;
+  const bool has_t = in->t != nullptr;
+  for (mh_scan* o : outs)  // capacity: the input size; the real counts arrive with the read-back below
+    if (o) MH_TRY(scan_alloc(o, n, has_t, true));
+  if (n < 3) {  // no interior point
+    for (mh_scan* o : outs)
+      if (o) o->n = 0;
+    return MH_OK;
+  }
+  const uint32_t cap = (uint32_t)((n + 255) / 256 * 256);
+  MH_TRY(ctx->build_c.reserve(2 * (size_t)cap * sizeof(unsigned long long)));  // word | pos
+  unsigned long long* word = ctx->build_c.as<unsigned long long>();
+  unsigned long long* pos = word + cap;
+  size_t tmp = 0;
+  MH_HIP(rocprim::exclusive_scan(nullptr, tmp, word, pos, 0ull, (size_t)cap, rocprim::plus<unsigned long long>(), s));
+  MH_TRY(ctx->sort_tmp.reserve(tmp));
+  if (!ctx->h_small) MH_HIP(hipHostMalloc((void**)&ctx->h_small, 64 * sizeof(uint32_t), hipHostMallocDefault));
+  uint32_t* h_counts = ctx->h_small + 16;  // (slots 0..6: mh_scan_bbox / mh_scan_deskew_pair)
+  const float gap2 = p->max_gap * p->max_gap, clr2 = p->min_clearance * p->min_clearance;
+  hipLaunchKernelGGL(k_curv_classify, dim3(cap / 256), dim3(256), 0, s, in->x, in->y, in->z, (uint32_t)n, cap, p->max_cosine, clr2,
+                     gap2, word);
+  size_t tb = ctx->sort_tmp.bytes;
+  MH_HIP(rocprim::exclusive_scan(ctx->sort_tmp.p, tb, word, pos, 0ull, (size_t)cap, rocprim::plus<unsigned long long>(), s));
+  CurvOut co[3];
+  for (int k = 0; k < 3; k++) {
+    mh_scan* o = outs[k];
+    co[k].x = o ? (float*)o->x : nullptr;
+    co[k].y = o ? (float*)o->y : nullptr;
+    co[k].z = o ? (float*)o->z : nullptr;
+    co[k].t = o ? (float*)o->t : nullptr;
+    co[k].src = o ? (uint32_t*)o->src : nullptr;
+  }
+  hipLaunchKernelGGL(k_curv_scatter, dim3(cap / 256), dim3(256), 0, s, in->x, in->y, in->z, in->t, in->src, (uint32_t)n, cap,
+                     word, pos, co[0], co[1], co[2], h_counts);
+  MH_HIP(hipGetLastError());
+  MH_HIP(mh::wait_stream(s));
+  for (int k = 0; k < 3; k++)
+    if (outs[k]) outs[k]->n = h_counts[k];
   return MH_OK;
 }
 

@@ -128,6 +128,9 @@ class LidarOdometry {
     uint64_t n_raw = 0, n_for_map = 0, n_for_icp = 0, n_map_points = 0, n_map_voxels = 0;
     Twist twist;              // twist used for the (last) de-skew of this scan
     double decim_map_resolution = 0, decim_icp_resolution = 0, map_voxel_size = 0;
+    // general filter chains (not the default one, whose record leaves it empty): points of every observation layer handed to
+    // ICP, by name.  There n_for_map = points the FilterMerge steps offered to the maps, n_for_icp = points of all those layers.
+    std::map<std::string, uint64_t> layer_sizes;
   };
 
   // ctx == nullptr: the process-wide default device context, taken at initialize()
@@ -183,6 +186,7 @@ class LidarOdometry {
 
  private:
   struct FilterPlan;  // the recognised observation filter chain, as data for mh_scan_preprocess / mh_scan_deskew
+  struct GeneralPlan;  // any other chain of the implemented filters: ordered steps over named device layers, several maps
   struct RawInput;  // where the points of the current observation come from
   struct Prefetch;  // the announced next observation and its worker
   const ScanRecord& process(double timestamp, const RawInput& in);
@@ -194,6 +198,9 @@ class LidarOdometry {
   void run_second_pass();
   void doUpdateAdaptiveThreshold(const CPose3D& motionModelError);
   void create_local_map();
+  std::shared_ptr<HashedVoxelPointCloud> make_map(const Config& def, double* voxel_size, float* remove_far) const;
+  void run_general_pass(int pass);
+  uint64_t maps_total(bool voxels) const;
   void ensure_device();
   void resolve_map_counts() const;  // fills n_map_points / n_map_voxels of the records that still wait for them
   bool map_is_empty();              // local_map_->empty() without a device round trip once the map is known to hold points
@@ -201,6 +208,7 @@ class LidarOdometry {
   std::shared_ptr<DeviceContext> ctx_;
   Params params_;
   std::unique_ptr<FilterPlan> plan_;
+  std::unique_ptr<GeneralPlan> gplan_;  // set instead of plan_ when FilterPlan does not recognise the chain
   ParameterSource source_;
   NavStateFuse navstate_;
   ICP::Ptr icp_[2];  // [0] RegularOdometry, [1] NoMotionModel

@@ -8,7 +8,9 @@
 #include <cstdio>
 #include <cstring>
 #include <condition_variable>
+#include <deque>
 #include <functional>
+#include <set>
 #include <mutex>
 #include <thread>
 #include <stdexcept>
@@ -323,6 +325,198 @@ struct LidarOdometry::FilterPlan : public Parameterizable {
   }
 };
 
+// Any other chain of the filters the device implements (extras/lidar3d-edges.yaml, -dual-map, -kissicp-like, -near-far):
+// ordered steps of the two passes over a name -> layer table, one device map per localmap_generator entry, one FilterMerge
+// per (layer, map).  Each step maps onto one entry point:
+//   FilterDeskew -> mh_scan_deskew; FilterByRange (output_layer_between) / FilterBoundingBox (inside and / or outside) /
+//   FilterDecimateVoxels -> mh_scan_preprocess with the other stages skipped; FilterCurvature -> mh_scan_curvature;
+//   FilterDeleteLayer -> the layer leaves the table; observations_filter_adjust_timestamps -> mh_scan_preprocess on 'raw'
+//   with every filter stage skipped (it keeps the finite points, as every preprocess call does).
+struct LidarOdometry::GeneralPlan : public Parameterizable {
+  enum class Kind { Deskew, Preprocess, Curvature, Delete };
+  struct Step {
+    Kind kind = Kind::Delete;
+    int pass = 1;
+    std::string cls, in;
+    std::vector<std::string> out;  // Deskew / Preprocess: 1; Curvature: larger, smaller, other ("" = not asked for); Delete: names
+    double res = 0, range_min = 0, range_max = 0, bbox_min[3] = {0, 0, 0}, bbox_max[3] = {0, 0, 0};
+    int32_t method = MH_DECIMATE_FIRST_POINT, bbox_mode = MH_BBOX_OFF;
+    uint32_t min_points = 0;
+    bool range_on = false;
+    double max_cosine = 0, min_clearance = 0, max_gap = 0;
+    bool skip_deskew = false;
+  };
+  struct MapSlot {
+    std::string name;
+    Config def;
+    std::shared_ptr<HashedVoxelPointCloud> map;  // created at the first key-frame (its $f{} formulas need the sensor range)
+    float remove_far = 0.f;
+    double voxel_size = 0;
+  };
+  std::deque<Step> steps;  // (a deque: the formulas are bound to the steps' fields by address)
+  int32_t timestamp_method = MH_TS_NONE;
+  double time_offset = 0;
+  std::vector<MapSlot> maps;
+  std::vector<std::pair<std::string, size_t>> merges;  // layer -> index in maps
+  // per-scan state: every layer name's buffer (reused scan after scan), the layers alive after pass 1 / now
+  std::map<std::string, std::shared_ptr<DevicePointCloud>> buf;
+  std::shared_ptr<DevicePointCloud> raw_adjusted;
+  std::set<std::string> alive_1st, alive;
+
+  static void unsupported(const std::string& what) {
+    throw std::runtime_error("LidarOdometry (HIP): unsupported observation filter chain: " + what +
+                             ". Implemented on the device: the chain of pipelines/lidar3d-default.yaml, and chains over named "
+                             "layers of FilterAdjustTimestamps, FilterDeskew, FilterByRange(output_layer_between), "
+                             "FilterBoundingBox, FilterDecimateVoxels(FirstPoint | ClosestToAverage), FilterCurvature, "
+                             "FilterDeleteLayer, and FilterMerge into HashedVoxelPointCloud / NDT maps");
+  }
+  static std::vector<std::string> names_of(const Config& c) {
+    std::vector<std::string> v;
+    if (c.kind == Config::Kind::Seq)
+      for (size_t i = 0; i < c.size(); i++) v.push_back(c.at(i).asString());
+    else if (!c.isNull())
+      v.push_back(c.asString());
+    return v;
+  }
+  void load_pass(const Config& f, int pass, std::set<std::string>& known) {
+    for (size_t k = 0; k < f.size(); k++) {
+      const std::string cn = class_of(f.at(k));
+      const Config& p = f.at(k)["params"];
+      steps.emplace_back();  // (declared formulas point into the step: it is built in place)
+      Step& st = steps.back();
+      st.pass = pass;
+      st.cls = cn;
+      auto input = [&]() {
+        st.in = p.getOr("input_pointcloud_layer", "");
+        if (!known.count(st.in)) unsupported(cn + " reads layer '" + st.in + "', which no earlier filter writes");
+      };
+      auto output = [&](const std::string& o) {
+        if (o.empty()) unsupported(cn + " without an output layer");
+        if (o == st.in) unsupported(cn + " writes its own input layer '" + o + "'");
+        if (o == "raw") unsupported(cn + " writes layer 'raw'");
+        st.out.push_back(o);
+      };
+      if (ends_with(cn, "FilterDeleteLayer")) {
+        st.kind = Kind::Delete;
+        st.out = names_of(p["pointcloud_layer_to_remove"]);
+        for (const auto& n : st.out) known.erase(n);
+      } else if (ends_with(cn, "FilterDeskew")) {
+        st.kind = Kind::Deskew;
+        input();
+        output(p.getOr("output_pointcloud_layer", ""));
+        if (p.has("skip_deskew")) st.skip_deskew = to_bool(p["skip_deskew"].asString());
+      } else if (ends_with(cn, "FilterByRange")) {
+        st.kind = Kind::Preprocess;
+        input();
+        if (!p.has("output_layer_between") || p.has("output_layer_outside")) unsupported("FilterByRange other than output_layer_between");
+        if (p.has("center")) unsupported("FilterByRange with a center");
+        output(p["output_layer_between"].asString());
+        st.range_on = true;
+        parameterFromConfig(p, "range_min", &st.range_min, true);
+        parameterFromConfig(p, "range_max", &st.range_max, true);
+      } else if (ends_with(cn, "FilterBoundingBox")) {
+        input();
+        const bool in_l = p.has("inside_pointcloud_layer"), out_l = p.has("outside_pointcloud_layer");
+        if (!in_l && !out_l) unsupported("FilterBoundingBox without an output layer");
+        const Step proto = st;
+        steps.pop_back();  // one step per output layer
+        for (int mode : {MH_BBOX_KEEP_INSIDE, MH_BBOX_KEEP_OUTSIDE}) {
+          if (!(mode == MH_BBOX_KEEP_INSIDE ? in_l : out_l)) continue;
+          steps.push_back(proto);
+          Step& b = steps.back();
+          b.kind = Kind::Preprocess;
+          b.bbox_mode = mode;
+          const std::string o = p[mode == MH_BBOX_KEEP_INSIDE ? "inside_pointcloud_layer" : "outside_pointcloud_layer"].asString();
+          if (o.empty() || o == b.in || o == "raw") unsupported("FilterBoundingBox output layer '" + o + "'");
+          b.out = {o};
+          for (int a = 0; a < 3; a++) {
+            declareParameter("bounding_box_min", p["bounding_box_min"].at(a).asString(), &b.bbox_min[a]);
+            declareParameter("bounding_box_max", p["bounding_box_max"].at(a).asString(), &b.bbox_max[a]);
+          }
+          known.insert(o);
+        }
+        continue;
+      } else if (ends_with(cn, "FilterDecimateVoxels")) {
+        st.kind = Kind::Preprocess;
+        input();
+        output(p.getOr("output_pointcloud_layer", ""));
+        if (p.has("decimate_method")) {
+          const std::string m = p["decimate_method"].asString();
+          if (ends_with(m, "ClosestToAverage")) st.method = MH_DECIMATE_CLOSEST_TO_AVERAGE;
+          else if (!ends_with(m, "FirstPoint")) unsupported("decimate_method " + m);
+        }
+        if (p.has("minimum_input_points_to_filter")) st.min_points = (uint32_t)to_double(p["minimum_input_points_to_filter"].asString());
+        parameterFromConfig(p, "voxel_filter_resolution", &st.res, true);
+      } else if (ends_with(cn, "FilterCurvature")) {
+        st.kind = Kind::Curvature;
+        input();
+        const char* keys[3] = {"output_layer_larger_curvature", "output_layer_smaller_curvature", "output_layer_other"};
+        for (const char* key : keys) {
+          const std::string o = p.getOr(key, "");
+          if (o.empty()) st.out.push_back("");
+          else output(o);
+        }
+        if (st.out[0].empty() && st.out[1].empty() && st.out[2].empty()) unsupported("FilterCurvature without an output layer");
+        if ((!st.out[0].empty() && (st.out[0] == st.out[1] || st.out[0] == st.out[2])) || (!st.out[1].empty() && st.out[1] == st.out[2]))
+          unsupported("FilterCurvature writes one layer twice");
+        parameterFromConfig(p, "max_cosine", &st.max_cosine, true);
+        parameterFromConfig(p, "min_clearance", &st.min_clearance, true);
+        parameterFromConfig(p, "max_gap", &st.max_gap, true);
+      } else {
+        unsupported(cn + (ends_with(cn, "Intensity") ? " (the device layers carry no intensity channel)" : ""));
+      }
+      if (st.kind != Kind::Delete)
+        for (const auto& o : st.out)
+          if (!o.empty()) known.insert(o);
+    }
+  }
+  void load(const Config& cfg) {
+    if (cfg.has("observations_filter_adjust_timestamps")) {
+      const Config& s = cfg["observations_filter_adjust_timestamps"];
+      for (size_t i = 0; i < s.size(); i++) {
+        if (!ends_with(class_of(s.at(i)), "FilterAdjustTimestamps")) unsupported(class_of(s.at(i)));
+        const Config& p = s.at(i)["params"];
+        if (p.getOr("pointcloud_layer", "raw") != "raw") unsupported("FilterAdjustTimestamps on a layer other than 'raw'");
+        const std::string m = p.getOr("method", "TimestampAdjustMethod::MiddleIsZero");
+        timestamp_method = ends_with(m, "MiddleIsZero") ? MH_TS_MIDDLE_IS_ZERO : ends_with(m, "EarliestIsZero") ? MH_TS_EARLIEST_IS_ZERO : -1;
+        if (timestamp_method < 0) unsupported("timestamp method " + m);
+        if (p.has("time_offset")) parameterFromConfig(p, "time_offset", &time_offset, false);
+      }
+    }
+    std::set<std::string> known = {"raw"};
+    if (cfg.has("observations_filter_1st_pass")) load_pass(cfg["observations_filter_1st_pass"], 1, known);
+    if (cfg.has("observations_filter_2nd_pass")) load_pass(cfg["observations_filter_2nd_pass"], 2, known);
+    const Config& gen = cfg["localmap_generator"];
+    for (size_t i = 0; i < gen.size(); i++) {
+      const Config& p = gen.at(i)["params"];
+      MapSlot m;
+      m.name = p.getOr("target_layer", "localmap");
+      m.def = p["metric_map_definition"];
+      const std::string c = m.def["class"].asString();
+      if (!ends_with(c, "HashedVoxelPointCloud") && !ends_with(c, "NDT"))
+        unsupported("local map class '" + c + "' (HashedVoxelPointCloud, NDT)");
+      for (const auto& o : maps)
+        if (o.name == m.name) unsupported("two local maps named '" + m.name + "'");
+      maps.push_back(m);
+    }
+    if (maps.empty()) unsupported("localmap_generator is empty");
+    const Config& mg = cfg["insert_observation_into_local_map"];
+    for (size_t i = 0; i < mg.size(); i++) {
+      if (!ends_with(class_of(mg.at(i)), "FilterMerge")) unsupported("insert_observation_into_local_map: " + class_of(mg.at(i)));
+      const Config& mp = mg.at(i)["params"];
+      const std::string layer = mp["input_pointcloud_layer"].asString(), target = mp.getOr("target_layer", "localmap");
+      if (!known.count(layer)) unsupported("FilterMerge reads layer '" + layer + "', which the filters do not leave");
+      if (mp.has("input_layer_in_local_coordinates") && !to_bool(mp["input_layer_in_local_coordinates"].asString()))
+        unsupported("FilterMerge with input_layer_in_local_coordinates: false");
+      size_t k = 0;
+      while (k < maps.size() && maps[k].name != target) k++;
+      if (k == maps.size()) unsupported("FilterMerge into '" + target + "', which no localmap_generator entry defines");
+      merges.emplace_back(layer, k);
+    }
+    if (merges.empty()) unsupported("insert_observation_into_local_map holds no FilterMerge");
+  }
+};
+
 // ================================================================== driver
 struct LidarOdometry::RawInput {
   size_t n = 0;
@@ -410,13 +604,23 @@ LidarOdometry::~LidarOdometry() {
 }
 
 void LidarOdometry::initialize(const Config& cfg) {
-  if (plan_) throw std::runtime_error("LidarOdometry::initialize() called twice; create a new object instead");
+  if (plan_ || gplan_) throw std::runtime_error("LidarOdometry::initialize() called twice; create a new object instead");
   params_.load_from(cfg["params"]);
   params_.attachToParameterSource(source_);
   if (cfg.has("navstate_fuse_params")) navstate_.initialize(cfg["navstate_fuse_params"]);
-  plan_ = std::make_unique<FilterPlan>();
-  plan_->load(cfg);
-  plan_->attachToParameterSource(source_);
+  // the default chain first (its fused path, prefetch and batching); any other chain of implemented filters as a general plan
+  try {
+    auto plan = std::make_unique<FilterPlan>();
+    plan->load(cfg);
+    plan_ = std::move(plan);
+    plan_->attachToParameterSource(source_);
+  } catch (const std::runtime_error& e) {
+    if (std::string(e.what()).find("unsupported observation filter chain") == std::string::npos) throw;
+    auto g = std::make_unique<GeneralPlan>();
+    g->load(cfg);  // throws its own "unsupported observation filter chain" naming what is implemented
+    gplan_ = std::move(g);
+    gplan_->attachToParameterSource(source_);
+  }
 
   // ICP pipelines (:340-358)
   auto t0 = icp_pipeline_from_yaml(cfg["icp_settings_with_vel"], ctx_);
@@ -452,10 +656,22 @@ void LidarOdometry::ensure_device() {
   for_icp_ = std::make_shared<DevicePointCloud>(ctx_);
 }
 
+uint64_t LidarOdometry::maps_total(bool voxels) const {  // general plans: all maps together
+  uint64_t n = 0;
+  for (const auto& m : gplan_->maps)
+    if (m.map) n += voxels ? m.map->voxelCount() : m.map->size();
+  return n;
+}
+
 void LidarOdometry::resolve_map_counts() const {
   if (!map_counts_pending_) return;
-  map_points_cached_ = local_map_ ? local_map_->size() : 0;  // (mh_map_get_info: waits for the update if it still runs)
-  map_voxels_cached_ = local_map_ ? local_map_->voxelCount() : 0;
+  if (gplan_) {
+    map_points_cached_ = maps_total(false);
+    map_voxels_cached_ = maps_total(true);
+  } else {
+    map_points_cached_ = local_map_ ? local_map_->size() : 0;  // (mh_map_get_info: waits for the update if it still runs)
+    map_voxels_cached_ = local_map_ ? local_map_->voxelCount() : 0;
+  }
   for (size_t i = map_counts_from_; i < records_.size(); i++) {
     if (records_[i].dropped) continue;  // (those returned before the map was looked at)
     records_[i].n_map_points = map_points_cached_;
@@ -470,7 +686,7 @@ void LidarOdometry::resolve_map_counts() const {
 bool LidarOdometry::map_is_empty() {
   if (!local_map_) return true;
   if (map_known_nonempty_) return false;
-  map_known_nonempty_ = local_map_->size() != 0;
+  map_known_nonempty_ = gplan_ ? maps_total(false) != 0 : local_map_->size() != 0;  // (a metric map is empty when all its layers are)
   return !map_known_nonempty_;
 }
 
@@ -482,6 +698,8 @@ void LidarOdometry::reset() {
   map_known_nonempty_ = false;
   navstate_.reset();
   local_map_.reset();
+  if (gplan_)
+    for (auto& m : gplan_->maps) m.map.reset();
   last_lidar_pose_ = CPose3D();
   last_icp_was_good_ = true;
   last_icp_quality_ = 0;
@@ -552,7 +770,68 @@ static mh_preprocess_params make_pp(double decim_map_res, double decim_icp_res, 
   return pp;
 }
 
+void LidarOdometry::run_general_pass(int pass) {
+  GeneralPlan& g = *gplan_;
+  const auto& v = source_.getVariableValues();
+  auto layer = [&](const std::string& name) -> std::shared_ptr<DevicePointCloud> {
+    if (name == "raw") return g.raw_adjusted ? g.raw_adjusted : cur_raw_;
+    auto& b = g.buf[name];
+    if (!b) b = std::make_shared<DevicePointCloud>(ctx_);
+    return b;
+  };
+  if (pass == 1) {
+    g.raw_adjusted.reset();
+    if (g.timestamp_method != MH_TS_NONE) {  // observations_filter_adjust_timestamps over all raw points
+      const double zero[3] = {0, 0, 0};
+      const mh_preprocess_params pp = make_pp(0, 0, 0, 0, 0, MH_BBOX_OFF, zero, zero, g.timestamp_method, g.time_offset);
+      auto out = layer(" raw (time stamps adjusted)");
+      check(mh_scan_preprocess(cur_raw_->handle(), &pp, out->handle(), nullptr), "mh_scan_preprocess (adjust time stamps)");
+      g.raw_adjusted = out;
+    }
+    g.alive = {"raw"};
+  } else {
+    g.alive = g.alive_1st;  // (the twist hook runs this pass again from the same start)
+  }
+  for (const auto& st : g.steps) {
+    if (st.pass != pass) continue;
+    using K = GeneralPlan::Kind;
+    if (st.kind == K::Delete) {
+      for (const auto& n : st.out) g.alive.erase(n);
+      continue;
+    }
+    if (!g.alive.count(st.in)) throw std::runtime_error("LidarOdometry (HIP): " + st.cls + " reads the deleted layer '" + st.in + "'");
+    const mh_scan* in = layer(st.in)->handle();
+    if (st.kind == K::Deskew) {
+      const double tw[6] = {v.at("vx"), v.at("vy"), v.at("vz"), v.at("wx"), v.at("wy"), v.at("wz")};
+      check(mh_scan_deskew(in, st.skip_deskew ? nullptr : tw, layer(st.out[0])->handle()), "mh_scan_deskew");
+    } else if (st.kind == K::Preprocess) {
+      const mh_preprocess_params pp = make_pp(st.res, 0, st.min_points, st.range_min, st.range_on ? st.range_max : 0, st.bbox_mode,
+                                              st.bbox_min, st.bbox_max, MH_TS_NONE, 0, st.method);
+      check(mh_scan_preprocess(in, &pp, layer(st.out[0])->handle(), nullptr), "mh_scan_preprocess");
+    } else {
+      mh_curvature_params cp;
+      memset(&cp, 0, sizeof(cp));
+      cp.max_cosine = (float)st.max_cosine;
+      cp.min_clearance = (float)st.min_clearance;
+      cp.max_gap = (float)st.max_gap;
+      mh_scan* o[3];
+      for (int k = 0; k < 3; k++) o[k] = st.out[k].empty() ? nullptr : layer(st.out[k])->handle();
+      check(mh_scan_curvature(in, &cp, o[0], o[1], o[2]), "mh_scan_curvature");
+    }
+    for (const auto& n : st.out)
+      if (!n.empty()) g.alive.insert(n);
+  }
+  if (pass == 1) {
+    g.alive_1st = g.alive;
+  } else {
+    // the sensor-range estimate reads the alphabetically first point layer of the observation (LidarOdometry.cpp:1515-1545)
+    for (int a = 0; a < 3; a++) icp_bb_min_[a] = icp_bb_max_[a] = 0.f;
+    if (!g.alive.empty()) layer(*g.alive.begin())->boundingBox(icp_bb_min_, icp_bb_max_);
+  }
+}
+
 void LidarOdometry::run_first_pass() {
+  if (gplan_) return run_general_pass(1);
   const FilterPlan& f = *plan_;
   const mh_preprocess_params pp = make_pp(f.decim_map_res, f.decim_icp_res, f.min_points_to_filter, f.range_min, f.range_max,
                                           f.bbox_mode, f.bbox_min, f.bbox_max, f.timestamp_method, f.time_offset, f.decim_map_method, f.decim_icp_method);
@@ -564,6 +843,7 @@ void LidarOdometry::run_first_pass() {
 void LidarOdometry::setAlignBatcher(std::shared_ptr<mp2p_icp_hip::AlignBatcher> b) {
   // the instances of a batch run on their own host threads: each needs a context (stream + scratch) of its own, the
   // process-wide default one would be shared between threads (molahip.h: one context, one thread at a time)
+  if (gplan_) return;  // general plans run unbatched
   if (b && (!ctx_ || ctx_ == DeviceContext::Default()))
     throw std::runtime_error("LidarOdometry::setAlignBatcher: this instance uses the process-wide default context; construct "
                              "it with a DeviceContext of its own");
@@ -662,6 +942,7 @@ void LidarOdometry::launch_prefetch() {
 }
 
 void LidarOdometry::run_second_pass() {
+  if (gplan_) return run_general_pass(2);
   const auto& v = source_.getVariableValues();
   const double tw[6] = {v.at("vx"), v.at("vy"), v.at("vz"), v.at("wx"), v.at("wy"), v.at("wz")};
   const double* twp = plan_->skip_deskew ? nullptr : tw;
@@ -690,25 +971,35 @@ void LidarOdometry::doUpdateAdaptiveThreshold(const CPose3D& err) {  // :1449-14
 }
 
 void LidarOdometry::create_local_map() {  // :1165-1171 with yaml:228-242
+  if (gplan_) {  // one map per localmap_generator entry; local_map_ = the first (localMap(), the ICP schedule)
+    for (auto& m : gplan_->maps) m.map = make_map(m.def, &m.voxel_size, &m.remove_far);
+    local_map_ = gplan_->maps[0].map;
+    map_voxel_size_ = gplan_->maps[0].voxel_size;
+    return;
+  }
+  local_map_ = make_map(map_def_, &map_voxel_size_, &remove_voxels_farther_than_);
+}
+
+std::shared_ptr<HashedVoxelPointCloud> LidarOdometry::make_map(const Config& def, double* voxel_size, float* remove_far) const {
   const auto& vars = source_.getVariableValues();
-  const std::string cls = map_def_["class"].asString();
-  const Config& co = map_def_["creationOpts"];
-  const Config& io = map_def_["insertOpts"];
+  const std::string cls = def["class"].asString();
+  const Config& co = def["creationOpts"];
+  const Config& io = def["insertOpts"];
   mh_map_params mp{};
-  map_voxel_size_ = eval_now(co["voxel_size"].asString(), vars);
-  mp.voxel_size = (float)map_voxel_size_;
+  *voxel_size = eval_now(co["voxel_size"].asString(), vars);
+  mp.voxel_size = (float)*voxel_size;
   mp.max_points_per_voxel = io.has("max_points_per_voxel") ? (uint32_t)eval_now(io["max_points_per_voxel"].asString(), vars) : 0;
   mp.index_mode = molahip_host::plugin_switches().index_mode;
   mp.far_voxel_metric = molahip_host::plugin_switches().far_voxel_metric;  // MOLA_HIP_FAR_VOXEL_METRIC
   mp.min_distance_between_points = io.has("min_distance_between_points") ? (float)eval_now(io["min_distance_between_points"].asString(), vars) : 0.f;
-  remove_voxels_farther_than_ = io.has("remove_voxels_farther_than") ? (float)eval_now(io["remove_voxels_farther_than"].asString(), vars) : 0.f;
+  *remove_far = io.has("remove_voxels_farther_than") ? (float)eval_now(io["remove_voxels_farther_than"].asString(), vars) : 0.f;
   if (ends_with(cls, "NDT")) {
     mp.ndt_max_eigen_ratio = io.has("max_eigen_ratio_for_planes") ? (float)eval_now(io["max_eigen_ratio_for_planes"].asString(), vars) : 0.05f;
     mp.ndt_min_points = 4;
   } else if (!ends_with(cls, "HashedVoxelPointCloud")) {
     throw std::runtime_error("local map class '" + cls + "' has no device implementation (HashedVoxelPointCloud, NDT)");
   }
-  local_map_ = std::make_shared<HashedVoxelPointCloud>(mp, ctx_);
+  return std::make_shared<HashedVoxelPointCloud>(mp, ctx_);
 }
 
 const LidarOdometry::ScanRecord& LidarOdometry::onLidar(double this_obs_tim, const float* x, const float* y, const float* z,
@@ -731,7 +1022,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   const size_t n = in.n;
   const bool has_t = in.t != nullptr || (in.data && in.off_t >= 0);
   (void)has_t;
-  if (!plan_) throw std::runtime_error("LidarOdometry::onLidar called before initialize()");
+  if (!plan_ && !gplan_) throw std::runtime_error("LidarOdometry::onLidar called before initialize()");
   records_.emplace_back();
   ScanRecord& rec = records_.back();
   rec.timestamp = this_obs_tim;
@@ -802,10 +1093,20 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     StageTimer tt(profile_, "onLidar.1.filter_2nd");
     run_second_pass();  // :739
   }
-  rec.decim_map_resolution = plan_->decim_map_res;
-  rec.decim_icp_resolution = plan_->decim_icp_res;
-  rec.n_for_map = for_map_->size();
-  rec.n_for_icp = for_icp_->size();
+  if (gplan_) {
+    for (const auto& name : gplan_->alive) {
+      const uint64_t k = (name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name))->size();
+      rec.layer_sizes[name] = k;
+      rec.n_for_icp += k;
+    }
+    for (const auto& [name, m] : gplan_->merges)
+      if (rec.layer_sizes.count(name)) rec.n_for_map += rec.layer_sizes[name];
+  } else {
+    rec.decim_map_resolution = plan_->decim_map_res;
+    rec.decim_icp_resolution = plan_->decim_icp_res;
+    rec.n_for_map = for_map_->size();
+    rec.n_for_icp = for_icp_->size();
+  }
 
   // sensor range low-pass from the first point layer of the observation, 'decimated_for_icp' (:744, 1515-1545)
   if (estimated_sensor_max_range_) {
@@ -869,9 +1170,16 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     size_t remaining = icp_params.maxIterations;
     mp2p_icp_hip::Results res;
     mp2p_icp_hip::metric_map_t obs, glob;
-    obs.layers[plan_->layer_for_icp] = for_icp_;
-    obs.layers[plan_->layer_for_map] = for_map_;
-    glob.layers[plan_->map_layer] = local_map_;
+    if (gplan_) {  // every layer the filters leave, every map (the ICP pipeline's matchers pick their pairs)
+      for (const auto& name : gplan_->alive)
+        obs.layers[name] = name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name);
+      for (const auto& m : gplan_->maps)
+        if (m.map) glob.layers[m.name] = m.map;
+    } else {
+      obs.layers[plan_->layer_for_icp] = for_icp_;
+      obs.layers[plan_->layer_for_map] = for_map_;
+      glob.layers[plan_->map_layer] = local_map_;
+    }
     std::optional<StageTimer> t_icp;
     t_icp.emplace(profile_, "onLidar.3.run_icp");
     do {
@@ -890,6 +1198,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
       profile_["icp.enqueued_iterations"] += icp.lastAlignEnqueuedIterations();
       profile_["icp.executed_iterations"] += (double)res.nIterations;
       profile_["icp.align_calls"] += 1.0;
+      if (gplan_) profile_["icp.fused_align_calls"] += icp.lastAlignUsedFusedPath() ? 1.0 : 0.0;  // (general plans: which route)
       profile_["onLidar.3.icp_host_setup"] += icp.lastAlignSetupSeconds();
       remaining -= std::min(remaining, res.nIterations);
       rec.icp_iterations += (uint32_t)res.nIterations;
@@ -958,6 +1267,9 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   if (!last_icp_was_good_ && trajectory_.size() == 1) {
     resolve_map_counts();  // (earlier records keep the counts of the map they saw)
     if (local_map_) local_map_->clear();
+    if (gplan_)
+      for (auto& m : gplan_->maps)
+        if (m.map && m.map != local_map_) m.map->clear();
     map_known_nonempty_ = false;
     map_points_cached_ = map_voxels_cached_ = 0;
     trajectory_.clear();
@@ -973,7 +1285,16 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     updatePipelineDynamicVariables();  // robot_x..robot_roll (:1194)
     resolve_map_counts();  // the previous update's counters (it finished before this scan's alignment started: no wait)
     // asynchronous: the update runs on the map's own stream and is waited for by the next use of the map only
-    local_map_->insertPointCloud(*for_map_, last_lidar_pose_, remove_voxels_farther_than_);
+    if (gplan_) {  // each FilterMerge into its own map, with that map's far-voxel removal
+      for (const auto& [name, k] : gplan_->merges) {
+        if (!gplan_->alive.count(name)) continue;
+        const auto& m = gplan_->maps[k];
+        m.map->insertPointCloud(*(name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name)),
+                                last_lidar_pose_, m.remove_far);
+      }
+    } else {
+      local_map_->insertPointCloud(*for_map_, last_lidar_pose_, remove_voxels_farther_than_);
+    }
     rec.map_updated = true;
     if (rec.n_for_map == 0) map_known_nonempty_ = false;  // (nothing offered: ask the device next time)
     map_counts_pending_ = true;
@@ -994,6 +1315,34 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
 
 std::map<std::string, std::string> LidarOdometry::describePipeline() const {
   std::map<std::string, std::string> d;
+  if (gplan_) {
+    const GeneralPlan& g = *gplan_;
+    d["plan"] = "general";
+    d["timestamp_method"] = std::to_string(g.timestamp_method);
+    size_t k = 0;
+    for (const auto& st : g.steps) {
+      std::string line = "pass" + std::to_string(st.pass) + " " + st.cls.substr(st.cls.rfind(':') == std::string::npos ? 0 : st.cls.rfind(':') + 1);
+      if (st.kind == GeneralPlan::Kind::Delete) {
+        line += " ";
+        for (size_t i = 0; i < st.out.size(); i++) line += (i ? "," : "") + st.out[i];
+      } else {
+        line += " " + st.in + " ->";
+        for (size_t i = 0; i < st.out.size(); i++) line += (i ? "," : " ") + (st.out[i].empty() ? std::string("-") : st.out[i]);
+        if (st.bbox_mode != MH_BBOX_OFF) line += st.bbox_mode == MH_BBOX_KEEP_INSIDE ? " (inside)" : " (outside)";
+      }
+      char key[32];
+      snprintf(key, sizeof(key), "step:%02zu", k++);
+      d[key] = line;
+    }
+    d["steps"] = std::to_string(k);
+    for (const auto& m : g.maps) d["map:" + m.name] = m.def["class"].asString();
+    for (const auto& [layer, i] : g.merges) d["merge:" + layer] = g.maps[i].name;
+    d["map_class"] = g.maps[0].def["class"].asString();
+    d["icp_path"] = icp_[0] ? icp_[0]->alignPath() : "";
+    for (const auto& p : g.declaredParameters()) d["formula:" + p.name + (d.count("formula:" + p.name) ? "#" + std::to_string(d.size()) : "")] = p.expr;
+    for (const auto& p : params_.declaredParameters()) d["formula:" + p.name] = p.expr;
+    return d;
+  }
   if (!plan_) return d;
   d["layer_for_map"] = plan_->layer_for_map;
   d["layer_for_icp"] = plan_->layer_for_icp;

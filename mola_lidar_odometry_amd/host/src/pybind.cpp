@@ -144,6 +144,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["twist"] = std::vector<double>{r.twist.vx, r.twist.vy, r.twist.vz, r.twist.wx, r.twist.wy, r.twist.wz};
     d["decim_map_resolution"] = r.decim_map_resolution; d["decim_icp_resolution"] = r.decim_icp_resolution;
     d["map_voxel_size"] = r.map_voxel_size;
+    d["layer_sizes"] = r.layer_sizes;
     return d;
   };
   py::class_<LidarOdometry>(m, "LidarOdometry", py::dynamic_attr())
