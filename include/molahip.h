@@ -45,7 +45,8 @@ extern "C" {
 #define MH_VERSION_PATCH 0
 /* The parameter structs of this header carry no size field: they grow at the END, and every growth bumps MH_ABI_VERSION (6:
  * mh_preprocess_params' two decimation-method fields, round 5; 7: mh_layer_pair and mh_icp_align_layers, later also
- * mh_curvature_params and mh_scan_curvature: new structs and entry points change no existing layout, and a binder that lacks
+ * mh_curvature_params and mh_scan_curvature, then the intensity channel's entry points and mh_by_intensity_params: new structs
+ * and entry points change no existing layout, and a binder that lacks
  * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
  * built with) and zero-initialises every struct it passes -- a field the binder does not know then reads as its default. */
@@ -216,6 +217,10 @@ MH_API mh_status mh_scan_update(mh_scan* scan, const float* x, const float* y, c
  * MH_MEM_HOST_PINNED (asynchronous upload, see Conventions). */
 MH_API mh_status mh_scan_update_aos(mh_scan* scan, const void* data, size_t n, size_t point_step, size_t off_x,
                                     size_t off_y, size_t off_z, int64_t off_t, int32_t mem);
+/* The same, plus an optional float32 intensity at off_i (< 0: none; KITTI / MulRan rows: 12).  mh_scan_update_aos is the
+ * off_i = -1 case.  mh_scan_update and mh_scan_update_aos leave a scan without intensity. */
+MH_API mh_status mh_scan_update_aos_i(mh_scan* scan, const void* data, size_t n, size_t point_step, size_t off_x,
+                                      size_t off_y, size_t off_z, int64_t off_t, int64_t off_i, int32_t mem);
 /* Optional: queue the construction of the scan's search order for the tile matcher (large layers: the points sorted by
  * 2x2x2-voxel block of the local frame and cut into tiles) right behind an upload, for the voxel size of the
  * map it will be aligned against, so that it overlaps whatever else the device is doing.  Asynchronous on the context's
@@ -255,6 +260,11 @@ typedef struct {
 
 /* Attach per-point time stamps [s] (relative to the scan's reference time) to a scan of the same size. */
 MH_API mh_status mh_scan_set_timestamps(mh_scan* scan, const float* t, size_t n, int32_t mem);
+/* Attach a per-point intensity to a scan of the same size (the optional channel of the intensity filters below).  Every call
+ * that derives a layer -- mh_scan_preprocess(_batch), mh_scan_deskew(_pair), mh_scan_curvature, mh_scan_by_intensity --
+ * gives its outputs the input's intensity when the input has one: out.i[k] == raw.i[out.src_idx[k]], bit for bit.  Maps,
+ * matching and alignment ignore the channel. */
+MH_API mh_status mh_scan_set_intensity(mh_scan* scan, const float* i, size_t n, int32_t mem);
 /* raw -> decimate(map res) -> by-range -> bounding box -> out_map -> decimate(icp res) -> out_icp (may be NULL).
  * Survivors keep the raw order (upstream's FirstPoint decimation emits them in the iteration order of its hash
  * container, which is implementation-defined: same set, deterministic order here).  The outputs carry adjusted
@@ -309,8 +319,32 @@ typedef struct {
 } mh_curvature_params;
 MH_API mh_status mh_scan_curvature(const mh_scan* in, const mh_curvature_params* p, mh_scan* out_larger, mh_scan* out_smaller,
                                    mh_scan* out_other);
+/* FilterNormalizeIntensity [U] (extras/lidar3d-intensity.yaml:260-263), in place on `layer`.  Upstream's source is not
+ * vendored: a restatement, parity unpinned.  A layer without intensity: MH_ERR_INVALID_ARGUMENT, the layer untouched.
+ *   lo, hi = min and max of the layer's non-NaN intensities;
+ *   range: a HOST pointer or NULL.  NULL = remember_intensity_range: false.  Otherwise it holds the remembered {min, max} on
+ *     entry ({NaN, NaN}: none yet); lo and hi are widened by it and the result is written back;
+ *   no non-NaN value and nothing remembered: the layer and `range` stay unchanged;
+ *   d = hi - lo;  k = d > 0 ? 1.0f / d : 0.0f (correctly rounded);
+ *   every value I becomes (I - lo) * k, in float, unfused (NaN stays NaN).
+ * Queued on the layer's context stream; one wait ends the call. */
+MH_API mh_status mh_scan_normalize_intensity(mh_scan* layer, float range[2]);
+/* FilterByIntensity [U] (extras/lidar3d-intensity.yaml:265-270): I < low_threshold -> low; else I > high_threshold -> high;
+ * else mid (NaN lands in mid).  Each output keeps the input order and carries xyz, time stamps (when the input has them),
+ * the intensity, and src_idx = the input's src_idx when it has one, else the input index.  Any output may be NULL, not all of
+ * them; the outputs differ from `in` and from each other; all scans belong to one context.  An input without intensity:
+ * MH_ERR_INVALID_ARGUMENT, the outputs untouched.  Layers of up to 2^21 - 1 points (the packed counters of
+ * mh_scan_curvature, whose scan and scatter this call shares); one read-back of the three counts ends the call. */
+typedef struct {
+  float low_threshold;   /* values below: output_layer_low_intensity */
+  float high_threshold;  /* values above: output_layer_high_intensity */
+} mh_by_intensity_params;
+MH_API mh_status mh_scan_by_intensity(const mh_scan* in, const mh_by_intensity_params* p, mh_scan* out_low, mh_scan* out_mid,
+                                      mh_scan* out_high);
 /* Copy a scan to HOST arrays (any may be NULL; t / src_idx are zero-filled when the scan has none). */
 MH_API mh_status mh_scan_download(const mh_scan* scan, float* x, float* y, float* z, float* t, uint32_t* src_idx);
+/* Copy a scan's intensity to a HOST array of n entries; MH_ERR_INVALID_ARGUMENT when the scan carries none. */
+MH_API mh_status mh_scan_download_intensity(const mh_scan* scan, float* i);
 
 /* ------------------------------------------------------------------------------------------------
  * Matcher-granular path.  Replaces mp2p_icp::Matcher_Points_DistanceThreshold::implMatchOneLayer [U]

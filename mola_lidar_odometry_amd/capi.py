@@ -137,6 +137,10 @@ class CurvatureParams(C.Structure):
     _fields_ = [("max_cosine", C.c_float), ("min_clearance", C.c_float), ("max_gap", C.c_float)]
 
 
+class ByIntensityParams(C.Structure):
+    _fields_ = [("low_threshold", C.c_float), ("high_threshold", C.c_float)]
+
+
 TS_NONE, TS_MIDDLE_IS_ZERO, TS_EARLIEST_IS_ZERO = 0, 1, 2
 DECIMATE_FIRST_POINT, DECIMATE_CLOSEST_TO_AVERAGE = 0, 1
 BBOX_OFF, BBOX_KEEP_OUTSIDE, BBOX_KEEP_INSIDE = 0, 1, 2
@@ -169,20 +173,26 @@ _SIGNATURES = {
     "mh_scan_update": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
     "mh_scan_update_aos": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                        C.c_int64, C.c_int32]),
+    "mh_scan_update_aos_i": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                         C.c_int64, C.c_int64, C.c_int32]),
     "mh_scan_prepare": (C.c_int32, [C.c_void_p, C.c_float]),
     "mh_scan_destroy": (C.c_int32, [C.c_void_p]),
     "mh_scan_size": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "mh_map_insert": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_float]),
     "mh_scan_set_timestamps": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
+    "mh_scan_set_intensity": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
     "mh_scan_preprocess": (C.c_int32, [C.c_void_p, C.POINTER(PreprocessParams), C.c_void_p, C.c_void_p]),
     "mh_scan_preprocess_batch": (C.c_int32, [C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(PreprocessParams), C.c_size_t,
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "mh_scan_deskew": (C.c_int32, [C.c_void_p, _DP, C.c_void_p]),
     "mh_scan_deskew_pair": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_void_p, C.c_void_p, _FP, _FP, C.POINTER(C.c_uint64)]),
     "mh_scan_curvature": (C.c_int32, [C.c_void_p, C.POINTER(CurvatureParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mh_scan_normalize_intensity": (C.c_int32, [C.c_void_p, _FP]),
+    "mh_scan_by_intensity": (C.c_int32, [C.c_void_p, C.POINTER(ByIntensityParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mh_host_alloc_pinned": (C.c_int32, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "mh_host_free_pinned": (C.c_int32, [C.c_void_p]),
     "mh_scan_download": (C.c_int32, [C.c_void_p, _FP, _FP, _FP, _FP, _UP]),
+    "mh_scan_download_intensity": (C.c_int32, [C.c_void_p, _FP]),
     "mh_scan_bbox": (C.c_int32, [C.c_void_p, _FP, _FP, C.POINTER(C.c_uint64)]),
     "mh_nn_search": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_double, C.c_double, C.POINTER(PairsOut), C.c_int32,
                                  C.POINTER(MatchInfo)]),
@@ -433,6 +443,29 @@ class Scan:
         _chk(lib().mh_scan_set_timestamps(self._h, _vp(t), len(t), MEM_HOST))
         return self
 
+    def set_intensity(self, i):
+        """Attach a per-point intensity (mh_scan_set_intensity); derived layers carry it along."""
+        i = _f32(i)
+        _chk(lib().mh_scan_set_intensity(self._h, _vp(i), len(i), MEM_HOST))
+        return self
+
+    def download_intensity(self):
+        """The intensity channel (mh_scan_download_intensity); CapiError when the scan carries none."""
+        n = len(self)
+        i = np.zeros(max(n, 1), np.float32)
+        _chk(lib().mh_scan_download_intensity(self._h, i.ctypes.data_as(_FP)))
+        return i[:n]
+
+    def normalize_intensity(self, range_=None):
+        """FilterNormalizeIntensity in place (mh_scan_normalize_intensity).  range_: None (remember_intensity_range: false)
+        or a float32 array of 2, the remembered {min, max} ({nan, nan}: none yet), updated in place."""
+        return scan_normalize_intensity(self, range_)
+
+    def by_intensity(self, params: "ByIntensityParams", out_low: "Scan | None", out_mid: "Scan | None" = None,
+                     out_high: "Scan | None" = None):
+        """FilterByIntensity on the device (mh_scan_by_intensity): self = the input layer; any output may be None."""
+        return scan_by_intensity(self, params, out_low, out_mid, out_high)
+
     def preprocess(self, params: "PreprocessParams", out_map: "Scan", out_icp: "Scan | None" = None):
         """1st-pass observation filters on the device (mh_scan_preprocess): self = raw scan."""
         _chk(lib().mh_scan_preprocess(self._h, C.byref(params), out_map._h, out_icp._h if out_icp is not None else None))
@@ -496,6 +529,12 @@ class Scan:
         """Asynchronous upload of n interleaved records from page-locked host memory (MH_MEM_HOST_PINNED): ONE copy of the
         raw bytes + the de-interleave kernel, queued on the context's stream; returns at once."""
         _chk(lib().mh_scan_update_aos(self._h, C.c_void_p(ptr), n, point_step, off_x, off_y, off_z, off_t, MEM_HOST_PINNED))
+
+    def update_interleaved_i(self, records, off_x=0, off_y=4, off_z=8, off_t=-1, off_i=-1):
+        """update_interleaved plus a float32 intensity at byte offset off_i (< 0: none; KITTI rows: 12), mh_scan_update_aos_i."""
+        a = np.ascontiguousarray(records, dtype=np.float32)
+        assert a.ndim == 2
+        _chk(lib().mh_scan_update_aos_i(self._h, _vp(a), a.shape[0], a.shape[1] * 4, off_x, off_y, off_z, off_t, off_i, MEM_HOST))
 
     def update_interleaved(self, records, off_x=0, off_y=4, off_z=8, off_t=-1):
         """records: C-contiguous float32 [n,k] rows (KITTI .bin: k=4) -- one copy, de-interleaved on the device."""
@@ -926,6 +965,29 @@ def scan_curvature(scan: "Scan", params: "CurvatureParams", out_larger: "Scan | 
     h = lambda sc: sc._h if sc is not None else None
     _chk(lib().mh_scan_curvature(scan._h, C.byref(params), h(out_larger), h(out_smaller), h(out_other)))
     return out_larger, out_smaller, out_other
+
+
+def scan_normalize_intensity(scan: "Scan", range_=None):
+    """mh_scan_normalize_intensity (molahip.h states the rule).  range_: None, or a float32 array of 2 updated in place.
+    Returns range_."""
+    if range_ is not None:
+        assert isinstance(range_, np.ndarray) and range_.dtype == np.float32 and range_.shape == (2,) and range_.flags.c_contiguous
+    _chk(lib().mh_scan_normalize_intensity(scan._h, range_.ctypes.data_as(_FP) if range_ is not None else None))
+    return range_
+
+
+def scan_by_intensity(scan: "Scan", params: "ByIntensityParams", out_low: "Scan | None", out_mid: "Scan | None" = None,
+                      out_high: "Scan | None" = None):
+    """mh_scan_by_intensity: split `scan` into its low-, mid- and high-intensity points (molahip.h states the rule).  Returns the
+    three outputs (None where none was given)."""
+    h = lambda sc: sc._h if sc is not None else None
+    _chk(lib().mh_scan_by_intensity(scan._h, C.byref(params), h(out_low), h(out_mid), h(out_high)))
+    return out_low, out_mid, out_high
+
+
+def by_intensity_params(low_threshold=0.1, high_threshold=0.9) -> ByIntensityParams:
+    """Defaults: the values of extras/lidar3d-intensity.yaml's FilterByIntensity."""
+    return ByIntensityParams(float(low_threshold), float(high_threshold))
 
 
 def curvature_params(max_cosine=0.4, min_clearance=0.20, max_gap=1.0) -> CurvatureParams:

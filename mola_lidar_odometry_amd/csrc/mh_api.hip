@@ -44,13 +44,14 @@ mh_status stage_in(mh_ctx* ctx, DevBuf& buf, size_t offset_bytes, const void* sr
   return MH_OK;
 }
 
-mh_status scan_alloc(mh_scan* s, size_t n, bool with_t, bool with_src) {
+mh_status scan_alloc(mh_scan* s, size_t n, bool with_t, bool with_src, bool with_i) {
   mh_ctx* ctx = s->ctx;
   const size_t stride = ((n * sizeof(float) + 255) / 256) * 256;
-  if (s->xyz.bytes < 3 * stride || (s->aux.bytes < 2 * stride && (with_t || with_src))) {
+  if (s->xyz.bytes < 3 * stride || (s->aux.bytes < 2 * stride && (with_t || with_src)) || (with_i && (s->ibuf.bytes < stride || !s->ibuf.p))) {
     MH_HIP(mh::wait_stream(ctx->stream));  // nobody may still read the old buffers
     MH_TRY(s->xyz.reserve(3 * stride ? 3 * stride : 256));
     if (with_t || with_src) MH_TRY(s->aux.reserve(2 * stride ? 2 * stride : 256));
+    if (with_i) MH_TRY(s->ibuf.reserve(stride ? stride : 256));
   }
   char* base = s->xyz.as<char>();
   s->x = (const float*)base;
@@ -58,6 +59,7 @@ mh_status scan_alloc(mh_scan* s, size_t n, bool with_t, bool with_src) {
   s->z = (const float*)(base + 2 * stride);
   s->t = with_t ? (const float*)s->aux.as<char>() : nullptr;
   s->src = with_src ? (const uint32_t*)(s->aux.as<char>() + stride) : nullptr;
+  s->i = with_i ? s->ibuf.as<const float>() : nullptr;
   s->n = n;
   scan_drop_tiles(s);
   return MH_OK;
@@ -271,6 +273,7 @@ static mh_status scan_set(mh_scan* s, const float* x, const float* y, const floa
   s->z = (const float*)(base + 2 * stride);
   s->t = nullptr;  // new points: whatever channels the old ones carried are gone
   s->src = nullptr;
+  s->i = nullptr;
   s->n = n;
   scan_drop_tiles(s);
   return MH_OK;
@@ -287,6 +290,7 @@ mh_status mh_scan_create(mh_ctx* ctx, const float* x, const float* y, const floa
   if (st != MH_OK) {
     s->xyz.release();
     s->aux.release();
+    s->ibuf.release();
     scan_free_tiles(s);
     delete s;
     return st;
@@ -306,6 +310,7 @@ mh_status mh_scan_destroy(mh_scan* scan) {
   (void)mh::wait_stream(scan->ctx->stream);
   scan->xyz.release();
   scan->aux.release();
+  scan->ibuf.release();
   scan_free_tiles(scan);
   delete scan;
   return MH_OK;

@@ -250,8 +250,10 @@ struct mh_scan {
   mh_ctx* ctx = nullptr;
   mh::DevBuf xyz;  // own storage: x[n] | y[n] | z[n] (SoA, 256-byte aligned sections)
   mh::DevBuf aux;  // optional channels: t[n] | src[n]
+  mh::DevBuf ibuf;  // optional intensity channel i[n] (a buffer of its own: the paths that size `aux` stay as they are)
   const float *x = nullptr, *y = nullptr, *z = nullptr;  // device pointers actually used
   const float* t = nullptr;       // per-point time stamps [s] or null
+  const float* i = nullptr;       // per-point intensity or null (maps and alignments ignore it)
   const uint32_t* src = nullptr;  // index of each point in the raw scan it was filtered from, or null
   size_t n = 0;
   // Search order of the tile matcher (mh_tile.hip), a cache that belongs to the point content: the points sorted by
@@ -277,8 +279,8 @@ hipError_t wait_event(hipEvent_t e);
 mh_status set_device(const mh_ctx* ctx);
 // copy `n` elements of a caller array living in `mem` into device scratch (returns device ptr)
 mh_status stage_in(mh_ctx* ctx, DevBuf& buf, size_t offset_bytes, const void* src, size_t bytes, int32_t mem);
-// (re)size a scan's own storage for n points (+ optional t / src channels) and point x,y,z,t,src at it
-mh_status scan_alloc(mh_scan* s, size_t n, bool with_t, bool with_src);
+// (re)size a scan's own storage for n points (+ optional t / src / intensity channels) and point x,y,z,t,src,i at it
+mh_status scan_alloc(mh_scan* s, size_t n, bool with_t, bool with_src, bool with_i = false);
 // map (re)build from device arrays; src_ids null = identity.  evict: 0 or {cx,cy,cz,dist_in_grid} voxel test.
 // n_stored: the first n_stored inputs are points the map already stores (accepted by the insertion rules before).
 // sorted copy + tile table of a scan for voxel size 1/inv_vs (no-op when valid); asynchronous on the scan's stream,

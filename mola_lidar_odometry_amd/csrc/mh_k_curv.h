@@ -42,14 +42,16 @@ __global__ __launch_bounds__(256) void k_curv_classify(const float* __restrict__
 
 struct CurvOut {
   float *x, *y, *z, *t;  // t null: no time stamps (the input has none)
+  float* i;              // null: no intensity (the input has none)
   uint32_t* src;         // null: this output was not asked for
 };
 
-// scatter every classified point to its output; the first lane also writes the three counts (the scan's total) to
+// scatter every classified point to its output (also the words of k_int_classify, mh_k_intensity.h); the first lane also writes the three counts (the scan's total) to
 // page-locked host memory
 __global__ __launch_bounds__(256) void k_curv_scatter(const float* __restrict__ x, const float* __restrict__ y,
                                                       const float* __restrict__ z, const float* __restrict__ t,
-                                                      const uint32_t* __restrict__ src, uint32_t n, uint32_t cap,
+                                                      const float* __restrict__ in_i, const uint32_t* __restrict__ src,
+                                                      uint32_t n, uint32_t cap,
                                                       const unsigned long long* __restrict__ word,
                                                       const unsigned long long* __restrict__ pos, CurvOut o0, CurvOut o1,
                                                       CurvOut o2, uint32_t* __restrict__ host_counts) {
@@ -76,6 +78,7 @@ __global__ __launch_bounds__(256) void k_curv_scatter(const float* __restrict__ 
   oy[k] = y[i];
   oz[k] = z[i];
   if (t) (f == 0u ? o0.t : f == 1u ? o1.t : o2.t)[k] = t[i];
+  if (in_i) (f == 0u ? o0.i : f == 1u ? o1.i : o2.i)[k] = in_i[i];
   osrc[k] = src ? src[i] : i;
 }
 

@@ -9,6 +9,9 @@
 //   (flags) -> exclusive scan -> order-preserving compaction (survivors keep the raw order)
 //   FilterDeskew            -> p' = Exp_SO3(w t_i) p + v t_i, fp64, rounded to float
 //   FilterCurvature         -> three-point stencil, one scan of packed class counters, three-way compaction (mh_k_curv.h)
+//   FilterNormalizeIntensity / FilterByIntensity -> min / max reduction + in-place rewrite; thresholds through the
+//                              curvature filter's scan and scatter (mh_k_intensity.h)
+// Every call that derives a layer carries the input's optional intensity channel along (out.i[k] == raw.i[out.src[k]]).
 // All of it is HBM-bound byte/index work: coalesced SoA streams, one pass per stage, atomics only on the
 // (L2-resident) decimation table.
 #include <string.h>
@@ -18,6 +21,7 @@
 #include "mh_internal.h"
 #include "mh_nn_device.h"
 #include "mh_k_curv.h"
+#include "mh_k_intensity.h"
 
 using namespace mh;
 
@@ -257,14 +261,15 @@ __device__ __forceinline__ void deskew_point(const Twist& tw, float x, float y, 
 }
 
 __global__ void k_pp_deskew(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-                            const float* __restrict__ t, const uint32_t* __restrict__ src, uint32_t n, Twist tw,
-                            float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz,
-                            float* __restrict__ ot, uint32_t* __restrict__ osrc) {
+                            const float* __restrict__ t, const uint32_t* __restrict__ src, const float* __restrict__ in_i,
+                            uint32_t n, Twist tw, float* __restrict__ ox, float* __restrict__ oy, float* __restrict__ oz,
+                            float* __restrict__ ot, uint32_t* __restrict__ osrc, float* __restrict__ oi) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float tf = t[i];
   ot[i] = tf;
   if (src) osrc[i] = src[i];
+  if (in_i) oi[i] = in_i[i];
   float gx, gy, gz;
   deskew_point(tw, x[i], y[i], z[i], tf, gx, gy, gz);
   ox[i] = gx;
@@ -279,8 +284,10 @@ __global__ void k_pp_deskew(const float* __restrict__ x, const float* __restrict
 struct DeskewLayer {
   const float *x, *y, *z, *t;
   const uint32_t* src;
+  const float* i;  // null: no intensity
   float *ox, *oy, *oz, *ot;
   uint32_t* osrc;
+  float* oi;
   uint32_t n;
 };
 
@@ -291,6 +298,7 @@ __global__ __launch_bounds__(1024) void k_pp_deskew_pair(DeskewLayer big, Deskew
     const float tf = big.t[i];
     big.ot[i] = tf;
     if (big.src) big.osrc[i] = big.src[i];
+    if (big.i) big.oi[i] = big.i[i];
     float gx, gy, gz;
     deskew_point(tw, big.x[i], big.y[i], big.z[i], tf, gx, gy, gz);
     big.ox[i] = gx;
@@ -304,6 +312,7 @@ __global__ __launch_bounds__(1024) void k_pp_deskew_pair(DeskewLayer big, Deskew
     const float tf = small.t[i];
     small.ot[i] = tf;
     if (small.src) small.osrc[i] = small.src[i];
+    if (small.i) small.oi[i] = small.i[i];
     float p[3];
     deskew_point(tw, small.x[i], small.y[i], small.z[i], tf, p[0], p[1], p[2]);
     small.ox[i] = p[0];
@@ -344,8 +353,8 @@ __global__ __launch_bounds__(1024) void k_pp_deskew_pair(DeskewLayer big, Deskew
 
 // interleaved records (step/offsets in 4-byte words) -> SoA
 __global__ void k_pp_deinterleave(const uint32_t* __restrict__ data, uint32_t n, uint32_t step, uint32_t ox, uint32_t oy,
-                                  uint32_t oz, int32_t ot, float* __restrict__ x, float* __restrict__ y,
-                                  float* __restrict__ z, float* __restrict__ t) {
+                                  uint32_t oz, int32_t ot, int32_t oi, float* __restrict__ x, float* __restrict__ y,
+                                  float* __restrict__ z, float* __restrict__ t, float* __restrict__ inten) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t* rec = data + (size_t)i * step;
@@ -353,6 +362,7 @@ __global__ void k_pp_deinterleave(const uint32_t* __restrict__ data, uint32_t n,
   y[i] = __uint_as_float(rec[oy]);
   z[i] = __uint_as_float(rec[oz]);
   if (ot >= 0) t[i] = __uint_as_float(rec[ot]);
+  if (oi >= 0) inten[i] = __uint_as_float(rec[oi]);
 }
 
 inline uint32_t nblk(size_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
@@ -377,6 +387,8 @@ struct PpJob {
   uint32_t* msrc;
   float *ix, *iy, *iz, *it;    // out_icp
   uint32_t* isrc;
+  const float* in_i;           // raw intensity (null: none, and both outputs carry none)
+  float *mi, *ii;              // out_map / out_icp intensity
 };
 
 __global__ __launch_bounds__(256) void k_pp_init_b(const PpJob* __restrict__ jobs) {
@@ -652,12 +664,14 @@ __global__ __launch_bounds__(256) void k_pp_compact_b(const PpJob* __restrict__ 
       G(j.mt)[o] = tv;
     }
     G(j.msrc)[o] = j.src ? G(j.src)[i] : i;
+    if (j.in_i) G(j.mi)[o] = G(j.in_i)[i];  // (the kept point's own value, whichever decimation method chose it)
   } else {
     G(j.ix)[o] = G(j.mx)[i];
     G(j.iy)[o] = G(j.my)[i];
     G(j.iz)[o] = G(j.mz)[i];
     if (j.want_t) G(j.it)[o] = G(j.mt)[i];  // out_map's stamps are adjusted already
     G(j.isrc)[o] = G(j.msrc)[i];
+    if (j.in_i) G(j.ii)[o] = G(j.mi)[i];
   }
 }
 
@@ -749,11 +763,15 @@ mh_status preprocess_batch(size_t n_jobs, const mh_scan* const* raws, const mh_p
     j.first2 = j.first1 + j.tsize1;
     table_off += (size_t)j.tsize1 + j.tsize2;
     j.counters = d_counts + 8 * k;
-    MH_TRY(scan_alloc(om, n, has_t, true));  // capacity: the raw size; the real counts arrive with the read-back below
+    const bool has_i = raw->i != nullptr;
+    j.in_i = raw->i;
+    MH_TRY(scan_alloc(om, n, has_t, true, has_i));  // capacity: the raw size; the real counts arrive with the read-back below
     j.mx = (float*)om->x; j.my = (float*)om->y; j.mz = (float*)om->z; j.mt = (float*)om->t; j.msrc = (uint32_t*)om->src;
+    j.mi = (float*)om->i;
     if (oi) {
-      MH_TRY(scan_alloc(oi, n, has_t, true));
+      MH_TRY(scan_alloc(oi, n, has_t, true, has_i));
       j.ix = (float*)oi->x; j.iy = (float*)oi->y; j.iz = (float*)oi->z; j.it = (float*)oi->t; j.isrc = (uint32_t*)oi->src;
+      j.ii = (float*)oi->i;
       any_icp = true;
     }
     any_t = any_t || (has_t && p->timestamp_method != MH_TS_NONE);
@@ -869,8 +887,44 @@ mh_status mh_scan_set_timestamps(mh_scan* scan, const float* t, size_t n, int32_
   return MH_OK;
 }
 
+mh_status mh_scan_set_intensity(mh_scan* scan, const float* i, size_t n, int32_t mem) {
+  MH_REQUIRE(scan, "null scan");
+  MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE, "bad mem space");
+  MH_REQUIRE(n == scan->n, "intensity count differs from the scan size");
+  MH_REQUIRE(n == 0 || i, "null intensities");
+  mh_ctx* ctx = scan->ctx;
+  MH_TRY(set_device(ctx));
+  const size_t stride = ((n * sizeof(float) + 255) / 256) * 256;
+  if (scan->ibuf.bytes < stride || !scan->ibuf.p) {
+    MH_HIP(mh::wait_stream(ctx->stream));
+    MH_TRY(scan->ibuf.reserve(stride ? stride : 256));
+  }
+  if (n) {
+    MH_HIP(hipMemcpyAsync(scan->ibuf.p, i, n * sizeof(float),
+                          mem == MH_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
+    if (mem == MH_MEM_HOST) MH_HIP(mh::wait_stream(ctx->stream));  // host array is borrowed for the call only
+  }
+  scan->i = scan->ibuf.as<const float>();
+  return MH_OK;
+}
+
+mh_status mh_scan_download_intensity(const mh_scan* scan, float* i) {
+  MH_REQUIRE(scan && i, "null argument");
+  MH_REQUIRE(scan->i, "the scan carries no intensity");
+  mh_ctx* ctx = scan->ctx;
+  MH_TRY(set_device(ctx));
+  if (scan->n) MH_HIP(hipMemcpyAsync(i, scan->i, scan->n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  MH_HIP(mh::wait_stream(ctx->stream));
+  return MH_OK;
+}
+
 mh_status mh_scan_update_aos(mh_scan* scan, const void* data, size_t n, size_t point_step, size_t off_x, size_t off_y,
                              size_t off_z, int64_t off_t, int32_t mem) {
+  return mh_scan_update_aos_i(scan, data, n, point_step, off_x, off_y, off_z, off_t, -1, mem);
+}
+
+mh_status mh_scan_update_aos_i(mh_scan* scan, const void* data, size_t n, size_t point_step, size_t off_x, size_t off_y,
+                               size_t off_z, int64_t off_t, int64_t off_i, int32_t mem) {
   MH_REQUIRE(scan, "null scan");
   MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE || mem == MH_MEM_HOST_PINNED, "bad mem space");
   MH_REQUIRE(n == 0 || data, "null data");
@@ -879,15 +933,18 @@ mh_status mh_scan_update_aos(mh_scan* scan, const void* data, size_t n, size_t p
   MH_REQUIRE(off_x % 4 == 0 && off_y % 4 == 0 && off_z % 4 == 0 && off_x + 4 <= point_step && off_y + 4 <= point_step &&
                  off_z + 4 <= point_step, "coordinate offsets must be multiples of 4 inside the record");
   MH_REQUIRE(off_t < 0 || (off_t % 4 == 0 && (size_t)off_t + 4 <= point_step), "time stamp offset must be a multiple of 4 inside the record");
+  MH_REQUIRE(off_i < 0 || (off_i % 4 == 0 && (size_t)off_i + 4 <= point_step), "intensity offset must be a multiple of 4 inside the record");
   mh_ctx* ctx = scan->ctx;
   MH_TRY(set_device(ctx));
   hipStream_t s = ctx->stream;
   const size_t stride = ((n * sizeof(float) + 255) / 256) * 256;
   const size_t raw_bytes = n * point_step;
-  if (scan->xyz.bytes < 3 * stride || (off_t >= 0 && scan->aux.bytes < 2 * stride) || ctx->build_a.bytes < raw_bytes) {
+  if (scan->xyz.bytes < 3 * stride || (off_t >= 0 && scan->aux.bytes < 2 * stride) || ctx->build_a.bytes < raw_bytes ||
+      (off_i >= 0 && (scan->ibuf.bytes < stride || !scan->ibuf.p))) {
     MH_HIP(mh::wait_stream(s));  // nobody may still read the old buffers
     MH_TRY(scan->xyz.reserve(3 * stride ? 3 * stride : 256));
     if (off_t >= 0) MH_TRY(scan->aux.reserve(2 * stride ? 2 * stride : 256));
+    if (off_i >= 0) MH_TRY(scan->ibuf.reserve(stride ? stride : 256));
     MH_TRY(ctx->build_a.reserve(raw_bytes ? raw_bytes : 256));
   }
   char* base = scan->xyz.as<char>();
@@ -896,6 +953,7 @@ mh_status mh_scan_update_aos(mh_scan* scan, const void* data, size_t n, size_t p
   scan->z = (const float*)(base + 2 * stride);
   scan->t = off_t >= 0 ? (const float*)scan->aux.p : nullptr;
   scan->src = nullptr;
+  scan->i = off_i >= 0 ? scan->ibuf.as<const float>() : nullptr;
   scan->n = n;
   scan_drop_tiles(scan);
   if (!n) return MH_OK;
@@ -906,7 +964,8 @@ mh_status mh_scan_update_aos(mh_scan* scan, const void* data, size_t n, size_t p
   }
   hipLaunchKernelGGL(k_pp_deinterleave, dim3(nblk(n, 256)), dim3(256), 0, s, recs, (uint32_t)n, (uint32_t)(point_step / 4),
                      (uint32_t)(off_x / 4), (uint32_t)(off_y / 4), (uint32_t)(off_z / 4), off_t >= 0 ? (int32_t)(off_t / 4) : -1,
-                     (float*)scan->x, (float*)scan->y, (float*)scan->z, (float*)scan->t);
+                     off_i >= 0 ? (int32_t)(off_i / 4) : -1, (float*)scan->x, (float*)scan->y, (float*)scan->z,
+                     (float*)scan->t, (float*)scan->i);
   MH_HIP(hipGetLastError());
   if (mem != MH_MEM_HOST_PINNED) MH_HIP(mh::wait_stream(s));  // `data` is borrowed for the call only
   return MH_OK;
@@ -960,7 +1019,7 @@ mh_status mh_scan_deskew(const mh_scan* in, const double twist[6], mh_scan* out)
   MH_TRY(set_device(ctx));
   hipStream_t s = ctx->stream;
   const size_t n = in->n;
-  MH_TRY(scan_alloc(out, n, in->t != nullptr, in->src != nullptr));
+  MH_TRY(scan_alloc(out, n, in->t != nullptr, in->src != nullptr, in->i != nullptr));
   if (!n) return MH_OK;
   if (twist && in->t) {
     Twist tw;
@@ -968,12 +1027,14 @@ mh_status mh_scan_deskew(const mh_scan* in, const double twist[6], mh_scan* out)
       MH_REQUIRE(isfinite(twist[i]), "non-finite twist");
       tw.v[i] = twist[i];
     }
-    hipLaunchKernelGGL(k_pp_deskew, dim3(nblk(n, 256)), dim3(256), 0, s, in->x, in->y, in->z, in->t, in->src,
-                       (uint32_t)n, tw, (float*)out->x, (float*)out->y, (float*)out->z, (float*)out->t, (uint32_t*)out->src);
+    hipLaunchKernelGGL(k_pp_deskew, dim3(nblk(n, 256)), dim3(256), 0, s, in->x, in->y, in->z, in->t, in->src, in->i,
+                       (uint32_t)n, tw, (float*)out->x, (float*)out->y, (float*)out->z, (float*)out->t, (uint32_t*)out->src,
+                       (float*)out->i);
     MH_HIP(hipGetLastError());
   } else {  // skip_deskew / silently_ignore_no_timestamps
     if (in->t) MH_HIP(hipMemcpyAsync((void*)out->t, in->t, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (in->src) MH_HIP(hipMemcpyAsync((void*)out->src, in->src, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    if (in->i) MH_HIP(hipMemcpyAsync((void*)out->i, in->i, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     MH_HIP(hipMemcpyAsync((void*)out->x, in->x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     MH_HIP(hipMemcpyAsync((void*)out->y, in->y, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     MH_HIP(hipMemcpyAsync((void*)out->z, in->z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -981,11 +1042,12 @@ mh_status mh_scan_deskew(const mh_scan* in, const double twist[6], mh_scan* out)
   return MH_OK;
 }
 
-mh_status mh_scan_curvature(const mh_scan* in, const mh_curvature_params* p, mh_scan* out_larger, mh_scan* out_smaller,
-                            mh_scan* out_other) {
-  MH_REQUIRE(in && p, "null argument");
-  mh_scan* outs[3] = {out_larger, out_smaller, out_other};
-  MH_REQUIRE(out_larger || out_smaller || out_other, "all outputs are NULL");
+// The host half of the three-way splits (mh_scan_curvature, mh_scan_by_intensity): argument checks, outputs sized for the
+// input, `classify(word, cap)` queues the kernel that writes every point's packed class word (mh_k_curv.h), then one scan of
+// the words, one scatter and one read-back of the three counts.  Inputs of fewer than `min_n` points leave the outputs empty.
+extern "C++" template <class Classify>
+static mh_status split3(const mh_scan* in, mh_scan* const (&outs)[3], size_t min_n, Classify classify) {
+  MH_REQUIRE(outs[0] || outs[1] || outs[2], "all outputs are NULL");
   for (int k = 0; k < 3; k++) {
     if (!outs[k]) continue;
     MH_REQUIRE(outs[k] != in, "an output is the input scan");
@@ -997,10 +1059,9 @@ mh_status mh_scan_curvature(const mh_scan* in, const mh_curvature_params* p, mh_
   MH_TRY(set_device(ctx));
   hipStream_t s = ctx->stream;
   const size_t n = in->n;
-  const bool has_t = in->t != nullptr;
   for (mh_scan* o : outs)  // capacity: the input size; the real counts arrive with the read-back below
-    if (o) MH_TRY(scan_alloc(o, n, has_t, true));
-  if (n < 3) {  // no interior point
+    if (o) MH_TRY(scan_alloc(o, n, in->t != nullptr, true, in->i != nullptr));
+  if (n < min_n) {
     for (mh_scan* o : outs)
       if (o) o->n = 0;
     return MH_OK;
@@ -1014,9 +1075,7 @@ mh_status mh_scan_curvature(const mh_scan* in, const mh_curvature_params* p, mh_
   MH_TRY(ctx->sort_tmp.reserve(tmp));
   if (!ctx->h_small) MH_HIP(hipHostMalloc((void**)&ctx->h_small, 64 * sizeof(uint32_t), hipHostMallocDefault));
   uint32_t* h_counts = ctx->h_small + 16;  // (slots 0..6: mh_scan_bbox / mh_scan_deskew_pair)
-  const float gap2 = p->max_gap * p->max_gap, clr2 = p->min_clearance * p->min_clearance;
-  hipLaunchKernelGGL(k_curv_classify, dim3(cap / 256), dim3(256), 0, s, in->x, in->y, in->z, (uint32_t)n, cap, p->max_cosine, clr2,
-                     gap2, word);
+  classify(s, word, cap);
   size_t tb = ctx->sort_tmp.bytes;
   MH_HIP(rocprim::exclusive_scan(ctx->sort_tmp.p, tb, word, pos, 0ull, (size_t)cap, rocprim::plus<unsigned long long>(), s));
   CurvOut co[3];
@@ -1026,14 +1085,70 @@ mh_status mh_scan_curvature(const mh_scan* in, const mh_curvature_params* p, mh_
     co[k].y = o ? (float*)o->y : nullptr;
     co[k].z = o ? (float*)o->z : nullptr;
     co[k].t = o ? (float*)o->t : nullptr;
+    co[k].i = o ? (float*)o->i : nullptr;
     co[k].src = o ? (uint32_t*)o->src : nullptr;
   }
-  hipLaunchKernelGGL(k_curv_scatter, dim3(cap / 256), dim3(256), 0, s, in->x, in->y, in->z, in->t, in->src, (uint32_t)n, cap,
-                     word, pos, co[0], co[1], co[2], h_counts);
+  hipLaunchKernelGGL(k_curv_scatter, dim3(cap / 256), dim3(256), 0, s, in->x, in->y, in->z, in->t, in->i, in->src, (uint32_t)n,
+                     cap, word, pos, co[0], co[1], co[2], h_counts);
   MH_HIP(hipGetLastError());
   MH_HIP(mh::wait_stream(s));
   for (int k = 0; k < 3; k++)
     if (outs[k]) outs[k]->n = h_counts[k];
+  return MH_OK;
+}
+
+mh_status mh_scan_curvature(const mh_scan* in, const mh_curvature_params* p, mh_scan* out_larger, mh_scan* out_smaller,
+                            mh_scan* out_other) {
+  MH_REQUIRE(in && p, "null argument");
+  mh_scan* const outs[3] = {out_larger, out_smaller, out_other};
+  const float gap2 = p->max_gap * p->max_gap, clr2 = p->min_clearance * p->min_clearance, max_cosine = p->max_cosine;
+  return split3(in, outs, 3, [&](hipStream_t s, unsigned long long* word, uint32_t cap) {  // (fewer than 3: no interior point)
+    hipLaunchKernelGGL(k_curv_classify, dim3(cap / 256), dim3(256), 0, s, in->x, in->y, in->z, (uint32_t)in->n, cap, max_cosine,
+                       clr2, gap2, word);
+  });
+}
+
+mh_status mh_scan_by_intensity(const mh_scan* in, const mh_by_intensity_params* p, mh_scan* out_low, mh_scan* out_mid,
+                               mh_scan* out_high) {
+  MH_REQUIRE(in && p, "null argument");
+  MH_REQUIRE(in->i, "the input layer carries no intensity");
+  mh_scan* const outs[3] = {out_low, out_mid, out_high};
+  const float low = p->low_threshold, high = p->high_threshold;
+  return split3(in, outs, 1, [&](hipStream_t s, unsigned long long* word, uint32_t cap) {
+    hipLaunchKernelGGL(k_int_classify, dim3(cap / 256), dim3(256), 0, s, in->i, (uint32_t)in->n, cap, low, high, word);
+  });
+}
+
+mh_status mh_scan_normalize_intensity(mh_scan* layer, float range[2]) {
+  MH_REQUIRE(layer, "null argument");
+  MH_REQUIRE(layer->i, "the layer carries no intensity");
+  mh_ctx* ctx = layer->ctx;
+  MH_TRY(set_device(ctx));
+  hipStream_t s = ctx->stream;
+  const size_t n = layer->n;
+  const float nan = __builtin_nanf("");
+  const float rem_lo = range ? range[0] : nan, rem_hi = range ? range[1] : nan;
+  if (!n && isnan(rem_lo) && isnan(rem_hi)) return MH_OK;  // nothing to learn, nothing to change
+  MH_TRY(ctx->build_e.reserve(64));
+  uint32_t* words = ctx->build_e.as<uint32_t>();
+  if (!ctx->h_small) MH_HIP(hipHostMalloc((void**)&ctx->h_small, 64 * sizeof(uint32_t), hipHostMallocDefault));
+  float* h_range = reinterpret_cast<float*>(ctx->h_small + 20);  // (16..18: the split counts)
+  MH_HIP(hipMemsetAsync(words, 0, 2 * sizeof(uint32_t), s));
+  float* io = const_cast<float*>(layer->i);  // (the channel is the scan's own storage)
+  const uint32_t n4 = (uint32_t)(n / 4);
+  if (n) {
+    const uint32_t g = nblk(n4 ? n4 : 1, 256);
+    hipLaunchKernelGGL(k_int_minmax, dim3(g < 256u ? g : 256u), dim3(256), 0, s, io, (uint32_t)n, words);
+  }
+  const uint32_t lanes = n4 + (uint32_t)(n % 4);  // one float4 per lane, then one lane per left-over value
+  hipLaunchKernelGGL(k_int_apply, dim3(nblk(lanes ? lanes : 1, 256)), dim3(256), 0, s, io, (uint32_t)n, words, rem_lo, rem_hi,
+                     h_range);
+  MH_HIP(hipGetLastError());
+  MH_HIP(mh::wait_stream(s));
+  if (range && !(isnan(h_range[0]) && isnan(h_range[1]))) {  // (no range at all: `range` stays as it was)
+    range[0] = h_range[0];
+    range[1] = h_range[1];
+  }
   return MH_OK;
 }
 
@@ -1066,13 +1181,14 @@ mh_status mh_scan_deskew_pair(const mh_scan* in_a, const mh_scan* in_b, const do
     MH_REQUIRE(isfinite(twist[i]), "non-finite twist");
     tw.v[i] = twist[i];
   }
-  MH_TRY(scan_alloc(out_a, in_a->n, true, in_a->src != nullptr));
-  MH_TRY(scan_alloc(out_b, in_b->n, true, in_b->src != nullptr));
+  MH_TRY(scan_alloc(out_a, in_a->n, true, in_a->src != nullptr, in_a->i != nullptr));
+  MH_TRY(scan_alloc(out_b, in_b->n, true, in_b->src != nullptr, in_b->i != nullptr));
   if (!ctx->h_small) MH_HIP(hipHostMalloc((void**)&ctx->h_small, 64 * sizeof(uint32_t), hipHostMallocDefault));
   auto layer = [](const mh_scan* in, mh_scan* out) {
     DeskewLayer l;
-    l.x = in->x; l.y = in->y; l.z = in->z; l.t = in->t; l.src = in->src;
+    l.x = in->x; l.y = in->y; l.z = in->z; l.t = in->t; l.src = in->src; l.i = in->i;
     l.ox = (float*)out->x; l.oy = (float*)out->y; l.oz = (float*)out->z; l.ot = (float*)out->t; l.osrc = (uint32_t*)out->src;
+    l.oi = (float*)out->i;
     l.n = (uint32_t)in->n;
     return l;
   };

@@ -149,9 +149,11 @@ class LidarOdometry {
   // The same for raw interleaved records as sensors and data sets deliver them (KITTI velodyne .bin: point_step 16,
   // offsets 0/4/8; PointCloud2: its own): the bytes go to the device as they are and are split into channels there
   // (the job of observations_generator, lidar3d-default.yaml:250-262).  Time stamps: float32 field at off_t (>= 0), or
-  // the separate array `t` (may be nullptr).
+  // the separate array `t` (may be nullptr).  Intensity: float32 field at off_i (>= 0), read only when the pipeline holds an
+  // intensity filter (setIntensityInput); such a pipeline rejects a scan without it.
   const ScanRecord& onLidarInterleaved(double timestamp, const void* data, size_t n, size_t point_step, size_t off_x,
-                                       size_t off_y, size_t off_z, long long off_t = -1, const float* t = nullptr);
+                                       size_t off_y, size_t off_z, long long off_t = -1, const float* t = nullptr,
+                                       long long off_i = -1);
 
   // Off-line replay (data sets, eval/cli_kitti.sh): announce the NEXT observation before calling onLidar* for the
   // current one.  Its upload and first filter pass then run on a second stream of the same device, in a worker thread,
@@ -163,7 +165,10 @@ class LidarOdometry {
   // (mp2p_icp_hip::AlignBatcher); call after initialize(), drive every instance from its own host thread
   void setAlignBatcher(std::shared_ptr<mp2p_icp_hip::AlignBatcher> b);
   void prefetchInterleaved(const void* data, size_t n, size_t point_step, size_t off_x, size_t off_y, size_t off_z,
-                           long long off_t = -1, const float* t = nullptr);
+                           long long off_t = -1, const float* t = nullptr, long long off_i = -1);
+  // Before initialize(): the observations carry a float32 intensity (onLidarInterleaved's off_i).  Only then does a general
+  // plan accept FilterNormalizeIntensity / FilterByIntensity; without it initialize() rejects them.
+  void setIntensityInput(bool on) { intensity_input_ = on; }
   void prefetch(const float* x, const float* y, const float* z, const float* t, size_t n);
 
   // (n_map_points / n_map_voxels of the records since the last key-frame are read back from the device lazily: here, and
@@ -174,6 +179,8 @@ class LidarOdometry {
   void saveTrajectoryTUM(const std::string& path) const;
   const Params& params() const { return params_; }
   std::shared_ptr<HashedVoxelPointCloud> localMap() const { return local_map_; }
+  // points of every local map by name (general plans: one per localmap_generator entry; 0 before the first key-frame)
+  std::map<std::string, uint64_t> localMapSizes() const;
   std::map<std::string, double> dynamicVariables() const { return source_.getVariableValues(); }
   // what initialize() recognised in the pipeline file (for tests / logs)
   std::map<std::string, std::string> describePipeline() const;
@@ -246,6 +253,7 @@ class LidarOdometry {
   mutable uint64_t map_points_cached_ = 0, map_voxels_cached_ = 0;
   mutable bool map_known_nonempty_ = false;
   bool input_pinned_ = false;
+  bool intensity_input_ = false;  // setIntensityInput
   std::map<std::string, double> profile_;
 };
 

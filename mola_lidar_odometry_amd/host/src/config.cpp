@@ -13,6 +13,26 @@ namespace mp2p_icp_hip {
 // ================================================================== expressions
 struct ExprCompiler;
 namespace {
+// A formula's variable: the exact name first, else the one variable whose name matches regardless of case (upstream's
+// formulas go through exprtk, which matches names that way: lidar3d-intensity.yaml:29 writes WX for the driver's wx).
+// No match, or several case-insensitive ones: end().
+std::map<std::string, double>::const_iterator find_var(const std::map<std::string, double>& vars, const std::string& name) {
+  auto it = vars.find(name);
+  if (it != vars.end()) return it;
+  auto lower = [](std::string v) {
+    for (char& c : v) c = (char)tolower((unsigned char)c);
+    return v;
+  };
+  const std::string want = lower(name);
+  auto hit = vars.end();
+  for (auto q = vars.begin(); q != vars.end(); ++q) {
+    if (lower(q->first) != want) continue;
+    if (hit != vars.end()) return vars.end();  // ambiguous
+    hit = q;
+  }
+  return hit;
+}
+
 struct ExprParser {
   const std::string& s;
   const std::map<std::string, double>& vars;
@@ -113,7 +133,7 @@ struct ExprParser {
       if (id == "pi" || id == "M_PI") return 3.14159265358979323846;
       if (id == "true") return 1.0;
       if (id == "false") return 0.0;
-      auto it = vars.find(id);
+      auto it = find_var(vars, id);
       if (it == vars.end()) fail("unknown variable '" + id + "'");
       return it->second;
     }
@@ -317,7 +337,7 @@ double CompiledExpression::evaluate(const std::vector<const double*>& values) co
 double CompiledExpression::evaluate(const std::map<std::string, double>& vars) const {
   std::vector<const double*> vals(vars_.size());
   for (size_t k = 0; k < vars_.size(); k++) {
-    auto it = vars.find(vars_[k]);
+    auto it = find_var(vars, vars_[k]);
     if (it == vars.end()) throw std::runtime_error("expression '" + text_ + "': unknown variable '" + vars_[k] + "'");
     vals[k] = &it->second;
   }
@@ -337,7 +357,7 @@ Parameterizable::Binding Parameterizable::bind(const std::map<std::string, doubl
   for (const auto& d : declared_) {
     std::vector<const double*> vals;
     for (const auto& name : d.compiled->variables()) {
-      auto it = vars.find(name);
+      auto it = find_var(vars, name);
       if (it == vars.end()) throw std::runtime_error("expression '" + d.expr + "': unknown variable '" + name + "'");
       vals.push_back(&it->second);
     }

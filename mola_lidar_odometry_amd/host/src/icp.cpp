@@ -237,9 +237,13 @@ void DevicePointCloud::setPoints(const float* x, const float* y, const float* z,
   check(mh_scan_update(scan_, x, y, z, n, MH_MEM_HOST), "mh_scan_update");
 }
 void DevicePointCloud::setPointsInterleaved(const void* data, size_t n, size_t point_step, size_t off_x, size_t off_y,
-                                            size_t off_z, long long off_t, bool pinned) {
-  check(mh_scan_update_aos(scan_, data, n, point_step, off_x, off_y, off_z, (int64_t)off_t, pinned ? MH_MEM_HOST_PINNED : MH_MEM_HOST),
-        "mh_scan_update_aos");
+                                            size_t off_z, long long off_t, bool pinned, long long off_i) {
+  check(mh_scan_update_aos_i(scan_, data, n, point_step, off_x, off_y, off_z, (int64_t)off_t, (int64_t)off_i,
+                             pinned ? MH_MEM_HOST_PINNED : MH_MEM_HOST),
+        "mh_scan_update_aos_i");
+}
+void DevicePointCloud::setIntensity(const float* i, size_t n) {
+  check(mh_scan_set_intensity(scan_, i, n, MH_MEM_HOST), "mh_scan_set_intensity");
 }
 void DevicePointCloud::setTimestamps(const float* t, size_t n) {
   check(mh_scan_set_timestamps(scan_, t, n, MH_MEM_HOST), "mh_scan_set_timestamps");

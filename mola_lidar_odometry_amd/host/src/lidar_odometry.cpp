@@ -331,9 +331,11 @@ struct LidarOdometry::FilterPlan : public Parameterizable {
 //   FilterDeskew -> mh_scan_deskew; FilterByRange (output_layer_between) / FilterBoundingBox (inside and / or outside) /
 //   FilterDecimateVoxels -> mh_scan_preprocess with the other stages skipped; FilterCurvature -> mh_scan_curvature;
 //   FilterDeleteLayer -> the layer leaves the table; observations_filter_adjust_timestamps -> mh_scan_preprocess on 'raw'
-//   with every filter stage skipped (it keeps the finite points, as every preprocess call does).
+//   with every filter stage skipped (it keeps the finite points, as every preprocess call does);
+//   with setIntensityInput(true) (extras/lidar3d-intensity.yaml): FilterNormalizeIntensity -> mh_scan_normalize_intensity in
+//   place, 1st pass only; FilterByIntensity -> mh_scan_by_intensity.
 struct LidarOdometry::GeneralPlan : public Parameterizable {
-  enum class Kind { Deskew, Preprocess, Curvature, Delete };
+  enum class Kind { Deskew, Preprocess, Curvature, Delete, NormalizeIntensity, ByIntensity };
   struct Step {
     Kind kind = Kind::Delete;
     int pass = 1;
@@ -345,6 +347,9 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
     bool range_on = false;
     double max_cosine = 0, min_clearance = 0, max_gap = 0;
     bool skip_deskew = false;
+    double low_threshold = 0, high_threshold = 0;  // ByIntensity
+    bool remember_range = false;                   // NormalizeIntensity: remember_intensity_range
+    float range[2] = {NAN, NAN};                   // ... the remembered {min, max} (reset() forgets it)
   };
   struct MapSlot {
     std::string name;
@@ -354,6 +359,8 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
     double voxel_size = 0;
   };
   std::deque<Step> steps;  // (a deque: the formulas are bound to the steps' fields by address)
+  bool intensity_input = false;  // LidarOdometry::setIntensityInput: intensity filters are accepted
+  bool reads_intensity = false;  // an intensity filter is among the steps: 'raw' carries the channel
   int32_t timestamp_method = MH_TS_NONE;
   double time_offset = 0;
   std::vector<MapSlot> maps;
@@ -368,7 +375,8 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
                              ". Implemented on the device: the chain of pipelines/lidar3d-default.yaml, and chains over named "
                              "layers of FilterAdjustTimestamps, FilterDeskew, FilterByRange(output_layer_between), "
                              "FilterBoundingBox, FilterDecimateVoxels(FirstPoint | ClosestToAverage), FilterCurvature, "
-                             "FilterDeleteLayer, and FilterMerge into HashedVoxelPointCloud / NDT maps");
+                             "FilterDeleteLayer, FilterNormalizeIntensity and FilterByIntensity (with setIntensityInput), "
+                             "and FilterMerge into HashedVoxelPointCloud / NDT maps");
   }
   static std::vector<std::string> names_of(const Config& c) {
     std::vector<std::string> v;
@@ -462,8 +470,34 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
         parameterFromConfig(p, "max_cosine", &st.max_cosine, true);
         parameterFromConfig(p, "min_clearance", &st.min_clearance, true);
         parameterFromConfig(p, "max_gap", &st.max_gap, true);
+      } else if (ends_with(cn, "Intensity") && !intensity_input) {
+        unsupported(cn + " (the observations carry no intensity: LidarOdometry::setIntensityInput(true) declares it)");
+      } else if (ends_with(cn, "FilterNormalizeIntensity")) {
+        // (the twist hook re-runs the 2nd pass from the same start: an in-place normalisation there, with its remembered
+        //  range, would be applied twice)
+        if (pass != 1) unsupported(cn + " in observations_filter_2nd_pass (it normalises in place, and the twist hook re-runs that pass)");
+        st.kind = Kind::NormalizeIntensity;
+        st.in = p.getOr("pointcloud_layer", "");
+        if (!known.count(st.in)) unsupported(cn + " reads layer '" + st.in + "', which no earlier filter writes");
+        if (p.has("remember_intensity_range")) st.remember_range = to_bool(p["remember_intensity_range"].asString());
+        reads_intensity = true;
+      } else if (ends_with(cn, "FilterByIntensity")) {
+        st.kind = Kind::ByIntensity;
+        input();
+        const char* keys[3] = {"output_layer_low_intensity", "output_layer_mid_intensity", "output_layer_high_intensity"};
+        for (const char* key : keys) {
+          const std::string o = p.getOr(key, "");
+          if (o.empty()) st.out.push_back("");
+          else output(o);
+        }
+        if (st.out[0].empty() && st.out[1].empty() && st.out[2].empty()) unsupported("FilterByIntensity without an output layer");
+        if ((!st.out[0].empty() && (st.out[0] == st.out[1] || st.out[0] == st.out[2])) || (!st.out[1].empty() && st.out[1] == st.out[2]))
+          unsupported("FilterByIntensity writes one layer twice");
+        parameterFromConfig(p, "low_threshold", &st.low_threshold, true);
+        parameterFromConfig(p, "high_threshold", &st.high_threshold, true);
+        reads_intensity = true;
       } else {
-        unsupported(cn + (ends_with(cn, "Intensity") ? " (the device layers carry no intensity channel)" : ""));
+        unsupported(cn);
       }
       if (st.kind != Kind::Delete)
         for (const auto& o : st.out)
@@ -524,9 +558,10 @@ struct LidarOdometry::RawInput {
   const void* data = nullptr;                                           // ... interleaved records
   size_t point_step = 0, off_x = 0, off_y = 0, off_z = 0;
   long long off_t = -1;
+  long long off_i = -1;  // float32 intensity inside the record, or -1
   bool same(const RawInput& o) const {
     return n == o.n && x == o.x && y == o.y && z == o.z && t == o.t && data == o.data && point_step == o.point_step &&
-           off_x == o.off_x && off_y == o.off_y && off_z == o.off_z && off_t == o.off_t;
+           off_x == o.off_x && off_y == o.off_y && off_z == o.off_z && off_t == o.off_t && off_i == o.off_i;
   }
 };
 
@@ -617,6 +652,7 @@ void LidarOdometry::initialize(const Config& cfg) {
   } catch (const std::runtime_error& e) {
     if (std::string(e.what()).find("unsupported observation filter chain") == std::string::npos) throw;
     auto g = std::make_unique<GeneralPlan>();
+    g->intensity_input = intensity_input_;
     g->load(cfg);  // throws its own "unsupported observation filter chain" naming what is implemented
     gplan_ = std::move(g);
     gplan_->attachToParameterSource(source_);
@@ -698,8 +734,10 @@ void LidarOdometry::reset() {
   map_known_nonempty_ = false;
   navstate_.reset();
   local_map_.reset();
-  if (gplan_)
+  if (gplan_) {
     for (auto& m : gplan_->maps) m.map.reset();
+    for (auto& st : gplan_->steps) st.range[0] = st.range[1] = NAN;  // (remember_intensity_range starts again)
+  }
   last_lidar_pose_ = CPose3D();
   last_icp_was_good_ = true;
   last_icp_quality_ = 0;
@@ -792,7 +830,7 @@ void LidarOdometry::run_general_pass(int pass) {
   } else {
     g.alive = g.alive_1st;  // (the twist hook runs this pass again from the same start)
   }
-  for (const auto& st : g.steps) {
+  for (auto& st : g.steps) {
     if (st.pass != pass) continue;
     using K = GeneralPlan::Kind;
     if (st.kind == K::Delete) {
@@ -800,8 +838,18 @@ void LidarOdometry::run_general_pass(int pass) {
       continue;
     }
     if (!g.alive.count(st.in)) throw std::runtime_error("LidarOdometry (HIP): " + st.cls + " reads the deleted layer '" + st.in + "'");
-    const mh_scan* in = layer(st.in)->handle();
-    if (st.kind == K::Deskew) {
+    mh_scan* in = layer(st.in)->handle();
+    if (st.kind == K::NormalizeIntensity) {  // (in place: the remembered range lives in the step, per step)
+      check(mh_scan_normalize_intensity(in, st.remember_range ? st.range : nullptr), "mh_scan_normalize_intensity");
+    } else if (st.kind == K::ByIntensity) {
+      mh_by_intensity_params bp;
+      memset(&bp, 0, sizeof(bp));
+      bp.low_threshold = (float)st.low_threshold;
+      bp.high_threshold = (float)st.high_threshold;
+      mh_scan* o[3];
+      for (int k = 0; k < 3; k++) o[k] = st.out[k].empty() ? nullptr : layer(st.out[k])->handle();
+      check(mh_scan_by_intensity(in, &bp, o[0], o[1], o[2]), "mh_scan_by_intensity");
+    } else if (st.kind == K::Deskew) {
       const double tw[6] = {v.at("vx"), v.at("vy"), v.at("vz"), v.at("wx"), v.at("wy"), v.at("wz")};
       check(mh_scan_deskew(in, st.skip_deskew ? nullptr : tw, layer(st.out[0])->handle()), "mh_scan_deskew");
     } else if (st.kind == K::Preprocess) {
@@ -860,10 +908,10 @@ void LidarOdometry::prefetch(const float* x, const float* y, const float* z, con
 }
 
 void LidarOdometry::prefetchInterleaved(const void* data, size_t n, size_t point_step, size_t off_x, size_t off_y,
-                                        size_t off_z, long long off_t, const float* t) {
+                                        size_t off_z, long long off_t, const float* t, long long off_i) {
   pf_->req = RawInput();
   pf_->req.n = n; pf_->req.data = data; pf_->req.point_step = point_step; pf_->req.off_x = off_x; pf_->req.off_y = off_y;
-  pf_->req.off_z = off_z; pf_->req.off_t = off_t; pf_->req.t = t;
+  pf_->req.off_z = off_z; pf_->req.off_t = off_t; pf_->req.t = t; pf_->req.off_i = off_i;
   pf_->requested = n > 0;
 }
 
@@ -1011,10 +1059,10 @@ const LidarOdometry::ScanRecord& LidarOdometry::onLidar(double this_obs_tim, con
 
 const LidarOdometry::ScanRecord& LidarOdometry::onLidarInterleaved(double this_obs_tim, const void* data, size_t n,
                                                                    size_t point_step, size_t off_x, size_t off_y,
-                                                                   size_t off_z, long long off_t, const float* t) {
+                                                                   size_t off_z, long long off_t, const float* t, long long off_i) {
   RawInput in;
   in.n = n; in.data = data; in.point_step = point_step; in.off_x = off_x; in.off_y = off_y; in.off_z = off_z;
-  in.off_t = off_t; in.t = t;
+  in.off_t = off_t; in.t = t; in.off_i = off_i;
   return process(this_obs_tim, in);
 }
 
@@ -1023,6 +1071,12 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   const bool has_t = in.t != nullptr || (in.data && in.off_t >= 0);
   (void)has_t;
   if (!plan_ && !gplan_) throw std::runtime_error("LidarOdometry::onLidar called before initialize()");
+  // 'raw' carries the intensity only when a filter reads it: otherwise the field is ignored (same records as without it)
+  const bool with_i = gplan_ && gplan_->reads_intensity;
+  if (with_i && !(in.data && in.off_i >= 0))
+    throw std::runtime_error("LidarOdometry (HIP): the pipeline's intensity filters need a per-point intensity, and this scan "
+                             "carries none (onLidarInterleaved with off_i >= 0)");
+  const long long off_i = with_i ? in.off_i : -1;
   records_.emplace_back();
   ScanRecord& rec = records_.back();
   rec.timestamp = this_obs_tim;
@@ -1050,7 +1104,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   if (pf_->requested && pf_->req.same(in)) pf_->requested = false;  // due before it could be launched
   if (!prepared) {
     StageTimer tt(profile_, "onLidar.0.upload_raw");
-    if (in.data) raw_->setPointsInterleaved(in.data, n, in.point_step, in.off_x, in.off_y, in.off_z, in.off_t, input_pinned_);
+    if (in.data) raw_->setPointsInterleaved(in.data, n, in.point_step, in.off_x, in.off_y, in.off_z, in.off_t, input_pinned_, off_i);
     else raw_->setPoints(in.x, in.y, in.z, n);
     if (in.t) raw_->setTimestamps(in.t, n);
   }
@@ -1080,7 +1134,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
       prepared = false;
       profile_["prefetch_misses"] += 1.0;
       StageTimer tt(profile_, "onLidar.0.upload_raw");
-      if (in.data) raw_->setPointsInterleaved(in.data, n, in.point_step, in.off_x, in.off_y, in.off_z, in.off_t, input_pinned_);
+      if (in.data) raw_->setPointsInterleaved(in.data, n, in.point_step, in.off_x, in.off_y, in.off_z, in.off_t, input_pinned_, off_i);
       else raw_->setPoints(in.x, in.y, in.z, n);
       if (in.t) raw_->setTimestamps(in.t, n);
     }
@@ -1313,8 +1367,19 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   return rec;
 }
 
+std::map<std::string, uint64_t> LidarOdometry::localMapSizes() const {
+  std::map<std::string, uint64_t> sizes;
+  if (gplan_) {
+    for (const auto& m : gplan_->maps) sizes[m.name] = m.map ? m.map->size() : 0;
+  } else if (plan_) {
+    sizes[plan_->map_layer] = local_map_ ? local_map_->size() : 0;
+  }
+  return sizes;
+}
+
 std::map<std::string, std::string> LidarOdometry::describePipeline() const {
   std::map<std::string, std::string> d;
+  d["intensity_input"] = intensity_input_ ? "true" : "false";
   if (gplan_) {
     const GeneralPlan& g = *gplan_;
     d["plan"] = "general";
@@ -1325,6 +1390,8 @@ std::map<std::string, std::string> LidarOdometry::describePipeline() const {
       if (st.kind == GeneralPlan::Kind::Delete) {
         line += " ";
         for (size_t i = 0; i < st.out.size(); i++) line += (i ? "," : "") + st.out[i];
+      } else if (st.kind == GeneralPlan::Kind::NormalizeIntensity) {
+        line += " " + st.in + " (in place" + (st.remember_range ? ", remembered range)" : ")");
       } else {
         line += " " + st.in + " ->";
         for (size_t i = 0; i < st.out.size(); i++) line += (i ? "," : " ") + (st.out[i].empty() ? std::string("-") : st.out[i]);

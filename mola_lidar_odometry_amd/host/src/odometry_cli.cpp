@@ -6,7 +6,7 @@
 // times.txt, and announces the next scan so that its upload and first filter pass overlap with the current ICP loop.
 //
 //   molahip-lo-cli --pipeline pipelines/lidar3d-default-hip.yaml --seq-dir /data/kitti/sequences/00 --out 00.tum
-//                  [--device 0 | --devices 0,1,..|all] [--no-prefetch] [--max-scans N] [--time-field BYTES] [--scan-log FILE]
+//                  [--device 0 | --devices 0,1,..|all] [--no-prefetch] [--max-scans N] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE]
 // --devices: config 4 of BASELINE.json without Python -- the sequences are assigned to the listed GPUs by LPT (longest
 // sequence first onto the least loaded device, what eval/cli_kitti.sh:9,23-36 leaves to GNU parallel's job slots), every
 // device runs its share like a --seq-dir list on one GPU (a host thread per sequence, one AlignBatcher per device); the
@@ -15,6 +15,8 @@
 // --seq-dir also takes a MulRan sequence folder (eval/cli_mulran.sh:23-36, `--input-mulran-seq KAIST01` with
 // MULRAN_BASE_DIR, apps/mola-lidar-odometry-cli.cpp:186-208): <dir>/sensor_data/Ouster/<stamp in ns>.bin (or <dir>/Ouster/),
 // float32 x,y,z,intensity rows like KITTI's, the scan's time stamp is its file name.
+// --intensity-field 12: the rows' fourth float is the intensity the filters of extras/lidar3d-intensity.yaml read (it also calls
+// LidarOdometry::setIntensityInput(true)); without it the field is ignored.
 // Several --seq-dir run together on the one GPU (what eval/cli_kitti.sh:23 does with GNU parallel -j3, as processes):
 // a host thread per sequence, their alignments merged into lock-step batches (mp2p_icp_hip::AlignBatcher).
 #include <algorithm>
@@ -106,6 +108,7 @@ struct RunOptions {
   long max_scans = -1;
   bool prefetch = true;
   long long time_field = -1;  // byte offset of a float32 per-point time stamp inside the 16-byte record, or -1
+  long long intensity_field = -1;  // byte offset of the float32 intensity inside the record (KITTI / MulRan: 12), or -1
   std::string scan_log;       // CSV of per-scan registration times and layer / map sizes
 };
 
@@ -196,6 +199,7 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
     mola_hip::LidarOdometry& lo = *lo_owner;
     rep.keep_alive = lo_owner;
     stamp("device context");
+    if (opt.intensity_field >= 0) lo.setIntensityInput(true);  // (before initialize(): the intensity filters need it)
     lo.initialize(mp2p_icp_hip::Config::FromYamlFile(pipeline));
     stamp("pipeline initialised");
     if (batcher) lo.setAlignBatcher(batcher);
@@ -206,8 +210,8 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
       const bool has_next = k + 1 < files.size();
       if (has_next) nxt = read_bin(files[k + 1]);  // (file reading is not part of the registration time)
       const auto t0 = std::chrono::steady_clock::now();
-      if (has_next && prefetch) lo.prefetchInterleaved(nxt.data(), nxt.size() / 4, 16, 0, 4, 8, opt.time_field);
-      const auto& rec = lo.onLidarInterleaved(stamps[k], cur.data(), cur.size() / 4, 16, 0, 4, 8, opt.time_field);
+      if (has_next && prefetch) lo.prefetchInterleaved(nxt.data(), nxt.size() / 4, 16, 0, 4, 8, opt.time_field, nullptr, opt.intensity_field);
+      const auto& rec = lo.onLidarInterleaved(stamps[k], cur.data(), cur.size() / 4, 16, 0, 4, 8, opt.time_field, nullptr, opt.intensity_field);
       const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       rep.seconds += dt;
       rep.scan_seconds.push_back(dt);
@@ -280,7 +284,7 @@ int main(int argc, char** argv) {
   RunOptions opt;
   bool print_profile = false, plan_only = false;
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
-                      "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
+                      "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --devices: the sequences are spread over the listed GPUs (longest first onto the least loaded device)\n";
@@ -298,6 +302,7 @@ int main(int argc, char** argv) {
       else if (a == "--devices") devices = parse_devices(val("--devices"));
       else if (a == "--max-scans") opt.max_scans = atol(val("--max-scans").c_str());
       else if (a == "--time-field") opt.time_field = atoll(val("--time-field").c_str());
+      else if (a == "--intensity-field") opt.intensity_field = atoll(val("--intensity-field").c_str());
       else if (a == "--scan-log") opt.scan_log = val("--scan-log");
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;

@@ -158,15 +158,17 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("reset", &LidarOdometry::reset)
       .def("onLidar", [rec2dict](LidarOdometry& lo, double stamp, py::array_t<float, py::array::c_style | py::array::forcecast> xyz,
                                  std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> t,
-                                 std::array<int, 3> xyz_fields, int t_field) {
+                                 std::array<int, 3> xyz_fields, int t_field, int i_field) {
         // [n,3] points or [n,k] float32 records (a KITTI .bin is [n,4]; a PointCloud2 payload of float fields likewise):
-        // the rows go to the device as they are and are split into channels there.  xyz_fields / t_field = column
-        // indices of the coordinates / of a per-point time stamp (-1: none, or the separate array `t`)
+        // the rows go to the device as they are and are split into channels there.  xyz_fields / t_field / i_field = column
+        // indices of the coordinates / of a per-point time stamp (-1: none, or the separate array `t`) / of the intensity
+        // (-1: none; read only by a pipeline with intensity filters, setIntensityInput)
         if (xyz.ndim() != 2 || xyz.shape(1) < 3) throw std::runtime_error("xyz must be [n,3] (or [n,k>=3] records)");
         const size_t n = (size_t)xyz.shape(0), k = (size_t)xyz.shape(1);
         for (int f : xyz_fields)
           if (f < 0 || (size_t)f >= k) throw std::runtime_error("xyz_fields out of range");
         if (t_field >= (int)k) throw std::runtime_error("t_field out of range");
+        if (i_field >= (int)k) throw std::runtime_error("i_field out of range");
         const float* tp = nullptr;
         if (t) {
           if ((size_t)t->size() != n) throw std::runtime_error("t must have n entries");
@@ -176,14 +178,15 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
           py::gil_scoped_release nogil;  // the numpy buffers are only read through their pointers: other drivers' threads may run
           (void)lo.onLidarInterleaved(stamp, xyz.data(), n, k * sizeof(float), 4u * (size_t)xyz_fields[0],
                                        4u * (size_t)xyz_fields[1], 4u * (size_t)xyz_fields[2],
-                                       t_field >= 0 ? 4ll * t_field : -1ll, tp);
+                                       t_field >= 0 ? 4ll * t_field : -1ll, tp, i_field >= 0 ? 4ll * i_field : -1ll);
         }
         return rec2dict(lo.records().back()); },  // (records(): the map counters of this record, read back now)
            py::arg("timestamp"), py::arg("xyz"), py::arg("t") = std::nullopt,
-           py::arg("xyz_fields") = std::array<int, 3>{0, 1, 2}, py::arg("t_field") = -1)
+           py::arg("xyz_fields") = std::array<int, 3>{0, 1, 2}, py::arg("t_field") = -1, py::arg("i_field") = -1)
+      .def("setIntensityInput", &LidarOdometry::setIntensityInput)
       .def("setAlignBatcher", &LidarOdometry::setAlignBatcher)
       .def("prefetch", [](py::object self, py::array xyz_any, std::optional<py::array> t_any,
-                          std::array<int, 3> xyz_fields, int t_field) {
+                          std::array<int, 3> xyz_fields, int t_field, int i_field) {
         // announce the NEXT scan (same arguments as the onLidar call that will follow): upload + first filter pass run
         // on a second stream while the current scan is registered.  The worker thread reads the caller's buffers, so
         // no hidden temporary may stand in for them: float32, C-contiguous arrays only (anything else is rejected
@@ -206,17 +209,18 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         for (int f : xyz_fields)
           if (f < 0 || (size_t)f >= k) throw std::runtime_error("xyz_fields out of range");
         if (t_field >= (int)k) throw std::runtime_error("t_field out of range");
+        if (i_field >= (int)k) throw std::runtime_error("i_field out of range");
         const float* tp = nullptr;
         if (t) {
           if ((size_t)t->size() != n) throw std::runtime_error("t must have n entries");
           tp = t->data();
         }
         lo.prefetchInterleaved(xyz.data(), n, k * sizeof(float), 4u * (size_t)xyz_fields[0], 4u * (size_t)xyz_fields[1],
-                               4u * (size_t)xyz_fields[2], t_field >= 0 ? 4ll * t_field : -1ll, tp);
+                               4u * (size_t)xyz_fields[2], t_field >= 0 ? 4ll * t_field : -1ll, tp, i_field >= 0 ? 4ll * i_field : -1ll);
         if (py::hasattr(self, "_prefetch_keepalive")) self.attr("_prefetch_inflight") = self.attr("_prefetch_keepalive");
         self.attr("_prefetch_keepalive") = py::make_tuple(xyz, t ? py::object(*t) : py::none()); },
            py::arg("xyz"), py::arg("t") = std::nullopt, py::arg("xyz_fields") = std::array<int, 3>{0, 1, 2},
-           py::arg("t_field") = -1)
+           py::arg("t_field") = -1, py::arg("i_field") = -1)
       .def("records", [rec2dict](const LidarOdometry& lo) { py::list l; for (auto& r : lo.records()) l.append(rec2dict(r)); return l; })
       .def("trajectory", [](const LidarOdometry& lo) {
         py::list l;
@@ -226,7 +230,8 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("dynamicVariables", &LidarOdometry::dynamicVariables)
       .def("describePipeline", &LidarOdometry::describePipeline)
       .def("profile", [](const LidarOdometry& lo) { return lo.profile(); })
-      .def("localMapSize", [](const LidarOdometry& lo) { return lo.localMap() ? lo.localMap()->size() : 0; });
+      .def("localMapSize", [](const LidarOdometry& lo) { return lo.localMap() ? lo.localMap()->size() : 0; })
+      .def("localMapSizes", &LidarOdometry::localMapSizes);
   py::class_<AlignBatcher, std::shared_ptr<AlignBatcher>>(m, "AlignBatcher")
       .def(py::init<size_t>(), py::arg("participants"))
       .def("leave", [](AlignBatcher& b) { b.leave(); }, py::call_guard<py::gil_scoped_release>())

@@ -284,14 +284,47 @@ def make_drive(n_scans: int = 12, dt: float = 0.1, speed: float = 8.0, yaw_rate:
     return dict(scene=scene, poses=plan["poses"], twists=plan["twists"], scans=scans, stamps=plan["stamps"])
 
 
-def write_kitti_sequence(root: str, drive, seq: str = "00") -> str:
+def drive_intensities(drive, gain: float = 0.4):
+    """Per-scan float32 intensities for the sweeps of make_drive (one array per scan, in the sweep's point order).  The value
+    is a function of the point's world position under the ground-truth pose (the sweep's own motion model, make_sweep):
+    every third box and 1.2 m wide stripes every 5 m along the facades are bright (0.92-0.95), the other boxes and the
+    facades mid (0.35-0.45), the ground dim (0.10-0.15), anything else 0.3; a +-2 % ripple over the position keeps the
+    values distinct.  Scan k multiplies all of it by 1 + gain * sin(1.3 k + 0.4), so the layer's range -- what
+    FilterNormalizeIntensity divides by, and what remember_intensity_range widens -- varies from scan to scan.  No random
+    stream is drawn: make_drive's outputs are what they are without this."""
+    boxes = drive["scene"].boxes
+    out = []
+    for k, (xyz, t) in enumerate(drive["scans"]):
+        T = np.asarray(drive["poses"][k], np.float64).reshape(3, 4)
+        tw = np.asarray(drive["twists"][k], np.float64)
+        tt = np.asarray(t, np.float64)
+        Rt = _so3_exp(tw[None, 3:] * tt[:, None])
+        p_ref = np.einsum("nij,nj->ni", Rt, np.asarray(xyz, np.float64)) + tw[None, :3] * tt[:, None]
+        w = p_ref @ T[:, :3].T + T[:, 3]
+        x, y, z = w[:, 0], w[:, 1], w[:, 2]
+        val = np.full(len(w), 0.3)
+        val[z < 0.15] = 0.10 + 0.05 * (0.5 + 0.5 * np.sin(0.3 * x[z < 0.15]))
+        facade = np.abs(np.abs(y) - FACADE_Y) < 0.3
+        val[facade] = np.where(np.mod(x[facade], 5.0) < 1.2, 0.92, 0.35)
+        eps = 0.1
+        for b, (x0, y0, z0, x1, y1, z1) in enumerate(boxes):
+            inside = (x > x0 - eps) & (x < x1 + eps) & (y > y0 - eps) & (y < y1 + eps) & (z > z0 + 0.15) & (z < z1 + eps)
+            val[inside] = 0.95 if b % 3 == 0 else 0.45
+        val *= 1.0 + 0.02 * np.sin(1.7 * x + 0.9 * y + 2.3 * z)
+        out.append((val * (1.0 + gain * np.sin(1.3 * k + 0.4))).astype(np.float32))
+    return out
+
+
+def write_kitti_sequence(root: str, drive, seq: str = "00", intensities=None) -> str:
     """The drive as a KITTI odometry sequence folder (velodyne/%06d.bin rows of float32 x,y,z,intensity + times.txt), what
-    molahip-lo-cli and eval/cli_kitti.sh's --input-kitti-seq read.  Returns the sequence directory."""
+    molahip-lo-cli and eval/cli_kitti.sh's --input-kitti-seq read.  intensities: per-scan arrays for the fourth float
+    (drive_intensities), zeros without.  Returns the sequence directory."""
     import os
     d = os.path.join(root, "sequences", seq)
     os.makedirs(os.path.join(d, "velodyne"), exist_ok=True)
     for k, (xyz, _) in enumerate(drive["scans"]):
-        np.concatenate([xyz, np.zeros((len(xyz), 1), np.float32)], 1).astype(np.float32).tofile(
+        inten = np.zeros(len(xyz), np.float32) if intensities is None else np.asarray(intensities[k], np.float32)
+        np.concatenate([xyz, inten[:, None]], 1).astype(np.float32).tofile(
             os.path.join(d, "velodyne", "%06d.bin" % k))
     np.savetxt(os.path.join(d, "times.txt"), drive["stamps"] - drive["stamps"][0], fmt="%.6e")
     return d

@@ -1,0 +1,312 @@
+"""The stand-alone driver on the intensity chain of extras/lidar3d-intensity.yaml (FilterNormalizeIntensity, FilterByIntensity,
+two maps): it is accepted only after setIntensityInput(True) and described step by step, its misuses are rejected with their
+reasons, and the formula evaluator resolves the file's upper-case WX (CPU).  On the GPU, over synth.make_drive(14) with
+synth.drive_intensities: it tracks the drive, its first scan's layers and bright map equal a numpy / oracle restatement, it
+is deterministic and field-order independent, the default pipeline ignores a supplied intensity, remember_intensity_range
+matters, and molahip-lo-cli --intensity-field 12 writes the trajectory of the pybind run."""
+import importlib.util
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from mola_lidar_odometry_amd import synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF_FILE = "/root/reference/pipelines/extras/lidar3d-intensity.yaml"
+CLI = os.path.join(ROOT, "mola_lidar_odometry_amd", "molahip-lo-cli")
+
+
+def _module(name):
+    spec = importlib.util.spec_from_file_location("_" + name, os.path.join(ROOT, "tests", name + ".py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+chains = _module("test_odometry_chains")
+intensity = _module("test_intensity")
+_E = "ESTIMATED_SENSOR_MAX_RANGE"
+
+
+def _map(name):
+    return f"""  - class_name: mp2p_icp_filters::Generator
+    params:
+      target_layer: '{name}'
+      metric_map_definition:
+        class: mola::HashedVoxelPointCloud
+        creationOpts:
+          voxel_size: '$f{{max(0.5, min(1.0, 0.015*{_E}))}}'
+        insertOpts:
+          max_points_per_voxel: 20
+          min_distance_between_points: 0
+          remove_voxels_farther_than: '$f{{max(100.0, 1.50*{_E})}}'
+"""
+
+
+def intensity_tail(remember="true"):
+    """The structure and values of extras/lidar3d-intensity.yaml from localmap_generator on."""
+    return ("localmap_generator:\n" + _map("localmap") + _map("localmap_bright") + f"""observations_filter_1st_pass:
+  - class_name: mp2p_icp_filters::FilterDeskew
+    params:
+      input_pointcloud_layer: 'raw'
+      output_pointcloud_layer: 'deskewed'
+      silently_ignore_no_timestamps: true
+      twist: [vx,vy,vz,wx,wy,wz]
+""" + chains._decimate("deskewed", "decimated_for_map_raw", f"0.55*1e-2*{_E}") + f"""  - class_name: mp2p_icp_filters::FilterByRange
+    params:
+      input_pointcloud_layer: 'decimated_for_map_raw'
+      output_layer_between: 'decimated_for_map_by_range'
+      range_min: max(1.0, 0.03*{_E})
+      range_max: 1.2*{_E}
+  - class_name: mp2p_icp_filters::FilterBoundingBox
+    params:
+      input_pointcloud_layer: 'decimated_for_map_by_range'
+      outside_pointcloud_layer: 'decimated_for_map'
+      bounding_box_min: [ -0.20*{_E}, -0.20*{_E}, 0.01*{_E} ]
+      bounding_box_max: [  0.20*{_E},  0.20*{_E}, 0.10*{_E} ]
+  - class_name: mp2p_icp_filters::FilterNormalizeIntensity
+    params:
+      pointcloud_layer: 'decimated_for_map'
+      remember_intensity_range: {remember}
+  - class_name: mp2p_icp_filters::FilterByIntensity
+    params:
+      input_pointcloud_layer: 'decimated_for_map'
+      output_layer_high_intensity: 'decimated_for_map_bright'
+      high_threshold: 0.9
+      low_threshold: 0.1
+""" + chains._decimate("decimated_for_map", "decimated_for_icp", f"1.6*1e-2*{_E}") + """  - class_name: mp2p_icp_filters::FilterDeleteLayer
+    params:
+      pointcloud_layer_to_remove: ['raw','deskewed', 'decimated_for_map_by_range', 'decimated_for_map_raw']
+insert_observation_into_local_map:
+""" + chains._merge("decimated_for_map", "localmap") + chains._merge("decimated_for_map_bright", "localmap_bright"))
+
+
+MATCHES = '          - {global: "localmap", local: "decimated_for_icp", weight: 1.0}\n'
+
+
+def pipeline(remember="true"):
+    return chains.inline_pipeline(intensity_tail(remember), MATCHES)
+
+
+@pytest.fixture(scope="module")
+def host():
+    from mola_lidar_odometry_amd import _mp2p_icp_hip as H
+    return H
+
+
+def _load(host, text, declare=True):
+    lo = host.LidarOdometry()
+    if declare:
+        lo.setIntensityInput(True)
+    lo.initialize(host.Config.FromYamlText(text))
+    return lo
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+def test_intensity_chain_is_accepted_and_described(host):
+    d = _load(host, pipeline()).describePipeline()
+    assert d["plan"] == "general" and d["intensity_input"] == "true"
+    steps = [d[f"step:{i:02d}"] for i in range(int(d["steps"]))]
+    assert "pass1 FilterNormalizeIntensity decimated_for_map (in place, remembered range)" in steps
+    assert "pass1 FilterByIntensity decimated_for_map -> -,-,decimated_for_map_bright" in steps
+    assert steps.index("pass1 FilterNormalizeIntensity decimated_for_map (in place, remembered range)") < \
+        steps.index("pass1 FilterByIntensity decimated_for_map -> -,-,decimated_for_map_bright")
+    assert sorted(k for k in d if k.startswith("map:")) == ["map:localmap", "map:localmap_bright"]
+    assert d["merge:decimated_for_map"] == "localmap" and d["merge:decimated_for_map_bright"] == "localmap_bright"
+    d2 = _load(host, pipeline("false")).describePipeline()
+    assert "pass1 FilterNormalizeIntensity decimated_for_map (in place)" in [d2[f"step:{i:02d}"] for i in range(int(d2["steps"]))]
+    assert _load(host, open(chains.PIPE).read(), declare=False).describePipeline()["intensity_input"] == "false"
+
+
+def test_intensity_chain_needs_the_declaration(host):
+    for cls in ("FilterNormalizeIntensity", "FilterByIntensity"):
+        text = pipeline()
+        if cls == "FilterByIntensity":  # (the first intensity filter of the chain is the one named)
+            text = text.replace("""  - class_name: mp2p_icp_filters::FilterNormalizeIntensity
+    params:
+      pointcloud_layer: 'decimated_for_map'
+      remember_intensity_range: true
+""", "")
+        with pytest.raises(RuntimeError, match=f"unsupported observation filter chain.*{cls}"):
+            _load(host, text, declare=False)
+
+
+def test_reference_intensity_file_initializes(host):
+    if not os.path.exists(REF_FILE):
+        pytest.skip("reference tree not present on this box")
+    lo = host.LidarOdometry()
+    lo.setIntensityInput(True)
+    lo.initialize(host.Config.FromYamlFile(REF_FILE))
+    d = lo.describePipeline()
+    assert d["plan"] == "general" and sorted(k[4:] for k in d if k.startswith("map:")) == ["localmap", "localmap_bright"]
+    with pytest.raises(RuntimeError, match="unsupported observation filter chain.*Intensity"):
+        host.LidarOdometry().initialize(host.Config.FromYamlFile(REF_FILE))
+
+
+def test_misplaced_or_empty_intensity_filters_are_rejected(host):
+    norm = """  - class_name: mp2p_icp_filters::FilterNormalizeIntensity
+    params:
+      pointcloud_layer: 'decimated_for_map'
+      remember_intensity_range: true
+"""
+    text = pipeline().replace(norm, "").replace("insert_observation_into_local_map:\n",
+                                                "observations_filter_2nd_pass:\n" + norm + "insert_observation_into_local_map:\n")
+    with pytest.raises(RuntimeError, match="FilterNormalizeIntensity in observations_filter_2nd_pass.*twist hook re-runs"):
+        _load(host, text)
+    text = pipeline().replace("      output_layer_high_intensity: 'decimated_for_map_bright'\n", "")
+    with pytest.raises(RuntimeError, match="FilterByIntensity without an output layer"):
+        _load(host, text)
+    text = pipeline().replace("      pointcloud_layer: 'decimated_for_map'\n      remember", "      pointcloud_layer: 'nowhere'\n      remember")
+    with pytest.raises(RuntimeError, match="unsupported observation filter chain.*'nowhere'"):
+        _load(host, text)
+
+
+def test_evaluator_resolves_names_regardless_of_case(host):
+    v = {"wx": 3.0, "wy": 4.0, "wz": 0.0, "ESTIMATED_SENSOR_MAX_RANGE": 10.0}
+    assert host.evaluate_expression("sqrt(WX^2+WY^2+WZ^2)", v) == 5.0
+    assert host.evaluate_compiled("sqrt(WX^2+WY^2+WZ^2)*estimated_sensor_max_range", v) == 50.0
+    # an exact match wins over a case-insensitive one
+    assert host.evaluate_expression("a + A", {"a": 1.0, "A": 10.0}) == 11.0
+    assert host.evaluate_expression("Ab", {"ab": 1.0, "AB": 10.0, "Ab": 100.0}) == 100.0
+    # several case-insensitive candidates and no exact one, or none at all: still an error
+    with pytest.raises(RuntimeError, match="unknown variable 'aB'"):
+        host.evaluate_expression("aB", {"ab": 1.0, "AB": 10.0})
+    with pytest.raises(RuntimeError, match="unknown variable 'nope'"):
+        host.evaluate_expression("nope", v)
+    with pytest.raises(RuntimeError, match="unknown variable 'nope'"):
+        host.evaluate_compiled("nope + 1", v)
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+@pytest.fixture(scope="module")
+def drive():
+    d = synth.make_drive(14)
+    d["intensity"] = synth.drive_intensities(d)
+    return d
+
+
+def _records(drive, k, order=(0, 1, 2, 3, 4)):
+    """Scan k as float32 records with the fields x, y, z, t, intensity placed at the columns `order` names."""
+    xyz, t = drive["scans"][k]
+    cols = [xyz[:, 0], xyz[:, 1], xyz[:, 2], t, drive["intensity"][k]]
+    rec = np.empty((len(xyz), 5), np.float32)
+    for f, c in enumerate(order):
+        rec[:, c] = cols[f]
+    return rec
+
+
+def _run(host, text, drive, order=(0, 1, 2, 3, 4), declare=True, with_i=True, n=None):
+    lo = host.LidarOdometry(0, True)
+    if declare:
+        lo.setIntensityInput(True)
+    lo.initialize(host.Config.FromYamlText(text))
+    sizes = []
+    for k in range(n or len(drive["scans"])):
+        rec = _records(drive, k, order)
+        lo.onLidar(float(drive["stamps"][k]), rec, None, [order[0], order[1], order[2]], order[3], order[4] if with_i else -1)
+        sizes.append(lo.localMapSizes())
+    return lo, lo.records(), sizes
+
+
+def _range0(xyz):
+    mn, mx = xyz.min(0), xyz.max(0)
+    return max(float(max(np.float32(np.sqrt((mx * mx).sum(dtype=np.float32))), np.float32(np.sqrt((mn * mn).sum(dtype=np.float32))))), 5.0)
+
+
+def _restated_scan0(drive):
+    """Scan 0 through the chain in numpy / the CPU oracle: no motion yet (twist 0), the sensor range from the raw cloud."""
+    from oracle import oracle_c
+    xyz, t = drive["scans"][0]
+    raw_i = drive["intensity"][0]
+    R = _range0(xyz)
+    d = oracle_c.deskew(xyz, t, np.zeros(6))
+    i1 = oracle_c.decimate_first_point(d, 0.55e-2 * R)
+    k1 = i1[oracle_c.filter_by_range(d[i1], max(1.0, 0.03 * R), 1.2 * R)]
+    box = [(-0.20 * R, -0.20 * R, 0.01 * R), (0.20 * R, 0.20 * R, 0.10 * R)]
+    k2 = k1[oracle_c.filter_bbox(d[k1], box[0], box[1], keep_inside=False)]
+    layer = d[k2]
+    norm, _ = intensity.normalize_np(raw_i[k2], np.array([np.nan, np.nan], np.float32))
+    bright = intensity.intensity_classes(norm, 0.1, 0.9) == intensity.HIGH
+    icp = oracle_c.decimate_first_point(layer, 1.6e-2 * R)
+    sizes = {"decimated_for_map": len(k2), "decimated_for_map_bright": int(bright.sum()), "decimated_for_icp": len(icp)}
+    return sizes, layer[bright]
+
+
+@pytest.mark.gpu
+def test_intensity_chain_tracks_the_drive(host, drive):
+    text = pipeline()
+    lo, recs, maps = _run(host, text, drive)
+    assert not any(r["dropped"] for r in recs)
+    for r in recs[2:]:
+        assert r["icp_run"] and r["icp_good"], r
+    ate = chains._ate(recs, drive)
+    print(f"intensity chain: ATE RMSE {ate:.4f} m over {len(recs)} scans")
+    assert ate < 0.2, ate
+    # scan 0 restated layer by layer, and what reached the bright map
+    from oracle import oracle_c
+    want, bright = _restated_scan0(drive)
+    assert recs[0]["layer_sizes"] == want, (recs[0]["layer_sizes"], want)
+    assert want["decimated_for_map_bright"] > 0
+    om = oracle_c.Map(recs[0]["map_voxel_size"], 20).insert(bright)
+    assert maps[0]["localmap_bright"] == om.num_points > 0
+    assert maps[-1]["localmap_bright"] >= maps[0]["localmap_bright"] and maps[-1]["localmap"] > maps[0]["localmap"]
+    # deterministic, and the same whatever the order of the record's fields
+    _, again, maps2 = _run(host, text, drive)
+    assert again == recs and maps2 == maps
+    _, perm, maps3 = _run(host, text, drive, order=(4, 2, 0, 1, 3))
+    assert perm == recs and maps3 == maps
+
+
+@pytest.mark.gpu
+def test_default_pipeline_ignores_a_supplied_intensity(host, drive):
+    text = open(chains.PIPE).read()
+    _, with_i, _ = _run(host, text, drive, declare=True, with_i=True)
+    _, without, _ = _run(host, text, drive, declare=False, with_i=False)
+    assert with_i == without
+
+
+@pytest.mark.gpu
+def test_intensity_chain_needs_intensity_in_every_scan(host, drive):
+    lo = host.LidarOdometry(0, True)
+    lo.setIntensityInput(True)
+    lo.initialize(host.Config.FromYamlText(pipeline()))
+    xyz, t = drive["scans"][0]
+    with pytest.raises(RuntimeError, match="intensity"):
+        lo.onLidar(float(drive["stamps"][0]), xyz, t)
+    assert len(lo.records()) == 0
+
+
+@pytest.mark.gpu
+def test_remembered_range_changes_the_bright_layer(host, drive):
+    _, on, _ = _run(host, pipeline("true"), drive)
+    _, off, _ = _run(host, pipeline("false"), drive)
+    b_on = [r["layer_sizes"]["decimated_for_map_bright"] for r in on]
+    b_off = [r["layer_sizes"]["decimated_for_map_bright"] for r in off]
+    assert b_on[0] == b_off[0]  # (nothing remembered yet)
+    assert b_on != b_off, (b_on, b_off)
+    # a scan of low gain after one of high gain: the widened range leaves it fewer bright points
+    assert any(a < b for a, b in zip(b_on, b_off))
+
+
+@pytest.mark.gpu
+def test_cli_intensity_field_matches_the_pybind_run(host, drive, tmp_path):
+    seq = synth.write_kitti_sequence(str(tmp_path / "kitti"), drive, intensities=drive["intensity"])
+    pipe = tmp_path / "intensity.yaml"
+    pipe.write_text(pipeline())
+    out = tmp_path / "cli.tum"
+    r = subprocess.run([CLI, "--pipeline", str(pipe), "--seq-dir", seq, "--out", str(out), "--intensity-field", "12"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    stamps = np.loadtxt(os.path.join(seq, "times.txt"), ndmin=1)
+    lo = host.LidarOdometry(0, True)
+    lo.setIntensityInput(True)
+    lo.initialize(host.Config.FromYamlText(pipeline()))
+    for k in range(len(stamps)):
+        rec = np.fromfile(os.path.join(seq, "velodyne", "%06d.bin" % k), np.float32).reshape(-1, 4)
+        lo.onLidar(float(stamps[k]), rec, None, [0, 1, 2], -1, 3)
+    mine = tmp_path / "pybind.tum"
+    lo.saveTrajectoryTUM(str(mine))
+    assert len(lo.records()) == len(drive["scans"])
+    assert out.read_text() == mine.read_text()
