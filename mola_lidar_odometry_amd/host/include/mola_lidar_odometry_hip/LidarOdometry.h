@@ -130,6 +130,8 @@ class LidarOdometry {
     double decim_map_resolution = 0, decim_icp_resolution = 0, map_voxel_size = 0;
     // general filter chains (not the default one, whose record leaves it empty): points of every observation layer handed to
     // ICP, by name.  There n_for_map = points the FilterMerge steps offered to the maps, n_for_icp = points of all those layers.
+    // All three describe the layers that were finally aligned and merged: after the last re-run of the 2nd pass that the twist
+    // hook asked for (a 2nd pass that filters after its de-skew can change them; LidarOdometry.cpp:973-1004, 1158-1206).
     std::map<std::string, uint64_t> layer_sizes;
   };
 
@@ -181,6 +183,29 @@ class LidarOdometry {
   std::shared_ptr<HashedVoxelPointCloud> localMap() const { return local_map_; }
   // points of every local map by name (general plans: one per localmap_generator entry; 0 before the first key-frame)
   std::map<std::string, uint64_t> localMapSizes() const;
+  // Debug accessors for tests (they wait for the device and copy to the host: not for timed paths).
+  // Every local map by name: stored points, occupied voxels, voxel size (zeros before the first key-frame).
+  struct MapStats {
+    uint64_t n_points = 0, n_voxels = 0;
+    double voxel_size = 0;
+  };
+  std::map<std::string, MapStats> localMapStats() const;
+  // An observation layer of the last scan of a general plan, as the last run of its filter left it (a layer that a
+  // FilterDeleteLayer removed keeps its content until the next scan writes it): coordinates, time stamps and source indices
+  // (zeros when the layer carries none), intensity (empty when the observations carry none).  Throws on an unknown name.
+  struct LayerDump {
+    std::vector<float> x, y, z, t, intensity;
+    std::vector<uint32_t> src_idx;
+    bool alive = false;  // among the layers handed to ICP
+  };
+  LayerDump downloadLayer(const std::string& name) const;
+  // A local map by name as mh_map_download gives it: points voxel by voxel, voxels in ascending (kx, ky, kz).
+  struct MapDump {
+    std::vector<float> x, y, z;
+    std::vector<uint32_t> src_idx, vox_first, vox_count;
+    std::vector<int32_t> vox_keys;  // 3 per voxel
+  };
+  MapDump downloadMap(const std::string& name) const;
   std::map<std::string, double> dynamicVariables() const { return source_.getVariableValues(); }
   // what initialize() recognised in the pipeline file (for tests / logs)
   std::map<std::string, std::string> describePipeline() const;
@@ -207,6 +232,7 @@ class LidarOdometry {
   void create_local_map();
   std::shared_ptr<HashedVoxelPointCloud> make_map(const Config& def, double* voxel_size, float* remove_far) const;
   void run_general_pass(int pass);
+  void record_layer_sizes(ScanRecord& rec) const;  // general plans: layer_sizes, n_for_icp, n_for_map of the live layers
   uint64_t maps_total(bool voxels) const;
   void ensure_device();
   void resolve_map_counts() const;  // fills n_map_points / n_map_voxels of the records that still wait for them

@@ -808,6 +808,10 @@ static mh_preprocess_params make_pp(double decim_map_res, double decim_icp_res, 
   return pp;
 }
 
+// general plans: the buffer of 'raw' with adjusted time stamps lives in the layer table under a key no pipeline can name
+// (downloadLayer() serves it as 'raw' and refuses the key itself)
+static const char* const kAdjustedRawKey = " raw (time stamps adjusted)";
+
 void LidarOdometry::run_general_pass(int pass) {
   GeneralPlan& g = *gplan_;
   const auto& v = source_.getVariableValues();
@@ -822,7 +826,7 @@ void LidarOdometry::run_general_pass(int pass) {
     if (g.timestamp_method != MH_TS_NONE) {  // observations_filter_adjust_timestamps over all raw points
       const double zero[3] = {0, 0, 0};
       const mh_preprocess_params pp = make_pp(0, 0, 0, 0, 0, MH_BBOX_OFF, zero, zero, g.timestamp_method, g.time_offset);
-      auto out = layer(" raw (time stamps adjusted)");
+      auto out = layer(kAdjustedRawKey);
       check(mh_scan_preprocess(cur_raw_->handle(), &pp, out->handle(), nullptr), "mh_scan_preprocess (adjust time stamps)");
       g.raw_adjusted = out;
     }
@@ -876,6 +880,18 @@ void LidarOdometry::run_general_pass(int pass) {
     for (int a = 0; a < 3; a++) icp_bb_min_[a] = icp_bb_max_[a] = 0.f;
     if (!g.alive.empty()) layer(*g.alive.begin())->boundingBox(icp_bb_min_, icp_bb_max_);
   }
+}
+
+void LidarOdometry::record_layer_sizes(ScanRecord& rec) const {
+  rec.layer_sizes.clear();
+  rec.n_for_icp = rec.n_for_map = 0;
+  for (const auto& name : gplan_->alive) {
+    const uint64_t k = (name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name))->size();
+    rec.layer_sizes[name] = k;
+    rec.n_for_icp += k;
+  }
+  for (const auto& [name, m] : gplan_->merges)
+    if (rec.layer_sizes.count(name)) rec.n_for_map += rec.layer_sizes[name];
 }
 
 void LidarOdometry::run_first_pass() {
@@ -1148,13 +1164,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     run_second_pass();  // :739
   }
   if (gplan_) {
-    for (const auto& name : gplan_->alive) {
-      const uint64_t k = (name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name))->size();
-      rec.layer_sizes[name] = k;
-      rec.n_for_icp += k;
-    }
-    for (const auto& [name, m] : gplan_->merges)
-      if (rec.layer_sizes.count(name)) rec.n_for_map += rec.layer_sizes[name];
+    record_layer_sizes(rec);
   } else {
     rec.decim_map_resolution = plan_->decim_map_res;
     rec.decim_icp_resolution = plan_->decim_icp_res;
@@ -1271,6 +1281,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
           updatePipelineTwistVariables(tw);
           source_.realize();
           run_second_pass();
+          if (gplan_) record_layer_sizes(rec);  // (the record describes the layers that are aligned and merged in the end)
           rec.twist = tw;
         }
       }
@@ -1375,6 +1386,67 @@ std::map<std::string, uint64_t> LidarOdometry::localMapSizes() const {
     sizes[plan_->map_layer] = local_map_ ? local_map_->size() : 0;
   }
   return sizes;
+}
+
+std::map<std::string, LidarOdometry::MapStats> LidarOdometry::localMapStats() const {
+  std::map<std::string, MapStats> out;
+  auto stats = [](const std::shared_ptr<HashedVoxelPointCloud>& m, double voxel_size) {
+    MapStats s;
+    if (m) {
+      s.n_points = m->size();  // (mh_map_get_info: waits for an update that still runs)
+      s.n_voxels = m->voxelCount();
+      s.voxel_size = voxel_size;
+    }
+    return s;
+  };
+  if (gplan_) {
+    for (const auto& m : gplan_->maps) out[m.name] = stats(m.map, m.voxel_size);
+  } else if (plan_) {
+    out[plan_->map_layer] = stats(local_map_, map_voxel_size_);
+  }
+  return out;
+}
+
+LidarOdometry::LayerDump LidarOdometry::downloadLayer(const std::string& name) const {
+  if (!gplan_) throw std::runtime_error("LidarOdometry::downloadLayer: only general plans keep their layers by name");
+  std::shared_ptr<DevicePointCloud> l;
+  if (name == "raw") {
+    l = gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_;
+  } else {
+    const auto it = gplan_->buf.find(name);
+    if (it != gplan_->buf.end()) l = it->second;
+  }
+  if (!l || name == kAdjustedRawKey) throw std::runtime_error("LidarOdometry::downloadLayer: no layer '" + name + "' in the last scan");
+  LayerDump d;
+  d.alive = gplan_->alive.count(name) != 0;
+  const size_t n = l->size();
+  d.x.resize(n); d.y.resize(n); d.z.resize(n); d.t.resize(n); d.src_idx.resize(n);
+  if (!n) return d;
+  check(mh_scan_download(l->handle(), d.x.data(), d.y.data(), d.z.data(), d.t.data(), d.src_idx.data()), "mh_scan_download");
+  if (gplan_->reads_intensity) {  // ('raw' carries the channel, and every derived layer inherits it)
+    d.intensity.resize(n);
+    check(mh_scan_download_intensity(l->handle(), d.intensity.data()), "mh_scan_download_intensity");
+  }
+  return d;
+}
+
+LidarOdometry::MapDump LidarOdometry::downloadMap(const std::string& name) const {
+  std::shared_ptr<HashedVoxelPointCloud> m;
+  if (gplan_) {
+    for (const auto& s : gplan_->maps)
+      if (s.name == name) m = s.map;
+  } else if (plan_ && plan_->map_layer == name) {
+    m = local_map_;
+  }
+  MapDump d;
+  if (!m) return d;  // (not created yet, or no such map: empty)
+  const size_t n = m->size(), v = m->voxelCount();
+  d.x.resize(n); d.y.resize(n); d.z.resize(n); d.src_idx.resize(n);
+  d.vox_keys.resize(3 * v); d.vox_first.resize(v); d.vox_count.resize(v);
+  if (!n) return d;
+  check(mh_map_download(m->handle(), d.x.data(), d.y.data(), d.z.data(), d.src_idx.data(), d.vox_keys.data(), d.vox_first.data(),
+                        d.vox_count.data()), "mh_map_download");
+  return d;
 }
 
 std::map<std::string, std::string> LidarOdometry::describePipeline() const {

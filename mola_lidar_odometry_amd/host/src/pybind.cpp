@@ -231,7 +231,40 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("describePipeline", &LidarOdometry::describePipeline)
       .def("profile", [](const LidarOdometry& lo) { return lo.profile(); })
       .def("localMapSize", [](const LidarOdometry& lo) { return lo.localMap() ? lo.localMap()->size() : 0; })
-      .def("localMapSizes", &LidarOdometry::localMapSizes);
+      .def("localMapSizes", &LidarOdometry::localMapSizes)
+      // debug accessors (they synchronise and copy: tests only)
+      .def("localMapStats", [](const LidarOdometry& lo) {
+        py::dict d;
+        for (const auto& [name, s] : lo.localMapStats()) d[py::str(name)] = py::make_tuple(s.n_points, s.n_voxels, s.voxel_size);
+        return d; })
+      .def("downloadLayer", [](const LidarOdometry& lo, const std::string& name) {
+        const LidarOdometry::LayerDump l = lo.downloadLayer(name);
+        const py::ssize_t n = (py::ssize_t)l.x.size();
+        py::array_t<float> xyz({n, (py::ssize_t)3});
+        auto w = xyz.mutable_unchecked<2>();
+        for (py::ssize_t i = 0; i < n; i++) { w(i, 0) = l.x[i]; w(i, 1) = l.y[i]; w(i, 2) = l.z[i]; }
+        py::dict d;
+        d["xyz"] = xyz;
+        d["t"] = py::array_t<float>(n, l.t.data());
+        d["src_idx"] = py::array_t<uint32_t>(n, l.src_idx.data());
+        d["intensity"] = l.intensity.empty() ? py::object(py::none()) : py::object(py::array_t<float>(n, l.intensity.data()));
+        d["alive"] = l.alive;
+        return d; })
+      .def("downloadMap", [](const LidarOdometry& lo, const std::string& name) {
+        const LidarOdometry::MapDump m = lo.downloadMap(name);
+        const py::ssize_t n = (py::ssize_t)m.x.size(), v = (py::ssize_t)m.vox_count.size();
+        py::array_t<float> xyz({n, (py::ssize_t)3});
+        auto w = xyz.mutable_unchecked<2>();
+        for (py::ssize_t i = 0; i < n; i++) { w(i, 0) = m.x[i]; w(i, 1) = m.y[i]; w(i, 2) = m.z[i]; }
+        py::array_t<int32_t> keys({v, (py::ssize_t)3});
+        if (v) std::copy(m.vox_keys.begin(), m.vox_keys.end(), keys.mutable_data());
+        py::dict d;
+        d["xyz"] = xyz;
+        d["src_idx"] = py::array_t<uint32_t>(n, m.src_idx.data());
+        d["vox_keys"] = keys;
+        d["vox_first"] = py::array_t<uint32_t>(v, m.vox_first.data());
+        d["vox_count"] = py::array_t<uint32_t>(v, m.vox_count.data());
+        return d; });
   py::class_<AlignBatcher, std::shared_ptr<AlignBatcher>>(m, "AlignBatcher")
       .def(py::init<size_t>(), py::arg("participants"))
       .def("leave", [](AlignBatcher& b) { b.leave(); }, py::call_guard<py::gil_scoped_release>())

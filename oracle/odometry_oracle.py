@@ -55,9 +55,37 @@ def _subst_env(text):
     return text
 
 
+# the top-level sections the oracle drivers read
+_SECTIONS = ("params", "navstate_fuse_params", "icp_settings_with_vel", "icp_settings_without_vel", "localmap_generator",
+             "observations_filter_adjust_timestamps", "observations_filter_1st_pass", "observations_filter_2nd_pass",
+             "insert_observation_into_local_map")
+
+
+def load_pipeline_text(text):
+    """YAML text -> dict.  A file whose error lies in a top-level section no oracle reads (extras/lidar3d-intensity.yaml indents
+    one key of its observations_generator differently, which the C++ loaders accept) is read again without those sections; an
+    error anywhere else, or one whose place is unknown, is raised as it is."""
+    text = _subst_env(text)
+    try:
+        return yaml.safe_load(text)
+    except yaml.MarkedYAMLError as first:
+        lines = text.splitlines()
+        section = [None] * len(lines)  # the top-level key every line belongs to
+        cur = None
+        for i, line in enumerate(lines):
+            m = re.match(r"^([A-Za-z_][A-Za-z0-9_]*):", line)
+            if m:
+                cur = m.group(1)
+            section[i] = cur
+        marks = [mk.line for mk in (first.context_mark, first.problem_mark) if mk is not None]
+        if not marks or any(mk >= len(lines) or section[mk] is None or section[mk] in _SECTIONS for mk in marks):
+            raise
+        return yaml.safe_load("\n".join(l for l, s in zip(lines, section) if s in _SECTIONS) + "\n")
+
+
 def load_pipeline(path):
     with open(path) as f:
-        return yaml.safe_load(_subst_env(f.read()))
+        return load_pipeline_text(f.read())
 
 
 def _b(v):
@@ -94,8 +122,9 @@ _KERNELS = {"None": oc.KERNEL_NONE, "GemanMcClure": oc.KERNEL_GM_C4, "GemanMcClu
 
 
 class OdometryOracle:
-    def __init__(self, pipeline_yaml_path, n_threads=8):
-        c = load_pipeline(pipeline_yaml_path)
+    def __init__(self, pipeline_yaml_path=None, n_threads=8, text=None):
+        """The pipeline from a file, or from YAML `text`."""
+        c = load_pipeline(pipeline_yaml_path) if text is None else load_pipeline_text(text)
         self.cfg = c
         self.p = c["params"]
         self.n_threads = n_threads
@@ -108,6 +137,15 @@ class OdometryOracle:
         self.motion_model_prior = _b(nav.get("motion_model_prior", False))
         it = [float(v) for v in (nav.get("initial_twist") or [])]
         self.initial_twist = np.array(it) if len(it) == 6 and any(v != 0.0 for v in it) else None
+        icp = c["icp_settings_with_vel"]
+        self.icp = icp
+        self.matchers = icp["matchers"]
+        self.solver = icp["solvers"][0]["params"]
+        self._load_chain(c)
+        self.reset()
+
+    def _load_chain(self, c):
+        """The default chain (FilterPlan of the C++ driver); oracle/chain_oracle.py reads any other."""
         f1 = c["observations_filter_1st_pass"]
         names = [e["class_name"].split("::")[-1] for e in f1]
         assert names == ["FilterDecimateVoxels", "FilterByRange", "FilterBoundingBox", "FilterDecimateVoxels"], names
@@ -115,12 +153,7 @@ class OdometryOracle:
         ts = c["observations_filter_adjust_timestamps"][0]["params"]
         self.ts_method = oc.TS_MIDDLE_IS_ZERO if str(ts["method"]).endswith("MiddleIsZero") else oc.TS_EARLIEST_IS_ZERO
         self.ts_offset = ts["time_offset"]
-        icp = c["icp_settings_with_vel"]
-        self.icp = icp
-        self.matchers = icp["matchers"]
-        self.solver = icp["solvers"][0]["params"]
         self.map_def = c["localmap_generator"][0]["params"]["metric_map_definition"]
-        self.reset()
 
     def reset(self):
         self.vars = {}
@@ -239,7 +272,25 @@ class OdometryOracle:
             self.est_range = max(_bbox_radius(xyz[np.isfinite(xyz).all(1)]), float(P["absolute_minimum_sensor_range"]))
         self._update_vars()
         rec["twist"] = np.array([self.vars[k] for k in ("vx", "vy", "vz", "wx", "wy", "wz")])
-        # ---- 1st pass + 2nd pass (yaml:278-350)
+        range_layer = self._run_filters(xyz, t, rec)
+        if self.est_range is not None:
+            radius = max(_bbox_radius(range_layer) if len(range_layer) else 0.0, float(P["absolute_minimum_sensor_range"]))
+            self.inst_range = radius
+            a = float(P["max_sensor_range_filter_coefficient"])
+            self.est_range = self.est_range * a + radius * (1.0 - a)
+        rec["estimated_sensor_max_range"], rec["instantaneous_sensor_max_range"] = self.est_range, self.inst_range
+        self.last_obs_tim = stamp
+        self.last_obs_timestamp = stamp
+        if self.first_ever is None:
+            self.first_ever = stamp
+        if len(xyz) == 0:
+            rec["dropped"] = True
+            return rec
+        return self._register(stamp, rec)
+
+    # ---- the parts a subclass with another filter chain / other maps replaces (oracle/chain_oracle.py)
+    def _run_filters(self, xyz, t, rec):
+        """1st pass + 2nd pass (yaml:278-350); returns the layer the sensor-range estimate reads."""
         v = self.vars
         d1, rg, bb, d2 = self.f1
         self.idx_map, self.idx_icp = oc.preprocess(
@@ -254,25 +305,50 @@ class OdometryOracle:
         rec["n_for_map"], rec["n_for_icp"] = len(self.for_map), len(self.for_icp)
         rec["decim_map_resolution"] = formula(d1["voxel_filter_resolution"], v)
         rec["decim_icp_resolution"] = formula(d2["voxel_filter_resolution"], v)
-        if self.est_range is not None:
-            radius = max(_bbox_radius(self.for_icp) if len(self.for_icp) else 0.0, float(P["absolute_minimum_sensor_range"]))
-            self.inst_range = radius
-            a = float(P["max_sensor_range_filter_coefficient"])
-            self.est_range = self.est_range * a + radius * (1.0 - a)
-        rec["estimated_sensor_max_range"], rec["instantaneous_sensor_max_range"] = self.est_range, self.inst_range
-        self.last_obs_tim = stamp
-        self.last_obs_timestamp = stamp
-        if self.first_ever is None:
-            self.first_ever = stamp
-        if len(xyz) == 0:
-            rec["dropped"] = True
-            return rec
+        return self.for_icp
 
+    def _redo_second_pass(self, rec):
+        """The twist hook changed vx..wz: the 2nd pass again (LidarOdometry.cpp:973-1004)."""
+        self._deskew_layers()
+
+    def _maps_empty(self):
+        return self.map is None or self.map.num_points == 0
+
+    def _align(self, T0, q, prior, rec):
+        return oc.icp_align(self.map, self.for_icp, T0, q, prior=prior, n_threads=self.n_threads)
+
+    def _clear_maps(self):
+        self.map = oc.Map(*self._map_args) if self.map is not None else None  # local_map->clear()
+
+    def _map_args_of(self, map_def):
+        """(oracle_c.Map arguments, remove_voxels_farther_than) of one metric_map_definition, from the variables of now."""
+        co, io = map_def["creationOpts"], map_def["insertOpts"]
+        voxel_size = formula(co["voxel_size"], self.vars)
+        ndt = map_def["class"].endswith("NDT")
+        args = (np.float32(voxel_size), int(formula(io["max_points_per_voxel"], self.vars)), oc.INDEX_FLOOR,
+                float(io.get("min_distance_between_points", 0.0)),
+                float(io.get("max_eigen_ratio_for_planes", 0.05)) if ndt else 0.0, 4)
+        return args, voxel_size, float(np.float32(formula(io.get("remove_voxels_farther_than", 0.0), self.vars)))
+
+    def _create_maps(self):
+        self._map_args, self.voxel_size, self.remove_far = self._map_args_of(self.map_def)
+        self.map = oc.Map(*self._map_args)
+
+    def _insert_into_maps(self):
+        self.map.insert_posed(self.for_map, self.last_pose, self.remove_far)
+
+    def _record_maps(self, rec):
+        rec["n_map_points"] = self.map.num_points if self.map is not None else 0
+        rec["n_map_voxels"] = self.map.num_voxels if self.map is not None else 0
+
+    def _register(self, stamp, rec):
+        P, A, L = self.p, self.p["adaptive_threshold"], self.p["local_map_updates"]
+        rec["margins"] = []  # (name, value, threshold) of the floating-point decisions of this scan outside the ICP loop
         update_map = False
         self.last_mm = self._nav_estimate(stamp)
         has_mm = self.last_mm is not None
         rec["had_motion_model"] = has_mm
-        if self.map is None or self.map.num_points == 0:
+        if self._maps_empty():
             rec["first_scan"] = True
             update_map = True
             self.trajectory.append((stamp, self.last_pose.copy()))
@@ -301,7 +377,7 @@ class OdometryOracle:
                                  # U12 (MOLA_HIP_MATCHED_POINTS=skip): points the plane matcher paired get no point pairing
                                  pt2pt_skip_plane_paired=os.environ.get("MOLA_HIP_MATCHED_POINTS", "again") in ("skip", "1"))
                 prior = (self.last_mm[0], self.last_mm[2]) if (has_mm and self.last_mm[2] is not None) else None
-                res = oc.icp_align(self.map, self.for_icp, T0, q, prior=prior, n_threads=self.n_threads)
+                res = self._align(T0, q, prior, rec)
                 rec["align_calls"] += 1
                 remaining -= min(remaining, res["n_iterations"])
                 rec["icp_iterations"] += res["n_iterations"]
@@ -315,12 +391,13 @@ class OdometryOracle:
                     tw = np.concatenate([inc[:, 3] / since_kf, w / since_kf])
                     for k, val in zip(("vx", "vy", "vz", "wx", "wy", "wz"), tw):
                         self.vars[k] = float(val)
-                    self._deskew_layers()
+                    self._redo_second_pass(rec)
                     rec["twist"] = tw
             rec["icp_run"] = True
             rec["termination"] = res["termination_reason"]
             rec["goodness"] = res["quality"]
             good = res["quality"] >= float(P["min_icp_goodness"])
+            rec["margins"].append(("min_icp_goodness", float(res["quality"]), float(P["min_icp_goodness"])))
             self.last_icp_was_good, self.last_icp_quality = good, res["quality"]
             rec["icp_good"] = good
             if good:
@@ -349,6 +426,9 @@ class OdometryOracle:
                 first, dist, rot = False, float(np.linalg.norm(rel[:, 3])), float(np.linalg.norm(oc.so3_log(rel.reshape(12))))
             else:
                 first, dist, rot = True, 0.0, 0.0
+            if good and _b(L["enabled"]) and has_mm and not first:
+                rec["margins"] += [("keyframe_trans", dist, formula(L["min_translation_between_keyframes"], self.vars)),
+                                   ("keyframe_rot", rot, math.radians(formula(L["min_rotation_between_keyframes"], self.vars)))]
             update_map = (good and _b(L["enabled"]) and has_mm and
                           (first or dist > formula(L["min_translation_between_keyframes"], self.vars) or
                            rot > math.radians(formula(L["min_rotation_between_keyframes"], self.vars))))
@@ -363,26 +443,18 @@ class OdometryOracle:
                         tp = self.last_pose.reshape(3, 4)[:, 3]
                         self.kfs = [k for k in self.kfs if np.linalg.norm(k.reshape(3, 4)[:, 3] - tp) <= maxd]
         if (not self.last_icp_was_good) and len(self.trajectory) == 1:
-            self.map = oc.Map(*self._map_args) if self.map is not None else None  # local_map->clear()
+            self._clear_maps()
             self.trajectory = []
             update_map = False
             self.last_icp_was_good = True
             rec["restarted"] = True
         if update_map:
             if self.map is None:
-                co, io = self.map_def["creationOpts"], self.map_def["insertOpts"]
-                self.voxel_size = formula(co["voxel_size"], self.vars)
-                ndt = self.map_def["class"].endswith("NDT")
-                self._map_args = (np.float32(self.voxel_size), int(formula(io["max_points_per_voxel"], self.vars)), oc.INDEX_FLOOR,
-                                  float(io.get("min_distance_between_points", 0.0)),
-                                  float(io.get("max_eigen_ratio_for_planes", 0.05)) if ndt else 0.0, 4)
-                self.map = oc.Map(*self._map_args)
-                self.remove_far = float(np.float32(formula(io.get("remove_voxels_farther_than", 0.0), self.vars)))
+                self._create_maps()
             self._update_vars()
-            self.map.insert_posed(self.for_map, self.last_pose, self.remove_far)
+            self._insert_into_maps()
             rec["map_updated"] = True
         rec["pose"] = self.last_pose.copy()
         rec["sigma"] = self.sigma
-        rec["n_map_points"] = self.map.num_points if self.map is not None else 0
-        rec["n_map_voxels"] = self.map.num_voxels if self.map is not None else 0
+        self._record_maps(rec)
         return rec

@@ -11,48 +11,11 @@ import numpy as np
 import pytest
 
 from mola_lidar_odometry_amd import capi
+from oracle.filters_np import LARGER, OTHER, SMALLER, curvature_classes, curvature_np  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-LARGER, SMALLER, OTHER = 0, 1, 2
 MH_ERR_INVALID_ARGUMENT = 1  # include/molahip.h
-
-
-def curvature_classes(xyz, max_cosine=0.4, min_clearance=0.20, max_gap=1.0):
-    """Class of every point (-1: end points, in no output), float32 throughout, in the order molahip.h writes it.  numpy's
-    float32 +, -, *, / and sqrt are correctly rounded, and nothing here is fused."""
-    p = np.asarray(xyz, np.float32).reshape(-1, 3)
-    n = len(p)
-    cls = np.full(n, -1, np.int64)
-    if n < 3:
-        return cls
-    f = np.float32
-    mc, mcl, mg = f(max_cosine), f(min_clearance), f(max_gap)
-    gap2, clr2 = mg * mg, mcl * mcl
-    with np.errstate(all="ignore"):
-        a = p[1:-1] - p[:-2]
-        b = p[2:] - p[1:-1]
-        na = (a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2]
-        nb = (b[:, 0] * b[:, 0] + b[:, 1] * b[:, 1]) + b[:, 2] * b[:, 2]
-        dot = (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
-        c = dot / (np.sqrt(na) * np.sqrt(nb))
-        gap = (na > gap2) | (nb > gap2)
-        clear = (na < clr2) | (nb < clr2)
-        inner = np.where(c < mc, LARGER, SMALLER)
-    cls[1:-1] = np.where(gap | clear, OTHER, inner)
-    return cls
-
-
-def curvature_np(xyz, t=None, src=None, **kw):
-    """The three outputs as dicts {xyz, t, src_idx} (t None without time stamps), in input order."""
-    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
-    cls = curvature_classes(xyz, **kw)
-    src = np.arange(len(xyz), dtype=np.uint32) if src is None else np.asarray(src, np.uint32)
-    out = []
-    for k in (LARGER, SMALLER, OTHER):
-        m = cls == k
-        out.append(dict(xyz=xyz[m], t=None if t is None else np.asarray(t, np.float32)[m], src_idx=src[m]))
-    return out
 
 
 def _idx(xyz, k, **kw):

@@ -16,7 +16,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
                                              ("fuzz_batch.py", 6, 104), ("fuzz_map_insert.py", 12, 105),
                                              ("fuzz_preprocess.py", 25, 106), ("fuzz_odometry.py", 3, 107),
                                              ("fuzz_hook_replay.py", 20, 108), ("stress_cli_sequences.py", 1, 109),
-                                             ("fuzz_layers.py", 12, 110)])
+                                             ("fuzz_layers.py", 12, 110),
+                                             # (the oracle side is the cost: 3.1 s per case measured on the CPU alone; the
+                                             #  tool's 2 % cap on set-apart cases applies from 50 cases up, so not here: the
+                                             #  campaigns of DESIGN.md section 5 hold it)
+                                             ("fuzz_chains.py", 30, 111)])
 def test_randomized_parity_tool(tool, cases, seed):
     env = dict(os.environ)
     for k in ("MH_MATCH", "MH_NO_PREV_BOUND", "MH_NO_FUSE16", "MH_NO_STEP_CHAIN", "MH_NO_LOCKSTEP", "MH_NO_GRAPH", "MH_NO_QIDX"):

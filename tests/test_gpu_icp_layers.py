@@ -529,7 +529,8 @@ def hl():
 
 
 @pytest.mark.parametrize("text", [DUAL_MAP, EDGES], ids=["dual-map", "edges"])
-def test_host_layer_fused_layers_equal_its_generic_loop(hl, small_workload, text):
+def test_host_layer_fused_layers_equal_its_generic_loop(hl, oracle, small_workload, text):
+    """... and BOTH routes equal the float64 reference the chain oracle driver aligns with (oracle/layers_oracle.py)."""
     w = small_workload
     near_l, far_l, near_g, far_g = _split(w)
     g = hl.metric_map_t()
@@ -558,6 +559,20 @@ def test_host_layer_fused_layers_equal_its_generic_loop(hl, small_workload, text
     assert a.n_pairs() == b.n_pairs()
     np.testing.assert_allclose(a.pose(), b.pose(), rtol=0, atol=1e-7)
     assert a.quality == pytest.approx(b.quality, abs=1e-12)
+    omaps = {"localmap": oracle.Map(1.0, 20).insert(w.map_xyz), "localmap_far": oracle.Map(0.5, 20).insert(far_g)}
+    k = np.arange(40)
+    thr = ([np.full(40, 3.0 * w.sigma), np.full(40, 2.0 * w.sigma)] if text is DUAL_MAP else
+           [2.0 * np.maximum(w.sigma, 2.0 * w.sigma - k / 20.0)] * 2)
+    pairs = [dict(map=omaps["localmap"], local=w.scan_xyz, threshold=thr[0], weight=1.0),
+             dict(map=omaps["localmap_far"], local=near_l, threshold=thr[1], weight=1.0)]
+    o = layers_oracle.icp_align_layers(pairs, synth.pose_from_ypr(w.guess_ypr), oracle.ICPParams(
+        max_iterations=40, kernel_param=0.5 * _base(w.sigma, 40), gn=oracle.GNParams(max_inner_iterations=2)))
+    assert layers_oracle.nearest_decision(o["margins"])[1] > 1e-9 and o["max_cond"] < 1e10  # (a comparable alignment)
+    for res in (a, b):
+        assert res.nIterations == o["n_iterations"] and res.terminationReason.name == capi.TERM_NAMES[o["termination_reason"]]
+        assert res.n_pairs() == o["n_final_pairs"] > 0
+        assert res.quality == pytest.approx(o["quality"], abs=1e-12)
+        np.testing.assert_allclose(res.pose(), o["T"], rtol=0, atol=1e-7)
 
 
 def test_host_layer_three_weighted_entries_match_the_reference(hl, oracle, small_workload):

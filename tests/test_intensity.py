@@ -12,59 +12,12 @@ import numpy as np
 import pytest
 
 from mola_lidar_odometry_amd import capi
+from oracle.filters_np import HIGH, LOW, MID, _ord, by_intensity_np, intensity_classes, normalize_np  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MH_ERR_INVALID_ARGUMENT = 1  # include/molahip.h
-LOW, MID, HIGH = 0, 1, 2
 NEW_SYMBOLS = ("mh_scan_set_intensity", "mh_scan_update_aos_i", "mh_scan_download_intensity", "mh_scan_normalize_intensity",
                "mh_scan_by_intensity")
-
-
-def _ord(a):
-    """Order-preserving uint32 of float32 values (-0 < +0), what the device's min / max compare."""
-    u = np.asarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    return np.where(u & 0x80000000, (~u) & 0xFFFFFFFF, u | 0x80000000).astype(np.uint64)
-
-
-def normalize_np(i, range_=None):
-    """FilterNormalizeIntensity as molahip.h states it: returns (new values, new range or None).  `range_` is the remembered
-    {min, max} ({nan, nan}: none); None = remember_intensity_range false."""
-    i = np.asarray(i, np.float32)
-    f = np.float32
-    good = i[~np.isnan(i)]
-    lo = hi = f(np.nan)
-    if len(good):
-        o = _ord(good)
-        lo, hi = good[np.argmin(o)], good[np.argmax(o)]
-    if range_ is not None:
-        rlo, rhi = f(range_[0]), f(range_[1])
-        if not np.isnan(rlo) and (np.isnan(lo) or rlo < lo):
-            lo = rlo
-        if not np.isnan(rhi) and (np.isnan(hi) or rhi > hi):
-            hi = rhi
-    if np.isnan(lo) and np.isnan(hi):
-        return i.copy(), (None if range_ is None else np.asarray(range_, np.float32).copy())
-    with np.errstate(all="ignore"):
-        d = f(hi - lo)
-        k = f(f(1.0) / d) if d > 0 else f(0.0)
-        out = ((i - lo) * k).astype(np.float32)
-    return out, (None if range_ is None else np.array([lo, hi], np.float32))
-
-
-def intensity_classes(i, low=0.1, high=0.9):
-    i = np.asarray(i, np.float32)
-    with np.errstate(invalid="ignore"):
-        return np.where(i < np.float32(low), LOW, np.where(i > np.float32(high), HIGH, MID))
-
-
-def by_intensity_np(xyz, i, t=None, src=None, low=0.1, high=0.9):
-    """The three outputs as dicts {xyz, t, i, src_idx} in input order."""
-    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
-    i = np.asarray(i, np.float32)
-    cls = intensity_classes(i, low, high)
-    src = np.arange(len(xyz), dtype=np.uint32) if src is None else np.asarray(src, np.uint32)
-    return [dict(xyz=xyz[cls == k], t=None if t is None else np.asarray(t, np.float32)[cls == k], i=i[cls == k],
-                 src_idx=src[cls == k]) for k in (LOW, MID, HIGH)]
 
 
 # ------------------------------------------------------------------------------------------------ CPU: the restatements

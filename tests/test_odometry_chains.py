@@ -1,13 +1,19 @@
 """Stand-alone driver on filter chains other than the default one (general plans over named device layers): the reference's
 extras pipelines and inline equivalents are recognised and described (CPU), intensity filters are rejected (CPU), and on the
 GPU the edges-, dual-map- and near-far-shaped chains track a synthetic drive, deterministically and identically through
-onLidar and the interleaved entry, with observation layers of the sizes a numpy restatement of the chain gives."""
+onLidar and the interleaved entry, with observation layers of the sizes a numpy restatement of the chain gives.
+
+The chain oracle (oracle/chain_oracle.py) restates the general plan independently.  On the CPU it tracks the drive on every
+chain, reproduces OdometryOracle on the default pipeline file, reads the same plan as describePipeline(), and gives hand-built
+known answers for what is new in it.  On the GPU the C++ driver is held to it SCAN BY SCAN (drive_against_oracle): the sixteen
+decision keys, every layer's size and content, every map's counts and content, scalars to 1e-9 and poses to 1e-6."""
 import os
 
 import numpy as np
 import pytest
 
 from mola_lidar_odometry_amd import synth, trajectory
+from oracle.chain_compare import DECISION_KEYS, SCALAR_KEYS, drive_against_oracle, feed as _feed  # noqa: F401 (_feed: test_odometry_intensity.py)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PIPE = os.path.join(ROOT, "pipelines", "lidar3d-default-hip.yaml")
@@ -166,6 +172,41 @@ def inline_pipeline(tail, matches):
 
 CHAINS = {"edges": (EDGES_TAIL, EDGES_MATCHES), "dual-map": (DUAL_TAIL, DUAL_MATCHES), "near-far": (NEARFAR_TAIL, NEARFAR_MATCHES)}
 
+# a chain whose 2nd pass FILTERS after its de-skew: a re-run of that pass by the twist hook can change the layers' sizes
+_ONE_MATCH = '          - {global: "localmap", local: "decimated_for_icp", weight: 1.0}\n'
+PASS2_TAIL = ("localmap_generator:\n" + _map("localmap", 20) + """observations_filter_adjust_timestamps:
+  - class_name: mp2p_icp_filters::FilterAdjustTimestamps
+    params:
+      pointcloud_layer: 'raw'
+      silently_ignore_no_timestamps: true
+      time_offset: 'SENSOR_TIME_OFFSET'
+      method: 'TimestampAdjustMethod::MiddleIsZero'
+observations_filter_1st_pass:
+""" + _decimate("raw", "skewed", "0.25") + """observations_filter_2nd_pass:
+  - class_name: mp2p_icp_filters::FilterDeskew
+    params:
+      input_pointcloud_layer: 'skewed'
+      output_pointcloud_layer: 'deskewed'
+      silently_ignore_no_timestamps: true
+  - class_name: mp2p_icp_filters::FilterByRange
+    params:
+      input_pointcloud_layer: 'deskewed'
+      output_layer_between: 'in_range'
+      range_min: 3.0
+      range_max: 30.0
+""" + _decimate("in_range", "decimated_for_map", "0.5") + _decimate("decimated_for_map", "decimated_for_icp", "1.5") +
+              """  - class_name: mp2p_icp_filters::FilterDeleteLayer
+    params:
+      pointcloud_layer_to_remove: ['raw', 'skewed', 'deskewed', 'in_range']
+insert_observation_into_local_map:
+""" + _merge("decimated_for_map", "localmap"))
+
+# the edges chain with a curvature split no point passes (max_gap below the point spacing): every aligned layer is empty, while a
+# plain decimation still feeds the first map -- NoPairings, a bad ICP, the motion model reset and the restart path, every scan
+NOPAIRS_TAIL = (EDGES_TAIL.replace("max_gap: 1.0", "max_gap: 0.001")
+                .replace("  - class_name: mp2p_icp_filters::FilterDeleteLayer", _decimate("filtered", "decimated_all", "1.0") +
+                         "  - class_name: mp2p_icp_filters::FilterDeleteLayer", 1) + _merge("decimated_all", "localmap_small_curvature"))
+
 
 @pytest.fixture(scope="module")
 def host():
@@ -175,6 +216,20 @@ def host():
 
 def _load(host, text):
     lo = host.LidarOdometry()
+    lo.initialize(host.Config.FromYamlText(text))
+    return lo
+
+
+# ------------------------------------------------------------------------------------------------ driver against the chain oracle
+def chain_oracle(text, n_threads=8):
+    from oracle import chain_oracle as co
+    return co.ChainOdometryOracle(text=text, n_threads=n_threads)
+
+
+def new_driver(host, text, intensity=False):
+    lo = host.LidarOdometry(0, True)
+    if intensity:
+        lo.setIntensityInput(True)
     lo.initialize(host.Config.FromYamlText(text))
     return lo
 
@@ -248,6 +303,206 @@ def test_chain_errors_name_the_problem(host):
         _load(host, bad)
 
 
+# ---- the chain oracle alone (CPU)
+def _oracle_run(text, drive, n=None, intensity=None):
+    o = chain_oracle(text)
+    for k, ((xyz, t), st) in enumerate(list(zip(drive["scans"], drive["stamps"]))[:n]):
+        o.on_lidar(float(st), xyz, t, intensity=None if intensity is None else intensity[k])
+    return o
+
+
+@pytest.fixture(scope="module")
+def cpu_drive():
+    return synth.make_drive(14)
+
+
+@pytest.mark.parametrize("chain,bar", [("edges", 0.5), ("dual-map", 0.2), ("near-far", 0.2)])
+def test_chain_oracle_tracks_the_drive(cpu_drive, chain, bar):
+    """The free-running oracle: the ATE bars of the GPU tests, no scan near a decision threshold or ill-conditioned (the cap of
+    the per-scan GPU comparison is zero such scans), and the same records when run again."""
+    from oracle.chain_oracle import ChainOdometryOracle
+    text = inline_pipeline(*CHAINS[chain])
+    o = _oracle_run(text, cpu_drive)
+    recs = o.records
+    assert recs[0]["first_scan"] and recs[0]["map_updated"] and not any(r["dropped"] for r in recs)
+    assert all(r["icp_run"] and r["icp_good"] for r in recs[2:])
+    assert _ate(recs, cpu_drive) < bar
+    assert [k for k, r in enumerate(recs) if ChainOdometryOracle.set_apart(r)] == []
+    assert sum(r["twist_corrections"] for r in recs) >= 1
+    again = _oracle_run(text, cpu_drive, n=6).records
+    for x, y in zip(again, recs):
+        assert x["layer_sizes"] == y["layer_sizes"] and x["maps"] == y["maps"] and np.array_equal(x["pose"], y["pose"])
+
+
+def test_chain_oracle_reproduces_the_default_chain_oracle(cpu_drive):
+    """On the default pipeline FILE the generalised oracle makes OdometryOracle's decisions, layers and maps, and its poses to
+    the bar at which tests/test_oracle_layers.py holds layers_oracle to the C oracle (1e-9; the solve is numpy's here).
+    (Measured on this drive: poses within 1.5e-15, sigma within 1.2e-16.)"""
+    from oracle import chain_oracle as co, odometry_oracle as oo
+    a, b = oo.OdometryOracle(PIPE), co.ChainOdometryOracle(PIPE)
+    for k, ((xyz, t), st) in enumerate(zip(cpu_drive["scans"], cpu_drive["stamps"])):
+        ra, rb = a.on_lidar(st, xyz, t), b.on_lidar(st, xyz, t)
+        for key in DECISION_KEYS:
+            if key not in ("n_for_map", "n_for_icp"):  # (general-plan meaning there: all layers / all merged layers)
+                assert ra[key] == rb[key], (k, key, ra[key], rb[key])
+        assert rb["layer_sizes"]["decimated_for_map"] == ra["n_for_map"] and rb["layer_sizes"]["decimated_for_icp"] == ra["n_for_icp"]
+        assert rb["n_for_map"] == ra["n_for_map"] and rb["n_for_icp"] == sum(rb["layer_sizes"].values())
+        assert np.array_equal(b.layers["decimated_for_map"]["src_idx"], a.idx_map), k
+        assert np.array_equal(b.layers["decimated_for_icp"]["src_idx"], a.idx_icp), k
+        assert np.array_equal(b.layers["decimated_for_map"]["xyz"], a.for_map) and np.array_equal(b.layers["decimated_for_icp"]["xyz"], a.for_icp)
+        assert rb["maps"] == {"localmap": (ra["n_map_points"], ra["n_map_voxels"], a.voxel_size)}
+        for key in SCALAR_KEYS:
+            assert abs(ra[key] - rb[key]) <= 1e-9 * max(1.0, abs(ra[key])), (k, key, ra[key], rb[key])
+        assert np.abs(ra["twist"] - rb["twist"]).max() < 1e-9
+        assert np.abs(ra["pose"] - rb["pose"]).max() < 1e-9, (k, np.abs(ra["pose"] - rb["pose"]).max())
+    assert sum(r["twist_corrections"] for r in b.records) >= 1
+    da, db = a.map.dump(), b.maps["localmap"]["map"].dump()
+    for key in ("vox_keys", "vox_count", "src_idx", "xyz"):
+        assert np.array_equal(da[key], db[key]), key
+
+
+def _plan_of(d):
+    """describePipeline() of a general plan in the shape of ChainOdometryOracle.describe() (without the pairs: the driver
+    describes its ICP objects elsewhere)."""
+    return dict(steps=[d[f"step:{i:02d}"] for i in range(int(d["steps"]))], maps={k[4:]: v for k, v in d.items() if k.startswith("map:")},
+                merges=sorted((k[6:], v) for k, v in d.items() if k.startswith("merge:")), timestamp_method=int(d["timestamp_method"]))
+
+
+def _assert_same_plan(lo, o, pairs=None):
+    want, got = o.describe(), _plan_of(lo.describePipeline())
+    assert got["steps"] == want["steps"]
+    assert got["maps"] == want["maps"] and list(got["maps"]) == sorted(want["maps"])
+    assert got["merges"] == sorted(want["merges"]) and got["timestamp_method"] == want["timestamp_method"]
+    if pairs is not None:
+        assert want["pairs"] == pairs
+
+
+@pytest.mark.parametrize("chain", sorted(CHAINS) + ["pass2", "nopairs"])
+def test_oracle_and_driver_read_the_same_plan(host, chain):
+    tail, matches = {"pass2": (PASS2_TAIL, _ONE_MATCH), "nopairs": (NOPAIRS_TAIL, EDGES_MATCHES)}.get(chain) or CHAINS[chain]
+    text = inline_pipeline(tail, matches)
+    pairs = {"dual-map": [("localmap", "decimated_for_icp", 1.0), ("localmap_far", "decimated_for_map_far", 0.5)],
+             "edges": [("localmap_large_curvature", "decimated_for_icp_large_curvature", 1.0),
+                       ("localmap_small_curvature", "decimated_for_icp_smaller_curvature", 1.0)]}.get(chain)
+    _assert_same_plan(_load(host, text), chain_oracle(text), pairs)
+
+
+def _reference_extras():
+    """Every odometry pipeline file of the reference's pipelines/extras/ (those with observation filters: the directory also
+    holds icp-pipeline_no_motion_model.yaml, an ICP block alone that no driver can be initialised from, and an .ini file)."""
+    if not os.path.isdir(REF_EXTRAS):
+        return ["(reference tree not present)"]
+    return sorted(f for f in os.listdir(REF_EXTRAS) if f.endswith(".yaml") and
+                  "observations_filter_1st_pass:" in open(os.path.join(REF_EXTRAS, f)).read())
+
+
+@pytest.mark.parametrize("name", _reference_extras())
+def test_oracle_and_driver_read_the_same_plan_from_reference_extras(host, name):
+    from oracle import chain_oracle as co
+    path = os.path.join(REF_EXTRAS, name)
+    if not os.path.exists(path):
+        pytest.skip("reference tree not present on this box")
+    lo = host.LidarOdometry()
+    lo.setIntensityInput(name == "lidar3d-intensity.yaml")
+    lo.initialize(host.Config.FromYamlFile(path))
+    _assert_same_plan(lo, co.ChainOdometryOracle(path))
+
+
+# ---- hand-built known answers for what is new in the chain oracle
+def _grid_scan(n=40, spacing=0.5, z=0.0):
+    g = np.arange(n, dtype=np.float32) * np.float32(spacing) + np.float32(2.0)
+    xyz = np.stack([np.repeat(g, n), np.tile(g, n), np.full(n * n, z, np.float32)], 1)
+    return xyz, np.linspace(-0.05, 0.05, n * n).astype(np.float32)
+
+
+def test_oracle_layer_deletion_and_second_pass_restart():
+    """FilterDeleteLayer removes layers from what is aligned; a re-run of the 2nd pass starts from the layers alive after the
+    1st -- also from one the 2nd pass itself deletes -- and de-skews with the twist of that moment."""
+    o = chain_oracle(inline_pipeline(PASS2_TAIL, _ONE_MATCH))
+    xyz, t = _grid_scan()
+    o.on_lidar(0.0, xyz, t)
+    assert sorted(o.layers) == ["decimated_for_icp", "decimated_for_map"] and sorted(o.layers1) == ["raw", "skewed"]
+    # 'raw' after FilterAdjustTimestamps (MiddleIsZero): every finite point, indexed into the input, time stamps centred
+    assert np.array_equal(o.layers1["raw"]["src_idx"], np.arange(len(xyz))) and abs(float(o.layers1["raw"]["t"].mean())) < 1e-6
+    # grid of 0.5 m, decimated at 0.25 m: every point survives; the range 3..30 m then cuts a known set
+    assert len(o.layers1["skewed"]["xyz"]) == len(xyz)
+    r = np.linalg.norm(xyz.astype(np.float64), axis=1)
+    assert len(o.layers["decimated_for_map"]["xyz"]) > 0
+    assert set(o.layers["decimated_for_map"]["src_idx"]) <= set(np.nonzero((r >= 3.0) & (r <= 30.0))[0])
+    before = o.layers["decimated_for_map"]["xyz"].copy()
+    rec = dict(o.records[-1])
+    o.vars.update(vx=10.0, wz=0.5)
+    o._redo_second_pass(rec)
+    assert sorted(o.layers) == ["decimated_for_icp", "decimated_for_map"] and sorted(o.layers1) == ["raw", "skewed"]
+    assert rec["layer_sizes"] == {n: len(l["xyz"]) for n, l in o.layers.items()}
+    moved = o.layers["decimated_for_map"]["xyz"]
+    assert len(moved) != len(before) or not np.array_equal(moved, before)
+    # the layer is the de-skew of `skewed` at the new twist, restated: p' = Rz(wz t) p + v t, then cut by range
+    s = o.layers1["skewed"]
+    i = int(o.layers["decimated_for_map"]["src_idx"][0])
+    j = int(np.nonzero(s["src_idx"] == i)[0][0])
+    ang, tt = 0.5 * float(s["t"][j]), float(s["t"][j])
+    p = s["xyz"][j].astype(np.float64)
+    want = np.array([np.cos(ang) * p[0] - np.sin(ang) * p[1] + 10.0 * tt, np.sin(ang) * p[0] + np.cos(ang) * p[1], p[2]])
+    assert np.abs(moved[0] - want).max() < 1e-5
+
+
+def test_oracle_remembers_an_intensity_range_per_step_and_forgets_it_on_reset():
+    norm = """  - class_name: mp2p_icp_filters::FilterNormalizeIntensity
+    params:
+      pointcloud_layer: '%s'
+      remember_intensity_range: true
+"""
+    tail = ("localmap_generator:\n" + _map("localmap", 20) + "observations_filter_1st_pass:\n" + _decimate("raw", "a", "0.25") +
+            _decimate("raw", "decimated_for_icp", "0.25") + (norm % "a") + (norm % "decimated_for_icp") +
+            "insert_observation_into_local_map:\n" + _merge("a", "localmap"))
+    o = chain_oracle(inline_pipeline(tail, _ONE_MATCH))
+    xyz, t = _grid_scan()
+    i0 = np.linspace(10.0, 20.0, len(xyz)).astype(np.float32)
+    o.on_lidar(0.0, xyz, t, intensity=i0)
+    a0 = o.layers["a"]["intensity"]
+    assert a0.min() == 0.0 and a0.max() == 1.0
+    # each step remembered the range of ITS layer's values (the second saw raw values, not the first step's output)
+    k_a, k_b = [k for k, st in enumerate(o.steps) if st["kind"] == "normalize"]
+    assert list(o.remembered[k_a]) == [10.0, 20.0] and list(o.remembered[k_b]) == [10.0, 20.0]
+    o.on_lidar(0.1, xyz, t, intensity=(i0 - 10.0) * np.float32(0.5) + np.float32(12.0))  # 12..17 inside the remembered 10..20
+    a1 = o.layers["a"]["intensity"]
+    assert abs(float(a1.min()) - 0.2) < 1e-6 and abs(float(a1.max()) - 0.7) < 1e-6
+    assert list(o.remembered[k_a]) == [10.0, 20.0]
+    o.reset()
+    assert o.remembered == {}
+    o.on_lidar(0.0, xyz, t, intensity=(i0 - 10.0) * np.float32(0.5) + np.float32(12.0))
+    assert o.layers["a"]["intensity"].min() == 0.0 and o.layers["a"]["intensity"].max() == 1.0
+
+
+def test_oracle_sensor_range_reads_the_first_live_layer_and_merges_into_the_named_map_only():
+    """Two layers, 'b_near' (points within 6 m) and 'a_far' (all): the instantaneous sensor range is the bounding-box radius of
+    'a_far', the alphabetically first; only the second map receives a FilterMerge."""
+    tail = ("localmap_generator:\n" + _map("localmap", 20) + _map("localmap_b", 10) + "observations_filter_1st_pass:\n" + """  - class_name: mp2p_icp_filters::FilterByRange
+    params:
+      input_pointcloud_layer: 'raw'
+      output_layer_between: 'b_near'
+      range_min: 0.0
+      range_max: 6.0
+""" + _decimate("raw", "a_far", "0.25") + """  - class_name: mp2p_icp_filters::FilterDeleteLayer
+    params:
+      pointcloud_layer_to_remove: ['raw']
+insert_observation_into_local_map:
+""" + _merge("b_near", "localmap_b"))
+    o = chain_oracle(inline_pipeline(tail, '          - {global: "localmap_b", local: "b_near", weight: 0.5}\n'))
+    xyz, t = _grid_scan()
+    r = o.on_lidar(0.0, xyz, t, intensity=np.ones(len(xyz), np.float32))
+    assert all(l["intensity"] is None for l in o.layers.values())  # (no filter reads it: 'raw' does not carry it)
+    mx = xyz.max(0)
+    radius = float(np.sqrt(np.float32(mx[0] * mx[0] + mx[1] * mx[1]) + mx[2] * mx[2]))
+    assert r["instantaneous_sensor_max_range"] == radius > 20.0
+    near = int(np.sum(np.linalg.norm(xyz.astype(np.float64), axis=1) <= 6.0))
+    assert 0 < near == r["layer_sizes"]["b_near"] < r["layer_sizes"]["a_far"] == len(xyz)
+    assert r["maps"]["localmap"][:2] == (0, 0) and r["maps"]["localmap_b"][0] == near
+    assert r["n_for_map"] == near and r["n_for_icp"] == near + len(xyz)
+    assert o.describe()["pairs"] == [("localmap_b", "b_near", 0.5)]
+
+
 # ------------------------------------------------------------------------------------------------ GPU
 def _ate(recs, drive):
     G = np.stack([trajectory.to44(p) for p in drive["poses"]])
@@ -282,10 +537,7 @@ def drive():
 def _restated_edges_layers(xyz, t, twist, R):
     """The edges chain in numpy / the CPU oracle for one scan: sensor range estimate R, de-skew twist."""
     from oracle import oracle_c
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_curv", os.path.join(ROOT, "tests", "test_curvature.py"))
-    cm = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(cm)
+    from oracle import filters_np as cm
     d = oracle_c.deskew(xyz, t, np.asarray(twist, np.float64))
     rmin, rmax = max(1.0, 0.05 * R), 1.2 * R
     k1 = oracle_c.filter_by_range(d, rmin, rmax)
@@ -354,3 +606,127 @@ def test_edges_chain_takes_the_fused_layers_route(host, drive):
     runs = sum(1 for r in recs if r["icp_run"])
     assert runs == len(recs) - 1 and prof["icp.align_calls"] >= runs
     assert prof["icp.fused_align_calls"] == prof["icp.align_calls"]
+
+
+# ------------------------------------------------------------------------------------------------ GPU: driver against chain oracle
+def _side_by_side(host, text, drive, n=None, first=0, intensity=None, setup=None):
+    lo, o = new_driver(host, text, intensity is not None), chain_oracle(text)
+    if setup is not None:
+        setup(lo)
+    sl = slice(first, None if n is None else first + n)
+    recs, apart = drive_against_oracle(lo, o, drive["scans"][sl], drive["stamps"][sl],
+                                       None if intensity is None else intensity[sl], first=first)
+    print("%d scans compared, %d scans set apart" % (len(recs), len(apart)))
+    assert apart == [], apart  # the cap for the committed drives and chains: zero
+    assert len(recs) == len(drive["scans"][sl])
+    return lo, o, recs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("chain", ["edges", "dual-map", "near-far"])
+def test_driver_matches_chain_oracle_every_scan(host, drive, chain):
+    """The C++ driver's general plan against oracle/chain_oracle.py over the whole drive, scan by scan (compare_scan): decisions,
+    layer sizes and contents, every map's counts, scalars, twist, pose; every map's content after the last scan."""
+    lo, o, recs = _side_by_side(host, inline_pipeline(*CHAINS[chain]), drive)
+    assert sum(a["twist_corrections"] for a, _ in recs) >= 1
+    assert sum(a["map_updated"] for a, _ in recs) >= 10
+    assert all(v[0] > 0 for v in lo.localMapStats().values())
+    if chain == "edges":  # an aligned layer that is EMPTY on some scans and not on others
+        sizes = [a["layer_sizes"]["decimated_for_icp_large_curvature"] for a, _ in recs]
+        assert 0 in sizes[2:] and max(sizes) > 0, sizes
+
+
+@pytest.mark.gpu
+def test_second_pass_that_filters_after_its_deskew(host, drive):
+    """The twist hook re-runs a 2nd pass that de-skews and THEN filters, from the layers alive after the 1st pass; the record's
+    layer_sizes / n_for_icp / n_for_map describe the layers of the last re-run, which were aligned in the end and merged."""
+    lo, o, recs = _side_by_side(host, inline_pipeline(PASS2_TAIL, _ONE_MATCH), drive, n=6)
+    assert sum(a["twist_corrections"] for a, _ in recs) > 0
+    for a, _ in recs:
+        assert a["n_for_map"] == a["layer_sizes"]["decimated_for_map"] and a["n_for_icp"] == sum(a["layer_sizes"].values())
+
+
+@pytest.mark.gpu
+def test_scans_without_time_stamps_are_copied_by_the_deskew(host, drive):
+    """silently_ignore_no_timestamps: the de-skew of a scan without time stamps is a copy, also when the twist is not zero."""
+    bare = dict(drive, scans=[(xyz, None) for xyz, _ in drive["scans"]])
+    lo, o, recs = _side_by_side(host, inline_pipeline(*CHAINS["edges"]), bare, n=5)
+    assert any(np.abs(a["twist"]).max() > 0.1 for a, _ in recs)
+    assert all(d == 0 for _, b in recs for d in b["deskew_ulps"].values())
+
+
+@pytest.mark.gpu
+def test_near_far_with_earliest_is_zero(host, drive):
+    text = inline_pipeline(*CHAINS["near-far"])
+    assert text.count("TimestampAdjustMethod::MiddleIsZero") == 1
+    text = text.replace("TimestampAdjustMethod::MiddleIsZero", "TimestampAdjustMethod::EarliestIsZero")
+    lo, o, recs = _side_by_side(host, text, drive, n=6)
+    assert int(lo.describePipeline()["timestamp_method"]) == 2
+    t = lo.downloadLayer("raw")["t"]
+    assert t.min() == 0.0 and t.max() > 0.05
+
+
+@pytest.mark.gpu
+def test_all_aligned_layers_empty_takes_the_restart_path(host, drive):
+    """No pairings at all: ICP ends with NoPairings, the result is bad, the motion model is reset and -- the trajectory holding
+    one pose -- the maps are cleared and the next scan starts again; the same decisions as the oracle, scan by scan."""
+    lo, o, recs = _side_by_side(host, inline_pipeline(NOPAIRS_TAIL, EDGES_MATCHES), drive, n=6)
+    assert [a["restarted"] for a, _ in recs] == [False, True] * 3
+    assert [a["first_scan"] for a, _ in recs] == [True, False] * 3
+    assert all(a["termination"] == 1 and not a["icp_good"] for a, _ in recs[1::2])
+
+
+@pytest.mark.gpu
+def test_reset_and_a_second_drive_on_the_same_object(host, drive):
+    text = inline_pipeline(*CHAINS["dual-map"])
+    lo, o, _ = _side_by_side(host, text, drive, n=5)
+    lo.reset()
+    o.reset()
+    assert lo.records() == [] and all(v == (0, 0, 0.0) for v in lo.localMapStats().values())
+    sl = slice(6, 11)
+    recs, apart = drive_against_oracle(lo, o, drive["scans"][sl], drive["stamps"][sl], first=6)
+    assert apart == [] and len(recs) == 5
+    fresh = new_driver(host, text)
+    for (xyz, t), st in zip(drive["scans"][sl], drive["stamps"][sl]):
+        fresh.onLidar(float(st), xyz, t)
+    assert fresh.records() == lo.records()
+    assert fresh.localMapStats() == lo.localMapStats()  # (maps recreated with the new drive's sensor range)
+
+
+@pytest.mark.gpu
+def test_dual_map_chain_with_the_motion_model_prior(host, drive, monkeypatch):
+    """motion_model_prior: the prior path of mh_icp_align_layers on every scan with a motion model."""
+    monkeypatch.setenv("MOLA_HIP_MOTION_MODEL_PRIOR", "true")
+    monkeypatch.setenv("MOLA_INITIAL_VX", "1.5")
+    lo, o, recs = _side_by_side(host, inline_pipeline(*CHAINS["dual-map"]), drive, n=8)
+    assert o.motion_model_prior and recs[1][0]["had_motion_model"]
+    monkeypatch.delenv("MOLA_HIP_MOTION_MODEL_PRIOR")
+    plain = new_driver(host, inline_pipeline(*CHAINS["dual-map"]))
+    for (xyz, t), st in list(zip(drive["scans"], drive["stamps"]))[:8]:
+        plain.onLidar(float(st), xyz, t)
+    assert [r["pose"] for r in plain.records()] != [a["pose"] for a, _ in recs]  # (the prior is not a no-op)
+
+
+@pytest.mark.gpu
+def test_edges_chain_with_closest_to_average_in_one_decimation(host, drive):
+    parts = EDGES_TAIL.split("DecimateMethod::FirstPoint")  # the third decimation: smaller_curvature -> its map layer
+    assert len(parts) == 5
+    tail = "DecimateMethod::FirstPoint".join(parts[:3]) + "DecimateMethod::ClosestToAverage" + "DecimateMethod::FirstPoint".join(parts[3:])
+    lo, o, recs = _side_by_side(host, inline_pipeline(tail, EDGES_MATCHES), drive, n=8)
+    first = new_driver(host, inline_pipeline(*CHAINS["edges"]))
+    for (xyz, t), st in list(zip(drive["scans"], drive["stamps"]))[:8]:
+        first.onLidar(float(st), xyz, t)
+    assert [r["pose"] for r in first.records()] != [a["pose"] for a, _ in recs]  # (other survivors than FirstPoint's)
+
+
+@pytest.mark.gpu
+def test_far_voxel_removal_is_each_maps_own(host, drive):
+    """The second map forgets voxels beyond max(10 m, 0.2 x range) of the vehicle, the first beyond 100 m: with the first map's
+    distance the second would keep everything (no point of this drive lies beyond 100 m)."""
+    tail = DUAL_TAIL.replace("max(100.0, 1.10*", "max(10.0, 0.20*")
+    assert tail != DUAL_TAIL
+    lo, o, recs = _side_by_side(host, inline_pipeline(tail, DUAL_MATCHES), drive, n=6)
+    keep_all = chain_oracle(inline_pipeline(*CHAINS["dual-map"]))
+    for (xyz, t), st in list(zip(drive["scans"], drive["stamps"]))[:6]:
+        keep_all.on_lidar(float(st), xyz, t)
+    assert lo.localMapStats()["localmap_far"][0] < keep_all.records[-1]["maps"]["localmap_far"][0]

@@ -26,7 +26,7 @@ def _module(name):
 
 
 chains = _module("test_odometry_chains")
-intensity = _module("test_intensity")
+from oracle import filters_np as intensity  # noqa: E402  (the float32 restatements of the two intensity filters)
 _E = "ESTIMATED_SENSOR_MAX_RANGE"
 
 
@@ -310,3 +310,74 @@ def test_cli_intensity_field_matches_the_pybind_run(host, drive, tmp_path):
     lo.saveTrajectoryTUM(str(mine))
     assert len(lo.records()) == len(drive["scans"])
     assert out.read_text() == mine.read_text()
+
+
+# ------------------------------------------------------------------------------------------------ GPU: driver against chain oracle
+@pytest.mark.gpu
+def test_intensity_driver_matches_chain_oracle_every_scan(host, drive):
+    """The intensity chain against oracle/chain_oracle.py over the whole drive, scan by scan: decisions, every layer's size,
+    points, source indices and (normalised) intensities, both maps' counts and contents, scalars, twist and pose."""
+    lo, o, recs = chains._side_by_side(host, pipeline(), drive, intensity=drive["intensity"])
+    bright = [a["layer_sizes"]["decimated_for_map_bright"] for a, _ in recs]
+    assert 0 in bright and max(bright) > 0, bright  # (a merged layer that is empty on some scans)
+    assert lo.localMapStats()["localmap_bright"][0] > 0
+
+
+# two FilterNormalizeIntensity steps on two different layers, each remembering ITS range
+def two_ranges_tail():
+    norm = """  - class_name: mp2p_icp_filters::FilterNormalizeIntensity
+    params:
+      pointcloud_layer: '%s'
+      remember_intensity_range: true
+"""
+    split = """  - class_name: mp2p_icp_filters::FilterByIntensity
+    params:
+      input_pointcloud_layer: '%s'
+      output_layer_high_intensity: '%s'
+      high_threshold: 0.8
+      low_threshold: 0.1
+"""
+    return ("localmap_generator:\n" + _map("localmap") + _map("localmap_bright") + """observations_filter_1st_pass:
+  - class_name: mp2p_icp_filters::FilterByRange
+    params:
+      input_pointcloud_layer: 'raw'
+      output_layer_between: 'near'
+      range_min: 1.0
+      range_max: 12.0
+""" + chains._decimate("raw", "decimated_for_map", "0.5") + (norm % "near") + (norm % "decimated_for_map") +
+            (split % ("near", "near_bright")) + (split % ("decimated_for_map", "map_bright")) +
+            chains._decimate("decimated_for_map", "decimated_for_icp", "1.5") + """  - class_name: mp2p_icp_filters::FilterDeleteLayer
+    params:
+      pointcloud_layer_to_remove: ['raw']
+insert_observation_into_local_map:
+""" + chains._merge("decimated_for_map", "localmap") + chains._merge("near_bright", "localmap_bright"))
+
+
+def test_oracle_and_driver_read_the_same_intensity_plans(host):
+    for text in (pipeline(), pipeline("false"), chains.inline_pipeline(two_ranges_tail(), MATCHES)):
+        chains._assert_same_plan(_load(host, text), chains.chain_oracle(text), [("localmap", "decimated_for_icp", 1.0)])
+
+
+def test_chain_oracle_tracks_the_drive_on_the_intensity_chain():
+    from oracle.chain_oracle import ChainOdometryOracle
+    d = synth.make_drive(14)
+    o = chains._oracle_run(pipeline(), d, intensity=synth.drive_intensities(d))
+    assert all(r["icp_run"] and r["icp_good"] for r in o.records[2:]) and chains._ate(o.records, d) < 0.2
+    assert [k for k, r in enumerate(o.records) if ChainOdometryOracle.set_apart(r)] == []
+
+
+@pytest.mark.gpu
+def test_two_normalise_steps_remember_their_own_ranges_and_reset_forgets_them(host, drive):
+    text = chains.inline_pipeline(two_ranges_tail(), MATCHES)
+    lo, o, recs = chains._side_by_side(host, text, drive, n=6, intensity=drive["intensity"])
+    k_near, k_all = [k for k, st in enumerate(o.steps) if st["kind"] == "normalize"]
+    assert not np.array_equal(o.remembered[k_near], o.remembered[k_all])  # (one shared range would show)
+    lo.reset()
+    o.reset()
+    sl = slice(7, 12)
+    again, apart = chains.drive_against_oracle(lo, o, drive["scans"][sl], drive["stamps"][sl], drive["intensity"][sl], first=7)
+    assert apart == [] and len(again) == 5
+    fresh = chains.new_driver(host, text, intensity=True)
+    for k in range(7, 12):
+        chains._feed(fresh, drive["stamps"][k], *drive["scans"][k], drive["intensity"][k])
+    assert fresh.records() == lo.records() and fresh.localMapStats() == lo.localMapStats()
