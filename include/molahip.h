@@ -625,8 +625,8 @@ MH_API mh_status mh_icp_align_batch(size_t n_jobs, const mh_map* const* maps, co
  *  - MH_ERR_INVALID_ARGUMENT: n_pairs 0 or above MH_MAX_LAYER_PAIRS, a null map / scan / threshold, maps and scans on more than
  *    one context, pt2pl_threshold != NULL.  MH_ERR_UNSUPPORTED: matched_points == MH_MATCHED_POINTS_SKIP with a scan shared by
  *    two pairs, profile != 0, a map of 2^30 or more records.
- * Per ICP iteration 1 + 2 * gn.max_inner_iterations launches, whatever the number of pairs.  No one-launch loops, streaming control or
- * lock-step batches on this path. */
+ * Per ICP iteration 1 + 2 * gn.max_inner_iterations launches, whatever the number of pairs.  No one-launch loops or streaming
+ * control on this path; several such alignments advance in lock step through mh_icp_align_layers_batch (below). */
 #define MH_MAX_LAYER_PAIRS 8
 typedef struct {
   const mh_map* map;            /* global layer */
@@ -640,6 +640,34 @@ MH_API mh_status mh_icp_align_layers(size_t n_pairs, const mh_layer_pair* pairs,
                                      const double T_guess[12], const mh_prior* prior, mh_icp_result* result,
                                      mh_icp_iter* trace, const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
                                      uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
+
+/* Many multi-layer alignments from one host thread, one context per job: mh_icp_align_batch for mh_icp_align_layers.  Job i has
+ * all its maps and scans on ONE context, distinct jobs have distinct contexts of the same device, and each job's pairs obey the
+ * contract above.  Job i uses params[i] when params_per_job != 0 (else the one *params), T_guesses + 12*i and priors[i] (array or
+ * entries may be NULL).  results[i] is bitwise what mh_icp_align_layers returns for job i alone -- T, cov, quality, n_iterations,
+ * termination_reason, n_final_pairs, potential_pairings -- and final_pair_counts[i * MH_MAX_LAYER_PAIRS + p] (nullable) is that
+ * call's final_pair_counts[p]; n_host_polls and n_enqueued_iterations describe the batch's loop control and may differ.  No trace
+ * and no final pairings: a caller that wants them calls mh_icp_align_layers.
+ *  - Jobs with equal gn.max_inner_iterations and compute_covariance form a lock-step group: every kernel of an iteration is ONE
+ *    launch over all pairs of all its jobs (per ICP iteration 1 + 2 * gn.max_inner_iterations launches for the whole group); a job
+ *    that has terminated leaves every later launch at once, so the jobs of a group end at different iterations.  Chunked loop
+ *    control on the first job's stream (poll_every of the group's first job; 0 = the longest of the jobs' own estimates), launched
+ *    directly, never from a captured graph.  A job alone in its group, trivial jobs (max_iterations == 0, no points) and every
+ *    job under MH_NO_LOCKSTEP=1 run through mh_icp_align_layers, one after the other.
+ *  - Work still queued on the jobs' own streams is ordered before the batch.
+ *  - Everything is validated before any device work.  MH_ERR_INVALID_ARGUMENT: n_jobs 0 or above MH_MAX_LAYER_BATCH_JOBS, a job
+ *    that mh_icp_align_layers rejects with that code, two jobs on one context, jobs on different devices.  MH_ERR_UNSUPPORTED: a
+ *    job that mh_icp_align_layers rejects with that code.  After an error every context stays usable. */
+#define MH_MAX_LAYER_BATCH_JOBS 64
+typedef struct {
+  size_t n_pairs;              /* 1 .. MH_MAX_LAYER_PAIRS */
+  const mh_layer_pair* pairs;
+} mh_layer_job;
+
+MH_API mh_status mh_icp_align_layers_batch(size_t n_jobs, const mh_layer_job* jobs, const mh_icp_params* params,
+                                           int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
+                                           mh_icp_result* results,
+                                           uint64_t* final_pair_counts /* n_jobs * MH_MAX_LAYER_PAIRS entries or NULL */);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,15 @@ class LayerPair(C.Structure):
                 ("weight", C.c_double)]
 
 
+class LayerJob(C.Structure):
+    """mh_layer_job: the layer pairs of one job of mh_icp_align_layers_batch."""
+    _fields_ = [("n_pairs", C.c_size_t), ("pairs", C.POINTER(LayerPair))]
+
+
+MAX_LAYER_PAIRS = 8        # MH_MAX_LAYER_PAIRS
+MAX_LAYER_BATCH_JOBS = 64  # MH_MAX_LAYER_BATCH_JOBS
+
+
 class PreprocessParams(C.Structure):
     _fields_ = [("decim_map_resolution", C.c_float), ("decim_icp_resolution", C.c_float),
                 ("min_points_to_filter", C.c_uint32), ("index_mode", C.c_int32), ("range_min", C.c_float),
@@ -219,6 +228,8 @@ _SIGNATURES = {
     "mh_icp_align_layers": (C.c_int32, [C.c_size_t, C.POINTER(LayerPair), C.POINTER(ICPParamsC), _DP, C.POINTER(Prior),
                                         C.POINTER(ICPResult), C.POINTER(ICPIter), C.POINTER(PairsOut),
                                         C.POINTER(C.c_uint64), C.c_int32]),
+    "mh_icp_align_layers_batch": (C.c_int32, [C.c_size_t, C.POINTER(LayerJob), C.POINTER(ICPParamsC), C.c_int32, _DP,
+                                              C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
 }
 
 _lib = None
@@ -819,32 +830,39 @@ def icp_align(m: Map, s: Scan, T_guess, p: ICPParams, prior=None, want_trace=Tru
     return out
 
 
-def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, want_pairs=False):
-    """mh_icp_align_layers: one alignment over several (map, scan) point-layer pairs with one Gauss-Newton solve.
-    `pairs`: a sequence of dicts {map, scan, threshold, threshold_angular_deg=0, weight=1} or tuples in that order; a
-    threshold is a scalar or max_iterations values.  p.threshold, p.threshold_angular_deg and p.gn.weight_pt2pt are not used.
-    Returns icp_align's dict plus pair_counts (final pairings per pair) and, with want_pairs, pairs (one dict per pair)."""
+def _layer_pairs(pairs, max_iterations):
+    """A LayerPair array of `pairs` (dicts {map, scan, threshold, threshold_angular_deg=0, weight=1} or tuples in that order),
+    the dicts, and the threshold arrays the array points into."""
     norm = []
     for e in pairs:
         if not isinstance(e, dict):
             e = dict(zip(("map", "scan", "threshold", "threshold_angular_deg", "weight"), e))
         norm.append(e)
-    n_pairs = len(norm)
-    p_c = replace(p, threshold=p.threshold if p.threshold is not None else 0.0)
-    cp, keep = p_c.c(T_guess)
-    T0 = _T12(T_guess)
-    arr = (LayerPair * max(1, n_pairs))()
+    arr = (LayerPair * max(1, len(norm)))()
     thr_keep = []
     for i, e in enumerate(norm):
         m, s = e.get("map"), e.get("scan")
         arr[i].map = m._h if m is not None else None
         arr[i].scan = s._h if s is not None else None
         if e.get("threshold") is not None:
-            t = np.ascontiguousarray(np.broadcast_to(np.asarray(e["threshold"], np.float64), (max(1, p.max_iterations),)))
+            t = np.ascontiguousarray(np.broadcast_to(np.asarray(e["threshold"], np.float64), (max(1, max_iterations),)))
             thr_keep.append(t)
             arr[i].threshold = t.ctypes.data_as(_DP)
         arr[i].threshold_angular_deg = float(e.get("threshold_angular_deg", 0.0) or 0.0)
         arr[i].weight = float(e.get("weight", 1.0) if e.get("weight") is not None else 1.0)
+    return arr, norm, thr_keep
+
+
+def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, want_pairs=False):
+    """mh_icp_align_layers: one alignment over several (map, scan) point-layer pairs with one Gauss-Newton solve.
+    `pairs`: a sequence of dicts {map, scan, threshold, threshold_angular_deg=0, weight=1} or tuples in that order; a
+    threshold is a scalar or max_iterations values.  p.threshold, p.threshold_angular_deg and p.gn.weight_pt2pt are not used.
+    Returns icp_align's dict plus pair_counts (final pairings per pair) and, with want_pairs, pairs (one dict per pair)."""
+    p_c = replace(p, threshold=p.threshold if p.threshold is not None else 0.0)
+    cp, keep = p_c.c(T_guess)
+    T0 = _T12(T_guess)
+    arr, norm, thr_keep = _layer_pairs(pairs, p.max_iterations)
+    n_pairs = len(norm)
     res = ICPResult()
     trace = (ICPIter * max(1, p.max_iterations))() if want_trace else None
     pr = _mk_prior(prior)
@@ -871,6 +889,48 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
             k = out["pair_counts"][i]
             out["pairs"].append(dict(local_idx=li[:k].copy(), global_idx=gi[:k].copy(),
                                      global_xyz=np.stack([gx[:k], gy[:k], gz[:k]], 1), d2=d2[:k].copy()))
+    return out
+
+
+def icp_align_layers_batch(jobs, T_guesses, params, priors=None):
+    """mh_icp_align_layers_batch: one multi-layer alignment per job, jobs of the same loop shape in lock step.  `jobs`: a
+    sequence of icp_align_layers' `pairs` arguments, every job on a Context of its own; `params`: one ICPParams or one per job.
+    Returns a list of icp_align_layers' dicts (no pairs, no trace); every entry has the bits of that job's single call."""
+    n = len(jobs)
+    T = np.ascontiguousarray(np.stack([_T12(t) for t in T_guesses]).reshape(len(T_guesses) * 12)) if n else np.zeros(12)
+    per_job = isinstance(params, (list, tuple))
+    plist = list(params) if per_job else [params] * max(1, n)
+    assert not per_job or len(plist) == n
+    plist = [replace(q, threshold=q.threshold if q.threshold is not None else 0.0) for q in plist]
+    if per_job:
+        made = [q.c(T[12 * i:12 * i + 12]) for i, q in enumerate(plist)]
+        cp = (ICPParamsC * max(1, n))(*[m[0] for m in made])
+        keep, cp_ref = [m[1] for m in made], cp
+    else:
+        cp, keep = plist[0].c(T[:12])
+        cp_ref = C.byref(cp)
+    jarr = (LayerJob * max(1, n))()
+    keep_pairs = []
+    for i, pairs in enumerate(jobs):
+        arr, norm, thr_keep = _layer_pairs(pairs, plist[i].max_iterations)
+        keep_pairs.append((arr, norm, thr_keep))
+        jarr[i].n_pairs = len(norm)
+        jarr[i].pairs = arr
+    pr_arr, keep_pr = None, []
+    if priors is not None:
+        pr_arr = (C.POINTER(Prior) * max(1, n))()
+        for i, pr in enumerate(priors):
+            if pr is not None:
+                keep_pr.append(_mk_prior(pr))
+                pr_arr[i] = C.pointer(keep_pr[-1])
+    res = (ICPResult * max(1, n))()
+    counts = (C.c_uint64 * (max(1, n) * MAX_LAYER_PAIRS))()
+    _chk(lib().mh_icp_align_layers_batch(n, jarr, cp_ref, 1 if per_job else 0, T.ctypes.data_as(_DP), pr_arr, res, counts))
+    out = []
+    for i in range(n):
+        d = _result_dict(res[i])
+        d["pair_counts"] = [int(counts[i * MAX_LAYER_PAIRS + k]) for k in range(len(keep_pairs[i][1]))]
+        out.append(d)
     return out
 
 

@@ -1109,29 +1109,13 @@ size_t mh_pairs_block_bytes(size_t n_scan_points) {
 mh_status mh_icp_align_layers(size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params, const double T_guess[12],
                               const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
                               uint64_t* final_pair_counts, int32_t pairs_mem) {
-  MH_REQUIRE(n_pairs >= 1 && n_pairs <= MH_MAX_LAYER_PAIRS, "n_pairs must be 1 .. MH_MAX_LAYER_PAIRS");
-  MH_REQUIRE(pairs && params && T_guess && result, "null argument");
-  for (size_t i = 0; i < n_pairs; i++) {
-    MH_REQUIRE(pairs[i].map && pairs[i].scan && pairs[i].threshold, "null map, scan or threshold in a layer pair");
-    MH_REQUIRE(pairs[i].map->ctx == pairs[0].scan->ctx && pairs[i].scan->ctx == pairs[0].scan->ctx,
-               "the maps and scans of a multi-layer alignment live on different contexts");
-  }
-  MH_REQUIRE(params->pt2pl_threshold == nullptr, "Matcher_Point2Plane is not supported with layer pairs");
-  MH_REQUIRE(pose_ok(T_guess), "non-finite initial guess");
-  MH_REQUIRE(params->max_iterations == 0 || params->kernel_param, "kernel_param array is required");
-  MH_REQUIRE(params->gn.max_inner_iterations >= 1, "gn.max_inner_iterations must be >= 1");
-  MH_REQUIRE(params->gn.robust_kernel <= MH_KERNEL_GM_C2, "unknown robust kernel");
-  MH_REQUIRE(params->max_iterations < (1u << 20), "max_iterations too large");
-  MH_REQUIRE(params->matched_points <= MH_MATCHED_POINTS_SKIP, "unknown matched_points mode");
+  MH_TRY(check_layers_args(n_pairs, pairs, params, T_guess, result));
   MH_REQUIRE(!final_pairs || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
-  if (params->profile != 0) return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: profile is not supported");
-  if (params->matched_points == MH_MATCHED_POINTS_SKIP)
-    for (size_t i = 0; i < n_pairs; i++)
-      for (size_t j = i + 1; j < n_pairs; j++)
-        if (pairs[i].scan == pairs[j].scan)
-          return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: MH_MATCHED_POINTS_SKIP with a scan shared by two pairs");
+  MH_TRY(check_layers_supported(n_pairs, pairs, params));
   return align_layers(read_switches(), (uint32_t)n_pairs, pairs, params, T_guess, prior, result, trace, final_pairs,
                       final_pair_counts, pairs_mem);
 }
+
+#include "mh_icp_layers_batch.inl"  // mh_icp_align_layers_batch
 
 }  // extern "C"

@@ -37,15 +37,25 @@ void fill_batch_desc(const AlignJob& j, BatchJob& d) {
 
 // Work still queued on a job's own stream (asynchronous uploads, filters, de-skew, an earlier alignment) must be
 // complete before `lead`'s stream reads that job's scan / state: an event per job, waited for by the leader's stream.
+mh_status order_after_stream_of(mh_ctx* lead, mh_ctx* ctx) {
+  if (ctx == lead || ctx->stream == lead->stream) return MH_OK;
+  if (hipStreamQuery(ctx->stream) == hipSuccess) return MH_OK;  // nothing pending there
+  MH_HIP(hipEventRecord(ctx->ev_ready, ctx->stream));
+  MH_HIP(hipStreamWaitEvent(lead->stream, ctx->ev_ready, 0));
+  return MH_OK;
+}
 mh_status order_after_job_streams(mh_ctx* lead, const std::vector<AlignJob*>& jobs) {
   for (AlignJob* j : jobs) {
     MH_TRY(map_ready_on(j->map, lead->stream));  // a key-frame update of this job's map still running on its side stream
-    if (j->ctx == lead || j->ctx->stream == lead->stream) continue;
-    if (hipStreamQuery(j->ctx->stream) == hipSuccess) continue;  // nothing pending there
-    MH_HIP(hipEventRecord(j->ctx->ev_ready, j->ctx->stream));
-    MH_HIP(hipStreamWaitEvent(lead->stream, j->ctx->ev_ready, 0));
+    MH_TRY(order_after_stream_of(lead, j->ctx));
   }
   (void)hipGetLastError();  // hipStreamQuery's hipErrorNotReady is not an error
+  return MH_OK;
+}
+// (multi-layer jobs: LayersJob::start has made every map ready on its job's own stream, which the leader's then waits for)
+mh_status order_after_layers_job_streams(mh_ctx* lead, const std::vector<LayersJob*>& jobs) {
+  for (LayersJob* j : jobs) MH_TRY(order_after_stream_of(lead, j->ctx));
+  (void)hipGetLastError();
   return MH_OK;
 }
 

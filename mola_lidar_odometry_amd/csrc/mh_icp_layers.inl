@@ -14,20 +14,44 @@ struct LayersLayout {
   uint32_t tot_match = 0, tot_acc = 0, tot_cov = 0;
 };
 
-mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pairs, const mh_icp_params* p, const double T0[12],
-                       const mh_prior* prior, mh_icp_result* res, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
-                       uint64_t* final_pair_counts, int32_t pairs_mem) {
-  mh_ctx* const ctx = pairs[0].scan->ctx;
+// One multi-layer alignment from its arguments to its uploaded [state | parameters | table | schedules]: what a single call and a
+// job of mh_icp_align_layers_batch share.  Everything start() queues goes to the job's own context stream.
+struct LayersJob {
+  mh_ctx* ctx = nullptr;
+  uint32_t np = 0;
+  const mh_layer_pair* pairs = nullptr;
+  const mh_icp_params* p = nullptr;
+  mh_icp_result* res = nullptr;
+  size_t total_n = 0;
+  bool trivial = false;       // nothing to run: the result is complete after start()
+  LayersLayout L;
+  const LayerTable* tab = nullptr;  // the pinned mirror of the device table (the pairing segments: count_pairs)
+  uint32_t chunk = 10;        // iterations of the first chunk
+
+  mh_status start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
+                  const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts);
+  void finish(uint32_t polls, uint32_t enqueued);
+  mh_status count_pairs(const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem);
+};
+
+mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
+                           const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts) {
+  np = np_;
+  pairs = pairs_;
+  p = p_;
+  res = res_;
+  ctx = pairs[0].scan->ctx;
   memset(res, 0, sizeof(*res));
   for (int i = 0; i < 12; i++) res->T[i] = T0[i];
   for (int i = 0; i < 6; i++) res->cov[i * 7] = 1e6;
   if (final_pair_counts)
     for (uint32_t i = 0; i < np; i++) final_pair_counts[i] = 0;
-  size_t total_n = 0;
+  total_n = 0;
   for (uint32_t i = 0; i < np; i++) total_n += pairs[i].scan->n;
   res->potential_pairings = total_n;  // every pair adds its layer size
   if (p->max_iterations == 0 || total_n == 0) {
     res->termination_reason = p->max_iterations == 0 ? MH_TERM_MAX_ITERATIONS : MH_TERM_NO_PAIRINGS;
+    trivial = true;
     return MH_OK;
   }
   MH_TRY(set_device(ctx));
@@ -47,8 +71,7 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
     if (!m->view(sw).pts_q) return fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (mh_icp_align_layers needs it)");
   }
   // layout: a pairing segment per pair (a scan shared by two pairs is paired again for each), flattened grids
-  LayersLayout L;
-  LayerTable* tab = nullptr;
+  L = LayersLayout();
   const size_t mi = p->max_iterations;
   const size_t tab_bytes = (sizeof(LayerTable) + 255) / 256 * 256;
   const size_t sched_bytes = (1 + (size_t)np) * mi * sizeof(double);  // kernel_param | threshold of pair 0 | ... | pair np-1
@@ -60,7 +83,8 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
     ctx->h_layers_cap = tab_bytes + sched_bytes;
   }
   MH_TRY(ctx->layers_tab.reserve(tab_bytes + sched_bytes));
-  tab = static_cast<LayerTable*>(ctx->h_layers);
+  LayerTable* const tab = static_cast<LayerTable*>(ctx->h_layers);
+  this->tab = tab;
   memset(tab, 0, sizeof(LayerTable));
   tab->n_pairs = np;
   for (uint32_t i = 0; i < np; i++) {
@@ -142,16 +166,61 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
   ctx->h_state->cur_ang2 = mk.ang2;
   ctx->h_state->cur_kparam = p->kernel_param[0];
   MH_TRY(upload_state_and_params(ctx, mk, sk));
+  const uint32_t expect = p->expected_iterations ? p->expected_iterations : ctx->layers_predicted;
+  chunk = p->poll_every ? p->poll_every : (expect ? (expect + kChunkMargin > 64 ? 64u : expect + kChunkMargin) : 10u);
+  return MH_OK;
+}
 
+// the result from the state block read back into ctx->h_state once the loop has terminated
+void LayersJob::finish(uint32_t polls, uint32_t enqueued) {
+  const IcpDeviceState* h = ctx->h_state;
+  if (p->poll_every == 0) ctx->layers_predicted = h->n_iterations + (h->term_reason == MH_TERM_MAX_ITERATIONS ? 0u : 1u);
+  res->n_host_polls = polls;
+  res->n_enqueued_iterations = enqueued;
+  for (int i = 0; i < 12; i++) res->T[i] = h->T[i];
+  if (p->compute_covariance)
+    for (int i = 0; i < 36; i++) res->cov[i] = h->cov[i];
+  res->n_iterations = h->n_iterations;
+  res->termination_reason = h->term_reason;
+  res->n_final_pairs = h->n_pairs;
+  res->quality = h->n_pairs ? (double)h->n_pairs / (double)total_n : 0.0;  // PairedRatio over all pairs
+  if (h->term_reason == MH_TERM_NO_PAIRINGS)
+    for (int i = 0; i < 36; i++) res->cov[i] = (i % 7 == 0) ? 1e6 : 0.0;
+}
+
+// every pair's final pairings compacted out of its segment (into final_pairs[i] when given) and counted
+mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
+  if (!(final_pairs || final_pair_counts) || !res->n_final_pairs) return MH_OK;
+  const mh_pairs_out none{};
+  uint64_t sum = 0;
+  for (uint32_t i = 0; i < np; i++) {
+    uint64_t c = 0;
+    if (pairs[i].scan->n)
+      MH_TRY(compact_pairs_of(ctx, tab->d[i].pair_gidx, tab->d[i].pair_q, pairs[i].scan->n, final_pairs ? &final_pairs[i] : &none,
+                              final_pairs ? pairs_mem : MH_MEM_DEVICE, &c));
+    if (final_pair_counts) final_pair_counts[i] = c;
+    sum += c;
+  }
+  if (sum != res->n_final_pairs)
+    return fail(MH_ERR_INTERNAL, "pair compaction count mismatch: %llu pairings in the buffers, %u in the last accumulation",
+                (unsigned long long)sum, res->n_final_pairs);
+  return MH_OK;
+}
+
+mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pairs, const mh_icp_params* p, const double T0[12],
+                       const mh_prior* prior, mh_icp_result* res, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
+                       uint64_t* final_pair_counts, int32_t pairs_mem) {
+  LayersJob job;
+  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts));
+  if (job.trivial) return MH_OK;
+  mh_ctx* const ctx = job.ctx;
+  const LayersLayout& L = job.L;
+  hipStream_t s = ctx->stream;
   const LayerTable* const dtab = ctx->layers_tab.as<LayerTable>();
   double* const part = ctx->partials.as<double>();
   const SolveK* const dsk = &ctx->d_params->sk;
   const uint32_t inner = p->gn.max_inner_iterations;
-  uint32_t chunk;
-  {
-    const uint32_t expect = p->expected_iterations ? p->expected_iterations : ctx->layers_predicted;
-    chunk = p->poll_every ? p->poll_every : (expect ? (expect + kChunkMargin > 64 ? 64u : expect + kChunkMargin) : 10u);
-  }
+  uint32_t chunk = job.chunk;
   uint32_t enqueued = 0, polls = 0;
   for (;;) {
     const uint32_t m = (p->max_iterations - enqueued) < chunk ? (p->max_iterations - enqueued) : chunk;
@@ -225,39 +294,42 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
     if (enqueued >= p->max_iterations) return fail(MH_ERR_INTERNAL, "device ICP loop did not terminate after max_iterations");
     if (p->poll_every == 0) chunk = kChunkNext;
   }
-  const IcpDeviceState* h = ctx->h_state;
-  if (p->poll_every == 0) ctx->layers_predicted = h->n_iterations + (h->term_reason == MH_TERM_MAX_ITERATIONS ? 0u : 1u);
-  res->n_host_polls = polls;
-  res->n_enqueued_iterations = enqueued;
-  for (int i = 0; i < 12; i++) res->T[i] = h->T[i];
-  if (p->compute_covariance)
-    for (int i = 0; i < 36; i++) res->cov[i] = h->cov[i];
-  res->n_iterations = h->n_iterations;
-  res->termination_reason = h->term_reason;
-  res->n_final_pairs = h->n_pairs;
-  res->quality = h->n_pairs ? (double)h->n_pairs / (double)total_n : 0.0;  // PairedRatio over all pairs
-  if (h->term_reason == MH_TERM_NO_PAIRINGS)
-    for (int i = 0; i < 36; i++) res->cov[i] = (i % 7 == 0) ? 1e6 : 0.0;
+  job.finish(polls, enqueued);
   if (trace) {
+    const IcpDeviceState* h = ctx->h_state;
     const uint32_t cnt = h->n_iterations < p->max_iterations ? h->n_iterations + 1 : p->max_iterations;
     memset(trace, 0, sizeof(mh_icp_iter) * p->max_iterations);
     const uint32_t valid = (h->term_reason == MH_TERM_NO_PAIRINGS || h->term_reason == MH_TERM_SOLVER_ERROR) ? h->n_iterations : cnt;
     if (valid) MH_HIP(hipMemcpy(trace, ctx->trace.p, sizeof(mh_icp_iter) * valid, hipMemcpyDeviceToHost));
   }
-  if ((final_pairs || final_pair_counts) && res->n_final_pairs) {
-    const mh_pairs_out none{};
-    uint64_t sum = 0;
-    for (uint32_t i = 0; i < np; i++) {
-      uint64_t c = 0;
-      if (pairs[i].scan->n)
-        MH_TRY(compact_pairs_of(ctx, tab->d[i].pair_gidx, tab->d[i].pair_q, pairs[i].scan->n, final_pairs ? &final_pairs[i] : &none,
-                                final_pairs ? pairs_mem : MH_MEM_DEVICE, &c));
-      if (final_pair_counts) final_pair_counts[i] = c;
-      sum += c;
-    }
-    if (sum != res->n_final_pairs)
-      return fail(MH_ERR_INTERNAL, "pair compaction count mismatch: %llu pairings in the buffers, %u in the last accumulation",
-                  (unsigned long long)sum, res->n_final_pairs);
+  return job.count_pairs(final_pairs, final_pair_counts, pairs_mem);
+}
+
+// the argument rules of mh_icp_align_layers (one job of mh_icp_align_layers_batch obeys the same): nothing here touches the device
+mh_status check_layers_args(size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params, const double* T_guess,
+                            const mh_icp_result* result) {
+  MH_REQUIRE(n_pairs >= 1 && n_pairs <= MH_MAX_LAYER_PAIRS, "n_pairs must be 1 .. MH_MAX_LAYER_PAIRS");
+  MH_REQUIRE(pairs && params && T_guess && result, "null argument");
+  for (size_t i = 0; i < n_pairs; i++) {
+    MH_REQUIRE(pairs[i].map && pairs[i].scan && pairs[i].threshold, "null map, scan or threshold in a layer pair");
+    MH_REQUIRE(pairs[i].map->ctx == pairs[0].scan->ctx && pairs[i].scan->ctx == pairs[0].scan->ctx,
+               "the maps and scans of a multi-layer alignment live on different contexts");
   }
+  MH_REQUIRE(params->pt2pl_threshold == nullptr, "Matcher_Point2Plane is not supported with layer pairs");
+  MH_REQUIRE(pose_ok(T_guess), "non-finite initial guess");
+  MH_REQUIRE(params->max_iterations == 0 || params->kernel_param, "kernel_param array is required");
+  MH_REQUIRE(params->gn.max_inner_iterations >= 1, "gn.max_inner_iterations must be >= 1");
+  MH_REQUIRE(params->gn.robust_kernel <= MH_KERNEL_GM_C2, "unknown robust kernel");
+  MH_REQUIRE(params->max_iterations < (1u << 20), "max_iterations too large");
+  MH_REQUIRE(params->matched_points <= MH_MATCHED_POINTS_SKIP, "unknown matched_points mode");
+  return MH_OK;
+}
+mh_status check_layers_supported(size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params) {
+  if (params->profile != 0) return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: profile is not supported");
+  if (params->matched_points == MH_MATCHED_POINTS_SKIP)
+    for (size_t i = 0; i < n_pairs; i++)
+      for (size_t j = i + 1; j < n_pairs; j++)
+        if (pairs[i].scan == pairs[j].scan)
+          return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: MH_MATCHED_POINTS_SKIP with a scan shared by two pairs");
   return MH_OK;
 }

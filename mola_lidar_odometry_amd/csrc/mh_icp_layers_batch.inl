@@ -1,0 +1,170 @@
+// mh_icp_layers_batch.inl -- mh_icp_align_layers_batch: many multi-layer alignments (one per context) from one host thread.  Jobs of
+// the same loop shape (inner steps, covariance) advance in LOCK STEP: k_match_layers_b / k_accum_layers_b / k_cov_accum_layers_b
+// walk one flattened range over (job, pair) (mh_k_layers.h), k_solve_b / k_cov_prepare_b / k_cov_finalize_b take a workgroup per
+// job.  Every job is set up by LayersJob::start exactly as a single call sets it up, in its own context; its partials keep the
+// single call's columns and stride, so its result has that call's bits.
+// Loop control is align_batch_run's chunked one on the lead job's stream.  The chunks are launched directly, NOT replayed from a
+// captured graph: a group's composition changes from batch to batch as sequences end, and a chunk is 1 + 2 * inner launches per
+// iteration for ALL jobs where the single calls issue that many each.
+// Included by mh_icp.hip inside its extern "C" block, after mh_icp_batch.inl (order_after_layers_job_streams, k_gather_states).
+
+static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
+  const uint32_t A = (uint32_t)g.size();
+  mh_ctx* const lead = g[0]->ctx;
+  MH_TRY(set_device(lead));
+  hipStream_t s = lead->stream;
+  MH_TRY(order_after_layers_job_streams(lead, g));
+  // [gathered states] | job descriptors of the solve / covariance kernels | the (job, pair) table: pinned mirror and device copy
+  const size_t desc_bytes = A * sizeof(BatchJob) + sizeof(LayerBatchTable);
+  const size_t need = A * sizeof(IcpDeviceState) + desc_bytes;
+  static_assert(sizeof(IcpDeviceState) % 8 == 0 && sizeof(BatchJob) % 8 == 0, "staging layout");
+  MH_TRY(lead->batch_desc.reserve(desc_bytes));
+  MH_TRY(lead->batch_states.reserve(A * sizeof(IcpDeviceState)));
+  if (lead->h_batch_cap < need) {
+    if (lead->h_batch) (void)hipHostFree(lead->h_batch);
+    lead->h_batch = nullptr;
+    lead->h_batch_cap = 0;
+    MH_HIP(hipHostMalloc(&lead->h_batch, need, hipHostMallocDefault));
+    lead->h_batch_cap = need;
+  }
+  IcpDeviceState* const h_states = reinterpret_cast<IcpDeviceState*>(lead->h_batch);
+  BatchJob* const h_desc = reinterpret_cast<BatchJob*>(h_states + A);
+  LayerBatchTable* const h_tab = reinterpret_cast<LayerBatchTable*>(h_desc + A);
+  memset(h_desc, 0, desc_bytes);
+  h_tab->n_jobs = A;
+  uint32_t tot_match = 0, tot_acc = 0, tot_cov = 0, max_iterations = 0, chunk = 0;
+  const mh_icp_params* const p0 = g[0]->p;
+  const uint32_t inner = p0->gn.max_inner_iterations;
+  const bool cov = p0->compute_covariance != 0, auto_chunk = p0->poll_every == 0;
+  for (uint32_t a = 0; a < A; a++) {
+    const LayersJob& j = *g[a];
+    h_tab->job_blk_match[a] = tot_match;
+    h_tab->job_blk_acc[a] = tot_acc;
+    h_tab->job_blk_cov[a] = tot_cov;
+    tot_match += j.L.tot_match;
+    tot_acc += j.L.tot_acc;
+    tot_cov += j.L.tot_cov;
+    LayerBatchJob& t = h_tab->j[a];
+    t.tab = j.ctx->layers_tab.as<LayerTable>();
+    t.st = j.ctx->d_state;
+    t.part = j.ctx->partials.as<double>();
+    t.tot_acc = j.L.tot_acc;
+    t.tot_cov = j.L.tot_cov;
+    BatchJob& d = h_desc[a];  // what k_solve_b, k_cov_prepare_b, k_cov_finalize_b and k_gather_states read of it
+    d.st = j.ctx->d_state;
+    d.sk = &j.ctx->d_params->sk;
+    d.part = t.part;
+    d.nbm = d.nba = j.L.tot_acc;
+    d.nb = j.L.tot_cov;
+    max_iterations = j.p->max_iterations > max_iterations ? j.p->max_iterations : max_iterations;
+    // automatic chunks: as long as the slowest job expects to run (align_batch_run has the reasoning)
+    if (auto_chunk && j.chunk > chunk) chunk = j.chunk;
+  }
+  if (!auto_chunk) chunk = p0->poll_every;
+  h_tab->job_blk_match[A] = tot_match;
+  h_tab->job_blk_acc[A] = tot_acc;
+  h_tab->job_blk_cov[A] = tot_cov;
+  MH_HIP(hipMemcpyAsync(lead->batch_desc.p, h_desc, desc_bytes, hipMemcpyHostToDevice, s));
+  const BatchJob* const dj = lead->batch_desc.as<BatchJob>();
+  const LayerBatchTable* const dt = reinterpret_cast<const LayerBatchTable*>(dj + A);
+  uint32_t enqueued = 0, polls = 0;
+  for (;;) {
+    const uint32_t m = (max_iterations - enqueued) < chunk ? (max_iterations - enqueued) : chunk;
+    for (uint32_t it = 0; it < m; it++) {
+      hipLaunchKernelGGL(k_match_layers_b, dim3(tot_match), dim3(kFlatThreads), 0, s, dt);
+      hipLaunchKernelGGL(k_accum_layers_b, dim3(tot_acc), dim3(kBlock), 0, s, dt, 1u);
+      hipLaunchKernelGGL(k_solve_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj, 1u);
+      for (uint32_t in = 1; in < inner; in++) {
+        hipLaunchKernelGGL(k_accum_layers_b, dim3(tot_acc), dim3(kBlock), 0, s, dt, 0u);
+        hipLaunchKernelGGL(k_solve_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj, 0u);
+      }
+    }
+    if (cov) {  // no-ops for jobs whose loop has not terminated
+      hipLaunchKernelGGL(k_cov_prepare_b, dim3(1, A), dim3(64), 0, s, dj);
+      hipLaunchKernelGGL(k_cov_accum_layers_b, dim3(tot_cov), dim3(kBlock), 0, s, dt);
+      hipLaunchKernelGGL(k_cov_finalize_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj);
+    }
+    hipLaunchKernelGGL(k_gather_states, dim3(A), dim3(256), 0, s, dj, lead->batch_states.as<IcpDeviceState>());
+    MH_HIP(hipGetLastError());
+    MH_HIP(hipMemcpyAsync(h_states, lead->batch_states.p, A * sizeof(IcpDeviceState), hipMemcpyDeviceToHost, s));
+    enqueued += m;
+    polls++;
+    MH_HIP(mh::wait_stream(s));
+    bool all_done = true;
+    for (uint32_t a = 0; a < A; a++) all_done = all_done && h_states[a].done;
+    if (all_done) break;
+    if (enqueued >= max_iterations) return fail(MH_ERR_INTERNAL, "device ICP loop did not terminate after max_iterations");
+    if (auto_chunk) chunk = kChunkNext;
+  }
+  for (uint32_t a = 0; a < A; a++) {
+    LayersJob& j = *g[a];
+    memcpy(j.ctx->h_state, &h_states[a], sizeof(IcpDeviceState));
+    j.finish(polls, enqueued < j.p->max_iterations ? enqueued : j.p->max_iterations);
+  }
+  return MH_OK;
+}
+
+mh_status mh_icp_align_layers_batch(size_t n_jobs, const mh_layer_job* jobs, const mh_icp_params* params, int32_t params_per_job,
+                                    const double* T_guesses, const mh_prior* const* priors, mh_icp_result* results,
+                                    uint64_t* final_pair_counts) {
+  MH_REQUIRE(n_jobs >= 1 && n_jobs <= MH_MAX_LAYER_BATCH_JOBS, "n_jobs must be 1 .. MH_MAX_LAYER_BATCH_JOBS");
+  MH_REQUIRE(jobs && params && T_guesses && results, "null argument");
+  auto P = [&](size_t i) { return params_per_job ? &params[i] : params; };
+  // everything is checked before anything is queued: after an error no context has seen any work
+  for (size_t i = 0; i < n_jobs; i++) {
+    MH_TRY(check_layers_args(jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, &results[i]));
+    for (size_t k = 0; k < i; k++)
+      MH_REQUIRE(jobs[k].pairs[0].scan->ctx != jobs[i].pairs[0].scan->ctx, "each job of a batch needs its own context");
+    MH_REQUIRE(jobs[i].pairs[0].scan->ctx->device == jobs[0].pairs[0].scan->ctx->device, "the jobs of a batch live on different devices");
+  }
+  for (size_t i = 0; i < n_jobs; i++) {
+    MH_TRY(check_layers_supported(jobs[i].n_pairs, jobs[i].pairs, P(i)));
+    for (size_t k = 0; k < jobs[i].n_pairs; k++)
+      if (jobs[i].pairs[k].map->n_records >= kFlatMaxRecords)
+        return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: a map of 2^30 or more records");
+  }
+  const Switches sw = read_switches();
+  auto counts_of = [&](size_t i) { return final_pair_counts ? final_pair_counts + i * MH_MAX_LAYER_PAIRS : nullptr; };
+  if (final_pair_counts)
+    for (size_t i = 0; i < n_jobs * MH_MAX_LAYER_PAIRS; i++) final_pair_counts[i] = 0;
+  // lock-step groups: same inner steps, same covariance switch (the launches of a chunk are the same for every job of a group)
+  std::vector<LayersJob> lj(n_jobs);
+  std::vector<std::vector<size_t>> groups;
+  std::vector<char> in_group(n_jobs, 0);
+  if (!sw.no_lockstep) {
+    for (size_t i = 0; i < n_jobs; i++) {
+      const mh_icp_params* q = P(i);
+      size_t total_n = 0;
+      for (size_t k = 0; k < jobs[i].n_pairs; k++) total_n += jobs[i].pairs[k].scan->n;
+      if (q->max_iterations == 0 || total_n == 0) continue;  // trivial: nothing to run
+      std::vector<size_t>* g = nullptr;
+      for (auto& c : groups)
+        if (P(c[0])->gn.max_inner_iterations == q->gn.max_inner_iterations && (P(c[0])->compute_covariance != 0) == (q->compute_covariance != 0))
+          g = &c;
+      if (!g) {
+        groups.emplace_back();
+        g = &groups.back();
+      }
+      g->push_back(i);
+    }
+    for (auto& c : groups)
+      if (c.size() >= 2)
+        for (size_t i : c) in_group[i] = 1;
+  }
+  for (auto& c : groups) {
+    if (c.size() < 2) continue;  // a job alone in its group gains nothing from lock step
+    std::vector<LayersJob*> g;
+    for (size_t i : c) {
+      MH_TRY(lj[i].start(sw, (uint32_t)jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr,
+                         &results[i], nullptr, counts_of(i)));
+      g.push_back(&lj[i]);
+    }
+    MH_TRY(align_layers_lockstep(g));
+    for (size_t i : c) MH_TRY(lj[i].count_pairs(nullptr, counts_of(i), MH_MEM_DEVICE));
+  }
+  for (size_t i = 0; i < n_jobs; i++)
+    if (!in_group[i])
+      MH_TRY(align_layers(sw, (uint32_t)jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr,
+                          &results[i], nullptr, nullptr, counts_of(i), MH_MEM_HOST));
+  return MH_OK;
+}

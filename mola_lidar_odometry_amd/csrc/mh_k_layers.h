@@ -8,6 +8,13 @@
 //   k_accum_layers    k_accum_body<true> with the pair's MatchK (its weight), into its columns of the shared partials
 //   k_cov_accum_layers  k_cov_accum_body over the pair's pairings, into its columns of the covariance partials
 // k_solve / k_cov_prepare / k_cov_finalize are launched as they are over all columns (fixed order: bitwise reproducible).
+//
+// mh_icp_align_layers_batch (the *_layers_b entry points): the flattened range one level up.  A device-resident job table holds,
+// per job, its own LayerTable (built as for a single call), its state block and its partials; job j owns the workgroups
+// [job_blk_*[j], job_blk_*[j + 1]) of each launch and, inside them, pair i of that job the range its own table gives.  A workgroup
+// finds its job, leaves at once when that job has terminated, then finds its pair.  Pair i writes the columns of the JOB's partials
+// it writes in a single call (stride: the job's total), so k_solve_b / k_cov_finalize_b (a workgroup per job: mh_k_launch.h) add
+// the same numbers in the same order and every job ends with the bits of its single call.
 #pragma once
 
 struct LayerDesc {
@@ -39,16 +46,12 @@ __device__ __forceinline__ uint32_t layer_of(const uint32_t __attribute__((addre
   return li;
 }
 
-__global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_layers(const IcpDeviceState* __restrict__ st,
-                                                                               const LayerTable* __restrict__ tab) {
-  __shared__ FlatWave sh[kFlatThreads / 64];
-  typedef const IcpDeviceState __attribute__((address_space(4))) * cstate_ptr;
-  const cstate_ptr cst = (cstate_ptr)uniform_const_ptr(st);
-  if (cst->done) return;  // grid-uniform
-  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
-  const uint32_t li = layer_of(ct->blk_match, ct->n_pairs, blockIdx.x);
+// one wave of pair-owned matching: workgroup `b` of the table's flattened match range (`cst`: the alignment's state, not terminated)
+typedef const IcpDeviceState __attribute__((address_space(4))) * clayers_state_ptr;
+__device__ __forceinline__ void match_layers_wave(FlatWave& sh, const clayers_state_ptr cst, const clayers_ptr ct, const uint32_t b) {
+  const uint32_t li = layer_of(ct->blk_match, ct->n_pairs, b);
   const uint32_t n = ct->d[li].n;
-  const uint32_t i0 = (blockIdx.x - ct->blk_match[li]) * kFlatPointsPerBlock + (threadIdx.x & ~63u);
+  const uint32_t i0 = (b - ct->blk_match[li]) * kFlatPointsPerBlock + (threadIdx.x & ~63u);
   if (i0 >= n) return;    // whole waves
   // field by field: scalar loads through the constant-space table (a MapView field added in mh_internal.h has to be added here:
   // the static_assert below fails until it is)
@@ -77,8 +80,16 @@ __global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_layers(co
   for (int k = 0; k < 12; k++) T[k] = cst->T[k];
   const double thr = G(ct->d[li].mk.thr)[iter];
   const float thr2 = (float)(thr * thr);  // what k_solve leaves in cur_thr2 for a single alignment
-  match_flat_wave(sh[threadIdx.x >> 6], map, T, thr2, ct->d[li].mk.ang2, have_prev, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz,
-                  n, i0, ct->d[li].pair_q, ct->d[li].pair_gidx, nullptr);
+  match_flat_wave(sh, map, T, thr2, ct->d[li].mk.ang2, have_prev, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, n, i0,
+                  ct->d[li].pair_q, ct->d[li].pair_gidx, nullptr);
+}
+
+__global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_layers(const IcpDeviceState* __restrict__ st,
+                                                                               const LayerTable* __restrict__ tab) {
+  __shared__ FlatWave sh[kFlatThreads / 64];
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
+  if (cst->done) return;  // grid-uniform
+  match_layers_wave(sh[threadIdx.x >> 6], cst, (clayers_ptr)uniform_const_ptr(tab), blockIdx.x);
 }
 
 __global__ __launch_bounds__(kBlock, MH_ACCUM_WAVES) void k_accum_layers(const IcpDeviceState* __restrict__ st,
@@ -97,4 +108,58 @@ __global__ __launch_bounds__(kBlock) void k_cov_accum_layers(const IcpDeviceStat
   const uint32_t li = layer_of(ct->blk_cov, ct->n_pairs, blockIdx.x);
   k_cov_accum_body(st, 0u, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n, ct->d[li].pair_gidx,
                    partials + ct->d[li].cov_off, pstride, blockIdx.x - ct->blk_cov[li]);
+}
+
+// ---- lock-step batches of multi-layer alignments (mh_icp_align_layers_batch) -----------------------------------------------------
+// (the job's SolveK and the column counts of its solves travel in the BatchJob array that k_solve_b / k_cov_*_b read)
+struct LayerBatchJob {
+  const LayerTable* tab;  // the job's own table, in its own context's memory
+  IcpDeviceState* st;
+  double* part;           // the job's partials: k_accum columns, later the covariance's
+  uint32_t tot_acc, tot_cov;  // their strides = the job's workgroups in the accumulation / covariance launches
+};
+
+struct LayerBatchTable {
+  uint32_t n_jobs, pad;
+  uint32_t job_blk_match[MH_MAX_LAYER_BATCH_JOBS + 1];  // first workgroup of each job in the flattened grids (+ the total)
+  uint32_t job_blk_acc[MH_MAX_LAYER_BATCH_JOBS + 1];
+  uint32_t job_blk_cov[MH_MAX_LAYER_BATCH_JOBS + 1];
+  LayerBatchJob j[MH_MAX_LAYER_BATCH_JOBS];
+};
+
+typedef const LayerBatchTable __attribute__((address_space(4))) * clayer_batch_ptr;
+
+// (the job of a workgroup: layer_of over the jobs' prefix array -- blockIdx.x and the table are wave-uniform, so the search is
+// scalar loads and scalar compares, at most MH_MAX_LAYER_BATCH_JOBS - 1 of them per workgroup)
+__global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_layers_b(const LayerBatchTable* __restrict__ bt) {
+  __shared__ FlatWave sh[kFlatThreads / 64];
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const uint32_t ji = layer_of(cb->job_blk_match, cb->n_jobs, blockIdx.x);
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(cb->j[ji].st);
+  if (cst->done) return;  // uniform over the job's workgroups
+  match_layers_wave(sh[threadIdx.x >> 6], cst, (clayers_ptr)uniform_const_ptr(cb->j[ji].tab), blockIdx.x - cb->job_blk_match[ji]);
+}
+
+__global__ __launch_bounds__(kBlock, MH_ACCUM_WAVES) void k_accum_layers_b(const LayerBatchTable* __restrict__ bt, uint32_t first) {
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const uint32_t ji = layer_of(cb->job_blk_acc, cb->n_jobs, blockIdx.x);
+  const IcpDeviceState* const st = cb->j[ji].st;
+  if (((clayers_state_ptr)uniform_const_ptr(st))->done) return;  // uniform over the job's workgroups
+  const LayerTable* const tab = cb->j[ji].tab;
+  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
+  const uint32_t b = blockIdx.x - cb->job_blk_acc[ji];
+  const uint32_t li = layer_of(ct->blk_acc, ct->n_pairs, b);
+  k_accum_body<true>(st, first, &tab->d[li].mk, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n, ct->d[li].pair_q,
+                     ct->d[li].pair_gidx, cb->j[ji].part + ct->d[li].col_off, cb->j[ji].tot_acc, b - ct->blk_acc[li]);
+}
+
+// (a job still running or whose covariance is done leaves inside the body, as in k_cov_accum_layers)
+__global__ __launch_bounds__(kBlock) void k_cov_accum_layers_b(const LayerBatchTable* __restrict__ bt) {
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const uint32_t ji = layer_of(cb->job_blk_cov, cb->n_jobs, blockIdx.x);
+  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(cb->j[ji].tab);
+  const uint32_t b = blockIdx.x - cb->job_blk_cov[ji];
+  const uint32_t li = layer_of(ct->blk_cov, ct->n_pairs, b);
+  k_cov_accum_body(cb->j[ji].st, 0u, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n, ct->d[li].pair_gidx,
+                   cb->j[ji].part + ct->d[li].cov_off, cb->j[ji].tot_cov, b - ct->blk_cov[li]);
 }

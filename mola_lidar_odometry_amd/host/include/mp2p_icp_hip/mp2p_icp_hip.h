@@ -383,8 +383,8 @@ class QualityEvaluator_PairedRatio {
 // idle, so the instances' alignments are merged: every instance runs on its own host thread, and where it would call
 // mh_icp_align it hands its request to the batcher and blocks; when ALL active participants are waiting, the last one
 // to arrive runs ONE mh_icp_align_batch over the requests (per-job parameters: every sequence has its own adaptive
-// threshold, iteration budget, hook check point; jobs with the same kernel chain advance in lock step) and wakes the
-// others.  Results are bitwise those of separate alignments, so every sequence's records are those of a solo run.
+// threshold, iteration budget, hook check point; jobs with the same kernel chain advance in lock step) -- and ONE
+// mh_icp_align_layers_batch over the multi-layer requests among them -- and wakes the others.  Results are bitwise those of separate alignments, so every sequence's records are those of a solo run.
 class AlignBatcher {
  public:
   explicit AlignBatcher(size_t participants);
@@ -392,6 +392,13 @@ class AlignBatcher {
   // `owner`: any address that identifies the participant (the same one in every call it makes; nullptr: the scan)
   mh_status align(const void* owner, const mh_map* map, const mh_scan* scan, const mh_icp_params* params, const double T_guess[12],
                   const mh_prior* prior, mh_icp_result* result, std::string* error);
+  // The same for a multi-layer alignment (mh_icp_align_layers; `pairs` all on the participant's own context): the multi-layer
+  // requests of a batch run as ONE mh_icp_align_layers_batch beside the single-pair ones' mh_icp_align_batch.
+  mh_status alignLayers(const void* owner, size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params,
+                        const double T_guess[12], const mh_prior* prior, mh_icp_result* result, std::string* error);
+  // An alignment that has no batched form (the matcher/solver-granular loop): `fn` runs on the caller's thread at once, and
+  // meanwhile the participant counts as one that is not waiting, so the others' batches are not held up for it.
+  void runOutside(const void* owner, const std::function<void()>& fn);
   // The observation filters of the participants' NEXT scans (mh_scan_preprocess) merged the same way, in sets of their
   // own: a sequence's filter request for scan k+1 and its alignment of scan k are in flight together.  Which requests
   // belong together is bookkeeping, not timing.  A participant announces a request on the thread that will align next
@@ -440,6 +447,8 @@ class AlignBatcher {
   struct Request {
     const mh_map* map = nullptr;
     const mh_scan* scan = nullptr;
+    size_t n_pairs = 0;                    // a multi-layer request: its pairs (map and scan are null)
+    const mh_layer_pair* pairs = nullptr;
     const mh_icp_params* params = nullptr;
     const double* T = nullptr;
     const mh_prior* prior = nullptr;
@@ -477,6 +486,7 @@ class AlignBatcher {
   size_t n_pp_batches_ = 0, n_pp_jobs_ = 0, n_pp_timeouts_ = 0, n_wait_timeouts_ = 0;
   std::chrono::steady_clock::time_point last_solo_{};  // when the latest alignment issued on its own arrived
   void run_batch(std::vector<Request*>& batch);  // called WITHOUT the mutex
+  mh_status submit(const void* owner, Request& rq, int32_t solo, std::string* error);  // a request's way through the batches
   void take_waiting_locked(std::vector<Request*>& batch);  // the ONLY way out of waiting_: clears every taken request's `lead`
   bool batch_due_locked() const;
   size_t threshold_locked() const;

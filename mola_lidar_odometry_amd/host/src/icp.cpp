@@ -686,39 +686,63 @@ void AlignBatcher::run_batch(std::vector<Request*>& batch) {
   // may start the next batch on their own contexts meanwhile: the C ABI is re-entrant across contexts)
   const size_t n = batch.size();
   const auto t_start = std::chrono::steady_clock::now();
-  std::vector<const mh_map*> maps(n);
-  std::vector<const mh_scan*> scans(n);
-  std::vector<mh_icp_params> params(n);
-  std::vector<double> T(12 * n);
-  std::vector<const mh_prior*> priors(n);
   std::vector<mh_icp_result> results(n);
-  bool any_prior = false;
-  for (size_t i = 0; i < n; i++) {
-    maps[i] = batch[i]->map;
-    scans[i] = batch[i]->scan;
-    params[i] = *batch[i]->params;
-    memcpy(&T[12 * i], batch[i]->T, 12 * sizeof(double));
-    priors[i] = batch[i]->prior;
-    any_prior = any_prior || batch[i]->prior;
-  }
-  mh_status st = MH_OK;
-  std::string err;
-  if (n == 1) {
-    st = mh_icp_align(maps[0], scans[0], &params[0], &T[0], priors[0], &results[0], nullptr, nullptr, MH_MEM_HOST);
-  } else {
-    st = mh_icp_align_batch(n, maps.data(), scans.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr,
-                            results.data(), nullptr, MH_MEM_HOST);
-  }
-  if (st != MH_OK) err = mh_last_error_string();  // (thread-local in the library: read it on the thread that made the call)
-  std::vector<mh_status> sts(n, st);
-  std::vector<std::string> errs(n, err);
-  if (st != MH_OK && n > 1) {
-    // one job's bad argument or allocation failure must not fail the other sequences: once more, one by one, so that
-    // every request gets its own status
-    for (size_t i = 0; i < n; i++) {
-      sts[i] = mh_icp_align(maps[i], scans[i], &params[i], &T[12 * i], priors[i], &results[i], nullptr, nullptr, MH_MEM_HOST);
-      errs[i] = sts[i] != MH_OK ? mh_last_error_string() : "";
+  std::vector<mh_status> sts(n, MH_OK);
+  std::vector<std::string> errs(n);
+  // the single-pair requests as one mh_icp_align_batch, the multi-layer ones as one mh_icp_align_layers_batch
+  for (const bool layers : {false, true}) {
+    std::vector<size_t> idx;
+    for (size_t i = 0; i < n; i++)
+      if ((batch[i]->pairs != nullptr) == layers) idx.push_back(i);
+    const size_t m = idx.size();
+    if (!m) continue;
+    std::vector<const mh_map*> maps(m);
+    std::vector<const mh_scan*> scans(m);
+    std::vector<mh_layer_job> jobs(m);
+    std::vector<mh_icp_params> params(m);
+    std::vector<double> T(12 * m);
+    std::vector<const mh_prior*> priors(m);
+    std::vector<mh_icp_result> res(m);
+    bool any_prior = false;
+    for (size_t k = 0; k < m; k++) {
+      const Request& rq = *batch[idx[k]];
+      maps[k] = rq.map;
+      scans[k] = rq.scan;
+      jobs[k].n_pairs = rq.n_pairs;
+      jobs[k].pairs = rq.pairs;
+      params[k] = *rq.params;
+      memcpy(&T[12 * k], rq.T, 12 * sizeof(double));
+      priors[k] = rq.prior;
+      any_prior = any_prior || rq.prior;
     }
+    auto one = [&](size_t k) {
+      return layers ? mh_icp_align_layers(jobs[k].n_pairs, jobs[k].pairs, &params[k], &T[12 * k], priors[k], &res[k], nullptr, nullptr,
+                                          nullptr, MH_MEM_HOST)
+                    : mh_icp_align(maps[k], scans[k], &params[k], &T[12 * k], priors[k], &res[k], nullptr, nullptr, MH_MEM_HOST);
+    };
+    mh_status st = MH_OK;
+    if (m == 1) {
+      st = one(0);
+    } else if (layers) {
+      st = mh_icp_align_layers_batch(m, jobs.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr, res.data(), nullptr);
+    } else {
+      st = mh_icp_align_batch(m, maps.data(), scans.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr,
+                              res.data(), nullptr, MH_MEM_HOST);
+    }
+    const std::string err = st != MH_OK ? mh_last_error_string() : "";  // (thread-local in the library: read it on the thread that made the call)
+    for (size_t k = 0; k < m; k++) {
+      sts[idx[k]] = st;
+      errs[idx[k]] = err;
+    }
+    if (st != MH_OK && m > 1) {
+      // one job's bad argument or allocation failure must not fail the other sequences: once more, one by one, so that
+      // every request gets its own status
+      for (size_t k = 0; k < m; k++) {
+        sts[idx[k]] = one(k);
+        errs[idx[k]] = sts[idx[k]] != MH_OK ? mh_last_error_string() : "";
+      }
+    }
+    for (size_t k = 0; k < m; k++) results[idx[k]] = res[k];
   }
   std::lock_guard<std::mutex> lk(mtx_);
   n_batches_++;
@@ -734,6 +758,39 @@ void AlignBatcher::run_batch(std::vector<Request*>& batch) {
     batch[i]->done = true;
   }
   cv_.notify_all();
+}
+
+mh_status AlignBatcher::alignLayers(const void* owner, size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params,
+                                    const double T_guess[12], const mh_prior* prior, mh_icp_result* result, std::string* error) {
+  Request rq;
+  rq.n_pairs = n_pairs; rq.pairs = pairs; rq.params = params; rq.T = T_guess; rq.prior = prior; rq.result = result;
+  // (no one-launch loops on the multi-layer path: nothing to ask the library; MOLA_HIP_BATCH_SOLO alone issues it at once)
+  return submit(owner ? owner : (const void*)pairs, rq, solo_ ? 1 : 0, error);
+}
+
+void AlignBatcher::runOutside(const void* owner, const std::function<void()>& fn) {
+  std::unique_lock<std::mutex> lk(mtx_);
+  owners_[owner].aligns++;
+  in_flight_ += 1;
+  auto wake_leader = [&] {  // whoever waits for a batch waits for those who are not in flight: if that is nobody now, one of them leads it
+    if (batch_due_locked()) {
+      waiting_.front()->lead = true;
+      cv_.notify_all();
+    }
+  };
+  wake_leader();
+  lk.unlock();
+  try {
+    fn();
+  } catch (...) {
+    lk.lock();
+    in_flight_ -= 1;
+    wake_leader();
+    throw;
+  }
+  lk.lock();
+  in_flight_ -= 1;
+  wake_leader();
 }
 
 mh_status AlignBatcher::align(const void* owner, const mh_map* map, const mh_scan* scan, const mh_icp_params* params,
@@ -753,10 +810,14 @@ mh_status AlignBatcher::align(const void* owner, const mh_map* map, const mh_sca
     }
     if (mh_icp_align_prefers_solo(scan, params, (uint32_t)callers, &solo) != MH_OK) solo = 0;
   }
+  return submit(owner ? owner : (const void*)scan, rq, solo, error);
+}
+
+mh_status AlignBatcher::submit(const void* owner, Request& rq, int32_t solo, std::string* error) {
   std::unique_lock<std::mutex> lk(mtx_);
   rq.arrived = std::chrono::steady_clock::now();
   {
-    OwnerState& os = owners_[owner ? owner : (const void*)scan];
+    OwnerState& os = owners_[owner];
     os.aligns++;  // this participant is past the filter set of its previous alignment count
     // A participant whose alignments run on their own is not in step with anybody: its prefetch worker's filter chain runs at
     // once instead of waiting for a set that only lock-step rounds complete (16 free-running sequences: 1.6 ms of every scan
@@ -964,7 +1025,9 @@ void ICP::align(const metric_map_t& pcLocal, const metric_map_t& pcGlobal, const
     align_fused_layers(pcLocal, pcGlobal, g, p, result, prior);
   } else {
     last_fused_ = false;
-    align_generic(pcLocal, pcGlobal, g, p, result, prior);
+    // (no batched form: beside a batcher the participant counts as busy meanwhile, so nobody waits for a request it will not make)
+    if (batcher_) batcher_->runOutside(batch_owner_, [&] { align_generic(pcLocal, pcGlobal, g, p, result, prior); });
+    else align_generic(pcLocal, pcGlobal, g, p, result, prior);
   }
 }
 
@@ -1223,7 +1286,8 @@ void ICP::align_fused(const PointCloud* host_local, const DevicePointCloud* dev_
 }
 
 // The multi-layer shapes on the device loop (mh_icp_align_layers).  Pairs in align_generic's matching order: matchers in list
-// order, entries in pointLayerMatches order.  Solo alignments (not through the AlignBatcher).
+// order, entries in pointLayerMatches order.  With a batcher set (and neither a trace nor the pairings wanted) the alignment joins
+// those of the other sequences: AlignBatcher::alignLayers, mh_icp_align_layers_batch.
 void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pcGlobal, const CPose3D& guess, const Parameters& p,
                              Results& result, const std::optional<CPose3DPDFGaussianInf>& prior) {
   const auto t_setup0 = std::chrono::steady_clock::now();
@@ -1316,8 +1380,14 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   }
   mh_icp_result r{};
   std::vector<mh_icp_iter> trace(p.generateDebugFiles ? mi : 0);
-  check(mh_icp_align_layers(pairs.size(), pairs.data(), &ip, guess.T, prior ? &pr : nullptr, &r, trace.empty() ? nullptr : trace.data(),
-                            want_pairs ? po.data() : nullptr, counts.data(), MH_MEM_HOST), "mh_icp_align_layers");
+  if (batcher_ && trace.empty() && !want_pairs) {
+    std::string err;
+    const mh_status st = batcher_->alignLayers(batch_owner_, pairs.size(), pairs.data(), &ip, guess.T, prior ? &pr : nullptr, &r, &err);
+    if (st != MH_OK) throw std::runtime_error(std::string("mh_icp_align_layers_batch: ") + mh_status_string(st) + ": " + err);
+  } else {
+    check(mh_icp_align_layers(pairs.size(), pairs.data(), &ip, guess.T, prior ? &pr : nullptr, &r, trace.empty() ? nullptr : trace.data(),
+                              want_pairs ? po.data() : nullptr, counts.data(), MH_MEM_HOST), "mh_icp_align_layers");
+  }
   if (p.generateDebugFiles) write_debug_file(p, guess, r, trace, (size_t)r.potential_pairings);
   last_iterations_[call_kind] = r.n_iterations + (r.termination_reason == MH_TERM_MAX_ITERATIONS ? 0u : 1u);
   last_polls_ = r.n_host_polls;

@@ -907,7 +907,8 @@ void LidarOdometry::run_first_pass() {
 void LidarOdometry::setAlignBatcher(std::shared_ptr<mp2p_icp_hip::AlignBatcher> b) {
   // the instances of a batch run on their own host threads: each needs a context (stream + scratch) of its own, the
   // process-wide default one would be shared between threads (molahip.h: one context, one thread at a time)
-  if (gplan_) return;  // general plans run unbatched
+  // (general plans too: their ICP joins through whichever route it takes -- mp2p_icp_hip::ICP::align; their filter steps and
+  // their next scan's upload are not announced to the batcher, launch_prefetch() is the default plan's)
   if (b && (!ctx_ || ctx_ == DeviceContext::Default()))
     throw std::runtime_error("LidarOdometry::setAlignBatcher: this instance uses the process-wide default context; construct "
                              "it with a DeviceContext of its own");

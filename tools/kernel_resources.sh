@@ -14,8 +14,9 @@ for l in sys.stdin:
     k,v=m.group(1),m.group(2).strip()
     if k=='name' and 'kd' not in v and cur.get('name') is None: cur['name']=v
     if k in('vgpr_count','sgpr_count','agpr_count','vgpr_spill_count','sgpr_spill_count','private_segment_fixed_size','group_segment_fixed_size'): cur[k]=v
-    if k=='symbol':
-        cur['symbol']=v; out.append(cur); cur={}
+    if k=='symbol': cur['symbol']=v
+    if k=='wavefront_size':  # the last key of a kernel's entry (they come in alphabetical order: .symbol before .vgpr_count)
+        out.append(cur); cur={}
 import subprocess
 for c in out:
     n=subprocess.run(['c++filt',c.get('symbol','').replace('.kd','')],capture_output=True,text=True).stdout.strip()[:60]
