@@ -476,8 +476,14 @@ MH_API mh_status mh_gn_solve(mh_ctx* ctx, const mh_pairs_pt2pt* pt2pt, const mh_
                              int32_t* solver_ok, mh_gn_step* trace);
 
 /* Replaces mp2p_icp::covariance() [U] (result consumed at LidarOdometry.cpp:1009,1035-1036,2090):
- * central-difference Jacobian of the stacked residuals wrt (x,y,z,yaw,pitch,roll), cov = (A^T A)^-1;
- * diag(1e6) when there are no pairings or A^T A is singular. */
+ * central-difference Jacobian of the stacked residuals wrt (x,y,z,yaw,pitch,roll) -- steps findif_xyz for the first three
+ * columns, findif_ang for the last three -- cov = (A^T A)^-1; diag(1e6) when there are no pairings or A^T A is singular.
+ * Singular means singular to working precision: a Cholesky pivot of A^T A not above 1e-10 of its diagonal entry (the differences
+ * carry rounding into A, so a pivot that is exactly zero -- fewer than six rows, two point pairings -- arrives as a tiny number
+ * of either sign).
+ * [U] The pairings enter unweighted: a point pairing gives three rows and a plane pairing one, whatever
+ * mh_gn_params::weight_pt2pt / weight_pt2pl were during the alignment (upstream's covariance() takes the pairings and the
+ * pose, no weights).  The fused path (mh_icp_result::cov) is this function of the final pose and pairings. */
 MH_API mh_status mh_covariance(mh_ctx* ctx, const mh_pairs_pt2pt* pt2pt, const mh_pairs_pt2pl* pt2pl, int32_t mem,
                                const double T[12], double findif_xyz, double findif_ang, double cov[36]);
 

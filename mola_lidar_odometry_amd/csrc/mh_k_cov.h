@@ -57,6 +57,12 @@ __device__ __forceinline__ void cov_rows_plane(const double* sD, double x, doubl
     for (int b = a; b < 6; b++) v[q++] = A[a] * A[b];
   v[21] = 1.0;
 }
+// A^T A counts as singular when a Cholesky pivot is not above this fraction of its diagonal entry.  A pivot that is zero in exact
+// arithmetic -- one or two point pairings, fewer than six rows -- arrives as rounding of either sign: the sums' own (a few eps of
+// the diagonal entry, 2e-16 measured) or the square of what the central differences carry into A (eps |x| / h: 2e-6 one kilometre
+// out at the default step, so 4e-12), and its SIGN used to decide between diag(1e6) and entries of 1e15.  A pairing set of any
+// use keeps its pivots above 1e-8 (a condition number of A^T A below 1e8); the CPU reference of the test suite applies the same rule.
+constexpr double kCovSingularRel = 1e-10;
 // (A^T A)^-1 from the 21 + 1 sums; diag(1e6) when there is nothing to invert
 __device__ __forceinline__ void cov_from_sums(const double* a, double* out36) {
   double AtA[36], cov[36];
@@ -67,7 +73,7 @@ __device__ __forceinline__ void cov_from_sums(const double* a, double* out36) {
       AtA[c * 6 + r] = a[q];
       q++;
     }
-  bool ok = a[21] > 0.5 && chol_inverse6(AtA, cov);
+  bool ok = a[21] > 0.5 && chol_inverse6(AtA, cov, kCovSingularRel);
   if (ok)
     for (int i = 0; i < 36; i++) ok = ok && isfinite(cov[i]);
   for (int i = 0; i < 36; i++) out36[i] = ok ? cov[i] : ((i % 7 == 0) ? 1e6 : 0.0);

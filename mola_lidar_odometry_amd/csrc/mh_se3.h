@@ -312,8 +312,9 @@ MH_HD bool ldlt_solve6_spd(const double Hfull[36], const double b[6], double x[6
   return ok;
 }
 
-// inverse of an SPD 6x6 via Cholesky (mrpt inverse_LLt in mp2p_icp::covariance); false if not SPD
-MH_HD bool chol_inverse6(const double A[36], double Ainv[36]) {
+// inverse of an SPD 6x6 via Cholesky (mrpt inverse_LLt in mp2p_icp::covariance); false if not SPD to working
+// precision: a pivot not above rel_tol times its diagonal entry.  The arithmetic of an accepted matrix does not depend on rel_tol.
+MH_HD bool chol_inverse6(const double A[36], double Ainv[36], double rel_tol) {
   double L[36];
 #pragma unroll
   for (int i = 0; i < 36; i++) L[i] = 0.0;
@@ -325,7 +326,7 @@ MH_HD bool chol_inverse6(const double A[36], double Ainv[36]) {
 #pragma unroll
       for (int k = 0; k < j; k++) s -= L[i * 6 + k] * L[j * 6 + k];
       if (i == j) {
-        if (!(s > 0.0)) return false;
+        if (!(s > rel_tol * A[i * 6 + i])) return false;
         L[i * 6 + i] = sqrt(s);
       } else {
         L[i * 6 + j] = s / L[j * 6 + j];

@@ -933,6 +933,11 @@ int orc_gn_solve(const orc_pairs_pt2pt* pp, const orc_pairs_pt2pl* pl, const orc
 /* ======================================================================================
  * Covariance -- mp2p_icp::covariance
  * ==================================================================================== */
+/* A^T A is singular to working precision when a Cholesky pivot is not above this fraction of its diagonal entry: a pivot that is
+ * zero in exact arithmetic (one or two point pairings, fewer than six rows) arrives as rounding of either sign -- the sums' own, a
+ * few eps of the diagonal entry, or the square of what the central differences carry into A (eps |x| / h: 2e-6 one kilometre out
+ * at the default step, so 4e-12) -- and its sign would decide between diag(1e6) and entries of 1e15. */
+#define ORC_COV_SINGULAR_REL 1e-10
 static int chol_inverse6(const double A[36], double Ainv[36]) {
   double L[36] = {0};
   for (int i = 0; i < 6; i++)
@@ -940,7 +945,7 @@ static int chol_inverse6(const double A[36], double Ainv[36]) {
       double s = A[i * 6 + j];
       for (int k = 0; k < j; k++) s -= L[i * 6 + k] * L[j * 6 + k];
       if (i == j) {
-        if (!(s > 0.0)) return 0;
+        if (!(s > ORC_COV_SINGULAR_REL * A[i * 6 + i])) return 0;
         L[i * 6 + i] = sqrt(s);
       } else
         L[i * 6 + j] = s / L[j * 6 + j];

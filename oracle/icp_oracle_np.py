@@ -218,11 +218,11 @@ def prior_term(prior, T):
 
 
 def gn_solve(T, pt2pt=None, pt2pl=None, inner=2, kernel=KERNEL_GM_C4, c=1.0, prior=None, min_delta=1e-7,
-             max_cost=0.0):
+             max_cost=0.0, w_pt2pt=1.0, w_pt2pl=1.0):
     T = np.asarray(T, dtype=np.float64).copy()
     steps = []
     for _ in range(inner):
-        H, g, cost = accumulate(T, pt2pt, pt2pl, kernel, c)
+        H, g, cost = accumulate(T, pt2pt, pt2pl, kernel, c, w_pt2pt, w_pt2pl)
         if prior is not None:
             Hp, gp = prior_term(prior, T)
             H, g = H + Hp, g + gp
@@ -235,6 +235,24 @@ def gn_solve(T, pt2pt=None, pt2pl=None, inner=2, kernel=KERNEL_GM_C4, c=1.0, pri
         if np.linalg.norm(delta) < min_delta:
             break
     return T, steps
+
+
+COV_SINGULAR_REL = 1e-10  # a Cholesky pivot of A^T A not above this fraction of its diagonal entry: singular (icp_oracle.c)
+
+
+def inverse_or_unknown(AtA):
+    """(A^T A)^-1, or diag(1e6) when A^T A is singular to working precision (include/molahip.h, mh_covariance)."""
+    L = np.zeros((6, 6))
+    for i in range(6):
+        for j in range(i + 1):
+            s = AtA[i, j] - L[i, :j] @ L[j, :j]
+            if i == j:
+                if not s > COV_SINGULAR_REL * AtA[i, i]:
+                    return np.eye(6) * 1e6
+                L[i, i] = np.sqrt(s)
+            else:
+                L[i, j] = s / L[j, j]
+    return np.linalg.inv(AtA)
 
 
 def covariance(T, pt2pt, findif_xyz=1e-7, findif_ang=1e-7):
@@ -258,7 +276,55 @@ def covariance(T, pt2pt, findif_xyz=1e-7, findif_ang=1e-7):
         h = findif_xyz if j < 3 else findif_ang
         d = np.zeros(6); d[j] = h
         A[:, j] = (resid(x0 + d) - resid(x0 - d)) / (2 * h)
-    return np.linalg.inv(A.T @ A)
+    return inverse_or_unknown(A.T @ A)
+
+
+def ypr_jacobian(T):
+    """(yaw, pitch, roll) of T and dR/dyaw, dR/dpitch, dR/droll of R = Rz(yaw) Ry(pitch) Rx(roll) in closed form."""
+    R = np.asarray(T, np.float64)[:3, :3]
+    pitch = np.arctan2(-R[2, 0], np.hypot(R[0, 0], R[1, 0]))
+    yaw = np.arctan2(R[1, 0], R[0, 0])
+    roll = np.arctan2(R[2, 1], R[2, 2])
+    cy, sy, cp, sp, cr, sr = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
+    Rz = np.array([[cy, -sy, 0], [sy, cy, 0], [0, 0, 1]])
+    Ry = np.array([[cp, 0, sp], [0, 1, 0], [-sp, 0, cp]])
+    Rx = np.array([[1, 0, 0], [0, cr, -sr], [0, sr, cr]])
+    dRz = np.array([[-sy, -cy, 0], [cy, -sy, 0], [0, 0, 0]])
+    dRy = np.array([[-sp, 0, cp], [0, 0, 0], [-cp, 0, -sp]])
+    dRx = np.array([[0, 0, 0], [0, -sr, -cr], [0, cr, -sr]])
+    return (yaw, pitch, roll), (dRz @ Ry @ Rx, Rz @ dRy @ Rx, Rz @ Ry @ dRx)
+
+
+def covariance_analytic(T, pt2pt=None, pt2pl=None):
+    """mp2p_icp::covariance with the Jacobian in closed form instead of central differences: the residual of a pairing is
+    R(yaw, pitch, roll) l + t - q, so d/d(x, y, z) = I and d/d(angle) = (dR/d angle) l; a point pairing gives three rows, a plane
+    pairing the one row n . (...).  cov = (A^T A)^-1 (no weights, like covariance()), diag(1e6) without pairings or when A^T A
+    is singular.  The
+    reference of the finite-difference implementations (C oracle, device): free of their step's truncation and rounding."""
+    T = np.asarray(T, np.float64)
+    if T.size == 12:
+        T = T44(T)
+    _, dR = ypr_jacobian(T)
+    rows = []
+    if pt2pt is not None and len(pt2pt[0]):
+        L = np.asarray(pt2pt[0], np.float32).astype(np.float64).reshape(-1, 3)
+        A = np.zeros((len(L), 3, 6))
+        A[:, :, :3] = np.eye(3)
+        for j in range(3):
+            A[:, :, 3 + j] = L @ dR[j].T
+        rows.append(A.reshape(-1, 6))
+    if pt2pl is not None and len(pt2pl[0]):
+        L = np.asarray(pt2pl[0], np.float32).astype(np.float64).reshape(-1, 3)
+        N = np.asarray(pt2pl[2], np.float32).astype(np.float64).reshape(-1, 3)
+        A = np.zeros((len(L), 6))
+        A[:, :3] = N
+        for j in range(3):
+            A[:, 3 + j] = np.einsum("ij,ij->i", N, L @ dR[j].T)
+        rows.append(A)
+    if not rows:
+        return np.eye(6) * 1e6
+    A = np.concatenate(rows)
+    return inverse_or_unknown(A.T @ A)
 
 
 def icp_align(m: VoxelMap, local_xyz, T_guess, thresholds, kernel_params, max_iterations, inner=2,

@@ -1,5 +1,6 @@
 """-m gpu: a short run of every randomized parity tool under tools/ (each compares the HIP path with the CPU oracle -- or a
-batch with its jobs run one by one -- on seeded random inputs; the long runs are quoted in DESIGN.md section 5).  The seeds
+batch with its jobs run one by one -- on seeded random inputs; the long runs are quoted in DESIGN.md section 5; fuzz_align.py
+and fuzz_batch.py also draw the pairing weights and the covariance's angular step, case by case and job by job).  The seeds
 differ from the ones used while developing, so every round-end run also covers cases nobody has looked at."""
 import os
 import subprocess

@@ -2,7 +2,8 @@
 
 Bars (north_star): bit-exact for the integer/index work (voxel contents, NN indices, fp32 d^2,
 pair counts, termination); fp64 solver quantities to ~1e-9 relative; final poses far inside the
-1e-4 m / 1e-4 rad tolerance (asserted at 1e-7)."""
+1e-4 m / 1e-4 rad tolerance (asserted at 1e-7).  The solver's scalar parameters (pairing weights, covariance steps) off their
+defaults: tests/test_gpu_solver_params.py, on the workloads and helpers of this file."""
 import numpy as np
 import pytest
 

@@ -597,3 +597,51 @@ def test_layer_weight_other_than_one_is_a_device_input(hl, oracle, small_workloa
         np.testing.assert_allclose(res.pose(), o["T"], atol=1e-7)
         poses[weight] = np.asarray(res.pose())
     assert np.abs(poses[1.0] - poses[3.0]).max() > 1e-4  # the weight matters against a prior
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("generic", [False, True])
+def test_ndt_pipeline_with_two_different_layer_weights_matches_oracle(hl, oracle, generic):
+    """lidar3d-ndt-hip.yaml with `weight: 0.4` on Matcher_Point2Plane's pointLayerMatches entry and `weight: 2.5` on the point
+    matcher's: ICP::align_fused hands the first to mh_gn_params::weight_pt2pl and the second to weight_pt2pt.  Plane rows and
+    point rows share one solve, so the pair of weights moves the pose without a prior: against the oracle with the same two
+    weights -- and, from the oracle alone, more than 1e-4 away from both the unit-weight pose and the swapped pair's."""
+    yaml = open(OUR_NDT_YAML).read()
+    assert yaml.count("weight: 1.0") == 2
+    yaml = yaml.replace("weight: 1.0", "weight: 0.4", 1).replace("weight: 1.0", "weight: 2.5", 1)
+    assert yaml.index("weight: 0.4") < yaml.index("Matcher_Points_DistanceThreshold") < yaml.index("weight: 2.5")
+    pts = synth.ndt_cloud(21)
+    scan = pts[np.random.default_rng(23).permutation(len(pts))[:4000]]
+    cfg = hl.Config.FromYamlText(yaml)["icp_settings_with_vel"]
+    icp, params = hl.icp_pipeline_from_yaml(cfg)
+    src = hl.ParameterSource()
+    sigma = 0.5
+    src.updateVariable("ADAPTIVE_THRESHOLD_SIGMA", sigma)
+    icp.attachToParameterSource(src)
+    icp.forceGenericPath(generic)
+    params.maxIterations = 60
+    g = hl.metric_map_t()
+    ndt = hl.NDT(1.0, 0, 0.2, 0.05)
+    ndt.setPoints(pts)
+    g.set_layer("localmap", ndt)
+    l = hl.metric_map_t()
+    l.set_layer("decimated_for_icp", hl.PointCloud(scan))
+    guess_ypr = [0.10, -0.08, 0.05, 0.008, -0.004, 0.005]
+    res = icp.align(l, g, hl.TPose3D(*guess_ypr), params)
+    assert icp.lastAlignUsedFusedPath() == (not generic)
+    om = oracle.Map(1.0, 0, 0, 0.2, 0.05, 4).insert(pts)
+    thr, kp = synth.threshold_schedule(sigma, 60)
+
+    def ref(w_pt2pt, w_pt2pl):
+        return oracle.icp_align(om, scan, oracle.pose_from_ypr(guess_ypr), oracle.ICPParams(
+            max_iterations=60, min_abs_step_trans=5e-4, min_abs_step_rot=5e-4, threshold=thr, kernel_param=kp,
+            pt2pl_threshold=1.0 * sigma, gn=oracle.GNParams(max_inner_iterations=1, weight_pt2pt=w_pt2pt, weight_pt2pl=w_pt2pl)))
+
+    o = ref(2.5, 0.4)
+    assert np.abs(o["T"] - ref(1.0, 1.0)["T"]).max() > 1e-4 and np.abs(o["T"] - ref(0.4, 2.5)["T"]).max() > 1e-4
+    assert res.nIterations == o["n_iterations"]
+    assert res.terminationReason.name == oracle.TERM_NAMES[o["termination_reason"]]
+    np.testing.assert_allclose(res.pose(), o["T"], atol=1e-7)
+    assert res.n_pairs() == o["n_final_pairs"] and res.n_pairs_pt2pl() == o["n_final_pairs_pt2pl"] > 500
+    assert res.quality == o["quality"]
+    np.testing.assert_allclose(np.reshape(res.cov(), (6, 6)), o["cov"], rtol=2e-5, atol=1e-6 * np.abs(o["cov"]).max())

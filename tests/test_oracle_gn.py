@@ -1,7 +1,9 @@
-"""Gauss-Newton solver / covariance of the C oracle vs the independent numpy oracle."""
+"""Gauss-Newton solver / covariance of the C oracle vs the independent numpy oracle; both covariances vs the
+closed form of the Jacobian, which gives the bound tests/test_gpu_solver_params.py holds the device to."""
 import numpy as np
 import pytest
 
+from cov_cases import COV_FD_BOUND, COV_KINDS, COV_POSES, cov_inputs, scaled_gap
 from oracle import icp_oracle_np as onp
 
 
@@ -124,3 +126,76 @@ def test_covariance_matches_numpy(oracle):
     assert np.all(np.linalg.eigvalsh(cov) > 0)
     cov0, _ = oracle.covariance(onp.T12(Tt), (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)))
     np.testing.assert_array_equal(cov0, np.eye(6) * 1e6)
+
+
+# ---------------------------------------------------------------------------- covariance against the closed form
+@pytest.mark.parametrize("kind", COV_KINDS)
+@pytest.mark.parametrize("n", [40, 257, 5000])
+@pytest.mark.parametrize("spread", [10.0, 60.0])
+def test_covariance_matches_the_closed_form(oracle, kind, n, spread):
+    """Both finite-difference covariances against the closed-form Jacobian of R(yaw, pitch, roll) l + t: point pairings,
+    plane pairings and both, at poses far from the small angles of an alignment.  The numpy oracle takes points only."""
+    pp, pl = cov_inputs(kind, n, spread)
+    for x in COV_POSES:
+        T = onp.pose_from_ypr(x)
+        ref = onp.covariance_analytic(T, pp, pl)
+        assert np.all(np.linalg.eigvalsh(ref) > 0)
+        cov, _ = oracle.covariance(onp.T12(T), pp, pl)
+        gap = scaled_gap(cov, ref)
+        print("C oracle vs closed form: %s n=%d spread=%g pose=%s scaled gap %.3e" % (kind, n, spread, x[3:], gap))
+        assert gap < COV_FD_BOUND
+        if kind == "points":
+            assert scaled_gap(onp.covariance(T, pp), ref) < COV_FD_BOUND
+    # the closed form is the plain Jacobian of pose_from_ypr: the angles read back from T are the ones that built it
+    (yaw, pitch, roll), _ = onp.ypr_jacobian(onp.pose_from_ypr(COV_POSES[1]))
+    np.testing.assert_allclose([yaw, pitch, roll], COV_POSES[1][3:], rtol=0, atol=1e-15)
+
+
+def test_covariance_closed_form_without_pairings():
+    e = np.zeros((0, 3), np.float32)
+    np.testing.assert_array_equal(onp.covariance_analytic(np.eye(4)), np.eye(6) * 1e6)
+    np.testing.assert_array_equal(onp.covariance_analytic(np.eye(4), (e, e), (e, e, e)), np.eye(6) * 1e6)
+
+
+@pytest.mark.parametrize("kind", COV_KINDS)
+@pytest.mark.parametrize("n", [40, 257, 5000])
+def test_covariance_angular_step_is_visible(oracle, kind, n):
+    """findif_ang = 0.05 leaves the truncation term of the central difference (h^2 / 6 = 4.2e-4 of every angular column,
+    twice that in the covariance): far above the bound the default steps are held to, so a test that hands the device
+    distinct steps sees a swapped or dropped one."""
+    for spread in (10.0, 60.0):
+        pp, pl = cov_inputs(kind, n, spread)
+        for x in COV_POSES:
+            T = onp.pose_from_ypr(x)
+            ref = onp.covariance_analytic(T, pp, pl)
+            cov, _ = oracle.covariance(onp.T12(T), pp, pl, 1e-7, 0.05)
+            rel = float(np.max(np.abs(cov - ref) / np.abs(ref)))
+            assert 20 * COV_FD_BOUND < rel < 1e-3, rel
+            assert scaled_gap(cov, ref) > 20 * COV_FD_BOUND
+            # and the translational step alone: 1e-3 is exact for a residual linear in t, up to rounding
+            cov_x, _ = oracle.covariance(onp.T12(T), pp, pl, 1e-3, 1e-7)
+            assert scaled_gap(cov_x, ref) < COV_FD_BOUND
+
+
+@pytest.mark.parametrize("w", [(0.3, 1.0), (1.0, 4.0), (0.3, 4.0)])
+@pytest.mark.parametrize("kernel", [0, 1, 4])
+def test_weighted_H_g_match_numpy(oracle, w, kernel):
+    """weight_pt2pt and weight_pt2pl off 1 on point pairs and plane pairs together: the C oracle against the numpy one."""
+    rng = np.random.default_rng(40 + kernel)
+    l, q, _ = make_pairs(rng)
+    pl = make_planes(rng)
+    T0 = onp.se3_exp(np.concatenate([rng.normal(0, 0.1, 3), rng.normal(0, 0.01, 3)]))
+    p = oracle.GNParams(max_inner_iterations=2, robust_kernel=kernel, robust_kernel_param=0.7, weight_pt2pt=w[0], weight_pt2pl=w[1])
+    T1, n, steps = oracle.gn_solve(onp.T12(T0), (l, q), pl, p)
+    T_ref, steps_ref = onp.gn_solve(T0, (l, q), pl, 2, kernel, 0.7, w_pt2pt=w[0], w_pt2pl=w[1])
+    assert n == 2
+    for a, b in zip(steps, steps_ref):
+        np.testing.assert_allclose(a["H"], b["H"], rtol=1e-11, atol=1e-9)
+        np.testing.assert_allclose(a["g"], b["g"], rtol=1e-10, atol=1e-9)
+        np.testing.assert_allclose(a["err_norm_sqr"], b["cost"], rtol=1e-12)
+        np.testing.assert_allclose(a["delta"], b["delta"], rtol=1e-8, atol=1e-11)
+    np.testing.assert_allclose(onp.T44(T1), T_ref, atol=1e-10)
+    # the weights are not a common factor: the step differs from the unweighted one
+    _, _, plain = oracle.gn_solve(onp.T12(T0), (l, q), pl, oracle.GNParams(max_inner_iterations=2, robust_kernel=kernel,
+                                                                           robust_kernel_param=0.7))
+    assert np.abs(plain[0]["delta"] - steps[0]["delta"]).max() > 1e-4

@@ -1,7 +1,8 @@
 """development aid: random alignments with everything the solver side takes -- robust kernel forms, 1-4 inner Gauss-Newton
-steps, min_delta / max_cost, priors, the device hook, stall thresholds, polling intervals, point maps and NDT maps
-(Matcher_Point2Plane riding along) -- against the CPU oracle: iteration count, termination reason, pair counts per
-iteration, final pairing indices bit for bit (d2 to the last fp32 bit), poses to 1e-7 (POSE_TOL of tests/test_gpu_parity.py)."""
+steps, min_delta / max_cost, the two pairing weights, priors, the device hook, stall thresholds, polling intervals, the angular
+step of the covariance, point maps and NDT maps (Matcher_Point2Plane riding along) -- against the CPU oracle: iteration count,
+termination reason, pair counts per iteration, final pairing indices bit for bit (d2 to the last fp32 bit), poses to 1e-7
+(POSE_TOL of tests/test_gpu_parity.py), the covariance to 2e-5 (the bar of test_covariance_matches_oracle)."""
 import os
 import sys
 
@@ -39,10 +40,11 @@ for case in range(n_cases):
     inner = int(rng.choice([1, 2, 2, 4]))
     kernel = int(rng.integers(0, 6))
     gkw = dict(max_inner_iterations=inner, robust_kernel=kernel, min_delta=float(rng.choice([0.0, 1e-7, 1e-4])),
-               max_cost=float(rng.choice([0.0, 0.0, 1e-3])))
+               max_cost=float(rng.choice([0.0, 0.0, 1e-3])), weight_pt2pt=float(rng.choice([1.0, 1.0, 0.25, 3.0])),
+               weight_pt2pl=float(rng.choice([1.0, 1.0, 0.25, 3.0])))
     kw = dict(max_iterations=iters, threshold=thr, kernel_param=kp, disable_stall_test=bool(rng.integers(0, 3) == 0),
               min_abs_step_trans=float(rng.choice([1e-4, 5e-4])), min_abs_step_rot=float(rng.choice([1e-4, 5e-4])),
-              threshold_angular_deg=float(rng.choice([0.0, 0.0, 0.5])))
+              threshold_angular_deg=float(rng.choice([0.0, 0.0, 0.5])), cov_findif_ang=float(rng.choice([1e-7, 1e-7, 1e-3])))
     if ndt:
         kw["pt2pl_threshold"] = float(rng.choice([0.3, 0.6]))
     if rng.integers(0, 4) == 0:
@@ -67,15 +69,17 @@ for case in range(n_cases):
               # coordinate on a rounding boundary may differ in its last bit (<= 8e-6 m at 100 m) and d2 by 2 |d| times that
               # -- anything more is a mismatch
               bool(np.all(np.abs(a["pairs"]["d2"] - b["pairs"]["d2"]) <= 2e-5 * np.sqrt(b["pairs"]["d2"]) + 1e-12)) and
-              float(np.abs(a["T"] - b["T"]).max()) < 1e-7 and a["quality"] == b["quality"])
+              float(np.abs(a["T"] - b["T"]).max()) < 1e-7 and a["quality"] == b["quality"] and
+              bool(np.allclose(a["cov"], b["cov"], rtol=2e-5, atol=1e-6 * np.abs(b["cov"]).max())))
         note = "iters %d term %s pairs %d" % (a["n_iterations"], capi.TERM_NAMES[a["termination_reason"]], a["n_final_pairs"])
         if not ok:
             ta, tb = [t["n_pairs"] for t in a["trace"]], [t["n_pairs"] for t in b["trace"]]
             first = next((i for i, (x, y) in enumerate(zip(ta, tb)) if x != y), None)
-            note += " | oracle iters %d term %s pairs %d; first differing iteration %s (%s vs %s); max |dT| %.3e; pairs equal %s; quality %r vs %r" % (
+            note += " | oracle iters %d term %s pairs %d; first differing iteration %s (%s vs %s); max |dT| %.3e; pairs equal %s; quality %r vs %r; max |dcov| / max |cov| %.3e" % (
                 b["n_iterations"], capi.TERM_NAMES[b["termination_reason"]], b["n_final_pairs"], first,
                 ta[first] if first is not None else None, tb[first] if first is not None else None, float(np.abs(a["T"] - b["T"]).max()),
-                [bool(np.array_equal(a["pairs"][k], b["pairs"][k])) for k in ("local_idx", "global_idx", "d2")], a["quality"], b["quality"])
+                [bool(np.array_equal(a["pairs"][k], b["pairs"][k])) for k in ("local_idx", "global_idx", "d2")], a["quality"], b["quality"],
+                float(np.abs(a["cov"] - b["cov"]).max() / np.abs(b["cov"]).max()))
             if len(a["pairs"]["d2"]) == len(b["pairs"]["d2"]) and len(a["pairs"]["d2"]):
                 dd = np.abs(a["pairs"]["d2"] - b["pairs"]["d2"])
                 k = int(dd.argmax())
@@ -85,8 +89,8 @@ for case in range(n_cases):
     except capi.MolahipError as e:
         ok, note = False, "ERROR " + str(e)[-80:]
     bad += 0 if ok else 1
-    print("case %3d ndt=%d n=%5d inner=%d kernel=%d min_delta=%g max_cost=%g stall_off=%d hook=%d prior=%d poll=%2d match=%-1s %s -> %s" % (
-        case, ndt, n_scan, inner, kernel, gkw["min_delta"], gkw["max_cost"], kw["disable_stall_test"], "hook_enabled" in kw,
-        prior is not None, poll, m, note, "ok" if ok else "MISMATCH"), flush=True)
+    print("case %3d ndt=%d n=%5d inner=%d kernel=%d min_delta=%g max_cost=%g w=(%g, %g) cov_ang=%g stall_off=%d hook=%d prior=%d poll=%2d match=%-1s %s -> %s" % (
+        case, ndt, n_scan, inner, kernel, gkw["min_delta"], gkw["max_cost"], gkw["weight_pt2pt"], gkw["weight_pt2pl"], kw["cov_findif_ang"],
+        kw["disable_stall_test"], "hook_enabled" in kw, prior is not None, poll, m, note, "ok" if ok else "MISMATCH"), flush=True)
 print("mismatches:", bad)
 sys.exit(1 if bad else 0)

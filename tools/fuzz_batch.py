@@ -1,6 +1,6 @@
 """development aid: random batches (2-10 jobs; layers of 300-60 k points = every lock-step kernel chain and the per-stream
-fallback; point maps and an NDT map; per-job budgets, schedules, solver settings, priors, hooks, stall test, final pairings) through mh_icp_align_batch against the same
-jobs run one by one: results bitwise equal."""
+fallback; point maps and an NDT map; per-job budgets, schedules, solver settings, pairing weights, covariance steps, priors, hooks,
+stall test, final pairings) through mh_icp_align_batch against the same jobs run one by one: results bitwise equal."""
 import os
 import sys
 
@@ -41,9 +41,11 @@ for case in range(n_cases):
         if rng.integers(0, 4) == 0:
             extra.update(hook_enabled=True, hook_min_trans=float(rng.choice([0.05, 0.2])), hook_min_rot=float(np.deg2rad(0.75)))
         gn = capi.GNParams(max_inner_iterations=int(rng.choice([1, 2, 2, 4])), robust_kernel=int(rng.integers(0, 6)),
-                           min_delta=float(rng.choice([0.0, 1e-7, 1e-4])), max_cost=float(rng.choice([0.0, 0.0, 1e-3])))
+                           min_delta=float(rng.choice([0.0, 1e-7, 1e-4])), max_cost=float(rng.choice([0.0, 0.0, 1e-3])),
+                           weight_pt2pt=float(rng.choice([1.0, 1.0, 0.25, 3.0])), weight_pt2pl=float(rng.choice([1.0, 1.0, 0.25, 3.0])))
         ps.append(capi.ICPParams(max_iterations=iters, threshold=thr, kernel_param=kp, disable_stall_test=bool(rng.integers(0, 2)),
-                                 poll_every=int(rng.choice([0, 4, iters])), gn=gn, **extra))
+                                 poll_every=int(rng.choice([0, 4, iters])), gn=gn,
+                                 cov_findif_ang=float(rng.choice([1e-7, 1e-7, 1e-3])), **extra))
         priors.append((guesses[-1], np.diag([4.0, 4.0, 4.0, 100.0, 100.0, 100.0])) if rng.integers(0, 4) == 0 else None)
     singles = []
     for j, (m, s, g, p, pr) in enumerate(zip(jm, scans, guesses, ps, priors)):
