@@ -200,12 +200,12 @@ mh_status mh_ctx_destroy(mh_ctx* ctx) {
   if (ctx->d_state) (void)hipFree(ctx->d_state);
   if (ctx->h_state) (void)hipHostFree(ctx->h_state);
   if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-  if (ctx->h_pp) (void)hipHostFree(ctx->h_pp);
-  if (ctx->h_sched) (void)hipHostFree(ctx->h_sched);
-  if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+  ctx->h_pp.release();
+  ctx->h_sched.release();
+  ctx->h_batch.release();
   ctx->layers_pairs.release();
   ctx->layers_tab.release();
-  if (ctx->h_layers) (void)hipHostFree(ctx->h_layers);
+  ctx->h_layers.release();
   ctx->batch_desc.release();
   ctx->batch_states.release();  // d_params / h_params point into the state blocks
   if (ctx->ev_poll) (void)hipEventDestroy(ctx->ev_poll);

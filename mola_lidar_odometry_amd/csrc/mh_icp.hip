@@ -16,6 +16,8 @@
 //                                  kernel bodies: matchers, accumulation, Gauss-Newton step + loop tail, the small layer's loops, covariance, pairings
 //   mh_k_launch.h                  their __global__ entry points (single alignment | one job per blockIdx.y)
 //   this file                      AlignJob: the chain a layer takes, loop control (one-launch loop | streaming | chunks + hipGraph), mh_icp_align
+//   mh_icp_job.inl                 what AlignJob and LayersJob share: result / state / solver set-up, graph cache, result read-back
+//   mh_icp_layers.inl, mh_icp_layers_batch.inl   LayersJob, mh_icp_align_layers, mh_icp_align_layers_batch
 //   mh_icp_batch.inl               mh_icp_align_batch (lock-step groups)
 //   mh_icp_api.inl                 matcher- / solver-granular entry points (mh_nn_search*, mh_gn_solve, mh_covariance)
 //   mh_dev_variants.h              (-DMH_DEV_VARIANTS only) the tile / wave / sorted-scan matchers that lost to the product kernels
@@ -385,6 +387,8 @@ constexpr uint32_t kStreamLead = 2;   // iterations a streaming alignment keeps 
 constexpr uint32_t kChunkMargin = 2;  // iterations the first chunk adds to the expected count
 constexpr uint32_t kChunkNext = 6;    // iterations of the chunks after the first (automatic polling)
 
+#include "mh_icp_job.inl"  // set-up, graph cache and read-back shared with LayersJob
+
 // One alignment in flight on one context: enqueue / poll state machine shared by mh_icp_align and
 // mh_icp_align_batch.
 struct AlignJob {
@@ -416,19 +420,17 @@ struct AlignJob {
   bool loop16 = false;         // run_loop16(): the whole loop of a small layer in ONE launch (plan.loop: k_icp16 / k_icpw)
   bool forbid_loop16 = false;  // ... not for this job: the second attempt after a loop whose workgroups gave up
   LoopAdmission loop_adm;      // what this job holds of the device's admission count while its loop runs
+  LoopExchange loop_x;         // ... its exchange block and serial numbers
+  uint32_t loop_steps = 0;     // ... and the Gauss-Newton steps it may take
+
+  uint64_t potential() const { return scan->n * (pl ? 2u : 1u); }  // every matcher adds its layer size (App.B U6)
 
   mh_status start(const Switches& switches, const mh_map* m, const mh_scan* sc, const mh_icp_params* prm, const double* T0,
                   const mh_prior* prior, mh_icp_result* r, mh_icp_iter* tr, size_t batch_index = 0) {
     sw = &switches; map = m; scan = sc; ctx = sc->ctx; p = prm; res = r; trace = tr;
     prof = prm->profile == 1 || (prm->profile == 2 && batch_index == 0);
     pl = prm->pt2pl_threshold != nullptr;
-    memset(res, 0, sizeof(*res));
-    for (int i = 0; i < 12; i++) res->T[i] = T0[i];
-    for (int i = 0; i < 6; i++) res->cov[i * 7] = 1e6;
-    res->potential_pairings = scan->n * (pl ? 2u : 1u);  // every matcher adds its layer size (App.B U6)
-    if (p->max_iterations == 0 || scan->n == 0) {
-      // ICP::align with nothing to iterate on: no pairings, quality 0, cov = diag(1e6)
-      res->termination_reason = p->max_iterations == 0 ? MH_TERM_MAX_ITERATIONS : MH_TERM_NO_PAIRINGS;
+    if (begin_result(res, p, T0, potential())) {
       finished = trivial = true;
       return MH_OK;
     }
@@ -447,40 +449,27 @@ struct AlignJob {
     MH_TRY(ctx->sched.reserve(3 * mi * sizeof(double)));
     {  // threshold | kernel_param | pt2pl_threshold schedules: packed in a pinned staging block, one upload
       const size_t nsched = (pl ? 3 : 2) * mi;
-      if (ctx->h_sched_cap < nsched) {
-        if (ctx->h_sched) (void)hipHostFree(ctx->h_sched);
-        ctx->h_sched = nullptr;
-        ctx->h_sched_cap = 0;
-        MH_HIP(hipHostMalloc((void**)&ctx->h_sched, 3 * mi * sizeof(double), hipHostMallocDefault));
-        ctx->h_sched_cap = 3 * mi;
-      }
-      memcpy(ctx->h_sched, p->threshold, mi * sizeof(double));
-      memcpy(ctx->h_sched + mi, p->kernel_param, mi * sizeof(double));
+      MH_TRY(ctx->h_sched.reserve(3 * mi * sizeof(double)));
+      double* const h_sched = ctx->h_sched.as<double>();
+      memcpy(h_sched, p->threshold, mi * sizeof(double));
+      memcpy(h_sched + mi, p->kernel_param, mi * sizeof(double));
       if (pl) {  // MH_PT2PL_CENTROID_DISTANCE travels as a negative threshold (pl_accept)
         const double sgn = p->pt2pl_mode == MH_PT2PL_CENTROID_DISTANCE ? -1.0 : 1.0;
-        for (size_t k = 0; k < mi; k++) ctx->h_sched[2 * mi + k] = sgn * fabs(p->pt2pl_threshold[k]);
+        for (size_t k = 0; k < mi; k++) h_sched[2 * mi + k] = sgn * fabs(p->pt2pl_threshold[k]);
       }
       nsched_pending = nsched;
       // a single alignment whose schedules fit behind the parameter block: they travel with it (one copy, below)
       inline_sched = (!defer_upload && nsched <= kInlineSchedDoubles) ? nsched : 0;
       if (inline_sched)
-        memcpy(reinterpret_cast<char*>(ctx->h_state) + kInlineSchedOffset, ctx->h_sched, nsched * sizeof(double));
+        memcpy(reinterpret_cast<char*>(ctx->h_state) + kInlineSchedOffset, h_sched, nsched * sizeof(double));
       else if (!defer_upload)
-        MH_HIP(hipMemcpyAsync(ctx->sched.p, ctx->h_sched, nsched * sizeof(double), hipMemcpyHostToDevice, s));
+        MH_HIP(hipMemcpyAsync(ctx->sched.p, h_sched, nsched * sizeof(double), hipMemcpyHostToDevice, s));
     }
     if (trace) MH_TRY(ctx->trace.reserve(mi * sizeof(mh_icp_iter)));
-    ctx->align_serial++;
-    init_state(ctx->h_state, T0);
-    // k_step16's hand-over: the uploaded block carries this alignment's epoch, every launch one more (a launch told what to
-    // expect waits for exactly that block: neither the previous alignment's nor the launch before last's will do)
-    serial_base = ((uint32_t)ctx->align_serial & 0x3FFu) << 22;
+    const double ang = p->threshold_angular_deg * 3.14159265358979323846 / 180.0;
+    serial_base = begin_state(ctx, T0, p->threshold[0], (float)(ang * ang), p->kernel_param[0]);  // uploaded together with the parameters below
     step_launches = 0;
     step_total = 0;
-    ctx->h_state->serial = serial_base;
-    const double ang = p->threshold_angular_deg * 3.14159265358979323846 / 180.0;
-    ctx->h_state->cur_thr2 = (float)(p->threshold[0] * p->threshold[0]);
-    ctx->h_state->cur_ang2 = (float)(ang * ang);
-    ctx->h_state->cur_kparam = p->kernel_param[0];  // uploaded together with the parameters below
 
     double* const sched_dev = inline_sched ? reinterpret_cast<double*>(reinterpret_cast<char*>(ctx->d_state) + kInlineSchedOffset)
                                            : ctx->sched.as<double>();
@@ -492,31 +481,7 @@ struct AlignJob {
     mk.w_pt2pl = p->gn.weight_pt2pl;
     mk.pl_thr = pl ? sched_dev + 2 * mi : nullptr;
     mk.skip_pl_paired = (pl && p->matched_points == MH_MATCHED_POINTS_SKIP) ? 1u : 0u;
-    memset(&sk, 0, sizeof(sk));
-    sk.max_iterations = p->max_iterations;
-    sk.disable_stall = p->disable_stall_test;
-    sk.max_inner = p->gn.max_inner_iterations;
-    sk.min_step_trans = p->min_abs_step_trans;
-    sk.min_step_rot = p->min_abs_step_rot;
-    sk.min_delta = p->gn.min_delta;
-    sk.max_cost = p->gn.max_cost;
-    sk.hook_enabled = p->hook_enabled;
-    sk.hook_trans = p->hook_min_trans;
-    sk.hook_rot = p->hook_min_rot;
-    sk.hook_cos_rot = (p->hook_min_rot > 0.0 && p->hook_min_rot < 3.0) ? cos(p->hook_min_rot) : __builtin_nan("");
-    if (p->hook_enabled) {
-      Pose C;
-      for (int i = 0; i < 12; i++) C.m[i] = p->hook_checkpoint[i];
-      const Pose Ci = inverse(C);
-      for (int i = 0; i < 12; i++) sk.hook_chk_inv[i] = Ci.m[i];
-    }
-    fill_prior(sk, prior);
-    sk.thr = mk.thr;
-    sk.kparam = mk.kparam;
-    sk.trace = trace ? ctx->trace.as<mh_icp_iter>() : nullptr;
-    sk.gn_trace = nullptr;
-    sk.cov_hx = p->cov_findif_xyz;
-    sk.cov_ha = p->cov_findif_ang;
+    sk = make_solve_params(p, prior, mk, trace ? ctx->trace.as<mh_icp_iter>() : nullptr);
     plan = plan_alignment(*sw, scan->n, pl, p->matched_points, map, prof,
                           p->poll_every == 0 && !defer_upload && ctx->d_progress != nullptr);
     if (plan.dev_matcher)
@@ -556,10 +521,9 @@ struct AlignJob {
         MH_TRY(map_ensure_qidx(*sw, map, ctx->stream));
         if (!map->view(*sw).pts_q) return fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (k_icpw needs it)");
       }
-      if (ctx->loop_x.bytes < kLoopExchangeBytes) {
-        MH_TRY(ctx->loop_x.reserve(kLoopExchangeBytes));
-        (void)hipMemsetAsync(ctx->loop_x.p, 0, kLoopExchangeBytes, s);
-      }
+      // (MH_LOOP16_TEST_ABANDON: the loop is cut short as if its workgroups had given up -- the caller's second attempt is what is tested)
+      loop_steps = sw->loop16_test_abandon ? 1u : p->max_iterations * p->gn.max_inner_iterations + 1u;
+      MH_TRY(loop_exchange(ctx, s, loop_steps, loop_x));
     }
     if (defer_upload) {
       ctx->h_params->mk = mk;
@@ -567,18 +531,9 @@ struct AlignJob {
     } else {
       MH_TRY(upload_state_and_params(ctx, mk, sk, inline_sched));
     }
-    // poll_every == 0: the first chunk is sized by what the previous alignment of this context needed (consecutive scans
-    // of a sequence converge in about as many iterations: one host round trip instead of three), later chunks are short
     auto_chunk = p->poll_every == 0;
-    // Every early-exit launch enqueued beyond the end of the loop costs ~1.5 us of stream time and every extra host poll
-    // ~25 us, so the first chunk should be as long as the loop will run: the caller's estimate when it has one (the
-    // odometry driver's calls alternate between short ones that the hook stops and long ones that converge, and it knows
-    // which kind it is making), else what this context's previous alignment needed.
     kind = 0;
-    {
-      const uint32_t expect = p->expected_iterations ? p->expected_iterations : ctx->predicted_iterations[kind];
-      chunk = p->poll_every ? p->poll_every : (expect ? (expect + kChunkMargin > 64 ? 64u : expect + kChunkMargin) : 10u);
-    }
+    chunk = first_chunk(p, ctx->predicted_iterations[kind]);
     polls = 0;
     enqueued = 0;
     prof_n = 0;
@@ -602,7 +557,7 @@ struct AlignJob {
   mh_status flush_deferred() {
     if (!defer_upload || finished) return MH_OK;
     MH_TRY(set_device(ctx));
-    MH_HIP(hipMemcpyAsync(ctx->sched.p, ctx->h_sched, nsched_pending * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    MH_HIP(hipMemcpyAsync(ctx->sched.p, ctx->h_sched.p, nsched_pending * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     MH_HIP(hipMemcpyAsync(ctx->d_state, ctx->h_state, kParamsOffset + sizeof(IcpDeviceParams), hipMemcpyHostToDevice,
                           ctx->stream));
     defer_upload = false;
@@ -617,26 +572,23 @@ struct AlignJob {
     hipStream_t s = ctx->stream;
     const uint32_t n = (uint32_t)scan->n;
     const uint32_t ngr = (n + kStepPoints - 1) / kStepPoints;
-    // (MH_LOOP16_TEST_ABANDON: the loop is cut short as if its workgroups had given up -- the caller's second attempt is what is tested)
-    const uint32_t max_steps = sw->loop16_test_abandon ? 1u : p->max_iterations * p->gn.max_inner_iterations + 1u;
-    const uint32_t serial0 = ctx->loop_serial;
-    ctx->loop_serial += max_steps + 2u;
+    const uint32_t max_steps = loop_steps, serial0 = loop_x.serial0;
     g_loop16_runs.fetch_add(1);
-    char* const xa = static_cast<char*>(ctx->loop_x.p);
-    char* const xb = xa + 2 * (size_t)kAccN * kLoopRowStride * 16;
+    void* const xa = loop_x.xa;
+    void* const xb = loop_x.xb;
     const MapView mv = map->view(*sw);
     if (plan.loop == Loop::Icpw)
       hipLaunchKernelGGL(k_icpw, dim3((ngr + kLwGroups - 1) / kLwGroups), dim3(kLwThreads), 0, s, ctx->d_state, &ctx->d_params->mk,
                          &ctx->d_params->sk, scan->x, scan->y, scan->z, n, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(),
-                         (void*)xa, ngr, serial0, max_steps, p->compute_covariance ? 1u : 0u);
+                         xa, ngr, serial0, max_steps, p->compute_covariance ? 1u : 0u);
     else if (pl)
       hipLaunchKernelGGL(k_icp16<true>, dim3(ngr), dim3(kSolveThreads), 0, s, ctx->d_state, &ctx->d_params->mk, &ctx->d_params->sk, scan->x,
                          scan->y, scan->z, n, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), ctx->pl_c.as<float4>(),
-                         ctx->pl_n.as<float4>(), (void*)xa, (void*)xb, ngr, serial0, max_steps, p->compute_covariance ? 1u : 0u);
+                         ctx->pl_n.as<float4>(), xa, xb, ngr, serial0, max_steps, p->compute_covariance ? 1u : 0u);
     else
       hipLaunchKernelGGL(k_icp16<false>, dim3(ngr), dim3(kSolveThreads), 0, s, ctx->d_state, &ctx->d_params->mk, &ctx->d_params->sk, scan->x,
                          scan->y, scan->z, n, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), (float4*)nullptr,
-                         (float4*)nullptr, (void*)xa, (void*)xb, ngr, serial0, max_steps, p->compute_covariance ? 1u : 0u);
+                         (float4*)nullptr, xa, xb, ngr, serial0, max_steps, p->compute_covariance ? 1u : 0u);
     enqueued = p->max_iterations;
     skip_tail = false;
     MH_TRY(enqueue_tail(/*cov_prepared=*/true));
@@ -809,35 +761,17 @@ struct AlignJob {
       // under streaming control only once the iteration budget is queued (a loop that ends earlier is seen by the next launch)
       if (step_chain && (!skip_tail || enqueued + m >= p->max_iterations)) launch_step(1u);
       if (skip_tail) return MH_OK;  // streaming: the tail below is enqueued once, by enqueue_tail()
-      if (p->compute_covariance) {  // no-ops unless the loop has terminated
-        hipLaunchKernelGGL(k_cov_prepare, dim3(1), dim3(64), 0, s, ctx->d_state, dsk, 0u);
-        hipLaunchKernelGGL(k_cov_accum, dim3(nb), dim3(kBlock), 0, s, ctx->d_state, 0u, scan->x, scan->y, scan->z, n,
-                           ctx->pair_gidx.as<uint32_t>(), part, nb);
-        if (pl)
-          hipLaunchKernelGGL(k_cov_accum_plbuf, dim3(nb), dim3(kBlock), 0, s, ctx->d_state, scan->x, scan->y, scan->z, n,
-                             ctx->pl_c.as<float4>(), ctx->pl_n.as<float4>(), partb, nb);
-        hipLaunchKernelGGL(k_cov_finalize, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, 0u, part, nb, nb,
-                           (const double*)partb, pl ? nb : 0u, pl ? nb : 0u);  // (the covariance kernels write nb columns)
-      }
-      MH_HIP(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(IcpDeviceState), hipMemcpyDeviceToHost, s));
-      return MH_OK;
+      return enqueue_cov_and_state(false);
     };
-    if (prof || sw->no_graph || streaming) {
-      MH_TRY(enqueue_kernels());
-      MH_HIP(hipGetLastError());
-      if (streaming) {  // (no event per iteration: the progress word is the signal)
-        enqueued += m;
-        return MH_OK;
-      }
-    } else {
+    // (the launches of a streamed chunk follow the progress word, those of a profiled one carry events: never from a graph)
+    const bool direct = prof || sw->no_graph || streaming;
+    unsigned long long key[32] = {0};
+    if (!direct) {
       if (step_chain) {  // the serial number this chunk's first k_step16 launch has to find (its launches carry their place in the chunk)
         ctx->h_params->sk.step_base = serial_base + step_total;
         MH_HIP(hipMemcpyAsync(&ctx->d_params->sk.step_base, &ctx->h_params->sk.step_base, sizeof(uint32_t), hipMemcpyHostToDevice, s));
         step_total += m * p->gn.max_inner_iterations + ((!skip_tail || enqueued + m >= p->max_iterations) ? 1u : 0u);
       }
-      // The launch sequence only depends on sizes and device pointers (the per-alignment values sit in device
-      // memory), so it is captured once and replayed: one host call per chunk instead of ~4 per iteration.
-      unsigned long long key[32] = {0};
       uint32_t fb;
       memcpy(&fb, &mv.inv_vs, 4);
       const unsigned long long kv[] = {n, nb, nbm, (unsigned long long)mt, m, p->gn.max_inner_iterations,
@@ -856,47 +790,10 @@ struct AlignJob {
                                        (unsigned long long)mv.pts_q};  // (a word each: no XOR folding)
       static_assert(sizeof(kv) <= sizeof(key), "graph key too small");
       memcpy(key, kv, sizeof(kv));
-      const bool cached = ctx->graph_exec && memcmp(key, ctx->graph_key, sizeof(key)) == 0;
-      const bool seen_before = memcmp(key, ctx->graph_candidate, sizeof(key)) == 0 && ctx->graph_candidate_align != ctx->align_serial;
-      if (!cached && !seen_before) {
-        // a shape not seen in an earlier alignment: launch directly and remember it; it is captured when a later
-        // alignment brings it again.  (The real pipeline's ICP layer changes size with every scan: capturing and
-        // instantiating a graph per alignment cost 0.4 ms each.)
-        if (memcmp(key, ctx->graph_candidate, sizeof(key)) != 0) {
-          memcpy(ctx->graph_candidate, key, sizeof(key));
-          ctx->graph_candidate_align = ctx->align_serial;
-        }
-        MH_TRY(enqueue_kernels());
-        MH_HIP(hipGetLastError());
-        enqueued += m;
-        MH_HIP(hipEventRecord(ctx->ev_poll, s));
-        return MH_OK;
-      }
-      if (!cached) {
-        if (ctx->graph_exec) {
-          (void)hipGraphExecDestroy(ctx->graph_exec);
-          ctx->graph_exec = nullptr;
-        }
-        hipGraph_t g = nullptr;
-        MH_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const mh_status cs = enqueue_kernels();
-        const hipError_t ce = hipStreamEndCapture(s, &g);
-        if (cs != MH_OK) {
-          if (g) (void)hipGraphDestroy(g);
-          return cs;
-        }
-        if (ce != hipSuccess) return fail(MH_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-        const hipError_t ie = hipGraphInstantiate(&ctx->graph_exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (ie != hipSuccess) {
-          ctx->graph_exec = nullptr;
-          return fail(MH_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
-        }
-        memcpy(ctx->graph_key, key, sizeof(key));
-      }
-      MH_HIP(hipGraphLaunch(ctx->graph_exec, s));
     }
+    MH_TRY(enqueue_cached(ctx, direct, key, enqueue_kernels));
     enqueued += m;
+    if (streaming) return MH_OK;  // (no event per iteration: the progress word is the signal)
     if (prof) MH_HIP(hipEventRecord(ctx->ev_t1, s));
     MH_HIP(hipEventRecord(ctx->ev_poll, s));
     return MH_OK;
@@ -936,26 +833,32 @@ struct AlignJob {
     return poll();
   }
 
-  mh_status enqueue_tail(bool cov_prepared = false) {  // cov_prepared: k_icp16 has done k_cov_prepare's part
-    MH_TRY(set_device(ctx));
+  // the covariance kernels (no-ops unless the loop has terminated; cov_prepared: k_icp16 has done k_cov_prepare's part) and the
+  // state read-back: what ends every chunk the host is going to look at
+  mh_status enqueue_cov_and_state(bool cov_prepared) {
     hipStream_t s = ctx->stream;
     const uint32_t n = (uint32_t)scan->n;
     double* part = ctx->partials.as<double>();
     double* partb = pl ? ctx->partials_b.as<double>() : nullptr;
-    const SolveK* dsk = &ctx->d_params->sk;
     if (p->compute_covariance) {
-      if (!cov_prepared) hipLaunchKernelGGL(k_cov_prepare, dim3(1), dim3(64), 0, s, ctx->d_state, dsk, 0u);
+      if (!cov_prepared) hipLaunchKernelGGL(k_cov_prepare, dim3(1), dim3(64), 0, s, ctx->d_state, &ctx->d_params->sk, 0u);
       hipLaunchKernelGGL(k_cov_accum, dim3(nb), dim3(kBlock), 0, s, ctx->d_state, 0u, scan->x, scan->y, scan->z, n,
                          ctx->pair_gidx.as<uint32_t>(), part, nb);
       if (pl)
         hipLaunchKernelGGL(k_cov_accum_plbuf, dim3(nb), dim3(kBlock), 0, s, ctx->d_state, scan->x, scan->y, scan->z, n,
                            ctx->pl_c.as<float4>(), ctx->pl_n.as<float4>(), partb, nb);
       hipLaunchKernelGGL(k_cov_finalize, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, 0u, part, nb, nb,
-                         (const double*)partb, pl ? nb : 0u, pl ? nb : 0u);
+                         (const double*)partb, pl ? nb : 0u, pl ? nb : 0u);  // (the covariance kernels write nb columns)
     }
     MH_HIP(hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(IcpDeviceState), hipMemcpyDeviceToHost, s));
+    return MH_OK;
+  }
+
+  mh_status enqueue_tail(bool cov_prepared = false) {
+    MH_TRY(set_device(ctx));
+    MH_TRY(enqueue_cov_and_state(cov_prepared));
     MH_HIP(hipGetLastError());
-    MH_HIP(hipEventRecord(ctx->ev_poll, s));
+    MH_HIP(hipEventRecord(ctx->ev_poll, ctx->stream));
     return MH_OK;
   }
 
@@ -975,32 +878,14 @@ struct AlignJob {
                   h->handover_timeouts, h->dbg[0], h->dbg[1], h->dbg[2], h->dbg[3], serial_base, h->dbg[4], h->dbg[5], h->dbg[6], h->dbg[7], h->n_iterations, (uint32_t)scan->n, (int)streaming);
     if (!h->done) return fail(MH_ERR_INTERNAL, "device ICP loop did not terminate after max_iterations");
     finished = true;
-    if (auto_chunk) ctx->predicted_iterations[kind] = h->n_iterations + (h->term_reason == MH_TERM_MAX_ITERATIONS ? 0u : 1u);
-    res->n_host_polls = polls;
-    res->n_enqueued_iterations = enqueued;
-    for (int i = 0; i < 12; i++) res->T[i] = h->T[i];
-    if (p->compute_covariance)
-      for (int i = 0; i < 36; i++) res->cov[i] = h->cov[i];
-    res->n_iterations = h->n_iterations;
-    res->termination_reason = h->term_reason;
-    res->n_final_pairs = h->n_pairs;
-    res->n_final_pairs_pt2pl = pl ? h->n_pairs_pl : 0u;
-    res->potential_pairings = scan->n * (pl ? 2u : 1u);
-    res->quality = (h->n_pairs && scan->n) ? (double)h->n_pairs / (double)res->potential_pairings : 0.0;  // PairedRatio
-    if (h->term_reason == MH_TERM_NO_PAIRINGS)
-      for (int i = 0; i < 36; i++) res->cov[i] = (i % 7 == 0) ? 1e6 : 0.0;
-    if (trace) {
-      const uint32_t cnt = h->n_iterations < p->max_iterations ? h->n_iterations + 1 : p->max_iterations;
-      memset(trace, 0, sizeof(mh_icp_iter) * p->max_iterations);
-      const uint32_t valid = (h->term_reason == MH_TERM_NO_PAIRINGS || h->term_reason == MH_TERM_SOLVER_ERROR)
-                                 ? h->n_iterations : cnt;
-      if (valid) MH_HIP(hipMemcpy(trace, ctx->trace.p, sizeof(mh_icp_iter) * valid, hipMemcpyDeviceToHost));
-    }
+    if (auto_chunk) ctx->predicted_iterations[kind] = live_iterations(h);
+    read_result(h, p, res, potential(), pl ? h->n_pairs_pl : 0u, polls, enqueued);
+    if (trace) MH_TRY(download_trace(ctx, h, p, trace));
     if (prof) {
       float ms = 0.f;
       double sum = 0.0;
       // launches enqueued after termination are early-exit no-ops; time only the live ones
-      uint32_t live = h->n_iterations + ((h->term_reason == MH_TERM_MAX_ITERATIONS) ? 0u : 1u);
+      uint32_t live = live_iterations(h);
       if (live > prof_n) live = prof_n;
       for (uint32_t i = 0; i < live; i++) {
         MH_HIP(hipEventElapsedTime(&ms, ctx->prof_ev[2 * i], ctx->prof_ev[2 * i + 1]));

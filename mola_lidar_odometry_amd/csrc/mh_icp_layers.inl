@@ -1,5 +1,6 @@
 // mh_icp_layers.inl -- mh_icp_align_layers: one ICP alignment over several Matcher_Points_DistanceThreshold (map, scan) pairs
-// (lidar3d-dual-map.yaml, lidar3d-edges.yaml) with one Gauss-Newton solve.  Included by mh_icp.hip inside its anonymous namespace.
+// (lidar3d-dual-map.yaml, lidar3d-edges.yaml) with one Gauss-Newton solve.  Included by mh_icp.hip inside its anonymous namespace,
+// after AlignJob; the set-up, graph cache and read-back it shares with AlignJob are mh_icp_job.inl's.
 //
 // Per ICP iteration:  k_match_layers -> k_accum_layers(first) -> k_solve -> [k_accum_layers -> k_solve] x (inner - 1)
 // over ALL pairs, whatever their number (mh_k_layers.h); the covariance kernels close the chunk that ends the loop.  Loop
@@ -41,19 +42,11 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   p = p_;
   res = res_;
   ctx = pairs[0].scan->ctx;
-  memset(res, 0, sizeof(*res));
-  for (int i = 0; i < 12; i++) res->T[i] = T0[i];
-  for (int i = 0; i < 6; i++) res->cov[i * 7] = 1e6;
   if (final_pair_counts)
     for (uint32_t i = 0; i < np; i++) final_pair_counts[i] = 0;
   total_n = 0;
-  for (uint32_t i = 0; i < np; i++) total_n += pairs[i].scan->n;
-  res->potential_pairings = total_n;  // every pair adds its layer size
-  if (p->max_iterations == 0 || total_n == 0) {
-    res->termination_reason = p->max_iterations == 0 ? MH_TERM_MAX_ITERATIONS : MH_TERM_NO_PAIRINGS;
-    trivial = true;
-    return MH_OK;
-  }
+  for (uint32_t i = 0; i < np; i++) total_n += pairs[i].scan->n;  // every pair adds its layer size
+  if ((trivial = begin_result(res, p, T0, total_n))) return MH_OK;
   MH_TRY(set_device(ctx));
   MH_TRY(ensure_state(ctx));
   hipStream_t s = ctx->stream;
@@ -75,15 +68,9 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   const size_t mi = p->max_iterations;
   const size_t tab_bytes = (sizeof(LayerTable) + 255) / 256 * 256;
   const size_t sched_bytes = (1 + (size_t)np) * mi * sizeof(double);  // kernel_param | threshold of pair 0 | ... | pair np-1
-  if (ctx->h_layers_cap < tab_bytes + sched_bytes) {
-    if (ctx->h_layers) (void)hipHostFree(ctx->h_layers);
-    ctx->h_layers = nullptr;
-    ctx->h_layers_cap = 0;
-    MH_HIP(hipHostMalloc(&ctx->h_layers, tab_bytes + sched_bytes, hipHostMallocDefault));
-    ctx->h_layers_cap = tab_bytes + sched_bytes;
-  }
+  MH_TRY(ctx->h_layers.reserve(tab_bytes + sched_bytes));
   MH_TRY(ctx->layers_tab.reserve(tab_bytes + sched_bytes));
-  LayerTable* const tab = static_cast<LayerTable*>(ctx->h_layers);
+  LayerTable* const tab = ctx->h_layers.as<LayerTable>();
   this->tab = tab;
   memset(tab, 0, sizeof(LayerTable));
   tab->n_pairs = np;
@@ -107,7 +94,7 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   const uint32_t cols = L.tot_acc > L.tot_cov ? L.tot_acc : L.tot_cov;
   MH_TRY(ctx->partials.reserve((size_t)kGenN * (cols ? cols : 1) * sizeof(double)));
   if (trace) MH_TRY(ctx->trace.reserve(mi * sizeof(mh_icp_iter)));
-  double* const h_sched = reinterpret_cast<double*>(static_cast<char*>(ctx->h_layers) + tab_bytes);
+  double* const h_sched = reinterpret_cast<double*>(ctx->h_layers.as<char>() + tab_bytes);
   double* const d_sched = reinterpret_cast<double*>(ctx->layers_tab.as<char>() + tab_bytes);
   memcpy(h_sched, p->kernel_param, mi * sizeof(double));
   char* const pb = ctx->layers_pairs.as<char>();
@@ -131,61 +118,20 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     d.col_off = tab->blk_acc[i];
     d.cov_off = tab->blk_cov[i];
   }
-  MH_HIP(hipMemcpyAsync(ctx->layers_tab.p, ctx->h_layers, tab_bytes + sched_bytes, hipMemcpyHostToDevice, s));
+  MH_HIP(hipMemcpyAsync(ctx->layers_tab.p, ctx->h_layers.p, tab_bytes + sched_bytes, hipMemcpyHostToDevice, s));
   // the shared state and the solver's parameters: pair 0 stands in where a single value is reported (the trace's threshold)
-  MatchK mk = tab->d[0].mk;
-  SolveK sk;
-  memset(&sk, 0, sizeof(sk));
-  sk.max_iterations = p->max_iterations;
-  sk.disable_stall = p->disable_stall_test;
-  sk.max_inner = p->gn.max_inner_iterations;
-  sk.min_step_trans = p->min_abs_step_trans;
-  sk.min_step_rot = p->min_abs_step_rot;
-  sk.min_delta = p->gn.min_delta;
-  sk.max_cost = p->gn.max_cost;
-  sk.hook_enabled = p->hook_enabled;
-  sk.hook_trans = p->hook_min_trans;
-  sk.hook_rot = p->hook_min_rot;
-  sk.hook_cos_rot = (p->hook_min_rot > 0.0 && p->hook_min_rot < 3.0) ? cos(p->hook_min_rot) : __builtin_nan("");
-  if (p->hook_enabled) {
-    Pose C;
-    for (int i = 0; i < 12; i++) C.m[i] = p->hook_checkpoint[i];
-    const Pose Ci = inverse(C);
-    for (int i = 0; i < 12; i++) sk.hook_chk_inv[i] = Ci.m[i];
-  }
-  fill_prior(sk, prior);
-  sk.thr = mk.thr;
-  sk.kparam = mk.kparam;
-  sk.trace = trace ? ctx->trace.as<mh_icp_iter>() : nullptr;
-  sk.cov_hx = p->cov_findif_xyz;
-  sk.cov_ha = p->cov_findif_ang;
-  ctx->align_serial++;
-  init_state(ctx->h_state, T0);
-  ctx->h_state->serial = ((uint32_t)ctx->align_serial & 0x3FFu) << 22;
-  ctx->h_state->cur_thr2 = (float)(pairs[0].threshold[0] * pairs[0].threshold[0]);
-  ctx->h_state->cur_ang2 = mk.ang2;
-  ctx->h_state->cur_kparam = p->kernel_param[0];
+  const MatchK mk = tab->d[0].mk;
+  const SolveK sk = make_solve_params(p, prior, mk, trace ? ctx->trace.as<mh_icp_iter>() : nullptr);
+  begin_state(ctx, T0, pairs[0].threshold[0], mk.ang2, p->kernel_param[0]);
   MH_TRY(upload_state_and_params(ctx, mk, sk));
-  const uint32_t expect = p->expected_iterations ? p->expected_iterations : ctx->layers_predicted;
-  chunk = p->poll_every ? p->poll_every : (expect ? (expect + kChunkMargin > 64 ? 64u : expect + kChunkMargin) : 10u);
+  chunk = first_chunk(p, ctx->layers_predicted);
   return MH_OK;
 }
 
-// the result from the state block read back into ctx->h_state once the loop has terminated
+// the result from the state block read back into ctx->h_state once the loop has terminated (PairedRatio over all pairs)
 void LayersJob::finish(uint32_t polls, uint32_t enqueued) {
-  const IcpDeviceState* h = ctx->h_state;
-  if (p->poll_every == 0) ctx->layers_predicted = h->n_iterations + (h->term_reason == MH_TERM_MAX_ITERATIONS ? 0u : 1u);
-  res->n_host_polls = polls;
-  res->n_enqueued_iterations = enqueued;
-  for (int i = 0; i < 12; i++) res->T[i] = h->T[i];
-  if (p->compute_covariance)
-    for (int i = 0; i < 36; i++) res->cov[i] = h->cov[i];
-  res->n_iterations = h->n_iterations;
-  res->termination_reason = h->term_reason;
-  res->n_final_pairs = h->n_pairs;
-  res->quality = h->n_pairs ? (double)h->n_pairs / (double)total_n : 0.0;  // PairedRatio over all pairs
-  if (h->term_reason == MH_TERM_NO_PAIRINGS)
-    for (int i = 0; i < 36; i++) res->cov[i] = (i % 7 == 0) ? 1e6 : 0.0;
+  if (p->poll_every == 0) ctx->layers_predicted = live_iterations(ctx->h_state);
+  read_result(ctx->h_state, p, res, total_n, 0u, polls, enqueued);
 }
 
 // every pair's final pairings compacted out of its segment (into final_pairs[i] when given) and counted
@@ -224,7 +170,7 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
   uint32_t enqueued = 0, polls = 0;
   for (;;) {
     const uint32_t m = (p->max_iterations - enqueued) < chunk ? (p->max_iterations - enqueued) : chunk;
-    auto enqueue_kernels = [&]() {
+    auto enqueue_kernels = [&]() -> mh_status {
       for (uint32_t j = 0; j < m; j++) {
         hipLaunchKernelGGL(k_match_layers, dim3(L.tot_match), dim3(kFlatThreads), 0, s, ctx->d_state, dtab);
         hipLaunchKernelGGL(k_accum_layers, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 1u, part, L.tot_acc);
@@ -243,49 +189,16 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
                            L.tot_cov, (const double*)nullptr, 0u, 0u);
       }
       (void)hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(IcpDeviceState), hipMemcpyDeviceToHost, s);
+      return MH_OK;
     };
-    // the launches depend on the sizes and the buffers only (the per-alignment values sit in device memory): a shape seen in
-    // an earlier alignment is captured once and replayed, as AlignJob::enqueue_chunk does
+    // a chunk's launches depend on these sizes and buffers only: through the graph cache, as AlignJob::enqueue_chunk's
     unsigned long long key[32] = {0};
     const unsigned long long kv[] = {kLayersGraphTag | np, m, inner, p->compute_covariance, L.tot_match, L.tot_acc, L.tot_cov,
                                      (unsigned long long)dtab, (unsigned long long)part, (unsigned long long)ctx->d_state,
                                      (unsigned long long)ctx->d_params, (unsigned long long)ctx->h_state};
     static_assert(sizeof(kv) <= sizeof(key), "graph key too small");
     memcpy(key, kv, sizeof(kv));
-    const bool cached = !sw.no_graph && ctx->graph_exec && memcmp(key, ctx->graph_key, sizeof(key)) == 0;
-    const bool seen_before = !sw.no_graph && memcmp(key, ctx->graph_candidate, sizeof(key)) == 0 &&
-                             ctx->graph_candidate_align != ctx->align_serial;
-    if (!cached && !seen_before) {
-      if (!sw.no_graph && memcmp(key, ctx->graph_candidate, sizeof(key)) != 0) {
-        memcpy(ctx->graph_candidate, key, sizeof(key));
-        ctx->graph_candidate_align = ctx->align_serial;
-      }
-      enqueue_kernels();
-      MH_HIP(hipGetLastError());
-    } else {
-      if (!cached) {
-        if (ctx->graph_exec) {
-          (void)hipGraphExecDestroy(ctx->graph_exec);
-          ctx->graph_exec = nullptr;
-        }
-        hipGraph_t g = nullptr;
-        MH_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        enqueue_kernels();
-        const hipError_t ce = hipStreamEndCapture(s, &g);
-        if (ce != hipSuccess) {
-          if (g) (void)hipGraphDestroy(g);
-          return fail(MH_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ce));
-        }
-        const hipError_t ie = hipGraphInstantiate(&ctx->graph_exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (ie != hipSuccess) {
-          ctx->graph_exec = nullptr;
-          return fail(MH_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
-        }
-        memcpy(ctx->graph_key, key, sizeof(key));
-      }
-      MH_HIP(hipGraphLaunch(ctx->graph_exec, s));
-    }
+    MH_TRY(enqueue_cached(ctx, sw.no_graph, key, enqueue_kernels));
     enqueued += m;
     MH_HIP(hipEventRecord(ctx->ev_poll, s));
     polls++;
@@ -295,13 +208,7 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
     if (p->poll_every == 0) chunk = kChunkNext;
   }
   job.finish(polls, enqueued);
-  if (trace) {
-    const IcpDeviceState* h = ctx->h_state;
-    const uint32_t cnt = h->n_iterations < p->max_iterations ? h->n_iterations + 1 : p->max_iterations;
-    memset(trace, 0, sizeof(mh_icp_iter) * p->max_iterations);
-    const uint32_t valid = (h->term_reason == MH_TERM_NO_PAIRINGS || h->term_reason == MH_TERM_SOLVER_ERROR) ? h->n_iterations : cnt;
-    if (valid) MH_HIP(hipMemcpy(trace, ctx->trace.p, sizeof(mh_icp_iter) * valid, hipMemcpyDeviceToHost));
-  }
+  if (trace) MH_TRY(download_trace(ctx, ctx->h_state, p, trace));
   return job.count_pairs(final_pairs, final_pair_counts, pairs_mem);
 }
 

@@ -6,7 +6,8 @@
 // Loop control is align_batch_run's chunked one on the lead job's stream.  The chunks are launched directly, NOT replayed from a
 // captured graph: a group's composition changes from batch to batch as sequences end, and a chunk is 1 + 2 * inner launches per
 // iteration for ALL jobs where the single calls issue that many each.
-// Included by mh_icp.hip inside its extern "C" block, after mh_icp_batch.inl (order_after_layers_job_streams, k_gather_states).
+// Included by mh_icp.hip inside its extern "C" block, after mh_icp_batch.inl (order_after_layers_job_streams, reserve_group_buffers,
+// gather_states).
 
 static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
   const uint32_t A = (uint32_t)g.size();
@@ -16,19 +17,9 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
   MH_TRY(order_after_layers_job_streams(lead, g));
   // [gathered states] | job descriptors of the solve / covariance kernels | the (job, pair) table: pinned mirror and device copy
   const size_t desc_bytes = A * sizeof(BatchJob) + sizeof(LayerBatchTable);
-  const size_t need = A * sizeof(IcpDeviceState) + desc_bytes;
-  static_assert(sizeof(IcpDeviceState) % 8 == 0 && sizeof(BatchJob) % 8 == 0, "staging layout");
-  MH_TRY(lead->batch_desc.reserve(desc_bytes));
-  MH_TRY(lead->batch_states.reserve(A * sizeof(IcpDeviceState)));
-  if (lead->h_batch_cap < need) {
-    if (lead->h_batch) (void)hipHostFree(lead->h_batch);
-    lead->h_batch = nullptr;
-    lead->h_batch_cap = 0;
-    MH_HIP(hipHostMalloc(&lead->h_batch, need, hipHostMallocDefault));
-    lead->h_batch_cap = need;
-  }
-  IcpDeviceState* const h_states = reinterpret_cast<IcpDeviceState*>(lead->h_batch);
-  BatchJob* const h_desc = reinterpret_cast<BatchJob*>(h_states + A);
+  IcpDeviceState* h_states = nullptr;
+  BatchJob* h_desc = nullptr;
+  MH_TRY(reserve_group_buffers(lead, A, sizeof(LayerBatchTable), h_states, h_desc));
   LayerBatchTable* const h_tab = reinterpret_cast<LayerBatchTable*>(h_desc + A);
   memset(h_desc, 0, desc_bytes);
   h_tab->n_jobs = A;
@@ -84,9 +75,7 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
       hipLaunchKernelGGL(k_cov_accum_layers_b, dim3(tot_cov), dim3(kBlock), 0, s, dt);
       hipLaunchKernelGGL(k_cov_finalize_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj);
     }
-    hipLaunchKernelGGL(k_gather_states, dim3(A), dim3(256), 0, s, dj, lead->batch_states.as<IcpDeviceState>());
-    MH_HIP(hipGetLastError());
-    MH_HIP(hipMemcpyAsync(h_states, lead->batch_states.p, A * sizeof(IcpDeviceState), hipMemcpyDeviceToHost, s));
+    MH_TRY(gather_states(lead, dj, A, h_states));
     enqueued += m;
     polls++;
     MH_HIP(mh::wait_stream(s));

@@ -89,6 +89,28 @@ struct DevBuf {
   T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// grow-only pinned (page-locked) host buffer: the mirrors that are filled on the host and travel in one copy.  Growing frees the
+// old block first (nothing in flight reads a mirror when its owner fills it again), so a pointer taken before a reserve() is stale
+// after it.
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  mh_status reserve(size_t need) {
+    if (need <= bytes) return MH_OK;
+    release();
+    MH_HIP(hipHostMalloc(&p, need, hipHostMallocDefault));
+    bytes = need;
+    return MH_OK;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  template <class T>
+  T* as() const { return reinterpret_cast<T*>(p); }
+};
+
 // ---- map layout in HBM -----------------------------------------------------------------------
 // One 16-byte slot per hash bucket: a single dwordx4 load answers "is voxel (kx,ky,kz) occupied,
 // and where are its points".  key packs 3 x 21-bit biased voxel indices; ~0 = empty.
@@ -154,12 +176,10 @@ struct mh_ctx {
   uint32_t loop_serial = 0;  // ... and the serial number its next loop's entries start from (never repeats)
   mh::DevBuf sched;       // threshold / kernel-param arrays (double)
   mh::DevBuf batch_desc, batch_states;  // lock-step batches led by this context: job descriptors, gathered states
-  void* h_batch = nullptr;              // pinned mirror of both
-  size_t h_batch_cap = 0;
+  mh::PinnedBuf h_batch;                // pinned mirror of both
   // iterations the last auto-chunked alignment needed (sizes the next first chunk when the caller gives no estimate)
   uint32_t predicted_iterations[2] = {0, 0};
-  double* h_sched = nullptr;  // pinned staging for them
-  size_t h_sched_cap = 0;
+  mh::PinnedBuf h_sched;  // pinned staging for them (double)
   mh::DevBuf trace;       // mh_icp_iter[max_iterations]
   mh::DevBuf compact;     // compaction scratch (block counts / offsets) and staged outputs
   mh::DevBuf staging;     // generic staging for host<->device array transfers
@@ -177,8 +197,7 @@ struct mh_ctx {
   unsigned long long graph_candidate[32] = {0};  // key of the last direct-launched chunk: captured when a LATER alignment repeats it
   unsigned long long graph_candidate_align = 0, align_serial = 0;
   uint32_t* h_small = nullptr;  // pinned, device-visible [64]: small results a kernel writes straight to the host (mh_scan_bbox)
-  char* h_pp = nullptr;      // page-locked staging of the filter chain: job descriptors up, counters down
-  size_t h_pp_bytes = 0;
+  mh::PinnedBuf h_pp;        // page-locked staging of the filter chain: job descriptors up, counters down
   hipEvent_t ev_poll = nullptr;
   hipEvent_t ev_ready = nullptr;  // "everything queued on this context's stream so far": what a batch leader waits for
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
@@ -189,8 +208,7 @@ struct mh_ctx {
   mh::DevBuf pairs_stage;  // compacted pairings of all jobs of a batch
   mh::DevBuf layers_pairs;  // mh_icp_align_layers: a segment of pairing buffers per pair
   mh::DevBuf layers_tab;    // ... its descriptor table + threshold schedules
-  void* h_layers = nullptr; // ... their pinned mirror
-  size_t h_layers_cap = 0;
+  mh::PinnedBuf h_layers;   // ... their pinned mirror
   uint32_t layers_predicted = 0;  // iterations its previous alignment ran (size of the first chunk)
   // profiling events for the match kernel (pairs), created lazily
   hipEvent_t* prof_ev = nullptr;

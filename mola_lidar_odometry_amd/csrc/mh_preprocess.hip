@@ -699,15 +699,9 @@ mh_status preprocess_batch(size_t n_jobs, const mh_scan* const* raws, const mh_p
   hipStream_t s = lead->stream;
   // pinned staging of the leader: job descriptors up, counters down
   const size_t stage_bytes = n_jobs * sizeof(PpJob) + n_jobs * 8 * sizeof(uint32_t);
-  if (lead->h_pp_bytes < stage_bytes) {
-    if (lead->h_pp) (void)hipHostFree(lead->h_pp);
-    lead->h_pp = nullptr;
-    lead->h_pp_bytes = 0;
-    MH_HIP(hipHostMalloc((void**)&lead->h_pp, 2 * stage_bytes, hipHostMallocDefault));
-    lead->h_pp_bytes = 2 * stage_bytes;
-  }
-  PpJob* h_jobs = reinterpret_cast<PpJob*>(lead->h_pp);
-  uint32_t* h_counts = reinterpret_cast<uint32_t*>(lead->h_pp + n_jobs * sizeof(PpJob));
+  if (lead->h_pp.bytes < stage_bytes) MH_TRY(lead->h_pp.reserve(2 * stage_bytes));  // (head-room: a batch that gains a job or two)
+  PpJob* h_jobs = lead->h_pp.as<PpJob>();
+  uint32_t* h_counts = reinterpret_cast<uint32_t*>(lead->h_pp.as<char>() + n_jobs * sizeof(PpJob));
   size_t total = 0, max_n = 0, max_t = 0, table_entries = 0;
   bool any_icp = false, any_t = false;
   for (size_t k = 0; k < n_jobs; k++) {

@@ -908,6 +908,78 @@ def test_batch_pairs_block_with_a_trivial_first_job(ctx):
         c.close()
 
 
+def test_pinned_mirrors_regrown_between_calls_give_the_bits_of_fresh_contexts():
+    """Every entry point stages its uploads in a page-locked mirror that its context keeps and grows on demand; growing frees
+    the old block, so a pointer held across the growth would read or write freed memory.  One set of contexts runs, in order:
+    mh_icp_align with budgets of 5, 40 and 5 iterations (the schedules' mirror grows, then is larger than needed);
+    mh_icp_align_batch with 2, then 6 jobs and a host pairs block (the lock-step mirror of the lead grows, four jobs' contexts are
+    new to alignments); mh_icp_align_layers with 1, then 4 pairs (the layer table's mirror grows); mh_icp_align_layers_batch with
+    2, then 5 jobs led by a context that has led no batch yet.  Every result -- pose, covariance, iteration count, termination
+    reason, the compacted pairings of the pairs block -- has the bits of the same call on contexts that have seen nothing else."""
+    w = synth.make_workload("t", 2000, 16, 125, 25.0, 6, voxel_size=2.0)
+    rng = np.random.default_rng(11)
+    subs = [[w.scan_xyz[rng.permutation(len(w.scan_xyz))[:300]] for _ in range(4)] for _ in range(6)]
+
+    class Rig:  # a context per entry of `which`, each with its own map and the four scans subs[entry]
+        def __init__(self, which):
+            self.ctxs = [capi.Context(0) for _ in which]
+            self.maps = [capi.Map(c, 2.0, 20).build(w.map_xyz) for c in self.ctxs]
+            self.scans = [[capi.Scan(c, s) for s in subs[i]] for i, c in zip(which, self.ctxs)]
+
+        def close(self):
+            for c in self.ctxs:
+                c.close()
+
+    def params(mi):
+        thr, kp = synth.threshold_schedule(2.0, mi)
+        return capi.ICPParams(max_iterations=mi, threshold=thr, kernel_param=kp), thr
+
+    # a call = (the long-lived rig's contexts it runs on, job by job; run(rig, positions of those contexts in the rig))
+    def single(mi):
+        return [0], lambda r, at: [capi.icp_align(r.maps[at[0]], r.scans[at[0]][0], w.T_guess, params(mi)[0], want_trace=False)]
+
+    def batch(k):
+        def run(r, at):
+            sizes = [300] * k
+            block = np.zeros(sum(capi.pairs_block_bytes(n) for n in sizes), np.uint8)
+            res = capi.icp_align_batch([r.maps[j] for j in at], [r.scans[j][0] for j in at], [w.T_guess] * k, params(40)[0],
+                                       pairs_block=block, pairs_mem=capi.MEM_HOST)
+            for d, pr in zip(res, capi.unpack_pairs_block(block, sizes, res)):
+                d["pairs"] = {key: v.copy() for key, v in pr.items()}
+            return res
+        return list(range(k)), run
+
+    def layers(n_pairs):
+        def run(r, at):
+            p, thr = params(40)
+            return [capi.icp_align_layers([(r.maps[at[0]], r.scans[at[0]][i], thr) for i in range(n_pairs)], w.T_guess, p,
+                                          want_trace=False)]
+        return [0], run
+
+    def layers_batch(k):
+        def run(r, at):
+            p, thr = params(40)
+            return capi.icp_align_layers_batch([[(r.maps[j], r.scans[j][i], thr) for i in range(2)] for j in at], [w.T_guess] * k, p)
+        return list(range(5, 5 - k, -1)), run  # (job 0, the lead, on the last context: it has led no batch before)
+
+    calls = [single(5), single(40), single(5), batch(2), batch(6), layers(1), layers(4), layers_batch(2), layers_batch(5)]
+    used = Rig(range(6))
+    for ci, (which, run) in enumerate(calls):
+        got = run(used, which)
+        fresh = Rig(which)
+        want = run(fresh, list(range(len(which))))
+        fresh.close()
+        assert len(got) == len(want) == len(which)
+        for a, b in zip(got, want):
+            assert b["n_iterations"] > 0 and b["n_final_pairs"] > 50, (ci, b)
+            assert (a["n_iterations"], a["termination_reason"], a["n_final_pairs"]) == (
+                b["n_iterations"], b["termination_reason"], b["n_final_pairs"]), ci
+            assert np.array_equal(a["T"], b["T"]) and np.array_equal(a["cov"], b["cov"]), ci
+            for key in b.get("pairs", {}):
+                assert np.array_equal(a["pairs"][key], b["pairs"][key]), (ci, key)
+    used.close()
+
+
 def test_align_is_bitwise_reproducible(ctx, small):
     w, gm, om, gs = small
     p = _params(capi, w, disable_stall_test=True)
