@@ -405,6 +405,12 @@ enum { MH_PT2PL_PLANE_DISTANCE = 0, MH_PT2PL_CENTROID_DISTANCE = 1 };
  * plane-paired points out of Matcher_Points_DistanceThreshold.  Unverified (U12), hence a switch; PAIR_AGAIN is what rounds
  * 1-3 did and stays the default until the reference decides (MOLA_HIP_MATCHED_POINTS=skip|again in the host layers). */
 enum { MH_MATCHED_POINTS_PAIR_AGAIN = 0, MH_MATCHED_POINTS_SKIP = 1 };
+/* Matcher_Points_DistanceThreshold::allowMatchAlreadyMatchedGlobalPoints [U] (default FALSE upstream; every reference pipeline
+ * writes true): with false a matcher runs serially and a point of a global layer is paired once per ICP iteration, by the first
+ * candidate in matching order; the "already paired" bits (MatchState::globalPairedBitField) live for one iteration and are shared
+ * by its matchers.  Unverified (U13).  Not a switch but a per-pair option: mh_layer_pair_opts::unique_global of
+ * mh_icp_align_layers_opts (below), which states the semantics; the other alignment entry points pair a map point as often as it
+ * is nearest.  The host layers set it from the pipeline's key; the mirror classes' default stays true. */
 
 MH_API mh_status mh_nn_search_pt2pl(const mh_map* map, const mh_scan* scan, const double T[12], double distance_threshold,
                                     uint32_t mode, const mh_pairs_pl_out* out, int32_t mem, mh_match_info* info);
@@ -646,6 +652,33 @@ MH_API mh_status mh_icp_align_layers(size_t n_pairs, const mh_layer_pair* pairs,
                                      const double T_guess[12], const mh_prior* prior, mh_icp_result* result,
                                      mh_icp_iter* trace, const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
                                      uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
+
+/* mh_icp_align_layers with Matcher_Points_DistanceThreshold::allowMatchAlreadyMatchedGlobalPoints per pair (U13 [U]: upstream's
+ * default is false, MatchState::globalPairedBitField).  opts == NULL or unique_global == 0 in every entry IS mh_icp_align_layers:
+ * the same launches, the same cached graphs, the same bits (mh_icp_align_layers calls this function with NULL).  Otherwise the
+ * contract above, n_pairs 1 included, plus:
+ *  - Claims: within one ICP iteration the accepted candidates (i, g) -- local point i of a pair, map point g -- are taken in
+ *    matching order: pairs in array order, local points in ascending index.  A candidate of a pair with unique_global != 0 is
+ *    dropped when g of that map has been claimed already, otherwise it is kept and claims g; a dropped point has no pairing in
+ *    that iteration (it is not offered its second-nearest neighbour).  A pair with unique_global == 0 neither tests nor sets
+ *    claims.  Claims are per MAP: pairs that share a map share its claims; they start empty in every iteration.  (The device
+ *    computes the equivalent minimum: the winner of g is the candidate with the smallest (pair, local index) naming it.)
+ *  - Counts: potential_pairings is unchanged; quality, NoPairings, the trace's n_pairs, the covariance, final_pairs and
+ *    final_pair_counts see the kept pairings only.
+ *  - Two more launches per ICP iteration, whatever the number of pairs.  Results are bitwise reproducible, MH_NO_GRAPH=1 included.
+ *  - MH_ERR_UNSUPPORTED also for: a unique pair whose scan has 2^29 or more points, or whose map has been offered 2^28 or more
+ *    points (mh_map_info::n_offered: the claim table has an 8-byte entry per source index of the map, owned by the context).
+ * No lock-step batch form: mh_icp_align_layers_batch has no opts. */
+typedef struct {
+  uint32_t unique_global;       /* 1: allowMatchAlreadyMatchedGlobalPoints == false (U13) */
+} mh_layer_pair_opts;
+
+MH_API mh_status mh_icp_align_layers_opts(size_t n_pairs, const mh_layer_pair* pairs,
+                                          const mh_layer_pair_opts* opts /* n_pairs entries or NULL */,
+                                          const mh_icp_params* params, const double T_guess[12], const mh_prior* prior,
+                                          mh_icp_result* result, mh_icp_iter* trace,
+                                          const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
+                                          uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
 
 /* Many multi-layer alignments from one host thread, one context per job: mh_icp_align_batch for mh_icp_align_layers.  Job i has
  * all its maps and scans on ONE context, distinct jobs have distinct contexts of the same device, and each job's pairs obey the

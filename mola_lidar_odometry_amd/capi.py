@@ -125,6 +125,11 @@ class LayerPair(C.Structure):
                 ("weight", C.c_double)]
 
 
+class LayerPairOpts(C.Structure):
+    """mh_layer_pair_opts: what mh_icp_align_layers_opts takes per pair beside its mh_layer_pair."""
+    _fields_ = [("unique_global", C.c_uint32)]
+
+
 class LayerJob(C.Structure):
     """mh_layer_job: the layer pairs of one job of mh_icp_align_layers_batch."""
     _fields_ = [("n_pairs", C.c_size_t), ("pairs", C.POINTER(LayerPair))]
@@ -228,6 +233,9 @@ _SIGNATURES = {
     "mh_icp_align_layers": (C.c_int32, [C.c_size_t, C.POINTER(LayerPair), C.POINTER(ICPParamsC), _DP, C.POINTER(Prior),
                                         C.POINTER(ICPResult), C.POINTER(ICPIter), C.POINTER(PairsOut),
                                         C.POINTER(C.c_uint64), C.c_int32]),
+    "mh_icp_align_layers_opts": (C.c_int32, [C.c_size_t, C.POINTER(LayerPair), C.POINTER(LayerPairOpts), C.POINTER(ICPParamsC),
+                                             _DP, C.POINTER(Prior), C.POINTER(ICPResult), C.POINTER(ICPIter),
+                                             C.POINTER(PairsOut), C.POINTER(C.c_uint64), C.c_int32]),
     "mh_icp_align_layers_batch": (C.c_int32, [C.c_size_t, C.POINTER(LayerJob), C.POINTER(ICPParamsC), C.c_int32, _DP,
                                               C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
 }
@@ -857,6 +865,8 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
     """mh_icp_align_layers: one alignment over several (map, scan) point-layer pairs with one Gauss-Newton solve.
     `pairs`: a sequence of dicts {map, scan, threshold, threshold_angular_deg=0, weight=1} or tuples in that order; a
     threshold is a scalar or max_iterations values.  p.threshold, p.threshold_angular_deg and p.gn.weight_pt2pt are not used.
+    A dict may carry unique_global (allowMatchAlreadyMatchedGlobalPoints == false for that pair, U13): with one that is set the
+    call goes to mh_icp_align_layers_opts.
     Returns icp_align's dict plus pair_counts (final pairings per pair) and, with want_pairs, pairs (one dict per pair)."""
     p_c = replace(p, threshold=p.threshold if p.threshold is not None else 0.0)
     cp, keep = p_c.c(T_guess)
@@ -877,8 +887,15 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
             po[i] = PairsOut(li.ctypes.data_as(_UP), gi.ctypes.data_as(_UP), gx.ctypes.data_as(_FP), gy.ctypes.data_as(_FP),
                              gz.ctypes.data_as(_FP), d2.ctypes.data_as(_FP))
             bufs.append((li, gi, gx, gy, gz, d2))
-    _chk(lib().mh_icp_align_layers(n_pairs, arr, C.byref(cp), T0.ctypes.data_as(_DP), C.byref(pr) if pr else None,
-                                   C.byref(res), trace, po, counts, MEM_HOST))
+    if any(e.get("unique_global") for e in norm):
+        opts = (LayerPairOpts * max(1, n_pairs))()
+        for i, e in enumerate(norm):
+            opts[i].unique_global = 1 if e.get("unique_global") else 0
+        _chk(lib().mh_icp_align_layers_opts(n_pairs, arr, opts, C.byref(cp), T0.ctypes.data_as(_DP), C.byref(pr) if pr else None,
+                                            C.byref(res), trace, po, counts, MEM_HOST))
+    else:
+        _chk(lib().mh_icp_align_layers(n_pairs, arr, C.byref(cp), T0.ctypes.data_as(_DP), C.byref(pr) if pr else None,
+                                       C.byref(res), trace, po, counts, MEM_HOST))
     out = _result_dict(res)
     out["pair_counts"] = [int(counts[i]) for i in range(n_pairs)]
     if want_trace:

@@ -204,6 +204,7 @@ mh_status mh_ctx_destroy(mh_ctx* ctx) {
   ctx->h_sched.release();
   ctx->h_batch.release();
   ctx->layers_pairs.release();
+  ctx->claims.release();
   ctx->layers_tab.release();
   ctx->h_layers.release();
   ctx->batch_desc.release();

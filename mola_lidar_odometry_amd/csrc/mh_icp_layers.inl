@@ -3,7 +3,9 @@
 // after AlignJob; the set-up, graph cache and read-back it shares with AlignJob are mh_icp_job.inl's.
 //
 // Per ICP iteration:  k_match_layers -> k_accum_layers(first) -> k_solve -> [k_accum_layers -> k_solve] x (inner - 1)
-// over ALL pairs, whatever their number (mh_k_layers.h); the covariance kernels close the chunk that ends the loop.  Loop
+// over ALL pairs, whatever their number (mh_k_layers.h); the covariance kernels close the chunk that ends the loop.  With a pair
+// whose map points pair once only (mh_icp_align_layers_opts, unique_global): k_claim_layers -> k_resolve_layers behind the match
+// (mh_k_claim.h), and the set of such pairs is part of the chunk's graph key.  Loop
 // control is AlignJob's chunked one: a chunk of iterations is enqueued (replayed from a captured graph once its shape repeats,
 // MH_NO_GRAPH=1: never), the host waits for its event and reads the done flag.
 
@@ -13,6 +15,9 @@ struct LayersLayout {
   size_t seg_q[MH_MAX_LAYER_PAIRS], seg_g[MH_MAX_LAYER_PAIRS];  // byte offsets of each pair's pairing buffers
   size_t pair_bytes = 0;
   uint32_t tot_match = 0, tot_acc = 0, tot_cov = 0;
+  uint32_t tot_claim = 0;    // workgroups of k_claim_layers / k_resolve_layers (0: no unique pair, neither is launched)
+  uint32_t unique_mask = 0;  // bit i: pair i is unique
+  size_t claim_off = 0;      // byte offset of the ClaimTable in layers_tab
 };
 
 // One multi-layer alignment from its arguments to its uploaded [state | parameters | table | schedules]: what a single call and a
@@ -30,13 +35,57 @@ struct LayersJob {
   uint32_t chunk = 10;        // iterations of the first chunk
 
   mh_status start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
-                  const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts);
+                  const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
+                  const mh_layer_pair_opts* opts = nullptr);
   void finish(uint32_t polls, uint32_t enqueued);
   mh_status count_pairs(const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem);
+  mh_status claims_begin(ClaimTable* ct);
 };
 
+// The claim table of this alignment's unique pairs (mh_k_claim.h): a region of the context's table per distinct map among them,
+// the flattened range of the two kernels, and the epochs of its iterations.  The table's memory is filled with ones (every
+// entry empty) when its block is new and when the epochs have run out; otherwise what earlier alignments left loses by its epoch.
+mh_status LayersJob::claims_begin(ClaimTable* ct) {
+  memset(ct, 0, sizeof(ClaimTable));
+  size_t region_off[MH_MAX_LAYER_PAIRS] = {0}, total = 0;
+  for (uint32_t i = 0; i < np; i++) {
+    ct->blk[i] = L.tot_claim;
+    if (!((L.unique_mask >> i) & 1u)) continue;
+    const mh_map* m = pairs[i].map;
+    if (pairs[i].scan->n >= kClaimMaxScan)
+      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_opts: a unique pair whose scan has 2^29 or more points");
+    if (m->n_offered >= kClaimMaxEntries)
+      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_opts: a unique pair whose map has been offered 2^28 or more points");
+    uint32_t first = i;
+    for (uint32_t j = 0; j < i; j++)
+      if (((L.unique_mask >> j) & 1u) && pairs[j].map == m && first == i) first = j;
+    if (first == i) {
+      region_off[i] = total;
+      total += ((size_t)m->n_offered + 31) / 32 * 32;
+    } else {
+      region_off[i] = region_off[first];
+    }
+    ct->entries[i] = (uint32_t)m->n_offered;
+    L.tot_claim += nblk(pairs[i].scan->n);
+  }
+  ct->blk[np] = L.tot_claim;
+  const void* const before = ctx->claims.p;
+  MH_TRY(ctx->claims.reserve((total ? total : 32) * sizeof(unsigned long long)));
+  const uint32_t mi = p->max_iterations;
+  if (ctx->claims.p != before || ctx->claim_epoch < mi) {
+    MH_HIP(hipMemsetAsync(ctx->claims.p, 0xFF, ctx->claims.bytes, ctx->stream));
+    ctx->claim_epoch = 0xFFFFFFFEu;
+  }
+  ct->epoch0 = ctx->claim_epoch;
+  ctx->claim_epoch -= mi;  // iteration k claims with epoch0 - k, k < max_iterations: the next alignment starts below all of them
+  for (uint32_t i = 0; i < np; i++)
+    if ((L.unique_mask >> i) & 1u) ct->region[i] = ctx->claims.as<unsigned long long>() + region_off[i];
+  return MH_OK;
+}
+
 mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
-                           const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts) {
+                           const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
+                           const mh_layer_pair_opts* opts) {
   np = np_;
   pairs = pairs_;
   p = p_;
@@ -68,8 +117,12 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   const size_t mi = p->max_iterations;
   const size_t tab_bytes = (sizeof(LayerTable) + 255) / 256 * 256;
   const size_t sched_bytes = (1 + (size_t)np) * mi * sizeof(double);  // kernel_param | threshold of pair 0 | ... | pair np-1
-  MH_TRY(ctx->h_layers.reserve(tab_bytes + sched_bytes));
-  MH_TRY(ctx->layers_tab.reserve(tab_bytes + sched_bytes));
+  for (uint32_t i = 0; opts && i < np; i++) L.unique_mask |= opts[i].unique_global ? 1u << i : 0u;
+  // (a call without unique pairs uploads the bytes it always did)
+  L.claim_off = (tab_bytes + sched_bytes + 255) / 256 * 256;
+  const size_t up_bytes = L.unique_mask ? L.claim_off + sizeof(ClaimTable) : tab_bytes + sched_bytes;
+  MH_TRY(ctx->h_layers.reserve(up_bytes));
+  MH_TRY(ctx->layers_tab.reserve(up_bytes));
   LayerTable* const tab = ctx->h_layers.as<LayerTable>();
   this->tab = tab;
   memset(tab, 0, sizeof(LayerTable));
@@ -118,7 +171,8 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     d.col_off = tab->blk_acc[i];
     d.cov_off = tab->blk_cov[i];
   }
-  MH_HIP(hipMemcpyAsync(ctx->layers_tab.p, ctx->h_layers.p, tab_bytes + sched_bytes, hipMemcpyHostToDevice, s));
+  if (L.unique_mask) MH_TRY(claims_begin(reinterpret_cast<ClaimTable*>(ctx->h_layers.as<char>() + L.claim_off)));
+  MH_HIP(hipMemcpyAsync(ctx->layers_tab.p, ctx->h_layers.p, up_bytes, hipMemcpyHostToDevice, s));
   // the shared state and the solver's parameters: pair 0 stands in where a single value is reported (the trace's threshold)
   const MatchK mk = tab->d[0].mk;
   const SolveK sk = make_solve_params(p, prior, mk, trace ? ctx->trace.as<mh_icp_iter>() : nullptr);
@@ -155,14 +209,15 @@ mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* fina
 
 mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pairs, const mh_icp_params* p, const double T0[12],
                        const mh_prior* prior, mh_icp_result* res, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
-                       uint64_t* final_pair_counts, int32_t pairs_mem) {
+                       uint64_t* final_pair_counts, int32_t pairs_mem, const mh_layer_pair_opts* opts = nullptr) {
   LayersJob job;
-  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts));
+  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts, opts));
   if (job.trivial) return MH_OK;
   mh_ctx* const ctx = job.ctx;
   const LayersLayout& L = job.L;
   hipStream_t s = ctx->stream;
   const LayerTable* const dtab = ctx->layers_tab.as<LayerTable>();
+  const ClaimTable* const dclaim = reinterpret_cast<const ClaimTable*>(ctx->layers_tab.as<char>() + L.claim_off);
   double* const part = ctx->partials.as<double>();
   const SolveK* const dsk = &ctx->d_params->sk;
   const uint32_t inner = p->gn.max_inner_iterations;
@@ -173,6 +228,10 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
     auto enqueue_kernels = [&]() -> mh_status {
       for (uint32_t j = 0; j < m; j++) {
         hipLaunchKernelGGL(k_match_layers, dim3(L.tot_match), dim3(kFlatThreads), 0, s, ctx->d_state, dtab);
+        if (L.tot_claim) {
+          hipLaunchKernelGGL(k_claim_layers, dim3(L.tot_claim), dim3(kBlock), 0, s, ctx->d_state, dtab, dclaim);
+          hipLaunchKernelGGL(k_resolve_layers, dim3(L.tot_claim), dim3(kBlock), 0, s, ctx->d_state, dtab, dclaim);
+        }
         hipLaunchKernelGGL(k_accum_layers, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 1u, part, L.tot_acc);
         hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, dsk, (const double*)part, L.tot_acc,
                            L.tot_acc, (const double*)nullptr, 0u, 0u, 1u);
@@ -196,8 +255,14 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
     const unsigned long long kv[] = {kLayersGraphTag | np, m, inner, p->compute_covariance, L.tot_match, L.tot_acc, L.tot_cov,
                                      (unsigned long long)dtab, (unsigned long long)part, (unsigned long long)ctx->d_state,
                                      (unsigned long long)ctx->d_params, (unsigned long long)ctx->h_state};
-    static_assert(sizeof(kv) <= sizeof(key), "graph key too small");
+    static_assert(sizeof(kv) + 3 * sizeof(key[0]) <= sizeof(key), "graph key too small");
     memcpy(key, kv, sizeof(kv));
+    if (L.tot_claim) {  // (without a unique pair the key is what it always was)
+      unsigned long long* const kc = key + sizeof(kv) / sizeof(kv[0]);
+      kc[0] = L.unique_mask;
+      kc[1] = L.tot_claim;
+      kc[2] = (unsigned long long)dclaim;
+    }
     MH_TRY(enqueue_cached(ctx, sw.no_graph, key, enqueue_kernels));
     enqueued += m;
     MH_HIP(hipEventRecord(ctx->ev_poll, s));

@@ -210,6 +210,8 @@ struct mh_ctx {
   mh::DevBuf layers_tab;    // ... its descriptor table + threshold schedules
   mh::PinnedBuf h_layers;   // ... their pinned mirror
   uint32_t layers_predicted = 0;  // iterations its previous alignment ran (size of the first chunk)
+  mh::DevBuf claims;              // mh_icp_align_layers_opts: the claim table of unique pairs (mh_k_claim.h), 64-bit entries
+  uint32_t claim_epoch = 0;       // ... the epoch its next alignment's first iteration claims with (descending)
   // profiling events for the match kernel (pairs), created lazily
   hipEvent_t* prof_ev = nullptr;
   uint32_t prof_cap = 0;

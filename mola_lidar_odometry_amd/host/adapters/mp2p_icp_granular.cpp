@@ -48,9 +48,10 @@ class Matcher_Points_DistanceThreshold_HIP : public Matcher_Points_DistanceThres
     {
         const auto& sw = molahip_host::plugin_switches();
         // what the device search implements: up to MH_MAX_PAIRINGS_PER_POINT pairings per point (nn_multiple_search, rgbd.yaml:138),
-        // no exclusivity bookkeeping between points, the whole layer (no random subsample), no earlier matcher's pairings to respect
+        // the whole layer (no random subsample), no earlier matcher's pairings to respect.  allowMatchAlreadyMatchedGlobalPoints_
+        // false (upstream's default, U13) keeps the device search: the claims are applied to its pairs below, on the host
         const bool device_shape = pairingsPerPoint >= 1 && pairingsPerPoint <= MH_MAX_PAIRINGS_PER_POINT &&
-                                  allowMatchAlreadyMatchedGlobalPoints_ && maxLocalPointsPerLayer_ == 0 &&
+                                  maxLocalPointsPerLayer_ == 0 &&
                                   (allowMatchAlreadyMatchedPoints_ || ms.localPairedBitField.point_layers.count(localName) == 0 ||
                                    ms.localPairedBitField.point_layers.at(localName).none());  // [U] members of Matcher_Points_Base / MatchState
         mh_map* dmap = nullptr;
@@ -79,8 +80,22 @@ class Matcher_Points_DistanceThreshold_HIP : public Matcher_Points_DistanceThres
         out.paired_pt2pt.reserve(out.paired_pt2pt.size() + info.n_pairs);
         auto& localBits = ms.localPairedBitField.point_layers[localName];  // [U] marks what later matchers must skip
         if (localBits.size() < n) localBits.resize(n);
+        // U13 [U]: the pairs arrive in ascending local index, upstream's serial order; a pair whose map point an earlier pair of
+        // this ICP iteration has taken (MatchState::globalPairedBitField, shared by the matchers of the iteration) is dropped,
+        // every other one takes its map point
+        const bool unique     = !allowMatchAlreadyMatchedGlobalPoints_;
+        auto*      globalBits = unique ? &ms.globalPairedBitField.point_layers[globalName] : nullptr;
+        uint64_t   n_emitted  = 0;
         for (uint64_t k = 0; k < info.n_pairs; k++)
         {
+            if (unique)
+            {
+                const size_t g = dev->pairs.gi[k];
+                if (globalBits->size() <= g) globalBits->resize(g + 1);
+                if ((*globalBits)[g]) continue;
+                globalBits->mark_as_set(g);
+            }
+            n_emitted++;
             mrpt::tfest::TMatchingPair mp;  // [U]
             mp.globalIdx = dev->pairs.gi[k];
             mp.localIdx  = dev->pairs.li[k];
@@ -92,7 +107,7 @@ class Matcher_Points_DistanceThreshold_HIP : public Matcher_Points_DistanceThres
         }
         // per-layer weight != 1 (pointLayerMatches.weight, yaml:204): recorded like upstream does [U]
         const double w = weight_pt2pt_layers.at(globalName).at(localName);
-        if (w != 1.0 && info.n_pairs) out.point_weights.emplace_back(info.n_pairs, w);
+        if (w != 1.0 && n_emitted) out.point_weights.emplace_back(n_emitted, w);
     }
 };
 IMPLEMENTS_MRPT_OBJECT(Matcher_Points_DistanceThreshold_HIP, mp2p_icp::Matcher_Points_DistanceThreshold, mp2p_icp)

@@ -29,8 +29,9 @@
 // since round 5), pairingsPerPoint 1.  And, through mh_icp_align_layers, several point-layer pairs in one solve:
 //   extras/lidar3d-dual-map.yaml:115-132   one Solver_GaussNewton, two Matcher_Points_DistanceThreshold on two layer pairs
 //   extras/lidar3d-edges.yaml:120-129      one Solver_GaussNewton, one Matcher_Points_DistanceThreshold with two entries
-// i.e. only ungated, enabled point matchers (pairingsPerPoint 1, allowMatchAlreadyMatchedGlobalPoints), 2 to MH_MAX_LAYER_PAIRS
-// {global, local} entries in all, each with its own threshold schedule, angular term and weight; pairs in upstream's matching
+// i.e. only ungated, enabled point matchers (pairingsPerPoint 1), 2 to MH_MAX_LAYER_PAIRS {global, local} entries in all -- 1 to
+// MH_MAX_LAYER_PAIRS when a matcher has allowMatchAlreadyMatchedGlobalPoints false (upstream's default, U13: the default pipeline
+// without the key runs here, mh_icp_align_layers_opts with unique_global) --, each with its own threshold schedule, angular term and weight; pairs in upstream's matching
 // order (matchers in list order, then weight_pt2pt_layers' std::map order: global name, then local name).  A local layer named by
 // two entries is paired again for each unless allowMatchAlreadyMatchedPoints is false and MOLA_HIP_MATCHED_POINTS=skip (then the
 // upstream loop runs).  Gated blocks (extras/lidar3d-near-far.yaml) go to the upstream loop.
@@ -131,6 +132,7 @@ struct LayerShape
     std::vector<const Matcher_Points_DistanceThreshold*> matchers;
     const Solver_GaussNewton* gn = nullptr;
     std::vector<Entry> entries;
+    bool any_unique = false;  // some matcher has allowMatchAlreadyMatchedGlobalPoints false (U13)
 };
 
 template <class M> bool single_unit_layer(const M& m, std::string& g, std::string& l, double* weight_out = nullptr)
@@ -383,9 +385,9 @@ class ICP_HIP : public ICP
         for (const auto& mp : matchers())
         {
             const auto* m = dynamic_cast<const Matcher_Points_DistanceThreshold*>(mp.get());
-            if (!m || !m->enabled || m->runFromIteration != 0 || m->runUpToIteration != 0 || m->pairingsPerPoint != 1 ||
-                !m->allowMatchAlreadyMatchedGlobalPoints)
-                return false;
+            if (!m || !m->enabled || m->runFromIteration != 0 || m->runUpToIteration != 0 || m->pairingsPerPoint != 1) return false;
+            // U13: a matcher that pairs a map point once per iteration (the claims of mh_icp_align_layers_opts)
+            if (!m->allowMatchAlreadyMatchedGlobalPoints && !m->weight_pt2pt_layers.empty()) ls.any_unique = true;
             if (!m->allowMatchAlreadyMatchedPoints_ && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP)
                 skip_paired = true;
             ls.matchers.push_back(m);
@@ -401,7 +403,7 @@ class ICP_HIP : public ICP
                     ls.entries.push_back(e);
                 }
         }
-        if (ls.entries.size() < 2 || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
+        if (ls.entries.size() < (ls.any_unique ? 1u : 2u) || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
         for (size_t i = 0; i < ls.entries.size(); i++)
             for (size_t j = i + 1; j < ls.entries.size(); j++)
                 if (skip_paired && ls.entries[i].localLayer == ls.entries[j].localLayer) return false;
@@ -421,9 +423,11 @@ class ICP_HIP : public ICP
         const size_t np = ls.entries.size();
         std::vector<const mrpt::maps::CPointsMap*> locals(np);
         std::vector<mh_layer_pair> pairs(np);
+        std::vector<mh_layer_pair_opts> opts(np);
         for (size_t i = 0; i < np; i++)
         {
             const auto& e = ls.entries[i];
+            opts[i].unique_global = e.m->allowMatchAlreadyMatchedGlobalPoints ? 0u : 1u;
             mh_map* m = dev_->device_map_of(*pcGlobal.layers.at(e.globalLayer), false);  // every global layer mirrored
             locals[i] = dynamic_cast<const mrpt::maps::CPointsMap*>(pcLocal.layers.at(e.localLayer).get());
             if (!m || !locals[i]) return upstream_align(pcLocal, pcGlobal, guess, p, result, prior, outputDebugInfo);
@@ -488,8 +492,8 @@ class ICP_HIP : public ICP
             q.max_iterations = budget;
             q.kernel_param   = kp.data();
             mh_icp_result rr{};
-            mh_check(mh_icp_align_layers(np, pairs.data(), &q, T0, prior ? &pr : nullptr, &rr, trace, po.data(), counts.data(),
-                                         MH_MEM_HOST), "mh_icp_align_layers");
+            mh_check(mh_icp_align_layers_opts(np, pairs.data(), ls.any_unique ? opts.data() : nullptr, &q, T0, prior ? &pr : nullptr, &rr,
+                                              trace, po.data(), counts.data(), MH_MEM_HOST), "mh_icp_align_layers_opts");
             return rr;
         };
         auto run = [&](uint32_t budget, mh_icp_iter* trace) {

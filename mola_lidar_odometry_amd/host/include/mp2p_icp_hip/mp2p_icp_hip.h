@@ -264,6 +264,9 @@ struct Pairings {  // mp2p_icp::Pairings::paired_pt2pt as SoA (+ pt2pl)
   // role of MatchState::localPairedBitField [U]: per local layer, which points the matchers of THIS iteration have paired so
   // far -- read by later matchers when MOLA_HIP_MATCHED_POINTS=skip (allowMatchAlreadyMatchedPoints = false upstream, U12)
   std::map<std::string, std::vector<uint8_t>> local_paired;
+  // role of MatchState::globalPairedBitField [U]: per global layer, which of its points (by the index the pairings report) the
+  // matchers of THIS iteration with allowMatchAlreadyMatchedGlobalPoints = false have paired so far (U13)
+  std::map<std::string, std::vector<uint8_t>> global_paired;
   bool empty() const { return localIdx.empty() && pl_lx.empty(); }
   size_t size() const { return localIdx.size() + pl_lx.size(); }
 };
@@ -323,6 +326,11 @@ class Matcher_Points_DistanceThreshold : public Matcher {
   double threshold = 0.5;
   double thresholdAngularDeg = 0;
   uint32_t pairingsPerPoint = 1;
+  // U13 [U]: false = a point of a global layer is paired once per ICP iteration, by the first candidate in matching order
+  // (matchers in list order, pointLayerMatches entries in order, local points in ascending index); a candidate that finds its map
+  // point taken is dropped, not offered another.  Upstream's default is FALSE; this mirror's stays true (every reference pipeline
+  // writes true, and a changed default would change what existing configurations compute): a pipeline that relies on upstream's
+  // default has to write the key.
   bool allowMatchAlreadyMatchedGlobalPoints = true;
   struct LayerMatch {
     std::string global, local;
@@ -344,7 +352,7 @@ class Matcher_Point2Plane : public Matcher {
   double distanceThreshold = 0.5;
   double planeEigenThreshold = 0.01, searchRadius = 1.0;  // [U] defaults; every pipeline that uses them sets them
   uint32_t knn = 5, minimumPlanePoints = 5;
-  bool allowMatchAlreadyMatchedGlobalPoints = true;
+  bool allowMatchAlreadyMatchedGlobalPoints = true;  // parsed, not applied: a plane pairing names no map point (nothing to claim)
   std::vector<Matcher_Points_DistanceThreshold::LayerMatch> pointLayerMatches;
   void initialize(const Config& params) override;
 

@@ -364,8 +364,18 @@ void Matcher_Points_DistanceThreshold::impl_match(const metric_map_t& pcGlobal, 
     if (paired.size() < n) paired.resize(n, 0);
     std::vector<uint8_t> paired_before;
     if (skip_paired) paired_before = paired;  // (a point's own second pair is not "already paired by an earlier matcher")
+    // U13 (allowMatchAlreadyMatchedGlobalPoints: false): the pairs arrive in ascending local index, so this is upstream's serial
+    // walk [U] -- a candidate whose map point an earlier candidate of this iteration has taken is dropped, every other one takes
+    // its map point; with pairingsPerPoint > 1 each of a point's candidates on its own
+    const bool unique = !allowMatchAlreadyMatchedGlobalPoints;
+    std::vector<uint8_t>* const claimed = unique ? &out.global_paired[lm.global] : nullptr;
     for (size_t k = 0; k < info.n_pairs; k++) {
       if (skip_paired && paired_before[li[k]]) continue;
+      if (unique) {
+        if (claimed->size() <= gi[k]) claimed->resize((size_t)gi[k] + 1, 0);
+        if ((*claimed)[gi[k]]) continue;
+        (*claimed)[gi[k]] = 1;
+      }
       paired[li[k]] = 1;
       out.localIdx.push_back(li[k]);
       out.globalIdx.push_back(gi[k]);
@@ -386,6 +396,7 @@ void Matcher_Point2Plane::initialize(const Config& c) {
   parameterFromConfig(c, "searchRadius", &searchRadius, false);
   if (c.has("knn")) knn = to_u32(c["knn"].asString());
   if (c.has("minimumPlanePoints")) minimumPlanePoints = to_u32(c["minimumPlanePoints"].asString());
+  // (kept for the pipelines that write it; never applied -- plane pairings name no map point, so there is nothing to claim, U13)
   if (c.has("allowMatchAlreadyMatchedGlobalPoints"))
     allowMatchAlreadyMatchedGlobalPoints = to_bool(c["allowMatchAlreadyMatchedGlobalPoints"].asString());
   if (c.has("runFromIteration")) runFromIteration = to_u32(c["runFromIteration"].asString());
@@ -587,6 +598,8 @@ bool ICP::can_fuse() const {
   if (!(m->enabled && m->runFromIteration == 0 && m->runUpToIteration == 0 && m->pairingsPerPoint == 1 &&
         m->pointLayerMatches.size() == 1))  // (its weight: any -- the fused loop's solver takes it, round 5)
     return false;
+  // U13: the single-pair chains and the one-launch loops pair a map point as often as it is nearest (can_fuse_layers takes it)
+  if (!m->allowMatchAlreadyMatchedGlobalPoints) return false;
   if (matchers_.size() == 2) {
     auto pl = std::dynamic_pointer_cast<Matcher_Point2Plane>(matchers_[0]);
     if (!pl || !pl->enabled || pl->runFromIteration || pl->runUpToIteration || pl->pointLayerMatches.size() != 1) return false;
@@ -597,21 +610,22 @@ bool ICP::can_fuse() const {
 }
 
 // several point-layer pairs in one solve (lidar3d-dual-map.yaml:115-132, lidar3d-edges.yaml:120-129): one Solver_GaussNewton, only
-// enabled, ungated Matcher_Points_DistanceThreshold with pairingsPerPoint 1 that may match already matched global points, 2 to
-// MH_MAX_LAYER_PAIRS entries in all.  A local layer named by two entries is paired again for each: only under
+// enabled, ungated Matcher_Points_DistanceThreshold with pairingsPerPoint 1, 2 to MH_MAX_LAYER_PAIRS entries in all -- or 1 to
+// MH_MAX_LAYER_PAIRS when a matcher has allowMatchAlreadyMatchedGlobalPoints: false (U13: mh_icp_align_layers_opts is the one
+// device loop that implements it, the default pipeline's single pair included).  A local layer named by two entries is paired again for each: only under
 // MOLA_HIP_MATCHED_POINTS=again (skip would leave the second entry's points out, which mh_icp_align_layers does not do).
 bool ICP::can_fuse_layers() const {
   if (force_generic_ || iteration_hook_) return false;
   if (matchers_.empty() || solvers_.size() != 1 || !std::dynamic_pointer_cast<Solver_GaussNewton>(solvers_[0])) return false;
   std::vector<std::string> locals;
+  bool any_unique = false;
   for (const auto& mm : matchers_) {
     auto m = std::dynamic_pointer_cast<Matcher_Points_DistanceThreshold>(mm);
-    if (!m || !m->enabled || m->runFromIteration || m->runUpToIteration || m->pairingsPerPoint != 1 ||
-        !m->allowMatchAlreadyMatchedGlobalPoints)
-      return false;
+    if (!m || !m->enabled || m->runFromIteration || m->runUpToIteration || m->pairingsPerPoint != 1) return false;
+    any_unique = any_unique || (!m->allowMatchAlreadyMatchedGlobalPoints && !m->pointLayerMatches.empty());
     for (const auto& lm : m->pointLayerMatches) locals.push_back(lm.local);
   }
-  if (locals.size() < 2 || locals.size() > MH_MAX_LAYER_PAIRS) return false;
+  if (locals.size() < (any_unique ? 1u : 2u) || locals.size() > MH_MAX_LAYER_PAIRS) return false;
   std::sort(locals.begin(), locals.end());
   const bool shared = std::adjacent_find(locals.begin(), locals.end()) != locals.end();
   return !(shared && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP);
@@ -1325,6 +1339,8 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
     const DevicePointCloud* dev = nullptr;
   };
   std::vector<mh_layer_pair> pairs;
+  std::vector<mh_layer_pair_opts> opts;  // U13: a matcher's allowMatchAlreadyMatchedGlobalPoints: false, for each of its entries
+  bool any_unique = false;
   std::vector<Entry> entries;
   const auto& ctx0 = global_layer(pcGlobal, ms[0]->pointLayerMatches[0].global).context();
   if (scan_ctx_ && scan_ctx_ != ctx0) {
@@ -1363,6 +1379,8 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
       lp.threshold_angular_deg = ms[j]->thresholdAngularDeg;
       lp.weight = lm.weight;
       pairs.push_back(lp);
+      opts.push_back(mh_layer_pair_opts{ms[j]->allowMatchAlreadyMatchedGlobalPoints ? 0u : 1u});
+      any_unique = any_unique || opts.back().unique_global;
       entries.push_back(e);
     }
   mh_prior pr;
@@ -1380,13 +1398,20 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   }
   mh_icp_result r{};
   std::vector<mh_icp_iter> trace(p.generateDebugFiles ? mi : 0);
-  if (batcher_ && trace.empty() && !want_pairs) {
+  auto solo = [&] {
+    check(mh_icp_align_layers_opts(pairs.size(), pairs.data(), any_unique ? opts.data() : nullptr, &ip, guess.T, prior ? &pr : nullptr,
+                                   &r, trace.empty() ? nullptr : trace.data(), want_pairs ? po.data() : nullptr, counts.data(),
+                                   MH_MEM_HOST), "mh_icp_align_layers_opts");
+  };
+  if (batcher_ && any_unique) {
+    // (mh_icp_align_layers_batch has no unique form: on its own, the participant counted as busy meanwhile -- as align_generic)
+    batcher_->runOutside(batch_owner_, solo);
+  } else if (batcher_ && trace.empty() && !want_pairs) {
     std::string err;
     const mh_status st = batcher_->alignLayers(batch_owner_, pairs.size(), pairs.data(), &ip, guess.T, prior ? &pr : nullptr, &r, &err);
     if (st != MH_OK) throw std::runtime_error(std::string("mh_icp_align_layers_batch: ") + mh_status_string(st) + ": " + err);
   } else {
-    check(mh_icp_align_layers(pairs.size(), pairs.data(), &ip, guess.T, prior ? &pr : nullptr, &r, trace.empty() ? nullptr : trace.data(),
-                              want_pairs ? po.data() : nullptr, counts.data(), MH_MEM_HOST), "mh_icp_align_layers");
+    solo();
   }
   if (p.generateDebugFiles) write_debug_file(p, guess, r, trace, (size_t)r.potential_pairings);
   last_iterations_[call_kind] = r.n_iterations + (r.termination_reason == MH_TERM_MAX_ITERATIONS ? 0u : 1u);
