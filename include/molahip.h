@@ -45,7 +45,8 @@ extern "C" {
 #define MH_VERSION_PATCH 0
 /* The parameter structs of this header carry no size field: they grow at the END, and every growth bumps MH_ABI_VERSION (6:
  * mh_preprocess_params' two decimation-method fields, round 5; 7: mh_layer_pair and mh_icp_align_layers, later also
- * mh_curvature_params and mh_scan_curvature, then the intensity channel's entry points and mh_by_intensity_params: new structs
+ * mh_curvature_params and mh_scan_curvature, then the intensity channel's entry points and mh_by_intensity_params,
+ * mh_layer_pair_gates and mh_icp_align_layers_gated: new structs
  * and entry points change no existing layout, and a binder that lacks
  * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
@@ -620,8 +621,9 @@ MH_API mh_status mh_icp_align_batch(size_t n_jobs, const mh_map* const* maps, co
 
 /* Fused path over several point-layer pairs.  Replaces mp2p_icp::ICP::align [U] with an ICP block of one or more
  * Matcher_Points_DistanceThreshold whose pointLayerMatches hold several {global, local, weight} entries and one
- * Solver_GaussNewton (pipelines/extras/lidar3d-dual-map.yaml:115-132, lidar3d-edges.yaml:120-129; no runFromIteration /
- * runUpToIteration gates, pairingsPerPoint 1, allowMatchAlreadyMatchedGlobalPoints true).
+ * Solver_GaussNewton (pipelines/extras/lidar3d-dual-map.yaml:115-132, lidar3d-edges.yaml:120-129; pairingsPerPoint 1; matchers with
+ * allowMatchAlreadyMatchedGlobalPoints false: mh_icp_align_layers_opts, with runFromIteration / runUpToIteration gates
+ * (lidar3d-near-far.yaml:183): mh_icp_align_layers_gated, both below).
  *  - Matching: in every ICP iteration k, pair i runs the matcher of mh_nn_search on (map_i, scan_i): the 27-voxel exact search,
  *    accepted iff d^2 < (float)(threshold_i[k]^2) + ang_i^2*|p'|^2 with ang_i from threshold_angular_deg_i as in mh_icp_align.
  *  - Solve: the pairings of ALL pairs go to one robust Gauss-Newton solve; pair i's rows are scaled by weight_i.  Inner steps,
@@ -679,6 +681,37 @@ MH_API mh_status mh_icp_align_layers_opts(size_t n_pairs, const mh_layer_pair* p
                                           mh_icp_result* result, mh_icp_iter* trace,
                                           const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
                                           uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
+
+/* mh_icp_align_layers_opts with Matcher::runFromIteration / runUpToIteration per pair (lidar3d-near-far.yaml:183), the rule of
+ * Matcher::match [U].  (A struct and an entry point of their own: mh_layer_pair_opts keeps its layout and MH_ABI_VERSION its
+ * value.)  gates == NULL or every field 0 IS mh_icp_align_layers_opts: the same launches, the same graph keys, the same upload, the
+ * same bits (mh_icp_align_layers_opts calls this function with NULL).  Otherwise the contracts above, n_pairs 1 included, plus:
+ *  - Active: pair i is active in ICP iteration k iff (from == 0 || k >= from) && (up_to == 0 || k <= up_to).
+ *  - An inactive pair neither searches nor contributes: it has no pairings in that iteration (nothing in the solve, nothing in the
+ *    trace's n_pairs), makes and loses no claims when it is unique_global, has nothing in the covariance, nothing in final_pairs[i]
+ *    (the arrays are not written) and final_pair_counts[i] == 0.
+ *  - NoPairings is decided on the active pairs' sum: at iteration 0 when every pair is gated off there (n_iterations 0), in a later
+ *    iteration when the active set becomes empty.
+ *  - potential_pairings: with k_last the iteration whose match produced the final pairings (the one that terminated the loop, or
+ *    max_iterations - 1), the sum of scan_i->n over the pairs active in k_last; quality = n_final_pairs / potential_pairings.
+ *  - The trace's threshold stays pair 0's schedule entry, active or not.
+ *  - The launch count is unchanged (1 + 2 * inner, + 2 with a unique pair): the gates are data of the uploaded pair table, tested
+ *    on the device with the iteration counter; a cached graph is reused whatever the gates are, nothing of them is in its key.  An
+ *    inactive pair's match workgroups store "not paired" for its points instead of searching.
+ * No lock-step batch form: mh_icp_align_layers_batch has no gates; a gated alignment runs on its own beside the batches, as a
+ * unique one does. */
+typedef struct {
+  uint32_t run_from_iteration;   /* Matcher::runFromIteration, 0 = no limit */
+  uint32_t run_up_to_iteration;  /* Matcher::runUpToIteration, 0 = no limit */
+} mh_layer_pair_gates;
+
+MH_API mh_status mh_icp_align_layers_gated(size_t n_pairs, const mh_layer_pair* pairs,
+                                           const mh_layer_pair_opts* opts /* n_pairs entries or NULL */,
+                                           const mh_layer_pair_gates* gates /* n_pairs entries or NULL */,
+                                           const mh_icp_params* params, const double T_guess[12], const mh_prior* prior,
+                                           mh_icp_result* result, mh_icp_iter* trace,
+                                           const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
+                                           uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
 
 /* Many multi-layer alignments from one host thread, one context per job: mh_icp_align_batch for mh_icp_align_layers.  Job i has
  * all its maps and scans on ONE context, distinct jobs have distinct contexts of the same device, and each job's pairs obey the

@@ -130,6 +130,11 @@ class LayerPairOpts(C.Structure):
     _fields_ = [("unique_global", C.c_uint32)]
 
 
+class LayerPairGates(C.Structure):
+    """mh_layer_pair_gates: Matcher::runFromIteration / runUpToIteration of a pair (0 = no limit)."""
+    _fields_ = [("run_from_iteration", C.c_uint32), ("run_up_to_iteration", C.c_uint32)]
+
+
 class LayerJob(C.Structure):
     """mh_layer_job: the layer pairs of one job of mh_icp_align_layers_batch."""
     _fields_ = [("n_pairs", C.c_size_t), ("pairs", C.POINTER(LayerPair))]
@@ -234,6 +239,10 @@ _SIGNATURES = {
                                         C.POINTER(ICPResult), C.POINTER(ICPIter), C.POINTER(PairsOut),
                                         C.POINTER(C.c_uint64), C.c_int32]),
     "mh_icp_align_layers_opts": (C.c_int32, [C.c_size_t, C.POINTER(LayerPair), C.POINTER(LayerPairOpts), C.POINTER(ICPParamsC),
+                                             _DP, C.POINTER(Prior), C.POINTER(ICPResult), C.POINTER(ICPIter),
+                                             C.POINTER(PairsOut), C.POINTER(C.c_uint64), C.c_int32]),
+    "mh_icp_align_layers_gated": (C.c_int32, [C.c_size_t, C.POINTER(LayerPair), C.POINTER(LayerPairOpts), C.POINTER(LayerPairGates),
+                                              C.POINTER(ICPParamsC),
                                              _DP, C.POINTER(Prior), C.POINTER(ICPResult), C.POINTER(ICPIter),
                                              C.POINTER(PairsOut), C.POINTER(C.c_uint64), C.c_int32]),
     "mh_icp_align_layers_batch": (C.c_int32, [C.c_size_t, C.POINTER(LayerJob), C.POINTER(ICPParamsC), C.c_int32, _DP,
@@ -866,7 +875,8 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
     `pairs`: a sequence of dicts {map, scan, threshold, threshold_angular_deg=0, weight=1} or tuples in that order; a
     threshold is a scalar or max_iterations values.  p.threshold, p.threshold_angular_deg and p.gn.weight_pt2pt are not used.
     A dict may carry unique_global (allowMatchAlreadyMatchedGlobalPoints == false for that pair, U13): with one that is set the
-    call goes to mh_icp_align_layers_opts.
+    call goes to mh_icp_align_layers_opts; run_from_iteration / run_up_to_iteration (Matcher::runFromIteration / runUpToIteration,
+    0 = no limit): with one that is set it goes to mh_icp_align_layers_gated.
     Returns icp_align's dict plus pair_counts (final pairings per pair) and, with want_pairs, pairs (one dict per pair)."""
     p_c = replace(p, threshold=p.threshold if p.threshold is not None else 0.0)
     cp, keep = p_c.c(T_guess)
@@ -887,10 +897,19 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
             po[i] = PairsOut(li.ctypes.data_as(_UP), gi.ctypes.data_as(_UP), gx.ctypes.data_as(_FP), gy.ctypes.data_as(_FP),
                              gz.ctypes.data_as(_FP), d2.ctypes.data_as(_FP))
             bufs.append((li, gi, gx, gy, gz, d2))
+    opts = None
     if any(e.get("unique_global") for e in norm):
         opts = (LayerPairOpts * max(1, n_pairs))()
         for i, e in enumerate(norm):
             opts[i].unique_global = 1 if e.get("unique_global") else 0
+    if any(e.get("run_from_iteration") or e.get("run_up_to_iteration") for e in norm):
+        gates = (LayerPairGates * max(1, n_pairs))()
+        for i, e in enumerate(norm):
+            gates[i].run_from_iteration = int(e.get("run_from_iteration") or 0)
+            gates[i].run_up_to_iteration = int(e.get("run_up_to_iteration") or 0)
+        _chk(lib().mh_icp_align_layers_gated(n_pairs, arr, opts, gates, C.byref(cp), T0.ctypes.data_as(_DP),
+                                             C.byref(pr) if pr else None, C.byref(res), trace, po, counts, MEM_HOST))
+    elif opts is not None:
         _chk(lib().mh_icp_align_layers_opts(n_pairs, arr, opts, C.byref(cp), T0.ctypes.data_as(_DP), C.byref(pr) if pr else None,
                                             C.byref(res), trace, po, counts, MEM_HOST))
     else:

@@ -992,15 +992,23 @@ size_t mh_pairs_block_bytes(size_t n_scan_points) {
 
 #include "mh_icp_api.inl"    // mh_nn_search*, mh_gn_solve, mh_covariance
 
-mh_status mh_icp_align_layers_opts(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
-                                   const mh_icp_params* params, const double T_guess[12], const mh_prior* prior,
-                                   mh_icp_result* result, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
-                                   uint64_t* final_pair_counts, int32_t pairs_mem) {
+mh_status mh_icp_align_layers_gated(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
+                                    const mh_layer_pair_gates* gates, const mh_icp_params* params, const double T_guess[12],
+                                    const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
+                                    const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
   MH_TRY(check_layers_args(n_pairs, pairs, params, T_guess, result));
   MH_REQUIRE(!final_pairs || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
   MH_TRY(check_layers_supported(n_pairs, pairs, params));
   return align_layers(read_switches(), (uint32_t)n_pairs, pairs, params, T_guess, prior, result, trace, final_pairs,
-                      final_pair_counts, pairs_mem, opts);
+                      final_pair_counts, pairs_mem, opts, gates);
+}
+
+mh_status mh_icp_align_layers_opts(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
+                                   const mh_icp_params* params, const double T_guess[12], const mh_prior* prior,
+                                   mh_icp_result* result, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
+                                   uint64_t* final_pair_counts, int32_t pairs_mem) {
+  return mh_icp_align_layers_gated(n_pairs, pairs, opts, nullptr, params, T_guess, prior, result, trace, final_pairs,
+                                   final_pair_counts, pairs_mem);
 }
 
 mh_status mh_icp_align_layers(size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params, const double T_guess[12],

@@ -5,7 +5,10 @@
 // Per ICP iteration:  k_match_layers -> k_accum_layers(first) -> k_solve -> [k_accum_layers -> k_solve] x (inner - 1)
 // over ALL pairs, whatever their number (mh_k_layers.h); the covariance kernels close the chunk that ends the loop.  With a pair
 // whose map points pair once only (mh_icp_align_layers_opts, unique_global): k_claim_layers -> k_resolve_layers behind the match
-// (mh_k_claim.h), and the set of such pairs is part of the chunk's graph key.  Loop
+// (mh_k_claim.h), and the set of such pairs is part of the chunk's graph key.
+// Iteration gates (mh_icp_align_layers_gated): data of the uploaded table, tested on the device -- a pair outside its interval
+// has its match workgroups store "not paired" instead of searching, and every later kernel of the iteration then finds nothing
+// of it.  Nothing about the gates enters the graph key.  Loop
 // control is AlignJob's chunked one: a chunk of iterations is enqueued (replayed from a captured graph once its shape repeats,
 // MH_NO_GRAPH=1: never), the host waits for its event and reads the done flag.
 
@@ -28,7 +31,7 @@ struct LayersJob {
   const mh_layer_pair* pairs = nullptr;
   const mh_icp_params* p = nullptr;
   mh_icp_result* res = nullptr;
-  size_t total_n = 0;
+  mh_layer_pair_gates gates[MH_MAX_LAYER_PAIRS] = {};  // all zero: no gate
   bool trivial = false;       // nothing to run: the result is complete after start()
   LayersLayout L;
   const LayerTable* tab = nullptr;  // the pinned mirror of the device table (the pairing segments: count_pairs)
@@ -36,7 +39,17 @@ struct LayersJob {
 
   mh_status start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
                   const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
-                  const mh_layer_pair_opts* opts = nullptr);
+                  const mh_layer_pair_opts* opts = nullptr, const mh_layer_pair_gates* gates_ = nullptr);
+  uint32_t k_last = 0;        // after finish(): the ICP iteration whose match produced the final pairings
+  bool active_in(uint32_t i, uint32_t k) const {  // layer_active (mh_k_layers.h) on the host
+    return k >= gates[i].run_from_iteration && (gates[i].run_up_to_iteration == 0 || k <= gates[i].run_up_to_iteration);
+  }
+  // potential_pairings: the layer sizes of the pairs that are active in ICP iteration k (all of them without gates)
+  uint64_t potential_in(uint32_t k) const {
+    uint64_t s = 0;
+    for (uint32_t i = 0; i < np; i++) s += active_in(i, k) ? pairs[i].scan->n : 0;
+    return s;
+  }
   void finish(uint32_t polls, uint32_t enqueued);
   mh_status count_pairs(const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem);
   mh_status claims_begin(ClaimTable* ct);
@@ -85,7 +98,7 @@ mh_status LayersJob::claims_begin(ClaimTable* ct) {
 
 mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
                            const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
-                           const mh_layer_pair_opts* opts) {
+                           const mh_layer_pair_opts* opts, const mh_layer_pair_gates* gates_) {
   np = np_;
   pairs = pairs_;
   p = p_;
@@ -93,9 +106,9 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   ctx = pairs[0].scan->ctx;
   if (final_pair_counts)
     for (uint32_t i = 0; i < np; i++) final_pair_counts[i] = 0;
-  total_n = 0;
-  for (uint32_t i = 0; i < np; i++) total_n += pairs[i].scan->n;  // every pair adds its layer size
-  if ((trivial = begin_result(res, p, T0, total_n))) return MH_OK;
+  for (uint32_t i = 0; i < np; i++) gates[i] = gates_ ? gates_[i] : mh_layer_pair_gates{};
+  // (every pair gated off in iteration 0 is NoPairings there, like no points at all)
+  if ((trivial = begin_result(res, p, T0, potential_in(0)))) return MH_OK;
   MH_TRY(set_device(ctx));
   MH_TRY(ensure_state(ctx));
   hipStream_t s = ctx->stream;
@@ -170,6 +183,8 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     d.mk.w_pt2pt = pairs[i].weight;
     d.col_off = tab->blk_acc[i];
     d.cov_off = tab->blk_cov[i];
+    d.run_from = gates[i].run_from_iteration;
+    d.run_up_to = gates[i].run_up_to_iteration;
   }
   if (L.unique_mask) MH_TRY(claims_begin(reinterpret_cast<ClaimTable*>(ctx->h_layers.as<char>() + L.claim_off)));
   MH_HIP(hipMemcpyAsync(ctx->layers_tab.p, ctx->h_layers.p, up_bytes, hipMemcpyHostToDevice, s));
@@ -185,7 +200,9 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
 // the result from the state block read back into ctx->h_state once the loop has terminated (PairedRatio over all pairs)
 void LayersJob::finish(uint32_t polls, uint32_t enqueued) {
   if (p->poll_every == 0) ctx->layers_predicted = live_iterations(ctx->h_state);
-  read_result(ctx->h_state, p, res, total_n, 0u, polls, enqueued);
+  // the iteration whose match produced the final pairings: the one that terminated the loop, or the last of max_iterations
+  k_last = ctx->h_state->n_iterations < p->max_iterations ? ctx->h_state->n_iterations : p->max_iterations - 1;
+  read_result(ctx->h_state, p, res, potential_in(k_last), 0u, polls, enqueued);
 }
 
 // every pair's final pairings compacted out of its segment (into final_pairs[i] when given) and counted
@@ -195,7 +212,7 @@ mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* fina
   uint64_t sum = 0;
   for (uint32_t i = 0; i < np; i++) {
     uint64_t c = 0;
-    if (pairs[i].scan->n)
+    if (pairs[i].scan->n && active_in(i, k_last))  // (a pair that is gated off there holds "not paired" throughout)
       MH_TRY(compact_pairs_of(ctx, tab->d[i].pair_gidx, tab->d[i].pair_q, pairs[i].scan->n, final_pairs ? &final_pairs[i] : &none,
                               final_pairs ? pairs_mem : MH_MEM_DEVICE, &c));
     if (final_pair_counts) final_pair_counts[i] = c;
@@ -209,9 +226,10 @@ mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* fina
 
 mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pairs, const mh_icp_params* p, const double T0[12],
                        const mh_prior* prior, mh_icp_result* res, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
-                       uint64_t* final_pair_counts, int32_t pairs_mem, const mh_layer_pair_opts* opts = nullptr) {
+                       uint64_t* final_pair_counts, int32_t pairs_mem, const mh_layer_pair_opts* opts = nullptr,
+                       const mh_layer_pair_gates* gates = nullptr) {
   LayersJob job;
-  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts, opts));
+  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts, opts, gates));
   if (job.trivial) return MH_OK;
   mh_ctx* const ctx = job.ctx;
   const LayersLayout& L = job.L;

@@ -9,7 +9,8 @@
 //                     x, y, z and |w| stay, the next iteration's search bound is made of them
 // The kernel boundary is the ordering between the two: no grid synchronisation, no fences.  Integer min only, so the verdict does
 // not depend on scheduling.  Both walk a flattened block range over the unique pairs (layer_of, mh_k_layers.h); pairs that are not
-// unique own no workgroup of it and neither test nor set claims.
+// unique own no workgroup of it and neither test nor set claims; a unique pair outside its runFromIteration / runUpToIteration
+// interval (layer_active, mh_k_layers.h) leaves both at once: it makes and loses no claims in that iteration.
 //
 // The claim table: one 64-bit entry per SOURCE INDEX of the map (mh_map_info::n_offered entries) -- the index the pairings report
 // and the only name of a map point that match_flat_wave leaves behind (the record's position is not stored); a map that has
@@ -49,6 +50,7 @@ __global__ __launch_bounds__(kBlock) void k_claim_layers(const IcpDeviceState* _
   const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
   const cclaim_ptr cc = (cclaim_ptr)uniform_const_ptr(claims);
   const uint32_t li = layer_of(cc->blk, ct->n_pairs, blockIdx.x);
+  if (!layer_active(ct, li, cst->iter)) return;  // (wave-uniform; k_match_layers has left kNoMatch in its whole segment)
   const uint32_t i = (blockIdx.x - cc->blk[li]) * kBlock + threadIdx.x;
   if (i >= ct->d[li].n) return;
   const uint32_t g = G(ct->d[li].pair_gidx)[i];
@@ -64,6 +66,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve_layers(const IcpDeviceState*
   const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
   const cclaim_ptr cc = (cclaim_ptr)uniform_const_ptr(claims);
   const uint32_t li = layer_of(cc->blk, ct->n_pairs, blockIdx.x);
+  if (!layer_active(ct, li, cst->iter)) return;  // (wave-uniform; k_match_layers has left kNoMatch in its whole segment)
   const uint32_t i = (blockIdx.x - cc->blk[li]) * kBlock + threadIdx.x;
   if (i >= ct->d[li].n) return;
   uint32_t* const gidx = ct->d[li].pair_gidx;

@@ -8,6 +8,10 @@
 //   k_accum_layers    k_accum_body<true> with the pair's MatchK (its weight), into its columns of the shared partials
 //   k_cov_accum_layers  k_cov_accum_body over the pair's pairings, into its columns of the covariance partials
 // k_solve / k_cov_prepare / k_cov_finalize are launched as they are over all columns (fixed order: bitwise reproducible).
+// Iteration gates (mh_icp_align_layers_gated): run_from / run_up_to of a pair's descriptor against the state's iteration counter,
+// both wave-uniform.  k_match_layers is where a gate acts: a pair outside its interval gets "not paired" stored for every point
+// instead of a search, and the accumulation, the covariance and the compaction then find nothing of it in what they read anyway
+// (zero columns in every accumulation launch).  An ungated table (both words 0) takes the branches it always took.
 //
 // mh_icp_align_layers_batch (the *_layers_b entry points): the flattened range one level up.  A device-resident job table holds,
 // per job, its own LayerTable (built as for a single call), its state block and its partials; job j owns the workgroups
@@ -26,6 +30,8 @@ struct LayerDesc {
   uint32_t n;
   uint32_t col_off;     // first column of its k_accum partials
   uint32_t cov_off;     // first column of its covariance partials
+  uint32_t run_from;    // Matcher::runFromIteration / runUpToIteration of this pair (mh_icp_align_layers_gated), 0 = no limit: the
+  uint32_t run_up_to;   // pair searches in ICP iteration k iff layer_active(k)
   uint32_t pad;
 };
 
@@ -46,6 +52,13 @@ __device__ __forceinline__ uint32_t layer_of(const uint32_t __attribute__((addre
   return li;
 }
 
+// Matcher::match's gate [U]: pair li takes part in ICP iteration `iter`.  Table and iteration are wave-uniform: scalar loads, scalar
+// compares.  (from == 0 needs no test of its own: iter >= 0.)
+__device__ __forceinline__ bool layer_active(const clayers_ptr ct, uint32_t li, uint32_t iter) {
+  const uint32_t from = ct->d[li].run_from, up_to = ct->d[li].run_up_to;
+  return iter >= from && (up_to == 0u || iter <= up_to);
+}
+
 // one wave of pair-owned matching: workgroup `b` of the table's flattened match range (`cst`: the alignment's state, not terminated)
 typedef const IcpDeviceState __attribute__((address_space(4))) * clayers_state_ptr;
 __device__ __forceinline__ void match_layers_wave(FlatWave& sh, const clayers_state_ptr cst, const clayers_ptr ct, const uint32_t b) {
@@ -53,6 +66,18 @@ __device__ __forceinline__ void match_layers_wave(FlatWave& sh, const clayers_st
   const uint32_t n = ct->d[li].n;
   const uint32_t i0 = (b - ct->blk_match[li]) * kFlatPointsPerBlock + (threadIdx.x & ~63u);
   if (i0 >= n) return;    // whole waves
+  const uint32_t iter = cst->iter;
+  if (!layer_active(ct, li, iter)) {
+    // A pair outside its iterations neither searches nor contributes: every point "not paired" (the verdict k_accum_body<true>
+    // reads in the sign, the index the claims, the covariance and the compaction read), whatever its segment held -- its own last
+    // active iteration's pairings or another alignment's.  One streaming store per point; no bound is left behind (|w| = inf).
+    const uint32_t i = i0 + (uint32_t)__lane_id();
+    if (i < n) {
+      G(reinterpret_cast<f32x4*>(ct->d[li].pair_q))[i] = (f32x4){0.f, 0.f, 0.f, -__builtin_inff()};
+      G(ct->d[li].pair_gidx)[i] = kNoMatch;
+    }
+    return;
+  }
   // field by field: scalar loads through the constant-space table (a MapView field added in mh_internal.h has to be added here:
   // the static_assert below fails until it is)
 #ifdef MH_DEBUG_WAVETRACE
@@ -73,8 +98,8 @@ __device__ __forceinline__ void match_layers_wave(FlatWave& sh, const clayers_st
 #ifdef MH_DEBUG_WAVETRACE
   map.dbg_stop = ct->d[li].map.dbg_stop;
 #endif
-  const uint32_t iter = cst->iter;
-  const bool have_prev = iter > 0 && !map.no_prev_bound;
+  // (the first active iteration of a pair finds no pairings of its own in its segment: unbounded, like iteration 0)
+  const bool have_prev = iter > ct->d[li].run_from && !map.no_prev_bound;
   double T[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) T[k] = cst->T[k];

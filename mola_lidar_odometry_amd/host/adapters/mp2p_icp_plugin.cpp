@@ -34,7 +34,8 @@
 // without the key runs here, mh_icp_align_layers_opts with unique_global) --, each with its own threshold schedule, angular term and weight; pairs in upstream's matching
 // order (matchers in list order, then weight_pt2pt_layers' std::map order: global name, then local name).  A local layer named by
 // two entries is paired again for each unless allowMatchAlreadyMatchedPoints is false and MOLA_HIP_MATCHED_POINTS=skip (then the
-// upstream loop runs).  Gated blocks (extras/lidar3d-near-far.yaml) go to the upstream loop.
+// upstream loop runs).  Gated blocks (extras/lidar3d-near-far.yaml) go to the upstream loop unless MOLA_HIP_FUSE_GATES=1: then to
+// mh_icp_align_layers_gated, a single gated pair included.
 // Global layers read: mola::HashedVoxelPointCloud (yaml:230), mola::NDT (ndt yaml:236) -- through their point / voxel
 // visitors, they are NOT mrpt::maps::CPointsMap --, mola::HashedVoxelPointCloudHIP (device owned, no mirror), and any
 // CPointsMap (pipelines/extras/localmap_definition_pointmap.ini).
@@ -133,6 +134,7 @@ struct LayerShape
     const Solver_GaussNewton* gn = nullptr;
     std::vector<Entry> entries;
     bool any_unique = false;  // some matcher has allowMatchAlreadyMatchedGlobalPoints false (U13)
+    bool any_gate = false;    // some matcher has runFromIteration / runUpToIteration (MOLA_HIP_FUSE_GATES=1)
 };
 
 template <class M> bool single_unit_layer(const M& m, std::string& g, std::string& l, double* weight_out = nullptr)
@@ -385,7 +387,12 @@ class ICP_HIP : public ICP
         for (const auto& mp : matchers())
         {
             const auto* m = dynamic_cast<const Matcher_Points_DistanceThreshold*>(mp.get());
-            if (!m || !m->enabled || m->runFromIteration != 0 || m->runUpToIteration != 0 || m->pairingsPerPoint != 1) return false;
+            if (!m || !m->enabled || m->pairingsPerPoint != 1) return false;
+            if (m->runFromIteration != 0 || m->runUpToIteration != 0)  // [U] iteration gates: the device tests them per pair
+            {
+                if (!molahip_host::fuse_gates(false, molahip_host::plugin_switches())) return false;
+                if (!m->weight_pt2pt_layers.empty()) ls.any_gate = true;
+            }
             // U13: a matcher that pairs a map point once per iteration (the claims of mh_icp_align_layers_opts)
             if (!m->allowMatchAlreadyMatchedGlobalPoints && !m->weight_pt2pt_layers.empty()) ls.any_unique = true;
             if (!m->allowMatchAlreadyMatchedPoints_ && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP)
@@ -403,7 +410,7 @@ class ICP_HIP : public ICP
                     ls.entries.push_back(e);
                 }
         }
-        if (ls.entries.size() < (ls.any_unique ? 1u : 2u) || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
+        if (ls.entries.size() < (ls.any_unique || ls.any_gate ? 1u : 2u) || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
         for (size_t i = 0; i < ls.entries.size(); i++)
             for (size_t j = i + 1; j < ls.entries.size(); j++)
                 if (skip_paired && ls.entries[i].localLayer == ls.entries[j].localLayer) return false;
@@ -424,10 +431,13 @@ class ICP_HIP : public ICP
         std::vector<const mrpt::maps::CPointsMap*> locals(np);
         std::vector<mh_layer_pair> pairs(np);
         std::vector<mh_layer_pair_opts> opts(np);
+        std::vector<mh_layer_pair_gates> gates(np);
         for (size_t i = 0; i < np; i++)
         {
             const auto& e = ls.entries[i];
             opts[i].unique_global = e.m->allowMatchAlreadyMatchedGlobalPoints ? 0u : 1u;
+            gates[i].run_from_iteration = e.m->runFromIteration;
+            gates[i].run_up_to_iteration = e.m->runUpToIteration;
             mh_map* m = dev_->device_map_of(*pcGlobal.layers.at(e.globalLayer), false);  // every global layer mirrored
             locals[i] = dynamic_cast<const mrpt::maps::CPointsMap*>(pcLocal.layers.at(e.localLayer).get());
             if (!m || !locals[i]) return upstream_align(pcLocal, pcGlobal, guess, p, result, prior, outputDebugInfo);
@@ -492,8 +502,9 @@ class ICP_HIP : public ICP
             q.max_iterations = budget;
             q.kernel_param   = kp.data();
             mh_icp_result rr{};
-            mh_check(mh_icp_align_layers_opts(np, pairs.data(), ls.any_unique ? opts.data() : nullptr, &q, T0, prior ? &pr : nullptr, &rr,
-                                              trace, po.data(), counts.data(), MH_MEM_HOST), "mh_icp_align_layers_opts");
+            mh_check(mh_icp_align_layers_gated(np, pairs.data(), ls.any_unique ? opts.data() : nullptr,
+                                               ls.any_gate ? gates.data() : nullptr, &q, T0, prior ? &pr : nullptr, &rr, trace,
+                                               po.data(), counts.data(), MH_MEM_HOST), "mh_icp_align_layers_gated");
             return rr;
         };
         auto run = [&](uint32_t budget, mh_icp_iter* trace) {

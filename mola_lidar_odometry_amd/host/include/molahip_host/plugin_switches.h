@@ -15,6 +15,9 @@
 //   MOLA_HIP_PT2PL_MODE       plane | centroid                                                                U10
 //   MOLA_HIP_FAR_VOXEL_METRIC chebyshev | l1 | l2     (device-owned maps: remove_voxels_farther_than, yaml:238) a8
 //   MOLA_HIP_FORCE_CPU        0 | 1                   (adapter only: every call to the upstream loop)
+//   MOLA_HIP_FUSE_GATES       (unset) | 0 | 1         matchers with runFromIteration / runUpToIteration on the fused multi-layer
+//                                                     loop (mh_icp_align_layers_gated); set, it overrides ICP::fuseGatedMatchers
+//                                                     and the adapter's default (off) both ways
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -33,6 +36,7 @@ struct PluginSwitches {
   uint32_t far_voxel_metric = MH_FAR_CHEBYSHEV;
   uint32_t matched_points = MH_MATCHED_POINTS_PAIR_AGAIN;  // MOLA_HIP_MATCHED_POINTS = again | skip (U12)
   bool force_cpu = false;
+  int fuse_gates = -1;  // MOLA_HIP_FUSE_GATES: -1 not set (the caller's own setting holds), 0 | 1
   // which of them came from the environment (the mirror classes only override their YAML values for those)
   bool has_gm_form = false, has_index_mode = false, has_cov_step = false, has_min_delta = false, has_max_cost = false,
        has_pt2pl_mode = false, has_far_metric = false;
@@ -85,6 +89,7 @@ inline PluginSwitches read_plugin_switches() {
   if (const char* e = getenv("MOLA_HIP_MATCHED_POINTS"))
     s.matched_points = (!strcmp(e, "skip") || !strcmp(e, "1")) ? MH_MATCHED_POINTS_SKIP : MH_MATCHED_POINTS_PAIR_AGAIN;
   if (const char* e = getenv("MOLA_HIP_FORCE_CPU")) s.force_cpu = atoi(e) != 0;
+  if (const char* e = getenv("MOLA_HIP_FUSE_GATES")) s.fuse_gates = atoi(e) != 0 ? 1 : 0;
   return s;
 }
 
@@ -95,6 +100,9 @@ inline PluginSwitches& plugin_switches_storage() {
 inline const PluginSwitches& plugin_switches() { return plugin_switches_storage(); }
 /** Re-read the environment (tests; a sweep driver that changes the variables inside one process). */
 inline void reload_plugin_switches() { plugin_switches_storage() = read_plugin_switches(); }
+
+/** Whether gated matchers go to the fused multi-layer loop: the environment when it says so, else the caller's `setting`. */
+inline bool fuse_gates(bool setting, const PluginSwitches& sw) { return sw.fuse_gates < 0 ? setting : sw.fuse_gates != 0; }
 
 /** MH_KERNEL_* for the NAME of an upstream mp2p_icp::RobustKernel enumerator [U] (names, not numeric values: the
  *  upstream enum's values are not relied on).  "GemanMcClure" resolves to the switched form. */

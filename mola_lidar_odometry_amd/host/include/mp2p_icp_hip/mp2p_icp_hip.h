@@ -562,8 +562,13 @@ class ICP {
   // false: Results::finalPairings stays empty in the fused path (the odometry driver never reads it)
   void setKeepFinalPairings(bool v) { keep_pairings_ = v; }
   void forceGenericPath(bool v) { force_generic_ = v; }
+  // true: Matcher_Points_DistanceThreshold with runFromIteration / runUpToIteration (lidar3d-near-far.yaml:183) run on the fused
+  // multi-layer loop (mh_icp_align_layers_gated) instead of forcing the generic one.  Default false: a pipeline keeps the path it
+  // had.  MOLA_HIP_FUSE_GATES=0|1 overrides it both ways.
+  void fuseGatedMatchers(bool v) { fuse_gated_ = v; }
   // the path align() takes for the configured pipeline (no alignment): "single" (mh_icp_align: lidar3d-default / -ndt shapes),
-  // "layers" (mh_icp_align_layers: several point-layer pairs, lidar3d-dual-map / -edges shapes) or "generic" (matcher by matcher).
+  // "layers" (mh_icp_align_layers: several point-layer pairs, lidar3d-dual-map / -edges shapes; with fuseGatedMatchers also gated
+  // ones, lidar3d-near-far) or "generic" (matcher by matcher).
   // "layers" also needs the maps handed to align() to qualify (global layers HashedVoxelPointCloud on one context, local layers
   // PointCloud / DevicePointCloud); otherwise that call runs the generic loop.
   std::string alignPath() const;
@@ -609,7 +614,7 @@ class ICP {
   mh_scan* scan_ = nullptr;                 // staging layer for host point clouds handed to the fused path ...
   std::shared_ptr<DeviceContext> scan_ctx_;  // ... and the (map's) context it lives in, kept alive until ~ICP has destroyed it
   std::map<std::string, mh_scan*> layer_scans_;  // align_fused_layers: a staging layer per host local layer (in scan_ctx_)
-  bool last_fused_ = false, force_generic_ = false, keep_pairings_ = true, hook_replay_ = false;
+  bool last_fused_ = false, force_generic_ = false, keep_pairings_ = true, hook_replay_ = false, fuse_gated_ = false;
   std::shared_ptr<AlignBatcher> batcher_;
   const void* batch_owner_ = nullptr;
   // how long the previous call of each kind ran: [0] calls with the full iteration budget, [1] re-entries after a hook

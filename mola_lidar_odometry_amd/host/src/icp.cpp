@@ -326,6 +326,17 @@ static const PointCloud& local_layer(const metric_map_t& m, const std::string& n
   if (!p) throw std::runtime_error("local layer '" + name + "' is not a point cloud");
   return *p;
 }
+// ... for the matcher-granular loop, which reads the local points on the host: a device-resident layer (the stand-alone driver's
+// general plans hand over DevicePointCloud) is downloaded into `downloaded` first
+static const PointCloud& local_layer(const metric_map_t& m, const std::string& name, PointCloud& downloaded) {
+  auto it = m.layers.find(name);
+  if (it != m.layers.end())
+    if (auto dev = std::dynamic_pointer_cast<DevicePointCloud>(it->second)) {
+      dev->download(downloaded.x, downloaded.y, downloaded.z);
+      return downloaded;
+    }
+  return local_layer(m, name);
+}
 static const HashedVoxelPointCloud& global_layer(const metric_map_t& m, const std::string& name) {
   auto it = m.layers.find(name);
   if (it == m.layers.end()) throw std::runtime_error("global layer '" + name + "' not found");
@@ -337,7 +348,8 @@ static const HashedVoxelPointCloud& global_layer(const metric_map_t& m, const st
 void Matcher_Points_DistanceThreshold::impl_match(const metric_map_t& pcGlobal, const metric_map_t& pcLocal,
                                                   const CPose3D& localPose, const MatchContext&, Pairings& out) const {
   for (const auto& lm : pointLayerMatches) {
-    const PointCloud& loc = local_layer(pcLocal, lm.local);
+    PointCloud downloaded;
+    const PointCloud& loc = local_layer(pcLocal, lm.local, downloaded);
     const HashedVoxelPointCloud& glob = global_layer(pcGlobal, lm.global);
     const size_t n = loc.size();
     out.potential_pairings += n * pairingsPerPoint;
@@ -610,22 +622,27 @@ bool ICP::can_fuse() const {
 }
 
 // several point-layer pairs in one solve (lidar3d-dual-map.yaml:115-132, lidar3d-edges.yaml:120-129): one Solver_GaussNewton, only
-// enabled, ungated Matcher_Points_DistanceThreshold with pairingsPerPoint 1, 2 to MH_MAX_LAYER_PAIRS entries in all -- or 1 to
+// enabled Matcher_Points_DistanceThreshold with pairingsPerPoint 1, 2 to MH_MAX_LAYER_PAIRS entries in all -- or 1 to
 // MH_MAX_LAYER_PAIRS when a matcher has allowMatchAlreadyMatchedGlobalPoints: false (U13: mh_icp_align_layers_opts is the one
-// device loop that implements it, the default pipeline's single pair included).  A local layer named by two entries is paired again for each: only under
+// device loop that implements it, the default pipeline's single pair included) or an iteration gate.  Gated matchers
+// (runFromIteration / runUpToIteration, lidar3d-near-far.yaml:183) only with fuseGatedMatchers / MOLA_HIP_FUSE_GATES=1
+// (mh_icp_align_layers_gated); otherwise they keep the generic loop.  A local layer named by two entries is paired again for each: only under
 // MOLA_HIP_MATCHED_POINTS=again (skip would leave the second entry's points out, which mh_icp_align_layers does not do).
 bool ICP::can_fuse_layers() const {
   if (force_generic_ || iteration_hook_) return false;
   if (matchers_.empty() || solvers_.size() != 1 || !std::dynamic_pointer_cast<Solver_GaussNewton>(solvers_[0])) return false;
   std::vector<std::string> locals;
-  bool any_unique = false;
+  bool single_pair_ok = false;  // a unique or gated matcher: shapes only the multi-layer loop takes, a single pair included
+  const bool gates_ok = molahip_host::fuse_gates(fuse_gated_, molahip_host::plugin_switches());
   for (const auto& mm : matchers_) {
     auto m = std::dynamic_pointer_cast<Matcher_Points_DistanceThreshold>(mm);
-    if (!m || !m->enabled || m->runFromIteration || m->runUpToIteration || m->pairingsPerPoint != 1) return false;
-    any_unique = any_unique || (!m->allowMatchAlreadyMatchedGlobalPoints && !m->pointLayerMatches.empty());
+    if (!m || !m->enabled || m->pairingsPerPoint != 1) return false;
+    const bool gated = m->runFromIteration || m->runUpToIteration;
+    if (gated && !gates_ok) return false;
+    single_pair_ok = single_pair_ok || ((!m->allowMatchAlreadyMatchedGlobalPoints || gated) && !m->pointLayerMatches.empty());
     for (const auto& lm : m->pointLayerMatches) locals.push_back(lm.local);
   }
-  if (locals.size() < (any_unique ? 1u : 2u) || locals.size() > MH_MAX_LAYER_PAIRS) return false;
+  if (locals.size() < (single_pair_ok ? 1u : 2u) || locals.size() > MH_MAX_LAYER_PAIRS) return false;
   std::sort(locals.begin(), locals.end());
   const bool shared = std::adjacent_find(locals.begin(), locals.end()) != locals.end();
   return !(shared && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP);
@@ -1340,7 +1357,8 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   };
   std::vector<mh_layer_pair> pairs;
   std::vector<mh_layer_pair_opts> opts;  // U13: a matcher's allowMatchAlreadyMatchedGlobalPoints: false, for each of its entries
-  bool any_unique = false;
+  std::vector<mh_layer_pair_gates> gates;  // a matcher's runFromIteration / runUpToIteration, for each of its entries
+  bool any_unique = false, any_gate = false;
   std::vector<Entry> entries;
   const auto& ctx0 = global_layer(pcGlobal, ms[0]->pointLayerMatches[0].global).context();
   if (scan_ctx_ && scan_ctx_ != ctx0) {
@@ -1381,6 +1399,8 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
       pairs.push_back(lp);
       opts.push_back(mh_layer_pair_opts{ms[j]->allowMatchAlreadyMatchedGlobalPoints ? 0u : 1u});
       any_unique = any_unique || opts.back().unique_global;
+      gates.push_back(mh_layer_pair_gates{ms[j]->runFromIteration, ms[j]->runUpToIteration});
+      any_gate = any_gate || ms[j]->runFromIteration || ms[j]->runUpToIteration;
       entries.push_back(e);
     }
   mh_prior pr;
@@ -1399,12 +1419,13 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   mh_icp_result r{};
   std::vector<mh_icp_iter> trace(p.generateDebugFiles ? mi : 0);
   auto solo = [&] {
-    check(mh_icp_align_layers_opts(pairs.size(), pairs.data(), any_unique ? opts.data() : nullptr, &ip, guess.T, prior ? &pr : nullptr,
-                                   &r, trace.empty() ? nullptr : trace.data(), want_pairs ? po.data() : nullptr, counts.data(),
-                                   MH_MEM_HOST), "mh_icp_align_layers_opts");
+    check(mh_icp_align_layers_gated(pairs.size(), pairs.data(), any_unique ? opts.data() : nullptr, any_gate ? gates.data() : nullptr,
+                                    &ip, guess.T, prior ? &pr : nullptr, &r, trace.empty() ? nullptr : trace.data(),
+                                    want_pairs ? po.data() : nullptr, counts.data(), MH_MEM_HOST), "mh_icp_align_layers_gated");
   };
-  if (batcher_ && any_unique) {
-    // (mh_icp_align_layers_batch has no unique form: on its own, the participant counted as busy meanwhile -- as align_generic)
+  if (batcher_ && (any_unique || any_gate)) {
+    // (mh_icp_align_layers_batch has no unique or gated form: on its own, the participant counted as busy meanwhile -- as
+    // align_generic)
     batcher_->runOutside(batch_owner_, solo);
   } else if (batcher_ && trace.empty() && !want_pairs) {
     std::string err;

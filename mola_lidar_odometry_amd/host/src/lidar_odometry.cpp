@@ -673,6 +673,7 @@ void LidarOdometry::initialize(const Config& cfg) {
   for (auto& icp : icp_) {
     icp->attachToParameterSource(source_);
     icp->setKeepFinalPairings(false);
+    icp->fuseGatedMatchers(true);  // gated blocks (lidar3d-near-far.yaml:183) on the device loop; MOLA_HIP_FUSE_GATES=0: as before
   }
   // local map definition (yaml:213-242), instantiated at the first key-frame when its $f{} formulas can be evaluated
   const Config& gen = cfg["localmap_generator"];

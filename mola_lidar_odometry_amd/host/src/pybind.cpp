@@ -62,6 +62,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["far_voxel_metric"] = s.far_voxel_metric; d["force_cpu"] = s.force_cpu;
     return d;
   });
+  m.def("plugin_switch_fuse_gates", [] { return molahip_host::plugin_switches().fuse_gates; });  // MOLA_HIP_FUSE_GATES: -1 not set (a function of its own: the keys of plugin_switches() are compared as a whole by their users)
   m.def("kernel_from_upstream_name", [](const std::string& n) { return molahip_host::kernel_from_upstream_name(n.c_str(), molahip_host::plugin_switches()); });
   m.def("term_reason_name", [](uint32_t t) { return std::string(enum2str(molahip_host::term_reason_to<IterTermReason>(t))); });
   m.def("evaluate_compiled", [](const std::string& e, const std::map<std::string, double>& v) { return CompiledExpression(e).evaluate(v); });
@@ -108,6 +109,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("cov", [](const Results& r) { return std::vector<double>(r.optimal_tf.cov, r.optimal_tf.cov + 36); })
       .def("n_pairs", [](const Results& r) { return r.finalPairings.size(); })
       .def("n_pairs_pt2pl", [](const Results& r) { return r.finalPairings.pl_lx.size(); })
+      .def("potential_pairings", [](const Results& r) { return r.finalPairings.potential_pairings; })
       .def("pair_global_idx", [](const Results& r) { return r.finalPairings.globalIdx; })
       .def("pair_local_idx", [](const Results& r) { return r.finalPairings.localIdx; });
   py::class_<ICP, std::shared_ptr<ICP>>(m, "ICP")
@@ -118,6 +120,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("setDeviceHook", &ICP::setDeviceHook)
       .def("clearHooks", &ICP::clearHooks)
       .def("forceGenericPath", &ICP::forceGenericPath)
+      .def("fuseGatedMatchers", &ICP::fuseGatedMatchers)
       .def("alignPath", &ICP::alignPath)
       .def("precomputeSchedule", &ICP::precomputeSchedule)
       .def("setHookReplay", &ICP::setHookReplay)
