@@ -46,7 +46,7 @@ extern "C" {
 /* The parameter structs of this header carry no size field: they grow at the END, and every growth bumps MH_ABI_VERSION (6:
  * mh_preprocess_params' two decimation-method fields, round 5; 7: mh_layer_pair and mh_icp_align_layers, later also
  * mh_curvature_params and mh_scan_curvature, then the intensity channel's entry points and mh_by_intensity_params,
- * mh_layer_pair_gates and mh_icp_align_layers_gated: new structs
+ * mh_layer_pair_gates and mh_icp_align_layers_gated, mh_layer_pair_knn and mh_icp_align_layers_kbest: new structs
  * and entry points change no existing layout, and a binder that lacks
  * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
@@ -713,6 +713,42 @@ MH_API mh_status mh_icp_align_layers_gated(size_t n_pairs, const mh_layer_pair* 
                                            const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
                                            uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
 
+/* mh_icp_align_layers_gated with Matcher_Points_DistanceThreshold::pairingsPerPoint per pair (lidar2d.yaml:156, rgbd.yaml:138 use
+ * 2).  (A struct and an entry point of their own again: the structs above keep their layout and MH_ABI_VERSION its value.)
+ * knn == NULL or every entry 0 or 1 IS mh_icp_align_layers_gated: the same launches, the same graph keys, the same upload, the same
+ * bits (mh_icp_align_layers_gated calls this function with NULL).  Otherwise the contracts above, n_pairs 1 included, plus, with
+ * k_i = pairings_per_point of pair i:
+ *  - Matching: in every iteration in which it is active, pair i runs the matcher of mh_nn_search_k with k_i: per local point the
+ *    k_i smallest (d^2, scan position) of the 27-voxel block, in that order, accepted in that order while d^2 < (float)(thr^2) +
+ *    ang^2*|p'|^2 -- the accepted ones are a prefix.
+ *  - Solve: every accepted pairing is one row block of the Gauss-Newton sums, scaled by the pair's weight; a local point
+ *    contributes up to k_i times.
+ *  - Counts: potential_pairings = sum of scan_i->n * k_i over the pairs active in k_last (pcLocal.size() * pairingsPerPoint [U], as
+ *    mh_nn_search_k reports it); quality, the trace's n_pairs and n_final_pairs count pairings.
+ *  - final_pairs[i]: arrays of scan_i->n * k_i entries, in ascending local index, a point's pairings in ascending distance (the
+ *    order of mh_nn_search_k).
+ *  - unique_global: the matching order gains a third level -- pair, local index, rank; each of a point's candidates is tested, and
+ *    claims, on its own.
+ *  - Gates: an inactive pair has no pairing in any of its scan_i->n * k_i entries.
+ *  - One more launch per ICP iteration when any k_i > 1 (the search of those pairs), whatever their number; the set of such pairs
+ *    and their k are part of the graph key.  Results are bitwise reproducible, MH_NO_GRAPH=1 and MH_NO_PREV_BOUND=1 included.
+ *  - MH_ERR_INVALID_ARGUMENT: a pairings_per_point above MH_MAX_PAIRINGS_PER_POINT.  MH_ERR_UNSUPPORTED: scan_i->n * k_i >= 2^32, or
+ *    >= 2^29 on a unique pair (the claim key's local field).
+ * No lock-step batch form: mh_icp_align_layers_batch has no knn; such an alignment runs on its own beside the batches, as a gated
+ * or a unique one does. */
+typedef struct {
+  uint32_t pairings_per_point;  /* 0 or 1: one; up to MH_MAX_PAIRINGS_PER_POINT */
+} mh_layer_pair_knn;
+
+MH_API mh_status mh_icp_align_layers_kbest(size_t n_pairs, const mh_layer_pair* pairs,
+                                           const mh_layer_pair_opts* opts /* n_pairs entries or NULL */,
+                                           const mh_layer_pair_gates* gates /* n_pairs entries or NULL */,
+                                           const mh_layer_pair_knn* knn /* n_pairs entries or NULL */,
+                                           const mh_icp_params* params, const double T_guess[12], const mh_prior* prior,
+                                           mh_icp_result* result, mh_icp_iter* trace,
+                                           const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
+                                           uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
+
 /* Many multi-layer alignments from one host thread, one context per job: mh_icp_align_batch for mh_icp_align_layers.  Job i has
  * all its maps and scans on ONE context, distinct jobs have distinct contexts of the same device, and each job's pairs obey the
  * contract above.  Job i uses params[i] when params_per_job != 0 (else the one *params), T_guesses + 12*i and priors[i] (array or
@@ -729,7 +765,8 @@ MH_API mh_status mh_icp_align_layers_gated(size_t n_pairs, const mh_layer_pair* 
  *  - Work still queued on the jobs' own streams is ordered before the batch.
  *  - Everything is validated before any device work.  MH_ERR_INVALID_ARGUMENT: n_jobs 0 or above MH_MAX_LAYER_BATCH_JOBS, a job
  *    that mh_icp_align_layers rejects with that code, two jobs on one context, jobs on different devices.  MH_ERR_UNSUPPORTED: a
- *    job that mh_icp_align_layers rejects with that code.  After an error every context stays usable. */
+ *    job that mh_icp_align_layers rejects with that code.  After an error every context stays usable.
+ *  - No opts, gates or knn: a unique, gated or pairingsPerPoint > 1 alignment runs on its own beside the batches. */
 #define MH_MAX_LAYER_BATCH_JOBS 64
 typedef struct {
   size_t n_pairs;              /* 1 .. MH_MAX_LAYER_PAIRS */

@@ -135,6 +135,11 @@ class LayerPairGates(C.Structure):
     _fields_ = [("run_from_iteration", C.c_uint32), ("run_up_to_iteration", C.c_uint32)]
 
 
+class LayerPairKnn(C.Structure):
+    """mh_layer_pair_knn: Matcher_Points_DistanceThreshold::pairingsPerPoint of a pair (0 or 1: one)."""
+    _fields_ = [("pairings_per_point", C.c_uint32)]
+
+
 class LayerJob(C.Structure):
     """mh_layer_job: the layer pairs of one job of mh_icp_align_layers_batch."""
     _fields_ = [("n_pairs", C.c_size_t), ("pairs", C.POINTER(LayerPair))]
@@ -245,6 +250,10 @@ _SIGNATURES = {
                                               C.POINTER(ICPParamsC),
                                              _DP, C.POINTER(Prior), C.POINTER(ICPResult), C.POINTER(ICPIter),
                                              C.POINTER(PairsOut), C.POINTER(C.c_uint64), C.c_int32]),
+    "mh_icp_align_layers_kbest": (C.c_int32, [C.c_size_t, C.POINTER(LayerPair), C.POINTER(LayerPairOpts), C.POINTER(LayerPairGates),
+                                              C.POINTER(LayerPairKnn), C.POINTER(ICPParamsC), _DP, C.POINTER(Prior),
+                                              C.POINTER(ICPResult), C.POINTER(ICPIter), C.POINTER(PairsOut), C.POINTER(C.c_uint64),
+                                              C.c_int32]),
     "mh_icp_align_layers_batch": (C.c_int32, [C.c_size_t, C.POINTER(LayerJob), C.POINTER(ICPParamsC), C.c_int32, _DP,
                                               C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
 }
@@ -870,19 +879,24 @@ def _layer_pairs(pairs, max_iterations):
     return arr, norm, thr_keep
 
 
-def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, want_pairs=False):
+def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, want_pairs=False, pairings_per_point=None):
     """mh_icp_align_layers: one alignment over several (map, scan) point-layer pairs with one Gauss-Newton solve.
     `pairs`: a sequence of dicts {map, scan, threshold, threshold_angular_deg=0, weight=1} or tuples in that order; a
     threshold is a scalar or max_iterations values.  p.threshold, p.threshold_angular_deg and p.gn.weight_pt2pt are not used.
     A dict may carry unique_global (allowMatchAlreadyMatchedGlobalPoints == false for that pair, U13): with one that is set the
     call goes to mh_icp_align_layers_opts; run_from_iteration / run_up_to_iteration (Matcher::runFromIteration / runUpToIteration,
-    0 = no limit): with one that is set it goes to mh_icp_align_layers_gated.
+    0 = no limit): with one that is set it goes to mh_icp_align_layers_gated.  pairings_per_point (pairingsPerPoint: one value
+    for every pair, or one per pair): when given the call goes to mh_icp_align_layers_kbest, and pair i's arrays hold up to
+    scan_i.n * k_i pairings, a point's in ascending distance.
     Returns icp_align's dict plus pair_counts (final pairings per pair) and, with want_pairs, pairs (one dict per pair)."""
     p_c = replace(p, threshold=p.threshold if p.threshold is not None else 0.0)
     cp, keep = p_c.c(T_guess)
     T0 = _T12(T_guess)
     arr, norm, thr_keep = _layer_pairs(pairs, p.max_iterations)
     n_pairs = len(norm)
+    kpp = None
+    if pairings_per_point is not None:
+        kpp = [int(k) for k in np.broadcast_to(np.asarray(pairings_per_point), (n_pairs,))]
     res = ICPResult()
     trace = (ICPIter * max(1, p.max_iterations))() if want_trace else None
     pr = _mk_prior(prior)
@@ -891,7 +905,7 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
     if want_pairs:
         po = (PairsOut * max(1, n_pairs))()
         for i, e in enumerate(norm):
-            n = max(e["scan"].n, 1)
+            n = max(e["scan"].n * (max(kpp[i], 1) if kpp else 1), 1)
             li, gi = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
             gx, gy, gz, d2 = (np.zeros(n, np.float32) for _ in range(4))
             po[i] = PairsOut(li.ctypes.data_as(_UP), gi.ctypes.data_as(_UP), gx.ctypes.data_as(_FP), gy.ctypes.data_as(_FP),
@@ -902,11 +916,19 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
         opts = (LayerPairOpts * max(1, n_pairs))()
         for i, e in enumerate(norm):
             opts[i].unique_global = 1 if e.get("unique_global") else 0
+    gates = None
     if any(e.get("run_from_iteration") or e.get("run_up_to_iteration") for e in norm):
         gates = (LayerPairGates * max(1, n_pairs))()
         for i, e in enumerate(norm):
             gates[i].run_from_iteration = int(e.get("run_from_iteration") or 0)
             gates[i].run_up_to_iteration = int(e.get("run_up_to_iteration") or 0)
+    if kpp is not None:
+        knn = (LayerPairKnn * max(1, n_pairs))()
+        for i, k in enumerate(kpp):
+            knn[i].pairings_per_point = k
+        _chk(lib().mh_icp_align_layers_kbest(n_pairs, arr, opts, gates, knn, C.byref(cp), T0.ctypes.data_as(_DP),
+                                             C.byref(pr) if pr else None, C.byref(res), trace, po, counts, MEM_HOST))
+    elif gates is not None:
         _chk(lib().mh_icp_align_layers_gated(n_pairs, arr, opts, gates, C.byref(cp), T0.ctypes.data_as(_DP),
                                              C.byref(pr) if pr else None, C.byref(res), trace, po, counts, MEM_HOST))
     elif opts is not None:

@@ -61,6 +61,7 @@
 #include "mh_k_launch.h"
 #include "mh_k_layers.h"
 #include "mh_k_claim.h"
+#include "mh_k_match_kbest.h"
 #include "mh_k_pairs.h"
 
 // ================================================================================================
@@ -992,15 +993,32 @@ size_t mh_pairs_block_bytes(size_t n_scan_points) {
 
 #include "mh_icp_api.inl"    // mh_nn_search*, mh_gn_solve, mh_covariance
 
+mh_status mh_icp_align_layers_kbest(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
+                                    const mh_layer_pair_gates* gates, const mh_layer_pair_knn* knn, const mh_icp_params* params,
+                                    const double T_guess[12], const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
+                                    const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
+  MH_TRY(check_layers_args(n_pairs, pairs, params, T_guess, result));
+  MH_REQUIRE(!final_pairs || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
+  for (size_t i = 0; knn && i < n_pairs; i++)
+    MH_REQUIRE(knn[i].pairings_per_point <= MH_MAX_PAIRINGS_PER_POINT, "pairings_per_point must be 0 .. MH_MAX_PAIRINGS_PER_POINT");
+  MH_TRY(check_layers_supported(n_pairs, pairs, params));
+  for (size_t i = 0; knn && i < n_pairs; i++) {
+    const uint64_t entries = (uint64_t)pairs[i].scan->n * (knn[i].pairings_per_point ? knn[i].pairings_per_point : 1u);
+    if (entries >= (1ull << 32))
+      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_kbest: scan size * pairings_per_point does not fit 32 bits");
+    if (opts && opts[i].unique_global && entries >= kClaimMaxScan)
+      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_kbest: a unique pair with 2^29 or more pairing entries");
+  }
+  return align_layers(read_switches(), (uint32_t)n_pairs, pairs, params, T_guess, prior, result, trace, final_pairs,
+                      final_pair_counts, pairs_mem, opts, gates, knn);
+}
+
 mh_status mh_icp_align_layers_gated(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
                                     const mh_layer_pair_gates* gates, const mh_icp_params* params, const double T_guess[12],
                                     const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
                                     const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
-  MH_TRY(check_layers_args(n_pairs, pairs, params, T_guess, result));
-  MH_REQUIRE(!final_pairs || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
-  MH_TRY(check_layers_supported(n_pairs, pairs, params));
-  return align_layers(read_switches(), (uint32_t)n_pairs, pairs, params, T_guess, prior, result, trace, final_pairs,
-                      final_pair_counts, pairs_mem, opts, gates);
+  return mh_icp_align_layers_kbest(n_pairs, pairs, opts, gates, nullptr, params, T_guess, prior, result, trace, final_pairs,
+                                   final_pair_counts, pairs_mem);
 }
 
 mh_status mh_icp_align_layers_opts(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,

@@ -8,7 +8,10 @@
 // (mh_k_claim.h), and the set of such pairs is part of the chunk's graph key.
 // Iteration gates (mh_icp_align_layers_gated): data of the uploaded table, tested on the device -- a pair outside its interval
 // has its match workgroups store "not paired" instead of searching, and every later kernel of the iteration then finds nothing
-// of it.  Nothing about the gates enters the graph key.  Loop
+// of it.  Nothing about the gates enters the graph key.
+// pairingsPerPoint > 1 (mh_icp_align_layers_kbest, mh_k_match_kbest.h): such a pair's segment holds n * k entries and it is searched
+// by k_match_layers_k, one more launch per iteration beside k_match_layers; the accumulation and the covariance are then the *_k
+// entry points, and the pairs' k are part of the graph key.  Loop
 // control is AlignJob's chunked one: a chunk of iterations is enqueued (replayed from a captured graph once its shape repeats,
 // MH_NO_GRAPH=1: never), the host waits for its event and reads the done flag.
 
@@ -21,6 +24,9 @@ struct LayersLayout {
   uint32_t tot_claim = 0;    // workgroups of k_claim_layers / k_resolve_layers (0: no unique pair, neither is launched)
   uint32_t unique_mask = 0;  // bit i: pair i is unique
   size_t claim_off = 0;      // byte offset of the ClaimTable in layers_tab
+  uint32_t tot_match_k = 0;  // workgroups of k_match_layers_k (0: no pair with k > 1; it is not launched, the kernels are the plain ones)
+  uint32_t knn_key = 0;      // 4 bits per pair: its k when above 1
+  size_t knn_off = 0;        // byte offset of the KnnTable in layers_tab
 };
 
 // One multi-layer alignment from its arguments to its uploaded [state | parameters | table | schedules]: what a single call and a
@@ -32,6 +38,7 @@ struct LayersJob {
   const mh_icp_params* p = nullptr;
   mh_icp_result* res = nullptr;
   mh_layer_pair_gates gates[MH_MAX_LAYER_PAIRS] = {};  // all zero: no gate
+  uint32_t kpp[MH_MAX_LAYER_PAIRS] = {};               // pairings per point, >= 1
   bool trivial = false;       // nothing to run: the result is complete after start()
   LayersLayout L;
   const LayerTable* tab = nullptr;  // the pinned mirror of the device table (the pairing segments: count_pairs)
@@ -39,15 +46,18 @@ struct LayersJob {
 
   mh_status start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
                   const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
-                  const mh_layer_pair_opts* opts = nullptr, const mh_layer_pair_gates* gates_ = nullptr);
+                  const mh_layer_pair_opts* opts = nullptr, const mh_layer_pair_gates* gates_ = nullptr,
+                  const mh_layer_pair_knn* knn = nullptr);
+  size_t entries(uint32_t i) const { return pairs[i].scan->n * (size_t)kpp[i]; }  // of pair i's pairing segment
   uint32_t k_last = 0;        // after finish(): the ICP iteration whose match produced the final pairings
   bool active_in(uint32_t i, uint32_t k) const {  // layer_active (mh_k_layers.h) on the host
     return k >= gates[i].run_from_iteration && (gates[i].run_up_to_iteration == 0 || k <= gates[i].run_up_to_iteration);
   }
-  // potential_pairings: the layer sizes of the pairs that are active in ICP iteration k (all of them without gates)
+  // potential_pairings: the layer sizes (times the pairings per point: pcLocal.size() * pairingsPerPoint [U]) of the pairs that
+  // are active in ICP iteration k (all of them without gates)
   uint64_t potential_in(uint32_t k) const {
     uint64_t s = 0;
-    for (uint32_t i = 0; i < np; i++) s += active_in(i, k) ? pairs[i].scan->n : 0;
+    for (uint32_t i = 0; i < np; i++) s += active_in(i, k) ? entries(i) : 0;
     return s;
   }
   void finish(uint32_t polls, uint32_t enqueued);
@@ -65,7 +75,7 @@ mh_status LayersJob::claims_begin(ClaimTable* ct) {
     ct->blk[i] = L.tot_claim;
     if (!((L.unique_mask >> i) & 1u)) continue;
     const mh_map* m = pairs[i].map;
-    if (pairs[i].scan->n >= kClaimMaxScan)
+    if (entries(i) >= kClaimMaxScan)
       return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_opts: a unique pair whose scan has 2^29 or more points");
     if (m->n_offered >= kClaimMaxEntries)
       return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_opts: a unique pair whose map has been offered 2^28 or more points");
@@ -79,7 +89,7 @@ mh_status LayersJob::claims_begin(ClaimTable* ct) {
       region_off[i] = region_off[first];
     }
     ct->entries[i] = (uint32_t)m->n_offered;
-    L.tot_claim += nblk(pairs[i].scan->n);
+    L.tot_claim += nblk(entries(i));
   }
   ct->blk[np] = L.tot_claim;
   const void* const before = ctx->claims.p;
@@ -98,7 +108,7 @@ mh_status LayersJob::claims_begin(ClaimTable* ct) {
 
 mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
                            const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
-                           const mh_layer_pair_opts* opts, const mh_layer_pair_gates* gates_) {
+                           const mh_layer_pair_opts* opts, const mh_layer_pair_gates* gates_, const mh_layer_pair_knn* knn) {
   np = np_;
   pairs = pairs_;
   p = p_;
@@ -107,6 +117,7 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   if (final_pair_counts)
     for (uint32_t i = 0; i < np; i++) final_pair_counts[i] = 0;
   for (uint32_t i = 0; i < np; i++) gates[i] = gates_ ? gates_[i] : mh_layer_pair_gates{};
+  for (uint32_t i = 0; i < np; i++) kpp[i] = knn && knn[i].pairings_per_point ? knn[i].pairings_per_point : 1u;
   // (every pair gated off in iteration 0 is NoPairings there, like no points at all)
   if ((trivial = begin_result(res, p, T0, potential_in(0)))) return MH_OK;
   MH_TRY(set_device(ctx));
@@ -133,15 +144,23 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   for (uint32_t i = 0; opts && i < np; i++) L.unique_mask |= opts[i].unique_global ? 1u << i : 0u;
   // (a call without unique pairs uploads the bytes it always did)
   L.claim_off = (tab_bytes + sched_bytes + 255) / 256 * 256;
-  const size_t up_bytes = L.unique_mask ? L.claim_off + sizeof(ClaimTable) : tab_bytes + sched_bytes;
+  for (uint32_t i = 0; i < np; i++) L.knn_key |= kpp[i] > 1u ? kpp[i] << (4 * i) : 0u;
+  L.knn_off = (L.claim_off + sizeof(ClaimTable) + 255) / 256 * 256;
+  const size_t up_bytes = L.knn_key ? L.knn_off + sizeof(KnnTable)
+                                    : L.unique_mask ? L.claim_off + sizeof(ClaimTable) : tab_bytes + sched_bytes;
   MH_TRY(ctx->h_layers.reserve(up_bytes));
   MH_TRY(ctx->layers_tab.reserve(up_bytes));
   LayerTable* const tab = ctx->h_layers.as<LayerTable>();
   this->tab = tab;
   memset(tab, 0, sizeof(LayerTable));
   tab->n_pairs = np;
+  KnnTable* const kt = reinterpret_cast<KnnTable*>(ctx->h_layers.as<char>() + L.knn_off);  // (written with a pair of k > 1 only)
+  if (L.knn_key) memset(kt, 0, sizeof(KnnTable));
   for (uint32_t i = 0; i < np; i++) {
-    const size_t n = pairs[i].scan->n, nn = n ? n : 1;
+    const size_t n = entries(i), nn = n ? n : 1;  // (k = 1: the points)
+    const size_t n_flat = kpp[i] > 1u ? 0 : n, n_flat_k = kpp[i] > 1u ? pairs[i].scan->n : 0;
+    if (L.knn_key) kt->blk[i] = L.tot_match_k;
+    L.tot_match_k += (uint32_t)((n_flat_k + kFlatPointsPerBlock - 1) / kFlatPointsPerBlock);
     L.seg_q[i] = L.pair_bytes;
     L.pair_bytes += (nn * sizeof(float4) + 255) / 256 * 256;
     L.seg_g[i] = L.pair_bytes;
@@ -149,13 +168,14 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     tab->blk_match[i] = L.tot_match;
     tab->blk_acc[i] = L.tot_acc;
     tab->blk_cov[i] = L.tot_cov;
-    L.tot_match += (uint32_t)((n + kFlatPointsPerBlock - 1) / kFlatPointsPerBlock);
+    L.tot_match += (uint32_t)((n_flat + kFlatPointsPerBlock - 1) / kFlatPointsPerBlock);
     L.tot_acc += n ? nblk_acc(n) : 0u;
     L.tot_cov += n ? nblk(n) : 0u;
   }
   tab->blk_match[np] = L.tot_match;
   tab->blk_acc[np] = L.tot_acc;
   tab->blk_cov[np] = L.tot_cov;
+  if (L.knn_key) kt->blk[np] = L.tot_match_k;
   MH_TRY(ctx->layers_pairs.reserve(L.pair_bytes));
   const uint32_t cols = L.tot_acc > L.tot_cov ? L.tot_acc : L.tot_cov;
   MH_TRY(ctx->partials.reserve((size_t)kGenN * (cols ? cols : 1) * sizeof(double)));
@@ -185,6 +205,7 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     d.cov_off = tab->blk_cov[i];
     d.run_from = gates[i].run_from_iteration;
     d.run_up_to = gates[i].run_up_to_iteration;
+    d.kpp = kpp[i] > 1u ? kpp[i] : 0u;  // (k = 1: the word the table always had there)
   }
   if (L.unique_mask) MH_TRY(claims_begin(reinterpret_cast<ClaimTable*>(ctx->h_layers.as<char>() + L.claim_off)));
   MH_HIP(hipMemcpyAsync(ctx->layers_tab.p, ctx->h_layers.p, up_bytes, hipMemcpyHostToDevice, s));
@@ -212,9 +233,20 @@ mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* fina
   uint64_t sum = 0;
   for (uint32_t i = 0; i < np; i++) {
     uint64_t c = 0;
-    if (pairs[i].scan->n && active_in(i, k_last))  // (a pair that is gated off there holds "not paired" throughout)
-      MH_TRY(compact_pairs_of(ctx, tab->d[i].pair_gidx, tab->d[i].pair_q, pairs[i].scan->n, final_pairs ? &final_pairs[i] : &none,
+    if (pairs[i].scan->n && active_in(i, k_last)) {  // (a pair that is gated off there holds "not paired" throughout)
+      MH_TRY(compact_pairs_of(ctx, tab->d[i].pair_gidx, tab->d[i].pair_q, entries(i), final_pairs ? &final_pairs[i] : &none,
                               final_pairs ? pairs_mem : MH_MEM_DEVICE, &c));
+      // the compaction numbers the ENTRIES: entry e belongs to local point e / k (mh_nn_search_k)
+      if (kpp[i] > 1u && c && final_pairs && final_pairs[i].local_idx) {
+        if (pairs_mem == MH_MEM_HOST) {
+          for (uint64_t e = 0; e < c; e++) final_pairs[i].local_idx[e] /= kpp[i];
+        } else {
+          hipLaunchKernelGGL(k_div_idx, dim3(nblk(c)), dim3(kBlock), 0, ctx->stream, final_pairs[i].local_idx, (uint32_t)c, kpp[i]);
+          MH_HIP(hipGetLastError());
+          MH_HIP(mh::wait_stream(ctx->stream));
+        }
+      }
+    }
     if (final_pair_counts) final_pair_counts[i] = c;
     sum += c;
   }
@@ -227,15 +259,19 @@ mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* fina
 mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pairs, const mh_icp_params* p, const double T0[12],
                        const mh_prior* prior, mh_icp_result* res, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
                        uint64_t* final_pair_counts, int32_t pairs_mem, const mh_layer_pair_opts* opts = nullptr,
-                       const mh_layer_pair_gates* gates = nullptr) {
+                       const mh_layer_pair_gates* gates = nullptr, const mh_layer_pair_knn* knn = nullptr) {
   LayersJob job;
-  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts, opts, gates));
+  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts, opts, gates, knn));
   if (job.trivial) return MH_OK;
   mh_ctx* const ctx = job.ctx;
   const LayersLayout& L = job.L;
   hipStream_t s = ctx->stream;
   const LayerTable* const dtab = ctx->layers_tab.as<LayerTable>();
   const ClaimTable* const dclaim = reinterpret_cast<const ClaimTable*>(ctx->layers_tab.as<char>() + L.claim_off);
+  const KnnTable* const dknn = reinterpret_cast<const KnnTable*>(ctx->layers_tab.as<char>() + L.knn_off);
+  // (a table with a pair of k > 1: the entry points that take the local point of an entry from its k)
+  const auto accum = L.knn_key ? k_accum_layers_k : k_accum_layers;
+  const auto cov_accum = L.knn_key ? k_cov_accum_layers_k : k_cov_accum_layers;
   double* const part = ctx->partials.as<double>();
   const SolveK* const dsk = &ctx->d_params->sk;
   const uint32_t inner = p->gn.max_inner_iterations;
@@ -245,23 +281,25 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
     const uint32_t m = (p->max_iterations - enqueued) < chunk ? (p->max_iterations - enqueued) : chunk;
     auto enqueue_kernels = [&]() -> mh_status {
       for (uint32_t j = 0; j < m; j++) {
-        hipLaunchKernelGGL(k_match_layers, dim3(L.tot_match), dim3(kFlatThreads), 0, s, ctx->d_state, dtab);
+        if (L.tot_match) hipLaunchKernelGGL(k_match_layers, dim3(L.tot_match), dim3(kFlatThreads), 0, s, ctx->d_state, dtab);
+        if (L.tot_match_k)
+          hipLaunchKernelGGL(k_match_layers_k, dim3(L.tot_match_k), dim3(kFlatThreads), 0, s, ctx->d_state, dtab, dknn);
         if (L.tot_claim) {
           hipLaunchKernelGGL(k_claim_layers, dim3(L.tot_claim), dim3(kBlock), 0, s, ctx->d_state, dtab, dclaim);
           hipLaunchKernelGGL(k_resolve_layers, dim3(L.tot_claim), dim3(kBlock), 0, s, ctx->d_state, dtab, dclaim);
         }
-        hipLaunchKernelGGL(k_accum_layers, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 1u, part, L.tot_acc);
+        hipLaunchKernelGGL(accum, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 1u, part, L.tot_acc);
         hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, dsk, (const double*)part, L.tot_acc,
                            L.tot_acc, (const double*)nullptr, 0u, 0u, 1u);
         for (uint32_t in = 1; in < inner; in++) {
-          hipLaunchKernelGGL(k_accum_layers, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 0u, part, L.tot_acc);
+          hipLaunchKernelGGL(accum, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 0u, part, L.tot_acc);
           hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, dsk, (const double*)part, L.tot_acc,
                              L.tot_acc, (const double*)nullptr, 0u, 0u, 0u);
         }
       }
       if (p->compute_covariance) {  // no-ops unless the loop has terminated
         hipLaunchKernelGGL(k_cov_prepare, dim3(1), dim3(64), 0, s, ctx->d_state, dsk, 0u);
-        hipLaunchKernelGGL(k_cov_accum_layers, dim3(L.tot_cov), dim3(kBlock), 0, s, ctx->d_state, dtab, part, L.tot_cov);
+        hipLaunchKernelGGL(cov_accum, dim3(L.tot_cov), dim3(kBlock), 0, s, ctx->d_state, dtab, part, L.tot_cov);
         hipLaunchKernelGGL(k_cov_finalize, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, 0u, (const double*)part, L.tot_cov,
                            L.tot_cov, (const double*)nullptr, 0u, 0u);
       }
@@ -273,13 +311,19 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
     const unsigned long long kv[] = {kLayersGraphTag | np, m, inner, p->compute_covariance, L.tot_match, L.tot_acc, L.tot_cov,
                                      (unsigned long long)dtab, (unsigned long long)part, (unsigned long long)ctx->d_state,
                                      (unsigned long long)ctx->d_params, (unsigned long long)ctx->h_state};
-    static_assert(sizeof(kv) + 3 * sizeof(key[0]) <= sizeof(key), "graph key too small");
+    static_assert(sizeof(kv) + 6 * sizeof(key[0]) <= sizeof(key), "graph key too small");
     memcpy(key, kv, sizeof(kv));
     if (L.tot_claim) {  // (without a unique pair the key is what it always was)
       unsigned long long* const kc = key + sizeof(kv) / sizeof(kv[0]);
       kc[0] = L.unique_mask;
       kc[1] = L.tot_claim;
       kc[2] = (unsigned long long)dclaim;
+    }
+    if (L.knn_key) {  // (and without a pair of k > 1)
+      unsigned long long* const kk = key + sizeof(kv) / sizeof(kv[0]) + 3;
+      kk[0] = L.knn_key;
+      kk[1] = L.tot_match_k;
+      kk[2] = (unsigned long long)dknn;
     }
     MH_TRY(enqueue_cached(ctx, sw.no_graph, key, enqueue_kernels));
     enqueued += m;

@@ -12,13 +12,14 @@ constexpr uint32_t kAccPPT = MH_ACC_PPT;  // scan points per lane of k_accum (to
 inline uint32_t nblk_acc(size_t n) { return (uint32_t)((n + (size_t)kBlock * kAccPPT - 1) / ((size_t)kBlock * kAccPPT)); }
 
 // SIGNED: the verdict rides in the sign of the pairing's distance (the plan / scan matcher, flat_signed_d2): no index array read
-template <bool SIGNED>
+// KD: pairingsPerPoint > 1 (mh_k_match_kbest.h) -- `n` counts the pairing ENTRIES, entry e belongs to local point e / kdiv
+template <bool SIGNED, bool KD = false>
 __device__ __forceinline__ void k_accum_body(const IcpDeviceState* __restrict__ st, uint32_t first,
                                                   const MatchK* __restrict__ kp, const float* __restrict__ lx,
                                                   const float* __restrict__ ly, const float* __restrict__ lz, uint32_t n,
                                                   const float4* __restrict__ pair_q,
                                                   const uint32_t* __restrict__ pair_gidx, double* __restrict__ partials,
-                                                  uint32_t pstride, uint32_t block_x) {
+                                                  uint32_t pstride, uint32_t block_x, uint32_t kdiv = 1u) {
   __shared__ BlockSumQ<kAccN> bs;
   // state and parameters through the scalar path (uniform addresses, not written during this kernel); the arrays through
   // global-space pointers (mh_nn_device.h, G())
@@ -47,7 +48,8 @@ __device__ __forceinline__ void k_accum_body(const IcpDeviceState* __restrict__ 
     q[u] = gq[ic];
     if (SIGNED) gi[u] = (i < n && !(__float_as_uint(q[u].w) >> 31)) ? 0u : kNoMatch;
     else gi[u] = i < n ? G(pair_gidx)[ic] : kNoMatch;
-    px[u] = G(lx)[ic]; py[u] = G(ly)[ic]; pz[u] = G(lz)[ic];
+    const uint32_t il = KD ? ic / kdiv : ic;
+    px[u] = G(lx)[il]; py[u] = G(ly)[il]; pz[u] = G(lz)[il];
   }
   Acc a;
   acc_zero(a);

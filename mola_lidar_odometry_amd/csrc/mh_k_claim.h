@@ -16,7 +16,7 @@
 // and the only name of a map point that match_flat_wave leaves behind (the record's position is not stored); a map that has
 // evicted points has more source indices than records, and one of 2^28 or more is refused.  Pairs that share a map share its
 // region: claims are per map.  An entry is
-//     epoch << 32 | pair order << 29 | local index
+//     epoch << 32 | pair order << 29 | local index     (local index * k + rank for a pair with k pairings per point)
 // with the epoch DESCENDING: every ICP iteration of every alignment on the context takes a smaller one than all before it, so
 // whatever an earlier iteration (or an earlier call, against another map, in a region laid out differently) left in an entry is
 // larger than any key of the current iteration and loses the atomicMin like an empty entry (all ones) would.  Chosen over clearing
@@ -26,7 +26,7 @@
 #pragma once
 
 constexpr uint32_t kClaimLocalBits = 29;                  // local index below, pair order (MH_MAX_LAYER_PAIRS = 8: 3 bits) above
-constexpr uint64_t kClaimMaxScan = 1ull << kClaimLocalBits;
+constexpr uint64_t kClaimMaxScan = 1ull << kClaimLocalBits;   // (entries: points x pairings per point)
 constexpr uint64_t kClaimMaxEntries = 1ull << 28;         // source indices of one map (2 GiB of entries)
 static_assert(MH_MAX_LAYER_PAIRS <= (1u << (32 - kClaimLocalBits)), "the pair order does not fit the claim key");
 
@@ -38,6 +38,14 @@ struct ClaimTable {
 };
 
 typedef const ClaimTable __attribute__((address_space(4))) * cclaim_ptr;
+
+// the pairing entries of pair li: its points, times its pairings per point (mh_k_match_kbest.h) -- entry e = point * k + rank, so
+// with the entry as the key's local field the matching order is (pair, local index, rank) and every candidate of a point makes
+// its own attempt
+__device__ __forceinline__ uint32_t layer_entries(const clayers_ptr ct, uint32_t li) {
+  const uint32_t k = ct->d[li].kpp;
+  return ct->d[li].n * (k ? k : 1u);
+}
 
 __device__ __forceinline__ unsigned long long claim_key(uint32_t epoch, uint32_t li, uint32_t i) {
   return ((unsigned long long)epoch << 32) | (unsigned long long)((li << kClaimLocalBits) | i);
@@ -52,7 +60,7 @@ __global__ __launch_bounds__(kBlock) void k_claim_layers(const IcpDeviceState* _
   const uint32_t li = layer_of(cc->blk, ct->n_pairs, blockIdx.x);
   if (!layer_active(ct, li, cst->iter)) return;  // (wave-uniform; k_match_layers has left kNoMatch in its whole segment)
   const uint32_t i = (blockIdx.x - cc->blk[li]) * kBlock + threadIdx.x;
-  if (i >= ct->d[li].n) return;
+  if (i >= layer_entries(ct, li)) return;
   const uint32_t g = G(ct->d[li].pair_gidx)[i];
   if (g == kNoMatch || g >= cc->entries[li]) return;  // (no source index reaches the region's end: mh_map_insert numbers them below n_offered)
   (void)__hip_atomic_fetch_min(G(cc->region[li]) + g, claim_key(cc->epoch0 - cst->iter, li, i), __ATOMIC_RELAXED,
@@ -68,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve_layers(const IcpDeviceState*
   const uint32_t li = layer_of(cc->blk, ct->n_pairs, blockIdx.x);
   if (!layer_active(ct, li, cst->iter)) return;  // (wave-uniform; k_match_layers has left kNoMatch in its whole segment)
   const uint32_t i = (blockIdx.x - cc->blk[li]) * kBlock + threadIdx.x;
-  if (i >= ct->d[li].n) return;
+  if (i >= layer_entries(ct, li)) return;
   uint32_t* const gidx = ct->d[li].pair_gidx;
   const uint32_t g = G(gidx)[i];
   if (g == kNoMatch || g >= cc->entries[li]) return;

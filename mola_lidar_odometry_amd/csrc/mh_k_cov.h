@@ -90,11 +90,13 @@ __device__ __forceinline__ void k_cov_prepare_body(IcpDeviceState* __restrict__ 
   for (int i = 0; i < 12; i++) st->covD[j * 12 + i] = out[i];
 }
 
+template <bool KD = false>  // KD: `n` pairing entries, entry e of local point e / kdiv (k_accum_body)
 __device__ __forceinline__ void k_cov_accum_body(const IcpDeviceState* __restrict__ st, uint32_t force,
                                                       const float* __restrict__ lx, const float* __restrict__ ly,
                                                       const float* __restrict__ lz, uint32_t n,
                                                       const uint32_t* __restrict__ pair_gidx,
-                                                      double* __restrict__ partials, uint32_t pstride, uint32_t block_x) {
+                                                      double* __restrict__ partials, uint32_t pstride, uint32_t block_x,
+                                                      uint32_t kdiv = 1u) {
   __shared__ double sD[72];
   __shared__ BlockSum<kCovN> lds;
   if (!force && (!st->done || st->cov_done)) return;
@@ -104,7 +106,10 @@ __device__ __forceinline__ void k_cov_accum_body(const IcpDeviceState* __restric
   double v[kCovN];
 #pragma unroll
   for (int j = 0; j < kCovN; j++) v[j] = 0.0;
-  if (i < n && pair_gidx[i] != kNoMatch) cov_rows_point(sD, lx[i], ly[i], lz[i], v);
+  if (i < n && pair_gidx[i] != kNoMatch) {
+    const uint32_t il = KD ? i / kdiv : i;
+    cov_rows_point(sD, lx[il], ly[il], lz[il], v);
+  }
   block_sum_rows<kCovN>(v, lds, partials, pstride, block_x);
 }
 

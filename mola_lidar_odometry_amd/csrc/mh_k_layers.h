@@ -32,8 +32,8 @@ struct LayerDesc {
   uint32_t cov_off;     // first column of its covariance partials
   uint32_t run_from;    // Matcher::runFromIteration / runUpToIteration of this pair (mh_icp_align_layers_gated), 0 = no limit: the
   uint32_t run_up_to;   // pair searches in ICP iteration k iff layer_active(k)
-  uint32_t pad;
-};
+  uint32_t kpp;         // pairingsPerPoint when above 1 (mh_icp_align_layers_kbest, mh_k_match_kbest.h), else 0: the segment holds
+};                      // n * kpp entries, entry e of local point e / kpp, and k_match_layers_k searches the pair
 
 struct LayerTable {
   uint32_t n_pairs, pad;

@@ -84,10 +84,18 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
 // Phases A2 and B for one set of candidate masks (mh_nn_flat.h's header): the wave's (point, code) pairs to LDS, a probe per
 // pair, the narrowed ranges cut into chunks, a lane per record of every chunk.  `init`: what a point's result word starts from
 // (the bound and "no record", or what an earlier stage found).  Returns the number of candidate pairs (wave-uniform); with none,
-// nothing is written to LDS.
-template <class FW>
+// nothing is written to LDS.  `ins`: what phase B does with the key of a record within the bound -- the minimum into the point's
+// result word here, the k smallest into k words for pairingsPerPoint > 1 (mh_k_match_kbest.h).
+struct FlatInsertMin {
+  template <class FW>
+  __device__ __forceinline__ void operator()(FW& sh, uint32_t p, unsigned long long key) const {
+    (void)__hip_atomic_fetch_min(&sh.RES[p], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+};
+template <class FW, class INS = FlatInsertMin>
 __device__ __forceinline__ uint32_t flat_plan_scan(FW& sh, const MapView& m, uint32_t lane, uint32_t cmask, unsigned long long kbase,
-                                                   float px, float py, float pz, float b0, unsigned long long init) {
+                                                   float px, float py, float pz, float b0, unsigned long long init,
+                                                   const INS ins = INS()) {
   constexpr int kFlatMaxCand = FW::kMaxCand;
   constexpr int kFlatMaxChunks = FW::kMaxChunks;
   const gslots_ptr slots4 = (gslots_ptr)m.slots;
@@ -199,9 +207,7 @@ __device__ __forceinline__ uint32_t flat_plan_scan(FW& sh, const MapView& m, uin
         const float dx = rec[u].x - Pq.x, dy = rec[u].y - Pq.y, dz = rec[u].z - Pq.z;
         const float d2 = (dx * dx + dy * dy) + dz * dz;  // fp32, un-fused, this order (bit-exact with the oracle)
         // only a record within the bound can be the answer ((d2, position) < (b0, none) <=> d2 <= b0)
-        if (valid[u] && d2 <= Pq.w)
-          (void)__hip_atomic_fetch_min(&sh.RES[pp[u]], ((unsigned long long)__float_as_uint(d2) << 32) | __float_as_uint(rec[u].w),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (valid[u] && d2 <= Pq.w) ins(sh, pp[u], ((unsigned long long)__float_as_uint(d2) << 32) | __float_as_uint(rec[u].w));
       }
     }
     wave_sync_lds_nn();
@@ -370,6 +376,7 @@ __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, 
 #ifdef MH_DEBUG_WAVETRACE
 static __device__ unsigned long long g_flatdbg[16];  // debug build: [0] searches (waves) [1] points [2] unbounded at entry [3] slow: out of range / no bound after stage 0
                                               // [4] slow: > kFlatMaxCand candidates [5] slow: chunk space [6] slow: bound not attained [7] candidates [8] chunks (stage 1) [9] D rounds
+                                              // match_kbest_wave (mh_k_match_kbest.h): [10] points [11] without a bound [12] > kFlatMaxCand candidates [13] chunk space [14] slot k - 1 empty [15] bounded scan of the lane's own, slot k - 1 empty
 #define MH_FLATDBG(i, v) do { const unsigned long long b_ = __ballot(v); if (lane == 0 && b_) atomicAdd(&g_flatdbg[i], (unsigned long long)__builtin_popcountll(b_)); } while (0)
 #define MH_FLATDBG_ADD(i, v) do { if (lane == 0) atomicAdd(&g_flatdbg[i], (unsigned long long)(v)); } while (0)
 #else

@@ -135,6 +135,7 @@ struct LayerShape
     std::vector<Entry> entries;
     bool any_unique = false;  // some matcher has allowMatchAlreadyMatchedGlobalPoints false (U13)
     bool any_gate = false;    // some matcher has runFromIteration / runUpToIteration (MOLA_HIP_FUSE_GATES=1)
+    bool any_knn = false;     // some matcher has pairingsPerPoint > 1 (MOLA_HIP_FUSE_KBEST=1)
 };
 
 template <class M> bool single_unit_layer(const M& m, std::string& g, std::string& l, double* weight_out = nullptr)
@@ -387,7 +388,13 @@ class ICP_HIP : public ICP
         for (const auto& mp : matchers())
         {
             const auto* m = dynamic_cast<const Matcher_Points_DistanceThreshold*>(mp.get());
-            if (!m || !m->enabled || m->pairingsPerPoint != 1) return false;
+            if (!m || !m->enabled) return false;
+            if (m->pairingsPerPoint != 1)  // lidar2d.yaml:156, rgbd.yaml:138: mh_icp_align_layers_kbest, when asked for
+            {
+                if (!molahip_host::fuse_kbest(false, molahip_host::plugin_switches())) return false;
+                if (m->pairingsPerPoint < 1 || m->pairingsPerPoint > MH_MAX_PAIRINGS_PER_POINT) return false;
+                if (!m->weight_pt2pt_layers.empty()) ls.any_knn = true;
+            }
             if (m->runFromIteration != 0 || m->runUpToIteration != 0)  // [U] iteration gates: the device tests them per pair
             {
                 if (!molahip_host::fuse_gates(false, molahip_host::plugin_switches())) return false;
@@ -410,7 +417,7 @@ class ICP_HIP : public ICP
                     ls.entries.push_back(e);
                 }
         }
-        if (ls.entries.size() < (ls.any_unique || ls.any_gate ? 1u : 2u) || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
+        if (ls.entries.size() < (ls.any_unique || ls.any_gate || ls.any_knn ? 1u : 2u) || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
         for (size_t i = 0; i < ls.entries.size(); i++)
             for (size_t j = i + 1; j < ls.entries.size(); j++)
                 if (skip_paired && ls.entries[i].localLayer == ls.entries[j].localLayer) return false;
@@ -432,9 +439,11 @@ class ICP_HIP : public ICP
         std::vector<mh_layer_pair> pairs(np);
         std::vector<mh_layer_pair_opts> opts(np);
         std::vector<mh_layer_pair_gates> gates(np);
+        std::vector<mh_layer_pair_knn> knn(np);
         for (size_t i = 0; i < np; i++)
         {
             const auto& e = ls.entries[i];
+            knn[i].pairings_per_point = static_cast<uint32_t>(e.m->pairingsPerPoint);
             opts[i].unique_global = e.m->allowMatchAlreadyMatchedGlobalPoints ? 0u : 1u;
             gates[i].run_from_iteration = e.m->runFromIteration;
             gates[i].run_up_to_iteration = e.m->runUpToIteration;
@@ -492,7 +501,7 @@ class ICP_HIP : public ICP
         size_t n_local = 0;
         for (size_t i = 0; i < np; i++)
         {
-            po[i] = layer_pairs_[i].out(locals[i]->getPointsBufferRef_x().size());
+            po[i] = layer_pairs_[i].out(locals[i]->getPointsBufferRef_x().size() * knn[i].pairings_per_point);
             n_local += locals[i]->getPointsBufferRef_x().size();
         }
         auto run_with = [&](uint32_t budget, mh_icp_iter* trace) {
@@ -502,9 +511,10 @@ class ICP_HIP : public ICP
             q.max_iterations = budget;
             q.kernel_param   = kp.data();
             mh_icp_result rr{};
-            mh_check(mh_icp_align_layers_gated(np, pairs.data(), ls.any_unique ? opts.data() : nullptr,
-                                               ls.any_gate ? gates.data() : nullptr, &q, T0, prior ? &pr : nullptr, &rr, trace,
-                                               po.data(), counts.data(), MH_MEM_HOST), "mh_icp_align_layers_gated");
+            mh_check(mh_icp_align_layers_kbest(np, pairs.data(), ls.any_unique ? opts.data() : nullptr,
+                                               ls.any_gate ? gates.data() : nullptr, ls.any_knn ? knn.data() : nullptr, &q, T0,
+                                               prior ? &pr : nullptr, &rr, trace, po.data(), counts.data(), MH_MEM_HOST),
+                     "mh_icp_align_layers_kbest");
             return rr;
         };
         auto run = [&](uint32_t budget, mh_icp_iter* trace) {

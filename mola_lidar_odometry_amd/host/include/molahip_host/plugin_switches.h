@@ -18,6 +18,9 @@
 //   MOLA_HIP_FUSE_GATES       (unset) | 0 | 1         matchers with runFromIteration / runUpToIteration on the fused multi-layer
 //                                                     loop (mh_icp_align_layers_gated); set, it overrides ICP::fuseGatedMatchers
 //                                                     and the adapter's default (off) both ways
+//   MOLA_HIP_FUSE_KBEST       (unset) | 0 | 1         matchers with pairingsPerPoint 2 .. MH_MAX_PAIRINGS_PER_POINT on the fused
+//                                                     multi-layer loop (mh_icp_align_layers_kbest); set, it overrides
+//                                                     ICP::fuseMultiPairings and the adapter's default (off) both ways
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -37,6 +40,7 @@ struct PluginSwitches {
   uint32_t matched_points = MH_MATCHED_POINTS_PAIR_AGAIN;  // MOLA_HIP_MATCHED_POINTS = again | skip (U12)
   bool force_cpu = false;
   int fuse_gates = -1;  // MOLA_HIP_FUSE_GATES: -1 not set (the caller's own setting holds), 0 | 1
+  int fuse_kbest = -1;  // MOLA_HIP_FUSE_KBEST: the same for pairingsPerPoint > 1
   // which of them came from the environment (the mirror classes only override their YAML values for those)
   bool has_gm_form = false, has_index_mode = false, has_cov_step = false, has_min_delta = false, has_max_cost = false,
        has_pt2pl_mode = false, has_far_metric = false;
@@ -90,6 +94,7 @@ inline PluginSwitches read_plugin_switches() {
     s.matched_points = (!strcmp(e, "skip") || !strcmp(e, "1")) ? MH_MATCHED_POINTS_SKIP : MH_MATCHED_POINTS_PAIR_AGAIN;
   if (const char* e = getenv("MOLA_HIP_FORCE_CPU")) s.force_cpu = atoi(e) != 0;
   if (const char* e = getenv("MOLA_HIP_FUSE_GATES")) s.fuse_gates = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("MOLA_HIP_FUSE_KBEST")) s.fuse_kbest = atoi(e) != 0 ? 1 : 0;
   return s;
 }
 
@@ -103,6 +108,8 @@ inline void reload_plugin_switches() { plugin_switches_storage() = read_plugin_s
 
 /** Whether gated matchers go to the fused multi-layer loop: the environment when it says so, else the caller's `setting`. */
 inline bool fuse_gates(bool setting, const PluginSwitches& sw) { return sw.fuse_gates < 0 ? setting : sw.fuse_gates != 0; }
+/** The same for matchers with pairingsPerPoint > 1. */
+inline bool fuse_kbest(bool setting, const PluginSwitches& sw) { return sw.fuse_kbest < 0 ? setting : sw.fuse_kbest != 0; }
 
 /** MH_KERNEL_* for the NAME of an upstream mp2p_icp::RobustKernel enumerator [U] (names, not numeric values: the
  *  upstream enum's values are not relied on).  "GemanMcClure" resolves to the switched form. */

@@ -566,6 +566,10 @@ class ICP {
   // multi-layer loop (mh_icp_align_layers_gated) instead of forcing the generic one.  Default false: a pipeline keeps the path it
   // had.  MOLA_HIP_FUSE_GATES=0|1 overrides it both ways.
   void fuseGatedMatchers(bool v) { fuse_gated_ = v; }
+  // The same for matchers with pairingsPerPoint 2 .. MH_MAX_PAIRINGS_PER_POINT (lidar2d.yaml:156, rgbd.yaml:138): the fused
+  // multi-layer loop (mh_icp_align_layers_kbest), a single pair included, instead of the generic one.  Default false;
+  // MOLA_HIP_FUSE_KBEST=0|1 overrides it both ways.
+  void fuseMultiPairings(bool v) { fuse_kbest_ = v; }
   // the path align() takes for the configured pipeline (no alignment): "single" (mh_icp_align: lidar3d-default / -ndt shapes),
   // "layers" (mh_icp_align_layers: several point-layer pairs, lidar3d-dual-map / -edges shapes; with fuseGatedMatchers also gated
   // ones, lidar3d-near-far) or "generic" (matcher by matcher).
@@ -614,7 +618,7 @@ class ICP {
   mh_scan* scan_ = nullptr;                 // staging layer for host point clouds handed to the fused path ...
   std::shared_ptr<DeviceContext> scan_ctx_;  // ... and the (map's) context it lives in, kept alive until ~ICP has destroyed it
   std::map<std::string, mh_scan*> layer_scans_;  // align_fused_layers: a staging layer per host local layer (in scan_ctx_)
-  bool last_fused_ = false, force_generic_ = false, keep_pairings_ = true, hook_replay_ = false, fuse_gated_ = false;
+  bool last_fused_ = false, force_generic_ = false, keep_pairings_ = true, hook_replay_ = false, fuse_gated_ = false, fuse_kbest_ = false;
   std::shared_ptr<AlignBatcher> batcher_;
   const void* batch_owner_ = nullptr;
   // how long the previous call of each kind ran: [0] calls with the full iteration budget, [1] re-entries after a hook

@@ -626,7 +626,8 @@ bool ICP::can_fuse() const {
 // MH_MAX_LAYER_PAIRS when a matcher has allowMatchAlreadyMatchedGlobalPoints: false (U13: mh_icp_align_layers_opts is the one
 // device loop that implements it, the default pipeline's single pair included) or an iteration gate.  Gated matchers
 // (runFromIteration / runUpToIteration, lidar3d-near-far.yaml:183) only with fuseGatedMatchers / MOLA_HIP_FUSE_GATES=1
-// (mh_icp_align_layers_gated); otherwise they keep the generic loop.  A local layer named by two entries is paired again for each: only under
+// (mh_icp_align_layers_gated); otherwise they keep the generic loop.  The same for pairingsPerPoint 2 .. MH_MAX_PAIRINGS_PER_POINT
+// with fuseMultiPairings / MOLA_HIP_FUSE_KBEST=1 (mh_icp_align_layers_kbest), a single pair included.  A local layer named by two entries is paired again for each: only under
 // MOLA_HIP_MATCHED_POINTS=again (skip would leave the second entry's points out, which mh_icp_align_layers does not do).
 bool ICP::can_fuse_layers() const {
   if (force_generic_ || iteration_hook_) return false;
@@ -634,12 +635,15 @@ bool ICP::can_fuse_layers() const {
   std::vector<std::string> locals;
   bool single_pair_ok = false;  // a unique or gated matcher: shapes only the multi-layer loop takes, a single pair included
   const bool gates_ok = molahip_host::fuse_gates(fuse_gated_, molahip_host::plugin_switches());
+  const bool kbest_ok = molahip_host::fuse_kbest(fuse_kbest_, molahip_host::plugin_switches());
   for (const auto& mm : matchers_) {
     auto m = std::dynamic_pointer_cast<Matcher_Points_DistanceThreshold>(mm);
-    if (!m || !m->enabled || m->pairingsPerPoint != 1) return false;
+    if (!m || !m->enabled) return false;
+    const bool multi = m->pairingsPerPoint != 1;  // (realizeWith has refused what is outside 1 .. MH_MAX_PAIRINGS_PER_POINT)
+    if (multi && !(kbest_ok && m->pairingsPerPoint >= 1 && m->pairingsPerPoint <= MH_MAX_PAIRINGS_PER_POINT)) return false;
     const bool gated = m->runFromIteration || m->runUpToIteration;
     if (gated && !gates_ok) return false;
-    single_pair_ok = single_pair_ok || ((!m->allowMatchAlreadyMatchedGlobalPoints || gated) && !m->pointLayerMatches.empty());
+    single_pair_ok = single_pair_ok || ((!m->allowMatchAlreadyMatchedGlobalPoints || gated || multi) && !m->pointLayerMatches.empty());
     for (const auto& lm : m->pointLayerMatches) locals.push_back(lm.local);
   }
   if (locals.size() < (single_pair_ok ? 1u : 2u) || locals.size() > MH_MAX_LAYER_PAIRS) return false;
@@ -1358,7 +1362,8 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   std::vector<mh_layer_pair> pairs;
   std::vector<mh_layer_pair_opts> opts;  // U13: a matcher's allowMatchAlreadyMatchedGlobalPoints: false, for each of its entries
   std::vector<mh_layer_pair_gates> gates;  // a matcher's runFromIteration / runUpToIteration, for each of its entries
-  bool any_unique = false, any_gate = false;
+  std::vector<mh_layer_pair_knn> knn;  // a matcher's pairingsPerPoint, for each of its entries
+  bool any_unique = false, any_gate = false, any_knn = false;
   std::vector<Entry> entries;
   const auto& ctx0 = global_layer(pcGlobal, ms[0]->pointLayerMatches[0].global).context();
   if (scan_ctx_ && scan_ctx_ != ctx0) {
@@ -1401,6 +1406,8 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
       any_unique = any_unique || opts.back().unique_global;
       gates.push_back(mh_layer_pair_gates{ms[j]->runFromIteration, ms[j]->runUpToIteration});
       any_gate = any_gate || ms[j]->runFromIteration || ms[j]->runUpToIteration;
+      knn.push_back(mh_layer_pair_knn{(uint32_t)ms[j]->pairingsPerPoint});
+      any_knn = any_knn || ms[j]->pairingsPerPoint > 1;
       entries.push_back(e);
     }
   mh_prior pr;
@@ -1412,19 +1419,20 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   std::vector<mh_pairs_out> po(pairs.size());
   std::vector<uint64_t> counts(pairs.size(), 0);
   for (size_t i = 0; want_pairs && i < pairs.size(); i++) {
-    const size_t n = entries[i].dev ? entries[i].dev->size() : entries[i].host->size();
+    const size_t n = (entries[i].dev ? entries[i].dev->size() : entries[i].host->size()) * (size_t)knn[i].pairings_per_point;
     li[i].resize(n); gi[i].resize(n); gx[i].resize(n); gy[i].resize(n); gz[i].resize(n); d2[i].resize(n);
     po[i] = mh_pairs_out{li[i].data(), gi[i].data(), gx[i].data(), gy[i].data(), gz[i].data(), d2[i].data()};
   }
   mh_icp_result r{};
   std::vector<mh_icp_iter> trace(p.generateDebugFiles ? mi : 0);
   auto solo = [&] {
-    check(mh_icp_align_layers_gated(pairs.size(), pairs.data(), any_unique ? opts.data() : nullptr, any_gate ? gates.data() : nullptr,
-                                    &ip, guess.T, prior ? &pr : nullptr, &r, trace.empty() ? nullptr : trace.data(),
-                                    want_pairs ? po.data() : nullptr, counts.data(), MH_MEM_HOST), "mh_icp_align_layers_gated");
+    check(mh_icp_align_layers_kbest(pairs.size(), pairs.data(), any_unique ? opts.data() : nullptr, any_gate ? gates.data() : nullptr,
+                                    any_knn ? knn.data() : nullptr, &ip, guess.T, prior ? &pr : nullptr, &r,
+                                    trace.empty() ? nullptr : trace.data(), want_pairs ? po.data() : nullptr, counts.data(),
+                                    MH_MEM_HOST), "mh_icp_align_layers_kbest");
   };
-  if (batcher_ && (any_unique || any_gate)) {
-    // (mh_icp_align_layers_batch has no unique or gated form: on its own, the participant counted as busy meanwhile -- as
+  if (batcher_ && (any_unique || any_gate || any_knn)) {
+    // (mh_icp_align_layers_batch has no unique, gated or pairingsPerPoint > 1 form: on its own, the participant counted as busy meanwhile -- as
     // align_generic)
     batcher_->runOutside(batch_owner_, solo);
   } else if (batcher_ && trace.empty() && !want_pairs) {

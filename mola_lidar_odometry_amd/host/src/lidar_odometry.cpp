@@ -674,6 +674,7 @@ void LidarOdometry::initialize(const Config& cfg) {
     icp->attachToParameterSource(source_);
     icp->setKeepFinalPairings(false);
     icp->fuseGatedMatchers(true);  // gated blocks (lidar3d-near-far.yaml:183) on the device loop; MOLA_HIP_FUSE_GATES=0: as before
+    icp->fuseMultiPairings(true);  // pairingsPerPoint > 1 likewise (profiles/layers_kbest.md); MOLA_HIP_FUSE_KBEST=0: as before
   }
   // local map definition (yaml:213-242), instantiated at the first key-frame when its $f{} formulas can be evaluated
   const Config& gen = cfg["localmap_generator"];
@@ -1493,6 +1494,7 @@ std::map<std::string, std::string> LidarOdometry::describePipeline() const {
   d["timestamp_method"] = std::to_string(plan_->timestamp_method);
   d["min_points_to_filter"] = std::to_string(plan_->min_points_to_filter);
   d["skip_deskew"] = plan_->skip_deskew ? "true" : "false";
+  d["icp_path"] = icp_[0] ? icp_[0]->alignPath() : "";
   for (const auto& p : plan_->declaredParameters()) d["formula:" + p.name + (d.count("formula:" + p.name) ? "#" + std::to_string(d.size()) : "")] = p.expr;
   for (const auto& p : params_.declaredParameters()) d["formula:" + p.name] = p.expr;
   return d;

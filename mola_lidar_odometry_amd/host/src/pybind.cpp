@@ -62,6 +62,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["far_voxel_metric"] = s.far_voxel_metric; d["force_cpu"] = s.force_cpu;
     return d;
   });
+  m.def("plugin_switch_fuse_kbest", [] { return molahip_host::plugin_switches().fuse_kbest; });  // MOLA_HIP_FUSE_KBEST: -1 not set
   m.def("plugin_switch_fuse_gates", [] { return molahip_host::plugin_switches().fuse_gates; });  // MOLA_HIP_FUSE_GATES: -1 not set (a function of its own: the keys of plugin_switches() are compared as a whole by their users)
   m.def("kernel_from_upstream_name", [](const std::string& n) { return molahip_host::kernel_from_upstream_name(n.c_str(), molahip_host::plugin_switches()); });
   m.def("term_reason_name", [](uint32_t t) { return std::string(enum2str(molahip_host::term_reason_to<IterTermReason>(t))); });
@@ -121,6 +122,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("clearHooks", &ICP::clearHooks)
       .def("forceGenericPath", &ICP::forceGenericPath)
       .def("fuseGatedMatchers", &ICP::fuseGatedMatchers)
+      .def("fuseMultiPairings", &ICP::fuseMultiPairings)
       .def("alignPath", &ICP::alignPath)
       .def("precomputeSchedule", &ICP::precomputeSchedule)
       .def("setHookReplay", &ICP::setHookReplay)

@@ -1,7 +1,8 @@
 """Gated matchers on the fused multi-layer loop against the matcher-by-matcher loop, in the stand-alone driver: molahip-lo-cli on a
 pipeline with an iteration gate (the reference's pipelines/extras/lidar3d-near-far.yaml) over the synthetic city drive of
 tools/multi_seq_bench.py, one sequence, MOLA_HIP_FUSE_GATES=1 against =0 in alternating runs of one build.
-    python tools/gates_bench.py PIPELINE.yaml [scans=120] [out.json]
+    python tools/gates_bench.py PIPELINE.yaml [scans=120] [out.json] [switch=MOLA_HIP_FUSE_GATES]
+(switch: MOLA_HIP_FUSE_KBEST for a pipeline with pairingsPerPoint > 1, profiles/layers_kbest.md.)
 Prints one line per run: steady scans/s, the profile's per-scan milliseconds and ICP counters."""
 import json
 import os
@@ -18,6 +19,7 @@ from mola_lidar_odometry_amd import synth_city  # noqa: E402
 def main():
     pipeline = sys.argv[1]
     n_scans = int(sys.argv[2]) if len(sys.argv) > 2 else 120
+    switch = sys.argv[4] if len(sys.argv) > 4 else "MOLA_HIP_FUSE_GATES"
     tmp = tempfile.mkdtemp(prefix="molahip_gates_")
     seq, _ = synth_city.write_kitti_drive(tmp, n_scans, time_channel=True)
     print("drive written", flush=True)
@@ -26,7 +28,7 @@ def main():
         for mode in ("1", "0"):
             cmd = [bench.CLI, "--pipeline", pipeline, "--out", os.path.join(tmp, "t%s_%d.tum" % (mode, rep)), "--profile",
                    "--time-field", "12", "--seq-dir", seq]
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=dict(os.environ, MOLA_HIP_FUSE_GATES=mode))
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=dict(os.environ, **{switch: mode}))
             if r.returncode != 0:
                 print("molahip-lo-cli failed (%d): %s" % (r.returncode, r.stderr[-800:]), flush=True)
                 return 3
@@ -36,7 +38,7 @@ def main():
             rec = dict(steady_scans_per_s=per["steady_scans_per_s"], scans=per["scans"], good=per["good"],
                        profile={k: v for k, v in prof.items() if k.startswith("icp.") or k.startswith("onLidar")})
             runs[mode].append(rec)
-            print("MOLA_HIP_FUSE_GATES=%s run %d: %s" % (mode, rep, json.dumps(rec)), flush=True)
+            print("%s=%s run %d: %s" % (switch, mode, rep, json.dumps(rec)), flush=True)
     if len(sys.argv) > 3:
         json.dump(runs, open(sys.argv[3], "w"), indent=1)
     return 0

@@ -8,6 +8,10 @@ The shape: the creal scan split by range into two layers (all points | points wi
 subsampled copy of it.  Each route: median of --reps warmed alignments, host clock around synchronised calls.
 
     python tools/layers_align_bench.py [--reps 200] [--pairs 2|3]
+
+--k K: ONE pair instead -- the whole creal layer against the 1 M-point map with pairingsPerPoint K -- on the routes `fused`
+(mh_icp_align_layers_kbest; K = 1: mh_icp_align_layers) and `generic` (mh_nn_search_k matcher by matcher); min - max over the
+repetitions and microseconds per ICP iteration are printed too.
 """
 import argparse
 import os
@@ -38,7 +42,7 @@ _YAML_MATCHER = """  - class: mp2p_icp::Matcher_Points_DistanceThreshold
     params:
       threshold: '%s*ADAPTIVE_THRESHOLD_SIGMA'
       thresholdAngularDeg: 0
-      pairingsPerPoint: 1
+      pairingsPerPoint: %d
       allowMatchAlreadyMatchedGlobalPoints: true
       pointLayerMatches:
         - {global: "%s", local: "%s", weight: 1.0}
@@ -53,6 +57,7 @@ def timed(fn, reps, warm=10):
         t0 = time.perf_counter()
         r = fn()
         ts.append(time.perf_counter() - t0)
+    timed.spread = (1e3 * float(np.min(ts)), 1e3 * float(np.max(ts)))
     return 1e3 * float(np.median(ts)), r
 
 
@@ -61,6 +66,7 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--pairs", type=int, default=2, choices=(2, 3))
     ap.add_argument("--routes", default="fused,generic,single")
+    ap.add_argument("--k", type=int, default=0, help="one pair with this pairingsPerPoint instead of the dual-map shape")
     a = ap.parse_args()
     w = synth.workload_creal()
     rng = np.linalg.norm(w.scan_xyz, axis=1)
@@ -71,6 +77,13 @@ def main():
     spec = [("localmap", "decimated_for_icp", 3.0), ("localmap_far", "decimated_for_icp_near", 2.0)]
     if a.pairs == 3:
         spec.append(("localmap_far", "decimated_for_icp", 2.5))
+    if a.k:
+        spec = spec[:1]
+    kw = dict(pairings_per_point=a.k) if a.k > 1 else {}
+
+    def per_iteration(ms, n_iterations, term):
+        its = n_iterations + (0 if term == "MaxIterations" else 1)  # iterations that ran a match
+        return "%.3f-%.3f ms, %.1f us / ICP iteration" % (timed.spread[0], timed.spread[1], 1e3 * ms / max(its, 1))
     ctx = capi.Context(0)
     maps = {"localmap": capi.Map(ctx, 1.0, 20).build(w.map_xyz), "localmap_far": capi.Map(ctx, 2.0, 20).build(far_g)}
     scans = {"decimated_for_icp": capi.Scan(ctx, full_l), "decimated_for_icp_near": capi.Scan(ctx, near_l)}
@@ -81,12 +94,14 @@ def main():
         ", ".join("%s<-%s" % (g, l) for g, l, _ in spec), len(full_l), len(near_l), len(w.map_xyz), len(far_g)))
     routes = a.routes.split(",")
     if "fused" in routes:
-        ms, r = timed(lambda: capi.icp_align_layers(pairs, w.T_guess, p, want_trace=False), a.reps)
+        ms, r = timed(lambda: capi.icp_align_layers(pairs, w.T_guess, p, want_trace=False, **kw), a.reps)
         print("fused   %.3f ms / alignment  (%d iterations, %s, %d pairs, %d host polls)" % (
             ms, r["n_iterations"], capi.TERM_NAMES[r["termination_reason"]], r["n_final_pairs"], r["n_host_polls"]))
+        if a.k:
+            print("fused   k=%d: %s" % (a.k, per_iteration(ms, r["n_iterations"], capi.TERM_NAMES[r["termination_reason"]])))
     if "generic" in routes:
         from mola_lidar_odometry_amd import _mp2p_icp_hip as hl
-        text = _YAML_HEAD % n_it + "".join(_YAML_MATCHER % (f, g, l) for g, l, f in spec)
+        text = _YAML_HEAD % n_it + "".join(_YAML_MATCHER % (f, max(a.k, 1), g, l) for g, l, f in spec)
         icp, params = hl.icp_pipeline_from_yaml(hl.Config.FromYamlText(text))
         src = hl.ParameterSource()
         src.updateVariable("ADAPTIVE_THRESHOLD_SIGMA", sigma)
@@ -106,6 +121,8 @@ def main():
         ms, r = timed(lambda: icp.align(loc, g, guess, params), a.reps, warm=3)
         print("generic %.3f ms / alignment  (%d iterations, %s, %d pairs)" % (ms, r.nIterations, r.terminationReason.name,
                                                                              r.n_pairs()))
+        if a.k:
+            print("generic k=%d: %s" % (a.k, per_iteration(ms, r.nIterations, r.terminationReason.name)))
     if "single" in routes:
         ms, r = timed(lambda: capi.icp_align(maps["localmap"], scans["decimated_for_icp"], w.T_guess, p, want_trace=False), a.reps)
         print("single  %.3f ms / alignment  (%d iterations, %s, %d pairs; larger pair alone)" % (
