@@ -46,7 +46,8 @@ extern "C" {
 /* The parameter structs of this header carry no size field: they grow at the END, and every growth bumps MH_ABI_VERSION (6:
  * mh_preprocess_params' two decimation-method fields, round 5; 7: mh_layer_pair and mh_icp_align_layers, later also
  * mh_curvature_params and mh_scan_curvature, then the intensity channel's entry points and mh_by_intensity_params,
- * mh_layer_pair_gates and mh_icp_align_layers_gated, mh_layer_pair_knn and mh_icp_align_layers_kbest: new structs
+ * mh_layer_pair_gates and mh_icp_align_layers_gated, mh_layer_pair_knn and mh_icp_align_layers_kbest, mh_layer_job_opts and
+ * mh_icp_align_layers_batch_opts: new structs
  * and entry points change no existing layout, and a binder that lacks
  * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
@@ -670,7 +671,7 @@ MH_API mh_status mh_icp_align_layers(size_t n_pairs, const mh_layer_pair* pairs,
  *  - Two more launches per ICP iteration, whatever the number of pairs.  Results are bitwise reproducible, MH_NO_GRAPH=1 included.
  *  - MH_ERR_UNSUPPORTED also for: a unique pair whose scan has 2^29 or more points, or whose map has been offered 2^28 or more
  *    points (mh_map_info::n_offered: the claim table has an 8-byte entry per source index of the map, owned by the context).
- * No lock-step batch form: mh_icp_align_layers_batch has no opts. */
+ * Lock-step batch form: mh_icp_align_layers_batch_opts (below) takes a job's opts. */
 typedef struct {
   uint32_t unique_global;       /* 1: allowMatchAlreadyMatchedGlobalPoints == false (U13) */
 } mh_layer_pair_opts;
@@ -698,8 +699,7 @@ MH_API mh_status mh_icp_align_layers_opts(size_t n_pairs, const mh_layer_pair* p
  *  - The launch count is unchanged (1 + 2 * inner, + 2 with a unique pair): the gates are data of the uploaded pair table, tested
  *    on the device with the iteration counter; a cached graph is reused whatever the gates are, nothing of them is in its key.  An
  *    inactive pair's match workgroups store "not paired" for its points instead of searching.
- * No lock-step batch form: mh_icp_align_layers_batch has no gates; a gated alignment runs on its own beside the batches, as a
- * unique one does. */
+ * Lock-step batch form: mh_icp_align_layers_batch_opts (below) takes a job's gates; they are no part of a group's key. */
 typedef struct {
   uint32_t run_from_iteration;   /* Matcher::runFromIteration, 0 = no limit */
   uint32_t run_up_to_iteration;  /* Matcher::runUpToIteration, 0 = no limit */
@@ -734,8 +734,7 @@ MH_API mh_status mh_icp_align_layers_gated(size_t n_pairs, const mh_layer_pair* 
  *    and their k are part of the graph key.  Results are bitwise reproducible, MH_NO_GRAPH=1 and MH_NO_PREV_BOUND=1 included.
  *  - MH_ERR_INVALID_ARGUMENT: a pairings_per_point above MH_MAX_PAIRINGS_PER_POINT.  MH_ERR_UNSUPPORTED: scan_i->n * k_i >= 2^32, or
  *    >= 2^29 on a unique pair (the claim key's local field).
- * No lock-step batch form: mh_icp_align_layers_batch has no knn; such an alignment runs on its own beside the batches, as a gated
- * or a unique one does. */
+ * Lock-step batch form: mh_icp_align_layers_batch_opts (below) takes a job's knn; jobs with a k_i > 1 form groups of their own. */
 typedef struct {
   uint32_t pairings_per_point;  /* 0 or 1: one; up to MH_MAX_PAIRINGS_PER_POINT */
 } mh_layer_pair_knn;
@@ -766,7 +765,8 @@ MH_API mh_status mh_icp_align_layers_kbest(size_t n_pairs, const mh_layer_pair* 
  *  - Everything is validated before any device work.  MH_ERR_INVALID_ARGUMENT: n_jobs 0 or above MH_MAX_LAYER_BATCH_JOBS, a job
  *    that mh_icp_align_layers rejects with that code, two jobs on one context, jobs on different devices.  MH_ERR_UNSUPPORTED: a
  *    job that mh_icp_align_layers rejects with that code.  After an error every context stays usable.
- *  - No opts, gates or knn: a unique, gated or pairingsPerPoint > 1 alignment runs on its own beside the batches. */
+ *  - No opts, gates or knn here: mh_icp_align_layers_batch_opts (below) takes them per job, and this function is that one with
+ *    the three arrays NULL in every job -- the same launches, the same uploads, the same bits. */
 #define MH_MAX_LAYER_BATCH_JOBS 64
 typedef struct {
   size_t n_pairs;              /* 1 .. MH_MAX_LAYER_PAIRS */
@@ -777,6 +777,36 @@ MH_API mh_status mh_icp_align_layers_batch(size_t n_jobs, const mh_layer_job* jo
                                            int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
                                            mh_icp_result* results,
                                            uint64_t* final_pair_counts /* n_jobs * MH_MAX_LAYER_PAIRS entries or NULL */);
+
+/* mh_icp_align_layers_batch for mh_icp_align_layers_kbest: every job with its own opts, gates and knn (each n_pairs entries or
+ * NULL, as that call takes them).  (A struct and an entry point of their own: mh_layer_job keeps its layout and MH_ABI_VERSION its
+ * value.)  Everything mh_icp_align_layers_batch promises holds, with "what the single call returns" read as
+ * mh_icp_align_layers_kbest(job i's pairs, opts, gates, knn): T, cov, quality, n_iterations, termination_reason, n_final_pairs,
+ * potential_pairings (by the gated / k-best rule above) and the per-pair counts, bit for bit.  All three arrays NULL (or zeros, or
+ * ones in knn) in every job IS mh_icp_align_layers_batch.  Otherwise, plus:
+ *  - Groups: the key is gn.max_inner_iterations, compute_covariance and ONE more bit -- whether the job has a pair with k_i > 1
+ *    (the single call chooses its accumulation kernels by exactly that).  Unique pairs and gates are not part of it.
+ *  - Launches per ICP iteration, for the whole group: 1 + 2 * gn.max_inner_iterations; + 1 in a group of the k > 1 kind (the search
+ *    of those pairs; the plain search is skipped when every pair of the group has k > 1); + 2 when any job has a unique pair (claim
+ *    and resolve -- a job without a unique pair owns no workgroup of them).  Claims stay per context: every job's claim table is
+ *    its own, so keys of different jobs never meet, and its epochs are consumed as by its single call.
+ *  - A job alone in its group, trivial jobs (max_iterations == 0, nothing active in iteration 0) and every job under
+ *    MH_NO_LOCKSTEP=1 run through mh_icp_align_layers_kbest with their arrays, one after the other.
+ *  - Everything is validated before any device work, for every job: MH_ERR_INVALID_ARGUMENT also for a pairings_per_point above
+ *    MH_MAX_PAIRINGS_PER_POINT; MH_ERR_UNSUPPORTED also for scan_i->n * k_i >= 2^32, a unique pair with 2^29 or more entries or whose
+ *    map has been offered 2^28 or more points.  After an error every context stays usable and no claim epoch has been consumed. */
+typedef struct {
+  size_t n_pairs;                      /* 1 .. MH_MAX_LAYER_PAIRS */
+  const mh_layer_pair* pairs;
+  const mh_layer_pair_opts* opts;      /* n_pairs entries or NULL */
+  const mh_layer_pair_gates* gates;    /* n_pairs entries or NULL */
+  const mh_layer_pair_knn* knn;        /* n_pairs entries or NULL */
+} mh_layer_job_opts;
+
+MH_API mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts* jobs, const mh_icp_params* params,
+                                                int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
+                                                mh_icp_result* results,
+                                                uint64_t* final_pair_counts /* n_jobs * MH_MAX_LAYER_PAIRS entries or NULL */);
 
 #ifdef __cplusplus
 }

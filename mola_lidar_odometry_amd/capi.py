@@ -145,6 +145,13 @@ class LayerJob(C.Structure):
     _fields_ = [("n_pairs", C.c_size_t), ("pairs", C.POINTER(LayerPair))]
 
 
+class LayerJobOpts(C.Structure):
+    """mh_layer_job_opts: one job of mh_icp_align_layers_batch_opts -- its pairs and, each n_pairs entries or NULL, their
+    mh_layer_pair_opts / mh_layer_pair_gates / mh_layer_pair_knn."""
+    _fields_ = [("n_pairs", C.c_size_t), ("pairs", C.POINTER(LayerPair)), ("opts", C.POINTER(LayerPairOpts)),
+                ("gates", C.POINTER(LayerPairGates)), ("knn", C.POINTER(LayerPairKnn))]
+
+
 MAX_LAYER_PAIRS = 8        # MH_MAX_LAYER_PAIRS
 MAX_LAYER_BATCH_JOBS = 64  # MH_MAX_LAYER_BATCH_JOBS
 
@@ -256,6 +263,8 @@ _SIGNATURES = {
                                               C.c_int32]),
     "mh_icp_align_layers_batch": (C.c_int32, [C.c_size_t, C.POINTER(LayerJob), C.POINTER(ICPParamsC), C.c_int32, _DP,
                                               C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
+    "mh_icp_align_layers_batch_opts": (C.c_int32, [C.c_size_t, C.POINTER(LayerJobOpts), C.POINTER(ICPParamsC), C.c_int32, _DP,
+                                                   C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
 }
 
 _lib = None
@@ -950,9 +959,12 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
     return out
 
 
-def icp_align_layers_batch(jobs, T_guesses, params, priors=None):
+def icp_align_layers_batch(jobs, T_guesses, params, priors=None, pairings_per_point=None):
     """mh_icp_align_layers_batch: one multi-layer alignment per job, jobs of the same loop shape in lock step.  `jobs`: a
     sequence of icp_align_layers' `pairs` arguments, every job on a Context of its own; `params`: one ICPParams or one per job.
+    A pair dict may carry unique_global, run_from_iteration and run_up_to_iteration as for icp_align_layers, and
+    pairings_per_point is one entry per job (None, one value for every pair of the job, or one per pair): when any job has any of
+    them the call goes to mh_icp_align_layers_batch_opts, otherwise to mh_icp_align_layers_batch.
     Returns a list of icp_align_layers' dicts (no pairs, no trace); every entry has the bits of that job's single call."""
     n = len(jobs)
     T = np.ascontiguousarray(np.stack([_T12(t) for t in T_guesses]).reshape(len(T_guesses) * 12)) if n else np.zeros(12)
@@ -967,13 +979,33 @@ def icp_align_layers_batch(jobs, T_guesses, params, priors=None):
     else:
         cp, keep = plist[0].c(T[:12])
         cp_ref = C.byref(cp)
-    jarr = (LayerJob * max(1, n))()
-    keep_pairs = []
-    for i, pairs in enumerate(jobs):
-        arr, norm, thr_keep = _layer_pairs(pairs, plist[i].max_iterations)
-        keep_pairs.append((arr, norm, thr_keep))
+    keep_pairs = [_layer_pairs(pairs, plist[i].max_iterations) for i, pairs in enumerate(jobs)]
+    assert pairings_per_point is None or len(pairings_per_point) == n
+    keep_opts = []  # per job: (opts, gates, knn), None where the job has none
+    for i, (arr, norm, thr_keep) in enumerate(keep_pairs):
+        n_pairs = len(norm)
+        opts = gates = knn = None
+        if any(e.get("unique_global") for e in norm):
+            opts = (LayerPairOpts * max(1, n_pairs))()
+            for k, e in enumerate(norm):
+                opts[k].unique_global = 1 if e.get("unique_global") else 0
+        if any(e.get("run_from_iteration") or e.get("run_up_to_iteration") for e in norm):
+            gates = (LayerPairGates * max(1, n_pairs))()
+            for k, e in enumerate(norm):
+                gates[k].run_from_iteration = int(e.get("run_from_iteration") or 0)
+                gates[k].run_up_to_iteration = int(e.get("run_up_to_iteration") or 0)
+        if pairings_per_point is not None and pairings_per_point[i] is not None:
+            knn = (LayerPairKnn * max(1, n_pairs))()
+            for k, v in enumerate(np.broadcast_to(np.asarray(pairings_per_point[i]), (n_pairs,))):
+                knn[k].pairings_per_point = int(v)
+        keep_opts.append((opts, gates, knn))
+    with_opts = any(o is not None for t in keep_opts for o in t)
+    jarr = ((LayerJobOpts if with_opts else LayerJob) * max(1, n))()
+    for i, (arr, norm, thr_keep) in enumerate(keep_pairs):
         jarr[i].n_pairs = len(norm)
         jarr[i].pairs = arr
+        if with_opts:
+            jarr[i].opts, jarr[i].gates, jarr[i].knn = keep_opts[i]  # (None: NULL)
     pr_arr, keep_pr = None, []
     if priors is not None:
         pr_arr = (C.POINTER(Prior) * max(1, n))()
@@ -983,7 +1015,8 @@ def icp_align_layers_batch(jobs, T_guesses, params, priors=None):
                 pr_arr[i] = C.pointer(keep_pr[-1])
     res = (ICPResult * max(1, n))()
     counts = (C.c_uint64 * (max(1, n) * MAX_LAYER_PAIRS))()
-    _chk(lib().mh_icp_align_layers_batch(n, jarr, cp_ref, 1 if per_job else 0, T.ctypes.data_as(_DP), pr_arr, res, counts))
+    call = lib().mh_icp_align_layers_batch_opts if with_opts else lib().mh_icp_align_layers_batch
+    _chk(call(n, jarr, cp_ref, 1 if per_job else 0, T.ctypes.data_as(_DP), pr_arr, res, counts))
     out = []
     for i in range(n):
         d = _result_dict(res[i])

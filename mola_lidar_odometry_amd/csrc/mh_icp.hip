@@ -17,7 +17,7 @@
 //   mh_k_launch.h                  their __global__ entry points (single alignment | one job per blockIdx.y)
 //   this file                      AlignJob: the chain a layer takes, loop control (one-launch loop | streaming | chunks + hipGraph), mh_icp_align
 //   mh_icp_job.inl                 what AlignJob and LayersJob share: result / state / solver set-up, graph cache, result read-back
-//   mh_icp_layers.inl, mh_icp_layers_batch.inl   LayersJob, mh_icp_align_layers, mh_icp_align_layers_batch
+//   mh_icp_layers.inl, mh_icp_layers_batch.inl   LayersJob, mh_icp_align_layers, mh_icp_align_layers_batch(_opts)
 //   mh_icp_batch.inl               mh_icp_align_batch (lock-step groups)
 //   mh_icp_api.inl                 matcher- / solver-granular entry points (mh_nn_search*, mh_gn_solve, mh_covariance)
 //   mh_dev_variants.h              (-DMH_DEV_VARIANTS only) the tile / wave / sorted-scan matchers that lost to the product kernels

@@ -3,6 +3,12 @@
 // walk one flattened range over (job, pair) (mh_k_layers.h), k_solve_b / k_cov_prepare_b / k_cov_finalize_b take a workgroup per
 // job.  Every job is set up by LayersJob::start exactly as a single call sets it up, in its own context; its partials keep the
 // single call's columns and stride, so its result has that call's bits.
+// mh_icp_align_layers_batch_opts: the same with every job's unique pairs, iteration gates and pairings per point (what
+// mh_icp_align_layers_kbest takes).  LayersJob::start builds the job's ClaimTable and KnnTable as for a single call; a group with
+// such a job uploads a LayerBatchOptTable (mh_k_claim.h) behind its LayerBatchTable and enqueues k_match_layers_kb behind
+// k_match_layers_b when a job has a pair with k > 1, and k_claim_layers_b -> k_resolve_layers_b before the first accumulation when
+// a job has a unique pair.  A group of the k > 1 kind accumulates through k_accum_layers_kb / k_cov_accum_layers_kb, as the single
+// call chooses the *_k entry points.  Gates are data of the jobs' tables.  A group without any of it issues what it always issued.
 // Loop control is align_batch_run's chunked one on the lead job's stream.  The chunks are launched directly, NOT replayed from a
 // captured graph: a group's composition changes from batch to batch as sequences end, and a chunk is 1 + 2 * inner launches per
 // iteration for ALL jobs where the single calls issue that many each.
@@ -16,14 +22,23 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
   hipStream_t s = lead->stream;
   MH_TRY(order_after_layers_job_streams(lead, g));
   // [gathered states] | job descriptors of the solve / covariance kernels | the (job, pair) table: pinned mirror and device copy
-  const size_t desc_bytes = A * sizeof(BatchJob) + sizeof(LayerBatchTable);
+  // ... and, in a group with a unique pair or a pair of k > 1, the jobs' claim / k-best tables and ranges behind it
+  bool with_opts = false, kbest = false;
+  for (const LayersJob* j : g) {
+    with_opts = with_opts || j->L.unique_mask || j->L.knn_key;
+    kbest = kbest || j->L.knn_key;
+  }
+  const size_t tab_bytes = sizeof(LayerBatchTable) + (with_opts ? sizeof(LayerBatchOptTable) : 0);
+  const size_t desc_bytes = A * sizeof(BatchJob) + tab_bytes;
   IcpDeviceState* h_states = nullptr;
   BatchJob* h_desc = nullptr;
-  MH_TRY(reserve_group_buffers(lead, A, sizeof(LayerBatchTable), h_states, h_desc));
+  MH_TRY(reserve_group_buffers(lead, A, tab_bytes, h_states, h_desc));
   LayerBatchTable* const h_tab = reinterpret_cast<LayerBatchTable*>(h_desc + A);
+  LayerBatchOptTable* const h_opt = with_opts ? reinterpret_cast<LayerBatchOptTable*>(h_tab + 1) : nullptr;
+  static_assert(sizeof(LayerBatchTable) % 8 == 0, "staging layout");
   memset(h_desc, 0, desc_bytes);
   h_tab->n_jobs = A;
-  uint32_t tot_match = 0, tot_acc = 0, tot_cov = 0, max_iterations = 0, chunk = 0;
+  uint32_t tot_match = 0, tot_acc = 0, tot_cov = 0, tot_claim = 0, tot_match_k = 0, max_iterations = 0, chunk = 0;
   const mh_icp_params* const p0 = g[0]->p;
   const uint32_t inner = p0->gn.max_inner_iterations;
   const bool cov = p0->compute_covariance != 0, auto_chunk = p0->poll_every == 0;
@@ -35,6 +50,15 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
     tot_match += j.L.tot_match;
     tot_acc += j.L.tot_acc;
     tot_cov += j.L.tot_cov;
+    if (h_opt) {  // (a job without a unique pair / a pair of k > 1 owns no workgroup of those launches: its address is never read)
+      char* const dbase = j.ctx->layers_tab.as<char>();
+      h_opt->job_blk_claim[a] = tot_claim;
+      h_opt->job_blk_match_k[a] = tot_match_k;
+      tot_claim += j.L.tot_claim;
+      tot_match_k += j.L.tot_match_k;
+      h_opt->j[a].claims = j.L.unique_mask ? reinterpret_cast<const ClaimTable*>(dbase + j.L.claim_off) : nullptr;
+      h_opt->j[a].knn = j.L.knn_key ? reinterpret_cast<const KnnTable*>(dbase + j.L.knn_off) : nullptr;
+    }
     LayerBatchJob& t = h_tab->j[a];
     t.tab = j.ctx->layers_tab.as<LayerTable>();
     t.st = j.ctx->d_state;
@@ -55,24 +79,38 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
   h_tab->job_blk_match[A] = tot_match;
   h_tab->job_blk_acc[A] = tot_acc;
   h_tab->job_blk_cov[A] = tot_cov;
+  if (h_opt) {
+    h_opt->job_blk_claim[A] = tot_claim;
+    h_opt->job_blk_match_k[A] = tot_match_k;
+  }
   MH_HIP(hipMemcpyAsync(lead->batch_desc.p, h_desc, desc_bytes, hipMemcpyHostToDevice, s));
   const BatchJob* const dj = lead->batch_desc.as<BatchJob>();
   const LayerBatchTable* const dt = reinterpret_cast<const LayerBatchTable*>(dj + A);
+  const LayerBatchOptTable* const dopt = reinterpret_cast<const LayerBatchOptTable*>(dt + 1);  // (read in a group with such a job only)
+  // (a group of the k > 1 kind: the entry points that take the local point of an entry from its k, as align_layers chooses them)
+  const auto accum = kbest ? k_accum_layers_kb : k_accum_layers_b;
+  const auto cov_accum = kbest ? k_cov_accum_layers_kb : k_cov_accum_layers_b;
   uint32_t enqueued = 0, polls = 0;
   for (;;) {
     const uint32_t m = (max_iterations - enqueued) < chunk ? (max_iterations - enqueued) : chunk;
     for (uint32_t it = 0; it < m; it++) {
-      hipLaunchKernelGGL(k_match_layers_b, dim3(tot_match), dim3(kFlatThreads), 0, s, dt);
-      hipLaunchKernelGGL(k_accum_layers_b, dim3(tot_acc), dim3(kBlock), 0, s, dt, 1u);
+      // (a launch without workgroups is skipped: every pair of the group with k > 1, nobody unique)
+      if (tot_match) hipLaunchKernelGGL(k_match_layers_b, dim3(tot_match), dim3(kFlatThreads), 0, s, dt);
+      if (tot_match_k) hipLaunchKernelGGL(k_match_layers_kb, dim3(tot_match_k), dim3(kFlatThreads), 0, s, dt, dopt);
+      if (tot_claim) {
+        hipLaunchKernelGGL(k_claim_layers_b, dim3(tot_claim), dim3(kBlock), 0, s, dt, dopt);
+        hipLaunchKernelGGL(k_resolve_layers_b, dim3(tot_claim), dim3(kBlock), 0, s, dt, dopt);
+      }
+      hipLaunchKernelGGL(accum, dim3(tot_acc), dim3(kBlock), 0, s, dt, 1u);
       hipLaunchKernelGGL(k_solve_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj, 1u);
       for (uint32_t in = 1; in < inner; in++) {
-        hipLaunchKernelGGL(k_accum_layers_b, dim3(tot_acc), dim3(kBlock), 0, s, dt, 0u);
+        hipLaunchKernelGGL(accum, dim3(tot_acc), dim3(kBlock), 0, s, dt, 0u);
         hipLaunchKernelGGL(k_solve_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj, 0u);
       }
     }
     if (cov) {  // no-ops for jobs whose loop has not terminated
       hipLaunchKernelGGL(k_cov_prepare_b, dim3(1, A), dim3(64), 0, s, dj);
-      hipLaunchKernelGGL(k_cov_accum_layers_b, dim3(tot_cov), dim3(kBlock), 0, s, dt);
+      hipLaunchKernelGGL(cov_accum, dim3(tot_cov), dim3(kBlock), 0, s, dt);
       hipLaunchKernelGGL(k_cov_finalize_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj);
     }
     MH_TRY(gather_states(lead, dj, A, h_states));
@@ -93,42 +131,69 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
   return MH_OK;
 }
 
-mh_status mh_icp_align_layers_batch(size_t n_jobs, const mh_layer_job* jobs, const mh_icp_params* params, int32_t params_per_job,
-                                    const double* T_guesses, const mh_prior* const* priors, mh_icp_result* results,
-                                    uint64_t* final_pair_counts) {
+// (pair k of a job: its options, the defaults where the job has no such array)
+static inline uint32_t job_kpp(const mh_layer_job_opts& j, size_t k) {
+  return j.knn && j.knn[k].pairings_per_point ? j.knn[k].pairings_per_point : 1u;
+}
+static inline bool job_unique(const mh_layer_job_opts& j, size_t k) { return j.opts && j.opts[k].unique_global; }
+
+mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts* jobs, const mh_icp_params* params,
+                                         int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
+                                         mh_icp_result* results, uint64_t* final_pair_counts) {
   MH_REQUIRE(n_jobs >= 1 && n_jobs <= MH_MAX_LAYER_BATCH_JOBS, "n_jobs must be 1 .. MH_MAX_LAYER_BATCH_JOBS");
   MH_REQUIRE(jobs && params && T_guesses && results, "null argument");
   auto P = [&](size_t i) { return params_per_job ? &params[i] : params; };
-  // everything is checked before anything is queued: after an error no context has seen any work
+  // everything is checked before anything is queued: after an error no context has seen any work (and no claim epoch is taken)
   for (size_t i = 0; i < n_jobs; i++) {
     MH_TRY(check_layers_args(jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, &results[i]));
     for (size_t k = 0; k < i; k++)
       MH_REQUIRE(jobs[k].pairs[0].scan->ctx != jobs[i].pairs[0].scan->ctx, "each job of a batch needs its own context");
     MH_REQUIRE(jobs[i].pairs[0].scan->ctx->device == jobs[0].pairs[0].scan->ctx->device, "the jobs of a batch live on different devices");
+    for (size_t k = 0; jobs[i].knn && k < jobs[i].n_pairs; k++)
+      MH_REQUIRE(jobs[i].knn[k].pairings_per_point <= MH_MAX_PAIRINGS_PER_POINT, "pairings_per_point must be 0 .. MH_MAX_PAIRINGS_PER_POINT");
   }
   for (size_t i = 0; i < n_jobs; i++) {
     MH_TRY(check_layers_supported(jobs[i].n_pairs, jobs[i].pairs, P(i)));
-    for (size_t k = 0; k < jobs[i].n_pairs; k++)
-      if (jobs[i].pairs[k].map->n_records >= kFlatMaxRecords)
+    for (size_t k = 0; k < jobs[i].n_pairs; k++) {
+      const mh_layer_pair& pr = jobs[i].pairs[k];
+      if (pr.map->n_records >= kFlatMaxRecords)
         return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: a map of 2^30 or more records");
+      // (what mh_icp_align_layers_kbest refuses before, and LayersJob::claims_begin inside, its start())
+      const uint64_t entries = (uint64_t)pr.scan->n * job_kpp(jobs[i], k);
+      if (jobs[i].knn && entries >= (1ull << 32))
+        return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_batch_opts: scan size * pairings_per_point does not fit 32 bits");
+      if (job_unique(jobs[i], k) && entries >= kClaimMaxScan)
+        return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_batch_opts: a unique pair with 2^29 or more pairing entries");
+      if (job_unique(jobs[i], k) && pr.map->n_offered >= kClaimMaxEntries)
+        return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_batch_opts: a unique pair whose map has been offered 2^28 or more points");
+    }
   }
   const Switches sw = read_switches();
   auto counts_of = [&](size_t i) { return final_pair_counts ? final_pair_counts + i * MH_MAX_LAYER_PAIRS : nullptr; };
   if (final_pair_counts)
     for (size_t i = 0; i < n_jobs * MH_MAX_LAYER_PAIRS; i++) final_pair_counts[i] = 0;
-  // lock-step groups: same inner steps, same covariance switch (the launches of a chunk are the same for every job of a group)
+  // lock-step groups: same inner steps, same covariance switch, and a pair with k > 1 or none (the launches of a chunk are the same
+  // for every job of a group; unique pairs and gates do not change them: a job without a unique pair owns no claim workgroup)
+  auto has_kbest = [&](size_t i) {
+    bool any = false;
+    for (size_t k = 0; k < jobs[i].n_pairs; k++) any = any || job_kpp(jobs[i], k) > 1u;
+    return any;
+  };
   std::vector<LayersJob> lj(n_jobs);
   std::vector<std::vector<size_t>> groups;
   std::vector<char> in_group(n_jobs, 0);
   if (!sw.no_lockstep) {
     for (size_t i = 0; i < n_jobs; i++) {
       const mh_icp_params* q = P(i);
-      size_t total_n = 0;
-      for (size_t k = 0; k < jobs[i].n_pairs; k++) total_n += jobs[i].pairs[k].scan->n;
-      if (q->max_iterations == 0 || total_n == 0) continue;  // trivial: nothing to run
+      // (LayersJob::potential_in(0): the entries of the pairs that are active in iteration 0)
+      uint64_t potential0 = 0;
+      for (size_t k = 0; k < jobs[i].n_pairs; k++)
+        if (!jobs[i].gates || jobs[i].gates[k].run_from_iteration == 0) potential0 += (uint64_t)jobs[i].pairs[k].scan->n * job_kpp(jobs[i], k);
+      if (q->max_iterations == 0 || potential0 == 0) continue;  // trivial: nothing to run
       std::vector<size_t>* g = nullptr;
       for (auto& c : groups)
-        if (P(c[0])->gn.max_inner_iterations == q->gn.max_inner_iterations && (P(c[0])->compute_covariance != 0) == (q->compute_covariance != 0))
+        if (P(c[0])->gn.max_inner_iterations == q->gn.max_inner_iterations &&
+            (P(c[0])->compute_covariance != 0) == (q->compute_covariance != 0) && has_kbest(c[0]) == has_kbest(i))
           g = &c;
       if (!g) {
         groups.emplace_back();
@@ -145,7 +210,7 @@ mh_status mh_icp_align_layers_batch(size_t n_jobs, const mh_layer_job* jobs, con
     std::vector<LayersJob*> g;
     for (size_t i : c) {
       MH_TRY(lj[i].start(sw, (uint32_t)jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr,
-                         &results[i], nullptr, counts_of(i)));
+                         &results[i], nullptr, counts_of(i), jobs[i].opts, jobs[i].gates, jobs[i].knn));
       g.push_back(&lj[i]);
     }
     MH_TRY(align_layers_lockstep(g));
@@ -154,6 +219,17 @@ mh_status mh_icp_align_layers_batch(size_t n_jobs, const mh_layer_job* jobs, con
   for (size_t i = 0; i < n_jobs; i++)
     if (!in_group[i])
       MH_TRY(align_layers(sw, (uint32_t)jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr,
-                          &results[i], nullptr, nullptr, counts_of(i), MH_MEM_HOST));
+                          &results[i], nullptr, nullptr, counts_of(i), MH_MEM_HOST, jobs[i].opts, jobs[i].gates, jobs[i].knn));
   return MH_OK;
+}
+
+// (the shared implementation with no opts, gates or knn: the checks, the groups, the uploads and the launches it always had)
+mh_status mh_icp_align_layers_batch(size_t n_jobs, const mh_layer_job* jobs, const mh_icp_params* params, int32_t params_per_job,
+                                    const double* T_guesses, const mh_prior* const* priors, mh_icp_result* results,
+                                    uint64_t* final_pair_counts) {
+  MH_REQUIRE(n_jobs >= 1 && n_jobs <= MH_MAX_LAYER_BATCH_JOBS, "n_jobs must be 1 .. MH_MAX_LAYER_BATCH_JOBS");
+  MH_REQUIRE(jobs, "null argument");
+  mh_layer_job_opts jo[MH_MAX_LAYER_BATCH_JOBS];
+  for (size_t i = 0; i < n_jobs; i++) jo[i] = mh_layer_job_opts{jobs[i].n_pairs, jobs[i].pairs, nullptr, nullptr, nullptr};
+  return mh_icp_align_layers_batch_opts(n_jobs, jo, params, params_per_job, T_guesses, priors, results, final_pair_counts);
 }

@@ -51,15 +51,12 @@ __device__ __forceinline__ unsigned long long claim_key(uint32_t epoch, uint32_t
   return ((unsigned long long)epoch << 32) | (unsigned long long)((li << kClaimLocalBits) | i);
 }
 
-__global__ __launch_bounds__(kBlock) void k_claim_layers(const IcpDeviceState* __restrict__ st, const LayerTable* __restrict__ tab,
-                                                         const ClaimTable* __restrict__ claims) {
-  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
-  if (cst->done) return;  // grid-uniform
-  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
-  const cclaim_ptr cc = (cclaim_ptr)uniform_const_ptr(claims);
-  const uint32_t li = layer_of(cc->blk, ct->n_pairs, blockIdx.x);
+// one workgroup of the claims of an alignment that has not terminated: workgroup `b` of its table's flattened claim range
+__device__ __forceinline__ void claim_layers_block(const clayers_state_ptr cst, const clayers_ptr ct, const cclaim_ptr cc,
+                                                   const uint32_t b) {
+  const uint32_t li = layer_of(cc->blk, ct->n_pairs, b);
   if (!layer_active(ct, li, cst->iter)) return;  // (wave-uniform; k_match_layers has left kNoMatch in its whole segment)
-  const uint32_t i = (blockIdx.x - cc->blk[li]) * kBlock + threadIdx.x;
+  const uint32_t i = (b - cc->blk[li]) * kBlock + threadIdx.x;
   if (i >= layer_entries(ct, li)) return;
   const uint32_t g = G(ct->d[li].pair_gidx)[i];
   if (g == kNoMatch || g >= cc->entries[li]) return;  // (no source index reaches the region's end: mh_map_insert numbers them below n_offered)
@@ -67,15 +64,12 @@ __global__ __launch_bounds__(kBlock) void k_claim_layers(const IcpDeviceState* _
                                __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(kBlock) void k_resolve_layers(const IcpDeviceState* __restrict__ st, const LayerTable* __restrict__ tab,
-                                                           const ClaimTable* __restrict__ claims) {
-  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
-  if (cst->done) return;  // grid-uniform
-  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
-  const cclaim_ptr cc = (cclaim_ptr)uniform_const_ptr(claims);
-  const uint32_t li = layer_of(cc->blk, ct->n_pairs, blockIdx.x);
+// ... and of their resolution, over the same range
+__device__ __forceinline__ void resolve_layers_block(const clayers_state_ptr cst, const clayers_ptr ct, const cclaim_ptr cc,
+                                                     const uint32_t b) {
+  const uint32_t li = layer_of(cc->blk, ct->n_pairs, b);
   if (!layer_active(ct, li, cst->iter)) return;  // (wave-uniform; k_match_layers has left kNoMatch in its whole segment)
-  const uint32_t i = (blockIdx.x - cc->blk[li]) * kBlock + threadIdx.x;
+  const uint32_t i = (b - cc->blk[li]) * kBlock + threadIdx.x;
   if (i >= layer_entries(ct, li)) return;
   uint32_t* const gidx = ct->d[li].pair_gidx;
   const uint32_t g = G(gidx)[i];
@@ -84,4 +78,63 @@ __global__ __launch_bounds__(kBlock) void k_resolve_layers(const IcpDeviceState*
   uint32_t* const w = reinterpret_cast<uint32_t*>(ct->d[li].pair_q + i) + 3;
   G(w)[0] = G(w)[0] | 0x80000000u;
   G(gidx)[i] = kNoMatch;
+}
+
+__global__ __launch_bounds__(kBlock) void k_claim_layers(const IcpDeviceState* __restrict__ st, const LayerTable* __restrict__ tab,
+                                                         const ClaimTable* __restrict__ claims) {
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
+  if (cst->done) return;  // grid-uniform
+  claim_layers_block(cst, (clayers_ptr)uniform_const_ptr(tab), (cclaim_ptr)uniform_const_ptr(claims), blockIdx.x);
+}
+
+__global__ __launch_bounds__(kBlock) void k_resolve_layers(const IcpDeviceState* __restrict__ st, const LayerTable* __restrict__ tab,
+                                                           const ClaimTable* __restrict__ claims) {
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
+  if (cst->done) return;  // grid-uniform
+  resolve_layers_block(cst, (clayers_ptr)uniform_const_ptr(tab), (cclaim_ptr)uniform_const_ptr(claims), blockIdx.x);
+}
+
+// ---- lock-step batches (mh_icp_align_layers_batch_opts) ---------------------------------------------------------------------------
+// What the claim and the k-best launches of a group need beside its LayerBatchTable (mh_k_layers.h), job by job in that table's
+// order: the job's ClaimTable and KnnTable in its own context's memory (null where it has no unique pair / no pair with k > 1:
+// such a job owns no workgroup of those launches and the address is never read), and the jobs' first workgroups in the two
+// flattened grids.  A table of its own, uploaded only for a group that has a job with an option: LayerBatchTable, its upload and
+// the *_layers_b kernels that read it stay what they were.
+struct KnnTable;
+struct LayerBatchOptJob {
+  const ClaimTable* claims;
+  const KnnTable* knn;
+};
+
+struct LayerBatchOptTable {
+  uint32_t job_blk_claim[MH_MAX_LAYER_BATCH_JOBS + 1];    // k_claim_layers_b / k_resolve_layers_b (+ the total)
+  uint32_t job_blk_match_k[MH_MAX_LAYER_BATCH_JOBS + 1];  // k_match_layers_kb
+  LayerBatchOptJob j[MH_MAX_LAYER_BATCH_JOBS];
+};
+
+typedef const LayerBatchOptTable __attribute__((address_space(4))) * clayer_batch_opt_ptr;
+
+// k_claim_layers / k_resolve_layers one level up, as k_match_layers_b is k_match_layers: the job by layer_of over the jobs' prefix
+// array, out when it has terminated, then the job's own ClaimTable with the job's own iteration counter.  Keys of different jobs
+// never meet: every job's regions lie in its own context's claim table.
+__global__ __launch_bounds__(kBlock) void k_claim_layers_b(const LayerBatchTable* __restrict__ bt,
+                                                           const LayerBatchOptTable* __restrict__ bo) {
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const clayer_batch_opt_ptr co = (clayer_batch_opt_ptr)uniform_const_ptr(bo);
+  const uint32_t ji = layer_of(co->job_blk_claim, cb->n_jobs, blockIdx.x);
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(cb->j[ji].st);
+  if (cst->done) return;  // uniform over the job's workgroups
+  claim_layers_block(cst, (clayers_ptr)uniform_const_ptr(cb->j[ji].tab), (cclaim_ptr)uniform_const_ptr(co->j[ji].claims),
+                     blockIdx.x - co->job_blk_claim[ji]);
+}
+
+__global__ __launch_bounds__(kBlock) void k_resolve_layers_b(const LayerBatchTable* __restrict__ bt,
+                                                             const LayerBatchOptTable* __restrict__ bo) {
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const clayer_batch_opt_ptr co = (clayer_batch_opt_ptr)uniform_const_ptr(bo);
+  const uint32_t ji = layer_of(co->job_blk_claim, cb->n_jobs, blockIdx.x);
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(cb->j[ji].st);
+  if (cst->done) return;  // uniform over the job's workgroups
+  resolve_layers_block(cst, (clayers_ptr)uniform_const_ptr(cb->j[ji].tab), (cclaim_ptr)uniform_const_ptr(co->j[ji].claims),
+                       blockIdx.x - co->job_blk_claim[ji]);
 }

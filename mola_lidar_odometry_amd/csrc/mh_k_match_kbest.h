@@ -233,17 +233,12 @@ struct KnnTable {
 };
 typedef const KnnTable __attribute__((address_space(4))) * cknn_ptr;
 
-__global__ __launch_bounds__(kFlatThreads) void k_match_layers_k(const IcpDeviceState* __restrict__ st,
-                                                                 const LayerTable* __restrict__ tab,
-                                                                 const KnnTable* __restrict__ knn) {
-  __shared__ FlatWaveK shk[kFlatThreads / 64];
-  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
-  if (cst->done) return;  // grid-uniform
-  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
-  const cknn_ptr ck = (cknn_ptr)uniform_const_ptr(knn);
-  const uint32_t li = layer_of(ck->blk, ct->n_pairs, blockIdx.x);
+// one wave of k_match_layers_k: workgroup `b` of the table's flattened k-best range (`cst`: the alignment's state, not terminated)
+__device__ __forceinline__ void match_layers_k_wave(mh::FlatWaveK& sh, const clayers_state_ptr cst, const clayers_ptr ct,
+                                                    const cknn_ptr ck, const uint32_t b) {
+  const uint32_t li = layer_of(ck->blk, ct->n_pairs, b);
   const uint32_t n = ct->d[li].n, k = ct->d[li].kpp;
-  const uint32_t i0 = (blockIdx.x - ck->blk[li]) * kFlatPointsPerBlock + (threadIdx.x & ~63u);
+  const uint32_t i0 = (b - ck->blk[li]) * kFlatPointsPerBlock + (threadIdx.x & ~63u);
   if (i0 >= n) return;    // whole waves
   const uint32_t iter = cst->iter;
   if (!layer_active(ct, li, iter)) {  // (match_layers_wave: "not paired" for every entry of the pair, no bound left behind)
@@ -273,8 +268,32 @@ __global__ __launch_bounds__(kFlatThreads) void k_match_layers_k(const IcpDevice
 #pragma unroll
   for (int j = 0; j < 12; j++) T[j] = cst->T[j];
   const double thr = G(ct->d[li].mk.thr)[iter];
-  match_kbest_wave(shk[threadIdx.x >> 6], map, T, (float)(thr * thr), ct->d[li].mk.ang2, have_prev, ct->d[li].lx, ct->d[li].ly,
+  match_kbest_wave(sh, map, T, (float)(thr * thr), ct->d[li].mk.ang2, have_prev, ct->d[li].lx, ct->d[li].ly,
                    ct->d[li].lz, n, k, i0, ct->d[li].pair_q, ct->d[li].pair_gidx);
+}
+
+__global__ __launch_bounds__(kFlatThreads) void k_match_layers_k(const IcpDeviceState* __restrict__ st,
+                                                                 const LayerTable* __restrict__ tab,
+                                                                 const KnnTable* __restrict__ knn) {
+  __shared__ FlatWaveK shk[kFlatThreads / 64];
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
+  if (cst->done) return;  // grid-uniform
+  match_layers_k_wave(shk[threadIdx.x >> 6], cst, (clayers_ptr)uniform_const_ptr(tab), (cknn_ptr)uniform_const_ptr(knn), blockIdx.x);
+}
+
+// k_match_layers_k for a lock-step group (mh_icp_align_layers_batch_opts, LayerBatchOptTable: mh_k_claim.h): the job by layer_of
+// over the jobs' k-best prefix array, out when it has terminated, then the job's own KnnTable.  A job without a pair of k > 1 owns
+// no workgroup here, a job whose pairs all have k > 1 none of k_match_layers_b.
+__global__ __launch_bounds__(kFlatThreads) void k_match_layers_kb(const LayerBatchTable* __restrict__ bt,
+                                                                  const LayerBatchOptTable* __restrict__ bo) {
+  __shared__ FlatWaveK shk[kFlatThreads / 64];
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const clayer_batch_opt_ptr co = (clayer_batch_opt_ptr)uniform_const_ptr(bo);
+  const uint32_t ji = layer_of(co->job_blk_match_k, cb->n_jobs, blockIdx.x);
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(cb->j[ji].st);
+  if (cst->done) return;  // uniform over the job's workgroups
+  match_layers_k_wave(shk[threadIdx.x >> 6], cst, (clayers_ptr)uniform_const_ptr(cb->j[ji].tab),
+                      (cknn_ptr)uniform_const_ptr(co->j[ji].knn), blockIdx.x - co->job_blk_match_k[ji]);
 }
 
 // k_accum_layers / k_cov_accum_layers for a table with a pair of k > 1: blk_acc / blk_cov are sized by the entries
@@ -296,4 +315,31 @@ __global__ __launch_bounds__(kBlock) void k_cov_accum_layers_k(const IcpDeviceSt
   const uint32_t k = ct->d[li].kpp ? ct->d[li].kpp : 1u;
   k_cov_accum_body<true>(st, 0u, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n * k, ct->d[li].pair_gidx,
                          partials + ct->d[li].cov_off, pstride, blockIdx.x - ct->blk_cov[li], k);
+}
+
+// ... and for a lock-step group with such a table among its jobs' (k_accum_layers_b / k_cov_accum_layers_b with the entries and
+// their k: a job whose table has no such pair divides by one and keeps its bits)
+__global__ __launch_bounds__(kBlock, MH_ACCUM_WAVES) void k_accum_layers_kb(const LayerBatchTable* __restrict__ bt, uint32_t first) {
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const uint32_t ji = layer_of(cb->job_blk_acc, cb->n_jobs, blockIdx.x);
+  const IcpDeviceState* const st = cb->j[ji].st;
+  if (((clayers_state_ptr)uniform_const_ptr(st))->done) return;  // uniform over the job's workgroups
+  const LayerTable* const tab = cb->j[ji].tab;
+  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
+  const uint32_t b = blockIdx.x - cb->job_blk_acc[ji];
+  const uint32_t li = layer_of(ct->blk_acc, ct->n_pairs, b);
+  const uint32_t k = ct->d[li].kpp ? ct->d[li].kpp : 1u;
+  k_accum_body<true, true>(st, first, &tab->d[li].mk, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n * k, ct->d[li].pair_q,
+                           ct->d[li].pair_gidx, cb->j[ji].part + ct->d[li].col_off, cb->j[ji].tot_acc, b - ct->blk_acc[li], k);
+}
+
+__global__ __launch_bounds__(kBlock) void k_cov_accum_layers_kb(const LayerBatchTable* __restrict__ bt) {
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const uint32_t ji = layer_of(cb->job_blk_cov, cb->n_jobs, blockIdx.x);
+  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(cb->j[ji].tab);
+  const uint32_t b = blockIdx.x - cb->job_blk_cov[ji];
+  const uint32_t li = layer_of(ct->blk_cov, ct->n_pairs, b);
+  const uint32_t k = ct->d[li].kpp ? ct->d[li].kpp : 1u;
+  k_cov_accum_body<true>(cb->j[ji].st, 0u, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n * k, ct->d[li].pair_gidx,
+                         cb->j[ji].part + ct->d[li].cov_off, cb->j[ji].tot_cov, b - ct->blk_cov[li], k);
 }

@@ -21,6 +21,10 @@
 //   MOLA_HIP_FUSE_KBEST       (unset) | 0 | 1         matchers with pairingsPerPoint 2 .. MH_MAX_PAIRINGS_PER_POINT on the fused
 //                                                     multi-layer loop (mh_icp_align_layers_kbest); set, it overrides
 //                                                     ICP::fuseMultiPairings and the adapter's default (off) both ways
+//   MOLA_HIP_BATCH_OPTS       1 | 0                   (host layer with an AlignBatcher only) multi-layer alignments with a unique
+//                                                     pair, a gate or pairingsPerPoint > 1 join the lock-step batches
+//                                                     (mh_icp_align_layers_batch_opts); 0: each runs on its own beside them
+//                                                     (AlignBatcher::runOutside), as before that entry point existed
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -41,6 +45,7 @@ struct PluginSwitches {
   bool force_cpu = false;
   int fuse_gates = -1;  // MOLA_HIP_FUSE_GATES: -1 not set (the caller's own setting holds), 0 | 1
   int fuse_kbest = -1;  // MOLA_HIP_FUSE_KBEST: the same for pairingsPerPoint > 1
+  bool batch_opts = true;  // MOLA_HIP_BATCH_OPTS: unique / gated / k-best multi-layer alignments join the AlignBatcher's batches
   // which of them came from the environment (the mirror classes only override their YAML values for those)
   bool has_gm_form = false, has_index_mode = false, has_cov_step = false, has_min_delta = false, has_max_cost = false,
        has_pt2pl_mode = false, has_far_metric = false;
@@ -95,6 +100,7 @@ inline PluginSwitches read_plugin_switches() {
   if (const char* e = getenv("MOLA_HIP_FORCE_CPU")) s.force_cpu = atoi(e) != 0;
   if (const char* e = getenv("MOLA_HIP_FUSE_GATES")) s.fuse_gates = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("MOLA_HIP_FUSE_KBEST")) s.fuse_kbest = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("MOLA_HIP_BATCH_OPTS")) s.batch_opts = atoi(e) != 0;
   return s;
 }
 
