@@ -46,9 +46,9 @@ extern "C" {
 /* The parameter structs of this header carry no size field: they grow at the END, and every growth bumps MH_ABI_VERSION (6:
  * mh_preprocess_params' two decimation-method fields, round 5; 7: mh_layer_pair and mh_icp_align_layers, later also
  * mh_curvature_params and mh_scan_curvature, then the intensity channel's entry points and mh_by_intensity_params,
- * mh_layer_pair_gates and mh_icp_align_layers_gated, mh_layer_pair_knn and mh_icp_align_layers_kbest, mh_layer_job_opts and
- * mh_icp_align_layers_batch_opts: new structs
- * and entry points change no existing layout, and a binder that lacks
+ * mh_layer_pair_gates and mh_icp_align_layers_gated, mh_layer_pair_knn and mh_icp_align_layers_kbest, mh_layer_pair_plane and
+ * mh_icp_align_layers_planes, mh_layer_job_opts and mh_icp_align_layers_batch_opts: new structs and entry points change no
+ * existing layout, and a binder that lacks
  * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
  * built with) and zero-initialises every struct it passes -- a field the binder does not know then reads as its default. */
@@ -747,6 +747,57 @@ MH_API mh_status mh_icp_align_layers_kbest(size_t n_pairs, const mh_layer_pair* 
                                            mh_icp_result* result, mh_icp_iter* trace,
                                            const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
                                            uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
+
+/* mh_icp_align_layers_kbest with Matcher_Point2Plane on a plain point layer (KNN + PCA) per pair: rgbd.yaml:133-151 has one
+ * Matcher_Points_DistanceThreshold (pairingsPerPoint 2) on its edge layers and one Matcher_Point2Plane on its plane layers, both
+ * feeding one Solver_GaussNewton.  (A struct and an entry point of their own once more: the structs above keep their layout and
+ * MH_ABI_VERSION its value.)  planes == NULL or knn == 0 in every entry IS mh_icp_align_layers_kbest: the same launches, the same
+ * graph keys, the same upload, the same bits (mh_icp_align_layers_kbest calls this function with NULL).  Otherwise the contracts
+ * above, n_pairs 1 included, plus, for a PLANE pair i (planes[i].knn != 0):
+ *  - Matching: in every iteration in which it is active, pair i runs the matcher of mh_nn_search_pt2pl_knn on (map_i, scan_i) at the
+ *    iteration's pose, with distance_threshold = pairs[i].threshold[k] (this matcher's schedule) and the other four parameters
+ *    from planes[i].  Given the same pose, the centroids, the normals and the index set are those of mh_nn_search_pt2pl_knn, bit
+ *    for bit.  (The map's NDT statistics, if any, are not used.)
+ *  - Solve: each plane pairing is ONE row, e = n.(R l + t - c), with the iteration's robust kernel and kernel_param, scaled by
+ *    pairs[i].weight.  gn.weight_pt2pl is ignored, as gn.weight_pt2pt already is.
+ *  - Counts: a plane pair adds scan_i->n to potential_pairings (over the pairs active in k_last, the gated rule); its pairings go
+ *    into n_final_pairs, the trace's n_pairs and final_pair_counts[i]; n_final_pairs_pt2pl is the sum over the plane pairs;
+ *    NoPairings is decided on the total.
+ *  - Covariance: mh_covariance over the union -- three rows per point pairing, one per plane pairing, unweighted.
+ *  - final_plane_pairs[i] (nullable array of n_pairs entries; arrays in pairs_mem of scan_i->n entries) receives the pair's plane
+ *    pairings in ascending local index.  final_pairs[i] is not written for a plane pair, final_plane_pairs[i] not for a point pair.
+ *  - Gates act on a plane pair as on any pair: outside its interval it has no pairing and nothing in any count.
+ *  - A scan shared between a plane pair and a point pair is paired again for each; the MH_MATCHED_POINTS_SKIP refusal is unchanged.
+ *  - MH_ERR_INVALID_ARGUMENT: a plane pair with unique_global != 0, pairings_per_point > 1 or threshold_angular_deg != 0; a knn,
+ *    search_radius, plane_eigen_threshold or an entry of its threshold schedule that mh_nn_search_pt2pl_knn rejects (the same
+ *    code decides; minimum_plane_points below 3 counts as 3 there and here).  Everything is validated before any device work;
+ *    afterwards the context stays usable.
+ *  - Launches per ICP iteration, with P = 1 when any pair is a plain point pair (k = 1) and 0 otherwise, K = 1 when any pair has
+ *    k > 1, A = 1 when any pair is a point pair (of either kind), U = 2 with a unique pair:
+ *        P + K + 1 + U + (A + 1 + 1) * gn.max_inner_iterations
+ *    -- the plane search, and per inner step the point accumulation (when there is a point pair), the plane accumulation and the
+ *    solve.  With point pairs that is 1 + gn.max_inner_iterations more than without the plane pairs; a table of plane pairs only
+ *    launches neither the plain search nor the point accumulation (1 + 2 * gn.max_inner_iterations).  The covariance that closes
+ *    the loop has one more launch.  The set of plane pairs and their knn are part of the graph key.  Results are bitwise
+ *    reproducible, MH_NO_GRAPH=1 and MH_NO_PREV_BOUND=1 included.
+ * No lock-step batch form yet: mh_icp_align_layers_batch_opts takes no planes. */
+typedef struct {
+  uint32_t knn;                   /* 0: a point pair (everything as before); 3 .. MH_MAX_PLANE_KNN: a plane pair */
+  uint32_t minimum_plane_points;  /* >= 3 */
+  double plane_eigen_threshold;
+  double search_radius;
+} mh_layer_pair_plane;
+
+MH_API mh_status mh_icp_align_layers_planes(size_t n_pairs, const mh_layer_pair* pairs,
+                                            const mh_layer_pair_opts* opts /* n_pairs entries or NULL */,
+                                            const mh_layer_pair_gates* gates /* n_pairs entries or NULL */,
+                                            const mh_layer_pair_knn* knn /* n_pairs entries or NULL */,
+                                            const mh_layer_pair_plane* planes /* n_pairs entries or NULL */,
+                                            const mh_icp_params* params, const double T_guess[12], const mh_prior* prior,
+                                            mh_icp_result* result, mh_icp_iter* trace,
+                                            const mh_pairs_out* final_pairs /* n_pairs entries or NULL */,
+                                            const mh_pairs_pl_out* final_plane_pairs /* n_pairs entries or NULL */,
+                                            uint64_t* final_pair_counts /* n_pairs entries or NULL */, int32_t pairs_mem);
 
 /* Many multi-layer alignments from one host thread, one context per job: mh_icp_align_batch for mh_icp_align_layers.  Job i has
  * all its maps and scans on ONE context, distinct jobs have distinct contexts of the same device, and each job's pairs obey the

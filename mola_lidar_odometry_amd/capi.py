@@ -140,6 +140,12 @@ class LayerPairKnn(C.Structure):
     _fields_ = [("pairings_per_point", C.c_uint32)]
 
 
+class LayerPairPlane(C.Structure):
+    """mh_layer_pair_plane: Matcher_Point2Plane (KNN + PCA) on a pair's point layers; knn 0 = a point pair."""
+    _fields_ = [("knn", C.c_uint32), ("minimum_plane_points", C.c_uint32), ("plane_eigen_threshold", C.c_double),
+                ("search_radius", C.c_double)]
+
+
 class LayerJob(C.Structure):
     """mh_layer_job: the layer pairs of one job of mh_icp_align_layers_batch."""
     _fields_ = [("n_pairs", C.c_size_t), ("pairs", C.POINTER(LayerPair))]
@@ -154,6 +160,7 @@ class LayerJobOpts(C.Structure):
 
 MAX_LAYER_PAIRS = 8        # MH_MAX_LAYER_PAIRS
 MAX_LAYER_BATCH_JOBS = 64  # MH_MAX_LAYER_BATCH_JOBS
+MAX_PLANE_KNN = 16         # MH_MAX_PLANE_KNN
 
 
 class PreprocessParams(C.Structure):
@@ -261,6 +268,10 @@ _SIGNATURES = {
                                               C.POINTER(LayerPairKnn), C.POINTER(ICPParamsC), _DP, C.POINTER(Prior),
                                               C.POINTER(ICPResult), C.POINTER(ICPIter), C.POINTER(PairsOut), C.POINTER(C.c_uint64),
                                               C.c_int32]),
+    "mh_icp_align_layers_planes": (C.c_int32, [C.c_size_t, C.POINTER(LayerPair), C.POINTER(LayerPairOpts), C.POINTER(LayerPairGates),
+                                               C.POINTER(LayerPairKnn), C.POINTER(LayerPairPlane), C.POINTER(ICPParamsC), _DP,
+                                               C.POINTER(Prior), C.POINTER(ICPResult), C.POINTER(ICPIter), C.POINTER(PairsOut),
+                                               C.POINTER(PairsPlOut), C.POINTER(C.c_uint64), C.c_int32]),
     "mh_icp_align_layers_batch": (C.c_int32, [C.c_size_t, C.POINTER(LayerJob), C.POINTER(ICPParamsC), C.c_int32, _DP,
                                               C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
     "mh_icp_align_layers_batch_opts": (C.c_int32, [C.c_size_t, C.POINTER(LayerJobOpts), C.POINTER(ICPParamsC), C.c_int32, _DP,
@@ -896,8 +907,12 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
     call goes to mh_icp_align_layers_opts; run_from_iteration / run_up_to_iteration (Matcher::runFromIteration / runUpToIteration,
     0 = no limit): with one that is set it goes to mh_icp_align_layers_gated.  pairings_per_point (pairingsPerPoint: one value
     for every pair, or one per pair): when given the call goes to mh_icp_align_layers_kbest, and pair i's arrays hold up to
-    scan_i.n * k_i pairings, a point's in ascending distance.
-    Returns icp_align's dict plus pair_counts (final pairings per pair) and, with want_pairs, pairs (one dict per pair)."""
+    scan_i.n * k_i pairings, a point's in ascending distance.  A dict may carry plane=dict(knn=..., minimum_plane_points=...,
+    plane_eigen_threshold=..., search_radius=...) (Matcher_Point2Plane on the pair's point layers, its threshold the matcher's
+    distanceThreshold): with one the call goes to mh_icp_align_layers_planes, and that pair's entry of `pairs` is
+    {local_idx, centroid, normal}.
+    Returns icp_align's dict (n_final_pairs_pt2pl: the plane pairs' pairings) plus pair_counts (final pairings per pair) and, with
+    want_pairs, pairs (one dict per pair)."""
     p_c = replace(p, threshold=p.threshold if p.threshold is not None else 0.0)
     cp, keep = p_c.c(T_guess)
     T0 = _T12(T_guess)
@@ -911,6 +926,22 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
     pr = _mk_prior(prior)
     counts = (C.c_uint64 * max(1, n_pairs))()
     po, bufs = None, []
+    planes = None
+    if any(e.get("plane") for e in norm):
+        planes = (LayerPairPlane * max(1, n_pairs))()
+        for i, e in enumerate(norm):
+            q = e.get("plane")
+            if q:
+                planes[i] = LayerPairPlane(int(q["knn"]), int(q["minimum_plane_points"]), float(q["plane_eigen_threshold"]),
+                                           float(q["search_radius"]))
+    ppl, pl_bufs = None, {}
+    if want_pairs and planes is not None:
+        ppl = (PairsPlOut * max(1, n_pairs))()
+        for i, e in enumerate(norm):
+            if e.get("plane"):
+                li, a, out_i = _pl_arrays(max(e["scan"].n, 1))
+                ppl[i] = out_i
+                pl_bufs[i] = (li, a)
     if want_pairs:
         po = (PairsOut * max(1, n_pairs))()
         for i, e in enumerate(norm):
@@ -931,7 +962,15 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
         for i, e in enumerate(norm):
             gates[i].run_from_iteration = int(e.get("run_from_iteration") or 0)
             gates[i].run_up_to_iteration = int(e.get("run_up_to_iteration") or 0)
-    if kpp is not None:
+    if planes is not None:
+        knn = None
+        if kpp is not None:
+            knn = (LayerPairKnn * max(1, n_pairs))()
+            for i, k in enumerate(kpp):
+                knn[i].pairings_per_point = k
+        _chk(lib().mh_icp_align_layers_planes(n_pairs, arr, opts, gates, knn, planes, C.byref(cp), T0.ctypes.data_as(_DP),
+                                              C.byref(pr) if pr else None, C.byref(res), trace, po, ppl, counts, MEM_HOST))
+    elif kpp is not None:
         knn = (LayerPairKnn * max(1, n_pairs))()
         for i, k in enumerate(kpp):
             knn[i].pairings_per_point = k
@@ -954,6 +993,11 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
         out["pairs"] = []
         for i, (li, gi, gx, gy, gz, d2) in enumerate(bufs):
             k = out["pair_counts"][i]
+            if i in pl_bufs:
+                pli, a = pl_bufs[i]
+                out["pairs"].append(dict(local_idx=pli[:k].copy(), centroid=np.stack(a[:3], 1)[:k].copy(),
+                                         normal=np.stack(a[3:], 1)[:k].copy()))
+                continue
             out["pairs"].append(dict(local_idx=li[:k].copy(), global_idx=gi[:k].copy(),
                                      global_xyz=np.stack([gx[:k], gy[:k], gz[:k]], 1), d2=d2[:k].copy()))
     return out

@@ -17,7 +17,9 @@
 //   mh_k_launch.h                  their __global__ entry points (single alignment | one job per blockIdx.y)
 //   this file                      AlignJob: the chain a layer takes, loop control (one-launch loop | streaming | chunks + hipGraph), mh_icp_align
 //   mh_icp_job.inl                 what AlignJob and LayersJob share: result / state / solver set-up, graph cache, result read-back
-//   mh_icp_layers.inl, mh_icp_layers_batch.inl   LayersJob, mh_icp_align_layers, mh_icp_align_layers_batch(_opts)
+//   mh_k_layers.h, mh_k_claim.h, mh_k_match_kbest.h, mh_k_match_planes.h
+//                                  the multi-layer loop's kernels: pair table, unique pairs, pairingsPerPoint > 1, plane pairs (KNN + PCA)
+//   mh_icp_layers.inl, mh_icp_layers_batch.inl   LayersJob, mh_icp_align_layers(_planes), mh_icp_align_layers_batch(_opts)
 //   mh_icp_batch.inl               mh_icp_align_batch (lock-step groups)
 //   mh_icp_api.inl                 matcher- / solver-granular entry points (mh_nn_search*, mh_gn_solve, mh_covariance)
 //   mh_dev_variants.h              (-DMH_DEV_VARIANTS only) the tile / wave / sorted-scan matchers that lost to the product kernels
@@ -62,6 +64,7 @@
 #include "mh_k_layers.h"
 #include "mh_k_claim.h"
 #include "mh_k_match_kbest.h"
+#include "mh_k_match_planes.h"
 #include "mh_k_pairs.h"
 
 // ================================================================================================
@@ -210,6 +213,60 @@ mh_status compact_pairs_of(mh_ctx* ctx, const uint32_t* gidx, const float4* q, s
 // ... of the context's own pair buffers (a single alignment's)
 mh_status compact_pairs(mh_ctx* ctx, size_t n, const mh_pairs_out* out, int32_t mem, uint64_t* n_pairs_out) {
   return compact_pairs_of(ctx, ctx->pair_gidx.as<uint32_t>(), ctx->pair_q.as<float4>(), n, out, mem, n_pairs_out);
+}
+
+// compaction of point-to-plane pairing buffers (pl_c / pl_n, n entries) into caller arrays
+mh_status compact_pl_pairs_of(mh_ctx* ctx, const float4* pl_c, const float4* pl_n, size_t n, const mh_pairs_pl_out* out, int32_t mem,
+                              uint64_t* n_pairs_out) {
+  hipStream_t s = ctx->stream;
+  const uint32_t nb = nblk(n);
+  const size_t n4 = ((n + 63) / 64) * 64;
+  // layout: flags[n4] | counts[nb] | offsets[nb] | total[1] | (host staging) li,cx,cy,cz,nx,ny,nz [n4 each]
+  const size_t hdr = ((n4 + (size_t)2 * nb + 1) * 4 + 255) / 256 * 256;
+  MH_TRY(ctx->compact.reserve(hdr + 7 * n4 * 4));
+  uint32_t* flags = ctx->compact.as<uint32_t>();
+  uint32_t* counts = flags + n4;
+  uint32_t* offsets = counts + nb;
+  uint32_t* total = offsets + nb;
+  char* stage = ctx->compact.as<char>() + hdr;
+  void* o[7] = {out->local_idx, out->cx, out->cy, out->cz, out->nx, out->ny, out->nz};
+  void* d[7];
+  for (int a = 0; a < 7; a++) d[a] = (mem == MH_MEM_DEVICE) ? o[a] : (o[a] ? (void*)(stage + (size_t)a * n4 * 4) : nullptr);
+  uint32_t h_total = 0;
+  if (n) {
+    hipLaunchKernelGGL(k_pl_flags, dim3(nb), dim3(kBlock), 0, s, pl_c, (uint32_t)n, flags);
+    hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(kBlock), 0, s, flags, (uint32_t)n, counts);
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, counts, nb, offsets, total);
+    hipLaunchKernelGGL(k_compact_pl, dim3(nb), dim3(kBlock), 0, s, flags, pl_c, pl_n,
+                       (uint32_t)n, offsets, (uint32_t*)d[0], (float*)d[1], (float*)d[2], (float*)d[3], (float*)d[4],
+                       (float*)d[5], (float*)d[6]);
+    MH_HIP(hipGetLastError());
+    MH_HIP(hipMemcpyAsync(&h_total, total, 4, hipMemcpyDeviceToHost, s));
+    MH_HIP(mh::wait_stream(s));
+  }
+  if (mem == MH_MEM_HOST && h_total)
+    for (int a = 0; a < 7; a++)
+      if (o[a]) MH_HIP(hipMemcpy(o[a], d[a], (size_t)h_total * 4, hipMemcpyDeviceToHost));
+  if (n_pairs_out) *n_pairs_out = h_total;
+  return MH_OK;
+}
+
+// the argument rules of the KNN + PCA plane matcher (mh_nn_search_pt2pl_knn; a plane pair of mh_icp_align_layers_planes obeys the
+// same) and its kernel argument
+mh_status check_pl_knn_params(const mh_pt2pl_knn_params* params) {
+  MH_REQUIRE(params->knn >= 3 && params->knn <= (uint32_t)kMaxPlaneKnn, "knn must be 3..MH_MAX_PLANE_KNN");
+  MH_REQUIRE(isfinite(params->distance_threshold) && isfinite(params->plane_eigen_threshold) && isfinite(params->search_radius) &&
+             params->search_radius > 0.0, "bad thresholds");
+  return MH_OK;
+}
+PlKnnArg pl_knn_arg(const mh_pt2pl_knn_params* params) {
+  PlKnnArg a;
+  a.distance_threshold = params->distance_threshold;
+  a.plane_eigen_threshold = params->plane_eigen_threshold;
+  a.radius2 = (float)(params->search_radius * params->search_radius);
+  a.knn = params->knn;
+  a.min_pts = params->minimum_plane_points < 3u ? 3u : params->minimum_plane_points;  // (three points span a plane)
+  return a;
 }
 
 std::atomic<unsigned long long> g_loop16_runs{0}, g_loop16_fallbacks{0};  // one-launch loops started / abandoned for the chain (mh_debug_loop_stats)
@@ -993,14 +1050,17 @@ size_t mh_pairs_block_bytes(size_t n_scan_points) {
 
 #include "mh_icp_api.inl"    // mh_nn_search*, mh_gn_solve, mh_covariance
 
-mh_status mh_icp_align_layers_kbest(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
-                                    const mh_layer_pair_gates* gates, const mh_layer_pair_knn* knn, const mh_icp_params* params,
-                                    const double T_guess[12], const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
-                                    const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
+mh_status mh_icp_align_layers_planes(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
+                                     const mh_layer_pair_gates* gates, const mh_layer_pair_knn* knn,
+                                     const mh_layer_pair_plane* planes, const mh_icp_params* params, const double T_guess[12],
+                                     const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
+                                     const mh_pairs_out* final_pairs, const mh_pairs_pl_out* final_plane_pairs,
+                                     uint64_t* final_pair_counts, int32_t pairs_mem) {
   MH_TRY(check_layers_args(n_pairs, pairs, params, T_guess, result));
-  MH_REQUIRE(!final_pairs || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
+  MH_REQUIRE(!(final_pairs || final_plane_pairs) || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
   for (size_t i = 0; knn && i < n_pairs; i++)
     MH_REQUIRE(knn[i].pairings_per_point <= MH_MAX_PAIRINGS_PER_POINT, "pairings_per_point must be 0 .. MH_MAX_PAIRINGS_PER_POINT");
+  MH_TRY(check_layers_planes(n_pairs, pairs, opts, knn, planes, params));
   MH_TRY(check_layers_supported(n_pairs, pairs, params));
   for (size_t i = 0; knn && i < n_pairs; i++) {
     const uint64_t entries = (uint64_t)pairs[i].scan->n * (knn[i].pairings_per_point ? knn[i].pairings_per_point : 1u);
@@ -1009,8 +1069,19 @@ mh_status mh_icp_align_layers_kbest(size_t n_pairs, const mh_layer_pair* pairs, 
     if (opts && opts[i].unique_global && entries >= kClaimMaxScan)
       return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_kbest: a unique pair with 2^29 or more pairing entries");
   }
+  bool any_plane = false;
+  for (size_t i = 0; planes && i < n_pairs; i++) any_plane = any_plane || planes[i].knn != 0u;
   return align_layers(read_switches(), (uint32_t)n_pairs, pairs, params, T_guess, prior, result, trace, final_pairs,
-                      final_pair_counts, pairs_mem, opts, gates, knn);
+                      final_pair_counts, pairs_mem, opts, gates, knn, any_plane ? planes : nullptr,
+                      any_plane ? final_plane_pairs : nullptr);
+}
+
+mh_status mh_icp_align_layers_kbest(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
+                                    const mh_layer_pair_gates* gates, const mh_layer_pair_knn* knn, const mh_icp_params* params,
+                                    const double T_guess[12], const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
+                                    const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
+  return mh_icp_align_layers_planes(n_pairs, pairs, opts, gates, knn, nullptr, params, T_guess, prior, result, trace, final_pairs,
+                                    nullptr, final_pair_counts, pairs_mem);
 }
 
 mh_status mh_icp_align_layers_gated(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,

@@ -175,37 +175,7 @@ mh_status mh_nn_search_dense(const mh_map* map, const mh_scan* scan, const doubl
 
 // compaction of the context's point-to-plane pairing buffers into caller arrays
 static mh_status compact_pl_pairs(mh_ctx* ctx, size_t n, const mh_pairs_pl_out* out, int32_t mem, uint64_t* n_pairs_out) {
-  hipStream_t s = ctx->stream;
-  const uint32_t nb = nblk(n);
-  const size_t n4 = ((n + 63) / 64) * 64;
-  // layout: flags[n4] | counts[nb] | offsets[nb] | total[1] | (host staging) li,cx,cy,cz,nx,ny,nz [n4 each]
-  const size_t hdr = ((n4 + (size_t)2 * nb + 1) * 4 + 255) / 256 * 256;
-  MH_TRY(ctx->compact.reserve(hdr + 7 * n4 * 4));
-  uint32_t* flags = ctx->compact.as<uint32_t>();
-  uint32_t* counts = flags + n4;
-  uint32_t* offsets = counts + nb;
-  uint32_t* total = offsets + nb;
-  char* stage = ctx->compact.as<char>() + hdr;
-  void* o[7] = {out->local_idx, out->cx, out->cy, out->cz, out->nx, out->ny, out->nz};
-  void* d[7];
-  for (int a = 0; a < 7; a++) d[a] = (mem == MH_MEM_DEVICE) ? o[a] : (o[a] ? (void*)(stage + (size_t)a * n4 * 4) : nullptr);
-  uint32_t h_total = 0;
-  if (n) {
-    hipLaunchKernelGGL(k_pl_flags, dim3(nb), dim3(kBlock), 0, s, ctx->pl_c.as<float4>(), (uint32_t)n, flags);
-    hipLaunchKernelGGL(k_count_valid, dim3(nb), dim3(kBlock), 0, s, flags, (uint32_t)n, counts);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, counts, nb, offsets, total);
-    hipLaunchKernelGGL(k_compact_pl, dim3(nb), dim3(kBlock), 0, s, flags, ctx->pl_c.as<float4>(), ctx->pl_n.as<float4>(),
-                       (uint32_t)n, offsets, (uint32_t*)d[0], (float*)d[1], (float*)d[2], (float*)d[3], (float*)d[4],
-                       (float*)d[5], (float*)d[6]);
-    MH_HIP(hipGetLastError());
-    MH_HIP(hipMemcpyAsync(&h_total, total, 4, hipMemcpyDeviceToHost, s));
-    MH_HIP(mh::wait_stream(s));
-  }
-  if (mem == MH_MEM_HOST && h_total)
-    for (int a = 0; a < 7; a++)
-      if (o[a]) MH_HIP(hipMemcpy(o[a], d[a], (size_t)h_total * 4, hipMemcpyDeviceToHost));
-  if (n_pairs_out) *n_pairs_out = h_total;
-  return MH_OK;
+  return compact_pl_pairs_of(ctx, ctx->pl_c.as<float4>(), ctx->pl_n.as<float4>(), n, out, mem, n_pairs_out);
 }
 
 mh_status mh_nn_search_pt2pl(const mh_map* map, const mh_scan* scan, const double T[12], double distance_threshold,
@@ -251,9 +221,7 @@ mh_status mh_nn_search_pt2pl_knn(const mh_map* map, const mh_scan* scan, const d
   MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE, "bad mem space");
   MH_REQUIRE(map->ctx->device == scan->ctx->device, "map and scan live on different devices");
   MH_REQUIRE(pose_ok(T), "non-finite pose");
-  MH_REQUIRE(params->knn >= 3 && params->knn <= (uint32_t)kMaxPlaneKnn, "knn must be 3..MH_MAX_PLANE_KNN");
-  MH_REQUIRE(isfinite(params->distance_threshold) && isfinite(params->plane_eigen_threshold) && isfinite(params->search_radius) &&
-             params->search_radius > 0.0, "bad thresholds");
+  MH_TRY(check_pl_knn_params(params));
   mh_ctx* ctx = scan->ctx;
   MH_TRY(set_device(ctx));
   MH_TRY(map_ready_on(map, ctx->stream));
@@ -265,12 +233,7 @@ mh_status mh_nn_search_pt2pl_knn(const mh_map* map, const mh_scan* scan, const d
   MH_TRY(ensure_pl_buffers(ctx, scan->n));
   PoseArg Ta;
   for (int i = 0; i < 12; i++) Ta.m[i] = T[i];
-  PlKnnArg a;
-  a.distance_threshold = params->distance_threshold;
-  a.plane_eigen_threshold = params->plane_eigen_threshold;
-  a.radius2 = (float)(params->search_radius * params->search_radius);
-  a.knn = params->knn;
-  a.min_pts = params->minimum_plane_points < 3u ? 3u : params->minimum_plane_points;  // (three points span a plane)
+  const PlKnnArg a = pl_knn_arg(params);
   hipLaunchKernelGGL(k_match_pl_knn, dim3(nblk(scan->n)), dim3(kBlock), 0, ctx->stream, Ta, a, scan->x, scan->y, scan->z,
                      (uint32_t)scan->n, map->view(sw), ctx->pl_c.as<float4>(), ctx->pl_n.as<float4>());
   MH_HIP(hipGetLastError());

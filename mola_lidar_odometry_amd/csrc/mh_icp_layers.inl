@@ -11,8 +11,11 @@
 // of it.  Nothing about the gates enters the graph key.
 // pairingsPerPoint > 1 (mh_icp_align_layers_kbest, mh_k_match_kbest.h): such a pair's segment holds n * k entries and it is searched
 // by k_match_layers_k, one more launch per iteration beside k_match_layers; the accumulation and the covariance are then the *_k
-// entry points, and the pairs' k are part of the graph key.  Loop
-// control is AlignJob's chunked one: a chunk of iterations is enqueued (replayed from a captured graph once its shape repeats,
+// entry points, and the pairs' k are part of the graph key.
+// Matcher_Point2Plane on a point layer (mh_icp_align_layers_planes, mh_k_match_planes.h): such a pair owns no workgroup and no
+// column of the plain kernels; k_match_layers_pl searches it, k_accum_layers_pl / k_cov_accum_layers_pl put its rows into the second
+// partials block that k_solve / k_cov_finalize sum behind the first, and the set of such pairs with their knn is part of the graph key.
+// Loop control is AlignJob's chunked one: a chunk of iterations is enqueued (replayed from a captured graph once its shape repeats,
 // MH_NO_GRAPH=1: never), the host waits for its event and reads the done flag.
 
 constexpr unsigned long long kLayersGraphTag = 0x4C41594552530000ull;  // "LAYERS": no size of a single alignment's key comes near it
@@ -27,6 +30,11 @@ struct LayersLayout {
   uint32_t tot_match_k = 0;  // workgroups of k_match_layers_k (0: no pair with k > 1; it is not launched, the kernels are the plain ones)
   uint32_t knn_key = 0;      // 4 bits per pair: its k when above 1
   size_t knn_off = 0;        // byte offset of the KnnTable in layers_tab
+  uint32_t tot_match_pl = 0; // workgroups of k_match_layers_pl (0: no plane pair; none of the plane kernels is launched)
+  uint32_t tot_acc_pl = 0;   // workgroups of k_accum_layers_pl / k_cov_accum_layers_pl = columns of the second partials block
+  unsigned long long plane_key = 0;  // 5 bits per pair: its knn when it is a plane pair
+  size_t plane_off = 0;      // byte offset of the PlaneTable in layers_tab
+  size_t seg_c[MH_MAX_LAYER_PAIRS], seg_n[MH_MAX_LAYER_PAIRS];  // byte offsets of a plane pair's pl_c / pl_n
 };
 
 // One multi-layer alignment from its arguments to its uploaded [state | parameters | table | schedules]: what a single call and a
@@ -39,6 +47,8 @@ struct LayersJob {
   mh_icp_result* res = nullptr;
   mh_layer_pair_gates gates[MH_MAX_LAYER_PAIRS] = {};  // all zero: no gate
   uint32_t kpp[MH_MAX_LAYER_PAIRS] = {};               // pairings per point, >= 1
+  mh_layer_pair_plane pl[MH_MAX_LAYER_PAIRS] = {};     // knn 0: a point pair
+  const PlaneTable* ptab = nullptr;  // the pinned mirror of the device's plane table (with a plane pair)
   bool trivial = false;       // nothing to run: the result is complete after start()
   LayersLayout L;
   const LayerTable* tab = nullptr;  // the pinned mirror of the device table (the pairing segments: count_pairs)
@@ -47,7 +57,7 @@ struct LayersJob {
   mh_status start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
                   const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
                   const mh_layer_pair_opts* opts = nullptr, const mh_layer_pair_gates* gates_ = nullptr,
-                  const mh_layer_pair_knn* knn = nullptr);
+                  const mh_layer_pair_knn* knn = nullptr, const mh_layer_pair_plane* planes = nullptr);
   size_t entries(uint32_t i) const { return pairs[i].scan->n * (size_t)kpp[i]; }  // of pair i's pairing segment
   uint32_t k_last = 0;        // after finish(): the ICP iteration whose match produced the final pairings
   bool active_in(uint32_t i, uint32_t k) const {  // layer_active (mh_k_layers.h) on the host
@@ -61,7 +71,8 @@ struct LayersJob {
     return s;
   }
   void finish(uint32_t polls, uint32_t enqueued);
-  mh_status count_pairs(const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem);
+  mh_status count_pairs(const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem,
+                        const mh_pairs_pl_out* final_plane_pairs = nullptr);
   mh_status claims_begin(ClaimTable* ct);
 };
 
@@ -108,7 +119,8 @@ mh_status LayersJob::claims_begin(ClaimTable* ct) {
 
 mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
                            const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
-                           const mh_layer_pair_opts* opts, const mh_layer_pair_gates* gates_, const mh_layer_pair_knn* knn) {
+                           const mh_layer_pair_opts* opts, const mh_layer_pair_gates* gates_, const mh_layer_pair_knn* knn,
+                           const mh_layer_pair_plane* planes) {
   np = np_;
   pairs = pairs_;
   p = p_;
@@ -118,6 +130,7 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     for (uint32_t i = 0; i < np; i++) final_pair_counts[i] = 0;
   for (uint32_t i = 0; i < np; i++) gates[i] = gates_ ? gates_[i] : mh_layer_pair_gates{};
   for (uint32_t i = 0; i < np; i++) kpp[i] = knn && knn[i].pairings_per_point ? knn[i].pairings_per_point : 1u;
+  for (uint32_t i = 0; i < np; i++) pl[i] = planes ? planes[i] : mh_layer_pair_plane{};
   // (every pair gated off in iteration 0 is NoPairings there, like no points at all)
   if ((trivial = begin_result(res, p, T0, potential_in(0)))) return MH_OK;
   MH_TRY(set_device(ctx));
@@ -146,8 +159,11 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   L.claim_off = (tab_bytes + sched_bytes + 255) / 256 * 256;
   for (uint32_t i = 0; i < np; i++) L.knn_key |= kpp[i] > 1u ? kpp[i] << (4 * i) : 0u;
   L.knn_off = (L.claim_off + sizeof(ClaimTable) + 255) / 256 * 256;
-  const size_t up_bytes = L.knn_key ? L.knn_off + sizeof(KnnTable)
-                                    : L.unique_mask ? L.claim_off + sizeof(ClaimTable) : tab_bytes + sched_bytes;
+  for (uint32_t i = 0; i < np; i++) L.plane_key |= (unsigned long long)pl[i].knn << (5 * i);
+  L.plane_off = (L.knn_off + sizeof(KnnTable) + 255) / 256 * 256;
+  const size_t up_bytes = L.plane_key ? L.plane_off + sizeof(PlaneTable)
+                          : L.knn_key ? L.knn_off + sizeof(KnnTable)
+                                      : L.unique_mask ? L.claim_off + sizeof(ClaimTable) : tab_bytes + sched_bytes;
   MH_TRY(ctx->h_layers.reserve(up_bytes));
   MH_TRY(ctx->layers_tab.reserve(up_bytes));
   LayerTable* const tab = ctx->h_layers.as<LayerTable>();
@@ -156,9 +172,21 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   tab->n_pairs = np;
   KnnTable* const kt = reinterpret_cast<KnnTable*>(ctx->h_layers.as<char>() + L.knn_off);  // (written with a pair of k > 1 only)
   if (L.knn_key) memset(kt, 0, sizeof(KnnTable));
+  PlaneTable* const pt = reinterpret_cast<PlaneTable*>(ctx->h_layers.as<char>() + L.plane_off);  // (written with a plane pair only)
+  if (L.plane_key) memset(pt, 0, sizeof(PlaneTable));
+  ptab = L.plane_key ? pt : nullptr;
   for (uint32_t i = 0; i < np; i++) {
     const size_t n = entries(i), nn = n ? n : 1;  // (k = 1: the points)
-    const size_t n_flat = kpp[i] > 1u ? 0 : n, n_flat_k = kpp[i] > 1u ? pairs[i].scan->n : 0;
+    const bool plane = pl[i].knn != 0u;
+    const size_t n_flat = (kpp[i] > 1u || plane) ? 0 : n, n_flat_k = kpp[i] > 1u ? pairs[i].scan->n : 0;
+    if (L.plane_key) {
+      pt->blk_match[i] = L.tot_match_pl;
+      pt->blk_acc[i] = pt->blk_cov[i] = L.tot_acc_pl;
+      if (plane) {
+        L.tot_match_pl += (uint32_t)((n + kFlatPointsPerBlock - 1) / kFlatPointsPerBlock);
+        L.tot_acc_pl += n ? nblk(n) : 0u;
+      }
+    }
     if (L.knn_key) kt->blk[i] = L.tot_match_k;
     L.tot_match_k += (uint32_t)((n_flat_k + kFlatPointsPerBlock - 1) / kFlatPointsPerBlock);
     L.seg_q[i] = L.pair_bytes;
@@ -169,13 +197,26 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     tab->blk_acc[i] = L.tot_acc;
     tab->blk_cov[i] = L.tot_cov;
     L.tot_match += (uint32_t)((n_flat + kFlatPointsPerBlock - 1) / kFlatPointsPerBlock);
-    L.tot_acc += n ? nblk_acc(n) : 0u;
-    L.tot_cov += n ? nblk(n) : 0u;
+    L.tot_acc += (n && !plane) ? nblk_acc(n) : 0u;
+    L.tot_cov += (n && !plane) ? nblk(n) : 0u;
+  }
+  for (uint32_t i = 0; i < np; i++) {  // (behind every pair's segments: a table without a plane pair keeps its layout)
+    if (!pl[i].knn) continue;
+    const size_t nn = pairs[i].scan->n ? pairs[i].scan->n : 1;
+    L.seg_c[i] = L.pair_bytes;
+    L.pair_bytes += (nn * sizeof(float4) + 255) / 256 * 256;
+    L.seg_n[i] = L.pair_bytes;
+    L.pair_bytes += (nn * sizeof(float4) + 255) / 256 * 256;
   }
   tab->blk_match[np] = L.tot_match;
   tab->blk_acc[np] = L.tot_acc;
   tab->blk_cov[np] = L.tot_cov;
   if (L.knn_key) kt->blk[np] = L.tot_match_k;
+  if (L.plane_key) {
+    pt->blk_match[np] = L.tot_match_pl;
+    pt->blk_acc[np] = pt->blk_cov[np] = L.tot_acc_pl;
+    MH_TRY(ctx->partials_b.reserve((size_t)kGenN * (L.tot_acc_pl ? L.tot_acc_pl : 1) * sizeof(double)));
+  }
   MH_TRY(ctx->layers_pairs.reserve(L.pair_bytes));
   const uint32_t cols = L.tot_acc > L.tot_cov ? L.tot_acc : L.tot_cov;
   MH_TRY(ctx->partials.reserve((size_t)kGenN * (cols ? cols : 1) * sizeof(double)));
@@ -206,6 +247,21 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     d.run_from = gates[i].run_from_iteration;
     d.run_up_to = gates[i].run_up_to_iteration;
     d.kpp = kpp[i] > 1u ? kpp[i] : 0u;  // (k = 1: the word the table always had there)
+    if (pl[i].knn) {  // (pair_q: what the next iteration's bound needs; distance threshold: the pair's schedule)
+      mh_pt2pl_knn_params kp{};
+      kp.plane_eigen_threshold = pl[i].plane_eigen_threshold;
+      kp.search_radius = pl[i].search_radius;
+      kp.knn = pl[i].knn;
+      kp.minimum_plane_points = pl[i].minimum_plane_points;
+      const PlKnnArg a = pl_knn_arg(&kp);
+      PlaneDesc& q = pt->d[i];
+      q.pl_c = reinterpret_cast<float4*>(pb + L.seg_c[i]);
+      q.pl_n = reinterpret_cast<float4*>(pb + L.seg_n[i]);
+      q.plane_eigen_threshold = a.plane_eigen_threshold;
+      q.radius2 = a.radius2;
+      q.knn = a.knn;
+      q.min_pts = a.min_pts;
+    }
   }
   if (L.unique_mask) MH_TRY(claims_begin(reinterpret_cast<ClaimTable*>(ctx->h_layers.as<char>() + L.claim_off)));
   MH_HIP(hipMemcpyAsync(ctx->layers_tab.p, ctx->h_layers.p, up_bytes, hipMemcpyHostToDevice, s));
@@ -223,17 +279,22 @@ void LayersJob::finish(uint32_t polls, uint32_t enqueued) {
   if (p->poll_every == 0) ctx->layers_predicted = live_iterations(ctx->h_state);
   // the iteration whose match produced the final pairings: the one that terminated the loop, or the last of max_iterations
   k_last = ctx->h_state->n_iterations < p->max_iterations ? ctx->h_state->n_iterations : p->max_iterations - 1;
-  read_result(ctx->h_state, p, res, potential_in(k_last), 0u, polls, enqueued);
+  read_result(ctx->h_state, p, res, potential_in(k_last), L.plane_key ? ctx->h_state->n_pairs_pl : 0u, polls, enqueued);
 }
 
 // every pair's final pairings compacted out of its segment (into final_pairs[i] when given) and counted
-mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
-  if (!(final_pairs || final_pair_counts) || !res->n_final_pairs) return MH_OK;
+mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem,
+                                 const mh_pairs_pl_out* final_plane_pairs) {
+  if (!(final_pairs || final_pair_counts || final_plane_pairs) || !res->n_final_pairs) return MH_OK;
   const mh_pairs_out none{};
+  const mh_pairs_pl_out none_pl{};
   uint64_t sum = 0;
   for (uint32_t i = 0; i < np; i++) {
     uint64_t c = 0;
-    if (pairs[i].scan->n && active_in(i, k_last)) {  // (a pair that is gated off there holds "not paired" throughout)
+    if (pl[i].knn && pairs[i].scan->n && active_in(i, k_last)) {
+      MH_TRY(compact_pl_pairs_of(ctx, ptab->d[i].pl_c, ptab->d[i].pl_n, pairs[i].scan->n,
+                                 final_plane_pairs ? &final_plane_pairs[i] : &none_pl, final_plane_pairs ? pairs_mem : MH_MEM_DEVICE, &c));
+    } else if (pairs[i].scan->n && active_in(i, k_last)) {  // (a pair that is gated off there holds "not paired" throughout)
       MH_TRY(compact_pairs_of(ctx, tab->d[i].pair_gidx, tab->d[i].pair_q, entries(i), final_pairs ? &final_pairs[i] : &none,
                               final_pairs ? pairs_mem : MH_MEM_DEVICE, &c));
       // the compaction numbers the ENTRIES: entry e belongs to local point e / k (mh_nn_search_k)
@@ -259,9 +320,10 @@ mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* fina
 mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pairs, const mh_icp_params* p, const double T0[12],
                        const mh_prior* prior, mh_icp_result* res, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
                        uint64_t* final_pair_counts, int32_t pairs_mem, const mh_layer_pair_opts* opts = nullptr,
-                       const mh_layer_pair_gates* gates = nullptr, const mh_layer_pair_knn* knn = nullptr) {
+                       const mh_layer_pair_gates* gates = nullptr, const mh_layer_pair_knn* knn = nullptr,
+                       const mh_layer_pair_plane* planes = nullptr, const mh_pairs_pl_out* final_plane_pairs = nullptr) {
   LayersJob job;
-  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts, opts, gates, knn));
+  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts, opts, gates, knn, planes));
   if (job.trivial) return MH_OK;
   mh_ctx* const ctx = job.ctx;
   const LayersLayout& L = job.L;
@@ -269,6 +331,10 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
   const LayerTable* const dtab = ctx->layers_tab.as<LayerTable>();
   const ClaimTable* const dclaim = reinterpret_cast<const ClaimTable*>(ctx->layers_tab.as<char>() + L.claim_off);
   const KnnTable* const dknn = reinterpret_cast<const KnnTable*>(ctx->layers_tab.as<char>() + L.knn_off);
+  const PlaneTable* const dpl = reinterpret_cast<const PlaneTable*>(ctx->layers_tab.as<char>() + L.plane_off);
+  // (the plane pairs' rows: the second partials block of k_solve / k_cov_finalize; without such a pair it is absent as before)
+  double* const partb = L.tot_acc_pl ? ctx->partials_b.as<double>() : nullptr;
+  const uint32_t nB = L.tot_acc_pl;
   // (a table with a pair of k > 1: the entry points that take the local point of an entry from its k)
   const auto accum = L.knn_key ? k_accum_layers_k : k_accum_layers;
   const auto cov_accum = L.knn_key ? k_cov_accum_layers_k : k_cov_accum_layers;
@@ -284,24 +350,29 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
         if (L.tot_match) hipLaunchKernelGGL(k_match_layers, dim3(L.tot_match), dim3(kFlatThreads), 0, s, ctx->d_state, dtab);
         if (L.tot_match_k)
           hipLaunchKernelGGL(k_match_layers_k, dim3(L.tot_match_k), dim3(kFlatThreads), 0, s, ctx->d_state, dtab, dknn);
+        if (L.tot_match_pl)
+          hipLaunchKernelGGL(k_match_layers_pl, dim3(L.tot_match_pl), dim3(kFlatThreads), 0, s, ctx->d_state, dtab, dpl);
         if (L.tot_claim) {
           hipLaunchKernelGGL(k_claim_layers, dim3(L.tot_claim), dim3(kBlock), 0, s, ctx->d_state, dtab, dclaim);
           hipLaunchKernelGGL(k_resolve_layers, dim3(L.tot_claim), dim3(kBlock), 0, s, ctx->d_state, dtab, dclaim);
         }
-        hipLaunchKernelGGL(accum, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 1u, part, L.tot_acc);
+        if (L.tot_acc) hipLaunchKernelGGL(accum, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 1u, part, L.tot_acc);
+        if (nB) hipLaunchKernelGGL(k_accum_layers_pl, dim3(nB), dim3(kBlock), 0, s, ctx->d_state, dtab, dpl, 1u, partb, nB);
         hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, dsk, (const double*)part, L.tot_acc,
-                           L.tot_acc, (const double*)nullptr, 0u, 0u, 1u);
+                           L.tot_acc, (const double*)partb, nB, nB, 1u);
         for (uint32_t in = 1; in < inner; in++) {
-          hipLaunchKernelGGL(accum, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 0u, part, L.tot_acc);
+          if (L.tot_acc) hipLaunchKernelGGL(accum, dim3(L.tot_acc), dim3(kBlock), 0, s, ctx->d_state, dtab, 0u, part, L.tot_acc);
+          if (nB) hipLaunchKernelGGL(k_accum_layers_pl, dim3(nB), dim3(kBlock), 0, s, ctx->d_state, dtab, dpl, 0u, partb, nB);
           hipLaunchKernelGGL(k_solve, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, dsk, (const double*)part, L.tot_acc,
-                             L.tot_acc, (const double*)nullptr, 0u, 0u, 0u);
+                             L.tot_acc, (const double*)partb, nB, nB, 0u);
         }
       }
       if (p->compute_covariance) {  // no-ops unless the loop has terminated
         hipLaunchKernelGGL(k_cov_prepare, dim3(1), dim3(64), 0, s, ctx->d_state, dsk, 0u);
-        hipLaunchKernelGGL(cov_accum, dim3(L.tot_cov), dim3(kBlock), 0, s, ctx->d_state, dtab, part, L.tot_cov);
+        if (L.tot_cov) hipLaunchKernelGGL(cov_accum, dim3(L.tot_cov), dim3(kBlock), 0, s, ctx->d_state, dtab, part, L.tot_cov);
+        if (nB) hipLaunchKernelGGL(k_cov_accum_layers_pl, dim3(nB), dim3(kBlock), 0, s, ctx->d_state, dtab, dpl, partb, nB);
         hipLaunchKernelGGL(k_cov_finalize, dim3(1), dim3(kSolveThreads), 0, s, ctx->d_state, 0u, (const double*)part, L.tot_cov,
-                           L.tot_cov, (const double*)nullptr, 0u, 0u);
+                           L.tot_cov, (const double*)partb, nB, nB);
       }
       (void)hipMemcpyAsync(ctx->h_state, ctx->d_state, sizeof(IcpDeviceState), hipMemcpyDeviceToHost, s);
       return MH_OK;
@@ -311,7 +382,7 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
     const unsigned long long kv[] = {kLayersGraphTag | np, m, inner, p->compute_covariance, L.tot_match, L.tot_acc, L.tot_cov,
                                      (unsigned long long)dtab, (unsigned long long)part, (unsigned long long)ctx->d_state,
                                      (unsigned long long)ctx->d_params, (unsigned long long)ctx->h_state};
-    static_assert(sizeof(kv) + 6 * sizeof(key[0]) <= sizeof(key), "graph key too small");
+    static_assert(sizeof(kv) + 10 * sizeof(key[0]) <= sizeof(key), "graph key too small");
     memcpy(key, kv, sizeof(kv));
     if (L.tot_claim) {  // (without a unique pair the key is what it always was)
       unsigned long long* const kc = key + sizeof(kv) / sizeof(kv[0]);
@@ -325,6 +396,13 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
       kk[1] = L.tot_match_k;
       kk[2] = (unsigned long long)dknn;
     }
+    if (L.plane_key) {  // (and without a plane pair)
+      unsigned long long* const kq = key + sizeof(kv) / sizeof(kv[0]) + 6;
+      kq[0] = L.plane_key;
+      kq[1] = ((unsigned long long)L.tot_match_pl << 32) | L.tot_acc_pl;
+      kq[2] = (unsigned long long)dpl;
+      kq[3] = (unsigned long long)partb;
+    }
     MH_TRY(enqueue_cached(ctx, sw.no_graph, key, enqueue_kernels));
     enqueued += m;
     MH_HIP(hipEventRecord(ctx->ev_poll, s));
@@ -336,7 +414,7 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
   }
   job.finish(polls, enqueued);
   if (trace) MH_TRY(download_trace(ctx, ctx->h_state, p, trace));
-  return job.count_pairs(final_pairs, final_pair_counts, pairs_mem);
+  return job.count_pairs(final_pairs, final_pair_counts, pairs_mem, final_plane_pairs);
 }
 
 // the argument rules of mh_icp_align_layers (one job of mh_icp_align_layers_batch obeys the same): nothing here touches the device
@@ -365,5 +443,26 @@ mh_status check_layers_supported(size_t n_pairs, const mh_layer_pair* pairs, con
       for (size_t j = i + 1; j < n_pairs; j++)
         if (pairs[i].scan == pairs[j].scan)
           return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: MH_MATCHED_POINTS_SKIP with a scan shared by two pairs");
+  return MH_OK;
+}
+
+// the argument rules of mh_icp_align_layers_planes' plane pairs (planes[i].knn != 0): nothing here touches the device
+mh_status check_layers_planes(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts, const mh_layer_pair_knn* knn,
+                              const mh_layer_pair_plane* planes, const mh_icp_params* params) {
+  for (size_t i = 0; planes && i < n_pairs; i++) {
+    if (!planes[i].knn) continue;
+    MH_REQUIRE(!(opts && opts[i].unique_global), "a plane pair cannot be unique_global");
+    MH_REQUIRE(!(knn && knn[i].pairings_per_point > 1u), "a plane pair has one pairing per point");
+    MH_REQUIRE(pairs[i].threshold_angular_deg == 0.0, "a plane pair has no angular threshold");
+    mh_pt2pl_knn_params kp{};
+    kp.plane_eigen_threshold = planes[i].plane_eigen_threshold;
+    kp.search_radius = planes[i].search_radius;
+    kp.knn = planes[i].knn;
+    kp.minimum_plane_points = planes[i].minimum_plane_points;
+    for (uint32_t k = 0; k < (params->max_iterations ? params->max_iterations : 1u); k++) {
+      kp.distance_threshold = params->max_iterations ? pairs[i].threshold[k] : 0.0;
+      MH_TRY(check_pl_knn_params(&kp));
+    }
+  }
   return MH_OK;
 }

@@ -152,13 +152,13 @@ __device__ __forceinline__ void k_cov_accum_plbuf_body(const IcpDeviceState* __r
                                                        const float* __restrict__ lx, const float* __restrict__ ly,
                                                        const float* __restrict__ lz, uint32_t n,
                                                        const float4* __restrict__ pl_c, const float4* __restrict__ pl_n,
-                                                       double* __restrict__ partials, uint32_t pstride) {
+                                                       double* __restrict__ partials, uint32_t pstride, uint32_t block_x) {
   __shared__ double sD[72];
   __shared__ BlockSum<kCovN> lds;
   if (!st->done || st->cov_done) return;
   if (threadIdx.x < 72) sD[threadIdx.x] = st->covD[threadIdx.x];
   __syncthreads();
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const uint32_t i = block_x * kBlock + threadIdx.x;
   double v[kCovN];
 #pragma unroll
   for (int j = 0; j < kCovN; j++) v[j] = 0.0;
@@ -166,14 +166,14 @@ __device__ __forceinline__ void k_cov_accum_plbuf_body(const IcpDeviceState* __r
     const float4 nn = pl_n[i];
     cov_rows_plane(sD, lx[i], ly[i], lz[i], (double)nn.x, (double)nn.y, (double)nn.z, v);
   }
-  block_sum_rows<kCovN>(v, lds, partials, pstride, blockIdx.x);
+  block_sum_rows<kCovN>(v, lds, partials, pstride, block_x);
 }
 __global__ __launch_bounds__(kBlock) void k_cov_accum_plbuf(const IcpDeviceState* __restrict__ st,
                                                             const float* __restrict__ lx, const float* __restrict__ ly,
                                                             const float* __restrict__ lz, uint32_t n,
                                                             const float4* __restrict__ pl_c, const float4* __restrict__ pl_n,
                                                             double* __restrict__ partials, uint32_t pstride) {
-  k_cov_accum_plbuf_body(st, lx, ly, lz, n, pl_c, pl_n, partials, pstride);
+  k_cov_accum_plbuf_body(st, lx, ly, lz, n, pl_c, pl_n, partials, pstride, blockIdx.x);
 }
 
 __device__ __forceinline__ void k_cov_finalize_body(IcpDeviceState* __restrict__ st, uint32_t force,

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_cov_finalize_b(const BatchJob
 __global__ __launch_bounds__(kBlock) void k_cov_accum_plbuf_b(const BatchJob* __restrict__ jobs) {
   const BatchJob& j = jobs[blockIdx.y];
   if (blockIdx.x >= j.nb || !j.partb) return;
-  k_cov_accum_plbuf_body(j.st, j.lx, j.ly, j.lz, j.n, j.pl_c, j.pl_n, j.partb, j.nb);
+  k_cov_accum_plbuf_body(j.st, j.lx, j.ly, j.lz, j.n, j.pl_c, j.pl_n, j.partb, j.nb, blockIdx.x);
 }
 template <bool PL, bool FUSED>
 __global__ __launch_bounds__(kBlock) void k_match16(const IcpDeviceState* __restrict__ st, const MatchK* __restrict__ kp,

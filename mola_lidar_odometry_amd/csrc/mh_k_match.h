@@ -84,13 +84,80 @@ __global__ __launch_bounds__(kBlock) void k_match_kbest(PoseArg Targ, float thr2
 // Matcher_Point2Plane on a plain point map (pipelines/rgbd.yaml:143-151; SURVEY 8a row a13 "otherwise KNN + PCA" [U]): one lane
 // per point -- the knn nearest records of the 27-voxel block (nn_search_kbest), the prefix of them inside the search radius,
 // mean + covariance in fp64, cyclic Jacobi (the operation sequence of k_ndt_stats and of the oracle), plane test e0 <= thr * e2,
-// distance test in fp64.  pl_c = {centroid, 1 | 0}, pl_n = {unit normal (largest component positive), 0}: what the
+// distance test in fp64 (pl_knn_plane).  pl_c = {centroid, 1 | 0}, pl_n = {unit normal (largest component positive), 0}: what the
 // point-to-plane rows and compact_pl_pairs read.  Not on a target pipeline's path: exactness first.
 struct PlKnnArg {
   double distance_threshold, plane_eigen_threshold;
   float radius2;
   uint32_t knn, min_pts;
 };
+// The plane of `cnt` >= 3 neighbour records (rec(r), r < cnt, ascending distance) and the verdict for the point (px, py, pz): the
+// ONE fp64 operation sequence of the KNN + PCA matcher -- k_match_pl_knn and the multi-layer loop's k_match_layers_pl
+// (mh_k_match_planes.h) both call it, so the two cannot drift.  rc / rn are written only when the pairing is accepted.
+template <class REC>
+__device__ __forceinline__ void pl_knn_plane(const PlKnnArg& a, uint32_t cnt, const REC& rec, float px, float py, float pz, float4& rc,
+                                             float4& rn) {
+  double mu[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int r = 0; r < kMaxPlaneKnn; r++)
+    if ((uint32_t)r < cnt) { const f32x4 nb = rec(r); mu[0] += (double)nb.x; mu[1] += (double)nb.y; mu[2] += (double)nb.z; }
+  mu[0] /= (double)cnt; mu[1] /= (double)cnt; mu[2] /= (double)cnt;
+  double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
+#pragma unroll
+  for (int r = 0; r < kMaxPlaneKnn; r++)
+    if ((uint32_t)r < cnt) {
+      const f32x4 nb = rec(r);
+      const double d0 = (double)nb.x - mu[0], d1 = (double)nb.y - mu[1], d2 = (double)nb.z - mu[2];
+      c00 += d0 * d0; c01 += d0 * d1; c02 += d0 * d2; c11 += d1 * d1; c12 += d1 * d2; c22 += d2 * d2;
+    }
+  const double inv = (double)(cnt - 1);
+  double A[3][3] = {{c00 / inv, c01 / inv, c02 / inv}, {c01 / inv, c11 / inv, c12 / inv}, {c02 / inv, c12 / inv, c22 / inv}};
+  double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  for (int sweep = 0; sweep < 12; sweep++) {
+#pragma unroll
+    for (int pq = 0; pq < 3; pq++) {
+      const int p = (pq == 2) ? 1 : 0, q = (pq == 0) ? 1 : 2, r = 3 - p - q;
+      const double apq = A[p][q];
+      if (apq != 0.0) {
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+        const double app = A[p][p] - t * apq, aqq = A[q][q] + t * apq;
+        const double arp = c * A[r][p] - sn * A[r][q], arq = sn * A[r][p] + c * A[r][q];
+        A[p][p] = app; A[q][q] = aqq; A[p][q] = 0.0; A[q][p] = 0.0;
+        A[r][p] = arp; A[p][r] = arp; A[r][q] = arq; A[q][r] = arq;
+#pragma unroll
+        for (int v = 0; v < 3; v++) {
+          const double vip = c * V[v][p] - sn * V[v][q], viq = sn * V[v][p] + c * V[v][q];
+          V[v][p] = vip; V[v][q] = viq;
+        }
+      }
+    }
+  }
+  // smallest / largest eigenvalue, the eigenvector of the smallest (first minimum: the oracle's stable sort)
+  const double w0 = A[0][0], w1 = A[1][1], w2 = A[2][2];
+  int imin = 0;
+  double wmin = w0, wmax = w0;
+  if (w1 < wmin) { wmin = w1; imin = 1; }
+  if (w2 < wmin) { wmin = w2; imin = 2; }
+  if (w1 > wmax) wmax = w1;
+  if (w2 > wmax) wmax = w2;
+  if (wmax > 0.0 && !(wmin > a.plane_eigen_threshold * wmax)) {
+    double nv[3] = {imin == 0 ? V[0][0] : (imin == 1 ? V[0][1] : V[0][2]), imin == 0 ? V[1][0] : (imin == 1 ? V[1][1] : V[1][2]),
+                    imin == 0 ? V[2][0] : (imin == 1 ? V[2][1] : V[2][2])};
+    const double len = sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+    int big = 0;
+    if (fabs(nv[1]) > fabs(nv[big])) big = 1;
+    if (fabs(nv[2]) > fabs(nv[big])) big = 2;
+    const double sgn = ((big == 0 ? nv[0] : (big == 1 ? nv[1] : nv[2])) < 0.0 ? -1.0 : 1.0) / len;
+    nv[0] *= sgn; nv[1] *= sgn; nv[2] *= sgn;
+    const double dist = fabs((nv[0] * ((double)px - mu[0]) + nv[1] * ((double)py - mu[1])) + nv[2] * ((double)pz - mu[2]));
+    if (!(dist > a.distance_threshold)) {
+      rc = make_float4((float)mu[0], (float)mu[1], (float)mu[2], 1.f);
+      rn = make_float4((float)nv[0], (float)nv[1], (float)nv[2], 0.f);
+    }
+  }
+}
 __global__ __launch_bounds__(kBlock) void k_match_pl_knn(PoseArg Targ, PlKnnArg a, const float* __restrict__ lx, const float* __restrict__ ly,
                                                          const float* __restrict__ lz, uint32_t n, MapView map, float4* __restrict__ pl_c,
                                                          float4* __restrict__ pl_n) {
@@ -116,65 +183,7 @@ __global__ __launch_bounds__(kBlock) void k_match_pl_knn(PoseArg Targ, PlKnnArg 
     f32x4 nb[kMaxPlaneKnn];
 #pragma unroll
     for (int r = 0; r < kMaxPlaneKnn; r++) nb[r] = pts4[(uint32_t)r < cnt ? (uint32_t)best[r] : (uint32_t)best[0]];
-    double mu[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int r = 0; r < kMaxPlaneKnn; r++)
-      if ((uint32_t)r < cnt) { mu[0] += (double)nb[r].x; mu[1] += (double)nb[r].y; mu[2] += (double)nb[r].z; }
-    mu[0] /= (double)cnt; mu[1] /= (double)cnt; mu[2] /= (double)cnt;
-    double c00 = 0, c01 = 0, c02 = 0, c11 = 0, c12 = 0, c22 = 0;
-#pragma unroll
-    for (int r = 0; r < kMaxPlaneKnn; r++)
-      if ((uint32_t)r < cnt) {
-        const double d0 = (double)nb[r].x - mu[0], d1 = (double)nb[r].y - mu[1], d2 = (double)nb[r].z - mu[2];
-        c00 += d0 * d0; c01 += d0 * d1; c02 += d0 * d2; c11 += d1 * d1; c12 += d1 * d2; c22 += d2 * d2;
-      }
-    const double inv = (double)(cnt - 1);
-    double A[3][3] = {{c00 / inv, c01 / inv, c02 / inv}, {c01 / inv, c11 / inv, c12 / inv}, {c02 / inv, c12 / inv, c22 / inv}};
-    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 12; sweep++) {
-#pragma unroll
-      for (int pq = 0; pq < 3; pq++) {
-        const int p = (pq == 2) ? 1 : 0, q = (pq == 0) ? 1 : 2, r = 3 - p - q;
-        const double apq = A[p][q];
-        if (apq != 0.0) {
-          const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-          const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-          const double app = A[p][p] - t * apq, aqq = A[q][q] + t * apq;
-          const double arp = c * A[r][p] - sn * A[r][q], arq = sn * A[r][p] + c * A[r][q];
-          A[p][p] = app; A[q][q] = aqq; A[p][q] = 0.0; A[q][p] = 0.0;
-          A[r][p] = arp; A[p][r] = arp; A[r][q] = arq; A[q][r] = arq;
-#pragma unroll
-          for (int v = 0; v < 3; v++) {
-            const double vip = c * V[v][p] - sn * V[v][q], viq = sn * V[v][p] + c * V[v][q];
-            V[v][p] = vip; V[v][q] = viq;
-          }
-        }
-      }
-    }
-    // smallest / largest eigenvalue, the eigenvector of the smallest (first minimum: the oracle's stable sort)
-    const double w0 = A[0][0], w1 = A[1][1], w2 = A[2][2];
-    int imin = 0;
-    double wmin = w0, wmax = w0;
-    if (w1 < wmin) { wmin = w1; imin = 1; }
-    if (w2 < wmin) { wmin = w2; imin = 2; }
-    if (w1 > wmax) wmax = w1;
-    if (w2 > wmax) wmax = w2;
-    if (wmax > 0.0 && !(wmin > a.plane_eigen_threshold * wmax)) {
-      double nv[3] = {imin == 0 ? V[0][0] : (imin == 1 ? V[0][1] : V[0][2]), imin == 0 ? V[1][0] : (imin == 1 ? V[1][1] : V[1][2]),
-                      imin == 0 ? V[2][0] : (imin == 1 ? V[2][1] : V[2][2])};
-      const double len = sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
-      int big = 0;
-      if (fabs(nv[1]) > fabs(nv[big])) big = 1;
-      if (fabs(nv[2]) > fabs(nv[big])) big = 2;
-      const double sgn = ((big == 0 ? nv[0] : (big == 1 ? nv[1] : nv[2])) < 0.0 ? -1.0 : 1.0) / len;
-      nv[0] *= sgn; nv[1] *= sgn; nv[2] *= sgn;
-      const double dist = fabs((nv[0] * ((double)px - mu[0]) + nv[1] * ((double)py - mu[1])) + nv[2] * ((double)pz - mu[2]));
-      if (!(dist > a.distance_threshold)) {
-        rc = make_float4((float)mu[0], (float)mu[1], (float)mu[2], 1.f);
-        rn = make_float4((float)nv[0], (float)nv[1], (float)nv[2], 0.f);
-      }
-    }
+    pl_knn_plane(a, cnt, [&](int r) { return nb[r]; }, px, py, pz, rc, rn);
   }
   pl_c[i] = rc;
   pl_n[i] = rn;

@@ -31,16 +31,22 @@
 
 namespace mh {
 
-struct FlatWaveK : FlatWave {
-  unsigned long long RESK[kMaxKnn * 64];  // slot r of point p: RESK[r * 64 + p] (the wave's points side by side: no bank conflicts)
+// KS result slots per point on top of a plan / scan wave BASE (the k-best pairs: kMaxKnn slots on FlatWave; the plane search of
+// mh_k_match_planes.h widens both through these parameters, so the kernels here keep their code objects and their LDS footprint)
+template <int KS, class BASE = FlatWave>
+struct FlatWaveKT : BASE {
+  unsigned long long RESK[KS * 64];  // slot r of point p: RESK[r * 64 + p] (the wave's points side by side: no bank conflicts)
 };
+typedef FlatWaveKT<kMaxKnn> FlatWaveK;
 
-struct FlatInsertK {
+template <int KS>
+struct FlatInsertKT {
   uint32_t k;
-  __device__ __forceinline__ void operator()(FlatWaveK& sh, uint32_t p, unsigned long long key) const {
+  template <class FW>
+  __device__ __forceinline__ void operator()(FW& sh, uint32_t p, unsigned long long key) const {
     // (a fixed trip count under predicates: phase B's loop over its records in flight stays unrolled, its arrays in registers)
 #pragma unroll
-    for (int r = 0; r < kMaxKnn; r++) {
+    for (int r = 0; r < KS; r++) {
       if ((uint32_t)r < k && key != ~0ull) {  // (~0: the slot's initial value has moved on -- nothing left to place)
         const unsigned long long old =
             __hip_atomic_fetch_min(&sh.RESK[(uint32_t)r * 64u + p], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -49,6 +55,7 @@ struct FlatInsertK {
     }
   }
 };
+typedef FlatInsertKT<kMaxKnn> FlatInsertK;
 
 // nn_search_kbest (mh_nn_device.h) with a starting bound b0 (+inf: none, and then the same search): only records with d2 <= b0
 // are kept, voxels are pruned against b0 until k records are found and against the k-th smallest from then on.  best[] ascending

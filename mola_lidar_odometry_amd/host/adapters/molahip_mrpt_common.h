@@ -193,6 +193,13 @@ class DeviceSession
         return mir.map;
     }
 
+    /** Does the host map carry NDT statistics (Matcher_Point2Plane then means the per-voxel planes, not KNN + PCA)? */
+    bool carries_ndt(const mrpt::maps::CMetricMap& g) const
+    {
+        HostMapView v;
+        return view_of(g, v) && v.params.ndt_max_eigen_ratio > 0;
+    }
+
     /** The local layer on the device (created on first use, refilled every call: the layer changes every scan).  `keep`: other
      *  layers whose scans the caller still holds (a multi-layer alignment uploads several) -- never evicted here. */
     mh_scan* upload(const mrpt::maps::CPointsMap& local, const std::vector<const mrpt::maps::CPointsMap*>* keep = nullptr)

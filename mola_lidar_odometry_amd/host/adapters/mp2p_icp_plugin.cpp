@@ -35,7 +35,9 @@
 // order (matchers in list order, then weight_pt2pt_layers' std::map order: global name, then local name).  A local layer named by
 // two entries is paired again for each unless allowMatchAlreadyMatchedPoints is false and MOLA_HIP_MATCHED_POINTS=skip (then the
 // upstream loop runs).  Gated blocks (extras/lidar3d-near-far.yaml) go to the upstream loop unless MOLA_HIP_FUSE_GATES=1: then to
-// mh_icp_align_layers_gated, a single gated pair included.
+// mh_icp_align_layers_gated, a single gated pair included.  A Matcher_Point2Plane among such point matchers, on point layers WITHOUT
+// plane statistics (pipelines/rgbd.yaml:133-151: KNN + PCA), goes to the upstream loop unless MOLA_HIP_FUSE_PLANES=1: then to
+// mh_icp_align_layers_planes, its pairings into Results::finalPairings.paired_pt2pl.
 // Global layers read: mola::HashedVoxelPointCloud (yaml:230), mola::NDT (ndt yaml:236) -- through their point / voxel
 // visitors, they are NOT mrpt::maps::CPointsMap --, mola::HashedVoxelPointCloudHIP (device owned, no mirror), and any
 // CPointsMap (pipelines/extras/localmap_definition_pointmap.ini).
@@ -125,17 +127,20 @@ struct LayerShape
 {
     struct Entry
     {
-        const Matcher_Points_DistanceThreshold* m = nullptr;
+        const Matcher_Points_DistanceThreshold* m = nullptr;  // a point pair's matcher ...
+        const Matcher_Point2Plane*              pl = nullptr; // ... or a plane pair's (KNN + PCA on point layers)
         size_t      matcher = 0;  // index into LayerShape::matchers (its threshold schedule)
         std::string globalLayer, localLayer;
         double      weight = 1.0;
     };
-    std::vector<const Matcher_Points_DistanceThreshold*> matchers;
+    std::vector<const Matcher_Points_DistanceThreshold*> matchers;  // per matcher: the point matcher, or null and ...
+    std::vector<const Matcher_Point2Plane*> plane_matchers;         // ... the plane matcher
     const Solver_GaussNewton* gn = nullptr;
     std::vector<Entry> entries;
     bool any_unique = false;  // some matcher has allowMatchAlreadyMatchedGlobalPoints false (U13)
     bool any_gate = false;    // some matcher has runFromIteration / runUpToIteration (MOLA_HIP_FUSE_GATES=1)
     bool any_knn = false;     // some matcher has pairingsPerPoint > 1 (MOLA_HIP_FUSE_KBEST=1)
+    bool any_plane = false;   // some matcher is a Matcher_Point2Plane (MOLA_HIP_FUSE_PLANES=1)
 };
 
 template <class M> bool single_unit_layer(const M& m, std::string& g, std::string& l, double* weight_out = nullptr)
@@ -387,6 +392,33 @@ class ICP_HIP : public ICP
         bool skip_paired = false;  // some matcher leaves points an earlier one paired out (U12, MOLA_HIP_MATCHED_POINTS=skip)
         for (const auto& mp : matchers())
         {
+            if (const auto* pl = dynamic_cast<const Matcher_Point2Plane*>(mp.get()))
+            {   // rgbd.yaml:143-151 on point layers: mh_icp_align_layers_planes, when asked for (an NDT layer: align_layers decides)
+                if (!molahip_host::fuse_planes(false, molahip_host::plugin_switches())) return false;
+                if (!pl->enabled || pl->knn < 3 || pl->knn > MH_MAX_PLANE_KNN || pl->maxLocalPointsPerLayer_ != 0) return false;
+                if (pl->runFromIteration != 0 || pl->runUpToIteration != 0)
+                {
+                    if (!molahip_host::fuse_gates(false, molahip_host::plugin_switches())) return false;
+                    if (!pl->weight_pt2pt_layers.empty()) ls.any_gate = true;
+                }
+                if (!pl->allowMatchAlreadyMatchedPoints_ && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP)
+                    skip_paired = true;
+                ls.matchers.push_back(nullptr);
+                ls.plane_matchers.push_back(pl);
+                for (const auto& [gname, locals] : pl->weight_pt2pt_layers)
+                    for (const auto& [lname, w] : locals)
+                    {
+                        LayerShape::Entry e;
+                        e.pl = pl;
+                        e.matcher = ls.matchers.size() - 1;
+                        e.globalLayer = gname;
+                        e.localLayer = lname;
+                        e.weight = w;
+                        ls.entries.push_back(e);
+                        ls.any_plane = true;
+                    }
+                continue;
+            }
             const auto* m = dynamic_cast<const Matcher_Points_DistanceThreshold*>(mp.get());
             if (!m || !m->enabled) return false;
             if (m->pairingsPerPoint != 1)  // lidar2d.yaml:156, rgbd.yaml:138: mh_icp_align_layers_kbest, when asked for
@@ -405,6 +437,7 @@ class ICP_HIP : public ICP
             if (!m->allowMatchAlreadyMatchedPoints_ && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP)
                 skip_paired = true;
             ls.matchers.push_back(m);
+            ls.plane_matchers.push_back(nullptr);
             for (const auto& [gname, locals] : m->weight_pt2pt_layers)  // [U] std::map: global name, then local name
                 for (const auto& [lname, w] : locals)
                 {
@@ -417,7 +450,7 @@ class ICP_HIP : public ICP
                     ls.entries.push_back(e);
                 }
         }
-        if (ls.entries.size() < (ls.any_unique || ls.any_gate || ls.any_knn ? 1u : 2u) || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
+        if (ls.entries.size() < (ls.any_unique || ls.any_gate || ls.any_knn || ls.any_plane ? 1u : 2u) || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
         for (size_t i = 0; i < ls.entries.size(); i++)
             for (size_t j = i + 1; j < ls.entries.size(); j++)
                 if (skip_paired && ls.entries[i].localLayer == ls.entries[j].localLayer) return false;
@@ -440,18 +473,35 @@ class ICP_HIP : public ICP
         std::vector<mh_layer_pair_opts> opts(np);
         std::vector<mh_layer_pair_gates> gates(np);
         std::vector<mh_layer_pair_knn> knn(np);
+        std::vector<mh_layer_pair_plane> planes(np);
         for (size_t i = 0; i < np; i++)
         {
             const auto& e = ls.entries[i];
-            knn[i].pairings_per_point = static_cast<uint32_t>(e.m->pairingsPerPoint);
-            opts[i].unique_global = e.m->allowMatchAlreadyMatchedGlobalPoints ? 0u : 1u;
-            gates[i].run_from_iteration = e.m->runFromIteration;
-            gates[i].run_up_to_iteration = e.m->runUpToIteration;
+            if (e.pl)
+            {   // a plane pairing names no map point (nothing to claim); on a layer with NDT statistics the matcher means the
+                // per-voxel planes, which this loop does not run
+                if (dev_->carries_ndt(*pcGlobal.layers.at(e.globalLayer)))
+                    return upstream_align(pcLocal, pcGlobal, guess, p, result, prior, outputDebugInfo);
+                knn[i].pairings_per_point = 1;
+                gates[i].run_from_iteration = e.pl->runFromIteration;
+                gates[i].run_up_to_iteration = e.pl->runUpToIteration;
+                planes[i].knn = e.pl->knn;
+                planes[i].minimum_plane_points = e.pl->minimumPlanePoints;
+                planes[i].plane_eigen_threshold = e.pl->planeEigenThreshold;
+                planes[i].search_radius = e.pl->searchRadius;
+            }
+            else
+            {
+                knn[i].pairings_per_point = static_cast<uint32_t>(e.m->pairingsPerPoint);
+                opts[i].unique_global = e.m->allowMatchAlreadyMatchedGlobalPoints ? 0u : 1u;
+                gates[i].run_from_iteration = e.m->runFromIteration;
+                gates[i].run_up_to_iteration = e.m->runUpToIteration;
+            }
             mh_map* m = dev_->device_map_of(*pcGlobal.layers.at(e.globalLayer), false);  // every global layer mirrored
             locals[i] = dynamic_cast<const mrpt::maps::CPointsMap*>(pcLocal.layers.at(e.localLayer).get());
             if (!m || !locals[i]) return upstream_align(pcLocal, pcGlobal, guess, p, result, prior, outputDebugInfo);
             pairs[i].map = m;
-            pairs[i].threshold_angular_deg = e.m->thresholdAngularDeg;
+            pairs[i].threshold_angular_deg = e.pl ? 0.0 : e.m->thresholdAngularDeg;
             pairs[i].weight = e.weight;  // Pairings::point_weights [U]: the entry's own weight
         }
         for (size_t i = 0; i < np; i++)  // every local layer uploaded (a layer named twice: once)
@@ -469,7 +519,8 @@ class ICP_HIP : public ICP
             for (uint32_t k = static_cast<uint32_t>(kp.size()); k < upto; k++)
             {
                 for (auto* src : attachedSources()) { src->updateVariable("ICP_ITERATION", k); src->realize(); }  // [U]
-                for (size_t j = 0; j < ls.matchers.size(); j++) thr[j].push_back(ls.matchers[j]->threshold);
+                for (size_t j = 0; j < ls.matchers.size(); j++)
+                    thr[j].push_back(ls.matchers[j] ? ls.matchers[j]->threshold : ls.plane_matchers[j]->distanceThreshold);
                 kp.push_back(ls.gn->robustKernelParam);
             }
         };
@@ -496,12 +547,15 @@ class ICP_HIP : public ICP
             for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) pr.info[i * 6 + j] = prior->cov_inv(i, j);
         }
         if (layer_pairs_.size() < np) layer_pairs_.resize(np);
+        if (ls.any_plane && layer_planes_.size() < np) layer_planes_.resize(np);
         std::vector<mh_pairs_out> po(np);
+        std::vector<mh_pairs_pl_out> ppl(np);
         std::vector<uint64_t> counts(np, 0);
         size_t n_local = 0;
         for (size_t i = 0; i < np; i++)
         {
-            po[i] = layer_pairs_[i].out(locals[i]->getPointsBufferRef_x().size() * knn[i].pairings_per_point);
+            if (planes[i].knn) ppl[i] = layer_planes_[i].out(locals[i]->getPointsBufferRef_x().size());
+            else po[i] = layer_pairs_[i].out(locals[i]->getPointsBufferRef_x().size() * knn[i].pairings_per_point);
             n_local += locals[i]->getPointsBufferRef_x().size();
         }
         auto run_with = [&](uint32_t budget, mh_icp_iter* trace) {
@@ -511,10 +565,11 @@ class ICP_HIP : public ICP
             q.max_iterations = budget;
             q.kernel_param   = kp.data();
             mh_icp_result rr{};
-            mh_check(mh_icp_align_layers_kbest(np, pairs.data(), ls.any_unique ? opts.data() : nullptr,
-                                               ls.any_gate ? gates.data() : nullptr, ls.any_knn ? knn.data() : nullptr, &q, T0,
-                                               prior ? &pr : nullptr, &rr, trace, po.data(), counts.data(), MH_MEM_HOST),
-                     "mh_icp_align_layers_kbest");
+            mh_check(mh_icp_align_layers_planes(np, pairs.data(), ls.any_unique ? opts.data() : nullptr,
+                                                ls.any_gate ? gates.data() : nullptr, ls.any_knn ? knn.data() : nullptr,
+                                                ls.any_plane ? planes.data() : nullptr, &q, T0, prior ? &pr : nullptr, &rr, trace,
+                                                po.data(), ls.any_plane ? ppl.data() : nullptr, counts.data(), MH_MEM_HOST),
+                     "mh_icp_align_layers_planes");
             return rr;
         };
         auto run = [&](uint32_t budget, mh_icp_iter* trace) {
@@ -564,6 +619,20 @@ class ICP_HIP : public ICP
             const auto& lx = locals[i]->getPointsBufferRef_x();
             const auto& ly = locals[i]->getPointsBufferRef_y();
             const auto& lz = locals[i]->getPointsBufferRef_z();
+            if (planes[i].knn)
+            {   // Pairings::paired_pt2pl [U]: {pl_global{plane, centroid}, pt_local}
+                const auto& q = layer_planes_[i];
+                for (uint64_t k = 0; k < counts[i]; k++)
+                {
+                    point_plane_pair_t pp;
+                    pp.pl_global.centroid = {q.cx[k], q.cy[k], q.cz[k]};
+                    pp.pl_global.plane    = mrpt::math::TPlane(mrpt::math::TPoint3D(q.cx[k], q.cy[k], q.cz[k]),
+                                                               mrpt::math::TVector3D(q.nx[k], q.ny[k], q.nz[k]));
+                    pp.pt_local           = {lx[q.li[k]], ly[q.li[k]], lz[q.li[k]]};
+                    result.finalPairings.paired_pt2pl.push_back(pp);
+                }
+                continue;
+            }
             const auto& b = layer_pairs_[i];
             for (uint64_t k = 0; k < counts[i]; k++)
             {
@@ -580,6 +649,7 @@ class ICP_HIP : public ICP
     }
 
     std::vector<molahip_mrpt::DeviceSession::PairBuffers> layer_pairs_;  // align_layers: result arrays per pair
+    std::vector<molahip_mrpt::DeviceSession::PlaneBuffers> layer_planes_;  // ... and per plane pair
     std::unique_ptr<molahip_mrpt::DeviceSession> dev_;  // context, map mirrors, staging scan, result buffers
     uint32_t last_iterations_ = 0;  // nIterations of the previous align(): sizes the first stage of the lazy threshold schedule
     AlignTrace trace_;

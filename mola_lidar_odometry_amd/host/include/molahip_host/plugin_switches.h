@@ -21,6 +21,9 @@
 //   MOLA_HIP_FUSE_KBEST       (unset) | 0 | 1         matchers with pairingsPerPoint 2 .. MH_MAX_PAIRINGS_PER_POINT on the fused
 //                                                     multi-layer loop (mh_icp_align_layers_kbest); set, it overrides
 //                                                     ICP::fuseMultiPairings and the adapter's default (off) both ways
+//   MOLA_HIP_FUSE_PLANES      (unset) | 0 | 1         Matcher_Point2Plane on point layers (KNN + PCA) on the fused multi-layer loop
+//                                                     (mh_icp_align_layers_planes); set, it overrides ICP::fusePlaneMatchers
+//                                                     and the adapter's default (off) both ways
 //   MOLA_HIP_BATCH_OPTS       1 | 0                   (host layer with an AlignBatcher only) multi-layer alignments with a unique
 //                                                     pair, a gate or pairingsPerPoint > 1 join the lock-step batches
 //                                                     (mh_icp_align_layers_batch_opts); 0: each runs on its own beside them
@@ -45,6 +48,7 @@ struct PluginSwitches {
   bool force_cpu = false;
   int fuse_gates = -1;  // MOLA_HIP_FUSE_GATES: -1 not set (the caller's own setting holds), 0 | 1
   int fuse_kbest = -1;  // MOLA_HIP_FUSE_KBEST: the same for pairingsPerPoint > 1
+  int fuse_planes = -1; // MOLA_HIP_FUSE_PLANES: the same for Matcher_Point2Plane on point layers
   bool batch_opts = true;  // MOLA_HIP_BATCH_OPTS: unique / gated / k-best multi-layer alignments join the AlignBatcher's batches
   // which of them came from the environment (the mirror classes only override their YAML values for those)
   bool has_gm_form = false, has_index_mode = false, has_cov_step = false, has_min_delta = false, has_max_cost = false,
@@ -100,6 +104,7 @@ inline PluginSwitches read_plugin_switches() {
   if (const char* e = getenv("MOLA_HIP_FORCE_CPU")) s.force_cpu = atoi(e) != 0;
   if (const char* e = getenv("MOLA_HIP_FUSE_GATES")) s.fuse_gates = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("MOLA_HIP_FUSE_KBEST")) s.fuse_kbest = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("MOLA_HIP_FUSE_PLANES")) s.fuse_planes = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("MOLA_HIP_BATCH_OPTS")) s.batch_opts = atoi(e) != 0;
   return s;
 }
@@ -116,6 +121,8 @@ inline void reload_plugin_switches() { plugin_switches_storage() = read_plugin_s
 inline bool fuse_gates(bool setting, const PluginSwitches& sw) { return sw.fuse_gates < 0 ? setting : sw.fuse_gates != 0; }
 /** The same for matchers with pairingsPerPoint > 1. */
 inline bool fuse_kbest(bool setting, const PluginSwitches& sw) { return sw.fuse_kbest < 0 ? setting : sw.fuse_kbest != 0; }
+/** The same for Matcher_Point2Plane on point layers (KNN + PCA). */
+inline bool fuse_planes(bool setting, const PluginSwitches& sw) { return sw.fuse_planes < 0 ? setting : sw.fuse_planes != 0; }
 
 /** MH_KERNEL_* for the NAME of an upstream mp2p_icp::RobustKernel enumerator [U] (names, not numeric values: the
  *  upstream enum's values are not relied on).  "GemanMcClure" resolves to the switched form. */

@@ -577,11 +577,16 @@ class ICP {
   // multi-layer loop (mh_icp_align_layers_kbest), a single pair included, instead of the generic one.  Default false;
   // MOLA_HIP_FUSE_KBEST=0|1 overrides it both ways.
   void fuseMultiPairings(bool v) { fuse_kbest_ = v; }
+  // Matcher_Point2Plane on point layers (KNN + PCA, rgbd.yaml:143-151) runs on the fused multi-layer loop
+  // (mh_icp_align_layers_planes), a single pair included, instead of the generic one -- unless its global layer carries NDT
+  // statistics.  Default false; MOLA_HIP_FUSE_PLANES=0|1 overrides it both ways.
+  void fusePlaneMatchers(bool v) { fuse_planes_ = v; }
   // the path align() takes for the configured pipeline (no alignment): "single" (mh_icp_align: lidar3d-default / -ndt shapes),
   // "layers" (mh_icp_align_layers: several point-layer pairs, lidar3d-dual-map / -edges shapes; with fuseGatedMatchers also gated
-  // ones, lidar3d-near-far) or "generic" (matcher by matcher).
+  // ones, lidar3d-near-far, with fusePlaneMatchers also Matcher_Point2Plane entries on point layers, rgbd.yaml:133-151) or
+  // "generic" (matcher by matcher).
   // "layers" also needs the maps handed to align() to qualify (global layers HashedVoxelPointCloud on one context, local layers
-  // PointCloud / DevicePointCloud); otherwise that call runs the generic loop.
+  // PointCloud / DevicePointCloud, no NDT statistics on a plane matcher's global layer); otherwise that call runs the generic loop.
   std::string alignPath() const;
   // evaluate the per-iteration thresholds of the fused paths (single or multi-layer) NOW, on the variables' current values; the next align()
   // re-uses them if the variables its formulas read still have these values (anything else: evaluated again, as before)
@@ -625,7 +630,7 @@ class ICP {
   mh_scan* scan_ = nullptr;                 // staging layer for host point clouds handed to the fused path ...
   std::shared_ptr<DeviceContext> scan_ctx_;  // ... and the (map's) context it lives in, kept alive until ~ICP has destroyed it
   std::map<std::string, mh_scan*> layer_scans_;  // align_fused_layers: a staging layer per host local layer (in scan_ctx_)
-  bool last_fused_ = false, force_generic_ = false, keep_pairings_ = true, hook_replay_ = false, fuse_gated_ = false, fuse_kbest_ = false;
+  bool last_fused_ = false, force_generic_ = false, keep_pairings_ = true, hook_replay_ = false, fuse_gated_ = false, fuse_kbest_ = false, fuse_planes_ = false;
   std::shared_ptr<AlignBatcher> batcher_;
   const void* batch_owner_ = nullptr;
   // how long the previous call of each kind ran: [0] calls with the full iteration budget, [1] re-entries after a hook

@@ -3,6 +3,7 @@
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -629,6 +630,25 @@ bool ICP::can_fuse() const {
 // (mh_icp_align_layers_gated); otherwise they keep the generic loop.  The same for pairingsPerPoint 2 .. MH_MAX_PAIRINGS_PER_POINT
 // with fuseMultiPairings / MOLA_HIP_FUSE_KBEST=1 (mh_icp_align_layers_kbest), a single pair included.  A local layer named by two entries is paired again for each: only under
 // MOLA_HIP_MATCHED_POINTS=again (skip would leave the second entry's points out, which mh_icp_align_layers does not do).
+// Enabled Matcher_Point2Plane entries (KNN + PCA on point layers, rgbd.yaml:143-151) only with fusePlaneMatchers /
+// MOLA_HIP_FUSE_PLANES=1 (mh_icp_align_layers_planes), gated ones under the gates switch as well; a single such pair included.
+namespace {
+// what the multi-layer loop reads of a matcher, whichever of its two kinds it is
+struct FusedMatcher {
+  const Matcher_Points_DistanceThreshold* pt = nullptr;
+  const Matcher_Point2Plane* pl = nullptr;
+  const Matcher* base() const { return pt ? static_cast<const Matcher*>(pt) : pl; }
+  const std::vector<Matcher_Points_DistanceThreshold::LayerMatch>& entries() const { return pt ? pt->pointLayerMatches : pl->pointLayerMatches; }
+  double threshold() const { return pt ? pt->threshold : pl->distanceThreshold; }
+};
+FusedMatcher fused_matcher(const Matcher::Ptr& mm) {
+  FusedMatcher f;
+  f.pt = dynamic_cast<const Matcher_Points_DistanceThreshold*>(mm.get());
+  if (!f.pt) f.pl = dynamic_cast<const Matcher_Point2Plane*>(mm.get());
+  return f;
+}
+}  // namespace
+
 bool ICP::can_fuse_layers() const {
   if (force_generic_ || iteration_hook_) return false;
   if (matchers_.empty() || solvers_.size() != 1 || !std::dynamic_pointer_cast<Solver_GaussNewton>(solvers_[0])) return false;
@@ -636,7 +656,15 @@ bool ICP::can_fuse_layers() const {
   bool single_pair_ok = false;  // a unique or gated matcher: shapes only the multi-layer loop takes, a single pair included
   const bool gates_ok = molahip_host::fuse_gates(fuse_gated_, molahip_host::plugin_switches());
   const bool kbest_ok = molahip_host::fuse_kbest(fuse_kbest_, molahip_host::plugin_switches());
+  const bool planes_ok = molahip_host::fuse_planes(fuse_planes_, molahip_host::plugin_switches());
   for (const auto& mm : matchers_) {
+    if (auto pl = std::dynamic_pointer_cast<Matcher_Point2Plane>(mm)) {
+      if (!planes_ok || !pl->enabled || pl->knn < 3 || pl->knn > MH_MAX_PLANE_KNN) return false;
+      if ((pl->runFromIteration || pl->runUpToIteration) && !gates_ok) return false;
+      single_pair_ok = single_pair_ok || !pl->pointLayerMatches.empty();
+      for (const auto& lm : pl->pointLayerMatches) locals.push_back(lm.local);
+      continue;
+    }
     auto m = std::dynamic_pointer_cast<Matcher_Points_DistanceThreshold>(mm);
     if (!m || !m->enabled) return false;
     const bool multi = m->pairingsPerPoint != 1;  // (realizeWith has refused what is outside 1 .. MH_MAX_PAIRINGS_PER_POINT)
@@ -659,16 +687,18 @@ std::string ICP::alignPath() const {
 }
 
 // the layers align_fused_layers needs: every global one a HashedVoxelPointCloud on the first one's context, every local one a
-// PointCloud or a DevicePointCloud
+// PointCloud or a DevicePointCloud.  A plane matcher's global layer must carry no NDT statistics: on such a layer the generic
+// route runs mh_nn_search_pt2pl (the per-voxel planes), which is another matcher than the loop's KNN + PCA.
 static bool layer_inputs_ok(const std::vector<Matcher::Ptr>& matchers, const metric_map_t& pcLocal, const metric_map_t& pcGlobal) {
   const DeviceContext* ctx = nullptr;
   for (const auto& mm : matchers)
-    for (const auto& lm : std::static_pointer_cast<Matcher_Points_DistanceThreshold>(mm)->pointLayerMatches) {
+    for (const auto& lm : fused_matcher(mm).entries()) {
       auto g = pcGlobal.layers.find(lm.global);
       auto l = pcLocal.layers.find(lm.local);
       if (g == pcGlobal.layers.end() || l == pcLocal.layers.end()) return false;
       auto hv = std::dynamic_pointer_cast<HashedVoxelPointCloud>(g->second);
       if (!hv || (ctx && hv->context().get() != ctx)) return false;
+      if (fused_matcher(mm).pl && std::dynamic_pointer_cast<NDT>(g->second)) return false;
       ctx = hv->context().get();
       // mh_icp_align_layers refuses a map of 2^30 or more records (records = points + two per voxel at most)
       mh_map_info info{};
@@ -677,7 +707,7 @@ static bool layer_inputs_ok(const std::vector<Matcher::Ptr>& matchers, const met
     }
   // ... and maps and scans on more than one context: a device local layer has to live on the maps' one
   for (const auto& mm : matchers)
-    for (const auto& lm : std::static_pointer_cast<Matcher_Points_DistanceThreshold>(mm)->pointLayerMatches) {
+    for (const auto& lm : fused_matcher(mm).entries()) {
       auto dev = std::dynamic_pointer_cast<DevicePointCloud>(pcLocal.layers.find(lm.local)->second);
       if (dev && dev->context().get() != ctx) return false;
     }
@@ -1171,13 +1201,13 @@ void ICP::precomputeSchedule(uint32_t n_iterations) {
 // one realize per iteration; kept with the values of the variables the formulas read
 void ICP::prepare_layer_schedule(uint32_t n_iterations) {
   auto s = std::static_pointer_cast<Solver_GaussNewton>(solvers_[0]);
-  std::vector<std::shared_ptr<Matcher_Points_DistanceThreshold>> ms;
-  for (const auto& mm : matchers_) ms.push_back(std::static_pointer_cast<Matcher_Points_DistanceThreshold>(mm));
+  std::vector<FusedMatcher> ms;  // (a plane matcher's schedule: its distanceThreshold)
+  for (const auto& mm : matchers_) ms.push_back(fused_matcher(mm));
   std::map<std::string, double> vars = source_ ? source_->getVariableValues() : own_source_.getVariableValues();
   double& it_var = vars["ICP_ITERATION"];
   it_var = 0.0;
   std::vector<Parameterizable::Binding> bm;
-  for (const auto& m : ms) bm.push_back(m->bind(vars));
+  for (const auto& mm : matchers_) bm.push_back(mm->bind(vars));
   const auto bs = s->bind(vars);
   std::vector<double> key;
   for (const Parameterizable::Binding* b : {&bs})
@@ -1196,7 +1226,7 @@ void ICP::prepare_layer_schedule(uint32_t n_iterations) {
     it_var = (double)k;
     for (const auto& b : bm) b.realize();
     bs.realize();
-    for (size_t j = 0; j < ms.size(); j++) layer_sched_.thr[j][k] = ms[j]->threshold;
+    for (size_t j = 0; j < ms.size(); j++) layer_sched_.thr[j][k] = ms[j].threshold();
     layer_sched_.kp[k] = s->robustKernelParam;
   }
   layer_sched_.valid = true;
@@ -1338,8 +1368,8 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
                              Results& result, const std::optional<CPose3DPDFGaussianInf>& prior) {
   const auto t_setup0 = std::chrono::steady_clock::now();
   auto s = std::static_pointer_cast<Solver_GaussNewton>(solvers_[0]);
-  std::vector<std::shared_ptr<Matcher_Points_DistanceThreshold>> ms;
-  for (const auto& mm : matchers_) ms.push_back(std::static_pointer_cast<Matcher_Points_DistanceThreshold>(mm));
+  std::vector<FusedMatcher> ms;
+  for (const auto& mm : matchers_) ms.push_back(fused_matcher(mm));
   // every matcher's threshold schedule and the solver's kernel parameter (a no-op when precomputeSchedule() ran on the same
   // values of the variables)
   const uint32_t mi = p.maxIterations;
@@ -1374,9 +1404,10 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   std::vector<mh_layer_pair_opts> opts;  // U13: a matcher's allowMatchAlreadyMatchedGlobalPoints: false, for each of its entries
   std::vector<mh_layer_pair_gates> gates;  // a matcher's runFromIteration / runUpToIteration, for each of its entries
   std::vector<mh_layer_pair_knn> knn;  // a matcher's pairingsPerPoint, for each of its entries
-  bool any_unique = false, any_gate = false, any_knn = false;
+  std::vector<mh_layer_pair_plane> planes;  // a Matcher_Point2Plane's knn, minimumPlanePoints, planeEigenThreshold, searchRadius
+  bool any_unique = false, any_gate = false, any_knn = false, any_plane = false;
   std::vector<Entry> entries;
-  const auto& ctx0 = global_layer(pcGlobal, ms[0]->pointLayerMatches[0].global).context();
+  const auto& ctx0 = global_layer(pcGlobal, ms[0].entries()[0].global).context();
   if (scan_ctx_ && scan_ctx_ != ctx0) {
     for (auto& e : layer_scans_) mh_scan_destroy(e.second);
     layer_scans_.clear();
@@ -1386,7 +1417,7 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   scan_ctx_ = ctx0;
   std::map<std::string, bool> staged;
   for (size_t j = 0; j < ms.size(); j++)
-    for (const auto& lm : ms[j]->pointLayerMatches) {
+    for (const auto& lm : ms[j].entries()) {
       Entry e;
       auto it = pcLocal.layers.find(lm.local);
       e.dev = std::dynamic_pointer_cast<DevicePointCloud>(it->second).get();
@@ -1410,15 +1441,25 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
       lp.map = global_layer(pcGlobal, lm.global).handle();
       lp.scan = scan;
       lp.threshold = thr[j].data();
-      lp.threshold_angular_deg = ms[j]->thresholdAngularDeg;
-      lp.weight = lm.weight;
+      lp.threshold_angular_deg = ms[j].pt ? ms[j].pt->thresholdAngularDeg : 0.0;
+      lp.weight = lm.weight;  // (a plane matcher's entries may differ in weight here: every pair scales its own rows)
       pairs.push_back(lp);
-      opts.push_back(mh_layer_pair_opts{ms[j]->allowMatchAlreadyMatchedGlobalPoints ? 0u : 1u});
+      // (a plane pairing names no map point: nothing to claim, whatever the matcher's allowMatchAlreadyMatchedGlobalPoints says)
+      opts.push_back(mh_layer_pair_opts{(ms[j].pt && !ms[j].pt->allowMatchAlreadyMatchedGlobalPoints) ? 1u : 0u});
       any_unique = any_unique || opts.back().unique_global;
-      gates.push_back(mh_layer_pair_gates{ms[j]->runFromIteration, ms[j]->runUpToIteration});
-      any_gate = any_gate || ms[j]->runFromIteration || ms[j]->runUpToIteration;
-      knn.push_back(mh_layer_pair_knn{(uint32_t)ms[j]->pairingsPerPoint});
-      any_knn = any_knn || ms[j]->pairingsPerPoint > 1;
+      gates.push_back(mh_layer_pair_gates{ms[j].base()->runFromIteration, ms[j].base()->runUpToIteration});
+      any_gate = any_gate || ms[j].base()->runFromIteration || ms[j].base()->runUpToIteration;
+      knn.push_back(mh_layer_pair_knn{ms[j].pt ? (uint32_t)ms[j].pt->pairingsPerPoint : 1u});
+      any_knn = any_knn || knn.back().pairings_per_point > 1;
+      mh_layer_pair_plane lpl{};
+      if (ms[j].pl) {
+        lpl.knn = ms[j].pl->knn;
+        lpl.minimum_plane_points = ms[j].pl->minimumPlanePoints;
+        lpl.plane_eigen_threshold = ms[j].pl->planeEigenThreshold;
+        lpl.search_radius = ms[j].pl->searchRadius;
+        any_plane = true;
+      }
+      planes.push_back(lpl);
       entries.push_back(e);
     }
   mh_prior pr;
@@ -1428,21 +1469,33 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   std::vector<std::vector<uint32_t>> li(pairs.size()), gi(pairs.size());
   std::vector<std::vector<float>> gx(pairs.size()), gy(pairs.size()), gz(pairs.size()), d2(pairs.size());
   std::vector<mh_pairs_out> po(pairs.size());
+  std::vector<mh_pairs_pl_out> ppl(pairs.size());  // a plane pair's final pairings: li | centroid in gx gy gz | normal in pn
+  std::vector<std::array<std::vector<float>, 3>> pn(pairs.size());
   std::vector<uint64_t> counts(pairs.size(), 0);
   for (size_t i = 0; want_pairs && i < pairs.size(); i++) {
     const size_t n = (entries[i].dev ? entries[i].dev->size() : entries[i].host->size()) * (size_t)knn[i].pairings_per_point;
-    li[i].resize(n); gi[i].resize(n); gx[i].resize(n); gy[i].resize(n); gz[i].resize(n); d2[i].resize(n);
+    li[i].resize(n); gx[i].resize(n); gy[i].resize(n); gz[i].resize(n);
+    if (planes[i].knn) {
+      for (auto& v : pn[i]) v.resize(n);
+      ppl[i] = mh_pairs_pl_out{li[i].data(), gx[i].data(), gy[i].data(), gz[i].data(), pn[i][0].data(), pn[i][1].data(), pn[i][2].data()};
+      continue;
+    }
+    gi[i].resize(n); d2[i].resize(n);
     po[i] = mh_pairs_out{li[i].data(), gi[i].data(), gx[i].data(), gy[i].data(), gz[i].data(), d2[i].data()};
   }
   mh_icp_result r{};
   std::vector<mh_icp_iter> trace(p.generateDebugFiles ? mi : 0);
   auto solo = [&] {
-    check(mh_icp_align_layers_kbest(pairs.size(), pairs.data(), any_unique ? opts.data() : nullptr, any_gate ? gates.data() : nullptr,
-                                    any_knn ? knn.data() : nullptr, &ip, guess.T, prior ? &pr : nullptr, &r,
-                                    trace.empty() ? nullptr : trace.data(), want_pairs ? po.data() : nullptr, counts.data(),
-                                    MH_MEM_HOST), "mh_icp_align_layers_kbest");
+    check(mh_icp_align_layers_planes(pairs.size(), pairs.data(), any_unique ? opts.data() : nullptr, any_gate ? gates.data() : nullptr,
+                                     any_knn ? knn.data() : nullptr, any_plane ? planes.data() : nullptr, &ip, guess.T,
+                                     prior ? &pr : nullptr, &r, trace.empty() ? nullptr : trace.data(),
+                                     want_pairs ? po.data() : nullptr, (want_pairs && any_plane) ? ppl.data() : nullptr, counts.data(),
+                                     MH_MEM_HOST), "mh_icp_align_layers_planes");
   };
-  if (batcher_ && (any_unique || any_gate || any_knn) && !molahip_host::plugin_switches().batch_opts) {
+  if (batcher_ && any_plane) {
+    // (no lock-step form with plane pairs yet: on its own beside the batches, the participant counted as busy meanwhile)
+    batcher_->runOutside(batch_owner_, solo);
+  } else if (batcher_ && (any_unique || any_gate || any_knn) && !molahip_host::plugin_switches().batch_opts) {
     // (MOLA_HIP_BATCH_OPTS=0, the A/B against mh_icp_align_layers_batch_opts: on its own, the participant counted as busy
     // meanwhile -- as align_generic)
     batcher_->runOutside(batch_owner_, solo);
@@ -1471,6 +1524,11 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
     PointCloud downloaded;
     if (entries[i].dev && counts[i]) entries[i].dev->download(downloaded.x, downloaded.y, downloaded.z);
     const PointCloud& local = entries[i].dev ? downloaded : *entries[i].host;
+    if (planes[i].knn) {
+      const std::vector<float> a[6] = {gx[i], gy[i], gz[i], pn[i][0], pn[i][1], pn[i][2]};
+      append_pl_pairs(local, li[i], a, counts[i], fp);
+      continue;
+    }
     for (uint64_t k = 0; k < counts[i]; k++) {
       fp.localIdx.push_back(li[i][k]);
       fp.globalIdx.push_back(gi[i][k]);

@@ -675,6 +675,7 @@ void LidarOdometry::initialize(const Config& cfg) {
     icp->setKeepFinalPairings(false);
     icp->fuseGatedMatchers(true);  // gated blocks (lidar3d-near-far.yaml:183) on the device loop; MOLA_HIP_FUSE_GATES=0: as before
     icp->fuseMultiPairings(true);  // pairingsPerPoint > 1 likewise (profiles/layers_kbest.md); MOLA_HIP_FUSE_KBEST=0: as before
+    icp->fusePlaneMatchers(true);  // Matcher_Point2Plane on point layers likewise (profiles/layers_planes.md); MOLA_HIP_FUSE_PLANES=0: as before
   }
   // local map definition (yaml:213-242), instantiated at the first key-frame when its $f{} formulas can be evaluated
   const Config& gen = cfg["localmap_generator"];

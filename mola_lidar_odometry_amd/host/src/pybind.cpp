@@ -63,6 +63,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     return d;
   });
   m.def("plugin_switch_fuse_kbest", [] { return molahip_host::plugin_switches().fuse_kbest; });  // MOLA_HIP_FUSE_KBEST: -1 not set
+  m.def("plugin_switch_fuse_planes", [] { return molahip_host::plugin_switches().fuse_planes; });  // MOLA_HIP_FUSE_PLANES: -1 not set
   m.def("plugin_switch_fuse_gates", [] { return molahip_host::plugin_switches().fuse_gates; });  // MOLA_HIP_FUSE_GATES: -1 not set (a function of its own: the keys of plugin_switches() are compared as a whole by their users)
   m.def("kernel_from_upstream_name", [](const std::string& n) { return molahip_host::kernel_from_upstream_name(n.c_str(), molahip_host::plugin_switches()); });
   m.def("term_reason_name", [](uint32_t t) { return std::string(enum2str(molahip_host::term_reason_to<IterTermReason>(t))); });
@@ -112,7 +113,15 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("n_pairs_pt2pl", [](const Results& r) { return r.finalPairings.pl_lx.size(); })
       .def("potential_pairings", [](const Results& r) { return r.finalPairings.potential_pairings; })
       .def("pair_global_idx", [](const Results& r) { return r.finalPairings.globalIdx; })
-      .def("pair_local_idx", [](const Results& r) { return r.finalPairings.localIdx; });
+      .def("pair_local_idx", [](const Results& r) { return r.finalPairings.localIdx; })
+      // the point-to-plane pairings, nine values each: local point | plane centroid | plane normal
+      .def("pairs_pt2pl", [](const Results& r) {
+        const Pairings& f = r.finalPairings;
+        std::vector<std::vector<float>> out(f.pl_lx.size());
+        for (size_t k = 0; k < out.size(); k++)
+          out[k] = {f.pl_lx[k], f.pl_ly[k], f.pl_lz[k], f.pl_cx[k], f.pl_cy[k], f.pl_cz[k], f.pl_nx[k], f.pl_ny[k], f.pl_nz[k]};
+        return out;
+      });
   py::class_<ICP, std::shared_ptr<ICP>>(m, "ICP")
       .def("align", [](ICP& icp, const metric_map_t& l, const metric_map_t& g, const TPose3D& guess, const Parameters& p,
                        std::optional<CPose3DPDFGaussianInf> prior) { Results r; icp.align(l, g, guess, p, r, prior); return r; },
@@ -123,6 +132,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("forceGenericPath", &ICP::forceGenericPath)
       .def("fuseGatedMatchers", &ICP::fuseGatedMatchers)
       .def("fuseMultiPairings", &ICP::fuseMultiPairings)
+      .def("fusePlaneMatchers", &ICP::fusePlaneMatchers)
       .def("alignPath", &ICP::alignPath)
       .def("precomputeSchedule", &ICP::precomputeSchedule)
       .def("setHookReplay", &ICP::setHookReplay)
