@@ -47,8 +47,8 @@ extern "C" {
  * mh_preprocess_params' two decimation-method fields, round 5; 7: mh_layer_pair and mh_icp_align_layers, later also
  * mh_curvature_params and mh_scan_curvature, then the intensity channel's entry points and mh_by_intensity_params,
  * mh_layer_pair_gates and mh_icp_align_layers_gated, mh_layer_pair_knn and mh_icp_align_layers_kbest, mh_layer_pair_plane and
- * mh_icp_align_layers_planes, mh_layer_job_opts and mh_icp_align_layers_batch_opts: new structs and entry points change no
- * existing layout, and a binder that lacks
+ * mh_icp_align_layers_planes, mh_layer_job_opts and mh_icp_align_layers_batch_opts, mh_layer_job_planes and
+ * mh_icp_align_layers_batch_planes: new structs and entry points change no existing layout, and a binder that lacks
  * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
  * built with) and zero-initialises every struct it passes -- a field the binder does not know then reads as its default. */
@@ -780,7 +780,7 @@ MH_API mh_status mh_icp_align_layers_kbest(size_t n_pairs, const mh_layer_pair* 
  *    launches neither the plain search nor the point accumulation (1 + 2 * gn.max_inner_iterations).  The covariance that closes
  *    the loop has one more launch.  The set of plane pairs and their knn are part of the graph key.  Results are bitwise
  *    reproducible, MH_NO_GRAPH=1 and MH_NO_PREV_BOUND=1 included.
- * No lock-step batch form yet: mh_icp_align_layers_batch_opts takes no planes. */
+ * Lock-step batch form: mh_icp_align_layers_batch_planes (below) takes a job's planes; plane jobs form groups of their own. */
 typedef struct {
   uint32_t knn;                   /* 0: a point pair (everything as before); 3 .. MH_MAX_PLANE_KNN: a plane pair */
   uint32_t minimum_plane_points;  /* >= 3 */
@@ -858,6 +858,37 @@ MH_API mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_jo
                                                 int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
                                                 mh_icp_result* results,
                                                 uint64_t* final_pair_counts /* n_jobs * MH_MAX_LAYER_PAIRS entries or NULL */);
+
+/* mh_icp_align_layers_batch_opts for mh_icp_align_layers_planes: every job with its own planes as well (n_pairs entries or NULL,
+ * as that call takes them).  (A struct and an entry point of their own: mh_layer_job_opts keeps its layout and MH_ABI_VERSION its
+ * value.)  Everything mh_icp_align_layers_batch_opts promises holds, with "the single call" read as
+ * mh_icp_align_layers_planes(job i's pairs, opts, gates, knn, planes): n_final_pairs_pt2pl and the per-pair counts of plane pairs
+ * included, bit for bit.  planes NULL (or knn 0 in every entry) in every job IS mh_icp_align_layers_batch_opts, which calls this
+ * function: the same uploads, the same launches, the same bits.  Otherwise, plus:
+ *  - Groups: the key is gn.max_inner_iterations, compute_covariance, whether the job has a pair with k_i > 1 and ONE more bit --
+ *    whether the job has a plane pair.  A group without a plane job issues exactly the kernels it issued before.
+ *  - Launches of a group of plane jobs per ICP iteration, for the whole group, by the single call's formula with P, K, U and A
+ *    taken over all jobs of the group:  P + K + 1 + U + (A + 1 + 1) * gn.max_inner_iterations.  A launch without workgroups is
+ *    skipped, the point accumulation and the point covariance accumulation of a group of plane pairs only included.  The solve and
+ *    the covariance finalisation add each job's plane rows behind its point rows in the single call's fixed order.
+ *  - A job alone in its group, trivial jobs and every job under MH_NO_LOCKSTEP=1 run through mh_icp_align_layers_planes with
+ *    their arrays, one after the other.
+ *  - Everything is validated before any device work, for every job: a plane pair by the rules of mh_icp_align_layers_planes
+ *    (MH_ERR_INVALID_ARGUMENT for unique_global != 0, pairings_per_point > 1, threshold_angular_deg != 0, and for whatever
+ *    mh_nn_search_pt2pl_knn rejects).  After an error every context stays usable and no claim epoch has been consumed. */
+typedef struct {
+  size_t n_pairs;                      /* 1 .. MH_MAX_LAYER_PAIRS */
+  const mh_layer_pair* pairs;
+  const mh_layer_pair_opts* opts;      /* n_pairs entries or NULL */
+  const mh_layer_pair_gates* gates;    /* n_pairs entries or NULL */
+  const mh_layer_pair_knn* knn;        /* n_pairs entries or NULL */
+  const mh_layer_pair_plane* planes;   /* n_pairs entries or NULL */
+} mh_layer_job_planes;
+
+MH_API mh_status mh_icp_align_layers_batch_planes(size_t n_jobs, const mh_layer_job_planes* jobs, const mh_icp_params* params,
+                                                  int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
+                                                  mh_icp_result* results,
+                                                  uint64_t* final_pair_counts /* n_jobs * MH_MAX_LAYER_PAIRS entries or NULL */);
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,13 @@ class LayerJobOpts(C.Structure):
                 ("gates", C.POINTER(LayerPairGates)), ("knn", C.POINTER(LayerPairKnn))]
 
 
+class LayerJobPlanes(C.Structure):
+    """mh_layer_job_planes: one job of mh_icp_align_layers_batch_planes -- mh_layer_job_opts plus the pairs' mh_layer_pair_plane
+    (n_pairs entries or NULL)."""
+    _fields_ = [("n_pairs", C.c_size_t), ("pairs", C.POINTER(LayerPair)), ("opts", C.POINTER(LayerPairOpts)),
+                ("gates", C.POINTER(LayerPairGates)), ("knn", C.POINTER(LayerPairKnn)), ("planes", C.POINTER(LayerPairPlane))]
+
+
 MAX_LAYER_PAIRS = 8        # MH_MAX_LAYER_PAIRS
 MAX_LAYER_BATCH_JOBS = 64  # MH_MAX_LAYER_BATCH_JOBS
 MAX_PLANE_KNN = 16         # MH_MAX_PLANE_KNN
@@ -276,6 +283,8 @@ _SIGNATURES = {
                                               C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
     "mh_icp_align_layers_batch_opts": (C.c_int32, [C.c_size_t, C.POINTER(LayerJobOpts), C.POINTER(ICPParamsC), C.c_int32, _DP,
                                                    C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
+    "mh_icp_align_layers_batch_planes": (C.c_int32, [C.c_size_t, C.POINTER(LayerJobPlanes), C.POINTER(ICPParamsC), C.c_int32, _DP,
+                                                     C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
 }
 
 _lib = None
@@ -1003,12 +1012,14 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
     return out
 
 
-def icp_align_layers_batch(jobs, T_guesses, params, priors=None, pairings_per_point=None):
+def icp_align_layers_batch(jobs, T_guesses, params, priors=None, pairings_per_point=None, planes_entry=False):
     """mh_icp_align_layers_batch: one multi-layer alignment per job, jobs of the same loop shape in lock step.  `jobs`: a
     sequence of icp_align_layers' `pairs` arguments, every job on a Context of its own; `params`: one ICPParams or one per job.
     A pair dict may carry unique_global, run_from_iteration and run_up_to_iteration as for icp_align_layers, and
     pairings_per_point is one entry per job (None, one value for every pair of the job, or one per pair): when any job has any of
-    them the call goes to mh_icp_align_layers_batch_opts, otherwise to mh_icp_align_layers_batch.
+    them the call goes to mh_icp_align_layers_batch_opts, otherwise to mh_icp_align_layers_batch.  A pair dict may carry plane=dict(...)
+    as for icp_align_layers: when a pair of any job does, the call goes to mh_icp_align_layers_batch_planes (planes_entry=True sends
+    it there whatever the jobs hold: a job without such a dict then passes NULL).
     Returns a list of icp_align_layers' dicts (no pairs, no trace); every entry has the bits of that job's single call."""
     n = len(jobs)
     T = np.ascontiguousarray(np.stack([_T12(t) for t in T_guesses]).reshape(len(T_guesses) * 12)) if n else np.zeros(12)
@@ -1026,6 +1037,7 @@ def icp_align_layers_batch(jobs, T_guesses, params, priors=None, pairings_per_po
     keep_pairs = [_layer_pairs(pairs, plist[i].max_iterations) for i, pairs in enumerate(jobs)]
     assert pairings_per_point is None or len(pairings_per_point) == n
     keep_opts = []  # per job: (opts, gates, knn), None where the job has none
+    keep_planes = []  # per job: its mh_layer_pair_plane array, None where no pair of it carries `plane`
     for i, (arr, norm, thr_keep) in enumerate(keep_pairs):
         n_pairs = len(norm)
         opts = gates = knn = None
@@ -1043,13 +1055,26 @@ def icp_align_layers_batch(jobs, T_guesses, params, priors=None, pairings_per_po
             for k, v in enumerate(np.broadcast_to(np.asarray(pairings_per_point[i]), (n_pairs,))):
                 knn[k].pairings_per_point = int(v)
         keep_opts.append((opts, gates, knn))
+        planes = None
+        if any(e.get("plane") for e in norm):
+            planes = (LayerPairPlane * max(1, n_pairs))()
+            for k, e in enumerate(norm):
+                q = e.get("plane")
+                if q:
+                    planes[k] = LayerPairPlane(int(q["knn"]), int(q["minimum_plane_points"]), float(q["plane_eigen_threshold"]),
+                                               float(q["search_radius"]))
+        keep_planes.append(planes)
     with_opts = any(o is not None for t in keep_opts for o in t)
-    jarr = ((LayerJobOpts if with_opts else LayerJob) * max(1, n))()
+    with_planes = bool(planes_entry) or any(q is not None for q in keep_planes)
+    with_opts = with_opts or with_planes
+    jarr = ((LayerJobPlanes if with_planes else LayerJobOpts if with_opts else LayerJob) * max(1, n))()
     for i, (arr, norm, thr_keep) in enumerate(keep_pairs):
         jarr[i].n_pairs = len(norm)
         jarr[i].pairs = arr
         if with_opts:
             jarr[i].opts, jarr[i].gates, jarr[i].knn = keep_opts[i]  # (None: NULL)
+        if with_planes:
+            jarr[i].planes = keep_planes[i]
     pr_arr, keep_pr = None, []
     if priors is not None:
         pr_arr = (C.POINTER(Prior) * max(1, n))()
@@ -1059,7 +1084,8 @@ def icp_align_layers_batch(jobs, T_guesses, params, priors=None, pairings_per_po
                 pr_arr[i] = C.pointer(keep_pr[-1])
     res = (ICPResult * max(1, n))()
     counts = (C.c_uint64 * (max(1, n) * MAX_LAYER_PAIRS))()
-    call = lib().mh_icp_align_layers_batch_opts if with_opts else lib().mh_icp_align_layers_batch
+    call = (lib().mh_icp_align_layers_batch_planes if with_planes
+            else lib().mh_icp_align_layers_batch_opts if with_opts else lib().mh_icp_align_layers_batch)
     _chk(call(n, jarr, cp_ref, 1 if per_job else 0, T.ctypes.data_as(_DP), pr_arr, res, counts))
     out = []
     for i in range(n):

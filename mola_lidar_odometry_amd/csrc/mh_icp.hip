@@ -19,7 +19,7 @@
 //   mh_icp_job.inl                 what AlignJob and LayersJob share: result / state / solver set-up, graph cache, result read-back
 //   mh_k_layers.h, mh_k_claim.h, mh_k_match_kbest.h, mh_k_match_planes.h
 //                                  the multi-layer loop's kernels: pair table, unique pairs, pairingsPerPoint > 1, plane pairs (KNN + PCA)
-//   mh_icp_layers.inl, mh_icp_layers_batch.inl   LayersJob, mh_icp_align_layers(_planes), mh_icp_align_layers_batch(_opts)
+//   mh_icp_layers.inl, mh_icp_layers_batch.inl   LayersJob, mh_icp_align_layers(_planes), mh_icp_align_layers_batch(_opts, _planes)
 //   mh_icp_batch.inl               mh_icp_align_batch (lock-step groups)
 //   mh_icp_api.inl                 matcher- / solver-granular entry points (mh_nn_search*, mh_gn_solve, mh_covariance)
 //   mh_dev_variants.h              (-DMH_DEV_VARIANTS only) the tile / wave / sorted-scan matchers that lost to the product kernels

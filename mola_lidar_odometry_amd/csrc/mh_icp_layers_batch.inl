@@ -9,6 +9,10 @@
 // k_match_layers_b when a job has a pair with k > 1, and k_claim_layers_b -> k_resolve_layers_b before the first accumulation when
 // a job has a unique pair.  A group of the k > 1 kind accumulates through k_accum_layers_kb / k_cov_accum_layers_kb, as the single
 // call chooses the *_k entry points.  Gates are data of the jobs' tables.  A group without any of it issues what it always issued.
+// mh_icp_align_layers_batch_planes: the same with every job's Matcher_Point2Plane pairs (what mh_icp_align_layers_planes takes).
+// Plane jobs form groups of their own.  Such a group uploads a LayerBatchPlaneTable (mh_k_match_planes.h) behind the other tables,
+// enqueues k_match_layers_pl_b behind the other searches and k_accum_layers_pl_b behind every point accumulation, and its solve
+// and covariance finalisation are k_solve_pl_b / k_cov_finalize_pl_b, which add each job's second partials block behind its first.
 // Loop control is align_batch_run's chunked one on the lead job's stream.  The chunks are launched directly, NOT replayed from a
 // captured graph: a group's composition changes from batch to batch as sequences end, and a chunk is 1 + 2 * inner launches per
 // iteration for ALL jobs where the single calls issue that many each.
@@ -23,22 +27,28 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
   MH_TRY(order_after_layers_job_streams(lead, g));
   // [gathered states] | job descriptors of the solve / covariance kernels | the (job, pair) table: pinned mirror and device copy
   // ... and, in a group with a unique pair or a pair of k > 1, the jobs' claim / k-best tables and ranges behind it
-  bool with_opts = false, kbest = false;
+  // ... and, in a group of plane jobs, their plane tables, second partials blocks and ranges behind that
+  bool with_opts = false, kbest = false, planes = false;
   for (const LayersJob* j : g) {
     with_opts = with_opts || j->L.unique_mask || j->L.knn_key;
     kbest = kbest || j->L.knn_key;
+    planes = planes || j->L.plane_key;
   }
-  const size_t tab_bytes = sizeof(LayerBatchTable) + (with_opts ? sizeof(LayerBatchOptTable) : 0);
+  const size_t opt_bytes = with_opts ? sizeof(LayerBatchOptTable) : 0;
+  const size_t tab_bytes = sizeof(LayerBatchTable) + opt_bytes + (planes ? sizeof(LayerBatchPlaneTable) : 0);
   const size_t desc_bytes = A * sizeof(BatchJob) + tab_bytes;
   IcpDeviceState* h_states = nullptr;
   BatchJob* h_desc = nullptr;
   MH_TRY(reserve_group_buffers(lead, A, tab_bytes, h_states, h_desc));
   LayerBatchTable* const h_tab = reinterpret_cast<LayerBatchTable*>(h_desc + A);
   LayerBatchOptTable* const h_opt = with_opts ? reinterpret_cast<LayerBatchOptTable*>(h_tab + 1) : nullptr;
-  static_assert(sizeof(LayerBatchTable) % 8 == 0, "staging layout");
+  LayerBatchPlaneTable* const h_pl =
+      planes ? reinterpret_cast<LayerBatchPlaneTable*>(reinterpret_cast<char*>(h_tab + 1) + opt_bytes) : nullptr;
+  static_assert(sizeof(LayerBatchTable) % 8 == 0 && sizeof(LayerBatchOptTable) % 8 == 0, "staging layout");
   memset(h_desc, 0, desc_bytes);
   h_tab->n_jobs = A;
-  uint32_t tot_match = 0, tot_acc = 0, tot_cov = 0, tot_claim = 0, tot_match_k = 0, max_iterations = 0, chunk = 0;
+  uint32_t tot_match = 0, tot_acc = 0, tot_cov = 0, tot_claim = 0, tot_match_k = 0, tot_match_pl = 0, tot_acc_pl = 0;
+  uint32_t max_iterations = 0, chunk = 0;
   const mh_icp_params* const p0 = g[0]->p;
   const uint32_t inner = p0->gn.max_inner_iterations;
   const bool cov = p0->compute_covariance != 0, auto_chunk = p0->poll_every == 0;
@@ -58,6 +68,15 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
       tot_match_k += j.L.tot_match_k;
       h_opt->j[a].claims = j.L.unique_mask ? reinterpret_cast<const ClaimTable*>(dbase + j.L.claim_off) : nullptr;
       h_opt->j[a].knn = j.L.knn_key ? reinterpret_cast<const KnnTable*>(dbase + j.L.knn_off) : nullptr;
+    }
+    if (h_pl) {  // (a job without plane points owns no workgroup of the plane launches, and its solve reads no second block)
+      h_pl->job_blk_match[a] = tot_match_pl;
+      h_pl->job_blk_acc[a] = tot_acc_pl;
+      tot_match_pl += j.L.tot_match_pl;
+      tot_acc_pl += j.L.tot_acc_pl;
+      h_pl->j[a].planes = j.L.plane_key ? reinterpret_cast<const PlaneTable*>(j.ctx->layers_tab.as<char>() + j.L.plane_off) : nullptr;
+      h_pl->j[a].partb = j.L.tot_acc_pl ? j.ctx->partials_b.as<double>() : nullptr;
+      h_pl->j[a].tot_acc_pl = j.L.tot_acc_pl;
     }
     LayerBatchJob& t = h_tab->j[a];
     t.tab = j.ctx->layers_tab.as<LayerTable>();
@@ -83,35 +102,48 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
     h_opt->job_blk_claim[A] = tot_claim;
     h_opt->job_blk_match_k[A] = tot_match_k;
   }
+  if (h_pl) {
+    h_pl->job_blk_match[A] = tot_match_pl;
+    h_pl->job_blk_acc[A] = tot_acc_pl;
+  }
   MH_HIP(hipMemcpyAsync(lead->batch_desc.p, h_desc, desc_bytes, hipMemcpyHostToDevice, s));
   const BatchJob* const dj = lead->batch_desc.as<BatchJob>();
   const LayerBatchTable* const dt = reinterpret_cast<const LayerBatchTable*>(dj + A);
   const LayerBatchOptTable* const dopt = reinterpret_cast<const LayerBatchOptTable*>(dt + 1);  // (read in a group with such a job only)
+  // (read in a group of plane jobs only)
+  const LayerBatchPlaneTable* const dpl =
+      reinterpret_cast<const LayerBatchPlaneTable*>(reinterpret_cast<const char*>(dt + 1) + opt_bytes);
   // (a group of the k > 1 kind: the entry points that take the local point of an entry from its k, as align_layers chooses them)
   const auto accum = kbest ? k_accum_layers_kb : k_accum_layers_b;
   const auto cov_accum = kbest ? k_cov_accum_layers_kb : k_cov_accum_layers_b;
+  // one inner step: the point rows, the plane rows, the solve over both blocks (a group without plane jobs: k_solve_b as ever)
+  auto step = [&](uint32_t first) {
+    if (tot_acc) hipLaunchKernelGGL(accum, dim3(tot_acc), dim3(kBlock), 0, s, dt, first);
+    if (tot_acc_pl) hipLaunchKernelGGL(k_accum_layers_pl_b, dim3(tot_acc_pl), dim3(kBlock), 0, s, dt, dpl, first);
+    if (planes) hipLaunchKernelGGL(k_solve_pl_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj, dpl, first);
+    else hipLaunchKernelGGL(k_solve_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj, first);
+  };
   uint32_t enqueued = 0, polls = 0;
   for (;;) {
     const uint32_t m = (max_iterations - enqueued) < chunk ? (max_iterations - enqueued) : chunk;
     for (uint32_t it = 0; it < m; it++) {
-      // (a launch without workgroups is skipped: every pair of the group with k > 1, nobody unique)
+      // (a launch without workgroups is skipped: every pair of the group with k > 1 or a plane pair, nobody unique, no point pair)
       if (tot_match) hipLaunchKernelGGL(k_match_layers_b, dim3(tot_match), dim3(kFlatThreads), 0, s, dt);
       if (tot_match_k) hipLaunchKernelGGL(k_match_layers_kb, dim3(tot_match_k), dim3(kFlatThreads), 0, s, dt, dopt);
+      if (tot_match_pl) hipLaunchKernelGGL(k_match_layers_pl_b, dim3(tot_match_pl), dim3(kFlatThreads), 0, s, dt, dpl);
       if (tot_claim) {
         hipLaunchKernelGGL(k_claim_layers_b, dim3(tot_claim), dim3(kBlock), 0, s, dt, dopt);
         hipLaunchKernelGGL(k_resolve_layers_b, dim3(tot_claim), dim3(kBlock), 0, s, dt, dopt);
       }
-      hipLaunchKernelGGL(accum, dim3(tot_acc), dim3(kBlock), 0, s, dt, 1u);
-      hipLaunchKernelGGL(k_solve_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj, 1u);
-      for (uint32_t in = 1; in < inner; in++) {
-        hipLaunchKernelGGL(accum, dim3(tot_acc), dim3(kBlock), 0, s, dt, 0u);
-        hipLaunchKernelGGL(k_solve_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj, 0u);
-      }
+      step(1u);
+      for (uint32_t in = 1; in < inner; in++) step(0u);
     }
     if (cov) {  // no-ops for jobs whose loop has not terminated
       hipLaunchKernelGGL(k_cov_prepare_b, dim3(1, A), dim3(64), 0, s, dj);
-      hipLaunchKernelGGL(cov_accum, dim3(tot_cov), dim3(kBlock), 0, s, dt);
-      hipLaunchKernelGGL(k_cov_finalize_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj);
+      if (tot_cov) hipLaunchKernelGGL(cov_accum, dim3(tot_cov), dim3(kBlock), 0, s, dt);
+      if (tot_acc_pl) hipLaunchKernelGGL(k_cov_accum_layers_pl_b, dim3(tot_acc_pl), dim3(kBlock), 0, s, dt, dpl);
+      if (planes) hipLaunchKernelGGL(k_cov_finalize_pl_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj, dpl);
+      else hipLaunchKernelGGL(k_cov_finalize_b, dim3(1, A), dim3(kSolveThreads), 0, s, dj);
     }
     MH_TRY(gather_states(lead, dj, A, h_states));
     enqueued += m;
@@ -132,14 +164,19 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
 }
 
 // (pair k of a job: its options, the defaults where the job has no such array)
-static inline uint32_t job_kpp(const mh_layer_job_opts& j, size_t k) {
+static inline uint32_t job_kpp(const mh_layer_job_planes& j, size_t k) {
   return j.knn && j.knn[k].pairings_per_point ? j.knn[k].pairings_per_point : 1u;
 }
-static inline bool job_unique(const mh_layer_job_opts& j, size_t k) { return j.opts && j.opts[k].unique_global; }
+static inline bool job_unique(const mh_layer_job_planes& j, size_t k) { return j.opts && j.opts[k].unique_global; }
+static inline bool job_has_plane(const mh_layer_job_planes& j) {
+  bool any = false;
+  for (size_t k = 0; j.planes && k < j.n_pairs; k++) any = any || j.planes[k].knn != 0u;
+  return any;
+}
 
-mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts* jobs, const mh_icp_params* params,
-                                         int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
-                                         mh_icp_result* results, uint64_t* final_pair_counts) {
+mh_status mh_icp_align_layers_batch_planes(size_t n_jobs, const mh_layer_job_planes* jobs, const mh_icp_params* params,
+                                           int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
+                                           mh_icp_result* results, uint64_t* final_pair_counts) {
   MH_REQUIRE(n_jobs >= 1 && n_jobs <= MH_MAX_LAYER_BATCH_JOBS, "n_jobs must be 1 .. MH_MAX_LAYER_BATCH_JOBS");
   MH_REQUIRE(jobs && params && T_guesses && results, "null argument");
   auto P = [&](size_t i) { return params_per_job ? &params[i] : params; };
@@ -151,6 +188,7 @@ mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts*
     MH_REQUIRE(jobs[i].pairs[0].scan->ctx->device == jobs[0].pairs[0].scan->ctx->device, "the jobs of a batch live on different devices");
     for (size_t k = 0; jobs[i].knn && k < jobs[i].n_pairs; k++)
       MH_REQUIRE(jobs[i].knn[k].pairings_per_point <= MH_MAX_PAIRINGS_PER_POINT, "pairings_per_point must be 0 .. MH_MAX_PAIRINGS_PER_POINT");
+    MH_TRY(check_layers_planes(jobs[i].n_pairs, jobs[i].pairs, jobs[i].opts, jobs[i].knn, jobs[i].planes, P(i)));
   }
   for (size_t i = 0; i < n_jobs; i++) {
     MH_TRY(check_layers_supported(jobs[i].n_pairs, jobs[i].pairs, P(i)));
@@ -170,10 +208,13 @@ mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts*
   }
   const Switches sw = read_switches();
   auto counts_of = [&](size_t i) { return final_pair_counts ? final_pair_counts + i * MH_MAX_LAYER_PAIRS : nullptr; };
+  // (as mh_icp_align_layers_planes hands them on: an array without a plane pair is no array)
+  auto planes_of = [&](size_t i) { return job_has_plane(jobs[i]) ? jobs[i].planes : nullptr; };
   if (final_pair_counts)
     for (size_t i = 0; i < n_jobs * MH_MAX_LAYER_PAIRS; i++) final_pair_counts[i] = 0;
-  // lock-step groups: same inner steps, same covariance switch, and a pair with k > 1 or none (the launches of a chunk are the same
-  // for every job of a group; unique pairs and gates do not change them: a job without a unique pair owns no claim workgroup)
+  // lock-step groups: same inner steps, same covariance switch, a pair with k > 1 or none, and a plane pair or none (the launches of
+  // a chunk are the same for every job of a group; unique pairs and gates do not change them: a job without a unique pair owns no
+  // claim workgroup)
   auto has_kbest = [&](size_t i) {
     bool any = false;
     for (size_t k = 0; k < jobs[i].n_pairs; k++) any = any || job_kpp(jobs[i], k) > 1u;
@@ -193,7 +234,8 @@ mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts*
       std::vector<size_t>* g = nullptr;
       for (auto& c : groups)
         if (P(c[0])->gn.max_inner_iterations == q->gn.max_inner_iterations &&
-            (P(c[0])->compute_covariance != 0) == (q->compute_covariance != 0) && has_kbest(c[0]) == has_kbest(i))
+            (P(c[0])->compute_covariance != 0) == (q->compute_covariance != 0) && has_kbest(c[0]) == has_kbest(i) &&
+            job_has_plane(jobs[c[0]]) == job_has_plane(jobs[i]))
           g = &c;
       if (!g) {
         groups.emplace_back();
@@ -210,7 +252,7 @@ mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts*
     std::vector<LayersJob*> g;
     for (size_t i : c) {
       MH_TRY(lj[i].start(sw, (uint32_t)jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr,
-                         &results[i], nullptr, counts_of(i), jobs[i].opts, jobs[i].gates, jobs[i].knn));
+                         &results[i], nullptr, counts_of(i), jobs[i].opts, jobs[i].gates, jobs[i].knn, planes_of(i)));
       g.push_back(&lj[i]);
     }
     MH_TRY(align_layers_lockstep(g));
@@ -219,8 +261,21 @@ mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts*
   for (size_t i = 0; i < n_jobs; i++)
     if (!in_group[i])
       MH_TRY(align_layers(sw, (uint32_t)jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr,
-                          &results[i], nullptr, nullptr, counts_of(i), MH_MEM_HOST, jobs[i].opts, jobs[i].gates, jobs[i].knn));
+                          &results[i], nullptr, nullptr, counts_of(i), MH_MEM_HOST, jobs[i].opts, jobs[i].gates, jobs[i].knn,
+                          planes_of(i)));
   return MH_OK;
+}
+
+// (the shared implementation with no planes: the checks, the groups, the uploads and the launches it always had)
+mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts* jobs, const mh_icp_params* params,
+                                         int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
+                                         mh_icp_result* results, uint64_t* final_pair_counts) {
+  MH_REQUIRE(n_jobs >= 1 && n_jobs <= MH_MAX_LAYER_BATCH_JOBS, "n_jobs must be 1 .. MH_MAX_LAYER_BATCH_JOBS");
+  MH_REQUIRE(jobs, "null argument");
+  mh_layer_job_planes jp[MH_MAX_LAYER_BATCH_JOBS];
+  for (size_t i = 0; i < n_jobs; i++)
+    jp[i] = mh_layer_job_planes{jobs[i].n_pairs, jobs[i].pairs, jobs[i].opts, jobs[i].gates, jobs[i].knn, nullptr};
+  return mh_icp_align_layers_batch_planes(n_jobs, jp, params, params_per_job, T_guesses, priors, results, final_pair_counts);
 }
 
 // (the shared implementation with no opts, gates or knn: the checks, the groups, the uploads and the launches it always had)

@@ -20,7 +20,8 @@
 // it writes in a single call (stride: the job's total), so k_solve_b / k_cov_finalize_b (a workgroup per job: mh_k_launch.h) add
 // the same numbers in the same order and every job ends with the bits of its single call.
 // (mh_icp_align_layers_batch_opts: the claim / resolve and k-best entry points of a group, and the table that lets their
-// workgroups find (job -> pair), are mh_k_claim.h's and mh_k_match_kbest.h's.)
+// workgroups find (job -> pair), are mh_k_claim.h's and mh_k_match_kbest.h's; mh_icp_align_layers_batch_planes: the plane entry
+// points of a group and their table are mh_k_match_planes.h's.)
 #pragma once
 
 struct LayerDesc {

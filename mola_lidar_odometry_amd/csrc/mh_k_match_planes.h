@@ -26,6 +26,8 @@
 // Launches: k_match_layers_pl walks a flattened range over the plane pairs only (PlaneTable) and is enqueued only when one
 // exists; k_accum_layers_pl writes their Gauss-Newton rows into columns of the SECOND partials block that k_solve sums in fixed
 // order behind the first, k_cov_accum_layers_pl likewise for the covariance.  The plain kernels stay the code objects they are.
+// Lock-step batches (mh_icp_align_layers_batch_planes): the three bodies are __device__ functions that the *_pl_b entry points at
+// the end of this file call too, one level up (job -> pair); k_solve_pl_b / k_cov_finalize_pl_b sum each job's two blocks.
 #pragma once
 
 namespace mh {
@@ -197,15 +199,10 @@ struct PlaneTable {
 };
 typedef const PlaneTable __attribute__((address_space(4))) * cplanes_ptr;
 
-__global__ __launch_bounds__(kFlatThreads) void k_match_layers_pl(const IcpDeviceState* __restrict__ st,
-                                                                  const LayerTable* __restrict__ tab,
-                                                                  const PlaneTable* __restrict__ planes) {
-  __shared__ mh::FlatWaveP shp[kFlatThreads / 64];
-  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
-  if (cst->done) return;  // grid-uniform
-  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
-  const cplanes_ptr cp = (cplanes_ptr)uniform_const_ptr(planes);
-  const uint32_t b = blockIdx.x;
+// one wave of k_match_layers_pl: workgroup `b` of the table's flattened plane-search range (`cst`: the alignment's state, not
+// terminated)
+__device__ __forceinline__ void match_layers_pl_wave(mh::FlatWaveP& sh, const clayers_state_ptr cst, const clayers_ptr ct,
+                                                     const cplanes_ptr cp, const uint32_t b) {
   const uint32_t li = layer_of(cp->blk_match, ct->n_pairs, b);
   const uint32_t n = ct->d[li].n;
   const uint32_t i0 = (b - cp->blk_match[li]) * kFlatPointsPerBlock + (threadIdx.x & ~63u);
@@ -243,23 +240,29 @@ __global__ __launch_bounds__(kFlatThreads) void k_match_layers_pl(const IcpDevic
   a.radius2 = cp->d[li].radius2;
   a.knn = cp->d[li].knn;
   a.min_pts = cp->d[li].min_pts;
-  mh::match_planes_wave(shp[threadIdx.x >> 6], map, T, a, have_prev, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, n, i0,
-                        ct->d[li].pair_q, cp->d[li].pl_c, cp->d[li].pl_n);
+  mh::match_planes_wave(sh, map, T, a, have_prev, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, n, i0, ct->d[li].pair_q, cp->d[li].pl_c,
+                        cp->d[li].pl_n);
+}
+
+__global__ __launch_bounds__(kFlatThreads) void k_match_layers_pl(const IcpDeviceState* __restrict__ st,
+                                                                  const LayerTable* __restrict__ tab,
+                                                                  const PlaneTable* __restrict__ planes) {
+  __shared__ mh::FlatWaveP shp[kFlatThreads / 64];
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
+  if (cst->done) return;  // grid-uniform
+  match_layers_pl_wave(shp[threadIdx.x >> 6], cst, (clayers_ptr)uniform_const_ptr(tab), (cplanes_ptr)uniform_const_ptr(planes),
+                       blockIdx.x);
 }
 
 // the Gauss-Newton rows of the plane pairs' stored pairings (acc_pt2pl_rows with the iteration's robust kernel and the pair's
-// weight), a point per lane, into the pair's columns of the second partials block
-__global__ __launch_bounds__(kBlock) void k_accum_layers_pl(const IcpDeviceState* __restrict__ st, const LayerTable* __restrict__ tab,
-                                                            const PlaneTable* __restrict__ planes, uint32_t first,
-                                                            double* __restrict__ partials, uint32_t pstride) {
-  __shared__ BlockSum<kGenN> lds;
-  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
-  if (cst->done) return;
+// weight), a point per lane, into the pair's columns of the second partials block: workgroup `b` of the table's flattened plane
+// accumulation range (`cst`: the alignment's state, not terminated; `partials`, `pstride`: the alignment's second block)
+__device__ __forceinline__ void accum_layers_pl_block(BlockSum<kGenN>& lds, const clayers_state_ptr cst, const clayers_ptr ct,
+                                                      const cplanes_ptr cp, const uint32_t first, double* __restrict__ partials,
+                                                      const uint32_t pstride, const uint32_t b) {
   if (!first && cst->inner == 0) return;  // the previous solve already closed this ICP iteration
-  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
-  const cplanes_ptr cp = (cplanes_ptr)uniform_const_ptr(planes);
-  const uint32_t li = layer_of(cp->blk_acc, ct->n_pairs, blockIdx.x);
-  const uint32_t bx = blockIdx.x - cp->blk_acc[li];
+  const uint32_t li = layer_of(cp->blk_acc, ct->n_pairs, b);
+  const uint32_t bx = b - cp->blk_acc[li];
   double T[12];
 #pragma unroll
   for (int j = 0; j < 12; j++) T[j] = cst->T[j];
@@ -277,13 +280,104 @@ __global__ __launch_bounds__(kBlock) void k_accum_layers_pl(const IcpDeviceState
   block_sum_rows<kGenN>(v, lds, partials + cp->blk_acc[li], pstride, bx);
 }
 
+__global__ __launch_bounds__(kBlock) void k_accum_layers_pl(const IcpDeviceState* __restrict__ st, const LayerTable* __restrict__ tab,
+                                                            const PlaneTable* __restrict__ planes, uint32_t first,
+                                                            double* __restrict__ partials, uint32_t pstride) {
+  __shared__ BlockSum<kGenN> lds;
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(st);
+  if (cst->done) return;
+  accum_layers_pl_block(lds, cst, (clayers_ptr)uniform_const_ptr(tab), (cplanes_ptr)uniform_const_ptr(planes), first, partials,
+                        pstride, blockIdx.x);
+}
+
+// ... and their covariance rows (an alignment still running, or whose covariance is done, leaves inside the body)
+__device__ __forceinline__ void cov_accum_layers_pl_block(const IcpDeviceState* __restrict__ st, const clayers_ptr ct,
+                                                          const cplanes_ptr cp, double* __restrict__ partials, const uint32_t pstride,
+                                                          const uint32_t b) {
+  const uint32_t li = layer_of(cp->blk_cov, ct->n_pairs, b);
+  k_cov_accum_plbuf_body(st, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n, cp->d[li].pl_c, cp->d[li].pl_n,
+                         partials + cp->blk_cov[li], pstride, b - cp->blk_cov[li]);
+}
+
 __global__ __launch_bounds__(kBlock) void k_cov_accum_layers_pl(const IcpDeviceState* __restrict__ st,
                                                                 const LayerTable* __restrict__ tab,
                                                                 const PlaneTable* __restrict__ planes, double* __restrict__ partials,
                                                                 uint32_t pstride) {
-  const clayers_ptr ct = (clayers_ptr)uniform_const_ptr(tab);
-  const cplanes_ptr cp = (cplanes_ptr)uniform_const_ptr(planes);
-  const uint32_t li = layer_of(cp->blk_cov, ct->n_pairs, blockIdx.x);
-  k_cov_accum_plbuf_body(st, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, ct->d[li].n, cp->d[li].pl_c, cp->d[li].pl_n,
-                         partials + cp->blk_cov[li], pstride, blockIdx.x - cp->blk_cov[li]);
+  cov_accum_layers_pl_block(st, (clayers_ptr)uniform_const_ptr(tab), (cplanes_ptr)uniform_const_ptr(planes), partials, pstride,
+                            blockIdx.x);
+}
+
+// ---- lock-step batches (mh_icp_align_layers_batch_planes) ------------------------------------------------------------------------
+// What the plane launches of a group need beside its LayerBatchTable (mh_k_layers.h), job by job in that table's order: the job's
+// PlaneTable and second partials block in its own context's memory, that block's columns (= its stride = the job's workgroups in
+// the plane accumulation and covariance launches), and the jobs' first workgroups in the two flattened grids (a plane pair's
+// covariance range is its accumulation range).  A job without plane points owns no workgroup of these launches.  A table of its
+// own, uploaded behind the LayerBatchTable / LayerBatchOptTable only for a group of plane jobs.
+struct LayerBatchPlaneJob {
+  const PlaneTable* planes;
+  double* partb;
+  uint32_t tot_acc_pl, pad;
+};
+
+struct LayerBatchPlaneTable {
+  uint32_t job_blk_match[MH_MAX_LAYER_BATCH_JOBS + 1];  // k_match_layers_pl_b (+ the total)
+  uint32_t job_blk_acc[MH_MAX_LAYER_BATCH_JOBS + 1];    // k_accum_layers_pl_b / k_cov_accum_layers_pl_b
+  LayerBatchPlaneJob j[MH_MAX_LAYER_BATCH_JOBS];
+};
+
+typedef const LayerBatchPlaneTable __attribute__((address_space(4))) * clayer_batch_plane_ptr;
+
+// The three kernels above one level up, as k_match_layers_kb is k_match_layers_k: the job by layer_of over the jobs' prefix
+// array, out when it has terminated (nothing of its pl_c / pl_n / pair_q is touched), then the body on the job's own tables,
+// state, iteration counter and second partials block with the single call's columns and stride.
+__global__ __launch_bounds__(kFlatThreads) void k_match_layers_pl_b(const LayerBatchTable* __restrict__ bt,
+                                                                    const LayerBatchPlaneTable* __restrict__ bp) {
+  __shared__ mh::FlatWaveP shp[kFlatThreads / 64];
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const clayer_batch_plane_ptr cq = (clayer_batch_plane_ptr)uniform_const_ptr(bp);
+  const uint32_t ji = layer_of(cq->job_blk_match, cb->n_jobs, blockIdx.x);
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(cb->j[ji].st);
+  if (cst->done) return;  // uniform over the job's workgroups
+  match_layers_pl_wave(shp[threadIdx.x >> 6], cst, (clayers_ptr)uniform_const_ptr(cb->j[ji].tab),
+                       (cplanes_ptr)uniform_const_ptr(cq->j[ji].planes), blockIdx.x - cq->job_blk_match[ji]);
+}
+
+__global__ __launch_bounds__(kBlock) void k_accum_layers_pl_b(const LayerBatchTable* __restrict__ bt,
+                                                              const LayerBatchPlaneTable* __restrict__ bp, uint32_t first) {
+  __shared__ BlockSum<kGenN> lds;
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const clayer_batch_plane_ptr cq = (clayer_batch_plane_ptr)uniform_const_ptr(bp);
+  const uint32_t ji = layer_of(cq->job_blk_acc, cb->n_jobs, blockIdx.x);
+  const clayers_state_ptr cst = (clayers_state_ptr)uniform_const_ptr(cb->j[ji].st);
+  if (cst->done) return;  // uniform over the job's workgroups
+  accum_layers_pl_block(lds, cst, (clayers_ptr)uniform_const_ptr(cb->j[ji].tab), (cplanes_ptr)uniform_const_ptr(cq->j[ji].planes),
+                        first, cq->j[ji].partb, cq->j[ji].tot_acc_pl, blockIdx.x - cq->job_blk_acc[ji]);
+}
+
+__global__ __launch_bounds__(kBlock) void k_cov_accum_layers_pl_b(const LayerBatchTable* __restrict__ bt,
+                                                                  const LayerBatchPlaneTable* __restrict__ bp) {
+  const clayer_batch_ptr cb = (clayer_batch_ptr)uniform_const_ptr(bt);
+  const clayer_batch_plane_ptr cq = (clayer_batch_plane_ptr)uniform_const_ptr(bp);
+  const uint32_t ji = layer_of(cq->job_blk_acc, cb->n_jobs, blockIdx.x);
+  cov_accum_layers_pl_block(cb->j[ji].st, (clayers_ptr)uniform_const_ptr(cb->j[ji].tab),
+                            (cplanes_ptr)uniform_const_ptr(cq->j[ji].planes), cq->j[ji].partb, cq->j[ji].tot_acc_pl,
+                            blockIdx.x - cq->job_blk_acc[ji]);
+}
+
+// k_solve_b / k_cov_finalize_b for a group of plane jobs: each job's second block behind its first, in the single call's fixed
+// order (k_solve_body / k_cov_finalize_body with partB, nB, nB).  Entry points of their own: k_solve_b and k_cov_finalize_b as
+// every other batch launches them read what they always read.
+__global__ __launch_bounds__(kSolveThreads) void k_solve_pl_b(const BatchJob* __restrict__ jobs,
+                                                              const LayerBatchPlaneTable* __restrict__ bp, uint32_t first) {
+  const BatchJob& j = jobs[blockIdx.y];
+  const uint32_t cols = first ? j.nbm : j.nba;
+  const uint32_t nB = bp->j[blockIdx.y].tot_acc_pl;
+  k_solve_body(j.st, j.sk, j.part, cols, cols, nB ? bp->j[blockIdx.y].partb : nullptr, nB, nB, first);
+}
+
+__global__ __launch_bounds__(kSolveThreads) void k_cov_finalize_pl_b(const BatchJob* __restrict__ jobs,
+                                                                     const LayerBatchPlaneTable* __restrict__ bp) {
+  const BatchJob& j = jobs[blockIdx.y];
+  const uint32_t nB = bp->j[blockIdx.y].tot_acc_pl;
+  k_cov_finalize_body(j.st, 0u, j.part, j.nb, j.nb, nB ? bp->j[blockIdx.y].partb : nullptr, nB, nB);
 }

@@ -28,6 +28,9 @@
 //                                                     pair, a gate or pairingsPerPoint > 1 join the lock-step batches
 //                                                     (mh_icp_align_layers_batch_opts); 0: each runs on its own beside them
 //                                                     (AlignBatcher::runOutside), as before that entry point existed
+//   MOLA_HIP_BATCH_PLANES     1 | 0                   (host layer with an AlignBatcher only) multi-layer alignments with a
+//                                                     Matcher_Point2Plane pair join the lock-step batches
+//                                                     (mh_icp_align_layers_batch_planes); 0: each runs on its own beside them
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +53,7 @@ struct PluginSwitches {
   int fuse_kbest = -1;  // MOLA_HIP_FUSE_KBEST: the same for pairingsPerPoint > 1
   int fuse_planes = -1; // MOLA_HIP_FUSE_PLANES: the same for Matcher_Point2Plane on point layers
   bool batch_opts = true;  // MOLA_HIP_BATCH_OPTS: unique / gated / k-best multi-layer alignments join the AlignBatcher's batches
+  bool batch_planes = true;  // MOLA_HIP_BATCH_PLANES: the same for alignments with a Matcher_Point2Plane pair
   // which of them came from the environment (the mirror classes only override their YAML values for those)
   bool has_gm_form = false, has_index_mode = false, has_cov_step = false, has_min_delta = false, has_max_cost = false,
        has_pt2pl_mode = false, has_far_metric = false;
@@ -106,6 +110,7 @@ inline PluginSwitches read_plugin_switches() {
   if (const char* e = getenv("MOLA_HIP_FUSE_KBEST")) s.fuse_kbest = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("MOLA_HIP_FUSE_PLANES")) s.fuse_planes = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("MOLA_HIP_BATCH_OPTS")) s.batch_opts = atoi(e) != 0;
+  if (const char* e = getenv("MOLA_HIP_BATCH_PLANES")) s.batch_planes = atoi(e) != 0;
   return s;
 }
 

@@ -392,7 +392,7 @@ class QualityEvaluator_PairedRatio {
 // mh_icp_align it hands its request to the batcher and blocks; when ALL active participants are waiting, the last one
 // to arrive runs ONE mh_icp_align_batch over the requests (per-job parameters: every sequence has its own adaptive
 // threshold, iteration budget, hook check point; jobs with the same kernel chain advance in lock step) -- and ONE
-// mh_icp_align_layers_batch over the multi-layer requests among them (mh_icp_align_layers_batch_opts when one of them has a unique pair, a gate or pairingsPerPoint > 1) -- and wakes the others.  Results are bitwise those of separate alignments, so every sequence's records are those of a solo run.
+// mh_icp_align_layers_batch over the multi-layer requests among them (mh_icp_align_layers_batch_opts when one of them has a unique pair, a gate or pairingsPerPoint > 1, mh_icp_align_layers_batch_planes when one has a Matcher_Point2Plane pair) -- and wakes the others.  Results are bitwise those of separate alignments, so every sequence's records are those of a solo run.
 class AlignBatcher {
  public:
   explicit AlignBatcher(size_t participants);
@@ -403,11 +403,12 @@ class AlignBatcher {
   // The same for a multi-layer alignment (mh_icp_align_layers; `pairs` all on the participant's own context): the multi-layer
   // requests of a batch run as ONE mh_icp_align_layers_batch beside the single-pair ones' mh_icp_align_batch.  `opts`, `gates`,
   // `knn`: what mh_icp_align_layers_kbest takes (n_pairs entries or null each); with one of them in any request of a batch the
-  // batch is ONE mh_icp_align_layers_batch_opts.
+  // batch is ONE mh_icp_align_layers_batch_opts.  `planes`: what mh_icp_align_layers_planes takes beside them; with it in any
+  // request the batch is ONE mh_icp_align_layers_batch_planes.
   mh_status alignLayers(const void* owner, size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params,
                         const double T_guess[12], const mh_prior* prior, mh_icp_result* result, std::string* error,
                         const mh_layer_pair_opts* opts = nullptr, const mh_layer_pair_gates* gates = nullptr,
-                        const mh_layer_pair_knn* knn = nullptr);
+                        const mh_layer_pair_knn* knn = nullptr, const mh_layer_pair_plane* planes = nullptr);
   // An alignment that has no batched form (the matcher/solver-granular loop): `fn` runs on the caller's thread at once, and
   // meanwhile the participant counts as one that is not waiting, so the others' batches are not held up for it.
   void runOutside(const void* owner, const std::function<void()>& fn);
@@ -464,6 +465,7 @@ class AlignBatcher {
     const mh_layer_pair_opts* opts = nullptr;    // ... and what mh_icp_align_layers_kbest takes beside them (null: none)
     const mh_layer_pair_gates* gates = nullptr;
     const mh_layer_pair_knn* knn = nullptr;
+    const mh_layer_pair_plane* planes = nullptr;  // ... and mh_icp_align_layers_planes
     const mh_icp_params* params = nullptr;
     const double* T = nullptr;
     const mh_prior* prior = nullptr;

@@ -755,7 +755,7 @@ void AlignBatcher::run_batch(std::vector<Request*>& batch) {
   std::vector<mh_status> sts(n, MH_OK);
   std::vector<std::string> errs(n);
   // the single-pair requests as one mh_icp_align_batch, the multi-layer ones as one mh_icp_align_layers_batch (_opts when one
-  // of them has a unique pair, a gate or pairingsPerPoint > 1)
+  // of them has a unique pair, a gate or pairingsPerPoint > 1, _planes when one has a Matcher_Point2Plane pair)
   for (const bool layers : {false, true}) {
     std::vector<size_t> idx;
     for (size_t i = 0; i < n; i++)
@@ -766,7 +766,8 @@ void AlignBatcher::run_batch(std::vector<Request*>& batch) {
     std::vector<const mh_scan*> scans(m);
     std::vector<mh_layer_job> jobs(m);
     std::vector<mh_layer_job_opts> jobs_opts(m);
-    bool any_opts = false;
+    std::vector<mh_layer_job_planes> jobs_planes(m);
+    bool any_opts = false, any_planes = false;
     std::vector<mh_icp_params> params(m);
     std::vector<double> T(12 * m);
     std::vector<const mh_prior*> priors(m);
@@ -780,19 +781,25 @@ void AlignBatcher::run_batch(std::vector<Request*>& batch) {
       jobs[k].pairs = rq.pairs;
       jobs_opts[k] = mh_layer_job_opts{rq.n_pairs, rq.pairs, rq.opts, rq.gates, rq.knn};
       any_opts = any_opts || rq.opts || rq.gates || rq.knn;
+      jobs_planes[k] = mh_layer_job_planes{rq.n_pairs, rq.pairs, rq.opts, rq.gates, rq.knn, rq.planes};
+      any_planes = any_planes || rq.planes;
       params[k] = *rq.params;
       memcpy(&T[12 * k], rq.T, 12 * sizeof(double));
       priors[k] = rq.prior;
       any_prior = any_prior || rq.prior;
     }
     auto one = [&](size_t k) {
-      return layers ? mh_icp_align_layers_kbest(jobs[k].n_pairs, jobs[k].pairs, jobs_opts[k].opts, jobs_opts[k].gates, jobs_opts[k].knn,
-                                                &params[k], &T[12 * k], priors[k], &res[k], nullptr, nullptr, nullptr, MH_MEM_HOST)
+      return layers ? mh_icp_align_layers_planes(jobs[k].n_pairs, jobs[k].pairs, jobs_opts[k].opts, jobs_opts[k].gates, jobs_opts[k].knn,
+                                                 jobs_planes[k].planes, &params[k], &T[12 * k], priors[k], &res[k], nullptr, nullptr,
+                                                 nullptr, nullptr, MH_MEM_HOST)
                     : mh_icp_align(maps[k], scans[k], &params[k], &T[12 * k], priors[k], &res[k], nullptr, nullptr, MH_MEM_HOST);
     };
     mh_status st = MH_OK;
     if (m == 1) {
       st = one(0);
+    } else if (layers && any_planes) {
+      st = mh_icp_align_layers_batch_planes(m, jobs_planes.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr,
+                                            res.data(), nullptr);
     } else if (layers && any_opts) {
       st = mh_icp_align_layers_batch_opts(m, jobs_opts.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr, res.data(),
                                           nullptr);
@@ -835,10 +842,11 @@ void AlignBatcher::run_batch(std::vector<Request*>& batch) {
 
 mh_status AlignBatcher::alignLayers(const void* owner, size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params,
                                     const double T_guess[12], const mh_prior* prior, mh_icp_result* result, std::string* error,
-                                    const mh_layer_pair_opts* opts, const mh_layer_pair_gates* gates, const mh_layer_pair_knn* knn) {
+                                    const mh_layer_pair_opts* opts, const mh_layer_pair_gates* gates, const mh_layer_pair_knn* knn,
+                                    const mh_layer_pair_plane* planes) {
   Request rq;
   rq.n_pairs = n_pairs; rq.pairs = pairs; rq.params = params; rq.T = T_guess; rq.prior = prior; rq.result = result;
-  rq.opts = opts; rq.gates = gates; rq.knn = knn;
+  rq.opts = opts; rq.gates = gates; rq.knn = knn; rq.planes = planes;
   // (no one-launch loops on the multi-layer path: nothing to ask the library; MOLA_HIP_BATCH_SOLO alone issues it at once)
   return submit(owner ? owner : (const void*)pairs, rq, solo_ ? 1 : 0, error);
 }
@@ -1363,7 +1371,8 @@ void ICP::align_fused(const PointCloud* host_local, const DevicePointCloud* dev_
 // The multi-layer shapes on the device loop (mh_icp_align_layers).  Pairs in align_generic's matching order: matchers in list
 // order, entries in pointLayerMatches order.  With a batcher set (and neither a trace nor the pairings wanted) the alignment joins
 // those of the other sequences: AlignBatcher::alignLayers, mh_icp_align_layers_batch -- with its unique pairs, gates and
-// pairings per point through mh_icp_align_layers_batch_opts (MOLA_HIP_BATCH_OPTS=0: such an alignment runs on its own instead).
+// pairings per point through mh_icp_align_layers_batch_opts (MOLA_HIP_BATCH_OPTS=0: such an alignment runs on its own instead),
+// with its Matcher_Point2Plane pairs through mh_icp_align_layers_batch_planes (MOLA_HIP_BATCH_PLANES=0: likewise).
 void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pcGlobal, const CPose3D& guess, const Parameters& p,
                              Results& result, const std::optional<CPose3DPDFGaussianInf>& prior) {
   const auto t_setup0 = std::chrono::steady_clock::now();
@@ -1492,8 +1501,9 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
                                      want_pairs ? po.data() : nullptr, (want_pairs && any_plane) ? ppl.data() : nullptr, counts.data(),
                                      MH_MEM_HOST), "mh_icp_align_layers_planes");
   };
-  if (batcher_ && any_plane) {
-    // (no lock-step form with plane pairs yet: on its own beside the batches, the participant counted as busy meanwhile)
+  if (batcher_ && any_plane && (!molahip_host::plugin_switches().batch_planes || !trace.empty() || want_pairs)) {
+    // (MOLA_HIP_BATCH_PLANES=0, the A/B against mh_icp_align_layers_batch_planes, or a trace / the pairings wanted: on its own
+    // beside the batches, the participant counted as busy meanwhile)
     batcher_->runOutside(batch_owner_, solo);
   } else if (batcher_ && (any_unique || any_gate || any_knn) && !molahip_host::plugin_switches().batch_opts) {
     // (MOLA_HIP_BATCH_OPTS=0, the A/B against mh_icp_align_layers_batch_opts: on its own, the participant counted as busy
@@ -1503,7 +1513,7 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
     std::string err;
     const mh_status st = batcher_->alignLayers(batch_owner_, pairs.size(), pairs.data(), &ip, guess.T, prior ? &pr : nullptr, &r, &err,
                                                any_unique ? opts.data() : nullptr, any_gate ? gates.data() : nullptr,
-                                               any_knn ? knn.data() : nullptr);
+                                               any_knn ? knn.data() : nullptr, any_plane ? planes.data() : nullptr);
     if (st != MH_OK) throw std::runtime_error(std::string("mh_icp_align_layers_batch: ") + mh_status_string(st) + ": " + err);
   } else {
     solo();
