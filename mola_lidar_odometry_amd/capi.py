@@ -908,6 +908,35 @@ def _layer_pairs(pairs, max_iterations):
     return arr, norm, thr_keep
 
 
+def _layer_pair_options(norm, pairings_per_point):
+    """(opts, gates, knn, planes) of one job: the mh_layer_pair_opts / _gates / _knn / _plane arrays of its normalised pair dicts
+    (unique_global; run_from_iteration, run_up_to_iteration; plane=dict(...)) and its pairings_per_point (None, one value for
+    every pair, or one per pair).  Each is None -- NULL to the library -- where the job sets no such option."""
+    n = max(1, len(norm))
+    opts = gates = knn = planes = None
+    if any(e.get("unique_global") for e in norm):
+        opts = (LayerPairOpts * n)()
+        for i, e in enumerate(norm):
+            opts[i].unique_global = 1 if e.get("unique_global") else 0
+    if any(e.get("run_from_iteration") or e.get("run_up_to_iteration") for e in norm):
+        gates = (LayerPairGates * n)()
+        for i, e in enumerate(norm):
+            gates[i].run_from_iteration = int(e.get("run_from_iteration") or 0)
+            gates[i].run_up_to_iteration = int(e.get("run_up_to_iteration") or 0)
+    if pairings_per_point is not None:
+        knn = (LayerPairKnn * n)()
+        for i, k in enumerate(np.broadcast_to(np.asarray(pairings_per_point), (len(norm),))):
+            knn[i].pairings_per_point = int(k)
+    if any(e.get("plane") for e in norm):
+        planes = (LayerPairPlane * n)()
+        for i, e in enumerate(norm):
+            q = e.get("plane")
+            if q:
+                planes[i] = LayerPairPlane(int(q["knn"]), int(q["minimum_plane_points"]), float(q["plane_eigen_threshold"]),
+                                           float(q["search_radius"]))
+    return opts, gates, knn, planes
+
+
 def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, want_pairs=False, pairings_per_point=None):
     """mh_icp_align_layers: one alignment over several (map, scan) point-layer pairs with one Gauss-Newton solve.
     `pairs`: a sequence of dicts {map, scan, threshold, threshold_angular_deg=0, weight=1} or tuples in that order; a
@@ -927,22 +956,12 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
     T0 = _T12(T_guess)
     arr, norm, thr_keep = _layer_pairs(pairs, p.max_iterations)
     n_pairs = len(norm)
-    kpp = None
-    if pairings_per_point is not None:
-        kpp = [int(k) for k in np.broadcast_to(np.asarray(pairings_per_point), (n_pairs,))]
+    opts, gates, knn, planes = _layer_pair_options(norm, pairings_per_point)
     res = ICPResult()
     trace = (ICPIter * max(1, p.max_iterations))() if want_trace else None
     pr = _mk_prior(prior)
     counts = (C.c_uint64 * max(1, n_pairs))()
     po, bufs = None, []
-    planes = None
-    if any(e.get("plane") for e in norm):
-        planes = (LayerPairPlane * max(1, n_pairs))()
-        for i, e in enumerate(norm):
-            q = e.get("plane")
-            if q:
-                planes[i] = LayerPairPlane(int(q["knn"]), int(q["minimum_plane_points"]), float(q["plane_eigen_threshold"]),
-                                           float(q["search_radius"]))
     ppl, pl_bufs = None, {}
     if want_pairs and planes is not None:
         ppl = (PairsPlOut * max(1, n_pairs))()
@@ -954,35 +973,16 @@ def icp_align_layers(pairs, T_guess, p: ICPParams, prior=None, want_trace=True, 
     if want_pairs:
         po = (PairsOut * max(1, n_pairs))()
         for i, e in enumerate(norm):
-            n = max(e["scan"].n * (max(kpp[i], 1) if kpp else 1), 1)
+            n = max(e["scan"].n * (max(knn[i].pairings_per_point, 1) if knn else 1), 1)
             li, gi = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
             gx, gy, gz, d2 = (np.zeros(n, np.float32) for _ in range(4))
             po[i] = PairsOut(li.ctypes.data_as(_UP), gi.ctypes.data_as(_UP), gx.ctypes.data_as(_FP), gy.ctypes.data_as(_FP),
                              gz.ctypes.data_as(_FP), d2.ctypes.data_as(_FP))
             bufs.append((li, gi, gx, gy, gz, d2))
-    opts = None
-    if any(e.get("unique_global") for e in norm):
-        opts = (LayerPairOpts * max(1, n_pairs))()
-        for i, e in enumerate(norm):
-            opts[i].unique_global = 1 if e.get("unique_global") else 0
-    gates = None
-    if any(e.get("run_from_iteration") or e.get("run_up_to_iteration") for e in norm):
-        gates = (LayerPairGates * max(1, n_pairs))()
-        for i, e in enumerate(norm):
-            gates[i].run_from_iteration = int(e.get("run_from_iteration") or 0)
-            gates[i].run_up_to_iteration = int(e.get("run_up_to_iteration") or 0)
     if planes is not None:
-        knn = None
-        if kpp is not None:
-            knn = (LayerPairKnn * max(1, n_pairs))()
-            for i, k in enumerate(kpp):
-                knn[i].pairings_per_point = k
         _chk(lib().mh_icp_align_layers_planes(n_pairs, arr, opts, gates, knn, planes, C.byref(cp), T0.ctypes.data_as(_DP),
                                               C.byref(pr) if pr else None, C.byref(res), trace, po, ppl, counts, MEM_HOST))
-    elif kpp is not None:
-        knn = (LayerPairKnn * max(1, n_pairs))()
-        for i, k in enumerate(kpp):
-            knn[i].pairings_per_point = k
+    elif knn is not None:
         _chk(lib().mh_icp_align_layers_kbest(n_pairs, arr, opts, gates, knn, C.byref(cp), T0.ctypes.data_as(_DP),
                                              C.byref(pr) if pr else None, C.byref(res), trace, po, counts, MEM_HOST))
     elif gates is not None:
@@ -1036,45 +1036,19 @@ def icp_align_layers_batch(jobs, T_guesses, params, priors=None, pairings_per_po
         cp_ref = C.byref(cp)
     keep_pairs = [_layer_pairs(pairs, plist[i].max_iterations) for i, pairs in enumerate(jobs)]
     assert pairings_per_point is None or len(pairings_per_point) == n
-    keep_opts = []  # per job: (opts, gates, knn), None where the job has none
-    keep_planes = []  # per job: its mh_layer_pair_plane array, None where no pair of it carries `plane`
-    for i, (arr, norm, thr_keep) in enumerate(keep_pairs):
-        n_pairs = len(norm)
-        opts = gates = knn = None
-        if any(e.get("unique_global") for e in norm):
-            opts = (LayerPairOpts * max(1, n_pairs))()
-            for k, e in enumerate(norm):
-                opts[k].unique_global = 1 if e.get("unique_global") else 0
-        if any(e.get("run_from_iteration") or e.get("run_up_to_iteration") for e in norm):
-            gates = (LayerPairGates * max(1, n_pairs))()
-            for k, e in enumerate(norm):
-                gates[k].run_from_iteration = int(e.get("run_from_iteration") or 0)
-                gates[k].run_up_to_iteration = int(e.get("run_up_to_iteration") or 0)
-        if pairings_per_point is not None and pairings_per_point[i] is not None:
-            knn = (LayerPairKnn * max(1, n_pairs))()
-            for k, v in enumerate(np.broadcast_to(np.asarray(pairings_per_point[i]), (n_pairs,))):
-                knn[k].pairings_per_point = int(v)
-        keep_opts.append((opts, gates, knn))
-        planes = None
-        if any(e.get("plane") for e in norm):
-            planes = (LayerPairPlane * max(1, n_pairs))()
-            for k, e in enumerate(norm):
-                q = e.get("plane")
-                if q:
-                    planes[k] = LayerPairPlane(int(q["knn"]), int(q["minimum_plane_points"]), float(q["plane_eigen_threshold"]),
-                                               float(q["search_radius"]))
-        keep_planes.append(planes)
-    with_opts = any(o is not None for t in keep_opts for o in t)
-    with_planes = bool(planes_entry) or any(q is not None for q in keep_planes)
-    with_opts = with_opts or with_planes
+    # per job: (opts, gates, knn, planes), None where the job has none
+    keep_opts = [_layer_pair_options(norm, pairings_per_point[i] if pairings_per_point is not None else None)
+                 for i, (arr, norm, thr_keep) in enumerate(keep_pairs)]
+    with_planes = bool(planes_entry) or any(t[3] is not None for t in keep_opts)
+    with_opts = with_planes or any(o is not None for t in keep_opts for o in t[:3])
     jarr = ((LayerJobPlanes if with_planes else LayerJobOpts if with_opts else LayerJob) * max(1, n))()
     for i, (arr, norm, thr_keep) in enumerate(keep_pairs):
         jarr[i].n_pairs = len(norm)
         jarr[i].pairs = arr
         if with_opts:
-            jarr[i].opts, jarr[i].gates, jarr[i].knn = keep_opts[i]  # (None: NULL)
+            jarr[i].opts, jarr[i].gates, jarr[i].knn = keep_opts[i][:3]  # (None: NULL)
         if with_planes:
-            jarr[i].planes = keep_planes[i]
+            jarr[i].planes = keep_opts[i][3]
     pr_arr, keep_pr = None, []
     if priors is not None:
         pr_arr = (C.POINTER(Prior) * max(1, n))()

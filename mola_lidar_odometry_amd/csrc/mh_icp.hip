@@ -19,7 +19,8 @@
 //   mh_icp_job.inl                 what AlignJob and LayersJob share: result / state / solver set-up, graph cache, result read-back
 //   mh_k_layers.h, mh_k_claim.h, mh_k_match_kbest.h, mh_k_match_planes.h
 //                                  the multi-layer loop's kernels: pair table, unique pairs, pairingsPerPoint > 1, plane pairs (KNN + PCA)
-//   mh_icp_layers.inl, mh_icp_layers_batch.inl   LayersJob, mh_icp_align_layers(_planes), mh_icp_align_layers_batch(_opts, _planes)
+//   mh_icp_layers.inl, mh_icp_layers_batch.inl   LayersView (one job description), check_layers_job, LayersJob; the single call and the
+//                                  lock-step batch behind mh_icp_align_layers* and mh_icp_align_layers_batch*
 //   mh_icp_batch.inl               mh_icp_align_batch (lock-step groups)
 //   mh_icp_api.inl                 matcher- / solver-granular entry points (mh_nn_search*, mh_gn_solve, mh_covariance)
 //   mh_dev_variants.h              (-DMH_DEV_VARIANTS only) the tile / wave / sorted-scan matchers that lost to the product kernels
@@ -1000,7 +1001,7 @@ mh_status align_single(const Switches& sw, const mh_map* map, const mh_scan* sca
   return MH_OK;
 }
 
-#include "mh_icp_layers.inl"  // align_layers (mh_icp_align_layers)
+#include "mh_icp_layers.inl"  // LayersView, check_layers_job, LayersJob, align_layers_as (mh_icp_align_layers*)
 
 }  // namespace
 
@@ -1050,61 +1051,46 @@ size_t mh_pairs_block_bytes(size_t n_scan_points) {
 
 #include "mh_icp_api.inl"    // mh_nn_search*, mh_gn_solve, mh_covariance
 
+// Five spellings of one call: each fills the job description (mh_layer_job_planes) and takes the shared path, align_layers_as.
 mh_status mh_icp_align_layers_planes(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
                                      const mh_layer_pair_gates* gates, const mh_layer_pair_knn* knn,
                                      const mh_layer_pair_plane* planes, const mh_icp_params* params, const double T_guess[12],
                                      const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
                                      const mh_pairs_out* final_pairs, const mh_pairs_pl_out* final_plane_pairs,
                                      uint64_t* final_pair_counts, int32_t pairs_mem) {
-  MH_TRY(check_layers_args(n_pairs, pairs, params, T_guess, result));
-  MH_REQUIRE(!(final_pairs || final_plane_pairs) || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
-  for (size_t i = 0; knn && i < n_pairs; i++)
-    MH_REQUIRE(knn[i].pairings_per_point <= MH_MAX_PAIRINGS_PER_POINT, "pairings_per_point must be 0 .. MH_MAX_PAIRINGS_PER_POINT");
-  MH_TRY(check_layers_planes(n_pairs, pairs, opts, knn, planes, params));
-  MH_TRY(check_layers_supported(n_pairs, pairs, params));
-  for (size_t i = 0; knn && i < n_pairs; i++) {
-    const uint64_t entries = (uint64_t)pairs[i].scan->n * (knn[i].pairings_per_point ? knn[i].pairings_per_point : 1u);
-    if (entries >= (1ull << 32))
-      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_kbest: scan size * pairings_per_point does not fit 32 bits");
-    if (opts && opts[i].unique_global && entries >= kClaimMaxScan)
-      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_kbest: a unique pair with 2^29 or more pairing entries");
-  }
-  bool any_plane = false;
-  for (size_t i = 0; planes && i < n_pairs; i++) any_plane = any_plane || planes[i].knn != 0u;
-  return align_layers(read_switches(), (uint32_t)n_pairs, pairs, params, T_guess, prior, result, trace, final_pairs,
-                      final_pair_counts, pairs_mem, opts, gates, knn, any_plane ? planes : nullptr,
-                      any_plane ? final_plane_pairs : nullptr);
+  return align_layers_as(__func__, {n_pairs, pairs, opts, gates, knn, planes}, params, T_guess, prior, result, trace, final_pairs,
+                         final_plane_pairs, final_pair_counts, pairs_mem);
 }
 
 mh_status mh_icp_align_layers_kbest(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
                                     const mh_layer_pair_gates* gates, const mh_layer_pair_knn* knn, const mh_icp_params* params,
                                     const double T_guess[12], const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
                                     const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
-  return mh_icp_align_layers_planes(n_pairs, pairs, opts, gates, knn, nullptr, params, T_guess, prior, result, trace, final_pairs,
-                                    nullptr, final_pair_counts, pairs_mem);
+  return align_layers_as(__func__, {n_pairs, pairs, opts, gates, knn, nullptr}, params, T_guess, prior, result, trace, final_pairs,
+                         nullptr, final_pair_counts, pairs_mem);
 }
 
 mh_status mh_icp_align_layers_gated(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
                                     const mh_layer_pair_gates* gates, const mh_icp_params* params, const double T_guess[12],
                                     const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace,
                                     const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
-  return mh_icp_align_layers_kbest(n_pairs, pairs, opts, gates, nullptr, params, T_guess, prior, result, trace, final_pairs,
-                                   final_pair_counts, pairs_mem);
+  return align_layers_as(__func__, {n_pairs, pairs, opts, gates, nullptr, nullptr}, params, T_guess, prior, result, trace,
+                         final_pairs, nullptr, final_pair_counts, pairs_mem);
 }
 
 mh_status mh_icp_align_layers_opts(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts,
                                    const mh_icp_params* params, const double T_guess[12], const mh_prior* prior,
                                    mh_icp_result* result, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
                                    uint64_t* final_pair_counts, int32_t pairs_mem) {
-  return mh_icp_align_layers_gated(n_pairs, pairs, opts, nullptr, params, T_guess, prior, result, trace, final_pairs,
-                                   final_pair_counts, pairs_mem);
+  return align_layers_as(__func__, {n_pairs, pairs, opts, nullptr, nullptr, nullptr}, params, T_guess, prior, result, trace,
+                         final_pairs, nullptr, final_pair_counts, pairs_mem);
 }
 
 mh_status mh_icp_align_layers(size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params, const double T_guess[12],
                               const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
                               uint64_t* final_pair_counts, int32_t pairs_mem) {
-  return mh_icp_align_layers_opts(n_pairs, pairs, nullptr, params, T_guess, prior, result, trace, final_pairs, final_pair_counts,
-                                  pairs_mem);
+  return align_layers_as(__func__, {n_pairs, pairs, nullptr, nullptr, nullptr, nullptr}, params, T_guess, prior, result, trace,
+                         final_pairs, nullptr, final_pair_counts, pairs_mem);
 }
 
 #include "mh_icp_layers_batch.inl"  // mh_icp_align_layers_batch

@@ -2,6 +2,12 @@
 // (lidar3d-dual-map.yaml, lidar3d-edges.yaml) with one Gauss-Newton solve.  Included by mh_icp.hip inside its anonymous namespace,
 // after AlignJob; the set-up, graph cache and read-back it shares with AlignJob are mh_icp_job.inl's.
 //
+// One description, one check, several public spellings.  An alignment is described by the ABI's mh_layer_job_planes {n_pairs,
+// pairs, opts, gates, knn, planes}: every mh_icp_align_layers* entry point fills one and calls align_layers_as, every
+// mh_icp_align_layers_batch* one fills one per job (mh_icp_layers_batch.inl).  LayersView is the only reader of the description
+// (the defaults of a NULL array live there), check_layers_job the only holder of the argument rules -- the single call and every
+// job of a batch pass it before anything is queued -- and LayersJob sets up what has passed.
+//
 // Per ICP iteration:  k_match_layers -> k_accum_layers(first) -> k_solve -> [k_accum_layers -> k_solve] x (inner - 1)
 // over ALL pairs, whatever their number (mh_k_layers.h); the covariance kernels close the chunk that ends the loop.  With a pair
 // whose map points pair once only (mh_icp_align_layers_opts, unique_global): k_claim_layers -> k_resolve_layers behind the match
@@ -37,39 +43,67 @@ struct LayersLayout {
   size_t seg_c[MH_MAX_LAYER_PAIRS], seg_n[MH_MAX_LAYER_PAIRS];  // byte offsets of a plane pair's pl_c / pl_n
 };
 
-// One multi-layer alignment from its arguments to its uploaded [state | parameters | table | schedules]: what a single call and a
-// job of mh_icp_align_layers_batch share.  Everything start() queues goes to the job's own context stream.
+// One multi-layer alignment as its caller describes it: the C ABI's mh_layer_job_planes, read through these accessors and nowhere
+// else.  A NULL array, a zero pairings_per_point and a planes array without a plane pair become their defaults HERE.
+struct LayersView {
+  mh_layer_job_planes d = {};
+  uint32_t np() const { return (uint32_t)d.n_pairs; }
+  const mh_layer_pair& pair(uint32_t i) const { return d.pairs[i]; }
+  bool unique(uint32_t i) const { return d.opts && d.opts[i].unique_global; }
+  uint32_t run_from(uint32_t i) const { return d.gates ? d.gates[i].run_from_iteration : 0u; }
+  uint32_t run_up_to(uint32_t i) const { return d.gates ? d.gates[i].run_up_to_iteration : 0u; }
+  uint32_t kpp(uint32_t i) const { return d.knn && d.knn[i].pairings_per_point ? d.knn[i].pairings_per_point : 1u; }  // >= 1
+  mh_layer_pair_plane plane(uint32_t i) const { return d.planes ? d.planes[i] : mh_layer_pair_plane{}; }  // knn 0: a point pair
+  uint64_t entries(uint32_t i) const { return (uint64_t)pair(i).scan->n * kpp(i); }  // of pair i's pairing segment
+  bool active_in(uint32_t i, uint32_t k) const {  // layer_active (mh_k_layers.h) on the host
+    return k >= run_from(i) && (run_up_to(i) == 0 || k <= run_up_to(i));
+  }
+  // potential_pairings: the layer sizes (times the pairings per point: pcLocal.size() * pairingsPerPoint [U]) of the pairs that
+  // are active in ICP iteration k (all of them without gates)
+  uint64_t potential_in(uint32_t k) const {
+    uint64_t s = 0;
+    for (uint32_t i = 0; i < np(); i++) s += active_in(i, k) ? entries(i) : 0;
+    return s;
+  }
+  template <class F>
+  bool any(F f) const {
+    bool a = false;
+    for (uint32_t i = 0; i < np(); i++) a = a || f(i);
+    return a;
+  }
+  bool has_unique() const { return any([&](uint32_t i) { return unique(i); }); }
+  bool has_knn() const { return any([&](uint32_t i) { return kpp(i) > 1u; }); }  // a pair with k > 1
+  bool has_plane() const { return any([&](uint32_t i) { return plane(i).knn != 0u; }); }
+};
+
+// a plane pair's parameters as the KNN + PCA matcher takes them (mh_nn_search_pt2pl_knn)
+inline mh_pt2pl_knn_params plane_params(const mh_layer_pair_plane& pl, double distance_threshold) {
+  mh_pt2pl_knn_params kp{};
+  kp.distance_threshold = distance_threshold;
+  kp.plane_eigen_threshold = pl.plane_eigen_threshold;
+  kp.search_radius = pl.search_radius;
+  kp.knn = pl.knn;
+  kp.minimum_plane_points = pl.minimum_plane_points;
+  return kp;
+}
+
+// One multi-layer alignment from its description to its uploaded [state | parameters | table | schedules]: what a single call and
+// a job of a batch share.  The description has passed check_layers_job; everything start() queues goes to the job's own
+// context stream.
 struct LayersJob {
   mh_ctx* ctx = nullptr;
-  uint32_t np = 0;
-  const mh_layer_pair* pairs = nullptr;
+  LayersView v;
   const mh_icp_params* p = nullptr;
   mh_icp_result* res = nullptr;
-  mh_layer_pair_gates gates[MH_MAX_LAYER_PAIRS] = {};  // all zero: no gate
-  uint32_t kpp[MH_MAX_LAYER_PAIRS] = {};               // pairings per point, >= 1
-  mh_layer_pair_plane pl[MH_MAX_LAYER_PAIRS] = {};     // knn 0: a point pair
   const PlaneTable* ptab = nullptr;  // the pinned mirror of the device's plane table (with a plane pair)
   bool trivial = false;       // nothing to run: the result is complete after start()
   LayersLayout L;
   const LayerTable* tab = nullptr;  // the pinned mirror of the device table (the pairing segments: count_pairs)
   uint32_t chunk = 10;        // iterations of the first chunk
 
-  mh_status start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
-                  const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
-                  const mh_layer_pair_opts* opts = nullptr, const mh_layer_pair_gates* gates_ = nullptr,
-                  const mh_layer_pair_knn* knn = nullptr, const mh_layer_pair_plane* planes = nullptr);
-  size_t entries(uint32_t i) const { return pairs[i].scan->n * (size_t)kpp[i]; }  // of pair i's pairing segment
+  mh_status start(const Switches& sw, const LayersView& v_, const mh_icp_params* p_, const double T0[12], const mh_prior* prior,
+                  mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts);
   uint32_t k_last = 0;        // after finish(): the ICP iteration whose match produced the final pairings
-  bool active_in(uint32_t i, uint32_t k) const {  // layer_active (mh_k_layers.h) on the host
-    return k >= gates[i].run_from_iteration && (gates[i].run_up_to_iteration == 0 || k <= gates[i].run_up_to_iteration);
-  }
-  // potential_pairings: the layer sizes (times the pairings per point: pcLocal.size() * pairingsPerPoint [U]) of the pairs that
-  // are active in ICP iteration k (all of them without gates)
-  uint64_t potential_in(uint32_t k) const {
-    uint64_t s = 0;
-    for (uint32_t i = 0; i < np; i++) s += active_in(i, k) ? entries(i) : 0;
-    return s;
-  }
   void finish(uint32_t polls, uint32_t enqueued);
   mh_status count_pairs(const mh_pairs_out* final_pairs, uint64_t* final_pair_counts, int32_t pairs_mem,
                         const mh_pairs_pl_out* final_plane_pairs = nullptr);
@@ -81,15 +115,13 @@ struct LayersJob {
 // entry empty) when its block is new and when the epochs have run out; otherwise what earlier alignments left loses by its epoch.
 mh_status LayersJob::claims_begin(ClaimTable* ct) {
   memset(ct, 0, sizeof(ClaimTable));
+  const uint32_t np = v.np();
+  const mh_layer_pair* const pairs = v.d.pairs;
   size_t region_off[MH_MAX_LAYER_PAIRS] = {0}, total = 0;
   for (uint32_t i = 0; i < np; i++) {
     ct->blk[i] = L.tot_claim;
     if (!((L.unique_mask >> i) & 1u)) continue;
-    const mh_map* m = pairs[i].map;
-    if (entries(i) >= kClaimMaxScan)
-      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_opts: a unique pair whose scan has 2^29 or more points");
-    if (m->n_offered >= kClaimMaxEntries)
-      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_opts: a unique pair whose map has been offered 2^28 or more points");
+    const mh_map* m = pairs[i].map;  // (its size and the pair's entries fit the claim key: check_layers_job)
     uint32_t first = i;
     for (uint32_t j = 0; j < i; j++)
       if (((L.unique_mask >> j) & 1u) && pairs[j].map == m && first == i) first = j;
@@ -100,7 +132,7 @@ mh_status LayersJob::claims_begin(ClaimTable* ct) {
       region_off[i] = region_off[first];
     }
     ct->entries[i] = (uint32_t)m->n_offered;
-    L.tot_claim += nblk(entries(i));
+    L.tot_claim += nblk(v.entries(i));
   }
   ct->blk[np] = L.tot_claim;
   const void* const before = ctx->claims.p;
@@ -117,22 +149,18 @@ mh_status LayersJob::claims_begin(ClaimTable* ct) {
   return MH_OK;
 }
 
-mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair* pairs_, const mh_icp_params* p_, const double T0[12],
-                           const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts,
-                           const mh_layer_pair_opts* opts, const mh_layer_pair_gates* gates_, const mh_layer_pair_knn* knn,
-                           const mh_layer_pair_plane* planes) {
-  np = np_;
-  pairs = pairs_;
+mh_status LayersJob::start(const Switches& sw, const LayersView& v_, const mh_icp_params* p_, const double T0[12],
+                           const mh_prior* prior, mh_icp_result* res_, mh_icp_iter* trace, uint64_t* final_pair_counts) {
+  v = v_;
   p = p_;
   res = res_;
+  const uint32_t np = v.np();
+  const mh_layer_pair* const pairs = v.d.pairs;
   ctx = pairs[0].scan->ctx;
   if (final_pair_counts)
     for (uint32_t i = 0; i < np; i++) final_pair_counts[i] = 0;
-  for (uint32_t i = 0; i < np; i++) gates[i] = gates_ ? gates_[i] : mh_layer_pair_gates{};
-  for (uint32_t i = 0; i < np; i++) kpp[i] = knn && knn[i].pairings_per_point ? knn[i].pairings_per_point : 1u;
-  for (uint32_t i = 0; i < np; i++) pl[i] = planes ? planes[i] : mh_layer_pair_plane{};
   // (every pair gated off in iteration 0 is NoPairings there, like no points at all)
-  if ((trivial = begin_result(res, p, T0, potential_in(0)))) return MH_OK;
+  if ((trivial = begin_result(res, p, T0, v.potential_in(0)))) return MH_OK;
   MH_TRY(set_device(ctx));
   MH_TRY(ensure_state(ctx));
   hipStream_t s = ctx->stream;
@@ -142,9 +170,6 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     for (uint32_t j = 0; j < i; j++) seen = seen || pairs[j].map == pairs[i].map;
     if (seen) continue;
     const mh_map* m = pairs[i].map;
-    // (n_records: exact once the last (re)build is resolved, an upper bound while it may still run -- never below the truth)
-    if (m->n_records >= kFlatMaxRecords)
-      return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: a map of 2^30 or more records");
     MH_TRY(map_ready_on(m, s));
     MH_TRY(map_ensure_qidx(sw, m, s));
     if (!m->view(sw).pts_q) return fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (mh_icp_align_layers needs it)");
@@ -154,12 +179,12 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   const size_t mi = p->max_iterations;
   const size_t tab_bytes = (sizeof(LayerTable) + 255) / 256 * 256;
   const size_t sched_bytes = (1 + (size_t)np) * mi * sizeof(double);  // kernel_param | threshold of pair 0 | ... | pair np-1
-  for (uint32_t i = 0; opts && i < np; i++) L.unique_mask |= opts[i].unique_global ? 1u << i : 0u;
+  for (uint32_t i = 0; i < np; i++) L.unique_mask |= v.unique(i) ? 1u << i : 0u;
   // (a call without unique pairs uploads the bytes it always did)
   L.claim_off = (tab_bytes + sched_bytes + 255) / 256 * 256;
-  for (uint32_t i = 0; i < np; i++) L.knn_key |= kpp[i] > 1u ? kpp[i] << (4 * i) : 0u;
+  for (uint32_t i = 0; i < np; i++) L.knn_key |= v.kpp(i) > 1u ? v.kpp(i) << (4 * i) : 0u;
   L.knn_off = (L.claim_off + sizeof(ClaimTable) + 255) / 256 * 256;
-  for (uint32_t i = 0; i < np; i++) L.plane_key |= (unsigned long long)pl[i].knn << (5 * i);
+  for (uint32_t i = 0; i < np; i++) L.plane_key |= (unsigned long long)v.plane(i).knn << (5 * i);
   L.plane_off = (L.knn_off + sizeof(KnnTable) + 255) / 256 * 256;
   const size_t up_bytes = L.plane_key ? L.plane_off + sizeof(PlaneTable)
                           : L.knn_key ? L.knn_off + sizeof(KnnTable)
@@ -176,9 +201,9 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
   if (L.plane_key) memset(pt, 0, sizeof(PlaneTable));
   ptab = L.plane_key ? pt : nullptr;
   for (uint32_t i = 0; i < np; i++) {
-    const size_t n = entries(i), nn = n ? n : 1;  // (k = 1: the points)
-    const bool plane = pl[i].knn != 0u;
-    const size_t n_flat = (kpp[i] > 1u || plane) ? 0 : n, n_flat_k = kpp[i] > 1u ? pairs[i].scan->n : 0;
+    const size_t n = v.entries(i), nn = n ? n : 1;  // (k = 1: the points)
+    const bool plane = v.plane(i).knn != 0u;
+    const size_t n_flat = (v.kpp(i) > 1u || plane) ? 0 : n, n_flat_k = v.kpp(i) > 1u ? pairs[i].scan->n : 0;
     if (L.plane_key) {
       pt->blk_match[i] = L.tot_match_pl;
       pt->blk_acc[i] = pt->blk_cov[i] = L.tot_acc_pl;
@@ -201,7 +226,7 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     L.tot_cov += (n && !plane) ? nblk(n) : 0u;
   }
   for (uint32_t i = 0; i < np; i++) {  // (behind every pair's segments: a table without a plane pair keeps its layout)
-    if (!pl[i].knn) continue;
+    if (!v.plane(i).knn) continue;
     const size_t nn = pairs[i].scan->n ? pairs[i].scan->n : 1;
     L.seg_c[i] = L.pair_bytes;
     L.pair_bytes += (nn * sizeof(float4) + 255) / 256 * 256;
@@ -244,15 +269,11 @@ mh_status LayersJob::start(const Switches& sw, uint32_t np_, const mh_layer_pair
     d.mk.w_pt2pt = pairs[i].weight;
     d.col_off = tab->blk_acc[i];
     d.cov_off = tab->blk_cov[i];
-    d.run_from = gates[i].run_from_iteration;
-    d.run_up_to = gates[i].run_up_to_iteration;
-    d.kpp = kpp[i] > 1u ? kpp[i] : 0u;  // (k = 1: the word the table always had there)
-    if (pl[i].knn) {  // (pair_q: what the next iteration's bound needs; distance threshold: the pair's schedule)
-      mh_pt2pl_knn_params kp{};
-      kp.plane_eigen_threshold = pl[i].plane_eigen_threshold;
-      kp.search_radius = pl[i].search_radius;
-      kp.knn = pl[i].knn;
-      kp.minimum_plane_points = pl[i].minimum_plane_points;
+    d.run_from = v.run_from(i);
+    d.run_up_to = v.run_up_to(i);
+    d.kpp = v.kpp(i) > 1u ? v.kpp(i) : 0u;  // (k = 1: the word the table always had there)
+    if (v.plane(i).knn) {  // (pair_q: what the next iteration's bound needs; distance threshold: the pair's schedule)
+      const mh_pt2pl_knn_params kp = plane_params(v.plane(i), 0.0);
       const PlKnnArg a = pl_knn_arg(&kp);
       PlaneDesc& q = pt->d[i];
       q.pl_c = reinterpret_cast<float4*>(pb + L.seg_c[i]);
@@ -279,7 +300,7 @@ void LayersJob::finish(uint32_t polls, uint32_t enqueued) {
   if (p->poll_every == 0) ctx->layers_predicted = live_iterations(ctx->h_state);
   // the iteration whose match produced the final pairings: the one that terminated the loop, or the last of max_iterations
   k_last = ctx->h_state->n_iterations < p->max_iterations ? ctx->h_state->n_iterations : p->max_iterations - 1;
-  read_result(ctx->h_state, p, res, potential_in(k_last), L.plane_key ? ctx->h_state->n_pairs_pl : 0u, polls, enqueued);
+  read_result(ctx->h_state, p, res, v.potential_in(k_last), L.plane_key ? ctx->h_state->n_pairs_pl : 0u, polls, enqueued);
 }
 
 // every pair's final pairings compacted out of its segment (into final_pairs[i] when given) and counted
@@ -289,20 +310,22 @@ mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* fina
   const mh_pairs_out none{};
   const mh_pairs_pl_out none_pl{};
   uint64_t sum = 0;
-  for (uint32_t i = 0; i < np; i++) {
+  const mh_layer_pair* const pairs = v.d.pairs;
+  for (uint32_t i = 0; i < v.np(); i++) {
     uint64_t c = 0;
-    if (pl[i].knn && pairs[i].scan->n && active_in(i, k_last)) {
+    const uint32_t kpp = v.kpp(i);
+    if (v.plane(i).knn && pairs[i].scan->n && v.active_in(i, k_last)) {
       MH_TRY(compact_pl_pairs_of(ctx, ptab->d[i].pl_c, ptab->d[i].pl_n, pairs[i].scan->n,
                                  final_plane_pairs ? &final_plane_pairs[i] : &none_pl, final_plane_pairs ? pairs_mem : MH_MEM_DEVICE, &c));
-    } else if (pairs[i].scan->n && active_in(i, k_last)) {  // (a pair that is gated off there holds "not paired" throughout)
-      MH_TRY(compact_pairs_of(ctx, tab->d[i].pair_gidx, tab->d[i].pair_q, entries(i), final_pairs ? &final_pairs[i] : &none,
+    } else if (pairs[i].scan->n && v.active_in(i, k_last)) {  // (a pair that is gated off there holds "not paired" throughout)
+      MH_TRY(compact_pairs_of(ctx, tab->d[i].pair_gidx, tab->d[i].pair_q, v.entries(i), final_pairs ? &final_pairs[i] : &none,
                               final_pairs ? pairs_mem : MH_MEM_DEVICE, &c));
       // the compaction numbers the ENTRIES: entry e belongs to local point e / k (mh_nn_search_k)
-      if (kpp[i] > 1u && c && final_pairs && final_pairs[i].local_idx) {
+      if (kpp > 1u && c && final_pairs && final_pairs[i].local_idx) {
         if (pairs_mem == MH_MEM_HOST) {
-          for (uint64_t e = 0; e < c; e++) final_pairs[i].local_idx[e] /= kpp[i];
+          for (uint64_t e = 0; e < c; e++) final_pairs[i].local_idx[e] /= kpp;
         } else {
-          hipLaunchKernelGGL(k_div_idx, dim3(nblk(c)), dim3(kBlock), 0, ctx->stream, final_pairs[i].local_idx, (uint32_t)c, kpp[i]);
+          hipLaunchKernelGGL(k_div_idx, dim3(nblk(c)), dim3(kBlock), 0, ctx->stream, final_pairs[i].local_idx, (uint32_t)c, kpp);
           MH_HIP(hipGetLastError());
           MH_HIP(mh::wait_stream(ctx->stream));
         }
@@ -317,14 +340,13 @@ mh_status LayersJob::count_pairs(const mh_pairs_out* final_pairs, uint64_t* fina
   return MH_OK;
 }
 
-mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pairs, const mh_icp_params* p, const double T0[12],
-                       const mh_prior* prior, mh_icp_result* res, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
-                       uint64_t* final_pair_counts, int32_t pairs_mem, const mh_layer_pair_opts* opts = nullptr,
-                       const mh_layer_pair_gates* gates = nullptr, const mh_layer_pair_knn* knn = nullptr,
-                       const mh_layer_pair_plane* planes = nullptr, const mh_pairs_pl_out* final_plane_pairs = nullptr) {
+mh_status align_layers(const Switches& sw, const LayersView& v, const mh_icp_params* p, const double T0[12], const mh_prior* prior,
+                       mh_icp_result* res, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
+                       const mh_pairs_pl_out* final_plane_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
   LayersJob job;
-  MH_TRY(job.start(sw, np, pairs, p, T0, prior, res, trace, final_pair_counts, opts, gates, knn, planes));
+  MH_TRY(job.start(sw, v, p, T0, prior, res, trace, final_pair_counts));
   if (job.trivial) return MH_OK;
+  const uint32_t np = v.np();
   mh_ctx* const ctx = job.ctx;
   const LayersLayout& L = job.L;
   hipStream_t s = ctx->stream;
@@ -414,55 +436,75 @@ mh_status align_layers(const Switches& sw, uint32_t np, const mh_layer_pair* pai
   }
   job.finish(polls, enqueued);
   if (trace) MH_TRY(download_trace(ctx, ctx->h_state, p, trace));
-  return job.count_pairs(final_pairs, final_pair_counts, pairs_mem, final_plane_pairs);
+  return job.count_pairs(final_pairs, final_pair_counts, pairs_mem, v.has_plane() ? final_plane_pairs : nullptr);
 }
 
-// the argument rules of mh_icp_align_layers (one job of mh_icp_align_layers_batch obeys the same): nothing here touches the device
-mh_status check_layers_args(size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params, const double* T_guess,
-                            const mh_icp_result* result) {
-  MH_REQUIRE(n_pairs >= 1 && n_pairs <= MH_MAX_LAYER_PAIRS, "n_pairs must be 1 .. MH_MAX_LAYER_PAIRS");
-  MH_REQUIRE(pairs && params && T_guess && result, "null argument");
-  for (size_t i = 0; i < n_pairs; i++) {
-    MH_REQUIRE(pairs[i].map && pairs[i].scan && pairs[i].threshold, "null map, scan or threshold in a layer pair");
-    MH_REQUIRE(pairs[i].map->ctx == pairs[0].scan->ctx && pairs[i].scan->ctx == pairs[0].scan->ctx,
-               "the maps and scans of a multi-layer alignment live on different contexts");
-  }
-  MH_REQUIRE(params->pt2pl_threshold == nullptr, "Matcher_Point2Plane is not supported with layer pairs");
-  MH_REQUIRE(pose_ok(T_guess), "non-finite initial guess");
-  MH_REQUIRE(params->max_iterations == 0 || params->kernel_param, "kernel_param array is required");
-  MH_REQUIRE(params->gn.max_inner_iterations >= 1, "gn.max_inner_iterations must be >= 1");
-  MH_REQUIRE(params->gn.robust_kernel <= MH_KERNEL_GM_C2, "unknown robust kernel");
-  MH_REQUIRE(params->max_iterations < (1u << 20), "max_iterations too large");
-  MH_REQUIRE(params->matched_points <= MH_MATCHED_POINTS_SKIP, "unknown matched_points mode");
-  return MH_OK;
-}
-mh_status check_layers_supported(size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params) {
-  if (params->profile != 0) return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: profile is not supported");
-  if (params->matched_points == MH_MATCHED_POINTS_SKIP)
-    for (size_t i = 0; i < n_pairs; i++)
-      for (size_t j = i + 1; j < n_pairs; j++)
-        if (pairs[i].scan == pairs[j].scan)
-          return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: MH_MATCHED_POINTS_SKIP with a scan shared by two pairs");
-  return MH_OK;
-}
-
-// the argument rules of mh_icp_align_layers_planes' plane pairs (planes[i].knn != 0): nothing here touches the device
-mh_status check_layers_planes(size_t n_pairs, const mh_layer_pair* pairs, const mh_layer_pair_opts* opts, const mh_layer_pair_knn* knn,
-                              const mh_layer_pair_plane* planes, const mh_icp_params* params) {
-  for (size_t i = 0; planes && i < n_pairs; i++) {
-    if (!planes[i].knn) continue;
-    MH_REQUIRE(!(opts && opts[i].unique_global), "a plane pair cannot be unique_global");
-    MH_REQUIRE(!(knn && knn[i].pairings_per_point > 1u), "a plane pair has one pairing per point");
-    MH_REQUIRE(pairs[i].threshold_angular_deg == 0.0, "a plane pair has no angular threshold");
-    mh_pt2pl_knn_params kp{};
-    kp.plane_eigen_threshold = planes[i].plane_eigen_threshold;
-    kp.search_radius = planes[i].search_radius;
-    kp.knn = planes[i].knn;
-    kp.minimum_plane_points = planes[i].minimum_plane_points;
-    for (uint32_t k = 0; k < (params->max_iterations ? params->max_iterations : 1u); k++) {
-      kp.distance_threshold = params->max_iterations ? pairs[i].threshold[k] : 0.0;
-      MH_TRY(check_pl_knn_params(&kp));
+// Every rule one multi-layer alignment must obey, for the single call and for each job of a batch alike; nothing here touches
+// the device, and nothing has been queued when it refuses.  Two passes, because a batch settles the Arguments of ALL its jobs
+// before the first Supported rule: MH_ERR_INVALID_ARGUMENT wins over MH_ERR_UNSUPPORTED.  `who` is the public entry point called.
+enum class LayerRules { Arguments, Supported };
+#define MH_REQUIRE_AS(who, cond, msg)                                                      \
+  do {                                                                                     \
+    if (!(cond)) return fail(MH_ERR_INVALID_ARGUMENT, "%s: %s", who, msg);                 \
+  } while (0)
+mh_status check_layers_job(const char* who, LayerRules rules, const LayersView& v, const mh_icp_params* params, const double* T_guess,
+                           const mh_icp_result* result) {
+  const size_t n_pairs = v.d.n_pairs;
+  const mh_layer_pair* const pairs = v.d.pairs;
+  if (rules == LayerRules::Arguments) {
+    MH_REQUIRE_AS(who, n_pairs >= 1 && n_pairs <= MH_MAX_LAYER_PAIRS, "n_pairs must be 1 .. MH_MAX_LAYER_PAIRS");
+    MH_REQUIRE_AS(who, pairs && params && T_guess && result, "null argument");
+    for (uint32_t i = 0; i < n_pairs; i++) {
+      MH_REQUIRE_AS(who, pairs[i].map && pairs[i].scan && pairs[i].threshold, "null map, scan or threshold in a layer pair");
+      MH_REQUIRE_AS(who, pairs[i].map->ctx == pairs[0].scan->ctx && pairs[i].scan->ctx == pairs[0].scan->ctx,
+                    "the maps and scans of a multi-layer alignment live on different contexts");
     }
+    MH_REQUIRE_AS(who, params->pt2pl_threshold == nullptr, "Matcher_Point2Plane is not supported with layer pairs");
+    MH_REQUIRE_AS(who, pose_ok(T_guess), "non-finite initial guess");
+    MH_REQUIRE_AS(who, params->max_iterations == 0 || params->kernel_param, "kernel_param array is required");
+    MH_REQUIRE_AS(who, params->gn.max_inner_iterations >= 1, "gn.max_inner_iterations must be >= 1");
+    MH_REQUIRE_AS(who, params->gn.robust_kernel <= MH_KERNEL_GM_C2, "unknown robust kernel");
+    MH_REQUIRE_AS(who, params->max_iterations < (1u << 20), "max_iterations too large");
+    MH_REQUIRE_AS(who, params->matched_points <= MH_MATCHED_POINTS_SKIP, "unknown matched_points mode");
+    for (uint32_t i = 0; i < n_pairs; i++) {
+      MH_REQUIRE_AS(who, v.kpp(i) <= MH_MAX_PAIRINGS_PER_POINT, "pairings_per_point must be 0 .. MH_MAX_PAIRINGS_PER_POINT");
+      if (!v.plane(i).knn) continue;
+      MH_REQUIRE_AS(who, !v.unique(i), "a plane pair cannot be unique_global");
+      MH_REQUIRE_AS(who, v.kpp(i) == 1u, "a plane pair has one pairing per point");
+      MH_REQUIRE_AS(who, pairs[i].threshold_angular_deg == 0.0, "a plane pair has no angular threshold");
+      for (uint32_t k = 0; k < (params->max_iterations ? params->max_iterations : 1u); k++) {  // (the same code as mh_nn_search_pt2pl_knn's)
+        const mh_pt2pl_knn_params kp = plane_params(v.plane(i), params->max_iterations ? pairs[i].threshold[k] : 0.0);
+        MH_TRY(check_pl_knn_params(&kp));
+      }
+    }
+    return MH_OK;
+  }
+  if (params->profile != 0) return fail(MH_ERR_UNSUPPORTED, "%s: profile is not supported", who);
+  for (uint32_t i = 0; i < n_pairs; i++) {
+    if (params->matched_points == MH_MATCHED_POINTS_SKIP)
+      for (uint32_t j = i + 1; j < n_pairs; j++)
+        if (pairs[i].scan == pairs[j].scan)
+          return fail(MH_ERR_UNSUPPORTED, "%s: MH_MATCHED_POINTS_SKIP with a scan shared by two pairs", who);
+    // (n_records: exact once the last (re)build is resolved, an upper bound while it may still run -- never below the truth)
+    if (pairs[i].map->n_records >= kFlatMaxRecords) return fail(MH_ERR_UNSUPPORTED, "%s: a map of 2^30 or more records", who);
+    if (v.d.knn && v.entries(i) >= (1ull << 32))  // (asked of a job with the array only, as ever)
+      return fail(MH_ERR_UNSUPPORTED, "%s: scan size * pairings_per_point does not fit 32 bits", who);
+    if (v.unique(i) && v.entries(i) >= kClaimMaxScan)
+      return fail(MH_ERR_UNSUPPORTED, "%s: a unique pair with 2^29 or more pairing entries", who);
+    if (v.unique(i) && pairs[i].map->n_offered >= kClaimMaxEntries)
+      return fail(MH_ERR_UNSUPPORTED, "%s: a unique pair whose map has been offered 2^28 or more points", who);
   }
   return MH_OK;
+}
+
+// the single call, under whichever of its five names it was made
+mh_status align_layers_as(const char* who, const mh_layer_job_planes& d, const mh_icp_params* params, const double* T_guess,
+                          const mh_prior* prior, mh_icp_result* result, mh_icp_iter* trace, const mh_pairs_out* final_pairs,
+                          const mh_pairs_pl_out* final_plane_pairs, uint64_t* final_pair_counts, int32_t pairs_mem) {
+  const LayersView v{d};
+  MH_TRY(check_layers_job(who, LayerRules::Arguments, v, params, T_guess, result));
+  MH_REQUIRE_AS(who, !(final_pairs || final_plane_pairs) || pairs_mem == MH_MEM_HOST || pairs_mem == MH_MEM_DEVICE, "bad mem space");
+  MH_TRY(check_layers_job(who, LayerRules::Supported, v, params, T_guess, result));
+  return align_layers(read_switches(), v, params, T_guess, prior, result, trace, final_pairs, final_plane_pairs, final_pair_counts,
+                      pairs_mem);
 }

@@ -1,4 +1,7 @@
-// mh_icp_layers_batch.inl -- mh_icp_align_layers_batch: many multi-layer alignments (one per context) from one host thread.  Jobs of
+// mh_icp_layers_batch.inl -- mh_icp_align_layers_batch: many multi-layer alignments (one per context) from one host thread.  The three
+// entry points (plain, _opts, _planes) are one function, align_layers_batch_as, on jobs described as mh_layer_job_planes: every job
+// passes check_layers_job (mh_icp_layers.inl) as a single call does, all jobs' argument rules before the first size limit, and the
+// group key is read from the jobs' LayersView.  Jobs of
 // the same loop shape (inner steps, covariance) advance in LOCK STEP: k_match_layers_b / k_accum_layers_b / k_cov_accum_layers_b
 // walk one flattened range over (job, pair) (mh_k_layers.h), k_solve_b / k_cov_prepare_b / k_cov_finalize_b take a workgroup per
 // job.  Every job is set up by LayersJob::start exactly as a single call sets it up, in its own context; its partials keep the
@@ -163,79 +166,43 @@ static mh_status align_layers_lockstep(const std::vector<LayersJob*>& g) {
   return MH_OK;
 }
 
-// (pair k of a job: its options, the defaults where the job has no such array)
-static inline uint32_t job_kpp(const mh_layer_job_planes& j, size_t k) {
-  return j.knn && j.knn[k].pairings_per_point ? j.knn[k].pairings_per_point : 1u;
-}
-static inline bool job_unique(const mh_layer_job_planes& j, size_t k) { return j.opts && j.opts[k].unique_global; }
-static inline bool job_has_plane(const mh_layer_job_planes& j) {
-  bool any = false;
-  for (size_t k = 0; j.planes && k < j.n_pairs; k++) any = any || j.planes[k].knn != 0u;
-  return any;
-}
-
-mh_status mh_icp_align_layers_batch_planes(size_t n_jobs, const mh_layer_job_planes* jobs, const mh_icp_params* params,
-                                           int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
-                                           mh_icp_result* results, uint64_t* final_pair_counts) {
-  MH_REQUIRE(n_jobs >= 1 && n_jobs <= MH_MAX_LAYER_BATCH_JOBS, "n_jobs must be 1 .. MH_MAX_LAYER_BATCH_JOBS");
-  MH_REQUIRE(jobs && params && T_guesses && results, "null argument");
+// the batch, under whichever of its three names it was made
+static mh_status align_layers_batch_as(const char* who, size_t n_jobs, const mh_layer_job_planes* jobs, const mh_icp_params* params,
+                                       int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
+                                       mh_icp_result* results, uint64_t* final_pair_counts) {
+  MH_REQUIRE_AS(who, n_jobs >= 1 && n_jobs <= MH_MAX_LAYER_BATCH_JOBS, "n_jobs must be 1 .. MH_MAX_LAYER_BATCH_JOBS");
+  MH_REQUIRE_AS(who, jobs && params && T_guesses && results, "null argument");
   auto P = [&](size_t i) { return params_per_job ? &params[i] : params; };
+  auto ctx_of = [&](size_t i) { return jobs[i].pairs[0].scan->ctx; };
   // everything is checked before anything is queued: after an error no context has seen any work (and no claim epoch is taken)
+  LayersView v[MH_MAX_LAYER_BATCH_JOBS];
   for (size_t i = 0; i < n_jobs; i++) {
-    MH_TRY(check_layers_args(jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, &results[i]));
-    for (size_t k = 0; k < i; k++)
-      MH_REQUIRE(jobs[k].pairs[0].scan->ctx != jobs[i].pairs[0].scan->ctx, "each job of a batch needs its own context");
-    MH_REQUIRE(jobs[i].pairs[0].scan->ctx->device == jobs[0].pairs[0].scan->ctx->device, "the jobs of a batch live on different devices");
-    for (size_t k = 0; jobs[i].knn && k < jobs[i].n_pairs; k++)
-      MH_REQUIRE(jobs[i].knn[k].pairings_per_point <= MH_MAX_PAIRINGS_PER_POINT, "pairings_per_point must be 0 .. MH_MAX_PAIRINGS_PER_POINT");
-    MH_TRY(check_layers_planes(jobs[i].n_pairs, jobs[i].pairs, jobs[i].opts, jobs[i].knn, jobs[i].planes, P(i)));
+    v[i].d = jobs[i];
+    MH_TRY(check_layers_job(who, LayerRules::Arguments, v[i], P(i), T_guesses + 12 * i, &results[i]));
+    for (size_t k = 0; k < i; k++) MH_REQUIRE_AS(who, ctx_of(k) != ctx_of(i), "each job of a batch needs its own context");
+    MH_REQUIRE_AS(who, ctx_of(i)->device == ctx_of(0)->device, "the jobs of a batch live on different devices");
   }
-  for (size_t i = 0; i < n_jobs; i++) {
-    MH_TRY(check_layers_supported(jobs[i].n_pairs, jobs[i].pairs, P(i)));
-    for (size_t k = 0; k < jobs[i].n_pairs; k++) {
-      const mh_layer_pair& pr = jobs[i].pairs[k];
-      if (pr.map->n_records >= kFlatMaxRecords)
-        return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers: a map of 2^30 or more records");
-      // (what mh_icp_align_layers_kbest refuses before, and LayersJob::claims_begin inside, its start())
-      const uint64_t entries = (uint64_t)pr.scan->n * job_kpp(jobs[i], k);
-      if (jobs[i].knn && entries >= (1ull << 32))
-        return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_batch_opts: scan size * pairings_per_point does not fit 32 bits");
-      if (job_unique(jobs[i], k) && entries >= kClaimMaxScan)
-        return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_batch_opts: a unique pair with 2^29 or more pairing entries");
-      if (job_unique(jobs[i], k) && pr.map->n_offered >= kClaimMaxEntries)
-        return fail(MH_ERR_UNSUPPORTED, "mh_icp_align_layers_batch_opts: a unique pair whose map has been offered 2^28 or more points");
-    }
-  }
+  for (size_t i = 0; i < n_jobs; i++)
+    MH_TRY(check_layers_job(who, LayerRules::Supported, v[i], P(i), T_guesses + 12 * i, &results[i]));
   const Switches sw = read_switches();
   auto counts_of = [&](size_t i) { return final_pair_counts ? final_pair_counts + i * MH_MAX_LAYER_PAIRS : nullptr; };
-  // (as mh_icp_align_layers_planes hands them on: an array without a plane pair is no array)
-  auto planes_of = [&](size_t i) { return job_has_plane(jobs[i]) ? jobs[i].planes : nullptr; };
   if (final_pair_counts)
     for (size_t i = 0; i < n_jobs * MH_MAX_LAYER_PAIRS; i++) final_pair_counts[i] = 0;
   // lock-step groups: same inner steps, same covariance switch, a pair with k > 1 or none, and a plane pair or none (the launches of
   // a chunk are the same for every job of a group; unique pairs and gates do not change them: a job without a unique pair owns no
   // claim workgroup)
-  auto has_kbest = [&](size_t i) {
-    bool any = false;
-    for (size_t k = 0; k < jobs[i].n_pairs; k++) any = any || job_kpp(jobs[i], k) > 1u;
-    return any;
-  };
   std::vector<LayersJob> lj(n_jobs);
   std::vector<std::vector<size_t>> groups;
   std::vector<char> in_group(n_jobs, 0);
   if (!sw.no_lockstep) {
     for (size_t i = 0; i < n_jobs; i++) {
       const mh_icp_params* q = P(i);
-      // (LayersJob::potential_in(0): the entries of the pairs that are active in iteration 0)
-      uint64_t potential0 = 0;
-      for (size_t k = 0; k < jobs[i].n_pairs; k++)
-        if (!jobs[i].gates || jobs[i].gates[k].run_from_iteration == 0) potential0 += (uint64_t)jobs[i].pairs[k].scan->n * job_kpp(jobs[i], k);
-      if (q->max_iterations == 0 || potential0 == 0) continue;  // trivial: nothing to run
+      if (q->max_iterations == 0 || v[i].potential_in(0) == 0) continue;  // trivial: nothing to run
       std::vector<size_t>* g = nullptr;
       for (auto& c : groups)
         if (P(c[0])->gn.max_inner_iterations == q->gn.max_inner_iterations &&
-            (P(c[0])->compute_covariance != 0) == (q->compute_covariance != 0) && has_kbest(c[0]) == has_kbest(i) &&
-            job_has_plane(jobs[c[0]]) == job_has_plane(jobs[i]))
+            (P(c[0])->compute_covariance != 0) == (q->compute_covariance != 0) && v[c[0]].has_knn() == v[i].has_knn() &&
+            v[c[0]].has_plane() == v[i].has_plane())
           g = &c;
       if (!g) {
         groups.emplace_back();
@@ -251,8 +218,7 @@ mh_status mh_icp_align_layers_batch_planes(size_t n_jobs, const mh_layer_job_pla
     if (c.size() < 2) continue;  // a job alone in its group gains nothing from lock step
     std::vector<LayersJob*> g;
     for (size_t i : c) {
-      MH_TRY(lj[i].start(sw, (uint32_t)jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr,
-                         &results[i], nullptr, counts_of(i), jobs[i].opts, jobs[i].gates, jobs[i].knn, planes_of(i)));
+      MH_TRY(lj[i].start(sw, v[i], P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr, &results[i], nullptr, counts_of(i)));
       g.push_back(&lj[i]);
     }
     MH_TRY(align_layers_lockstep(g));
@@ -260,31 +226,34 @@ mh_status mh_icp_align_layers_batch_planes(size_t n_jobs, const mh_layer_job_pla
   }
   for (size_t i = 0; i < n_jobs; i++)
     if (!in_group[i])
-      MH_TRY(align_layers(sw, (uint32_t)jobs[i].n_pairs, jobs[i].pairs, P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr,
-                          &results[i], nullptr, nullptr, counts_of(i), MH_MEM_HOST, jobs[i].opts, jobs[i].gates, jobs[i].knn,
-                          planes_of(i)));
+      MH_TRY(align_layers(sw, v[i], P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr, &results[i], nullptr, nullptr, nullptr,
+                          counts_of(i), MH_MEM_HOST));
   return MH_OK;
 }
 
-// (the shared implementation with no planes: the checks, the groups, the uploads and the launches it always had)
+// Three spellings of one call: each hands its jobs on as mh_layer_job_planes, the arrays it does not take NULL.
+mh_status mh_icp_align_layers_batch_planes(size_t n_jobs, const mh_layer_job_planes* jobs, const mh_icp_params* params,
+                                           int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
+                                           mh_icp_result* results, uint64_t* final_pair_counts) {
+  return align_layers_batch_as(__func__, n_jobs, jobs, params, params_per_job, T_guesses, priors, results, final_pair_counts);
+}
+
 mh_status mh_icp_align_layers_batch_opts(size_t n_jobs, const mh_layer_job_opts* jobs, const mh_icp_params* params,
                                          int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
                                          mh_icp_result* results, uint64_t* final_pair_counts) {
-  MH_REQUIRE(n_jobs >= 1 && n_jobs <= MH_MAX_LAYER_BATCH_JOBS, "n_jobs must be 1 .. MH_MAX_LAYER_BATCH_JOBS");
-  MH_REQUIRE(jobs, "null argument");
   mh_layer_job_planes jp[MH_MAX_LAYER_BATCH_JOBS];
-  for (size_t i = 0; i < n_jobs; i++)
+  for (size_t i = 0; jobs && i < n_jobs && i < MH_MAX_LAYER_BATCH_JOBS; i++)
     jp[i] = mh_layer_job_planes{jobs[i].n_pairs, jobs[i].pairs, jobs[i].opts, jobs[i].gates, jobs[i].knn, nullptr};
-  return mh_icp_align_layers_batch_planes(n_jobs, jp, params, params_per_job, T_guesses, priors, results, final_pair_counts);
+  return align_layers_batch_as(__func__, n_jobs, jobs ? jp : nullptr, params, params_per_job, T_guesses, priors, results,
+                               final_pair_counts);
 }
 
-// (the shared implementation with no opts, gates or knn: the checks, the groups, the uploads and the launches it always had)
 mh_status mh_icp_align_layers_batch(size_t n_jobs, const mh_layer_job* jobs, const mh_icp_params* params, int32_t params_per_job,
                                     const double* T_guesses, const mh_prior* const* priors, mh_icp_result* results,
                                     uint64_t* final_pair_counts) {
-  MH_REQUIRE(n_jobs >= 1 && n_jobs <= MH_MAX_LAYER_BATCH_JOBS, "n_jobs must be 1 .. MH_MAX_LAYER_BATCH_JOBS");
-  MH_REQUIRE(jobs, "null argument");
-  mh_layer_job_opts jo[MH_MAX_LAYER_BATCH_JOBS];
-  for (size_t i = 0; i < n_jobs; i++) jo[i] = mh_layer_job_opts{jobs[i].n_pairs, jobs[i].pairs, nullptr, nullptr, nullptr};
-  return mh_icp_align_layers_batch_opts(n_jobs, jo, params, params_per_job, T_guesses, priors, results, final_pair_counts);
+  mh_layer_job_planes jp[MH_MAX_LAYER_BATCH_JOBS];
+  for (size_t i = 0; jobs && i < n_jobs && i < MH_MAX_LAYER_BATCH_JOBS; i++)
+    jp[i] = mh_layer_job_planes{jobs[i].n_pairs, jobs[i].pairs, nullptr, nullptr, nullptr, nullptr};
+  return align_layers_batch_as(__func__, n_jobs, jobs ? jp : nullptr, params, params_per_job, T_guesses, priors, results,
+                               final_pair_counts);
 }

@@ -82,6 +82,7 @@
 #include <vector>
 
 #include "molahip_mrpt_common.h"        // device session, map mirror, MOLA_HIP_* switches
+#include "molahip_host/layer_job_builder.h"  // one multi-layer alignment as the library takes it
 #include "molahip_host/hook_replay.h"  // the opaque iteration hook on the fused loop (compiled + tested via host/src/icp.cpp)
 
 namespace mp2p_icp
@@ -137,10 +138,6 @@ struct LayerShape
     std::vector<const Matcher_Point2Plane*> plane_matchers;         // ... the plane matcher
     const Solver_GaussNewton* gn = nullptr;
     std::vector<Entry> entries;
-    bool any_unique = false;  // some matcher has allowMatchAlreadyMatchedGlobalPoints false (U13)
-    bool any_gate = false;    // some matcher has runFromIteration / runUpToIteration (MOLA_HIP_FUSE_GATES=1)
-    bool any_knn = false;     // some matcher has pairingsPerPoint > 1 (MOLA_HIP_FUSE_KBEST=1)
-    bool any_plane = false;   // some matcher is a Matcher_Point2Plane (MOLA_HIP_FUSE_PLANES=1)
 };
 
 template <class M> bool single_unit_layer(const M& m, std::string& g, std::string& l, double* weight_out = nullptr)
@@ -390,16 +387,19 @@ class ICP_HIP : public ICP
     {
         if (solvers().size() != 1 || !(ls.gn = dynamic_cast<const Solver_GaussNewton*>(solvers()[0].get()))) return false;
         bool skip_paired = false;  // some matcher leaves points an earlier one paired out (U12, MOLA_HIP_MATCHED_POINTS=skip)
+        // an entry of a unique (U13), gated, pairingsPerPoint > 1 or plane matcher: shapes only the multi-layer loop takes, a
+        // single pair included
+        bool single_pair_ok = false;
+        const auto& sw = molahip_host::plugin_switches();
         for (const auto& mp : matchers())
         {
             if (const auto* pl = dynamic_cast<const Matcher_Point2Plane*>(mp.get()))
             {   // rgbd.yaml:143-151 on point layers: mh_icp_align_layers_planes, when asked for (an NDT layer: align_layers decides)
-                if (!molahip_host::fuse_planes(false, molahip_host::plugin_switches())) return false;
+                if (!molahip_host::fuse_allowed(sw.fuse_planes, false)) return false;
                 if (!pl->enabled || pl->knn < 3 || pl->knn > MH_MAX_PLANE_KNN || pl->maxLocalPointsPerLayer_ != 0) return false;
                 if (pl->runFromIteration != 0 || pl->runUpToIteration != 0)
                 {
-                    if (!molahip_host::fuse_gates(false, molahip_host::plugin_switches())) return false;
-                    if (!pl->weight_pt2pt_layers.empty()) ls.any_gate = true;
+                    if (!molahip_host::fuse_allowed(sw.fuse_gates, false)) return false;
                 }
                 if (!pl->allowMatchAlreadyMatchedPoints_ && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP)
                     skip_paired = true;
@@ -415,7 +415,7 @@ class ICP_HIP : public ICP
                         e.localLayer = lname;
                         e.weight = w;
                         ls.entries.push_back(e);
-                        ls.any_plane = true;
+                        single_pair_ok = true;
                     }
                 continue;
             }
@@ -423,17 +423,16 @@ class ICP_HIP : public ICP
             if (!m || !m->enabled) return false;
             if (m->pairingsPerPoint != 1)  // lidar2d.yaml:156, rgbd.yaml:138: mh_icp_align_layers_kbest, when asked for
             {
-                if (!molahip_host::fuse_kbest(false, molahip_host::plugin_switches())) return false;
+                if (!molahip_host::fuse_allowed(sw.fuse_kbest, false)) return false;
                 if (m->pairingsPerPoint < 1 || m->pairingsPerPoint > MH_MAX_PAIRINGS_PER_POINT) return false;
-                if (!m->weight_pt2pt_layers.empty()) ls.any_knn = true;
             }
             if (m->runFromIteration != 0 || m->runUpToIteration != 0)  // [U] iteration gates: the device tests them per pair
             {
-                if (!molahip_host::fuse_gates(false, molahip_host::plugin_switches())) return false;
-                if (!m->weight_pt2pt_layers.empty()) ls.any_gate = true;
+                if (!molahip_host::fuse_allowed(sw.fuse_gates, false)) return false;
             }
-            // U13: a matcher that pairs a map point once per iteration (the claims of mh_icp_align_layers_opts)
-            if (!m->allowMatchAlreadyMatchedGlobalPoints && !m->weight_pt2pt_layers.empty()) ls.any_unique = true;
+            // (U13: a matcher that pairs a map point once per iteration takes the claims of mh_icp_align_layers_opts)
+            if (!m->allowMatchAlreadyMatchedGlobalPoints || m->pairingsPerPoint != 1 || m->runFromIteration != 0 || m->runUpToIteration != 0)
+                single_pair_ok = single_pair_ok || !m->weight_pt2pt_layers.empty();
             if (!m->allowMatchAlreadyMatchedPoints_ && molahip_host::plugin_switches().matched_points == MH_MATCHED_POINTS_SKIP)
                 skip_paired = true;
             ls.matchers.push_back(m);
@@ -450,7 +449,7 @@ class ICP_HIP : public ICP
                     ls.entries.push_back(e);
                 }
         }
-        if (ls.entries.size() < (ls.any_unique || ls.any_gate || ls.any_knn || ls.any_plane ? 1u : 2u) || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
+        if (ls.entries.size() < (single_pair_ok ? 1u : 2u) || ls.entries.size() > MH_MAX_LAYER_PAIRS) return false;
         for (size_t i = 0; i < ls.entries.size(); i++)
             for (size_t j = i + 1; j < ls.entries.size(); j++)
                 if (skip_paired && ls.entries[i].localLayer == ls.entries[j].localLayer) return false;
@@ -469,47 +468,41 @@ class ICP_HIP : public ICP
         if (!dev_) dev_ = std::make_unique<molahip_mrpt::DeviceSession>();
         const size_t np = ls.entries.size();
         std::vector<const mrpt::maps::CPointsMap*> locals(np);
-        std::vector<mh_layer_pair> pairs(np);
-        std::vector<mh_layer_pair_opts> opts(np);
-        std::vector<mh_layer_pair_gates> gates(np);
-        std::vector<mh_layer_pair_knn> knn(np);
-        std::vector<mh_layer_pair_plane> planes(np);
+        molahip_host::LayerJobBuilder jb;  // each entry with its matcher's options
         for (size_t i = 0; i < np; i++)
         {
             const auto& e = ls.entries[i];
-            if (e.pl)
-            {   // a plane pairing names no map point (nothing to claim); on a layer with NDT statistics the matcher means the
-                // per-voxel planes, which this loop does not run
-                if (dev_->carries_ndt(*pcGlobal.layers.at(e.globalLayer)))
-                    return upstream_align(pcLocal, pcGlobal, guess, p, result, prior, outputDebugInfo);
-                knn[i].pairings_per_point = 1;
-                gates[i].run_from_iteration = e.pl->runFromIteration;
-                gates[i].run_up_to_iteration = e.pl->runUpToIteration;
-                planes[i].knn = e.pl->knn;
-                planes[i].minimum_plane_points = e.pl->minimumPlanePoints;
-                planes[i].plane_eigen_threshold = e.pl->planeEigenThreshold;
-                planes[i].search_radius = e.pl->searchRadius;
-            }
-            else
-            {
-                knn[i].pairings_per_point = static_cast<uint32_t>(e.m->pairingsPerPoint);
-                opts[i].unique_global = e.m->allowMatchAlreadyMatchedGlobalPoints ? 0u : 1u;
-                gates[i].run_from_iteration = e.m->runFromIteration;
-                gates[i].run_up_to_iteration = e.m->runUpToIteration;
-            }
+            // a plane pairing names no map point (nothing to claim); on a layer with NDT statistics the matcher means the
+            // per-voxel planes, which this loop does not run
+            if (e.pl && dev_->carries_ndt(*pcGlobal.layers.at(e.globalLayer)))
+                return upstream_align(pcLocal, pcGlobal, guess, p, result, prior, outputDebugInfo);
             mh_map* m = dev_->device_map_of(*pcGlobal.layers.at(e.globalLayer), false);  // every global layer mirrored
             locals[i] = dynamic_cast<const mrpt::maps::CPointsMap*>(pcLocal.layers.at(e.localLayer).get());
             if (!m || !locals[i]) return upstream_align(pcLocal, pcGlobal, guess, p, result, prior, outputDebugInfo);
-            pairs[i].map = m;
-            pairs[i].threshold_angular_deg = e.pl ? 0.0 : e.m->thresholdAngularDeg;
-            pairs[i].weight = e.weight;  // Pairings::point_weights [U]: the entry's own weight
+            mh_layer_pair lp{};
+            lp.map = m;
+            lp.threshold_angular_deg = e.pl ? 0.0 : e.m->thresholdAngularDeg;
+            lp.weight = e.weight;  // Pairings::point_weights [U]: the entry's own weight
+            mh_layer_pair_gates lg{};
+            mh_layer_pair_plane lpl{};
+            lg.run_from_iteration = e.pl ? e.pl->runFromIteration : e.m->runFromIteration;
+            lg.run_up_to_iteration = e.pl ? e.pl->runUpToIteration : e.m->runUpToIteration;
+            if (e.pl)
+            {
+                lpl.knn = e.pl->knn;
+                lpl.minimum_plane_points = e.pl->minimumPlanePoints;
+                lpl.plane_eigen_threshold = e.pl->planeEigenThreshold;
+                lpl.search_radius = e.pl->searchRadius;
+            }
+            jb.push(lp, e.m && !e.m->allowMatchAlreadyMatchedGlobalPoints, lg, e.m ? static_cast<uint32_t>(e.m->pairingsPerPoint) : 1u, lpl);
         }
         for (size_t i = 0; i < np; i++)  // every local layer uploaded (a layer named twice: once)
         {
             size_t first = i;
             for (size_t j = 0; j < i; j++) if (locals[j] == locals[i]) { first = j; break; }
-            pairs[i].scan = first == i ? dev_->upload(*locals[i], &locals) : pairs[first].scan;
+            jb.pair(i).scan = first == i ? dev_->upload(*locals[i], &locals) : jb.pair(first).scan;
         }
+        const mh_layer_job_planes job = jb.job();
         mrpt::system::CTimeLoggerEntry tle(profiler(), "align_hip");
 
         // every matcher's threshold and the solver's kernel parameter per ICP_ITERATION, lazily as in align()
@@ -547,28 +540,27 @@ class ICP_HIP : public ICP
             for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) pr.info[i * 6 + j] = prior->cov_inv(i, j);
         }
         if (layer_pairs_.size() < np) layer_pairs_.resize(np);
-        if (ls.any_plane && layer_planes_.size() < np) layer_planes_.resize(np);
+        if (jb.has_plane() && layer_planes_.size() < np) layer_planes_.resize(np);
         std::vector<mh_pairs_out> po(np);
         std::vector<mh_pairs_pl_out> ppl(np);
         std::vector<uint64_t> counts(np, 0);
         size_t n_local = 0;
         for (size_t i = 0; i < np; i++)
         {
-            if (planes[i].knn) ppl[i] = layer_planes_[i].out(locals[i]->getPointsBufferRef_x().size());
-            else po[i] = layer_pairs_[i].out(locals[i]->getPointsBufferRef_x().size() * knn[i].pairings_per_point);
+            if (jb.is_plane(i)) ppl[i] = layer_planes_[i].out(locals[i]->getPointsBufferRef_x().size());
+            else po[i] = layer_pairs_[i].out(locals[i]->getPointsBufferRef_x().size() * jb.pairings_per_point(i));
             n_local += locals[i]->getPointsBufferRef_x().size();
         }
         auto run_with = [&](uint32_t budget, mh_icp_iter* trace) {
             ensure_schedule(budget);
-            for (size_t i = 0; i < np; i++) pairs[i].threshold = thr[ls.entries[i].matcher].data();
+            for (size_t i = 0; i < np; i++) jb.pair(i).threshold = thr[ls.entries[i].matcher].data();
             mh_icp_params q = ip;
             q.max_iterations = budget;
             q.kernel_param   = kp.data();
             mh_icp_result rr{};
-            mh_check(mh_icp_align_layers_planes(np, pairs.data(), ls.any_unique ? opts.data() : nullptr,
-                                                ls.any_gate ? gates.data() : nullptr, ls.any_knn ? knn.data() : nullptr,
-                                                ls.any_plane ? planes.data() : nullptr, &q, T0, prior ? &pr : nullptr, &rr, trace,
-                                                po.data(), ls.any_plane ? ppl.data() : nullptr, counts.data(), MH_MEM_HOST),
+            mh_check(mh_icp_align_layers_planes(job.n_pairs, job.pairs, job.opts, job.gates, job.knn, job.planes, &q, T0,
+                                                prior ? &pr : nullptr, &rr, trace, po.data(), jb.has_plane() ? ppl.data() : nullptr,
+                                                counts.data(), MH_MEM_HOST),
                      "mh_icp_align_layers_planes");
             return rr;
         };
@@ -619,7 +611,7 @@ class ICP_HIP : public ICP
             const auto& lx = locals[i]->getPointsBufferRef_x();
             const auto& ly = locals[i]->getPointsBufferRef_y();
             const auto& lz = locals[i]->getPointsBufferRef_z();
-            if (planes[i].knn)
+            if (jb.is_plane(i))
             {   // Pairings::paired_pt2pl [U]: {pl_global{plane, centroid}, pt_local}
                 const auto& q = layer_planes_[i];
                 for (uint64_t k = 0; k < counts[i]; k++)

@@ -122,12 +122,9 @@ inline const PluginSwitches& plugin_switches() { return plugin_switches_storage(
 /** Re-read the environment (tests; a sweep driver that changes the variables inside one process). */
 inline void reload_plugin_switches() { plugin_switches_storage() = read_plugin_switches(); }
 
-/** Whether gated matchers go to the fused multi-layer loop: the environment when it says so, else the caller's `setting`. */
-inline bool fuse_gates(bool setting, const PluginSwitches& sw) { return sw.fuse_gates < 0 ? setting : sw.fuse_gates != 0; }
-/** The same for matchers with pairingsPerPoint > 1. */
-inline bool fuse_kbest(bool setting, const PluginSwitches& sw) { return sw.fuse_kbest < 0 ? setting : sw.fuse_kbest != 0; }
-/** The same for Matcher_Point2Plane on point layers (KNN + PCA). */
-inline bool fuse_planes(bool setting, const PluginSwitches& sw) { return sw.fuse_planes < 0 ? setting : sw.fuse_planes != 0; }
+/** Whether a kind of matcher goes to the fused multi-layer loop (`switch_value`: PluginSwitches::fuse_gates, fuse_kbest or
+ *  fuse_planes): the environment when it says so, else the caller's `setting`. */
+inline bool fuse_allowed(int switch_value, bool setting) { return switch_value < 0 ? setting : switch_value != 0; }
 
 /** MH_KERNEL_* for the NAME of an upstream mp2p_icp::RobustKernel enumerator [U] (names, not numeric values: the
  *  upstream enum's values are not relied on).  "GemanMcClure" resolves to the switched form. */

@@ -392,7 +392,7 @@ class QualityEvaluator_PairedRatio {
 // mh_icp_align it hands its request to the batcher and blocks; when ALL active participants are waiting, the last one
 // to arrive runs ONE mh_icp_align_batch over the requests (per-job parameters: every sequence has its own adaptive
 // threshold, iteration budget, hook check point; jobs with the same kernel chain advance in lock step) -- and ONE
-// mh_icp_align_layers_batch over the multi-layer requests among them (mh_icp_align_layers_batch_opts when one of them has a unique pair, a gate or pairingsPerPoint > 1, mh_icp_align_layers_batch_planes when one has a Matcher_Point2Plane pair) -- and wakes the others.  Results are bitwise those of separate alignments, so every sequence's records are those of a solo run.
+// mh_icp_align_layers_batch_planes over the multi-layer requests among them, each with the job description it came with -- and wakes the others.  Results are bitwise those of separate alignments, so every sequence's records are those of a solo run.
 class AlignBatcher {
  public:
   explicit AlignBatcher(size_t participants);
@@ -400,15 +400,12 @@ class AlignBatcher {
   // `owner`: any address that identifies the participant (the same one in every call it makes; nullptr: the scan)
   mh_status align(const void* owner, const mh_map* map, const mh_scan* scan, const mh_icp_params* params, const double T_guess[12],
                   const mh_prior* prior, mh_icp_result* result, std::string* error);
-  // The same for a multi-layer alignment (mh_icp_align_layers; `pairs` all on the participant's own context): the multi-layer
-  // requests of a batch run as ONE mh_icp_align_layers_batch beside the single-pair ones' mh_icp_align_batch.  `opts`, `gates`,
-  // `knn`: what mh_icp_align_layers_kbest takes (n_pairs entries or null each); with one of them in any request of a batch the
-  // batch is ONE mh_icp_align_layers_batch_opts.  `planes`: what mh_icp_align_layers_planes takes beside them; with it in any
-  // request the batch is ONE mh_icp_align_layers_batch_planes.
-  mh_status alignLayers(const void* owner, size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params,
-                        const double T_guess[12], const mh_prior* prior, mh_icp_result* result, std::string* error,
-                        const mh_layer_pair_opts* opts = nullptr, const mh_layer_pair_gates* gates = nullptr,
-                        const mh_layer_pair_knn* knn = nullptr, const mh_layer_pair_plane* planes = nullptr);
+  // The same for a multi-layer alignment, described as the library takes it (`job`: the pairs, all on the participant's own
+  // context, and their opts, gates, knn and planes, each n_pairs entries or null; molahip_host::LayerJobBuilder makes one).  The
+  // multi-layer requests of a batch run as ONE mh_icp_align_layers_batch_planes beside the single-pair ones' mh_icp_align_batch --
+  // with the arrays null that is, bit for bit, the narrower entry point.
+  mh_status alignLayers(const void* owner, const mh_layer_job_planes& job, const mh_icp_params* params, const double T_guess[12],
+                        const mh_prior* prior, mh_icp_result* result, std::string* error);
   // An alignment that has no batched form (the matcher/solver-granular loop): `fn` runs on the caller's thread at once, and
   // meanwhile the participant counts as one that is not waiting, so the others' batches are not held up for it.
   void runOutside(const void* owner, const std::function<void()>& fn);
@@ -460,12 +457,7 @@ class AlignBatcher {
   struct Request {
     const mh_map* map = nullptr;
     const mh_scan* scan = nullptr;
-    size_t n_pairs = 0;                    // a multi-layer request: its pairs (map and scan are null)
-    const mh_layer_pair* pairs = nullptr;
-    const mh_layer_pair_opts* opts = nullptr;    // ... and what mh_icp_align_layers_kbest takes beside them (null: none)
-    const mh_layer_pair_gates* gates = nullptr;
-    const mh_layer_pair_knn* knn = nullptr;
-    const mh_layer_pair_plane* planes = nullptr;  // ... and mh_icp_align_layers_planes
+    mh_layer_job_planes job = {};  // a multi-layer request: its description (map and scan are null)
     const mh_icp_params* params = nullptr;
     const double* T = nullptr;
     const mh_prior* prior = nullptr;

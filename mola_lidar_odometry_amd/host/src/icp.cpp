@@ -13,6 +13,7 @@
 
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 #include "molahip_host/hook_replay.h"
+#include "molahip_host/layer_job_builder.h"
 #include "molahip_host/plugin_switches.h"
 
 namespace mp2p_icp_hip {
@@ -654,9 +655,9 @@ bool ICP::can_fuse_layers() const {
   if (matchers_.empty() || solvers_.size() != 1 || !std::dynamic_pointer_cast<Solver_GaussNewton>(solvers_[0])) return false;
   std::vector<std::string> locals;
   bool single_pair_ok = false;  // a unique or gated matcher: shapes only the multi-layer loop takes, a single pair included
-  const bool gates_ok = molahip_host::fuse_gates(fuse_gated_, molahip_host::plugin_switches());
-  const bool kbest_ok = molahip_host::fuse_kbest(fuse_kbest_, molahip_host::plugin_switches());
-  const bool planes_ok = molahip_host::fuse_planes(fuse_planes_, molahip_host::plugin_switches());
+  const bool gates_ok = molahip_host::fuse_allowed(molahip_host::plugin_switches().fuse_gates, fuse_gated_);
+  const bool kbest_ok = molahip_host::fuse_allowed(molahip_host::plugin_switches().fuse_kbest, fuse_kbest_);
+  const bool planes_ok = molahip_host::fuse_allowed(molahip_host::plugin_switches().fuse_planes, fuse_planes_);
   for (const auto& mm : matchers_) {
     if (auto pl = std::dynamic_pointer_cast<Matcher_Point2Plane>(mm)) {
       if (!planes_ok || !pl->enabled || pl->knn < 3 || pl->knn > MH_MAX_PLANE_KNN) return false;
@@ -754,20 +755,16 @@ void AlignBatcher::run_batch(std::vector<Request*>& batch) {
   std::vector<mh_icp_result> results(n);
   std::vector<mh_status> sts(n, MH_OK);
   std::vector<std::string> errs(n);
-  // the single-pair requests as one mh_icp_align_batch, the multi-layer ones as one mh_icp_align_layers_batch (_opts when one
-  // of them has a unique pair, a gate or pairingsPerPoint > 1, _planes when one has a Matcher_Point2Plane pair)
+  // the single-pair requests as one mh_icp_align_batch, the multi-layer ones as one mh_icp_align_layers_batch_planes
   for (const bool layers : {false, true}) {
     std::vector<size_t> idx;
     for (size_t i = 0; i < n; i++)
-      if ((batch[i]->pairs != nullptr) == layers) idx.push_back(i);
+      if ((batch[i]->job.pairs != nullptr) == layers) idx.push_back(i);
     const size_t m = idx.size();
     if (!m) continue;
     std::vector<const mh_map*> maps(m);
     std::vector<const mh_scan*> scans(m);
-    std::vector<mh_layer_job> jobs(m);
-    std::vector<mh_layer_job_opts> jobs_opts(m);
-    std::vector<mh_layer_job_planes> jobs_planes(m);
-    bool any_opts = false, any_planes = false;
+    std::vector<mh_layer_job_planes> jobs(m);
     std::vector<mh_icp_params> params(m);
     std::vector<double> T(12 * m);
     std::vector<const mh_prior*> priors(m);
@@ -777,34 +774,23 @@ void AlignBatcher::run_batch(std::vector<Request*>& batch) {
       const Request& rq = *batch[idx[k]];
       maps[k] = rq.map;
       scans[k] = rq.scan;
-      jobs[k].n_pairs = rq.n_pairs;
-      jobs[k].pairs = rq.pairs;
-      jobs_opts[k] = mh_layer_job_opts{rq.n_pairs, rq.pairs, rq.opts, rq.gates, rq.knn};
-      any_opts = any_opts || rq.opts || rq.gates || rq.knn;
-      jobs_planes[k] = mh_layer_job_planes{rq.n_pairs, rq.pairs, rq.opts, rq.gates, rq.knn, rq.planes};
-      any_planes = any_planes || rq.planes;
+      jobs[k] = rq.job;
       params[k] = *rq.params;
       memcpy(&T[12 * k], rq.T, 12 * sizeof(double));
       priors[k] = rq.prior;
       any_prior = any_prior || rq.prior;
     }
     auto one = [&](size_t k) {
-      return layers ? mh_icp_align_layers_planes(jobs[k].n_pairs, jobs[k].pairs, jobs_opts[k].opts, jobs_opts[k].gates, jobs_opts[k].knn,
-                                                 jobs_planes[k].planes, &params[k], &T[12 * k], priors[k], &res[k], nullptr, nullptr,
-                                                 nullptr, nullptr, MH_MEM_HOST)
+      return layers ? mh_icp_align_layers_planes(jobs[k].n_pairs, jobs[k].pairs, jobs[k].opts, jobs[k].gates, jobs[k].knn, jobs[k].planes,
+                                                 &params[k], &T[12 * k], priors[k], &res[k], nullptr, nullptr, nullptr, nullptr, MH_MEM_HOST)
                     : mh_icp_align(maps[k], scans[k], &params[k], &T[12 * k], priors[k], &res[k], nullptr, nullptr, MH_MEM_HOST);
     };
     mh_status st = MH_OK;
     if (m == 1) {
       st = one(0);
-    } else if (layers && any_planes) {
-      st = mh_icp_align_layers_batch_planes(m, jobs_planes.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr,
-                                            res.data(), nullptr);
-    } else if (layers && any_opts) {
-      st = mh_icp_align_layers_batch_opts(m, jobs_opts.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr, res.data(),
-                                          nullptr);
     } else if (layers) {
-      st = mh_icp_align_layers_batch(m, jobs.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr, res.data(), nullptr);
+      st = mh_icp_align_layers_batch_planes(m, jobs.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr, res.data(),
+                                            nullptr);
     } else {
       st = mh_icp_align_batch(m, maps.data(), scans.data(), params.data(), 1, T.data(), any_prior ? priors.data() : nullptr,
                               res.data(), nullptr, MH_MEM_HOST);
@@ -840,15 +826,12 @@ void AlignBatcher::run_batch(std::vector<Request*>& batch) {
   cv_.notify_all();
 }
 
-mh_status AlignBatcher::alignLayers(const void* owner, size_t n_pairs, const mh_layer_pair* pairs, const mh_icp_params* params,
-                                    const double T_guess[12], const mh_prior* prior, mh_icp_result* result, std::string* error,
-                                    const mh_layer_pair_opts* opts, const mh_layer_pair_gates* gates, const mh_layer_pair_knn* knn,
-                                    const mh_layer_pair_plane* planes) {
+mh_status AlignBatcher::alignLayers(const void* owner, const mh_layer_job_planes& job, const mh_icp_params* params,
+                                    const double T_guess[12], const mh_prior* prior, mh_icp_result* result, std::string* error) {
   Request rq;
-  rq.n_pairs = n_pairs; rq.pairs = pairs; rq.params = params; rq.T = T_guess; rq.prior = prior; rq.result = result;
-  rq.opts = opts; rq.gates = gates; rq.knn = knn; rq.planes = planes;
+  rq.job = job; rq.params = params; rq.T = T_guess; rq.prior = prior; rq.result = result;
   // (no one-launch loops on the multi-layer path: nothing to ask the library; MOLA_HIP_BATCH_SOLO alone issues it at once)
-  return submit(owner ? owner : (const void*)pairs, rq, solo_ ? 1 : 0, error);
+  return submit(owner ? owner : (const void*)job.pairs, rq, solo_ ? 1 : 0, error);
 }
 
 void AlignBatcher::runOutside(const void* owner, const std::function<void()>& fn) {
@@ -1370,9 +1353,9 @@ void ICP::align_fused(const PointCloud* host_local, const DevicePointCloud* dev_
 
 // The multi-layer shapes on the device loop (mh_icp_align_layers).  Pairs in align_generic's matching order: matchers in list
 // order, entries in pointLayerMatches order.  With a batcher set (and neither a trace nor the pairings wanted) the alignment joins
-// those of the other sequences: AlignBatcher::alignLayers, mh_icp_align_layers_batch -- with its unique pairs, gates and
-// pairings per point through mh_icp_align_layers_batch_opts (MOLA_HIP_BATCH_OPTS=0: such an alignment runs on its own instead),
-// with its Matcher_Point2Plane pairs through mh_icp_align_layers_batch_planes (MOLA_HIP_BATCH_PLANES=0: likewise).
+// those of the other sequences: AlignBatcher::alignLayers, mh_icp_align_layers_batch_planes with the job as described here
+// (MOLA_HIP_BATCH_OPTS=0: an alignment with a unique pair, a gate or pairingsPerPoint > 1 runs on its own instead;
+// MOLA_HIP_BATCH_PLANES=0: likewise one with a Matcher_Point2Plane pair).
 void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pcGlobal, const CPose3D& guess, const Parameters& p,
                              Results& result, const std::optional<CPose3DPDFGaussianInf>& prior) {
   const auto t_setup0 = std::chrono::steady_clock::now();
@@ -1409,12 +1392,7 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
     const PointCloud* host = nullptr;
     const DevicePointCloud* dev = nullptr;
   };
-  std::vector<mh_layer_pair> pairs;
-  std::vector<mh_layer_pair_opts> opts;  // U13: a matcher's allowMatchAlreadyMatchedGlobalPoints: false, for each of its entries
-  std::vector<mh_layer_pair_gates> gates;  // a matcher's runFromIteration / runUpToIteration, for each of its entries
-  std::vector<mh_layer_pair_knn> knn;  // a matcher's pairingsPerPoint, for each of its entries
-  std::vector<mh_layer_pair_plane> planes;  // a Matcher_Point2Plane's knn, minimumPlanePoints, planeEigenThreshold, searchRadius
-  bool any_unique = false, any_gate = false, any_knn = false, any_plane = false;
+  molahip_host::LayerJobBuilder jb;  // each entry with its matcher's options
   std::vector<Entry> entries;
   const auto& ctx0 = global_layer(pcGlobal, ms[0].entries()[0].global).context();
   if (scan_ctx_ && scan_ctx_ != ctx0) {
@@ -1452,39 +1430,36 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
       lp.threshold = thr[j].data();
       lp.threshold_angular_deg = ms[j].pt ? ms[j].pt->thresholdAngularDeg : 0.0;
       lp.weight = lm.weight;  // (a plane matcher's entries may differ in weight here: every pair scales its own rows)
-      pairs.push_back(lp);
-      // (a plane pairing names no map point: nothing to claim, whatever the matcher's allowMatchAlreadyMatchedGlobalPoints says)
-      opts.push_back(mh_layer_pair_opts{(ms[j].pt && !ms[j].pt->allowMatchAlreadyMatchedGlobalPoints) ? 1u : 0u});
-      any_unique = any_unique || opts.back().unique_global;
-      gates.push_back(mh_layer_pair_gates{ms[j].base()->runFromIteration, ms[j].base()->runUpToIteration});
-      any_gate = any_gate || ms[j].base()->runFromIteration || ms[j].base()->runUpToIteration;
-      knn.push_back(mh_layer_pair_knn{ms[j].pt ? (uint32_t)ms[j].pt->pairingsPerPoint : 1u});
-      any_knn = any_knn || knn.back().pairings_per_point > 1;
       mh_layer_pair_plane lpl{};
       if (ms[j].pl) {
         lpl.knn = ms[j].pl->knn;
         lpl.minimum_plane_points = ms[j].pl->minimumPlanePoints;
         lpl.plane_eigen_threshold = ms[j].pl->planeEigenThreshold;
         lpl.search_radius = ms[j].pl->searchRadius;
-        any_plane = true;
       }
-      planes.push_back(lpl);
+      // U13: allowMatchAlreadyMatchedGlobalPoints false (a plane pairing names no map point: nothing to claim, whatever the
+      // matcher says); runFromIteration / runUpToIteration; pairingsPerPoint
+      jb.push(lp, ms[j].pt && !ms[j].pt->allowMatchAlreadyMatchedGlobalPoints,
+              mh_layer_pair_gates{ms[j].base()->runFromIteration, ms[j].base()->runUpToIteration},
+              ms[j].pt ? (uint32_t)ms[j].pt->pairingsPerPoint : 1u, lpl);
       entries.push_back(e);
     }
   mh_prior pr;
   if (prior) fill_prior(prior, pr);
   last_setup_seconds_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_setup0).count();
   const bool want_pairs = keep_pairings_;
-  std::vector<std::vector<uint32_t>> li(pairs.size()), gi(pairs.size());
-  std::vector<std::vector<float>> gx(pairs.size()), gy(pairs.size()), gz(pairs.size()), d2(pairs.size());
-  std::vector<mh_pairs_out> po(pairs.size());
-  std::vector<mh_pairs_pl_out> ppl(pairs.size());  // a plane pair's final pairings: li | centroid in gx gy gz | normal in pn
-  std::vector<std::array<std::vector<float>, 3>> pn(pairs.size());
-  std::vector<uint64_t> counts(pairs.size(), 0);
-  for (size_t i = 0; want_pairs && i < pairs.size(); i++) {
-    const size_t n = (entries[i].dev ? entries[i].dev->size() : entries[i].host->size()) * (size_t)knn[i].pairings_per_point;
+  const mh_layer_job_planes job = jb.job();
+  const size_t np = jb.size();
+  std::vector<std::vector<uint32_t>> li(np), gi(np);
+  std::vector<std::vector<float>> gx(np), gy(np), gz(np), d2(np);
+  std::vector<mh_pairs_out> po(np);
+  std::vector<mh_pairs_pl_out> ppl(np);  // a plane pair's final pairings: li | centroid in gx gy gz | normal in pn
+  std::vector<std::array<std::vector<float>, 3>> pn(np);
+  std::vector<uint64_t> counts(np, 0);
+  for (size_t i = 0; want_pairs && i < np; i++) {
+    const size_t n = (entries[i].dev ? entries[i].dev->size() : entries[i].host->size()) * (size_t)jb.pairings_per_point(i);
     li[i].resize(n); gx[i].resize(n); gy[i].resize(n); gz[i].resize(n);
-    if (planes[i].knn) {
+    if (jb.is_plane(i)) {
       for (auto& v : pn[i]) v.resize(n);
       ppl[i] = mh_pairs_pl_out{li[i].data(), gx[i].data(), gy[i].data(), gz[i].data(), pn[i][0].data(), pn[i][1].data(), pn[i][2].data()};
       continue;
@@ -1495,25 +1470,22 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   mh_icp_result r{};
   std::vector<mh_icp_iter> trace(p.generateDebugFiles ? mi : 0);
   auto solo = [&] {
-    check(mh_icp_align_layers_planes(pairs.size(), pairs.data(), any_unique ? opts.data() : nullptr, any_gate ? gates.data() : nullptr,
-                                     any_knn ? knn.data() : nullptr, any_plane ? planes.data() : nullptr, &ip, guess.T,
+    check(mh_icp_align_layers_planes(job.n_pairs, job.pairs, job.opts, job.gates, job.knn, job.planes, &ip, guess.T,
                                      prior ? &pr : nullptr, &r, trace.empty() ? nullptr : trace.data(),
-                                     want_pairs ? po.data() : nullptr, (want_pairs && any_plane) ? ppl.data() : nullptr, counts.data(),
-                                     MH_MEM_HOST), "mh_icp_align_layers_planes");
+                                     want_pairs ? po.data() : nullptr, (want_pairs && jb.has_plane()) ? ppl.data() : nullptr,
+                                     counts.data(), MH_MEM_HOST), "mh_icp_align_layers_planes");
   };
-  if (batcher_ && any_plane && (!molahip_host::plugin_switches().batch_planes || !trace.empty() || want_pairs)) {
+  if (batcher_ && jb.has_plane() && (!molahip_host::plugin_switches().batch_planes || !trace.empty() || want_pairs)) {
     // (MOLA_HIP_BATCH_PLANES=0, the A/B against mh_icp_align_layers_batch_planes, or a trace / the pairings wanted: on its own
     // beside the batches, the participant counted as busy meanwhile)
     batcher_->runOutside(batch_owner_, solo);
-  } else if (batcher_ && (any_unique || any_gate || any_knn) && !molahip_host::plugin_switches().batch_opts) {
-    // (MOLA_HIP_BATCH_OPTS=0, the A/B against mh_icp_align_layers_batch_opts: on its own, the participant counted as busy
+  } else if (batcher_ && (jb.has_unique() || jb.has_gate() || jb.has_knn()) && !molahip_host::plugin_switches().batch_opts) {
+    // (MOLA_HIP_BATCH_OPTS=0, the A/B against the batch: on its own, the participant counted as busy
     // meanwhile -- as align_generic)
     batcher_->runOutside(batch_owner_, solo);
   } else if (batcher_ && trace.empty() && !want_pairs) {
     std::string err;
-    const mh_status st = batcher_->alignLayers(batch_owner_, pairs.size(), pairs.data(), &ip, guess.T, prior ? &pr : nullptr, &r, &err,
-                                               any_unique ? opts.data() : nullptr, any_gate ? gates.data() : nullptr,
-                                               any_knn ? knn.data() : nullptr, any_plane ? planes.data() : nullptr);
+    const mh_status st = batcher_->alignLayers(batch_owner_, job, &ip, guess.T, prior ? &pr : nullptr, &r, &err);
     if (st != MH_OK) throw std::runtime_error(std::string("mh_icp_align_layers_batch: ") + mh_status_string(st) + ": " + err);
   } else {
     solo();
@@ -1530,11 +1502,11 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
   Pairings& fp = result.finalPairings;
   fp.potential_pairings = r.potential_pairings;
   if (!want_pairs) return;
-  for (size_t i = 0; i < pairs.size(); i++) {
+  for (size_t i = 0; i < np; i++) {
     PointCloud downloaded;
     if (entries[i].dev && counts[i]) entries[i].dev->download(downloaded.x, downloaded.y, downloaded.z);
     const PointCloud& local = entries[i].dev ? downloaded : *entries[i].host;
-    if (planes[i].knn) {
+    if (jb.is_plane(i)) {
       const std::vector<float> a[6] = {gx[i], gy[i], gz[i], pn[i][0], pn[i][1], pn[i][2]};
       append_pl_pairs(local, li[i], a, counts[i], fp);
       continue;
