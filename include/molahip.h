@@ -48,7 +48,8 @@ extern "C" {
  * mh_curvature_params and mh_scan_curvature, then the intensity channel's entry points and mh_by_intensity_params,
  * mh_layer_pair_gates and mh_icp_align_layers_gated, mh_layer_pair_knn and mh_icp_align_layers_kbest, mh_layer_pair_plane and
  * mh_icp_align_layers_planes, mh_layer_job_opts and mh_icp_align_layers_batch_opts, mh_layer_job_planes and
- * mh_icp_align_layers_batch_planes: new structs and entry points change no existing layout, and a binder that lacks
+ * mh_icp_align_layers_batch_planes, mh_occmap_params / mh_occmap_info and the mh_occmap_* entry points: new structs and entry
+ * points change no existing layout, and a binder that lacks
  * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
  * built with) and zero-initialises every struct it passes -- a field the binder does not know then reads as its default. */
@@ -889,6 +890,88 @@ MH_API mh_status mh_icp_align_layers_batch_planes(size_t n_jobs, const mh_layer_
                                                   int32_t params_per_job, const double* T_guesses, const mh_prior* const* priors,
                                                   mh_icp_result* results,
                                                   uint64_t* final_pair_counts /* n_jobs * MH_MAX_LAYER_PAIRS entries or NULL */);
+
+/* ------------------------------------------------------------------------------------------------
+ * Occupancy voxel map: the local map class of pipelines/lidar2d.yaml:183-198, mrpt::maps::CVoxelMap [U] -- a log-odds
+ * occupancy map updated by ray tracing and searched through the centres of its occupied voxels.  Upstream's source is not
+ * vendored, so this is a restatement; parity with it is unpinned.  The reading implemented:
+ *
+ * Cells.  A cell is addressed by the packed 3 x 21-bit biased voxel index of mh_map: index = floor(p * (1/resolution)) in
+ *   fp32, un-fused (index_mode as in mh_map_params; a point is inside the key range when |p * (1/resolution)| < 1e6 per axis,
+ *   the test of mh_map).  A new cell starts at log-odds 0.
+ * Log-odds.  Integers with scale 16.  The host derives five integers once, in double (round(v) = floor(v + 0.5)), and the
+ *   device only ever sees them:
+ *     l_hit  = max(1, round(16 ln(prob_hit / (1 - prob_hit))))       l_min = round(16 ln(clamp_min / (1 - clamp_min)))
+ *     l_miss = max(1, round(16 ln((1 - prob_miss) / prob_miss)))     l_max = round(16 ln(clamp_max / (1 - clamp_max)))
+ *     l_occ  = floor(16 ln(t / (1 - t))) + 1,  t = occupied_threshold
+ *   A cell is occupied iff l >= l_occ.  (lidar2d.yaml's values: 14, 14, -47, 47, 7.)
+ * One insert of a layer (vehicle frame) at pose T:
+ *   1. every decimation-th point (0, decimation, ...) is composed with T: fp64, rounded to float, exactly as mh_map_insert;
+ *   2. a point is left out when it is non-finite; else when max_range > 0 and (dx*dx + dy*dy) + dz*dz > max_range*max_range
+ *      with d = p - (float)t in fp32; else when its index leaves the key range (these are counted: mh_occmap_info::n_left_out);
+ *   3. the end cell of every kept point gets one hit;
+ *   4. with ray_trace_free_space, every cell strictly between the cell o of T's translation and the end cell e gets one miss.
+ *      With ad = |e - o| per axis, s = sign(e - o), M = max(ad), these are the M - 1 cells, k = 1 .. M-1,
+ *        o_a + s_a * floor((2 k ad_a + M) / (2 M))   per axis a, in 64-bit integers
+ *      -- the closed form of the sequential integer line walk "add ad to an error vector; on each axis with 2 err >= M, step and
+ *      subtract M".  A cell that several steps or rays name gets one count from each;
+ *   5. the counts (h, m) of the whole insert are applied once per cell, independent of thread order:
+ *        MH_OCC_COUNTED: l = min(l_max, l + h l_hit) when h > 0, then l = max(l_min, l - m l_miss) when m > 0;
+ *        MH_OCC_ONCE:    l = min(l_max, l + l_hit) when h > 0; otherwise l = max(l_min, l - l_miss) when m > 0;
+ *   6. if remove_voxels_farther_than > 0, cells are erased by the rule and metric of mh_map_insert (far_voxel_metric, the
+ *      distance ceil(remove_voxels_farther_than / resolution) in cells), measured from the cell of T's translation.
+ * Search structure.  After every insert the centres ((float)index + 0.5f) * resolution (un-fused) of the occupied cells, in
+ *   ascending packed-key order, are built into an inner uncapped mh_map (max_points_per_voxel = 0) of voxel size V; every
+ *   matcher and ICP entry point takes that mh_map unchanged, and a matcher's global index is the centre's rank in that order.
+ *   Upstream searches a k-d tree over these centres; the 27-voxel search is that search exactly for pair distances <= V.  V
+ *   starts at search_voxel_size (0: 1.0 m) and only grows: mh_occmap_search_map takes the largest radius the coming alignment
+ *   can use and, if it exceeds V, rebuilds the inner map once with V doubled until it suffices.  Results depend on V only
+ *   through exact d2 ties between two centres.
+ * Memory.  An insert writes one 64-bit key per (ray, step) and per end cell; above max_keys_per_pass keys it works in passes
+ *   whose per-cell counts are summed before the rule is applied: the result does not depend on the pass size.  Every pass ends
+ *   in a read-back of its run count, so a pass size far below the key count of an insert is for tests only.
+ * The calls are synchronous (a few counters travel to the host per insert: a key-frame event, not a per-scan one).
+ * ---------------------------------------------------------------------------------------------- */
+enum { MH_OCC_COUNTED = 0, MH_OCC_ONCE = 1 };
+typedef struct mh_occmap mh_occmap;
+typedef struct {
+  float resolution;              /* creationOpts.resolution [m] > 0 */
+  float prob_hit, prob_miss;     /* insertOpts, inside (0, 1) */
+  float clamp_min, clamp_max;    /* insertOpts, inside (0, 1), clamp_min < clamp_max */
+  float occupied_threshold;      /* likelihoodOpts.occupiedThreshold, inside (0, 1) */
+  uint32_t ray_trace_free_space; /* insertOpts */
+  uint32_t decimation;           /* insertOpts, >= 1 */
+  float max_range;               /* insertOpts [m]; 0 = no limit */
+  uint32_t update_rule;          /* MH_OCC_* */
+  uint32_t index_mode;           /* MH_INDEX_* */
+  uint32_t far_voxel_metric;     /* MH_FAR_* */
+  float search_voxel_size;       /* the first V [m]; 0 = 1.0 */
+  uint32_t reserved_;
+  uint64_t max_keys_per_pass;    /* 0 = 2^24 */
+} mh_occmap_params;
+typedef struct {
+  uint64_t n_cells;                             /* stored cells */
+  uint64_t n_occupied;                          /* ... of which occupied: the points of the search map */
+  int32_t l_hit, l_miss, l_min, l_max, l_occ;   /* the five integers */
+  float search_voxel_size;                      /* the current V */
+  uint64_t n_left_out;                          /* last insert: points whose index left the key range */
+  uint64_t n_keys;                              /* last insert: keys written */
+  uint32_t n_passes;                            /* last insert: passes */
+  uint32_t reserved_;
+} mh_occmap_info;
+/* Refusals (MH_ERR_INVALID_ARGUMENT, before any device work): a NULL argument, resolution <= 0, a probability or clamp outside
+ * (0, 1), clamp_min >= clamp_max, decimation 0, an unknown rule; mh_occmap_insert: a scan of another context. */
+MH_API mh_status mh_occmap_create(mh_ctx* ctx, const mh_occmap_params* params, mh_occmap** out);
+MH_API mh_status mh_occmap_destroy(mh_occmap* occ);
+/* Forget every cell; the search voxel starts over: a cleared map behaves as a new one. */
+MH_API mh_status mh_occmap_clear(mh_occmap* occ);
+MH_API mh_status mh_occmap_insert(mh_occmap* occ, const mh_scan* scan, const double T[12], float remove_voxels_farther_than);
+MH_API mh_status mh_occmap_get_info(const mh_occmap* occ, mh_occmap_info* info);
+/* The cells in ascending key order to HOST arrays (either may be NULL): 3 indices and one log-odds value per cell. */
+MH_API mh_status mh_occmap_download(const mh_occmap* occ, int32_t* keys_xyz, int32_t* logodds);
+/* The search map for alignments whose pair distances do not exceed min_radius (see "Search structure").  The handle is the
+ * occupancy map's own: valid until the next insert, clear or growing call, never to be destroyed by the caller. */
+MH_API mh_status mh_occmap_search_map(mh_occmap* occ, float min_radius, const mh_map** out);
 
 #ifdef __cplusplus
 }

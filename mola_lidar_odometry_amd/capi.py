@@ -186,6 +186,22 @@ class ByIntensityParams(C.Structure):
     _fields_ = [("low_threshold", C.c_float), ("high_threshold", C.c_float)]
 
 
+class OccMapParams(C.Structure):
+    """mh_occmap_params: the occupancy voxel map (mrpt::maps::CVoxelMap stand-in)."""
+    _fields_ = [("resolution", C.c_float), ("prob_hit", C.c_float), ("prob_miss", C.c_float), ("clamp_min", C.c_float),
+                ("clamp_max", C.c_float), ("occupied_threshold", C.c_float), ("ray_trace_free_space", C.c_uint32),
+                ("decimation", C.c_uint32), ("max_range", C.c_float), ("update_rule", C.c_uint32), ("index_mode", C.c_uint32),
+                ("far_voxel_metric", C.c_uint32), ("search_voxel_size", C.c_float), ("reserved_", C.c_uint32),
+                ("max_keys_per_pass", C.c_uint64)]
+
+
+class OccMapInfo(C.Structure):
+    _fields_ = [("n_cells", C.c_uint64), ("n_occupied", C.c_uint64), ("l_hit", C.c_int32), ("l_miss", C.c_int32),
+                ("l_min", C.c_int32), ("l_max", C.c_int32), ("l_occ", C.c_int32), ("search_voxel_size", C.c_float),
+                ("n_left_out", C.c_uint64), ("n_keys", C.c_uint64), ("n_passes", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+OCC_COUNTED, OCC_ONCE = 0, 1  # mh_occmap_params::update_rule
 TS_NONE, TS_MIDDLE_IS_ZERO, TS_EARLIEST_IS_ZERO = 0, 1, 2
 DECIMATE_FIRST_POINT, DECIMATE_CLOSEST_TO_AVERAGE = 0, 1
 BBOX_OFF, BBOX_KEEP_OUTSIDE, BBOX_KEEP_INSIDE = 0, 1, 2
@@ -285,6 +301,13 @@ _SIGNATURES = {
                                                    C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
     "mh_icp_align_layers_batch_planes": (C.c_int32, [C.c_size_t, C.POINTER(LayerJobPlanes), C.POINTER(ICPParamsC), C.c_int32, _DP,
                                                      C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
+    "mh_occmap_create": (C.c_int32, [C.c_void_p, C.POINTER(OccMapParams), C.POINTER(C.c_void_p)]),
+    "mh_occmap_destroy": (C.c_int32, [C.c_void_p]),
+    "mh_occmap_clear": (C.c_int32, [C.c_void_p]),
+    "mh_occmap_insert": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_float]),
+    "mh_occmap_get_info": (C.c_int32, [C.c_void_p, C.POINTER(OccMapInfo)]),
+    "mh_occmap_download": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mh_occmap_search_map": (C.c_int32, [C.c_void_p, C.c_float, C.POINTER(C.c_void_p)]),
 }
 
 _lib = None
@@ -476,6 +499,71 @@ class Map:
         if self._h:
             if self.ctx._h:  # (see Scan.close)
                 lib().mh_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _BorrowedMap(Map):
+    """The search map of an OccMap: an mh_map the occupancy map owns (never destroyed from here)."""
+
+    def __init__(self, ctx: Context, handle):
+        self.ctx = ctx
+        self._h = handle
+
+    def close(self):
+        self._h = C.c_void_p()
+
+
+class OccMap:
+    """Device-resident occupancy voxel map (stands in for mrpt::maps::CVoxelMap; mh_occmap)."""
+
+    def __init__(self, ctx: Context, resolution=0.05, prob_hit=0.7, prob_miss=0.3, clamp_min=0.05, clamp_max=0.95,
+                 occupied_threshold=0.6, ray_trace_free_space=True, decimation=1, max_range=0.0, update_rule=OCC_COUNTED,
+                 index_mode=INDEX_FLOOR, far_voxel_metric=FAR_CHEBYSHEV, search_voxel_size=0.0, max_keys_per_pass=0):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        p = OccMapParams(resolution, prob_hit, prob_miss, clamp_min, clamp_max, occupied_threshold, int(bool(ray_trace_free_space)),
+                         decimation, max_range, update_rule, index_mode, far_voxel_metric, search_voxel_size, 0, max_keys_per_pass)
+        _chk(lib().mh_occmap_create(ctx._h, C.byref(p), C.byref(self._h)))
+        ctx._children.add(self)
+
+    def insert(self, scan: "Scan", T, remove_voxels_farther_than=0.0):
+        T = _T12(T)
+        _chk(lib().mh_occmap_insert(self._h, scan._h, T.ctypes.data_as(_DP), float(remove_voxels_farther_than)))
+        return self
+
+    def clear(self):
+        _chk(lib().mh_occmap_clear(self._h))
+        return self
+
+    def info(self) -> OccMapInfo:
+        i = OccMapInfo()
+        _chk(lib().mh_occmap_get_info(self._h, C.byref(i)))
+        return i
+
+    def download(self):
+        """(cell indices int32 [n, 3], log-odds int32 [n]) in ascending key order."""
+        n = int(self.info().n_cells)
+        keys, lo = np.zeros((max(n, 1), 3), np.int32), np.zeros(max(n, 1), np.int32)
+        _chk(lib().mh_occmap_download(self._h, keys.ctypes.data_as(C.POINTER(C.c_int32)), lo.ctypes.data_as(C.POINTER(C.c_int32))))
+        return keys[:n], lo[:n]
+
+    def search_map(self, min_radius=0.0) -> Map:
+        """The inner mh_map over the occupied centres, exact for pair distances <= min_radius (valid until the next insert,
+        clear or growing call)."""
+        h = C.c_void_p()
+        _chk(lib().mh_occmap_search_map(self._h, float(min_radius), C.byref(h)))
+        return _BorrowedMap(self.ctx, h)
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                lib().mh_occmap_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -206,6 +206,13 @@ class LidarOdometry {
     std::vector<int32_t> vox_keys;  // 3 per voxel
   };
   MapDump downloadMap(const std::string& name) const;
+  // A CVoxelMap local map by name as mh_occmap_download gives it: every stored cell's indices (3 per cell, ascending key
+  // order) and log-odds.  (downloadMap, localMapSizes and localMapStats report such a map's occupied centres.)
+  struct VoxelMapDump {
+    std::vector<int32_t> keys, logodds;
+    float search_voxel_size = 0.f;  // the voxel of the search map over the occupied centres (it grows with the matchers' radii)
+  };
+  VoxelMapDump downloadVoxelMap(const std::string& name) const;
   std::map<std::string, double> dynamicVariables() const { return source_.getVariableValues(); }
   // what initialize() recognised in the pipeline file (for tests / logs)
   std::map<std::string, std::string> describePipeline() const;

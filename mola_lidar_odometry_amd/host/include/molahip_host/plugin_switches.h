@@ -14,6 +14,8 @@
 //   MOLA_HIP_MIN_DELTA        1e-7            MOLA_HIP_MAX_COST       0                                       U8
 //   MOLA_HIP_PT2PL_MODE       plane | centroid                                                                U10
 //   MOLA_HIP_FAR_VOXEL_METRIC chebyshev | l1 | l2     (device-owned maps: remove_voxels_farther_than, yaml:238) a8
+//   MOLA_HIP_VOXELMAP_UPDATE  counted | once          (CVoxelMap stand-in: how a cell's hits and misses of ONE insert are applied,
+//                                                     MH_OCC_COUNTED / MH_OCC_ONCE, include/molahip.h) [U]
 //   MOLA_HIP_FORCE_CPU        0 | 1                   (adapter only: every call to the upstream loop)
 //   MOLA_HIP_FUSE_GATES       (unset) | 0 | 1         matchers with runFromIteration / runUpToIteration on the fused multi-layer
 //                                                     loop (mh_icp_align_layers_gated); set, it overrides ICP::fuseGatedMatchers
@@ -48,6 +50,7 @@ struct PluginSwitches {
   uint32_t pt2pl_mode = MH_PT2PL_PLANE_DISTANCE;
   uint32_t far_voxel_metric = MH_FAR_CHEBYSHEV;
   uint32_t matched_points = MH_MATCHED_POINTS_PAIR_AGAIN;  // MOLA_HIP_MATCHED_POINTS = again | skip (U12)
+  uint32_t voxelmap_update = MH_OCC_COUNTED;  // MOLA_HIP_VOXELMAP_UPDATE = counted | once
   bool force_cpu = false;
   int fuse_gates = -1;  // MOLA_HIP_FUSE_GATES: -1 not set (the caller's own setting holds), 0 | 1
   int fuse_kbest = -1;  // MOLA_HIP_FUSE_KBEST: the same for pairingsPerPoint > 1
@@ -105,6 +108,8 @@ inline PluginSwitches read_plugin_switches() {
   }
   if (const char* e = getenv("MOLA_HIP_MATCHED_POINTS"))
     s.matched_points = (!strcmp(e, "skip") || !strcmp(e, "1")) ? MH_MATCHED_POINTS_SKIP : MH_MATCHED_POINTS_PAIR_AGAIN;
+  if (const char* e = getenv("MOLA_HIP_VOXELMAP_UPDATE"))
+    s.voxelmap_update = (!strcmp(e, "once") || !strcmp(e, "1")) ? MH_OCC_ONCE : MH_OCC_COUNTED;
   if (const char* e = getenv("MOLA_HIP_FORCE_CPU")) s.force_cpu = atoi(e) != 0;
   if (const char* e = getenv("MOLA_HIP_FUSE_GATES")) s.fuse_gates = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("MOLA_HIP_FUSE_KBEST")) s.fuse_kbest = atoi(e) != 0 ? 1 : 0;

@@ -18,6 +18,7 @@
 //   QualityEvaluator_PairedRatio       lidar3d-default.yaml:206-209 same name
 //   ParameterSource / Parameterizable  LidarOdometry.cpp:356,1571-1635  same names (run-time formulas)
 //   mola::HashedVoxelPointCloud        lidar3d-default.yaml:228-242 HashedVoxelPointCloud (device resident)
+//   mrpt::maps::CVoxelMap              lidar2d.yaml:183-198         CVoxelMap (device resident, NN role only)
 //
 // Nothing here computes on the CPU: every numeric step is a call into libmolahip.
 #pragma once
@@ -223,19 +224,49 @@ class HashedVoxelPointCloud : public Layer {
   // full parameter set (also what the NDT subclass uses)
   HashedVoxelPointCloud(const mh_map_params& p, std::shared_ptr<DeviceContext> ctx);
   ~HashedVoxelPointCloud() override;
-  void setPoints(const float* x, const float* y, const float* z, size_t n);  // clear + insertPoint for each
-  void insertPoints(const float* x, const float* y, const float* z, size_t n);  // keeps a host copy, rebuilds
+  virtual void setPoints(const float* x, const float* y, const float* z, size_t n);  // clear + insertPoint for each
+  virtual void insertPoints(const float* x, const float* y, const float* z, size_t n);  // keeps a host copy, rebuilds
   // FilterMerge + insertPointCloud + far-voxel removal, all on the device (mh_map_insert; lidar3d-default.yaml:362-368)
-  void insertPointCloud(const DevicePointCloud& pc, const CPose3D& robot_pose, float remove_voxels_farther_than);
-  void clear();
-  size_t size() const;
-  size_t voxelCount() const;
+  virtual void insertPointCloud(const DevicePointCloud& pc, const CPose3D& robot_pose, float remove_voxels_farther_than);
+  virtual void clear();
+  virtual size_t size() const;
+  virtual size_t voxelCount() const;
+  // before an alignment is queued: the largest pair distance its matchers can accept on this layer (a no-op here; CVoxelMap
+  // grows its search voxel to it)
+  virtual void prepareSearch(double /*max_radius*/) const {}
   mh_map* handle() const { return map_; }
   const std::shared_ptr<DeviceContext>& context() const { return ctx_; }
 
- private:
+ protected:
+  struct NoMap {};  // a subclass that brings its own search map
+  HashedVoxelPointCloud(NoMap, std::shared_ptr<DeviceContext> ctx) : ctx_(std::move(ctx)) {}
   std::shared_ptr<DeviceContext> ctx_;
-  mh_map* map_ = nullptr;
+  mutable mh_map* map_ = nullptr;
+};
+// mrpt::maps::CVoxelMap stand-in (lidar2d.yaml:183-198), NN role only: a device-resident log-odds occupancy voxel map updated
+// by ray tracing (mh_occmap, include/molahip.h) whose handle() is the inner search map over the centres of its occupied
+// voxels -- so every matcher, ICP path and AlignBatcher batch takes it as the HashedVoxelPointCloud it derives from.  size() =
+// occupied centres, voxelCount() = stored cells.  The update rule follows MOLA_HIP_VOXELMAP_UPDATE unless `p` was filled by hand.
+class CVoxelMap : public HashedVoxelPointCloud {
+ public:
+  explicit CVoxelMap(const mh_occmap_params& p, std::shared_ptr<DeviceContext> ctx = DeviceContext::Default());
+  // lidar2d.yaml's values, `resolution` apart
+  static mh_occmap_params defaultParams(float resolution);
+  ~CVoxelMap() override;
+  void setPoints(const float* x, const float* y, const float* z, size_t n) override;     // (points without a pose they were
+  void insertPoints(const float* x, const float* y, const float* z, size_t n) override;  //  seen from are no input of this map: both throw)
+  void insertPointCloud(const DevicePointCloud& pc, const CPose3D& robot_pose, float remove_voxels_farther_than) override;
+  void clear() override;
+  size_t size() const override;
+  size_t voxelCount() const override;
+  void prepareSearch(double max_radius) const override;
+  mh_occmap* occHandle() const { return occ_; }
+  float searchVoxelSize() const;  // the inner search map's voxel: it starts at 1 m and grows with prepareSearch
+  // cells in ascending key order: 3 indices each, and their log-odds
+  void download(std::vector<int32_t>& keys_xyz, std::vector<int32_t>& logodds) const;
+
+ private:
+  mh_occmap* occ_ = nullptr;
 };
 // mola::NDT stand-in (lidar3d-ndt.yaml:236-254): the same device map plus per-voxel mean / covariance / eigen
 // statistics, i.e. additionally NearestPlaneCapable for Matcher_Point2Plane

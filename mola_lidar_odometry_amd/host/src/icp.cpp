@@ -270,6 +270,72 @@ size_t HashedVoxelPointCloud::voxelCount() const {
   return i.n_voxels;
 }
 
+// ---- CVoxelMap
+mh_occmap_params CVoxelMap::defaultParams(float resolution) {
+  mh_occmap_params p{};
+  p.resolution = resolution;
+  p.prob_hit = 0.70f;
+  p.prob_miss = 0.30f;
+  p.clamp_min = 0.05f;
+  p.clamp_max = 0.95f;
+  p.occupied_threshold = 0.60f;
+  p.ray_trace_free_space = 1;
+  p.decimation = 1;
+  p.update_rule = molahip_host::plugin_switches().voxelmap_update;    // MOLA_HIP_VOXELMAP_UPDATE (default counted)
+  p.index_mode = molahip_host::plugin_switches().index_mode;          // MOLA_HIP_INDEX_MODE
+  p.far_voxel_metric = molahip_host::plugin_switches().far_voxel_metric;  // MOLA_HIP_FAR_VOXEL_METRIC
+  return p;
+}
+CVoxelMap::CVoxelMap(const mh_occmap_params& p, std::shared_ptr<DeviceContext> ctx) : HashedVoxelPointCloud(NoMap{}, std::move(ctx)) {
+  check(mh_occmap_create(ctx_->get(), &p, &occ_), "mh_occmap_create");
+  prepareSearch(0.0);
+}
+CVoxelMap::~CVoxelMap() {
+  mh_occmap_destroy(occ_);
+  map_ = nullptr;  // (the search map was the occupancy map's own)
+}
+void CVoxelMap::setPoints(const float*, const float*, const float*, size_t) {
+  throw std::runtime_error("CVoxelMap::setPoints: an occupancy map is updated by insertPointCloud (ray tracing from a pose)");
+}
+void CVoxelMap::insertPoints(const float*, const float*, const float*, size_t) {
+  throw std::runtime_error("CVoxelMap::insertPoints: an occupancy map is updated by insertPointCloud (ray tracing from a pose)");
+}
+float CVoxelMap::searchVoxelSize() const {
+  mh_occmap_info i;
+  check(mh_occmap_get_info(occ_, &i), "mh_occmap_get_info");
+  return i.search_voxel_size;
+}
+void CVoxelMap::insertPointCloud(const DevicePointCloud& pc, const CPose3D& robot_pose, float remove_voxels_farther_than) {
+  check(mh_occmap_insert(occ_, pc.handle(), robot_pose.T, remove_voxels_farther_than), "mh_occmap_insert");
+  prepareSearch(0.0);
+}
+void CVoxelMap::clear() {
+  check(mh_occmap_clear(occ_), "mh_occmap_clear");
+  prepareSearch(0.0);
+}
+size_t CVoxelMap::size() const {
+  mh_occmap_info i;
+  check(mh_occmap_get_info(occ_, &i), "mh_occmap_get_info");
+  return i.n_occupied;
+}
+size_t CVoxelMap::voxelCount() const {
+  mh_occmap_info i;
+  check(mh_occmap_get_info(occ_, &i), "mh_occmap_get_info");
+  return i.n_cells;
+}
+void CVoxelMap::prepareSearch(double max_radius) const {
+  const mh_map* m = nullptr;
+  map_ = nullptr;  // (a growing call replaces the search map: nothing of the old one is kept across it, whatever it returns)
+  check(mh_occmap_search_map(occ_, (float)max_radius, &m), "mh_occmap_search_map");
+  map_ = const_cast<mh_map*>(m);  // (the entry points that take it read it only)
+}
+void CVoxelMap::download(std::vector<int32_t>& keys_xyz, std::vector<int32_t>& logodds) const {
+  const size_t n = voxelCount();
+  keys_xyz.resize(3 * n);
+  logodds.resize(n);
+  if (n) check(mh_occmap_download(occ_, keys_xyz.data(), logodds.data()), "mh_occmap_download");
+}
+
 // ================================================================== parameters
 static uint32_t to_u32(const std::string& s) { return (uint32_t)strtoul(s.c_str(), nullptr, 10); }
 static bool to_bool(const std::string& s) { return s == "true" || s == "True" || s == "1" || s == "yes"; }
@@ -368,6 +434,7 @@ void Matcher_Points_DistanceThreshold::impl_match(const metric_map_t& pcGlobal, 
     std::vector<float> gx(cap), gy(cap), gz(cap), d2(cap);
     mh_pairs_out po{li.data(), gi.data(), gx.data(), gy.data(), gz.data(), d2.data()};
     mh_match_info info{};
+    glob.prepareSearch(threshold);
     const mh_status st = mh_nn_search_k(glob.handle(), scan, localPose.T, threshold, thresholdAngularDeg, pairingsPerPoint, &po,
                                         MH_MEM_HOST, &info);
     mh_scan_destroy(scan);
@@ -463,6 +530,7 @@ void Matcher_Point2Plane::impl_match(const metric_map_t& pcGlobal, const metric_
     mh_pairs_pl_out po{li.data(), a[0].data(), a[1].data(), a[2].data(), a[3].data(), a[4].data(), a[5].data()};
     mh_match_info info{};
     mh_status st;
+    glob.prepareSearch(std::max(distanceThreshold, searchRadius));
     if (dynamic_cast<const NDT*>(&glob)) {  // per-voxel planes
       st = mh_nn_search_pt2pl(glob.handle(), scan, localPose.T, distanceThreshold, molahip_host::plugin_switches().pt2pl_mode, &po,
                               MH_MEM_HOST, &info);
@@ -1234,6 +1302,11 @@ void ICP::align_fused(const PointCloud* host_local, const DevicePointCloud* dev_
   const auto t_setup0 = std::chrono::steady_clock::now();
   prepare_schedule(p.maxIterations);  // (a no-op when precomputeSchedule() ran on the same values of the variables)
   const std::vector<double>&thr = sched_.thr, &kp = sched_.kp, &plthr = sched_.plthr;
+  {  // the largest pair distance of the whole call, before the map's handle is read (an occupancy map sizes its search voxel by it)
+    double radius = thr.empty() ? 0.0 : *std::max_element(thr.begin(), thr.end());
+    if (mpl && !plthr.empty()) radius = std::max(radius, *std::max_element(plthr.begin(), plthr.end()));
+    global.prepareSearch(radius);
+  }
   if (p.maxIterations) realize_iteration(0);
   mh_icp_params ip{};
   ip.max_iterations = p.maxIterations;
@@ -1402,6 +1475,18 @@ void ICP::align_fused_layers(const metric_map_t& pcLocal, const metric_map_t& pc
     scan_ = nullptr;
   }
   scan_ctx_ = ctx0;
+  // First every global layer is told the largest pair distance that ANY pair of this call can accept on it (an occupancy map
+  // sizes its search voxel by it, and growing replaces its search map), only then are the handles read: a handle taken before a
+  // later pair's larger radius would name a map that no longer exists.
+  {
+    std::map<std::string, double> radius_of;
+    for (size_t j = 0; j < ms.size(); j++) {
+      double radius = thr[j].empty() ? 0.0 : *std::max_element(thr[j].begin(), thr[j].end());
+      if (ms[j].pl) radius = std::max(radius, ms[j].pl->searchRadius);
+      for (const auto& lm : ms[j].entries()) radius_of[lm.global] = std::max(radius_of[lm.global], radius);
+    }
+    for (const auto& [name, radius] : radius_of) global_layer(pcGlobal, name).prepareSearch(radius);
+  }
   std::map<std::string, bool> staged;
   for (size_t j = 0; j < ms.size(); j++)
     for (const auto& lm : ms[j].entries()) {

@@ -376,7 +376,7 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
                              "layers of FilterAdjustTimestamps, FilterDeskew, FilterByRange(output_layer_between), "
                              "FilterBoundingBox, FilterDecimateVoxels(FirstPoint | ClosestToAverage), FilterCurvature, "
                              "FilterDeleteLayer, FilterNormalizeIntensity and FilterByIntensity (with setIntensityInput), "
-                             "and FilterMerge into HashedVoxelPointCloud / NDT maps");
+                             "and FilterMerge into HashedVoxelPointCloud / NDT / CVoxelMap maps");
   }
   static std::vector<std::string> names_of(const Config& c) {
     std::vector<std::string> v;
@@ -527,8 +527,8 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
       m.name = p.getOr("target_layer", "localmap");
       m.def = p["metric_map_definition"];
       const std::string c = m.def["class"].asString();
-      if (!ends_with(c, "HashedVoxelPointCloud") && !ends_with(c, "NDT"))
-        unsupported("local map class '" + c + "' (HashedVoxelPointCloud, NDT)");
+      if (!ends_with(c, "HashedVoxelPointCloud") && !ends_with(c, "NDT") && !ends_with(c, "CVoxelMap"))
+        unsupported("local map class '" + c + "' (HashedVoxelPointCloud, NDT, CVoxelMap)");
       for (const auto& o : maps)
         if (o.name == m.name) unsupported("two local maps named '" + m.name + "'");
       maps.push_back(m);
@@ -1053,6 +1053,22 @@ std::shared_ptr<HashedVoxelPointCloud> LidarOdometry::make_map(const Config& def
   const std::string cls = def["class"].asString();
   const Config& co = def["creationOpts"];
   const Config& io = def["insertOpts"];
+  if (ends_with(cls, "CVoxelMap")) {  // mrpt::maps::CVoxelMap (lidar2d.yaml:183-198): the occupancy voxel map
+    auto num = [&](const Config& c, const char* key, double dflt) { return c.has(key) ? eval_now(c[key].asString(), vars) : dflt; };
+    mh_occmap_params op = mp2p_icp_hip::CVoxelMap::defaultParams(0.f);
+    *voxel_size = num(co, "resolution", 0.20);
+    op.resolution = (float)*voxel_size;
+    op.prob_hit = (float)num(io, "prob_hit", op.prob_hit);
+    op.prob_miss = (float)num(io, "prob_miss", op.prob_miss);
+    op.clamp_min = (float)num(io, "clamp_min", op.clamp_min);
+    op.clamp_max = (float)num(io, "clamp_max", op.clamp_max);
+    if (io.has("ray_trace_free_space")) op.ray_trace_free_space = to_bool(io["ray_trace_free_space"].asString()) ? 1u : 0u;
+    op.decimation = (uint32_t)std::max(1.0, num(io, "decimation", 1.0));
+    op.max_range = (float)std::max(0.0, num(io, "max_range", 0.0));
+    if (def.has("likelihoodOpts")) op.occupied_threshold = (float)num(def["likelihoodOpts"], "occupiedThreshold", op.occupied_threshold);
+    *remove_far = (float)num(io, "remove_voxels_farther_than", 0.0);
+    return std::make_shared<mp2p_icp_hip::CVoxelMap>(op, ctx_);
+  }
   mh_map_params mp{};
   *voxel_size = eval_now(co["voxel_size"].asString(), vars);
   mp.voxel_size = (float)*voxel_size;
@@ -1065,7 +1081,7 @@ std::shared_ptr<HashedVoxelPointCloud> LidarOdometry::make_map(const Config& def
     mp.ndt_max_eigen_ratio = io.has("max_eigen_ratio_for_planes") ? (float)eval_now(io["max_eigen_ratio_for_planes"].asString(), vars) : 0.05f;
     mp.ndt_min_points = 4;
   } else if (!ends_with(cls, "HashedVoxelPointCloud")) {
-    throw std::runtime_error("local map class '" + cls + "' has no device implementation (HashedVoxelPointCloud, NDT)");
+    throw std::runtime_error("local map class '" + cls + "' has no device implementation (HashedVoxelPointCloud, NDT, CVoxelMap)");
   }
   return std::make_shared<HashedVoxelPointCloud>(mp, ctx_);
 }
@@ -1444,12 +1460,32 @@ LidarOdometry::MapDump LidarOdometry::downloadMap(const std::string& name) const
   }
   MapDump d;
   if (!m) return d;  // (not created yet, or no such map: empty)
-  const size_t n = m->size(), v = m->voxelCount();
+  // (the search structure's own counts: a CVoxelMap reports its occupied centres here, and its cells in downloadVoxelMap)
+  mh_map_info mi{};
+  check(mh_map_get_info(m->handle(), &mi), "mh_map_get_info");
+  const size_t n = mi.n_points, v = mi.n_voxels;
   d.x.resize(n); d.y.resize(n); d.z.resize(n); d.src_idx.resize(n);
   d.vox_keys.resize(3 * v); d.vox_first.resize(v); d.vox_count.resize(v);
   if (!n) return d;
   check(mh_map_download(m->handle(), d.x.data(), d.y.data(), d.z.data(), d.src_idx.data(), d.vox_keys.data(), d.vox_first.data(),
                         d.vox_count.data()), "mh_map_download");
+  return d;
+}
+
+LidarOdometry::VoxelMapDump LidarOdometry::downloadVoxelMap(const std::string& name) const {
+  std::shared_ptr<HashedVoxelPointCloud> m;
+  if (gplan_) {
+    for (const auto& s : gplan_->maps)
+      if (s.name == name) m = s.map;
+  } else if (plan_ && plan_->map_layer == name) {
+    m = local_map_;
+  }
+  VoxelMapDump d;
+  if (!m) return d;  // (not created yet, or no such map: empty)
+  auto vm = std::dynamic_pointer_cast<mp2p_icp_hip::CVoxelMap>(m);
+  if (!vm) throw std::runtime_error("LidarOdometry::downloadVoxelMap: local map '" + name + "' is not a CVoxelMap");
+  vm->download(d.keys, d.logodds);
+  d.search_voxel_size = vm->searchVoxelSize();
   return d;
 }
 

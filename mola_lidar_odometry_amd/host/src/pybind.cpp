@@ -64,6 +64,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
   });
   m.def("plugin_switch_fuse_kbest", [] { return molahip_host::plugin_switches().fuse_kbest; });  // MOLA_HIP_FUSE_KBEST: -1 not set
   m.def("plugin_switch_fuse_planes", [] { return molahip_host::plugin_switches().fuse_planes; });  // MOLA_HIP_FUSE_PLANES: -1 not set
+  m.def("plugin_switch_voxelmap_update", [] { return molahip_host::plugin_switches().voxelmap_update; });  // MOLA_HIP_VOXELMAP_UPDATE: MH_OCC_*
   m.def("plugin_switch_fuse_gates", [] { return molahip_host::plugin_switches().fuse_gates; });  // MOLA_HIP_FUSE_GATES: -1 not set (a function of its own: the keys of plugin_switches() are compared as a whole by their users)
   m.def("kernel_from_upstream_name", [](const std::string& n) { return molahip_host::kernel_from_upstream_name(n.c_str(), molahip_host::plugin_switches()); });
   m.def("term_reason_name", [](uint32_t t) { return std::string(enum2str(molahip_host::term_reason_to<IterTermReason>(t))); });
@@ -162,7 +163,8 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["layer_sizes"] = r.layer_sizes;
     return d;
   };
-  py::class_<LidarOdometry>(m, "LidarOdometry", py::dynamic_attr())
+  py::class_<LidarOdometry> lo_class(m, "LidarOdometry", py::dynamic_attr());
+  lo_class
       .def(py::init([](int device, bool own_context) {
              // default: the process-wide context on device 0; device >= 0 / own_context: a context (stream + scratch) of
              // its own on that device -- one per GPU rank, and required when several drivers run in threads of one process
@@ -280,6 +282,16 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         d["vox_first"] = py::array_t<uint32_t>(v, m.vox_first.data());
         d["vox_count"] = py::array_t<uint32_t>(v, m.vox_count.data());
         return d; });
+  lo_class.def("downloadVoxelMap", [](const LidarOdometry& lo, const std::string& name) {
+    const LidarOdometry::VoxelMapDump v = lo.downloadVoxelMap(name);
+    const py::ssize_t n = (py::ssize_t)v.logodds.size();
+    py::array_t<int32_t> keys({n, (py::ssize_t)3});
+    if (n) std::copy(v.keys.begin(), v.keys.end(), keys.mutable_data());
+    py::dict d;
+    d["keys"] = keys;
+    d["logodds"] = py::array_t<int32_t>(n, v.logodds.data());
+    d["search_voxel_size"] = v.search_voxel_size;
+    return d; });
   py::class_<AlignBatcher, std::shared_ptr<AlignBatcher>>(m, "AlignBatcher")
       .def(py::init<size_t>(), py::arg("participants"))
       .def("leave", [](AlignBatcher& b) { b.leave(); }, py::call_guard<py::gil_scoped_release>())
