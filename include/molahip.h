@@ -48,7 +48,8 @@ extern "C" {
  * mh_curvature_params and mh_scan_curvature, then the intensity channel's entry points and mh_by_intensity_params,
  * mh_layer_pair_gates and mh_icp_align_layers_gated, mh_layer_pair_knn and mh_icp_align_layers_kbest, mh_layer_pair_plane and
  * mh_icp_align_layers_planes, mh_layer_job_opts and mh_icp_align_layers_batch_opts, mh_layer_job_planes and
- * mh_icp_align_layers_batch_planes, mh_occmap_params / mh_occmap_info and the mh_occmap_* entry points: new structs and entry
+ * mh_icp_align_layers_batch_planes, mh_occmap_params / mh_occmap_info and the mh_occmap_* entry points, mh_range_image_params and
+ * mh_scan_edges_from_range_image: new structs and entry
  * points change no existing layout, and a binder that lacks
  * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
@@ -344,6 +345,38 @@ typedef struct {
 } mh_by_intensity_params;
 MH_API mh_status mh_scan_by_intensity(const mh_scan* in, const mh_by_intensity_params* p, mh_scan* out_low, mh_scan* out_mid,
                                       mh_scan* out_high);
+/* GeneratorEdgesFromRangeImage [U] (rgbd.yaml:233-244): turns an organised range image into an `edges` and a `planes` layer.
+ * Upstream's source is not vendored, so this is a restatement; parity with it is unpinned.  `range` is row-major rows x cols,
+ * R[r, c]; 0 means "no return".  With W = row_window_length:
+ *   Classification, per row r, in integers:
+ *     pixel (r, c) is scored iff W <= c < cols - W and all 2W+1 samples R[r, c-W .. c+W] are non-zero;
+ *     S = (sum of those 2W+1 samples) - (2W+1) * R[r, c]            (exact in int32: |S| <= 128 * 65535)
+ *     (float)|S| > score_threshold  -> edges (a strict comparison);  every other scored pixel -> planes;
+ *     unscored pixels go to neither layer.
+ *   Point of a pixel, in float, unfused, in the order written (correctly rounded divide and square root):
+ *     d = (float)R * range_units;  kx = (cx - (float)c) / fx;  ky = (cy - (float)r) / fy;
+ *     range_is_depth != 0:  xs = d, ys = d*kx, zs = d*ky            (the MRPT sensor frame: x forward, y left, z up)
+ *     otherwise:            xs = (float)((double)d / sqrt((1.0 + (double)kx*kx) + (double)ky*ky)), ys = xs*kx, zs = xs*ky
+ *     vehicle frame, P = sensor_pose, coordinate i:  (float)(((P[4i]*xs + P[4i+1]*ys) + P[4i+2]*zs) + P[4i+3])  in fp64.
+ *   Order: both layers hold their pixels in row-major pixel order (an order-preserving compaction, as every filter here).
+ * The outputs carry no time stamps and no intensity; src_idx = the pixel index r * cols + c.  `edges` or `planes` may be
+ * NULL, not both; they differ from each other and belong to `ctx`.  `mem`: MH_MEM_HOST, MH_MEM_DEVICE or MH_MEM_HOST_PINNED
+ * (see Conventions).  Refused before any device work, the outputs untouched: MH_ERR_INVALID_ARGUMENT for zero rows or cols,
+ * W outside 1..64, fx, fy or range_units not > 0, a negative or non-finite score_threshold, both outputs NULL, a scan of
+ * another context; MH_ERR_UNSUPPORTED for more than 2^21 - 1 pixels (the packed counters of mh_scan_curvature, whose scan
+ * this call shares).  An image with cols < 2W+1 is valid and yields two empty layers.  Queued on the context's stream; one
+ * read-back of the two counts ends the call.  Bitwise reproducible: no float atomics, no waiting between workgroups. */
+typedef struct {
+  uint32_t rows, cols;        /* > 0 */
+  float fx, fy, cx, cy;       /* pinhole intrinsics [px]; fx, fy > 0 */
+  float range_units;          /* metres per count, > 0 */
+  uint32_t range_is_depth;    /* != 0: the value is the depth along the optical axis; 0: the distance along the ray */
+  double sensor_pose[12];     /* sensor on the vehicle, row-major 3x4 */
+  uint32_t row_window_length; /* W, 1..64 (rgbd.yaml:244 has 6) */
+  float score_threshold;      /* rgbd.yaml:243 has 10; finite, >= 0 */
+} mh_range_image_params;
+MH_API mh_status mh_scan_edges_from_range_image(mh_ctx* ctx, const uint16_t* range, int32_t mem, const mh_range_image_params* p,
+                                                mh_scan* edges, mh_scan* planes);
 /* Copy a scan to HOST arrays (any may be NULL; t / src_idx are zero-filled when the scan has none). */
 MH_API mh_status mh_scan_download(const mh_scan* scan, float* x, float* y, float* z, float* t, uint32_t* src_idx);
 /* Copy a scan's intensity to a HOST array of n entries; MH_ERR_INVALID_ARGUMENT when the scan carries none. */

@@ -186,6 +186,13 @@ class ByIntensityParams(C.Structure):
     _fields_ = [("low_threshold", C.c_float), ("high_threshold", C.c_float)]
 
 
+class RangeImageParams(C.Structure):
+    """mh_range_image_params: camera, range encoding and the classifier's two values (mh_scan_edges_from_range_image)."""
+    _fields_ = [("rows", C.c_uint32), ("cols", C.c_uint32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("range_units", C.c_float), ("range_is_depth", C.c_uint32), ("sensor_pose", C.c_double * 12),
+                ("row_window_length", C.c_uint32), ("score_threshold", C.c_float)]
+
+
 class OccMapParams(C.Structure):
     """mh_occmap_params: the occupancy voxel map (mrpt::maps::CVoxelMap stand-in)."""
     _fields_ = [("resolution", C.c_float), ("prob_hit", C.c_float), ("prob_miss", C.c_float), ("clamp_min", C.c_float),
@@ -301,6 +308,8 @@ _SIGNATURES = {
                                                    C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
     "mh_icp_align_layers_batch_planes": (C.c_int32, [C.c_size_t, C.POINTER(LayerJobPlanes), C.POINTER(ICPParamsC), C.c_int32, _DP,
                                                      C.POINTER(C.POINTER(Prior)), C.POINTER(ICPResult), C.POINTER(C.c_uint64)]),
+    "mh_scan_edges_from_range_image": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(RangeImageParams), C.c_void_p,
+                                                   C.c_void_p]),
     "mh_occmap_create": (C.c_int32, [C.c_void_p, C.POINTER(OccMapParams), C.POINTER(C.c_void_p)]),
     "mh_occmap_destroy": (C.c_int32, [C.c_void_p]),
     "mh_occmap_clear": (C.c_int32, [C.c_void_p]),
@@ -1266,6 +1275,31 @@ def scan_by_intensity(scan: "Scan", params: "ByIntensityParams", out_low: "Scan 
     h = lambda sc: sc._h if sc is not None else None
     _chk(lib().mh_scan_by_intensity(scan._h, C.byref(params), h(out_low), h(out_mid), h(out_high)))
     return out_low, out_mid, out_high
+
+
+def range_image_params(rows, cols, fx, fy, cx, cy, range_units=0.001, range_is_depth=True, sensor_pose=None,
+                       row_window_length=6, score_threshold=10.0) -> RangeImageParams:
+    """Defaults: the values of rgbd.yaml's GeneratorEdgesFromRangeImage; sensor_pose: 3x4 (or 4x4) row-major, identity if None."""
+    P = np.eye(4)[:3] if sensor_pose is None else np.asarray(sensor_pose, np.float64)[:3, :4]
+    return RangeImageParams(int(rows), int(cols), float(fx), float(fy), float(cx), float(cy), float(range_units),
+                            1 if range_is_depth else 0, (C.c_double * 12)(*map(float, np.ascontiguousarray(P).ravel())),
+                            int(row_window_length), float(score_threshold))
+
+
+def scan_edges_from_range_image(ctx: "Context", range_image, params: "RangeImageParams", edges: "Scan | None",
+                                planes: "Scan | None" = None, mem=MEM_HOST):
+    """mh_scan_edges_from_range_image (molahip.h states the rule).  range_image: a C-contiguous uint16 numpy array of
+    rows x cols (mem MEM_HOST, or MEM_HOST_PINNED when its memory is page-locked), or an integer address with mem naming
+    where it lives (MEM_DEVICE: a device pointer).  Returns (edges, planes), None where none was given."""
+    if isinstance(range_image, np.ndarray):
+        assert range_image.dtype == np.uint16 and range_image.flags.c_contiguous
+        assert range_image.size == params.rows * params.cols and mem != MEM_DEVICE
+        ptr = range_image.ctypes.data
+    else:
+        ptr = int(range_image)
+    h = lambda sc: sc._h if sc is not None else None
+    _chk(lib().mh_scan_edges_from_range_image(ctx._h, C.c_void_p(ptr), int(mem), C.byref(params), h(edges), h(planes)))
+    return edges, planes
 
 
 def by_intensity_params(low_threshold=0.1, high_threshold=0.9) -> ByIntensityParams:

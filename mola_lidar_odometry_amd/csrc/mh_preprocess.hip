@@ -11,6 +11,8 @@
 //   FilterCurvature         -> three-point stencil, one scan of packed class counters, three-way compaction (mh_k_curv.h)
 //   FilterNormalizeIntensity / FilterByIntensity -> min / max reduction + in-place rewrite; thresholds through the
 //                              curvature filter's scan and scatter (mh_k_intensity.h)
+//   GeneratorEdgesFromRangeImage -> row stencil over a 16-bit range image staged in LDS, the same packed-counter scan, a
+//                              scatter that unprojects each kept pixel (mh_k_rimg.h)
 // Every call that derives a layer carries the input's optional intensity channel along (out.i[k] == raw.i[out.src[k]]).
 // All of it is HBM-bound byte/index work: coalesced SoA streams, one pass per stage, atomics only on the
 // (L2-resident) decimation table.
@@ -22,6 +24,7 @@
 #include "mh_nn_device.h"
 #include "mh_k_curv.h"
 #include "mh_k_intensity.h"
+#include "mh_k_rimg.h"
 
 using namespace mh;
 
@@ -1111,6 +1114,72 @@ mh_status mh_scan_by_intensity(const mh_scan* in, const mh_by_intensity_params* 
   return split3(in, outs, 1, [&](hipStream_t s, unsigned long long* word, uint32_t cap) {
     hipLaunchKernelGGL(k_int_classify, dim3(cap / 256), dim3(256), 0, s, in->i, (uint32_t)in->n, cap, low, high, word);
   });
+}
+
+mh_status mh_scan_edges_from_range_image(mh_ctx* ctx, const uint16_t* range, int32_t mem, const mh_range_image_params* p,
+                                         mh_scan* edges, mh_scan* planes) {
+  MH_REQUIRE(ctx && range && p, "null argument");
+  MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE || mem == MH_MEM_HOST_PINNED, "bad mem space");
+  MH_REQUIRE(p->rows > 0 && p->cols > 0, "empty image");
+  MH_REQUIRE(p->row_window_length >= 1 && p->row_window_length <= kRimgMaxW, "row_window_length outside 1..64");
+  MH_REQUIRE(p->fx > 0.f && p->fy > 0.f && p->range_units > 0.f, "fx, fy and range_units must be positive");
+  MH_REQUIRE(isfinite(p->score_threshold) && p->score_threshold >= 0.f, "score_threshold must be finite and >= 0");
+  MH_REQUIRE(edges || planes, "both outputs are NULL");
+  MH_REQUIRE(edges != planes, "outputs must be distinct scans");
+  MH_REQUIRE((!edges || edges->ctx == ctx) && (!planes || planes->ctx == ctx), "a scan belongs to another context");
+  const size_t n = (size_t)p->rows * p->cols;
+  if (n > kCurvMaxPoints)
+    return mh::fail(MH_ERR_UNSUPPORTED, "%s: image above 2^21 - 1 pixels (the packed 21-bit counters of the scan)", __func__);
+  MH_TRY(set_device(ctx));
+  hipStream_t s = ctx->stream;
+  mh_scan* const outs[2] = {edges, planes};
+  const uint32_t W = p->row_window_length;
+  if (p->cols < 2 * W + 1) {  // no scored column
+    for (mh_scan* o : outs)
+      if (o) MH_TRY(scan_alloc(o, 0, false, true));
+    return MH_OK;
+  }
+  for (mh_scan* o : outs)  // capacity: the pixel count; the real counts arrive with the read-back below
+    if (o) MH_TRY(scan_alloc(o, n, false, true));
+  const uint32_t cap = (uint32_t)((n + 255) / 256 * 256);
+  MH_TRY(ctx->build_c.reserve(2 * (size_t)cap * sizeof(unsigned long long)));  // word | pos
+  unsigned long long* word = ctx->build_c.as<unsigned long long>();
+  unsigned long long* pos = word + cap;
+  size_t tmp = 0;
+  MH_HIP(rocprim::exclusive_scan(nullptr, tmp, word, pos, 0ull, (size_t)cap, rocprim::plus<unsigned long long>(), s));
+  MH_TRY(ctx->sort_tmp.reserve(tmp));
+  if (!ctx->h_small) MH_HIP(hipHostMalloc((void**)&ctx->h_small, 64 * sizeof(uint32_t), hipHostMallocDefault));
+  uint32_t* h_counts = ctx->h_small + 16;  // (the split counts' slots)
+  const uint16_t* img = range;
+  if (mem != MH_MEM_DEVICE) {  // the only copy of the call: the image as it is
+    MH_TRY(ctx->build_a.reserve(n * sizeof(uint16_t)));
+    MH_HIP(hipMemcpyAsync(ctx->build_a.p, range, n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    img = ctx->build_a.as<uint16_t>();
+  }
+  const uint32_t nseg = (p->cols + kRimgSeg - 1) / kRimgSeg;
+  hipLaunchKernelGGL(k_rimg_classify, dim3(p->rows * nseg), dim3(kRimgSeg), 0, s, img, p->rows, p->cols, nseg, W,
+                     p->score_threshold, (uint32_t)n, cap, word);
+  size_t tb = ctx->sort_tmp.bytes;
+  MH_HIP(rocprim::exclusive_scan(ctx->sort_tmp.p, tb, word, pos, 0ull, (size_t)cap, rocprim::plus<unsigned long long>(), s));
+  RimgCam cam;
+  cam.fx = p->fx; cam.fy = p->fy; cam.cx = p->cx; cam.cy = p->cy; cam.units = p->range_units;
+  cam.is_depth = p->range_is_depth ? 1u : 0u;
+  for (int k = 0; k < 12; k++) cam.P[k] = p->sensor_pose[k];
+  RimgOut ro[2];
+  for (int k = 0; k < 2; k++) {
+    mh_scan* o = outs[k];
+    ro[k].x = o ? (float*)o->x : nullptr;
+    ro[k].y = o ? (float*)o->y : nullptr;
+    ro[k].z = o ? (float*)o->z : nullptr;
+    ro[k].src = o ? (uint32_t*)o->src : nullptr;
+  }
+  hipLaunchKernelGGL(k_rimg_scatter, dim3(cap / 256), dim3(256), 0, s, img, p->cols, (uint32_t)n, cap, cam, word, pos, ro[0],
+                     ro[1], h_counts);
+  MH_HIP(hipGetLastError());
+  MH_HIP(mh::wait_stream(s));  // (also ends the borrow of a pageable `range`; a pinned one was read by the copy queued above)
+  for (int k = 0; k < 2; k++)
+    if (outs[k]) outs[k]->n = h_counts[k];
+  return MH_OK;
 }
 
 mh_status mh_scan_normalize_intensity(mh_scan* layer, float range[2]) {

@@ -157,6 +157,13 @@ class LidarOdometry {
                                        size_t off_y, size_t off_z, long long off_t = -1, const float* t = nullptr,
                                        long long off_i = -1);
 
+  // One depth-image observation, for a pipeline whose observations_generator is a GeneratorEdgesFromRangeImage (rgbd.yaml):
+  // `range` is row-major camera.rows x camera.cols, 0 = no return; `camera` holds the intrinsics, the range encoding and the
+  // sensor's pose on the vehicle (include/molahip.h, mh_range_image_params); its row_window_length and score_threshold are
+  // overwritten from the pipeline.  With setInputPinned(true) `range` is page-locked and uploaded asynchronously.  A pipeline
+  // that takes point clouds throws here, and onLidar* throws on a depth-image pipeline (std::runtime_error, naming the other).
+  const ScanRecord& onDepthImage(double timestamp, const uint16_t* range, const mh_range_image_params& camera);
+
   // Off-line replay (data sets, eval/cli_kitti.sh): announce the NEXT observation before calling onLidar* for the
   // current one.  Its upload and first filter pass then run on a second stream of the same device, in a worker thread,
   // while the current scan is in its ICP loop; the next onLidar* call (same buffer, same layout) picks the result up.
@@ -190,6 +197,9 @@ class LidarOdometry {
     double voxel_size = 0;
   };
   std::map<std::string, MapStats> localMapStats() const;
+  // The class of every local map object by name: "HashedVoxelPointCloud" (also an NDT map, which is one with plane
+  // statistics), "CVoxelMap" or "SparseTreesPointCloud" ("" before the first key-frame).
+  std::map<std::string, std::string> localMapClasses() const;
   // An observation layer of the last scan of a general plan, as the last run of its filter left it (a layer that a
   // FilterDeleteLayer removed keeps its content until the next scan writes it): coordinates, time stamps and source indices
   // (zeros when the layer carries none), intensity (empty when the observations carry none).  Throws on an unknown name.
@@ -239,6 +249,7 @@ class LidarOdometry {
   void create_local_map();
   std::shared_ptr<HashedVoxelPointCloud> make_map(const Config& def, double* voxel_size, float* remove_far) const;
   void run_general_pass(int pass);
+  void run_generator(const RawInput& in);  // depth-image plans: the observations_generator step
   void record_layer_sizes(ScanRecord& rec) const;  // general plans: layer_sizes, n_for_icp, n_for_map of the live layers
   uint64_t maps_total(bool voxels) const;
   void ensure_device();

@@ -19,6 +19,7 @@
 //   ParameterSource / Parameterizable  LidarOdometry.cpp:356,1571-1635  same names (run-time formulas)
 //   mola::HashedVoxelPointCloud        lidar3d-default.yaml:228-242 HashedVoxelPointCloud (device resident)
 //   mrpt::maps::CVoxelMap              lidar2d.yaml:183-198         CVoxelMap (device resident, NN role only)
+//   mola::SparseTreesPointCloud        rgbd.yaml:203-217            SparseTreesPointCloud (device resident, NN role only)
 //
 // Nothing here computes on the CPU: every numeric step is a call into libmolahip.
 #pragma once
@@ -267,6 +268,20 @@ class CVoxelMap : public HashedVoxelPointCloud {
 
  private:
   mh_occmap* occ_ = nullptr;
+};
+// mola::SparseTreesPointCloud stand-in (rgbd.yaml:203-217) [U], NN role only.  Upstream keeps a sparse grid of cells of
+// `grid_size`, each holding its points under a KD-tree: nearest-neighbour queries are exact over the stored points; with
+// minimum_points_clearance > 0 a point is dropped at insertion when a stored point of its own cell is closer; with
+// remove_submaps_farther_than > 0 whole cells farther than that from the insertion pose are removed.  That IS an uncapped
+// mh_map whose voxel is the cell: voxel_size = grid_size, max_points_per_voxel = 0, min_distance_between_points =
+// minimum_points_clearance, mh_map_insert(..., remove_submaps_farther_than) -- so this class adds no handle and no kernel,
+// and a matcher radius above grid_size is refused as it is for a HashedVoxelPointCloud voxel.  Upstream's source is not
+// vendored: parity with it is unpinned.  (Cells of >= 1 m filled at centimetre spacing hold hundreds of records: the search
+// inside such a cell is a whole-voxel scan; profiles/rgbd.md has the cost.)
+class SparseTreesPointCloud : public HashedVoxelPointCloud {
+ public:
+  SparseTreesPointCloud(float grid_size, float minimum_points_clearance,
+                        std::shared_ptr<DeviceContext> ctx = DeviceContext::Default());
 };
 // mola::NDT stand-in (lidar3d-ndt.yaml:236-254): the same device map plus per-voxel mean / covariance / eigen
 // statistics, i.e. additionally NearestPlaneCapable for Matcher_Point2Plane

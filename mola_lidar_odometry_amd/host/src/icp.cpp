@@ -201,6 +201,17 @@ size_t NDT::planeCount() const {
   check(mh_map_get_info(handle(), &i), "mh_map_get_info");
   return i.n_planes;
 }
+static mh_map_params sparse_trees_params(float grid_size, float minimum_points_clearance) {
+  mh_map_params p{};
+  p.voxel_size = grid_size;    // the cell
+  p.max_points_per_voxel = 0;  // uncapped
+  p.index_mode = molahip_host::plugin_switches().index_mode;
+  p.far_voxel_metric = molahip_host::plugin_switches().far_voxel_metric;
+  p.min_distance_between_points = minimum_points_clearance;
+  return p;
+}
+SparseTreesPointCloud::SparseTreesPointCloud(float grid_size, float minimum_points_clearance, std::shared_ptr<DeviceContext> ctx)
+    : HashedVoxelPointCloud(sparse_trees_params(grid_size, minimum_points_clearance), std::move(ctx)) {}
 HashedVoxelPointCloud::~HashedVoxelPointCloud() { mh_map_destroy(map_); }
 
 void HashedVoxelPointCloud::setPoints(const float* x, const float* y, const float* z, size_t n) {

@@ -334,8 +334,11 @@ struct LidarOdometry::FilterPlan : public Parameterizable {
 //   with every filter stage skipped (it keeps the finite points, as every preprocess call does);
 //   with setIntensityInput(true) (extras/lidar3d-intensity.yaml): FilterNormalizeIntensity -> mh_scan_normalize_intensity in
 //   place, 1st pass only; FilterByIntensity -> mh_scan_by_intensity.
+//   observations_generator (rgbd.yaml:226-244): absent or a plain Generator -> the observation is the point layer 'raw';
+//   GeneratorEdgesFromRangeImage -> the observation is a depth image (onDepthImage) that mh_scan_edges_from_range_image turns
+//   into target_layer and planes_target_layer when it is uploaded -- the only layers the passes start from, there is no 'raw'.
 struct LidarOdometry::GeneralPlan : public Parameterizable {
-  enum class Kind { Deskew, Preprocess, Curvature, Delete, NormalizeIntensity, ByIntensity };
+  enum class Kind { Deskew, Preprocess, Curvature, Delete, NormalizeIntensity, ByIntensity, EdgesFromRangeImage };
   struct Step {
     Kind kind = Kind::Delete;
     int pass = 1;
@@ -350,6 +353,8 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
     double low_threshold = 0, high_threshold = 0;  // ByIntensity
     bool remember_range = false;                   // NormalizeIntensity: remember_intensity_range
     float range[2] = {NAN, NAN};                   // ... the remembered {min, max} (reset() forgets it)
+    uint32_t row_window_length = 0;                // EdgesFromRangeImage (pass 0: it runs when the image is uploaded)
+    double score_threshold = 0;
   };
   struct MapSlot {
     std::string name;
@@ -361,6 +366,9 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
   std::deque<Step> steps;  // (a deque: the formulas are bound to the steps' fields by address)
   bool intensity_input = false;  // LidarOdometry::setIntensityInput: intensity filters are accepted
   bool reads_intensity = false;  // an intensity filter is among the steps: 'raw' carries the channel
+  bool depth_input = false;      // observations_generator is a GeneratorEdgesFromRangeImage: steps[0] is its step
+  bool has_2nd_pass = false;     // any step of observations_filter_2nd_pass
+  float gen_bb_min[3] = {0, 0, 0}, gen_bb_max[3] = {0, 0, 0};  // depth_input: union bounding box of the generator's layers
   int32_t timestamp_method = MH_TS_NONE;
   double time_offset = 0;
   std::vector<MapSlot> maps;
@@ -376,7 +384,16 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
                              "layers of FilterAdjustTimestamps, FilterDeskew, FilterByRange(output_layer_between), "
                              "FilterBoundingBox, FilterDecimateVoxels(FirstPoint | ClosestToAverage), FilterCurvature, "
                              "FilterDeleteLayer, FilterNormalizeIntensity and FilterByIntensity (with setIntensityInput), "
-                             "and FilterMerge into HashedVoxelPointCloud / NDT / CVoxelMap maps");
+                             "and FilterMerge into HashedVoxelPointCloud / NDT / CVoxelMap / SparseTreesPointCloud maps; "
+                             "observations_generator: Generator (point clouds) or GeneratorEdgesFromRangeImage (depth images)");
+  }
+  // observations_generator names a GeneratorEdgesFromRangeImage (such a file always takes the general plan)
+  static bool wants_depth_input(const Config& cfg) {
+    if (!cfg.has("observations_generator")) return false;
+    const Config& gen = cfg["observations_generator"];
+    for (size_t i = 0; i < gen.size(); i++)
+      if (ends_with(class_of(gen.at(i)), "GeneratorEdgesFromRangeImage")) return true;
+    return false;
   }
   static std::vector<std::string> names_of(const Config& c) {
     std::vector<std::string> v;
@@ -518,8 +535,36 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
       }
     }
     std::set<std::string> known = {"raw"};
+    if (cfg.has("observations_generator")) {
+      const Config& og = cfg["observations_generator"];
+      for (size_t i = 0; i < og.size(); i++) {
+        const std::string cn = class_of(og.at(i));
+        if (ends_with(cn, "::Generator") || cn == "Generator") continue;  // point clouds into 'raw': what onLidar* does
+        if (!ends_with(cn, "GeneratorEdgesFromRangeImage")) unsupported("observations_generator " + cn);
+        if (depth_input) unsupported("two GeneratorEdgesFromRangeImage entries");
+        if (og.size() != 1) unsupported("GeneratorEdgesFromRangeImage beside another generator");
+        if (timestamp_method != MH_TS_NONE) unsupported("FilterAdjustTimestamps with a depth-image generator (there is no 'raw')");
+        const Config& p = og.at(i)["params"];
+        steps.emplace_back();
+        Step& st = steps.back();
+        st.kind = Kind::EdgesFromRangeImage;
+        st.pass = 0;
+        st.cls = cn;
+        st.out = {p.getOr("target_layer", "edges"), p.getOr("planes_target_layer", "planes")};
+        if (st.out[0].empty() || st.out[1].empty() || st.out[0] == st.out[1] || st.out[0] == "raw" || st.out[1] == "raw")
+          unsupported(cn + " needs two distinct layers target_layer and planes_target_layer");
+        const double W = p.has("row_window_length") ? to_double(p["row_window_length"].asString()) : 6.0;
+        if (!(W >= 1 && W <= 64) || W != std::floor(W)) unsupported(cn + " with row_window_length outside 1..64");
+        st.row_window_length = (uint32_t)W;
+        st.score_threshold = 10.0;
+        if (p.has("score_threshold")) parameterFromConfig(p, "score_threshold", &st.score_threshold, false);
+        depth_input = true;
+        known = {st.out[0], st.out[1]};
+      }
+    }
     if (cfg.has("observations_filter_1st_pass")) load_pass(cfg["observations_filter_1st_pass"], 1, known);
     if (cfg.has("observations_filter_2nd_pass")) load_pass(cfg["observations_filter_2nd_pass"], 2, known);
+    for (const auto& st : steps) has_2nd_pass = has_2nd_pass || st.pass == 2;
     const Config& gen = cfg["localmap_generator"];
     for (size_t i = 0; i < gen.size(); i++) {
       const Config& p = gen.at(i)["params"];
@@ -527,8 +572,9 @@ struct LidarOdometry::GeneralPlan : public Parameterizable {
       m.name = p.getOr("target_layer", "localmap");
       m.def = p["metric_map_definition"];
       const std::string c = m.def["class"].asString();
-      if (!ends_with(c, "HashedVoxelPointCloud") && !ends_with(c, "NDT") && !ends_with(c, "CVoxelMap"))
-        unsupported("local map class '" + c + "' (HashedVoxelPointCloud, NDT, CVoxelMap)");
+      if (!ends_with(c, "HashedVoxelPointCloud") && !ends_with(c, "NDT") && !ends_with(c, "CVoxelMap") &&
+          !ends_with(c, "SparseTreesPointCloud"))
+        unsupported("local map class '" + c + "' (HashedVoxelPointCloud, NDT, CVoxelMap, SparseTreesPointCloud)");
       for (const auto& o : maps)
         if (o.name == m.name) unsupported("two local maps named '" + m.name + "'");
       maps.push_back(m);
@@ -559,8 +605,10 @@ struct LidarOdometry::RawInput {
   size_t point_step = 0, off_x = 0, off_y = 0, off_z = 0;
   long long off_t = -1;
   long long off_i = -1;  // float32 intensity inside the record, or -1
+  const uint16_t* depth = nullptr;  // ... or a range image of cam.rows x cam.cols (onDepthImage; n = its pixel count)
+  mh_range_image_params cam{};
   bool same(const RawInput& o) const {
-    return n == o.n && x == o.x && y == o.y && z == o.z && t == o.t && data == o.data && point_step == o.point_step &&
+    return depth == o.depth && cam.rows == o.cam.rows && cam.cols == o.cam.cols && n == o.n && x == o.x && y == o.y && z == o.z && t == o.t && data == o.data && point_step == o.point_step &&
            off_x == o.off_x && off_y == o.off_y && off_z == o.off_z && off_t == o.off_t && off_i == o.off_i;
   }
 };
@@ -645,6 +693,8 @@ void LidarOdometry::initialize(const Config& cfg) {
   if (cfg.has("navstate_fuse_params")) navstate_.initialize(cfg["navstate_fuse_params"]);
   // the default chain first (its fused path, prefetch and batching); any other chain of implemented filters as a general plan
   try {
+    if (GeneralPlan::wants_depth_input(cfg))  // (the default chain reads 'raw': a depth-image file always takes the general plan)
+      throw std::runtime_error("unsupported observation filter chain: depth-image generator");
     auto plan = std::make_unique<FilterPlan>();
     plan->load(cfg);
     plan_ = std::move(plan);
@@ -834,6 +884,7 @@ void LidarOdometry::run_general_pass(int pass) {
       g.raw_adjusted = out;
     }
     g.alive = {"raw"};
+    if (g.depth_input) g.alive = {g.steps[0].out[0], g.steps[0].out[1]};  // what the generator wrote at upload
   } else {
     g.alive = g.alive_1st;  // (the twist hook runs this pass again from the same start)
   }
@@ -880,8 +931,9 @@ void LidarOdometry::run_general_pass(int pass) {
     g.alive_1st = g.alive;
   } else {
     // the sensor-range estimate reads the alphabetically first point layer of the observation (LidarOdometry.cpp:1515-1545)
-    for (int a = 0; a < 3; a++) icp_bb_min_[a] = icp_bb_max_[a] = 0.f;
-    if (!g.alive.empty()) layer(*g.alive.begin())->boundingBox(icp_bb_min_, icp_bb_max_);
+    // (depth images: the union box of the generator's layers -- all point layers of the observation as it arrived)
+    for (int a = 0; a < 3; a++) icp_bb_min_[a] = g.depth_input ? g.gen_bb_min[a] : 0.f, icp_bb_max_[a] = g.depth_input ? g.gen_bb_max[a] : 0.f;
+    if (!g.depth_input && !g.alive.empty()) layer(*g.alive.begin())->boundingBox(icp_bb_min_, icp_bb_max_);
   }
 }
 
@@ -1069,6 +1121,12 @@ std::shared_ptr<HashedVoxelPointCloud> LidarOdometry::make_map(const Config& def
     *remove_far = (float)num(io, "remove_voxels_farther_than", 0.0);
     return std::make_shared<mp2p_icp_hip::CVoxelMap>(op, ctx_);
   }
+  if (ends_with(cls, "SparseTreesPointCloud")) {  // mola::SparseTreesPointCloud (rgbd.yaml:203-217): an uncapped map whose voxel is the cell
+    auto num = [&](const Config& c, const char* key, double dflt) { return c.has(key) ? eval_now(c[key].asString(), vars) : dflt; };
+    *voxel_size = num(co, "grid_size", 10.0);
+    *remove_far = (float)num(io, "remove_submaps_farther_than", 0.0);
+    return std::make_shared<mp2p_icp_hip::SparseTreesPointCloud>((float)*voxel_size, (float)num(io, "minimum_points_clearance", 0.0), ctx_);
+  }
   mh_map_params mp{};
   *voxel_size = eval_now(co["voxel_size"].asString(), vars);
   mp.voxel_size = (float)*voxel_size;
@@ -1081,7 +1139,7 @@ std::shared_ptr<HashedVoxelPointCloud> LidarOdometry::make_map(const Config& def
     mp.ndt_max_eigen_ratio = io.has("max_eigen_ratio_for_planes") ? (float)eval_now(io["max_eigen_ratio_for_planes"].asString(), vars) : 0.05f;
     mp.ndt_min_points = 4;
   } else if (!ends_with(cls, "HashedVoxelPointCloud")) {
-    throw std::runtime_error("local map class '" + cls + "' has no device implementation (HashedVoxelPointCloud, NDT, CVoxelMap)");
+    throw std::runtime_error("local map class '" + cls + "' has no device implementation (HashedVoxelPointCloud, NDT, CVoxelMap, SparseTreesPointCloud)");
   }
   return std::make_shared<HashedVoxelPointCloud>(mp, ctx_);
 }
@@ -1102,11 +1160,58 @@ const LidarOdometry::ScanRecord& LidarOdometry::onLidarInterleaved(double this_o
   return process(this_obs_tim, in);
 }
 
+const LidarOdometry::ScanRecord& LidarOdometry::onDepthImage(double this_obs_tim, const uint16_t* range,
+                                                             const mh_range_image_params& camera) {
+  if (!range || !camera.rows || !camera.cols) throw std::runtime_error("LidarOdometry::onDepthImage: empty image");
+  RawInput in;
+  in.depth = range;
+  in.cam = camera;
+  in.n = (size_t)camera.rows * camera.cols;
+  return process(this_obs_tim, in);
+}
+
+// observations_generator of a depth-image plan: the image goes up (asynchronously from page-locked memory, setInputPinned)
+// and leaves the generator's two layers; their union bounding box feeds the sensor-range estimate
+void LidarOdometry::run_generator(const RawInput& in) {
+  GeneralPlan& g = *gplan_;
+  const GeneralPlan::Step& st = g.steps[0];
+  mh_range_image_params cam = in.cam;
+  cam.row_window_length = st.row_window_length;  // (the pipeline's values, whatever the caller left there)
+  cam.score_threshold = (float)st.score_threshold;
+  std::shared_ptr<DevicePointCloud> out[2];
+  for (int k = 0; k < 2; k++) {
+    auto& b = g.buf[st.out[k]];
+    if (!b) b = std::make_shared<DevicePointCloud>(ctx_);
+    out[k] = b;
+  }
+  check(mh_scan_edges_from_range_image(ctx_->get(), in.depth, input_pinned_ ? MH_MEM_HOST_PINNED : MH_MEM_HOST, &cam,
+                                       out[0]->handle(), out[1]->handle()), "mh_scan_edges_from_range_image");
+  bool any = false;
+  for (int k = 0; k < 2; k++) {
+    if (!out[k]->size()) continue;
+    float mn[3], mx[3];
+    out[k]->boundingBox(mn, mx);
+    for (int a = 0; a < 3; a++) {
+      g.gen_bb_min[a] = any ? std::min(g.gen_bb_min[a], mn[a]) : mn[a];
+      g.gen_bb_max[a] = any ? std::max(g.gen_bb_max[a], mx[a]) : mx[a];
+    }
+    any = true;
+  }
+  if (!any)
+    for (int a = 0; a < 3; a++) g.gen_bb_min[a] = g.gen_bb_max[a] = 0.f;
+}
+
 const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, const RawInput& in) {
   const size_t n = in.n;
   const bool has_t = in.t != nullptr || (in.data && in.off_t >= 0);
   (void)has_t;
   if (!plan_ && !gplan_) throw std::runtime_error("LidarOdometry::onLidar called before initialize()");
+  if (in.depth && !(gplan_ && gplan_->depth_input))
+    throw std::runtime_error("LidarOdometry (HIP): onDepthImage needs a pipeline whose observations_generator is a "
+                             "GeneratorEdgesFromRangeImage; this one takes point clouds (onLidar / onLidarInterleaved)");
+  if (!in.depth && gplan_ && gplan_->depth_input)
+    throw std::runtime_error("LidarOdometry (HIP): this pipeline's observations_generator is a GeneratorEdgesFromRangeImage: it "
+                             "takes depth images (onDepthImage), not point clouds");
   // 'raw' carries the intensity only when a filter reads it: otherwise the field is ignored (same records as without it)
   const bool with_i = gplan_ && gplan_->reads_intensity;
   if (with_i && !(in.data && in.off_i >= 0))
@@ -1140,7 +1245,8 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   if (pf_->requested && pf_->req.same(in)) pf_->requested = false;  // due before it could be launched
   if (!prepared) {
     StageTimer tt(profile_, "onLidar.0.upload_raw");
-    if (in.data) raw_->setPointsInterleaved(in.data, n, in.point_step, in.off_x, in.off_y, in.off_z, in.off_t, input_pinned_, off_i);
+    if (in.depth) run_generator(in);
+    else if (in.data) raw_->setPointsInterleaved(in.data, n, in.point_step, in.off_x, in.off_y, in.off_z, in.off_t, input_pinned_, off_i);
     else raw_->setPoints(in.x, in.y, in.z, n);
     if (in.t) raw_->setTimestamps(in.t, n);
   }
@@ -1148,7 +1254,11 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   // first call: sensor range from the raw cloud (:660, 1487-1513)
   if (!estimated_sensor_max_range_ && n) {
     float mn[3], mx[3];
-    cur_raw_->boundingBox(mn, mx);
+    if (in.depth) {
+      for (int a = 0; a < 3; a++) mn[a] = gplan_->gen_bb_min[a], mx[a] = gplan_->gen_bb_max[a];
+    } else {
+      cur_raw_->boundingBox(mn, mx);
+    }
     estimated_sensor_max_range_ = std::max(bbox_radius(mn, mx), params_.absolute_minimum_sensor_range);
   }
   {
@@ -1300,7 +1410,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
           tw.wx = w[0] / At; tw.wy = w[1] / At; tw.wz = w[2] / At;
           updatePipelineTwistVariables(tw);
           source_.realize();
-          run_second_pass();
+          if (!(gplan_ && gplan_->depth_input && !gplan_->has_2nd_pass)) run_second_pass();  // (no 2nd pass, no de-skew: nothing to run again)
           if (gplan_) record_layer_sizes(rec);  // (the record describes the layers that are aligned and merged in the end)
           rec.twist = tw;
         }
@@ -1427,6 +1537,22 @@ std::map<std::string, LidarOdometry::MapStats> LidarOdometry::localMapStats() co
   return out;
 }
 
+std::map<std::string, std::string> LidarOdometry::localMapClasses() const {
+  std::map<std::string, std::string> out;
+  auto cls = [](const std::shared_ptr<HashedVoxelPointCloud>& m) -> std::string {
+    if (!m) return "";
+    if (std::dynamic_pointer_cast<mp2p_icp_hip::SparseTreesPointCloud>(m)) return "SparseTreesPointCloud";
+    if (std::dynamic_pointer_cast<mp2p_icp_hip::CVoxelMap>(m)) return "CVoxelMap";
+    return "HashedVoxelPointCloud";
+  };
+  if (gplan_) {
+    for (const auto& m : gplan_->maps) out[m.name] = cls(m.map);
+  } else if (plan_) {
+    out[plan_->map_layer] = cls(local_map_);
+  }
+  return out;
+}
+
 LidarOdometry::LayerDump LidarOdometry::downloadLayer(const std::string& name) const {
   if (!gplan_) throw std::runtime_error("LidarOdometry::downloadLayer: only general plans keep their layers by name");
   std::shared_ptr<DevicePointCloud> l;
@@ -1495,6 +1621,7 @@ std::map<std::string, std::string> LidarOdometry::describePipeline() const {
   if (gplan_) {
     const GeneralPlan& g = *gplan_;
     d["plan"] = "general";
+    d["input"] = g.depth_input ? "depth_image" : "point_cloud";
     d["timestamp_method"] = std::to_string(g.timestamp_method);
     size_t k = 0;
     for (const auto& st : g.steps) {
@@ -1502,6 +1629,8 @@ std::map<std::string, std::string> LidarOdometry::describePipeline() const {
       if (st.kind == GeneralPlan::Kind::Delete) {
         line += " ";
         for (size_t i = 0; i < st.out.size(); i++) line += (i ? "," : "") + st.out[i];
+      } else if (st.kind == GeneralPlan::Kind::EdgesFromRangeImage) {
+        line += " depth image -> " + st.out[0] + "," + st.out[1] + " (row_window_length " + std::to_string(st.row_window_length) + ")";
       } else if (st.kind == GeneralPlan::Kind::NormalizeIntensity) {
         line += " " + st.in + " (in place" + (st.remember_range ? ", remembered range)" : ")");
       } else {

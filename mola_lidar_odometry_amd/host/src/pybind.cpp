@@ -1,5 +1,6 @@
 // pybind.cpp -- Python view of the C++ host layer, used by tests/test_host_layer.py so that the parity tests
 // drive ICP::align() exactly the way mola::LidarOdometry does (LidarOdometry.cpp:961-962).
+#include <cstring>
 #include <pybind11/functional.h>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -200,6 +201,29 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         return rec2dict(lo.records().back()); },  // (records(): the map counters of this record, read back now)
            py::arg("timestamp"), py::arg("xyz"), py::arg("t") = std::nullopt,
            py::arg("xyz_fields") = std::array<int, 3>{0, 1, 2}, py::arg("t_field") = -1, py::arg("i_field") = -1)
+      .def("onDepthImage", [rec2dict](LidarOdometry& lo, double stamp, py::array range, double fx, double fy, double cx, double cy,
+                                      double range_units, bool range_is_depth, std::optional<std::vector<double>> sensor_pose) {
+        // [rows, cols] uint16 range image, 0 = no return; read through its pointer: a C-contiguous uint16 array only (anything
+        // else is rejected instead of converted).  sensor_pose: 12 values, row-major 3x4 (default: identity)
+        if (!py::dtype::of<uint16_t>().is(range.dtype()) || !(range.flags() & py::array::c_style) || range.ndim() != 2)
+          throw std::runtime_error("range must be a C-contiguous [rows, cols] uint16 array");
+        if (sensor_pose && sensor_pose->size() != 12) throw std::runtime_error("sensor_pose must hold 12 values (row-major 3x4)");
+        mh_range_image_params cam;
+        memset(&cam, 0, sizeof(cam));
+        cam.rows = (uint32_t)range.shape(0);
+        cam.cols = (uint32_t)range.shape(1);
+        cam.fx = (float)fx; cam.fy = (float)fy; cam.cx = (float)cx; cam.cy = (float)cy;
+        cam.range_units = (float)range_units;
+        cam.range_is_depth = range_is_depth ? 1u : 0u;
+        for (int i = 0; i < 12; i++) cam.sensor_pose[i] = sensor_pose ? (*sensor_pose)[i] : (i % 5 == 0 ? 1.0 : 0.0);
+        {
+          py::gil_scoped_release nogil;
+          (void)lo.onDepthImage(stamp, static_cast<const uint16_t*>(range.data()), cam);
+        }
+        return rec2dict(lo.records().back()); },
+           py::arg("timestamp"), py::arg("range"), py::arg("fx"), py::arg("fy"), py::arg("cx"), py::arg("cy"),
+           py::arg("range_units") = 0.001, py::arg("range_is_depth") = true, py::arg("sensor_pose") = std::nullopt)
+      .def("localMapClasses", &LidarOdometry::localMapClasses)
       .def("setIntensityInput", &LidarOdometry::setIntensityInput)
       .def("setAlignBatcher", &LidarOdometry::setAlignBatcher)
       .def("prefetch", [](py::object self, py::array xyz_any, std::optional<py::array> t_any,
