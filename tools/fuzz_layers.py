@@ -8,7 +8,11 @@ to 1e-7; covariance to the tolerance of the parity suite.  A one-pair case is al
 few cases are run again on the warm context at the end: bitwise their first run.  A case whose run decides a stall, hook,
 min_delta or max_cost comparison within 1e-9 (relative) of its threshold, or solves normal equations with a condition number
 above 1e10 (one or two distinct pairings in all: the step is then made of rounding, on the device as in any float64
-restatement), is listed apart with that evidence, and whether it agreed anyway."""
+restatement), is listed apart with that evidence, and whether it agreed anyway.
+
+fuzz_layers.py [cases [seed [dense]]]: with the third argument `dense` the maps are tests/dense_cases.py's (the uncapped dense-voxel
+maps room, mixed and room_clear and the cap-20 map beside them) instead of the outdoor scene, the scans 1 to 2561 points of the
+room with points pushed a voxel out of its walls; every other draw, and the default draws, are unchanged."""
 import os
 import sys
 
@@ -39,7 +43,46 @@ def scan_size():
     return max(0, edge * int(rng.integers(1, 58 if edge == 1024 else 200)) + int(rng.choice([-1, 0, 1])))
 
 
+dense = len(sys.argv) > 3 and sys.argv[3] == "dense"
+if dense:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dense_cases as dc  # noqa: E402
+    dense_inp = dc.Inputs()
+
+
+def dense_inputs():
+    """(pose, cloud, points per map, map arguments, a scan-size draw) from the dense-cell inputs"""
+    T_gt = dc.pose(float(rng.uniform(-0.5, 0.5)), float(rng.uniform(-0.5, 0.5)), float(rng.uniform(-0.1, 0.2)), float(rng.uniform(-0.2, 0.2)),
+                   float(rng.normal(0, 0.01)), float(rng.normal(0, 0.01)))
+    cloud = dc.draw_scan(dense_inp.maps["room"][0], T_gt, 4000, rng)
+    keys = [str(k) for k in rng.choice(["room", "mixed", "room_clear", "capped"], int(rng.integers(1, 4)))]
+    mps = [dense_inp.maps[k][0] for k in keys]
+    maps = [(dense_inp.maps[k][1], dense_inp.maps[k][2], 0, dense_inp.maps[k][3]) for k in keys]
+    return T_gt, cloud, mps, maps
+
+
 def make_case():
+    if dense:
+        T_gt, cloud, mp, maps = dense_inputs()
+        n_maps, n_pairs = len(maps), int(rng.integers(1, 5))
+        scans = [cloud[rng.choice(len(cloud), int(rng.choice([1, 63, 64, 65, 129, 700, 2000, 2561])), replace=False)].copy()
+                 for _ in range(int(rng.integers(1, min(n_pairs, 3) + 1)))]
+        iters = int(rng.integers(12, 21))
+        thr0, kp = dc.schedule(iters, float(rng.uniform(0.8, 1.5))), np.full(iters, 0.3)
+        pairs = [dict(map=int(rng.integers(0, n_maps)), scan=int(rng.integers(0, len(scans))), threshold=float(rng.uniform(0.7, 1.2)) * thr0,
+                      threshold_angular_deg=0.0, weight=float(rng.choice([1.0, float(rng.uniform(0.1, 5.0))]))) for _ in range(n_pairs)]
+        d = rng.normal(0, 1, 6)
+        off = np.concatenate([d[:3] * float(rng.uniform(0.03, 0.15)) / np.linalg.norm(d[:3]), d[3:] * np.deg2rad(0.6)])
+        guess = oracle_c.pose_compose(T_gt, dc.pose(*off))
+        gkw = dict(max_inner_iterations=int(rng.integers(1, 5)), robust_kernel=int(rng.integers(0, 6)),
+                   min_delta=float(rng.choice([0.0, 1e-7, 1e-4])), max_cost=0.0)
+        kw = dict(max_iterations=iters, kernel_param=kp, disable_stall_test=bool(rng.integers(0, 2)))
+        prior = (T_gt, dc.PRIOR_INFO) if rng.integers(0, 3) == 0 else None
+        if sum(len(scans[i]) for i in {e["scan"] for e in pairs}) < 63:  # (one-point layers alone do not hold six dimensions: the
+            prior = (T_gt, dc.PRIOR_INFO)                                #  weak prior of the fixed cases, or the case is set apart)
+        ctl = dict(poll_every=int(rng.choice([0, 0, 1, 3, 7])), expected_iterations=0)
+        sw = [k for k in SWITCHES[:3] if rng.integers(0, 4) == 0]
+        return dict(mp=mp, maps=maps, scans=scans, pairs=pairs, guess=guess, gkw=gkw, kw=kw, prior=prior, ctl=ctl, sw=sw)
     pose = [float(rng.uniform(-2, 2)), float(rng.uniform(-2, 2)), synth.SENSOR_H, float(rng.uniform(-0.2, 0.2)), 0.002, -0.002]
     cloud = synth.make_scan(scene, pose, rings=64, azimuths=1000, seed=int(rng.integers(1, 10000)))
     mp = synth.make_map(scene, int(rng.choice([40000, 100000])), int(rng.integers(1, 10000)))
@@ -130,8 +173,9 @@ def bitwise(a, b, single=False):
 bad, near, kept = 0, [], []
 for case in range(n_cases):
     c = make_case()
-    g_maps = [capi.Map(ctx, *m).build(c["mp"]) for m in c["maps"]]
-    o_maps = [oracle_c.Map(*m).insert(c["mp"]) for m in c["maps"]]
+    mps = c["mp"] if isinstance(c["mp"], list) else [c["mp"]] * len(c["maps"])  # (dense: every map its own points)
+    g_maps = [capi.Map(ctx, *m).build(q) for m, q in zip(c["maps"], mps)]
+    o_maps = [oracle_c.Map(*m).insert(q) for m, q in zip(c["maps"], mps)]
     g_scans = [capi.Scan(ctx, s) for s in c["scans"]]
     try:
         r = run_device(c, g_maps, g_scans)
@@ -166,7 +210,7 @@ for case in range(n_cases):
     bad += 0 if ok else 1
     print("case %3d pairs=%d maps=%s scans=%s inner=%d kernel=%d min_delta=%g max_cost=%g stall_off=%d hook=%d prior=%d "
           "poll=%d expect=%d sw=%s %s -> %s" % (
-              case, len(c["pairs"]), [("ndt" if len(m) > 3 else "trunc" if m[2] else "floor", round(m[0], 2), m[1]) for m in c["maps"]],
+              case, len(c["pairs"]), [("ndt" if len(m) > 4 else "trunc" if m[2] else "floor", round(m[0], 2), m[1]) for m in c["maps"]],
               [len(s) for s in c["scans"]], c["gkw"]["max_inner_iterations"], c["gkw"]["robust_kernel"], c["gkw"]["min_delta"],
               c["gkw"]["max_cost"], c["kw"]["disable_stall_test"], "hook_enabled" in c["kw"], c["prior"] is not None,
               c["ctl"]["poll_every"], c["ctl"]["expected_iterations"], ",".join(s[3:] for s in c["sw"]) or "-", note,
