@@ -49,7 +49,7 @@ extern "C" {
  * mh_layer_pair_gates and mh_icp_align_layers_gated, mh_layer_pair_knn and mh_icp_align_layers_kbest, mh_layer_pair_plane and
  * mh_icp_align_layers_planes, mh_layer_job_opts and mh_icp_align_layers_batch_opts, mh_layer_job_planes and
  * mh_icp_align_layers_batch_planes, mh_occmap_params / mh_occmap_info and the mh_occmap_* entry points, mh_range_image_params and
- * mh_scan_edges_from_range_image: new structs and entry
+ * mh_scan_edges_from_range_image, mh_radius_out / mh_radius_info and mh_nn_search_radius: new structs and entry
  * points change no existing layout, and a binder that lacks
  * an entry point finds out when it resolves the symbol).  A binder built against this header checks
  * `mh_abi_version() == MH_ABI_VERSION` once after loading the library (capi.py does; the C++ host layer links the header it was
@@ -420,6 +420,47 @@ MH_API mh_status mh_nn_search_k(const mh_map* map, const mh_scan* scan, const do
  * the 27-voxel block (no threshold applied).  Arrays hold scan-size entries; any may be NULL. */
 MH_API mh_status mh_nn_search_dense(const mh_map* map, const mh_scan* scan, const double T[12], uint32_t* global_idx,
                                     float* gx, float* gy, float* gz, float* d2, int32_t mem);
+
+/* Radius search: mrpt::maps::NearestNeighborsCapable::nn_radius_search [U] on the hashed voxel map, batched over a scan -- the
+ * one neighbour query with a VARIABLE number of results per point.  Upstream's source is not vendored, so parity with it is
+ * unpinned [U] as for every other map query; what follows is the specification.
+ *  - The query point of scan point l is p' = (float)(R*l + t), as in every other search.
+ *  - Its results are EVERY stored map point (x, y, z) with d2 < r2, where dx = x - p'x (dy, dz alike),
+ *    d2 = (dx*dx + dy*dy) + dz*dz in fp32, un-fused, and r2 = (float)(radius * radius) with the square taken in fp64.  The
+ *    comparison is strict: d2 == r2 is out.  The set is defined over all stored points; which voxels are visited is an
+ *    implementation matter (a conservative block around voxel_of(p' -+ radius) per axis, widened against fp32 rounding:
+ *    extra voxels cost time and never change results).
+ *  - Order.  MH_RADIUS_VISIT_ORDER: the map's storage order -- voxels ascending in (kx, ky, kz), insertion order inside a
+ *    voxel.  That is the order of mh_map_download, so a point's results are a subsequence of the download.
+ *    MH_RADIUS_SORTED: ascending (d2, visit position); the first result of a point is then mh_nn_search_dense's answer
+ *    whenever that answer lies within the radius.
+ *  - Both index modes.  On an NDT map the two statistics records of a voxel are never results.
+ *  - A non-finite p', or one with |p' / voxel_size| >= 1e6 on any axis (the guard of the other searches), has no results.  A
+ *    voxel of the block whose index leaves the key range is skipped.
+ *  - Outputs.  The arrays of mh_radius_out live in `mem` (MH_MEM_HOST or MH_MEM_DEVICE); any may be NULL, and so may `out`.
+ *    `offsets` (scan size + 1 entries; the results of point i are entries [offsets[i], offsets[i+1])) and `info` are always
+ *    filled; max_per_query is the largest result count of any point.  The result arrays are written only if
+ *    capacity >= n_results, and then n_written = n_results; otherwise n_written = 0, they are not touched, and the status is
+ *    still MH_OK: a count-only first call (capacity 0) and a sized second call are the intended use.
+ *  - The call blocks like mh_nn_search_dense and orders itself behind a queued mh_map_insert.  An empty scan: MH_OK, offsets[0] = 0.
+ *  - Refusals, all decided before anything is queued: MH_ERR_INVALID_ARGUMENT for a NULL map, scan, T or info, a bad `mem`, a
+ *    non-finite pose, a radius that is not finite or not > 0, unknown flag bits, map and scan on different devices;
+ *    MH_ERR_UNSUPPORTED for radius > MH_RADIUS_MAX_VOXELS x voxel_size (a block wider than 8 voxels per axis).
+ *    MH_ERR_UNSUPPORTED also for a total of 2^32 results or more (known once they are counted; info holds the count). */
+enum { MH_RADIUS_VISIT_ORDER = 0, MH_RADIUS_SORTED = 1 };
+#define MH_RADIUS_MAX_VOXELS 3
+typedef struct {       /* arrays live in `mem`; any may be NULL */
+  uint32_t* offsets;    /* scan size + 1 entries: results of point i are [offsets[i], offsets[i+1]) */
+  uint32_t* global_idx; /* source index of the map point, as the other searches report it */
+  float *gx, *gy, *gz, *d2;
+  uint64_t capacity;    /* entries each result array can hold */
+} mh_radius_out;
+typedef struct {
+  uint64_t n_results, n_written;
+  uint32_t max_per_query, reserved_;
+} mh_radius_info;
+MH_API mh_status mh_nn_search_radius(const mh_map* map, const mh_scan* scan, const double T[12], double radius, uint32_t flags,
+                                     const mh_radius_out* out, int32_t mem, mh_radius_info* info);
 
 /* Replaces mp2p_icp::Matcher_Point2Plane::implMatchOneLayer [U] on a mola::NDT [U] map (lidar3d-ndt.yaml:195-200,
  * 236-254).  The upstream semantics are unverified (SURVEY App.B U10); implemented default: among

@@ -29,6 +29,8 @@ KERNEL_NONE, KERNEL_GM_C4, KERNEL_GM_KISS, KERNEL_GM_BARRON, KERNEL_CAUCHY, KERN
 TERM_NAMES = ["Undefined", "NoPairings", "SolverError", "MaxIterations", "Stalled",
               "QualityCheckpointFailed", "HookRequest"]
 NO_MATCH = 0xFFFFFFFF
+RADIUS_VISIT_ORDER, RADIUS_SORTED = 0, 1             # mh_nn_search_radius flags
+RADIUS_MAX_VOXELS = 3                                # MH_RADIUS_MAX_VOXELS
 
 _FP = C.POINTER(C.c_float)
 _UP = C.POINTER(C.c_uint32)
@@ -69,6 +71,16 @@ class PairsPlOut(C.Structure):
 
 class MatchInfo(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("potential_pairings", C.c_uint64)]
+
+
+class RadiusOut(C.Structure):
+    """mh_radius_out: where mh_nn_search_radius writes (arrays in `mem`, any may be NULL)."""
+    _fields_ = [("offsets", _UP), ("global_idx", _UP), ("gx", _FP), ("gy", _FP), ("gz", _FP), ("d2", _FP),
+                ("capacity", C.c_uint64)]
+
+
+class RadiusInfo(C.Structure):
+    _fields_ = [("n_results", C.c_uint64), ("n_written", C.c_uint64), ("max_per_query", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
 class PairsPt2Pt(C.Structure):
@@ -268,6 +280,8 @@ _SIGNATURES = {
                                    C.c_int32, C.POINTER(MatchInfo)]),
     "mh_nn_search_dense": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32]),
+    "mh_nn_search_radius": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_double, C.c_uint32, C.POINTER(RadiusOut), C.c_int32,
+                                        C.POINTER(RadiusInfo)]),
     "mh_nn_search_pt2pl": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_double, C.c_uint32, C.POINTER(PairsPlOut), C.c_int32,
                                        C.POINTER(MatchInfo)]),
     "mh_nn_search_pt2pl_knn": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.POINTER(Pt2PlKnnParams), C.POINTER(PairsPlOut), C.c_int32,
@@ -810,6 +824,30 @@ def nn_search_dense(m: Map, s: Scan, T):
                                   MEM_HOST))
     k = s.n
     return dict(global_idx=gi[:k], global_xyz=np.stack([gx[:k], gy[:k], gz[:k]], 1), d2=d2[:k])
+
+
+def nn_search_radius(m: Map, s: Scan, T, radius, sorted=False):
+    """Every stored map point within `radius` of each transformed scan point (mh_nn_search_radius): a count-only call, then a
+    sized one.  Returns (offsets [n + 1], global_idx, xyz [k, 3], d2); the results of point i are rows offsets[i]:offsets[i + 1],
+    in the map's storage order, or by ascending (d2, storage position) with sorted=True."""
+    n = s.n
+    T = _T12(T)
+    flags = RADIUS_SORTED if sorted else RADIUS_VISIT_ORDER
+    off = np.zeros(n + 1, np.uint32)
+    info = RadiusInfo()
+    out = RadiusOut()
+    out.offsets = off.ctypes.data_as(_UP)
+    _chk(lib().mh_nn_search_radius(m._h, s._h, T.ctypes.data_as(_DP), float(radius), flags, C.byref(out), MEM_HOST, C.byref(info)))
+    k = int(info.n_results)
+    gi = np.zeros(max(k, 1), np.uint32)
+    gx, gy, gz, d2 = (np.zeros(max(k, 1), np.float32) for _ in range(4))
+    if k:
+        out = RadiusOut(off.ctypes.data_as(_UP), gi.ctypes.data_as(_UP), gx.ctypes.data_as(_FP), gy.ctypes.data_as(_FP),
+                        gz.ctypes.data_as(_FP), d2.ctypes.data_as(_FP), k)
+        _chk(lib().mh_nn_search_radius(m._h, s._h, T.ctypes.data_as(_DP), float(radius), flags, C.byref(out), MEM_HOST,
+                                       C.byref(info)))
+        assert int(info.n_written) == k
+    return off, gi[:k], np.stack([gx[:k], gy[:k], gz[:k]], 1), d2[:k]
 
 
 @dataclass

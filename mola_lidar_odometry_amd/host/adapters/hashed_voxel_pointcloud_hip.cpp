@@ -7,6 +7,7 @@
 #include <mrpt/obs/CObservationPointCloud.h>  // [U]
 #include <mrpt/opengl/CPointCloud.h>          // [U]
 
+#include <cmath>
 #include <iostream>
 #include <stdexcept>
 
@@ -159,10 +160,45 @@ void HashedVoxelPointCloudHIP::nn_multiple_search(const mrpt::math::TPoint3Df& q
         resultIndicesOrIDs.push_back(gi[k]);
     }
 }
-void HashedVoxelPointCloudHIP::nn_radius_search(const mrpt::math::TPoint3Df&, float, std::vector<mrpt::math::TPoint3Df>&,
-                                                std::vector<float>&, std::vector<uint64_t>&, size_t) const
+void HashedVoxelPointCloudHIP::nn_radius_search(const mrpt::math::TPoint3Df& q, float search_radius_sqr,
+                                                std::vector<mrpt::math::TPoint3Df>& results, std::vector<float>& out_dists_sqr,
+                                                std::vector<uint64_t>& resultIndicesOrIDs, size_t maxPoints) const
 {
-    THROW_EXCEPTION("nn_radius_search: not provided by the device map");
+    // one query through mh_nn_search_radius: a count-only call, then a sized one.  maxPoints == 0: every stored point closer than
+    // the radius, in the map's storage order; maxPoints > 0: the nearest maxPoints of them in ascending (distance, storage
+    // position) -- the sorted form, truncated here.  sqrt in fp64 of a float squares back to that float, so the device compares
+    // d^2 with exactly search_radius_sqr.  A radius above MH_RADIUS_MAX_VOXELS voxels is refused by the library (mh_check throws).
+    results.clear();
+    out_dists_sqr.clear();
+    resultIndicesOrIDs.clear();
+    if (!map_ || !(search_radius_sqr > 0.f)) return;
+    mh_check(mh_scan_update(staging_, &q.x, &q.y, &q.z, 1, MH_MEM_HOST), "mh_scan_update");
+    const double   I[12]  = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const double   radius = std::sqrt((double)search_radius_sqr);
+    const uint32_t flags  = maxPoints > 0 ? MH_RADIUS_SORTED : MH_RADIUS_VISIT_ORDER;
+    uint32_t       off[2] = {0, 0};
+    mh_radius_out  out{};
+    mh_radius_info info{};
+    out.offsets = off;
+    mh_check(mh_nn_search_radius(map_, staging_, I, radius, flags, &out, MH_MEM_HOST, &info), "mh_nn_search_radius");
+    const size_t k = (size_t)info.n_results;
+    if (!k) return;
+    std::vector<uint32_t> gi(k);
+    std::vector<float>    gx(k), gy(k), gz(k), d2(k);
+    out.global_idx = gi.data();
+    out.gx         = gx.data();
+    out.gy         = gy.data();
+    out.gz         = gz.data();
+    out.d2         = d2.data();
+    out.capacity   = k;
+    mh_check(mh_nn_search_radius(map_, staging_, I, radius, flags, &out, MH_MEM_HOST, &info), "mh_nn_search_radius");
+    const size_t keep = maxPoints > 0 && maxPoints < (size_t)info.n_written ? maxPoints : (size_t)info.n_written;
+    for (size_t e = 0; e < keep; e++)
+    {
+        results.emplace_back(gx[e], gy[e], gz[e]);
+        out_dists_sqr.push_back(d2[e]);
+        resultIndicesOrIDs.push_back(gi[e]);
+    }
 }
 
 std::string HashedVoxelPointCloudHIP::asString() const { return "HashedVoxelPointCloudHIP (device resident, libmolahip)"; }

@@ -8,7 +8,8 @@
 // mh_map on the GPU.  insertObservation / insertAnotherMap (what FilterMerge calls, yaml:362-368) forward to
 // mh_map_insert, so the key-frame update needs no host copy of the map, and ICP_HIP (mp2p_icp_plugin.cpp) takes the
 // handle directly instead of mirroring a host map.  The NearestNeighborsCapable methods are implemented for
-// completeness (single queries through mh_nn_search_dense: slow, meant for tools, not for the ICP loop).
+// completeness (single queries through mh_nn_search_dense / mh_nn_search_k / mh_nn_search_radius: slow, meant for tools, not
+// for the ICP loop).
 #pragma once
 #include <mrpt/maps/CMetricMap.h>                // [U]
 #include <mrpt/maps/NearestNeighborsCapable.h>   // [U]

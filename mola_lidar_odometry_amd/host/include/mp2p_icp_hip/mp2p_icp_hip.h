@@ -217,6 +217,13 @@ class DevicePointCloud : public Layer {
   std::shared_ptr<DeviceContext> ctx_;
   mh_scan* scan_ = nullptr;
 };
+// what NearestNeighborsCapable::nn_radius_search [U] returns, for a batch of queries (mh_nn_search_radius): the results of query i
+// are entries [offsets[i], offsets[i + 1]) of the other arrays
+struct RadiusResults {
+  std::vector<uint32_t> offsets, globalIdx;
+  std::vector<float> gx, gy, gz, errSq;
+  uint32_t maxPerQuery = 0;
+};
 // mola::HashedVoxelPointCloud stand-in, device resident (NearestNeighborsCapable role only)
 class HashedVoxelPointCloud : public Layer {
  public:
@@ -235,6 +242,12 @@ class HashedVoxelPointCloud : public Layer {
   // before an alignment is queued: the largest pair distance its matchers can accept on this layer (a no-op here; CVoxelMap
   // grows its search voxel to it)
   virtual void prepareSearch(double /*max_radius*/) const {}
+  // every stored point within `radius` of (float)(T * query), per query (mh_nn_search_radius: a count-only call, then a sized
+  // one): in the map's storage order, or sorted by ascending (distance, storage position).  Calls prepareSearch(radius) first,
+  // so a CVoxelMap answers over the centres of its occupied voxels.
+  RadiusResults radiusSearch(const DevicePointCloud& queries, const CPose3D& T, double radius, bool sorted = false) const;
+  RadiusResults radiusSearch(const float* x, const float* y, const float* z, size_t n, const CPose3D& T, double radius,
+                             bool sorted = false) const;
   mh_map* handle() const { return map_; }
   const std::shared_ptr<DeviceContext>& context() const { return ctx_; }
 

@@ -237,6 +237,35 @@ void HashedVoxelPointCloud::insertPointCloud(const DevicePointCloud& pc, const C
 
 void HashedVoxelPointCloud::clear() { check(mh_map_build(map_, nullptr, nullptr, nullptr, 0, MH_MEM_HOST), "mh_map_build"); }
 
+RadiusResults HashedVoxelPointCloud::radiusSearch(const DevicePointCloud& queries, const CPose3D& T, double radius, bool sorted) const {
+  prepareSearch(radius);
+  RadiusResults r;
+  const size_t n = queries.size();
+  r.offsets.assign(n + 1, 0u);
+  const uint32_t flags = sorted ? MH_RADIUS_SORTED : MH_RADIUS_VISIT_ORDER;
+  mh_radius_out out{};
+  mh_radius_info info{};
+  out.offsets = r.offsets.data();
+  check(mh_nn_search_radius(map_, queries.handle(), T.T, radius, flags, &out, MH_MEM_HOST, &info), "mh_nn_search_radius");
+  r.maxPerQuery = info.max_per_query;
+  const size_t k = (size_t)info.n_results;
+  if (!k) return r;
+  r.globalIdx.resize(k);
+  r.gx.resize(k); r.gy.resize(k); r.gz.resize(k); r.errSq.resize(k);
+  out.global_idx = r.globalIdx.data();
+  out.gx = r.gx.data(); out.gy = r.gy.data(); out.gz = r.gz.data(); out.d2 = r.errSq.data();
+  out.capacity = k;
+  check(mh_nn_search_radius(map_, queries.handle(), T.T, radius, flags, &out, MH_MEM_HOST, &info), "mh_nn_search_radius");
+  if (info.n_written != k) throw std::runtime_error("mh_nn_search_radius: the map changed between the counting and the sized call");
+  return r;
+}
+RadiusResults HashedVoxelPointCloud::radiusSearch(const float* x, const float* y, const float* z, size_t n, const CPose3D& T,
+                                                  double radius, bool sorted) const {
+  DevicePointCloud pc(ctx_);
+  pc.setPoints(x, y, z, n);
+  return radiusSearch(pc, T, radius, sorted);
+}
+
 DevicePointCloud::DevicePointCloud(std::shared_ptr<DeviceContext> ctx) : ctx_(std::move(ctx)) {
   check(mh_scan_create(ctx_->get(), nullptr, nullptr, nullptr, 0, MH_MEM_HOST, &scan_), "mh_scan_create");
 }

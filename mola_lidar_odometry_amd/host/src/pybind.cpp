@@ -85,7 +85,35 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("insertPoints", [](HashedVoxelPointCloud& h, py::array_t<float, py::array::c_style | py::array::forcecast> xyz) {
         auto c = make_cloud(xyz); h.insertPoints(c->x.data(), c->y.data(), c->z.data(), c->size()); })
       .def("size", &HashedVoxelPointCloud::size)
-      .def("voxelCount", &HashedVoxelPointCloud::voxelCount);
+      .def("voxelCount", &HashedVoxelPointCloud::voxelCount)
+      // (offsets, global_idx, xyz [k, 3], d2) of mh_nn_search_radius; T: 12 values, row-major [R|t]
+      .def("radiusSearch", [](const HashedVoxelPointCloud& h, py::array_t<float, py::array::c_style | py::array::forcecast> xyz,
+                              std::vector<double> T, double radius, bool sorted) {
+        if (T.size() != 12) throw std::runtime_error("need 12 values");
+        CPose3D P; std::copy(T.begin(), T.end(), P.T);
+        auto c = make_cloud(xyz);
+        const RadiusResults r = h.radiusSearch(c->x.data(), c->y.data(), c->z.data(), c->size(), P, radius, sorted);
+        const py::ssize_t k = (py::ssize_t)r.globalIdx.size();
+        py::array_t<float> pts({k, (py::ssize_t)3});
+        auto w = pts.mutable_unchecked<2>();
+        for (py::ssize_t i = 0; i < k; i++) { w(i, 0) = r.gx[i]; w(i, 1) = r.gy[i]; w(i, 2) = r.gz[i]; }
+        return py::make_tuple(py::array_t<uint32_t>((py::ssize_t)r.offsets.size(), r.offsets.data()),
+                              py::array_t<uint32_t>(k, r.globalIdx.data()), pts, py::array_t<float>(k, r.errSq.data()));
+      }, py::arg("queries"), py::arg("T"), py::arg("radius"), py::arg("sorted") = false);
+  py::class_<SparseTreesPointCloud, HashedVoxelPointCloud, std::shared_ptr<SparseTreesPointCloud>>(m, "SparseTreesPointCloud")
+      .def(py::init([](float grid, float clearance) { return std::make_shared<SparseTreesPointCloud>(grid, clearance); }));
+  py::class_<CVoxelMap, HashedVoxelPointCloud, std::shared_ptr<CVoxelMap>>(m, "CVoxelMap")
+      .def(py::init([](float resolution) { return std::make_shared<CVoxelMap>(CVoxelMap::defaultParams(resolution)); }))
+      .def("insertPointCloud", [](CVoxelMap& v, py::array_t<float, py::array::c_style | py::array::forcecast> xyz, std::vector<double> T,
+                                  float remove_voxels_farther_than) {
+        if (T.size() != 12) throw std::runtime_error("need 12 values");
+        CPose3D P; std::copy(T.begin(), T.end(), P.T);
+        auto c = make_cloud(xyz);
+        DevicePointCloud pc(v.context());
+        pc.setPoints(c->x.data(), c->y.data(), c->z.data(), c->size());
+        v.insertPointCloud(pc, P, remove_voxels_farther_than);
+      }, py::arg("xyz"), py::arg("T"), py::arg("remove_voxels_farther_than") = 0.f)
+      .def("searchVoxelSize", &CVoxelMap::searchVoxelSize);
   py::class_<NDT, HashedVoxelPointCloud, std::shared_ptr<NDT>>(m, "NDT")
       .def(py::init([](float vs, uint32_t cap, float min_dist, float ratio) { return std::make_shared<NDT>(vs, cap, min_dist, ratio); }))
       .def("planeCount", &NDT::planeCount);
