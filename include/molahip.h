@@ -377,6 +377,31 @@ typedef struct {
 } mh_range_image_params;
 MH_API mh_status mh_scan_edges_from_range_image(mh_ctx* ctx, const uint16_t* range, int32_t mem, const mh_range_image_params* p,
                                                 mh_scan* edges, mh_scan* planes);
+/* The clouds of the sensors of one rig, each in its own sensor frame, merged into one vehicle-frame layer: what
+ * mola::LidarOdometry::onLidarImpl does on the CPU for every observation of a synchronised group (LidarOdometry.cpp:704-721: the
+ * generator applies the sensor's pose, FilterAdjustTimestamps runs with that sensor's SENSOR_TIME_OFFSET, merge_with appends).
+ * `out` holds the sum of the sources' sizes: source 0's points first in their own order, then source 1's, and so on.  Point j
+ * of source k, with P = params[k].sensor_pose and x, y, z promoted to double:
+ *   x' = (float)(((P[0]*x + P[1]*y) + P[2]*z) + P[3]);  y' and z' with rows 1 and 2 of P            (fp64, unfused, rounded once)
+ *   time stamp, timestamp_method != MH_TS_NONE: tmin_k, tmax_k = min and max over ALL stamps of source k alone, compared as the
+ *     order-preserving unsigned image of their bits (-0 below +0), as mh_scan_preprocess takes them;
+ *     d = 0.5f*(tmin_k + tmax_k) for MH_TS_MIDDLE_IS_ZERO, tmin_k for MH_TS_EARLIEST_IS_ZERO;  t' = (t - d) + time_offset, in float
+ *   time stamp, MH_TS_NONE: t' = t.   Intensity: copied.
+ * `out` carries time stamps only when every non-empty source does (a mix: MH_ERR_INVALID_ARGUMENT), and intensity likewise; it
+ * carries no src_idx, and its tile order is dropped, as after mh_scan_update_aos_i.  Empty sources are legal and contribute
+ * nothing; a source may appear more than once.  Refused with a message (mh_last_error_string) before any device work, `out`
+ * untouched, all MH_ERR_INVALID_ARGUMENT: n_sources 0 or above MH_MAX_MERGE_SOURCES, a NULL pointer, `out` among the sources,
+ * scans of different contexts, a bad timestamp_method, a total of 2^31 - 16 points or more.  Asynchronous on the context's
+ * stream like mh_scan_deskew: the host knows the output size, nothing is read back.  At most two launches (the min / max of
+ * the stamps, skipped when no source adjusts its stamps; the fill) and one small copy, whatever n_sources is. */
+#define MH_MAX_MERGE_SOURCES 8
+typedef struct {
+  double sensor_pose[12];   /* the sensor on the vehicle, row-major 3x4 */
+  int32_t timestamp_method; /* MH_TS_*, applied to THIS source's stamps alone */
+  float time_offset;        /* this source's SENSOR_TIME_OFFSET; ignored with MH_TS_NONE, as in mh_scan_preprocess */
+} mh_merge_source;          /* 104 bytes */
+MH_API mh_status mh_scan_merge_sensors(size_t n_sources, const mh_scan* const* sources, const mh_merge_source* params,
+                                       mh_scan* out);
 /* Copy a scan to HOST arrays (any may be NULL; t / src_idx are zero-filled when the scan has none). */
 MH_API mh_status mh_scan_download(const mh_scan* scan, float* x, float* y, float* z, float* t, uint32_t* src_idx);
 /* Copy a scan's intensity to a HOST array of n entries; MH_ERR_INVALID_ARGUMENT when the scan carries none. */

@@ -205,6 +205,14 @@ class RangeImageParams(C.Structure):
                 ("row_window_length", C.c_uint32), ("score_threshold", C.c_float)]
 
 
+class MergeSource(C.Structure):
+    """mh_merge_source: one sensor of a rig for mh_scan_merge_sensors -- its pose on the vehicle and its time-stamp adjustment."""
+    _fields_ = [("sensor_pose", C.c_double * 12), ("timestamp_method", C.c_int32), ("time_offset", C.c_float)]
+
+
+MAX_MERGE_SOURCES = 8  # MH_MAX_MERGE_SOURCES
+
+
 class OccMapParams(C.Structure):
     """mh_occmap_params: the occupancy voxel map (mrpt::maps::CVoxelMap stand-in)."""
     _fields_ = [("resolution", C.c_float), ("prob_hit", C.c_float), ("prob_miss", C.c_float), ("clamp_min", C.c_float),
@@ -265,6 +273,7 @@ _SIGNATURES = {
     "mh_scan_preprocess_batch": (C.c_int32, [C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(PreprocessParams), C.c_size_t,
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "mh_scan_deskew": (C.c_int32, [C.c_void_p, _DP, C.c_void_p]),
+    "mh_scan_merge_sensors": (C.c_int32, [C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(MergeSource), C.c_void_p]),
     "mh_scan_deskew_pair": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_void_p, C.c_void_p, _FP, _FP, C.POINTER(C.c_uint64)]),
     "mh_scan_curvature": (C.c_int32, [C.c_void_p, C.POINTER(CurvatureParams), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mh_scan_normalize_intensity": (C.c_int32, [C.c_void_p, _FP]),
@@ -1286,6 +1295,23 @@ def preprocess_batch(raws, params, out_maps, out_icps=None):
     hs = lambda scans: (C.c_void_p * n)(*[(sc._h if sc is not None else None) for sc in scans])
     _chk(lib().mh_scan_preprocess_batch(n, hs(raws), arr, C.sizeof(PreprocessParams) if per_job else 0, hs(out_maps),
                                         hs(out_icps) if out_icps is not None else None))
+
+
+def merge_source(sensor_pose=None, timestamp_method=TS_NONE, time_offset=0.0) -> MergeSource:
+    """sensor_pose: 12 values or a 3x4 / 4x4 matrix, the sensor on the vehicle (default: identity)."""
+    P = np.eye(4)[:3] if sensor_pose is None else np.asarray(sensor_pose, np.float64).reshape(-1)[:12].reshape(3, 4)
+    return MergeSource((C.c_double * 12)(*[float(v) for v in P.ravel()]), int(timestamp_method), float(time_offset))
+
+
+def scan_merge_sensors(sources, params, out: "Scan"):
+    """mh_scan_merge_sensors: the scans of a rig's sensors (each in its sensor frame) appended into `out` in the vehicle frame,
+    source 0 first; params: one MergeSource (merge_source(...)) per source.  Asynchronous on the context's stream."""
+    assert len(sources) == len(params)
+    n = len(sources)
+    hs = (C.c_void_p * max(n, 1))(*[s._h for s in sources])
+    ps = (MergeSource * max(n, 1))(*params)
+    _chk(lib().mh_scan_merge_sensors(n, hs, ps, out._h))
+    return out
 
 
 def scan_curvature(scan: "Scan", params: "CurvatureParams", out_larger: "Scan | None", out_smaller: "Scan | None" = None,

@@ -11,6 +11,8 @@
 //   FilterCurvature         -> three-point stencil, one scan of packed class counters, three-way compaction (mh_k_curv.h)
 //   FilterNormalizeIntensity / FilterByIntensity -> min / max reduction + in-place rewrite; thresholds through the
 //                              curvature filter's scan and scatter (mh_k_intensity.h)
+//   (multi-LiDAR rigs)      -> sensor pose + per-sensor time-stamp adjust + append: two launches for any number of sensors
+//                              (mh_k_merge.h)
 //   GeneratorEdgesFromRangeImage -> row stencil over a 16-bit range image staged in LDS, the same packed-counter scan, a
 //                              scatter that unprojects each kept pixel (mh_k_rimg.h)
 // Every call that derives a layer carries the input's optional intensity channel along (out.i[k] == raw.i[out.src[k]]).
@@ -25,6 +27,7 @@
 #include "mh_k_curv.h"
 #include "mh_k_intensity.h"
 #include "mh_k_rimg.h"
+#include "mh_k_merge.h"
 
 using namespace mh;
 
@@ -1004,6 +1007,62 @@ mh_status mh_scan_preprocess_batch(size_t n_jobs, const mh_scan* const* raws, co
     }
   }
   return preprocess_batch(n_jobs, raws, params, params_stride, out_maps, out_icps);
+}
+
+mh_status mh_scan_merge_sensors(size_t n_sources, const mh_scan* const* sources, const mh_merge_source* params, mh_scan* out) {
+  MH_REQUIRE(n_sources >= 1 && n_sources <= MH_MAX_MERGE_SOURCES, "n_sources must be in 1..MH_MAX_MERGE_SOURCES");
+  MH_REQUIRE(sources && params && out, "null argument");
+  size_t total = 0, n_live = 0, n_with_t = 0, n_with_i = 0;
+  for (size_t k = 0; k < n_sources; k++) {
+    const mh_scan* src = sources[k];
+    MH_REQUIRE(src, "null source scan");
+    MH_REQUIRE(src != out, "`out` is among the sources");
+    MH_REQUIRE(src->ctx == out->ctx, "scans belong to different contexts");
+    MH_REQUIRE(params[k].timestamp_method >= MH_TS_NONE && params[k].timestamp_method <= MH_TS_EARLIEST_IS_ZERO, "bad timestamp_method");
+    if (!src->n) continue;
+    total += src->n;
+    MH_REQUIRE(total < 0x7FFFFFF0ull, "the sources hold 2^31 - 16 points or more");
+    n_live++;
+    n_with_t += src->t ? 1 : 0;
+    n_with_i += src->i ? 1 : 0;
+  }
+  MH_REQUIRE(n_with_t == 0 || n_with_t == n_live, "some sources carry time stamps and some do not");
+  MH_REQUIRE(n_with_i == 0 || n_with_i == n_live, "some sources carry an intensity and some do not");
+  const bool has_t = n_live && n_with_t == n_live, has_i = n_live && n_with_i == n_live;
+  mh_ctx* ctx = out->ctx;
+  MH_TRY(set_device(ctx));
+  hipStream_t s = ctx->stream;
+  MH_TRY(scan_alloc(out, total, has_t, false, has_i));
+  if (!total) return MH_OK;
+  MergeTable tab;
+  memset(&tab, 0, sizeof(tab));
+  uint32_t off = 0, max_adjusted = 0;
+  for (size_t k = 0; k < MH_MAX_MERGE_SOURCES; k++) {
+    tab.start[k] = off;
+    tab.mm[k][0] = 0xFFFFFFFFu;
+    if (k >= n_sources) continue;
+    const mh_scan* src = sources[k];
+    MergeSrc& m = tab.s[k];
+    m.x = src->x; m.y = src->y; m.z = src->z; m.t = src->t; m.i = src->i;
+    for (int c = 0; c < 12; c++) m.P[c] = params[k].sensor_pose[c];
+    m.n = (uint32_t)src->n;
+    m.method = (has_t && src->n) ? params[k].timestamp_method : MH_TS_NONE;
+    m.offset = params[k].time_offset;
+    if (m.method != MH_TS_NONE && m.n > max_adjusted) max_adjusted = m.n;
+    off += m.n;
+  }
+  tab.start[MH_MAX_MERGE_SOURCES] = off;
+  MH_TRY(ctx->build_e.reserve(sizeof(MergeTable)));
+  MergeTable* d_tab = ctx->build_e.as<MergeTable>();
+  MH_HIP(hipMemcpyAsync(d_tab, &tab, sizeof(tab), hipMemcpyHostToDevice, s));  // (pageable: staged before the call returns)
+  if (max_adjusted) {
+    const uint32_t g = nblk(max_adjusted, 256);
+    hipLaunchKernelGGL(k_merge_tminmax, dim3(g < 128u ? g : 128u, (uint32_t)n_sources), dim3(256), 0, s, d_tab);
+  }
+  hipLaunchKernelGGL(k_merge_fill, dim3(nblk(total, 256)), dim3(256), 0, s, d_tab, (uint32_t)total, (float*)out->x, (float*)out->y,
+                     (float*)out->z, (float*)out->t, (float*)out->i);
+  MH_HIP(hipGetLastError());
+  return MH_OK;
 }
 
 mh_status mh_scan_deskew(const mh_scan* in, const double twist[6], mh_scan* out) {

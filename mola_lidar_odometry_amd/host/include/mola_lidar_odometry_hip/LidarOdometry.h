@@ -4,6 +4,7 @@
 // all "file:line" relative to /root/reference) so that a whole sequence can run on a box without the MOLA stack,
 // configured by the reference's own pipeline file (pipelines/lidar3d-default.yaml / lidar3d-ndt.yaml):
 //
+//   [rigs] labelled observations -> sync window -> [device] sensor poses, per-sensor time offsets, merge   (:643-721)
 //   raw scan -> [device] time-stamp adjust, decimate, range / box filters, de-skew      (yaml:267-350; :730-741)
 //            -> constant-velocity guess                                                  (:808-811, 854-877)
 //            -> [device] ICP with the twist-re-estimation hook loop                      (:919-1007)
@@ -12,11 +13,12 @@
 //            -> key-frame decision, [device] local-map update                            (:1066-1118, 1160-1206)
 //
 // Host code here is control logic only; every point touches the GPU through include/molahip.h.  What is NOT here:
-// MOLA module plumbing, multi-LiDAR sync, IMU/GNSS/wheel inputs, simplemap generation, visualisation, ROS.
+// MOLA module plumbing, IMU/GNSS/wheel inputs, simplemap generation, visualisation, ROS.
 #pragma once
 #include <map>
 #include <memory>
 #include <optional>
+#include <regex>
 #include <string>
 #include <vector>
 
@@ -91,6 +93,32 @@ class SearchablePoseList {
   std::vector<CPose3D> poses_;
 };
 
+// The grouping rule of a multi-LiDAR rig (LidarOdometry.cpp:664-689, 702-713), host logic only: the latest observation of
+// every label waits until `lidar_count` labels are present; the group is then the waiting observations within
+// `max_time_offset` of the one that completed it, in byte-wise label order (the order of the reference's std::map), and the
+// waiting set is emptied.  The reference time is the stamp of the FIRST KEPT observation in that order, not the first to arrive.
+// lidar_count <= 1: every observation is a group of its own.
+class SensorSync {
+ public:
+  struct Group {
+    std::vector<std::string> labels;     // kept, in merge order
+    std::vector<double> stamps, dts;     // their time stamps; dts[k] = stamps[k] - stamps[0] (each source's SENSOR_TIME_OFFSET)
+    std::vector<std::string> discarded;  // waiting observations outside the window
+  };
+  explicit SensorSync(uint32_t lidar_count = 1, double max_time_offset = 25e-3) : lidar_count_(lidar_count), max_time_offset_(max_time_offset) {}
+  // a newer observation of a label replaces the one that waits
+  std::optional<Group> push(const std::string& label, double stamp);
+  void clear() { waiting_.clear(); }
+  std::vector<std::string> waiting() const;
+  uint32_t lidarCount() const { return lidar_count_; }
+  double maxTimeOffset() const { return max_time_offset_; }
+
+ private:
+  uint32_t lidar_count_;
+  double max_time_offset_;
+  std::map<std::string, double> waiting_;
+};
+
 class LidarOdometry {
  public:
   // the params: block of the pipeline file (yaml:6-122); formulas are re-evaluated every scan
@@ -110,6 +138,9 @@ class LidarOdometry {
     double initial_sigma = 0.5, min_motion = 0.1, maximum_sigma = 5.0, kp = 5.0, alpha = 0.99;
     bool validity_check_enabled = false;
     uint32_t validity_minimum_point_count = 1000;
+    uint32_t lidar_count = 1;        // multiple_lidars.lidar_count (reference LidarOdometry.h:152)
+    double max_time_offset = 25e-3;  // multiple_lidars.max_time_offset [s] (:156)
+    std::vector<std::string> lidar_sensor_labels;  // regular expressions, std::regex_match (:261-275, 576-577); empty: every label
     void load_from(const Config& c);
   };
 
@@ -133,6 +164,12 @@ class LidarOdometry {
     // All three describe the layers that were finally aligned and merged: after the last re-run of the 2nd pass that the twist
     // hook asked for (a 2nd pass that filters after its de-skew can change them; LidarOdometry.cpp:973-1004, 1158-1206).
     std::map<std::string, uint64_t> layer_sizes;
+    // labelled observations (onLidarFrom): `ignored` = the label matches none of lidar_sensor_labels; `waiting` = uploaded, the
+    // group is not complete yet (no trajectory entry, the pose unchanged).  n_sensors = sources merged into this scan (1 on the
+    // unlabelled entry points), sensor_labels = their labels in merge order; n_raw is the merged count.
+    bool waiting = false, ignored = false;
+    uint32_t n_sensors = 1;
+    std::vector<std::string> sensor_labels;
   };
 
   // ctx == nullptr: the process-wide default device context, taken at initialize()
@@ -156,6 +193,20 @@ class LidarOdometry {
   const ScanRecord& onLidarInterleaved(double timestamp, const void* data, size_t n, size_t point_step, size_t off_x,
                                        size_t off_y, size_t off_z, long long off_t = -1, const float* t = nullptr,
                                        long long off_i = -1);
+
+  // One observation of a labelled sensor of a rig (params.multiple_lidars, params.lidar_sensor_labels), the points in the
+  // SENSOR frame: `sensor_pose` is the sensor on the vehicle (12 doubles, row-major 3x4; null = identity).  Restates
+  // LidarOdometry.cpp:643-721 and :759-763 in their order: label filter -> minimum time between scans per label -> upload
+  // into a device layer kept per label (the caller's buffer is borrowed for the call only; page-locked input as
+  // setInputPinned says) -> first-call sensor-range estimate from this one observation in the vehicle frame -> wait until
+  // lidar_count labels are present (SensorSync) -> ONE mh_scan_merge_sensors of the kept observations into 'raw' (sensor poses,
+  // FilterAdjustTimestamps per source with SENSOR_TIME_OFFSET = its stamp minus the first kept one's) -> the rest of onLidar at
+  // the triggering observation's time stamp.  With lidar_count 1 it is the same flow with a group of one: a single LiDAR with a
+  // mounting pose.  On a rig (lidar_count > 1) onLidar, onLidarInterleaved and prefetch* throw; prefetch* also throws once a
+  // labelled observation has been received (no prefetch overlap for rigs).
+  const ScanRecord& onLidarFrom(const std::string& sensor_label, const double* sensor_pose, double timestamp, const void* data,
+                                size_t n, size_t point_step, size_t off_x, size_t off_y, size_t off_z, long long off_t = -1,
+                                const float* t = nullptr, long long off_i = -1);
 
   // One depth-image observation, for a pipeline whose observations_generator is a GeneratorEdgesFromRangeImage (rgbd.yaml):
   // `range` is row-major camera.rows x camera.cols, 0 = no return; `camera` holds the intrinsics, the range encoding and the
@@ -249,7 +300,9 @@ class LidarOdometry {
   void create_local_map();
   std::shared_ptr<HashedVoxelPointCloud> make_map(const Config& def, double* voxel_size, float* remove_far) const;
   void run_general_pass(int pass);
-  void run_generator(const RawInput& in);  // depth-image plans: the observations_generator step
+  void run_generator(const RawInput& in);
+  void merge_sensors(const std::vector<std::string>& labels, const std::vector<mh_merge_source>& srcs, DevicePointCloud& out);
+  void refuse_unlabelled(const char* what) const;  // rigs take onLidarFrom only  // depth-image plans: the observations_generator step
   void record_layer_sizes(ScanRecord& rec) const;  // general plans: layer_sizes, n_for_icp, n_for_map of the live layers
   uint64_t maps_total(bool voxels) const;
   void ensure_device();
@@ -284,6 +337,17 @@ class LidarOdometry {
   CPose3D last_lidar_pose_;
   bool last_icp_was_good_ = true;
   double last_icp_quality_ = 0;
+  // rigs: the waiting set, the device layer and mounting pose of every label, the per-label times of the drop test (:647-650, 763)
+  SensorSync sync_;
+  struct SensorSlot {
+    std::shared_ptr<DevicePointCloud> cloud;
+    double pose[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  };
+  std::map<std::string, SensorSlot> sensors_;
+  std::shared_ptr<DevicePointCloud> range_probe_;  // the first observation in the vehicle frame, for the range estimate
+  std::map<std::string, double> last_obs_tim_by_label_;
+  std::vector<std::regex> label_patterns_;  // params_.lidar_sensor_labels, compiled once
+  bool labelled_seen_ = false, merged_input_ = false;
   std::optional<double> last_obs_tim_, last_icp_timestamp_, first_ever_timestamp_, last_obs_timestamp_;
   std::optional<NavStateFuse::NavState> last_motion_model_output_;
   double adapt_thres_sigma_ = 0;

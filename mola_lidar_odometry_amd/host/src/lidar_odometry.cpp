@@ -217,6 +217,52 @@ void LidarOdometry::Params::load_from(const Config& c) {
     flag(v, "enabled", validity_check_enabled);
     if (v.has("minimum_point_count")) validity_minimum_point_count = (uint32_t)to_double(v["minimum_point_count"].asString());
   }
+  if (c.has("multiple_lidars")) {
+    const Config& m = c["multiple_lidars"];
+    if (m.has("lidar_count")) lidar_count = (uint32_t)to_double(m["lidar_count"].asString());
+    num(m, "max_time_offset", max_time_offset);
+  }
+  // a scalar or a sequence of regular expressions (:261-275).  The reference insists on the key; the pipeline files of this
+  // driver have lived without it, so here its absence means "every label".
+  lidar_sensor_labels.clear();
+  if (c.has("lidar_sensor_labels")) {
+    const Config& l = c["lidar_sensor_labels"];
+    if (l.kind == Config::Kind::Seq)
+      for (size_t i = 0; i < l.size(); i++) lidar_sensor_labels.push_back(l.at(i).asString());
+    else if (!l.isNull())
+      lidar_sensor_labels.push_back(l.asString());
+  }
+}
+
+// ================================================================== rigs: the grouping rule
+std::optional<SensorSync::Group> SensorSync::push(const std::string& label, double stamp) {
+  if (lidar_count_ <= 1) {  // single LiDAR (:686-689): no waiting set, no window
+    Group g;
+    g.labels = {label};
+    g.stamps = {stamp};
+    g.dts = {0.0};
+    return g;
+  }
+  waiting_[label] = stamp;  // (:668)
+  if (waiting_.size() < lidar_count_) return std::nullopt;
+  Group g;
+  for (const auto& [l, t] : waiting_) {  // label order (:674-679)
+    if (std::abs(t - stamp) > max_time_offset_) {
+      g.discarded.push_back(l);
+      continue;
+    }
+    g.labels.push_back(l);
+    g.stamps.push_back(t);
+    g.dts.push_back(t - g.stamps.front());  // relative to the first KEPT observation in label order (:702, 711)
+  }
+  waiting_.clear();  // (:681)
+  return g;
+}
+
+std::vector<std::string> SensorSync::waiting() const {
+  std::vector<std::string> l;
+  for (const auto& kv : waiting_) l.push_back(kv.first);
+  return l;
 }
 
 // The observation filter chain the device implements, recognised from the pipeline file:
@@ -607,6 +653,9 @@ struct LidarOdometry::RawInput {
   long long off_i = -1;  // float32 intensity inside the record, or -1
   const uint16_t* depth = nullptr;  // ... or a range image of cam.rows x cam.cols (onDepthImage; n = its pixel count)
   mh_range_image_params cam{};
+  // ... or the merged cloud of a rig's group, already in raw_ (onLidarFrom): its labels in merge order, the one that completed it
+  const std::vector<std::string>* merged_labels = nullptr;
+  const std::string* trigger_label = nullptr;
   bool same(const RawInput& o) const {
     return depth == o.depth && cam.rows == o.cam.rows && cam.cols == o.cam.cols && n == o.n && x == o.x && y == o.y && z == o.z && t == o.t && data == o.data && point_step == o.point_step &&
            off_x == o.off_x && off_y == o.off_y && off_z == o.off_z && off_t == o.off_t && off_i == o.off_i;
@@ -708,6 +757,22 @@ void LidarOdometry::initialize(const Config& cfg) {
     gplan_->attachToParameterSource(source_);
   }
 
+  if (params_.lidar_count < 1 || params_.lidar_count > MH_MAX_MERGE_SOURCES)
+    throw std::runtime_error("LidarOdometry (HIP): params.multiple_lidars.lidar_count is " + std::to_string(params_.lidar_count) +
+                             "; the device merges 1.." + std::to_string(MH_MAX_MERGE_SOURCES) + " sensors (MH_MAX_MERGE_SOURCES)");
+  if (params_.lidar_count > 1 && gplan_ && gplan_->depth_input)
+    throw std::runtime_error("LidarOdometry (HIP): params.multiple_lidars.lidar_count > 1 on a depth-image pipeline: rigs of depth "
+                             "cameras are not implemented (one camera carries its pose in onDepthImage)");
+  sync_ = SensorSync(params_.lidar_count, params_.max_time_offset);
+  label_patterns_.clear();
+  for (const auto& re : params_.lidar_sensor_labels) {
+    try {
+      label_patterns_.emplace_back(re);
+    } catch (const std::regex_error& e) {
+      throw std::runtime_error("LidarOdometry (HIP): params.lidar_sensor_labels: '" + re + "' is not a regular expression: " + e.what());
+    }
+  }
+
   // ICP pipelines (:340-358)
   auto t0 = icp_pipeline_from_yaml(cfg["icp_settings_with_vel"], ctx_);
   icp_[0] = std::get<0>(t0);
@@ -762,7 +827,7 @@ void LidarOdometry::resolve_map_counts() const {
     map_voxels_cached_ = local_map_ ? local_map_->voxelCount() : 0;
   }
   for (size_t i = map_counts_from_; i < records_.size(); i++) {
-    if (records_[i].dropped) continue;  // (those returned before the map was looked at)
+    if (records_[i].dropped || records_[i].waiting || records_[i].ignored) continue;  // (those returned before the map was looked at)
     records_[i].n_map_points = map_points_cached_;
     records_[i].n_map_voxels = map_voxels_cached_;
   }
@@ -795,6 +860,9 @@ void LidarOdometry::reset() {
   last_icp_was_good_ = true;
   last_icp_quality_ = 0;
   last_obs_tim_.reset();
+  sync_.clear();
+  last_obs_tim_by_label_.clear();
+  labelled_seen_ = merged_input_ = false;
   last_icp_timestamp_.reset();
   first_ever_timestamp_.reset();
   last_obs_timestamp_.reset();
@@ -876,7 +944,8 @@ void LidarOdometry::run_general_pass(int pass) {
   };
   if (pass == 1) {
     g.raw_adjusted.reset();
-    if (g.timestamp_method != MH_TS_NONE) {  // observations_filter_adjust_timestamps over all raw points
+    // observations_filter_adjust_timestamps over all raw points (a rig's merged cloud: done per sensor by the merge)
+    if (g.timestamp_method != MH_TS_NONE && !merged_input_) {
       const double zero[3] = {0, 0, 0};
       const mh_preprocess_params pp = make_pp(0, 0, 0, 0, 0, MH_BBOX_OFF, zero, zero, g.timestamp_method, g.time_offset);
       auto out = layer(kAdjustedRawKey);
@@ -953,7 +1022,8 @@ void LidarOdometry::run_first_pass() {
   if (gplan_) return run_general_pass(1);
   const FilterPlan& f = *plan_;
   const mh_preprocess_params pp = make_pp(f.decim_map_res, f.decim_icp_res, f.min_points_to_filter, f.range_min, f.range_max,
-                                          f.bbox_mode, f.bbox_min, f.bbox_max, f.timestamp_method, f.time_offset, f.decim_map_method, f.decim_icp_method);
+                                          f.bbox_mode, f.bbox_min, f.bbox_max, merged_input_ ? (int32_t)MH_TS_NONE : f.timestamp_method,
+                                          f.time_offset, f.decim_map_method, f.decim_icp_method);  // (a rig's merged cloud: adjusted per sensor)
   // (not through the batcher even when there is one: its filter sets are made of the PREFETCH requests, one action per
   // alignment and participant -- this call is the first scan of a sequence, or a prepared scan that has to be redone)
   check(mh_scan_preprocess(raw_->handle(), &pp, map_skewed_->handle(), icp_skewed_->handle()), "mh_scan_preprocess");
@@ -973,7 +1043,15 @@ void LidarOdometry::setAlignBatcher(std::shared_ptr<mp2p_icp_hip::AlignBatcher> 
 }
 
 // ---- the announced next observation: upload + first pass on a second stream while this scan is in its ICP loop
+void LidarOdometry::refuse_unlabelled(const char* what) const {
+  if (params_.lidar_count > 1)
+    throw std::runtime_error(std::string("LidarOdometry (HIP): ") + what + " on a rig (params.multiple_lidars.lidar_count = " +
+                             std::to_string(params_.lidar_count) + "): its observations carry a sensor label, use onLidarFrom");
+}
+
 void LidarOdometry::prefetch(const float* x, const float* y, const float* z, const float* t, size_t n) {
+  refuse_unlabelled("prefetch");
+  if (labelled_seen_) throw std::runtime_error("LidarOdometry (HIP): prefetch after a labelled observation (onLidarFrom): prefetch overlap for rigs is not implemented");
   pf_->req = RawInput();  // (a prepared scan that is still waiting to be picked up stays untouched)
   pf_->req.n = n; pf_->req.x = x; pf_->req.y = y; pf_->req.z = z; pf_->req.t = t;
   pf_->requested = n > 0;
@@ -981,6 +1059,8 @@ void LidarOdometry::prefetch(const float* x, const float* y, const float* z, con
 
 void LidarOdometry::prefetchInterleaved(const void* data, size_t n, size_t point_step, size_t off_x, size_t off_y,
                                         size_t off_z, long long off_t, const float* t, long long off_i) {
+  refuse_unlabelled("prefetchInterleaved");
+  if (labelled_seen_) throw std::runtime_error("LidarOdometry (HIP): prefetchInterleaved after a labelled observation (onLidarFrom): prefetch overlap for rigs is not implemented");
   pf_->req = RawInput();
   pf_->req.n = n; pf_->req.data = data; pf_->req.point_step = point_step; pf_->req.off_x = off_x; pf_->req.off_y = off_y;
   pf_->req.off_z = off_z; pf_->req.off_t = off_t; pf_->req.t = t; pf_->req.off_i = off_i;
@@ -1146,6 +1226,7 @@ std::shared_ptr<HashedVoxelPointCloud> LidarOdometry::make_map(const Config& def
 
 const LidarOdometry::ScanRecord& LidarOdometry::onLidar(double this_obs_tim, const float* x, const float* y, const float* z,
                                                         const float* t, size_t n) {
+  refuse_unlabelled("onLidar");
   RawInput in;
   in.n = n; in.x = x; in.y = y; in.z = z; in.t = t;
   return process(this_obs_tim, in);
@@ -1154,9 +1235,112 @@ const LidarOdometry::ScanRecord& LidarOdometry::onLidar(double this_obs_tim, con
 const LidarOdometry::ScanRecord& LidarOdometry::onLidarInterleaved(double this_obs_tim, const void* data, size_t n,
                                                                    size_t point_step, size_t off_x, size_t off_y,
                                                                    size_t off_z, long long off_t, const float* t, long long off_i) {
+  refuse_unlabelled("onLidarInterleaved");
   RawInput in;
   in.n = n; in.data = data; in.point_step = point_step; in.off_x = off_x; in.off_y = off_y; in.off_z = off_z;
   in.off_t = off_t; in.t = t; in.off_i = off_i;
+  return process(this_obs_tim, in);
+}
+
+void LidarOdometry::merge_sensors(const std::vector<std::string>& labels, const std::vector<mh_merge_source>& srcs, DevicePointCloud& out) {
+  const mh_scan* scans[MH_MAX_MERGE_SOURCES];
+  for (size_t k = 0; k < labels.size(); k++) scans[k] = sensors_.at(labels[k]).cloud->handle();
+  check(mh_scan_merge_sensors(labels.size(), scans, srcs.data(), out.handle()), "mh_scan_merge_sensors");
+}
+
+const LidarOdometry::ScanRecord& LidarOdometry::onLidarFrom(const std::string& label, const double* sensor_pose, double this_obs_tim,
+                                                            const void* data, size_t n, size_t point_step, size_t off_x,
+                                                            size_t off_y, size_t off_z, long long off_t, const float* t,
+                                                            long long off_i) {
+  if (!plan_ && !gplan_) throw std::runtime_error("LidarOdometry::onLidarFrom called before initialize()");
+  if (gplan_ && gplan_->depth_input)
+    throw std::runtime_error("LidarOdometry (HIP): this pipeline's observations_generator is a GeneratorEdgesFromRangeImage: it "
+                             "takes depth images (onDepthImage), not point clouds");
+  const bool with_i = gplan_ && gplan_->reads_intensity;
+  if (with_i && off_i < 0)
+    throw std::runtime_error("LidarOdometry (HIP): the pipeline's intensity filters need a per-point intensity, and this scan "
+                             "carries none (onLidarFrom with off_i >= 0)");
+  auto side_record = [&]() -> ScanRecord& {  // a record of an observation that does not become a scan
+    records_.emplace_back();
+    ScanRecord& r = records_.back();
+    r.timestamp = this_obs_tim;
+    r.n_raw = n;
+    r.pose = last_lidar_pose_;
+    r.n_sensors = 0;
+    r.sensor_labels = {label};
+    return r;
+  };
+  // 1. is it a LiDAR of ours? (:576-577)
+  if (!label_patterns_.empty()) {
+    bool ours = false;
+    for (const auto& re : label_patterns_) ours = ours || std::regex_match(label, re);
+    if (!ours) {
+      ScanRecord& r = side_record();
+      r.ignored = true;
+      return r;
+    }
+  }
+  // 2. observations of one label too close in time (:644-657).  NOTE the reference records the time under the label of the
+  // observation that COMPLETES a group only, and only after the validity check (:763): a sensor whose observations always
+  // wait is never dropped by this test.  Kept (process() writes last_obs_tim_by_label_ for the triggering label).
+  if (auto it = last_obs_tim_by_label_.find(label); it != last_obs_tim_by_label_.end() && (this_obs_tim - it->second) < params_.min_time_between_scans) {
+    ScanRecord& r = side_record();
+    r.dropped = true;
+    return r;
+  }
+  if (!labelled_seen_) cancel_prefetch();  // (an announced unlabelled scan: from here on the driver is fed by label)
+  labelled_seen_ = true;
+  ensure_device();
+  // 3. the observation goes to the device at once, in its sensor frame, stamps untouched; a newer one replaces a waiting one
+  SensorSlot& slot = sensors_[label];
+  {
+    StageTimer tt(profile_, "onLidar.0.upload_raw");
+    if (!slot.cloud) slot.cloud = std::make_shared<DevicePointCloud>(ctx_);
+    slot.cloud->setPointsInterleaved(data, n, point_step, off_x, off_y, off_z, off_t, input_pinned_, with_i ? off_i : -1);
+    if (t) slot.cloud->setTimestamps(t, n);
+    for (int c = 0; c < 12; c++) slot.pose[c] = sensor_pose ? sensor_pose[c] : (c % 5 == 0 ? 1.0 : 0.0);
+  }
+  auto source_of = [&](const std::string& l, int32_t method, double offset) {
+    mh_merge_source m;
+    memset(&m, 0, sizeof(m));
+    for (int c = 0; c < 12; c++) m.sensor_pose[c] = sensors_.at(l).pose[c];
+    m.timestamp_method = method;
+    m.time_offset = (float)offset;
+    return m;
+  };
+  // 4. first call: the sensor range from this one observation in the vehicle frame (:662, 1487-1513), even if it then waits
+  if (!estimated_sensor_max_range_ && n) {
+    if (!range_probe_) range_probe_ = std::make_shared<DevicePointCloud>(ctx_);
+    merge_sensors({label}, {source_of(label, MH_TS_NONE, 0)}, *range_probe_);
+    float mn[3], mx[3];
+    range_probe_->boundingBox(mn, mx);
+    estimated_sensor_max_range_ = std::max(bbox_radius(mn, mx), params_.absolute_minimum_sensor_range);
+    updatePipelineDynamicVariables();  // (the estimate is published now, as the next observation's :692 would)
+  }
+  // 5. / 6. the group (:664-689)
+  const std::optional<SensorSync::Group> group = sync_.push(label, this_obs_tim);
+  if (!group) {
+    ScanRecord& r = side_record();
+    r.waiting = true;
+    return r;
+  }
+  // 7. one merge into 'raw': sensor poses, and FilterAdjustTimestamps per source with ITS SENSOR_TIME_OFFSET (:692, 704-721)
+  updatePipelineDynamicVariables();
+  const int32_t method = plan_ ? plan_->timestamp_method : gplan_->timestamp_method;
+  std::vector<mh_merge_source> srcs;
+  for (size_t k = 0; k < group->labels.size(); k++) {
+    source_.updateVariable("SENSOR_TIME_OFFSET", group->dts[k]);  // (keeps the last source's value afterwards, :713)
+    source_.realize();
+    srcs.push_back(source_of(group->labels[k], method, plan_ ? plan_->time_offset : gplan_->time_offset));
+  }
+  {
+    StageTimer tt(profile_, "onLidar.0.merge_sensors");
+    merge_sensors(group->labels, srcs, *raw_);
+  }
+  RawInput in;
+  in.n = raw_->size();
+  in.merged_labels = &group->labels;
+  in.trigger_label = &label;
   return process(this_obs_tim, in);
 }
 
@@ -1212,9 +1396,11 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   if (!in.depth && gplan_ && gplan_->depth_input)
     throw std::runtime_error("LidarOdometry (HIP): this pipeline's observations_generator is a GeneratorEdgesFromRangeImage: it "
                              "takes depth images (onDepthImage), not point clouds");
+  const bool merged = in.merged_labels != nullptr;  // a rig's group: 'raw' is on the device already, adjusted per sensor
+  merged_input_ = merged;
   // 'raw' carries the intensity only when a filter reads it: otherwise the field is ignored (same records as without it)
   const bool with_i = gplan_ && gplan_->reads_intensity;
-  if (with_i && !(in.data && in.off_i >= 0))
+  if (with_i && !merged && !(in.data && in.off_i >= 0))
     throw std::runtime_error("LidarOdometry (HIP): the pipeline's intensity filters need a per-point intensity, and this scan "
                              "carries none (onLidarInterleaved with off_i >= 0)");
   const long long off_i = with_i ? in.off_i : -1;
@@ -1223,9 +1409,13 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   rec.timestamp = this_obs_tim;
   rec.n_raw = n;
   rec.pose = last_lidar_pose_;
+  if (merged) {
+    rec.n_sensors = (uint32_t)in.merged_labels->size();
+    rec.sensor_labels = *in.merged_labels;
+  }
 
-  // drop scans too close in time (:644-657)
-  if (last_obs_tim_ && (this_obs_tim - *last_obs_tim_) < params_.min_time_between_scans) {
+  // drop scans too close in time (:644-657; labelled observations: per label, in onLidarFrom)
+  if (!merged && last_obs_tim_ && (this_obs_tim - *last_obs_tim_) < params_.min_time_between_scans) {
     rec.dropped = true;
     return rec;
   }
@@ -1243,7 +1433,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     if (ok && pf_->in.same(in)) prepared = true;
   }
   if (pf_->requested && pf_->req.same(in)) pf_->requested = false;  // due before it could be launched
-  if (!prepared) {
+  if (!prepared && !merged) {
     StageTimer tt(profile_, "onLidar.0.upload_raw");
     if (in.depth) run_generator(in);
     else if (in.data) raw_->setPointsInterleaved(in.data, n, in.point_step, in.off_x, in.off_y, in.off_z, in.off_t, input_pinned_, off_i);
@@ -1318,7 +1508,8 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     rec.dropped = true;
     return rec;
   }
-  last_obs_tim_ = this_obs_tim;
+  if (merged) last_obs_tim_by_label_[*in.trigger_label] = this_obs_tim;  // (:763: the label that completed the group only)
+  else last_obs_tim_ = this_obs_tim;
   last_obs_timestamp_ = this_obs_tim;
   if (!first_ever_timestamp_) first_ever_timestamp_ = this_obs_tim;
   if (n == 0) {  // :769-775
@@ -1618,6 +1809,14 @@ LidarOdometry::VoxelMapDump LidarOdometry::downloadVoxelMap(const std::string& n
 std::map<std::string, std::string> LidarOdometry::describePipeline() const {
   std::map<std::string, std::string> d;
   d["intensity_input"] = intensity_input_ ? "true" : "false";
+  {
+    char buf[96];
+    snprintf(buf, sizeof(buf), "lidar_count %u max_time_offset %g", params_.lidar_count, params_.max_time_offset);
+    d["multiple_lidars"] = buf;
+    std::string labels;
+    for (const auto& re : params_.lidar_sensor_labels) labels += (labels.empty() ? "" : " | ") + re;
+    d["lidar_sensor_labels"] = params_.lidar_sensor_labels.empty() ? "(any)" : labels;
+  }
   if (gplan_) {
     const GeneralPlan& g = *gplan_;
     d["plan"] = "general";

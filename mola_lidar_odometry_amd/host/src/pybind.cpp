@@ -190,6 +190,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["decim_map_resolution"] = r.decim_map_resolution; d["decim_icp_resolution"] = r.decim_icp_resolution;
     d["map_voxel_size"] = r.map_voxel_size;
     d["layer_sizes"] = r.layer_sizes;
+    d["waiting"] = r.waiting; d["ignored"] = r.ignored; d["n_sensors"] = r.n_sensors; d["sensor_labels"] = r.sensor_labels;
     return d;
   };
   py::class_<LidarOdometry> lo_class(m, "LidarOdometry", py::dynamic_attr());
@@ -229,6 +230,34 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         return rec2dict(lo.records().back()); },  // (records(): the map counters of this record, read back now)
            py::arg("timestamp"), py::arg("xyz"), py::arg("t") = std::nullopt,
            py::arg("xyz_fields") = std::array<int, 3>{0, 1, 2}, py::arg("t_field") = -1, py::arg("i_field") = -1)
+      .def("onLidarFrom", [rec2dict](LidarOdometry& lo, const std::string& label, double stamp,
+                                     py::array_t<float, py::array::c_style | py::array::forcecast> xyz,
+                                     std::optional<py::array_t<float, py::array::c_style | py::array::forcecast>> t,
+                                     std::array<int, 3> xyz_fields, int t_field, int i_field, std::optional<std::vector<double>> sensor_pose) {
+        // one observation of a labelled sensor of a rig, points in the SENSOR frame (arguments as onLidar's); sensor_pose: 12
+        // values, row-major 3x4, the sensor on the vehicle (default: identity)
+        if (xyz.ndim() != 2 || xyz.shape(1) < 3) throw std::runtime_error("xyz must be [n,3] (or [n,k>=3] records)");
+        const size_t n = (size_t)xyz.shape(0), k = (size_t)xyz.shape(1);
+        for (int f : xyz_fields)
+          if (f < 0 || (size_t)f >= k) throw std::runtime_error("xyz_fields out of range");
+        if (t_field >= (int)k) throw std::runtime_error("t_field out of range");
+        if (i_field >= (int)k) throw std::runtime_error("i_field out of range");
+        if (sensor_pose && sensor_pose->size() != 12) throw std::runtime_error("sensor_pose must hold 12 values (row-major 3x4)");
+        const float* tp = nullptr;
+        if (t) {
+          if ((size_t)t->size() != n) throw std::runtime_error("t must have n entries");
+          tp = t->data();
+        }
+        {
+          py::gil_scoped_release nogil;
+          (void)lo.onLidarFrom(label, sensor_pose ? sensor_pose->data() : nullptr, stamp, xyz.data(), n, k * sizeof(float),
+                               4u * (size_t)xyz_fields[0], 4u * (size_t)xyz_fields[1], 4u * (size_t)xyz_fields[2],
+                               t_field >= 0 ? 4ll * t_field : -1ll, tp, i_field >= 0 ? 4ll * i_field : -1ll);
+        }
+        return rec2dict(lo.records().back()); },
+           py::arg("label"), py::arg("timestamp"), py::arg("xyz"), py::arg("t") = std::nullopt,
+           py::arg("xyz_fields") = std::array<int, 3>{0, 1, 2}, py::arg("t_field") = -1, py::arg("i_field") = -1,
+           py::arg("sensor_pose") = std::nullopt)
       .def("onDepthImage", [rec2dict](LidarOdometry& lo, double stamp, py::array range, double fx, double fy, double cx, double cy,
                                       double range_units, bool range_is_depth, std::optional<std::vector<double>> sensor_pose) {
         // [rows, cols] uint16 range image, 0 = no return; read through its pointer: a C-contiguous uint16 array only (anything
@@ -344,6 +373,15 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["logodds"] = py::array_t<int32_t>(n, v.logodds.data());
     d["search_voxel_size"] = v.search_voxel_size;
     return d; });
+  // the grouping rule of a rig on its own (host logic only: testable without a device; the driver holds one)
+  py::class_<mola_hip::SensorSync>(m, "SensorSync")
+      .def(py::init<uint32_t, double>(), py::arg("lidar_count") = 1, py::arg("max_time_offset") = 25e-3)
+      .def("push", [](mola_hip::SensorSync& s, const std::string& label, double stamp) -> py::object {
+        const auto g = s.push(label, stamp);
+        if (!g) return py::none();
+        return py::make_tuple(g->labels, g->dts, g->discarded); })
+      .def("waiting", &mola_hip::SensorSync::waiting)
+      .def("clear", &mola_hip::SensorSync::clear);
   py::class_<AlignBatcher, std::shared_ptr<AlignBatcher>>(m, "AlignBatcher")
       .def(py::init<size_t>(), py::arg("participants"))
       .def("leave", [](AlignBatcher& b) { b.leave(); }, py::call_guard<py::gil_scoped_release>())
