@@ -202,6 +202,26 @@ MH_API mh_status mh_map_download(const mh_map* map, float* x, float* y, float* z
  * NULL): centroid, unit normal (largest component positive) and the plane flag.  Zeros when NDT is off. */
 MH_API mh_status mh_map_download_ndt(const mh_map* map, float* cx, float* cy, float* cz, float* nx, float* ny, float* nz,
                                      uint32_t* is_plane);
+/* Snapshot restore: the inverse of mh_map_download.  The input is exactly what mh_map_download returns -- n points voxel by
+ * voxel, voxels in ascending packed key (kx, ky, kz), in-voxel insertion order, with the source index of every point -- plus
+ * mh_map_info::n_offered; arrays live in `mem` (MH_MEM_HOST or MH_MEM_DEVICE).  Whatever the map held before is replaced.
+ *  - Afterwards the map is indistinguishable from the one that was downloaded: the same mh_map_download and
+ *    mh_map_download_ndt bits (the NDT statistics are recomputed from the stored points, as every rebuild does), the same
+ *    n_points / n_offered / n_voxels / n_planes and bounding box in mh_map_get_info (table_size is an implementation matter: it
+ *    follows the history of a map and no query depends on it), the same answers from every search route, and the same result
+ *    of a following mh_map_insert: its source indices continue from n_offered, its cap and clearance rule see the restored
+ *    points as stored ones.
+ *  - Restore stores exactly the points given: it applies no cap and no min_distance_between_points decision of its own.
+ *  - MH_ERR_INVALID_ARGUMENT, and the map is left EMPTY (n_offered 0), when the input could not have been a download of a map
+ *    with these mh_map_params: voxel keys not non-decreasing in input order under the map's voxel size and index mode; a voxel
+ *    holding more than max_points_per_voxel points (when that is > 0); a non-finite point or one outside the key range
+ *    (|coord| / voxel_size >= 1e6); n_offered < n.  The checks are one device pass over the keys (an adjacent-key compare into
+ *    the build's flag word), not a host loop.  (A NULL map, a bad `mem`, NULL arrays with n > 0, n or n_offered beyond what
+ *    32-bit source indices can number: MH_ERR_INVALID_ARGUMENT too, and the map is not touched.)
+ *  - n == 0: an empty map that keeps n_offered (arrays may be NULL).
+ *  - Like mh_map_build the call is synchronous about its verdict and leaves nothing in flight. */
+MH_API mh_status mh_map_restore(mh_map* map, const float* x, const float* y, const float* z, const uint32_t* src_idx, size_t n,
+                                uint64_t n_offered, int32_t mem);
 
 /* ------------------------------------------------------------------------------------------------
  * Scan: the local point layer handed to align() ("decimated_for_icp", lidar3d-default.yaml:204),
@@ -486,6 +506,35 @@ typedef struct {
 } mh_radius_info;
 MH_API mh_status mh_nn_search_radius(const mh_map* map, const mh_scan* scan, const double T[12], double radius, uint32_t flags,
                                      const mh_radius_out* out, int32_t mem, mh_radius_info* info);
+
+/* Pose-candidate scoring: how well does one scan fit one map under each of MANY candidate poses -- the data-parallel core of a
+ * relocalization (a grid of starts around a coarse pose, scored before the best few are refined by ICP).  One launch scores
+ * every candidate; everything is exact, there are no tolerances.
+ *  - Per candidate c (poses + 12 * c: row-major 3x4, fp64, HOST memory) and scan point l: p' = (float)(R_c*l + t_c) exactly as
+ *    in every other search; the neighbour is mh_nn_search_dense's answer, the first minimum over the 27-voxel block.
+ *  - Acceptance is mh_nn_search's own test: thr2 = (float)(threshold * threshold), ang = threshold_angular_deg * pi / 180,
+ *    ang2 = (float)(ang * ang) (both squares in fp64); accepted iff a neighbour was found and d2 < thr2 + ang2 * |p'|^2, with
+ *    |p'|^2 = (px*px + py*py) + pz*pz, all in fp32, un-fused.
+ *  - n_paired = the number of accepted points.  cost = the sum over the accepted points of
+ *    q = (d2 * qscale >= 16777215.0f) ? 0xFFFFFF : (uint32_t)(d2 * qscale),  qscale = (float)(1048576.0 / (double)thr2):
+ *    one fp32 multiply, truncation -- a quantised squared residual in units of thr2 / 2^20.  An integer sum does not depend on
+ *    the order of summation, so scores are bit-identical from run to run and between any two implementations (which an fp64
+ *    sum of d2 would not be).
+ *  - A non-finite p', or one with |p' / voxel_size| >= 1e6 on any axis, pairs with nothing.  On an NDT map the statistics
+ *    records are never neighbours.  Both index modes.
+ *  - `scores` holds n_poses entries in `mem` (MH_MEM_HOST or MH_MEM_DEVICE); reserved_ is 0.  The call orders itself behind a
+ *    queued mh_map_insert and blocks until the scores are in `mem`.  n_poses == 0 or an empty scan: MH_OK, zeroed scores.
+ *  - Refusals, all decided before anything is queued: MH_ERR_INVALID_ARGUMENT for a NULL map, scan or scores, NULL poses with
+ *    n_poses > 0, a bad `mem`, map and scan on different devices, any non-finite pose entry, a threshold that is not finite or
+ *    outside [1e-3, 1e3] m, a negative or non-finite angular threshold; MH_ERR_UNSUPPORTED for n_poses > MH_SCORE_MAX_POSES. */
+#define MH_SCORE_MAX_POSES 1048576
+typedef struct {
+  uint32_t n_paired;
+  uint32_t reserved_;
+  uint64_t cost;
+} mh_pose_score; /* 16 bytes */
+MH_API mh_status mh_score_poses(const mh_map* map, const mh_scan* scan, const double* poses, size_t n_poses, double threshold,
+                                double threshold_angular_deg, mh_pose_score* scores, int32_t mem);
 
 /* Replaces mp2p_icp::Matcher_Point2Plane::implMatchOneLayer [U] on a mola::NDT [U] map (lidar3d-ndt.yaml:195-200,
  * 236-254).  The upstream semantics are unverified (SURVEY App.B U10); implemented default: among

@@ -83,6 +83,15 @@ class RadiusInfo(C.Structure):
     _fields_ = [("n_results", C.c_uint64), ("n_written", C.c_uint64), ("max_per_query", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class PoseScore(C.Structure):
+    """mh_pose_score: accepted points of one candidate pose and the sum of their quantised squared residuals (mh_score_poses)."""
+    _fields_ = [("n_paired", C.c_uint32), ("reserved_", C.c_uint32), ("cost", C.c_uint64)]
+
+
+POSE_SCORE_DTYPE = np.dtype([("n_paired", np.uint32), ("reserved_", np.uint32), ("cost", np.uint64)])
+SCORE_MAX_POSES = 1 << 20                            # MH_SCORE_MAX_POSES
+
+
 class PairsPt2Pt(C.Structure):
     _fields_ = [("lx", _FP), ("ly", _FP), ("lz", _FP), ("gx", _FP), ("gy", _FP), ("gz", _FP), ("n", C.c_size_t)]
 
@@ -256,6 +265,7 @@ _SIGNATURES = {
     "mh_map_get_info": (C.c_int32, [C.c_void_p, C.POINTER(MapInfo)]),
     "mh_map_download": (C.c_int32, [C.c_void_p, _FP, _FP, _FP, _UP, C.POINTER(C.c_int32), _UP, _UP]),
     "mh_map_download_ndt": (C.c_int32, [C.c_void_p, _FP, _FP, _FP, _FP, _FP, _FP, _UP]),
+    "mh_map_restore": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_int32]),
     "mh_scan_create": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
                                    C.POINTER(C.c_void_p)]),
     "mh_scan_update": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
@@ -291,6 +301,7 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_int32]),
     "mh_nn_search_radius": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_double, C.c_uint32, C.POINTER(RadiusOut), C.c_int32,
                                         C.POINTER(RadiusInfo)]),
+    "mh_score_poses": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_int32]),
     "mh_nn_search_pt2pl": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_double, C.c_uint32, C.POINTER(PairsPlOut), C.c_int32,
                                        C.POINTER(MatchInfo)]),
     "mh_nn_search_pt2pl_knn": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.POINTER(Pt2PlKnnParams), C.POINTER(PairsPlOut), C.c_int32,
@@ -519,6 +530,21 @@ class Map:
                                    first.ctypes.data_as(_UP), count.ctypes.data_as(_UP)))
         return dict(xyz=np.stack([x[:n], y[:n], z[:n]], 1), src_idx=src[:n], vox_keys=keys[:v], vox_first=first[:v],
                     vox_count=count[:v])
+
+    def restore(self, xyz, src_idx, n_offered):
+        """Bring back what download() returned (plus info().n_offered): mh_map_restore.  The map is afterwards indistinguishable
+        from the one that was downloaded; an input that no download could have produced raises and leaves the map empty."""
+        x, y, z = _soa(xyz)
+        src = np.ascontiguousarray(src_idx, dtype=np.uint32)
+        if len(src) != len(x):
+            raise ValueError("src_idx must hold one entry per point")
+        _chk(lib().mh_map_restore(self._h, _vp(x), _vp(y), _vp(z), _vp(src), len(x), int(n_offered), MEM_HOST))
+        return self
+
+    def restore_device(self, x_ptr, y_ptr, z_ptr, src_ptr, n, n_offered):
+        _chk(lib().mh_map_restore(self._h, C.c_void_p(x_ptr), C.c_void_p(y_ptr), C.c_void_p(z_ptr), C.c_void_p(src_ptr), n,
+                                  int(n_offered), MEM_DEVICE))
+        return self
 
     def download_ndt(self):
         v = int(self.info().n_voxels)
@@ -857,6 +883,19 @@ def nn_search_radius(m: Map, s: Scan, T, radius, sorted=False):
                                        C.byref(info)))
         assert int(info.n_written) == k
     return off, gi[:k], np.stack([gx[:k], gy[:k], gz[:k]], 1), d2[:k]
+
+
+def score_poses(m: Map, s: Scan, poses, threshold, threshold_angular_deg=0.0):
+    """Score one scan against one map under every candidate pose (mh_score_poses).  poses: [k, 12] (or [k, 3, 4] / [k, 4, 4]),
+    fp64.  Returns a structured array of k entries with the fields n_paired (uint32) and cost (uint64)."""
+    P = np.asarray(poses, dtype=np.float64)
+    if P.ndim == 3:
+        P = P[:, :3, :]
+    P = np.ascontiguousarray(P.reshape(-1, 12))
+    out = np.zeros(max(len(P), 1), POSE_SCORE_DTYPE)
+    _chk(lib().mh_score_poses(m._h, s._h, P.ctypes.data_as(_DP), len(P), float(threshold), float(threshold_angular_deg),
+                              _vp(out), MEM_HOST))
+    return out[:len(P)]
 
 
 @dataclass

@@ -321,7 +321,8 @@ inline void scan_free_tiles(mh_scan*) {}
 // Asynchronous on stream `s` (the context's); scratch from `m`.  Counts / bbox / the
 // out-of-range verdict are resolved lazily (map_resolve).
 mh_status map_build_device(const Switches& sw, mh_map* m, hipStream_t s, const float* dx, const float* dy, const float* dz,
-                           const uint32_t* dsrc, size_t n, const int* evict, size_t n_stored, bool collected = false);
+                           const uint32_t* dsrc, size_t n, const int* evict, size_t n_stored, bool collected = false,
+                           bool restore = false);  // restore: mh_map_restore -- keep every keyed point, flag what no download holds
 mh_status map_build_prologue(mh_map* m, hipStream_t s, size_t n, size_t n_stored, uint32_t** counters_out,
                              unsigned long long** keys_out, uint32_t** idx_out);
 // wait (host) for the last (re)build's counters and refresh n_points / n_voxels / n_records / n_planes / bbox; returns the

@@ -486,6 +486,22 @@ __global__ void k_compose_new(const float* __restrict__ x, const float* __restri
   osrc[i] = src0 + i;
 }
 
+// mh_map_restore: what a download of a map with these parameters cannot look like, found on the keys in input order and
+// OR-ed into the build's flag word (counters[0]; bit 0 is k_keys' out-of-range flag): bit 1 = a point without a key
+// (non-finite, or outside the key range), bit 2 = a key smaller than its predecessor's, bit 3 = more than `cap` equal keys
+// in a row (equal keys are contiguous once the order holds, so the entry `cap` places back tells).
+constexpr uint32_t kRestoreNoKey = 2u, kRestoreOrder = 4u, kRestoreCap = 8u;
+__global__ void k_restore_check(const unsigned long long* __restrict__ keys, uint32_t n, uint32_t cap, uint32_t* __restrict__ flags) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long k = keys[i];
+  uint32_t f = 0;
+  if (k == kEmptyKey) f |= kRestoreNoKey;
+  if (i > 0 && keys[i - 1] > k) f |= kRestoreOrder;
+  if (cap > 0 && i >= cap && keys[i - cap] == k) f |= kRestoreCap;
+  if (f) atomicOr(&flags[0], f);
+}
+
 inline uint32_t nblk(size_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 
 }  // namespace
@@ -688,6 +704,51 @@ mh_status mh_map_insert(mh_map* m, const mh_scan* scan, const double T[12], floa
   return MH_OK;
 }
 
+mh_status mh_map_restore(mh_map* m, const float* x, const float* y, const float* z, const uint32_t* src_idx, size_t n,
+                         uint64_t n_offered, int32_t mem) {
+  MH_REQUIRE(m, "null map");
+  MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE, "bad mem space");
+  MH_REQUIRE(n == 0 || (x && y && z && src_idx), "null point arrays");
+  MH_REQUIRE(n < 0x7FFFFFF0ull && n_offered < 0xFFFFFFF0ull, "too many points");
+  const Switches sw = read_switches();
+  mh_ctx* ctx = m->ctx;
+  MH_TRY(set_device(ctx));
+  hipStream_t s = ctx->stream;
+  MH_HIP(mh::wait_stream(s));  // a restore invalidates everything queued against the old content
+  (void)map_resolve(m);        // (a pending verdict about the OLD content is moot now)
+  if (n_offered < n) {
+    MH_TRY(mh_map_build(m, nullptr, nullptr, nullptr, 0, MH_MEM_HOST));
+    return fail(MH_ERR_INVALID_ARGUMENT, "mh_map_restore: n_offered (%llu) < n (%zu): not a download of a map", (unsigned long long)n_offered, n);
+  }
+  const float *dx = x, *dy = y, *dz = z;
+  const uint32_t* dsrc = src_idx;
+  if (n > 0 && mem == MH_MEM_HOST) {
+    const size_t stride = ((n * sizeof(float) + 255) / 256) * 256;
+    MH_TRY(ctx->staging.reserve(4 * stride));
+    MH_TRY(stage_in(ctx, ctx->staging, 0, x, n * sizeof(float), mem));
+    MH_TRY(stage_in(ctx, ctx->staging, stride, y, n * sizeof(float), mem));
+    MH_TRY(stage_in(ctx, ctx->staging, 2 * stride, z, n * sizeof(float), mem));
+    MH_TRY(stage_in(ctx, ctx->staging, 3 * stride, src_idx, n * sizeof(uint32_t), mem));
+    dx = (const float*)ctx->staging.as<char>();
+    dy = (const float*)(ctx->staging.as<char>() + stride);
+    dz = (const float*)(ctx->staging.as<char>() + 2 * stride);
+    dsrc = (const uint32_t*)(ctx->staging.as<char>() + 3 * stride);
+  }
+  MH_TRY(map_build_device(sw, m, s, dx, dy, dz, dsrc, n, nullptr, 0, false, true));
+  m->n_offered = n_offered;
+  MH_TRY(map_resolve_counts(m));  // the verdict, synchronously
+  m->deferred_error = MH_OK;      // (an out-of-range point is this call's own refusal below, not a deferred one)
+  const uint32_t flags = n ? m->h_counts[0] : 0u;
+  if (flags) {
+    MH_TRY(mh_map_build(m, nullptr, nullptr, nullptr, 0, MH_MEM_HOST));  // the map is left empty
+    return fail(MH_ERR_INVALID_ARGUMENT, "mh_map_restore: the input is not a download of a map with these parameters:%s%s%s",
+                (flags & (1u | kRestoreNoKey)) ? " a non-finite point or one outside the key range;" : "",
+                (flags & kRestoreOrder) ? " voxel keys not in ascending order;" : "",
+                (flags & kRestoreCap) ? " a voxel holds more than max_points_per_voxel points;" : "");
+  }
+  return MH_OK;
+}
+
 }  // extern "C"
 
 namespace mh {
@@ -831,7 +892,7 @@ mh_status map_build_prologue(mh_map* m, hipStream_t s, size_t n, size_t n_stored
 }
 
 mh_status map_build_device(const Switches& sw, mh_map* m, hipStream_t s, const float* dx, const float* dy, const float* dz,
-                           const uint32_t* dsrc, size_t n, const int* evict, size_t n_stored, bool collected) {
+                           const uint32_t* dsrc, size_t n, const int* evict, size_t n_stored, bool collected, bool restore) {
   const uint32_t ndt = m->params.ndt_max_eigen_ratio > 0.f ? 1u : 0u;
   const size_t n_vox_ub = n_stored ? std::min<size_t>(n, m->n_voxels + (n - n_stored)) : n;
   const size_t n_rec_ub = n + (ndt ? 2 * n_vox_ub : 0);
@@ -880,6 +941,8 @@ mh_status map_build_device(const Switches& sw, mh_map* m, hipStream_t s, const f
     if (!collected)
       hipLaunchKernelGGL(k_keys, dim3(nblk(n, B)), dim3(B), 0, s, dx, dy, dz, N, m->inv_vs,
                          (uint32_t)(m->params.index_mode == MH_INDEX_TRUNC), ev_keys, m->params.far_voxel_metric, keys, idx, counters);
+    // mh_map_restore: could the input have been a download?  (on the keys in INPUT order, before the sort hides their order)
+    if (restore) hipLaunchKernelGGL(k_restore_check, dim3(nblk(n, B)), dim3(B), 0, s, keys, N, m->params.max_points_per_voxel, counters);
     unsigned long long* keys_new = keys + 2 * n;
     uint32_t* idx_new = idx + 2 * n;
     size_t tmp = 0;
@@ -914,7 +977,9 @@ mh_status map_build_device(const Switches& sw, mh_map* m, hipStream_t s, const f
     tb = m->sort_tmp.bytes;
     MH_HIP(rocprim::inclusive_scan(m->sort_tmp.p, tb, head, vid1, N, rocprim::plus<uint32_t>(), s));
     hipLaunchKernelGGL(k_vstart, dim3(nblk(n, B)), dim3(B), 0, s, head, vid1, N, vstart);
-    if (m->params.min_distance_between_points > 0.f)
+    if (restore)  // exactly the points given: no cap and no clearance decision (k_restore_check has flagged a voxel over the cap)
+      hipLaunchKernelGGL(k_keep, dim3(nblk(n, B)), dim3(B), 0, s, keys_s, vid1, vstart, N, 0u, keep);
+    else if (m->params.min_distance_between_points > 0.f)
       hipLaunchKernelGGL(k_keep_seq, dim3(nblk(n, kKeepBlock)), dim3(kKeepBlock), 0, s, dx, dy, dz, keys_s, idx_s, head, vid1,
                          vstart, N, m->params.max_points_per_voxel, m->params.min_distance_between_points, (uint32_t)n_stored,
                          keep_lds_points(sw), keep);

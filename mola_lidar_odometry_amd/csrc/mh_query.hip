@@ -1,6 +1,7 @@
 // mh_query.hip -- map queries with a variable number of results per point: mh_nn_search_radius, the stand-in for
 // mrpt::maps::NearestNeighborsCapable::nn_radius_search [U] on the hashed voxel map.  A translation unit of its own: the
-// matcher, map and filter objects are built from sources this query does not touch.
+// matcher, map and filter objects are built from sources this query does not touch.  Also mh_score_poses (at the end): one
+// scan scored under many candidate poses in one launch (mh_k_score.h).
 //
 // count (k_radius<false>) -> sum / max + rocPRIM exclusive scan -> one read-back of {sum, max} -> fill (k_radius<true>)
 // [-> rocPRIM stable radix sort of (query, d2 bits) -> gather] -> copies.  Scratch is the context's grow-only buffers (build_a..e,
@@ -12,6 +13,7 @@
 #include <algorithm>
 
 #include "mh_k_radius.h"
+#include "mh_k_score.h"
 
 using namespace mh;
 
@@ -172,6 +174,67 @@ mh_status mh_nn_search_radius(const mh_map* map, const mh_scan* scan, const doub
     if (out->gz) MH_HIP(hipMemcpy(out->gz, dst.z, nr * 4, hipMemcpyDeviceToHost));
     if (out->d2) MH_HIP(hipMemcpy(out->d2, dst.d2, nr * 4, hipMemcpyDeviceToHost));
   }
+  return MH_OK;
+}
+
+mh_status mh_score_poses(const mh_map* map, const mh_scan* scan, const double* poses, size_t n_poses, double threshold,
+                         double threshold_angular_deg, mh_pose_score* scores, int32_t mem) {
+  // ---- refusals: all decided before anything is queued
+  MH_REQUIRE(map && scan && scores && (poses || n_poses == 0), "null argument");
+  MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE, "bad mem space");
+  MH_REQUIRE(map->ctx->device == scan->ctx->device, "map and scan live on different devices");
+  MH_REQUIRE(isfinite(threshold) && threshold >= 1.0e-3 && threshold <= 1.0e3, "threshold must be finite and within [1e-3, 1e3] m");
+  MH_REQUIRE(isfinite(threshold_angular_deg) && threshold_angular_deg >= 0.0, "angular threshold must be finite and >= 0");
+  if (n_poses > (size_t)MH_SCORE_MAX_POSES)
+    return fail(MH_ERR_UNSUPPORTED, "mh_score_poses: %zu poses exceed MH_SCORE_MAX_POSES (%d)", n_poses, MH_SCORE_MAX_POSES);
+  for (size_t c = 0; c < n_poses; c++) MH_REQUIRE(pose_finite(poses + 12 * c), "non-finite pose");
+  MH_REQUIRE(scan->n < 0xFFFFFFFFull, "scan size does not fit 32 bits");
+  const Switches sw = read_switches();
+
+  mh_ctx* ctx = scan->ctx;
+  MH_TRY(set_device(ctx));
+  hipStream_t s = ctx->stream;
+  const size_t n = scan->n;
+  if (n_poses == 0) return MH_OK;
+  const size_t sbytes = n_poses * sizeof(mh_pose_score);
+  if (n == 0) {  // zeroed scores
+    if (mem == MH_MEM_HOST) {
+      memset(scores, 0, sbytes);
+    } else {
+      MH_HIP(hipMemsetAsync(scores, 0, sbytes, s));
+      MH_HIP(mh::wait_stream(s));
+    }
+    return MH_OK;
+  }
+  MH_TRY(map_ready_on(map, s));
+
+  const float thr2 = (float)(threshold * threshold);  // the squares taken in fp64, rounded once (mh_nn_search)
+  const double ang = threshold_angular_deg * 3.14159265358979323846 / 180.0;
+  const float ang2 = (float)(ang * ang);
+  const float qscale = (float)(1048576.0 / (double)thr2);
+  const MapView mv = map->view(sw);
+
+  // the poses travel in one copy; host-bound scores are summed in a staging block
+  MH_TRY(ctx->staging.reserve(n_poses * 12 * sizeof(double)));
+  MH_TRY(stage_in(ctx, ctx->staging, 0, poses, n_poses * 12 * sizeof(double), MH_MEM_HOST));
+  const double* d_poses = ctx->staging.as<double>();
+  mh_pose_score* d_scores = scores;
+  if (mem == MH_MEM_HOST) {
+    MH_TRY(ctx->compact.reserve(sbytes));
+    d_scores = ctx->compact.as<mh_pose_score>();
+  }
+  MH_HIP(hipMemsetAsync(d_scores, 0, sbytes, s));
+  // one workgroup per (candidate, tile), flattened; launches of at most 2^30 workgroups
+  const uint32_t n_tiles = nblk(n, kScoreBlock);
+  const size_t per_launch = std::max<size_t>(1, (size_t(1) << 30) / n_tiles);
+  for (size_t c0 = 0; c0 < n_poses; c0 += per_launch) {
+    const size_t nc = std::min(per_launch, n_poses - c0);
+    hipLaunchKernelGGL(k_score_poses, dim3((uint32_t)(nc * n_tiles)), dim3(kScoreBlock), 0, s, d_poses + 12 * c0, n_tiles, scan->x,
+                       scan->y, scan->z, (uint32_t)n, mv, thr2, ang2, qscale, d_scores + c0);
+    MH_HIP(hipGetLastError());
+  }
+  if (mem == MH_MEM_HOST) MH_HIP(hipMemcpyAsync(scores, d_scores, sbytes, hipMemcpyDeviceToHost, s));
+  MH_HIP(mh::wait_stream(s));
   return MH_OK;
 }
 

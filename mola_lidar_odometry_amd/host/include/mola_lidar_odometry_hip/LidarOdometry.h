@@ -11,6 +11,12 @@
 //            -> goodness gate, motion-model update, trajectory                           (:1026-1045)
 //            -> adaptive sigma                                                           (:1052-1064, 1437-1485)
 //            -> key-frame decision, [device] local-map update                            (:1066-1118, 1160-1206)
+// Localization in a saved map: saveLocalMaps() writes the local maps (molahip_host/local_map_file.h),
+// params.local_map_updates.load_existing_local_map brings them back at initialize() / reset() (:465-470), initial_localization
+// seeds the motion model at the first registration (:779-794), and relocalizeNearPose() -- the role of
+// mola::Relocalization::relocalize_near_pose_pdf, whose body is a TODO in the reference (LidarOdometry.h:425-437,
+// LidarOdometry.cpp:2222-2230) -- finds the pose in the map from a coarse one: a grid of candidates scored on the device in one
+// launch (mh_score_poses), the best few refined by ICP.
 //
 // Host code here is control logic only; every point touches the GPU through include/molahip.h.  What is NOT here:
 // MOLA module plumbing, IMU/GNSS/wheel inputs, simplemap generation, visualisation, ROS.
@@ -119,6 +125,13 @@ class SensorSync {
   std::map<std::string, double> waiting_;
 };
 
+// The candidate poses of a relocalization around `mean` with covariance `cov` (6x6 row-major, (x, y, z, yaw, pitch, roll)
+// order): a grid over x, y and yaw; z, pitch and roll are the mean's.  Per axis n = 2 * ceil(sigmas * sigma / step) + 1 nodes at
+// (i - (n - 1) / 2) * step, sigma = sqrt of the axis' diagonal entry; the offsets are added to the mean's TPose3D fields (map
+// frame); enumeration order x outer, y middle, yaw inner.  More than max_candidates nodes: std::runtime_error (coarsen the steps).
+std::vector<TPose3D> relocalization_grid(const TPose3D& mean, const double cov[36], double step_xy, double step_yaw_rad,
+                                         double sigmas = 3.0, size_t max_candidates = 65536);
+
 class LidarOdometry {
  public:
   // the params: block of the pipeline file (yaml:6-122); formulas are re-evaluated every scan
@@ -141,7 +154,34 @@ class LidarOdometry {
     uint32_t lidar_count = 1;        // multiple_lidars.lidar_count (reference LidarOdometry.h:152)
     double max_time_offset = 25e-3;  // multiple_lidars.max_time_offset [s] (:156)
     std::vector<std::string> lidar_sensor_labels;  // regular expressions, std::regex_match (:261-275, 576-577); empty: every label
+    // local_map_updates.load_existing_local_map (MOLA_LOAD_MM, yaml:40; :465-470): a file written by saveLocalMaps().  Non-empty:
+    // the local maps are created from the FILE's parameters and restored at initialize() and again by reset(); the first
+    // observation is then registered by ICP (no "first scan" entry).  With mapping enabled the key-frame list starts empty, so
+    // the first good alignment with a motion model is a key-frame merged into the loaded map (multi-session mapping).  The rule
+    // "bad ICP while the trajectory holds one pose: clear the map and start again" (:1148-1158) is kept and CAN discard a loaded map.
+    std::string load_existing_local_map;
     void load_from(const Config& c);
+  };
+  // the initial_localization: block of the pipeline file (yaml:147-151; :779-794).  enabled: at the first observation that
+  // reaches registration the fixed pose is fused into the motion model at t - 0.2 and t - 0.1 (once), so that registration
+  // starts there with a zero twist.  Only InitLocalization::FixedPose exists here (no GNSS input): anything else is refused at
+  // initialize().  relocalize_sigmas: [sigma_x [m], sigma_y [m], sigma_yaw [deg]] is this implementation's extension: the first
+  // observation is then served by relocalizeNearPose() around fixed_initial_pose instead of the plain seed.
+  struct InitialLocalization {
+    bool enabled = false;
+    std::string method = "InitLocalization::FixedPose";
+    TPose3D fixed_initial_pose;
+    bool relocalize = false;
+    double relocalize_sigmas[3] = {0, 0, 0};
+  };
+  // the relocalization: block (this implementation's own key, as motion_model_prior is)
+  struct RelocalizationOptions {
+    std::string score_threshold;  // [m] formula over the dynamic variables; empty: 0.5 x the searched map's voxel size
+    double step_xy = 0;           // [m] 0: the score threshold
+    double step_yaw_deg = 3.0;
+    double sigmas = 3.0;
+    uint32_t refine_top_k = 4;
+    uint32_t max_candidates = 65536;
   };
 
   // one line of the per-scan log (what the reference spreads over debug traces / the parameter source)
@@ -170,6 +210,12 @@ class LidarOdometry {
     bool waiting = false, ignored = false;
     uint32_t n_sensors = 1;
     std::vector<std::string> sensor_labels;
+    // a relocalization request served at this scan (relocalizeNearPose): candidates scored, the best candidate's accepted
+    // points, the winner's ICP quality, the candidate indices that were refined (in rank order); relocalized = accepted
+    bool relocalization_tried = false, relocalized = false;
+    uint32_t reloc_candidates = 0, reloc_best_n_paired = 0;
+    double reloc_best_quality = 0;
+    std::vector<uint32_t> reloc_ranks;
   };
 
   // ctx == nullptr: the process-wide default device context, taken at initialize()
@@ -238,6 +284,28 @@ class LidarOdometry {
   // TUM format "t x y z qx qy qz qw" (estimated_trajectory.output_file, yaml:79-81; eval/cli_kitti.sh:41-50)
   void saveTrajectoryTUM(const std::string& path) const;
   const Params& params() const { return params_; }
+  const InitialLocalization& initialLocalization() const { return init_loc_; }
+  const RelocalizationOptions& relocalizationOptions() const { return reloc_opts_; }
+  // Every local map of the plan, by name, into one file (molahip_host/local_map_file.h); throws before the first key-frame
+  // (no map yet) and for a plan with a CVoxelMap (an occupancy map has no snapshot).
+  void saveLocalMaps(const std::string& path) const;
+  // The role of mola::Relocalization::relocalize_near_pose_pdf: `mean` with covariance `cov` (6x6 row-major, (x, y, z, yaw, pitch,
+  // roll)) is where the vehicle is believed to be in the map frame.  The request is served by the next observation that reaches
+  // registration with a non-empty map, after its filter passes and before the motion-model query:
+  //   1. candidates: relocalization_grid over x, y, yaw (relocalization.step_xy / step_yaw_deg / sigmas); more than
+  //      max_candidates makes THIS call throw (when the map whose voxel sizes the defaults is not there yet: the serving scan);
+  //   2. one mh_score_poses of the (global, local) layers of the first pointLayerMatches entry of the first enabled
+  //      Matcher_Points_DistanceThreshold of the no-motion-model ICP block, at relocalization.score_threshold;
+  //   3. rank by (n_paired descending, cost ascending, index ascending), keep refine_top_k;
+  //   4. align from each kept candidate with the NoMotionModel ICP, no prior, hooks cleared, one after another; the winner has
+  //      the highest quality, ties go to the better rank;
+  //   5. quality >= min_icp_goodness: the motion model is reset and seeded with the winner's pose as initial_localization does,
+  //      the last pose is set, the request is cleared and the scan's normal registration runs from there; otherwise the request
+  //      stays pending for the next observation and the scan proceeds as it would have.
+  // At relocalization time the twist is unknown: the layers were de-skewed with the current twist variables, which are zero
+  // after a reset.  With an AlignBatcher set this throws: the batch protocol has no slot for extra alignments of one member.
+  void relocalizeNearPose(const CPose3D& mean, const double cov[36]);
+  bool relocalizationPending() const { return reloc_request_.has_value(); }
   std::shared_ptr<HashedVoxelPointCloud> localMap() const { return local_map_; }
   // points of every local map by name (general plans: one per localmap_generator entry; 0 before the first key-frame)
   std::map<std::string, uint64_t> localMapSizes() const;
@@ -306,6 +374,11 @@ class LidarOdometry {
   void record_layer_sizes(ScanRecord& rec) const;  // general plans: layer_sizes, n_for_icp, n_for_map of the live layers
   uint64_t maps_total(bool voxels) const;
   void ensure_device();
+  void restore_loaded_maps();                                // load_existing_local_map: the maps from the file's records
+  void seed_motion_model(double t, const CPose3D& pose);     // fuse `pose` at t - 0.2 and t - 0.1 (:779-794)
+  void scan_layers(mp2p_icp_hip::metric_map_t& obs, mp2p_icp_hip::metric_map_t& glob) const;  // what this scan's ICP aligns
+  void serve_relocalization(double t, ScanRecord& rec);
+  double reloc_score_threshold(const std::string& global_layer) const;  // NaN while the searched map is not there
   void resolve_map_counts() const;  // fills n_map_points / n_map_voxels of the records that still wait for them
   bool map_is_empty();              // local_map_->empty() without a device round trip once the map is known to hold points
 
@@ -360,6 +433,15 @@ class LidarOdometry {
   mutable size_t map_counts_from_ = 0;
   mutable uint64_t map_points_cached_ = 0, map_voxels_cached_ = 0;
   mutable bool map_known_nonempty_ = false;
+  InitialLocalization init_loc_;
+  RelocalizationOptions reloc_opts_;
+  std::vector<molahip_host::LocalMapRecord> loaded_maps_;  // load_existing_local_map, read at initialize()
+  bool initial_localization_done_ = false;
+  struct RelocRequest {
+    CPose3D mean;
+    double cov[36];
+  };
+  std::optional<RelocRequest> reloc_request_;
   bool input_pinned_ = false;
   bool intensity_input_ = false;  // setIntensityInput
   std::map<std::string, double> profile_;

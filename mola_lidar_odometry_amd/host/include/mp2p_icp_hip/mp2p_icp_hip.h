@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "molahip.h"
+#include "molahip_host/local_map_file.h"
 
 namespace mp2p_icp_hip {
 
@@ -250,13 +251,28 @@ class HashedVoxelPointCloud : public Layer {
                              bool sorted = false) const;
   mh_map* handle() const { return map_; }
   const std::shared_ptr<DeviceContext>& context() const { return ctx_; }
+  // ---- snapshot / restore (mh_map_download + mh_map_restore; the file: molahip_host/local_map_file.h)
+  const mh_map_params& params() const { return params_; }
+  virtual const char* className() const { return "HashedVoxelPointCloud"; }  // the class string of the map file
+  // the stored content as mh_map_download gives it, n_offered and the parameters, under `name`
+  virtual molahip_host::LocalMapRecord snapshot(const std::string& name = "map", float remove_voxels_farther_than = 0.f) const;
+  // replaces the content by a snapshot's; afterwards the map is indistinguishable from the one that was saved (searches,
+  // following insertions).  The record's class and parameters must be this map's: a map FROM a record's parameters is what
+  // make_local_map builds.
+  virtual void restore(const molahip_host::LocalMapRecord& rec);
+  // one map per file; loadFromFile takes the map called `name`, or the only one when `name` is empty
+  virtual void saveToFile(const std::string& path, const std::string& name = "map", float remove_voxels_farther_than = 0.f) const;
+  virtual void loadFromFile(const std::string& path, const std::string& name = "");
 
  protected:
   struct NoMap {};  // a subclass that brings its own search map
   HashedVoxelPointCloud(NoMap, std::shared_ptr<DeviceContext> ctx) : ctx_(std::move(ctx)) {}
   std::shared_ptr<DeviceContext> ctx_;
   mutable mh_map* map_ = nullptr;
+  mh_map_params params_{};
 };
+// a new map of the record's class with the record's parameters, holding the record's content (restored)
+std::shared_ptr<HashedVoxelPointCloud> make_local_map(const molahip_host::LocalMapRecord& rec, std::shared_ptr<DeviceContext> ctx);
 // mrpt::maps::CVoxelMap stand-in (lidar2d.yaml:183-198), NN role only: a device-resident log-odds occupancy voxel map updated
 // by ray tracing (mh_occmap, include/molahip.h) whose handle() is the inner search map over the centres of its occupied
 // voxels -- so every matcher, ICP path and AlignBatcher batch takes it as the HashedVoxelPointCloud it derives from.  size() =
@@ -275,6 +291,10 @@ class CVoxelMap : public HashedVoxelPointCloud {
   size_t voxelCount() const override;
   void prepareSearch(double max_radius) const override;
   mh_occmap* occHandle() const { return occ_; }
+  // an occupancy map has no snapshot yet (its cells and log-odds are not what mh_map_restore takes): these throw and say so
+  const char* className() const override { return "CVoxelMap"; }
+  molahip_host::LocalMapRecord snapshot(const std::string& name = "map", float remove_voxels_farther_than = 0.f) const override;
+  void restore(const molahip_host::LocalMapRecord& rec) override;
   float searchVoxelSize() const;  // the inner search map's voxel: it starts at 1 m and grows with prepareSearch
   // cells in ascending key order: 3 indices each, and their log-odds
   void download(std::vector<int32_t>& keys_xyz, std::vector<int32_t>& logodds) const;
@@ -295,6 +315,8 @@ class SparseTreesPointCloud : public HashedVoxelPointCloud {
  public:
   SparseTreesPointCloud(float grid_size, float minimum_points_clearance,
                         std::shared_ptr<DeviceContext> ctx = DeviceContext::Default());
+  SparseTreesPointCloud(const mh_map_params& p, std::shared_ptr<DeviceContext> ctx) : HashedVoxelPointCloud(p, std::move(ctx)) {}
+  const char* className() const override { return "SparseTreesPointCloud"; }
 };
 // mola::NDT stand-in (lidar3d-ndt.yaml:236-254): the same device map plus per-voxel mean / covariance / eigen
 // statistics, i.e. additionally NearestPlaneCapable for Matcher_Point2Plane
@@ -302,6 +324,8 @@ class NDT : public HashedVoxelPointCloud {
  public:
   NDT(float voxel_size, uint32_t max_points_per_voxel, float min_distance_between_points, float max_eigen_ratio_for_planes,
       std::shared_ptr<DeviceContext> ctx = DeviceContext::Default());
+  NDT(const mh_map_params& p, std::shared_ptr<DeviceContext> ctx) : HashedVoxelPointCloud(p, std::move(ctx)) {}
+  const char* className() const override { return "NDT"; }
   size_t planeCount() const;
 };
 struct metric_map_t {

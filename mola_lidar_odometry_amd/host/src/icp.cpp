@@ -176,9 +176,72 @@ HashedVoxelPointCloud::HashedVoxelPointCloud(float voxel_size, uint32_t max_poin
   p.index_mode = molahip_host::plugin_switches().index_mode;          // MOLA_HIP_INDEX_MODE (default floor)
   p.far_voxel_metric = molahip_host::plugin_switches().far_voxel_metric;  // MOLA_HIP_FAR_VOXEL_METRIC (default Chebyshev)
   check(mh_map_create(ctx_->get(), &p, &map_), "mh_map_create");
+  params_ = p;
 }
 HashedVoxelPointCloud::HashedVoxelPointCloud(const mh_map_params& p, std::shared_ptr<DeviceContext> ctx) : ctx_(std::move(ctx)) {
   check(mh_map_create(ctx_->get(), &p, &map_), "mh_map_create");
+  params_ = p;
+}
+
+// ---- snapshot / restore
+molahip_host::LocalMapRecord HashedVoxelPointCloud::snapshot(const std::string& name, float remove_voxels_farther_than) const {
+  molahip_host::LocalMapRecord r;
+  r.name = name;
+  r.class_name = className();
+  r.params = params_;
+  r.remove_voxels_farther_than = remove_voxels_farther_than;
+  mh_map_info mi{};
+  check(mh_map_get_info(map_, &mi), "mh_map_get_info");
+  r.n_offered = mi.n_offered;
+  const size_t n = mi.n_points;
+  r.x.resize(n); r.y.resize(n); r.z.resize(n); r.src_idx.resize(n);
+  if (n) check(mh_map_download(map_, r.x.data(), r.y.data(), r.z.data(), r.src_idx.data(), nullptr, nullptr, nullptr), "mh_map_download");
+  return r;
+}
+void HashedVoxelPointCloud::restore(const molahip_host::LocalMapRecord& rec) {
+  if (rec.class_name != className())
+    throw std::runtime_error(std::string("HashedVoxelPointCloud::restore: map '") + rec.name + "' was saved from a " + rec.class_name +
+                             ", this object is a " + className());
+  const mh_map_params &a = rec.params, &b = params_;
+  if (a.voxel_size != b.voxel_size || a.max_points_per_voxel != b.max_points_per_voxel || a.index_mode != b.index_mode ||
+      a.min_distance_between_points != b.min_distance_between_points || a.ndt_max_eigen_ratio != b.ndt_max_eigen_ratio ||
+      a.ndt_min_points != b.ndt_min_points || a.far_voxel_metric != b.far_voxel_metric)
+    throw std::runtime_error("HashedVoxelPointCloud::restore: map '" + rec.name + "' was saved with other parameters (voxel_size " +
+                             std::to_string(a.voxel_size) + ", max_points_per_voxel " + std::to_string(a.max_points_per_voxel) +
+                             ", index_mode " + std::to_string(a.index_mode) + ") than this map's (" + std::to_string(b.voxel_size) + ", " +
+                             std::to_string(b.max_points_per_voxel) + ", " + std::to_string(b.index_mode) +
+                             "); make_local_map() builds a map from the saved parameters");
+  check(mh_map_restore(map_, rec.x.data(), rec.y.data(), rec.z.data(), rec.src_idx.data(), rec.x.size(), rec.n_offered, MH_MEM_HOST),
+        "mh_map_restore");
+}
+void HashedVoxelPointCloud::saveToFile(const std::string& path, const std::string& name, float remove_voxels_farther_than) const {
+  molahip_host::write_local_map_file(path, {snapshot(name, remove_voxels_farther_than)});
+}
+void HashedVoxelPointCloud::loadFromFile(const std::string& path, const std::string& name) {
+  const std::vector<molahip_host::LocalMapRecord> maps = molahip_host::read_local_map_file(path);
+  const molahip_host::LocalMapRecord* pick = nullptr;
+  for (const auto& m : maps)
+    if (name.empty() ? maps.size() == 1 : m.name == name) pick = &m;
+  if (!pick)
+    throw std::runtime_error("local map file '" + path + "': " + (name.empty() ? "holds " + std::to_string(maps.size()) + " maps: name the one to load"
+                                                                                : "holds no map called '" + name + "'"));
+  restore(*pick);
+}
+std::shared_ptr<HashedVoxelPointCloud> make_local_map(const molahip_host::LocalMapRecord& rec, std::shared_ptr<DeviceContext> ctx) {
+  std::shared_ptr<HashedVoxelPointCloud> m;
+  if (rec.class_name == "HashedVoxelPointCloud") m = std::make_shared<HashedVoxelPointCloud>(rec.params, std::move(ctx));
+  else if (rec.class_name == "NDT") m = std::make_shared<NDT>(rec.params, std::move(ctx));
+  else if (rec.class_name == "SparseTreesPointCloud") m = std::make_shared<SparseTreesPointCloud>(rec.params, std::move(ctx));
+  else throw std::runtime_error("make_local_map: map '" + rec.name + "' is a '" + rec.class_name + "', which this loader cannot build");
+  m->restore(rec);
+  return m;
+}
+molahip_host::LocalMapRecord CVoxelMap::snapshot(const std::string&, float) const {
+  throw std::runtime_error("CVoxelMap: an occupancy voxel map has no snapshot (saveToFile / saveLocalMaps cover HashedVoxelPointCloud, "
+                           "NDT and SparseTreesPointCloud; the cells and log-odds of a CVoxelMap are not part of the map file yet)");
+}
+void CVoxelMap::restore(const molahip_host::LocalMapRecord&) {
+  throw std::runtime_error("CVoxelMap: an occupancy voxel map cannot be restored from a map file (no snapshot of its cells and log-odds yet)");
 }
 
 static mh_map_params ndt_params(float vs, uint32_t cap, float min_dist, float ratio) {

@@ -3,6 +3,7 @@
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
 #include "molahip_host/plugin_switches.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -202,6 +203,12 @@ void LidarOdometry::Params::load_from(const Config& c) {
     parameterFromConfig(l, "min_rotation_between_keyframes", &min_rotation_between_keyframes, true);
     parameterFromConfig(l, "max_distance_to_keep_keyframes", &max_distance_to_keep_keyframes, false);
     if (l.has("check_for_removal_every_n")) check_for_removal_every_n = (uint32_t)to_double(l["check_for_removal_every_n"].asString());
+    load_existing_local_map.clear();
+    if (l.has("load_existing_local_map") && !l["load_existing_local_map"].isNull()) {
+      std::string f = l["load_existing_local_map"].asString();
+      if (f.size() >= 2 && (f.front() == '"' || f.front() == '\'') && f.back() == f.front()) f = f.substr(1, f.size() - 2);  // (${MOLA_LOAD_MM|""})
+      load_existing_local_map = f;
+    }
   }
   if (c.has("adaptive_threshold")) {
     const Config& a = c["adaptive_threshold"];
@@ -797,7 +804,273 @@ void LidarOdometry::initialize(const Config& cfg) {
   if (gen.size() < 1) throw std::runtime_error("localmap_generator is empty");
   map_def_ = gen.at(0)["params"]["metric_map_definition"];
 
-  reset();  // device objects are created at the first scan: a pipeline can be loaded and checked without a GPU
+  // initial_localization (yaml:147-151) and this implementation's relocalization: block
+  init_loc_ = InitialLocalization();
+  if (cfg.has("initial_localization")) {
+    const Config& il = cfg["initial_localization"];
+    if (il.has("enabled")) init_loc_.enabled = to_bool(il["enabled"].asString());
+    if (il.has("method")) init_loc_.method = il["method"].asString();
+    if (!ends_with(init_loc_.method, "FixedPose"))
+      throw std::runtime_error("LidarOdometry (HIP): initial_localization.method '" + init_loc_.method +
+                               "' is not implemented: only InitLocalization::FixedPose is (there are no GNSS inputs here)");
+    if (il.has("fixed_initial_pose")) {
+      const Config& fp = il["fixed_initial_pose"];
+      if (fp.size() != 6) throw std::runtime_error("LidarOdometry (HIP): initial_localization.fixed_initial_pose needs 6 values (x y z yaw pitch roll)");
+      double v[6];
+      for (size_t i = 0; i < 6; i++) v[i] = to_double(fp.at(i).asString());
+      init_loc_.fixed_initial_pose = TPose3D{v[0], v[1], v[2], v[3], v[4], v[5]};
+    }
+    if (il.has("relocalize_sigmas") && il["relocalize_sigmas"].size() > 0) {
+      const Config& rs = il["relocalize_sigmas"];
+      if (rs.size() != 3) throw std::runtime_error("LidarOdometry (HIP): initial_localization.relocalize_sigmas needs 3 values (sigma_x [m], sigma_y [m], sigma_yaw [deg])");
+      for (size_t i = 0; i < 3; i++) {
+        init_loc_.relocalize_sigmas[i] = to_double(rs.at(i).asString());
+        if (!(init_loc_.relocalize_sigmas[i] >= 0.0) || !std::isfinite(init_loc_.relocalize_sigmas[i]))
+          throw std::runtime_error("LidarOdometry (HIP): initial_localization.relocalize_sigmas must be finite and >= 0");
+      }
+      init_loc_.relocalize = true;
+    }
+  }
+  reloc_opts_ = RelocalizationOptions();
+  if (cfg.has("relocalization")) {
+    const Config& r = cfg["relocalization"];
+    if (r.has("score_threshold") && !r["score_threshold"].isNull()) reloc_opts_.score_threshold = r["score_threshold"].asString();
+    if (r.has("step_xy") && !r["step_xy"].isNull()) reloc_opts_.step_xy = to_double(r["step_xy"].asString());
+    if (r.has("step_yaw_deg")) reloc_opts_.step_yaw_deg = to_double(r["step_yaw_deg"].asString());
+    if (r.has("sigmas")) reloc_opts_.sigmas = to_double(r["sigmas"].asString());
+    if (r.has("refine_top_k")) reloc_opts_.refine_top_k = (uint32_t)to_double(r["refine_top_k"].asString());
+    if (r.has("max_candidates")) reloc_opts_.max_candidates = (uint32_t)to_double(r["max_candidates"].asString());
+    if (!(reloc_opts_.step_xy >= 0.0) || !(reloc_opts_.step_yaw_deg > 0.0) || !(reloc_opts_.sigmas > 0.0) || reloc_opts_.refine_top_k < 1 ||
+        reloc_opts_.max_candidates < 1 || reloc_opts_.max_candidates > MH_SCORE_MAX_POSES)
+      throw std::runtime_error("LidarOdometry (HIP): relocalization: step_xy >= 0, step_yaw_deg > 0, sigmas > 0, refine_top_k >= 1 and "
+                               "1 <= max_candidates <= " + std::to_string(MH_SCORE_MAX_POSES) + " are required");
+  }
+
+  // a saved map (:465-470): read now, names held against the plan's; the device maps are made by reset()
+  loaded_maps_.clear();
+  if (!params_.load_existing_local_map.empty()) {
+    const std::string& path = params_.load_existing_local_map;
+    loaded_maps_ = molahip_host::read_local_map_file(path);
+    std::vector<std::string> want;
+    if (gplan_) for (const auto& m : gplan_->maps) want.push_back(m.name);
+    else want.push_back(plan_->map_layer);
+    std::vector<std::string> have;
+    for (const auto& r : loaded_maps_) have.push_back(r.name);
+    auto sorted = [](std::vector<std::string> v) { std::sort(v.begin(), v.end()); return v; };
+    if (sorted(want) != sorted(have)) {
+      auto join = [](const std::vector<std::string>& v) { std::string o; for (const auto& x : v) o += (o.empty() ? "'" : ", '") + x + "'"; return o; };
+      throw std::runtime_error("LidarOdometry (HIP): params.local_map_updates.load_existing_local_map: local map file '" + path + "' holds the maps " +
+                               join(have) + ", the pipeline's localmap_generator makes " + join(want) + ": the names must match");
+    }
+  }
+
+  reset();  // device objects are created at the first scan: a pipeline can be loaded and checked without a GPU (a saved map
+            // is restored here, which needs one)
+}
+
+void LidarOdometry::restore_loaded_maps() {
+  if (!ctx_) ctx_ = DeviceContext::Default();
+  auto rec_of = [&](const std::string& name) -> const molahip_host::LocalMapRecord& {
+    for (const auto& r : loaded_maps_)
+      if (r.name == name) return r;
+    throw std::runtime_error("local map file: no map called '" + name + "'");  // (initialize() has checked the names)
+  };
+  if (gplan_) {
+    for (auto& m : gplan_->maps) {
+      const auto& r = rec_of(m.name);
+      m.map = mp2p_icp_hip::make_local_map(r, ctx_);
+      m.voxel_size = (double)r.params.voxel_size;
+      m.remove_far = r.remove_voxels_farther_than;
+    }
+    local_map_ = gplan_->maps[0].map;
+    map_voxel_size_ = gplan_->maps[0].voxel_size;
+  } else {
+    const auto& r = rec_of(plan_->map_layer);
+    local_map_ = mp2p_icp_hip::make_local_map(r, ctx_);
+    map_voxel_size_ = (double)r.params.voxel_size;
+    remove_voxels_farther_than_ = r.remove_voxels_farther_than;
+  }
+  map_points_cached_ = gplan_ ? maps_total(false) : local_map_->size();
+  map_voxels_cached_ = gplan_ ? maps_total(true) : local_map_->voxelCount();
+  map_known_nonempty_ = map_points_cached_ != 0;
+}
+
+void LidarOdometry::saveLocalMaps(const std::string& path) const {
+  std::vector<molahip_host::LocalMapRecord> recs;
+  if (gplan_) {
+    for (const auto& m : gplan_->maps) {
+      if (!m.map) throw std::runtime_error("LidarOdometry::saveLocalMaps: local map '" + m.name + "' does not exist yet (no key-frame so far)");
+      recs.push_back(m.map->snapshot(m.name, m.remove_far));
+    }
+  } else {
+    if (!plan_ || !local_map_) throw std::runtime_error("LidarOdometry::saveLocalMaps: the local map does not exist yet (no key-frame so far)");
+    recs.push_back(local_map_->snapshot(plan_->map_layer, remove_voxels_farther_than_));
+  }
+  molahip_host::write_local_map_file(path, recs);
+}
+
+void LidarOdometry::seed_motion_model(double t, const CPose3D& pose) {  // "fake an evolution to have an initial velocity estimation" (:784-790)
+  navstate_.fuse_pose(t - 0.2, pose);  // (cov null: the 1e-12 diagonal of :783)
+  navstate_.fuse_pose(t - 0.1, pose);
+}
+
+void LidarOdometry::scan_layers(mp2p_icp_hip::metric_map_t& obs, mp2p_icp_hip::metric_map_t& glob) const {
+  if (gplan_) {  // every layer the filters leave, every map (the ICP pipeline's matchers pick their pairs)
+    for (const auto& name : gplan_->alive)
+      obs.layers[name] = name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name);
+    for (const auto& m : gplan_->maps)
+      if (m.map) glob.layers[m.name] = m.map;
+  } else {
+    obs.layers[plan_->layer_for_icp] = for_icp_;
+    obs.layers[plan_->layer_for_map] = for_map_;
+    glob.layers[plan_->map_layer] = local_map_;
+  }
+}
+
+// ================================================================== relocalization
+std::vector<TPose3D> relocalization_grid(const TPose3D& mean, const double cov[36], double step_xy, double step_yaw_rad, double sigmas,
+                                         size_t max_candidates) {
+  if (!(step_xy > 0.0) || !(step_yaw_rad > 0.0) || !(sigmas > 0.0) || !std::isfinite(step_xy) || !std::isfinite(step_yaw_rad) || !std::isfinite(sigmas))
+    throw std::runtime_error("relocalization_grid: the steps and sigmas must be finite and > 0");
+  auto nodes = [&](double var, double step) -> size_t {
+    if (!(var >= 0.0) || !std::isfinite(var)) throw std::runtime_error("relocalization_grid: the covariance diagonal must be finite and >= 0");
+    const double half = std::ceil(sigmas * std::sqrt(var) / step);
+    if (!(half < 1.0e7)) throw std::runtime_error("relocalization_grid: more than max_candidates candidates: coarsen the steps");
+    return 2 * (size_t)half + 1;
+  };
+  const size_t nx = nodes(cov[0], step_xy), ny = nodes(cov[7], step_xy), nyaw = nodes(cov[21], step_yaw_rad);
+  if (nx * ny > max_candidates || nx * ny * nyaw > max_candidates)
+    throw std::runtime_error("relocalization_grid: " + std::to_string(nx) + " x " + std::to_string(ny) + " x " + std::to_string(nyaw) +
+                             " candidates exceed max_candidates (" + std::to_string(max_candidates) + "): coarsen the steps or tighten the covariance");
+  std::vector<TPose3D> out;
+  out.reserve(nx * ny * nyaw);
+  auto off = [](size_t i, size_t n, double step) { return ((double)i - (double)(n - 1) / 2.0) * step; };
+  for (size_t ix = 0; ix < nx; ix++)
+    for (size_t iy = 0; iy < ny; iy++)
+      for (size_t iw = 0; iw < nyaw; iw++) {
+        TPose3D p = mean;
+        p.x = mean.x + off(ix, nx, step_xy);
+        p.y = mean.y + off(iy, ny, step_xy);
+        p.yaw = mean.yaw + off(iw, nyaw, step_yaw_rad);
+        out.push_back(p);
+      }
+  return out;
+}
+
+namespace {
+// the (global, local) layers a relocalization scores: the first pointLayerMatches entry of the first enabled
+// Matcher_Points_DistanceThreshold of an ICP block
+bool scored_layers(ICP& icp, std::string& global, std::string& local) {
+  for (const auto& m : icp.matchers()) {
+    auto* pm = dynamic_cast<mp2p_icp_hip::Matcher_Points_DistanceThreshold*>(m.get());
+    if (!pm || !pm->enabled || pm->pointLayerMatches.empty()) continue;
+    global = pm->pointLayerMatches[0].global;
+    local = pm->pointLayerMatches[0].local;
+    return true;
+  }
+  return false;
+}
+}  // namespace
+
+double LidarOdometry::reloc_score_threshold(const std::string& global_layer) const {
+  if (!reloc_opts_.score_threshold.empty()) return eval_now(reloc_opts_.score_threshold, source_.getVariableValues());
+  std::shared_ptr<HashedVoxelPointCloud> g;
+  if (gplan_) {
+    for (const auto& m : gplan_->maps)
+      if (m.name == global_layer) g = m.map;
+  } else if (plan_ && plan_->map_layer == global_layer) {
+    g = local_map_;
+  }
+  if (!g) return NAN;
+  mh_map_info mi{};
+  check(mh_map_get_info(g->handle(), &mi), "mh_map_get_info");
+  return 0.5 * (double)mi.voxel_size;
+}
+
+void LidarOdometry::relocalizeNearPose(const CPose3D& mean, const double cov[36]) {
+  if (!plan_ && !gplan_) throw std::runtime_error("LidarOdometry::relocalizeNearPose called before initialize()");
+  if (batcher_)
+    throw std::runtime_error("LidarOdometry::relocalizeNearPose: not available with an AlignBatcher (the batch protocol has no slot for "
+                             "the extra alignments of one member)");
+  for (int i = 0; i < 12; i++)
+    if (!std::isfinite(mean.T[i])) throw std::runtime_error("LidarOdometry::relocalizeNearPose: non-finite pose");
+  std::string g, l;
+  if (!scored_layers(*icp_[1], g, l))
+    throw std::runtime_error("LidarOdometry::relocalizeNearPose: the no-motion-model ICP block has no enabled Matcher_Points_DistanceThreshold "
+                             "to score candidates with");
+  // the candidate count is checked now, so that the caller can coarsen (when the defaults need a map that is not there yet: at
+  // the scan that serves the request)
+  const double thr = reloc_score_threshold(g);
+  if (std::isfinite(thr)) {
+    const double step = reloc_opts_.step_xy > 0 ? reloc_opts_.step_xy : thr;
+    (void)relocalization_grid(mean.asTPose(), cov, step, reloc_opts_.step_yaw_deg * kDeg2Rad, reloc_opts_.sigmas, reloc_opts_.max_candidates);
+  }
+  RelocRequest rq;
+  rq.mean = mean;
+  for (int i = 0; i < 36; i++) rq.cov[i] = cov[i];
+  reloc_request_ = rq;
+}
+
+void LidarOdometry::serve_relocalization(double t, ScanRecord& rec) {
+  StageTimer tt(profile_, "onLidar.2.relocalize");
+  ICP& icp = *icp_[1];
+  std::string gname, lname;
+  if (!scored_layers(icp, gname, lname)) throw std::runtime_error("LidarOdometry: relocalization: no Matcher_Points_DistanceThreshold to score with");
+  mp2p_icp_hip::metric_map_t obs, glob;
+  scan_layers(obs, glob);
+  const auto gi = glob.layers.find(gname);
+  const auto li = obs.layers.find(lname);
+  auto global = gi == glob.layers.end() ? nullptr : std::dynamic_pointer_cast<HashedVoxelPointCloud>(gi->second);
+  auto local = li == obs.layers.end() ? nullptr : std::dynamic_pointer_cast<DevicePointCloud>(li->second);
+  if (!global || !local)
+    throw std::runtime_error("LidarOdometry: relocalization: the layers '" + gname + "' / '" + lname + "' of the no-motion-model ICP block are not among this scan's");
+  const double thr = reloc_score_threshold(gname);
+  const double step = reloc_opts_.step_xy > 0 ? reloc_opts_.step_xy : thr;
+  const std::vector<TPose3D> cand = relocalization_grid(reloc_request_->mean.asTPose(), reloc_request_->cov, step,
+                                                        reloc_opts_.step_yaw_deg * kDeg2Rad, reloc_opts_.sigmas, reloc_opts_.max_candidates);
+  rec.relocalization_tried = true;
+  rec.reloc_candidates = (uint32_t)cand.size();
+  // ---- score: one launch over all candidates
+  std::vector<double> poses(12 * cand.size());
+  for (size_t c = 0; c < cand.size(); c++) {
+    const CPose3D P(cand[c]);
+    std::copy(P.T, P.T + 12, &poses[12 * c]);
+  }
+  std::vector<mh_pose_score> scores(cand.size());
+  global->prepareSearch(thr);
+  check(mh_score_poses(global->handle(), local->handle(), poses.data(), cand.size(), thr, 0.0, scores.data(), MH_MEM_HOST), "mh_score_poses");
+  // ---- rank: (n_paired descending, cost ascending, index ascending)
+  std::vector<uint32_t> order(cand.size());
+  for (size_t c = 0; c < order.size(); c++) order[c] = (uint32_t)c;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    if (scores[a].n_paired != scores[b].n_paired) return scores[a].n_paired > scores[b].n_paired;
+    return scores[a].cost < scores[b].cost;
+  });
+  order.resize(std::min<size_t>(order.size(), reloc_opts_.refine_top_k));
+  rec.reloc_ranks = order;
+  rec.reloc_best_n_paired = order.empty() ? 0 : scores[order[0]].n_paired;
+  // ---- refine the kept candidates, one after another
+  bool have = false;
+  mp2p_icp_hip::Results best;
+  for (uint32_t c : order) {
+    mp2p_icp_hip::Results res;
+    icp.clearHooks();
+    icp.align(obs, glob, cand[c], icp_params_[1], res, std::nullopt);
+    profile_["relocalize.align_calls"] += 1.0;
+    if (!have || res.quality > best.quality) {  // (ties go to the better rank)
+      best = res;
+      have = true;
+    }
+  }
+  rec.reloc_best_quality = have ? best.quality : 0.0;
+  // ---- accept
+  if (have && best.quality >= params_.min_icp_goodness) {
+    navstate_.reset();
+    seed_motion_model(t, best.optimal_tf.mean);
+    last_lidar_pose_ = best.optimal_tf.mean;
+    reloc_request_.reset();
+    rec.relocalized = true;
+  }
 }
 
 void LidarOdometry::ensure_device() {
@@ -874,6 +1147,9 @@ void LidarOdometry::reset() {
   localmap_check_removal_counter_ = 0;
   trajectory_.clear();
   records_.clear();
+  initial_localization_done_ = false;
+  reloc_request_.reset();
+  if (!loaded_maps_.empty()) restore_loaded_maps();  // (the reference's reset() runs initialize() again: the file is loaded again)
 }
 
 void LidarOdometry::updatePipelineTwistVariables(const Twist& tw) {  // :1571-1579
@@ -1517,6 +1793,24 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     return rec;
   }
 
+  // initial localization (:779-794), once, at the first observation that reaches registration
+  if (init_loc_.enabled && !initial_localization_done_) {
+    const CPose3D fixed(init_loc_.fixed_initial_pose);
+    if (init_loc_.relocalize) {  // this implementation's extension: search around the fixed pose
+      double cov[36] = {0};
+      cov[0] = init_loc_.relocalize_sigmas[0] * init_loc_.relocalize_sigmas[0];
+      cov[7] = init_loc_.relocalize_sigmas[1] * init_loc_.relocalize_sigmas[1];
+      const double syaw = init_loc_.relocalize_sigmas[2] * kDeg2Rad;
+      cov[21] = syaw * syaw;
+      relocalizeNearPose(fixed, cov);
+    } else {
+      seed_motion_model(this_obs_tim, fixed);
+    }
+    initial_localization_done_ = true;
+  }
+  // a pending relocalization request, served with a non-empty map, before the motion-model query
+  if (reloc_request_ && !map_is_empty()) serve_relocalization(this_obs_tim, rec);
+
   bool updateLocalMap = false;
   {
     StageTimer tt(profile_, "onLidar.2.navstate");
@@ -1555,16 +1849,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     size_t remaining = icp_params.maxIterations;
     mp2p_icp_hip::Results res;
     mp2p_icp_hip::metric_map_t obs, glob;
-    if (gplan_) {  // every layer the filters leave, every map (the ICP pipeline's matchers pick their pairs)
-      for (const auto& name : gplan_->alive)
-        obs.layers[name] = name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name);
-      for (const auto& m : gplan_->maps)
-        if (m.map) glob.layers[m.name] = m.map;
-    } else {
-      obs.layers[plan_->layer_for_icp] = for_icp_;
-      obs.layers[plan_->layer_for_map] = for_map_;
-      glob.layers[plan_->map_layer] = local_map_;
-    }
+    scan_layers(obs, glob);
     std::optional<StageTimer> t_icp;
     t_icp.emplace(profile_, "onLidar.3.run_icp");
     do {

@@ -110,6 +110,7 @@ struct RunOptions {
   long long time_field = -1;  // byte offset of a float32 per-point time stamp inside the 16-byte record, or -1
   long long intensity_field = -1;  // byte offset of the float32 intensity inside the record (KITTI / MulRan: 12), or -1
   std::string scan_log;       // CSV of per-scan registration times and layer / map sizes
+  std::string save_local_map;  // --save-local-map: the local maps at the end of the sequence (FILE_<k> for several sequences)
 };
 
 // what the replay leaves behind besides the trajectory: layer and map sizes (records()), optionally a per-scan CSV
@@ -169,7 +170,7 @@ void list_sequence(const std::string& seq_dir, long max_scans, std::vector<std::
 
 // one sequence, start to end; with a batcher its alignments join those of the other sequences of the process
 void run_sequence(const std::string& pipeline, const std::string& seq_dir, const std::string& out, int device, const RunOptions& opt,
-                  std::shared_ptr<mp2p_icp_hip::AlignBatcher> batcher, SequenceReport& rep) {
+                  std::shared_ptr<mp2p_icp_hip::AlignBatcher> batcher, SequenceReport& rep, const std::string& save_map = std::string()) {
   rep.seq_dir = seq_dir;
   rep.out = out;
   rep.device = device;
@@ -232,6 +233,7 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
     }
     lo.saveTrajectoryTUM(out);
     stamp("trajectory saved");
+    if (!save_map.empty()) lo.saveLocalMaps(save_map);  // (what params.local_map_updates.load_existing_local_map of a later run reads)
     rep.profile = lo.profile();
     finish_report(lo, opt, rep);
     stamp("report finished");
@@ -285,8 +287,11 @@ int main(int argc, char** argv) {
   bool print_profile = false, plan_only = false;
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
+                      "                      [--save-local-map FILE]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
+                      "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
+                      "  the pipeline's params.local_map_updates.load_existing_local_map (MOLA_LOAD_MM), and starts at initial_localization (MOLA_INITIAL_*)\n"
                       "  --devices: the sequences are spread over the listed GPUs (longest first onto the least loaded device)\n";
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -304,6 +309,7 @@ int main(int argc, char** argv) {
       else if (a == "--time-field") opt.time_field = atoll(val("--time-field").c_str());
       else if (a == "--intensity-field") opt.intensity_field = atoll(val("--intensity-field").c_str());
       else if (a == "--scan-log") opt.scan_log = val("--scan-log");
+      else if (a == "--save-local-map") opt.save_local_map = val("--save-local-map");
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
       else if (a == "--plan-only") plan_only = true;
@@ -357,7 +363,7 @@ int main(int argc, char** argv) {
     (void)mh_device_count(&n_dev);
   }
   if (N == 1) {
-    run_sequence(pipeline, seq_dirs[0], out, devices[0], opt, nullptr, reps[0]);
+    run_sequence(pipeline, seq_dirs[0], out, devices[0], opt, nullptr, reps[0], opt.save_local_map);
   } else {
     // a batcher per device slot: the sequences of a slot advance together, the slots independently of each other
     for (size_t d = 0; d < D; d++)
@@ -365,7 +371,7 @@ int main(int argc, char** argv) {
     std::vector<std::thread> th;
     for (size_t k = 0; k < N; k++)
       th.emplace_back(run_sequence, pipeline, seq_dirs[k], stem + "_" + std::to_string(k) + ".tum", devices[slot[k]], std::cref(opt),
-                      batchers[slot[k]], std::ref(reps[k]));
+                      batchers[slot[k]], std::ref(reps[k]), opt.save_local_map.empty() ? std::string() : opt.save_local_map + "_" + std::to_string(k));
     for (auto& t : th) t.join();
   }
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

@@ -86,6 +86,9 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         auto c = make_cloud(xyz); h.insertPoints(c->x.data(), c->y.data(), c->z.data(), c->size()); })
       .def("size", &HashedVoxelPointCloud::size)
       .def("voxelCount", &HashedVoxelPointCloud::voxelCount)
+      .def("className", [](const HashedVoxelPointCloud& h) { return std::string(h.className()); })
+      .def("saveToFile", &HashedVoxelPointCloud::saveToFile, py::arg("path"), py::arg("name") = "map", py::arg("remove_voxels_farther_than") = 0.f)
+      .def("loadFromFile", &HashedVoxelPointCloud::loadFromFile, py::arg("path"), py::arg("name") = "")
       // (offsets, global_idx, xyz [k, 3], d2) of mh_nn_search_radius; T: 12 values, row-major [R|t]
       .def("radiusSearch", [](const HashedVoxelPointCloud& h, py::array_t<float, py::array::c_style | py::array::forcecast> xyz,
                               std::vector<double> T, double radius, bool sorted) {
@@ -191,6 +194,8 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["map_voxel_size"] = r.map_voxel_size;
     d["layer_sizes"] = r.layer_sizes;
     d["waiting"] = r.waiting; d["ignored"] = r.ignored; d["n_sensors"] = r.n_sensors; d["sensor_labels"] = r.sensor_labels;
+    d["relocalization_tried"] = r.relocalization_tried; d["relocalized"] = r.relocalized; d["reloc_candidates"] = r.reloc_candidates;
+    d["reloc_best_n_paired"] = r.reloc_best_n_paired; d["reloc_best_quality"] = r.reloc_best_quality; d["reloc_ranks"] = r.reloc_ranks;
     return d;
   };
   py::class_<LidarOdometry> lo_class(m, "LidarOdometry", py::dynamic_attr());
@@ -281,6 +286,28 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
            py::arg("timestamp"), py::arg("range"), py::arg("fx"), py::arg("fy"), py::arg("cx"), py::arg("cy"),
            py::arg("range_units") = 0.001, py::arg("range_is_depth") = true, py::arg("sensor_pose") = std::nullopt)
       .def("localMapClasses", &LidarOdometry::localMapClasses)
+      .def("saveLocalMaps", &LidarOdometry::saveLocalMaps, py::call_guard<py::gil_scoped_release>())
+      // mean: 12 values, row-major [R|t]; cov: 36 values, row-major 6x6 in (x, y, z, yaw, pitch, roll)
+      .def("relocalizeNearPose", [](LidarOdometry& lo, std::vector<double> mean, std::vector<double> cov) {
+        if (mean.size() != 12 || cov.size() != 36) throw std::runtime_error("need 12 pose values and 36 covariance values");
+        CPose3D P; std::copy(mean.begin(), mean.end(), P.T);
+        lo.relocalizeNearPose(P, cov.data()); })
+      .def("relocalizationPending", &LidarOdometry::relocalizationPending)
+      .def("initialLocalization", [](const LidarOdometry& lo) {
+        const auto& il = lo.initialLocalization();
+        py::dict d;
+        d["enabled"] = il.enabled; d["method"] = il.method; d["relocalize"] = il.relocalize;
+        d["fixed_initial_pose"] = std::vector<double>{il.fixed_initial_pose.x, il.fixed_initial_pose.y, il.fixed_initial_pose.z,
+                                                      il.fixed_initial_pose.yaw, il.fixed_initial_pose.pitch, il.fixed_initial_pose.roll};
+        d["relocalize_sigmas"] = std::vector<double>(il.relocalize_sigmas, il.relocalize_sigmas + 3);
+        return d; })
+      .def("relocalizationOptions", [](const LidarOdometry& lo) {
+        const auto& r = lo.relocalizationOptions();
+        py::dict d;
+        d["score_threshold"] = r.score_threshold; d["step_xy"] = r.step_xy; d["step_yaw_deg"] = r.step_yaw_deg; d["sigmas"] = r.sigmas;
+        d["refine_top_k"] = r.refine_top_k; d["max_candidates"] = r.max_candidates;
+        return d; })
+      .def("loadExistingLocalMap", [](const LidarOdometry& lo) { return lo.params().load_existing_local_map; })
       .def("setIntensityInput", &LidarOdometry::setIntensityInput)
       .def("setAlignBatcher", &LidarOdometry::setAlignBatcher)
       .def("prefetch", [](py::object self, py::array xyz_any, std::optional<py::array> t_any,
@@ -387,5 +414,74 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("leave", [](AlignBatcher& b) { b.leave(); }, py::call_guard<py::gil_scoped_release>())
       .def("batches", &AlignBatcher::batches)
       .def("jobs", &AlignBatcher::jobs);
+  // ---- the local-map file on host arrays (molahip_host/local_map_file.h): a map is a dict with the keys name, class_name,
+  // params (voxel_size, max_points_per_voxel, index_mode, min_distance_between_points, ndt_max_eigen_ratio, ndt_min_points,
+  // far_voxel_metric), remove_voxels_farther_than, n_offered, xyz [n, 3] float32, src_idx [n] uint32
+  m.def("write_local_map_file", [](const std::string& path, const std::vector<py::dict>& maps) {
+    std::vector<molahip_host::LocalMapRecord> recs;
+    for (const py::dict& d : maps) {
+      molahip_host::LocalMapRecord r;
+      r.name = d["name"].cast<std::string>();
+      r.class_name = d["class_name"].cast<std::string>();
+      const py::dict p = d["params"].cast<py::dict>();
+      r.params.voxel_size = p["voxel_size"].cast<float>();
+      r.params.max_points_per_voxel = p["max_points_per_voxel"].cast<uint32_t>();
+      r.params.index_mode = p["index_mode"].cast<uint32_t>();
+      r.params.min_distance_between_points = p["min_distance_between_points"].cast<float>();
+      r.params.ndt_max_eigen_ratio = p["ndt_max_eigen_ratio"].cast<float>();
+      r.params.ndt_min_points = p["ndt_min_points"].cast<uint32_t>();
+      r.params.far_voxel_metric = p["far_voxel_metric"].cast<uint32_t>();
+      r.remove_voxels_farther_than = d["remove_voxels_farther_than"].cast<float>();
+      r.n_offered = d["n_offered"].cast<uint64_t>();
+      auto xyz = d["xyz"].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+      auto src = d["src_idx"].cast<py::array_t<uint32_t, py::array::c_style | py::array::forcecast>>();
+      if (xyz.ndim() != 2 || xyz.shape(1) != 3 || src.ndim() != 1 || src.shape(0) != xyz.shape(0))
+        throw std::runtime_error("xyz must be [n, 3] and src_idx [n]");
+      const py::ssize_t n = xyz.shape(0);
+      auto a = xyz.unchecked<2>();
+      r.x.resize(n); r.y.resize(n); r.z.resize(n);
+      for (py::ssize_t i = 0; i < n; i++) { r.x[i] = a(i, 0); r.y[i] = a(i, 1); r.z[i] = a(i, 2); }
+      r.src_idx.assign(src.data(), src.data() + n);
+      recs.push_back(std::move(r));
+    }
+    molahip_host::write_local_map_file(path, recs); });
+  m.def("read_local_map_file", [](const std::string& path) {
+    py::list out;
+    for (const auto& r : molahip_host::read_local_map_file(path)) {
+      py::dict d, p;
+      d["name"] = r.name; d["class_name"] = r.class_name;
+      p["voxel_size"] = r.params.voxel_size; p["max_points_per_voxel"] = r.params.max_points_per_voxel; p["index_mode"] = r.params.index_mode;
+      p["min_distance_between_points"] = r.params.min_distance_between_points; p["ndt_max_eigen_ratio"] = r.params.ndt_max_eigen_ratio;
+      p["ndt_min_points"] = r.params.ndt_min_points; p["far_voxel_metric"] = r.params.far_voxel_metric;
+      d["params"] = p;
+      d["remove_voxels_farther_than"] = r.remove_voxels_farther_than; d["n_offered"] = r.n_offered;
+      const py::ssize_t n = (py::ssize_t)r.x.size();
+      py::array_t<float> xyz({n, (py::ssize_t)3});
+      auto w = xyz.mutable_unchecked<2>();
+      for (py::ssize_t i = 0; i < n; i++) { w(i, 0) = r.x[i]; w(i, 1) = r.y[i]; w(i, 2) = r.z[i]; }
+      d["xyz"] = xyz;
+      d["src_idx"] = py::array_t<uint32_t>(n, r.src_idx.data());
+      out.append(d);
+    }
+    return out; });
+  m.attr("LOCAL_MAP_FILE_VERSION") = molahip_host::kLocalMapFileVersion;
+  // candidate poses of a relocalization: mean = (x, y, z, yaw, pitch, roll), cov = 36 values; returns (poses [k, 12], rows [k, 6])
+  m.def("relocalization_grid", [](std::vector<double> mean, std::vector<double> cov, double step_xy, double step_yaw_rad, double sigmas,
+                                  size_t max_candidates) {
+    if (mean.size() != 6 || cov.size() != 36) throw std::runtime_error("need 6 pose values (x y z yaw pitch roll) and 36 covariance values");
+    const TPose3D mu{mean[0], mean[1], mean[2], mean[3], mean[4], mean[5]};
+    const std::vector<TPose3D> g = mola_hip::relocalization_grid(mu, cov.data(), step_xy, step_yaw_rad, sigmas, max_candidates);
+    const py::ssize_t k = (py::ssize_t)g.size();
+    py::array_t<double> poses({k, (py::ssize_t)12}), rows({k, (py::ssize_t)6});
+    auto wp = poses.mutable_unchecked<2>();
+    auto wr = rows.mutable_unchecked<2>();
+    for (py::ssize_t i = 0; i < k; i++) {
+      const CPose3D P(g[i]);
+      for (int j = 0; j < 12; j++) wp(i, j) = P.T[j];
+      const double v[6] = {g[i].x, g[i].y, g[i].z, g[i].yaw, g[i].pitch, g[i].roll};
+      for (int j = 0; j < 6; j++) wr(i, j) = v[j];
+    }
+    return py::make_tuple(poses, rows); },
+        py::arg("mean"), py::arg("cov"), py::arg("step_xy"), py::arg("step_yaw_rad"), py::arg("sigmas") = 3.0, py::arg("max_candidates") = 65536);
   m.def("icp_pipeline_from_yaml", [](const Config& c) { auto t = icp_pipeline_from_yaml(c); return py::make_tuple(std::get<0>(t), std::get<1>(t)); });
 }
