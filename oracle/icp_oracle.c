@@ -985,6 +985,14 @@ void orc_covariance(const orc_pairs_pt2pt* pp, const orc_pairs_pt2pl* pl, const 
     memcpy(x, x0, sizeof(x)); x[j] += hh[j]; orc_pose_from_ypr(x, Tp[j]);
     memcpy(x, x0, sizeof(x)); x[j] -= hh[j]; orc_pose_from_ypr(x, Tm[j]);
   }
+  /* The central difference of the residual R l + t - q is taken on the POSE, Td[j] = Tp[j] - Tm[j] entry by entry, and applied
+   * to the point: in exact arithmetic that is (f(x + h) - f(x - h)) for every pairing.  Forming f(x + h) and f(x - h) per pairing
+   * first rounds each to an ulp of the WORLD coordinate before they cancel -- eps |t| / h per entry, 4.6e-4 at 4.1e5 m with the
+   * default step, different for every pairing: a covariance of a hundred pairings then sits several times the suite's tolerance
+   * (2e-5) away from the same difference taken in extended precision (tests/test_far_cpu.py), where this form stays inside it. */
+  double Td[6][12];
+  for (int j = 0; j < 6; j++)
+    for (int k = 0; k < 12; k++) Td[j][k] = Tp[j][k] - Tm[j][k];
   double AtA[36] = {0};
   {
     /* point-to-point block rows, thread-split with an ordered join (same scheme as the GN accumulation) */
@@ -1003,9 +1011,8 @@ void orc_covariance(const orc_pairs_pt2pt* pp, const orc_pairs_pt2pl* pl, const 
         double A[3][6];
         for (int j = 0; j < 6; j++)
           for (int r = 0; r < 3; r++) {
-            const double fp = R_(Tp[j], r, 0) * l[0] + R_(Tp[j], r, 1) * l[1] + R_(Tp[j], r, 2) * l[2] + t_(Tp[j], r);
-            const double fm = R_(Tm[j], r, 0) * l[0] + R_(Tm[j], r, 1) * l[1] + R_(Tm[j], r, 2) * l[2] + t_(Tm[j], r);
-            A[r][j] = (fp - fm) / (2.0 * hh[j]); /* the constant -q cancels */
+            const double df = R_(Td[j], r, 0) * l[0] + R_(Td[j], r, 1) * l[1] + R_(Td[j], r, 2) * l[2] + t_(Td[j], r);
+            A[r][j] = df / (2.0 * hh[j]); /* the constant -q cancels */
           }
         for (int r = 0; r < 3; r++)
           for (int a = 0; a < 6; a++)
@@ -1023,9 +1030,7 @@ void orc_covariance(const orc_pairs_pt2pt* pp, const orc_pairs_pt2pl* pl, const 
     for (int j = 0; j < 6; j++) {
       double d = 0;
       for (int r = 0; r < 3; r++) {
-        const double fp = R_(Tp[j], r, 0) * l[0] + R_(Tp[j], r, 1) * l[1] + R_(Tp[j], r, 2) * l[2] + t_(Tp[j], r);
-        const double fm = R_(Tm[j], r, 0) * l[0] + R_(Tm[j], r, 1) * l[1] + R_(Tm[j], r, 2) * l[2] + t_(Tm[j], r);
-        d += nrm[r] * (fp - fm);
+        d += nrm[r] * (R_(Td[j], r, 0) * l[0] + R_(Td[j], r, 1) * l[1] + R_(Td[j], r, 2) * l[2] + t_(Td[j], r));
       }
       A[j] = d / (2.0 * hh[j]);
     }

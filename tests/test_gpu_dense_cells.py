@@ -18,6 +18,7 @@ import dense_cases as dc
 import kbest_ref
 from mola_lidar_odometry_amd import capi
 from oracle import layers_oracle, oracle_c
+from route_tables import FAMILIES, LOOP16_CASES, LOOPW_CASES, MULTI, SEARCH, env_id
 
 pytestmark = pytest.mark.gpu
 
@@ -105,17 +106,10 @@ def _assert_same_bits(a, b, what):
 
 
 # ------------------------------------------------------------------- a. single pair, every shipped family, room and mixed
-# test_gpu_parity.py::test_every_kernel_variant_matches_the_oracle's list without the development letters (t, w, o), plus the
-# default route's launch chain (the one-launch loops: section b).  No loop starts under these switches, except under MH_MATCH=s
-# alone: the row search's loop k_icp16, 2.6 ms for these 2000 points and 16 iterations (profiles/dense_cells.md).
-FAMILIES = [{"MH_NO_LOOP16": "1"}, {"MH_MATCH": "s"}, {"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1"},
-            {"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1", "MH_NO_FUSE16": "1"}, {"MH_MATCH": "q"}, {"MH_MATCH": "p"}, {"MH_MATCH": "x"},
-            {"MH_MATCH": "q", "MH_NO_GRAPH": "1"}, {"MH_MATCH": "f"}, {"MH_MATCH": "f", "MH_NO_GRAPH": "1"}]
-SEARCH = [{}, {"MH_NO_PREV_BOUND": "1"}, {"MH_NO_QIDX": "1"}]
-
-
-def _id(env):
-    return "-".join("%s=%s" % (k[3:], v) for k, v in env.items()) or "plain"
+# FAMILIES x SEARCH: tests/route_tables.py (test_gpu_parity.py::test_every_kernel_variant_matches_the_oracle's list without the
+# development letters, plus the default route's launch chain; the one-launch loops: section b).  No loop starts under these
+# switches, except under MH_MATCH=s alone: the row search's loop k_icp16.
+_id = env_id
 
 
 @pytest.mark.parametrize("search", SEARCH, ids=_id)
@@ -142,12 +136,7 @@ def test_single_pair_small_layers(ctx, inp, dmaps, single_refs, mk, match, n, mo
 
 
 # --------------------------------------------------------------- b. the launch chain against the one-launch loops
-# (points, iterations) of the cases that let a loop run, sized from the loop times measured on the dense map
-# (profiles/dense_cells.md) so that they stay below half the 20 ms limit: k_icp16 takes 2.6 ms for 2000 points and 16 iterations;
-# k_icpw takes 1.1 ms per iteration at any of these sizes (the tower's voxel decides), 6.5 ms for six -- twelve iterations took
-# 13 ms, sixteen 18 ms, so the larger budgets run on the chain alone.
-LOOP16_CASES = [(129, 6), (2000, 16)]
-LOOPW_CASES = [(129, 6), (2000, 6), (2561, 6)]
+# LOOP16_CASES, LOOPW_CASES: tests/route_tables.py, sized from the measured loop times of profiles/dense_cells.md
 CHAIN_CASES = dc.CHAIN_CASES  # (their references pass the set-apart rule in tests/test_dense_cpu.py like every other)
 
 
@@ -240,10 +229,6 @@ def _check(r, c, o, what):
     if r["pair_counts"] == o["pair_counts"]:
         diffs += _compare_pairs(c, r, o)
     assert not diffs, (what, diffs)
-
-
-MULTI = ["two_pairs", "beside_capped", "k2", "k8", "k2_mixed", "k2_n1", "k2_n63", "k2_n64", "k2_n65", "k2_n129", "unique", "gated",
-         "rgbd", "knn16"]
 
 
 @pytest.mark.parametrize("name", MULTI)

@@ -20,6 +20,7 @@ import pytest
 from cov_cases import COV_FD_BOUND, COV_KINDS, COV_POSES, cov_inputs, scaled_gap
 from mola_lidar_odometry_amd import capi, synth
 from oracle import icp_oracle_np as onp
+from route_tables import PLANE_MATCHER_KERNELS, POINT_MATCHER_KERNELS
 
 pytestmark = pytest.mark.gpu
 
@@ -132,25 +133,7 @@ def _setenv(monkeypatch, env):
 
 
 # ---------------------------------------------------------------------------- plane weight: every kernel that runs the plane matcher
-@pytest.mark.parametrize("n,env,inner,skip", [
-    (1500, {}, 2, False),                              # k_icp16<true> (loop_stats: ran, not abandoned)
-    (1500, {}, 1, False),
-    (1500, {"MH_NO_LOOP16": "1"}, 2, False),           # k_step16<true>, streaming control
-    (5000, {"MH_NO_LOOP16": "1"}, 2, False),
-    (5000, {}, 2, False),                              # k_step16<true> (layers of 2561-8192 points take it by size)
-    (5000, {}, 1, False),
-    (5000, {"MH_NO_STEP_CHAIN": "1"}, 2, False),       # k_match16<true, false> | k_accum_both | k_solve
-    (5000, {"MH_NO_FUSE16": "1"}, 2, False),           # (no effect on an NDT layer: the row kernel never fuses its first step there)
-    (5000, {"MH_NO_STEP_CHAIN": "1", "MH_NO_FUSE16": "1"}, 1, False),
-    (10000, {}, 2, False),                             # above the step chain by size: k_match16<true, false> | k_accum_both
-    (5000, {"MH_MATCH": "p"}, 2, False),               # k_match_pl<FUSED> (its own first step) + one lane per point; k_accum_both inside
-    (5000, {"MH_MATCH": "p"}, 1, False),
-    (40000, {}, 2, False),                             # k_match_pl<FUSED> + plan / scan matcher, by size
-    (40000, {"MH_MATCH": "p"}, 1, False),
-    (5000, {"MH_MATCH": "q"}, 2, False),               # k_match_pl<FUSED> + quad matcher
-    (5000, {"MH_MATCH": "f"}, 2, False),
-    (5000, {}, 2, True),                               # matched_points = skip: both verdicts in the row kernel
-])
+@pytest.mark.parametrize("n,env,inner,skip", PLANE_MATCHER_KERNELS)   # (tests/route_tables.py: the kernel of every row)
 def test_plane_weight_through_every_plane_matcher(ctx, oracle, n, env, inner, skip, monkeypatch):
     """NDT map, weights (0.25, 3.0) on (point rows, plane rows): Matcher_Point2Plane's rows are weighted at five kernel sites
     (k_icp16<true>, k_step16<true>, k_icp16_b<true>, k_accum_both, k_match_pl's fused first step -- the `FUSED` of
@@ -172,24 +155,7 @@ def test_plane_weight_through_every_plane_matcher(ctx, oracle, n, env, inner, sk
 
 
 # ---------------------------------------------------------------------------- point weight: every family of the point matcher
-@pytest.mark.parametrize("n,env", [
-    (1500, {}),                                                              # k_icp16<false>
-    (1500, {"MH_NO_LOOP16": "1"}),                                           # k_step16<false>
-    (3000, {"MH_LOOPW": "all"}),                                             # k_icpw
-    (5000, {}),                                                              # k_step16 under streaming control
-    (5000, {"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1"}),                      # k_match16<false, FUSED> | k_solve | k_accum
-    (5000, {"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1", "MH_NO_FUSE16": "1"}),  # k_match16<false, false> | k_accum
-    (10000, {}),                                                             # fused row kernel by size
-    (20000, {}),                                                             # row kernel + k_accum by size
-    (5000, {"MH_MATCH": "f"}),                                               # k_match_flat | k_accum | k_solve
-    (40000, {}),                                                             # ... by size
-    (5000, {"MH_MATCH": "q"}),
-    (5000, {"MH_MATCH": "p"}),
-    (5000, {"MH_MATCH": "x"}),
-    (5000, {"MH_MATCH": "t"}),                                               # (development library only: tests/conftest.py)
-    (5000, {"MH_MATCH": "w"}),
-    (5000, {"MH_MATCH": "o"}),
-])
+@pytest.mark.parametrize("n,env", POINT_MATCHER_KERNELS)               # (tests/route_tables.py: the family of every row)
 @pytest.mark.parametrize("wpt", [0.25, 4.0])
 def test_point_weight_next_to_a_prior_through_every_family(ctx, oracle, n, env, wpt, monkeypatch):
     """Plain map, a prior of information diag(200, 200, 200, 2000, 2000, 2000) at the guess, weight_pt2pt in {0.25, 4}: the
