@@ -222,6 +222,46 @@ MH_API mh_status mh_map_download_ndt(const mh_map* map, float* cx, float* cy, fl
  *  - Like mh_map_build the call is synchronous about its verdict and leaves nothing in flight. */
 MH_API mh_status mh_map_restore(mh_map* map, const float* x, const float* y, const float* z, const uint32_t* src_idx, size_t n,
                                 uint64_t n_offered, int32_t mem);
+/* A whole group of key-frames inserted at once: the session map of a recorded drive built from its key-frames without K
+ * rebuilds of everything stored (K calls of mh_map_insert gather, re-sort and rebuild the stored content K times).
+ *  - Definition.  The map afterwards is bit for bit the map after
+ *        for f in 0 .. n_frames-1:  mh_map_insert(map, scan(frames[f]), frames[f].T, 0)
+ *    -- the same mh_map_download and mh_map_download_ndt bits, the same n_points / n_offered / n_voxels / n_planes and bounding
+ *    box, the same answers from every search route, the same result of a following mh_map_insert.  The source index of point i
+ *    of frame f is (n_offered before the call) + sum of n_g over g < f + i.  The cap and min_distance_between_points see the
+ *    points of earlier frames as stored ones.  There is no far removal.  (table_size is an implementation matter, as for
+ *    mh_map_restore.)
+ *  - Composition.  Each point is composed with its frame's pose as mh_map_insert composes it:
+ *    (float)(((T0*px + T1*py) + T2*pz) + T3) per row, in fp64, un-fused.
+ *  - Passes.  Frames are taken in order into passes of at most max_points_per_pass points (0: the library's default, 2^21 points
+ *    = 24 MB of staged coordinates); a frame larger than that is a pass of its own.  Each pass is one upload (host arrays are
+ *    packed into a page-locked mirror; device arrays are read in place and only the tables travel), one compose launch over all
+ *    its frames behind the stored points, and one rebuild.  By the definition the result does not depend on the pass size; a
+ *    small value exists for tests only (as mh_occmap_params::max_keys_per_pass does).
+ *  - Arrays live in `mem`: MH_MEM_HOST, MH_MEM_HOST_PINNED or MH_MEM_DEVICE (x, y, z of a frame may be NULL when its n is 0).
+ *  - Out-of-range points (|coord| / voxel_size >= 1e6 after composition) are left out and reported as ONE deferred verdict for
+ *    the call, by the protocol of mh_map_insert: mh_map_info::deferred_status until the next insertion on this map returns
+ *    MH_WARN_PREVIOUS_OUT_OF_RANGE; a verdict pending from an earlier insertion is returned by this call in the same way.
+ *  - MH_ERR_INVALID_ARGUMENT before any device work, the map untouched: a NULL map; NULL frames with n_frames > 0; a bad `mem`;
+ *    NULL arrays with n > 0; a non-finite pose entry (of an empty frame too); n_frames > MH_MAX_INSERT_FRAMES; totals beyond
+ *    mh_map_insert's limits summed over the whole call (stored + offered points >= 0x7FFFFFF0, n_offered + offered >= 0xFFFFFFF0).
+ *    (The totals check needs the stored count, so it follows the lazy read-back of the previous update's counts; nothing is
+ *    launched, and a pending verdict stays pending.)
+ *  - n_frames == 0 or only empty frames: MH_OK, nothing changes.
+ *  - A failure in a later pass (out of memory): earlier passes stay inserted and n_offered says how far the call got; the handle
+ *    stays usable.  A call that fails has not returned a verdict pending from an earlier insertion: that verdict stays pending,
+ *    together with this call's own.  Staging and scratch are reserved before the stored content is touched; should the rebuild itself run out of
+ *    memory the map reads as empty, as after a failed mh_map_insert.
+ *  - The call returns once the caller's arrays may be reused (device arrays: once the last compose launch has read them); counts
+ *    and verdict travel lazily, as for mh_map_insert. */
+#define MH_MAX_INSERT_FRAMES 1048576
+typedef struct {
+  const float *x, *y, *z; /* n points, vehicle frame, arrays in `mem`; may be NULL when n == 0 */
+  uint64_t n;
+  double T[12];           /* row-major 3x4, the key-frame's pose */
+} mh_map_frame;           /* 128 bytes */
+MH_API mh_status mh_map_insert_frames(mh_map* map, const mh_map_frame* frames, size_t n_frames, int32_t mem,
+                                      uint64_t max_points_per_pass);
 
 /* ------------------------------------------------------------------------------------------------
  * Scan: the local point layer handed to align() ("decimated_for_icp", lidar3d-default.yaml:204),

@@ -237,6 +237,12 @@ class OccMapInfo(C.Structure):
                 ("n_left_out", C.c_uint64), ("n_keys", C.c_uint64), ("n_passes", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class MapFrame(C.Structure):
+    """mh_map_frame: one key-frame of mh_map_insert_frames (arrays of n points in the vehicle frame + its pose)."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p), ("n", C.c_uint64), ("T", C.c_double * 12)]
+
+
+MAX_INSERT_FRAMES = 1048576  # MH_MAX_INSERT_FRAMES
 OCC_COUNTED, OCC_ONCE = 0, 1  # mh_occmap_params::update_rule
 TS_NONE, TS_MIDDLE_IS_ZERO, TS_EARLIEST_IS_ZERO = 0, 1, 2
 DECIMATE_FIRST_POINT, DECIMATE_CLOSEST_TO_AVERAGE = 0, 1
@@ -266,6 +272,7 @@ _SIGNATURES = {
     "mh_map_download": (C.c_int32, [C.c_void_p, _FP, _FP, _FP, _UP, C.POINTER(C.c_int32), _UP, _UP]),
     "mh_map_download_ndt": (C.c_int32, [C.c_void_p, _FP, _FP, _FP, _FP, _FP, _FP, _UP]),
     "mh_map_restore": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_int32]),
+    "mh_map_insert_frames": (C.c_int32, [C.c_void_p, C.POINTER(MapFrame), C.c_size_t, C.c_int32, C.c_uint64]),
     "mh_scan_create": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32,
                                    C.POINTER(C.c_void_p)]),
     "mh_scan_update": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
@@ -509,6 +516,33 @@ class Map:
         if st == MH_WARN_PREVIOUS_OUT_OF_RANGE:  # inserted; the PREVIOUS update left out-of-range points out (not a failure)
             import warnings
             warnings.warn(lib().mh_last_error_string().decode(errors="replace"), RuntimeWarning, stacklevel=2)
+            return self
+        _chk(st)
+        return self
+
+    def insert_frames(self, frames, max_points_per_pass=0):
+        """A group of key-frames at once (mh_map_insert_frames): `frames` is a sequence of (xyz [n, 3], T); the result is bit for
+        bit that of insert() called for every frame in order, without far removal."""
+        keep = [(_soa(xyz), _T12(T)) for xyz, T in frames]
+        arr = (MapFrame * max(len(keep), 1))()
+        for e, ((x, y, z), T) in zip(arr, keep):
+            e.x, e.y, e.z, e.n = _vp(x), _vp(y), _vp(z), len(x)
+            e.T[:] = T.tolist()
+        return self._frames_status(lib().mh_map_insert_frames(self._h, arr, len(keep), MEM_HOST, int(max_points_per_pass)))
+
+    def insert_frames_device(self, frames, max_points_per_pass=0):
+        """The same from device arrays: `frames` is a sequence of (x_ptr, y_ptr, z_ptr, n, T)."""
+        frames = list(frames)
+        arr = (MapFrame * max(len(frames), 1))()
+        for e, (xp, yp, zp, n, T) in zip(arr, frames):
+            e.x, e.y, e.z, e.n = xp, yp, zp, int(n)
+            e.T[:] = _T12(T).tolist()
+        return self._frames_status(lib().mh_map_insert_frames(self._h, arr, len(frames), MEM_DEVICE, int(max_points_per_pass)))
+
+    def _frames_status(self, st):
+        if st == MH_WARN_PREVIOUS_OUT_OF_RANGE:  # inserted; the PREVIOUS update left out-of-range points out (not a failure)
+            import warnings
+            warnings.warn(lib().mh_last_error_string().decode(errors="replace"), RuntimeWarning, stacklevel=3)
             return self
         _chk(st)
         return self

@@ -240,6 +240,7 @@ struct mh_map {
   mutable uint64_t n_points = 0, n_voxels = 0, n_records = 0, n_planes = 0;
   uint64_t n_offered = 0, table_size = 0;
   mh::DevBuf merge;  // mh_map_insert staging: x | y | z | src of (stored + new) points
+  mh::PinnedBuf h_frames;  // mh_map_insert_frames: page-locked mirror of one pass's upload (points | prefix array | frame table)
   mutable float bbox_min[3] = {0, 0, 0}, bbox_max[3] = {0, 0, 0};
   uint32_t* h_counts = nullptr;          // pinned [16]: what k_scatter / k_ndt_stats left in the device counters
   hipEvent_t ev_counts = nullptr;        // recorded behind that copy: "the last (re)build is complete"

@@ -21,6 +21,8 @@
 
 using namespace mh;
 
+#include "mh_k_frames.h"
+
 namespace {
 
 __device__ __forceinline__ int voxel_index(float c, float inv_vs, uint32_t trunc) {
@@ -544,6 +546,7 @@ mh_status mh_map_destroy(mh_map* m) {
   m->vox_first.release();
   m->vox_count.release();
   m->merge.release();
+  m->h_frames.release();
   m->pts_q.release();
   delete m;
   return MH_OK;
@@ -699,6 +702,122 @@ mh_status mh_map_insert(mh_map* m, const mh_scan* scan, const double T[12], floa
   MH_TRY(map_build_device(sw, m, s, mx, my, mz, msrc, total, evict, n_old, fused_collect));
   m->n_offered += n_new;
   if (prev_out_of_range)  // a status of its own, not a failure (a caller must be able to tell "inserted" from "not inserted")
+    return fail(MH_WARN_PREVIOUS_OUT_OF_RANGE, "the PREVIOUS update of this map held points whose voxel index exceeds the +-2^20 range of the "
+                                               "packed key (|coord|/voxel_size must be < 1e6); they were left out.  This call's insertion HAS been performed");
+  return MH_OK;
+}
+
+// The library's own pass size (max_points_per_pass == 0): 2 M points are 24 MB of staged coordinates.
+constexpr uint64_t kFramesPassPoints = 1ull << 21;
+
+mh_status mh_map_insert_frames(mh_map* m, const mh_map_frame* frames, size_t n_frames, int32_t mem, uint64_t max_points_per_pass) {
+  MH_REQUIRE(m, "null map");
+  MH_REQUIRE(n_frames == 0 || frames, "null frames");
+  MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE || mem == MH_MEM_HOST_PINNED, "bad mem space");
+  MH_REQUIRE(n_frames <= MH_MAX_INSERT_FRAMES, "too many frames");
+  uint64_t sum = 0;
+  for (size_t f = 0; f < n_frames; f++) {
+    const mh_map_frame& fr = frames[f];
+    MH_REQUIRE(fr.n == 0 || (fr.x && fr.y && fr.z), "null point arrays");
+    MH_REQUIRE(fr.n < 0x7FFFFFF0ull, "too many points");
+    for (int i = 0; i < 12; i++) MH_REQUIRE(isfinite(fr.T[i]), "non-finite pose");
+    sum += fr.n;  // (2^20 frames of less than 2^31 points: no overflow)
+  }
+  if (sum == 0) return MH_OK;
+  const Switches sw = read_switches();
+  mh_ctx* ctx = m->ctx;
+  MH_TRY(set_device(ctx));
+  MH_TRY(map_resolve_counts(m));
+  // mh_map_insert's limits, for the call as a whole (every offered point kept is the bound the host knows)
+  MH_REQUIRE(m->n_points + sum < 0x7FFFFFF0ull && m->n_offered + sum < 0xFFFFFFF0ull, "too many points");
+  // the protocol of mh_map_insert: the previous update's verdict is reported by this call, after its own insertion; the
+  // verdicts of this call's passes collect in deferred_error (map_resolve_counts between the passes) and stay there as ONE.
+  // A call that fails in a pass has not reported the previous verdict: it is put back, so the next insert still does.
+  const bool prev_out_of_range = m->deferred_error != MH_OK;
+  m->deferred_error = MH_OK;
+  struct KeepVerdict {
+    mh_map* m;
+    bool pending;
+    ~KeepVerdict() { if (pending) m->deferred_error = MH_ERR_OUT_OF_RANGE; }
+  } keep{m, prev_out_of_range};
+  hipStream_t s = ctx->stream;
+  const uint64_t budget = max_points_per_pass ? max_points_per_pass : kFramesPassPoints;
+  const uint32_t ndt = m->params.ndt_max_eigen_ratio > 0.f ? 1u : 0u;
+  const bool staged = mem != MH_MEM_DEVICE;  // host arrays travel through the mirror; device arrays are read in place
+  size_t f0 = 0;
+  while (f0 < n_frames) {
+    size_t f1 = f0;
+    uint64_t P = 0;  // frames in order while they fit; a frame larger than the budget is a pass of its own
+    while (f1 < n_frames && (P == 0 || P + frames[f1].n <= budget)) P += frames[f1++].n;
+    const size_t nf = f1 - f0;
+    if (P == 0) break;  // (only empty frames were left)
+    MH_TRY(map_resolve_counts(m));  // the previous pass's counts; the mirror and the staging are free again behind them
+    const size_t n_old = m->n_points, total = n_old + P;
+    // upload layout: [x | y | z of the pass's points (host arrays only)] prefix array [nf + 1] | frame table [nf]
+    const size_t pstride = staged ? ((P * sizeof(float) + 255) / 256) * 256 : 0;
+    const size_t off_start = 3 * pstride;
+    const size_t off_table = off_start + (((nf + 1) * sizeof(uint32_t) + 255) / 256) * 256;
+    const size_t up_bytes = off_table + nf * sizeof(FrameSrc);
+    const size_t stride = ((total * sizeof(float) + 255) / 256) * 256;
+    // everything that can be reserved without touching the stored content, first: running out of memory here leaves the
+    // earlier passes inserted and the map as it is
+    MH_TRY(m->h_frames.reserve(up_bytes));
+    MH_TRY(ctx->staging.reserve(up_bytes));
+    MH_TRY(m->merge.reserve(4 * stride));
+    MH_TRY(m->build_e.reserve(total * sizeof(uint32_t) + 64));
+    MH_TRY(m->build_a.reserve((2 * total + P) * sizeof(unsigned long long)));
+    MH_TRY(m->build_b.reserve((2 * total + P) * sizeof(uint32_t)));
+    MH_TRY(m->build_c.reserve(2 * total * sizeof(uint32_t)));
+    MH_TRY(m->build_d.reserve(2 * total * sizeof(uint32_t)));
+    char* h = m->h_frames.as<char>();
+    char* d = ctx->staging.as<char>();
+    uint32_t* h_start = (uint32_t*)(h + off_start);
+    FrameSrc* h_tab = (FrameSrc*)(h + off_table);
+    uint64_t at = 0;
+    for (size_t k = 0; k < nf; k++) {
+      const mh_map_frame& fr = frames[f0 + k];
+      h_start[k] = (uint32_t)at;
+      FrameSrc& e = h_tab[k];
+      if (staged) {
+        if (fr.n) {
+          memcpy(h + at * sizeof(float), fr.x, fr.n * sizeof(float));
+          memcpy(h + pstride + at * sizeof(float), fr.y, fr.n * sizeof(float));
+          memcpy(h + 2 * pstride + at * sizeof(float), fr.z, fr.n * sizeof(float));
+        }
+        e.x = (const float*)d + at;
+        e.y = (const float*)(d + pstride) + at;
+        e.z = (const float*)(d + 2 * pstride) + at;
+      } else {
+        e.x = fr.x; e.y = fr.y; e.z = fr.z;
+      }
+      for (int i = 0; i < 12; i++) e.T[i] = fr.T[i];
+      at += fr.n;
+    }
+    h_start[nf] = (uint32_t)at;
+    MH_HIP(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, s));  // the pass's one upload
+    char* base = m->merge.as<char>();
+    float *mx = (float*)base, *my = (float*)(base + stride), *mz = (float*)(base + 2 * stride);
+    uint32_t* msrc = (uint32_t*)(base + 3 * stride);
+    if (m->n_voxels)
+      hipLaunchKernelGGL(k_gather_stored, dim3(nblk(m->n_voxels, 128)), dim3(128), 0, s, m->pts.as<float4>(),
+                         m->vox_first.as<uint32_t>(), m->vox_count.as<uint32_t>(), (uint32_t)m->n_voxels, ndt, mx, my, mz, msrc);
+    hipLaunchKernelGGL(k_compose_frames, dim3(nblk(P, 256)), dim3(256), 0, s, (const uint32_t*)(d + off_start),
+                       (const FrameSrc*)(d + off_table), (uint32_t)nf, (uint32_t)P, (uint32_t)m->n_offered, (uint32_t)n_old, mx, my,
+                       mz, msrc);
+    mh_status st = MH_OK;
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) st = fail(MH_ERR_HIP, "mh_map_insert_frames: launch failed: %s", hipGetErrorString(e));
+    if (st == MH_OK) st = map_build_device(sw, m, s, mx, my, mz, msrc, total, nullptr, n_old);
+    if (st != MH_OK) {  // (nothing may still read the mirror when the next call fills it)
+      (void)mh::wait_stream(s);
+      return st;
+    }
+    m->n_offered += P;
+    f0 = f1;
+  }
+  // device arrays are the caller's again once the last compose launch has read them
+  if (!staged) MH_HIP(mh::wait_stream(s));
+  keep.pending = false;  // (reported right here)
+  if (prev_out_of_range)
     return fail(MH_WARN_PREVIOUS_OUT_OF_RANGE, "the PREVIOUS update of this map held points whose voxel index exceeds the +-2^20 range of the "
                                                "packed key (|coord|/voxel_size must be < 1e6); they were left out.  This call's insertion HAS been performed");
   return MH_OK;

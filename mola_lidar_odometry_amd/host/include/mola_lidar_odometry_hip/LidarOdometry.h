@@ -18,8 +18,16 @@
 // LidarOdometry.cpp:2222-2230) -- finds the pose in the map from a coarse one: a grid of candidates scored on the device in one
 // launch (mh_score_poses), the best few refined by ICP.
 //
+// Key-frames of the session (params.simplemap; the role of the reference's simplemap, :1117-1138, 1209-1296): with
+// simplemap.generate the scans that are far enough from the key-frames taken so far are kept on the host -- pose, covariance,
+// twist and the layers their FilterMerge steps merge (not the raw observation: that layer is what a local-map key-frame merges,
+// and it is 10-50 times smaller) -- and saved to a key-frame file (molahip_host/keyframe_file.h); build_session_maps() turns them
+// into the maps of the WHOLE drive, one mh_map_insert_frames per map, in the format load_existing_local_map loads.  One
+// deliberate difference: the reference stores the first scan even with generate: false (:817-824); here nothing is stored
+// unless generate is on.
+//
 // Host code here is control logic only; every point touches the GPU through include/molahip.h.  What is NOT here:
-// MOLA module plumbing, IMU/GNSS/wheel inputs, simplemap generation, visualisation, ROS.
+// MOLA module plumbing, IMU/GNSS/wheel inputs, MRPT .simplemap serialisation, visualisation, ROS.
 #pragma once
 #include <map>
 #include <memory>
@@ -28,6 +36,7 @@
 #include <string>
 #include <vector>
 
+#include "molahip_host/keyframe_file.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 
 namespace mola_hip {
@@ -99,6 +108,50 @@ class SearchablePoseList {
   std::vector<CPose3D> poses_;
 };
 
+// The key-frames of a session and the distance checker that decides them (state_.distance_checker_simplemap,
+// LidarOdometry.cpp:1070-1071, 1117-1138), host logic only.  measure_from_last_kf_only: distances are measured from the last
+// key-frame; otherwise from the closest of all (SearchablePoseList).  The rule, per scan that reached registration:
+//   - the first scan (no ICP: it becomes the map) is a key-frame with points; the checker is not touched (:817-824);
+//   - a scan with a good ICP is a key-frame iff it is the first pose in the checker, or its translation from the closest (or
+//     last) key-frame exceeds min_translation [m], or its rotation exceeds min_rotation [deg]; it then enters the checker;
+//   - with add_non_keyframes_too every other scan with a good ICP is stored without points;
+//   - a scan with a bad ICP is not stored.
+// Unlike the local-map rule neither a motion model nor local_map_updates.enabled is asked for.
+class KeyFrameStore {
+ public:
+  struct Verdict {
+    bool stored = false, keyframe = false;  // keyframe: stored with points
+  };
+  explicit KeyFrameStore(bool measure_from_last_kf_only = false) : last_only_(measure_from_last_kf_only) {}
+  Verdict decide(bool first_scan, bool icp_good, const CPose3D& pose, double min_translation, double min_rotation_deg,
+                 bool add_non_keyframes_too);
+  void add(molahip_host::KeyFrame f) { set_.frames.push_back(std::move(f)); }
+  // the frames (and the target maps they name); reset(): forget the checker and start from `initial` (a loaded file's content)
+  const molahip_host::KeyFrameSet& set() const { return set_; }
+  void setTargets(std::vector<molahip_host::KeyFrameTarget> maps) { set_.maps = std::move(maps); }
+  void reset(const molahip_host::KeyFrameSet& initial = {});
+  bool measureFromLastOnly() const { return last_only_; }
+
+ private:
+  bool last_only_;
+  SearchablePoseList all_;
+  std::optional<CPose3D> last_;
+  molahip_host::KeyFrameSet set_;
+};
+
+// The maps of the whole drive from its key-frames: for every target map of the header a new map of the recorded class and
+// parameters (mp2p_icp_hip::make_local_map), then ONE insertFrames of that map's layers in frame order, then step order;
+// returned as the records saveLocalMaps() writes (remove_voxels_farther_than is the recorded one: what a run that loads the
+// file and goes on mapping applies).  A header that names a CVoxelMap is refused: an occupancy map has no snapshot (recording
+// such a plan is allowed, building from it is not).  max_points_per_pass: mh_map_insert_frames' (0 = the library's).
+std::vector<molahip_host::LocalMapRecord> build_session_maps(const molahip_host::KeyFrameSet& frames, std::shared_ptr<DeviceContext> ctx = nullptr,
+                                                             uint64_t max_points_per_pass = 0);
+std::vector<molahip_host::LocalMapRecord> build_session_maps(const std::string& keyframe_file, std::shared_ptr<DeviceContext> ctx = nullptr,
+                                                             uint64_t max_points_per_pass = 0);
+// ... written as a version-1 local-map file (write_local_map_file): what load_existing_local_map loads
+void build_session_map_file(const molahip_host::KeyFrameSet& frames, const std::string& local_map_file, std::shared_ptr<DeviceContext> ctx = nullptr,
+                            uint64_t max_points_per_pass = 0);
+
 // The grouping rule of a multi-LiDAR rig (LidarOdometry.cpp:664-689, 702-713), host logic only: the latest observation of
 // every label waits until `lidar_count` labels are present; the group is then the waiting observations within
 // `max_time_offset` of the one that completed it, in byte-wise label order (the order of the reference's std::map), and the
@@ -160,6 +213,18 @@ class LidarOdometry {
     // the first good alignment with a motion model is a key-frame merged into the loaded map (multi-session mapping).  The rule
     // "bad ICP while the trajectory holds one pose: clear the map and start again" (:1148-1158) is kept and CAN discard a loaded map.
     std::string load_existing_local_map;
+    // the simplemap: block (reference LidarOdometry.h:280-332), same keys.  The two min_* are formulas like local_map_updates'.
+    // load_existing_simple_map names a key-frame file (molahip_host/keyframe_file.h) whose frames the store starts with.  New
+    // frames go under the file's header: its map names are held against the pipeline's at initialize(), its classes and
+    // mh_map_params when the maps exist (the scan that makes them throws if they differ); its remove_voxels_farther_than stays;
+    // generate_lazy_load_scan_files: true is refused at initialize(); save_gnss_max_age is read and ignored (no GNSS input).
+    struct SimpleMapOptions {
+      bool generate = false;
+      double min_translation_between_keyframes = 1.0, min_rotation_between_keyframes = 30.0;  // [m] [deg] formulas
+      bool measure_from_last_kf_only = false, add_non_keyframes_too = false, generate_lazy_load_scan_files = false;
+      double save_gnss_max_age = 1.0;
+      std::string save_final_map_to_file, load_existing_simple_map;
+    } simplemap;
     void load_from(const Config& c);
   };
   // the initial_localization: block of the pipeline file (yaml:147-151; :779-794).  enabled: at the first observation that
@@ -216,6 +281,8 @@ class LidarOdometry {
     uint32_t reloc_candidates = 0, reloc_best_n_paired = 0;
     double reloc_best_quality = 0;
     std::vector<uint32_t> reloc_ranks;
+    // params.simplemap.generate: this scan is stored in the key-frame store (simplemap_frame), with its points (simplemap_keyframe)
+    bool simplemap_keyframe = false, simplemap_frame = false;
   };
 
   // ctx == nullptr: the process-wide default device context, taken at initialize()
@@ -289,6 +356,10 @@ class LidarOdometry {
   // Every local map of the plan, by name, into one file (molahip_host/local_map_file.h); throws before the first key-frame
   // (no map yet) and for a plan with a CVoxelMap (an occupancy map has no snapshot).
   void saveLocalMaps(const std::string& path) const;
+  // The key-frames stored so far (empty unless params.simplemap.generate, or a load_existing_simple_map file was given), and
+  // their file.  The destructor writes params.simplemap.save_final_map_to_file when that is set and generate is on.
+  const molahip_host::KeyFrameSet& keyFrames() const { return kf_store_.set(); }
+  void saveKeyFrames(const std::string& path) const;
   // The role of mola::Relocalization::relocalize_near_pose_pdf: `mean` with covariance `cov` (6x6 row-major, (x, y, z, yaw, pitch,
   // roll)) is where the vehicle is believed to be in the map frame.  The request is served by the next observation that reaches
   // registration with a non-empty map, after its filter passes and before the motion-model query:
@@ -379,6 +450,9 @@ class LidarOdometry {
   void scan_layers(mp2p_icp_hip::metric_map_t& obs, mp2p_icp_hip::metric_map_t& glob) const;  // what this scan's ICP aligns
   void serve_relocalization(double t, ScanRecord& rec);
   double reloc_score_threshold(const std::string& global_layer) const;  // NaN while the searched map is not there
+  void store_keyframe(ScanRecord& rec, bool first_scan, bool icp_good, const double* cov);  // params.simplemap.generate
+  std::vector<molahip_host::KeyFrameTarget> keyframe_targets() const;  // the plan's maps as the key-frame file's header names them
+  void check_loaded_keyframe_targets(const std::vector<molahip_host::KeyFrameTarget>& plan) const;  // throws on another class or mh_map_params
   void resolve_map_counts() const;  // fills n_map_points / n_map_voxels of the records that still wait for them
   bool map_is_empty();              // local_map_->empty() without a device round trip once the map is known to hold points
 
@@ -436,6 +510,9 @@ class LidarOdometry {
   InitialLocalization init_loc_;
   RelocalizationOptions reloc_opts_;
   std::vector<molahip_host::LocalMapRecord> loaded_maps_;  // load_existing_local_map, read at initialize()
+  KeyFrameStore kf_store_;
+  molahip_host::KeyFrameSet loaded_keyframes_;  // load_existing_simple_map, read at initialize()
+  bool kf_targets_known_ = false;               // the header's target maps are final once the maps exist (their $f{} formulas)
   bool initial_localization_done_ = false;
   struct RelocRequest {
     CPose3D mean;

@@ -225,6 +225,12 @@ struct RadiusResults {
   std::vector<float> gx, gy, gz, errSq;
   uint32_t maxPerQuery = 0;
 };
+// one key-frame of insertFrames: a host layer in the vehicle frame and the pose it was taken at
+struct PosedFrame {
+  const float *x = nullptr, *y = nullptr, *z = nullptr;
+  size_t n = 0;
+  CPose3D pose;
+};
 // mola::HashedVoxelPointCloud stand-in, device resident (NearestNeighborsCapable role only)
 class HashedVoxelPointCloud : public Layer {
  public:
@@ -237,6 +243,9 @@ class HashedVoxelPointCloud : public Layer {
   virtual void insertPoints(const float* x, const float* y, const float* z, size_t n);  // keeps a host copy, rebuilds
   // FilterMerge + insertPointCloud + far-voxel removal, all on the device (mh_map_insert; lidar3d-default.yaml:362-368)
   virtual void insertPointCloud(const DevicePointCloud& pc, const CPose3D& robot_pose, float remove_voxels_farther_than);
+  // a whole group of key-frames at once (mh_map_insert_frames): bit for bit what insertPointCloud(frame, pose, 0) gives when
+  // called for every frame in order, with one rebuild per pass instead of one per frame.  max_points_per_pass 0: the library's.
+  virtual void insertFrames(const std::vector<PosedFrame>& frames, uint64_t max_points_per_pass = 0);
   virtual void clear();
   virtual size_t size() const;
   virtual size_t voxelCount() const;
@@ -286,6 +295,7 @@ class CVoxelMap : public HashedVoxelPointCloud {
   void setPoints(const float* x, const float* y, const float* z, size_t n) override;     // (points without a pose they were
   void insertPoints(const float* x, const float* y, const float* z, size_t n) override;  //  seen from are no input of this map: both throw)
   void insertPointCloud(const DevicePointCloud& pc, const CPose3D& robot_pose, float remove_voxels_farther_than) override;
+  void insertFrames(const std::vector<PosedFrame>& frames, uint64_t max_points_per_pass = 0) override;  // throws: an occupancy map is updated by ray tracing
   void clear() override;
   size_t size() const override;
   size_t voxelCount() const override;

@@ -298,6 +298,21 @@ void HashedVoxelPointCloud::insertPointCloud(const DevicePointCloud& pc, const C
   check(st, "mh_map_insert");
 }
 
+void HashedVoxelPointCloud::insertFrames(const std::vector<PosedFrame>& frames, uint64_t max_points_per_pass) {
+  std::vector<mh_map_frame> f(frames.size());
+  for (size_t k = 0; k < frames.size(); k++) {
+    f[k].x = frames[k].x; f[k].y = frames[k].y; f[k].z = frames[k].z;
+    f[k].n = frames[k].n;
+    std::copy(frames[k].pose.T, frames[k].pose.T + 12, f[k].T);
+  }
+  const mh_status st = mh_map_insert_frames(map_, f.data(), f.size(), MH_MEM_HOST, max_points_per_pass);
+  if (st == MH_WARN_PREVIOUS_OUT_OF_RANGE) {  // these frames ARE in the map; an earlier update lost its wild points: log, go on
+    fprintf(stderr, "[molahip] warning: %s\n", mh_last_error_string());
+    return;
+  }
+  check(st, "mh_map_insert_frames");
+}
+
 void HashedVoxelPointCloud::clear() { check(mh_map_build(map_, nullptr, nullptr, nullptr, 0, MH_MEM_HOST), "mh_map_build"); }
 
 RadiusResults HashedVoxelPointCloud::radiusSearch(const DevicePointCloud& queries, const CPose3D& T, double radius, bool sorted) const {
@@ -411,6 +426,10 @@ float CVoxelMap::searchVoxelSize() const {
 void CVoxelMap::insertPointCloud(const DevicePointCloud& pc, const CPose3D& robot_pose, float remove_voxels_farther_than) {
   check(mh_occmap_insert(occ_, pc.handle(), robot_pose.T, remove_voxels_farther_than), "mh_occmap_insert");
   prepareSearch(0.0);
+}
+void CVoxelMap::insertFrames(const std::vector<PosedFrame>&, uint64_t) {
+  throw std::runtime_error("CVoxelMap::insertFrames: an occupancy map is updated by ray tracing from the pose each scan was seen from "
+                           "(insertPointCloud), not by inserting point layers; it has no batched insertion");
 }
 void CVoxelMap::clear() {
   check(mh_occmap_clear(occ_), "mh_occmap_clear");

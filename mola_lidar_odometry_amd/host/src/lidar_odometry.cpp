@@ -182,6 +182,87 @@ void SearchablePoseList::removeAllFartherThan(const CPose3D& p, double max_dist)
   poses_.swap(kept);
 }
 
+// ================================================================== key-frames of the session
+KeyFrameStore::Verdict KeyFrameStore::decide(bool first_scan, bool icp_good, const CPose3D& pose, double min_translation,
+                                             double min_rotation_deg, bool add_non_keyframes_too) {
+  Verdict v;
+  if (first_scan) {  // (:817-824: a key-frame with its points; the checker is not touched)
+    v.stored = v.keyframe = true;
+    return v;
+  }
+  if (!icp_good) return v;
+  bool is_first;
+  CPose3D d;
+  if (last_only_) {
+    is_first = !last_.has_value();
+    if (!is_first) d = pose - *last_;
+  } else {
+    std::tie(is_first, d) = all_.check(pose);
+  }
+  const bool enough = is_first || d.translationNorm() > min_translation || d.rotationAngle() > min_rotation_deg * kDeg2Rad;
+  v.keyframe = enough;
+  v.stored = enough || add_non_keyframes_too;
+  if (enough) {
+    if (last_only_) last_ = pose;
+    else all_.insert(pose);
+  }
+  return v;
+}
+
+void KeyFrameStore::reset(const molahip_host::KeyFrameSet& initial) {
+  all_.clear();
+  last_.reset();
+  set_ = initial;
+}
+
+std::vector<molahip_host::LocalMapRecord> build_session_maps(const molahip_host::KeyFrameSet& set, std::shared_ptr<DeviceContext> ctx,
+                                                             uint64_t max_points_per_pass) {
+  for (const auto& t : set.maps) {
+    if (t.class_name == "CVoxelMap")
+      throw std::runtime_error("build_session_maps: target map '" + t.name + "' is a '" + t.class_name + "': an occupancy map has no snapshot, so "
+                               "no session map can be built from its key-frames (HashedVoxelPointCloud, NDT and SparseTreesPointCloud can)");
+    if (!molahip_host::local_map_class_known(t.class_name))
+      throw std::runtime_error("build_session_maps: target map '" + t.name + "' is of the unknown class '" + t.class_name +
+                               "' (HashedVoxelPointCloud, NDT and SparseTreesPointCloud can be built)");
+  }
+  if (!ctx) ctx = DeviceContext::Default();
+  std::vector<molahip_host::LocalMapRecord> out;
+  for (size_t k = 0; k < set.maps.size(); k++) {
+    const auto& t = set.maps[k];
+    molahip_host::LocalMapRecord empty;
+    empty.name = t.name;
+    empty.class_name = t.class_name;
+    empty.params = t.params;
+    empty.remove_voxels_farther_than = t.remove_voxels_farther_than;
+    auto map = mp2p_icp_hip::make_local_map(empty, ctx);
+    std::vector<mp2p_icp_hip::PosedFrame> frames;
+    for (const auto& f : set.frames) {
+      if (!f.has_points) continue;
+      for (const auto& l : f.layers) {  // frame order, then step order
+        if (l.map_index != k) continue;
+        mp2p_icp_hip::PosedFrame pf;
+        pf.x = l.x.data(); pf.y = l.y.data(); pf.z = l.z.data();
+        pf.n = l.x.size();
+        std::copy(f.pose, f.pose + 12, pf.pose.T);
+        frames.push_back(pf);
+      }
+    }
+    map->insertFrames(frames, max_points_per_pass);
+    out.push_back(map->snapshot(t.name, t.remove_voxels_farther_than));
+  }
+  return out;
+}
+
+std::vector<molahip_host::LocalMapRecord> build_session_maps(const std::string& keyframe_file, std::shared_ptr<DeviceContext> ctx,
+                                                             uint64_t max_points_per_pass) {
+  return build_session_maps(molahip_host::read_keyframe_file(keyframe_file), std::move(ctx), max_points_per_pass);
+}
+
+void build_session_map_file(const molahip_host::KeyFrameSet& frames, const std::string& local_map_file, std::shared_ptr<DeviceContext> ctx,
+                            uint64_t max_points_per_pass) {
+  molahip_host::write_local_map_file(local_map_file, build_session_maps(frames, std::move(ctx), max_points_per_pass));
+}
+
 // ================================================================== parameters
 void LidarOdometry::Params::load_from(const Config& c) {
   auto num = [&](const Config& n, const char* k, double& v) { if (n.has(k)) v = to_double(n[k].asString()); };
@@ -209,6 +290,26 @@ void LidarOdometry::Params::load_from(const Config& c) {
       if (f.size() >= 2 && (f.front() == '"' || f.front() == '\'') && f.back() == f.front()) f = f.substr(1, f.size() - 2);  // (${MOLA_LOAD_MM|""})
       load_existing_local_map = f;
     }
+  }
+  simplemap = SimpleMapOptions();
+  if (c.has("simplemap")) {
+    const Config& m = c["simplemap"];
+    auto text = [&](const char* k, std::string& v) {
+      if (!m.has(k) || m[k].isNull()) return;
+      std::string f = m[k].asString();
+      if (f.size() >= 2 && (f.front() == '"' || f.front() == '\'') && f.back() == f.front()) f = f.substr(1, f.size() - 2);  // (${MOLA_LOAD_SM|""})
+      v = f;
+    };
+    flag(m, "generate", simplemap.generate);
+    // DECLARE_PARAMETER_IN_OPT: formulas over wx,wy,wz and ESTIMATED_SENSOR_MAX_RANGE (yaml:71-72), realised with local_map_updates'
+    parameterFromConfig(m, "min_translation_between_keyframes", &simplemap.min_translation_between_keyframes, false);
+    parameterFromConfig(m, "min_rotation_between_keyframes", &simplemap.min_rotation_between_keyframes, false);
+    flag(m, "measure_from_last_kf_only", simplemap.measure_from_last_kf_only);
+    flag(m, "add_non_keyframes_too", simplemap.add_non_keyframes_too);
+    flag(m, "generate_lazy_load_scan_files", simplemap.generate_lazy_load_scan_files);
+    num(m, "save_gnss_max_age", simplemap.save_gnss_max_age);  // (read and ignored: there is no GNSS input)
+    text("save_final_map_to_file", simplemap.save_final_map_to_file);
+    text("load_existing_simple_map", simplemap.load_existing_simple_map);
   }
   if (c.has("adaptive_threshold")) {
     const Config& a = c["adaptive_threshold"];
@@ -740,6 +841,13 @@ LidarOdometry::LidarOdometry(std::shared_ptr<DeviceContext> ctx) : ctx_(std::mov
 LidarOdometry::~LidarOdometry() {
   cancel_prefetch();
   if (batcher_) batcher_->forgetOwner(this);
+  if (params_.simplemap.generate && !params_.simplemap.save_final_map_to_file.empty()) {  // (:1884-1903: "at destruction time")
+    try {
+      saveKeyFrames(params_.simplemap.save_final_map_to_file);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "[molahip] warning: the key-frames were not saved: %s\n", e.what());
+    }
+  }
 }
 
 void LidarOdometry::initialize(const Config& cfg) {
@@ -864,6 +972,23 @@ void LidarOdometry::initialize(const Config& cfg) {
     }
   }
 
+  // key-frames of the session (params.simplemap)
+  if (params_.simplemap.generate_lazy_load_scan_files)
+    throw std::runtime_error("LidarOdometry (HIP): params.simplemap.generate_lazy_load_scan_files: true is not implemented: a key-frame file "
+                             "holds its layers itself (molahip_host/keyframe_file.h)");
+  kf_store_ = KeyFrameStore(params_.simplemap.measure_from_last_kf_only);
+  loaded_keyframes_ = molahip_host::KeyFrameSet();
+  if (!params_.simplemap.load_existing_simple_map.empty()) {
+    loaded_keyframes_ = molahip_host::read_keyframe_file(params_.simplemap.load_existing_simple_map);
+    std::vector<std::string> want, have;
+    if (gplan_) for (const auto& m : gplan_->maps) want.push_back(m.name);
+    else want.push_back(plan_->map_layer);
+    for (const auto& t : loaded_keyframes_.maps) have.push_back(t.name);
+    if (want != have)
+      throw std::runtime_error("LidarOdometry (HIP): params.simplemap.load_existing_simple_map: the key-frame file '" +
+                               params_.simplemap.load_existing_simple_map + "' was recorded for other target maps than this pipeline's");
+  }
+
   reset();  // device objects are created at the first scan: a pipeline can be loaded and checked without a GPU (a saved map
             // is restored here, which needs one)
 }
@@ -907,6 +1032,88 @@ void LidarOdometry::saveLocalMaps(const std::string& path) const {
     recs.push_back(local_map_->snapshot(plan_->map_layer, remove_voxels_farther_than_));
   }
   molahip_host::write_local_map_file(path, recs);
+}
+
+std::vector<molahip_host::KeyFrameTarget> LidarOdometry::keyframe_targets() const {
+  std::vector<molahip_host::KeyFrameTarget> out;
+  auto target = [](const std::string& name, const HashedVoxelPointCloud& m, float remove_far) {
+    molahip_host::KeyFrameTarget t;
+    t.name = name;
+    t.class_name = m.className();
+    t.params = m.params();
+    t.remove_voxels_farther_than = remove_far;
+    return t;
+  };
+  if (gplan_) {
+    for (const auto& m : gplan_->maps) out.push_back(target(m.name, *m.map, m.remove_far));
+  } else {
+    out.push_back(target(plan_->map_layer, *local_map_, remove_voxels_farther_than_));
+  }
+  return out;
+}
+
+void LidarOdometry::saveKeyFrames(const std::string& path) const {
+  if (!kf_store_.set().frames.empty() && kf_store_.set().maps.empty())
+    throw std::runtime_error("LidarOdometry::saveKeyFrames: the target maps are not known yet");  // (cannot happen: the first stored scan makes them)
+  molahip_host::write_keyframe_file(path, kf_store_.set());
+}
+
+// params.simplemap.load_existing_simple_map: the new frames are appended under the file's header, so build_session_maps builds
+// them with the file's class and mh_map_params: these must be the running plan's.  (remove_voxels_farther_than is not held
+// against the plan: it follows the first scan's range estimate, and a session map is built without far removal.)
+void LidarOdometry::check_loaded_keyframe_targets(const std::vector<molahip_host::KeyFrameTarget>& plan) const {
+  const auto& file = loaded_keyframes_.maps;
+  for (size_t k = 0; k < file.size() && k < plan.size(); k++) {  // (initialize() has checked the names and their order)
+    const mh_map_params &a = file[k].params, &b = plan[k].params;
+    const bool same = file[k].class_name == plan[k].class_name && a.voxel_size == b.voxel_size && a.max_points_per_voxel == b.max_points_per_voxel &&
+                      a.index_mode == b.index_mode && a.min_distance_between_points == b.min_distance_between_points &&
+                      a.ndt_max_eigen_ratio == b.ndt_max_eigen_ratio && a.ndt_min_points == b.ndt_min_points &&
+                      a.far_voxel_metric == b.far_voxel_metric;
+    if (!same)
+      throw std::runtime_error("LidarOdometry (HIP): params.simplemap.load_existing_simple_map: the key-frame file '" +
+                               params_.simplemap.load_existing_simple_map + "' was recorded for a map '" + file[k].name + "' of class " +
+                               file[k].class_name + ", voxel size " + std::to_string(a.voxel_size) + ", cap " + std::to_string(a.max_points_per_voxel) +
+                               "; this pipeline makes a " + plan[k].class_name + ", voxel size " + std::to_string(b.voxel_size) + ", cap " +
+                               std::to_string(b.max_points_per_voxel) + ": class and map parameters must match for the session to be continued");
+  }
+}
+
+// params.simplemap.generate: the decision of :1117-1138 (KeyFrameStore::decide) and, for a stored scan, its host copy -- pose,
+// covariance, the twist of its last de-skew and, for a key-frame, the input layer of every FilterMerge step as the last run of
+// the second pass left it (one blocking download on this instance's stream, after the scan's registration).
+void LidarOdometry::store_keyframe(ScanRecord& rec, bool first_scan, bool icp_good, const double* cov) {
+  const KeyFrameStore::Verdict v = kf_store_.decide(first_scan, icp_good, last_lidar_pose_, params_.simplemap.min_translation_between_keyframes,
+                                                    params_.simplemap.min_rotation_between_keyframes, params_.simplemap.add_non_keyframes_too);
+  if (!v.stored) return;
+  StageTimer tt(profile_, "onLidar.5.store_keyframe");
+  molahip_host::KeyFrame f;
+  f.timestamp = rec.timestamp;
+  std::copy(last_lidar_pose_.T, last_lidar_pose_.T + 12, f.pose);
+  if (cov) std::copy(cov, cov + 36, f.cov);
+  f.has_twist = rec.had_motion_model || rec.twist_corrections > 0;
+  if (f.has_twist) {
+    const double tw[6] = {rec.twist.vx, rec.twist.vy, rec.twist.vz, rec.twist.wx, rec.twist.wy, rec.twist.wz};
+    std::copy(tw, tw + 6, f.twist);
+  }
+  f.has_points = v.keyframe;
+  if (v.keyframe) {
+    if (gplan_) {
+      for (const auto& [name, k] : gplan_->merges) {
+        molahip_host::KeyFrameLayer l;
+        l.map_index = (uint32_t)k;
+        if (gplan_->alive.count(name))  // (a layer the filters did not leave this scan: an empty entry, as nothing is merged)
+          (name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name))->download(l.x, l.y, l.z);
+        f.layers.push_back(std::move(l));
+      }
+    } else {
+      molahip_host::KeyFrameLayer l;
+      for_map_->download(l.x, l.y, l.z);
+      f.layers.push_back(std::move(l));
+    }
+  }
+  kf_store_.add(std::move(f));
+  rec.simplemap_frame = true;
+  rec.simplemap_keyframe = v.keyframe;
 }
 
 void LidarOdometry::seed_motion_model(double t, const CPose3D& pose) {  // "fake an evolution to have an initial velocity estimation" (:784-790)
@@ -1149,6 +1356,8 @@ void LidarOdometry::reset() {
   records_.clear();
   initial_localization_done_ = false;
   reloc_request_.reset();
+  kf_store_.reset(loaded_keyframes_);  // (likewise: the store starts from the loaded file's frames again)
+  kf_targets_known_ = false;  // (a loaded header is held against the plan's maps once they exist: check_loaded_keyframe_targets)
   if (!loaded_maps_.empty()) restore_loaded_maps();  // (the reference's reset() runs initialize() again: the file is loaded again)
 }
 
@@ -1812,6 +2021,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   if (reloc_request_ && !map_is_empty()) serve_relocalization(this_obs_tim, rec);
 
   bool updateLocalMap = false;
+  double kf_cov[36] = {0};  // the alignment's covariance, for the key-frame store (zeros for a first scan)
   {
     StageTimer tt(profile_, "onLidar.2.navstate");
     last_motion_model_output_ = navstate_.estimated_navstate(this_obs_tim);  // :810-811
@@ -1904,6 +2114,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     last_icp_was_good_ = icpIsGood;
     last_icp_quality_ = res.quality;
     rec.icp_good = icpIsGood;
+    if (params_.simplemap.generate) std::copy(&res.optimal_tf.cov[0], &res.optimal_tf.cov[0] + 36, kf_cov);
     if (icpIsGood) {
       last_lidar_pose_ = res.optimal_tf.mean;
       navstate_.fuse_pose(this_obs_tim, res.optimal_tf.mean, res.optimal_tf.cov);
@@ -1949,6 +2160,10 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     rec.restarted = true;
   }
 
+  // ---- key-frames of the session (:1117-1138, 1209-1296), before the map update is queued: the download then waits for
+  // nothing but this scan's own registration
+  if (params_.simplemap.generate && !rec.restarted) store_keyframe(rec, rec.first_scan, rec.icp_good, kf_cov);
+
   // ---- local map update (:1158-1206): FilterMerge of the de-skewed map layer at the current pose, on the device
   if (updateLocalMap) {
     StageTimer tt(profile_, "onLidar.4.update_local_map");
@@ -1974,6 +2189,12 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   // the next alignment's threshold schedules while the device works on the map update (the formulas' variables -- the
   // adaptive sigma -- are final for this scan; align() checks the values and evaluates again if they differ after all)
   if (icp_[0] && local_map_) icp_[0]->precomputeSchedule(icp_params_[0].maxIterations);
+  if (params_.simplemap.generate && !kf_targets_known_ && local_map_) {  // (the maps exist from the first key-frame on)
+    const auto targets = keyframe_targets();
+    if (loaded_keyframes_.maps.empty()) kf_store_.setTargets(targets);
+    else check_loaded_keyframe_targets(targets);  // (the file's header stays; the new frames must have been recorded for it)
+    kf_targets_known_ = true;
+  }
   rec.pose = last_lidar_pose_;
   rec.sigma = adapt_thres_sigma_;
   rec.map_voxel_size = map_voxel_size_;

@@ -111,6 +111,8 @@ struct RunOptions {
   long long intensity_field = -1;  // byte offset of the float32 intensity inside the record (KITTI / MulRan: 12), or -1
   std::string scan_log;       // CSV of per-scan registration times and layer / map sizes
   std::string save_local_map;  // --save-local-map: the local maps at the end of the sequence (FILE_<k> for several sequences)
+  std::string output_simplemap;    // --output-simplemap: record key-frames (params.simplemap.generate) and save them at the end (FILE_<k> likewise)
+  std::string output_session_map;  // --output-session-map: ... and the maps of the whole drive built from them, as a local-map file (FILE_<k> likewise)
 };
 
 // what the replay leaves behind besides the trajectory: layer and map sizes (records()), optionally a per-scan CSV
@@ -168,9 +170,26 @@ void list_sequence(const std::string& seq_dir, long max_scans, std::vector<std::
   while (stamps.size() < files.size()) stamps.push_back(0.1 * (double)stamps.size());  // 10 Hz when times.txt is absent
 }
 
-// one sequence, start to end; with a batcher its alignments join those of the other sequences of the process
+// cfg[key] = value for a scalar, the map entry made if absent
+mp2p_icp_hip::Config& config_child(mp2p_icp_hip::Config& c, const std::string& key) {
+  for (auto& kv : c.map)
+    if (kv.first == key) return kv.second;
+  c.kind = mp2p_icp_hip::Config::Kind::Map;
+  c.map.emplace_back(key, mp2p_icp_hip::Config());
+  return c.map.back().second;
+}
+void config_set(mp2p_icp_hip::Config& c, const std::string& key, const std::string& value) {
+  mp2p_icp_hip::Config& n = config_child(c, key);
+  n = mp2p_icp_hip::Config();
+  n.kind = mp2p_icp_hip::Config::Kind::Scalar;
+  n.scalar = value;
+}
+
+// one sequence, start to end; with a batcher its alignments join those of the other sequences of the process.  `suffix` ("" for a
+// single sequence, "_<k>" for sequence k of several) goes behind every output name of --save-local-map, --output-simplemap and
+// --output-session-map, so that no two sequences write one file.
 void run_sequence(const std::string& pipeline, const std::string& seq_dir, const std::string& out, int device, const RunOptions& opt,
-                  std::shared_ptr<mp2p_icp_hip::AlignBatcher> batcher, SequenceReport& rep, const std::string& save_map = std::string()) {
+                  std::shared_ptr<mp2p_icp_hip::AlignBatcher> batcher, SequenceReport& rep, const std::string& suffix) {
   rep.seq_dir = seq_dir;
   rep.out = out;
   rep.device = device;
@@ -201,7 +220,15 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
     rep.keep_alive = lo_owner;
     stamp("device context");
     if (opt.intensity_field >= 0) lo.setIntensityInput(true);  // (before initialize(): the intensity filters need it)
-    lo.initialize(mp2p_icp_hip::Config::FromYamlFile(pipeline));
+    mp2p_icp_hip::Config cfg = mp2p_icp_hip::Config::FromYamlFile(pipeline);
+    if (!opt.output_simplemap.empty() || !opt.output_session_map.empty()) {
+      // params.simplemap.generate on, whatever the file says; saved explicitly below (the driver object outlives the report and is
+      // never torn down, so its destructor writes nothing)
+      mp2p_icp_hip::Config& sm = config_child(config_child(cfg, "params"), "simplemap");
+      config_set(sm, "generate", "true");
+      config_set(sm, "save_final_map_to_file", "");
+    }
+    lo.initialize(cfg);
     stamp("pipeline initialised");
     if (batcher) lo.setAlignBatcher(batcher);
 
@@ -233,7 +260,10 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
     }
     lo.saveTrajectoryTUM(out);
     stamp("trajectory saved");
-    if (!save_map.empty()) lo.saveLocalMaps(save_map);  // (what params.local_map_updates.load_existing_local_map of a later run reads)
+    if (!opt.save_local_map.empty()) lo.saveLocalMaps(opt.save_local_map + suffix);  // (what params.local_map_updates.load_existing_local_map of a later run reads)
+    if (!opt.output_simplemap.empty()) lo.saveKeyFrames(opt.output_simplemap + suffix);
+    if (!opt.output_session_map.empty())
+      mola_hip::build_session_map_file(lo.keyFrames(), opt.output_session_map + suffix, std::make_shared<mp2p_icp_hip::DeviceContext>(device));
     rep.profile = lo.profile();
     finish_report(lo, opt, rep);
     stamp("report finished");
@@ -285,13 +315,20 @@ int main(int argc, char** argv) {
   std::vector<int> devices;
   RunOptions opt;
   bool print_profile = false, plan_only = false;
+  std::string build_from;  // --build-session-map
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
-                      "                      [--save-local-map FILE]\n"
+                      "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE]\n"
+                      "       molahip-lo-cli --build-session-map KEYFRAMES --save-local-map FILE [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
                       "  the pipeline's params.local_map_updates.load_existing_local_map (MOLA_LOAD_MM), and starts at initial_localization (MOLA_INITIAL_*)\n"
+                      "  --output-simplemap: record the key-frames of the session (params.simplemap.generate) and save them to FILE at the end\n"
+                      "  (FILE_<k> for several sequences)\n"
+                      "  --output-session-map: ... and build the maps of the whole drive from them into FILE (FILE_<k> for several sequences),\n"
+                      "  a local-map file like --save-local-map's\n"
+                      "  --build-session-map: no sequence is run: the maps are built from the key-frame file KEYFRAMES into --save-local-map's FILE\n"
                       "  --devices: the sequences are spread over the listed GPUs (longest first onto the least loaded device)\n";
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -310,6 +347,9 @@ int main(int argc, char** argv) {
       else if (a == "--intensity-field") opt.intensity_field = atoll(val("--intensity-field").c_str());
       else if (a == "--scan-log") opt.scan_log = val("--scan-log");
       else if (a == "--save-local-map") opt.save_local_map = val("--save-local-map");
+      else if (a == "--output-simplemap") opt.output_simplemap = val("--output-simplemap");
+      else if (a == "--output-session-map") opt.output_session_map = val("--output-session-map");
+      else if (a == "--build-session-map") build_from = val("--build-session-map");
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
       else if (a == "--plan-only") plan_only = true;
@@ -318,6 +358,29 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n%s", e.what(), usage);
       return 2;
     }
+  }
+  if (!build_from.empty()) {  // the maps of a recorded drive, no sequence
+    if (opt.save_local_map.empty() || !seq_dirs.empty()) {
+      fprintf(stderr, "--build-session-map needs --save-local-map FILE and takes no sequence\n%s", usage);
+      return 2;
+    }
+    try {
+      const molahip_host::KeyFrameSet set = molahip_host::read_keyframe_file(build_from);
+      const auto maps = mola_hip::build_session_maps(set, std::make_shared<mp2p_icp_hip::DeviceContext>(devices.empty() ? 0 : devices[0]));
+      molahip_host::write_local_map_file(opt.save_local_map, maps);
+      size_t with_points = 0;
+      for (const auto& f : set.frames) with_points += f.has_points ? 1 : 0;
+      printf("{\"keyframe_file\": \"%s\", \"frames\": %zu, \"keyframes\": %zu, \"local_map_file\": \"%s\", \"maps\": [", build_from.c_str(),
+             set.frames.size(), with_points, opt.save_local_map.c_str());
+      for (size_t k = 0; k < maps.size(); k++)
+        printf("%s{\"name\": \"%s\", \"points\": %zu, \"offered\": %llu}", k ? ", " : "", maps[k].name.c_str(), maps[k].x.size(),
+               (unsigned long long)maps[k].n_offered);
+      printf("]}\n");
+    } catch (const std::exception& e) {
+      fprintf(stderr, "molahip-lo-cli: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (pipeline.empty() || seq_dirs.empty()) {
     fprintf(stderr, "%s", usage);
@@ -363,7 +426,7 @@ int main(int argc, char** argv) {
     (void)mh_device_count(&n_dev);
   }
   if (N == 1) {
-    run_sequence(pipeline, seq_dirs[0], out, devices[0], opt, nullptr, reps[0], opt.save_local_map);
+    run_sequence(pipeline, seq_dirs[0], out, devices[0], opt, nullptr, reps[0], std::string());
   } else {
     // a batcher per device slot: the sequences of a slot advance together, the slots independently of each other
     for (size_t d = 0; d < D; d++)
@@ -371,7 +434,7 @@ int main(int argc, char** argv) {
     std::vector<std::thread> th;
     for (size_t k = 0; k < N; k++)
       th.emplace_back(run_sequence, pipeline, seq_dirs[k], stem + "_" + std::to_string(k) + ".tum", devices[slot[k]], std::cref(opt),
-                      batchers[slot[k]], std::ref(reps[k]), opt.save_local_map.empty() ? std::string() : opt.save_local_map + "_" + std::to_string(k));
+                      batchers[slot[k]], std::ref(reps[k]), "_" + std::to_string(k));
     for (auto& t : th) t.join();
   }
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

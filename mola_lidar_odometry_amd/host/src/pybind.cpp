@@ -84,6 +84,21 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         auto c = make_cloud(xyz); h.setPoints(c->x.data(), c->y.data(), c->z.data(), c->size()); })
       .def("insertPoints", [](HashedVoxelPointCloud& h, py::array_t<float, py::array::c_style | py::array::forcecast> xyz) {
         auto c = make_cloud(xyz); h.insertPoints(c->x.data(), c->y.data(), c->z.data(), c->size()); })
+      // frames: a sequence of (xyz [n, 3], T: 12 values); bit for bit what insertPointCloud(frame, T, 0) per frame gives
+      .def("insertFrames", [](HashedVoxelPointCloud& h, const std::vector<std::pair<py::array_t<float, py::array::c_style | py::array::forcecast>, std::vector<double>>>& frames,
+                              uint64_t max_points_per_pass) {
+        std::vector<std::shared_ptr<PointCloud>> clouds;
+        std::vector<PosedFrame> f;
+        for (const auto& [xyz, T] : frames) {
+          if (T.size() != 12) throw std::runtime_error("need 12 values");
+          clouds.push_back(make_cloud(xyz));
+          PosedFrame pf;
+          pf.x = clouds.back()->x.data(); pf.y = clouds.back()->y.data(); pf.z = clouds.back()->z.data();
+          pf.n = clouds.back()->size();
+          std::copy(T.begin(), T.end(), pf.pose.T);
+          f.push_back(pf);
+        }
+        h.insertFrames(f, max_points_per_pass); }, py::arg("frames"), py::arg("max_points_per_pass") = 0)
       .def("size", &HashedVoxelPointCloud::size)
       .def("voxelCount", &HashedVoxelPointCloud::voxelCount)
       .def("className", [](const HashedVoxelPointCloud& h) { return std::string(h.className()); })
@@ -175,6 +190,147 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
           ICP::IterationHook_Output o;
           o.request_stop = f(in.currentIteration, std::vector<double>(in.currentSolution->optimalPose.T, in.currentSolution->optimalPose.T + 12));
           return o; }); });
+  // ---- key-frames (molahip_host/keyframe_file.h) as dicts: {"maps": [{name, class_name, params, remove_voxels_farther_than}],
+  // "frames": [{timestamp, pose [12], cov [36], twist [6] or None, layers: None (a frame without points) or [(map_index, xyz [n, 3])]}]}
+  auto params2dict = [](const mh_map_params& q) {
+    py::dict p;
+    p["voxel_size"] = q.voxel_size; p["max_points_per_voxel"] = q.max_points_per_voxel; p["index_mode"] = q.index_mode;
+    p["min_distance_between_points"] = q.min_distance_between_points; p["ndt_max_eigen_ratio"] = q.ndt_max_eigen_ratio;
+    p["ndt_min_points"] = q.ndt_min_points; p["far_voxel_metric"] = q.far_voxel_metric;
+    return p;
+  };
+  auto dict2params = [](const py::dict& p) {
+    mh_map_params q{};
+    q.voxel_size = p["voxel_size"].cast<float>();
+    q.max_points_per_voxel = p["max_points_per_voxel"].cast<uint32_t>();
+    q.index_mode = p["index_mode"].cast<uint32_t>();
+    q.min_distance_between_points = p["min_distance_between_points"].cast<float>();
+    q.ndt_max_eigen_ratio = p["ndt_max_eigen_ratio"].cast<float>();
+    q.ndt_min_points = p["ndt_min_points"].cast<uint32_t>();
+    q.far_voxel_metric = p["far_voxel_metric"].cast<uint32_t>();
+    return q;
+  };
+  auto kfset2dict = [params2dict](const molahip_host::KeyFrameSet& set) {
+    py::list maps, frames;
+    for (const auto& t : set.maps) {
+      py::dict d;
+      d["name"] = t.name; d["class_name"] = t.class_name; d["params"] = params2dict(t.params);
+      d["remove_voxels_farther_than"] = t.remove_voxels_farther_than;
+      maps.append(d);
+    }
+    for (const auto& f : set.frames) {
+      py::dict d;
+      d["timestamp"] = f.timestamp;
+      d["pose"] = std::vector<double>(f.pose, f.pose + 12);
+      d["cov"] = std::vector<double>(f.cov, f.cov + 36);
+      d["twist"] = f.has_twist ? py::object(py::cast(std::vector<double>(f.twist, f.twist + 6))) : py::object(py::none());
+      if (f.has_points) {
+        py::list layers;
+        for (const auto& l : f.layers) {
+          const py::ssize_t n = (py::ssize_t)l.x.size();
+          py::array_t<float> xyz({n, (py::ssize_t)3});
+          auto w = xyz.mutable_unchecked<2>();
+          for (py::ssize_t i = 0; i < n; i++) { w(i, 0) = l.x[i]; w(i, 1) = l.y[i]; w(i, 2) = l.z[i]; }
+          layers.append(py::make_tuple(l.map_index, xyz));
+        }
+        d["layers"] = layers;
+      } else {
+        d["layers"] = py::none();
+      }
+      frames.append(d);
+    }
+    py::dict out;
+    out["maps"] = maps; out["frames"] = frames;
+    return out;
+  };
+  auto dict2kfset = [dict2params](const py::dict& in) {
+    molahip_host::KeyFrameSet set;
+    for (const py::handle& h : in["maps"].cast<py::list>()) {
+      const py::dict d = h.cast<py::dict>();
+      molahip_host::KeyFrameTarget t;
+      t.name = d["name"].cast<std::string>();
+      t.class_name = d["class_name"].cast<std::string>();
+      t.params = dict2params(d["params"].cast<py::dict>());
+      t.remove_voxels_farther_than = d["remove_voxels_farther_than"].cast<float>();
+      set.maps.push_back(std::move(t));
+    }
+    for (const py::handle& h : in["frames"].cast<py::list>()) {
+      const py::dict d = h.cast<py::dict>();
+      molahip_host::KeyFrame f;
+      f.timestamp = d["timestamp"].cast<double>();
+      const auto pose = d["pose"].cast<std::vector<double>>();
+      const auto cov = d["cov"].cast<std::vector<double>>();
+      if (pose.size() != 12 || cov.size() != 36) throw std::runtime_error("a frame needs 12 pose values and 36 covariance values");
+      std::copy(pose.begin(), pose.end(), f.pose);
+      std::copy(cov.begin(), cov.end(), f.cov);
+      if (!d["twist"].is_none()) {
+        const auto tw = d["twist"].cast<std::vector<double>>();
+        if (tw.size() != 6) throw std::runtime_error("a twist has 6 values");
+        f.has_twist = true;
+        std::copy(tw.begin(), tw.end(), f.twist);
+      }
+      if (!d["layers"].is_none()) {
+        f.has_points = true;
+        for (const py::handle& lh : d["layers"].cast<py::list>()) {
+          const py::tuple lt = lh.cast<py::tuple>();
+          molahip_host::KeyFrameLayer l;
+          l.map_index = lt[0].cast<uint32_t>();
+          auto xyz = lt[1].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+          if (xyz.ndim() != 2 || xyz.shape(1) != 3) throw std::runtime_error("a layer's xyz must be [n, 3]");
+          const py::ssize_t n = xyz.shape(0);
+          auto a = xyz.unchecked<2>();
+          l.x.resize(n); l.y.resize(n); l.z.resize(n);
+          for (py::ssize_t i = 0; i < n; i++) { l.x[i] = a(i, 0); l.y[i] = a(i, 1); l.z[i] = a(i, 2); }
+          f.layers.push_back(std::move(l));
+        }
+      }
+      set.frames.push_back(std::move(f));
+    }
+    return set;
+  };
+  m.def("write_keyframe_file", [dict2kfset](const std::string& path, const py::dict& set) { molahip_host::write_keyframe_file(path, dict2kfset(set)); });
+  m.def("read_keyframe_file", [kfset2dict](const std::string& path) { return kfset2dict(molahip_host::read_keyframe_file(path)); });
+  m.attr("KEYFRAME_FILE_VERSION") = molahip_host::kKeyFrameFileVersion;
+  auto maps2list = [params2dict](const std::vector<molahip_host::LocalMapRecord>& recs) {
+    py::list out;
+    for (const auto& r : recs) {
+      py::dict d;
+      d["name"] = r.name; d["class_name"] = r.class_name; d["params"] = params2dict(r.params);
+      d["remove_voxels_farther_than"] = r.remove_voxels_farther_than; d["n_offered"] = r.n_offered;
+      const py::ssize_t n = (py::ssize_t)r.x.size();
+      py::array_t<float> xyz({n, (py::ssize_t)3});
+      auto w = xyz.mutable_unchecked<2>();
+      for (py::ssize_t i = 0; i < n; i++) { w(i, 0) = r.x[i]; w(i, 1) = r.y[i]; w(i, 2) = r.z[i]; }
+      d["xyz"] = xyz;
+      d["src_idx"] = py::array_t<uint32_t>(n, r.src_idx.data());
+      out.append(d);
+    }
+    return out;
+  };
+  // the maps of the whole drive from key-frames (a dict as above, or the path of a key-frame file): a list of map dicts as
+  // read_local_map_file returns them; with `local_map_file` they are also written there (a version-1 local-map file)
+  m.def("build_session_maps", [dict2kfset, maps2list](const py::object& frames, uint64_t max_points_per_pass, const std::string& local_map_file) {
+    const molahip_host::KeyFrameSet set = py::isinstance<py::str>(frames) ? molahip_host::read_keyframe_file(frames.cast<std::string>())
+                                                                         : dict2kfset(frames.cast<py::dict>());
+    std::vector<molahip_host::LocalMapRecord> recs;
+    {
+      py::gil_scoped_release nogil;
+      recs = mola_hip::build_session_maps(set, nullptr, max_points_per_pass);
+      if (!local_map_file.empty()) molahip_host::write_local_map_file(local_map_file, recs);
+    }
+    return maps2list(recs); }, py::arg("frames"), py::arg("max_points_per_pass") = 0, py::arg("local_map_file") = "");
+  // the key-frame decision on its own (host logic only: testable without a device; the driver holds one)
+  py::class_<mola_hip::KeyFrameStore>(m, "KeyFrameStore")
+      .def(py::init<bool>(), py::arg("measure_from_last_kf_only") = false)
+      .def("decide", [](mola_hip::KeyFrameStore& s, bool first_scan, bool icp_good, std::vector<double> pose, double min_translation,
+                        double min_rotation_deg, bool add_non_keyframes_too) {
+        if (pose.size() != 12) throw std::runtime_error("need 12 values");
+        CPose3D P; std::copy(pose.begin(), pose.end(), P.T);
+        const auto v = s.decide(first_scan, icp_good, P, min_translation, min_rotation_deg, add_non_keyframes_too);
+        return py::make_tuple(v.stored, v.keyframe); },
+           py::arg("first_scan"), py::arg("icp_good"), py::arg("pose"), py::arg("min_translation"), py::arg("min_rotation_deg"),
+           py::arg("add_non_keyframes_too") = false)
+      .def("reset", [](mola_hip::KeyFrameStore& s) { s.reset(); });
   // ---- stand-alone odometry driver
   using mola_hip::LidarOdometry;
   auto rec2dict = [](const LidarOdometry::ScanRecord& r) {
@@ -196,6 +352,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["waiting"] = r.waiting; d["ignored"] = r.ignored; d["n_sensors"] = r.n_sensors; d["sensor_labels"] = r.sensor_labels;
     d["relocalization_tried"] = r.relocalization_tried; d["relocalized"] = r.relocalized; d["reloc_candidates"] = r.reloc_candidates;
     d["reloc_best_n_paired"] = r.reloc_best_n_paired; d["reloc_best_quality"] = r.reloc_best_quality; d["reloc_ranks"] = r.reloc_ranks;
+    d["simplemap_keyframe"] = r.simplemap_keyframe; d["simplemap_frame"] = r.simplemap_frame;
     return d;
   };
   py::class_<LidarOdometry> lo_class(m, "LidarOdometry", py::dynamic_attr());
@@ -287,6 +444,17 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
            py::arg("range_units") = 0.001, py::arg("range_is_depth") = true, py::arg("sensor_pose") = std::nullopt)
       .def("localMapClasses", &LidarOdometry::localMapClasses)
       .def("saveLocalMaps", &LidarOdometry::saveLocalMaps, py::call_guard<py::gil_scoped_release>())
+      .def("keyFrames", [kfset2dict](const LidarOdometry& lo) { return kfset2dict(lo.keyFrames()); })
+      .def("saveKeyFrames", &LidarOdometry::saveKeyFrames, py::call_guard<py::gil_scoped_release>())
+      .def("simplemapOptions", [](const LidarOdometry& lo) {
+        const auto& o = lo.params().simplemap;
+        py::dict d;
+        d["generate"] = o.generate; d["min_translation_between_keyframes"] = o.min_translation_between_keyframes;
+        d["min_rotation_between_keyframes"] = o.min_rotation_between_keyframes; d["measure_from_last_kf_only"] = o.measure_from_last_kf_only;
+        d["add_non_keyframes_too"] = o.add_non_keyframes_too; d["generate_lazy_load_scan_files"] = o.generate_lazy_load_scan_files;
+        d["save_gnss_max_age"] = o.save_gnss_max_age; d["save_final_map_to_file"] = o.save_final_map_to_file;
+        d["load_existing_simple_map"] = o.load_existing_simple_map;
+        return d; })
       // mean: 12 values, row-major [R|t]; cov: 36 values, row-major 6x6 in (x, y, z, yaw, pitch, roll)
       .def("relocalizeNearPose", [](LidarOdometry& lo, std::vector<double> mean, std::vector<double> cov) {
         if (mean.size() != 12 || cov.size() != 36) throw std::runtime_error("need 12 pose values and 36 covariance values");
