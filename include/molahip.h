@@ -576,6 +576,69 @@ typedef struct {
 MH_API mh_status mh_score_poses(const mh_map* map, const mh_scan* scan, const double* poses, size_t n_poses, double threshold,
                                 double threshold_angular_deg, mh_pose_score* scores, int32_t mem);
 
+/* Place recognition by a polar height descriptor (in the manner of Scan Context): from "this scan" to "these few stored frames
+ * look like it, under this yaw" -- the coarse pose a relocalization needs when nobody supplies one.  A descriptor is R rings x S
+ * sectors of bytes around the vehicle, desc[ring * S + sector], each the quantised height of the highest point of its bin (0:
+ * empty).  Everything is integer or compare-only fp32: results are exact and do not depend on the order of the points.
+ *
+ * THE DESCRIPTOR (this text is the specification; tests/place_ref.py restates it in numpy and every byte must agree).  No
+ * transcendental function runs on the device; every boundary comes from a table the host builds in fp64 and rounds once to
+ * fp32; all point arithmetic is un-fused fp32.
+ *  - Parameters: R = n_rings in [1, MH_PLACE_MAX_RINGS]; S = n_sectors, a multiple of 8 in [8, MH_PLACE_MAX_SECTORS];
+ *    0 <= min_range < max_range; z_min < z_max; all values finite (and the tables below finite in fp32).
+ *  - Host tables: ring_edge2[k] = (float)(e_k * e_k), e_k = min_range + k * (max_range - min_range) / R in fp64, k = 0..R;
+ *    tan_edge[j] = (float)tan(2 * pi * j / S), j = 1..S/8-1;  zscale = (float)(254.0 / ((double)z_max - (double)z_min)).
+ *  - A point (x, y, z) is skipped when a coordinate is non-finite; when x = y = 0; when r2 = x*x + y*y lies outside
+ *    [ring_edge2[0], ring_edge2[R]); when z lies outside [z_min, z_max).
+ *  - ring = the number of k in 1..R-1 with ring_edge2[k] <= r2.
+ *  - level = min(255, 1 + (uint32)((z - z_min) * zscale)): one subtraction, one multiplication, a truncation.
+ *  - sector, by quarter turns; each case gives a > 0 and b >= 0:
+ *        x > 0 and y >= 0: Q = 0, (a, b) = (x, y);        x <= 0 and y > 0: Q = 1, (a, b) = (y, -x);
+ *        x < 0 and y <= 0: Q = 2, (a, b) = (-x, -y);      x >= 0 and y < 0: Q = 3, (a, b) = (-y, x).
+ *    With E = S / 8:  if b < a:  o = #{j in 1..E-1 : b >= tan_edge[j] * a};  otherwise  o = (2E - 1) - #{j : a > tan_edge[j] * b}.
+ *    sector = Q * (S / 4) + o.  This is floor(atan2(y, x) * S / 2pi) mod S away from the boundaries; axes and diagonals lie on
+ *    the closed lower end of their sector.
+ *  - A bin holds the maximum level of its points.
+ *  - Binding property: turning every point by an exact quarter turn, (x, y) -> (-y, x), shifts the descriptor by exactly S/4
+ *    columns: desc'[r][(c + S/4) mod S] = desc[r][c].
+ *
+ * THE SEARCH.  For the stored descriptor d_k and the query q,  D(k, s) = sum over r, c of | q[r][(c + s) mod S] - d_k[r][c] |;
+ * out[k] = {shift, dist} is the smallest D(k, .) and the smallest s that attains it.  D <= 32 * 128 * 255 < 2^20.  With this sign
+ * a query taken by a vehicle turned by yaw psi against the stored frame gives shift ~ -psi * S / 2pi (mod S).
+ *
+ *  - mh_place_describe: the descriptor of one scan, n_rings * n_sectors bytes in `mem`.  An empty scan gives all zeros.
+ *  - mh_place_db_create / _destroy / _size: a database of descriptors of one parameter set on the context's device.
+ *  - mh_place_db_add: appends n_desc ready descriptors (n_desc * R * S bytes in `mem`); n_desc == 0 changes nothing.
+ *  - mh_place_db_add_frames: bit for bit the loop  for f: mh_place_describe(scan(frames[f])); mh_place_db_add  -- in passes of
+ *    one upload and one flat launch over all points of the pass, as mh_map_insert_frames.  frames[f].T is ignored; an empty
+ *    frame appends an all-zero descriptor; x, y, z may be NULL when n is 0.  Device arrays live on the database's device.
+ *  - mh_place_search: `out` holds mh_place_db_size entries in `mem`, `query` R * S bytes in `query_mem`.  An empty database:
+ *    MH_OK, nothing is written.
+ *  - `mem`: MH_MEM_HOST, MH_MEM_HOST_PINNED or MH_MEM_DEVICE.  Every call orders itself on the context's stream and blocks
+ *    until its output is in `mem` (and the caller's arrays may be reused).
+ *  - Refusals, all decided before any device work, the database untouched: MH_ERR_INVALID_ARGUMENT for NULL handles or arrays
+ *    (NULL point arrays with n > 0), a bad `mem`, parameters outside the ranges above; MH_ERR_UNSUPPORTED when the database
+ *    would hold more than MH_PLACE_MAX_DESCRIPTORS descriptors.  (No entry point takes both a scan and a database, so there
+ *    is no pair of handles that could live on different devices.) */
+#define MH_PLACE_MAX_RINGS 32
+#define MH_PLACE_MAX_SECTORS 128
+#define MH_PLACE_MAX_DESCRIPTORS 1048576
+typedef struct {
+  uint32_t n_rings, n_sectors;
+  float min_range, max_range, z_min, z_max;
+} mh_place_params; /* 24 bytes */
+typedef struct {
+  uint32_t shift, dist;
+} mh_place_match; /* 8 bytes */
+typedef struct mh_place_db mh_place_db;
+MH_API mh_status mh_place_describe(const mh_scan* scan, const mh_place_params* params, uint8_t* desc, int32_t mem);
+MH_API mh_status mh_place_db_create(mh_ctx* ctx, const mh_place_params* params, mh_place_db** out);
+MH_API mh_status mh_place_db_destroy(mh_place_db* db);
+MH_API mh_status mh_place_db_size(const mh_place_db* db, uint64_t* n);
+MH_API mh_status mh_place_db_add(mh_place_db* db, const uint8_t* desc, size_t n_desc, int32_t mem);
+MH_API mh_status mh_place_db_add_frames(mh_place_db* db, const mh_map_frame* frames, size_t n_frames, int32_t mem);
+MH_API mh_status mh_place_search(const mh_place_db* db, const uint8_t* query, int32_t query_mem, mh_place_match* out, int32_t mem);
+
 /* Replaces mp2p_icp::Matcher_Point2Plane::implMatchOneLayer [U] on a mola::NDT [U] map (lidar3d-ndt.yaml:195-200,
  * 236-254).  The upstream semantics are unverified (SURVEY App.B U10); implemented default: among
  * the planar voxels of the 3x3x3 block around voxel(p') the one with the nearest centroid is taken (fp32 d^2, first

@@ -243,6 +243,21 @@ class MapFrame(C.Structure):
 
 
 MAX_INSERT_FRAMES = 1048576  # MH_MAX_INSERT_FRAMES
+
+
+class PlaceParams(C.Structure):
+    """mh_place_params: rings x sectors of the polar height descriptor, its range annulus and z window (mh_place_describe)."""
+    _fields_ = [("n_rings", C.c_uint32), ("n_sectors", C.c_uint32), ("min_range", C.c_float), ("max_range", C.c_float),
+                ("z_min", C.c_float), ("z_max", C.c_float)]
+
+
+class PlaceMatch(C.Structure):
+    """mh_place_match: the best column shift of the query against one stored descriptor and its L1 distance."""
+    _fields_ = [("shift", C.c_uint32), ("dist", C.c_uint32)]
+
+
+PLACE_MATCH_DTYPE = np.dtype([("shift", np.uint32), ("dist", np.uint32)])
+PLACE_MAX_RINGS, PLACE_MAX_SECTORS, PLACE_MAX_DESCRIPTORS = 32, 128, 1 << 20  # MH_PLACE_MAX_*
 OCC_COUNTED, OCC_ONCE = 0, 1  # mh_occmap_params::update_rule
 TS_NONE, TS_MIDDLE_IS_ZERO, TS_EARLIEST_IS_ZERO = 0, 1, 2
 DECIMATE_FIRST_POINT, DECIMATE_CLOSEST_TO_AVERAGE = 0, 1
@@ -309,6 +324,13 @@ _SIGNATURES = {
     "mh_nn_search_radius": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_double, C.c_uint32, C.POINTER(RadiusOut), C.c_int32,
                                         C.POINTER(RadiusInfo)]),
     "mh_score_poses": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_int32]),
+    "mh_place_describe": (C.c_int32, [C.c_void_p, C.POINTER(PlaceParams), C.c_void_p, C.c_int32]),
+    "mh_place_db_create": (C.c_int32, [C.c_void_p, C.POINTER(PlaceParams), C.POINTER(C.c_void_p)]),
+    "mh_place_db_destroy": (C.c_int32, [C.c_void_p]),
+    "mh_place_db_size": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mh_place_db_add": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32]),
+    "mh_place_db_add_frames": (C.c_int32, [C.c_void_p, C.POINTER(MapFrame), C.c_size_t, C.c_int32]),
+    "mh_place_search": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "mh_nn_search_pt2pl": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.c_double, C.c_uint32, C.POINTER(PairsPlOut), C.c_int32,
                                        C.POINTER(MatchInfo)]),
     "mh_nn_search_pt2pl_knn": (C.c_int32, [C.c_void_p, C.c_void_p, _DP, C.POINTER(Pt2PlKnnParams), C.POINTER(PairsPlOut), C.c_int32,
@@ -930,6 +952,91 @@ def score_poses(m: Map, s: Scan, poses, threshold, threshold_angular_deg=0.0):
     _chk(lib().mh_score_poses(m._h, s._h, P.ctypes.data_as(_DP), len(P), float(threshold), float(threshold_angular_deg),
                               _vp(out), MEM_HOST))
     return out[:len(P)]
+
+
+def place_params(n_rings=20, n_sectors=64, min_range=1.0, max_range=80.0, z_min=-3.0, z_max=27.0) -> PlaceParams:
+    return PlaceParams(int(n_rings), int(n_sectors), float(min_range), float(max_range), float(z_min), float(z_max))
+
+
+def place_describe(s: Scan, params: PlaceParams):
+    """The polar height descriptor of one scan (mh_place_describe): uint8 [n_rings, n_sectors]."""
+    out = np.zeros((params.n_rings, params.n_sectors), np.uint8)
+    _chk(lib().mh_place_describe(s._h, C.byref(params), _vp(out), MEM_HOST))
+    return out
+
+
+def place_describe_device(s: Scan, params: PlaceParams, desc_ptr: int):
+    """The same into device memory (n_rings * n_sectors bytes at desc_ptr)."""
+    _chk(lib().mh_place_describe(s._h, C.byref(params), C.c_void_p(desc_ptr), MEM_DEVICE))
+
+
+class PlaceDB:
+    """A database of place descriptors on one context's device (mh_place_db)."""
+
+    def __init__(self, ctx: Context, params: PlaceParams):
+        self.ctx = ctx
+        self.params = params
+        self._h = C.c_void_p()
+        _chk(lib().mh_place_db_create(ctx._h, C.byref(params), C.byref(self._h)))
+        ctx._children.add(self)
+
+    def __len__(self):
+        n = C.c_uint64(0)
+        _chk(lib().mh_place_db_size(self._h, C.byref(n)))
+        return int(n.value)
+
+    def add(self, desc):
+        """Append ready descriptors: uint8 [k, n_rings, n_sectors] (or one [n_rings, n_sectors])."""
+        rs = self.params.n_rings * self.params.n_sectors
+        d = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, rs)
+        _chk(lib().mh_place_db_add(self._h, _vp(d), len(d), MEM_HOST))
+        return self
+
+    def add_device(self, desc_ptr: int, n_desc: int):
+        _chk(lib().mh_place_db_add(self._h, C.c_void_p(desc_ptr), int(n_desc), MEM_DEVICE))
+        return self
+
+    def add_frames(self, frames):
+        """Describe and append a group of frames in one call (mh_place_db_add_frames): `frames` is a sequence of xyz [n, 3]."""
+        keep = [_soa(xyz) for xyz in frames]
+        arr = (MapFrame * max(len(keep), 1))()
+        for e, (x, y, z) in zip(arr, keep):
+            e.x, e.y, e.z, e.n = _vp(x), _vp(y), _vp(z), len(x)
+        _chk(lib().mh_place_db_add_frames(self._h, arr, len(keep), MEM_HOST))
+        return self
+
+    def add_frames_device(self, frames):
+        """The same from device arrays: `frames` is a sequence of (x_ptr, y_ptr, z_ptr, n)."""
+        frames = list(frames)
+        arr = (MapFrame * max(len(frames), 1))()
+        for e, (xp, yp, zp, n) in zip(arr, frames):
+            e.x, e.y, e.z, e.n = xp, yp, zp, int(n)
+        _chk(lib().mh_place_db_add_frames(self._h, arr, len(frames), MEM_DEVICE))
+        return self
+
+    def search(self, query):
+        """The query (uint8 [n_rings, n_sectors]) against every stored descriptor (mh_place_search): a structured array of
+        len(self) entries with the fields shift and dist."""
+        q = np.ascontiguousarray(query, dtype=np.uint8).reshape(self.params.n_rings * self.params.n_sectors)
+        k = len(self)
+        out = np.zeros(max(k, 1), PLACE_MATCH_DTYPE)
+        _chk(lib().mh_place_search(self._h, _vp(q), MEM_HOST, _vp(out), MEM_HOST))
+        return out[:k]
+
+    def search_device(self, query_ptr: int, out_ptr: int):
+        _chk(lib().mh_place_search(self._h, C.c_void_p(query_ptr), MEM_DEVICE, C.c_void_p(out_ptr), MEM_DEVICE))
+
+    def close(self):
+        if self._h:
+            if self.ctx._h:
+                lib().mh_place_db_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 @dataclass

@@ -185,6 +185,34 @@ class SensorSync {
 std::vector<TPose3D> relocalization_grid(const TPose3D& mean, const double cov[36], double step_xy, double step_yaw_rad,
                                          double sigmas = 3.0, size_t max_candidates = 65536);
 
+// Place recognition over the key-frames of a session (include/molahip.h, mh_place_*): an mh_place_db of the polar height
+// descriptors of the frames' first stored layer (layers[0]: the input layer of the first FilterMerge step, vehicle frame) and the
+// frame every descriptor belongs to.  Descriptors are recomputed from the stored layers; the key-frame file does not hold them.
+class PlaceIndex {
+ public:
+  struct Match {
+    uint32_t frame = 0, shift = 0, dist = 0;  // index into the KeyFrameSet's frames; mh_place_match of its descriptor
+  };
+  explicit PlaceIndex(const mh_place_params& params, std::shared_ptr<DeviceContext> ctx = nullptr);
+  ~PlaceIndex();
+  PlaceIndex(const PlaceIndex&) = delete;
+  PlaceIndex& operator=(const PlaceIndex&) = delete;
+  // appends the frames from index `first` on that have points (a non-empty layers[0]) in ONE mh_place_db_add_frames; returns
+  // how many were appended
+  size_t addKeyFrames(const molahip_host::KeyFrameSet& set, size_t first = 0);
+  // every stored descriptor against the layer's, ranked by (dist ascending, frame ascending)
+  std::vector<Match> query(const DevicePointCloud& layer) const;
+  std::vector<uint8_t> describe(const DevicePointCloud& layer) const;  // n_rings * n_sectors bytes, desc[ring * S + sector]
+  size_t size() const { return frame_of_.size(); }
+  const mh_place_params& params() const { return params_; }
+
+ private:
+  std::shared_ptr<DeviceContext> ctx_;
+  mh_place_params params_;
+  mh_place_db* db_ = nullptr;
+  std::vector<uint32_t> frame_of_;
+};
+
 class LidarOdometry {
  public:
   // the params: block of the pipeline file (yaml:6-122); formulas are re-evaluated every scan
@@ -247,6 +275,12 @@ class LidarOdometry {
     double sigmas = 3.0;
     uint32_t refine_top_k = 4;
     uint32_t max_candidates = 65536;
+    // relocalizeInKeyFrames: the descriptor (mh_place_params), the ranked frames kept, and the spread searched around each
+    uint32_t place_rings = 20, place_sectors = 64;
+    double place_min_range = 1.0, place_max_range = 80.0, place_z_min = -3.0, place_z_max = 27.0;
+    uint32_t place_top_k = 4;
+    double place_sigma_xy = 1.0;          // [m]
+    double place_sigma_yaw_deg = 5.625;   // one sector of the default descriptor
   };
 
   // one line of the per-scan log (what the reference spreads over debug traces / the parameter source)
@@ -281,6 +315,10 @@ class LidarOdometry {
     uint32_t reloc_candidates = 0, reloc_best_n_paired = 0;
     double reloc_best_quality = 0;
     std::vector<uint32_t> reloc_ranks;
+    // ... a relocalizeInKeyFrames request: the key-frames kept by the place search in rank order (indices into keyFrames()),
+    // their column shifts and descriptor distances
+    bool place_tried = false;
+    std::vector<uint32_t> place_frames, place_shifts, place_dists;
     // params.simplemap.generate: this scan is stored in the key-frame store (simplemap_frame), with its points (simplemap_keyframe)
     bool simplemap_keyframe = false, simplemap_frame = false;
   };
@@ -376,6 +414,18 @@ class LidarOdometry {
   // At relocalization time the twist is unknown: the layers were de-skewed with the current twist variables, which are zero
   // after a reset.  With an AlignBatcher set this throws: the batch protocol has no slot for extra alignments of one member.
   void relocalizeNearPose(const CPose3D& mean, const double cov[36]);
+  // The same without a coarse pose: place recognition over the stored key-frames supplies it.  Preconditions and failure path
+  // are relocalizeNearPose's.  The serving scan
+  //   1. brings a PlaceIndex (relocalization.place_rings ... place_z_max) up to date with the key-frame store (keyFrames(): a
+  //      load_existing_simple_map file's frames and those recorded since) and describes the input layer of the first FilterMerge
+  //      step as this scan's passes left it -- the role layers[0] has in a key-frame; a store without a frame with points
+  //      throws and names load_existing_simple_map;
+  //   2. searches and keeps the first place_top_k frames, ranked by (dist ascending, frame ascending);
+  //   3. per kept frame: mean = frame pose (+) Rz(-shift * 2 pi / place_sectors), candidates = relocalization_grid(mean,
+  //      diag(place_sigma_xy^2, place_sigma_xy^2, ., place_sigma_yaw^2, ., .)) with the steps, sigmas and max_candidates above;
+  //      the lists are concatenated in rank order and their total counts against max_candidates;
+  //   4. runs steps 2-5 of relocalizeNearPose on the concatenated list.
+  void relocalizeInKeyFrames();
   bool relocalizationPending() const { return reloc_request_.has_value(); }
   std::shared_ptr<HashedVoxelPointCloud> localMap() const { return local_map_; }
   // points of every local map by name (general plans: one per localmap_generator entry; 0 before the first key-frame)
@@ -449,6 +499,7 @@ class LidarOdometry {
   void seed_motion_model(double t, const CPose3D& pose);     // fuse `pose` at t - 0.2 and t - 0.1 (:779-794)
   void scan_layers(mp2p_icp_hip::metric_map_t& obs, mp2p_icp_hip::metric_map_t& glob) const;  // what this scan's ICP aligns
   void serve_relocalization(double t, ScanRecord& rec);
+  std::vector<TPose3D> place_candidates(ScanRecord& rec, double step);  // steps 1-3 of relocalizeInKeyFrames
   double reloc_score_threshold(const std::string& global_layer) const;  // NaN while the searched map is not there
   void store_keyframe(ScanRecord& rec, bool first_scan, bool icp_good, const double* cov);  // params.simplemap.generate
   std::vector<molahip_host::KeyFrameTarget> keyframe_targets() const;  // the plan's maps as the key-frame file's header names them
@@ -517,8 +568,11 @@ class LidarOdometry {
   struct RelocRequest {
     CPose3D mean;
     double cov[36];
+    bool in_keyframes = false;  // relocalizeInKeyFrames: mean and cov come from the place search at the serving scan
   };
   std::optional<RelocRequest> reloc_request_;
+  std::unique_ptr<PlaceIndex> place_index_;  // relocalizeInKeyFrames: built at the first serving scan
+  size_t place_frames_seen_ = 0;             // ... and how many frames of the key-frame store it has looked at
   bool input_pinned_ = false;
   bool intensity_input_ = false;  // setIntensityInput
   std::map<std::string, double> profile_;

@@ -948,6 +948,24 @@ void LidarOdometry::initialize(const Config& cfg) {
     if (r.has("sigmas")) reloc_opts_.sigmas = to_double(r["sigmas"].asString());
     if (r.has("refine_top_k")) reloc_opts_.refine_top_k = (uint32_t)to_double(r["refine_top_k"].asString());
     if (r.has("max_candidates")) reloc_opts_.max_candidates = (uint32_t)to_double(r["max_candidates"].asString());
+    auto num = [&](const char* k, double& v) { if (r.has(k)) v = to_double(r[k].asString()); };
+    auto cnt = [&](const char* k, uint32_t& v) { if (r.has(k)) v = (uint32_t)to_double(r[k].asString()); };
+    cnt("place_rings", reloc_opts_.place_rings);
+    cnt("place_sectors", reloc_opts_.place_sectors);
+    num("place_min_range", reloc_opts_.place_min_range);
+    num("place_max_range", reloc_opts_.place_max_range);
+    num("place_z_min", reloc_opts_.place_z_min);
+    num("place_z_max", reloc_opts_.place_z_max);
+    cnt("place_top_k", reloc_opts_.place_top_k);
+    num("place_sigma_xy", reloc_opts_.place_sigma_xy);
+    num("place_sigma_yaw_deg", reloc_opts_.place_sigma_yaw_deg);
+    const RelocalizationOptions& o = reloc_opts_;
+    if (o.place_rings < 1 || o.place_rings > MH_PLACE_MAX_RINGS || o.place_sectors < 8 || o.place_sectors > MH_PLACE_MAX_SECTORS || o.place_sectors % 8 ||
+        !(o.place_min_range >= 0.0) || !(o.place_min_range < o.place_max_range) || !std::isfinite(o.place_max_range) || !(o.place_z_min < o.place_z_max) ||
+        !std::isfinite(o.place_z_min) || !std::isfinite(o.place_z_max) || o.place_top_k < 1 || !(o.place_sigma_xy >= 0.0) || !std::isfinite(o.place_sigma_xy) ||
+        !(o.place_sigma_yaw_deg >= 0.0) || !std::isfinite(o.place_sigma_yaw_deg))
+      throw std::runtime_error("LidarOdometry (HIP): relocalization: place_rings in [1, 32], place_sectors a multiple of 8 in [8, 128], 0 <= place_min_range "
+                               "< place_max_range, place_z_min < place_z_max, place_top_k >= 1, place_sigma_xy >= 0 and place_sigma_yaw_deg >= 0 are required");
     if (!(reloc_opts_.step_xy >= 0.0) || !(reloc_opts_.step_yaw_deg > 0.0) || !(reloc_opts_.sigmas > 0.0) || reloc_opts_.refine_top_k < 1 ||
         reloc_opts_.max_candidates < 1 || reloc_opts_.max_candidates > MH_SCORE_MAX_POSES)
       throw std::runtime_error("LidarOdometry (HIP): relocalization: step_xy >= 0, step_yaw_deg > 0, sigmas > 0, refine_top_k >= 1 and "
@@ -1218,6 +1236,121 @@ void LidarOdometry::relocalizeNearPose(const CPose3D& mean, const double cov[36]
   reloc_request_ = rq;
 }
 
+void LidarOdometry::relocalizeInKeyFrames() {
+  if (!plan_ && !gplan_) throw std::runtime_error("LidarOdometry::relocalizeInKeyFrames called before initialize()");
+  if (batcher_)
+    throw std::runtime_error("LidarOdometry::relocalizeInKeyFrames: not available with an AlignBatcher (the batch protocol has no slot for "
+                             "the extra alignments of one member)");
+  std::string g, l;
+  if (!scored_layers(*icp_[1], g, l))
+    throw std::runtime_error("LidarOdometry::relocalizeInKeyFrames: the no-motion-model ICP block has no enabled Matcher_Points_DistanceThreshold "
+                             "to score candidates with");
+  RelocRequest rq;
+  for (int i = 0; i < 36; i++) rq.cov[i] = 0.0;
+  rq.in_keyframes = true;
+  reloc_request_ = rq;
+}
+
+std::vector<TPose3D> LidarOdometry::place_candidates(ScanRecord& rec, double step) {
+  const RelocalizationOptions& o = reloc_opts_;
+  const molahip_host::KeyFrameSet& set = kf_store_.set();
+  // ---- 1. the index follows the store
+  if (!place_index_) {
+    mh_place_params pp{};
+    pp.n_rings = o.place_rings;
+    pp.n_sectors = o.place_sectors;
+    pp.min_range = (float)o.place_min_range;
+    pp.max_range = (float)o.place_max_range;
+    pp.z_min = (float)o.place_z_min;
+    pp.z_max = (float)o.place_z_max;
+    place_index_ = std::make_unique<PlaceIndex>(pp, ctx_);
+    place_frames_seen_ = 0;
+  }
+  if (place_frames_seen_ < set.frames.size()) {
+    place_index_->addKeyFrames(set, place_frames_seen_);
+    place_frames_seen_ = set.frames.size();
+  }
+  if (place_index_->size() == 0)
+    throw std::runtime_error("LidarOdometry: relocalizeInKeyFrames: the key-frame store holds no frame with points: name the key-frame file of the "
+                             "session in params.simplemap.load_existing_simple_map (MOLA_LOAD_SM)");
+  std::shared_ptr<DevicePointCloud> layer;
+  if (gplan_) {
+    if (!gplan_->merges.empty()) {
+      const std::string& name = gplan_->merges.front().first;
+      if (gplan_->alive.count(name)) layer = name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name);
+    }
+  } else {
+    layer = for_map_;
+  }
+  if (!layer) throw std::runtime_error("LidarOdometry: relocalizeInKeyFrames: the input layer of the first FilterMerge step is not among this scan's");
+  // ---- 2. search, keep place_top_k
+  std::vector<PlaceIndex::Match> m = place_index_->query(*layer);
+  m.resize(std::min<size_t>(m.size(), o.place_top_k));
+  rec.place_tried = true;
+  // ---- 3. a grid around every kept frame, concatenated in rank order
+  double cov[36] = {0};
+  cov[0] = cov[7] = o.place_sigma_xy * o.place_sigma_xy;
+  const double syaw = o.place_sigma_yaw_deg * kDeg2Rad;
+  cov[21] = syaw * syaw;
+  std::vector<TPose3D> cand;
+  for (const PlaceIndex::Match& k : m) {
+    rec.place_frames.push_back(k.frame);
+    rec.place_shifts.push_back(k.shift);
+    rec.place_dists.push_back(k.dist);
+    CPose3D fp;
+    std::copy(set.frames[k.frame].pose, set.frames[k.frame].pose + 12, fp.T);
+    TPose3D rz;
+    rz.yaw = -(double)k.shift * 2.0 * M_PI / (double)o.place_sectors;
+    const CPose3D mean = fp + CPose3D(rz);
+    const std::vector<TPose3D> g = relocalization_grid(mean.asTPose(), cov, step, o.step_yaw_deg * kDeg2Rad, o.sigmas, o.max_candidates);
+    if (cand.size() + g.size() > o.max_candidates)
+      throw std::runtime_error("relocalization_grid: " + std::to_string(cand.size() + g.size()) + " candidates over " + std::to_string(m.size()) +
+                               " key-frames exceed max_candidates (" + std::to_string(o.max_candidates) + "): coarsen the steps or tighten the covariance");
+    cand.insert(cand.end(), g.begin(), g.end());
+  }
+  return cand;
+}
+
+// ---- PlaceIndex
+PlaceIndex::PlaceIndex(const mh_place_params& params, std::shared_ptr<DeviceContext> ctx) : ctx_(ctx ? std::move(ctx) : DeviceContext::Default()), params_(params) {
+  check(mh_place_db_create(ctx_->get(), &params_, &db_), "mh_place_db_create");
+}
+PlaceIndex::~PlaceIndex() {
+  if (db_) (void)mh_place_db_destroy(db_);
+}
+size_t PlaceIndex::addKeyFrames(const molahip_host::KeyFrameSet& set, size_t first) {
+  std::vector<mh_map_frame> f;
+  std::vector<uint32_t> idx;
+  for (size_t k = first; k < set.frames.size(); k++) {
+    const molahip_host::KeyFrame& kf = set.frames[k];
+    if (!kf.has_points || kf.layers.empty() || kf.layers[0].x.empty()) continue;
+    mh_map_frame e{};
+    e.x = kf.layers[0].x.data(); e.y = kf.layers[0].y.data(); e.z = kf.layers[0].z.data();
+    e.n = kf.layers[0].x.size();
+    std::copy(kf.pose, kf.pose + 12, e.T);
+    f.push_back(e);
+    idx.push_back((uint32_t)k);
+  }
+  if (f.empty()) return 0;
+  check(mh_place_db_add_frames(db_, f.data(), f.size(), MH_MEM_HOST), "mh_place_db_add_frames");
+  frame_of_.insert(frame_of_.end(), idx.begin(), idx.end());
+  return f.size();
+}
+std::vector<uint8_t> PlaceIndex::describe(const DevicePointCloud& layer) const {
+  std::vector<uint8_t> d((size_t)params_.n_rings * params_.n_sectors);
+  check(mh_place_describe(layer.handle(), &params_, d.data(), MH_MEM_HOST), "mh_place_describe");
+  return d;
+}
+std::vector<PlaceIndex::Match> PlaceIndex::query(const DevicePointCloud& layer) const {
+  const std::vector<uint8_t> q = describe(layer);
+  std::vector<mh_place_match> out(frame_of_.size());
+  check(mh_place_search(db_, q.data(), MH_MEM_HOST, out.data(), MH_MEM_HOST), "mh_place_search");
+  std::vector<Match> m(out.size());
+  for (size_t k = 0; k < out.size(); k++) m[k] = Match{frame_of_[k], out[k].shift, out[k].dist};
+  std::stable_sort(m.begin(), m.end(), [](const Match& a, const Match& b) { return a.dist != b.dist ? a.dist < b.dist : a.frame < b.frame; });
+  return m;
+}
+
 void LidarOdometry::serve_relocalization(double t, ScanRecord& rec) {
   StageTimer tt(profile_, "onLidar.2.relocalize");
   ICP& icp = *icp_[1];
@@ -1233,8 +1366,12 @@ void LidarOdometry::serve_relocalization(double t, ScanRecord& rec) {
     throw std::runtime_error("LidarOdometry: relocalization: the layers '" + gname + "' / '" + lname + "' of the no-motion-model ICP block are not among this scan's");
   const double thr = reloc_score_threshold(gname);
   const double step = reloc_opts_.step_xy > 0 ? reloc_opts_.step_xy : thr;
-  const std::vector<TPose3D> cand = relocalization_grid(reloc_request_->mean.asTPose(), reloc_request_->cov, step,
-                                                        reloc_opts_.step_yaw_deg * kDeg2Rad, reloc_opts_.sigmas, reloc_opts_.max_candidates);
+  // the candidate list: a grid around the given pose, or the grids around the key-frames the place search kept; everything
+  // below is the same for both requests
+  const std::vector<TPose3D> cand = reloc_request_->in_keyframes
+                                        ? place_candidates(rec, step)
+                                        : relocalization_grid(reloc_request_->mean.asTPose(), reloc_request_->cov, step,
+                                                              reloc_opts_.step_yaw_deg * kDeg2Rad, reloc_opts_.sigmas, reloc_opts_.max_candidates);
   rec.relocalization_tried = true;
   rec.reloc_candidates = (uint32_t)cand.size();
   // ---- score: one launch over all candidates
@@ -1357,6 +1494,8 @@ void LidarOdometry::reset() {
   initial_localization_done_ = false;
   reloc_request_.reset();
   kf_store_.reset(loaded_keyframes_);  // (likewise: the store starts from the loaded file's frames again)
+  place_index_.reset();                // (... and the place index follows it from its first frame)
+  place_frames_seen_ = 0;
   kf_targets_known_ = false;  // (a loaded header is held against the plan's maps once they exist: check_loaded_keyframe_targets)
   if (!loaded_maps_.empty()) restore_loaded_maps();  // (the reference's reset() runs initialize() again: the file is loaded again)
 }

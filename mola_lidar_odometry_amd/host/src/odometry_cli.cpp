@@ -112,6 +112,7 @@ struct RunOptions {
   std::string scan_log;       // CSV of per-scan registration times and layer / map sizes
   std::string save_local_map;  // --save-local-map: the local maps at the end of the sequence (FILE_<k> for several sequences)
   std::string output_simplemap;    // --output-simplemap: record key-frames (params.simplemap.generate) and save them at the end (FILE_<k> likewise)
+  bool relocalize_in_keyframes = false;  // --relocalize-in-keyframes: LidarOdometry::relocalizeInKeyFrames() before the first scan
   std::string output_session_map;  // --output-session-map: ... and the maps of the whole drive built from them, as a local-map file (FILE_<k> likewise)
 };
 
@@ -231,6 +232,7 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
     lo.initialize(cfg);
     stamp("pipeline initialised");
     if (batcher) lo.setAlignBatcher(batcher);
+    if (opt.relocalize_in_keyframes) lo.relocalizeInKeyFrames();  // served by the first scan that reaches registration
 
     std::vector<float> cur, nxt;  // both stay alive while the driver may still read them
     if (!files.empty()) cur = read_bin(files[0]);
@@ -318,7 +320,7 @@ int main(int argc, char** argv) {
   std::string build_from;  // --build-session-map
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
-                      "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE]\n"
+                      "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE] [--relocalize-in-keyframes]\n"
                       "       molahip-lo-cli --build-session-map KEYFRAMES --save-local-map FILE [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
@@ -329,6 +331,9 @@ int main(int argc, char** argv) {
                       "  --output-session-map: ... and build the maps of the whole drive from them into FILE (FILE_<k> for several sequences),\n"
                       "  a local-map file like --save-local-map's\n"
                       "  --build-session-map: no sequence is run: the maps are built from the key-frame file KEYFRAMES into --save-local-map's FILE\n"
+                      "  --relocalize-in-keyframes: the vehicle is found in a saved session without a prior pose: place recognition over the\n"
+                      "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
+                      "  one sequence per device only\n"
                       "  --devices: the sequences are spread over the listed GPUs (longest first onto the least loaded device)\n";
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
@@ -350,6 +355,7 @@ int main(int argc, char** argv) {
       else if (a == "--output-simplemap") opt.output_simplemap = val("--output-simplemap");
       else if (a == "--output-session-map") opt.output_session_map = val("--output-session-map");
       else if (a == "--build-session-map") build_from = val("--build-session-map");
+      else if (a == "--relocalize-in-keyframes") opt.relocalize_in_keyframes = true;
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
       else if (a == "--plan-only") plan_only = true;
@@ -419,6 +425,12 @@ int main(int argc, char** argv) {
   std::vector<std::shared_ptr<mp2p_icp_hip::AlignBatcher>> batchers(D);
   std::vector<size_t> per_slot(D, 0);
   for (size_t k = 0; k < N; k++) per_slot[slot[k]]++;
+  if (opt.relocalize_in_keyframes && N > 1)
+    for (size_t d = 0; d < D; d++)
+      if (per_slot[d] > 1) {  // (those sequences share an AlignBatcher, which has no slot for a relocalization's extra alignments)
+        fprintf(stderr, "molahip-lo-cli: --relocalize-in-keyframes takes one sequence per device; device %d would run %zu\n", devices[d], per_slot[d]);
+        return 2;
+      }
   const auto t0 = std::chrono::steady_clock::now();
   {  // the HIP runtime is initialised ONCE, here, inside the measured wall clock -- eight threads doing it at the same moment took
      // 0.20 s to their first context against 0.12 s (MOLAHIP_STARTUP_LOG=1)

@@ -319,6 +319,47 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       if (!local_map_file.empty()) molahip_host::write_local_map_file(local_map_file, recs);
     }
     return maps2list(recs); }, py::arg("frames"), py::arg("max_points_per_pass") = 0, py::arg("local_map_file") = "");
+  // place recognition over key-frames (mola_hip::PlaceIndex): the descriptor parameters as keywords, key-frame sets as the dicts above
+  auto place_params = [](uint32_t rings, uint32_t sectors, float min_range, float max_range, float z_min, float z_max) {
+    mh_place_params p{};
+    p.n_rings = rings; p.n_sectors = sectors; p.min_range = min_range; p.max_range = max_range; p.z_min = z_min; p.z_max = z_max;
+    return p;
+  };
+  auto desc2array = [](const std::vector<uint8_t>& d, const mh_place_params& p) {
+    py::array_t<uint8_t> a({(py::ssize_t)p.n_rings, (py::ssize_t)p.n_sectors});
+    std::copy(d.begin(), d.end(), a.mutable_data());
+    return a;
+  };
+  py::class_<mola_hip::PlaceIndex>(m, "PlaceIndex")
+      .def(py::init([place_params](uint32_t rings, uint32_t sectors, float min_range, float max_range, float z_min, float z_max) {
+             return std::make_unique<mola_hip::PlaceIndex>(place_params(rings, sectors, min_range, max_range, z_min, z_max)); }),
+           py::arg("n_rings") = 20, py::arg("n_sectors") = 64, py::arg("min_range") = 1.0f, py::arg("max_range") = 80.0f,
+           py::arg("z_min") = -3.0f, py::arg("z_max") = 27.0f)
+      .def("add_keyframes", [dict2kfset](mola_hip::PlaceIndex& ix, const py::object& frames, size_t first) {
+        const molahip_host::KeyFrameSet set = py::isinstance<py::str>(frames) ? molahip_host::read_keyframe_file(frames.cast<std::string>())
+                                                                             : dict2kfset(frames.cast<py::dict>());
+        return ix.addKeyFrames(set, first); }, py::arg("frames"), py::arg("first") = 0)
+      // [(frame, shift, dist)] ranked by (dist ascending, frame ascending)
+      .def("query", [](const mola_hip::PlaceIndex& ix, py::array_t<float, py::array::c_style | py::array::forcecast> xyz) {
+        auto c = make_cloud(xyz);
+        DevicePointCloud d(DeviceContext::Default());
+        d.setPoints(c->x.data(), c->y.data(), c->z.data(), c->size());
+        py::list out;
+        for (const auto& k : ix.query(d)) out.append(py::make_tuple(k.frame, k.shift, k.dist));
+        return out; })
+      .def("size", &mola_hip::PlaceIndex::size);
+  // the descriptor of one layer (xyz [n, 3], vehicle frame): uint8 [n_rings, n_sectors]
+  m.def("place_describe", [place_params, desc2array](py::array_t<float, py::array::c_style | py::array::forcecast> xyz, uint32_t rings, uint32_t sectors,
+                                                     float min_range, float max_range, float z_min, float z_max) {
+    const mh_place_params p = place_params(rings, sectors, min_range, max_range, z_min, z_max);
+    auto c = make_cloud(xyz);
+    DevicePointCloud d(DeviceContext::Default());
+    d.setPoints(c->x.data(), c->y.data(), c->z.data(), c->size());
+    std::vector<uint8_t> desc((size_t)rings * sectors);
+    mp2p_icp_hip::check(mh_place_describe(d.handle(), &p, desc.data(), MH_MEM_HOST), "mh_place_describe");
+    return desc2array(desc, p); },
+        py::arg("layer"), py::arg("n_rings") = 20, py::arg("n_sectors") = 64, py::arg("min_range") = 1.0f, py::arg("max_range") = 80.0f,
+        py::arg("z_min") = -3.0f, py::arg("z_max") = 27.0f);
   // the key-frame decision on its own (host logic only: testable without a device; the driver holds one)
   py::class_<mola_hip::KeyFrameStore>(m, "KeyFrameStore")
       .def(py::init<bool>(), py::arg("measure_from_last_kf_only") = false)
@@ -353,6 +394,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["relocalization_tried"] = r.relocalization_tried; d["relocalized"] = r.relocalized; d["reloc_candidates"] = r.reloc_candidates;
     d["reloc_best_n_paired"] = r.reloc_best_n_paired; d["reloc_best_quality"] = r.reloc_best_quality; d["reloc_ranks"] = r.reloc_ranks;
     d["simplemap_keyframe"] = r.simplemap_keyframe; d["simplemap_frame"] = r.simplemap_frame;
+    d["place_tried"] = r.place_tried; d["place_frames"] = r.place_frames; d["place_shifts"] = r.place_shifts; d["place_dists"] = r.place_dists;
     return d;
   };
   py::class_<LidarOdometry> lo_class(m, "LidarOdometry", py::dynamic_attr());
@@ -460,6 +502,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         if (mean.size() != 12 || cov.size() != 36) throw std::runtime_error("need 12 pose values and 36 covariance values");
         CPose3D P; std::copy(mean.begin(), mean.end(), P.T);
         lo.relocalizeNearPose(P, cov.data()); })
+      .def("relocalizeInKeyFrames", &LidarOdometry::relocalizeInKeyFrames)
       .def("relocalizationPending", &LidarOdometry::relocalizationPending)
       .def("initialLocalization", [](const LidarOdometry& lo) {
         const auto& il = lo.initialLocalization();
@@ -474,6 +517,9 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         py::dict d;
         d["score_threshold"] = r.score_threshold; d["step_xy"] = r.step_xy; d["step_yaw_deg"] = r.step_yaw_deg; d["sigmas"] = r.sigmas;
         d["refine_top_k"] = r.refine_top_k; d["max_candidates"] = r.max_candidates;
+        d["place_rings"] = r.place_rings; d["place_sectors"] = r.place_sectors; d["place_min_range"] = r.place_min_range;
+        d["place_max_range"] = r.place_max_range; d["place_z_min"] = r.place_z_min; d["place_z_max"] = r.place_z_max;
+        d["place_top_k"] = r.place_top_k; d["place_sigma_xy"] = r.place_sigma_xy; d["place_sigma_yaw_deg"] = r.place_sigma_yaw_deg;
         return d; })
       .def("loadExistingLocalMap", [](const LidarOdometry& lo) { return lo.params().load_existing_local_map; })
       .def("setIntensityInput", &LidarOdometry::setIntensityInput)
