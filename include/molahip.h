@@ -285,10 +285,8 @@ MH_API mh_status mh_scan_update_aos(mh_scan* scan, const void* data, size_t n, s
  * off_i = -1 case.  mh_scan_update and mh_scan_update_aos leave a scan without intensity. */
 MH_API mh_status mh_scan_update_aos_i(mh_scan* scan, const void* data, size_t n, size_t point_step, size_t off_x,
                                       size_t off_y, size_t off_z, int64_t off_t, int64_t off_i, int32_t mem);
-/* Optional: queue the construction of the scan's search order for the tile matcher (large layers: the points sorted by
- * 2x2x2-voxel block of the local frame and cut into tiles) right behind an upload, for the voxel size of the
- * map it will be aligned against, so that it overlaps whatever else the device is doing.  Asynchronous on the context's
- * stream.  mh_icp_align / mh_icp_align_batch build it themselves when it is missing or stale. */
+/* Kept for the ABI: checks its arguments (scan, voxel_size > 0) and does nothing else.  It used to queue the scan's search
+ * order for the tile matcher, which was removed; the matchers search the scan as it is. */
 MH_API mh_status mh_scan_prepare(const mh_scan* scan, float voxel_size);
 MH_API mh_status mh_scan_destroy(mh_scan* scan);
 MH_API mh_status mh_scan_size(const mh_scan* scan, uint64_t* n);
@@ -448,7 +446,7 @@ MH_API mh_status mh_scan_edges_from_range_image(mh_ctx* ctx, const uint16_t* ran
  *     d = 0.5f*(tmin_k + tmax_k) for MH_TS_MIDDLE_IS_ZERO, tmin_k for MH_TS_EARLIEST_IS_ZERO;  t' = (t - d) + time_offset, in float
  *   time stamp, MH_TS_NONE: t' = t.   Intensity: copied.
  * `out` carries time stamps only when every non-empty source does (a mix: MH_ERR_INVALID_ARGUMENT), and intensity likewise; it
- * carries no src_idx, and its tile order is dropped, as after mh_scan_update_aos_i.  Empty sources are legal and contribute
+ * carries no src_idx, as after mh_scan_update_aos_i.  Empty sources are legal and contribute
  * nothing; a source may appear more than once.  Refused with a message (mh_last_error_string) before any device work, `out`
  * untouched, all MH_ERR_INVALID_ARGUMENT: n_sources 0 or above MH_MAX_MERGE_SOURCES, a NULL pointer, `out` among the sources,
  * scans of different contexts, a bad timestamp_method, a total of 2^31 - 16 points or more.  Asynchronous on the context's
@@ -839,9 +837,9 @@ MH_API mh_status mh_icp_align_prefers_solo(const mh_scan* scan, const mh_icp_par
  * each other and that were run again launch by launch (same result bit for bit; expected to stay 0).  Either may be NULL. */
 MH_API void mh_debug_loop_stats(uint64_t* loops_started, uint64_t* loops_abandoned);
 
-/* 1 when the library was built with -DMH_DEV_VARIANTS (tools/build_variants.sh): the matcher families that were measured against
- * the product kernels and lost -- MH_MATCH=t (tile matcher, map records staged in LDS), w (wave matcher), o (sorted scan) -- are
- * then selectable for A/B runs and parity tests.  The shipped library returns 0 and rejects those three values of MH_MATCH. */
+/* Always 0.  It used to tell the development library from the shipped one; the development library no longer exists: the matcher
+ * families it carried -- MH_MATCH=t (tile matcher, map records staged in LDS), w (wave matcher), o (sorted scan) -- lost to the
+ * product kernels and were removed, and mh_icp_align / mh_icp_align_batch reject those three letters. */
 MH_API int32_t mh_debug_dev_variants(void);
 
 /* Results::finalPairings.paired_pt2pl [U] of the LAST mh_icp_align run on `scan`'s context (arrays in `mem`, scan-size
@@ -853,7 +851,7 @@ MH_API mh_status mh_icp_get_pt2pl_pairs(const mh_scan* scan, const mh_pairs_pl_o
  * budgets and hook check points), guesses + 12*i, priors[i] (array or entries may be NULL), and writes results[i]; every
  * result is bitwise what mh_icp_align gives for that job alone.  Jobs that run the same kernel chain advance in LOCK
  * STEP: each kernel of an iteration is one launch over all of them (the jobs' tails fill each other's idle lanes) --
- * large layers (quad / tile matcher), 8-12 k-point layers (row matcher with the fused accumulation), layers up to 8 k
+ * large layers (quad / plan-scan matcher), 8-12 k-point layers (row matcher with the fused accumulation), layers up to 8 k
  * points (k_step16: search + sums per launch, the Gauss-Newton step carried into the next launch; also with
  * Matcher_Point2Plane on NDT maps); the rest is interleaved, one stream per job.  With profile = 2, job 0's match_kernel_ms is its share of the lock-step match
  * launches.  Work still queued on the jobs' own streams (asynchronous uploads, de-skew, filters) is ordered before the

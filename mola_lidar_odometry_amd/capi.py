@@ -441,7 +441,7 @@ def loop_stats():
 
 
 def dev_variants() -> bool:
-    """True when the loaded library is the development build (tools/build_variants.sh): MH_MATCH=t|w|o are selectable."""
+    """Always False: the development library (the tile / wave / sorted-scan matchers, MH_MATCH=t|w|o) no longer exists."""
     return bool(lib().mh_debug_dev_variants())
 
 
@@ -784,7 +784,7 @@ class Scan:
         _chk(lib().mh_scan_update(self._h, _vp(x), _vp(y), _vp(z), len(x), MEM_HOST))
 
     def prepare(self, voxel_size: float):
-        """Queue the build of the tile matcher's search order behind whatever was uploaded last (asynchronous)."""
+        """Kept for the ABI: mh_scan_prepare checks its arguments and does nothing else (the tile matcher it served was removed)."""
         _chk(lib().mh_scan_prepare(self._h, float(voxel_size)))
         return self
 

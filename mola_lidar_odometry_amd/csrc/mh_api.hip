@@ -61,7 +61,6 @@ mh_status scan_alloc(mh_scan* s, size_t n, bool with_t, bool with_src, bool with
   s->src = with_src ? (const uint32_t*)(s->aux.as<char>() + stride) : nullptr;
   s->i = with_i ? s->ibuf.as<const float>() : nullptr;
   s->n = n;
-  scan_drop_tiles(s);
   return MH_OK;
 }
 
@@ -276,7 +275,6 @@ static mh_status scan_set(mh_scan* s, const float* x, const float* y, const floa
   s->src = nullptr;
   s->i = nullptr;
   s->n = n;
-  scan_drop_tiles(s);
   return MH_OK;
 }
 
@@ -292,7 +290,6 @@ mh_status mh_scan_create(mh_ctx* ctx, const float* x, const float* y, const floa
     s->xyz.release();
     s->aux.release();
     s->ibuf.release();
-    scan_free_tiles(s);
     delete s;
     return st;
   }
@@ -312,7 +309,6 @@ mh_status mh_scan_destroy(mh_scan* scan) {
   scan->xyz.release();
   scan->aux.release();
   scan->ibuf.release();
-  scan_free_tiles(scan);
   delete scan;
   return MH_OK;
 }
@@ -323,14 +319,12 @@ mh_status mh_scan_size(const mh_scan* scan, uint64_t* n) {
   return MH_OK;
 }
 
-#ifndef MH_DEV_VARIANTS
-// The search order this call queues is what the tile / wave / sorted matchers read (mh_tile.hip: development library only); the
-// shipped matchers search the scan as it is, so there is nothing to prepare.
+// Kept for the ABI: the search order this call used to queue was read by the tile / wave / sorted-scan matchers, which were
+// removed; the matchers search the scan as it is, so there is nothing to prepare.
 mh_status mh_scan_prepare(const mh_scan* scan, float voxel_size) {
   MH_REQUIRE(scan, "null scan");
   MH_REQUIRE(voxel_size > 0.f, "voxel_size must be > 0");
   return MH_OK;
 }
-#endif
 
 }  // extern "C"

@@ -23,7 +23,6 @@
 //                                  lock-step batch behind mh_icp_align_layers* and mh_icp_align_layers_batch*
 //   mh_icp_batch.inl               mh_icp_align_batch (lock-step groups)
 //   mh_icp_api.inl                 matcher- / solver-granular entry points (mh_nn_search*, mh_gn_solve, mh_covariance)
-//   mh_dev_variants.h              (-DMH_DEV_VARIANTS only) the tile / wave / sorted-scan matchers that lost to the product kernels
 //
 // Kernel sequence per ICP iteration of a LARGE layer (everything stays in HBM/L2; the host never sees pairings):
 //   k_match_flat     a wave per 64 scan points: transform, exact bounded search (plan / scan), threshold test, store pairing
@@ -374,21 +373,16 @@ enum class Matcher : int {
   Literal = 1,  // "x": one lane per point, the literal 27-voxel scan of the reference (A/B baseline)        -> k_match<true, 0>
   Quad = 4,     // "q": a DPP quad per scan point, merged candidate scans (the default of rounds 1-4)        -> k_match4 + k_accum
   Row = 5,      // "s": a DPP row (16 lanes) per point (default up to kRowMaxPoints)                         -> k_match16 + k_accum
-  Tile = 6,     // "t": a workgroup per tile of the spatially sorted scan, map records staged in LDS        -> k_match_tile + k_accum
-  Wave = 7,     // "w": a wave per tile of 64 sorted points, wave-uniform candidates through the scalar path -> k_match_wave + k_accum
-  Ordered = 8,  // "o": "q" over the scan in search order (the sort of "t" / "w", no tiles)                   -> k_match4 + k_accum
   Flat = 9,     // "f": plan / scan (mh_nn_flat.h; default above kRowMaxPoints): a wave per 64 points, per-point / per-voxel /
                 //      per-record work each on all 64 lanes                                                  -> k_match_flat + k_accum
-};  // ("t", "w", "o": mh_dev_variants.h, the development library only)
+};  // (6, 7, 8 were "t", "w", "o": the tile / wave / sorted-scan matchers, removed -- profiles/r02_tile_matcher.md; the letters are refused)
 // the one-lane matchers sum the first Gauss-Newton step themselves; every other one leaves it to k_accum (or the row kernel)
 inline bool one_lane(Matcher m) { return m == Matcher::Point || m == Matcher::Literal; }
-// the matchers that search the scan in its sorted order (mh_tile.hip)
-inline bool sorted_scan(Matcher m) { return m == Matcher::Tile || m == Matcher::Wave || m == Matcher::Ordered; }
 
 enum class Loop { None, Icp16, Icpw };  // one-launch loop: k_icp16 (a DPP row per point) | k_icpw (plan / scan search)
 struct AlignPlan {
   Matcher matcher = Matcher::Row;
-  char dev_matcher = 0;     // MH_MATCH names a matcher of the development library, this one lacks it (start() fails)
+  char retired = 0;         // MH_MATCH names a matcher that was removed ("t", "w", "o"): start() fails
   bool fused16 = false;     // the row kernel accumulates the first Gauss-Newton step itself (layers above the one-workgroup size)
   bool step_chain = false;  // k_step16 launches (row-kernel layers up to kStepMaxPoints)
   bool streaming = false;   // run_streaming(): iterations enqueued one by one behind the device's published progress
@@ -409,13 +403,7 @@ AlignPlan plan_alignment(const Switches& sw, size_t n, bool pl, uint32_t matched
     case 's': a.matcher = Matcher::Row; break;
     case 'p': a.matcher = Matcher::Point; break;
     case 'x': a.matcher = Matcher::Literal; break;
-#ifdef MH_DEV_VARIANTS
-    case 't': a.matcher = Matcher::Tile; break;
-    case 'w': a.matcher = Matcher::Wave; break;
-    case 'o': a.matcher = Matcher::Ordered; break;
-#else
-    case 't': case 'w': case 'o': a.dev_matcher = sw.match; a.matcher = Matcher::Flat; break;
-#endif
+    case 't': case 'w': case 'o': a.retired = sw.match; a.matcher = Matcher::Flat; break;
   }
   if (map && a.matcher == Matcher::Literal && map->view(sw).ndt) a.matcher = Matcher::Point;  // "x" walks contiguous z-runs; NDT maps interleave statistics records
   // MH_MATCHED_POINTS_SKIP (U12): the point matcher has to know the plane matcher's verdict for the same point -- the row
@@ -544,16 +532,13 @@ struct AlignJob {
     sk = make_solve_params(p, prior, mk, trace ? ctx->trace.as<mh_icp_iter>() : nullptr);
     plan = plan_alignment(*sw, scan->n, pl, p->matched_points, map, prof,
                           p->poll_every == 0 && !defer_upload && ctx->d_progress != nullptr);
-    if (plan.dev_matcher)
-      return fail(MH_ERR_INVALID_ARGUMENT, "MH_MATCH=%c names a development matcher: build tools/variants/libmolahip_dev.so (tools/build_variants.sh)", plan.dev_matcher);
+    if (plan.retired)
+      return fail(MH_ERR_INVALID_ARGUMENT, "MH_MATCH=%c names a matcher that was retired (the tile / wave / sorted-scan matchers): no build has it", plan.retired);
     const Matcher mt = plan.matcher;
     streaming = plan.streaming;
     sk.host_progress = streaming ? ctx->d_progress : nullptr;
     nb = nblk(scan->n);
-#ifdef MH_DEV_VARIANTS
-    if (sorted_scan(mt)) MH_TRY(scan_build_tiles(scan, map->inv_vs, mt == Matcher::Wave ? 64u : 256u));
-#endif
-    if (mt == Matcher::Quad || mt == Matcher::Flat || sorted_scan(mt)) {  // nn_search_quad / the plan-scan matcher read the map's sub-voxel index
+    if (mt == Matcher::Quad || mt == Matcher::Flat) {  // nn_search_quad / the plan-scan matcher read the map's sub-voxel index
       MH_TRY(map_ensure_qidx(*sw, map, ctx->stream));
       if (!map->view(*sw).pts_q) return fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (matcher variant %d needs it)", (int)mt);
     }
@@ -672,9 +657,6 @@ struct AlignJob {
     const uint32_t n = (uint32_t)scan->n;
     const MapView mv = map->view(*sw);
     const Matcher mt = plan.matcher;
-#ifdef MH_DEV_VARIANTS
-    if (mt == Matcher::Tile || mt == Matcher::Wave) MH_TRY(scan_tiles_ready(scan));  // the launch grid needs the tile count
-#endif
     const uint32_t m = (p->max_iterations - enqueued) < chunk ? (p->max_iterations - enqueued) : chunk;
     PoseArg dummy{};
     double* part = ctx->partials.as<double>();
@@ -749,47 +731,15 @@ struct AlignJob {
           else if (!plan.fused16)
             hipLaunchKernelGGL(k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                                ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nbm);
-#ifdef MH_DEV_VARIANTS
-        } else if (mt == Matcher::Wave) {
-#ifdef MH_DEBUG_WAVETRACE
-          MH_LAUNCH_WAVE(sw->wave_lds, s, ctx->d_state, scan, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), MH_WT_G);
-#else
-          MH_LAUNCH_WAVE(sw->wave_lds, s, ctx->d_state, scan, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), );
-#endif
-          if (prof) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));  // the match kernel alone
-          hipLaunchKernelGGL(k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
-                             ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
-        } else if (mt == Matcher::Tile) {
-          hipLaunchKernelGGL(k_match_tile, dim3(scan->n_tiles), dim3(kTileThreads), 0, s, ctx->d_state, scan->sx, scan->sy, scan->sz,
-                             scan->perm, scan->tile_start, scan->n_tiles, mv, ctx->pair_q.as<float4>(),
-                             ctx->pair_gidx.as<uint32_t>()
-#ifdef MH_DEBUG_WAVETRACE
-                             , g_wtrace
-#endif
-          );
-          if (prof) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));  // the match kernel alone
-          hipLaunchKernelGGL(k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
-                             ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
-#endif
         } else if (mt == Matcher::Flat) {
           hipLaunchKernelGGL(k_match_flat, dim3(nblk_flat(n)), dim3(kFlatThreads), 0, s, ctx->d_state, scan->x, scan->y, scan->z, n, mv,
-                             ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), (const uint32_t*)nullptr);
+                             ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>());
           if (prof) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));  // the match kernel alone
           hipLaunchKernelGGL(k_accum<true>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                              ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
-        } else if (mt == Matcher::Quad || mt == Matcher::Ordered) {
-#ifdef MH_DEV_VARIANTS
-          const bool ord = mt == Matcher::Ordered;  // the scan in search order
-#else
-          const bool ord = false;
-#endif
-          hipLaunchKernelGGL(k_match4, dim3((uint32_t)((4ull * n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ctx->d_state,
-                             ord ? scan->sx : scan->x, ord ? scan->sy : scan->y, ord ? scan->sz : scan->z, n, mv,
-                             ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), ord ? scan->perm : (const uint32_t*)nullptr
-#ifdef MH_DEBUG_WAVETRACE
-                             , g_wtrace
-#endif
-          );
+        } else if (mt == Matcher::Quad) {
+          hipLaunchKernelGGL(k_match4, dim3((uint32_t)((4ull * n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, ctx->d_state, scan->x, scan->y,
+                             scan->z, n, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>());
           if (prof) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));  // the match kernel alone
           hipLaunchKernelGGL(k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                              ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
@@ -845,8 +795,6 @@ struct AlignJob {
                                        (unsigned long long)(pl ? ctx->pl_c.p : nullptr),
                                        (unsigned long long)(pl ? ctx->pl_n.p : nullptr),
                                        (unsigned long long)(pl ? ctx->partials_b.p : nullptr),
-                                       sorted_scan(mt) ? (unsigned long long)scan->sx : (unsigned long long)mt,
-                                       sorted_scan(mt) ? (unsigned long long)scan->n_tiles : 0ull,
                                        (unsigned long long)mv.pts_q};  // (a word each: no XOR folding)
       static_assert(sizeof(kv) <= sizeof(key), "graph key too small");
       memcpy(key, kv, sizeof(kv));
@@ -1030,11 +978,7 @@ mh_status mh_icp_align_prefers_solo(const mh_scan* scan, const mh_icp_params* p,
 }
 
 int32_t mh_debug_dev_variants(void) {
-#ifdef MH_DEV_VARIANTS
-  return 1;
-#else
   return 0;
-#endif
 }
 
 void mh_debug_loop_stats(uint64_t* loops_started, uint64_t* loops_abandoned) {

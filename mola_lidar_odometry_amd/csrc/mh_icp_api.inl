@@ -1,40 +1,6 @@
 // mh_icp_api.inl -- the matcher- and solver-granular entry points (mh_nn_search*, mh_gn_solve, mh_covariance: what the
 // Matcher_* / Solver_GaussNewton plugin classes call).  Included by mh_icp.hip inside its extern "C" block.
-
-namespace {
-#ifdef MH_DEV_VARIANTS
-// MH_MATCH=t: the matcher-granular entry points run the tile matcher too (the parity tests drive every search kernel
-// through mh_nn_search / mh_nn_search_dense); thr2 = +inf: no threshold
-mh_status launch_tile_search(const Switches& sw, const mh_map* map, const mh_scan* scan, const double T[12], float thr2, float ang2) {
-  mh_ctx* ctx = scan->ctx;
-  const bool wave = tile_points(sw) == 64u;
-  MH_TRY(scan_build_tiles(scan, map->inv_vs, wave ? 64u : 256u));
-  MH_TRY(scan_tiles_ready(scan));
-  MH_TRY(map_ensure_qidx(sw, map, ctx->stream));  // (sparse tiles are searched by quads)
-  MH_HIP(mh::wait_stream(ctx->stream));  // the pinned state mirror may still be travelling
-  init_state(ctx->h_state, T);
-  ctx->h_state->cur_thr2 = thr2;
-  ctx->h_state->cur_ang2 = ang2;
-  MH_HIP(hipMemcpyAsync(ctx->d_state, ctx->h_state, sizeof(IcpDeviceState), hipMemcpyHostToDevice, ctx->stream));
-  if (scan->n_tiles && wave)
-    MH_LAUNCH_WAVE(sw.wave_lds, ctx->stream, ctx->d_state, scan, map->view(sw), ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), MH_WT_NULL);
-  else if (scan->n_tiles)
-    hipLaunchKernelGGL(k_match_tile, dim3(scan->n_tiles), dim3(kTileThreads), 0, ctx->stream, ctx->d_state, scan->sx, scan->sy,
-                       scan->sz, scan->perm, scan->tile_start, scan->n_tiles, map->view(sw), ctx->pair_q.as<float4>(),
-                       ctx->pair_gidx.as<uint32_t>()
-#ifdef MH_DEBUG_WAVETRACE
-                       , (unsigned long long*)nullptr
-#endif
-    );
-  MH_HIP(hipGetLastError());
-  return MH_OK;
-}
-inline bool tile_search_forced(const Switches& sw) { return sw.match == 't' || sw.match == 'w'; }
-#else  // the shipped library: the matcher-granular entry points run k_match<false, 1> whatever MH_MATCH says
-inline bool tile_search_forced(const Switches&) { return false; }
-inline mh_status launch_tile_search(const Switches&, const mh_map*, const mh_scan*, const double*, float, float) { return MH_OK; }
-#endif
-}  // namespace
+// The searches here run k_match<false, 1> whatever MH_MATCH says.
 
 mh_status mh_nn_search(const mh_map* map, const mh_scan* scan, const double T[12], double threshold,
                        double threshold_angular_deg, const mh_pairs_out* out, int32_t mem, mh_match_info* info) {
@@ -60,12 +26,9 @@ mh_status mh_nn_search(const mh_map* map, const mh_scan* scan, const double T[12
   const double ang = threshold_angular_deg * 3.14159265358979323846 / 180.0;
   mk.ang2 = (float)(ang * ang);
   MH_TRY(upload_params(ctx, mk, sk0));
-  if (tile_search_forced(sw))
-    MH_TRY(launch_tile_search(sw, map, scan, T, (float)(threshold * threshold), mk.ang2));
-  else
-    hipLaunchKernelGGL((k_match<false, 1>), dim3(nblk(scan->n)), dim3(kBlock), 0, ctx->stream, ctx->d_state, Ta,
-                       (float)(threshold * threshold), 1u, &ctx->d_params->mk, scan->x, scan->y, scan->z, (uint32_t)scan->n, map->view(sw),
-                       ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), (double*)nullptr, 0u);
+  hipLaunchKernelGGL((k_match<false, 1>), dim3(nblk(scan->n)), dim3(kBlock), 0, ctx->stream, ctx->d_state, Ta,
+                     (float)(threshold * threshold), 1u, &ctx->d_params->mk, scan->x, scan->y, scan->z, (uint32_t)scan->n, map->view(sw),
+                     ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), (double*)nullptr, 0u);
   MH_HIP(hipGetLastError());
   mh_pairs_out none{};
   uint64_t np = 0;
@@ -140,13 +103,9 @@ mh_status mh_nn_search_dense(const mh_map* map, const mh_scan* scan, const doubl
   SolveK sk0{};
   hipStream_t s = ctx->stream;
   MH_TRY(upload_params(ctx, mk, sk0));
-  if (tile_search_forced(sw))
-    MH_TRY(launch_tile_search(sw, map, scan, T, __builtin_inff(), 0.f));
-  else
-    hipLaunchKernelGGL((k_match<false, 1>), dim3(nblk(n)), dim3(kBlock), 0, s, ctx->d_state, Ta, 0.f, 0u,
-                       &ctx->d_params->mk, scan->x,
-                       scan->y, scan->z, (uint32_t)n, map->view(sw), ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(),
-                       (double*)nullptr, 0u);
+  hipLaunchKernelGGL((k_match<false, 1>), dim3(nblk(n)), dim3(kBlock), 0, s, ctx->d_state, Ta, 0.f, 0u, &ctx->d_params->mk, scan->x,
+                     scan->y, scan->z, (uint32_t)n, map->view(sw), ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(),
+                     (double*)nullptr, 0u);
   uint32_t* o_gi = global_idx;
   float *o_x = gx, *o_y = gy, *o_z = gz, *o_d2 = d2;
   const size_t n4 = ((n + 63) / 64) * 64;

@@ -29,12 +29,6 @@ void fill_batch_desc(const AlignJob& j, BatchJob& d) {
   }
   d.sched_dst = j.ctx->sched.as<uint32_t>();
   d.sched_dwords = (uint32_t)(2 * j.nsched_pending);
-  if (sorted_scan(j.plan.matcher)) {
-    d.sx = j.scan->sx; d.sy = j.scan->sy; d.sz = j.scan->sz;
-    d.perm = j.scan->perm;
-    d.tile_start = j.scan->tile_start;
-    d.n_tiles = j.scan->n_tiles;
-  }
 }
 
 // Work still queued on a job's own stream (asynchronous uploads, filters, de-skew, an earlier alignment) must be
@@ -160,15 +154,14 @@ mh_status gather_states(mh_ctx* lead, const BatchJob* dj, uint32_t A, IcpDeviceS
 // Lock-step mode: every kernel of an iteration is ONE launch over all jobs of a group (blockIdx.y = job).  The jobs'
 // tails fill each other's idle lanes, which concurrent streams do not achieve (HIP maps them onto four hardware queues
 // whose kernels mostly run one after the other).  A group = the jobs that run the same kernel chain:
-//   quad / tile matcher + k_accum + k_solve (large layers), row matcher with the fused first accumulation (2-12 k
+//   quad / plan-scan matcher + k_accum + k_solve (large layers), row matcher with the fused first accumulation (2-12 k
 //   points), row matcher + one-workgroup accumulate-and-solve (<= 2 k points: what lidar3d-default.yaml feeds), and the
 //   same with Matcher_Point2Plane riding along (lidar3d-ndt.yaml);
 // each job keeps its own parameters (iteration budget, schedules, hook check point, prior), state block, termination
 // flag and iteration count.  Jobs whose chain has no lock-step form (or that are alone in their group) take the
 // per-stream path.
 // (the kinds of the matcher chains are their matchers' numbers: K_ROWF = the row matcher with the fused first accumulation)
-enum LockstepKind { K_NONE = -1, K_QUAD = (int)Matcher::Quad, K_ROWF = (int)Matcher::Row, K_TILE = (int)Matcher::Tile,
-                    K_WAVE = (int)Matcher::Wave, K_ORD = (int)Matcher::Ordered, K_FLAT = (int)Matcher::Flat, K_STEP = 16, K_STEP_PL };
+enum LockstepKind { K_NONE = -1, K_QUAD = (int)Matcher::Quad, K_ROWF = (int)Matcher::Row, K_FLAT = (int)Matcher::Flat, K_STEP = 16, K_STEP_PL };
 struct LockstepGroup {  // (movable, not copyable: the admission)
   int kind = K_NONE;
   std::vector<AlignJob*> jobs;
@@ -312,10 +305,6 @@ mh_status stage_group(const Switches& sw, LockstepGroup& g, const PairsPlan* pp)
   mh_ctx* lead = g.lead;
   MH_TRY(set_device(lead));
   hipStream_t s = lead->stream;
-#ifdef MH_DEV_VARIANTS
-  if (g.kind == K_TILE || g.kind == K_WAVE)
-    for (AlignJob* j : g.jobs) MH_TRY(scan_tiles_ready(j->scan));  // tile counts (the builds were queued by start())
-#endif
   MH_TRY(order_after_job_streams(lead, g.jobs));
   size_t stage_bytes = 0;
   for (AlignJob* j : g.jobs) stage_bytes += kBlockBytes + j->nsched_pending * sizeof(double);
@@ -332,8 +321,6 @@ mh_status stage_group(const Switches& sw, LockstepGroup& g, const PairsPlan* pp)
     uint32_t bm = (uint32_t)((4ull * d.n + kBlock - 1) / kBlock);  // quad
     if (g.kind == K_ROWF) bm = d.nbm;
     if (g.kind == K_FLAT) bm = nblk_flat(d.n);
-    if (g.kind == K_TILE) bm = d.n_tiles;
-    if (g.kind == K_WAVE) bm = d.n_tiles;
     if (g.step_chain()) {  // all jobs' workgroups resident at once: kStepMaxWorkgroups shared between them
       const uint32_t cap = kStepMaxWorkgroups / A ? kStepMaxWorkgroups / A : 1u;
       const uint32_t ng = (d.n + kStepPoints - 1) / kStepPoints;
@@ -385,15 +372,6 @@ mh_status enqueue_group_iteration(const Switches& sw, LockstepGroup& g, bool pr)
   if (pr) MH_HIP(hipEventRecord(g.lead->prof_ev[2 * g.prof_n], s));
   switch (g.kind) {
     case K_ROWF: hipLaunchKernelGGL(k_match16f_b, dim3(g.gx_match, A), dim3(kBlock), 0, s, g.dj); break;
-#ifdef MH_DEV_VARIANTS
-    case K_TILE: hipLaunchKernelGGL(k_match_tile_b, dim3(g.gx_match, A), dim3(kTileThreads), 0, s, g.dj); break;
-    case K_WAVE:
-      if (sw.wave_lds) hipLaunchKernelGGL(k_match_wave_dense_b<true>, dim3(g.gx_match, A), dim3(64), 0, s, g.dj);
-      else hipLaunchKernelGGL(k_match_wave_dense_b<false>, dim3(g.gx_match, A), dim3(64), 0, s, g.dj);
-      hipLaunchKernelGGL(k_match_wave_sparse_b, dim3(g.gx_match, A), dim3(kBlock), 0, s, g.dj);
-      break;
-    case K_ORD: hipLaunchKernelGGL(k_match4o_b, dim3(g.gx_match, A), dim3(kBlock), 0, s, g.dj); break;
-#endif
     case K_FLAT: hipLaunchKernelGGL(k_match_flat_b, dim3(g.gx_match, A), dim3(kFlatThreads), 0, s, g.dj); break;
     default: hipLaunchKernelGGL(k_match4_b, dim3(g.gx_match, A), dim3(kBlock), 0, s, g.dj); break;
   }

@@ -100,10 +100,6 @@ struct BatchJob {
   float4 *pl_c, *pl_n;           // point-to-plane pairings or null
   uint32_t* sched_dst;           // where this job keeps its threshold schedules (staged start-up copy) ...
   uint32_t sched_dwords, stage_off;  // ... their size, and where this job's [state | params | schedules] start in the staging block
-  // tile matcher: the scan in search order (mh_tile.hip)
-  const float *sx, *sy, *sz;
-  const uint32_t *perm, *tile_start;
-  uint32_t n_tiles, tile_pad;
   uint32_t* cp_counts;   // [nb] pairs per 256-point block | [nb] exclusive offsets
   uint32_t* cp_out;      // six arrays of cp_stride entries: local_idx | global_idx | gx | gy | gz | d2
   uint32_t cp_stride, cp_pad;

@@ -137,9 +137,6 @@ struct MapView {  // (k_match_layers, mh_k_layers.h, copies it field by field: k
   // re-ordered by (x half, y half) of the voxel, w = the record's index in `pts` (the reference's scan position: the
   // tie-break); the quadrants' boundaries ride in the count word of the voxel's hash slot (slot_count(), mh_nn_device.h)
   const float4* pts_q;
-#ifdef MH_DEBUG_WAVETRACE
-  uint32_t dbg_stop;  // debug build: leave the quad search after phase N (tools/wavetrace_probe.py)
-#endif
 };
 
 __host__ __device__ inline unsigned long long pack_key(int kx, int ky, int kz) {
@@ -260,9 +257,6 @@ struct mh_map {
     v.ndt = params.ndt_max_eigen_ratio > 0.f ? 1u : 0u;
     v.no_prev_bound = sw.no_prev_bound ? 1u : 0u;
     v.pts_q = qidx_valid ? pts_q.as<float4>() : nullptr;
-#ifdef MH_DEBUG_WAVETRACE
-    v.dbg_stop = sw.dbg_stop;
-#endif
     return v;
   }
 };
@@ -277,20 +271,6 @@ struct mh_scan {
   const float* i = nullptr;       // per-point intensity or null (maps and alignments ignore it)
   const uint32_t* src = nullptr;  // index of each point in the raw scan it was filtered from, or null
   size_t n = 0;
-  // Search order of the tile matcher (mh_tile.hip), a cache that belongs to the point content: the points sorted by
-  // (2x2x2-voxel block of the LOCAL frame, quarter-voxel Morton code inside it) and cut into tiles of <= 256 consecutive
-  // points that never cross a block.  A rigid transform keeps a tile's points together, so the map records one tile needs
-  // fit one workgroup's LDS whatever the pose.  Built lazily (scan_build_tiles), dropped whenever the points change.
-  mutable mh::DevBuf tiles;  // sx | sy | sz | perm | tile_start[n + 1]
-  mutable const float *sx = nullptr, *sy = nullptr, *sz = nullptr;
-  mutable const uint32_t* perm = nullptr;        // sorted position -> index in x/y/z
-  mutable const uint32_t* tile_start = nullptr;  // [n_tiles + 1]
-  mutable uint32_t n_tiles = 0;
-  mutable float tile_inv_vs = 0.f;
-  mutable uint32_t tile_points = 0;
-  mutable bool tiles_valid = false, tiles_pending = false;  // pending: n_tiles still travelling to h_ntiles
-  mutable uint32_t* h_ntiles = nullptr;  // pinned
-  mutable hipEvent_t ev_tiles = nullptr;
 };
 
 namespace mh {
@@ -304,21 +284,6 @@ mh_status stage_in(mh_ctx* ctx, DevBuf& buf, size_t offset_bytes, const void* sr
 mh_status scan_alloc(mh_scan* s, size_t n, bool with_t, bool with_src, bool with_i = false);
 // map (re)build from device arrays; src_ids null = identity.  evict: 0 or {cx,cy,cz,dist_in_grid} voxel test.
 // n_stored: the first n_stored inputs are points the map already stores (accepted by the insertion rules before).
-// sorted copy + tile table of a scan for voxel size 1/inv_vs (no-op when valid); asynchronous on the scan's stream,
-// scan_tiles_ready() waits for the tile count
-#ifdef MH_DEV_VARIANTS  // (mh_tile.hip: the search order of the tile / wave / sorted matchers -- development library only)
-mh_status scan_build_tiles(const mh_scan* s, float inv_vs, uint32_t tile_points);
-uint32_t tile_points(const Switches& sw);
-mh_status scan_tiles_ready(const mh_scan* s);
-void scan_drop_tiles(mh_scan* s);  // host-side bookkeeping only (the points changed)
-void scan_free_tiles(mh_scan* s);
-#else
-inline mh_status scan_build_tiles(const mh_scan*, float, uint32_t) { return MH_OK; }
-inline uint32_t tile_points(const Switches&) { return 0; }
-inline mh_status scan_tiles_ready(const mh_scan*) { return MH_OK; }
-inline void scan_drop_tiles(mh_scan*) {}
-inline void scan_free_tiles(mh_scan*) {}
-#endif
 // Asynchronous on stream `s` (the context's); scratch from `m`.  Counts / bbox / the
 // out-of-range verdict are resolved lazily (map_resolve).
 mh_status map_build_device(const Switches& sw, mh_map* m, hipStream_t s, const float* dx, const float* dy, const float* dz,

@@ -6,17 +6,8 @@
 __global__ __launch_bounds__(kBlock, MH_QUAD_WAVES) void k_match4(const IcpDeviceState* __restrict__ st,
                                                    const float* __restrict__ lx, const float* __restrict__ ly,
                                                    const float* __restrict__ lz, uint32_t n, MapView map,
-                                                   float4* __restrict__ pair_q, uint32_t* __restrict__ pair_gidx,
-                                                   const uint32_t* __restrict__ perm
-#ifdef MH_DEBUG_WAVETRACE
-                                                   , unsigned long long* __restrict__ wtrace
-#endif
-) {
-  k_match4_body(st, lx, ly, lz, n, map, pair_q, pair_gidx, perm
-#ifdef MH_DEBUG_WAVETRACE
-                , wtrace
-#endif
-  );
+                                                   float4* __restrict__ pair_q, uint32_t* __restrict__ pair_gidx) {
+  k_match4_body(st, lx, ly, lz, n, map, pair_q, pair_gidx);
 }
 // ================================================================================================
 // k_match_flat: the plan / scan matcher (mh_nn_flat.h) -- a wave per 64 consecutive scan points, per-point, per-voxel and
@@ -38,7 +29,7 @@ inline uint32_t nblk_flat(size_t n) { return (uint32_t)(((n + kFlatPointsPerBloc
 __device__ __forceinline__ void k_match_flat_body(const IcpDeviceState* __restrict__ st, const float* __restrict__ lx,
                                                   const float* __restrict__ ly, const float* __restrict__ lz, uint32_t n,
                                                   MapView map, float4* __restrict__ pair_q, uint32_t* __restrict__ pair_gidx,
-                                                  const uint32_t* __restrict__ perm, uint32_t block_x) {
+                                                  uint32_t block_x) {
   __shared__ FlatWave sh[kFlatThreads / 64];
   typedef const IcpDeviceState __attribute__((address_space(4))) * cstate_ptr;
   const cstate_ptr cst = (cstate_ptr)uniform_const_ptr(st);
@@ -50,21 +41,17 @@ __device__ __forceinline__ void k_match_flat_body(const IcpDeviceState* __restri
   double T[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) T[k] = cst->T[k];
-  match_flat_wave(sh[threadIdx.x >> 6], map, T, cst->cur_thr2, cst->cur_ang2, have_prev, lx, ly, lz, n, i0, pair_q, pair_gidx, perm);
+  match_flat_wave(sh[threadIdx.x >> 6], map, T, cst->cur_thr2, cst->cur_ang2, have_prev, lx, ly, lz, n, i0, pair_q, pair_gidx);
 }
 __global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_flat(const IcpDeviceState* __restrict__ st, const float* __restrict__ lx,
                                                              const float* __restrict__ ly, const float* __restrict__ lz, uint32_t n,
                                                              MapView map, float4* __restrict__ pair_q,
-                                                             uint32_t* __restrict__ pair_gidx, const uint32_t* __restrict__ perm) {
-  k_match_flat_body(st, lx, ly, lz, n, map, pair_q, pair_gidx, perm, blockIdx.x);
+                                                             uint32_t* __restrict__ pair_gidx) {
+  k_match_flat_body(st, lx, ly, lz, n, map, pair_q, pair_gidx, blockIdx.x);
 }
 __global__ __launch_bounds__(kBlock, MH_QUAD_WAVES) void k_match4_b(const BatchJob* __restrict__ jobs) {
   const BatchJob& j = jobs[blockIdx.y];
-  k_match4_body(j.st, j.lx, j.ly, j.lz, j.n, j.map, j.pair_q, j.pair_gidx, nullptr
-#ifdef MH_DEBUG_WAVETRACE
-                , nullptr
-#endif
-  );
+  k_match4_body(j.st, j.lx, j.ly, j.lz, j.n, j.map, j.pair_q, j.pair_gidx);
 }
 // A whole job per XCD.  Workgroup L of a launch runs on XCD L % 8 (tools/xcd_exchange.hip: 0 exceptions in 256; the grid's width is
 // a multiple of 8), so with blockIdx.y = job every job's workgroups are dealt over all eight XCDs and every XCD's L2 fetches its own
@@ -82,11 +69,8 @@ __global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_flat_b(co
     bx = slot % gridDim.x;
   }
   const BatchJob& j = jobs[job];
-  k_match_flat_body(j.st, j.lx, j.ly, j.lz, j.n, j.map, j.pair_q, j.pair_gidx, nullptr, bx);
+  k_match_flat_body(j.st, j.lx, j.ly, j.lz, j.n, j.map, j.pair_q, j.pair_gidx, bx);
 }
-#ifdef MH_DEV_VARIANTS
-#include "mh_dev_variants.h"  // k_match_tile*, k_match_wave_*, k_match4o_b: development library only
-#endif
 template <bool SIGNED>
 __global__ __launch_bounds__(kBlock, MH_ACCUM_WAVES) void k_accum(const IcpDeviceState* __restrict__ st, uint32_t first,
                                                   const MatchK* __restrict__ kp, const float* __restrict__ lx,

@@ -83,11 +83,7 @@ __device__ __forceinline__ void match_layers_wave(FlatWave& sh, const clayers_st
   }
   // field by field: scalar loads through the constant-space table (a MapView field added in mh_internal.h has to be added here:
   // the static_assert below fails until it is)
-#ifdef MH_DEBUG_WAVETRACE
-  static_assert(sizeof(MapView) == 56, "MapView changed: copy the new field in k_match_layers");
-#else
   static_assert(sizeof(MapView) == 48, "MapView changed: copy the new field in k_match_layers");
-#endif
   MapView map;
   map.slots = ct->d[li].map.slots;
   map.pts = ct->d[li].map.pts;
@@ -98,9 +94,6 @@ __device__ __forceinline__ void match_layers_wave(FlatWave& sh, const clayers_st
   map.ndt = ct->d[li].map.ndt;
   map.no_prev_bound = ct->d[li].map.no_prev_bound;
   map.pts_q = ct->d[li].map.pts_q;
-#ifdef MH_DEBUG_WAVETRACE
-  map.dbg_stop = ct->d[li].map.dbg_stop;
-#endif
   // (the first active iteration of a pair finds no pairings of its own in its segment: unbounded, like iteration 0)
   const bool have_prev = iter > ct->d[li].run_from && !map.no_prev_bound;
   double T[12];
@@ -109,7 +102,7 @@ __device__ __forceinline__ void match_layers_wave(FlatWave& sh, const clayers_st
   const double thr = G(ct->d[li].mk.thr)[iter];
   const float thr2 = (float)(thr * thr);  // what k_solve leaves in cur_thr2 for a single alignment
   match_flat_wave(sh, map, T, thr2, ct->d[li].mk.ang2, have_prev, ct->d[li].lx, ct->d[li].ly, ct->d[li].lz, n, i0,
-                  ct->d[li].pair_q, ct->d[li].pair_gidx, nullptr);
+                  ct->d[li].pair_q, ct->d[li].pair_gidx);
 }
 
 __global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_layers(const IcpDeviceState* __restrict__ st,

@@ -193,7 +193,7 @@ __global__ void k_div_idx(uint32_t* __restrict__ idx, uint32_t n, uint32_t k) {
   if (i < n) idx[i] /= k;
 }
 
-#ifdef MH_DEBUG_WAVETRACE
+#ifdef MH_DEBUG_PHASES
 // debug build only: wall_clock64 (100 MHz) at numbered points of the one-workgroup kernels, last launch wins
 __device__ unsigned long long g_phase[32];
 #define MH_PHASE(i) do { if (threadIdx.x == 0) g_phase[i] = wall_clock64(); } while (0)
@@ -217,14 +217,6 @@ extern "C" __attribute__((visibility("default"))) int mh_debug_flat_counters(uns
 #define MH_LOOP_STAMP(i) do { } while (0)
 #define MH_LOOP_STAMPS_OUT(steps) do { } while (0)
 #endif
-#ifdef MH_DEBUG_WAVETRACE
-static unsigned long long* g_wtrace = nullptr;  // debug build only: [2 * n_waves] begin/end wall_clock64 of the last launch
-extern "C" __attribute__((visibility("default"))) int mh_debug_wavetrace(unsigned long long* host_out, size_t n_waves) {
-  if (!g_wtrace) { if (hipMalloc(&g_wtrace, 16u << 20) != hipSuccess) return 1; (void)hipMemset(g_wtrace, 0, 16u << 20); return 0; }
-  (void)hipDeviceSynchronize();
-  return hipMemcpy(host_out, g_wtrace, n_waves * 16, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
-}
-#endif
 // ================================================================================================
 // k_match4: correspondence search with a DPP quad per scan point (nn_search_quad).  Device-state driven like the
 // fused k_match, but it only stores the pairings: the first Gauss-Newton accumulation is the k_accum launch that
@@ -233,35 +225,23 @@ extern "C" __attribute__((visibility("default"))) int mh_debug_wavetrace(unsigne
 __device__ __forceinline__ void k_match4_body(const IcpDeviceState* __restrict__ st,
                                                    const float* __restrict__ lx, const float* __restrict__ ly,
                                                    const float* __restrict__ lz, uint32_t n, MapView map,
-                                                   float4* __restrict__ pair_q, uint32_t* __restrict__ pair_gidx,
-                                                   const uint32_t* __restrict__ perm  // null, or lx/ly/lz are the scan in
-                                                                                      // search order: point i is perm[i]
-#ifdef MH_DEBUG_WAVETRACE
-                                                   , unsigned long long* __restrict__ wtrace
-#endif
-) {
-#ifdef MH_DEBUG_WAVETRACE
-  struct WT { unsigned long long* p; unsigned long long t0; uint32_t w;
-              __device__ ~WT() { if ((threadIdx.x & 63) == 0 && p) { p[2 * w] = t0; p[2 * w + 1] = wall_clock64(); } } }
-      wt{wtrace, (unsigned long long)wall_clock64(), (blockIdx.x * kBlock + threadIdx.x) >> 6};
-#endif
+                                                   float4* __restrict__ pair_q, uint32_t* __restrict__ pair_gidx) {
   // everything needed per iteration sits in the state block (k_solve publishes the next threshold there): one batch of
   // scalar loads instead of the chain state -> parameter block -> threshold table, and the point is fetched alongside
   const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;
   const uint32_t i = gl >> 2, sub = gl & 3u;
   const uint32_t ic = i < n ? i : n - 1;
-  const uint32_t o = perm ? G(perm)[ic] : ic;  // (clamped: lanes past the end of a short job of a batch read, and never write)
-  const float x = G(lx)[ic], y = G(ly)[ic], z = G(lz)[ic];
+  const float x = G(lx)[ic], y = G(ly)[ic], z = G(lz)[ic];  // (clamped: lanes past the end of a short job of a batch read, and never write)
   // the state block through the scalar path (uniform address, not written during this kernel): the pose in SGPRs
   typedef const IcpDeviceState __attribute__((address_space(4))) * cstate_ptr;
   const cstate_ptr cst = (cstate_ptr)uniform_const_ptr(st);
   const uint32_t done = cst->done;
-  // From the second ICP iteration on, pair_q[o] still holds the record this point was paired with under the previous
+  // From the second ICP iteration on, pair_q[i] still holds the record this point was paired with under the previous
   // pose: its distance under the new pose bounds the search (nn_search_quad).  Iteration 0 of every alignment starts
   // without one (the buffer may hold another scan's pairings).
   const bool have_prev = cst->iter > 0 && !map.no_prev_bound;
   f32x4 prev = (f32x4){0.f, 0.f, 0.f, __builtin_inff()};
-  if (have_prev) prev = G(reinterpret_cast<const f32x4*>(pair_q))[o];  // grid-uniform branch
+  if (have_prev) prev = G(reinterpret_cast<const f32x4*>(pair_q))[ic];  // grid-uniform branch
   double T[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) T[k] = cst->T[k];
@@ -279,8 +259,8 @@ __device__ __forceinline__ void k_match4_body(const IcpDeviceState* __restrict__
   if (sub == 0) {
     const float n2 = (px * px + py * py) + pz * pz;
     const bool ok = r.found && (r.d2 < thr2 + ang2 * n2);
-    G(reinterpret_cast<f32x4*>(pair_q))[o] = (f32x4){r.pt.x, r.pt.y, r.pt.z, r.d2};
-    G(pair_gidx)[o] = ok ? __float_as_uint(r.pt.w) : kNoMatch;
+    G(reinterpret_cast<f32x4*>(pair_q))[ic] = (f32x4){r.pt.x, r.pt.y, r.pt.z, r.d2};
+    G(pair_gidx)[ic] = ok ? __float_as_uint(r.pt.w) : kNoMatch;
   }
 }
 

@@ -227,9 +227,6 @@ __device__ __forceinline__ void match_layers_pl_wave(mh::FlatWaveP& sh, const cl
   map.ndt = ct->d[li].map.ndt;
   map.no_prev_bound = ct->d[li].map.no_prev_bound;
   map.pts_q = ct->d[li].map.pts_q;
-#ifdef MH_DEBUG_WAVETRACE
-  map.dbg_stop = ct->d[li].map.dbg_stop;
-#endif
   const bool have_prev = iter > ct->d[li].run_from && !map.no_prev_bound;
   double T[12];
 #pragma unroll

@@ -598,9 +598,6 @@ __device__ __forceinline__ NNResult nn_search_quad(const MapView& m, uint32_t su
   const Gaps gx = axis_gaps(qx, cx, vs, m.trunc), gy = axis_gaps(qy, cy, vs, m.trunc), gz = axis_gaps(qz, cz, vs, m.trunc);
   const QuadBounds qb = quad_bounds(gx, gy, gz, sub);
   nnkey_t best = kNNKeyNone;
-#ifdef MH_DEBUG_WAVETRACE
-  if (m.dbg_stop == 1) return r;  // prologue only
-#endif
   const uint32_t kFaces = (1u << 4) | (1u << 10) | (1u << 12) | (1u << 14) | (1u << 16) | (1u << 22);
   const uint32_t kCorners = (1u << 0) | (1u << 2) | (1u << 6) | (1u << 8) | (1u << 18) | (1u << 20) | (1u << 24) | (1u << 26);
   const uint32_t kEdges = 0x07FFFFFFu & ~(kFaces | kCorners | (1u << 13));
@@ -625,13 +622,7 @@ __device__ __forceinline__ NNResult nn_search_quad(const MapView& m, uint32_t su
     const u32x4 sl_s = slots4[hash_key(key_s) & m.mask];
     uint32_t f1[1], c1[1];
     nn_resolve(m, slots4, key, sl_c, true, f1[0], c1[0]);
-#ifdef MH_DEBUG_WAVETRACE
-    if (m.dbg_stop == 2) { r.d2 = (float)(f1[0] + c1[0] + sl_s.z); return r; }  // + own-voxel probe
-#endif
     best = nn_scan_merged_quad<1>(spts, f1, c1, sub, qx, qy, qz, best);
-#ifdef MH_DEBUG_WAVETRACE
-    if (m.dbg_stop == 3) { r.d2 = nnkey_d2(best) + (float)sl_s.z; return r; }  // + own-voxel scan
-#endif
     // the speculated neighbours that did survive: one merged scan, no further probe round trip
     const uint32_t live0 = quad_bound_mask(qb, sub, nnkey_d2(best));
     uint32_t f_s, n_s;
@@ -691,9 +682,6 @@ __device__ __forceinline__ NNResult nn_search_quad(const MapView& m, uint32_t su
     best = kNNKeyNone;
     todo = 0x07FFFFFFu;
   }
-#ifdef MH_DEBUG_WAVETRACE
-  if (m.dbg_stop == 4) { r.d2 = nnkey_d2(best); return r; }  // + neighbours, without the final record fetch
-#endif
   if (nnkey_idx(best) != 0xFFFFFFFFu) {
     r.pt = pts4[nnkey_idx(best)];
     r.d2 = nnkey_d2(best);
@@ -840,22 +828,7 @@ __device__ __forceinline__ NNResult nn_search_row16(const MapView& m, uint32_t r
   return r;
 }
 
-// (generic wave helpers; the tile / wave searches that came with them live in mh_nn_dev_variants.h)
-template <int CTRL>
-__device__ __forceinline__ int dpp_keep_i32(int old, int v) {
-  return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xF, 0xF, false);  // lanes without a source keep `old`
-}
-__device__ __forceinline__ int wave_min_i32(int v) {
-  const int big = 0x7FFFFFFF;
-  v = min(v, dpp_keep_i32<0x101>(big, v));  // row_shl:1
-  v = min(v, dpp_keep_i32<0x102>(big, v));
-  v = min(v, dpp_keep_i32<0x104>(big, v));
-  v = min(v, dpp_keep_i32<0x108>(big, v));  // lane 0 of each row holds the row's minimum
-  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-__device__ __forceinline__ int wave_max_i32(int v) { return -wave_min_i32(-v); }  // (callers stay away from INT_MIN)
-
+// (generic wave helpers)
 // inclusive prefix sum over the 64 lanes of a wave (DPP row shifts inside the 16-lane rows, three readlanes across)
 __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
   int x = (int)v;
@@ -887,12 +860,6 @@ __device__ __forceinline__ cf32x4_ptr uniform_const_ptr(const void* p) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
   return (cf32x4_ptr)(((unsigned long long)hi << 32) | lo);
 }
-
-// Four records [f + j, f + j + 4) of a run of c, indices clamped into the run (a duplicate of the last record can neither
-// lower a minimum nor win a strict '<'): four scalar loads, wave-uniform addresses.
-#ifdef MH_DEV_VARIANTS
-#include "mh_nn_dev_variants.h"  // nn_search_tile, nn_search_wave
-#endif
 
 // ---- robust kernels (mp2p_icp::create_robust_kernel [U], lidar3d-default.yaml:188-190) ---------
 __device__ __forceinline__ double robust_weight(uint32_t kernel, double c, double e2) {

@@ -215,8 +215,8 @@ __device__ __forceinline__ uint32_t flat_plan_scan(FW& sh, const MapView& m, uin
   return n_cands;
 }
 
-// One wave, 64 consecutive scan points starting at `i0` (lanes past `n` idle).  perm: null, or the layer is in search
-// order and point i's pairing goes to perm[i].  Everything uniform (pose, thresholds, have_prev) comes in SGPRs.
+// One wave, 64 consecutive scan points starting at `i0` (lanes past `n` idle).  Everything uniform (pose, thresholds,
+// have_prev) comes in SGPRs.
 // The pairing's fourth word: d2 of the nearest record, its SIGN the verdict of the distance test (set = not accepted; d2 >= 0, so
 // the bit is free) -- the accumulation that follows this matcher (k_accum<true>) then needs the 16 bytes of the pairing and not
 // the 4 of the index array as well: 28 instead of 32 bytes per point of a launch that streams at 0.57 of the HBM peak.  The index
@@ -227,20 +227,18 @@ __device__ __forceinline__ float flat_signed_d2(float d2, bool accepted) {
 __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, const double* __restrict__ T, float thr2,
                                                 float ang2, bool have_prev, const float* __restrict__ lx,
                                                 const float* __restrict__ ly, const float* __restrict__ lz, uint32_t n,
-                                                uint32_t i0, float4* __restrict__ pair_q, uint32_t* __restrict__ pair_gidx,
-                                                const uint32_t* __restrict__ perm) {
+                                                uint32_t i0, float4* __restrict__ pair_q, uint32_t* __restrict__ pair_gidx) {
   const uint32_t lane = (uint32_t)__lane_id();
   const uint32_t i = i0 + lane;
   const bool in = i < n;
   const uint32_t ic = in ? i : n - 1;
-  const uint32_t o = perm ? G(perm)[ic] : ic;
   const gslots_ptr slots4 = (gslots_ptr)m.slots;
   const gpts_ptr pts4 = (gpts_ptr)m.pts;
   const gpts_ptr spts = (gpts_ptr)m.pts_q;
   // ---- A1: the point ------------------------------------------------------------------------------------------------
   const float x = G(lx)[ic], y = G(ly)[ic], z = G(lz)[ic];
   f32x4 prev = (f32x4){0.f, 0.f, 0.f, __builtin_inff()};
-  if (have_prev) prev = G(reinterpret_cast<const f32x4*>(pair_q))[o];  // grid-uniform branch
+  if (have_prev) prev = G(reinterpret_cast<const f32x4*>(pair_q))[ic];  // grid-uniform branch
   float px, py, pz;
   transform_point(T, x, y, z, px, py, pz);
   float b0 = __builtin_inff();
@@ -330,8 +328,8 @@ __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, 
       const float d2 = __uint_as_float((uint32_t)(res >> 32));
       const float n2 = (px * px + py * py) + pz * pz;
       const bool ok = d2 < thr2 + ang2 * n2;
-      G(reinterpret_cast<f32x4*>(pair_q))[o] = (f32x4){w.x, w.y, w.z, flat_signed_d2(d2, ok)};
-      G(pair_gidx)[o] = ok ? __float_as_uint(w.w) : kNoMatch;
+      G(reinterpret_cast<f32x4*>(pair_q))[ic] = (f32x4){w.x, w.y, w.z, flat_signed_d2(d2, ok)};
+      G(pair_gidx)[ic] = ok ? __float_as_uint(w.w) : kNoMatch;
     } else if (planned) {
       slow = true;
       if (!spilled) b0s = __builtin_inff();  // the bound was not attained inside the block: once more, without it
@@ -356,11 +354,10 @@ __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, 
       const NNResult r = nn_search_quad(m, sub, P.x, P.y, P.z, P.w);
       if (sub == 0u) {
         const uint32_t ip = i0 + p;
-        const uint32_t op = perm ? G(perm)[ip] : ip;
         const float n2 = (P.x * P.x + P.y * P.y) + P.z * P.z;
         const bool ok = r.found && (r.d2 < thr2 + ang2 * n2);
-        G(reinterpret_cast<f32x4*>(pair_q))[op] = (f32x4){r.pt.x, r.pt.y, r.pt.z, flat_signed_d2(r.d2, ok)};
-        G(pair_gidx)[op] = ok ? __float_as_uint(r.pt.w) : kNoMatch;
+        G(reinterpret_cast<f32x4*>(pair_q))[ip] = (f32x4){r.pt.x, r.pt.y, r.pt.z, flat_signed_d2(r.d2, ok)};
+        G(pair_gidx)[ip] = ok ? __float_as_uint(r.pt.w) : kNoMatch;
       }
     }
   }
@@ -373,7 +370,7 @@ __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, 
 // b0: the squared distance to the record paired with it in the previous iteration (attained by a map record) or +inf.
 // Phases A1 (masks) | stage 0 | A2 | B | C | D exactly as in match_flat_wave: the same candidate set, the same fp32 arithmetic,
 // the same 64-bit key -- the lexicographic minimum of (d2, scan position) over the 27-voxel block.
-#ifdef MH_DEBUG_WAVETRACE
+#ifdef MH_DEBUG_PHASES
 static __device__ unsigned long long g_flatdbg[16];  // debug build: [0] searches (waves) [1] points [2] unbounded at entry [3] slow: out of range / no bound after stage 0
                                               // [4] slow: > kFlatMaxCand candidates [5] slow: chunk space [6] slow: bound not attained [7] candidates [8] chunks (stage 1) [9] D rounds
                                               // match_kbest_wave (mh_k_match_kbest.h): [10] points [11] without a bound [12] > kFlatMaxCand candidates [13] chunk space [14] slot k - 1 empty [15] bounded scan of the lane's own, slot k - 1 empty

@@ -955,7 +955,6 @@ mh_status mh_scan_update_aos_i(mh_scan* scan, const void* data, size_t n, size_t
   scan->src = nullptr;
   scan->i = off_i >= 0 ? scan->ibuf.as<const float>() : nullptr;
   scan->n = n;
-  scan_drop_tiles(scan);
   if (!n) return MH_OK;
   const uint32_t* recs = (const uint32_t*)data;
   if (mem != MH_MEM_DEVICE) {  // the only copy of the call: the raw bytes as they are

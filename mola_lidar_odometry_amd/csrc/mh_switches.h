@@ -25,12 +25,6 @@ struct Switches {
   bool no_prev_bound = false, no_qidx = false, map_full_sort = false, map_no_collect = false;
   long keep_lds = LONG_MAX;  // (clamped to 1..kKeepLds where it is used)
   bool loop16_test_abandon = false, debug_verify_batch = false;
-#ifdef MH_DEV_VARIANTS
-  bool wave_lds = false;
-#endif
-#ifdef MH_DEBUG_WAVETRACE
-  uint32_t dbg_stop = 0;
-#endif
 };
 
 inline Switches read_switches() {
@@ -58,12 +52,6 @@ inline Switches read_switches() {
   if ((e = getenv("MH_KEEP_LDS"))) sw.keep_lds = atol(e);
   sw.loop16_test_abandon = on("MH_LOOP16_TEST_ABANDON");
   sw.debug_verify_batch = on("MH_DEBUG_VERIFY_BATCH");
-#ifdef MH_DEV_VARIANTS
-  sw.wave_lds = on("MH_WAVE_LDS");
-#endif
-#ifdef MH_DEBUG_WAVETRACE
-  if ((e = getenv("MH_DBG_STOP"))) sw.dbg_stop = (uint32_t)atoi(e);
-#endif
   return sw;
 }
 

@@ -2,10 +2,11 @@
 tests/test_gpu_dense_cells.py, tests/test_gpu_solver_params.py and tests/test_gpu_far_origin.py; no GPU, no inputs.
 
 Which kernel a row runs follows from plan_alignment (csrc/mh_icp.hip) and is confirmed by the one-line mutants of DESIGN.md
-section 5.  MH_MATCH=t|w|o name the development matchers (tests/conftest.py skips them on the shipped library)."""
+section 5.  MH_MATCH=t|w|o named the tile / wave / sorted-scan matchers, which were removed: the library refuses the letters
+(test_gpu_parity.py::test_retired_matcher_letters_are_refused) and no table lists them."""
 
 # ------------------------------------------------------------------------------------------------ single pair, dense-cell maps
-# test_gpu_parity.py::test_every_kernel_variant_matches_the_oracle's list without the development letters (t, w, o), plus the
+# test_gpu_parity.py::test_every_kernel_variant_matches_the_oracle's list, plus the
 # default route's launch chain (the one-launch loops have cases of their own).  No loop starts under these switches, except under
 # MH_MATCH=s alone: the row search's loop k_icp16, 2.6 ms for 2000 points and 16 iterations (profiles/dense_cells.md).
 FAMILIES = [{"MH_NO_LOOP16": "1"}, {"MH_MATCH": "s"}, {"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1"},
@@ -65,9 +66,6 @@ POINT_MATCHER_KERNELS = [
     (5000, {"MH_MATCH": "q"}),
     (5000, {"MH_MATCH": "p"}),
     (5000, {"MH_MATCH": "x"}),
-    (5000, {"MH_MATCH": "t"}),                                               # (development library only: tests/conftest.py)
-    (5000, {"MH_MATCH": "w"}),
-    (5000, {"MH_MATCH": "o"}),
 ]
 
 

@@ -106,8 +106,8 @@ def _assert_same_bits(a, b, what):
 
 
 # ------------------------------------------------------------------- a. single pair, every shipped family, room and mixed
-# FAMILIES x SEARCH: tests/route_tables.py (test_gpu_parity.py::test_every_kernel_variant_matches_the_oracle's list without the
-# development letters, plus the default route's launch chain; the one-launch loops: section b).  No loop starts under these
+# FAMILIES x SEARCH: tests/route_tables.py (test_gpu_parity.py::test_every_kernel_variant_matches_the_oracle's list, plus the
+# default route's launch chain; the one-launch loops: section b).  No loop starts under these
 # switches, except under MH_MATCH=s alone: the row search's loop k_icp16.
 _id = env_id
 

@@ -381,13 +381,13 @@ def test_nn_voxel_boundary_and_negative_coords(ctx, oracle):
 
 @pytest.mark.parametrize("vs,cap,mode,offset", [(1.0, 20, 0, 0.0), (0.3, 5, 0, 0.0), (2.5, 0, 0, 0.0), (1.0, 20, 1, 0.0),
                                                 (1.0, 20, 0, 50000.0), (0.7, 8, 0, -12345.0), (0.3, 20, 1, 3.0)])
-@pytest.mark.parametrize("match", ["p", "t", "w"])
+@pytest.mark.parametrize("match", ["p"])
 def test_nn_pruning_is_exact_on_adversarial_clouds(ctx, oracle, vs, cap, mode, offset, match, monkeypatch):
     """The production search prunes voxels with a conservative distance bound; its output must stay
     bit-identical to the exhaustive 27-voxel scan of the oracle.  Adversarial inputs: lattice-aligned map
     points and queries (exact distance ties in different voxels), queries exactly on voxel boundaries,
     coordinates where fp32 spacing is coarse, voxel sizes whose reciprocal is inexact, trunc indexing."""
-    monkeypatch.setenv("MH_MATCH", match)  # p: one lane per point through the caches; t: tiles staged in LDS; w: wave-uniform candidates
+    monkeypatch.setenv("MH_MATCH", match)  # p: one lane per point through the caches
     rng = np.random.default_rng(int(vs * 10) + cap + mode)
     g = np.arange(-6, 6, 0.25, dtype=np.float32)
     lattice = np.stack(np.meshgrid(g, g, g[:24], indexing="ij"), -1).reshape(-1, 3)
@@ -1184,9 +1184,9 @@ def test_profile_fields(ctx, small):
 @pytest.mark.parametrize("env", [{"MH_MATCH": "s"}, {"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1"},
                                  {"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1", "MH_NO_FUSE16": "1"}, {"MH_MATCH": "q"},
                                  {"MH_MATCH": "p"}, {"MH_MATCH": "x"}, {"MH_MATCH": "q", "MH_NO_GRAPH": "1"},
-                                 {"MH_MATCH": "t"}, {"MH_MATCH": "t", "MH_NO_GRAPH": "1"}, {"MH_MATCH": "w"},
-                                 {"MH_MATCH": "w", "MH_NO_GRAPH": "1"}, {"MH_MATCH": "w", "MH_WAVE_LDS": "1"},
-                                 {"MH_MATCH": "o"}, {"MH_MATCH": "f"}, {"MH_MATCH": "f", "MH_NO_GRAPH": "1"}])
+                                 # (env7 .. env12 were the tile / wave / sorted-scan matchers; the two below keep their ids)
+                                 pytest.param({"MH_MATCH": "f"}, id="env13"),
+                                 pytest.param({"MH_MATCH": "f", "MH_NO_GRAPH": "1"}, id="env14")])
 @pytest.mark.parametrize("n_scan", [2000, 5000])
 def test_every_kernel_variant_matches_the_oracle(ctx, oracle, env, n_scan, monkeypatch):
     """The default path picks its kernels by layer size (row / quad search, one-workgroup or multi-launch solve);
@@ -1207,6 +1207,52 @@ def test_every_kernel_variant_matches_the_oracle(ctx, oracle, env, n_scan, monke
     np.testing.assert_array_equal(g["pairs"]["global_idx"], o["pairs"]["global_idx"])
     np.testing.assert_array_equal(g["pairs"]["d2"], o["pairs"]["d2"])
     np.testing.assert_allclose(g["T"], o["T"], rtol=0, atol=1e-9)
+
+
+MH_ERR_INVALID_ARGUMENT = 1  # (include/molahip.h)
+
+
+@pytest.mark.parametrize("letter", ["t", "w", "o"])
+def test_retired_matcher_letters_are_refused(ctx, letter, monkeypatch):
+    """MH_MATCH=t|w|o named the tile / wave / sorted-scan matchers, which were removed: mh_icp_align refuses the letter with
+    MH_ERR_INVALID_ARGUMENT and a message that names it, and leaves nothing behind -- the same context, map and scan then align
+    as they did before the refusal, bit for bit."""
+    pts = np.random.default_rng(64).uniform(-5, 5, (64, 3)).astype(np.float32)
+    gm, gs = capi.Map(ctx, 1.0, 20).build(pts), capi.Scan(ctx, pts)
+    guess = synth.pose_from_ypr(np.array([0.05, -0.03, 0.02, 0.01, 0.0, 0.0]))
+    thr, kp = synth.threshold_schedule(2.0, 10)
+    p = capi.ICPParams(max_iterations=10, threshold=thr, kernel_param=kp)
+    monkeypatch.delenv("MH_MATCH", raising=False)
+    before = capi.icp_align(gm, gs, guess, p)
+    assert before["n_final_pairs"] == 64
+    monkeypatch.setenv("MH_MATCH", letter)
+    with pytest.raises(capi.MolahipError) as e:
+        capi.icp_align(gm, gs, guess, p)
+    assert e.value.status == MH_ERR_INVALID_ARGUMENT
+    assert ("MH_MATCH=%s" % letter) in capi.lib().mh_last_error_string().decode()
+    monkeypatch.delenv("MH_MATCH")
+    after = capi.icp_align(gm, gs, guess, p)
+    assert after["n_iterations"] == before["n_iterations"] and after["n_final_pairs"] == 64
+    assert after["termination_reason"] == before["termination_reason"]
+    assert np.asarray(after["T"]).tobytes() == np.asarray(before["T"]).tobytes()
+
+
+def test_scan_prepare_is_a_checked_no_op(ctx):
+    """mh_scan_prepare stays in the ABI for the callers that have it: it checks its arguments and touches nothing."""
+    pts = np.random.default_rng(65).uniform(-5, 5, (65, 3)).astype(np.float32)
+    s = capi.Scan(ctx, pts)
+    d0 = s.download()
+    assert s.prepare(1.0) is s
+    for vs in (0.0, -1.0):
+        with pytest.raises(capi.MolahipError) as e:
+            s.prepare(vs)
+        assert e.value.status == MH_ERR_INVALID_ARGUMENT
+    assert capi.lib().mh_scan_prepare(None, 1.0) == MH_ERR_INVALID_ARGUMENT
+    d1 = s.download()
+    assert len(s) == 65 and sorted(d0) == sorted(d1)
+    for k in d0:
+        assert d0[k].tobytes() == d1[k].tobytes(), k
+    assert d1["xyz"].tobytes() == pts.tobytes()
 
 
 @pytest.mark.parametrize("vs,shift", [(0.25, 0.9), (0.4, 0.6), (1.0, 0.3)])

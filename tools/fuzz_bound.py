@@ -65,9 +65,8 @@ for case in range(0 if dense else n_cases):
     mode = int(rng.choice([0, 0, 1]))
     n_scan = int(rng.choice([1500, 4000, 9000, 20000, 24000]))
     shift = float(rng.uniform(0.05, 1.2))
-    match = str(rng.choice(["f", "q", "s", "f", "s", "o", "t", "w", "p", "f"]))  # f: the plan / scan matcher (default of large layers, round 5)
-    if match in "otw" and not capi.dev_variants():  # (development matchers: tools/build_variants.sh)
-        match = "f"
+    # f: the plan / scan matcher (default of large layers, round 5); ten entries, so that a seed keeps drawing the cases it always drew
+    match = str(rng.choice(["f", "q", "s", "f", "s", "f", "f", "f", "p", "f"]))
     seed = int(rng.integers(1, 10000))
     scene = synth.make_scene(seed, 60.0, 20)
     mp = synth.make_map(scene, int(rng.choice([40000, 150000])), seed)

@@ -43,22 +43,15 @@ for case in range(n_cases):
     om = oracle_c.Map(vs, cap, mode).insert(pts)
     o = oracle_c.match_points(om, q, T, 1e9)
     fails = []
-    variants = (("p", {}), ("x", {}), ("q", {}), ("s", {}))
-    if capi.dev_variants():  # (the development library: tools/build_variants.sh)
-        variants += (("t", {}), ("w", {}), ("w", {"MH_WAVE_LDS": "1"}))
-    for match, extra in variants:
+    for match in ("p", "x", "q", "s"):
         os.environ["MH_MATCH"] = match
-        for k, v in extra.items():
-            os.environ[k] = v
         gm = capi.Map(ctx, vs, cap, mode).build(pts)
         d = capi.nn_search_dense(gm, capi.Scan(ctx, q), T)
-        for k in extra:
-            del os.environ[k]
         found = d["global_idx"] != capi.NO_MATCH
         ok = (np.array_equal(np.nonzero(found)[0], o["local_idx"]) and np.array_equal(d["global_idx"][found], o["global_idx"]) and
               np.array_equal(d["d2"][found], o["d2"]) and np.array_equal(d["global_xyz"][found], o["global_xyz"]))
         if not ok:
-            fails.append(match + ("+lds" if extra else ""))
+            fails.append(match)
     # Matcher_Points_DistanceThreshold with pairingsPerPoint = k (mh_nn_search_k) against the oracle's k-best restatement
     kk = int(rng.choice([2, 3, 5, 8]))
     thr_k = float(rng.choice([1e9, 0.4 * vs, 1.5 * vs]))

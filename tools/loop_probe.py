@@ -1,5 +1,5 @@
 """Where a step of the one-launch loop (k_icp16) spends its time: accumulated wall_clock64 stamps of workgroup 0 (debug library:
-tools/build_dbg.sh, -DMH_DEBUG_WAVETRACE).
+tools/build_dbg.sh, -DMH_DEBUG_PHASES).
 
     bash tools/build_dbg.sh && MOLAHIP_LIB_PATH=tools/libmolahip_dbg.so python tools/loop_probe.py
 """

@@ -1,5 +1,5 @@
 """The phases of the one-launch loop (k_icp16) inside the real pipeline: the first scans of the synthetic city drive through the
-Python runner on the DEBUG library (phase stamps accumulated by workgroup 0 of the last alignment).
+Python runner on the DEBUG library (tools/build_dbg.sh, -DMH_DEBUG_PHASES: phase stamps accumulated by workgroup 0 of the last alignment).
 
     bash tools/build_dbg.sh && mkdir -p /tmp/mhdbg && cp tools/libmolahip_dbg.so /tmp/mhdbg/libmolahip.so
     LD_LIBRARY_PATH=/tmp/mhdbg MOLAHIP_LIB_PATH=/tmp/mhdbg/libmolahip.so python tools/loop_probe_pipeline.py [scans]

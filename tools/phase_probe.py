@@ -1,4 +1,4 @@
-"""wall_clock64 phase stamps of the small-layer kernels (debug library: tools/build_dbg.sh, -DMH_DEBUG_WAVETRACE; last launch wins).
+"""wall_clock64 phase stamps of the small-layer kernels (debug library: tools/build_dbg.sh, -DMH_DEBUG_PHASES; last launch wins).
 
     bash tools/build_dbg.sh && MOLAHIP_LIB_PATH=tools/libmolahip_dbg.so python tools/phase_probe.py
 
