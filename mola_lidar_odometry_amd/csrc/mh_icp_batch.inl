@@ -173,6 +173,7 @@ struct LockstepGroup {  // (movable, not copyable: the admission)
   uint32_t m = 0;  // iterations of the chunk being enqueued
   uint32_t src = 2, par = 0, launches = 0;  // k_step16_b: the state block (2 = canonical) and the partials half the next launch reads; launches so far
   bool cov = false, done = false, auto_chunk = false;
+  bool off32 = true;       // K_FLAT: flat_off32 holds for every job (k_match_flat_b<true>)
   bool loop_wave = false;  // ... as k_icpw_b (point layers): every job its own workgroups
   uint32_t gx_loopw = 1;   // ... whose launch has this many workgroups per job
   bool loop_now = false;   // k_icp16_b: the group's whole loops in ONE launch (admit_group_loops; cleared when a job's workgroups gave up)
@@ -320,7 +321,10 @@ mh_status stage_group(const Switches& sw, LockstepGroup& g, const PairsPlan* pp)
     d.stage_off = (uint32_t)(off / 4);
     uint32_t bm = (uint32_t)((4ull * d.n + kBlock - 1) / kBlock);  // quad
     if (g.kind == K_ROWF) bm = d.nbm;
-    if (g.kind == K_FLAT) bm = nblk_flat(d.n);
+    if (g.kind == K_FLAT) {
+      bm = nblk_flat(d.n);
+      g.off32 = g.off32 && flat_off32(j.map, d.n);
+    }
     if (g.step_chain()) {  // all jobs' workgroups resident at once: kStepMaxWorkgroups shared between them
       const uint32_t cap = kStepMaxWorkgroups / A ? kStepMaxWorkgroups / A : 1u;
       const uint32_t ng = (d.n + kStepPoints - 1) / kStepPoints;
@@ -372,7 +376,7 @@ mh_status enqueue_group_iteration(const Switches& sw, LockstepGroup& g, bool pr)
   if (pr) MH_HIP(hipEventRecord(g.lead->prof_ev[2 * g.prof_n], s));
   switch (g.kind) {
     case K_ROWF: hipLaunchKernelGGL(k_match16f_b, dim3(g.gx_match, A), dim3(kBlock), 0, s, g.dj); break;
-    case K_FLAT: hipLaunchKernelGGL(k_match_flat_b, dim3(g.gx_match, A), dim3(kFlatThreads), 0, s, g.dj); break;
+    case K_FLAT: hipLaunchKernelGGL(g.off32 ? k_match_flat_b<true> : k_match_flat_b<false>, dim3(g.gx_match, A), dim3(kFlatThreads), 0, s, g.dj); break;
     default: hipLaunchKernelGGL(k_match4_b, dim3(g.gx_match, A), dim3(kBlock), 0, s, g.dj); break;
   }
   if (pr) {

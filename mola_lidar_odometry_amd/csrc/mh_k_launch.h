@@ -25,7 +25,15 @@ constexpr uint32_t kFlatPointsPerBlock = kFlatThreads; // a lane per point in ph
 __device__ __forceinline__ uint32_t nblk_flat_dev(uint32_t n) { return (n + kFlatPointsPerBlock - 1u) / kFlatPointsPerBlock; }
 // (the grid width is a multiple of 8 = the XCDs a launch is dealt over, whatever the layer's size)
 constexpr uint32_t kFlatGridUnit = 8u;
+// OFF32 (below): may the launch form its byte offsets in 32 bits (match_flat_wave)?  Every offset it forms stays inside one of these
+// allocations or below 16 bytes x the scan's points, so it is below 2^32 when they are at most that large.  Conservative: a
+// grow-only buffer that is larger than its content only sends the launch to the 64-bit instantiation.
+inline bool flat_off32(const mh_map* map, size_t n) {
+  constexpr size_t kLim = (size_t)1 << 32;
+  return map->slots.bytes <= kLim && map->pts.bytes <= kLim && map->pts_q.bytes <= kLim && n * sizeof(float4) <= kLim;
+}
 inline uint32_t nblk_flat(size_t n) { return (uint32_t)(((n + kFlatPointsPerBlock - 1) / kFlatPointsPerBlock + kFlatGridUnit - 1) / kFlatGridUnit * kFlatGridUnit); }
+template <bool OFF32>
 __device__ __forceinline__ void k_match_flat_body(const IcpDeviceState* __restrict__ st, const float* __restrict__ lx,
                                                   const float* __restrict__ ly, const float* __restrict__ lz, uint32_t n,
                                                   MapView map, float4* __restrict__ pair_q, uint32_t* __restrict__ pair_gidx,
@@ -41,13 +49,14 @@ __device__ __forceinline__ void k_match_flat_body(const IcpDeviceState* __restri
   double T[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) T[k] = cst->T[k];
-  match_flat_wave(sh[threadIdx.x >> 6], map, T, cst->cur_thr2, cst->cur_ang2, have_prev, lx, ly, lz, n, i0, pair_q, pair_gidx);
+  match_flat_wave<OFF32>(sh[threadIdx.x >> 6], map, T, cst->cur_thr2, cst->cur_ang2, have_prev, lx, ly, lz, n, i0, pair_q, pair_gidx);
 }
+template <bool OFF32>
 __global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_flat(const IcpDeviceState* __restrict__ st, const float* __restrict__ lx,
                                                              const float* __restrict__ ly, const float* __restrict__ lz, uint32_t n,
                                                              MapView map, float4* __restrict__ pair_q,
                                                              uint32_t* __restrict__ pair_gidx) {
-  k_match_flat_body(st, lx, ly, lz, n, map, pair_q, pair_gidx, blockIdx.x);
+  k_match_flat_body<OFF32>(st, lx, ly, lz, n, map, pair_q, pair_gidx, blockIdx.x);
 }
 __global__ __launch_bounds__(kBlock, MH_QUAD_WAVES) void k_match4_b(const BatchJob* __restrict__ jobs) {
   const BatchJob& j = jobs[blockIdx.y];
@@ -60,6 +69,7 @@ __global__ __launch_bounds__(kBlock, MH_QUAD_WAVES) void k_match4_b(const BatchJ
 // FETCH_SIZE 155.5 -> 89.7 MB per launch of 32 scans, traffic 1.64 -> 1.08 x compulsory, L2 hit rate 47 -> 69 %, headline
 // 6320-6330 -> 6470-6480 scans/s.  (Unlike a contiguous PART of one scan per XCD -- profiles/r05_match_kernel.md section 5: 1.22 x
 // at -37 % speed -- whole scans are equal work.)  -DMH_FLAT_NO_JOB_XCD: the plain order (A/B).
+template <bool OFF32>  // (true: flat_off32 holds for EVERY job of the launch)
 __global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_flat_b(const BatchJob* __restrict__ jobs) {
   uint32_t job = blockIdx.y, bx = blockIdx.x;
   const uint32_t whole = gridDim.y & ~7u;  // jobs that are dealt an XCD each
@@ -69,7 +79,7 @@ __global__ __launch_bounds__(kFlatThreads, MH_FLAT_WAVES) void k_match_flat_b(co
     bx = slot % gridDim.x;
   }
   const BatchJob& j = jobs[job];
-  k_match_flat_body(j.st, j.lx, j.ly, j.lz, j.n, j.map, j.pair_q, j.pair_gidx, bx);
+  k_match_flat_body<OFF32>(j.st, j.lx, j.ly, j.lz, j.n, j.map, j.pair_q, j.pair_gidx, bx);
 }
 template <bool SIGNED>
 __global__ __launch_bounds__(kBlock, MH_ACCUM_WAVES) void k_accum(const IcpDeviceState* __restrict__ st, uint32_t first,

@@ -27,6 +27,19 @@ typedef const u32x4 MH_AS_GLOBAL* gslots_ptr;
 typedef const f32x4 MH_AS_GLOBAL* gpts_ptr;
 template <class T>
 __device__ __forceinline__ T MH_AS_GLOBAL* G(T* p) { return (T MH_AS_GLOBAL*)p; }
+// Element i of a global array with a wave-uniform base.  `base[i]` with a 32-bit index is a 64-bit address per lane: shift, add
+// with carry, two registers (v_lshl_add_u64, then `global_load v[a:b], off`).  OFF32: the byte offset is formed in 32 bits and
+// the base stays in SGPRs (v_lshlrev_b32, then `global_load v, s[a:b]`) -- ONLY where the host has checked that every byte
+// offset into the array is below 2^32 (flat_off32, mh_k_launch.h); without it, the plain expression.
+template <bool OFF32, class T>
+__device__ __forceinline__ T MH_AS_GLOBAL* gat(T MH_AS_GLOBAL* base, uint32_t i) {
+  if constexpr (OFF32) {
+    typedef const char MH_AS_GLOBAL* gbytes_ptr;
+    return (T MH_AS_GLOBAL*)((gbytes_ptr)base + (uint32_t)(i * (uint32_t)sizeof(T)));
+  } else {
+    return base + i;
+  }
+}
 
 // p' = (float)(R*l + t): double pose x float point, rounded once to float
 // (Matcher_Points_Base::transform_local_to_global [U] -> CPose3D::composePoint; SURVEY App.B U4)
@@ -389,7 +402,8 @@ __device__ __forceinline__ void nn_search_kbest(const MapView& m, float qx, floa
 
 // {first, count} of voxel `key` given the slot its hash points at; count 0 when absent or not wanted
 // (raw: the slot's count word as stored -- with the quadrants' boundaries of an indexed voxel, slot_count() -- wherever linear
-// probing found the voxel)
+// probing found the voxel; OFF32: gat)
+template <bool OFF32 = false>
 __device__ __forceinline__ void nn_resolve(const MapView& m, gslots_ptr slots4, unsigned long long key, u32x4 sl,
                                            bool want, uint32_t& first, uint32_t& cnt, uint32_t* raw = nullptr) {
   first = 0;
@@ -401,7 +415,7 @@ __device__ __forceinline__ void nn_resolve(const MapView& m, gslots_ptr slots4, 
     uint32_t h = hash_key(key) & m.mask;
     do {
       h = (h + 1) & m.mask;
-      sl = slots4[h];
+      sl = *gat<OFF32>(slots4, h);
       sk = ((unsigned long long)sl.y << 32) | sl.x;
     } while (sk != key && sk != kEmptyKey);
   }
@@ -464,7 +478,7 @@ __device__ __forceinline__ nnkey_t quad_min_key(nnkey_t k) {
 }
 
 // One round trip: W records per lane of the merged ranges.
-template <int NV, int W>
+template <int NV, int W, bool OFF32 = false>
 __device__ __forceinline__ nnkey_t nn_scan_round_quad(gpts_ptr pts4, const uint32_t (&start)[NV],
                                                       const uint32_t (&pre)[NV + 1], uint32_t t0, uint32_t sub, float qx,
                                                       float qy, float qz, nnkey_t best) {
@@ -481,7 +495,7 @@ __device__ __forceinline__ nnkey_t nn_scan_round_quad(gpts_ptr pts4, const uint3
 #pragma unroll
     for (int v = 1; v < NV; v++) off = t >= pre[v] ? start[v] : off;
     ri[u] = t + off;
-    c[u] = pts4[ri[u]];
+    c[u] = *gat<OFF32>(pts4, ri[u]);
   }
 #pragma unroll
   for (int u = 0; u < W; u++) {
@@ -497,7 +511,7 @@ __device__ __forceinline__ nnkey_t nn_scan_round_quad(gpts_ptr pts4, const uint3
   return best;
 }
 
-template <int NV>
+template <int NV, bool OFF32 = false>
 __device__ __forceinline__ nnkey_t nn_scan_merged_quad(gpts_ptr pts4, const uint32_t (&first)[NV],
                                                        const uint32_t (&cnt)[NV], uint32_t sub, float qx, float qy, float qz,
                                                        nnkey_t best) {
@@ -509,7 +523,7 @@ __device__ __forceinline__ nnkey_t nn_scan_merged_quad(gpts_ptr pts4, const uint
     start[v] = first[v] - pre[v];
   }
   const uint32_t total = pre[NV];  // the same in the four lanes
-  for (uint32_t t0 = 0; t0 < total; t0 += 4 * kQuadW) best = nn_scan_round_quad<NV, kQuadW>(pts4, start, pre, t0, sub, qx, qy, qz, best);
+  for (uint32_t t0 = 0; t0 < total; t0 += 4 * kQuadW) best = nn_scan_round_quad<NV, kQuadW, OFF32>(pts4, start, pre, t0, sub, qx, qy, qz, best);
   return quad_min_key(best);
 }
 
@@ -581,6 +595,7 @@ __device__ __forceinline__ void quad_narrow(const MapView& m, uint32_t qv, int c
   n = b_hi - b_lo;
 }
 
+template <bool OFF32 = false>  // (gat: 32-bit byte offsets into the slot table and both record arrays)
 __device__ __forceinline__ NNResult nn_search_quad(const MapView& m, uint32_t sub, float qx, float qy, float qz,
                                                    float bound0 = __builtin_inff()) {
   NNResult r;
@@ -618,20 +633,20 @@ __device__ __forceinline__ NNResult nn_search_quad(const MapView& m, uint32_t su
     const unsigned long long key_s = nn_key_of(kbase, c_spec);
     // the query's own voxel (code 13): the four lanes read the same slot
     const unsigned long long key = nn_key_of(kbase, 13);
-    const u32x4 sl_c = slots4[hash_key(key) & m.mask];
-    const u32x4 sl_s = slots4[hash_key(key_s) & m.mask];
+    const u32x4 sl_c = *gat<OFF32>(slots4, hash_key(key) & m.mask);
+    const u32x4 sl_s = *gat<OFF32>(slots4, hash_key(key_s) & m.mask);
     uint32_t f1[1], c1[1];
-    nn_resolve(m, slots4, key, sl_c, true, f1[0], c1[0]);
-    best = nn_scan_merged_quad<1>(spts, f1, c1, sub, qx, qy, qz, best);
+    nn_resolve<OFF32>(m, slots4, key, sl_c, true, f1[0], c1[0]);
+    best = nn_scan_merged_quad<1, OFF32>(spts, f1, c1, sub, qx, qy, qz, best);
     // the speculated neighbours that did survive: one merged scan, no further probe round trip
     const uint32_t live0 = quad_bound_mask(qb, sub, nnkey_d2(best));
     uint32_t f_s, n_s;
-    nn_resolve(m, slots4, key_s, sl_s, ((live0 >> c_spec) & 1u) != 0, f_s, n_s);
+    nn_resolve<OFF32>(m, slots4, key_s, sl_s, ((live0 >> c_spec) & 1u) != 0, f_s, n_s);
     // (the edge lane may repeat a face code when two gaps tie at zero: count it once)
     if (sub == 3 && (c_e == c_fx || c_e == c_fy || c_e == c_fz)) n_s = 0;
     const uint32_t first[4] = {quad_bcast<0>(f_s), quad_bcast<1>(f_s), quad_bcast<2>(f_s), quad_bcast<3>(f_s)};
     const uint32_t cnt[4] = {quad_bcast<0>(n_s), quad_bcast<1>(n_s), quad_bcast<2>(n_s), quad_bcast<3>(n_s)};
-    best = nn_scan_merged_quad<4>(spts, first, cnt, sub, qx, qy, qz, best);
+    best = nn_scan_merged_quad<4, OFF32>(spts, first, cnt, sub, qx, qy, qz, best);
     todo &= ~(1u << 13) & ~spec_bits;
   }
   for (int pass = 0; pass < 2; pass++) {
@@ -667,14 +682,14 @@ __device__ __forceinline__ NNResult nn_search_quad(const MapView& m, uint32_t su
         }
       }
       const unsigned long long key = nn_key_of(kbase, c_mine < 0 ? 0 : c_mine);
-      const u32x4 sl = slots4[hash_key(key) & m.mask];  // one probe per lane, four per point in flight
+      const u32x4 sl = *gat<OFF32>(slots4, hash_key(key) & m.mask);  // one probe per lane, four per point in flight
       // the quadrant boundaries of the probed voxel come in its slot's count word, wherever linear probing finds the slot
       uint32_t f_mine, n_mine, qv;
-      nn_resolve(m, slots4, key, sl, c_mine >= 0, f_mine, n_mine, &qv);
+      nn_resolve<OFF32>(m, slots4, key, sl, c_mine >= 0, f_mine, n_mine, &qv);
       quad_narrow(m, qv, c_mine, qx, qy, nnkey_d2(best), f_mine, n_mine);
       const uint32_t first[4] = {quad_bcast<0>(f_mine), quad_bcast<1>(f_mine), quad_bcast<2>(f_mine), quad_bcast<3>(f_mine)};
       const uint32_t cnt[4] = {quad_bcast<0>(n_mine), quad_bcast<1>(n_mine), quad_bcast<2>(n_mine), quad_bcast<3>(n_mine)};
-      best = nn_scan_merged_quad<4>(spts, first, cnt, sub, qx, qy, qz, best);
+      best = nn_scan_merged_quad<4, OFF32>(spts, first, cnt, sub, qx, qy, qz, best);
       if (cand) cand &= quad_bound_mask(qb, sub, nnkey_d2(best)) | (1u << 13);
     }
     if (!bounded || nnkey_idx(best) != 0xFFFFFFFFu) break;
@@ -683,7 +698,7 @@ __device__ __forceinline__ NNResult nn_search_quad(const MapView& m, uint32_t su
     todo = 0x07FFFFFFu;
   }
   if (nnkey_idx(best) != 0xFFFFFFFFu) {
-    r.pt = pts4[nnkey_idx(best)];
+    r.pt = *gat<OFF32>(pts4, nnkey_idx(best));
     r.d2 = nnkey_d2(best);
     r.found = true;
   }

@@ -92,7 +92,9 @@ struct FlatInsertMin {
     (void)__hip_atomic_fetch_min(&sh.RES[p], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
 };
-template <class FW, class INS = FlatInsertMin>
+// OFF32: 32-bit byte offsets on scalar bases for the probes and the record loads (gat, mh_nn_device.h); the default is the code every
+// other caller keeps.
+template <bool OFF32 = false, class FW, class INS = FlatInsertMin>
 __device__ __forceinline__ uint32_t flat_plan_scan(FW& sh, const MapView& m, uint32_t lane, uint32_t cmask, unsigned long long kbase,
                                                    float px, float py, float pz, float b0, unsigned long long init,
                                                    const INS ins = INS()) {
@@ -144,7 +146,7 @@ __device__ __forceinline__ uint32_t flat_plan_scan(FW& sh, const MapView& m, uin
         const uint32_t c = base + 64u * (uint32_t)k + lane;
         ent[k] = sh.CL[c < n_cands ? c : 0u];  // (clamped: the load of an idle lane is a hit on entry 0's slot)
         keys[k] = nn_key_of(sh.KB[ent[k] & 63u], (int)(ent[k] >> 8));
-        sls[k] = slots4[hash_key(keys[k]) & m.mask];
+        sls[k] = *gat<OFF32>(slots4, hash_key(keys[k]) & m.mask);
       }
 #pragma unroll
       for (int k = 0; k < kFlatProbes; k++) {
@@ -155,7 +157,7 @@ __device__ __forceinline__ uint32_t flat_plan_scan(FW& sh, const MapView& m, uin
         const int code = (int)(ent[k] >> 8);
         const f32x4 P = sh.P[p];
         uint32_t f, cnt, qv;
-        nn_resolve(m, slots4, keys[k], sls[k], act, f, cnt, &qv);
+        nn_resolve<OFF32>(m, slots4, keys[k], sls[k], act, f, cnt, &qv);
         quad_narrow(m, qv, code, P.x, P.y, P.w, f, cnt);
         const uint32_t nchunks = (cnt + (uint32_t)kFlatLPP - 1u) / (uint32_t)kFlatLPP;
         // chunk space by a DPP prefix sum over the wave's candidates of this pass (the order of the chunks does not matter
@@ -199,7 +201,7 @@ __device__ __forceinline__ uint32_t flat_plan_scan(FW& sh, const MapView& m, uin
         pp[u] = sh.CHP[tt];
         const uint32_t last = ch >> 30;
         valid[u] = ok && sub <= last;
-        rec[u] = spts[(ch & 0x3FFFFFFFu) + (sub < last ? sub : last)];  // clamped into the chunk: no load behind a branch
+        rec[u] = *gat<OFF32>(spts, (ch & 0x3FFFFFFFu) + (sub < last ? sub : last));  // clamped into the chunk: no load behind a branch
       }
 #pragma unroll
       for (int u = 0; u < kFlatW; u++) {
@@ -224,6 +226,9 @@ __device__ __forceinline__ uint32_t flat_plan_scan(FW& sh, const MapView& m, uin
 __device__ __forceinline__ float flat_signed_d2(float d2, bool accepted) {
   return __uint_as_float(__float_as_uint(d2) | (accepted ? 0u : 0x80000000u));
 }
+// OFF32: every byte offset into the slot table, both record arrays and the scan's arrays fits 32 bits (the host's flat_off32): they
+// are formed in 32 bits on scalar bases (gat, mh_nn_device.h).
+template <bool OFF32 = false>
 __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, const double* __restrict__ T, float thr2,
                                                 float ang2, bool have_prev, const float* __restrict__ lx,
                                                 const float* __restrict__ ly, const float* __restrict__ lz, uint32_t n,
@@ -236,9 +241,9 @@ __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, 
   const gpts_ptr pts4 = (gpts_ptr)m.pts;
   const gpts_ptr spts = (gpts_ptr)m.pts_q;
   // ---- A1: the point ------------------------------------------------------------------------------------------------
-  const float x = G(lx)[ic], y = G(ly)[ic], z = G(lz)[ic];
+  const float x = *gat<OFF32>(G(lx), ic), y = *gat<OFF32>(G(ly), ic), z = *gat<OFF32>(G(lz), ic);
   f32x4 prev = (f32x4){0.f, 0.f, 0.f, __builtin_inff()};
-  if (have_prev) prev = G(reinterpret_cast<const f32x4*>(pair_q))[ic];  // grid-uniform branch
+  if (have_prev) prev = *gat<OFF32>(G(reinterpret_cast<const f32x4*>(pair_q)), ic);  // grid-uniform branch
   float px, py, pz;
   transform_point(T, x, y, z, px, py, pz);
   float b0 = __builtin_inff();
@@ -260,7 +265,7 @@ __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, 
   const int cx = voxel_of(px, m.inv_vs, m.trunc), cy = voxel_of(py, m.inv_vs, m.trunc), cz = voxel_of(pz, m.inv_vs, m.trunc);
   const unsigned long long kbase = pack_key(cx - 1, cy - 1, cz - 1);
   if (__ballot(unbounded) != 0ull) {  // stage 0 (wave-uniform): the own voxel of the points that have no bound
-    n_cands = flat_plan_scan(sh, m, lane, unbounded ? (1u << 13) : 0u, kbase, px, py, pz, b0, 0x7F800000FFFFFFFFull);
+    n_cands = flat_plan_scan<OFF32>(sh, m, lane, unbounded ? (1u << 13) : 0u, kbase, px, py, pz, b0, 0x7F800000FFFFFFFFull);
     const unsigned long long r0 = sh.RES[lane];  // (n_cands > 0: somebody is unbounded)
     if (unbounded && (uint32_t)r0 != 0xFFFFFFFFu && sh.SLOWF[lane] == 0) {  // what it found becomes the bound of stage 1
       own_done = true;
@@ -309,8 +314,8 @@ __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, 
       cmask = 0;
     }
   }
-  n_cands = flat_plan_scan(sh, m, lane, cmask, kbase, px, py, pz, b0,
-                           own_done ? res0 : (((unsigned long long)__float_as_uint(b0) << 32) | 0xFFFFFFFFull));
+  n_cands = flat_plan_scan<OFF32>(sh, m, lane, cmask, kbase, px, py, pz, b0,
+                                  own_done ? res0 : (((unsigned long long)__float_as_uint(b0) << 32) | 0xFFFFFFFFull));
   // ---- C: the pairing ----------------------------------------------------------------------------------------------------
   bool slow = in && !planned;
   float b0s = b0;  // the bound phase D starts from
@@ -324,12 +329,12 @@ __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, 
     }
     const uint32_t idx = (uint32_t)res;
     if (planned && !spilled && idx != 0xFFFFFFFFu) {
-      const f32x4 w = pts4[idx];
+      const f32x4 w = *gat<OFF32>(pts4, idx);
       const float d2 = __uint_as_float((uint32_t)(res >> 32));
       const float n2 = (px * px + py * py) + pz * pz;
       const bool ok = d2 < thr2 + ang2 * n2;
-      G(reinterpret_cast<f32x4*>(pair_q))[ic] = (f32x4){w.x, w.y, w.z, flat_signed_d2(d2, ok)};
-      G(pair_gidx)[ic] = ok ? __float_as_uint(w.w) : kNoMatch;
+      *gat<OFF32>(G(reinterpret_cast<f32x4*>(pair_q)), ic) = (f32x4){w.x, w.y, w.z, flat_signed_d2(d2, ok)};
+      *gat<OFF32>(G(pair_gidx), ic) = ok ? __float_as_uint(w.w) : kNoMatch;
     } else if (planned) {
       slow = true;
       if (!spilled) b0s = __builtin_inff();  // the bound was not attained inside the block: once more, without it
@@ -351,13 +356,13 @@ __device__ __forceinline__ void match_flat_wave(FlatWave& sh, const MapView& m, 
     if (k < ns) {  // whole quads
       const uint32_t p = sh.SL[k];
       const f32x4 P = sh.P[p];
-      const NNResult r = nn_search_quad(m, sub, P.x, P.y, P.z, P.w);
+      const NNResult r = nn_search_quad<OFF32>(m, sub, P.x, P.y, P.z, P.w);
       if (sub == 0u) {
         const uint32_t ip = i0 + p;
         const float n2 = (P.x * P.x + P.y * P.y) + P.z * P.z;
         const bool ok = r.found && (r.d2 < thr2 + ang2 * n2);
-        G(reinterpret_cast<f32x4*>(pair_q))[ip] = (f32x4){r.pt.x, r.pt.y, r.pt.z, flat_signed_d2(r.d2, ok)};
-        G(pair_gidx)[ip] = ok ? __float_as_uint(r.pt.w) : kNoMatch;
+        *gat<OFF32>(G(reinterpret_cast<f32x4*>(pair_q)), ip) = (f32x4){r.pt.x, r.pt.y, r.pt.z, flat_signed_d2(r.d2, ok)};
+        *gat<OFF32>(G(pair_gidx), ip) = ok ? __float_as_uint(r.pt.w) : kNoMatch;
       }
     }
   }
