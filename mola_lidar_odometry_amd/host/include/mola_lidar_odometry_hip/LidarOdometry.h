@@ -185,6 +185,23 @@ class SensorSync {
 std::vector<TPose3D> relocalization_grid(const TPose3D& mean, const double cov[36], double step_xy, double step_yaw_rad,
                                          double sigmas = 3.0, size_t max_candidates = 65536);
 
+// Steps 2-4 of LidarOdometry::relocalizeNearPose on their own (the driver calls this; so does a loop closure's verification,
+// LoopClosure.h): ONE mh_score_poses of `local_layer` of pcLocal (a DevicePointCloud) against `global_layer` of pcGlobal (a device
+// map) over all candidates at score_threshold; rank by (n_paired descending, cost ascending, index ascending), keep refine_top_k;
+// icp.align from each kept candidate with hooks cleared and no prior, one after another; the winner has the highest quality, ties
+// go to the better rank.  The ICP's dynamic variables are the caller's business.  `seconds` (optional): wall time is added to its
+// entries "score" and "refine".
+struct RelocalizationRefinement {
+  std::vector<uint32_t> ranks;           // the candidates refined, in rank order
+  std::vector<mh_pose_score> scores;     // ... and their scores
+  bool have = false;                     // false: no candidate at all
+  mp2p_icp_hip::Results best;            // the winner's alignment
+};
+RelocalizationRefinement score_rank_refine(ICP& icp, const mp2p_icp_hip::Parameters& icp_params, const mp2p_icp_hip::metric_map_t& pcLocal,
+                                           const mp2p_icp_hip::metric_map_t& pcGlobal, const std::string& global_layer, const std::string& local_layer,
+                                           const std::vector<TPose3D>& candidates, double score_threshold, uint32_t refine_top_k,
+                                           std::map<std::string, double>* seconds = nullptr);
+
 // Place recognition over the key-frames of a session (include/molahip.h, mh_place_*): an mh_place_db of the polar height
 // descriptors of the frames' first stored layer (layers[0]: the input layer of the first FilterMerge step, vehicle frame) and the
 // frame every descriptor belongs to.  Descriptors are recomputed from the stored layers; the key-frame file does not hold them.
@@ -577,5 +594,8 @@ class LidarOdometry {
   bool intensity_input_ = false;  // setIntensityInput
   std::map<std::string, double> profile_;
 };
+
+// the relocalization: block of a pipeline file as initialize() reads it (defaults when absent; std::runtime_error on values out of range)
+LidarOdometry::RelocalizationOptions relocalization_options(const Config& pipeline);
 
 }  // namespace mola_hip

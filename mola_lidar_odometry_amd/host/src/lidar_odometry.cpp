@@ -850,6 +850,42 @@ LidarOdometry::~LidarOdometry() {
   }
 }
 
+// the relocalization: block (this implementation's own key): the pose-candidate search and the place descriptor
+LidarOdometry::RelocalizationOptions relocalization_options(const Config& cfg) {
+  LidarOdometry::RelocalizationOptions o;
+  if (cfg.has("relocalization")) {
+    const Config& r = cfg["relocalization"];
+    if (r.has("score_threshold") && !r["score_threshold"].isNull()) o.score_threshold = r["score_threshold"].asString();
+    if (r.has("step_xy") && !r["step_xy"].isNull()) o.step_xy = to_double(r["step_xy"].asString());
+    if (r.has("step_yaw_deg")) o.step_yaw_deg = to_double(r["step_yaw_deg"].asString());
+    if (r.has("sigmas")) o.sigmas = to_double(r["sigmas"].asString());
+    if (r.has("refine_top_k")) o.refine_top_k = (uint32_t)to_double(r["refine_top_k"].asString());
+    if (r.has("max_candidates")) o.max_candidates = (uint32_t)to_double(r["max_candidates"].asString());
+    auto num = [&](const char* k, double& v) { if (r.has(k)) v = to_double(r[k].asString()); };
+    auto cnt = [&](const char* k, uint32_t& v) { if (r.has(k)) v = (uint32_t)to_double(r[k].asString()); };
+    cnt("place_rings", o.place_rings);
+    cnt("place_sectors", o.place_sectors);
+    num("place_min_range", o.place_min_range);
+    num("place_max_range", o.place_max_range);
+    num("place_z_min", o.place_z_min);
+    num("place_z_max", o.place_z_max);
+    cnt("place_top_k", o.place_top_k);
+    num("place_sigma_xy", o.place_sigma_xy);
+    num("place_sigma_yaw_deg", o.place_sigma_yaw_deg);
+    if (o.place_rings < 1 || o.place_rings > MH_PLACE_MAX_RINGS || o.place_sectors < 8 || o.place_sectors > MH_PLACE_MAX_SECTORS || o.place_sectors % 8 ||
+        !(o.place_min_range >= 0.0) || !(o.place_min_range < o.place_max_range) || !std::isfinite(o.place_max_range) || !(o.place_z_min < o.place_z_max) ||
+        !std::isfinite(o.place_z_min) || !std::isfinite(o.place_z_max) || o.place_top_k < 1 || !(o.place_sigma_xy >= 0.0) || !std::isfinite(o.place_sigma_xy) ||
+        !(o.place_sigma_yaw_deg >= 0.0) || !std::isfinite(o.place_sigma_yaw_deg))
+      throw std::runtime_error("LidarOdometry (HIP): relocalization: place_rings in [1, 32], place_sectors a multiple of 8 in [8, 128], 0 <= place_min_range "
+                               "< place_max_range, place_z_min < place_z_max, place_top_k >= 1, place_sigma_xy >= 0 and place_sigma_yaw_deg >= 0 are required");
+    if (!(o.step_xy >= 0.0) || !(o.step_yaw_deg > 0.0) || !(o.sigmas > 0.0) || o.refine_top_k < 1 ||
+        o.max_candidates < 1 || o.max_candidates > MH_SCORE_MAX_POSES)
+      throw std::runtime_error("LidarOdometry (HIP): relocalization: step_xy >= 0, step_yaw_deg > 0, sigmas > 0, refine_top_k >= 1 and "
+                               "1 <= max_candidates <= " + std::to_string(MH_SCORE_MAX_POSES) + " are required");
+  }
+  return o;
+}
+
 void LidarOdometry::initialize(const Config& cfg) {
   if (plan_ || gplan_) throw std::runtime_error("LidarOdometry::initialize() called twice; create a new object instead");
   params_.load_from(cfg["params"]);
@@ -939,38 +975,7 @@ void LidarOdometry::initialize(const Config& cfg) {
       init_loc_.relocalize = true;
     }
   }
-  reloc_opts_ = RelocalizationOptions();
-  if (cfg.has("relocalization")) {
-    const Config& r = cfg["relocalization"];
-    if (r.has("score_threshold") && !r["score_threshold"].isNull()) reloc_opts_.score_threshold = r["score_threshold"].asString();
-    if (r.has("step_xy") && !r["step_xy"].isNull()) reloc_opts_.step_xy = to_double(r["step_xy"].asString());
-    if (r.has("step_yaw_deg")) reloc_opts_.step_yaw_deg = to_double(r["step_yaw_deg"].asString());
-    if (r.has("sigmas")) reloc_opts_.sigmas = to_double(r["sigmas"].asString());
-    if (r.has("refine_top_k")) reloc_opts_.refine_top_k = (uint32_t)to_double(r["refine_top_k"].asString());
-    if (r.has("max_candidates")) reloc_opts_.max_candidates = (uint32_t)to_double(r["max_candidates"].asString());
-    auto num = [&](const char* k, double& v) { if (r.has(k)) v = to_double(r[k].asString()); };
-    auto cnt = [&](const char* k, uint32_t& v) { if (r.has(k)) v = (uint32_t)to_double(r[k].asString()); };
-    cnt("place_rings", reloc_opts_.place_rings);
-    cnt("place_sectors", reloc_opts_.place_sectors);
-    num("place_min_range", reloc_opts_.place_min_range);
-    num("place_max_range", reloc_opts_.place_max_range);
-    num("place_z_min", reloc_opts_.place_z_min);
-    num("place_z_max", reloc_opts_.place_z_max);
-    cnt("place_top_k", reloc_opts_.place_top_k);
-    num("place_sigma_xy", reloc_opts_.place_sigma_xy);
-    num("place_sigma_yaw_deg", reloc_opts_.place_sigma_yaw_deg);
-    const RelocalizationOptions& o = reloc_opts_;
-    if (o.place_rings < 1 || o.place_rings > MH_PLACE_MAX_RINGS || o.place_sectors < 8 || o.place_sectors > MH_PLACE_MAX_SECTORS || o.place_sectors % 8 ||
-        !(o.place_min_range >= 0.0) || !(o.place_min_range < o.place_max_range) || !std::isfinite(o.place_max_range) || !(o.place_z_min < o.place_z_max) ||
-        !std::isfinite(o.place_z_min) || !std::isfinite(o.place_z_max) || o.place_top_k < 1 || !(o.place_sigma_xy >= 0.0) || !std::isfinite(o.place_sigma_xy) ||
-        !(o.place_sigma_yaw_deg >= 0.0) || !std::isfinite(o.place_sigma_yaw_deg))
-      throw std::runtime_error("LidarOdometry (HIP): relocalization: place_rings in [1, 32], place_sectors a multiple of 8 in [8, 128], 0 <= place_min_range "
-                               "< place_max_range, place_z_min < place_z_max, place_top_k >= 1, place_sigma_xy >= 0 and place_sigma_yaw_deg >= 0 are required");
-    if (!(reloc_opts_.step_xy >= 0.0) || !(reloc_opts_.step_yaw_deg > 0.0) || !(reloc_opts_.sigmas > 0.0) || reloc_opts_.refine_top_k < 1 ||
-        reloc_opts_.max_candidates < 1 || reloc_opts_.max_candidates > MH_SCORE_MAX_POSES)
-      throw std::runtime_error("LidarOdometry (HIP): relocalization: step_xy >= 0, step_yaw_deg > 0, sigmas > 0, refine_top_k >= 1 and "
-                               "1 <= max_candidates <= " + std::to_string(MH_SCORE_MAX_POSES) + " are required");
-  }
+  reloc_opts_ = relocalization_options(cfg);
 
   // a saved map (:465-470): read now, names held against the plan's; the device maps are made by reset()
   loaded_maps_.clear();
@@ -1351,6 +1356,55 @@ std::vector<PlaceIndex::Match> PlaceIndex::query(const DevicePointCloud& layer) 
   return m;
 }
 
+RelocalizationRefinement score_rank_refine(ICP& icp, const mp2p_icp_hip::Parameters& icp_params, const mp2p_icp_hip::metric_map_t& pcLocal,
+                                           const mp2p_icp_hip::metric_map_t& pcGlobal, const std::string& global_layer, const std::string& local_layer,
+                                           const std::vector<TPose3D>& cand, double score_threshold, uint32_t refine_top_k,
+                                           std::map<std::string, double>* seconds) {
+  const auto gi = pcGlobal.layers.find(global_layer);
+  const auto li = pcLocal.layers.find(local_layer);
+  auto global = gi == pcGlobal.layers.end() ? nullptr : std::dynamic_pointer_cast<HashedVoxelPointCloud>(gi->second);
+  auto local = li == pcLocal.layers.end() ? nullptr : std::dynamic_pointer_cast<DevicePointCloud>(li->second);
+  if (!global || !local)
+    throw std::runtime_error("score_rank_refine: the layers '" + global_layer + "' / '" + local_layer + "' are not a device map and a device point layer of the maps given");
+  RelocalizationRefinement out;
+  const auto t0 = std::chrono::steady_clock::now();
+  // ---- score: one launch over all candidates
+  std::vector<double> poses(12 * cand.size());
+  for (size_t c = 0; c < cand.size(); c++) {
+    const CPose3D P(cand[c]);
+    std::copy(P.T, P.T + 12, &poses[12 * c]);
+  }
+  std::vector<mh_pose_score> scores(cand.size());
+  global->prepareSearch(score_threshold);
+  check(mh_score_poses(global->handle(), local->handle(), poses.data(), cand.size(), score_threshold, 0.0, scores.data(), MH_MEM_HOST), "mh_score_poses");
+  // ---- rank: (n_paired descending, cost ascending, index ascending)
+  std::vector<uint32_t> order(cand.size());
+  for (size_t c = 0; c < order.size(); c++) order[c] = (uint32_t)c;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    if (scores[a].n_paired != scores[b].n_paired) return scores[a].n_paired > scores[b].n_paired;
+    return scores[a].cost < scores[b].cost;
+  });
+  order.resize(std::min<size_t>(order.size(), refine_top_k));
+  out.ranks = order;
+  for (uint32_t c : order) out.scores.push_back(scores[c]);
+  const auto t1 = std::chrono::steady_clock::now();
+  // ---- refine the kept candidates, one after another
+  for (uint32_t c : order) {
+    mp2p_icp_hip::Results res;
+    icp.clearHooks();
+    icp.align(pcLocal, pcGlobal, cand[c], icp_params, res, std::nullopt);
+    if (!out.have || res.quality > out.best.quality) {  // (ties go to the better rank)
+      out.best = res;
+      out.have = true;
+    }
+  }
+  if (seconds) {
+    (*seconds)["score"] += std::chrono::duration<double>(t1 - t0).count();
+    (*seconds)["refine"] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+  }
+  return out;
+}
+
 void LidarOdometry::serve_relocalization(double t, ScanRecord& rec) {
   StageTimer tt(profile_, "onLidar.2.relocalize");
   ICP& icp = *icp_[1];
@@ -1360,9 +1414,8 @@ void LidarOdometry::serve_relocalization(double t, ScanRecord& rec) {
   scan_layers(obs, glob);
   const auto gi = glob.layers.find(gname);
   const auto li = obs.layers.find(lname);
-  auto global = gi == glob.layers.end() ? nullptr : std::dynamic_pointer_cast<HashedVoxelPointCloud>(gi->second);
-  auto local = li == obs.layers.end() ? nullptr : std::dynamic_pointer_cast<DevicePointCloud>(li->second);
-  if (!global || !local)
+  if (gi == glob.layers.end() || li == obs.layers.end() || !std::dynamic_pointer_cast<HashedVoxelPointCloud>(gi->second) ||
+      !std::dynamic_pointer_cast<DevicePointCloud>(li->second))
     throw std::runtime_error("LidarOdometry: relocalization: the layers '" + gname + "' / '" + lname + "' of the no-motion-model ICP block are not among this scan's");
   const double thr = reloc_score_threshold(gname);
   const double step = reloc_opts_.step_xy > 0 ? reloc_opts_.step_xy : thr;
@@ -1374,38 +1427,13 @@ void LidarOdometry::serve_relocalization(double t, ScanRecord& rec) {
                                                               reloc_opts_.step_yaw_deg * kDeg2Rad, reloc_opts_.sigmas, reloc_opts_.max_candidates);
   rec.relocalization_tried = true;
   rec.reloc_candidates = (uint32_t)cand.size();
-  // ---- score: one launch over all candidates
-  std::vector<double> poses(12 * cand.size());
-  for (size_t c = 0; c < cand.size(); c++) {
-    const CPose3D P(cand[c]);
-    std::copy(P.T, P.T + 12, &poses[12 * c]);
-  }
-  std::vector<mh_pose_score> scores(cand.size());
-  global->prepareSearch(thr);
-  check(mh_score_poses(global->handle(), local->handle(), poses.data(), cand.size(), thr, 0.0, scores.data(), MH_MEM_HOST), "mh_score_poses");
-  // ---- rank: (n_paired descending, cost ascending, index ascending)
-  std::vector<uint32_t> order(cand.size());
-  for (size_t c = 0; c < order.size(); c++) order[c] = (uint32_t)c;
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    if (scores[a].n_paired != scores[b].n_paired) return scores[a].n_paired > scores[b].n_paired;
-    return scores[a].cost < scores[b].cost;
-  });
-  order.resize(std::min<size_t>(order.size(), reloc_opts_.refine_top_k));
-  rec.reloc_ranks = order;
-  rec.reloc_best_n_paired = order.empty() ? 0 : scores[order[0]].n_paired;
-  // ---- refine the kept candidates, one after another
-  bool have = false;
-  mp2p_icp_hip::Results best;
-  for (uint32_t c : order) {
-    mp2p_icp_hip::Results res;
-    icp.clearHooks();
-    icp.align(obs, glob, cand[c], icp_params_[1], res, std::nullopt);
-    profile_["relocalize.align_calls"] += 1.0;
-    if (!have || res.quality > best.quality) {  // (ties go to the better rank)
-      best = res;
-      have = true;
-    }
-  }
+  // ---- score, rank, refine (the step a loop closure's verification shares)
+  const RelocalizationRefinement rr = score_rank_refine(icp, icp_params_[1], obs, glob, gname, lname, cand, thr, reloc_opts_.refine_top_k);
+  rec.reloc_ranks = rr.ranks;
+  rec.reloc_best_n_paired = rr.scores.empty() ? 0 : rr.scores[0].n_paired;
+  profile_["relocalize.align_calls"] += (double)rr.ranks.size();
+  const bool have = rr.have;
+  const mp2p_icp_hip::Results& best = rr.best;
   rec.reloc_best_quality = have ? best.quality : 0.0;
   // ---- accept
   if (have && best.quality >= params_.min_icp_goodness) {

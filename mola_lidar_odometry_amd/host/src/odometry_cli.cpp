@@ -42,6 +42,7 @@
 #include <mutex>
 
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
+#include "mola_lidar_odometry_hip/LoopClosure.h"
 #include "molahip.h"
 
 namespace {
@@ -318,10 +319,12 @@ int main(int argc, char** argv) {
   RunOptions opt;
   bool print_profile = false, plan_only = false;
   std::string build_from;  // --build-session-map
+  std::string close_from, loop_report;  // --close-loops, --loop-report
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
                       "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE] [--relocalize-in-keyframes]\n"
                       "       molahip-lo-cli --build-session-map KEYFRAMES --save-local-map FILE [--device N]\n"
+                      "       molahip-lo-cli --close-loops KEYFRAMES --pipeline FILE.yaml --output-simplemap FILE [--output-session-map FILE] [--loop-report FILE.json] [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
@@ -331,6 +334,9 @@ int main(int argc, char** argv) {
                       "  --output-session-map: ... and build the maps of the whole drive from them into FILE (FILE_<k> for several sequences),\n"
                       "  a local-map file like --save-local-map's\n"
                       "  --build-session-map: no sequence is run: the maps are built from the key-frame file KEYFRAMES into --save-local-map's FILE\n"
+                      "  --close-loops: no sequence is run: revisits among the key-frames of KEYFRAMES are detected, verified on the device and closed\n"
+                      "  (the pipeline's loop_closure: block); the key-frames with corrected poses go to --output-simplemap's FILE, the maps built from\n"
+                      "  them to --output-session-map's, the report (pairs tried, qualities, optimiser cost, stage times) to --loop-report's\n"
                       "  --relocalize-in-keyframes: the vehicle is found in a saved session without a prior pose: place recognition over the\n"
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
@@ -355,6 +361,8 @@ int main(int argc, char** argv) {
       else if (a == "--output-simplemap") opt.output_simplemap = val("--output-simplemap");
       else if (a == "--output-session-map") opt.output_session_map = val("--output-session-map");
       else if (a == "--build-session-map") build_from = val("--build-session-map");
+      else if (a == "--close-loops") close_from = val("--close-loops");
+      else if (a == "--loop-report") loop_report = val("--loop-report");
       else if (a == "--relocalize-in-keyframes") opt.relocalize_in_keyframes = true;
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
@@ -364,6 +372,36 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n%s", e.what(), usage);
       return 2;
     }
+  }
+  if (!close_from.empty()) {  // the loops of a recorded drive closed, no sequence
+    if (pipeline.empty() || opt.output_simplemap.empty() || !seq_dirs.empty() || !build_from.empty()) {
+      fprintf(stderr, "--close-loops needs --pipeline FILE and --output-simplemap FILE and takes no sequence\n%s", usage);
+      return 2;
+    }
+    try {
+      auto ctx = std::make_shared<mp2p_icp_hip::DeviceContext>(devices.empty() ? 0 : devices[0]);
+      const mola_hip::LoopClosureResult r =
+          mola_hip::close_loops(molahip_host::read_keyframe_file(close_from), mp2p_icp_hip::Config::FromYamlFile(pipeline), ctx);
+      molahip_host::write_keyframe_file(opt.output_simplemap, r.corrected);
+      if (!opt.output_session_map.empty()) mola_hip::build_session_map_file(r.corrected, opt.output_session_map, ctx);
+      const std::string json = r.report.toJson();
+      if (!loop_report.empty()) {
+        FILE* f = fopen(loop_report.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + loop_report);
+        fputs(json.c_str(), f);
+        fclose(f);
+      }
+      size_t accepted = 0;
+      for (const auto& p : r.report.pairs) accepted += p.accepted ? 1 : 0;
+      printf("{\"keyframe_file\": \"%s\", \"frames\": %zu, \"pairs_tried\": %zu, \"loops_closed\": %zu, \"cost_before\": %.9g, \"cost_after\": %.9g, "
+             "\"optimizer_iterations\": %u, \"output_simplemap\": \"%s\"}\n",
+             close_from.c_str(), r.corrected.frames.size(), r.report.pairs.size(), accepted, r.report.cost_before, r.report.cost_after,
+             r.report.optimizer_iterations, opt.output_simplemap.c_str());
+    } catch (const std::exception& e) {
+      fprintf(stderr, "molahip-lo-cli: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (!build_from.empty()) {  // the maps of a recorded drive, no sequence
     if (opt.save_local_map.empty() || !seq_dirs.empty()) {

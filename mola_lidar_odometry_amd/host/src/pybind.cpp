@@ -7,6 +7,7 @@
 #include <pybind11/stl.h>
 
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
+#include "mola_lidar_odometry_hip/LoopClosure.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 #include "molahip_host/plugin_switches.h"
 
@@ -184,6 +185,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("alignPath", &ICP::alignPath)
       .def("precomputeSchedule", &ICP::precomputeSchedule)
       .def("setHookReplay", &ICP::setHookReplay)
+      .def("setKeepFinalPairings", &ICP::setKeepFinalPairings)
       .def("lastAlignUsedFusedPath", &ICP::lastAlignUsedFusedPath)
       .def("setIterationHook", [](ICP& icp, std::function<bool(uint32_t, std::vector<double>)> f) {
         icp.setIterationHook([f](const ICP::IterationHook_Input& in) {
@@ -697,5 +699,139 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     }
     return py::make_tuple(poses, rows); },
         py::arg("mean"), py::arg("cov"), py::arg("step_xy"), py::arg("step_yaw_rad"), py::arg("sigmas") = 3.0, py::arg("max_candidates") = 65536);
+  // steps 2-4 of a relocalization on their own (mola_hip::score_rank_refine): candidates = TPose3D rows [k, 6]; host PointCloud
+  // layers of pcLocal are uploaded to the global layer's device first (the driver's layers live there already).
+  // -> {ranks, n_paired, cost (of the kept candidates), have, quality, iterations, pose [12]}
+  m.def("score_rank_refine", [](ICP& icp, const Parameters& p, const metric_map_t& pcLocal, const metric_map_t& pcGlobal, const std::string& global_layer,
+                                const std::string& local_layer, py::array_t<double, py::array::c_style | py::array::forcecast> candidates,
+                                double score_threshold, uint32_t refine_top_k) {
+    if (candidates.ndim() != 2 || candidates.shape(1) != 6) throw std::runtime_error("candidates must be [k, 6] rows of x y z yaw pitch roll");
+    const auto gi = pcGlobal.layers.find(global_layer);
+    auto g = gi == pcGlobal.layers.end() ? nullptr : std::dynamic_pointer_cast<HashedVoxelPointCloud>(gi->second);
+    if (!g) throw std::runtime_error("score_rank_refine: no device map called '" + global_layer + "' in pcGlobal");
+    metric_map_t local;
+    for (const auto& [name, layer] : pcLocal.layers) {
+      auto host_cloud = std::dynamic_pointer_cast<PointCloud>(layer);
+      if (!host_cloud) { local.layers[name] = layer; continue; }
+      auto dev = std::make_shared<DevicePointCloud>(g->context());
+      dev->setPoints(host_cloud->x.data(), host_cloud->y.data(), host_cloud->z.data(), host_cloud->size());
+      local.layers[name] = dev;
+    }
+    std::vector<TPose3D> cand((size_t)candidates.shape(0));
+    auto a = candidates.unchecked<2>();
+    for (size_t c = 0; c < cand.size(); c++) cand[c] = TPose3D{a(c, 0), a(c, 1), a(c, 2), a(c, 3), a(c, 4), a(c, 5)};
+    mola_hip::RelocalizationRefinement r;
+    {
+      py::gil_scoped_release nogil;
+      r = mola_hip::score_rank_refine(icp, p, local, pcGlobal, global_layer, local_layer, cand, score_threshold, refine_top_k);
+    }
+    std::vector<uint32_t> n_paired;
+    std::vector<uint64_t> cost;
+    for (const auto& s : r.scores) n_paired.push_back(s.n_paired), cost.push_back(s.cost);
+    py::dict d;
+    d["ranks"] = r.ranks; d["n_paired"] = n_paired; d["cost"] = cost; d["have"] = r.have; d["quality"] = r.best.quality;
+    d["iterations"] = r.best.nIterations; d["pose"] = std::vector<double>(r.best.optimal_tf.mean.T, r.best.optimal_tf.mean.T + 12);
+    return d; }, py::arg("icp"), py::arg("params"), py::arg("pcLocal"), py::arg("pcGlobal"), py::arg("global_layer"), py::arg("local_layer"),
+        py::arg("candidates"), py::arg("score_threshold"), py::arg("refine_top_k"));
+  // ---- loop closure over a key-frame set (mola_lidar_odometry_hip/LoopClosure.h)
+  using mola_hip::LoopClosureOptions;
+  auto opts2dict = [](const LoopClosureOptions& o) {
+    py::dict d;
+    d["min_travel"] = o.min_travel; d["gate_base"] = o.gate_base; d["gate_rate"] = o.gate_rate; d["max_place_dist"] = o.max_place_dist;
+    d["top_k"] = o.top_k; d["min_travel_between_closures"] = o.min_travel_between_closures; d["submap_radius"] = o.submap_radius;
+    d["sigma_xy"] = o.sigma_xy; d["sigma_yaw_deg"] = o.sigma_yaw_deg; d["sigma"] = o.sigma; d["min_quality"] = o.min_quality;
+    d["odometry_sigma_xyz"] = o.odometry_sigma_xyz; d["odometry_sigma_rot_deg"] = o.odometry_sigma_rot_deg;
+    d["loop_sigma_xyz"] = o.loop_sigma_xyz; d["loop_sigma_rot_deg"] = o.loop_sigma_rot_deg; d["max_iterations"] = o.max_iterations;
+    d["min_step"] = o.min_step;
+    return d;
+  };
+  // the defaults (sigma: the driver's default initial_sigma) with the dict's entries over them, held to the same ranges
+  auto dict2opts = [](const py::dict& d) {
+    LoopClosureOptions o;
+    o.sigma = mola_hip::LidarOdometry::Params().initial_sigma;
+    auto num = [&](const char* k, double& v) { if (d.contains(k)) v = d[k].cast<double>(); };
+    auto cnt = [&](const char* k, uint32_t& v) { if (d.contains(k)) v = d[k].cast<uint32_t>(); };
+    num("min_travel", o.min_travel); num("gate_base", o.gate_base); num("gate_rate", o.gate_rate); cnt("max_place_dist", o.max_place_dist);
+    cnt("top_k", o.top_k); num("min_travel_between_closures", o.min_travel_between_closures); num("submap_radius", o.submap_radius);
+    num("sigma_xy", o.sigma_xy); num("sigma_yaw_deg", o.sigma_yaw_deg); num("sigma", o.sigma); num("min_quality", o.min_quality);
+    num("odometry_sigma_xyz", o.odometry_sigma_xyz); num("odometry_sigma_rot_deg", o.odometry_sigma_rot_deg);
+    num("loop_sigma_xyz", o.loop_sigma_xyz); num("loop_sigma_rot_deg", o.loop_sigma_rot_deg); cnt("max_iterations", o.max_iterations);
+    num("min_step", o.min_step);
+    o.validate();
+    return o;
+  };
+  // the loop_closure: block of a pipeline Config as a dict (an absent block: the defaults)
+  m.def("loop_closure_options", [opts2dict](const Config& c) { return opts2dict(LoopClosureOptions::FromConfig(c)); });
+  // the candidate rule on host arrays: poses [K, 12], has_points [K], matches[k] = [(frame, shift, dist)] ranked as PlaceIndex.query
+  // ranks them, options as a dict of loop_closure: keys, accept(i, j, shift, dist) -> bool (None: every pair is accepted).
+  // -> [(i, j, shift, dist)] of the pairs handed to accept, in order
+  m.def("loop_candidates", [dict2opts](py::array_t<double, py::array::c_style | py::array::forcecast> poses, const std::vector<bool>& has_points,
+                                       const std::vector<std::vector<std::tuple<uint32_t, uint32_t, uint32_t>>>& matches, const py::dict& options,
+                                       const py::object& accept) {
+    if (poses.ndim() != 2 || poses.shape(1) != 12) throw std::runtime_error("poses must be [K, 12]");
+    const size_t K = (size_t)poses.shape(0);
+    if (has_points.size() != K || matches.size() != K) throw std::runtime_error("has_points and matches need one entry per pose");
+    std::vector<mola_hip::LoopFrame> frames(K);
+    for (size_t k = 0; k < K; k++) {
+      std::copy(poses.data() + 12 * k, poses.data() + 12 * k + 12, frames[k].pose);
+      frames[k].has_points = has_points[k];
+      for (const auto& [f, s, d] : matches[k]) {
+        if (f >= K) throw std::runtime_error("a match names frame " + std::to_string(f) + " of " + std::to_string(K));
+        frames[k].matches.push_back(mola_hip::PlaceIndex::Match{f, s, d});
+      }
+    }
+    std::function<bool(const mola_hip::LoopPair&)> verify;
+    if (!accept.is_none()) verify = [&accept](const mola_hip::LoopPair& p) { return accept(p.i, p.j, p.shift, p.dist).cast<bool>(); };
+    py::list out;
+    for (const auto& p : mola_hip::loop_candidates(frames, dict2opts(options), verify)) out.append(py::make_tuple(p.i, p.j, p.shift, p.dist));
+    return out; }, py::arg("poses"), py::arg("has_points"), py::arg("matches"), py::arg("options") = py::dict(), py::arg("accept") = py::none());
+  // poses [K, 12]; loops = [(a, b, Z: 12 values, node b in node a)]; the weights and the stop as a dict of loop_closure: keys.
+  // -> {poses [K, 12], cost_before, cost_after, iterations, costs}
+  m.def("optimize_pose_graph", [dict2opts](py::array_t<double, py::array::c_style | py::array::forcecast> poses,
+                                           const std::vector<std::tuple<uint32_t, uint32_t, std::vector<double>>>& loops, const py::dict& options) {
+    if (poses.ndim() != 2 || poses.shape(1) != 12) throw std::runtime_error("poses must be [K, 12]");
+    std::vector<mola_hip::PoseGraphEdge> edges;
+    for (const auto& [a, b, Z] : loops) {
+      if (Z.size() != 12) throw std::runtime_error("an edge's Z needs 12 values");
+      mola_hip::PoseGraphEdge e;
+      e.a = a; e.b = b;
+      std::copy(Z.begin(), Z.end(), e.Z);
+      edges.push_back(e);
+    }
+    const std::vector<double> in(poses.data(), poses.data() + poses.size());
+    const LoopClosureOptions o = dict2opts(options);
+    mola_hip::PoseGraphResult r;
+    {
+      py::gil_scoped_release nogil;
+      r = mola_hip::optimize_pose_graph(in, edges, o);
+    }
+    py::array_t<double> P({poses.shape(0), (py::ssize_t)12});
+    std::copy(r.poses.begin(), r.poses.end(), P.mutable_data());
+    py::dict d;
+    d["poses"] = P; d["cost_before"] = r.cost_before; d["cost_after"] = r.cost_after; d["iterations"] = r.iterations; d["costs"] = r.costs;
+    return d; }, py::arg("poses"), py::arg("loops"), py::arg("options") = py::dict());
+  // key-frames (a dict as above, or the path of a key-frame file) and the whole pipeline Config -> (corrected set as a dict, report);
+  // with `output_keyframe_file` the corrected set is also written there
+  m.def("close_loops", [dict2kfset, kfset2dict](const py::object& frames, const Config& pipeline, const std::string& output_keyframe_file) {
+    const molahip_host::KeyFrameSet set = py::isinstance<py::str>(frames) ? molahip_host::read_keyframe_file(frames.cast<std::string>())
+                                                                         : dict2kfset(frames.cast<py::dict>());
+    mola_hip::LoopClosureResult r;
+    {
+      py::gil_scoped_release nogil;
+      r = mola_hip::close_loops(set, pipeline);
+      if (!output_keyframe_file.empty()) molahip_host::write_keyframe_file(output_keyframe_file, r.corrected);
+    }
+    py::dict rep;
+    py::list pairs;
+    for (const auto& p : r.report.pairs) {
+      py::dict d;
+      d["i"] = p.i; d["j"] = p.j; d["shift"] = p.shift; d["dist"] = p.dist; d["candidates"] = p.candidates; d["ranks"] = p.ranks;
+      d["quality"] = p.quality; d["iterations"] = p.iterations; d["accepted"] = p.accepted; d["Z"] = std::vector<double>(p.Z, p.Z + 12);
+      pairs.append(d);
+    }
+    rep["pairs"] = pairs; rep["cost_before"] = r.report.cost_before; rep["cost_after"] = r.report.cost_after;
+    rep["optimizer_iterations"] = r.report.optimizer_iterations; rep["seconds"] = r.report.seconds; rep["counts"] = r.report.counts;
+    rep["json"] = r.report.toJson();
+    return py::make_tuple(kfset2dict(r.corrected), rep); }, py::arg("frames"), py::arg("pipeline"), py::arg("output_keyframe_file") = "");
   m.def("icp_pipeline_from_yaml", [](const Config& c) { auto t = icp_pipeline_from_yaml(c); return py::make_tuple(std::get<0>(t), std::get<1>(t)); });
 }
