@@ -837,6 +837,13 @@ MH_API mh_status mh_icp_align_prefers_solo(const mh_scan* scan, const mh_icp_par
  * each other and that were run again launch by launch (same result bit for bit; expected to stay 0).  Either may be NULL. */
 MH_API void mh_debug_loop_stats(uint64_t* loops_started, uint64_t* loops_abandoned);
 
+/* Statistics (process-wide, no effect on results): launches of the plan / scan matcher (large layers, MH_MATCH=f) that went to the
+ * device so far, by kernel: launches[0] k_match_flat with 32-bit byte offsets, [1] k_match_flat with 64-bit offsets (a map buffer
+ * above 2^32 bytes, a scan above 2^28 points, or MH_NO_OFF32=1), [2] and [3] the same for k_match_flat_b, the lock-step batches'.
+ * They count what ran, not what was decided: a launch replayed from a captured graph counts each time that graph is launched.
+ * The two instantiations give the same bits; the test suite reads these counters to know which one it has checked. */
+MH_API void mh_debug_flat_stats(uint64_t launches[4]);
+
 /* Always 0.  It used to tell the development library from the shipped one; the development library no longer exists: the matcher
  * families it carried -- MH_MATCH=t (tile matcher, map records staged in LDS), w (wave matcher), o (sorted scan) -- lost to the
  * product kernels and were removed, and mh_icp_align / mh_icp_align_batch reject those three letters. */

@@ -272,6 +272,7 @@ _SIGNATURES = {
     "mh_device_count": (C.c_int32, [C.POINTER(C.c_int32)]),
     "mh_debug_fail_allocations": (C.c_int32, [C.c_int32, C.c_int32]),
     "mh_debug_loop_stats": (None, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mh_debug_flat_stats": (None, [C.POINTER(C.c_uint64)]),
     "mh_debug_dev_variants": (C.c_int32, []),
     "mh_abi_version": (C.c_uint32, []),
     "mh_icp_align_prefers_solo": (C.c_int32, [C.c_void_p, C.POINTER(ICPParamsC), C.c_uint32, C.POINTER(C.c_int32)]),
@@ -438,6 +439,15 @@ def loop_stats():
     a, b = C.c_uint64(0), C.c_uint64(0)
     lib().mh_debug_loop_stats(C.byref(a), C.byref(b))
     return int(a.value), int(b.value)
+
+
+def flat_stats():
+    """Launches of the plan / scan matcher that went to the device so far in this process (mh_debug_flat_stats), replays of a
+    captured graph included: (k_match_flat<true>, k_match_flat<false>, k_match_flat_b<true>, k_match_flat_b<false>) -- <true>
+    forms its byte offsets in 32 bits, <false> in 64 (MH_NO_OFF32=1, or a map or scan too large for the former)."""
+    a = (C.c_uint64 * 4)()
+    lib().mh_debug_flat_stats(a)
+    return tuple(int(v) for v in a)
 
 
 def dev_variants() -> bool:

@@ -270,6 +270,12 @@ PlKnnArg pl_knn_arg(const mh_pt2pl_knn_params* params) {
 }
 
 std::atomic<unsigned long long> g_loop16_runs{0}, g_loop16_fallbacks{0};  // one-launch loops started / abandoned for the chain (mh_debug_loop_stats)
+// plan / scan matcher launches that went to the device (mh_debug_flat_stats): k_match_flat<true> | <false> | k_match_flat_b<true> |
+// <false>.  Counted where a launch is issued; the launches a captured chunk holds are counted on every replay (enqueue_cached).
+std::atomic<unsigned long long> g_flat_launches[4];
+inline void count_flat_launches(uint32_t which, uint32_t k) {
+  if (k) g_flat_launches[which].fetch_add(k, std::memory_order_relaxed);
+}
 uint32_t loop_cu_limit(const Switches& sw, int device) {
   static uint32_t cap[64] = {0};
   uint32_t& cu = cap[(unsigned)device % 64u];
@@ -465,6 +471,7 @@ struct AlignJob {
   bool pl = false;    // Matcher_Point2Plane runs before the point matcher (lidar3d-ndt.yaml:195-210)
   bool streaming = false;  // run_streaming(): iterations are enqueued one by one behind the device's published progress
   bool skip_tail = false;  // ... and the covariance kernels + state read-back only once the loop has ended
+  bool flat32 = false;     // Matcher::Flat: k_match_flat<true> (flat_off32 holds and MH_NO_OFF32 is off), decided once in start(); a word of the graph key
   bool loop16 = false;         // run_loop16(): the whole loop of a small layer in ONE launch (plan.loop: k_icp16 / k_icpw)
   bool forbid_loop16 = false;  // ... not for this job: the second attempt after a loop whose workgroups gave up
   LoopAdmission loop_adm;      // what this job holds of the device's admission count while its loop runs
@@ -542,6 +549,7 @@ struct AlignJob {
       MH_TRY(map_ensure_qidx(*sw, map, ctx->stream));
       if (!map->view(*sw).pts_q) return fail(MH_ERR_INTERNAL, "the map's sub-voxel index is missing (matcher variant %d needs it)", (int)mt);
     }
+    flat32 = mt == Matcher::Flat && !sw->no_off32 && flat_off32(map, scan->n);  // (after map_ensure_qidx: pts_q has its size)
     nba = nblk_acc(scan->n);
     // who writes the partials of the first Gauss-Newton step: the row kernel (16 points per workgroup), k_accum, or k_match
     nbm = plan.fused16 ? (uint32_t)((16ull * scan->n + kBlock - 1) / kBlock) : (one_lane(mt) ? nb : nba);
@@ -732,8 +740,9 @@ struct AlignJob {
             hipLaunchKernelGGL(k_accum<false>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                                ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nbm);
         } else if (mt == Matcher::Flat) {
-          hipLaunchKernelGGL(flat_off32(map, n) ? k_match_flat<true> : k_match_flat<false>, dim3(nblk_flat(n)), dim3(kFlatThreads), 0, s,
+          hipLaunchKernelGGL(flat32 ? k_match_flat<true> : k_match_flat<false>, dim3(nblk_flat(n)), dim3(kFlatThreads), 0, s,
                              ctx->d_state, scan->x, scan->y, scan->z, n, mv, ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>());
+          ctx->flat_issued[flat32 ? 0 : 1]++;  // (enqueue_cached counts them: now, or whenever the captured chunk is launched)
           if (prof) MH_HIP(hipEventRecord(ctx->prof_ev[2 * prof_n + 1], s));  // the match kernel alone
           hipLaunchKernelGGL(k_accum<true>, dim3(nba), dim3(kBlock), 0, s, ctx->d_state, 1u, dmk, scan->x, scan->y, scan->z, n,
                              ctx->pair_q.as<float4>(), ctx->pair_gidx.as<uint32_t>(), part, nba);
@@ -791,7 +800,7 @@ struct AlignJob {
                                        (unsigned long long)ctx->pair_gidx.p, (unsigned long long)part,
                                        (unsigned long long)ctx->d_state, (unsigned long long)ctx->d_params,
                                        (unsigned long long)ctx->h_state,
-                                       (pl ? 2ull : 1ull) | (plan.fused16 ? 8ull : 0ull) | (step_chain ? 16ull : 0ull),
+                                       (pl ? 2ull : 1ull) | (plan.fused16 ? 8ull : 0ull) | (step_chain ? 16ull : 0ull) | (flat32 ? 32ull : 0ull),
                                        (unsigned long long)(pl ? ctx->pl_c.p : nullptr),
                                        (unsigned long long)(pl ? ctx->pl_n.p : nullptr),
                                        (unsigned long long)(pl ? ctx->partials_b.p : nullptr),
@@ -984,6 +993,11 @@ int32_t mh_debug_dev_variants(void) {
 void mh_debug_loop_stats(uint64_t* loops_started, uint64_t* loops_abandoned) {
   if (loops_started) *loops_started = g_loop16_runs.load();
   if (loops_abandoned) *loops_abandoned = g_loop16_fallbacks.load();
+}
+
+void mh_debug_flat_stats(uint64_t launches[4]) {
+  if (!launches) return;
+  for (int k = 0; k < 4; k++) launches[k] = g_flat_launches[k].load(std::memory_order_relaxed);
 }
 
 size_t mh_pairs_block_bytes(size_t n_scan_points) {

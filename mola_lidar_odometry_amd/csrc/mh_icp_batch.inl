@@ -173,7 +173,7 @@ struct LockstepGroup {  // (movable, not copyable: the admission)
   uint32_t m = 0;  // iterations of the chunk being enqueued
   uint32_t src = 2, par = 0, launches = 0;  // k_step16_b: the state block (2 = canonical) and the partials half the next launch reads; launches so far
   bool cov = false, done = false, auto_chunk = false;
-  bool off32 = true;       // K_FLAT: flat_off32 holds for every job (k_match_flat_b<true>)
+  bool off32 = true;       // K_FLAT: flat_off32 holds for every job and MH_NO_OFF32 is off (k_match_flat_b<true>)
   bool loop_wave = false;  // ... as k_icpw_b (point layers): every job its own workgroups
   uint32_t gx_loopw = 1;   // ... whose launch has this many workgroups per job
   bool loop_now = false;   // k_icp16_b: the group's whole loops in ONE launch (admit_group_loops; cleared when a job's workgroups gave up)
@@ -323,7 +323,7 @@ mh_status stage_group(const Switches& sw, LockstepGroup& g, const PairsPlan* pp)
     if (g.kind == K_ROWF) bm = d.nbm;
     if (g.kind == K_FLAT) {
       bm = nblk_flat(d.n);
-      g.off32 = g.off32 && flat_off32(j.map, d.n);
+      g.off32 = g.off32 && !sw.no_off32 && flat_off32(j.map, d.n);
     }
     if (g.step_chain()) {  // all jobs' workgroups resident at once: kStepMaxWorkgroups shared between them
       const uint32_t cap = kStepMaxWorkgroups / A ? kStepMaxWorkgroups / A : 1u;
@@ -376,7 +376,10 @@ mh_status enqueue_group_iteration(const Switches& sw, LockstepGroup& g, bool pr)
   if (pr) MH_HIP(hipEventRecord(g.lead->prof_ev[2 * g.prof_n], s));
   switch (g.kind) {
     case K_ROWF: hipLaunchKernelGGL(k_match16f_b, dim3(g.gx_match, A), dim3(kBlock), 0, s, g.dj); break;
-    case K_FLAT: hipLaunchKernelGGL(g.off32 ? k_match_flat_b<true> : k_match_flat_b<false>, dim3(g.gx_match, A), dim3(kFlatThreads), 0, s, g.dj); break;
+    case K_FLAT:
+      hipLaunchKernelGGL(g.off32 ? k_match_flat_b<true> : k_match_flat_b<false>, dim3(g.gx_match, A), dim3(kFlatThreads), 0, s, g.dj);
+      count_flat_launches(g.off32 ? 2u : 3u, 1u);  // (no graph on this path: what is issued runs)
+      break;
     default: hipLaunchKernelGGL(k_match4_b, dim3(g.gx_match, A), dim3(kBlock), 0, s, g.dj); break;
   }
   if (pr) {
@@ -568,7 +571,10 @@ static mh_status align_batch_run(const Switches& sw, size_t n_jobs, const mh_map
     for (size_t j = 0; j < i; j++)
       MH_REQUIRE(scans[j]->ctx != scans[i]->ctx, "each job of a batch needs its own context");
     MH_REQUIRE(!pairs_block || scans[i]->ctx->device == scans[0]->ctx->device, "a pairs block needs all jobs on one device");
-    jobs[i].defer_upload = n_jobs >= 2;  // a lock-step group uploads its jobs' blocks in one staged copy
+    // a lock-step group uploads its jobs' blocks in one staged copy.  A batch of ONE job defers as well: a job that uploads at once
+    // is planned for streaming control (plan_alignment's auto_control), which only mh_icp_align runs (run_streaming) -- chunked by
+    // run_per_stream below, such a job records no event for its poll, which then read the state block before the device wrote it.
+    jobs[i].defer_upload = true;
     MH_TRY(jobs[i].start(sw, maps[i], scans[i], P(i), T_guesses + 12 * i, priors ? priors[i] : nullptr, &results[i],
                          nullptr, i));
   }

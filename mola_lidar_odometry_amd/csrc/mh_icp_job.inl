@@ -122,9 +122,12 @@ mh_status loop_exchange(mh_ctx* ctx, hipStream_t s, uint32_t max_steps, LoopExch
 // directly and remembered; it is captured when a LATER alignment brings it again.  (The real pipeline's ICP layer changes size
 // with every scan: capturing and instantiating a graph per alignment cost 0.4 ms each.)  `direct`: no cache (MH_NO_GRAPH=1,
 // profiled or streamed launches).
+// The plan / scan matcher launches `enqueue` issues are tallied in ctx->flat_issued: issued directly they have gone to the device and
+// are counted at once; issued under capture they are recorded beside the key and counted whenever that graph is launched.
 template <class Enqueue>
 mh_status enqueue_cached(mh_ctx* ctx, bool direct, const unsigned long long (&key)[32], Enqueue&& enqueue) {
   hipStream_t s = ctx->stream;
+  ctx->flat_issued[0] = ctx->flat_issued[1] = 0;
   const bool cached = !direct && ctx->graph_exec && memcmp(key, ctx->graph_key, sizeof(key)) == 0;
   const bool candidate = !direct && memcmp(key, ctx->graph_candidate, sizeof(key)) == 0;
   if (!cached && !(candidate && ctx->graph_candidate_align != ctx->align_serial)) {
@@ -132,7 +135,9 @@ mh_status enqueue_cached(mh_ctx* ctx, bool direct, const unsigned long long (&ke
       memcpy(ctx->graph_candidate, key, sizeof(key));
       ctx->graph_candidate_align = ctx->align_serial;
     }
-    MH_TRY(enqueue());
+    const mh_status es = enqueue();
+    for (uint32_t k = 0; k < 2; k++) count_flat_launches(k, ctx->flat_issued[k]);
+    MH_TRY(es);
     MH_HIP(hipGetLastError());
     return MH_OK;
   }
@@ -156,7 +161,9 @@ mh_status enqueue_cached(mh_ctx* ctx, bool direct, const unsigned long long (&ke
       return fail(MH_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
     }
     memcpy(ctx->graph_key, key, sizeof(key));
+    memcpy(ctx->graph_flat, ctx->flat_issued, sizeof(ctx->graph_flat));
   }
   MH_HIP(hipGraphLaunch(ctx->graph_exec, s));
+  for (uint32_t k = 0; k < 2; k++) count_flat_launches(k, ctx->graph_flat[k]);
   return MH_OK;
 }

@@ -191,6 +191,8 @@ struct mh_ctx {
   uint32_t* d_progress = nullptr;  // ... its device-visible address
   hipGraphExec_t graph_exec = nullptr;  // captured chunk of ICP iterations (replayed while graph_key matches)
   unsigned long long graph_key[32] = {0};
+  uint32_t graph_flat[2] = {0, 0};   // k_match_flat<true> / <false> launches the captured chunk holds: counted on every replay (mh_debug_flat_stats)
+  uint32_t flat_issued[2] = {0, 0};  // ... and those of the chunk being enqueued, directly or under capture (enqueue_cached takes them)
   unsigned long long graph_candidate[32] = {0};  // key of the last direct-launched chunk: captured when a LATER alignment repeats it
   unsigned long long graph_candidate_align = 0, align_serial = 0;
   uint32_t* h_small = nullptr;  // pinned, device-visible [64]: small results a kernel writes straight to the host (mh_scan_bbox)

@@ -1,6 +1,7 @@
 // mh_k_launch.h -- the __global__ entry points of the kernel bodies: one alignment per launch, or one job per blockIdx.y (*_b, the
 // lock-step batches of mh_icp_align_batch).
 #pragma once
+#include "mh_flat_off32.h"
 
 // ---- kernel entry points of the bodies above: one alignment per launch, or one job per blockIdx.y -------------------
 __global__ __launch_bounds__(kBlock, MH_QUAD_WAVES) void k_match4(const IcpDeviceState* __restrict__ st,
@@ -25,12 +26,11 @@ constexpr uint32_t kFlatPointsPerBlock = kFlatThreads; // a lane per point in ph
 __device__ __forceinline__ uint32_t nblk_flat_dev(uint32_t n) { return (n + kFlatPointsPerBlock - 1u) / kFlatPointsPerBlock; }
 // (the grid width is a multiple of 8 = the XCDs a launch is dealt over, whatever the layer's size)
 constexpr uint32_t kFlatGridUnit = 8u;
-// OFF32 (below): may the launch form its byte offsets in 32 bits (match_flat_wave)?  Every offset it forms stays inside one of these
-// allocations or below 16 bytes x the scan's points, so it is below 2^32 when they are at most that large.  Conservative: a
-// grow-only buffer that is larger than its content only sends the launch to the 64-bit instantiation.
+// OFF32 (below): may the launch form its byte offsets in 32 bits (match_flat_wave)?  The rule and the argument it rests on:
+// flat_off32_sizes, mh_flat_off32.h.  The host decides once per alignment (AlignJob::flat32) or group (LockstepGroup::off32), and
+// MH_NO_OFF32=1 sends every launch to the 64-bit instantiation.
 inline bool flat_off32(const mh_map* map, size_t n) {
-  constexpr size_t kLim = (size_t)1 << 32;
-  return map->slots.bytes <= kLim && map->pts.bytes <= kLim && map->pts_q.bytes <= kLim && n * sizeof(float4) <= kLim;
+  return mh::flat_off32_sizes(map->slots.bytes, map->pts.bytes, map->pts_q.bytes, n);
 }
 inline uint32_t nblk_flat(size_t n) { return (uint32_t)(((n + kFlatPointsPerBlock - 1) / kFlatPointsPerBlock + kFlatGridUnit - 1) / kFlatGridUnit * kFlatGridUnit); }
 template <bool OFF32>

@@ -23,6 +23,7 @@ struct Switches {
   uint32_t solo_max_callers = 4, lockstep_groups = 1;
   bool no_step_chain = false, no_fuse16 = false, no_stream = false, no_graph = false, no_lockstep = false;
   bool no_prev_bound = false, no_qidx = false, map_full_sort = false, map_no_collect = false;
+  bool no_off32 = false;  // the plan / scan matcher's 64-bit-offset instantiation whatever the sizes (flat_off32, mh_k_launch.h)
   long keep_lds = LONG_MAX;  // (clamped to 1..kKeepLds where it is used)
   bool loop16_test_abandon = false, debug_verify_batch = false;
 };
@@ -47,6 +48,7 @@ inline Switches read_switches() {
   sw.no_lockstep = on("MH_NO_LOCKSTEP");
   sw.no_prev_bound = on("MH_NO_PREV_BOUND");
   sw.no_qidx = on("MH_NO_QIDX");
+  sw.no_off32 = on("MH_NO_OFF32");
   sw.map_full_sort = on("MH_MAP_FULL_SORT");
   sw.map_no_collect = on("MH_MAP_NO_COLLECT");
   if ((e = getenv("MH_KEEP_LDS"))) sw.keep_lds = atol(e);

@@ -13,10 +13,15 @@ the unbounded iteration, the others the bounded ones.
                 oracle's poses alone and asserted;
   ties, empties voxels filled to the cap with one coordinate (the lowest scan position wins), points whose own voxel is empty, points
                 with no record in their 27-voxel block;
-  batch         nine jobs in lock step (eight dealt an XCD each, one in plain order) against single alignments and the oracle.
+  batch         1, 7, 8, 9, 16 and 17 jobs in lock step (k_match_flat_b deals whole groups of eight jobs an XCD each: 0, 0, 8, 8, 16, 16
+                of them, and keeps 1, 7, 0, 1, 0, 1 in plain order) against single alignments and the oracle;
+  graph cache   the switch below toggled under a warm graph cache: the replayed chunk is the decided instantiation's.
 
-The 64-bit-offset instantiation of the kernels takes a map or scan of 2^32 bytes or more: not reachable at test size; it is the
-kernels' earlier code, instruction for instruction (profiles/flat_trim.md)."""
+Both instantiations of the kernels run every case: the 32-bit-offset one as the sizes here select it, and the 64-bit-offset one --
+which a map buffer above 2^32 bytes or a scan above 2^28 points selects, out of reach at test size -- under MH_NO_OFF32=1.  They
+give the same bits, so a result cannot tell which of them ran: the library counts the launches of each where they are issued, a
+captured graph's on every replay (capi.flat_stats), and every device run here is held to "only the counter of the instantiation
+the switch names moved".  The rule that chooses between them, at its boundary: tests/test_flat_off32_cpu.py."""
 import functools
 
 import numpy as np
@@ -105,25 +110,57 @@ class Refs:
         self.runs = {k: oracle.icp_align(self.om, scan, T0, params(oracle, k), prior=self.prior, want_pairs=True) for k in ITS}
 
 
+FLAT, FLAT_WIDE, FLAT_B, FLAT_B_WIDE = range(4)  # capi.flat_stats(): k_match_flat<true>, <false>, k_match_flat_b<true>, <false>
+
+
+def moved(before):
+    """what the launch counters have gained since `before`"""
+    return tuple(a - b for a, b in zip(capi.flat_stats(), before))
+
+
+def only(which, count):
+    out = [0, 0, 0, 0]
+    out[which] = count
+    return tuple(out)
+
+
+def set_instantiation(monkeypatch, wide):
+    """wide: MH_NO_OFF32=1, the 64-bit-offset kernels"""
+    if wide:
+        monkeypatch.setenv("MH_NO_OFF32", "1")
+    else:
+        monkeypatch.delenv("MH_NO_OFF32", raising=False)
+
+
 def assert_case(ctx, ref, monkeypatch, gm=None):
-    """MH_MATCH=f against the oracle and against MH_MATCH=q, max_iterations 1 .. 4"""
+    """MH_MATCH=f, as it is and with MH_NO_OFF32=1, against the oracle and against MH_MATCH=q, max_iterations 1 .. 4"""
     gm = gm or capi.Map(ctx, VS, CAP).build(ref.mp)
     gs = capi.Scan(ctx, ref.scan)
     for k in ITS:
         o = ref.runs[k]
-        got = {}
-        for match in ("f", "q"):
-            monkeypatch.setenv("MH_MATCH", match)
-            got[match] = capi.icp_align(gm, gs, ref.T0, params(capi, k), prior=ref.prior, want_pairs=True)
-        f, q = got["f"], got["q"]
-        assert f["n_iterations"] == o["n_iterations"] and f["n_final_pairs"] == o["n_final_pairs"], k
-        assert [t["n_pairs"] for t in f["trace"]] == [t["n_pairs"] for t in o["trace"]], k
-        for key in ("local_idx", "global_idx", "d2"):
-            np.testing.assert_array_equal(f["pairs"][key], o["pairs"][key], err_msg="%s, max_iterations %d" % (key, k))
-            np.testing.assert_array_equal(f["pairs"][key], q["pairs"][key], err_msg="%s vs q, max_iterations %d" % (key, k))
-        np.testing.assert_allclose(f["T"], o["T"], atol=POSE_TOL, rtol=0)
-        assert np.asarray(f["T"]).tobytes() == np.asarray(q["T"]).tobytes(), k
-        assert np.asarray(f["cov"]).tobytes() == np.asarray(q["cov"]).tobytes(), k
+        set_instantiation(monkeypatch, False)
+        monkeypatch.setenv("MH_MATCH", "q")
+        c0 = capi.flat_stats()
+        q = capi.icp_align(gm, gs, ref.T0, params(capi, k), prior=ref.prior, want_pairs=True)
+        assert moved(c0) == (0, 0, 0, 0), k  # (the quad matcher is not the plan / scan matcher)
+        monkeypatch.setenv("MH_MATCH", "f")
+        for wide in (False, True):
+            set_instantiation(monkeypatch, wide)
+            c0 = capi.flat_stats()
+            f = capi.icp_align(gm, gs, ref.T0, params(capi, k), prior=ref.prior, want_pairs=True)
+            # one k_match_flat launch per enqueued iteration, all of the instantiation the switch names, none of the other or of
+            # the batch kernels -- else the comparisons below have checked the wrong kernel
+            assert f["n_enqueued_iterations"] >= max(1, f["n_iterations"]), (k, wide)
+            assert moved(c0) == only(FLAT_WIDE if wide else FLAT, f["n_enqueued_iterations"]), (k, wide)
+            assert f["n_iterations"] == o["n_iterations"] and f["n_final_pairs"] == o["n_final_pairs"], (k, wide)
+            assert [t["n_pairs"] for t in f["trace"]] == [t["n_pairs"] for t in o["trace"]], (k, wide)
+            for key in ("local_idx", "global_idx", "d2"):
+                np.testing.assert_array_equal(f["pairs"][key], o["pairs"][key], err_msg="%s, max_iterations %d, wide %d" % (key, k, wide))
+                np.testing.assert_array_equal(f["pairs"][key], q["pairs"][key], err_msg="%s vs q, max_iterations %d, wide %d" % (key, k, wide))
+            np.testing.assert_allclose(f["T"], o["T"], atol=POSE_TOL, rtol=0)
+            assert np.asarray(f["T"]).tobytes() == np.asarray(q["T"]).tobytes(), (k, wide)
+            assert np.asarray(f["cov"]).tobytes() == np.asarray(q["cov"]).tobytes(), (k, wide)
+    set_instantiation(monkeypatch, False)
     return gm
 
 
@@ -251,32 +288,122 @@ def test_ties_at_the_cap_empty_own_voxels_and_empty_blocks(ctx, oracle, monkeypa
 BATCH_SIZES = (1, 63, 64, 65, 128, 129, 1000, 64, 129)
 
 
-def test_nine_jobs_in_lock_step(ctx, oracle, length_map, monkeypatch):
-    """gridDim.y = 9: the first eight jobs are dealt an XCD each, the ninth keeps the plain order (k_match_flat_b)"""
-    mp, scan = _length_inputs()
-    om = oracle.Map(VS, CAP).insert(mp)
+BATCH_OFFSETS = (0.2, 0.02, 0.2, 0.6, 0.02, 0.2, 0.6, 0.2, 0.02)
+JOB_COUNTS = (1, 7, 8, 9, 16, 17)
+
+
+@functools.lru_cache(maxsize=None)
+def _batch_inputs():
+    """the jobs of the largest batch; a smaller one takes the first of them (sizes and guesses go round BATCH_SIZES / BATCH_OFFSETS)"""
+    _, scan = _length_inputs()
     rng = np.random.default_rng(7300)
-    subs = [np.ascontiguousarray(scan[rng.permutation(len(scan))[:n]]) for n in BATCH_SIZES]
-    guesses = [guess(off) for off in (0.2, 0.02, 0.2, 0.6, 0.02, 0.2, 0.6, 0.2, 0.02)]
-    priors = [prior_for(1)] * len(BATCH_SIZES)  # the weak prior for every job: one group (the 1000-point job's data outweigh it)
+    sizes = [BATCH_SIZES[i % len(BATCH_SIZES)] for i in range(max(JOB_COUNTS))]
+    subs = [np.ascontiguousarray(scan[rng.permutation(len(scan))[:n]]) for n in sizes]
+    return sizes, subs, [guess(BATCH_OFFSETS[i % len(BATCH_OFFSETS)]) for i in range(len(sizes))]
+
+
+_batch_refs = {}
+
+
+def batch_ref(oracle, i, k):
+    """the oracle's alignment of job i with max_iterations k: computed once, shared by every batch that holds the job"""
+    if not _batch_refs:
+        _batch_refs["map"] = oracle.Map(VS, CAP).insert(_length_inputs()[0])
+    if (i, k) not in _batch_refs:
+        _, subs, guesses = _batch_inputs()
+        _batch_refs[(i, k)] = oracle.icp_align(_batch_refs["map"], subs[i], guesses[i], params(oracle, k), prior=prior_for(1), want_pairs=True)
+    return _batch_refs[(i, k)]
+
+
+@pytest.fixture(scope="module")
+def batch_ctxs():
+    cs = [capi.Context(0) for _ in range(max(JOB_COUNTS))]
+    yield cs
+    for c in cs:
+        c.close()
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["off32", "off64"])
+@pytest.mark.parametrize("jobs", JOB_COUNTS)
+def test_jobs_in_lock_step(ctx, oracle, length_map, batch_ctxs, jobs, wide, monkeypatch):
+    """gridDim.y = jobs: k_match_flat_b deals the first 8 * floor(jobs / 8) jobs an XCD each, the others keep the plain order -- none
+    dealt (7 jobs), all dealt (8, 16), one left over (9, 17) -- in both instantiations, against single alignments and the oracle.
+
+    The launch counters: the batch call moves the counter of k_match_flat_b in the instantiation the switch names and no other, by
+    no more than max_iterations (a group never enqueues more iterations than its longest job may run) and no less than the
+    iterations its longest job ran -- with the stall test off that is max_iterations for any job that still finds pairs, so the
+    count is exact then; with two jobs or more it is below jobs x max_iterations: the jobs shared their launches.
+
+    A batch of ONE job has no lock-step group (a job alone in its group gains nothing from one: form_groups): it takes the
+    single-alignment chain, chunk by chunk, and the counter that moves is k_match_flat's.  gridDim.y = 1 does not occur.
+
+    What no result shows: WHICH jobs are dealt.  The dealing is a bijection of (block, job) for any `whole` that is a multiple of
+    eight and at most the job count, so `gridDim.y & ~15u` in place of `& ~7u` passes here (tried): it only changes which XCD's L2
+    fetches a map, which is the benchmark's to see.  A `whole` that is no multiple of eight, or exceeds the job count, reads job
+    descriptors that do not exist."""
+    sizes, subs, guesses = (v[:jobs] for v in _batch_inputs())
+    priors = [prior_for(1)] * jobs  # the weak prior for every job: one group (the 1000-point job's data outweigh it)
     monkeypatch.setenv("MH_MATCH", "f")
-    ctxs = [capi.Context(0) for _ in BATCH_SIZES]
-    scans = [capi.Scan(c, s) for c, s in zip(ctxs, subs)]
-    nbytes = sum(capi.pairs_block_bytes(n) for n in BATCH_SIZES)
+    set_instantiation(monkeypatch, wide)
+    scans = [capi.Scan(c, s) for c, s in zip(batch_ctxs, subs)]
+    nbytes = sum(capi.pairs_block_bytes(n) for n in sizes)
+    if jobs == 1:
+        want = FLAT_WIDE if wide else FLAT
+    else:
+        want = FLAT_B_WIDE if wide else FLAT_B
     for k in ITS:
+        c0 = capi.flat_stats()
         singles = [capi.icp_align(length_map, capi.Scan(ctx, s), g, params(capi, k), prior=pr, want_trace=False, want_pairs=True)
                    for s, g, pr in zip(subs, guesses, priors)]
+        assert moved(c0) == only(FLAT_WIDE if wide else FLAT, sum(a["n_enqueued_iterations"] for a in singles)), k
         block = np.zeros(nbytes, np.uint8)
-        res = capi.icp_align_batch([length_map] * len(scans), scans, guesses, params(capi, k), priors=priors, pairs_block=block)
-        ctxs[0].synchronize()
-        for s, g, pr, a, r, bp in zip(subs, guesses, priors, singles, res, capi.unpack_pairs_block(block, list(BATCH_SIZES), res)):
-            o = oracle.icp_align(om, s, g, params(oracle, k), prior=pr, want_pairs=True)
+        c0 = capi.flat_stats()
+        res = capi.icp_align_batch([length_map] * jobs, scans, guesses, params(capi, k), priors=priors, pairs_block=block)
+        batch_ctxs[0].synchronize()
+        launches = moved(c0)
+        ran = max(r["n_iterations"] for r in res)
+        assert launches == only(want, launches[want]) and max(1, ran) <= launches[want] <= k, (k, launches, ran)
+        assert jobs == 1 or launches[want] < jobs * k, (k, launches)
+        for i, (a, r, bp) in enumerate(zip(singles, res, capi.unpack_pairs_block(block, list(sizes), res))):
+            o = batch_ref(oracle, i, k)
             assert (r["n_iterations"], r["n_final_pairs"]) == (a["n_iterations"], a["n_final_pairs"]) == (o["n_iterations"], o["n_final_pairs"])
             assert np.array_equal(r["T"], a["T"]) and np.array_equal(r["cov"], a["cov"])
             np.testing.assert_allclose(r["T"], o["T"], atol=POSE_TOL, rtol=0)
             for key in ("local_idx", "global_idx", "d2"):
                 assert np.array_equal(bp[key], a["pairs"][key]), (k, key)
                 assert np.array_equal(bp[key], o["pairs"][key]), (k, key)
-    for c in ctxs:
-        c.close()
+
+
+# ------------------------------------------------------------------------------------------------------------ graph cache
+def test_the_switch_toggled_under_a_warm_graph_cache(ctx, length_map, monkeypatch):
+    """One context, one map, one 1000-point scan, graphs on.  A chunk's launch sequence is captured when a later alignment brings
+    its key again and replayed from then on: of three alignments without the switch the second captures and the third replays.
+    Then two with MH_NO_OFF32=1 and two without: the instantiation is a word of the graph key, so the first of each pair misses the
+    cache and launches directly, the second captures anew.  All seven results are the same bytes, and in every alignment the
+    counters move on the side the switch names only -- a replayed graph counts what it holds -- by exactly max_iterations (with
+    poll_every = max_iterations an alignment is ONE chunk of that many iterations, launched directly or as one graph)."""
+    _, scan = _length_inputs()
+    gs = capi.Scan(ctx, scan[:1000])
+    n_it = 4
+    p = capi.ICPParams(max_iterations=n_it, threshold=THRESHOLD, kernel_param=KERNEL_PARAM, disable_stall_test=True, poll_every=n_it)
+    monkeypatch.setenv("MH_MATCH", "f")
+    for var in ("MH_NO_GRAPH", "MH_NO_STREAM"):
+        monkeypatch.delenv(var, raising=False)
+    runs = []
+    for phase, (wide, repeats) in enumerate([(False, 3), (True, 2), (False, 2)]):
+        set_instantiation(monkeypatch, wide)
+        for rep in range(repeats):
+            c0 = capi.flat_stats()
+            r = capi.icp_align(length_map, gs, guess(0.2), p, want_trace=False, want_pairs=True)
+            assert moved(c0) == only(FLAT_WIDE if wide else FLAT, n_it), (phase, rep, wide)
+            assert (r["n_iterations"], r["n_enqueued_iterations"], r["n_host_polls"]) == (n_it, n_it, 1), (phase, rep)
+            runs.append(r)
+    first = runs[0]
+    assert first["n_final_pairs"] > 900
+    for r in runs[1:]:
+        assert np.asarray(r["T"]).tobytes() == np.asarray(first["T"]).tobytes()
+        assert np.asarray(r["cov"]).tobytes() == np.asarray(first["cov"]).tobytes()
+        assert r["n_final_pairs"] == first["n_final_pairs"]
+        for key in ("local_idx", "global_idx", "d2", "global_xyz"):
+            assert r["pairs"][key].tobytes() == first["pairs"][key].tobytes(), key
 

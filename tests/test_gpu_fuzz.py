@@ -24,7 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
                                              ("fuzz_chains.py", 30, 111)])
 def test_randomized_parity_tool(tool, cases, seed):
     env = dict(os.environ)
-    for k in ("MH_MATCH", "MH_NO_PREV_BOUND", "MH_NO_FUSE16", "MH_NO_STEP_CHAIN", "MH_NO_LOCKSTEP", "MH_NO_GRAPH", "MH_NO_QIDX"):
+    for k in ("MH_MATCH", "MH_NO_PREV_BOUND", "MH_NO_FUSE16", "MH_NO_STEP_CHAIN", "MH_NO_LOCKSTEP", "MH_NO_GRAPH", "MH_NO_QIDX",
+              "MH_NO_OFF32"):
         env.pop(k, None)  # (the tools choose their own switches)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", tool), str(cases), str(seed)], capture_output=True, text=True,
                        timeout=500, env=env, cwd=ROOT)

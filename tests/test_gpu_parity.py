@@ -694,6 +694,29 @@ def test_align_batch_equals_single(ctx, oracle, small):
             np.testing.assert_array_equal(b["cov"], s["cov"])
 
 
+@pytest.mark.parametrize("match", [None, "s", "q", "f"])
+@pytest.mark.parametrize("poll", [0, 3])
+def test_align_batch_of_one_job_equals_single(ctx, small, match, poll, monkeypatch):
+    """A batch of ONE job has no lock-step group and nobody runs the streaming control for it: it is chunked on its own stream like
+    a job left alone in a larger batch.  (With automatic polling it used to be planned for streaming all the same and its poll read
+    the state block before the device had written it: MH_ERR_INTERNAL, "did not terminate after max_iterations".)  Stall-terminated
+    and run to the iteration limit, every matcher of a chain that can be forced on the small workload: the single alignment's bits."""
+    w, gm, om, gs = small
+    if match:
+        monkeypatch.setenv("MH_MATCH", match)
+    c2 = capi.Context(0)
+    s2 = capi.Scan(c2, w.scan_xyz)
+    for p in (_params(capi, w, 300, poll_every=poll), _params(capi, w, 5, poll_every=poll, disable_stall_test=True)):
+        single = capi.icp_align(gm, gs, w.T_guess, p, want_trace=False)
+        for _ in range(2):  # (the second call finds what the first left in the context: predicted chunk, graph cache)
+            b = capi.icp_align_batch([gm], [s2], [w.T_guess], p)[0]
+            assert (b["n_iterations"], b["termination_reason"], b["n_final_pairs"]) == \
+                   (single["n_iterations"], single["termination_reason"], single["n_final_pairs"])
+            np.testing.assert_array_equal(b["T"], single["T"])
+            np.testing.assert_array_equal(b["cov"], single["cov"])
+    c2.close()
+
+
 @pytest.mark.parametrize("inner,ndt", [(1, False), (2, False), (2, True)])
 def test_small_layer_batches_give_the_bits_of_single_alignments(ctx, inner, ndt):
     """Layers of up to 8 k points run k_step16 -- search + sums per launch, the Gauss-Newton step carried into the next launch
@@ -1186,7 +1209,11 @@ def test_profile_fields(ctx, small):
                                  {"MH_MATCH": "p"}, {"MH_MATCH": "x"}, {"MH_MATCH": "q", "MH_NO_GRAPH": "1"},
                                  # (env7 .. env12 were the tile / wave / sorted-scan matchers; the two below keep their ids)
                                  pytest.param({"MH_MATCH": "f"}, id="env13"),
-                                 pytest.param({"MH_MATCH": "f", "MH_NO_GRAPH": "1"}, id="env14")])
+                                 pytest.param({"MH_MATCH": "f", "MH_NO_GRAPH": "1"}, id="env14"),
+                                 # (the plan / scan matcher's 64-bit-offset kernels; that they are what runs under the switch:
+                                 #  tests/test_gpu_flat_trim.py, by the launch counters)
+                                 pytest.param({"MH_MATCH": "f", "MH_NO_OFF32": "1"}, id="env15"),
+                                 pytest.param({"MH_MATCH": "f", "MH_NO_OFF32": "1", "MH_NO_GRAPH": "1"}, id="env16")])
 @pytest.mark.parametrize("n_scan", [2000, 5000])
 def test_every_kernel_variant_matches_the_oracle(ctx, oracle, env, n_scan, monkeypatch):
     """The default path picks its kernels by layer size (row / quad search, one-workgroup or multi-launch solve);
