@@ -29,6 +29,7 @@
 // Host code here is control logic only; every point touches the GPU through include/molahip.h.  What is NOT here:
 // MOLA module plumbing, IMU/GNSS/wheel inputs, MRPT .simplemap serialisation, visualisation, ROS.
 #pragma once
+#include <functional>
 #include <map>
 #include <memory>
 #include <optional>
@@ -51,6 +52,8 @@ using mp2p_icp_hip::ICP;
 using mp2p_icp_hip::Parameterizable;
 using mp2p_icp_hip::ParameterSource;
 using mp2p_icp_hip::TPose3D;
+
+class OnlineLoopCloser;  // LoopClosure.h
 
 struct Twist {
   double vx = 0, vy = 0, vz = 0, wx = 0, wy = 0, wz = 0;  // vehicle frame, the frame FilterDeskew integrates in
@@ -84,6 +87,9 @@ class NavStateFuse {
   // cov: 6x6 row-major covariance of `pose` in (x,y,z,yaw,pitch,roll) (Results::optimal_tf.cov), or null = exact
   void fuse_pose(double t, const CPose3D& pose, const double* cov = nullptr);
   std::optional<NavState> estimated_navstate(double t) const;
+  // a correction of the map frame (a loop closure): the last fused pose becomes delta (+) pose.  The twist is in the vehicle frame
+  // and stays, as do the covariance and the times.
+  void rebase(const CPose3D& delta);
 
  private:
   std::optional<CPose3D> last_pose_;
@@ -129,6 +135,9 @@ class KeyFrameStore {
   // the frames (and the target maps they name); reset(): forget the checker and start from `initial` (a loaded file's content)
   const molahip_host::KeyFrameSet& set() const { return set_; }
   void setTargets(std::vector<molahip_host::KeyFrameTarget> maps) { set_.maps = std::move(maps); }
+  // other poses for the stored frames (12 values each, one per frame: a loop closure's correction); the distance checker is
+  // rebuilt from the new poses of the frames that had entered it
+  void setPoses(const std::vector<double>& poses);
   void reset(const molahip_host::KeyFrameSet& initial = {});
   bool measureFromLastOnly() const { return last_only_; }
 
@@ -136,8 +145,15 @@ class KeyFrameStore {
   bool last_only_;
   SearchablePoseList all_;
   std::optional<CPose3D> last_;
+  std::vector<size_t> in_checker_;  // the frames whose poses entered the checker (decide() names the frame the next add() appends)
   molahip_host::KeyFrameSet set_;
 };
+
+// The key-frame layers that build target map `map_index` of a set, in frame order then step order, at the frames' poses; `keep`
+// (optional) restricts the frames.  What build_session_maps() hands to insertFrames, and the driver when a loop closure rebuilds its
+// local maps around the vehicle.  The pointers are into `set`.
+std::vector<mp2p_icp_hip::PosedFrame> session_map_frames(const molahip_host::KeyFrameSet& set, size_t map_index,
+                                                         const std::function<bool(const molahip_host::KeyFrame&)>& keep = nullptr);
 
 // The maps of the whole drive from its key-frames: for every target map of the header a new map of the recorded class and
 // parameters (mp2p_icp_hip::make_local_map), then ONE insertFrames of that map's layers in frame order, then step order;
@@ -151,6 +167,13 @@ std::vector<molahip_host::LocalMapRecord> build_session_maps(const std::string& 
 // ... written as a version-1 local-map file (write_local_map_file): what load_existing_local_map loads
 void build_session_map_file(const molahip_host::KeyFrameSet& frames, const std::string& local_map_file, std::shared_ptr<DeviceContext> ctx = nullptr,
                             uint64_t max_points_per_pass = 0);
+
+// The pose rules of online_loop_closure: (LidarOdometry below), host logic only.  P: a scan's pose; S: the pose the key-frame store
+// holds for a stored frame at that time; C: a frame's corrected pose.
+CPose3D loop_raw_pose(const CPose3D& raw_prev, const CPose3D& P, const CPose3D& S_prev);  // raw_k = raw_{k-1} (+) (P_k (-) S_{k-1}); P_k itself while S_{k-1} == raw_{k-1}
+CPose3D loop_correction(const CPose3D& C, const CPose3D& P);                              // delta = C (+) P^-1: delta (+) P = C
+CPose3D trajectory_anchor(const CPose3D& P, const CPose3D& S);                            // rel = P (-) S
+CPose3D trajectory_corrected(const CPose3D& C, const CPose3D& rel);                       // C (+) rel
 
 // The grouping rule of a multi-LiDAR rig (LidarOdometry.cpp:664-689, 702-713), host logic only: the latest observation of
 // every label waits until `lidar_count` labels are present; the group is then the waiting observations within
@@ -338,6 +361,19 @@ class LidarOdometry {
     std::vector<uint32_t> place_frames, place_shifts, place_dists;
     // params.simplemap.generate: this scan is stored in the key-frame store (simplemap_frame), with its points (simplemap_keyframe)
     bool simplemap_keyframe = false, simplemap_frame = false;
+    // online_loop_closure: this scan's stored frame went to the loop closer, which verified loop_pairs = (i, j, quality, accepted)
+    // for it (loop_tried) and accepted one (loop_closed).  With correct_driver the closure moved the map frame by delta: `pose` is
+    // the corrected one, loop_correction_trans [m] / loop_correction_rot [rad] are delta's norms and loop_rebuilt_frames the
+    // key-frames the local maps were rebuilt from.
+    bool loop_tried = false, loop_closed = false;
+    struct LoopPairRecord {
+      uint32_t i = 0, j = 0;
+      double quality = 0;
+      bool accepted = false;
+    };
+    std::vector<LoopPairRecord> loop_pairs;
+    double loop_correction_trans = 0, loop_correction_rot = 0;
+    uint32_t loop_rebuilt_frames = 0;
   };
 
   // ctx == nullptr: the process-wide default device context, taken at initialize()
@@ -405,6 +441,23 @@ class LidarOdometry {
   const std::vector<std::pair<double, CPose3D>>& estimatedTrajectory() const { return trajectory_; }
   // TUM format "t x y z qx qy qz qw" (estimated_trajectory.output_file, yaml:79-81; eval/cli_kitti.sh:41-50)
   void saveTrajectoryTUM(const std::string& path) const;
+  // The trajectory as the loop closures so far correct it: every entry hangs on the last stored key-frame at or before it by the
+  // relative pose it had when it was made, and follows that frame's corrected pose (entries before the first stored frame stay).
+  // estimatedTrajectory() bit for bit while no loop has been closed; estimatedTrajectory() itself keeps what was estimated at the time.
+  std::vector<std::pair<double, CPose3D>> correctedTrajectory() const;
+  void saveCorrectedTrajectoryTUM(const std::string& path) const;
+  // online_loop_closure: (LoopClosure.h) -- enabled: every stored key-frame goes to an OnlineLoopCloser with its RAW pose, raw_k =
+  // raw_{k-1} (+) (P_k (-) S_{k-1}): P_k the scan's pose, S_{k-1} the pose the store holds for the previous frame at that time; a
+  // load_existing_simple_map file's frames go first with their file poses.  With correct_driver an accepted closure is fed back
+  // inside the same onLidar* call, after the scan's own map update: the store's poses become the corrected ones, the last pose and
+  // the motion model move by delta = C_i (+) P_i^-1, and every local map is cleared and rebuilt by one insertFrames from the stored
+  // key-frames within its recorded remove_voxels_farther_than of the vehicle (0: all).  initialize() demands simplemap.generate and
+  // refuses a CVoxelMap plan and an ICP block close_loops() would refuse; setAlignBatcher() throws.
+  // loopCloser(): null when disabled or before the first stored frame; it reads the layers of this object's key-frame store (no second
+  // copy of the session's points), so it is to be used while this object lives.  rawKeyFrames(): the set on which close_loops()
+  // reproduces the run.
+  std::shared_ptr<const OnlineLoopCloser> loopCloser() const { return loop_closer_; }
+  molahip_host::KeyFrameSet rawKeyFrames() const;
   const Params& params() const { return params_; }
   const InitialLocalization& initialLocalization() const { return init_loc_; }
   const RelocalizationOptions& relocalizationOptions() const { return reloc_opts_; }
@@ -523,6 +576,8 @@ class LidarOdometry {
   void check_loaded_keyframe_targets(const std::vector<molahip_host::KeyFrameTarget>& plan) const;  // throws on another class or mh_map_params
   void resolve_map_counts() const;  // fills n_map_points / n_map_voxels of the records that still wait for them
   bool map_is_empty();              // local_map_->empty() without a device round trip once the map is known to hold points
+  void feed_loop_closer(ScanRecord& rec);                        // online_loop_closure: the stored frames not pushed yet; feedback
+  void apply_loop_correction(ScanRecord& rec, const CPose3D& stored_pose_before);  // ... pose, motion model, local maps
 
   std::shared_ptr<DeviceContext> ctx_;
   Params params_;
@@ -590,6 +645,16 @@ class LidarOdometry {
   std::optional<RelocRequest> reloc_request_;
   std::unique_ptr<PlaceIndex> place_index_;  // relocalizeInKeyFrames: built at the first serving scan
   size_t place_frames_seen_ = 0;             // ... and how many frames of the key-frame store it has looked at
+  // online_loop_closure:
+  bool loop_enabled_ = false, loop_correct_ = true;
+  Config loop_cfg_;                               // the pipeline file, for the closer (made when the target maps are known)
+  std::shared_ptr<OnlineLoopCloser> loop_closer_;
+  size_t loop_pushed_ = 0;                        // frames of the key-frame store the closer has
+  struct TrajectoryAnchor {
+    long frame = -1;  // the last stored frame at or before the entry (-1: none yet)
+    CPose3D rel;      // the entry's pose in that frame, when it was made
+  };
+  std::vector<TrajectoryAnchor> trajectory_anchor_;  // one per trajectory_ entry (kept while enabled)
   bool input_pinned_ = false;
   bool intensity_input_ = false;  // setIntensityInput
   std::map<std::string, double> profile_;

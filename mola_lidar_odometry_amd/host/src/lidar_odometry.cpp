@@ -1,6 +1,7 @@
 // lidar_odometry.cpp -- see mola_lidar_odometry_hip/LidarOdometry.h.  Control logic only: the arithmetic on points
 // is behind include/molahip.h.  Citations are module/src/LidarOdometry.cpp unless another file is named.
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
+#include "mola_lidar_odometry_hip/LoopClosure.h"
 #include "molahip_host/plugin_switches.h"
 
 #include <algorithm>
@@ -96,6 +97,10 @@ void NavStateFuse::fuse_pose(double t, const CPose3D& pose, const double* cov) {
   last_pose_ = pose;
   for (int i = 0; i < 36; i++) last_cov_[i] = cov ? cov[i] : ((i % 7 == 0) ? 1e-12 : 0.0);  // (:834-836: "cannot be zero")
   last_t_ = t;
+}
+
+void NavStateFuse::rebase(const CPose3D& delta) {
+  if (last_pose_) last_pose_ = delta + *last_pose_;
 }
 
 namespace {
@@ -205,6 +210,7 @@ KeyFrameStore::Verdict KeyFrameStore::decide(bool first_scan, bool icp_good, con
   if (enough) {
     if (last_only_) last_ = pose;
     else all_.insert(pose);
+    in_checker_.push_back(set_.frames.size());
   }
   return v;
 }
@@ -212,7 +218,40 @@ KeyFrameStore::Verdict KeyFrameStore::decide(bool first_scan, bool icp_good, con
 void KeyFrameStore::reset(const molahip_host::KeyFrameSet& initial) {
   all_.clear();
   last_.reset();
+  in_checker_.clear();
   set_ = initial;
+}
+
+void KeyFrameStore::setPoses(const std::vector<double>& poses) {
+  if (poses.size() != 12 * set_.frames.size())
+    throw std::runtime_error("KeyFrameStore::setPoses: " + std::to_string(poses.size()) + " values for " + std::to_string(set_.frames.size()) + " frames");
+  for (size_t k = 0; k < set_.frames.size(); k++) std::copy(&poses[12 * k], &poses[12 * k] + 12, set_.frames[k].pose);
+  all_.clear();
+  last_.reset();
+  for (size_t k : in_checker_) {
+    if (k >= set_.frames.size()) continue;
+    CPose3D p;
+    std::copy(set_.frames[k].pose, set_.frames[k].pose + 12, p.T);
+    if (last_only_) last_ = p;
+    else all_.insert(p);
+  }
+}
+
+std::vector<mp2p_icp_hip::PosedFrame> session_map_frames(const molahip_host::KeyFrameSet& set, size_t map_index,
+                                                         const std::function<bool(const molahip_host::KeyFrame&)>& keep) {
+  std::vector<mp2p_icp_hip::PosedFrame> frames;
+  for (const auto& f : set.frames) {
+    if (!f.has_points || (keep && !keep(f))) continue;
+    for (const auto& l : f.layers) {  // frame order, then step order
+      if (l.map_index != map_index) continue;
+      mp2p_icp_hip::PosedFrame pf;
+      pf.x = l.x.data(); pf.y = l.y.data(); pf.z = l.z.data();
+      pf.n = l.x.size();
+      std::copy(f.pose, f.pose + 12, pf.pose.T);
+      frames.push_back(pf);
+    }
+  }
+  return frames;
 }
 
 std::vector<molahip_host::LocalMapRecord> build_session_maps(const molahip_host::KeyFrameSet& set, std::shared_ptr<DeviceContext> ctx,
@@ -235,19 +274,7 @@ std::vector<molahip_host::LocalMapRecord> build_session_maps(const molahip_host:
     empty.params = t.params;
     empty.remove_voxels_farther_than = t.remove_voxels_farther_than;
     auto map = mp2p_icp_hip::make_local_map(empty, ctx);
-    std::vector<mp2p_icp_hip::PosedFrame> frames;
-    for (const auto& f : set.frames) {
-      if (!f.has_points) continue;
-      for (const auto& l : f.layers) {  // frame order, then step order
-        if (l.map_index != k) continue;
-        mp2p_icp_hip::PosedFrame pf;
-        pf.x = l.x.data(); pf.y = l.y.data(); pf.z = l.z.data();
-        pf.n = l.x.size();
-        std::copy(f.pose, f.pose + 12, pf.pose.T);
-        frames.push_back(pf);
-      }
-    }
-    map->insertFrames(frames, max_points_per_pass);
+    map->insertFrames(session_map_frames(set, k), max_points_per_pass);
     out.push_back(map->snapshot(t.name, t.remove_voxels_farther_than));
   }
   return out;
@@ -1012,6 +1039,38 @@ void LidarOdometry::initialize(const Config& cfg) {
                                params_.simplemap.load_existing_simple_map + "' was recorded for other target maps than this pipeline's");
   }
 
+  // online_loop_closure: (LoopClosure.h): read and checked whether enabled or not
+  {
+    const OnlineLoopClosureOptions ol = OnlineLoopClosureOptions::FromConfig(cfg);
+    loop_enabled_ = ol.enabled;
+    loop_correct_ = ol.correct_driver;
+    loop_cfg_ = Config();
+    if (loop_enabled_) {
+      (void)LoopClosureOptions::FromConfig(cfg);  // (the closer's gates and weights: out of range is refused here, not at the first key-frame)
+      if (!params_.simplemap.generate)
+        throw std::runtime_error("LidarOdometry (HIP): online_loop_closure: enabled needs params.simplemap.generate: true: the loop closer "
+                                 "works on the key-frame store");
+      std::vector<std::string> names;
+      auto refuse_occupancy = [](const std::string& name, const Config& def) {
+        if (ends_with(def["class"].asString(), "CVoxelMap"))
+          throw std::runtime_error("LidarOdometry (HIP): online_loop_closure: local map '" + name + "' is a 'CVoxelMap': an occupancy map cannot be "
+                                   "built from key-frames, so no submap to verify a loop in and no map to rebuild after one (HashedVoxelPointCloud, "
+                                   "NDT and SparseTreesPointCloud can)");
+      };
+      if (gplan_) {
+        for (const auto& m : gplan_->maps) {
+          refuse_occupancy(m.name, m.def);
+          names.push_back(m.name);
+        }
+      } else {
+        refuse_occupancy(plan_->map_layer, map_def_);
+        names.push_back(plan_->map_layer);
+      }
+      check_loop_closure_icp(*icp_[1], names, "LidarOdometry (HIP): online_loop_closure");
+      loop_cfg_ = cfg;
+    }
+  }
+
   reset();  // device objects are created at the first scan: a pipeline can be loaded and checked without a GPU (a saved map
             // is restored here, which needs one)
 }
@@ -1524,6 +1583,9 @@ void LidarOdometry::reset() {
   kf_store_.reset(loaded_keyframes_);  // (likewise: the store starts from the loaded file's frames again)
   place_index_.reset();                // (... and the place index follows it from its first frame)
   place_frames_seen_ = 0;
+  loop_closer_.reset();  // (made again, and fed the loaded frames again, once the target maps are known)
+  loop_pushed_ = 0;
+  trajectory_anchor_.clear();
   kf_targets_known_ = false;  // (a loaded header is held against the plan's maps once they exist: check_loaded_keyframe_targets)
   if (!loaded_maps_.empty()) restore_loaded_maps();  // (the reference's reset() runs initialize() again: the file is loaded again)
 }
@@ -1686,6 +1748,9 @@ void LidarOdometry::setAlignBatcher(std::shared_ptr<mp2p_icp_hip::AlignBatcher> 
   // process-wide default one would be shared between threads (molahip.h: one context, one thread at a time)
   // (general plans too: their ICP joins through whichever route it takes -- mp2p_icp_hip::ICP::align; their filter steps and
   // their next scan's upload are not announced to the batcher, launch_prefetch() is the default plan's)
+  if (b && loop_enabled_)
+    throw std::runtime_error("LidarOdometry::setAlignBatcher: not available with online_loop_closure: enabled (the batch protocol of an "
+                             "AlignBatcher has no slot for the extra alignments that verify a loop)");
   if (b && (!ctx_ || ctx_ == DeviceContext::Default()))
     throw std::runtime_error("LidarOdometry::setAlignBatcher: this instance uses the process-wide default context; construct "
                              "it with a DeviceContext of its own");
@@ -2322,6 +2387,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     map_known_nonempty_ = false;
     map_points_cached_ = map_voxels_cached_ = 0;
     trajectory_.clear();
+    trajectory_anchor_.clear();
     updateLocalMap = false;
     last_icp_was_good_ = true;
     rec.restarted = true;
@@ -2362,6 +2428,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     else check_loaded_keyframe_targets(targets);  // (the file's header stays; the new frames must have been recorded for it)
     kf_targets_known_ = true;
   }
+  if (loop_enabled_) feed_loop_closer(rec);
   rec.pose = last_lidar_pose_;
   rec.sigma = adapt_thres_sigma_;
   rec.map_voxel_size = map_voxel_size_;
@@ -2370,6 +2437,133 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     rec.n_map_voxels = map_voxels_cached_;
   }
   return rec;
+}
+
+// ---- online_loop_closure: (LidarOdometry.h, LoopClosure.h)
+CPose3D loop_raw_pose(const CPose3D& raw_prev, const CPose3D& P, const CPose3D& S_prev) {
+  if (std::memcmp(raw_prev.T, S_prev.T, sizeof(raw_prev.T)) == 0) return P;  // nothing corrected yet: the raw chain IS the estimated one, bit for bit
+  return raw_prev + (P - S_prev);
+}
+CPose3D loop_correction(const CPose3D& C, const CPose3D& P) { return C + (CPose3D() - P); }
+CPose3D trajectory_anchor(const CPose3D& P, const CPose3D& S) { return P - S; }
+CPose3D trajectory_corrected(const CPose3D& C, const CPose3D& rel) { return C + rel; }
+
+void LidarOdometry::feed_loop_closer(ScanRecord& rec) {
+  // every trajectory entry hangs on the last stored frame at or before it (this scan's own frame, when it was stored)
+  const auto& stored = kf_store_.set().frames;
+  while (trajectory_anchor_.size() < trajectory_.size()) {
+    TrajectoryAnchor a;
+    if (!stored.empty()) {
+      a.frame = (long)stored.size() - 1;
+      CPose3D S;
+      std::copy(stored.back().pose, stored.back().pose + 12, S.T);
+      a.rel = trajectory_anchor(trajectory_[trajectory_anchor_.size()].second, S);
+    }
+    trajectory_anchor_.push_back(a);
+  }
+  if (!kf_targets_known_ || loop_pushed_ >= stored.size()) return;
+  StageTimer tt(profile_, "onLidar.6.loop_closure");
+  if (!loop_closer_) {
+    loop_closer_ = std::make_shared<OnlineLoopCloser>(kf_store_.set().maps, loop_cfg_, ctx_);
+    loop_closer_->readFramesFrom(&stored);  // (the store's own layers: no second copy of the session's points)
+  }
+  bool closed = false;
+  const size_t n_loaded = loaded_keyframes_.frames.size();
+  for (; loop_pushed_ < stored.size(); loop_pushed_++) {
+    const size_t k = loop_pushed_;
+    CPose3D raw;  // raw_k = raw_{k-1} (+) (P_k (-) S_{k-1}); frame 0 and a loaded file's frames: their poses as they are
+    std::copy(stored[k].pose, stored[k].pose + 12, raw.T);
+    if (k > 0 && k >= n_loaded) {
+      CPose3D S, R;
+      std::copy(stored[k - 1].pose, stored[k - 1].pose + 12, S.T);
+      std::copy(&loop_closer_->rawPoses()[12 * (k - 1)], &loop_closer_->rawPoses()[12 * (k - 1)] + 12, R.T);
+      raw = loop_raw_pose(R, raw, S);
+    }
+    const OnlineLoopCloser::Step st = loop_closer_->pushStored(k, raw.T);
+    const bool own = k + 1 == stored.size() && rec.simplemap_frame;  // this scan's frame
+    if (own) {
+      rec.loop_tried = st.tried;
+      rec.loop_closed = st.closed;
+      for (const auto& p : st.pairs) rec.loop_pairs.push_back(ScanRecord::LoopPairRecord{p.i, p.j, p.quality, p.accepted});
+    }
+    closed = closed || st.closed;
+  }
+  if (!loop_correct_ || loop_closer_->loops().empty()) return;
+  // the store follows the closer: close_loops(rawKeyFrames()) gives keyFrames()' poses at any time
+  CPose3D before;
+  std::copy(stored.back().pose, stored.back().pose + 12, before.T);
+  kf_store_.setPoses(loop_closer_->correctedPoses());
+  if (closed) apply_loop_correction(rec, before);
+}
+
+void LidarOdometry::apply_loop_correction(ScanRecord& rec, const CPose3D& stored_pose_before) {
+  StageTimer tt(profile_, "onLidar.6.loop_correction");  // (inside onLidar.6.loop_closure)
+  const auto& set = kf_store_.set();
+  CPose3D C;
+  std::copy(set.frames.back().pose, set.frames.back().pose + 12, C.T);
+  // ---- pose and motion model: delta = C_i (+) P_i^-1 moves the map frame
+  CPose3D delta;
+  if (rec.simplemap_frame) {  // the last stored frame is this scan's: its corrected pose is the vehicle's, bit for bit
+    delta = loop_correction(C, last_lidar_pose_);
+    last_lidar_pose_ = C;
+  } else {  // (a closure among the frames of a loaded file, found at a scan that was not stored itself)
+    delta = loop_correction(C, stored_pose_before);
+    last_lidar_pose_ = delta + last_lidar_pose_;
+  }
+  navstate_.rebase(delta);
+  if (last_motion_model_output_) last_motion_model_output_->pose.mean = delta + last_motion_model_output_->pose.mean;
+  rec.loop_correction_trans = delta.translationNorm();
+  rec.loop_correction_rot = delta.rotationAngle();
+  // ---- local maps: cleared and rebuilt from the stored key-frames around the vehicle, one insertFrames per map
+  resolve_map_counts();  // (earlier records keep the counts of the map they saw)
+  auto rebuild = [&](HashedVoxelPointCloud& map, size_t k, bool first) {
+    const double far = k < set.maps.size() ? (double)set.maps[k].remove_voxels_farther_than : 0.0;
+    auto near = [&](const molahip_host::KeyFrame& f) {
+      if (!(far > 0.0)) return true;
+      const double dx = f.pose[3] - last_lidar_pose_.T[3], dy = f.pose[7] - last_lidar_pose_.T[7], dz = f.pose[11] - last_lidar_pose_.T[11];
+      return std::sqrt(dx * dx + dy * dy + dz * dz) <= far;
+    };
+    map.clear();
+    map.insertFrames(session_map_frames(set, k, near), 0);
+    if (!first) return;
+    // the local-map key-frame list becomes the poses of exactly the frames the first map was rebuilt from
+    distance_checker_local_map_.clear();
+    for (const auto& f : set.frames) {
+      if (!f.has_points || !near(f)) continue;
+      CPose3D p;
+      std::copy(f.pose, f.pose + 12, p.T);
+      distance_checker_local_map_.insert(p);
+      rec.loop_rebuilt_frames++;
+    }
+  };
+  if (gplan_) {
+    for (size_t k = 0; k < gplan_->maps.size(); k++)
+      if (gplan_->maps[k].map) rebuild(*gplan_->maps[k].map, k, k == 0);
+  } else if (local_map_) {
+    rebuild(*local_map_, 0, true);
+  }
+  map_known_nonempty_ = false;  // (ask the device)
+  map_counts_pending_ = true;
+  map_counts_from_ = records_.size() - 1;
+}
+
+molahip_host::KeyFrameSet LidarOdometry::rawKeyFrames() const {
+  if (loop_closer_) return loop_closer_->rawKeyFrames();
+  return molahip_host::KeyFrameSet();
+}
+
+std::vector<std::pair<double, CPose3D>> LidarOdometry::correctedTrajectory() const {
+  std::vector<std::pair<double, CPose3D>> out = trajectory_;
+  if (!loop_closer_ || loop_closer_->loops().empty()) return out;
+  const std::vector<double>& C = loop_closer_->correctedPoses();
+  for (size_t n = 0; n < out.size() && n < trajectory_anchor_.size(); n++) {
+    const TrajectoryAnchor& a = trajectory_anchor_[n];
+    if (a.frame < 0 || 12 * ((size_t)a.frame + 1) > C.size()) continue;
+    CPose3D Ca;
+    std::copy(&C[12 * (size_t)a.frame], &C[12 * (size_t)a.frame] + 12, Ca.T);
+    out[n].second = trajectory_corrected(Ca, a.rel);
+  }
+  return out;
 }
 
 std::map<std::string, uint64_t> LidarOdometry::localMapSizes() const {
@@ -2538,10 +2732,10 @@ std::map<std::string, std::string> LidarOdometry::describePipeline() const {
   return d;
 }
 
-void LidarOdometry::saveTrajectoryTUM(const std::string& path) const {
+static void write_tum(const std::string& path, const std::vector<std::pair<double, CPose3D>>& trajectory) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) throw std::runtime_error("cannot write " + path);
-  for (const auto& [t, p] : trajectory_) {
+  for (const auto& [t, p] : trajectory) {
     // rotation matrix -> unit quaternion (w >= 0)
     const double* T = p.T;
     const double tr = T[0] + T[5] + T[10];
@@ -2564,5 +2758,8 @@ void LidarOdometry::saveTrajectoryTUM(const std::string& path) const {
   }
   fclose(f);
 }
+
+void LidarOdometry::saveTrajectoryTUM(const std::string& path) const { write_tum(path, trajectory_); }
+void LidarOdometry::saveCorrectedTrajectoryTUM(const std::string& path) const { write_tum(path, correctedTrajectory()); }
 
 }  // namespace mola_hip

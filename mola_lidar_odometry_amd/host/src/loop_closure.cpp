@@ -21,7 +21,7 @@ struct Stage {  // adds the wall time of its scope to a report entry, and one to
   std::map<std::string, double>& sec;
   const char* name;
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  Stage(LoopReport& r, const char* n) : sec(r.seconds), name(n) { r.counts[n] += 1.0; }
+  Stage(LoopReport& r, const char* n, bool count = true) : sec(r.seconds), name(n) { if (count) r.counts[n] += 1.0; }
   ~Stage() { sec[name] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
@@ -97,48 +97,80 @@ void LoopClosureOptions::validate() const {
   not_negative("min_step", min_step);
 }
 
+OnlineLoopClosureOptions OnlineLoopClosureOptions::FromConfig(const Config& cfg) {
+  OnlineLoopClosureOptions o;
+  if (cfg.has("online_loop_closure") && !cfg["online_loop_closure"].isNull()) {
+    const Config& c = cfg["online_loop_closure"];
+    auto flag = [&](const char* k, bool& v) {
+      if (!c.has(k) || c[k].isNull()) return;
+      const std::string s = c[k].asString();
+      if (s == "true" || s == "True" || s == "1" || s == "yes") v = true;
+      else if (s == "false" || s == "False" || s == "0" || s == "no") v = false;
+      else throw std::runtime_error(std::string("online_loop_closure: ") + k + " must be true or false");
+    };
+    flag("enabled", o.enabled);
+    flag("correct_driver", o.correct_driver);
+    if (c.has("check_every_n_keyframes") && !c["check_every_n_keyframes"].isNull()) {
+      const double d = strtod(c["check_every_n_keyframes"].asString().c_str(), nullptr);
+      if (!(d >= 1.0) || !(d <= 4294967295.0) || d != std::floor(d))
+        throw std::runtime_error("online_loop_closure: check_every_n_keyframes must be an integer >= 1");
+      o.check_every_n_keyframes = (uint32_t)d;
+    }
+  }
+  o.validate();
+  return o;
+}
+
+void OnlineLoopClosureOptions::validate() const {
+  if (check_every_n_keyframes < 1) throw std::runtime_error("online_loop_closure: check_every_n_keyframes must be an integer >= 1");
+}
+
 // ================================================================== candidate selection
+namespace {
+double path_step(const double* a, const double* b) {  // |t_b - t_a|
+  const double dx = b[3] - a[3], dy = b[7] - a[7], dz = b[11] - a[11];
+  return std::sqrt(dx * dx + dy * dy + dz * dz);
+}
+}  // namespace
+
 std::vector<double> path_lengths(const std::vector<LoopFrame>& frames) {
   std::vector<double> s(frames.size(), 0.0);
-  for (size_t k = 1; k < frames.size(); k++) {
-    const double dx = frames[k].pose[3] - frames[k - 1].pose[3], dy = frames[k].pose[7] - frames[k - 1].pose[7],
-                 dz = frames[k].pose[11] - frames[k - 1].pose[11];
-    s[k] = s[k - 1] + std::sqrt(dx * dx + dy * dy + dz * dz);
-  }
+  for (size_t k = 1; k < frames.size(); k++) s[k] = s[k - 1] + path_step(frames[k - 1].pose, frames[k].pose);
   return s;
+}
+
+bool loop_candidates_step(const std::vector<LoopFrame>& frames, const std::vector<double>& s, size_t i, const LoopClosureOptions& opt,
+                          LoopCandidateState& state, const std::function<bool(const LoopPair&)>& verify, std::vector<LoopPair>& tried) {
+  if (!frames[i].has_points) return false;
+  if (state.closed && s[i] < state.s_closed + opt.min_travel_between_closures) return false;
+  uint32_t n = 0;
+  for (const PlaceIndex::Match& m : frames[i].matches) {
+    if (n >= opt.top_k) break;
+    const size_t j = m.frame;
+    if (j >= i || !frames[j].has_points) continue;
+    const double travel = s[i] - s[j];
+    if (!(travel >= opt.min_travel)) continue;
+    if (!(path_step(frames[j].pose, frames[i].pose) <= opt.gate_base + opt.gate_rate * travel)) continue;
+    if (opt.max_place_dist != 0 && m.dist > opt.max_place_dist) continue;
+    n++;
+    LoopPair p;
+    p.i = (uint32_t)i; p.j = (uint32_t)j; p.shift = m.shift; p.dist = m.dist;
+    tried.push_back(p);
+    if (!verify || verify(p)) {
+      state.closed = true;
+      state.s_closed = s[i];
+      return true;
+    }
+  }
+  return false;
 }
 
 std::vector<LoopPair> loop_candidates(const std::vector<LoopFrame>& frames, const LoopClosureOptions& opt,
                                       const std::function<bool(const LoopPair&)>& verify) {
   const std::vector<double> s = path_lengths(frames);
   std::vector<LoopPair> tried;
-  bool closed = false;
-  double s_closed = 0.0;
-  for (size_t i = 0; i < frames.size(); i++) {
-    if (!frames[i].has_points) continue;
-    if (closed && s[i] < s_closed + opt.min_travel_between_closures) continue;
-    uint32_t n = 0;
-    for (const PlaceIndex::Match& m : frames[i].matches) {
-      if (n >= opt.top_k) break;
-      const size_t j = m.frame;
-      if (j >= i || !frames[j].has_points) continue;
-      const double travel = s[i] - s[j];
-      if (!(travel >= opt.min_travel)) continue;
-      const double dx = frames[i].pose[3] - frames[j].pose[3], dy = frames[i].pose[7] - frames[j].pose[7],
-                   dz = frames[i].pose[11] - frames[j].pose[11];
-      if (!(std::sqrt(dx * dx + dy * dy + dz * dz) <= opt.gate_base + opt.gate_rate * travel)) continue;
-      if (opt.max_place_dist != 0 && m.dist > opt.max_place_dist) continue;
-      n++;
-      LoopPair p;
-      p.i = (uint32_t)i; p.j = (uint32_t)j; p.shift = m.shift; p.dist = m.dist;
-      tried.push_back(p);
-      if (!verify || verify(p)) {
-        closed = true;
-        s_closed = s[i];
-        break;
-      }
-    }
-  }
+  LoopCandidateState state;
+  for (size_t i = 0; i < frames.size(); i++) (void)loop_candidates_step(frames, s, i, opt, state, verify, tried);
   return tried;
 }
 
@@ -406,37 +438,22 @@ std::string LoopReport::toJson() const {
   return o;
 }
 
-// ================================================================== close_loops
-LoopClosureResult close_loops(const molahip_host::KeyFrameSet& set, const Config& pipeline, std::shared_ptr<DeviceContext> ctx) {
-  const LoopClosureOptions opt = LoopClosureOptions::FromConfig(pipeline);
-  const LidarOdometry::RelocalizationOptions reloc = relocalization_options(pipeline);
-  for (const auto& t : set.maps) {
-    if (t.class_name == "CVoxelMap")
-      throw std::runtime_error("close_loops: target map '" + t.name + "' is a '" + t.class_name + "': an occupancy map cannot be built from "
-                               "key-frames, so no submap to verify a loop in (HashedVoxelPointCloud, NDT and SparseTreesPointCloud can)");
-    if (!molahip_host::local_map_class_known(t.class_name))
-      throw std::runtime_error("close_loops: target map '" + t.name + "' is of the unknown class '" + t.class_name + "'");
-  }
-  // ---- the ICP the driver relocalizes with, its variables as after reset()
-  const Config& block = pipeline.has("icp_settings_without_vel") ? pipeline["icp_settings_without_vel"] : pipeline["icp_settings_with_vel"];
-  if (!ctx) ctx = DeviceContext::Default();
-  auto made = icp_pipeline_from_yaml(block, ctx);
-  ICP::Ptr icp = std::get<0>(made);
-  const Parameters icp_params = std::get<1>(made);
-  ParameterSource source;
-  icp->attachToParameterSource(source);
-  icp->setKeepFinalPairings(false);
-  icp->fuseGatedMatchers(true);
-  icp->fuseMultiPairings(true);
-  icp->fusePlaneMatchers(true);
+// ================================================================== what close_loops and OnlineLoopCloser share
+namespace {
+
+struct IcpLayers {
+  std::map<std::string, int> local_layers;  // local layer name -> the target map whose stored points it holds
+  std::string gname, lname;                 // the (global, local) layers candidates are scored on
+};
+
+IcpLayers icp_layers(ICP& icp, const std::vector<std::string>& map_names, const std::string& who) {
   auto map_index_of = [&](const std::string& name) -> int {
-    for (size_t k = 0; k < set.maps.size(); k++)
-      if (set.maps[k].name == name) return (int)k;
+    for (size_t k = 0; k < map_names.size(); k++)
+      if (map_names[k] == name) return (int)k;
     return -1;
   };
-  std::map<std::string, int> local_layers;  // local layer name -> the target map whose stored points it holds
-  std::string gname, lname;
-  for (const auto& m : icp->matchers()) {
+  IcpLayers out;
+  for (const auto& m : icp.matchers()) {
     if (!m->enabled) continue;
     const std::vector<Matcher_Points_DistanceThreshold::LayerMatch>* lm = nullptr;
     auto* pm = dynamic_cast<Matcher_Points_DistanceThreshold*>(m.get());
@@ -446,90 +463,138 @@ LoopClosureResult close_loops(const molahip_host::KeyFrameSet& set, const Config
     for (const auto& e : *lm) {
       const int k = map_index_of(e.global);
       if (k < 0)
-        throw std::runtime_error("close_loops: the ICP block matches against the global layer '" + e.global +
+        throw std::runtime_error(who + ": the ICP block matches against the global layer '" + e.global +
                                  "', which is no target map of the key-frame file's header");
-      const auto it = local_layers.find(e.local);
-      if (it != local_layers.end() && it->second != k)
-        throw std::runtime_error("close_loops: the local layer '" + e.local + "' is matched against two target maps; a key-frame stores one input layer per map");
-      local_layers[e.local] = k;
+      const auto it = out.local_layers.find(e.local);
+      if (it != out.local_layers.end() && it->second != k)
+        throw std::runtime_error(who + ": the local layer '" + e.local + "' is matched against two target maps; a key-frame stores one input layer per map");
+      out.local_layers[e.local] = k;
     }
-    if (pm && gname.empty() && !pm->pointLayerMatches.empty()) {
-      gname = pm->pointLayerMatches[0].global;
-      lname = pm->pointLayerMatches[0].local;
+    if (pm && out.gname.empty() && !pm->pointLayerMatches.empty()) {
+      out.gname = pm->pointLayerMatches[0].global;
+      out.lname = pm->pointLayerMatches[0].local;
     }
   }
-  if (gname.empty()) throw std::runtime_error("close_loops: the ICP block has no enabled Matcher_Points_DistanceThreshold to score candidates with");
-  double min_range = LidarOdometry::Params().absolute_minimum_sensor_range;
-  if (pipeline.has("params") && pipeline["params"].has("absolute_minimum_sensor_range"))
-    min_range = strtod(pipeline["params"]["absolute_minimum_sensor_range"].asString().c_str(), nullptr);
-  for (const char* v : {"vx", "vy", "vz", "wx", "wy", "wz", "robot_x", "robot_y", "robot_z", "robot_yaw", "robot_pitch", "robot_roll", "ICP_ITERATION",
-                        "icp_iterations", "SENSOR_TIME_OFFSET", "twistCorrectionCount"})
-    source.updateVariable(v, 0.0);
-  source.updateVariable("ADAPTIVE_THRESHOLD_SIGMA", opt.sigma);
-  source.updateVariable("INSTANTANEOUS_SENSOR_MAX_RANGE", 20.0);
-  source.updateVariable("ESTIMATED_SENSOR_MAX_RANGE", min_range);
+  if (out.gname.empty()) throw std::runtime_error(who + ": the ICP block has no enabled Matcher_Points_DistanceThreshold to score candidates with");
+  return out;
+}
 
-  LoopClosureResult out;
-  out.corrected = set;
-  LoopReport& rep = out.report;
-  const size_t K = set.frames.size();
-  auto usable = [&](size_t k) { return set.frames[k].has_points && !set.frames[k].layers.empty() && !set.frames[k].layers[0].x.empty(); };
+void refuse_unbuildable_targets(const std::vector<molahip_host::KeyFrameTarget>& maps, const std::string& who) {
+  for (const auto& t : maps) {
+    if (t.class_name == "CVoxelMap")
+      throw std::runtime_error(who + ": target map '" + t.name + "' is a '" + t.class_name + "': an occupancy map cannot be built from "
+                               "key-frames, so no submap to verify a loop in (HashedVoxelPointCloud, NDT and SparseTreesPointCloud can)");
+    if (!molahip_host::local_map_class_known(t.class_name))
+      throw std::runtime_error(who + ": target map '" + t.name + "' is of the unknown class '" + t.class_name + "'");
+  }
+}
 
-  // ---- the place index: every frame with points described once; the host copies are the queries
+bool usable(const molahip_host::KeyFrame& f) { return f.has_points && !f.layers.empty() && !f.layers[0].x.empty(); }
+
+}  // namespace
+
+void check_loop_closure_icp(ICP& icp, const std::vector<std::string>& map_names, const std::string& who) { (void)icp_layers(icp, map_names, who); }
+
+// The ICP the driver relocalizes with (its variables as after reset()), the place database, the frames' selection data, the loop
+// edges and the report: close_loops fills `frames` and `s` for the whole set before it selects, OnlineLoopCloser frame by frame.
+struct LoopCloserCore {
+  const LoopClosureOptions opt;
+  const LidarOdometry::RelocalizationOptions reloc;
+  const std::vector<molahip_host::KeyFrameTarget> maps;
+  std::shared_ptr<DeviceContext> ctx;
+  ICP::Ptr icp;
+  Parameters icp_params;
+  ParameterSource source;
+  IcpLayers layers;
+  double min_range = 0, thr = 0;
   mh_place_params pp{};
-  pp.n_rings = reloc.place_rings; pp.n_sectors = reloc.place_sectors;
-  pp.min_range = (float)reloc.place_min_range; pp.max_range = (float)reloc.place_max_range;
-  pp.z_min = (float)reloc.place_z_min; pp.z_max = (float)reloc.place_z_max;
-  struct Db {
-    mh_place_db* h = nullptr;
-    ~Db() { if (h) (void)mh_place_db_destroy(h); }
-  } db;
-  check(mh_place_db_create(ctx->get(), &pp, &db.h), "mh_place_db_create");
-  const size_t dsize = (size_t)pp.n_rings * pp.n_sectors;
-  std::vector<uint32_t> frame_of;
-  std::vector<std::vector<uint8_t>> desc;
-  {
+  mh_place_db* db = nullptr;
+  size_t dsize = 0;
+  std::vector<uint32_t> frame_of;                          // database entry -> frame
+  const std::vector<molahip_host::KeyFrame>* kf = nullptr;  // the frames by index: their layers
+  std::vector<LoopFrame> frames;                           // ... their recorded (raw) poses and match lists
+  std::vector<double> s;                                   // ... and path lengths
+  std::vector<PoseGraphEdge> loops;
+  LoopReport rep;
+
+  LoopCloserCore(const std::vector<molahip_host::KeyFrameTarget>& maps_, const Config& pipeline, std::shared_ptr<DeviceContext> ctx_, const std::string& who)
+      : opt(LoopClosureOptions::FromConfig(pipeline)), reloc(relocalization_options(pipeline)), maps(maps_), ctx(std::move(ctx_)) {
+    refuse_unbuildable_targets(maps, who);
+    const Config& block = pipeline.has("icp_settings_without_vel") ? pipeline["icp_settings_without_vel"] : pipeline["icp_settings_with_vel"];
+    if (!ctx) ctx = DeviceContext::Default();
+    auto made = icp_pipeline_from_yaml(block, ctx);
+    icp = std::get<0>(made);
+    icp_params = std::get<1>(made);
+    icp->attachToParameterSource(source);
+    icp->setKeepFinalPairings(false);
+    icp->fuseGatedMatchers(true);
+    icp->fuseMultiPairings(true);
+    icp->fusePlaneMatchers(true);
+    std::vector<std::string> names;
+    for (const auto& t : maps) names.push_back(t.name);
+    layers = icp_layers(*icp, names, who);
+    min_range = LidarOdometry::Params().absolute_minimum_sensor_range;
+    if (pipeline.has("params") && pipeline["params"].has("absolute_minimum_sensor_range"))
+      min_range = strtod(pipeline["params"]["absolute_minimum_sensor_range"].asString().c_str(), nullptr);
+    for (const char* v : {"vx", "vy", "vz", "wx", "wy", "wz", "robot_x", "robot_y", "robot_z", "robot_yaw", "robot_pitch", "robot_roll", "ICP_ITERATION",
+                          "icp_iterations", "SENSOR_TIME_OFFSET", "twistCorrectionCount"})
+      source.updateVariable(v, 0.0);
+    source.updateVariable("ADAPTIVE_THRESHOLD_SIGMA", opt.sigma);
+    source.updateVariable("INSTANTANEOUS_SENSOR_MAX_RANGE", 20.0);
+    source.updateVariable("ESTIMATED_SENSOR_MAX_RANGE", min_range);
+    pp.n_rings = reloc.place_rings; pp.n_sectors = reloc.place_sectors;
+    pp.min_range = (float)reloc.place_min_range; pp.max_range = (float)reloc.place_max_range;
+    pp.z_min = (float)reloc.place_z_min; pp.z_max = (float)reloc.place_z_max;
+    check(mh_place_db_create(ctx->get(), &pp, &db), "mh_place_db_create");
+    dsize = (size_t)pp.n_rings * pp.n_sectors;
+    for (size_t k = 0; k < maps.size(); k++)
+      if (maps[k].name == layers.gname) thr = 0.5 * (double)maps[k].params.voxel_size;
+  }
+  ~LoopCloserCore() { if (db) (void)mh_place_db_destroy(db); }
+  LoopCloserCore(const LoopCloserCore&) = delete;
+  LoopCloserCore& operator=(const LoopCloserCore&) = delete;
+
+  // the descriptor of a frame's first stored layer (counted as one "describe")
+  std::vector<uint8_t> describe(const molahip_host::KeyFrame& f) {
+    Stage st(rep, "describe");
+    const auto& l = f.layers[0];
     DevicePointCloud layer(ctx);
-    for (size_t k = 0; k < K; k++) {
-      if (!usable(k)) continue;
-      Stage st(rep, "describe");
-      const auto& l = set.frames[k].layers[0];
-      layer.setPoints(l.x.data(), l.y.data(), l.z.data(), l.x.size());
-      std::vector<uint8_t> d(dsize);
-      check(mh_place_describe(layer.handle(), &pp, d.data(), MH_MEM_HOST), "mh_place_describe");
-      check(mh_place_db_add(db.h, d.data(), 1, MH_MEM_HOST), "mh_place_db_add");
-      frame_of.push_back((uint32_t)k);
-      desc.push_back(std::move(d));
-    }
+    layer.setPoints(l.x.data(), l.y.data(), l.z.data(), l.x.size());
+    std::vector<uint8_t> d(dsize);
+    check(mh_place_describe(layer.handle(), &pp, d.data(), MH_MEM_HOST), "mh_place_describe");
+    return d;
   }
-  std::vector<LoopFrame> frames(K);
-  for (size_t k = 0; k < K; k++) {
-    std::copy(set.frames[k].pose, set.frames[k].pose + 12, frames[k].pose);
-    frames[k].has_points = usable(k);
+  // ... appended to the database as frame k's (its time goes to "describe")
+  void add(const std::vector<uint8_t>& d, size_t k) {
+    Stage st(rep, "describe", false);
+    check(mh_place_db_add(db, d.data(), 1, MH_MEM_HOST), "mh_place_db_add");
+    frame_of.push_back((uint32_t)k);
   }
-  std::vector<mh_place_match> found(frame_of.size());
-  for (size_t q = 0; q < frame_of.size(); q++) {
+  // every descriptor of the database against `d`, ranked by (dist ascending, frame ascending)
+  std::vector<PlaceIndex::Match> search(const std::vector<uint8_t>& d) {
     Stage st(rep, "search");
-    check(mh_place_search(db.h, desc[q].data(), MH_MEM_HOST, found.data(), MH_MEM_HOST), "mh_place_search");
-    std::vector<PlaceIndex::Match>& m = frames[frame_of[q]].matches;
+    std::vector<PlaceIndex::Match> m;
+    if (frame_of.empty()) return m;  // (an empty database has nothing to launch on)
+    std::vector<mh_place_match> found(frame_of.size());
+    check(mh_place_search(db, d.data(), MH_MEM_HOST, found.data(), MH_MEM_HOST), "mh_place_search");
     m.resize(found.size());
     for (size_t k = 0; k < found.size(); k++) m[k] = PlaceIndex::Match{frame_of[k], found[k].shift, found[k].dist};
     std::stable_sort(m.begin(), m.end(), [](const PlaceIndex::Match& a, const PlaceIndex::Match& b) { return a.dist != b.dist ? a.dist < b.dist : a.frame < b.frame; });
+    return m;
   }
 
-  // ---- verification of one pair on the device
-  const std::vector<double> s = path_lengths(frames);
-  double thr = 0.5 * (double)set.maps[(size_t)map_index_of(gname)].params.voxel_size;
-  std::vector<PoseGraphEdge> loops;
-  auto verify = [&](const LoopPair& c) -> bool {
+  // verification of one pair on the device; an accepted one becomes a loop edge
+  bool verify(const LoopPair& c) {
+    const std::vector<molahip_host::KeyFrame>& set_frames = *kf;
+    const size_t K = frames.size();
     LoopReport::Pair pr;
     pr.i = c.i; pr.j = c.j; pr.shift = c.shift; pr.dist = c.dist;
-    const CPose3D Ti = pose_of(set.frames[c.i].pose), Tj = pose_of(set.frames[c.j].pose);
+    const CPose3D Ti = pose_of(frames[c.i].pose), Tj = pose_of(frames[c.j].pose);
     metric_map_t glob, obs;
     {
       Stage st(rep, "submap");
-      for (size_t k = 0; k < set.maps.size(); k++) {
-        const auto& t = set.maps[k];
+      for (size_t k = 0; k < maps.size(); k++) {
+        const auto& t = maps[k];
         molahip_host::LocalMapRecord empty;
         empty.name = t.name;
         empty.class_name = t.class_name;
@@ -538,21 +603,21 @@ LoopClosureResult close_loops(const molahip_host::KeyFrameSet& set, const Config
         std::vector<PosedFrame> pf;
         for (size_t q = 0; q < K; q++) {
           if (!frames[q].has_points || !(std::fabs(s[q] - s[c.j]) <= opt.submap_radius) || !(s[c.i] - s[q] >= opt.min_travel)) continue;
-          for (const auto& l : set.frames[q].layers) {  // step order
+          for (const auto& l : set_frames[q].layers) {  // step order
             if (l.map_index != k) continue;
             PosedFrame f;
             f.x = l.x.data(); f.y = l.y.data(); f.z = l.z.data();
             f.n = l.x.size();
-            f.pose = pose_of(set.frames[q].pose) - Tj;
+            f.pose = pose_of(frames[q].pose) - Tj;
             pf.push_back(f);
           }
         }
         map->insertFrames(pf, 0);
         glob.layers[t.name] = map;
       }
-      for (const auto& [name, k] : local_layers) {
+      for (const auto& [name, k] : layers.local_layers) {
         std::vector<float> x, y, z;
-        for (const auto& l : set.frames[c.i].layers) {
+        for (const auto& l : set_frames[c.i].layers) {
           if ((int)l.map_index != k) continue;
           x.insert(x.end(), l.x.begin(), l.x.end());
           y.insert(y.end(), l.y.begin(), l.y.end());
@@ -567,7 +632,7 @@ LoopClosureResult close_loops(const molahip_host::KeyFrameSet& set, const Config
     // the variables of this frame
     double range = 0.0;
     {
-      const auto& l = set.frames[c.i].layers[0];
+      const auto& l = set_frames[c.i].layers[0];
       for (size_t p = 0; p < l.x.size(); p++) {
         const double x = l.x[p], y = l.y[p], z = l.z[p], r2 = x * x + y * y + z * z;
         if (std::isfinite(r2)) range = std::max(range, r2);
@@ -588,7 +653,8 @@ LoopClosureResult close_loops(const molahip_host::KeyFrameSet& set, const Config
     const std::vector<TPose3D> cand =
         relocalization_grid((Ti - Tj).asTPose(), cov, step, reloc.step_yaw_deg * kDeg2Rad, reloc.sigmas, reloc.max_candidates);
     pr.candidates = (uint32_t)cand.size();
-    const RelocalizationRefinement rr = score_rank_refine(*icp, icp_params, obs, glob, gname, lname, cand, thr, reloc.refine_top_k, &rep.seconds);
+    const RelocalizationRefinement rr =
+        score_rank_refine(*icp, icp_params, obs, glob, layers.gname, layers.lname, cand, thr, reloc.refine_top_k, &rep.seconds);
     rep.counts["score"] += 1.0;
     rep.counts["refine"] += (double)rr.ranks.size();
     pr.ranks = rr.ranks;
@@ -606,23 +672,154 @@ LoopClosureResult close_loops(const molahip_host::KeyFrameSet& set, const Config
     }
     rep.pairs.push_back(pr);
     return pr.accepted;
-  };
-  (void)loop_candidates(frames, opt, verify);
+  }
+
+  // one optimisation over all frames, from their recorded (raw) poses and every loop edge so far
+  std::vector<double> optimize(bool count = true) {
+    const size_t K = frames.size();
+    std::vector<double> poses(12 * K);
+    for (size_t k = 0; k < K; k++) std::copy(frames[k].pose, frames[k].pose + 12, &poses[12 * k]);
+    PoseGraphResult g;
+    {
+      Stage st(rep, "optimize", count);
+      g = optimize_pose_graph(poses, loops, opt);
+    }
+    rep.cost_before = g.cost_before;
+    rep.cost_after = g.cost_after;
+    rep.optimizer_iterations = g.iterations;
+    return std::move(g.poses);
+  }
+};
+
+// ================================================================== close_loops
+LoopClosureResult close_loops(const molahip_host::KeyFrameSet& set, const Config& pipeline, std::shared_ptr<DeviceContext> ctx) {
+  LoopCloserCore core(set.maps, pipeline, std::move(ctx), "close_loops");
+  LoopClosureResult out;
+  out.corrected = set;
+  const size_t K = set.frames.size();
+  core.kf = &set.frames;
+  // ---- the place index: every frame with points described once; the host copies are the queries
+  std::vector<std::vector<uint8_t>> desc;
+  for (size_t k = 0; k < K; k++) {
+    if (!usable(set.frames[k])) continue;
+    desc.push_back(core.describe(set.frames[k]));
+    core.add(desc.back(), k);
+  }
+  core.frames.resize(K);
+  for (size_t k = 0; k < K; k++) {
+    std::copy(set.frames[k].pose, set.frames[k].pose + 12, core.frames[k].pose);
+    core.frames[k].has_points = usable(set.frames[k]);
+  }
+  for (size_t q = 0; q < desc.size(); q++) core.frames[core.frame_of[q]].matches = core.search(desc[q]);
+  core.s = path_lengths(core.frames);
+  (void)loop_candidates(core.frames, core.opt, [&](const LoopPair& c) { return core.verify(c); });
 
   // ---- one optimisation over all frames
-  if (loops.empty()) return out;  // the input, bit for bit
-  std::vector<double> poses(12 * K);
-  for (size_t k = 0; k < K; k++) std::copy(set.frames[k].pose, set.frames[k].pose + 12, &poses[12 * k]);
-  PoseGraphResult g;
-  {
-    Stage st(rep, "optimize");
-    g = optimize_pose_graph(poses, loops, opt);
+  if (!core.loops.empty()) {  // (otherwise the input, bit for bit)
+    const std::vector<double> poses = core.optimize();
+    for (size_t k = 0; k < K; k++) std::copy(&poses[12 * k], &poses[12 * k] + 12, out.corrected.frames[k].pose);
   }
-  rep.cost_before = g.cost_before;
-  rep.cost_after = g.cost_after;
-  rep.optimizer_iterations = g.iterations;
-  for (size_t k = 0; k < K; k++) std::copy(&g.poses[12 * k], &g.poses[12 * k] + 12, out.corrected.frames[k].pose);
+  out.report = std::move(core.rep);
   return out;
+}
+
+// ================================================================== OnlineLoopCloser
+OnlineLoopCloser::OnlineLoopCloser(const std::vector<molahip_host::KeyFrameTarget>& maps, const Config& pipeline, std::shared_ptr<DeviceContext> ctx)
+    : online_(OnlineLoopClosureOptions::FromConfig(pipeline)) {
+  core_ = std::make_unique<LoopCloserCore>(maps, pipeline, std::move(ctx), "OnlineLoopCloser");
+  core_->kf = &frames_;
+}
+OnlineLoopCloser::~OnlineLoopCloser() = default;
+size_t OnlineLoopCloser::size() const { return raw_.size() / 12; }
+const std::vector<double>& OnlineLoopCloser::rawPoses() const { return raw_; }
+const std::vector<double>& OnlineLoopCloser::correctedPoses() const { return corrected_; }
+const std::vector<PoseGraphEdge>& OnlineLoopCloser::loops() const { return core_->loops; }
+const LoopReport& OnlineLoopCloser::report() const { return core_->rep; }
+
+void OnlineLoopCloser::readFramesFrom(const std::vector<molahip_host::KeyFrame>* frames) {
+  if (size() != 0) throw std::runtime_error("OnlineLoopCloser::readFramesFrom: frames have been pushed already");
+  if (!frames) throw std::runtime_error("OnlineLoopCloser::readFramesFrom: no frames");
+  external_ = frames;
+  core_->kf = frames;
+}
+
+molahip_host::KeyFrameSet OnlineLoopCloser::rawKeyFrames() const {
+  molahip_host::KeyFrameSet set;
+  set.maps = core_->maps;
+  set.frames.assign(core_->kf->begin(), core_->kf->begin() + (std::ptrdiff_t)size());
+  for (size_t k = 0; k < set.frames.size(); k++) std::copy(&raw_[12 * k], &raw_[12 * k] + 12, set.frames[k].pose);
+  return set;
+}
+
+OnlineLoopCloser::Step OnlineLoopCloser::push(molahip_host::KeyFrame frame) {
+  if (external_) throw std::runtime_error("OnlineLoopCloser::push: the frames are read from the caller's vector (readFramesFrom); use pushStored");
+  double raw[12];
+  std::copy(frame.pose, frame.pose + 12, raw);
+  frames_.push_back(std::move(frame));
+  try {
+    return push_frame(frames_.back(), raw);
+  } catch (...) {
+    frames_.pop_back();
+    throw;
+  }
+}
+
+OnlineLoopCloser::Step OnlineLoopCloser::pushStored(size_t index, const double raw_pose[12]) {
+  if (!external_) throw std::runtime_error("OnlineLoopCloser::pushStored: no vector to read the frames from (readFramesFrom)");
+  if (index != size() || index >= external_->size())
+    throw std::runtime_error("OnlineLoopCloser::pushStored: frame " + std::to_string(index) + " is not the next one (" + std::to_string(size()) +
+                             " pushed, " + std::to_string(external_->size()) + " stored)");
+  return push_frame((*external_)[index], raw_pose);
+}
+
+// `f` is frame size() of the vector the core reads the layers from.  Nothing of the closer's state is kept when a device call throws:
+// the same frame can be pushed again.
+OnlineLoopCloser::Step OnlineLoopCloser::push_frame(const molahip_host::KeyFrame& f, const double raw[12]) {
+  LoopCloserCore& c = *core_;
+  for (int k = 0; k < 12; k++)
+    if (!std::isfinite(raw[k])) throw std::runtime_error("OnlineLoopCloser::push: non-finite pose");
+  const size_t i = size();
+  const size_t n_loops = c.loops.size(), n_pairs = c.rep.pairs.size(), n_points = n_with_points_;
+  const LoopCandidateState state = state_;
+  LoopFrame lf;
+  std::copy(raw, raw + 12, lf.pose);
+  lf.has_points = usable(f);
+  c.s.push_back(i == 0 ? 0.0 : c.s[i - 1] + path_step(c.frames[i - 1].pose, raw));
+  c.frames.push_back(std::move(lf));
+  raw_.insert(raw_.end(), raw, raw + 12);
+  Step step;
+  try {
+    std::vector<uint8_t> d;
+    if (c.frames[i].has_points) {
+      const bool checked = n_with_points_++ % online_.check_every_n_keyframes == 0;
+      d = c.describe(f);
+      if (checked) {
+        c.frames[i].matches = c.search(d);  // the frames < i: the database as it stands before this frame's descriptor enters
+        std::vector<LoopPair> tried;
+        step.closed = loop_candidates_step(c.frames, c.s, i, c.opt, state_, [&](const LoopPair& p) { return c.verify(p); }, tried);
+        step.pairs.assign(c.rep.pairs.begin() + (std::ptrdiff_t)n_pairs, c.rep.pairs.end());
+        step.tried = !step.pairs.empty();
+        std::vector<PlaceIndex::Match>().swap(c.frames[i].matches);  // (no later frame reads them)
+      }
+    }
+    // the correction: from the raw chain and every loop so far, never from the previous correction -- what close_loops gives for
+    // the frames pushed so far
+    std::vector<double> corrected;
+    if (!c.loops.empty()) corrected = c.optimize(step.closed);
+    if (c.frames[i].has_points) c.add(d, i);  // (last: the database changes only when everything else has succeeded)
+    if (c.loops.empty()) corrected_.insert(corrected_.end(), raw, raw + 12);
+    else corrected_ = std::move(corrected);
+  } catch (...) {
+    c.s.pop_back();
+    c.frames.pop_back();
+    raw_.resize(12 * i);
+    c.loops.resize(n_loops);
+    c.rep.pairs.resize(n_pairs);
+    state_ = state;
+    n_with_points_ = n_points;
+    throw;
+  }
+  return step;
 }
 
 LoopReport close_loops_file(const std::string& keyframe_file, const Config& pipeline, const std::string& output_keyframe_file,

@@ -103,6 +103,8 @@ struct SequenceReport {
   double mean_icp_points = 0, mean_map_layer_points = 0, mean_raw_points = 0;
   uint64_t final_map_points = 0, max_map_points = 0, final_map_voxels = 0;
   std::vector<double> scan_seconds;  // --scan-log: registration time of every scan
+  bool online_loop_closure = false;  // the pipeline's online_loop_closure: block is enabled ...
+  size_t loops_closed = 0;           // ... and closed this many loops while driving
 };
 
 struct RunOptions {
@@ -115,6 +117,7 @@ struct RunOptions {
   std::string output_simplemap;    // --output-simplemap: record key-frames (params.simplemap.generate) and save them at the end (FILE_<k> likewise)
   bool relocalize_in_keyframes = false;  // --relocalize-in-keyframes: LidarOdometry::relocalizeInKeyFrames() before the first scan
   std::string output_session_map;  // --output-session-map: ... and the maps of the whole drive built from them, as a local-map file (FILE_<k> likewise)
+  std::string output_corrected_trajectory;  // --output-corrected-trajectory: LidarOdometry::correctedTrajectory() as a TUM file
 };
 
 // what the replay leaves behind besides the trajectory: layer and map sizes (records()), optionally a per-scan CSV
@@ -262,6 +265,9 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
       }
     }
     lo.saveTrajectoryTUM(out);
+    if (!opt.output_corrected_trajectory.empty()) lo.saveCorrectedTrajectoryTUM(opt.output_corrected_trajectory + suffix);
+    rep.online_loop_closure = mola_hip::OnlineLoopClosureOptions::FromConfig(cfg).enabled;
+    if (lo.loopCloser()) rep.loops_closed = lo.loopCloser()->loops().size();
     stamp("trajectory saved");
     if (!opt.save_local_map.empty()) lo.saveLocalMaps(opt.save_local_map + suffix);  // (what params.local_map_updates.load_existing_local_map of a later run reads)
     if (!opt.output_simplemap.empty()) lo.saveKeyFrames(opt.output_simplemap + suffix);
@@ -341,6 +347,17 @@ int main(int argc, char** argv) {
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
                       "  --devices: the sequences are spread over the listed GPUs (longest first onto the least loaded device)\n";
+  // (shown after it when the run asks for online loop closure: the pipeline's online_loop_closure: block, or the option itself)
+  const char* usage_online = "  --output-corrected-trajectory: with the pipeline's online_loop_closure: block enabled loops are closed while driving; the\n"
+                             "  trajectory as the closures correct it goes to FILE (TUM), --out keeps what was estimated at the time; one sequence only\n";
+  auto online_enabled = [&]() {
+    if (pipeline.empty()) return false;
+    try {
+      return mola_hip::OnlineLoopClosureOptions::FromConfig(mp2p_icp_hip::Config::FromYamlFile(pipeline)).enabled;
+    } catch (const std::exception&) {
+      return false;  // (the run itself reports what is wrong with the file)
+    }
+  };
   for (int i = 1; i < argc; i++) {
     const std::string a = argv[i];
     auto val = [&](const char* name) -> std::string {
@@ -360,6 +377,7 @@ int main(int argc, char** argv) {
       else if (a == "--save-local-map") opt.save_local_map = val("--save-local-map");
       else if (a == "--output-simplemap") opt.output_simplemap = val("--output-simplemap");
       else if (a == "--output-session-map") opt.output_session_map = val("--output-session-map");
+      else if (a == "--output-corrected-trajectory") opt.output_corrected_trajectory = val("--output-corrected-trajectory");
       else if (a == "--build-session-map") build_from = val("--build-session-map");
       else if (a == "--close-loops") close_from = val("--close-loops");
       else if (a == "--loop-report") loop_report = val("--loop-report");
@@ -427,11 +445,16 @@ int main(int argc, char** argv) {
     return 0;
   }
   if (pipeline.empty() || seq_dirs.empty()) {
-    fprintf(stderr, "%s", usage);
+    fprintf(stderr, "%s%s", usage, !opt.output_corrected_trajectory.empty() || online_enabled() ? usage_online : "");
     return 2;
   }
   if (devices.empty()) devices = {0};
   const size_t N = seq_dirs.size(), D = devices.size();
+  if ((N > 1 || D > 1) && online_enabled()) {
+    fprintf(stderr, "molahip-lo-cli: the pipeline's online_loop_closure: block is enabled: one sequence on one device only (several sequences of a "
+                    "process align through an AlignBatcher, whose batch protocol has no slot for the extra alignments that verify a loop)\n");
+    return 2;
+  }
   // which sequence runs where: scan counts are known from the folders (no GPU needed for the plan)
   std::vector<size_t> n_scans(N, 0), slot(N, 0), load(D, 0);
   try {
@@ -498,10 +521,12 @@ int main(int argc, char** argv) {
     total += r.scans;
     printf("{\"sequence_dir\": \"%s\", \"device\": %d, \"scans\": %zu, \"good\": %zu, \"keyframes\": %zu, \"icp_iterations\": %zu, "
            "\"seconds\": %.6f, \"scans_per_s\": %.3f, \"steady_scans_per_s\": %.3f, \"mean_raw_points\": %.1f, \"mean_icp_points\": %.1f, "
-           "\"mean_map_layer_points\": %.1f, \"final_map_points\": %llu, \"max_map_points\": %llu, \"final_map_voxels\": %llu, \"tum\": \"%s\"}\n",
+           "\"mean_map_layer_points\": %.1f, \"final_map_points\": %llu, \"max_map_points\": %llu, \"final_map_voxels\": %llu, \"tum\": \"%s\"",
            r.seq_dir.c_str(), r.device, r.scans, r.good, r.keyframes, r.iterations, r.seconds, r.seconds > 0 ? r.scans / r.seconds : 0.0,
            r.steady_seconds > 0 ? r.steady_scans / r.steady_seconds : 0.0, r.mean_raw_points, r.mean_icp_points, r.mean_map_layer_points,
            (unsigned long long)r.final_map_points, (unsigned long long)r.max_map_points, (unsigned long long)r.final_map_voxels, r.out.c_str());
+    if (r.online_loop_closure) printf(", \"loops_closed\": %zu", r.loops_closed);
+    printf("}\n");
     if (print_profile && r.scans) {  // host milliseconds per scan and stage (LidarOdometry::profile()), steady state
       const double ns = (double)(r.steady_scans ? r.steady_scans : r.scans);
       printf("{\"profile_ms_per_scan\": {");
@@ -551,7 +576,12 @@ int main(int argc, char** argv) {
              "\"steady_scans_per_s\": %.3f}",
              d ? ", " : "", d, devices[d], per_slot[d], dev_scans[d], dev_seconds[d], dev_seconds[d] > 0 ? dev_scans[d] / dev_seconds[d] : 0.0,
              dev_steady_seconds[d] > 0 ? dev_steady[d] / dev_steady_seconds[d] : 0.0);
-    printf("]}\n");
+    printf("]");
+    size_t loops_closed = 0;
+    bool online = false;
+    for (const auto& r : reps) online = online || r.online_loop_closure, loops_closed += r.loops_closed;
+    if (online) printf(", \"loops_closed\": %zu", loops_closed);  // (the pipeline's online_loop_closure: block; absent, the line is as before)
+    printf("}\n");
   }
   // Everything asked for is on disk and on stdout.  The drivers' destructors would now hipFree a few hundred buffers one by one,
   // each call a wait for the whole device: 0.2 s for eight sequences -- the operating system takes the memory back faster

@@ -397,6 +397,12 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["reloc_best_n_paired"] = r.reloc_best_n_paired; d["reloc_best_quality"] = r.reloc_best_quality; d["reloc_ranks"] = r.reloc_ranks;
     d["simplemap_keyframe"] = r.simplemap_keyframe; d["simplemap_frame"] = r.simplemap_frame;
     d["place_tried"] = r.place_tried; d["place_frames"] = r.place_frames; d["place_shifts"] = r.place_shifts; d["place_dists"] = r.place_dists;
+    d["loop_tried"] = r.loop_tried; d["loop_closed"] = r.loop_closed;
+    py::list loop_pairs;
+    for (const auto& p : r.loop_pairs) loop_pairs.append(py::make_tuple(p.i, p.j, p.quality, p.accepted));
+    d["loop_pairs"] = loop_pairs;
+    d["loop_correction_trans"] = r.loop_correction_trans; d["loop_correction_rot"] = r.loop_correction_rot;
+    d["loop_rebuilt_frames"] = r.loop_rebuilt_frames;
     return d;
   };
   py::class_<LidarOdometry> lo_class(m, "LidarOdometry", py::dynamic_attr());
@@ -568,6 +574,14 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         for (auto& [t, p] : lo.estimatedTrajectory()) l.append(py::make_tuple(t, std::vector<double>(p.T, p.T + 12)));
         return l; })
       .def("saveTrajectoryTUM", &LidarOdometry::saveTrajectoryTUM)
+      .def("correctedTrajectory", [](const LidarOdometry& lo) {
+        py::list l;
+        for (auto& [t, p] : lo.correctedTrajectory()) l.append(py::make_tuple(t, std::vector<double>(p.T, p.T + 12)));
+        return l; })
+      .def("saveCorrectedTrajectoryTUM", &LidarOdometry::saveCorrectedTrajectoryTUM)
+      .def("rawKeyFrames", [kfset2dict](const LidarOdometry& lo) { return kfset2dict(lo.rawKeyFrames()); })
+      .def("loopCloser", [](const LidarOdometry& lo) { return std::const_pointer_cast<mola_hip::OnlineLoopCloser>(lo.loopCloser()); },
+           py::keep_alive<0, 1>())  // (the closer reads the layers of the driver's key-frame store)
       .def("dynamicVariables", &LidarOdometry::dynamicVariables)
       .def("describePipeline", &LidarOdometry::describePipeline)
       .def("profile", [](const LidarOdometry& lo) { return lo.profile(); })
@@ -833,5 +847,122 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     rep["optimizer_iterations"] = r.report.optimizer_iterations; rep["seconds"] = r.report.seconds; rep["counts"] = r.report.counts;
     rep["json"] = r.report.toJson();
     return py::make_tuple(kfset2dict(r.corrected), rep); }, py::arg("frames"), py::arg("pipeline"), py::arg("output_keyframe_file") = "");
+  // ---- the same while driving (mola_hip::OnlineLoopCloser)
+  // the online_loop_closure: block of a pipeline Config as a dict (an absent block: the defaults)
+  m.def("online_loop_closure_options", [](const Config& c) {
+    const auto o = mola_hip::OnlineLoopClosureOptions::FromConfig(c);
+    py::dict d;
+    d["enabled"] = o.enabled; d["correct_driver"] = o.correct_driver; d["check_every_n_keyframes"] = o.check_every_n_keyframes;
+    return d; });
+  // the candidate rule for ONE frame i = len(poses) - 1: poses [i + 1, 12], has_points [i + 1], frame i's match list, the options,
+  // state = (closed, s_closed) as the previous step returned it (None: none yet) -> ([(i, j, shift, dist)], accepted, state)
+  m.def("loop_candidates_step", [dict2opts](py::array_t<double, py::array::c_style | py::array::forcecast> poses, const std::vector<bool>& has_points,
+                                            const std::vector<std::tuple<uint32_t, uint32_t, uint32_t>>& matches, const py::dict& options,
+                                            const py::object& state, const py::object& accept) {
+    if (poses.ndim() != 2 || poses.shape(1) != 12 || poses.shape(0) < 1) throw std::runtime_error("poses must be [i + 1, 12]");
+    const size_t K = (size_t)poses.shape(0);
+    if (has_points.size() != K) throw std::runtime_error("has_points needs one entry per pose");
+    std::vector<mola_hip::LoopFrame> frames(K);
+    for (size_t k = 0; k < K; k++) {
+      std::copy(poses.data() + 12 * k, poses.data() + 12 * k + 12, frames[k].pose);
+      frames[k].has_points = has_points[k];
+    }
+    for (const auto& [f, s, d] : matches) frames[K - 1].matches.push_back(mola_hip::PlaceIndex::Match{f, s, d});  // (later frames are skipped)
+    mola_hip::LoopCandidateState st;
+    if (!state.is_none()) {
+      const py::tuple t = state.cast<py::tuple>();
+      st.closed = t[0].cast<bool>();
+      st.s_closed = t[1].cast<double>();
+    }
+    std::function<bool(const mola_hip::LoopPair&)> verify;
+    if (!accept.is_none()) verify = [&accept](const mola_hip::LoopPair& p) { return accept(p.i, p.j, p.shift, p.dist).cast<bool>(); };
+    std::vector<mola_hip::LoopPair> tried;
+    const bool accepted = mola_hip::loop_candidates_step(frames, mola_hip::path_lengths(frames), K - 1, dict2opts(options), st, verify, tried);
+    py::list out;
+    for (const auto& p : tried) out.append(py::make_tuple(p.i, p.j, p.shift, p.dist));
+    return py::make_tuple(out, accepted, py::make_tuple(st.closed, st.s_closed)); },
+        py::arg("poses"), py::arg("has_points"), py::arg("matches"), py::arg("options") = py::dict(), py::arg("state") = py::none(),
+        py::arg("accept") = py::none());
+  auto pair2dict = [](const mola_hip::LoopReport::Pair& p) {
+    py::dict d;
+    d["i"] = p.i; d["j"] = p.j; d["shift"] = p.shift; d["dist"] = p.dist; d["candidates"] = p.candidates; d["ranks"] = p.ranks;
+    d["quality"] = p.quality; d["iterations"] = p.iterations; d["accepted"] = p.accepted; d["Z"] = std::vector<double>(p.Z, p.Z + 12);
+    return d;
+  };
+  auto poses2array = [](const std::vector<double>& v) {
+    py::array_t<double> P({(py::ssize_t)(v.size() / 12), (py::ssize_t)12});
+    std::copy(v.begin(), v.end(), P.mutable_data());
+    return P;
+  };
+  // maps: the "maps" list of a key-frame dict; push(frame): one entry of its "frames" list, the pose the RAW one
+  py::class_<mola_hip::OnlineLoopCloser, std::shared_ptr<mola_hip::OnlineLoopCloser>>(m, "OnlineLoopCloser")
+      .def(py::init([dict2kfset](const py::list& maps, const Config& pipeline) {
+             py::dict d;
+             d["maps"] = maps; d["frames"] = py::list();
+             return std::make_shared<mola_hip::OnlineLoopCloser>(dict2kfset(d).maps, pipeline); }), py::arg("maps"), py::arg("pipeline"))
+      .def("push", [dict2kfset, pair2dict](mola_hip::OnlineLoopCloser& c, const py::dict& frame) {
+        py::dict d;
+        py::list one;
+        one.append(frame);
+        d["maps"] = py::list(); d["frames"] = one;
+        molahip_host::KeyFrameSet set = dict2kfset(d);
+        mola_hip::OnlineLoopCloser::Step st;
+        {
+          py::gil_scoped_release nogil;
+          st = c.push(std::move(set.frames[0]));
+        }
+        py::dict out;
+        py::list pairs;
+        for (const auto& p : st.pairs) pairs.append(pair2dict(p));
+        out["tried"] = st.tried; out["closed"] = st.closed; out["pairs"] = pairs;
+        return out; })
+      .def("size", &mola_hip::OnlineLoopCloser::size)
+      .def("rawPoses", [poses2array](const mola_hip::OnlineLoopCloser& c) { return poses2array(c.rawPoses()); })
+      .def("correctedPoses", [poses2array](const mola_hip::OnlineLoopCloser& c) { return poses2array(c.correctedPoses()); })
+      .def("loops", [](const mola_hip::OnlineLoopCloser& c) {
+        py::list l;
+        for (const auto& e : c.loops()) l.append(py::make_tuple(e.a, e.b, std::vector<double>(e.Z, e.Z + 12)));
+        return l; })
+      .def("options", [](const mola_hip::OnlineLoopCloser& c) {
+        py::dict d;
+        d["enabled"] = c.options().enabled; d["correct_driver"] = c.options().correct_driver;
+        d["check_every_n_keyframes"] = c.options().check_every_n_keyframes;
+        return d; })
+      .def("rawKeyFrames", [kfset2dict](const mola_hip::OnlineLoopCloser& c) { return kfset2dict(c.rawKeyFrames()); })
+      .def("report", [pair2dict](const mola_hip::OnlineLoopCloser& c) {
+        const mola_hip::LoopReport& r = c.report();
+        py::dict rep;
+        py::list pairs;
+        for (const auto& p : r.pairs) pairs.append(pair2dict(p));
+        rep["pairs"] = pairs; rep["cost_before"] = r.cost_before; rep["cost_after"] = r.cost_after;
+        rep["optimizer_iterations"] = r.optimizer_iterations; rep["seconds"] = r.seconds; rep["counts"] = r.counts;
+        rep["json"] = r.toJson();
+        return rep; });
+  // the pose rules of the driver's online loop closure and the motion model's rebase, on 12-value poses
+  auto to_pose = [](const std::vector<double>& T) {
+    if (T.size() != 12) throw std::runtime_error("a pose has 12 values");
+    CPose3D p;
+    std::copy(T.begin(), T.end(), p.T);
+    return p;
+  };
+  auto from_pose = [](const CPose3D& p) { return std::vector<double>(p.T, p.T + 12); };
+  m.def("loop_raw_pose", [to_pose, from_pose](const std::vector<double>& raw_prev, const std::vector<double>& P, const std::vector<double>& S_prev) {
+    return from_pose(mola_hip::loop_raw_pose(to_pose(raw_prev), to_pose(P), to_pose(S_prev))); });
+  m.def("loop_correction", [to_pose, from_pose](const std::vector<double>& C, const std::vector<double>& P) {
+    return from_pose(mola_hip::loop_correction(to_pose(C), to_pose(P))); });
+  m.def("trajectory_anchor", [to_pose, from_pose](const std::vector<double>& P, const std::vector<double>& S) {
+    return from_pose(mola_hip::trajectory_anchor(to_pose(P), to_pose(S))); });
+  m.def("trajectory_corrected", [to_pose, from_pose](const std::vector<double>& C, const std::vector<double>& rel) {
+    return from_pose(mola_hip::trajectory_corrected(to_pose(C), to_pose(rel))); });
+  // the constant-velocity motion model: fuse_pose(t, pose), estimated_navstate(t) -> (pose, twist [6]) or None, rebase(delta)
+  py::class_<mola_hip::NavStateFuse>(m, "NavStateFuse")
+      .def(py::init<>())
+      .def("fuse_pose", [to_pose](mola_hip::NavStateFuse& n, double t, const std::vector<double>& pose) { n.fuse_pose(t, to_pose(pose)); })
+      .def("estimated_navstate", [from_pose](const mola_hip::NavStateFuse& n, double t) -> py::object {
+        const auto ns = n.estimated_navstate(t);
+        if (!ns) return py::none();
+        const mola_hip::Twist& w = ns->twist;
+        return py::make_tuple(from_pose(ns->pose.mean), std::vector<double>{w.vx, w.vy, w.vz, w.wx, w.wy, w.wz}); })
+      .def("rebase", [to_pose](mola_hip::NavStateFuse& n, const std::vector<double>& delta) { n.rebase(to_pose(delta)); });
   m.def("icp_pipeline_from_yaml", [](const Config& c) { auto t = icp_pipeline_from_yaml(c); return py::make_tuple(std::get<0>(t), std::get<1>(t)); });
 }
