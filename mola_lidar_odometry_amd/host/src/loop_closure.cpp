@@ -1,6 +1,8 @@
 // loop_closure.cpp -- see mola_lidar_odometry_hip/LoopClosure.h.  Host logic only: every point touches the GPU through the calls
 // the relocalization already makes (mh_place_*, mh_map_insert_frames, mh_score_poses, the ICP of mp2p_icp_hip).
 #include "mola_lidar_odometry_hip/LoopClosure.h"
+#include "mola_lidar_odometry_hip/SessionJoin.h"
+#include "loop_closure_internal.h"
 
 #include <algorithm>
 #include <chrono>
@@ -269,53 +271,22 @@ struct Profile {
   }
 };
 
-}  // namespace
+void edge_weights(double sxyz, double srot_deg, double w[6]) {
+  const double srot = srot_deg * kDeg2Rad;
+  for (int k = 0; k < 3; k++) w[k] = 1.0 / (sxyz * sxyz), w[3 + k] = 1.0 / (srot * srot);
+}
 
-PoseGraphResult optimize_pose_graph(const std::vector<double>& poses, const std::vector<PoseGraphEdge>& loops, const LoopClosureOptions& opt) {
-  if (poses.size() % 12) throw std::runtime_error("optimize_pose_graph: 12 values per pose");
-  const size_t K = poses.size() / 12;
-  for (const PoseGraphEdge& e : loops) {
-    if (e.a >= K || e.b >= K)
-      throw std::runtime_error("optimize_pose_graph: a loop edge names node " + std::to_string(std::max(e.a, e.b)) + " of " + std::to_string(K));
-    if (e.a == e.b) throw std::runtime_error("optimize_pose_graph: a loop edge from node " + std::to_string(e.a) + " to itself");
-  }
-  for (double v : poses)
-    if (!std::isfinite(v)) throw std::runtime_error("optimize_pose_graph: non-finite pose");
-  PoseGraphResult out;
-  out.poses = poses;
-  if (loops.empty() || K < 2) {  // the chain's residuals are zero by construction
-    out.costs.push_back(0.0);
-    return out;
-  }
-  std::vector<CPose3D> T(K);
-  for (size_t k = 0; k < K; k++) T[k] = pose_of(&poses[12 * k]);
-  auto weights = [](double sxyz, double srot_deg, double w[6]) {
-    const double srot = srot_deg * kDeg2Rad;
-    for (int k = 0; k < 3; k++) w[k] = 1.0 / (sxyz * sxyz), w[3 + k] = 1.0 / (srot * srot);
-  };
-  std::vector<GraphEdge> edges;
-  edges.reserve(K - 1 + loops.size());
-  for (size_t k = 1; k < K; k++) {
-    GraphEdge e;
-    e.a = (uint32_t)(k - 1); e.b = (uint32_t)k;
-    e.Z = T[k] - T[k - 1];
-    weights(opt.odometry_sigma_xyz, opt.odometry_sigma_rot_deg, e.w);
-    edges.push_back(e);
-  }
-  for (const PoseGraphEdge& l : loops) {
-    GraphEdge e;
-    e.a = l.a; e.b = l.b;
-    e.Z = pose_of(l.Z);
-    weights(opt.loop_sigma_xyz, opt.loop_sigma_rot_deg, e.w);
-    edges.push_back(e);
-  }
-  // the envelope: variable block v = node v + 1 (node 0 is fixed); a block row starts at the lowest block it shares an edge with
-  const size_t nb = K - 1, n = 6 * nb;
+// The Levenberg-Marquardt loop of LoopClosure.h over the nodes T: the first n_fixed stay as they are, node v >= n_fixed is variable
+// block v - n_fixed.  Fills out's costs and iteration count; T holds the optimum.
+void solve_graph(std::vector<CPose3D>& T, const size_t n_fixed, const std::vector<GraphEdge>& edges, const LoopClosureOptions& opt, PoseGraphResult& out) {
+  const size_t K = T.size();
+  // the envelope: a block row starts at the lowest block it shares an edge with
+  const size_t nb = K - n_fixed, n = 6 * nb;
   std::vector<size_t> first_block(nb);
   for (size_t v = 0; v < nb; v++) first_block[v] = v;
   for (const GraphEdge& e : edges) {
-    if (e.a == 0 || e.b == 0) continue;
-    const size_t lo = std::min(e.a, e.b) - 1, hi = std::max(e.a, e.b) - 1;
+    if (e.a < n_fixed || e.b < n_fixed) continue;
+    const size_t lo = std::min(e.a, e.b) - n_fixed, hi = std::max(e.a, e.b) - n_fixed;
     first_block[hi] = std::min(first_block[hi], lo);
   }
   Profile H;
@@ -328,7 +299,7 @@ PoseGraphResult optimize_pose_graph(const std::vector<double>& poses, const std:
     total += r - H.first[r] + 1;
   }
   std::vector<double> Hv(total), g(n), delta(n);
-  std::vector<CPose3D> Tn(K);
+  std::vector<CPose3D> Tn(T);
   double cost = graph_cost(edges, T);
   out.cost_before = cost;
   out.costs.push_back(cost);
@@ -342,16 +313,16 @@ PoseGraphResult optimize_pose_graph(const std::vector<double>& poses, const std:
       edge_residual(e, T[e.a], T[e.b], r, J[0], J[1]);
       const uint32_t node[2] = {e.a, e.b};
       for (int p = 0; p < 2; p++) {
-        if (node[p] == 0) continue;
-        const size_t rp = 6 * (node[p] - 1);
+        if (node[p] < n_fixed) continue;
+        const size_t rp = 6 * (node[p] - n_fixed);
         for (int i = 0; i < 6; i++) {
           double s = 0;
           for (int k = 0; k < 6; k++) s += J[p][k * 6 + i] * e.w[k] * r[k];
           g[rp + i] += s;
         }
         for (int q = 0; q < 2; q++) {
-          if (node[q] == 0 || node[q] > node[p]) continue;  // lower triangle: block row p, block column q <= p
-          const size_t cq = 6 * (node[q] - 1);
+          if (node[q] < n_fixed || node[q] > node[p]) continue;  // lower triangle: block row p, block column q <= p
+          const size_t cq = 6 * (node[q] - n_fixed);
           for (int i = 0; i < 6; i++)
             for (int j = 0; j < 6; j++) {
               if (p == q && j > i) continue;
@@ -382,8 +353,8 @@ PoseGraphResult optimize_pose_graph(const std::vector<double>& poses, const std:
         lambda = std::max(10.0 * lambda, 1e-6);
         continue;
       }
-      Tn[0] = T[0];
-      for (size_t v = 0; v < nb; v++) Tn[v + 1] = T[v + 1] + CPose3D::FromRotVecAndTranslation(&delta[6 * v + 3], &delta[6 * v]);
+      for (size_t v = 0; v < n_fixed; v++) Tn[v] = T[v];
+      for (size_t v = 0; v < nb; v++) Tn[v + n_fixed] = T[v + n_fixed] + CPose3D::FromRotVecAndTranslation(&delta[6 * v + 3], &delta[6 * v]);
       const double cn = graph_cost(edges, Tn);
       if (cn <= cost) {
         T.swap(Tn);
@@ -400,7 +371,125 @@ PoseGraphResult optimize_pose_graph(const std::vector<double>& poses, const std:
     if (!accepted || maxd < opt.min_step) break;
   }
   out.cost_after = cost;
+}
+
+}  // namespace
+
+PoseGraphResult optimize_pose_graph(const std::vector<double>& poses, const std::vector<PoseGraphEdge>& loops, const LoopClosureOptions& opt) {
+  if (poses.size() % 12) throw std::runtime_error("optimize_pose_graph: 12 values per pose");
+  const size_t K = poses.size() / 12;
+  for (const PoseGraphEdge& e : loops) {
+    if (e.a >= K || e.b >= K)
+      throw std::runtime_error("optimize_pose_graph: a loop edge names node " + std::to_string(std::max(e.a, e.b)) + " of " + std::to_string(K));
+    if (e.a == e.b) throw std::runtime_error("optimize_pose_graph: a loop edge from node " + std::to_string(e.a) + " to itself");
+  }
+  for (double v : poses)
+    if (!std::isfinite(v)) throw std::runtime_error("optimize_pose_graph: non-finite pose");
+  PoseGraphResult out;
+  out.poses = poses;
+  if (loops.empty() || K < 2) {  // the chain's residuals are zero by construction
+    out.costs.push_back(0.0);
+    return out;
+  }
+  std::vector<CPose3D> T(K);
+  for (size_t k = 0; k < K; k++) T[k] = pose_of(&poses[12 * k]);
+  std::vector<GraphEdge> edges;
+  edges.reserve(K - 1 + loops.size());
+  for (size_t k = 1; k < K; k++) {
+    GraphEdge e;
+    e.a = (uint32_t)(k - 1); e.b = (uint32_t)k;
+    e.Z = T[k] - T[k - 1];
+    edge_weights(opt.odometry_sigma_xyz, opt.odometry_sigma_rot_deg, e.w);
+    edges.push_back(e);
+  }
+  for (const PoseGraphEdge& l : loops) {
+    GraphEdge e;
+    e.a = l.a; e.b = l.b;
+    e.Z = pose_of(l.Z);
+    edge_weights(opt.loop_sigma_xyz, opt.loop_sigma_rot_deg, e.w);
+    edges.push_back(e);
+  }
+  solve_graph(T, 1, edges, opt, out);  // node 0 is fixed
   for (size_t k = 1; k < K; k++) std::copy(T[k].T, T[k].T + 12, &out.poses[12 * k]);
+  return out;
+}
+
+// (SessionJoin.h; here because it runs on solve_graph)
+PoseGraphResult optimize_pose_graph_anchored(const std::vector<double>& poses, size_t n_fixed, const std::vector<uint32_t>& chain_starts,
+                                             const std::vector<PoseGraphEdge>& links, const LoopClosureOptions& opt) {
+  const char* who = "optimize_pose_graph_anchored: ";
+  if (poses.size() % 12) throw std::runtime_error(std::string(who) + "12 values per pose");
+  const size_t K = poses.size() / 12;
+  if (n_fixed < 1 || n_fixed > K) throw std::runtime_error(std::string(who) + std::to_string(n_fixed) + " fixed nodes of " + std::to_string(K) + ": at least one, at most all");
+  for (double v : poses)
+    if (!std::isfinite(v)) throw std::runtime_error(std::string(who) + "non-finite pose");
+  // chain[k]: the first node of free node k's chain
+  std::vector<bool> starts(K, false);
+  if (n_fixed < K) starts[n_fixed] = true;
+  for (uint32_t c : chain_starts) {
+    if (c < n_fixed || c >= K) throw std::runtime_error(std::string(who) + "a chain cannot start at node " + std::to_string(c) + " (" + std::to_string(n_fixed) + " fixed, " + std::to_string(K) + " in all)");
+    starts[c] = true;
+  }
+  std::vector<size_t> chain(K, 0);
+  for (size_t k = n_fixed; k < K; k++) chain[k] = starts[k] ? k : chain[k - 1];
+  for (const PoseGraphEdge& e : links) {
+    if (e.a >= K || e.b >= K) throw std::runtime_error(std::string(who) + "an edge names node " + std::to_string(std::max(e.a, e.b)) + " of " + std::to_string(K));
+    if (e.a == e.b) throw std::runtime_error(std::string(who) + "an edge from node " + std::to_string(e.a) + " to itself");
+    if (e.a < n_fixed && e.b < n_fixed)
+      throw std::runtime_error(std::string(who) + "the edge (" + std::to_string(e.a) + ", " + std::to_string(e.b) + ") joins two fixed nodes");
+  }
+  opt.validate();
+  PoseGraphResult out;
+  out.poses = poses;
+  std::vector<CPose3D> T(K);
+  for (size_t k = 0; k < K; k++) T[k] = pose_of(&poses[12 * k]);
+  // ---- the chain edges, from the poses as given (a rigid placement does not change them)
+  std::vector<GraphEdge> edges;
+  for (size_t k = n_fixed + 1; k < K; k++) {
+    if (starts[k]) continue;
+    GraphEdge e;
+    e.a = (uint32_t)(k - 1); e.b = (uint32_t)k;
+    e.Z = T[k] - T[k - 1];
+    edge_weights(opt.odometry_sigma_xyz, opt.odometry_sigma_rot_deg, e.w);
+    edges.push_back(e);
+  }
+  // ---- every chain placed by its first edge from a fixed node
+  std::vector<size_t> n_edges(K, 0);  // per chain (indexed by its first node)
+  std::vector<bool> placed(K, false);
+  bool overdetermined = false;
+  for (const PoseGraphEdge& l : links) {
+    const bool a_fixed = l.a < n_fixed, b_fixed = l.b < n_fixed;
+    if (!a_fixed) n_edges[chain[l.a]]++;
+    if (!b_fixed && (a_fixed || chain[l.b] != chain[l.a])) n_edges[chain[l.b]]++;
+    if (!a_fixed && !b_fixed) overdetermined = true;
+    if (a_fixed == b_fixed) continue;
+    const size_t c = chain[a_fixed ? l.b : l.a];
+    if (placed[c]) continue;
+    placed[c] = true;
+    const CPose3D Z = pose_of(l.Z), I;
+    const CPose3D G = a_fixed ? (T[l.a] + Z) + (I - T[l.b]) : (T[l.b] + (I - Z)) + (I - T[l.a]);
+    for (size_t k = c; k < K && chain[k] == c; k++) T[k] = G + T[k];
+  }
+  for (size_t k = n_fixed; k < K; k++) {
+    if (!starts[k]) continue;
+    if (!placed[k])
+      throw std::runtime_error(std::string(who) + "the chain that starts at node " + std::to_string(k) + " has no edge from a fixed node: its frame is undetermined");
+    if (n_edges[k] > 1) overdetermined = true;
+  }
+  for (size_t k = n_fixed; k < K; k++) std::copy(T[k].T, T[k].T + 12, &out.poses[12 * k]);
+  if (!overdetermined) {  // every residual is zero by construction
+    out.costs.push_back(0.0);
+    return out;
+  }
+  for (const PoseGraphEdge& l : links) {
+    GraphEdge e;
+    e.a = l.a; e.b = l.b;
+    e.Z = pose_of(l.Z);
+    edge_weights(opt.loop_sigma_xyz, opt.loop_sigma_rot_deg, e.w);
+    edges.push_back(e);
+  }
+  solve_graph(T, n_fixed, edges, opt, out);
+  for (size_t k = n_fixed; k < K; k++) std::copy(T[k].T, T[k].T + 12, &out.poses[12 * k]);
   return out;
 }
 
@@ -585,11 +674,28 @@ struct LoopCloserCore {
 
   // verification of one pair on the device; an accepted one becomes a loop edge
   bool verify(const LoopPair& c) {
-    const std::vector<molahip_host::KeyFrame>& set_frames = *kf;
-    const size_t K = frames.size();
     LoopReport::Pair pr;
     pr.i = c.i; pr.j = c.j; pr.shift = c.shift; pr.dist = c.dist;
     const CPose3D Ti = pose_of(frames[c.i].pose), Tj = pose_of(frames[c.j].pose);
+    verify_at((*kf)[c.i], c.j, [&](size_t q) { return s[c.i] - s[q] >= opt.min_travel; }, (Ti - Tj).asTPose(), opt.sigma_xy, opt.sigma_yaw_deg, pr);
+    if (pr.accepted) {
+      PoseGraphEdge e;
+      e.a = c.j; e.b = c.i;
+      std::copy(pr.Z, pr.Z + 12, e.Z);
+      loops.push_back(e);
+    }
+    rep.pairs.push_back(pr);
+    return pr.accepted;
+  }
+
+  // The verification itself: `observed` (a frame with points, of this set or of another) against the submap around frame j -- the
+  // frames q with points, |s_q - s_j| <= submap_radius and keep(q), at T_j^-1 T_q -- from the grid of (sigma_xy, sigma_yaw_deg)
+  // around `centre`, the guess of the observed frame in frame j.  Fills pr's candidates, ranks, quality, iterations, Z and accepted.
+  void verify_at(const molahip_host::KeyFrame& observed, size_t j, const std::function<bool(size_t)>& keep, const TPose3D& centre, double sigma_xy,
+                 double sigma_yaw_deg, LoopReport::Pair& pr) {
+    const std::vector<molahip_host::KeyFrame>& set_frames = *kf;
+    const size_t K = frames.size();
+    const CPose3D Tj = pose_of(frames[j].pose);
     metric_map_t glob, obs;
     {
       Stage st(rep, "submap");
@@ -602,7 +708,7 @@ struct LoopCloserCore {
         auto map = make_local_map(empty, ctx);
         std::vector<PosedFrame> pf;
         for (size_t q = 0; q < K; q++) {
-          if (!frames[q].has_points || !(std::fabs(s[q] - s[c.j]) <= opt.submap_radius) || !(s[c.i] - s[q] >= opt.min_travel)) continue;
+          if (!frames[q].has_points || !(std::fabs(s[q] - s[j]) <= opt.submap_radius) || !keep(q)) continue;
           for (const auto& l : set_frames[q].layers) {  // step order
             if (l.map_index != k) continue;
             PosedFrame f;
@@ -617,7 +723,7 @@ struct LoopCloserCore {
       }
       for (const auto& [name, k] : layers.local_layers) {
         std::vector<float> x, y, z;
-        for (const auto& l : set_frames[c.i].layers) {
+        for (const auto& l : observed.layers) {
           if ((int)l.map_index != k) continue;
           x.insert(x.end(), l.x.begin(), l.x.end());
           y.insert(y.end(), l.y.begin(), l.y.end());
@@ -632,7 +738,7 @@ struct LoopCloserCore {
     // the variables of this frame
     double range = 0.0;
     {
-      const auto& l = set_frames[c.i].layers[0];
+      const auto& l = observed.layers[0];
       for (size_t p = 0; p < l.x.size(); p++) {
         const double x = l.x[p], y = l.y[p], z = l.z[p], r2 = x * x + y * y + z * z;
         if (std::isfinite(r2)) range = std::max(range, r2);
@@ -648,10 +754,9 @@ struct LoopCloserCore {
     }
     const double step = reloc.step_xy > 0 ? reloc.step_xy : thr;
     double cov[36] = {0};
-    cov[0] = cov[7] = opt.sigma_xy * opt.sigma_xy;
-    cov[21] = (opt.sigma_yaw_deg * kDeg2Rad) * (opt.sigma_yaw_deg * kDeg2Rad);
-    const std::vector<TPose3D> cand =
-        relocalization_grid((Ti - Tj).asTPose(), cov, step, reloc.step_yaw_deg * kDeg2Rad, reloc.sigmas, reloc.max_candidates);
+    cov[0] = cov[7] = sigma_xy * sigma_xy;
+    cov[21] = (sigma_yaw_deg * kDeg2Rad) * (sigma_yaw_deg * kDeg2Rad);
+    const std::vector<TPose3D> cand = relocalization_grid(centre, cov, step, reloc.step_yaw_deg * kDeg2Rad, reloc.sigmas, reloc.max_candidates);
     pr.candidates = (uint32_t)cand.size();
     const RelocalizationRefinement rr =
         score_rank_refine(*icp, icp_params, obs, glob, layers.gname, layers.lname, cand, thr, reloc.refine_top_k, &rep.seconds);
@@ -664,14 +769,6 @@ struct LoopCloserCore {
       std::copy(rr.best.optimal_tf.mean.T, rr.best.optimal_tf.mean.T + 12, pr.Z);
       pr.accepted = rr.best.quality >= opt.min_quality;
     }
-    if (pr.accepted) {
-      PoseGraphEdge e;
-      e.a = c.j; e.b = c.i;
-      std::copy(pr.Z, pr.Z + 12, e.Z);
-      loops.push_back(e);
-    }
-    rep.pairs.push_back(pr);
-    return pr.accepted;
   }
 
   // one optimisation over all frames, from their recorded (raw) poses and every loop edge so far
@@ -690,6 +787,38 @@ struct LoopCloserCore {
     return std::move(g.poses);
   }
 };
+
+// ================================================================== the verification lent to session_join.cpp
+PairVerifier::PairVerifier(const std::vector<molahip_host::KeyFrameTarget>& maps, const Config& pipeline, std::shared_ptr<DeviceContext> ctx,
+                           const std::string& who)
+    : core_(std::make_unique<LoopCloserCore>(maps, pipeline, std::move(ctx), who)) {}
+PairVerifier::~PairVerifier() = default;
+void PairVerifier::setMapFrames(const std::vector<molahip_host::KeyFrame>& frames) {
+  LoopCloserCore& c = *core_;
+  c.kf = &frames;
+  c.frames.assign(frames.size(), LoopFrame());
+  for (size_t k = 0; k < frames.size(); k++) {
+    std::copy(frames[k].pose, frames[k].pose + 12, c.frames[k].pose);
+    c.frames[k].has_points = mola_hip::usable(frames[k]);
+  }
+  c.s = path_lengths(c.frames);
+}
+const std::vector<LoopFrame>& PairVerifier::mapFrames() const { return core_->frames; }
+void PairVerifier::verify(const molahip_host::KeyFrame& observed, size_t j, const TPose3D& centre, double sigma_xy, double sigma_yaw_deg,
+                          LoopReport::Pair& pr) {
+  core_->verify_at(observed, j, [](size_t) { return true; }, centre, sigma_xy, sigma_yaw_deg, pr);
+}
+const LoopClosureOptions& PairVerifier::options() const { return core_->opt; }
+const LidarOdometry::RelocalizationOptions& PairVerifier::relocalization() const { return core_->reloc; }
+const mh_place_params& PairVerifier::placeParams() const { return core_->pp; }
+const std::shared_ptr<DeviceContext>& PairVerifier::context() const { return core_->ctx; }
+LoopReport& PairVerifier::report() { return core_->rep; }
+bool PairVerifier::usable(const molahip_host::KeyFrame& f) { return mola_hip::usable(f); }
+void PairVerifier::checkWithoutDevice(const std::vector<molahip_host::KeyFrameTarget>& maps, const Config& pipeline, const std::string& who) {
+  (void)LoopClosureOptions::FromConfig(pipeline);
+  (void)relocalization_options(pipeline);
+  refuse_unbuildable_targets(maps, who);
+}
 
 // ================================================================== close_loops
 LoopClosureResult close_loops(const molahip_host::KeyFrameSet& set, const Config& pipeline, std::shared_ptr<DeviceContext> ctx) {

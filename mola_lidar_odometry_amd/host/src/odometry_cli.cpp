@@ -43,6 +43,7 @@
 
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
 #include "mola_lidar_odometry_hip/LoopClosure.h"
+#include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "molahip.h"
 
 namespace {
@@ -326,11 +327,13 @@ int main(int argc, char** argv) {
   bool print_profile = false, plan_only = false;
   std::string build_from;  // --build-session-map
   std::string close_from, loop_report;  // --close-loops, --loop-report
+  std::vector<std::string> join_files;  // --join-sessions A B
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
                       "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE] [--relocalize-in-keyframes]\n"
                       "       molahip-lo-cli --build-session-map KEYFRAMES --save-local-map FILE [--device N]\n"
                       "       molahip-lo-cli --close-loops KEYFRAMES --pipeline FILE.yaml --output-simplemap FILE [--output-session-map FILE] [--loop-report FILE.json] [--device N]\n"
+                      "       molahip-lo-cli --join-sessions KEYFRAMES_A KEYFRAMES_B --pipeline FILE.yaml --output-simplemap FILE [--output-session-map FILE] [--loop-report FILE.json] [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
@@ -343,6 +346,10 @@ int main(int argc, char** argv) {
                       "  --close-loops: no sequence is run: revisits among the key-frames of KEYFRAMES are detected, verified on the device and closed\n"
                       "  (the pipeline's loop_closure: block); the key-frames with corrected poses go to --output-simplemap's FILE, the maps built from\n"
                       "  them to --output-session-map's, the report (pairs tried, qualities, optimiser cost, stage times) to --loop-report's\n"
+                      "  --join-sessions: no sequence is run: the drive of KEYFRAMES_B is found in the one of KEYFRAMES_A (place recognition, links verified\n"
+                      "  on the device; the pipeline's session_join: block) and its key-frames are put into A's frame; A's key-frames and then B's go to\n"
+                      "  --output-simplemap's FILE, the maps built from them to --output-session-map's, the report to --loop-report's; when the sessions\n"
+                      "  cannot be joined nothing is written and the exit status is 1\n"
                       "  --relocalize-in-keyframes: the vehicle is found in a saved session without a prior pose: place recognition over the\n"
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
@@ -381,6 +388,10 @@ int main(int argc, char** argv) {
       else if (a == "--build-session-map") build_from = val("--build-session-map");
       else if (a == "--close-loops") close_from = val("--close-loops");
       else if (a == "--loop-report") loop_report = val("--loop-report");
+      else if (a == "--join-sessions") {
+        join_files.push_back(val("--join-sessions"));
+        join_files.push_back(val("--join-sessions"));
+      }
       else if (a == "--relocalize-in-keyframes") opt.relocalize_in_keyframes = true;
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
@@ -390,6 +401,43 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n%s", e.what(), usage);
       return 2;
     }
+  }
+  if (!join_files.empty()) {  // two recorded drives put into one frame, no sequence
+    if (join_files.size() != 2 || pipeline.empty() || opt.output_simplemap.empty() || !seq_dirs.empty() || !build_from.empty() || !close_from.empty()) {
+      fprintf(stderr, "--join-sessions takes two key-frame files once, needs --pipeline FILE and --output-simplemap FILE and takes no sequence\n%s", usage);
+      return 2;
+    }
+    try {
+      auto ctx = std::make_shared<mp2p_icp_hip::DeviceContext>(devices.empty() ? 0 : devices[0]);
+      const mola_hip::SessionJoinResult r = mola_hip::join_sessions(molahip_host::read_keyframe_file(join_files[0]), molahip_host::read_keyframe_file(join_files[1]),
+                                                                    mp2p_icp_hip::Config::FromYamlFile(pipeline), ctx);
+      const std::string json = r.report.toJson();
+      if (!loop_report.empty()) {
+        FILE* f = fopen(loop_report.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + loop_report);
+        fputs(json.c_str(), f);
+        fclose(f);
+      } else {
+        fputs(json.c_str(), stdout);
+      }
+      if (r.is_joined) {
+        molahip_host::write_keyframe_file(opt.output_simplemap, r.joined);
+        if (!opt.output_session_map.empty()) mola_hip::build_session_map_file(r.joined, opt.output_session_map, ctx);
+      }
+      printf("{\"keyframe_files\": [\"%s\", \"%s\"], \"frames\": %zu, \"pairs_tried\": %zu, \"links_accepted\": %u, \"joined\": %s, \"cost_before\": %.9g, "
+             "\"cost_after\": %.9g, \"optimizer_iterations\": %u, \"output_simplemap\": \"%s\"}\n",
+             join_files[0].c_str(), join_files[1].c_str(), r.joined.frames.size(), r.report.pairs.size(), r.report.links_accepted, r.is_joined ? "true" : "false",
+             r.report.cost_before, r.report.cost_after, r.report.optimizer_iterations, r.is_joined ? opt.output_simplemap.c_str() : "");
+      if (!r.is_joined) {
+        fprintf(stderr, "molahip-lo-cli: the sessions were not joined: %u accepted links (the pipeline's session_join: min_links decides); nothing written\n",
+                r.report.links_accepted);
+        return 1;
+      }
+    } catch (const std::exception& e) {
+      fprintf(stderr, "molahip-lo-cli: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (!close_from.empty()) {  // the loops of a recorded drive closed, no sequence
     if (pipeline.empty() || opt.output_simplemap.empty() || !seq_dirs.empty() || !build_from.empty()) {

@@ -8,6 +8,7 @@
 
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
 #include "mola_lidar_odometry_hip/LoopClosure.h"
+#include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 #include "molahip_host/plugin_switches.h"
 
@@ -938,6 +939,151 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         rep["optimizer_iterations"] = r.optimizer_iterations; rep["seconds"] = r.seconds; rep["counts"] = r.counts;
         rep["json"] = r.toJson();
         return rep; });
+  // ---- two sessions joined (mola_lidar_odometry_hip/SessionJoin.h)
+  using mola_hip::SessionJoinOptions;
+  // the session_join: block of a pipeline Config as a dict (an absent block: the defaults)
+  m.def("session_join_options", [](const Config& c) {
+    const SessionJoinOptions o = SessionJoinOptions::FromConfig(c);
+    py::dict d;
+    d["top_k"] = o.top_k; d["max_place_dist"] = o.max_place_dist; d["min_links"] = o.min_links;
+    d["min_travel_between_links"] = o.min_travel_between_links; d["max_anchor_frames"] = o.max_anchor_frames;
+    return d; });
+  auto dict2jopts = [](const py::dict& d) {
+    SessionJoinOptions o;
+    auto cnt = [&](const char* k, uint32_t& v) { if (d.contains(k)) v = d[k].cast<uint32_t>(); };
+    cnt("top_k", o.top_k); cnt("max_place_dist", o.max_place_dist); cnt("min_links", o.min_links); cnt("max_anchor_frames", o.max_anchor_frames);
+    if (d.contains("min_travel_between_links")) o.min_travel_between_links = d["min_travel_between_links"].cast<double>();
+    o.validate();
+    return o;
+  };
+  auto frames_of = [](py::array_t<double, py::array::c_style | py::array::forcecast> poses, const std::vector<bool>& has_points, const char* what) {
+    if (poses.ndim() != 2 || poses.shape(1) != 12) throw std::runtime_error(std::string(what) + ": poses must be [K, 12]");
+    const size_t K = (size_t)poses.shape(0);
+    if (has_points.size() != K) throw std::runtime_error(std::string(what) + ": has_points needs one entry per pose");
+    std::vector<mola_hip::LoopFrame> frames(K);
+    for (size_t k = 0; k < K; k++) {
+      std::copy(poses.data() + 12 * k, poses.data() + 12 * k + 12, frames[k].pose);
+      frames[k].has_points = has_points[k];
+    }
+    return frames;
+  };
+  // the rule's verification as a Python callable: accept(b, j, shift, dist, phase, centre [12]) -> None (rejected) or Z (12 values)
+  auto join_verify = [](const py::object& accept) {
+    mola_hip::JoinVerify verify;
+    if (!accept.is_none())
+      verify = [&accept](const mola_hip::JoinPair& p, double Z[12]) {
+        const py::object r = accept(p.b, p.j, p.shift, p.dist, p.phase, std::vector<double>(p.centre, p.centre + 12));
+        if (r.is_none()) return false;
+        const std::vector<double> z = r.cast<std::vector<double>>();
+        if (z.size() != 12) throw std::runtime_error("accept must return None or the 12 values of Z");
+        std::copy(z.begin(), z.end(), Z);
+        return true;
+      };
+    return verify;
+  };
+  auto jpair2tuple = [](const mola_hip::JoinPair& p) {
+    return py::make_tuple(p.b, p.j, p.shift, p.dist, p.phase, std::vector<double>(p.centre, p.centre + 12));
+  };
+  auto jlink2tuple = [](const mola_hip::JoinLink& l) { return py::make_tuple(l.b, l.j, std::vector<double>(l.Z, l.Z + 12)); };
+  // the whole candidate rule on host arrays: A's poses [KA, 12] and has_points, B's poses [KB, 12], has_points and match lists
+  // (matches_b[b] = [(A frame, shift, dist)], ranked), options: session_join: keys (top_k resolved, >= 1) plus gate_base, gate_rate
+  // and place_sectors.  -> (tried [(b, j, shift, dist, phase, centre)], links [(b, j, Z)])
+  m.def("join_candidates", [dict2jopts, dict2opts, frames_of, join_verify, jpair2tuple, jlink2tuple](
+                               py::array_t<double, py::array::c_style | py::array::forcecast> poses_a, const std::vector<bool>& has_a,
+                               py::array_t<double, py::array::c_style | py::array::forcecast> poses_b, const std::vector<bool>& has_b,
+                               const std::vector<std::vector<std::tuple<uint32_t, uint32_t, uint32_t>>>& matches_b, const py::dict& options,
+                               const py::object& accept) {
+    const std::vector<mola_hip::LoopFrame> A = frames_of(poses_a, has_a, "A");
+    std::vector<mola_hip::LoopFrame> B = frames_of(poses_b, has_b, "B");
+    if (matches_b.size() != B.size()) throw std::runtime_error("matches_b needs one entry per B pose");
+    for (size_t b = 0; b < B.size(); b++)
+      for (const auto& [f, s, d] : matches_b[b]) {
+        if (f >= A.size()) throw std::runtime_error("a match names frame " + std::to_string(f) + " of " + std::to_string(A.size()));
+        B[b].matches.push_back(mola_hip::PlaceIndex::Match{f, s, d});
+      }
+    const SessionJoinOptions o = dict2jopts(options);
+    const uint32_t sectors = options.contains("place_sectors") ? options["place_sectors"].cast<uint32_t>() : 64u;
+    const mola_hip::JoinCandidates c = mola_hip::join_candidates(A, B, o, o.top_k, sectors, dict2opts(options), join_verify(accept));
+    py::list tried, links;
+    for (const auto& p : c.tried) tried.append(jpair2tuple(p));
+    for (const auto& l : c.links) links.append(jlink2tuple(l));
+    return py::make_tuple(tried, links); },
+        py::arg("poses_a"), py::arg("has_points_a"), py::arg("poses_b"), py::arg("has_points_b"), py::arg("matches_b"), py::arg("options") = py::dict(),
+        py::arg("accept") = py::none());
+  // the link rule for ONE frame b of a sweep: `matches` is frame b's list, carried = (b', j', Z') -> (tried, accepted, carried)
+  m.def("join_candidates_step", [dict2jopts, dict2opts, frames_of, join_verify, jpair2tuple, jlink2tuple](
+                                    py::array_t<double, py::array::c_style | py::array::forcecast> poses_a, const std::vector<bool>& has_a,
+                                    py::array_t<double, py::array::c_style | py::array::forcecast> poses_b, const std::vector<bool>& has_b, size_t b,
+                                    uint32_t phase, const std::vector<std::tuple<uint32_t, uint32_t, uint32_t>>& matches, const py::dict& options,
+                                    const std::tuple<uint32_t, uint32_t, std::vector<double>>& carried, const py::object& accept) {
+    const std::vector<mola_hip::LoopFrame> A = frames_of(poses_a, has_a, "A");
+    std::vector<mola_hip::LoopFrame> B = frames_of(poses_b, has_b, "B");
+    mola_hip::JoinLink link;
+    link.b = std::get<0>(carried); link.j = std::get<1>(carried);
+    if (b >= B.size() || link.b >= B.size() || link.j >= A.size() || std::get<2>(carried).size() != 12)
+      throw std::runtime_error("join_candidates_step: b, or the carried link, names a frame that is not there");
+    std::copy(std::get<2>(carried).begin(), std::get<2>(carried).end(), link.Z);
+    for (const auto& [f, s, d] : matches) B[b].matches.push_back(mola_hip::PlaceIndex::Match{f, s, d});
+    const SessionJoinOptions o = dict2jopts(options);
+    std::vector<mola_hip::JoinPair> tried;
+    const bool accepted = mola_hip::join_candidates_step(A, B, mola_hip::path_lengths(B), b, phase, o, o.top_k, dict2opts(options), link, join_verify(accept), tried);
+    py::list out;
+    for (const auto& p : tried) out.append(jpair2tuple(p));
+    return py::make_tuple(out, accepted, jlink2tuple(link)); },
+        py::arg("poses_a"), py::arg("has_points_a"), py::arg("poses_b"), py::arg("has_points_b"), py::arg("b"), py::arg("phase"), py::arg("matches"),
+        py::arg("options"), py::arg("carried"), py::arg("accept") = py::none());
+  // poses [K, 12], the first n_fixed fixed; chain_starts; edges = [(a, b, Z: 12 values, node b in node a)]; the weights and the stop
+  // as a dict of loop_closure: keys.  -> {poses [K, 12], cost_before, cost_after, iterations, costs}
+  m.def("optimize_pose_graph_anchored", [dict2opts](py::array_t<double, py::array::c_style | py::array::forcecast> poses, size_t n_fixed,
+                                                    const std::vector<uint32_t>& chain_starts,
+                                                    const std::vector<std::tuple<uint32_t, uint32_t, std::vector<double>>>& edges_in, const py::dict& options) {
+    if (poses.ndim() != 2 || poses.shape(1) != 12) throw std::runtime_error("poses must be [K, 12]");
+    std::vector<mola_hip::PoseGraphEdge> edges;
+    for (const auto& [a, b, Z] : edges_in) {
+      if (Z.size() != 12) throw std::runtime_error("an edge's Z needs 12 values");
+      mola_hip::PoseGraphEdge e;
+      e.a = a; e.b = b;
+      std::copy(Z.begin(), Z.end(), e.Z);
+      edges.push_back(e);
+    }
+    const std::vector<double> in(poses.data(), poses.data() + poses.size());
+    const LoopClosureOptions o = dict2opts(options);
+    mola_hip::PoseGraphResult r;
+    {
+      py::gil_scoped_release nogil;
+      r = mola_hip::optimize_pose_graph_anchored(in, n_fixed, chain_starts, edges, o);
+    }
+    py::array_t<double> P({poses.shape(0), (py::ssize_t)12});
+    std::copy(r.poses.begin(), r.poses.end(), P.mutable_data());
+    py::dict d;
+    d["poses"] = P; d["cost_before"] = r.cost_before; d["cost_after"] = r.cost_after; d["iterations"] = r.iterations; d["costs"] = r.costs;
+    return d; }, py::arg("poses"), py::arg("n_fixed"), py::arg("chain_starts"), py::arg("edges"), py::arg("options") = py::dict());
+  // two key-frame sets (dicts as close_loops takes them, or paths of key-frame files) and the whole pipeline Config -> (joined set as
+  // a dict, is_joined, report); with `output_keyframe_file` the joined set is also written there when the sessions are joined
+  m.def("join_sessions", [dict2kfset, kfset2dict](const py::object& a, const py::object& b, const Config& pipeline, const std::string& output_keyframe_file) {
+    auto load = [&](const py::object& f) {
+      return py::isinstance<py::str>(f) ? molahip_host::read_keyframe_file(f.cast<std::string>()) : dict2kfset(f.cast<py::dict>());
+    };
+    const molahip_host::KeyFrameSet A = load(a), B = load(b);
+    mola_hip::SessionJoinResult r;
+    {
+      py::gil_scoped_release nogil;
+      r = mola_hip::join_sessions(A, B, pipeline);
+      if (r.is_joined && !output_keyframe_file.empty()) molahip_host::write_keyframe_file(output_keyframe_file, r.joined);
+    }
+    py::dict rep;
+    py::list pairs;
+    for (const auto& p : r.report.pairs) {
+      py::dict d;
+      d["i"] = p.i; d["j"] = p.j; d["phase"] = p.phase; d["shift"] = p.shift; d["dist"] = p.dist; d["candidates"] = p.candidates; d["ranks"] = p.ranks;
+      d["quality"] = p.quality; d["iterations"] = p.iterations; d["accepted"] = p.accepted; d["Z"] = std::vector<double>(p.Z, p.Z + 12);
+      pairs.append(d);
+    }
+    rep["pairs"] = pairs; rep["links_accepted"] = r.report.links_accepted; rep["joined"] = r.report.joined; rep["cost_before"] = r.report.cost_before;
+    rep["cost_after"] = r.report.cost_after; rep["optimizer_iterations"] = r.report.optimizer_iterations; rep["seconds"] = r.report.seconds;
+    rep["counts"] = r.report.counts; rep["json"] = r.report.toJson();
+    return py::make_tuple(kfset2dict(r.joined), r.is_joined, rep); },
+        py::arg("a"), py::arg("b"), py::arg("pipeline"), py::arg("output_keyframe_file") = "");
   // the pose rules of the driver's online loop closure and the motion model's rebase, on 12-value poses
   auto to_pose = [](const std::vector<double>& T) {
     if (T.size() != 12) throw std::runtime_error("a pose has 12 values");
