@@ -330,7 +330,11 @@ MH_API mh_status mh_scan_set_intensity(mh_scan* scan, const float* i, size_t n, 
 /* raw -> decimate(map res) -> by-range -> bounding box -> out_map -> decimate(icp res) -> out_icp (may be NULL).
  * Survivors keep the raw order (upstream's FirstPoint decimation emits them in the iteration order of its hash
  * container, which is implementation-defined: same set, deterministic order here).  The outputs carry adjusted
- * time stamps (when `raw` has them) and each point's index in `raw`; they are the *_skewed layers. */
+ * time stamps (when `raw` has them) and each point's index in `raw`; they are the *_skewed layers.
+ * A finite point with |coordinate / resolution| >= 1e6 on any axis does not fit the packed voxel key of a decimation:
+ * a stage that decimates leaves it out, and the call returns MH_ERR_OUT_OF_RANGE with both outputs complete -- the
+ * chain's result for the scan without such points.  A stage that does not decimate (resolution 0, or an input below
+ * min_points_to_filter) passes the point like any other, and a non-finite point raises nothing. */
 MH_API mh_status mh_scan_preprocess(const mh_scan* raw, const mh_preprocess_params* params, mh_scan* out_map,
                                     mh_scan* out_icp);
 /* The same chain for the scans of several sequences at once: every step is ONE launch over all of them, issued on the
@@ -338,7 +342,9 @@ MH_API mh_status mh_scan_preprocess(const mh_scan* raw, const mh_preprocess_para
  * brings all counts -- N sequences in one process cost the host one sequence's launches (the callers' threads contend
  * for the runtime otherwise).  `params` is an array with `params_stride` bytes between entries (0: one set for all);
  * `out_icps` may be NULL, or hold NULL entries.  Outputs are those of n_jobs separate mh_scan_preprocess calls, bit for
- * bit.  Each job's three scans belong to one context; the contexts may differ from job to job (same device). */
+ * bit.  Each job's three scans belong to one context; the contexts may differ from job to job (same device).
+ * When a job has a point outside the key range (see mh_scan_preprocess) the call returns MH_ERR_OUT_OF_RANGE; the
+ * outputs of every job, that one included, are complete and equal to those of their single calls. */
 MH_API mh_status mh_scan_preprocess_batch(size_t n_jobs, const mh_scan* const* raws, const mh_preprocess_params* params,
                                           size_t params_stride, mh_scan* const* out_maps, mh_scan* const* out_icps);
 /* FilterDeskew (yaml:328-350): p' = Exp_SO3(w*t_i)*p + v*t_i with twist = (vx,vy,vz,wx,wy,wz) in the vehicle frame,

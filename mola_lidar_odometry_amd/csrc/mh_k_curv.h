@@ -1,6 +1,6 @@
 // mh_k_curv.h -- FilterCurvature [U] on the device (included by mh_preprocess.hip; semantics in include/molahip.h at
 // mh_scan_curvature): a three-point stencil that sorts every interior point into one of three classes, then an ordered
-// three-way compaction.  Same flag -> position -> compact shape as k_pp_flag / k_pp_compact, with ONE scan for the three
+// three-way compaction.  Same flag -> position -> compact shape as k_pp_flag_b / k_pp_compact_b, with ONE scan for the three
 // outputs: each point contributes a 64-bit word holding a 1 in the 21-bit field of its class, so the exclusive scan of
 // those words gives every point its place in its own output, and the scan's total gives the three counts.
 #pragma once

@@ -12,7 +12,7 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t merge_ord(float f) {  // (f2ord of k_pp_tminmax)
+__device__ __forceinline__ uint32_t merge_ord(float f) {  // (f2ord of k_pp_tminmax_b)
   const uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_merge_fill(const MergeTable* __restrict
   if (ot) {
     float tv = mh::G(s.t)[j];
     const int32_t method = s.method;
-    if (method != MH_TS_NONE) {  // FilterAdjustTimestamps over THIS source's stamps (k_pp_compact's arithmetic)
+    if (method != MH_TS_NONE) {  // FilterAdjustTimestamps over THIS source's stamps (k_pp_compact_b's arithmetic)
       const float tmin = merge_unord(tab->mm[k][0]), tmax = merge_unord(tab->mm[k][1]);
       const float dt = method == MH_TS_MIDDLE_IS_ZERO ? 0.5f * (tmin + tmax) : tmin;
       tv = (tv - dt) + s.offset;

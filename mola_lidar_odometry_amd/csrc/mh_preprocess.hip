@@ -55,32 +55,6 @@ __device__ __forceinline__ float ord2f(uint32_t u) {
   return __uint_as_float(u);
 }
 
-// counters[0] = min(t), counters[1] = max(t) as order-preserving uints.  Grid-stride over a fixed, small grid: one
-// pair of atomics per workgroup (one per wave serialised ~2 k same-address atomics: 44 us for a 120 k-point scan)
-__global__ __launch_bounds__(256) void k_pp_tminmax(const float* __restrict__ t, uint32_t n, uint32_t* __restrict__ counters) {
-  __shared__ uint32_t smn[4], smx[4];
-  uint32_t mn = 0xFFFFFFFFu, mx = 0u;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const uint32_t o = f2ord(t[i]);
-    mn = min(mn, o);
-    mx = max(mx, o);
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    mn = min(mn, (uint32_t)__shfl_xor((int)mn, off));
-    mx = max(mx, (uint32_t)__shfl_xor((int)mx, off));
-  }
-  if ((threadIdx.x & 63) == 0) { smn[threadIdx.x >> 6] = mn; smx[threadIdx.x >> 6] = mx; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    mn = min(min(smn[0], smn[1]), min(smn[2], smn[3]));
-    mx = max(max(smx[0], smx[1]), max(smx[2], smx[3]));
-    if (mn != 0xFFFFFFFFu) {
-      atomicMin(&counters[0], mn);
-      atomicMax(&counters[1], mx);
-    }
-  }
-}
-
 __device__ __forceinline__ bool pp_key(float px, float py, float pz, float inv, uint32_t trunc, unsigned long long& key,
                                        uint32_t* __restrict__ counters) {
   if (!(isfinite(px) && isfinite(py) && isfinite(pz))) return false;
@@ -93,81 +67,7 @@ __device__ __forceinline__ bool pp_key(float px, float py, float pz, float inv, 
   return true;
 }
 
-// FirstPoint decimation, pass 1: every point claims its voxel's table entry and records the smallest point index
-__global__ void k_pp_insert(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-                            uint32_t n, float inv, uint32_t trunc, unsigned long long* __restrict__ keys,
-                            uint32_t* __restrict__ first_idx, uint32_t mask, uint32_t* __restrict__ counters) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  unsigned long long key;
-  if (!pp_key(x[i], y[i], z[i], inv, trunc, key, counters)) return;
-  uint32_t h = hash_key(key) & mask;
-  for (;;) {
-    const unsigned long long old = atomicCAS(&keys[h], kEmptyKey, key);
-    if (old == kEmptyKey || old == key) break;
-    h = (h + 1) & mask;
-  }
-  atomicMin(&first_idx[h], i);
-}
-
-// pass 2: flag = first point of its voxel (when decimating) && FilterByRange && FilterBoundingBox
-__global__ void k_pp_flag(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-                          uint32_t n, StageParams sp, const unsigned long long* __restrict__ keys,
-                          const uint32_t* __restrict__ first_idx, uint32_t mask, uint32_t* __restrict__ counters,
-                          uint32_t* __restrict__ flag, uint32_t count_slot) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool valid = i < n;
-  const float px = valid ? x[i] : 0.f, py = valid ? y[i] : 0.f, pz = valid ? z[i] : 0.f;
-  bool keep = valid && isfinite(px) && isfinite(py) && isfinite(pz);
-  if (keep && sp.decimate) {
-    unsigned long long key;
-    keep = pp_key(px, py, pz, sp.inv_res, sp.trunc, key, counters);
-    if (keep) {
-      uint32_t h = hash_key(key) & mask;
-      while (keys[h] != key) h = (h + 1) & mask;  // inserted by pass 1
-      keep = first_idx[h] == i;
-    }
-  }
-  if (keep && sp.range_on) {
-    const float dx = px - sp.cx, dy = py - sp.cy, dz = pz - sp.cz;
-    const float sq = (dx * dx + dy * dy) + dz * dz;
-    keep = sq >= sp.sq_min && sq <= sp.sq_max;
-  }
-  if (keep && sp.bbox_mode) {
-    const bool inside = px >= sp.bmin[0] && px <= sp.bmax[0] && py >= sp.bmin[1] && py <= sp.bmax[1] &&
-                        pz >= sp.bmin[2] && pz <= sp.bmax[2];
-    keep = inside == (sp.bbox_mode == MH_BBOX_KEEP_INSIDE);
-  }
-  if (valid) flag[i] = keep ? 1u : 0u;
-  const unsigned long long kept = __ballot(keep);  // survivor count: one atomic per wavefront
-  if ((threadIdx.x & 63) == 0 && kept) atomicAdd(&counters[count_slot], (uint32_t)__popcll(kept));
-}
-
-__global__ void k_pp_compact(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
-                             const float* __restrict__ t, const uint32_t* __restrict__ src, uint32_t n,
-                             const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos, int32_t ts_method,
-                             float ts_offset, const uint32_t* __restrict__ counters, float* __restrict__ ox,
-                             float* __restrict__ oy, float* __restrict__ oz, float* __restrict__ ot,
-                             uint32_t* __restrict__ osrc) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || !flag[i]) return;
-  const uint32_t o = pos[i];
-  ox[o] = x[i];
-  oy[o] = y[i];
-  oz[o] = z[i];
-  if (ot) {
-    float tv = t[i];
-    if (ts_method != MH_TS_NONE) {  // FilterAdjustTimestamps over ALL raw points (it runs before the decimation)
-      const float tmin = ord2f(counters[0]), tmax = ord2f(counters[1]);
-      const float dt = ts_method == MH_TS_MIDDLE_IS_ZERO ? 0.5f * (tmin + tmax) : tmin;
-      tv = (tv - dt) + ts_offset;
-    }
-    ot[o] = tv;
-  }
-  osrc[o] = src ? src[i] : i;
-}
-
-// The same for a layer one workgroup can walk (what the sensor-range estimate reads every scan: the ~1 k-point ICP
+// The bounding box of a layer one workgroup can walk (what the sensor-range estimate reads every scan: the ~1 k-point ICP
 // layer): no counters to initialise, no atomics, and the seven words go straight to page-locked HOST memory -- one
 // launch and one wait instead of an upload, a launch, a download and a wait.
 __global__ __launch_bounds__(1024) void k_pp_bbox_one(const float* __restrict__ x, const float* __restrict__ y,
@@ -417,6 +317,8 @@ __global__ __launch_bounds__(256) void k_pp_init_b(const PpJob* __restrict__ job
   }
 }
 
+// counters[0] = min(t), counters[1] = max(t) as order-preserving uints.  Grid-stride over a fixed, small grid: one
+// pair of atomics per workgroup (one per wave serialised ~2 k same-address atomics: 44 us for a 120 k-point scan)
 __global__ __launch_bounds__(256) void k_pp_tminmax_b(const PpJob* __restrict__ jobs) {
   const PpJob& j = jobs[blockIdx.y];
   if (!j.t || j.s1.ts_method == MH_TS_NONE) return;
@@ -462,6 +364,7 @@ __device__ __forceinline__ void pp_stage_view(const PpJob& j, const float*& x, c
   }
 }
 
+// decimation, pass 1: every point claims its voxel's table entry and records the smallest point index
 template <int STAGE>
 __global__ __launch_bounds__(256) void k_pp_insert_b(const PpJob* __restrict__ jobs) {
   const PpJob& j = jobs[blockIdx.y];
@@ -496,6 +399,7 @@ __global__ __launch_bounds__(256) void k_pp_insert_b(const PpJob* __restrict__ j
   (void)__hip_atomic_fetch_min(&G(first)[h], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// pass 2: flag = the point the table names for its voxel (when decimating) && FilterByRange && FilterBoundingBox
 template <int STAGE>
 __global__ __launch_bounds__(256) void k_pp_flag_b(const PpJob* __restrict__ jobs, uint32_t* __restrict__ flag) {
   const PpJob& j = jobs[blockIdx.y];

@@ -27,7 +27,9 @@ for case in range(n_cases):
     for _ in range(int(rng.integers(0, 4))):
         if n:
             xyz[int(rng.integers(0, n))] = [np.nan, 1, 1] if rng.integers(0, 2) else [1, -np.inf, 1]
-    t = (1.7e4 + np.sort(rng.uniform(0.0, 0.1, n))).astype(np.float32)
+    # every other case: stamps relative to mid-sweep, U(-0.05, 0.05), as real drivers deliver them (the negative branch of the
+    # min / max reduction's ordered-uint image); the others: absolute stamps
+    t = ((-0.05 if case % 2 else 1.7e4) + np.sort(rng.uniform(0.0, 0.1, n))).astype(np.float32)
     pp = dict(decim_map_resolution=float(rng.choice([0.0, 0.2, 0.35, 1.0])), decim_icp_resolution=float(rng.choice([0.0, 0.7, 1.1, 2.0])),
               min_points_to_filter=int(rng.choice([0, 300, 2000, 10 ** 7])), range_min=float(rng.choice([0.0, 2.0, 5.0])),
               range_max=float(rng.choice([0.0, 30.0, 70.0])), bbox_mode=int(rng.integers(0, 3)),

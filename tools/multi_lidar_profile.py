@@ -1,6 +1,6 @@
 """The run behind profiles/multi_lidar.md: a two-LiDAR rig drive (tests/multi_lidar_inline.py: 2 x 9600 points per group)
 through onLidarFrom, then one unsplit 19 200-point scan through onLidar on the same text (the rig path adjusts its stamps in
-the merge and never launches k_pp_tminmax).  Prints the host stage times per group.  For kernel durations run it under
+the merge and never launches k_pp_tminmax_b).  Prints the host stage times per group.  For kernel durations run it under
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o multi_lidar -- python tools/multi_lidar_profile.py
 alone (no counters, no other tracing)."""
 import json
