@@ -207,6 +207,8 @@ class SensorSync {
 // frame); enumeration order x outer, y middle, yaw inner.  More than max_candidates nodes: std::runtime_error (coarsen the steps).
 std::vector<TPose3D> relocalization_grid(const TPose3D& mean, const double cov[36], double step_xy, double step_yaw_rad,
                                          double sigmas = 3.0, size_t max_candidates = 65536);
+// ... whether that grid stays within max_candidates (the same count, without making the poses)
+bool relocalization_grid_fits(const double cov[36], double step_xy, double step_yaw_rad, double sigmas = 3.0, size_t max_candidates = 65536);
 
 // Steps 2-4 of LidarOdometry::relocalizeNearPose on their own (the driver calls this; so does a loop closure's verification,
 // LoopClosure.h): ONE mh_score_poses of `local_layer` of pcLocal (a DevicePointCloud) against `global_layer` of pcGlobal (a device
@@ -251,6 +253,68 @@ class PlaceIndex {
   mh_place_params params_;
   mh_place_db* db_ = nullptr;
   std::vector<uint32_t> frame_of_;
+};
+
+// The optional top-level lost_recovery: block (this implementation's own key): what LidarOdometry does once its own judgement of
+// the alignments says that the vehicle is lost.  An absent block and enabled: false leave the driver as it is without the block.
+struct LostRecoveryOptions {
+  bool enabled = false;
+  uint32_t bad_scans_to_lost = 3;               // consecutive rejected alignments that make the driver LOST
+  std::string method = "near_then_keyframes";   // near | keyframes | near_then_keyframes
+  double near_sigma_xy = 3.0;                   // [m]   the covariance of a `near` attempt around the last good pose: x, y ...
+  double near_sigma_yaw_deg = 15.0;             // [deg] ... and yaw; the other entries are zero
+  uint32_t retry_every_n_scans = 5;             // scans from one attempt to the next while LOST
+  uint32_t max_attempts = 0;                    // per loss; 0: no limit
+  bool needsKeyFrames() const { return method != "near"; }
+  // out of range: std::runtime_error starting "lost_recovery: <key>"
+  static LostRecoveryOptions FromConfig(const Config& pipeline);
+  void validate() const;
+};
+
+// The state machine of lost_recovery: (LidarOdometry below), host logic only: the driver tells it what happened to a scan and does
+// what it answers.  Per scan that reaches registration, in this order:
+//   1. lost() is the state the scan arrived in;
+//   2. a pending relocalization request was served -> served(succeeded): the driver's own request counts as an attempt; success of
+//      anyone's request is TRACKING with the streaks at zero; a failed own request is to be cleared (the answer) and the next one
+//      is due retry_every_n_scans scans after this one;
+//   3. the alignment ran and the scan did not restart the map -> gate(icp_good): a rejected one extends the bad streak, and at
+//      bad_scans_to_lost the driver is LOST (the first attempt is due at once); a good one ends the bad streak, and while LOST
+//      bad_scans_to_lost good ones in a row are TRACKING again;
+//   4. due(request_pending, near_fits) -> the attempt to place now for the NEXT observation (0 none, 1 near, 2 keyframes): only while
+//      LOST, no request of anyone pending, the retry count run down and max_attempts not reached; with near_then_keyframes the first
+//      attempt of a loss is `near`, every later one `keyframes`.  A `near` attempt whose candidate grid would exceed
+//      relocalization.max_candidates (near_fits false) is SKIPPED: no request is placed and no device work done, so it is no
+//      attempt -- neither attempts() nor max_attempts count it, skipped() does; near_then_keyframes goes on to `keyframes` at
+//      once, method near waits retry_every_n_scans scans and looks again.  placed(kind) after the request was made;
+//      callerRequested() when the caller made one (it replaces the driver's own).
+class LostRecovery {
+ public:
+  struct Fields {  // what a ScanRecord shows of this
+    bool lost = false, recovery_succeeded = false;
+    uint32_t recovery_attempt = 0, bad_streak = 0;
+  };
+  explicit LostRecovery(const LostRecoveryOptions& o = LostRecoveryOptions()) : o_(o) {}
+  void reset() { *this = LostRecovery(o_); }
+  bool lost() const { return lost_; }
+  uint32_t badStreak() const { return bad_streak_; }
+  uint32_t ownPending() const { return own_pending_; }
+  uint32_t timesLost() const { return times_lost_; }
+  uint32_t attempts() const { return attempts_; }
+  uint32_t timesRecovered() const { return times_recovered_; }
+  bool gaveUp() const { return lost_ && o_.max_attempts != 0 && attempts_this_loss_ >= o_.max_attempts; }
+  void callerRequested() { own_pending_ = 0; }
+  bool served(bool succeeded, Fields& f);   // true: clear the request (the driver's own, failed)
+  void gate(bool icp_good, Fields& f);
+  uint32_t due(bool request_pending, bool near_fits = true);
+  uint32_t skipped() const { return skipped_; }  // `near` attempts skipped (no attempts: attempts() does not count them)
+  void placed(uint32_t kind) { own_pending_ = kind; }
+  const LostRecoveryOptions& options() const { return o_; }
+
+ private:
+  LostRecoveryOptions o_;
+  bool lost_ = false, near_done_ = false;  // near_done_: this loss has had its `near` turn (near_then_keyframes)
+  uint32_t bad_streak_ = 0, good_streak_ = 0, own_pending_ = 0, wait_ = 0, attempts_this_loss_ = 0;
+  uint32_t times_lost_ = 0, attempts_ = 0, times_recovered_ = 0, skipped_ = 0;
 };
 
 class LidarOdometry {
@@ -374,6 +438,15 @@ class LidarOdometry {
     std::vector<LoopPairRecord> loop_pairs;
     double loop_correction_trans = 0, loop_correction_rot = 0;
     uint32_t loop_rebuilt_frames = 0;
+    // lost_recovery: the driver was LOST when this scan arrived (lost); the request this scan served was the driver's own
+    // (recovery_attempt: 0 none, 1 near, 2 keyframes) and was accepted (recovery_succeeded); bad_streak = rejected alignments in a
+    // row up to and including this scan.  recovery_gave_up: when this scan ended the driver was LOST with max_attempts used up (it
+    // places no further request; a caller's request or bad_scans_to_lost good alignments still bring it back).
+    bool lost = false;
+    uint32_t recovery_attempt = 0;
+    bool recovery_succeeded = false;
+    uint32_t bad_streak = 0;
+    bool recovery_gave_up = false;
   };
 
   // ctx == nullptr: the process-wide default device context, taken at initialize()
@@ -497,6 +570,39 @@ class LidarOdometry {
   //   4. runs steps 2-5 of relocalizeNearPose on the concatenated list.
   void relocalizeInKeyFrames();
   bool relocalizationPending() const { return reloc_request_.has_value(); }
+  // lost_recovery: (LostRecoveryOptions, LostRecovery above) -- enabled: the driver judges by its own alignments whether it is lost and
+  // then places the requests above itself.  All of it is host logic inside onLidar* / onLidarFrom / onDepthImage, after the gate
+  // that sets icp_good:
+  //   1. TRACKING -> LOST: bad_scans_to_lost scans in a row with icp_run && !icp_good (a scan that restarted the map neither counts
+  //      nor breaks the run); the pose of that moment -- the last good one -- is remembered;
+  //   2. the scan that makes the driver LOST places the first request; the NEXT observation serves it, as it serves a caller's.
+  //      near: relocalizeNearPose(remembered pose, diag(near_sigma_xy^2, near_sigma_xy^2, ., near_sigma_yaw^2, ., .));
+  //      keyframes: relocalizeInKeyFrames(); near_then_keyframes: the first attempt of a loss is near, every later one keyframes;
+  //   3. a failed attempt clears the driver's own request (a caller's stays pending, as before); the next one is placed so that it
+  //      is served retry_every_n_scans scans after the failed one; after max_attempts (not 0) attempts of one loss none is placed
+  //      (recoveryGaveUp(), recovery_gave_up of the records).  An own request that cannot be served at all -- the key-frame store
+  //      holds no frame with points, the grids around the kept key-frames exceed relocalization.max_candidates, the scored layers
+  //      are not among the scan's -- would throw out of onLidar* on every scan with nobody to withdraw it: it is a failed attempt
+  //      like any other (the record shows the attempt and no search), and lastRecoveryError() keeps what was thrown.  A caller's
+  //      request throws as before.  A `near` attempt whose grid would exceed max_candidates is not placed at all (LostRecovery);
+  //   4. a caller's request takes precedence: while one is pending the driver places none, and a caller's request replaces the
+  //      driver's own; if it succeeds the driver is TRACKING;
+  //   5. while LOST an alignment that passes min_icp_goodness moves the pose, the motion model and the trajectory as before, but
+  //      neither the local maps (nor their key-frame list) nor the key-frame store take the scan;
+  //   6. LOST -> TRACKING: an accepted request (step 5 of relocalizeNearPose: the serving scan's registration runs from the
+  //      found pose and is trusted again), or bad_scans_to_lost good alignments in a row (the last of them is trusted again),
+  //      whichever comes first; the streaks are zero then.
+  // initialize() refuses, naming lost_recovery: -- a method that needs key-frames without simplemap.generate or
+  // load_existing_simple_map; online_loop_closure: enabled (its raw chain has no rule for a jump); an AlignBatcher (setAlignBatcher
+  // refuses too, both in the words of relocalizeInKeyFrames' refusal); and whatever relocalizeNearPose / relocalizeInKeyFrames
+  // refuse of the plan.  reset() is TRACKING, all counts zero.
+  const LostRecoveryOptions& lostRecoveryOptions() const { return lost_.options(); }
+  bool isLost() const { return lost_.lost(); }
+  uint32_t timesLost() const { return lost_.timesLost(); }
+  uint32_t recoveryAttempts() const { return lost_.attempts(); }
+  uint32_t timesRecovered() const { return lost_.timesRecovered(); }
+  bool recoveryGaveUp() const { return lost_.gaveUp(); }                      // LOST, and max_attempts used up
+  const std::string& lastRecoveryError() const { return recovery_error_; }  // what the last own request that could not be served threw
   std::shared_ptr<HashedVoxelPointCloud> localMap() const { return local_map_; }
   // points of every local map by name (general plans: one per localmap_generator entry; 0 before the first key-frame)
   std::map<std::string, uint64_t> localMapSizes() const;
@@ -643,6 +749,16 @@ class LidarOdometry {
     bool in_keyframes = false;  // relocalizeInKeyFrames: mean and cov come from the place search at the serving scan
   };
   std::optional<RelocRequest> reloc_request_;
+  // what relocalizeNearPose / relocalizeInKeyFrames refuse of the batcher, of `mean` (when given) and of the plan, in this order;
+  // -> the layers to score with
+  void check_can_relocalize(const char* who, std::string& global_layer, std::string& local_layer, const CPose3D* mean = nullptr) const;
+  void note_served(ScanRecord& rec, double seconds);  // lost_recovery: a request was served, in `seconds`; rec.relocalized says how
+  void place_recovery_request(uint32_t kind);        // lost_recovery: the driver's own request through the public calls
+  void near_attempt_cov(double cov[36]) const;       // ... the covariance of a `near` attempt
+  bool near_attempt_fits() const;                    // ... and whether its grid stays within relocalization.max_candidates
+  LostRecovery lost_;                                // lost_recovery: (used only when its options are enabled)
+  CPose3D lost_pose_;                                // ... the last good pose when the driver became LOST
+  std::string recovery_error_;                       // ... lastRecoveryError()
   std::unique_ptr<PlaceIndex> place_index_;  // relocalizeInKeyFrames: built at the first serving scan
   size_t place_frames_seen_ = 0;             // ... and how many frames of the key-frame store it has looked at
   // online_loop_closure:

@@ -913,6 +913,119 @@ LidarOdometry::RelocalizationOptions relocalization_options(const Config& cfg) {
   return o;
 }
 
+// the lost_recovery: block (this implementation's own key)
+LostRecoveryOptions LostRecoveryOptions::FromConfig(const Config& cfg) {
+  LostRecoveryOptions o;
+  if (cfg.has("lost_recovery") && !cfg["lost_recovery"].isNull()) {
+    const Config& c = cfg["lost_recovery"];
+    auto given = [&](const char* k) { return c.has(k) && !c[k].isNull(); };
+    if (given("enabled")) {
+      const std::string s = c["enabled"].asString();
+      if (s == "true" || s == "True" || s == "1" || s == "yes") o.enabled = true;
+      else if (s == "false" || s == "False" || s == "0" || s == "no") o.enabled = false;
+      else throw std::runtime_error("lost_recovery: enabled must be true or false");
+    }
+    auto cnt = [&](const char* k, uint32_t& v, double lo) {
+      if (!given(k)) return;
+      const std::string s = c[k].asString();
+      char* end = nullptr;
+      const double d = strtod(s.c_str(), &end);
+      if (end == s.c_str() || *end != 0 || !(d >= lo) || !(d <= 4294967295.0) || d != std::floor(d))
+        throw std::runtime_error(std::string("lost_recovery: ") + k + " must be an integer >= " + std::to_string((int)lo));
+      v = (uint32_t)d;
+    };
+    auto num = [&](const char* k, double& v) {
+      if (!given(k)) return;
+      const std::string s = c[k].asString();
+      char* end = nullptr;
+      v = strtod(s.c_str(), &end);
+      if (end == s.c_str() || *end != 0) v = NAN;  // (refused by validate())
+    };
+    cnt("bad_scans_to_lost", o.bad_scans_to_lost, 1.0);
+    if (given("method")) o.method = c["method"].asString();
+    num("near_sigma_xy", o.near_sigma_xy);
+    num("near_sigma_yaw_deg", o.near_sigma_yaw_deg);
+    cnt("retry_every_n_scans", o.retry_every_n_scans, 1.0);
+    cnt("max_attempts", o.max_attempts, 0.0);
+  }
+  o.validate();
+  return o;
+}
+
+void LostRecoveryOptions::validate() const {
+  if (bad_scans_to_lost < 1) throw std::runtime_error("lost_recovery: bad_scans_to_lost must be an integer >= 1");
+  if (method != "near" && method != "keyframes" && method != "near_then_keyframes")
+    throw std::runtime_error("lost_recovery: method must be one of near, keyframes, near_then_keyframes; it is '" + method + "'");
+  if (!(near_sigma_xy >= 0.0) || !std::isfinite(near_sigma_xy)) throw std::runtime_error("lost_recovery: near_sigma_xy must be finite and >= 0");
+  if (!(near_sigma_yaw_deg >= 0.0) || !std::isfinite(near_sigma_yaw_deg))
+    throw std::runtime_error("lost_recovery: near_sigma_yaw_deg must be finite and >= 0");
+  if (retry_every_n_scans < 1) throw std::runtime_error("lost_recovery: retry_every_n_scans must be an integer >= 1");
+}
+
+// ---- LostRecovery: the rule is in LidarOdometry.h
+bool LostRecovery::served(bool succeeded, Fields& f) {
+  const uint32_t own = own_pending_;
+  own_pending_ = 0;
+  if (own) {
+    f.recovery_attempt = own;
+    attempts_++;
+    attempts_this_loss_++;
+  }
+  if (succeeded) {
+    f.recovery_succeeded = own != 0;
+    if (lost_) {
+      lost_ = false;
+      times_recovered_++;
+    }
+    bad_streak_ = good_streak_ = 0;
+    return false;
+  }
+  if (own) wait_ = o_.retry_every_n_scans;
+  return own != 0;
+}
+
+void LostRecovery::gate(bool icp_good, Fields& f) {
+  if (icp_good) {
+    bad_streak_ = 0;
+    if (lost_ && ++good_streak_ >= o_.bad_scans_to_lost) {
+      lost_ = false;
+      good_streak_ = 0;
+      times_recovered_++;
+    }
+  } else {
+    bad_streak_++;
+    good_streak_ = 0;
+    if (!lost_ && bad_streak_ >= o_.bad_scans_to_lost) {
+      lost_ = true;
+      times_lost_++;
+      attempts_this_loss_ = 0;
+      near_done_ = false;
+      wait_ = 0;
+    }
+  }
+  f.bad_streak = bad_streak_;
+}
+
+uint32_t LostRecovery::due(bool request_pending, bool near_fits) {
+  if (!lost_) return 0;
+  if (wait_ > 0) wait_--;
+  if (request_pending || wait_ > 0 || gaveUp()) return 0;
+  const bool near = o_.method == "near" || (o_.method == "near_then_keyframes" && !near_done_);
+  if (!near) return 2;
+  near_done_ = true;
+  if (near_fits) return 1;
+  skipped_++;  // no request, no device work: not an attempt
+  if (o_.method == "near_then_keyframes") return 2;
+  wait_ = o_.retry_every_n_scans;
+  return 0;
+}
+
+namespace {
+// lost_recovery: with an AlignBatcher, whichever of initialize() and setAlignBatcher() comes second: relocalizeInKeyFrames' refusal
+const char* const kNoRecoveryWithBatcher = "enabled: LidarOdometry::relocalizeInKeyFrames: not available with an AlignBatcher (the batch protocol has "
+                                           "no slot for the extra alignments of one member)";
+}  // namespace
+
 void LidarOdometry::initialize(const Config& cfg) {
   if (plan_ || gplan_) throw std::runtime_error("LidarOdometry::initialize() called twice; create a new object instead");
   params_.load_from(cfg["params"]);
@@ -1071,6 +1184,28 @@ void LidarOdometry::initialize(const Config& cfg) {
     }
   }
 
+  // lost_recovery: (LidarOdometry.h): read and checked whether enabled or not; what it needs is asked for only when enabled
+  {
+    const LostRecoveryOptions lr = LostRecoveryOptions::FromConfig(cfg);
+    if (lr.enabled) {
+      const std::string who = "LidarOdometry (HIP): lost_recovery: ";
+      if (lr.needsKeyFrames() && !params_.simplemap.generate && params_.simplemap.load_existing_simple_map.empty())
+        throw std::runtime_error(who + "method '" + lr.method + "' needs key-frames to search: params.simplemap.generate: true or "
+                                 "params.simplemap.load_existing_simple_map (method: near needs none)");
+      if (loop_enabled_)
+        throw std::runtime_error(who + "enabled together with online_loop_closure: enabled is not implemented (the raw chain of the loop "
+                                 "closer has no rule for a jump of the pose)");
+      if (batcher_) throw std::runtime_error(who + kNoRecoveryWithBatcher);  // (setAlignBatcher says the same when it comes second)
+      try {  // (what the requests themselves refuse of the plan: an ICP block without a matcher to score with)
+        std::string g, l;
+        check_can_relocalize(lr.needsKeyFrames() ? "relocalizeInKeyFrames" : "relocalizeNearPose", g, l);
+      } catch (const std::runtime_error& e) {
+        throw std::runtime_error(who + "enabled, but " + e.what());
+      }
+    }
+    lost_ = LostRecovery(lr);
+  }
+
   reset();  // device objects are created at the first scan: a pipeline can be loaded and checked without a GPU (a saved map
             // is restored here, which needs one)
 }
@@ -1217,8 +1352,8 @@ void LidarOdometry::scan_layers(mp2p_icp_hip::metric_map_t& obs, mp2p_icp_hip::m
 }
 
 // ================================================================== relocalization
-std::vector<TPose3D> relocalization_grid(const TPose3D& mean, const double cov[36], double step_xy, double step_yaw_rad, double sigmas,
-                                         size_t max_candidates) {
+namespace {
+void relocalization_grid_nodes(const double cov[36], double step_xy, double step_yaw_rad, double sigmas, size_t& nx, size_t& ny, size_t& nyaw) {
   if (!(step_xy > 0.0) || !(step_yaw_rad > 0.0) || !(sigmas > 0.0) || !std::isfinite(step_xy) || !std::isfinite(step_yaw_rad) || !std::isfinite(sigmas))
     throw std::runtime_error("relocalization_grid: the steps and sigmas must be finite and > 0");
   auto nodes = [&](double var, double step) -> size_t {
@@ -1227,7 +1362,20 @@ std::vector<TPose3D> relocalization_grid(const TPose3D& mean, const double cov[3
     if (!(half < 1.0e7)) throw std::runtime_error("relocalization_grid: more than max_candidates candidates: coarsen the steps");
     return 2 * (size_t)half + 1;
   };
-  const size_t nx = nodes(cov[0], step_xy), ny = nodes(cov[7], step_xy), nyaw = nodes(cov[21], step_yaw_rad);
+  nx = nodes(cov[0], step_xy), ny = nodes(cov[7], step_xy), nyaw = nodes(cov[21], step_yaw_rad);
+}
+}  // namespace
+
+bool relocalization_grid_fits(const double cov[36], double step_xy, double step_yaw_rad, double sigmas, size_t max_candidates) {
+  size_t nx, ny, nyaw;
+  relocalization_grid_nodes(cov, step_xy, step_yaw_rad, sigmas, nx, ny, nyaw);
+  return !(nx * ny > max_candidates || nx * ny * nyaw > max_candidates);
+}
+
+std::vector<TPose3D> relocalization_grid(const TPose3D& mean, const double cov[36], double step_xy, double step_yaw_rad, double sigmas,
+                                         size_t max_candidates) {
+  size_t nx, ny, nyaw;
+  relocalization_grid_nodes(cov, step_xy, step_yaw_rad, sigmas, nx, ny, nyaw);
   if (nx * ny > max_candidates || nx * ny * nyaw > max_candidates)
     throw std::runtime_error("relocalization_grid: " + std::to_string(nx) + " x " + std::to_string(ny) + " x " + std::to_string(nyaw) +
                              " candidates exceed max_candidates (" + std::to_string(max_candidates) + "): coarsen the steps or tighten the covariance");
@@ -1276,17 +1424,22 @@ double LidarOdometry::reloc_score_threshold(const std::string& global_layer) con
   return 0.5 * (double)mi.voxel_size;
 }
 
+void LidarOdometry::check_can_relocalize(const char* who, std::string& g, std::string& l, const CPose3D* mean) const {
+  if (batcher_)
+    throw std::runtime_error(std::string("LidarOdometry::") + who + ": not available with an AlignBatcher (the batch protocol has no slot for "
+                             "the extra alignments of one member)");
+  if (mean)
+    for (int i = 0; i < 12; i++)
+      if (!std::isfinite(mean->T[i])) throw std::runtime_error(std::string("LidarOdometry::") + who + ": non-finite pose");
+  if (!scored_layers(*icp_[1], g, l))
+    throw std::runtime_error(std::string("LidarOdometry::") + who + ": the no-motion-model ICP block has no enabled Matcher_Points_DistanceThreshold "
+                             "to score candidates with");
+}
+
 void LidarOdometry::relocalizeNearPose(const CPose3D& mean, const double cov[36]) {
   if (!plan_ && !gplan_) throw std::runtime_error("LidarOdometry::relocalizeNearPose called before initialize()");
-  if (batcher_)
-    throw std::runtime_error("LidarOdometry::relocalizeNearPose: not available with an AlignBatcher (the batch protocol has no slot for "
-                             "the extra alignments of one member)");
-  for (int i = 0; i < 12; i++)
-    if (!std::isfinite(mean.T[i])) throw std::runtime_error("LidarOdometry::relocalizeNearPose: non-finite pose");
   std::string g, l;
-  if (!scored_layers(*icp_[1], g, l))
-    throw std::runtime_error("LidarOdometry::relocalizeNearPose: the no-motion-model ICP block has no enabled Matcher_Points_DistanceThreshold "
-                             "to score candidates with");
+  check_can_relocalize("relocalizeNearPose", g, l, &mean);
   // the candidate count is checked now, so that the caller can coarsen (when the defaults need a map that is not there yet: at
   // the scan that serves the request)
   const double thr = reloc_score_threshold(g);
@@ -1298,21 +1451,51 @@ void LidarOdometry::relocalizeNearPose(const CPose3D& mean, const double cov[36]
   rq.mean = mean;
   for (int i = 0; i < 36; i++) rq.cov[i] = cov[i];
   reloc_request_ = rq;
+  lost_.callerRequested();  // (place_recovery_request() says afterwards when the request is the driver's own)
 }
 
 void LidarOdometry::relocalizeInKeyFrames() {
   if (!plan_ && !gplan_) throw std::runtime_error("LidarOdometry::relocalizeInKeyFrames called before initialize()");
-  if (batcher_)
-    throw std::runtime_error("LidarOdometry::relocalizeInKeyFrames: not available with an AlignBatcher (the batch protocol has no slot for "
-                             "the extra alignments of one member)");
   std::string g, l;
-  if (!scored_layers(*icp_[1], g, l))
-    throw std::runtime_error("LidarOdometry::relocalizeInKeyFrames: the no-motion-model ICP block has no enabled Matcher_Points_DistanceThreshold "
-                             "to score candidates with");
+  check_can_relocalize("relocalizeInKeyFrames", g, l);
   RelocRequest rq;
   for (int i = 0; i < 36; i++) rq.cov[i] = 0.0;
   rq.in_keyframes = true;
   reloc_request_ = rq;
+  lost_.callerRequested();
+}
+
+// lost_recovery: the covariance of a `near` attempt, and whether its grid stays within relocalization.max_candidates (where
+// relocalizeNearPose would throw; true while the searched map, whose voxel size the default step is, does not exist)
+void LidarOdometry::near_attempt_cov(double cov[36]) const {
+  const LostRecoveryOptions& o = lost_.options();
+  std::fill(cov, cov + 36, 0.0);
+  cov[0] = cov[7] = o.near_sigma_xy * o.near_sigma_xy;
+  const double syaw = o.near_sigma_yaw_deg * kDeg2Rad;
+  cov[21] = syaw * syaw;
+}
+
+bool LidarOdometry::near_attempt_fits() const {
+  std::string g, l;
+  if (!scored_layers(*icp_[1], g, l)) return true;
+  const double thr = reloc_score_threshold(g);
+  if (!std::isfinite(thr)) return true;
+  double cov[36];
+  near_attempt_cov(cov);
+  return relocalization_grid_fits(cov, reloc_opts_.step_xy > 0 ? reloc_opts_.step_xy : thr, reloc_opts_.step_yaw_deg * kDeg2Rad, reloc_opts_.sigmas,
+                                  reloc_opts_.max_candidates);
+}
+
+// lost_recovery: the driver's own request, made as a caller makes it
+void LidarOdometry::place_recovery_request(uint32_t kind) {
+  if (kind == 1) {
+    double cov[36];
+    near_attempt_cov(cov);
+    relocalizeNearPose(lost_pose_, cov);
+  } else {
+    relocalizeInKeyFrames();
+  }
+  lost_.placed(kind);
 }
 
 std::vector<TPose3D> LidarOdometry::place_candidates(ScanRecord& rec, double step) {
@@ -1466,6 +1649,7 @@ RelocalizationRefinement score_rank_refine(ICP& icp, const mp2p_icp_hip::Paramet
 
 void LidarOdometry::serve_relocalization(double t, ScanRecord& rec) {
   StageTimer tt(profile_, "onLidar.2.relocalize");
+  const auto t_served = std::chrono::steady_clock::now();
   ICP& icp = *icp_[1];
   std::string gname, lname;
   if (!scored_layers(icp, gname, lname)) throw std::runtime_error("LidarOdometry: relocalization: no Matcher_Points_DistanceThreshold to score with");
@@ -1502,6 +1686,20 @@ void LidarOdometry::serve_relocalization(double t, ScanRecord& rec) {
     reloc_request_.reset();
     rec.relocalized = true;
   }
+  if (lost_.options().enabled) note_served(rec, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_served).count());
+}
+
+// lost_recovery: the driver's own request is an attempt, and does not stay pending when it fails
+void LidarOdometry::note_served(ScanRecord& rec, double seconds) {
+  LostRecovery::Fields f;
+  if (lost_.served(rec.relocalized, f)) reloc_request_.reset();
+  rec.recovery_attempt = f.recovery_attempt;
+  rec.recovery_succeeded = f.recovery_succeeded;
+  if (f.recovery_attempt) {
+    profile_["lost_recovery.attempts"] += 1.0;
+    profile_["lost_recovery.seconds"] += seconds;
+  }
+  rec.bad_streak = lost_.badStreak();
 }
 
 void LidarOdometry::ensure_device() {
@@ -1580,6 +1778,9 @@ void LidarOdometry::reset() {
   records_.clear();
   initial_localization_done_ = false;
   reloc_request_.reset();
+  lost_.reset();  // (TRACKING, the streaks and the counts zero)
+  lost_pose_ = CPose3D();
+  recovery_error_.clear();
   kf_store_.reset(loaded_keyframes_);  // (likewise: the store starts from the loaded file's frames again)
   place_index_.reset();                // (... and the place index follows it from its first frame)
   place_frames_seen_ = 0;
@@ -1751,6 +1952,8 @@ void LidarOdometry::setAlignBatcher(std::shared_ptr<mp2p_icp_hip::AlignBatcher> 
   if (b && loop_enabled_)
     throw std::runtime_error("LidarOdometry::setAlignBatcher: not available with online_loop_closure: enabled (the batch protocol of an "
                              "AlignBatcher has no slot for the extra alignments that verify a loop)");
+  if (b && lost_.options().enabled)
+    throw std::runtime_error(std::string("LidarOdometry::setAlignBatcher: not available with lost_recovery: ") + kNoRecoveryWithBatcher);
   if (b && (!ctx_ || ctx_ == DeviceContext::Default()))
     throw std::runtime_error("LidarOdometry::setAlignBatcher: this instance uses the process-wide default context; construct "
                              "it with a DeviceContext of its own");
@@ -2250,9 +2453,34 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     initial_localization_done_ = true;
   }
   // a pending relocalization request, served with a non-empty map, before the motion-model query
-  if (reloc_request_ && !map_is_empty()) serve_relocalization(this_obs_tim, rec);
+  const bool recovery = lost_.options().enabled;  // lost_recovery: (LidarOdometry.h)
+  if (recovery) {
+    rec.lost = lost_.lost();
+    rec.bad_streak = lost_.badStreak();
+  }
+  if (reloc_request_ && !map_is_empty()) {
+    if (recovery && lost_.ownPending()) {
+      // the driver's own request: nobody could withdraw one that cannot be served, and it would throw on every scan from here on.
+      // It is a failed attempt (rule 3 in LidarOdometry.h); the record shows the attempt and no search
+      const auto t_served = std::chrono::steady_clock::now();
+      try {
+        serve_relocalization(this_obs_tim, rec);
+      } catch (const std::runtime_error& e) {
+        recovery_error_ = e.what();
+        profile_["lost_recovery.not_served"] += 1.0;
+        rec.relocalization_tried = rec.relocalized = rec.place_tried = false;
+        rec.place_frames.clear(), rec.place_shifts.clear(), rec.place_dists.clear(), rec.reloc_ranks.clear();
+        rec.reloc_candidates = rec.reloc_best_n_paired = 0;
+        rec.reloc_best_quality = 0.0;
+        note_served(rec, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_served).count());
+      }
+    } else {
+      serve_relocalization(this_obs_tim, rec);
+    }
+  }
 
   bool updateLocalMap = false;
+  bool map_trusted = true;  // lost_recovery: false while LOST -- the scan goes neither into the local maps nor into the key-frame store
   double kf_cov[36] = {0};  // the alignment's covariance, for the key-frame store (zeros for a first scan)
   {
     StageTimer tt(profile_, "onLidar.2.navstate");
@@ -2360,11 +2588,21 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     // ---- adaptive threshold, also after a rejected ICP (:1052-1064)
     if (params_.adaptive_threshold_enabled) doUpdateAdaptiveThreshold(res.optimal_tf.mean - CPose3D(init_guess));
 
+    // ---- lost_recovery: the streaks and the state follow the gate (a scan that restarts the map below stands outside them)
+    if (recovery && !(!icpIsGood && trajectory_.size() == 1)) {
+      const bool was_lost = lost_.lost();
+      LostRecovery::Fields f;
+      lost_.gate(icpIsGood, f);
+      rec.bad_streak = f.bad_streak;
+      if (!was_lost && lost_.lost()) lost_pose_ = last_lidar_pose_;  // (a rejected alignment has not moved it: the last good pose)
+    }
+    map_trusted = !recovery || !lost_.lost();
+
     // ---- key-frame decision (:1066-1118)
     const auto [isFirstPoseInChecker, distanceToClosest] = distance_checker_local_map_.check(last_lidar_pose_);
     const double dist_eucl_since_last = distanceToClosest.translationNorm();
     const double rot_since_last = distanceToClosest.rotationAngle();
-    updateLocalMap = icpIsGood && params_.local_map_updates_enabled && hasMotionModel &&
+    updateLocalMap = map_trusted && icpIsGood && params_.local_map_updates_enabled && hasMotionModel &&
                      (isFirstPoseInChecker || dist_eucl_since_last > params_.min_translation_between_keyframes ||
                       rot_since_last > params_.min_rotation_between_keyframes * kDeg2Rad);
     if (updateLocalMap) {
@@ -2395,7 +2633,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
 
   // ---- key-frames of the session (:1117-1138, 1209-1296), before the map update is queued: the download then waits for
   // nothing but this scan's own registration
-  if (params_.simplemap.generate && !rec.restarted) store_keyframe(rec, rec.first_scan, rec.icp_good, kf_cov);
+  if (params_.simplemap.generate && !rec.restarted && map_trusted) store_keyframe(rec, rec.first_scan, rec.icp_good, kf_cov);
 
   // ---- local map update (:1158-1206): FilterMerge of the de-skewed map layer at the current pose, on the device
   if (updateLocalMap) {
@@ -2429,6 +2667,11 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     kf_targets_known_ = true;
   }
   if (loop_enabled_) feed_loop_closer(rec);
+  if (recovery) {  // lost_recovery: the driver's own request, for the next observation to serve
+    const uint32_t kind = lost_.due(reloc_request_.has_value(), !lost_.lost() || near_attempt_fits());
+    if (kind) place_recovery_request(kind);
+    rec.recovery_gave_up = lost_.gaveUp();
+  }
   rec.pose = last_lidar_pose_;
   rec.sigma = adapt_thres_sigma_;
   rec.map_voxel_size = map_voxel_size_;

@@ -106,6 +106,8 @@ struct SequenceReport {
   std::vector<double> scan_seconds;  // --scan-log: registration time of every scan
   bool online_loop_closure = false;  // the pipeline's online_loop_closure: block is enabled ...
   size_t loops_closed = 0;           // ... and closed this many loops while driving
+  bool lost_recovery = false;        // the pipeline's lost_recovery: block is enabled ...
+  unsigned times_lost = 0, recovery_attempts = 0, times_recovered = 0;  // ... LidarOdometry::timesLost() and its like
 };
 
 struct RunOptions {
@@ -269,6 +271,8 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
     if (!opt.output_corrected_trajectory.empty()) lo.saveCorrectedTrajectoryTUM(opt.output_corrected_trajectory + suffix);
     rep.online_loop_closure = mola_hip::OnlineLoopClosureOptions::FromConfig(cfg).enabled;
     if (lo.loopCloser()) rep.loops_closed = lo.loopCloser()->loops().size();
+    rep.lost_recovery = lo.lostRecoveryOptions().enabled;
+    rep.times_lost = lo.timesLost(), rep.recovery_attempts = lo.recoveryAttempts(), rep.times_recovered = lo.timesRecovered();
     stamp("trajectory saved");
     if (!opt.save_local_map.empty()) lo.saveLocalMaps(opt.save_local_map + suffix);  // (what params.local_map_updates.load_existing_local_map of a later run reads)
     if (!opt.output_simplemap.empty()) lo.saveKeyFrames(opt.output_simplemap + suffix);
@@ -574,6 +578,8 @@ int main(int argc, char** argv) {
            r.steady_seconds > 0 ? r.steady_scans / r.steady_seconds : 0.0, r.mean_raw_points, r.mean_icp_points, r.mean_map_layer_points,
            (unsigned long long)r.final_map_points, (unsigned long long)r.max_map_points, (unsigned long long)r.final_map_voxels, r.out.c_str());
     if (r.online_loop_closure) printf(", \"loops_closed\": %zu", r.loops_closed);
+    if (r.lost_recovery)  // (the pipeline's lost_recovery: block; absent or disabled, the line is as before)
+      printf(", \"times_lost\": %u, \"recovery_attempts\": %u, \"times_recovered\": %u", r.times_lost, r.recovery_attempts, r.times_recovered);
     printf("}\n");
     if (print_profile && r.scans) {  // host milliseconds per scan and stage (LidarOdometry::profile()), steady state
       const double ns = (double)(r.steady_scans ? r.steady_scans : r.scans);
@@ -629,6 +635,11 @@ int main(int argc, char** argv) {
     bool online = false;
     for (const auto& r : reps) online = online || r.online_loop_closure, loops_closed += r.loops_closed;
     if (online) printf(", \"loops_closed\": %zu", loops_closed);  // (the pipeline's online_loop_closure: block; absent, the line is as before)
+    unsigned times_lost = 0, recovery_attempts = 0, times_recovered = 0;
+    bool recovery = false;
+    for (const auto& r : reps)
+      recovery = recovery || r.lost_recovery, times_lost += r.times_lost, recovery_attempts += r.recovery_attempts, times_recovered += r.times_recovered;
+    if (recovery) printf(", \"times_lost\": %u, \"recovery_attempts\": %u, \"times_recovered\": %u", times_lost, recovery_attempts, times_recovered);
     printf("}\n");
   }
   // Everything asked for is on disk and on stdout.  The drivers' destructors would now hipFree a few hundred buffers one by one,

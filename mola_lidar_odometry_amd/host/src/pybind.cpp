@@ -404,8 +404,58 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["loop_pairs"] = loop_pairs;
     d["loop_correction_trans"] = r.loop_correction_trans; d["loop_correction_rot"] = r.loop_correction_rot;
     d["loop_rebuilt_frames"] = r.loop_rebuilt_frames;
+    d["lost"] = r.lost; d["recovery_attempt"] = r.recovery_attempt; d["recovery_succeeded"] = r.recovery_succeeded; d["bad_streak"] = r.bad_streak;
+    d["recovery_gave_up"] = r.recovery_gave_up;
     return d;
   };
+  auto lost2dict = [](const mola_hip::LostRecoveryOptions& o) {
+    py::dict d;
+    d["enabled"] = o.enabled; d["bad_scans_to_lost"] = o.bad_scans_to_lost; d["method"] = o.method; d["near_sigma_xy"] = o.near_sigma_xy;
+    d["near_sigma_yaw_deg"] = o.near_sigma_yaw_deg; d["retry_every_n_scans"] = o.retry_every_n_scans; d["max_attempts"] = o.max_attempts;
+    return d;
+  };
+  // the lost_recovery: block of a pipeline Config as a dict (an absent block: the defaults)
+  m.def("lost_recovery_options", [lost2dict](const Config& c) { return lost2dict(mola_hip::LostRecoveryOptions::FromConfig(c)); });
+  // the state machine of lost_recovery: on its own (host logic only; the driver holds one).  scan(icp_good, outcome, caller_request, near_fits):
+  // one scan that reaches registration, in the driver's order -- the caller may have placed a request before it (caller_request); a
+  // pending request is served with `outcome` (a failed caller's request stays pending); the gate sees icp_good (None: the alignment
+  // did not run, or the scan restarted the map); the driver's own request is placed when due (near_fits: a `near`
+  // attempt's grid stays within max_candidates; false: skipped) -> the record fields, and what was placed.
+  struct LostRecoveryHook {
+    mola_hip::LostRecovery m;
+    bool pending = false;
+  };
+  py::class_<LostRecoveryHook>(m, "LostRecovery")
+      .def(py::init([](const Config& c) { return LostRecoveryHook{mola_hip::LostRecovery(mola_hip::LostRecoveryOptions::FromConfig(c)), false}; }))
+      .def("scan", [](LostRecoveryHook& h, std::optional<bool> icp_good, bool outcome, bool caller_request, bool near_fits) {
+        mola_hip::LostRecovery::Fields f;
+        if (caller_request) {
+          h.pending = true;
+          h.m.callerRequested();
+        }
+        f.lost = h.m.lost();
+        f.bad_streak = h.m.badStreak();
+        if (h.pending) {
+          const bool clear = h.m.served(outcome, f);
+          if (outcome || clear) h.pending = false;
+        }
+        if (icp_good) h.m.gate(*icp_good, f);
+        const uint32_t kind = h.m.due(h.pending, near_fits);
+        if (kind) {
+          h.pending = true;
+          h.m.placed(kind);
+        }
+        py::dict d;
+        d["lost"] = f.lost; d["recovery_attempt"] = f.recovery_attempt; d["recovery_succeeded"] = f.recovery_succeeded; d["bad_streak"] = f.bad_streak;
+        d["recovery_gave_up"] = h.m.gaveUp(); d["placed"] = kind; d["pending"] = h.pending;
+        return d; }, py::arg("icp_good"), py::arg("outcome") = false, py::arg("caller_request") = false, py::arg("near_fits") = true)
+      .def("reset", [](LostRecoveryHook& h) { h.m.reset(); h.pending = false; })
+      .def("isLost", [](const LostRecoveryHook& h) { return h.m.lost(); })
+      .def("timesLost", [](const LostRecoveryHook& h) { return h.m.timesLost(); })
+      .def("recoveryAttempts", [](const LostRecoveryHook& h) { return h.m.attempts(); })
+      .def("timesRecovered", [](const LostRecoveryHook& h) { return h.m.timesRecovered(); })
+      .def("skipped", [](const LostRecoveryHook& h) { return h.m.skipped(); })
+      .def("gaveUp", [](const LostRecoveryHook& h) { return h.m.gaveUp(); });
   py::class_<LidarOdometry> lo_class(m, "LidarOdometry", py::dynamic_attr());
   lo_class
       .def(py::init([](int device, bool own_context) {
@@ -513,6 +563,13 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         lo.relocalizeNearPose(P, cov.data()); })
       .def("relocalizeInKeyFrames", &LidarOdometry::relocalizeInKeyFrames)
       .def("relocalizationPending", &LidarOdometry::relocalizationPending)
+      .def("lostRecoveryOptions", [lost2dict](const LidarOdometry& lo) { return lost2dict(lo.lostRecoveryOptions()); })
+      .def("isLost", &LidarOdometry::isLost)
+      .def("timesLost", &LidarOdometry::timesLost)
+      .def("recoveryAttempts", &LidarOdometry::recoveryAttempts)
+      .def("timesRecovered", &LidarOdometry::timesRecovered)
+      .def("recoveryGaveUp", &LidarOdometry::recoveryGaveUp)
+      .def("lastRecoveryError", [](const LidarOdometry& lo) { return lo.lastRecoveryError(); })
       .def("initialLocalization", [](const LidarOdometry& lo) {
         const auto& il = lo.initialLocalization();
         py::dict d;
