@@ -16,11 +16,10 @@
 #pragma once
 #include <stdint.h>
 
+#include "mh_place_bin.h"
+
 namespace mh {
 
-constexpr uint32_t kPlaceBlock = 256;                // four waves of 64
-constexpr uint32_t kPlacePointsPerLane = 8;
-constexpr uint32_t kPlaceChunk = kPlaceBlock * kPlacePointsPerLane;  // points of a pass per workgroup
 constexpr uint32_t kPlaceMaxBins = MH_PLACE_MAX_RINGS * MH_PLACE_MAX_SECTORS;
 
 struct PlaceTables {  // built on the host in fp64, rounded once (place_make_tables, mh_place.hip)
@@ -29,20 +28,6 @@ struct PlaceTables {  // built on the host in fp64, rounded once (place_make_tab
   float z_min, z_max, zscale;
   uint32_t R, S;
 };
-
-struct PlaceSrc {
-  const float *x, *y, *z;  // the frame's points (device memory; never read for an empty frame)
-};
-
-// the frame of point q: the last f in [lo, hi] with start[f] <= q; empty frames are stepped over by the upper bound
-__device__ __forceinline__ uint32_t place_frame_of(const uint32_t* __restrict__ start, uint32_t lo, uint32_t hi, uint32_t q) {
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1u) >> 1;
-    if (start[mid] <= q) lo = mid;
-    else hi = mid - 1u;
-  }
-  return lo;
-}
 
 // bin (ring * S + sector) and level (1..255) of one point; false: the point is skipped
 __device__ __forceinline__ bool place_bin(const PlaceTables& t, float x, float y, float z, uint32_t& bin, uint32_t& level) {
@@ -54,21 +39,7 @@ __device__ __forceinline__ bool place_bin(const PlaceTables& t, float x, float y
   uint32_t ring = 0;
   for (uint32_t k = 1; k < t.R; k++) ring += t.ring_edge2[k] <= r2 ? 1u : 0u;
   level = min(255u, 1u + (uint32_t)((z - t.z_min) * t.zscale));
-  uint32_t Q;
-  float a, b;
-  if (x > 0.f && y >= 0.f) { Q = 0; a = x; b = y; }
-  else if (x <= 0.f && y > 0.f) { Q = 1; a = y; b = -x; }
-  else if (x < 0.f && y <= 0.f) { Q = 2; a = -x; b = -y; }
-  else { Q = 3; a = -y; b = x; }
-  const uint32_t E = t.S >> 3;
-  uint32_t o = 0;
-  if (b < a) {
-    for (uint32_t j = 1; j < E; j++) o += b >= t.tan_edge[j] * a ? 1u : 0u;
-  } else {
-    for (uint32_t j = 1; j < E; j++) o += a > t.tan_edge[j] * b ? 1u : 0u;
-    o = (2u * E - 1u) - o;
-  }
-  bin = ring * t.S + Q * (t.S >> 2) + o;
+  bin = ring * t.S + place_sector(t.tan_edge, t.S, x, y);
   return true;
 }
 

@@ -43,6 +43,7 @@
 
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
 #include "mola_lidar_odometry_hip/LoopClosure.h"
+#include "mola_lidar_odometry_hip/MapCleaning.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "molahip.h"
 
@@ -332,12 +333,14 @@ int main(int argc, char** argv) {
   std::string build_from;  // --build-session-map
   std::string close_from, loop_report;  // --close-loops, --loop-report
   std::vector<std::string> join_files;  // --join-sessions A B
+  std::vector<std::string> clean_files;  // --clean-keyframes IN OUT
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
                       "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE] [--relocalize-in-keyframes]\n"
                       "       molahip-lo-cli --build-session-map KEYFRAMES --save-local-map FILE [--device N]\n"
                       "       molahip-lo-cli --close-loops KEYFRAMES --pipeline FILE.yaml --output-simplemap FILE [--output-session-map FILE] [--loop-report FILE.json] [--device N]\n"
                       "       molahip-lo-cli --join-sessions KEYFRAMES_A KEYFRAMES_B --pipeline FILE.yaml --output-simplemap FILE [--output-session-map FILE] [--loop-report FILE.json] [--device N]\n"
+                      "       molahip-lo-cli --clean-keyframes KEYFRAMES_IN KEYFRAMES_OUT [-c FILE.yaml] [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
@@ -354,6 +357,9 @@ int main(int argc, char** argv) {
                       "  on the device; the pipeline's session_join: block) and its key-frames are put into A's frame; A's key-frames and then B's go to\n"
                       "  --output-simplemap's FILE, the maps built from them to --output-session-map's, the report to --loop-report's; when the sessions\n"
                       "  cannot be joined nothing is written and the exit status is 1\n"
+                      "  --clean-keyframes: no sequence is run: points that other key-frames look straight through (moving objects) are taken out of\n"
+                      "  the key-frames of KEYFRAMES_IN (the pipeline's map_cleaning: block; -c or --pipeline, optional) and the set goes to KEYFRAMES_OUT;\n"
+                      "  run it after --close-loops / --join-sessions and before --build-session-map\n"
                       "  --relocalize-in-keyframes: the vehicle is found in a saved session without a prior pose: place recognition over the\n"
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
@@ -376,7 +382,7 @@ int main(int argc, char** argv) {
       return argv[++i];
     };
     try {
-      if (a == "--pipeline") pipeline = val("--pipeline");
+      if (a == "--pipeline" || a == "-c") pipeline = val("--pipeline");
       else if (a == "--seq-dir") seq_dirs.push_back(val("--seq-dir"));
       else if (a == "--out") out = val("--out");
       else if (a == "--device") devices = {atoi(val("--device").c_str())};
@@ -396,6 +402,10 @@ int main(int argc, char** argv) {
         join_files.push_back(val("--join-sessions"));
         join_files.push_back(val("--join-sessions"));
       }
+      else if (a == "--clean-keyframes") {
+        clean_files.push_back(val("--clean-keyframes"));
+        clean_files.push_back(val("--clean-keyframes"));
+      }
       else if (a == "--relocalize-in-keyframes") opt.relocalize_in_keyframes = true;
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
@@ -405,6 +415,24 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n%s", e.what(), usage);
       return 2;
     }
+  }
+  if (!clean_files.empty()) {  // moving objects taken out of a recorded drive's key-frames, no sequence
+    if (clean_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty()) {
+      fprintf(stderr, "--clean-keyframes takes one key-frame file to read and one to write, once, and takes no sequence\n%s", usage);
+      return 2;
+    }
+    try {
+      const mola_hip::MapCleaningOptions copt =
+          mola_hip::MapCleaningOptions::FromConfig(pipeline.empty() ? mp2p_icp_hip::Config::FromYamlText("") : mp2p_icp_hip::Config::FromYamlFile(pipeline));
+      auto ctx = std::make_shared<mp2p_icp_hip::DeviceContext>(devices.empty() ? 0 : devices[0]);
+      const mola_hip::CleaningReport r = mola_hip::clean_keyframes_file(clean_files[0], clean_files[1], copt, ctx);
+      printf("{\"keyframe_file\": \"%s\", \"output_simplemap\": \"%s\", \"cleaning\": %s}\n", clean_files[0].c_str(), clean_files[1].c_str(),
+             r.toJson().c_str());
+    } catch (const std::exception& e) {
+      fprintf(stderr, "molahip-lo-cli: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (!join_files.empty()) {  // two recorded drives put into one frame, no sequence
     if (join_files.size() != 2 || pipeline.empty() || opt.output_simplemap.empty() || !seq_dirs.empty() || !build_from.empty() || !close_from.empty()) {

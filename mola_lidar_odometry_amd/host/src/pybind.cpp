@@ -8,6 +8,7 @@
 
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
 #include "mola_lidar_odometry_hip/LoopClosure.h"
+#include "mola_lidar_odometry_hip/MapCleaning.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 #include "molahip_host/plugin_switches.h"
@@ -1141,6 +1142,64 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     rep["counts"] = r.report.counts; rep["json"] = r.report.toJson();
     return py::make_tuple(kfset2dict(r.joined), r.is_joined, rep); },
         py::arg("a"), py::arg("b"), py::arg("pipeline"), py::arg("output_keyframe_file") = "");
+  // ---- moving objects taken out of key-frames (mola_lidar_odometry_hip/MapCleaning.h)
+  using mola_hip::MapCleaningOptions;
+  // `options`: a pipeline Config, or the YAML text of one (its map_cleaning: block is read; absent: the defaults)
+  auto cleaning_opts = [](const py::object& options) {
+    if (options.is_none()) return MapCleaningOptions::FromConfig(Config::FromYamlText(""));
+    if (py::isinstance<py::str>(options)) return MapCleaningOptions::FromConfig(Config::FromYamlText(options.cast<std::string>()));
+    return MapCleaningOptions::FromConfig(options.cast<const Config&>());
+  };
+  m.def("map_cleaning_options", [cleaning_opts](const py::object& options) {
+    const MapCleaningOptions o = cleaning_opts(options);
+    py::dict d;
+    d["n_rings"] = o.n_rings; d["n_sectors"] = o.n_sectors; d["el_min_deg"] = o.el_min_deg; d["el_max_deg"] = o.el_max_deg;
+    d["min_range"] = o.min_range; d["max_range"] = o.max_range; d["rel_margin"] = o.rel_margin;
+    d["origin_x"] = o.origin[0]; d["origin_y"] = o.origin[1]; d["origin_z"] = o.origin[2];
+    d["win_rings"] = o.win_rings; d["win_sectors"] = o.win_sectors; d["max_view_distance"] = o.max_view_distance;
+    d["max_views_per_frame"] = o.max_views_per_frame; d["min_through_votes"] = o.min_through_votes; d["agree_weight"] = o.agree_weight;
+    const mh_clean_params p = o.deviceParams();  // what the device is given: the floats of mh_clean_params
+    d["device_params"] = py::make_tuple(p.n_rings, p.n_sectors, p.el_min, p.el_max, p.min_range, p.max_range, p.rel_margin,
+                                        py::make_tuple(p.origin[0], p.origin[1], p.origin[2]), p.win_rings, p.win_sectors);
+    return d; }, py::arg("options") = py::none());
+  // poses [K, 12], has_points [K] -> the neighbour list of every frame (host rule 1)
+  m.def("cleaning_neighbours", [cleaning_opts](py::array_t<double, py::array::c_style | py::array::forcecast> poses, const std::vector<bool>& has_points,
+                                               const py::object& options) {
+    if (poses.ndim() != 2 || poses.shape(1) != 12) throw std::runtime_error("cleaning_neighbours: poses must be [K, 12]");
+    if (has_points.size() != (size_t)poses.shape(0)) throw std::runtime_error("cleaning_neighbours: has_points needs one entry per pose");
+    const std::vector<double> P(poses.data(), poses.data() + poses.size());
+    const std::vector<uint8_t> has(has_points.begin(), has_points.end());
+    return mola_hip::cleaning_neighbours(P, has, cleaning_opts(options)); },
+        py::arg("poses"), py::arg("has_points"), py::arg("options") = py::none());
+  m.def("cleaning_relative_pose", [](const std::vector<double>& Ti, const std::vector<double>& Tj) {
+    if (Ti.size() != 12 || Tj.size() != 12) throw std::runtime_error("a pose has 12 values");
+    std::vector<double> T(12);
+    mola_hip::cleaning_relative_pose(Ti.data(), Tj.data(), T.data());
+    return T; });
+  m.def("cleaning_removes", [cleaning_opts](py::array_t<uint32_t, py::array::c_style | py::array::forcecast> votes, const py::object& options) {
+    const MapCleaningOptions o = cleaning_opts(options);
+    std::vector<bool> out((size_t)votes.size());
+    for (size_t k = 0; k < out.size(); k++) out[k] = mola_hip::cleaning_removes(votes.data()[k], o);
+    return out; }, py::arg("votes"), py::arg("options") = py::none());
+  // a key-frame set (a dict as close_loops takes it, or the path of a key-frame file) -> (cleaned set as a dict, report); with
+  // `output_keyframe_file` the cleaned set is also written there
+  m.def("clean_keyframes", [dict2kfset, kfset2dict, cleaning_opts](const py::object& frames, const py::object& options, const std::string& output_keyframe_file) {
+    const molahip_host::KeyFrameSet set = py::isinstance<py::str>(frames) ? molahip_host::read_keyframe_file(frames.cast<std::string>())
+                                                                         : dict2kfset(frames.cast<py::dict>());
+    const MapCleaningOptions o = cleaning_opts(options);
+    mola_hip::CleaningResult r;
+    {
+      py::gil_scoped_release nogil;
+      r = mola_hip::clean_keyframes(set, o);
+      if (!output_keyframe_file.empty()) molahip_host::write_keyframe_file(output_keyframe_file, r.cleaned);
+    }
+    py::dict rep;
+    py::list per;
+    for (const auto& f : r.report.frames) per.append(py::make_tuple(f.points_in, f.points_removed, f.neighbours));
+    rep["frames"] = per; rep["points_in"] = r.report.points_in; rep["points_removed"] = r.report.points_removed; rep["pairs"] = r.report.pairs;
+    rep["seconds"] = r.report.seconds; rep["json"] = r.report.toJson();
+    return py::make_tuple(kfset2dict(r.cleaned), rep); },
+        py::arg("frames"), py::arg("options") = py::none(), py::arg("output_keyframe_file") = "");
   // the pose rules of the driver's online loop closure and the motion model's rebase, on 12-value poses
   auto to_pose = [](const std::vector<double>& T) {
     if (T.size() != 12) throw std::runtime_error("a pose has 12 values");
