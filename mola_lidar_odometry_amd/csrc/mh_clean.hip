@@ -16,19 +16,10 @@
 
 #include "molahip_clean.h"
 #include "mh_internal.h"
+#include "mh_views.h"
 #include "mh_k_clean.h"
 
 using namespace mh;
-
-struct mh_views {
-  mh_ctx* ctx = nullptr;
-  mh_clean_params params{};
-  CleanTables tab{};
-  DevBuf img;          // size * A*S words, img[k][ring * S + sector]
-  uint64_t size = 0;
-  PinnedBuf h_frames;  // page-locked mirror of one pass's upload
-  DevBuf nbr;          // vote_frames: the neighbour list of the call (start | view | T)
-};
 
 namespace {
 
@@ -142,15 +133,6 @@ mh_status stage_pass(mh_ctx* ctx, PinnedBuf& mirror, const mh_map_frame* frames,
   ps.d_start = (const uint32_t*)(d + off_start);
   ps.d_tiles = (const uint32_t*)(d + off_tiles);
   ps.d_table = (const PlaceSrc*)(d + off_table);
-  return MH_OK;
-}
-
-// room for n_total views; what is stored moves along when the block grows (the outgrown block stays valid behind it)
-mh_status views_reserve(mh_views* v, uint64_t n_total) {
-  const size_t AS = (size_t)v->tab.A * v->tab.S * sizeof(uint32_t);
-  void* old = v->img.p;
-  MH_TRY(v->img.reserve(n_total * AS));
-  if (old && old != v->img.p && v->size) MH_HIP(hipMemcpyAsync(v->img.p, old, v->size * AS, hipMemcpyDeviceToDevice, v->ctx->stream));
   return MH_OK;
 }
 

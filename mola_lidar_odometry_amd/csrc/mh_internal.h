@@ -246,6 +246,14 @@ struct mh_map {
   mutable bool counts_pending = false;   // n_points ... bbox above are stale until map_resolve() has seen ev_counts
   mutable bool build_in_flight = false;  // the last (re)build may still run: consumers on OTHER streams order themselves with map_ready_on()
   mutable mh_status deferred_error = MH_OK;  // an insertion's out-of-range verdict, reported by the next call that resolves
+  // molahip_live.h: an erasing rebuild is queued against counts that may still be on their way, so what it has to hand on lives
+  // on the device -- d_live = {points erased since the map was created (64 bit), the out-of-range flag of an update whose
+  // counters the erasing rebuild overwrote before the host saw them} -- and travels to the pinned h_live ahead of the rebuild's
+  // own read-back; map_resolve_counts() takes both in
+  mh::DevBuf d_live;
+  uint64_t* h_live = nullptr;        // pinned [2]
+  mutable bool live_pending = false, live_flag_taken = false;
+  mutable uint64_t erased_total = 0;
   // mh_map_insert's scratch is the map's own
   mh::DevBuf build_a, build_b, build_c, build_d, build_e, sort_tmp;
   mh::MapView view(const mh::Switches& sw) const {

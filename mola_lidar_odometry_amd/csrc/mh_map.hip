@@ -539,6 +539,8 @@ mh_status mh_map_destroy(mh_map* m) {
   if (m->ev_counts) (void)hipEventDestroy(m->ev_counts);
   if (m->ev_qidx) (void)hipEventDestroy(m->ev_qidx);
   if (m->h_counts) (void)hipHostFree(m->h_counts);
+  if (m->h_live) (void)hipHostFree(m->h_live);
+  m->d_live.release();
   for (mh::DevBuf* b : {&m->build_a, &m->build_b, &m->build_c, &m->build_d, &m->build_e, &m->sort_tmp}) b->release();
   m->slots.release();
   m->pts.release();
@@ -896,6 +898,14 @@ mh_status map_resolve_counts(const mh_map* m) {
     m->n_records = h[10];
     m->n_points = h[10] - (ndt ? 2u * h[9] : 0u);
     m->n_planes = m->n_points ? h[8] : 0;
+    if (m->live_pending) {  // erasing rebuilds since the last look (mh_live.hip)
+      m->live_pending = false;
+      m->erased_total = m->h_live[0];
+      if (m->h_live[1] && !m->live_flag_taken) {  // an update's verdict that only the erasing rebuild behind it has seen
+        m->deferred_error = MH_ERR_OUT_OF_RANGE;
+        m->live_flag_taken = true;
+      }
+    }
     for (int a = 0; a < 3; a++) {
       m->bbox_min[a] = m->n_points ? ord2f(h[2 + a]) : 0.f;
       m->bbox_max[a] = m->n_points ? ord2f(h[5 + a]) : 0.f;

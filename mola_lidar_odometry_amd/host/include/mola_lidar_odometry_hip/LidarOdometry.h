@@ -37,6 +37,7 @@
 #include <string>
 #include <vector>
 
+#include "mola_lidar_odometry_hip/LiveMapCleaning.h"
 #include "molahip_host/keyframe_file.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 
@@ -447,6 +448,9 @@ class LidarOdometry {
     bool recovery_succeeded = false;
     uint32_t bad_streak = 0;
     bool recovery_gave_up = false;
+    // online_map_cleaning: this scan's local map update was followed by an erasing of the target maps (LiveMapCleaning.h);
+    // n_map_points / n_map_voxels are then the counts AFTER the erasing
+    bool map_cleaned = false;
   };
 
   // ctx == nullptr: the process-wide default device context, taken at initialize()
@@ -603,6 +607,15 @@ class LidarOdometry {
   uint32_t timesRecovered() const { return lost_.timesRecovered(); }
   bool recoveryGaveUp() const { return lost_.gaveUp(); }                      // LOST, and max_attempts used up
   const std::string& lastRecoveryError() const { return recovery_error_; }  // what the last own request that could not be served threw
+  // online_map_cleaning: (LiveMapCleaning.h) -- enabled: every local map update is followed, inside the same onLidar* call and
+  // after all of its insertPointCloud calls, by the rule of LiveMapCleaner on the target maps: the view of view_layer's cloud into
+  // the ring, then (every every_n_updates updates) one mh_map_erase_seen_through per target map -- all queued on the device.
+  // Whatever clears the maps (the restart after a bad first alignment, reset()) empties the ring.  Key-frames go into the
+  // key-frame store as recorded.  initialize() refuses, naming online_map_cleaning: -- a target that is a CVoxelMap or not a map
+  // of the plan, a view_layer the plan does not make, online_loop_closure: with correct_driver (its rebuild from the key-frames
+  // would bring the erased points back), an AlignBatcher (setAlignBatcher refuses too).
+  const OnlineMapCleaningOptions& onlineMapCleaningOptions() const { return live_opts_; }
+  uint64_t mapPointsErased() const;  // points erased from the target maps since they were created (waits for the device)
   std::shared_ptr<HashedVoxelPointCloud> localMap() const { return local_map_; }
   // points of every local map by name (general plans: one per localmap_generator entry; 0 before the first key-frame)
   std::map<std::string, uint64_t> localMapSizes() const;
@@ -771,6 +784,10 @@ class LidarOdometry {
     CPose3D rel;      // the entry's pose in that frame, when it was made
   };
   std::vector<TrajectoryAnchor> trajectory_anchor_;  // one per trajectory_ entry (kept while enabled)
+  // online_map_cleaning:
+  OnlineMapCleaningOptions live_opts_;
+  std::unique_ptr<LiveMapCleaner> live_cleaner_;  // made at the first local map update (the maps and their context exist then)
+  bool clean_live_maps();                          // the rule of LiveMapCleaner behind this scan's insertions
   bool input_pinned_ = false;
   bool intensity_input_ = false;  // setIntensityInput
   std::map<std::string, double> profile_;

@@ -17,7 +17,7 @@
 //      z arrays shrink (kept points in their order).  A version-1 key-frame file: build_session_maps(), close_loops() and
 //      join_sessions() take it as it is.
 //
-// Not built: cleaning while driving; cleaning a live local map; per-point sensor origins for rigs (one origin per set: points of a
+// Cleaning the live local map while driving is LiveMapCleaning.h (row g11).  Not built: per-point sensor origins for rigs (one origin per set: points of a
 // merged multi-LiDAR frame are binned as if seen from it); CVoxelMap plans (refused by name, as close_loops and join_sessions do).
 #pragma once
 #include <map>
@@ -49,8 +49,19 @@ struct MapCleaningOptions {
   uint32_t agree_weight = 1;                   // >= 0
   static MapCleaningOptions FromConfig(const Config& pipeline);
   void validate() const;
+  void validateAs(const std::string& block) const;  // the same checks, the refusals naming another block (LiveMapCleaning.h)
   mh_clean_params deviceParams() const;  // degrees to radians in fp64, then one rounding to the struct's floats
 };
+
+// ---- what map_cleaning: and online_map_cleaning: (LiveMapCleaning.h) read alike.  `c` is the block, `block` its name in refusals.
+// The keys both hold: n_rings .. win_sectors, max_view_distance, min_through_votes, agree_weight
+const std::vector<std::string>& cleaning_shared_keys();
+void read_cleaning_shared_keys(const Config& c, const std::string& block, MapCleaningOptions& o);
+// a key that is neither shared nor among own_keys is refused
+void cleaning_block_unknown_keys(const Config& c, const std::string& block, const std::vector<std::string>& own_keys);
+// an absent or null key leaves `v` as it is; anything but a number / an integer >= 0 is refused
+void cleaning_block_number(const Config& c, const std::string& block, const char* key, double& v);
+void cleaning_block_count(const Config& c, const std::string& block, const char* key, uint32_t& v);
 
 // ---- host rules (testable without a device)
 // poses: 12 doubles per frame; has_points: one flag per frame.  out[i]: the neighbours of frame i (rule 1).

@@ -1024,6 +1024,9 @@ namespace {
 // lost_recovery: with an AlignBatcher, whichever of initialize() and setAlignBatcher() comes second: relocalizeInKeyFrames' refusal
 const char* const kNoRecoveryWithBatcher = "enabled: LidarOdometry::relocalizeInKeyFrames: not available with an AlignBatcher (the batch protocol has "
                                            "no slot for the extra alignments of one member)";
+// online_map_cleaning: likewise
+const char* const kNoLiveCleaningWithBatcher = "enabled is not available with an AlignBatcher (the instances of a lock-step batch share one "
+                                               "round of alignments; map updates queued between them are not part of its protocol)";
 }  // namespace
 
 void LidarOdometry::initialize(const Config& cfg) {
@@ -1204,6 +1207,44 @@ void LidarOdometry::initialize(const Config& cfg) {
       }
     }
     lost_ = LostRecovery(lr);
+  }
+
+  // online_map_cleaning: (LiveMapCleaning.h): read and checked whether enabled or not
+  {
+    live_opts_ = OnlineMapCleaningOptions::FromConfig(cfg);
+    live_cleaner_.reset();
+    if (live_opts_.enabled) {
+      const std::string who = "LidarOdometry (HIP): online_map_cleaning: ";
+      std::vector<std::pair<std::string, bool>> maps;  // the plan's maps: name, is an occupancy map
+      if (gplan_)
+        for (const auto& m : gplan_->maps) maps.emplace_back(m.name, ends_with(m.def["class"].asString(), "CVoxelMap"));
+      else
+        maps.emplace_back(plan_->map_layer, ends_with(map_def_["class"].asString(), "CVoxelMap"));
+      for (const auto& t : live_opts_.target_maps) {
+        const auto it = std::find_if(maps.begin(), maps.end(), [&](const auto& m) { return m.first == t; });
+        if (it == maps.end()) throw std::runtime_error(who + "target_maps names '" + t + "', which is no local map of this pipeline");
+        if (it->second)
+          throw std::runtime_error(who + "target map '" + t + "' is a 'CVoxelMap': an occupancy map stores no points to erase and is cleared by "
+                                   "its own ray tracing (HashedVoxelPointCloud, NDT and SparseTreesPointCloud maps can be targets)");
+      }
+      if (live_opts_.target_maps.empty() && std::all_of(maps.begin(), maps.end(), [](const auto& m) { return m.second; }))
+        throw std::runtime_error(who + "enabled, but every local map of this pipeline is a 'CVoxelMap': there is no point map to erase from");
+      if (!live_opts_.view_layer.empty()) {
+        bool known = false;
+        if (gplan_) {
+          known = live_opts_.view_layer == "raw";
+          for (const auto& st : gplan_->steps)
+            known = known || std::find(st.out.begin(), st.out.end(), live_opts_.view_layer) != st.out.end();
+        } else {
+          known = live_opts_.view_layer == plan_->layer_for_map || live_opts_.view_layer == plan_->layer_for_icp;
+        }
+        if (!known) throw std::runtime_error(who + "view_layer '" + live_opts_.view_layer + "' is no observation layer this pipeline's filters make");
+      }
+      if (loop_enabled_ && loop_correct_)
+        throw std::runtime_error(who + "enabled together with online_loop_closure: correct_driver: true is not implemented (an accepted closure "
+                                 "rebuilds the local maps from the key-frames, which would bring the erased points back)");
+      if (batcher_) throw std::runtime_error(who + kNoLiveCleaningWithBatcher);  // (setAlignBatcher says the same when it comes second)
+    }
   }
 
   reset();  // device objects are created at the first scan: a pipeline can be loaded and checked without a GPU (a saved map
@@ -1753,6 +1794,7 @@ void LidarOdometry::reset() {
   map_points_cached_ = map_voxels_cached_ = 0;
   map_known_nonempty_ = false;
   navstate_.reset();
+  live_cleaner_.reset();  // (online_map_cleaning: the ring goes with the maps)
   local_map_.reset();
   if (gplan_) {
     for (auto& m : gplan_->maps) m.map.reset();
@@ -1954,6 +1996,8 @@ void LidarOdometry::setAlignBatcher(std::shared_ptr<mp2p_icp_hip::AlignBatcher> 
                              "AlignBatcher has no slot for the extra alignments that verify a loop)");
   if (b && lost_.options().enabled)
     throw std::runtime_error(std::string("LidarOdometry::setAlignBatcher: not available with lost_recovery: ") + kNoRecoveryWithBatcher);
+  if (b && live_opts_.enabled)
+    throw std::runtime_error(std::string("LidarOdometry::setAlignBatcher: not available with online_map_cleaning: ") + kNoLiveCleaningWithBatcher);
   if (b && (!ctx_ || ctx_ == DeviceContext::Default()))
     throw std::runtime_error("LidarOdometry::setAlignBatcher: this instance uses the process-wide default context; construct "
                              "it with a DeviceContext of its own");
@@ -2624,6 +2668,7 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
         if (m.map && m.map != local_map_) m.map->clear();
     map_known_nonempty_ = false;
     map_points_cached_ = map_voxels_cached_ = 0;
+    if (live_cleaner_) live_cleaner_->clear();  // (online_map_cleaning: whatever clears the maps empties the ring)
     trajectory_.clear();
     trajectory_anchor_.clear();
     updateLocalMap = false;
@@ -2653,7 +2698,8 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
       local_map_->insertPointCloud(*for_map_, last_lidar_pose_, remove_voxels_farther_than_);
     }
     rec.map_updated = true;
-    if (rec.n_for_map == 0) map_known_nonempty_ = false;  // (nothing offered: ask the device next time)
+    if (live_opts_.enabled) rec.map_cleaned = clean_live_maps();  // online_map_cleaning: (LiveMapCleaning.h)
+    if (rec.n_for_map == 0 || rec.map_cleaned) map_known_nonempty_ = false;  // (nothing offered, or points erased: ask the device next time)
     map_counts_pending_ = true;
     map_counts_from_ = records_.size() - 1;
   }
@@ -2680,6 +2726,41 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
     rec.n_map_voxels = map_voxels_cached_;
   }
   return rec;
+}
+
+// ---- online_map_cleaning: (LidarOdometry.h, LiveMapCleaning.h)
+bool LidarOdometry::clean_live_maps() {
+  if (!live_cleaner_) live_cleaner_ = std::make_unique<LiveMapCleaner>(live_opts_, ctx_);
+  std::vector<HashedVoxelPointCloud*> targets;
+  const auto wanted = [&](const std::string& name) {
+    return live_opts_.target_maps.empty() || std::find(live_opts_.target_maps.begin(), live_opts_.target_maps.end(), name) != live_opts_.target_maps.end();
+  };
+  const DevicePointCloud* view = nullptr;
+  if (gplan_) {
+    for (const auto& m : gplan_->maps)
+      if (m.map && wanted(m.name) && std::string(m.map->className()) != "CVoxelMap") targets.push_back(m.map.get());
+    const std::string name = live_opts_.view_layer.empty() ? gplan_->merges.at(0).first : live_opts_.view_layer;
+    if (!gplan_->alive.count(name))
+      throw std::runtime_error("LidarOdometry (HIP): online_map_cleaning: view_layer '" + name + "' is not among the layers this scan's filters left");
+    view = (name == "raw" ? (gplan_->raw_adjusted ? gplan_->raw_adjusted : cur_raw_) : gplan_->buf.at(name)).get();
+  } else {
+    targets.push_back(local_map_.get());
+    view = (live_opts_.view_layer == plan_->layer_for_icp && live_opts_.view_layer != plan_->layer_for_map ? for_icp_ : for_map_).get();
+  }
+  return live_cleaner_->update(*view, last_lidar_pose_, targets);
+}
+
+uint64_t LidarOdometry::mapPointsErased() const {
+  uint64_t total = 0;
+  auto add = [&](const std::shared_ptr<HashedVoxelPointCloud>& m) {
+    if (!m || std::string(m->className()) == "CVoxelMap") return;
+    uint64_t n = 0;
+    mp2p_icp_hip::check(mh_map_erased_total(m->handle(), &n), "mh_map_erased_total");
+    total += n;
+  };
+  if (gplan_) for (const auto& m : gplan_->maps) add(m.map);
+  else add(local_map_);
+  return total;
 }
 
 // ---- online_loop_closure: (LidarOdometry.h, LoopClosure.h)

@@ -109,6 +109,8 @@ struct SequenceReport {
   size_t loops_closed = 0;           // ... and closed this many loops while driving
   bool lost_recovery = false;        // the pipeline's lost_recovery: block is enabled ...
   unsigned times_lost = 0, recovery_attempts = 0, times_recovered = 0;  // ... LidarOdometry::timesLost() and its like
+  bool online_map_cleaning = false;   // the pipeline's online_map_cleaning: block is enabled ...
+  uint64_t map_points_erased = 0;     // ... LidarOdometry::mapPointsErased()
 };
 
 struct RunOptions {
@@ -274,6 +276,8 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
     if (lo.loopCloser()) rep.loops_closed = lo.loopCloser()->loops().size();
     rep.lost_recovery = lo.lostRecoveryOptions().enabled;
     rep.times_lost = lo.timesLost(), rep.recovery_attempts = lo.recoveryAttempts(), rep.times_recovered = lo.timesRecovered();
+    rep.online_map_cleaning = lo.onlineMapCleaningOptions().enabled;
+    if (rep.online_map_cleaning) rep.map_points_erased = lo.mapPointsErased();
     stamp("trajectory saved");
     if (!opt.save_local_map.empty()) lo.saveLocalMaps(opt.save_local_map + suffix);  // (what params.local_map_updates.load_existing_local_map of a later run reads)
     if (!opt.output_simplemap.empty()) lo.saveKeyFrames(opt.output_simplemap + suffix);
@@ -530,6 +534,18 @@ int main(int argc, char** argv) {
   }
   if (devices.empty()) devices = {0};
   const size_t N = seq_dirs.size(), D = devices.size();
+  if (N > 1 || D > 1) {
+    bool cleaning = false;
+    try {
+      cleaning = mola_hip::OnlineMapCleaningOptions::FromConfig(mp2p_icp_hip::Config::FromYamlFile(pipeline)).enabled;
+    } catch (const std::exception&) {  // (the run itself reports what is wrong with the file)
+    }
+    if (cleaning) {
+      fprintf(stderr, "molahip-lo-cli: the pipeline's online_map_cleaning: block is enabled: one sequence on one device only (several sequences of a "
+                      "process align through an AlignBatcher, whose protocol has no place for map updates queued between its rounds)\n");
+      return 2;
+    }
+  }
   if ((N > 1 || D > 1) && online_enabled()) {
     fprintf(stderr, "molahip-lo-cli: the pipeline's online_loop_closure: block is enabled: one sequence on one device only (several sequences of a "
                     "process align through an AlignBatcher, whose batch protocol has no slot for the extra alignments that verify a loop)\n");
@@ -608,6 +624,8 @@ int main(int argc, char** argv) {
     if (r.online_loop_closure) printf(", \"loops_closed\": %zu", r.loops_closed);
     if (r.lost_recovery)  // (the pipeline's lost_recovery: block; absent or disabled, the line is as before)
       printf(", \"times_lost\": %u, \"recovery_attempts\": %u, \"times_recovered\": %u", r.times_lost, r.recovery_attempts, r.times_recovered);
+    if (r.online_map_cleaning)  // (the pipeline's online_map_cleaning: block; absent or disabled, the line is as before)
+      printf(", \"map_points_erased\": %llu", (unsigned long long)r.map_points_erased);
     printf("}\n");
     if (print_profile && r.scans) {  // host milliseconds per scan and stage (LidarOdometry::profile()), steady state
       const double ns = (double)(r.steady_scans ? r.steady_scans : r.scans);
@@ -668,6 +686,10 @@ int main(int argc, char** argv) {
     for (const auto& r : reps)
       recovery = recovery || r.lost_recovery, times_lost += r.times_lost, recovery_attempts += r.recovery_attempts, times_recovered += r.times_recovered;
     if (recovery) printf(", \"times_lost\": %u, \"recovery_attempts\": %u, \"times_recovered\": %u", times_lost, recovery_attempts, times_recovered);
+    uint64_t map_points_erased = 0;
+    bool cleaning = false;
+    for (const auto& r : reps) cleaning = cleaning || r.online_map_cleaning, map_points_erased += r.map_points_erased;
+    if (cleaning) printf(", \"map_points_erased\": %llu", (unsigned long long)map_points_erased);
     printf("}\n");
   }
   // Everything asked for is on disk and on stdout.  The drivers' destructors would now hipFree a few hundred buffers one by one,

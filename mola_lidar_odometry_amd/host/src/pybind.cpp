@@ -407,6 +407,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["loop_rebuilt_frames"] = r.loop_rebuilt_frames;
     d["lost"] = r.lost; d["recovery_attempt"] = r.recovery_attempt; d["recovery_succeeded"] = r.recovery_succeeded; d["bad_streak"] = r.bad_streak;
     d["recovery_gave_up"] = r.recovery_gave_up;
+    d["map_cleaned"] = r.map_cleaned;
     return d;
   };
   auto lost2dict = [](const mola_hip::LostRecoveryOptions& o) {
@@ -415,6 +416,43 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["near_sigma_yaw_deg"] = o.near_sigma_yaw_deg; d["retry_every_n_scans"] = o.retry_every_n_scans; d["max_attempts"] = o.max_attempts;
     return d;
   };
+  // the online_map_cleaning: block (mola_lidar_odometry_hip/LiveMapCleaning.h) as a dict
+  auto live2dict = [](const mola_hip::OnlineMapCleaningOptions& o) {
+    py::dict d;
+    d["enabled"] = o.enabled;
+    d["n_rings"] = o.n_rings; d["n_sectors"] = o.n_sectors; d["el_min_deg"] = o.el_min_deg; d["el_max_deg"] = o.el_max_deg;
+    d["min_range"] = o.min_range; d["max_range"] = o.max_range; d["rel_margin"] = o.rel_margin;
+    d["origin_x"] = o.origin[0]; d["origin_y"] = o.origin[1]; d["origin_z"] = o.origin[2];
+    d["win_rings"] = o.win_rings; d["win_sectors"] = o.win_sectors; d["max_view_distance"] = o.max_view_distance;
+    d["max_views"] = o.max_views; d["min_through_votes"] = o.min_through_votes; d["agree_weight"] = o.agree_weight;
+    d["every_n_updates"] = o.every_n_updates; d["view_layer"] = o.view_layer; d["target_maps"] = o.target_maps;
+    const mh_clean_params p = o.deviceParams();  // what the device is given: the floats of mh_clean_params
+    d["device_params"] = py::make_tuple(p.n_rings, p.n_sectors, p.el_min, p.el_max, p.min_range, p.max_range, p.rel_margin,
+                                        py::make_tuple(p.origin[0], p.origin[1], p.origin[2]), p.win_rings, p.win_sectors);
+    return d;
+  };
+  // `options`: a pipeline Config, the YAML text of one, or None (the defaults)
+  auto live_opts = [](const py::object& options) {
+    using mola_hip::OnlineMapCleaningOptions;
+    if (options.is_none()) return OnlineMapCleaningOptions::FromConfig(Config::FromYamlText(""));
+    if (py::isinstance<py::str>(options)) return OnlineMapCleaningOptions::FromConfig(Config::FromYamlText(options.cast<std::string>()));
+    return OnlineMapCleaningOptions::FromConfig(options.cast<const Config&>());
+  };
+  m.def("online_map_cleaning_options", [live2dict, live_opts](const py::object& options) { return live2dict(live_opts(options)); },
+        py::arg("options") = py::none());
+  // the ring rule on its own (host logic only; the driver's LiveMapCleaner holds one): poses [K, 12] of K local map updates in a
+  // row -> per update (slot, due, neighbour slots)
+  m.def("live_ring_fold", [live_opts](py::array_t<double, py::array::c_style | py::array::forcecast> poses, const py::object& options) {
+    if (poses.ndim() != 2 || poses.shape(1) != 12) throw std::runtime_error("live_ring_fold: poses must be [K, 12]");
+    const mola_hip::OnlineMapCleaningOptions o = live_opts(options);
+    mola_hip::LiveRing ring(o.max_views, o.every_n_updates);
+    py::list out;
+    for (py::ssize_t k = 0; k < poses.shape(0); k++) {
+      const double* P = poses.data() + 12 * k;
+      const mola_hip::LiveRing::Step st = ring.put(P);
+      out.append(py::make_tuple(st.slot, st.due, st.due ? ring.neighbours(P, o.max_view_distance) : std::vector<uint32_t>()));
+    }
+    return out; }, py::arg("poses"), py::arg("options") = py::none());
   // the lost_recovery: block of a pipeline Config as a dict (an absent block: the defaults)
   m.def("lost_recovery_options", [lost2dict](const Config& c) { return lost2dict(mola_hip::LostRecoveryOptions::FromConfig(c)); });
   // the state machine of lost_recovery: on its own (host logic only; the driver holds one).  scan(icp_good, outcome, caller_request, near_fits):
@@ -565,6 +603,8 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("relocalizeInKeyFrames", &LidarOdometry::relocalizeInKeyFrames)
       .def("relocalizationPending", &LidarOdometry::relocalizationPending)
       .def("lostRecoveryOptions", [lost2dict](const LidarOdometry& lo) { return lost2dict(lo.lostRecoveryOptions()); })
+      .def("onlineMapCleaningOptions", [live2dict](const LidarOdometry& lo) { return live2dict(lo.onlineMapCleaningOptions()); })
+      .def("mapPointsErased", &LidarOdometry::mapPointsErased)
       .def("isLost", &LidarOdometry::isLost)
       .def("timesLost", &LidarOdometry::timesLost)
       .def("recoveryAttempts", &LidarOdometry::recoveryAttempts)
