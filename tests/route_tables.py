@@ -1,5 +1,6 @@
 """The route inventory of the alignment tests: which switches and layer sizes reach which kernel.  One definition, imported by
-tests/test_gpu_dense_cells.py, tests/test_gpu_solver_params.py and tests/test_gpu_far_origin.py; no GPU, no inputs.
+tests/test_gpu_dense_cells.py, tests/test_gpu_solver_params.py, tests/test_gpu_far_origin.py and (MUTATION_ROUTES, through
+tests/mutation_cases.py) tests/test_gpu_map_mutations.py; no GPU, no inputs.
 
 Which kernel a row runs follows from plan_alignment (csrc/mh_icp.hip) and is confirmed by the one-line mutants of DESIGN.md
 section 5.  MH_MATCH=t|w|o named the tile / wave / sorted-scan matchers, which were removed: the library refuses the letters
@@ -67,6 +68,60 @@ POINT_MATCHER_KERNELS = [
     (5000, {"MH_MATCH": "p"}),
     (5000, {"MH_MATCH": "x"}),
 ]
+
+
+# ------------------------------------------------------------------------------------------------ warm maps after a map update
+# tests/test_gpu_map_mutations.py runs every row on a handle that has been searched before and was then updated
+# (tests/mutation_cases.py).  The sizes are the small ones at which each kernel still takes its own path (dense_cases.SIZES,
+# LOOP16_CASES, LOOPW_CASES), every loop runs MUTATION_IT iterations, so the loop times of profiles/dense_cells.md still hold.
+# maps: "point" (plain point maps, an occupancy map's search map among them), "ndt", "any".
+MUTATION_IT = 6
+
+
+def _row(family, name, maps="any", **spec):
+    return dict(family=family, name=name, maps=maps, **spec)
+
+
+MUTATION_ROUTES = [
+    # ---- single alignments on point maps
+    _row("align", "icp16_n129", "point", n=129, env={}),                                                     # k_icp16
+    _row("align", "icp16_n2000", "point", n=2000, env={}),
+    _row("align", "icpw_n2561", "point", n=2561, env={"MH_LOOPW": "all"}),                                   # k_icpw
+    _row("align", "step16", "point", n=2000, env={"MH_NO_LOOP16": "1"}),                                     # k_step16
+    _row("align", "rows_fused", "point", n=2000, env={"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1"}),            # k_match16<false, FUSED>
+    _row("align", "rows", "point", n=2000, env={"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1", "MH_NO_FUSE16": "1"}),
+    _row("align", "q", "point", n=2000, env={"MH_MATCH": "q"}),                                              # k_match4
+    _row("align", "p", "point", n=2000, env={"MH_MATCH": "p"}),
+    _row("align", "x", "point", n=2000, env={"MH_MATCH": "x"}),
+    _row("align", "f", "point", n=2000, env={"MH_MATCH": "f"}),                                              # k_match_flat<true>
+    _row("align", "f_off64", "point", n=2000, env={"MH_MATCH": "f", "MH_NO_OFF32": "1"}),                    # k_match_flat<false>
+    _row("align", "q_nograph", "point", n=2000, env={"MH_MATCH": "q", "MH_NO_GRAPH": "1"}),
+    _row("align", "f_nograph", "point", n=2000, env={"MH_MATCH": "f", "MH_NO_GRAPH": "1"}),
+    # ---- the NDT kind: the rows of PLANE_MATCHER_KERNELS at 2000 points; where size alone chose the kernel there, MH_MATCH does
+    _row("align", "ndt_icp16", "ndt", n=2000, env={}, inner=2),                                              # k_icp16<true>
+    _row("align", "ndt_icp16_inner1", "ndt", n=2000, env={}, inner=1),
+    _row("align", "ndt_step16", "ndt", n=2000, env={"MH_NO_LOOP16": "1"}, inner=2),                          # k_step16<true>
+    _row("align", "ndt_step16_inner1", "ndt", n=2000, env={"MH_NO_LOOP16": "1"}, inner=1),
+    _row("align", "ndt_rows", "ndt", n=2000, env={"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1"}, inner=2),       # k_match16<true, false>
+    _row("align", "ndt_rows_nofuse", "ndt", n=2000, env={"MH_MATCH": "s", "MH_NO_STEP_CHAIN": "1", "MH_NO_FUSE16": "1"}, inner=1),
+    _row("align", "ndt_p", "ndt", n=2000, env={"MH_MATCH": "p"}, inner=2),                                   # k_match_pl<FUSED> + a lane per point
+    _row("align", "ndt_p_inner1", "ndt", n=2000, env={"MH_MATCH": "p"}, inner=1),
+    _row("align", "ndt_q", "ndt", n=2000, env={"MH_MATCH": "q"}, inner=2),                                   # ... + quad matcher
+    _row("align", "ndt_f", "ndt", n=2000, env={"MH_MATCH": "f"}, inner=2),                                   # ... + plan / scan matcher
+    _row("align", "ndt_skip", "ndt", n=2000, env={"MH_NO_LOOP16": "1"}, inner=2, skip=True),                 # matched_points = skip
+    # ---- the granular queries
+    _row("query", "dense"), _row("query", "nn"), _row("query", "nn_k3"), _row("query", "radius"), _row("query", "radius_sorted"),
+    _row("query", "score16"), _row("query", "pt2pl", "ndt"), _row("query", "pt2pl_knn"),
+    # ---- multi-layer: two pairs that share the updated map; k-best; a plane pair; unique-global
+    _row("layers", "two_pairs"), _row("layers", "k2"), _row("layers", "plane_pair"), _row("layers", "unique"),
+    # ---- one lock-step batch: three jobs on three contexts, each map updated on its own context, led by job 0
+    _row("batch", "icpw_b", env={}), _row("batch", "chain_b", env={"MH_LOOPW": "none"}),
+]
+
+
+def mutation_routes(ndt):
+    """the rows that apply to a map kind"""
+    return [r for r in MUTATION_ROUTES if r["maps"] in ("any", "ndt" if ndt else "point")]
 
 
 def loop_expected(n, env):
