@@ -13,6 +13,8 @@
 #pragma once
 #include "mh_internal.h"
 
+// (the kernels are static: mh_occmap.hip and mh_occgrid.hip both include this file)
+
 namespace mh {
 namespace occ {
 
@@ -63,12 +65,12 @@ __device__ __forceinline__ uint32_t lower_bound_u64(const unsigned long long* __
 // Per selected point j (point j * decimation of the layer): p = (float)(R p + t) in fp64 like mh_map_insert; left out when
 // non-finite, when farther than max_range from the pose's translation, when its index leaves the key range (counted);
 // otherwise its end cell, M = max |e - o|, and its number of work items: M - 1 in-between cells (ray tracing) + 1 end cell.
-__global__ __launch_bounds__(256) void k_occ_rays(const float* __restrict__ x, const float* __restrict__ y,
-                                                  const float* __restrict__ z, uint32_t n_sel, uint32_t decimation, Pose12 T,
-                                                  float otx, float oty, float otz, int ox, int oy, int oz, float inv_res,
-                                                  uint32_t trunc, float max_range2 /* < 0: off */, uint32_t ray_trace,
-                                                  int4* __restrict__ ray_e, uint32_t* __restrict__ items,
-                                                  uint32_t* __restrict__ counters /* [0]: points whose index left the range */) {
+static __global__ __launch_bounds__(256) void k_occ_rays(const float* __restrict__ x, const float* __restrict__ y,
+                                                         const float* __restrict__ z, uint32_t n_sel, uint32_t decimation, Pose12 T,
+                                                         float otx, float oty, float otz, int ox, int oy, int oz, float inv_res,
+                                                         uint32_t trunc, float max_range2 /* < 0: off */, uint32_t ray_trace,
+                                                         int4* __restrict__ ray_e, uint32_t* __restrict__ items,
+                                                         uint32_t* __restrict__ counters /* [0]: points whose index left the range */) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n_sel) return;
   const size_t i = (size_t)j * decimation;
@@ -103,10 +105,10 @@ __global__ __launch_bounds__(256) void k_occ_rays(const float* __restrict__ x, c
 // Item k_local < M - 1 is in-between cell k = k_local + 1 of the integer line walk in closed form,
 //   o_a + s_a * floor((2 k ad_a + M) / (2 M))   per axis a, 64-bit integers,
 // the last item of a ray is its end cell (a hit).
-__global__ __launch_bounds__(256) void k_occ_keys(const unsigned long long* __restrict__ prefix,
-                                                  const int4* __restrict__ ray_e, uint32_t n_rays, int ox, int oy, int oz,
-                                                  uint32_t ray_trace, unsigned long long g0, uint32_t count,
-                                                  unsigned long long* __restrict__ keys) {
+static __global__ __launch_bounds__(256) void k_occ_keys(const unsigned long long* __restrict__ prefix,
+                                                         const int4* __restrict__ ray_e, uint32_t n_rays, int ox, int oy, int oz,
+                                                         uint32_t ray_trace, unsigned long long g0, uint32_t count,
+                                                         unsigned long long* __restrict__ keys) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= count) return;
   const unsigned long long g = g0 + t;
@@ -135,17 +137,17 @@ __global__ __launch_bounds__(256) void k_occ_keys(const unsigned long long* __re
 }
 
 // (cell << 1 | is_miss, count) entries, sorted: head[i] = 1 on a cell's first entry (a cell has one or two, the hit first)
-__global__ __launch_bounds__(256) void k_occ_cell_heads(const unsigned long long* __restrict__ ek, uint32_t n,
-                                                        uint32_t* __restrict__ head) {
+static __global__ __launch_bounds__(256) void k_occ_cell_heads(const unsigned long long* __restrict__ ek, uint32_t n,
+                                                               uint32_t* __restrict__ head) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   head[i] = (i == 0 || (ek[i - 1] >> 1) != (ek[i] >> 1)) ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(256) void k_occ_cells(const unsigned long long* __restrict__ ek, const uint32_t* __restrict__ ec,
-                                                   const uint32_t* __restrict__ head, const uint32_t* __restrict__ pos,
-                                                   uint32_t n, unsigned long long* __restrict__ ucell,
-                                                   uint32_t* __restrict__ uh, uint32_t* __restrict__ um) {
+static __global__ __launch_bounds__(256) void k_occ_cells(const unsigned long long* __restrict__ ek, const uint32_t* __restrict__ ec,
+                                                          const uint32_t* __restrict__ head, const uint32_t* __restrict__ pos,
+                                                          uint32_t n, unsigned long long* __restrict__ ucell,
+                                                          uint32_t* __restrict__ uh, uint32_t* __restrict__ um) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || !head[i]) return;
   const unsigned long long k = ek[i], cell = k >> 1;
@@ -163,9 +165,9 @@ __global__ __launch_bounds__(256) void k_occ_cells(const unsigned long long* __r
 }
 
 // per touched cell: where it stands in the store, and whether it is new to it (is_new has n_u + 1 entries, the last one 0)
-__global__ __launch_bounds__(256) void k_occ_join(const unsigned long long* __restrict__ ucell, uint32_t n_u,
-                                                  const unsigned long long* __restrict__ skey, uint32_t n_s,
-                                                  uint32_t* __restrict__ ulb, uint32_t* __restrict__ is_new) {
+static __global__ __launch_bounds__(256) void k_occ_join(const unsigned long long* __restrict__ ucell, uint32_t n_u,
+                                                         const unsigned long long* __restrict__ skey, uint32_t n_s,
+                                                         uint32_t* __restrict__ ulb, uint32_t* __restrict__ is_new) {
   const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u > n_u) return;
   if (u == n_u) {
@@ -181,14 +183,14 @@ __global__ __launch_bounds__(256) void k_occ_join(const unsigned long long* __re
 // Threads [0, n_s): the stored cells; threads [n_s, n_s + n_u): the touched cells that are new.  Everybody computes its own
 // place in the merged, ascending sequence (stored cell s: s + new cells below it; new cell u: its rank among the new ones +
 // stored cells below it), applies the rule once, and leaves keep / occupied flags: keep << 32 | occupied.
-__global__ __launch_bounds__(256) void k_occ_merge(const unsigned long long* __restrict__ skey, const int* __restrict__ slo,
-                                                   uint32_t n_s, const unsigned long long* __restrict__ ucell,
-                                                   const uint32_t* __restrict__ uh, const uint32_t* __restrict__ um,
-                                                   const uint32_t* __restrict__ ulb, const uint32_t* __restrict__ is_new,
-                                                   const uint32_t* __restrict__ new_rank /* exclusive, n_u + 1 */, uint32_t n_u,
-                                                   Rule rule, int4 evict /* {cx,cy,cz,dist}; w < 0: off */, uint32_t metric,
-                                                   unsigned long long* __restrict__ mkey, int* __restrict__ mlo,
-                                                   unsigned long long* __restrict__ flags) {
+static __global__ __launch_bounds__(256) void k_occ_merge(const unsigned long long* __restrict__ skey, const int* __restrict__ slo,
+                                                          uint32_t n_s, const unsigned long long* __restrict__ ucell,
+                                                          const uint32_t* __restrict__ uh, const uint32_t* __restrict__ um,
+                                                          const uint32_t* __restrict__ ulb, const uint32_t* __restrict__ is_new,
+                                                          const uint32_t* __restrict__ new_rank /* exclusive, n_u + 1 */, uint32_t n_u,
+                                                          Rule rule, int4 evict /* {cx,cy,cz,dist}; w < 0: off */, uint32_t metric,
+                                                          unsigned long long* __restrict__ mkey, int* __restrict__ mlo,
+                                                          unsigned long long* __restrict__ flags) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_s + n_u) return;
   if (t == 0) flags[n_s + n_u] = 0ull;  // (the entry behind the last place: the scan leaves the totals there)
@@ -222,11 +224,11 @@ __global__ __launch_bounds__(256) void k_occ_merge(const unsigned long long* __r
 }
 
 // scan = exclusive prefix sum of the flags (n + 1 entries; the last one holds the totals)
-__global__ __launch_bounds__(256) void k_occ_compact(const unsigned long long* __restrict__ mkey, const int* __restrict__ mlo,
-                                                     const unsigned long long* __restrict__ flags,
-                                                     const unsigned long long* __restrict__ scan, uint32_t n, float resolution,
-                                                     unsigned long long* __restrict__ okey, int* __restrict__ olo,
-                                                     float* __restrict__ cx, float* __restrict__ cy, float* __restrict__ cz) {
+static __global__ __launch_bounds__(256) void k_occ_compact(const unsigned long long* __restrict__ mkey, const int* __restrict__ mlo,
+                                                            const unsigned long long* __restrict__ flags,
+                                                            const unsigned long long* __restrict__ scan, uint32_t n, float resolution,
+                                                            unsigned long long* __restrict__ okey, int* __restrict__ olo,
+                                                            float* __restrict__ cx, float* __restrict__ cy, float* __restrict__ cz) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const unsigned long long f = flags[i];

@@ -7,96 +7,17 @@
 // into per-cell hit / miss counts, merge-joins those with the store, applies the update rule once per cell, removes far
 // cells, and rebuilds the inner mh_map from the occupied centres.  Every step is independent of thread order.
 #include <math.h>
-#include <string.h>  // (rocPRIM's texture iterator calls the host memset without declaring it)
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <new>
 #include <vector>
 
-#include "mh_k_occ.h"
+#include "mh_occmap_internal.h"
 
 using namespace mh;
 using namespace mh::occ;
 
-struct mh_occmap {
-  mh_ctx* ctx = nullptr;
-  mh_occmap_params params{};
-  float inv_res = 1.f;
-  Rule rule{};
-  uint64_t max_keys_per_pass = 0;
-  // the store: ping-pong pair of (keys, log-odds); `cur` is the valid one
-  DevBuf skey[2], slo[2];
-  int cur = 0;
-  uint64_t n_cells = 0, n_occupied = 0;
-  // the occupied centres (ascending key order) and the search map built from them
-  DevBuf cx, cy, cz;
-  mh_map* inner = nullptr;
-  float V = 1.f;
-  // last insert
-  uint64_t n_left_out = 0, n_keys = 0;
-  uint32_t n_passes = 0;
-  // scratch
-  DevBuf ray_e, items, prefix, counters;   // per ray
-  DevBuf pk, pks, rk, rc;                  // per pass: keys, sorted keys, run keys, run counts
-  DevBuf ak[2], ac[2], mk, mc;             // accumulated (key, count) entries of all passes; merge scratch
-  DevBuf head, pos, ucell, uh, um, ulb, is_new, new_rank;  // per touched cell
-  DevBuf mkey, mlo, flags, fscan;          // merged sequence
-  DevBuf tmp;                              // rocPRIM temporary storage
-  unsigned long long* h_rb = nullptr;      // pinned [4]: read-backs
-};
-
 namespace {
-
-constexpr uint64_t kDefaultKeysPerPass = 1ull << 24;  // 128 MiB of keys, and as much again sorted
-
-inline uint32_t nblk(size_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
-
-struct ToU64 {
-  __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
-};
-
-mh_status inner_rebuild(mh_occmap* o) {
-  return mh_map_build(o->inner, o->cx.as<float>(), o->cy.as<float>(), o->cz.as<float>(), o->n_occupied, MH_MEM_DEVICE);
-}
-
-// A search map of voxel size v over the present centres in place of the present one.  The new map is complete before the old
-// one goes: a failure leaves the occupancy map, its search map and its V as they were.
-mh_status inner_replace(mh_occmap* o, float v) {
-  mh_map_params mp{};
-  mp.voxel_size = v;
-  mp.max_points_per_voxel = 0;
-  mp.index_mode = o->params.index_mode;
-  mp.far_voxel_metric = o->params.far_voxel_metric;
-  mh_map* fresh = nullptr;
-  MH_TRY(mh_map_create(o->ctx, &mp, &fresh));
-  const mh_status st = mh_map_build(fresh, o->cx.as<float>(), o->cy.as<float>(), o->cz.as<float>(), o->n_occupied, MH_MEM_DEVICE);
-  if (st != MH_OK) {
-    (void)mh_map_destroy(fresh);
-    return st;
-  }
-  (void)mh_map_destroy(o->inner);
-  o->inner = fresh;
-  o->V = v;
-  return MH_OK;
-}
-
-// read `n` 64-bit words from the device (blocking)
-mh_status read_back(mh_occmap* o, const void* src, size_t n, hipStream_t s) {
-  MH_HIP(hipMemcpyAsync(o->h_rb, src, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  MH_HIP(mh::wait_stream(s));
-  return MH_OK;
-}
-
-template <class F>
-mh_status with_tmp(mh_occmap* o, F&& call) {  // rocPRIM's two-call protocol
-  size_t bytes = 0;
-  MH_HIP(call(nullptr, bytes));
-  MH_TRY(o->tmp.reserve(bytes ? bytes : 256));
-  bytes = o->tmp.bytes;
-  MH_HIP(call(o->tmp.p, bytes));
-  return MH_OK;
-}
 
 // log-odds of a probability, scale 16
 double lo16(double p) { return 16.0 * log(p / (1.0 - p)); }
@@ -158,8 +79,10 @@ mh_status mh_occmap_destroy(mh_occmap* o) {
   for (DevBuf* b : {&o->skey[0], &o->skey[1], &o->slo[0], &o->slo[1], &o->cx, &o->cy, &o->cz, &o->ray_e, &o->items, &o->prefix,
                     &o->counters, &o->pk, &o->pks, &o->rk, &o->rc, &o->ak[0], &o->ak[1], &o->ac[0], &o->ac[1], &o->mk, &o->mc,
                     &o->head, &o->pos, &o->ucell, &o->uh, &o->um, &o->ulb, &o->is_new, &o->new_rank, &o->mkey, &o->mlo,
-                    &o->flags, &o->fscan, &o->tmp})
+                    &o->flags, &o->fscan, &o->tmp, &o->f_up, &o->f_rayf, &o->f_pf, &o->f_pfs, &o->f_ek, &o->f_ev, &o->f_ak[0],
+                    &o->f_ak[1], &o->f_af[0], &o->f_af[1], &o->f_ac[0], &o->f_ac[1], &o->f_ustart, &o->f_unew, &o->f_grid})
     b->release();
+  o->f_h.release();
   delete o;
   return MH_OK;
 }

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "molahip.h"
+#include "molahip_occgrid.h"
 #include "molahip_host/local_map_file.h"
 
 namespace mp2p_icp_hip {
@@ -296,6 +297,15 @@ class CVoxelMap : public HashedVoxelPointCloud {
   void insertPoints(const float* x, const float* y, const float* z, size_t n) override;  //  seen from are no input of this map: both throw)
   void insertPointCloud(const DevicePointCloud& pc, const CPose3D& robot_pose, float remove_voxels_farther_than) override;
   void insertFrames(const std::vector<PosedFrame>& frames, uint64_t max_points_per_pass = 0) override;  // throws: an occupancy map is updated by ray tracing
+  // a whole group of key-frames ray-traced at once (mh_occmap_insert_frames, include/molahip_occgrid.h): bit for bit what
+  // insertPointCloud(frame, pose, 0) gives when called for every frame in order.  max_points_per_pass 0: the library's.
+  void insertPointCloudFrames(const std::vector<PosedFrame>& frames, uint64_t max_points_per_pass = 0);
+  // per-axis minimum and maximum cell index over the stored cells (mh_occmap_index_bounds); false on an empty map
+  bool indexBounds(int32_t lo[3], int32_t hi[3]) const;
+  // the maximum log-odds per column of a height band (mh_occmap_project_grid): ny * nx entries, y outer, MH_OCCGRID_NONE
+  // where the band holds no stored cell
+  std::vector<int32_t> projectGrid(const mh_occgrid_window& window) const;
+  mh_occmap_info occInfo() const;
   void clear() override;
   size_t size() const override;
   size_t voxelCount() const override;

@@ -431,6 +431,32 @@ void CVoxelMap::insertFrames(const std::vector<PosedFrame>&, uint64_t) {
   throw std::runtime_error("CVoxelMap::insertFrames: an occupancy map is updated by ray tracing from the pose each scan was seen from "
                            "(insertPointCloud), not by inserting point layers; it has no batched insertion");
 }
+void CVoxelMap::insertPointCloudFrames(const std::vector<PosedFrame>& frames, uint64_t max_points_per_pass) {
+  std::vector<mh_map_frame> f(frames.size());
+  for (size_t k = 0; k < frames.size(); k++) {
+    f[k].x = frames[k].x; f[k].y = frames[k].y; f[k].z = frames[k].z;
+    f[k].n = frames[k].n;
+    std::copy(frames[k].pose.T, frames[k].pose.T + 12, f[k].T);
+  }
+  const mh_status st = mh_occmap_insert_frames(occ_, f.data(), f.size(), MH_MEM_HOST, max_points_per_pass);
+  prepareSearch(0.0);  // (a failed call may have applied earlier passes: the search map is the occupancy map's present one)
+  check(st, "mh_occmap_insert_frames");
+}
+bool CVoxelMap::indexBounds(int32_t lo[3], int32_t hi[3]) const {
+  uint64_t n = 0;
+  check(mh_occmap_index_bounds(occ_, lo, hi, &n), "mh_occmap_index_bounds");
+  return n > 0;
+}
+std::vector<int32_t> CVoxelMap::projectGrid(const mh_occgrid_window& window) const {
+  std::vector<int32_t> out((size_t)window.nx * window.ny);
+  check(mh_occmap_project_grid(occ_, &window, out.data()), "mh_occmap_project_grid");
+  return out;
+}
+mh_occmap_info CVoxelMap::occInfo() const {
+  mh_occmap_info i;
+  check(mh_occmap_get_info(occ_, &i), "mh_occmap_get_info");
+  return i;
+}
 void CVoxelMap::clear() {
   check(mh_occmap_clear(occ_), "mh_occmap_clear");
   prepareSearch(0.0);

@@ -44,6 +44,7 @@
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
 #include "mola_lidar_odometry_hip/LoopClosure.h"
 #include "mola_lidar_odometry_hip/MapCleaning.h"
+#include "mola_lidar_odometry_hip/OccupancyGrid.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "molahip.h"
 
@@ -338,6 +339,7 @@ int main(int argc, char** argv) {
   std::string close_from, loop_report;  // --close-loops, --loop-report
   std::vector<std::string> join_files;  // --join-sessions A B
   std::vector<std::string> clean_files;  // --clean-keyframes IN OUT
+  std::vector<std::string> grid_files;   // --build-occupancy-grid KEYFRAMES OUT_PREFIX
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
                       "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE] [--relocalize-in-keyframes]\n"
@@ -345,6 +347,7 @@ int main(int argc, char** argv) {
                       "       molahip-lo-cli --close-loops KEYFRAMES --pipeline FILE.yaml --output-simplemap FILE [--output-session-map FILE] [--loop-report FILE.json] [--device N]\n"
                       "       molahip-lo-cli --join-sessions KEYFRAMES_A KEYFRAMES_B --pipeline FILE.yaml --output-simplemap FILE [--output-session-map FILE] [--loop-report FILE.json] [--device N]\n"
                       "       molahip-lo-cli --clean-keyframes KEYFRAMES_IN KEYFRAMES_OUT [-c FILE.yaml] [--device N]\n"
+                      "       molahip-lo-cli --build-occupancy-grid KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
@@ -364,6 +367,9 @@ int main(int argc, char** argv) {
                       "  --clean-keyframes: no sequence is run: points that other key-frames look straight through (moving objects) are taken out of\n"
                       "  the key-frames of KEYFRAMES_IN (the pipeline's map_cleaning: block; -c or --pipeline, optional) and the set goes to KEYFRAMES_OUT;\n"
                       "  run it after --close-loops / --join-sessions and before --build-session-map\n"
+                      "  --build-occupancy-grid: no sequence is run: every key-frame of KEYFRAMES is ray-traced from its pose into an occupancy map and a\n"
+                      "  height band of it is projected to a 2-D grid (the pipeline's occupancy_grid: block; -c or --pipeline, optional), written as\n"
+                      "  OUT_PREFIX.pgm and OUT_PREFIX.yaml for a map server; a key-frame file of any plan is taken\n"
                       "  --relocalize-in-keyframes: the vehicle is found in a saved session without a prior pose: place recognition over the\n"
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
@@ -410,6 +416,10 @@ int main(int argc, char** argv) {
         clean_files.push_back(val("--clean-keyframes"));
         clean_files.push_back(val("--clean-keyframes"));
       }
+      else if (a == "--build-occupancy-grid") {
+        grid_files.push_back(val("--build-occupancy-grid"));
+        grid_files.push_back(val("--build-occupancy-grid"));
+      }
       else if (a == "--relocalize-in-keyframes") opt.relocalize_in_keyframes = true;
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
@@ -419,6 +429,30 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n%s", e.what(), usage);
       return 2;
     }
+  }
+  if (!grid_files.empty()) {  // a navigation occupancy grid from a recorded drive's key-frames, no sequence
+    if (grid_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty() || !clean_files.empty()) {
+      fprintf(stderr, "--build-occupancy-grid takes one key-frame file to read and one output prefix, once, and takes no sequence\n%s", usage);
+      return 2;
+    }
+    try {
+      const mola_hip::OccupancyGridOptions gopt =
+          mola_hip::OccupancyGridOptions::FromConfig(pipeline.empty() ? mp2p_icp_hip::Config::FromYamlText("") : mp2p_icp_hip::Config::FromYamlFile(pipeline));
+      const molahip_host::KeyFrameSet set = molahip_host::read_keyframe_file(grid_files[0]);  // (a missing file is refused before a device is asked for)
+      auto ctx = std::make_shared<mp2p_icp_hip::DeviceContext>(devices.empty() ? 0 : devices[0]);
+      const mola_hip::OccupancyGrid g = mola_hip::build_occupancy_grid(set, gopt, ctx);
+      mola_hip::write_occupancy_grid(g, grid_files[1]);
+      printf("{\"keyframe_file\": \"%s\", \"occupancy_grid\": \"%s\", \"frames\": %llu, \"points\": %llu, \"map_cells\": %llu, \"grid_x0\": %d, "
+             "\"grid_y0\": %d, \"grid_nx\": %u, \"grid_ny\": %u, \"cells_occupied\": %llu, \"cells_free\": %llu, \"cells_unknown\": %llu, "
+             "\"seconds_insert\": %.6f, \"seconds_project\": %.6f}\n",
+             grid_files[0].c_str(), grid_files[1].c_str(), (unsigned long long)g.frames, (unsigned long long)g.points, (unsigned long long)g.map_cells,
+             g.x0, g.y0, g.nx, g.ny, (unsigned long long)g.cells_occupied, (unsigned long long)g.cells_free, (unsigned long long)g.cells_unknown,
+             g.seconds_insert, g.seconds_project);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "molahip-lo-cli: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (!clean_files.empty()) {  // moving objects taken out of a recorded drive's key-frames, no sequence
     if (clean_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty()) {

@@ -9,6 +9,7 @@
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
 #include "mola_lidar_odometry_hip/LoopClosure.h"
 #include "mola_lidar_odometry_hip/MapCleaning.h"
+#include "mola_lidar_odometry_hip/OccupancyGrid.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 #include "molahip_host/plugin_switches.h"
@@ -134,7 +135,42 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
         pc.setPoints(c->x.data(), c->y.data(), c->z.data(), c->size());
         v.insertPointCloud(pc, P, remove_voxels_farther_than);
       }, py::arg("xyz"), py::arg("T"), py::arg("remove_voxels_farther_than") = 0.f)
-      .def("searchVoxelSize", &CVoxelMap::searchVoxelSize);
+      .def("searchVoxelSize", &CVoxelMap::searchVoxelSize)
+      // frames: a list of (xyz [n, 3], T [12]) ray-traced at once (mh_occmap_insert_frames)
+      .def("insertPointCloudFrames", [](CVoxelMap& v, const std::vector<std::pair<py::array_t<float, py::array::c_style | py::array::forcecast>, std::vector<double>>>& frames,
+                                        uint64_t max_points_per_pass) {
+        std::vector<decltype(make_cloud(frames[0].first))> clouds;
+        std::vector<PosedFrame> f;
+        for (const auto& [xyz, T] : frames) {
+          if (T.size() != 12) throw std::runtime_error("need 12 values");
+          clouds.push_back(make_cloud(xyz));
+          PosedFrame pf;
+          pf.x = clouds.back()->x.data(); pf.y = clouds.back()->y.data(); pf.z = clouds.back()->z.data();
+          pf.n = clouds.back()->size();
+          std::copy(T.begin(), T.end(), pf.pose.T);
+          f.push_back(pf);
+        }
+        v.insertPointCloudFrames(f, max_points_per_pass); }, py::arg("frames"), py::arg("max_points_per_pass") = 0)
+      // (lo [3], hi [3]) of the stored cells' indices, or None for an empty map
+      .def("indexBounds", [](const CVoxelMap& v) -> py::object {
+        int32_t lo[3], hi[3];
+        if (!v.indexBounds(lo, hi)) return py::none();
+        return py::make_tuple(py::make_tuple(lo[0], lo[1], lo[2]), py::make_tuple(hi[0], hi[1], hi[2])); })
+      // int32 [ny, nx]: the maximum log-odds per column of the band z_lo..z_hi (cell indices), INT32_MIN where nothing is stored
+      .def("projectGrid", [](const CVoxelMap& v, int32_t x0, int32_t y0, uint32_t nx, uint32_t ny, int32_t z_lo, int32_t z_hi) {
+        mh_occgrid_window w{};
+        w.x0 = x0; w.y0 = y0; w.nx = nx; w.ny = ny; w.z_lo = z_lo; w.z_hi = z_hi;
+        const std::vector<int32_t> g = v.projectGrid(w);
+        py::array_t<int32_t> out({(py::ssize_t)ny, (py::ssize_t)nx});
+        std::copy(g.begin(), g.end(), out.mutable_data());
+        return out; }, py::arg("x0"), py::arg("y0"), py::arg("nx"), py::arg("ny"), py::arg("z_lo"), py::arg("z_hi"))
+      // (keys int32 [n, 3], log-odds int32 [n]) in ascending key order
+      .def("download", [](const CVoxelMap& v) {
+        std::vector<int32_t> k, l;
+        v.download(k, l);
+        py::array_t<int32_t> keys({(py::ssize_t)l.size(), (py::ssize_t)3});
+        std::copy(k.begin(), k.end(), keys.mutable_data());
+        return py::make_tuple(keys, py::array_t<int32_t>((py::ssize_t)l.size(), l.data())); });
   py::class_<NDT, HashedVoxelPointCloud, std::shared_ptr<NDT>>(m, "NDT")
       .def(py::init([](float vs, uint32_t cap, float min_dist, float ratio) { return std::make_shared<NDT>(vs, cap, min_dist, ratio); }))
       .def("planeCount", &NDT::planeCount);
@@ -1240,6 +1276,78 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     rep["seconds"] = r.report.seconds; rep["json"] = r.report.toJson();
     return py::make_tuple(kfset2dict(r.cleaned), rep); },
         py::arg("frames"), py::arg("options") = py::none(), py::arg("output_keyframe_file") = "");
+  // ---- a navigation occupancy grid from key-frames (mola_lidar_odometry_hip/OccupancyGrid.h)
+  using mola_hip::OccupancyGrid;
+  using mola_hip::OccupancyGridOptions;
+  // `options`: a pipeline Config, or the YAML text of one (its occupancy_grid: block is read; absent: the defaults)
+  auto grid_opts = [](const py::object& options) {
+    if (options.is_none()) return OccupancyGridOptions::FromConfig(Config::FromYamlText(""));
+    if (py::isinstance<py::str>(options)) return OccupancyGridOptions::FromConfig(Config::FromYamlText(options.cast<std::string>()));
+    return OccupancyGridOptions::FromConfig(options.cast<const Config&>());
+  };
+  auto grid2dict = [](const OccupancyGrid& g) {
+    py::dict d;
+    d["x0"] = g.x0; d["y0"] = g.y0; d["nx"] = g.nx; d["ny"] = g.ny; d["resolution"] = g.resolution;
+    d["z_lo"] = g.z_lo; d["z_hi"] = g.z_hi; d["l_occ"] = g.l_occ;
+    py::array_t<int32_t> mx({(py::ssize_t)(g.max_logodds.empty() ? 0 : g.ny), (py::ssize_t)g.nx});
+    std::copy(g.max_logodds.begin(), g.max_logodds.end(), mx.mutable_data());
+    py::array_t<int8_t> cells({(py::ssize_t)g.ny, (py::ssize_t)g.nx});
+    std::copy(g.cells.begin(), g.cells.end(), cells.mutable_data());
+    d["max_logodds"] = mx; d["cells"] = cells;
+    d["cells_occupied"] = g.cells_occupied; d["cells_free"] = g.cells_free; d["cells_unknown"] = g.cells_unknown;
+    d["frames"] = g.frames; d["points"] = g.points; d["map_cells"] = g.map_cells;
+    d["seconds_insert"] = g.seconds_insert; d["seconds_project"] = g.seconds_project;
+    return d;
+  };
+  auto dict2grid = [](const py::dict& d) {
+    OccupancyGrid g;
+    g.x0 = d["x0"].cast<int32_t>(); g.y0 = d["y0"].cast<int32_t>(); g.nx = d["nx"].cast<uint32_t>(); g.ny = d["ny"].cast<uint32_t>();
+    g.resolution = d["resolution"].cast<double>();
+    if (d.contains("l_occ")) g.l_occ = d["l_occ"].cast<int32_t>();
+    if (d.contains("max_logodds") && !d.contains("cells")) {
+      auto mx = d["max_logodds"].cast<py::array_t<int32_t, py::array::c_style | py::array::forcecast>>();
+      g.max_logodds.assign(mx.data(), mx.data() + mx.size());
+      mola_hip::occupancy_grid_classify(g);
+    } else {
+      auto c = d["cells"].cast<py::array_t<int8_t, py::array::c_style | py::array::forcecast>>();
+      g.cells.assign(c.data(), c.data() + c.size());
+    }
+    return g;
+  };
+  m.def("occupancy_grid_options", [grid_opts](const py::object& options) {
+    const OccupancyGridOptions o = grid_opts(options);
+    py::dict d;
+    d["resolution"] = o.resolution; d["prob_hit"] = o.prob_hit; d["prob_miss"] = o.prob_miss; d["clamp_min"] = o.clamp_min;
+    d["clamp_max"] = o.clamp_max; d["occupied_threshold"] = o.occupied_threshold; d["ray_trace_free_space"] = o.ray_trace_free_space;
+    d["max_range"] = o.max_range; d["decimation"] = o.decimation; d["update_rule"] = o.update_rule; d["target_map"] = o.target_map;
+    d["z_min"] = o.z_min; d["z_max"] = o.z_max; d["margin_cells"] = o.margin_cells;
+    d["z_lo"] = mola_hip::occupancy_grid_z_index(o.z_min, o.resolution); d["z_hi"] = mola_hip::occupancy_grid_z_index(o.z_max, o.resolution);
+    return d; }, py::arg("options") = py::none());
+  m.def("occupancy_grid_z_index", &mola_hip::occupancy_grid_z_index, py::arg("z"), py::arg("resolution"));
+  // int32 maxima [ny, nx] + l_occ -> (int8 cells [ny, nx], occupied, free, unknown): the trinary rule
+  m.def("occupancy_grid_classify", [](py::array_t<int32_t, py::array::c_style | py::array::forcecast> max_logodds, int32_t l_occ) {
+    if (max_logodds.ndim() != 2) throw std::runtime_error("occupancy_grid_classify: max_logodds must be [ny, nx]");
+    OccupancyGrid g;
+    g.ny = (uint32_t)max_logodds.shape(0); g.nx = (uint32_t)max_logodds.shape(1); g.l_occ = l_occ;
+    g.max_logodds.assign(max_logodds.data(), max_logodds.data() + max_logodds.size());
+    mola_hip::occupancy_grid_classify(g);
+    py::array_t<int8_t> cells({(py::ssize_t)g.ny, (py::ssize_t)g.nx});
+    std::copy(g.cells.begin(), g.cells.end(), cells.mutable_data());
+    return py::make_tuple(cells, g.cells_occupied, g.cells_free, g.cells_unknown); }, py::arg("max_logodds"), py::arg("l_occ"));
+  // a key-frame set (a dict, or the path of a key-frame file) -> the grid as a dict
+  m.def("build_occupancy_grid", [dict2kfset, grid_opts, grid2dict](const py::object& frames, const py::object& options, uint64_t max_points_per_pass) {
+    const molahip_host::KeyFrameSet set = py::isinstance<py::str>(frames) ? molahip_host::read_keyframe_file(frames.cast<std::string>())
+                                                                         : dict2kfset(frames.cast<py::dict>());
+    const OccupancyGridOptions o = grid_opts(options);
+    OccupancyGrid g;
+    {
+      py::gil_scoped_release nogil;
+      g = mola_hip::build_occupancy_grid(set, o, nullptr, max_points_per_pass);
+    }
+    return grid2dict(g); }, py::arg("frames"), py::arg("options") = py::none(), py::arg("max_points_per_pass") = 0);
+  m.def("write_occupancy_grid", [dict2grid](const py::dict& grid, const std::string& prefix) { mola_hip::write_occupancy_grid(dict2grid(grid), prefix); },
+        py::arg("grid"), py::arg("prefix"));
+  m.def("read_occupancy_grid", [grid2dict](const std::string& prefix) { return grid2dict(mola_hip::read_occupancy_grid(prefix)); }, py::arg("prefix"));
   // the pose rules of the driver's online loop closure and the motion model's rebase, on 12-value poses
   auto to_pose = [](const std::vector<double>& T) {
     if (T.size() != 12) throw std::runtime_error("a pose has 12 values");
