@@ -27,7 +27,8 @@
 // unless generate is on.
 //
 // Host code here is control logic only; every point touches the GPU through include/molahip.h.  What is NOT here:
-// MOLA module plumbing, IMU/GNSS/wheel inputs, MRPT .simplemap serialisation, visualisation, ROS.
+// MOLA module plumbing, IMU/GNSS/wheel inputs (but for the gyroscope rate of gyro_deskew:, GyroDeskew.h), MRPT .simplemap
+// serialisation, visualisation, ROS.
 #pragma once
 #include <functional>
 #include <map>
@@ -37,6 +38,7 @@
 #include <string>
 #include <vector>
 
+#include "mola_lidar_odometry_hip/GyroDeskew.h"
 #include "mola_lidar_odometry_hip/LiveMapCleaning.h"
 #include "molahip_host/keyframe_file.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
@@ -451,6 +453,10 @@ class LidarOdometry {
     // online_map_cleaning: this scan's local map update was followed by an erasing of the target maps (LiveMapCleaning.h);
     // n_map_points / n_map_voxels are then the counts AFTER the erasing
     bool map_cleaned = false;
+    // gyro_deskew: this scan's 2nd pass de-skewed with a motion table of gyro_segments segments cut from the gyro samples
+    // (false with the block enabled: the samples did not cover the sweep and the constant twist was used)
+    bool gyro_deskew = false;
+    uint32_t gyro_segments = 0;
   };
 
   // ctx == nullptr: the process-wide default device context, taken at initialize()
@@ -616,6 +622,18 @@ class LidarOdometry {
   // would bring the erased points back), an AlignBatcher (setAlignBatcher refuses too).
   const OnlineMapCleaningOptions& onlineMapCleaningOptions() const { return live_opts_; }
   uint64_t mapPointsErased() const;  // points erased from the target maps since they were created (waits for the device)
+  // gyro_deskew: (GyroDeskew.h) -- enabled: onGyro() feeds a GyroBuffer (any time, any thread that also calls onLidar*: not
+  // concurrently with them); every scan that reaches its 2nd pass asks build_motion_table(buffer, its time stamp, the options)
+  // ONCE for the rotations of its sweep, and both the default plan's de-skew pair and every FilterDeskew step of a general plan
+  // then call mh_scan_deskew_motion[_pair] with them and the current vx, vy, vz -- the twist hook re-runs the pass with a new v
+  // and the same rotations (wx, wy, wz are not read).  A scan whose sweep the samples do not cover is de-skewed with the constant
+  // twist as without the block (ScanRecord::gyro_deskew says which).  skip_deskew wins over the block.  initialize() refuses,
+  // naming gyro_deskew: -- a depth-image plan (no time stamps to de-skew by) and an AlignBatcher (setAlignBatcher refuses too).
+  // With the block absent or disabled onGyro() ignores the sample.  Call it after initialize(); reset() empties the buffer.
+  void onGyro(double t, const double w[3]);
+  const GyroDeskewOptions& gyroDeskewOptions() const { return gyro_opts_; }
+  uint64_t scansGyroDeskewed() const { return scans_gyro_deskewed_; }
+  uint64_t gyroSamplesDropped() const { return gyro_buf_.dropped(); }
   std::shared_ptr<HashedVoxelPointCloud> localMap() const { return local_map_; }
   // points of every local map by name (general plans: one per localmap_generator entry; 0 before the first key-frame)
   std::map<std::string, uint64_t> localMapSizes() const;
@@ -788,6 +806,11 @@ class LidarOdometry {
   OnlineMapCleaningOptions live_opts_;
   std::unique_ptr<LiveMapCleaner> live_cleaner_;  // made at the first local map update (the maps and their context exist then)
   bool clean_live_maps();                          // the rule of LiveMapCleaner behind this scan's insertions
+  // gyro_deskew:
+  GyroDeskewOptions gyro_opts_;
+  GyroBuffer gyro_buf_;
+  std::optional<MotionTable> gyro_table_;  // the rotations of the current scan's sweep (v is set at every use)
+  uint64_t scans_gyro_deskewed_ = 0;
   bool input_pinned_ = false;
   bool intensity_input_ = false;  // setIntensityInput
   std::map<std::string, double> profile_;

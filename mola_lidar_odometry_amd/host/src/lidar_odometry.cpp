@@ -1027,6 +1027,9 @@ const char* const kNoRecoveryWithBatcher = "enabled: LidarOdometry::relocalizeIn
 // online_map_cleaning: likewise
 const char* const kNoLiveCleaningWithBatcher = "enabled is not available with an AlignBatcher (the instances of a lock-step batch share one "
                                                "round of alignments; map updates queued between them are not part of its protocol)";
+// gyro_deskew: likewise
+const char* const kNoGyroDeskewWithBatcher = "enabled is not available with an AlignBatcher (a lock-step batch prepares its members' scans with "
+                                             "mh_scan_preprocess_batch and the constant twist; it has no slot for a motion table per member)";
 }  // namespace
 
 void LidarOdometry::initialize(const Config& cfg) {
@@ -1244,6 +1247,19 @@ void LidarOdometry::initialize(const Config& cfg) {
         throw std::runtime_error(who + "enabled together with online_loop_closure: correct_driver: true is not implemented (an accepted closure "
                                  "rebuilds the local maps from the key-frames, which would bring the erased points back)");
       if (batcher_) throw std::runtime_error(who + kNoLiveCleaningWithBatcher);  // (setAlignBatcher says the same when it comes second)
+    }
+  }
+
+  // gyro_deskew: (GyroDeskew.h): read and checked whether enabled or not
+  {
+    gyro_opts_ = GyroDeskewOptions::FromConfig(cfg);
+    gyro_buf_.setBufferSeconds(gyro_opts_.buffer_seconds);
+    if (gyro_opts_.enabled) {
+      const std::string who = "LidarOdometry (HIP): gyro_deskew: ";
+      if (gplan_ && gplan_->depth_input)
+        throw std::runtime_error(who + "enabled on a depth-image pipeline (GeneratorEdgesFromRangeImage): its pixels carry no time stamps, "
+                                 "there is nothing to de-skew by");
+      if (batcher_) throw std::runtime_error(who + kNoGyroDeskewWithBatcher);  // (setAlignBatcher says the same when it comes second)
     }
   }
 
@@ -1795,6 +1811,9 @@ void LidarOdometry::reset() {
   map_known_nonempty_ = false;
   navstate_.reset();
   live_cleaner_.reset();  // (online_map_cleaning: the ring goes with the maps)
+  gyro_buf_.clear();      // (gyro_deskew: the samples, the drop count and the scan count start again)
+  gyro_table_.reset();
+  scans_gyro_deskewed_ = 0;
   local_map_.reset();
   if (gplan_) {
     for (auto& m : gplan_->maps) m.map.reset();
@@ -1935,7 +1954,13 @@ void LidarOdometry::run_general_pass(int pass) {
       check(mh_scan_by_intensity(in, &bp, o[0], o[1], o[2]), "mh_scan_by_intensity");
     } else if (st.kind == K::Deskew) {
       const double tw[6] = {v.at("vx"), v.at("vy"), v.at("vz"), v.at("wx"), v.at("wy"), v.at("wz")};
-      check(mh_scan_deskew(in, st.skip_deskew ? nullptr : tw, layer(st.out[0])->handle()), "mh_scan_deskew");
+      if (gyro_table_ && !st.skip_deskew) {  // gyro_deskew: the measured rotations of this sweep, the current v
+        for (int a = 0; a < 3; a++) gyro_table_->v[a] = tw[a];
+        const mh_motion_table mt = gyro_table_->table();
+        check(mh_scan_deskew_motion(in, &mt, layer(st.out[0])->handle()), "mh_scan_deskew_motion");
+      } else {
+        check(mh_scan_deskew(in, st.skip_deskew ? nullptr : tw, layer(st.out[0])->handle()), "mh_scan_deskew");
+      }
     } else if (st.kind == K::Preprocess) {
       const mh_preprocess_params pp = make_pp(st.res, 0, st.min_points, st.range_min, st.range_on ? st.range_max : 0, st.bbox_mode,
                                               st.bbox_min, st.bbox_max, MH_TS_NONE, 0, st.method);
@@ -1998,6 +2023,8 @@ void LidarOdometry::setAlignBatcher(std::shared_ptr<mp2p_icp_hip::AlignBatcher> 
     throw std::runtime_error(std::string("LidarOdometry::setAlignBatcher: not available with lost_recovery: ") + kNoRecoveryWithBatcher);
   if (b && live_opts_.enabled)
     throw std::runtime_error(std::string("LidarOdometry::setAlignBatcher: not available with online_map_cleaning: ") + kNoLiveCleaningWithBatcher);
+  if (b && gyro_opts_.enabled)
+    throw std::runtime_error(std::string("LidarOdometry::setAlignBatcher: not available with gyro_deskew: ") + kNoGyroDeskewWithBatcher);
   if (b && (!ctx_ || ctx_ == DeviceContext::Default()))
     throw std::runtime_error("LidarOdometry::setAlignBatcher: this instance uses the process-wide default context; construct "
                              "it with a DeviceContext of its own");
@@ -2110,6 +2137,13 @@ void LidarOdometry::run_second_pass() {
   const auto& v = source_.getVariableValues();
   const double tw[6] = {v.at("vx"), v.at("vy"), v.at("vz"), v.at("wx"), v.at("wy"), v.at("wz")};
   const double* twp = plan_->skip_deskew ? nullptr : tw;
+  if (gyro_table_ && twp) {  // gyro_deskew: the measured rotations of this sweep, the current v
+    for (int a = 0; a < 3; a++) gyro_table_->v[a] = tw[a];
+    const mh_motion_table mt = gyro_table_->table();
+    check(mh_scan_deskew_motion_pair(cur_map_skewed_->handle(), cur_icp_skewed_->handle(), &mt, for_map_->handle(), for_icp_->handle(),
+                                     icp_bb_min_, icp_bb_max_, nullptr), "mh_scan_deskew_motion_pair");
+    return;
+  }
   // both layers and the bounding box of the de-skewed ICP layer (read by the sensor-range estimate right below) at once
   check(mh_scan_deskew_pair(cur_map_skewed_->handle(), cur_icp_skewed_->handle(), twp, for_map_->handle(), for_icp_->handle(),
                             icp_bb_min_, icp_bb_max_, nullptr), "mh_scan_deskew_pair");
@@ -2439,6 +2473,16 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
       if (in.t) raw_->setTimestamps(in.t, n);
     }
   }
+  gyro_table_.reset();
+  // gyro_deskew: the rotations of this sweep, once per scan and before either pass (a general plan may de-skew in its first; the
+  // twist hook changes v only)
+  if (gyro_opts_.enabled && (merged || has_t)) {
+    bool deskews = plan_ && !plan_->skip_deskew;  // (skip_deskew wins over the block; a scan without stamps is copied either way)
+    if (gplan_)
+      for (const auto& st : gplan_->steps) deskews = deskews || (st.kind == GeneralPlan::Kind::Deskew && !st.skip_deskew);
+    const double zero[3] = {0, 0, 0};
+    if (deskews) gyro_table_ = build_motion_table(gyro_buf_, this_obs_tim, gyro_opts_, zero);
+  }
   if (!prepared) {
     StageTimer tt(profile_, "onLidar.1.filter_1st");
     run_first_pass();  // :734
@@ -2446,6 +2490,11 @@ const LidarOdometry::ScanRecord& LidarOdometry::process(double this_obs_tim, con
   {
     StageTimer tt(profile_, "onLidar.1.filter_2nd");
     run_second_pass();  // :739
+  }
+  if (gyro_table_) {
+    rec.gyro_deskew = true;
+    rec.gyro_segments = (uint32_t)gyro_table_->segments.size();
+    scans_gyro_deskewed_++;
   }
   if (gplan_) {
     record_layer_sizes(rec);
@@ -2761,6 +2810,12 @@ uint64_t LidarOdometry::mapPointsErased() const {
   if (gplan_) for (const auto& m : gplan_->maps) add(m.map);
   else add(local_map_);
   return total;
+}
+
+// ---- gyro_deskew: (LidarOdometry.h, GyroDeskew.h)
+void LidarOdometry::onGyro(double t, const double w[3]) {
+  if (!gyro_opts_.enabled) return;  // (the block absent or disabled: nothing is kept, nothing is counted)
+  gyro_buf_.push(t, w);
 }
 
 // ---- online_loop_closure: (LidarOdometry.h, LoopClosure.h)

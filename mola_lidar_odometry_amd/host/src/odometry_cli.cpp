@@ -112,6 +112,8 @@ struct SequenceReport {
   unsigned times_lost = 0, recovery_attempts = 0, times_recovered = 0;  // ... LidarOdometry::timesLost() and its like
   bool online_map_cleaning = false;   // the pipeline's online_map_cleaning: block is enabled ...
   uint64_t map_points_erased = 0;     // ... LidarOdometry::mapPointsErased()
+  bool gyro_deskew = false;           // the pipeline's gyro_deskew: block is enabled ...
+  uint64_t scans_gyro_deskewed = 0;   // ... LidarOdometry::scansGyroDeskewed()
 };
 
 struct RunOptions {
@@ -125,6 +127,7 @@ struct RunOptions {
   bool relocalize_in_keyframes = false;  // --relocalize-in-keyframes: LidarOdometry::relocalizeInKeyFrames() before the first scan
   std::string output_session_map;  // --output-session-map: ... and the maps of the whole drive built from them, as a local-map file (FILE_<k> likewise)
   std::string output_corrected_trajectory;  // --output-corrected-trajectory: LidarOdometry::correctedTrajectory() as a TUM file
+  std::string gyro_file;  // --gyro-file: lines "t wx wy wz" on the clock of the scans' stamps, fed through LidarOdometry::onGyro (gyro_deskew:)
 };
 
 // what the replay leaves behind besides the trajectory: layer and map sizes (records()), optionally a per-scan CSV
@@ -244,12 +247,19 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
     stamp("pipeline initialised");
     if (batcher) lo.setAlignBatcher(batcher);
     if (opt.relocalize_in_keyframes) lo.relocalizeInKeyFrames();  // served by the first scan that reaches registration
+    // --gyro-file: before a scan the driver gets the samples up to the end of that scan's window (and a step beyond, for coverage)
+    std::vector<mola_hip::GyroSample> gyro;
+    size_t gyro_next = 0;
+    if (!opt.gyro_file.empty()) gyro = mola_hip::read_gyro_file(opt.gyro_file);
+    const mola_hip::GyroDeskewOptions& go = lo.gyroDeskewOptions();
+    const double gyro_ahead = go.time_zero_offset + go.window[1] + 2.0 * go.max_gap;
 
     std::vector<float> cur, nxt;  // both stay alive while the driver may still read them
     if (!files.empty()) cur = read_bin(files[0]);
     for (size_t k = 0; k < files.size(); k++) {
       const bool has_next = k + 1 < files.size();
       if (has_next) nxt = read_bin(files[k + 1]);  // (file reading is not part of the registration time)
+      for (; gyro_next < gyro.size() && gyro[gyro_next].t <= stamps[k] + gyro_ahead; gyro_next++) lo.onGyro(gyro[gyro_next].t, gyro[gyro_next].w);
       const auto t0 = std::chrono::steady_clock::now();
       if (has_next && prefetch) lo.prefetchInterleaved(nxt.data(), nxt.size() / 4, 16, 0, 4, 8, opt.time_field, nullptr, opt.intensity_field);
       const auto& rec = lo.onLidarInterleaved(stamps[k], cur.data(), cur.size() / 4, 16, 0, 4, 8, opt.time_field, nullptr, opt.intensity_field);
@@ -279,6 +289,8 @@ void run_sequence(const std::string& pipeline, const std::string& seq_dir, const
     rep.times_lost = lo.timesLost(), rep.recovery_attempts = lo.recoveryAttempts(), rep.times_recovered = lo.timesRecovered();
     rep.online_map_cleaning = lo.onlineMapCleaningOptions().enabled;
     if (rep.online_map_cleaning) rep.map_points_erased = lo.mapPointsErased();
+    rep.gyro_deskew = go.enabled;
+    rep.scans_gyro_deskewed = lo.scansGyroDeskewed();
     stamp("trajectory saved");
     if (!opt.save_local_map.empty()) lo.saveLocalMaps(opt.save_local_map + suffix);  // (what params.local_map_updates.load_existing_local_map of a later run reads)
     if (!opt.output_simplemap.empty()) lo.saveKeyFrames(opt.output_simplemap + suffix);
@@ -374,6 +386,18 @@ int main(int argc, char** argv) {
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
                       "  --devices: the sequences are spread over the listed GPUs (longest first onto the least loaded device)\n";
+  // (shown after it when the run asks for the gyro de-skew: the pipeline's gyro_deskew: block, or the option itself)
+  const char* usage_gyro = "  --gyro-file FILE: gyroscope samples, text lines 't wx wy wz' ([s] on the clock of the scans' stamps, [rad/s]; '#' starts a\n"
+                           "  comment), for the pipeline's gyro_deskew: block: every scan is de-skewed with the rotation measured during its sweep; one\n"
+                           "  sequence only\n";
+  auto gyro_enabled = [&]() {
+    if (pipeline.empty()) return false;
+    try {
+      return mola_hip::GyroDeskewOptions::FromConfig(mp2p_icp_hip::Config::FromYamlFile(pipeline)).enabled;
+    } catch (const std::exception&) {
+      return false;  // (the run itself reports what is wrong with the file)
+    }
+  };
   // (shown after it when the run asks for online loop closure: the pipeline's online_loop_closure: block, or the option itself)
   const char* usage_online = "  --output-corrected-trajectory: with the pipeline's online_loop_closure: block enabled loops are closed while driving; the\n"
                              "  trajectory as the closures correct it goes to FILE (TUM), --out keeps what was estimated at the time; one sequence only\n";
@@ -405,6 +429,7 @@ int main(int argc, char** argv) {
       else if (a == "--output-simplemap") opt.output_simplemap = val("--output-simplemap");
       else if (a == "--output-session-map") opt.output_session_map = val("--output-session-map");
       else if (a == "--output-corrected-trajectory") opt.output_corrected_trajectory = val("--output-corrected-trajectory");
+      else if (a == "--gyro-file") opt.gyro_file = val("--gyro-file");
       else if (a == "--build-session-map") build_from = val("--build-session-map");
       else if (a == "--close-loops") close_from = val("--close-loops");
       else if (a == "--loop-report") loop_report = val("--loop-report");
@@ -563,7 +588,8 @@ int main(int argc, char** argv) {
     return 0;
   }
   if (pipeline.empty() || seq_dirs.empty()) {
-    fprintf(stderr, "%s%s", usage, !opt.output_corrected_trajectory.empty() || online_enabled() ? usage_online : "");
+    fprintf(stderr, "%s%s%s", usage, !opt.output_corrected_trajectory.empty() || online_enabled() ? usage_online : "",
+            !opt.gyro_file.empty() || gyro_enabled() ? usage_gyro : "");
     return 2;
   }
   if (devices.empty()) devices = {0};
@@ -578,6 +604,28 @@ int main(int argc, char** argv) {
       fprintf(stderr, "molahip-lo-cli: the pipeline's online_map_cleaning: block is enabled: one sequence on one device only (several sequences of a "
                       "process align through an AlignBatcher, whose protocol has no place for map updates queued between its rounds)\n");
       return 2;
+    }
+  }
+  {
+    // gyro_deskew: and --gyro-file: one sequence on one device; the file is read (and refused by line) before any device work
+    const bool gyro_on = gyro_enabled();
+    if ((N > 1 || D > 1) && (gyro_on || !opt.gyro_file.empty())) {
+      fprintf(stderr, "molahip-lo-cli: %s: one sequence on one device only (one gyro stream belongs to one drive, and several sequences of a "
+                      "process align through an AlignBatcher, which has no slot for a motion table per member)\n",
+              gyro_on ? "the pipeline's gyro_deskew: block is enabled" : "--gyro-file");
+      return 2;
+    }
+    if (!opt.gyro_file.empty()) {
+      if (!gyro_on) {
+        fprintf(stderr, "molahip-lo-cli: --gyro-file needs the pipeline's gyro_deskew: block with enabled: true (the samples would be ignored)\n");
+        return 2;
+      }
+      try {
+        (void)mola_hip::read_gyro_file(opt.gyro_file);
+      } catch (const std::exception& e) {
+        fprintf(stderr, "molahip-lo-cli: --gyro-file: %s\n", e.what());
+        return 2;
+      }
     }
   }
   if ((N > 1 || D > 1) && online_enabled()) {
@@ -660,6 +708,8 @@ int main(int argc, char** argv) {
       printf(", \"times_lost\": %u, \"recovery_attempts\": %u, \"times_recovered\": %u", r.times_lost, r.recovery_attempts, r.times_recovered);
     if (r.online_map_cleaning)  // (the pipeline's online_map_cleaning: block; absent or disabled, the line is as before)
       printf(", \"map_points_erased\": %llu", (unsigned long long)r.map_points_erased);
+    if (r.gyro_deskew)  // (the pipeline's gyro_deskew: block; absent or disabled, the line is as before)
+      printf(", \"scans_gyro_deskewed\": %llu", (unsigned long long)r.scans_gyro_deskewed);
     printf("}\n");
     if (print_profile && r.scans) {  // host milliseconds per scan and stage (LidarOdometry::profile()), steady state
       const double ns = (double)(r.steady_scans ? r.steady_scans : r.scans);
@@ -724,6 +774,10 @@ int main(int argc, char** argv) {
     bool cleaning = false;
     for (const auto& r : reps) cleaning = cleaning || r.online_map_cleaning, map_points_erased += r.map_points_erased;
     if (cleaning) printf(", \"map_points_erased\": %llu", (unsigned long long)map_points_erased);
+    uint64_t scans_gyro_deskewed = 0;
+    bool gyro = false;
+    for (const auto& r : reps) gyro = gyro || r.gyro_deskew, scans_gyro_deskewed += r.scans_gyro_deskewed;
+    if (gyro) printf(", \"scans_gyro_deskewed\": %llu", (unsigned long long)scans_gyro_deskewed);
     printf("}\n");
   }
   // Everything asked for is on disk and on stdout.  The drivers' destructors would now hipFree a few hundred buffers one by one,

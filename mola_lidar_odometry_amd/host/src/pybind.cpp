@@ -444,6 +444,7 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     d["lost"] = r.lost; d["recovery_attempt"] = r.recovery_attempt; d["recovery_succeeded"] = r.recovery_succeeded; d["bad_streak"] = r.bad_streak;
     d["recovery_gave_up"] = r.recovery_gave_up;
     d["map_cleaned"] = r.map_cleaned;
+    d["gyro_deskew"] = r.gyro_deskew; d["gyro_segments"] = r.gyro_segments;
     return d;
   };
   auto lost2dict = [](const mola_hip::LostRecoveryOptions& o) {
@@ -474,6 +475,52 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     if (py::isinstance<py::str>(options)) return OnlineMapCleaningOptions::FromConfig(Config::FromYamlText(options.cast<std::string>()));
     return OnlineMapCleaningOptions::FromConfig(options.cast<const Config&>());
   };
+  // the gyro_deskew: block (mola_lidar_odometry_hip/GyroDeskew.h) as a dict; `options` as above
+  auto gyro_opts = [](const py::object& options) {
+    using mola_hip::GyroDeskewOptions;
+    if (options.is_none()) return GyroDeskewOptions::FromConfig(Config::FromYamlText(""));
+    if (py::isinstance<py::str>(options)) return GyroDeskewOptions::FromConfig(Config::FromYamlText(options.cast<std::string>()));
+    return GyroDeskewOptions::FromConfig(options.cast<const Config&>());
+  };
+  auto gyro2dict = [](const mola_hip::GyroDeskewOptions& o) {
+    py::dict d;
+    d["enabled"] = o.enabled; d["window"] = std::vector<double>(o.window, o.window + 2); d["segments"] = o.segments; d["max_gap"] = o.max_gap;
+    d["time_zero_offset"] = o.time_zero_offset; d["gyro_bias"] = std::vector<double>(o.gyro_bias, o.gyro_bias + 3);
+    d["sensor_rotation"] = std::vector<double>(o.sensor_rotation, o.sensor_rotation + 9); d["buffer_seconds"] = o.buffer_seconds;
+    return d;
+  };
+  m.def("gyro_deskew_options", [gyro2dict, gyro_opts](const py::object& options) { return gyro2dict(gyro_opts(options)); }, py::arg("options") = py::none());
+  // the host rule on its own: samples (t [n], w [n, 3]) pushed into a GyroBuffer of the options' length in order, then
+  // build_motion_table -> None (no coverage) or dict(knots [K], R [K, 3, 3], w [K, 3], v [3]); "dropped" / "kept" ride along
+  m.def("gyro_motion_table", [gyro_opts](py::array_t<double, py::array::c_style | py::array::forcecast> t,
+                                         py::array_t<double, py::array::c_style | py::array::forcecast> w, double timestamp, const py::object& options,
+                                         std::vector<double> v) -> py::object {
+    if (t.ndim() != 1 || w.ndim() != 2 || w.shape(1) != 3 || w.shape(0) != t.shape(0)) throw std::runtime_error("gyro_motion_table: t must be [n] and w [n, 3]");
+    if (v.size() != 3) throw std::runtime_error("gyro_motion_table: v has 3 values");
+    const mola_hip::GyroDeskewOptions o = gyro_opts(options);
+    mola_hip::GyroBuffer buf(o.buffer_seconds);
+    for (py::ssize_t k = 0; k < t.shape(0); k++) buf.push(t.data()[k], w.data() + 3 * k);
+    const auto tab = mola_hip::build_motion_table(buf, timestamp, o, v.data());
+    py::dict d;
+    d["dropped"] = buf.dropped(); d["kept"] = buf.size();
+    if (!tab) { d["table"] = py::none(); return d; }
+    const py::ssize_t K = (py::ssize_t)tab->segments.size();
+    py::array_t<double> knots(K), R({K, (py::ssize_t)3, (py::ssize_t)3}), ws({K, (py::ssize_t)3});
+    for (py::ssize_t s = 0; s < K; s++) {
+      knots.mutable_data()[s] = tab->segments[(size_t)s].knot;
+      std::copy(tab->segments[(size_t)s].R, tab->segments[(size_t)s].R + 9, R.mutable_data() + 9 * s);
+      std::copy(tab->segments[(size_t)s].w, tab->segments[(size_t)s].w + 3, ws.mutable_data() + 3 * s);
+    }
+    py::dict tb;
+    tb["knots"] = knots; tb["R"] = R; tb["w"] = ws; tb["v"] = std::vector<double>(tab->v, tab->v + 3);
+    d["table"] = tb;
+    return d; }, py::arg("t"), py::arg("w"), py::arg("timestamp"), py::arg("options") = py::none(), py::arg("v") = std::vector<double>{0, 0, 0});
+  // the command line's --gyro-file text -> (t [n], w [n, 3])
+  m.def("parse_gyro_text", [](const std::string& text) {
+    const auto g = mola_hip::parse_gyro_text(text);
+    py::array_t<double> t((py::ssize_t)g.size()), w({(py::ssize_t)g.size(), (py::ssize_t)3});
+    for (size_t k = 0; k < g.size(); k++) { t.mutable_data()[k] = g[k].t; std::copy(g[k].w, g[k].w + 3, w.mutable_data() + 3 * k); }
+    return py::make_tuple(t, w); }, py::arg("text"));
   m.def("online_map_cleaning_options", [live2dict, live_opts](const py::object& options) { return live2dict(live_opts(options)); },
         py::arg("options") = py::none());
   // the ring rule on its own (host logic only; the driver's LiveMapCleaner holds one): poses [K, 12] of K local map updates in a
@@ -641,6 +688,12 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
       .def("lostRecoveryOptions", [lost2dict](const LidarOdometry& lo) { return lost2dict(lo.lostRecoveryOptions()); })
       .def("onlineMapCleaningOptions", [live2dict](const LidarOdometry& lo) { return live2dict(lo.onlineMapCleaningOptions()); })
       .def("mapPointsErased", &LidarOdometry::mapPointsErased)
+      .def("onGyro", [](LidarOdometry& lo, double t, std::vector<double> w) {
+        if (w.size() != 3) throw std::runtime_error("onGyro: w has 3 values");
+        lo.onGyro(t, w.data()); })
+      .def("gyroDeskewOptions", [gyro2dict](const LidarOdometry& lo) { return gyro2dict(lo.gyroDeskewOptions()); })
+      .def("scansGyroDeskewed", &LidarOdometry::scansGyroDeskewed)
+      .def("gyroSamplesDropped", &LidarOdometry::gyroSamplesDropped)
       .def("isLost", &LidarOdometry::isLost)
       .def("timesLost", &LidarOdometry::timesLost)
       .def("recoveryAttempts", &LidarOdometry::recoveryAttempts)
