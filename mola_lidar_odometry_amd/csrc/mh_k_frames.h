@@ -10,37 +10,19 @@
 // wave through uniform addresses; a wave that straddles frames repeats the search per lane between those two bounds and
 // reads its frame's entry per lane, as k_merge_fill does.  No LDS, no atomics, nothing shared between workgroups.
 #pragma once
+#include "mh_k_frame_src.h"  // FrameSrc, frame_of, compose_posed_point
 
 namespace {
 
-struct FrameSrc {
-  const float *x, *y, *z;  // the frame's points (device memory; never read for an empty frame)
-  double T[12];            // row-major 3x4, the key-frame's pose
-};
-static_assert(sizeof(FrameSrc) == 120, "FrameSrc is mirrored on the host byte for byte");
-
-// the frame of point q: the last f in [lo, hi] with start[f] <= q (start[lo] <= q < start[hi + 1]); empty frames, whose
-// offset equals their successor's, are stepped over by the upper bound
-__device__ __forceinline__ uint32_t frame_of(const uint32_t* __restrict__ start, uint32_t lo, uint32_t hi, uint32_t q) {
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1u) >> 1;
-    if (start[mid] <= q) lo = mid;
-    else hi = mid - 1u;
-  }
-  return lo;
-}
-
-// p_map = (float)(R*p + t), the arithmetic of k_compose_new (fp64, un-fused, rounded once).  FramePtr: the table entry through
-// the constant address space (a wave-uniform entry: scalar loads) or the global one (a lane's own entry).
 #define MH_FRAMES_AS(n) __attribute__((address_space(n)))
 template <class FramePtr>
 __device__ __forceinline__ void compose_frame_point(FramePtr s, uint32_t j, uint32_t o, uint32_t src, float* __restrict__ ox,
                                                     float* __restrict__ oy, float* __restrict__ oz, uint32_t* __restrict__ osrc) {
-  const double px = ((const float MH_FRAMES_AS(1)*)s->x)[j], py = ((const float MH_FRAMES_AS(1)*)s->y)[j],
-               pz = ((const float MH_FRAMES_AS(1)*)s->z)[j];
-  ox[o] = (float)(((s->T[0] * px + s->T[1] * py) + s->T[2] * pz) + s->T[3]);
-  oy[o] = (float)(((s->T[4] * px + s->T[5] * py) + s->T[6] * pz) + s->T[7]);
-  oz[o] = (float)(((s->T[8] * px + s->T[9] * py) + s->T[10] * pz) + s->T[11]);
+  float px, py, pz;
+  compose_posed_point(s, j, px, py, pz);
+  ox[o] = px;
+  oy[o] = py;
+  oz[o] = pz;
   osrc[o] = src;
 }
 

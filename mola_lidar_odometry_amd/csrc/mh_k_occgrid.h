@@ -17,6 +17,7 @@
 //   (prefix sum over the flags, k_occ_compact: mh_k_occ.h)
 // Nothing waits on another thread, there are no float atomics; the only atomics are integer min / max / add.
 #pragma once
+#include "mh_k_frame_src.h"  // frame_of, compose_posed_point
 #include "mh_k_occ.h"
 
 namespace mh {
@@ -31,16 +32,6 @@ struct OccFrame {
 };
 static_assert(sizeof(OccFrame) == 144, "OccFrame is mirrored on the host byte for byte");
 
-// the frame of selected point q: the last f in [lo, hi] with start[f] <= q (k_compose_frames' search)
-__device__ __forceinline__ uint32_t occ_frame_of(const uint32_t* __restrict__ start, uint32_t lo, uint32_t hi, uint32_t q) {
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1u) >> 1;
-    if (start[mid] <= q) lo = mid;
-    else hi = mid - 1u;
-  }
-  return lo;
-}
-
 // `start` is the prefix array of the pass's SELECTED points (every decimation-th of each frame), n_frames + 1 entries.  A wave
 // whose first and last point share a frame (all but one wave per frame) finds it with wave-uniform searches and reads pose and
 // pointers through uniform addresses (scalar loads); a wave that straddles frames searches per lane between those bounds.
@@ -54,16 +45,14 @@ static __global__ __launch_bounds__(256) void k_occf_rays(const uint32_t* __rest
   const uint32_t q_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(q & ~63u));  // (wave-uniform)
   if (q_first >= total) return;
   const uint32_t q_last = min(q_first + 63u, total - 1u);
-  const uint32_t f_first = occ_frame_of(start, 0u, n_frames - 1u, q_first);
-  const uint32_t f_last = occ_frame_of(start, f_first, n_frames - 1u, q_last);
+  const uint32_t f_first = frame_of(start, 0u, n_frames - 1u, q_first);
+  const uint32_t f_last = frame_of(start, f_first, n_frames - 1u, q_last);
   if (q >= total) return;
-  const uint32_t f = f_first == f_last ? f_first : occ_frame_of(start, f_first, f_last, q);
+  const uint32_t f = f_first == f_last ? f_first : frame_of(start, f_first, f_last, q);
   const OccFrame* __restrict__ s = fr + f;
   const size_t i = (size_t)(q - start[f]) * decimation;
-  const double lx = s->x[i], ly = s->y[i], lz = s->z[i];
-  const float px = (float)(((s->T[0] * lx + s->T[1] * ly) + s->T[2] * lz) + s->T[3]);
-  const float py = (float)(((s->T[4] * lx + s->T[5] * ly) + s->T[6] * lz) + s->T[7]);
-  const float pz = (float)(((s->T[8] * lx + s->T[9] * ly) + s->T[10] * lz) + s->T[11]);
+  float px, py, pz;
+  compose_posed_point(s, i, px, py, pz);
   int4 e = make_int4(0, 0, 0, 0);
   uint32_t cnt = 0;
   if (isfinite(px) && isfinite(py) && isfinite(pz)) {

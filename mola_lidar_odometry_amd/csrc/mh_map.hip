@@ -17,6 +17,7 @@
 #include <new>
 #include <vector>
 
+#include "mh_frames_pass.h"
 #include "mh_internal.h"
 
 using namespace mh;
@@ -709,22 +710,10 @@ mh_status mh_map_insert(mh_map* m, const mh_scan* scan, const double T[12], floa
   return MH_OK;
 }
 
-// The library's own pass size (max_points_per_pass == 0): 2 M points are 24 MB of staged coordinates.
-constexpr uint64_t kFramesPassPoints = 1ull << 21;
-
 mh_status mh_map_insert_frames(mh_map* m, const mh_map_frame* frames, size_t n_frames, int32_t mem, uint64_t max_points_per_pass) {
   MH_REQUIRE(m, "null map");
-  MH_REQUIRE(n_frames == 0 || frames, "null frames");
-  MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE || mem == MH_MEM_HOST_PINNED, "bad mem space");
-  MH_REQUIRE(n_frames <= MH_MAX_INSERT_FRAMES, "too many frames");
   uint64_t sum = 0;
-  for (size_t f = 0; f < n_frames; f++) {
-    const mh_map_frame& fr = frames[f];
-    MH_REQUIRE(fr.n == 0 || (fr.x && fr.y && fr.z), "null point arrays");
-    MH_REQUIRE(fr.n < 0x7FFFFFF0ull, "too many points");
-    for (int i = 0; i < 12; i++) MH_REQUIRE(isfinite(fr.T[i]), "non-finite pose");
-    sum += fr.n;  // (2^20 frames of less than 2^31 points: no overflow)
-  }
+  MH_TRY(frames_check(__func__, frames, n_frames, mem, &sum));  // (the refusals, the split into passes, the upload: mh_frames_pass.h)
   if (sum == 0) return MH_OK;
   const Switches sw = read_switches();
   mh_ctx* ctx = m->ctx;
@@ -748,18 +737,15 @@ mh_status mh_map_insert_frames(mh_map* m, const mh_map_frame* frames, size_t n_f
   const bool staged = mem != MH_MEM_DEVICE;  // host arrays travel through the mirror; device arrays are read in place
   size_t f0 = 0;
   while (f0 < n_frames) {
-    size_t f1 = f0;
     uint64_t P = 0;  // frames in order while they fit; a frame larger than the budget is a pass of its own
-    while (f1 < n_frames && (P == 0 || P + frames[f1].n <= budget)) P += frames[f1++].n;
+    const size_t f1 = frames_next_pass(frames, n_frames, f0, budget, &P);
     const size_t nf = f1 - f0;
     if (P == 0) break;  // (only empty frames were left)
     MH_TRY(map_resolve_counts(m));  // the previous pass's counts; the mirror and the staging are free again behind them
     const size_t n_old = m->n_points, total = n_old + P;
     // upload layout: [x | y | z of the pass's points (host arrays only)] prefix array [nf + 1] | frame table [nf]
-    const size_t pstride = staged ? ((P * sizeof(float) + 255) / 256) * 256 : 0;
-    const size_t off_start = 3 * pstride;
-    const size_t off_table = off_start + (((nf + 1) * sizeof(uint32_t) + 255) / 256) * 256;
-    const size_t up_bytes = off_table + nf * sizeof(FrameSrc);
+    const FramesUpload up = frames_upload_layout(nf, P, staged, sizeof(FrameSrc));
+    const size_t off_start = up.off_start, off_table = up.off_table, up_bytes = up.bytes;
     const size_t stride = ((total * sizeof(float) + 255) / 256) * 256;
     // everything that can be reserved without touching the stored content, first: running out of memory here leaves the
     // earlier passes inserted and the map as it is
@@ -773,29 +759,7 @@ mh_status mh_map_insert_frames(mh_map* m, const mh_map_frame* frames, size_t n_f
     MH_TRY(m->build_d.reserve(2 * total * sizeof(uint32_t)));
     char* h = m->h_frames.as<char>();
     char* d = ctx->staging.as<char>();
-    uint32_t* h_start = (uint32_t*)(h + off_start);
-    FrameSrc* h_tab = (FrameSrc*)(h + off_table);
-    uint64_t at = 0;
-    for (size_t k = 0; k < nf; k++) {
-      const mh_map_frame& fr = frames[f0 + k];
-      h_start[k] = (uint32_t)at;
-      FrameSrc& e = h_tab[k];
-      if (staged) {
-        if (fr.n) {
-          memcpy(h + at * sizeof(float), fr.x, fr.n * sizeof(float));
-          memcpy(h + pstride + at * sizeof(float), fr.y, fr.n * sizeof(float));
-          memcpy(h + 2 * pstride + at * sizeof(float), fr.z, fr.n * sizeof(float));
-        }
-        e.x = (const float*)d + at;
-        e.y = (const float*)(d + pstride) + at;
-        e.z = (const float*)(d + 2 * pstride) + at;
-      } else {
-        e.x = fr.x; e.y = fr.y; e.z = fr.z;
-      }
-      for (int i = 0; i < 12; i++) e.T[i] = fr.T[i];
-      at += fr.n;
-    }
-    h_start[nf] = (uint32_t)at;
+    frames_fill_upload<FrameSrc>(up, frames + f0, nf, staged, h, d);
     MH_HIP(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, s));  // the pass's one upload
     char* base = m->merge.as<char>();
     float *mx = (float*)base, *my = (float*)(base + stride), *mz = (float*)(base + 2 * stride);

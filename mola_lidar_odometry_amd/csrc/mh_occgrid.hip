@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/molahip_occgrid.h"
+#include "mh_frames_pass.h"
 #include "mh_k_occgrid.h"
 #include "mh_occmap_internal.h"
 
@@ -15,10 +16,6 @@ using namespace mh;
 using namespace mh::occ;
 
 namespace {
-
-constexpr uint64_t kOccFramesPassPoints = 1ull << 21;  // the library's own pass size, as mh_map_insert_frames'
-
-size_t up256(size_t b) { return ((b + 255) / 256) * 256; }
 
 // One pass: frames[0 .. nf) (P points, S selected ones, S > 0) folded into the store.  The store is swapped last: a failure
 // leaves it as the previous pass left it.
@@ -30,40 +27,25 @@ mh_status occ_frames_pass(mh_occmap* o, const mh_map_frame* frames, size_t nf, u
   const uint32_t B = 256;
 
   // ---- the pass's one upload: [x | y | z of its points (host arrays only)] prefix array [nf + 1] | frame table [nf]
-  const size_t pstride = staged ? up256(P * sizeof(float)) : 0;
-  const size_t off_start = 3 * pstride;
-  const size_t off_table = off_start + up256((nf + 1) * sizeof(uint32_t));
-  const size_t up_bytes = off_table + nf * sizeof(OccFrame);
+  const FramesUpload up = frames_upload_layout(nf, P, staged, sizeof(OccFrame));  // (mh_frames_pass.h: the layout, the packing)
+  const size_t off_start = up.off_start, off_table = up.off_table, up_bytes = up.bytes;
   MH_TRY(o->f_h.reserve(up_bytes));
   MH_TRY(o->f_up.reserve(up_bytes));
   char* h = o->f_h.as<char>();
   char* d = o->f_up.as<char>();
   uint32_t* h_start = (uint32_t*)(h + off_start);
   OccFrame* h_tab = (OccFrame*)(h + off_table);
-  uint64_t at = 0, sel = 0;
+  frames_fill_upload<OccFrame>(up, frames, nf, staged, h, d);
+  uint64_t sel = 0;  // the prefix array is over the SELECTED points (every decimation-th of each frame)
   for (size_t k = 0; k < nf; k++) {
     const mh_map_frame& fr = frames[k];
     h_start[k] = (uint32_t)sel;
     OccFrame& e = h_tab[k];
-    if (staged) {
-      if (fr.n) {
-        memcpy(h + at * sizeof(float), fr.x, fr.n * sizeof(float));
-        memcpy(h + pstride + at * sizeof(float), fr.y, fr.n * sizeof(float));
-        memcpy(h + 2 * pstride + at * sizeof(float), fr.z, fr.n * sizeof(float));
-      }
-      e.x = (const float*)d + at;
-      e.y = (const float*)(d + pstride) + at;
-      e.z = (const float*)(d + 2 * pstride) + at;
-    } else {
-      e.x = fr.x; e.y = fr.y; e.z = fr.z;
-    }
-    for (int i = 0; i < 12; i++) e.T[i] = fr.T[i];
     for (int a = 0; a < 3; a++) {
       e.ot[a] = (float)fr.T[4 * a + 3];
       const float sc = e.ot[a] * o->inv_res;
       e.oc[a] = trunc ? (int)sc : (int)floorf(sc);
     }
-    at += fr.n;
     sel += (fr.n + PR.decimation - 1) / PR.decimation;
   }
   h_start[nf] = (uint32_t)sel;
@@ -288,38 +270,26 @@ uint32_t mh_occgrid_api_version(void) { return MH_OCCGRID_API_VERSION; }
 mh_status mh_occmap_insert_frames(mh_occmap* o, const mh_map_frame* frames, size_t n_frames, int32_t mem,
                                   uint64_t max_points_per_pass) {
   MH_REQUIRE(o, "null map");
-  MH_REQUIRE(n_frames == 0 || frames, "null frames");
-  MH_REQUIRE(mem == MH_MEM_HOST || mem == MH_MEM_DEVICE || mem == MH_MEM_HOST_PINNED, "bad mem space");
-  MH_REQUIRE(n_frames <= MH_MAX_INSERT_FRAMES, "too many frames");
   uint64_t sum = 0;
-  for (size_t f = 0; f < n_frames; f++) {
-    const mh_map_frame& fr = frames[f];
-    MH_REQUIRE(fr.n == 0 || (fr.x && fr.y && fr.z), "null point arrays");
-    MH_REQUIRE(fr.n < 0x7FFFFFF0ull, "too many points");
-    for (int i = 0; i < 12; i++) MH_REQUIRE(isfinite(fr.T[i]), "non-finite pose");
+  MH_TRY(frames_check(__func__, frames, n_frames, mem, &sum));  // (the refusals every batched posed-frame call shares)
+  for (size_t f = 0; f < n_frames; f++)
     for (int a = 0; a < 3; a++)
-      MH_REQUIRE(fabsf((float)fr.T[4 * a + 3] * o->inv_res) < 1.0e6f, "insertion pose outside the key range");
-    sum += fr.n;
-  }
+      MH_REQUIRE(fabsf((float)frames[f].T[4 * a + 3] * o->inv_res) < 1.0e6f, "insertion pose outside the key range");
   if (sum == 0) return MH_OK;
   MH_REQUIRE(o->n_cells < 0x3FFFFFF0ull, "too many points");
   MH_TRY(set_device(o->ctx));
   o->n_left_out = o->n_keys = 0;
   o->n_passes = 0;
-  const uint64_t budget = std::min<uint64_t>(max_points_per_pass ? max_points_per_pass : kOccFramesPassPoints, 0x7FFFFFEFull);
+  const uint64_t budget = std::min<uint64_t>(max_points_per_pass ? max_points_per_pass : kFramesPassPoints, 0x7FFFFFEFull);
   const bool staged = mem != MH_MEM_DEVICE;
   const uint32_t dec = o->params.decimation;
   mh_status st = MH_OK;
   bool applied = false;
   size_t f0 = 0;
   while (f0 < n_frames && st == MH_OK) {
-    size_t f1 = f0;
     uint64_t P = 0, S = 0;  // frames in order while they fit; a frame larger than the budget is a pass of its own
-    while (f1 < n_frames && (P == 0 || P + frames[f1].n <= budget)) {
-      P += frames[f1].n;
-      S += (frames[f1].n + dec - 1) / dec;
-      f1++;
-    }
+    const size_t f1 = frames_next_pass(frames, n_frames, f0, budget, &P);
+    for (size_t f = f0; f < f1; f++) S += (frames[f].n + dec - 1) / dec;
     if (P == 0) break;  // (only empty frames were left)
     const int cur = o->cur;
     st = occ_frames_pass(o, frames + f0, f1 - f0, P, S, staged);

@@ -45,6 +45,7 @@
 #include "mola_lidar_odometry_hip/LoopClosure.h"
 #include "mola_lidar_odometry_hip/MapCleaning.h"
 #include "mola_lidar_odometry_hip/OccupancyGrid.h"
+#include "mola_lidar_odometry_hip/Traversability.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "molahip.h"
 
@@ -352,6 +353,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> join_files;  // --join-sessions A B
   std::vector<std::string> clean_files;  // --clean-keyframes IN OUT
   std::vector<std::string> grid_files;   // --build-occupancy-grid KEYFRAMES OUT_PREFIX
+  std::vector<std::string> trav_files;   // --build-traversability KEYFRAMES OUT_PREFIX
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
                       "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE] [--relocalize-in-keyframes]\n"
@@ -360,6 +362,7 @@ int main(int argc, char** argv) {
                       "       molahip-lo-cli --join-sessions KEYFRAMES_A KEYFRAMES_B --pipeline FILE.yaml --output-simplemap FILE [--output-session-map FILE] [--loop-report FILE.json] [--device N]\n"
                       "       molahip-lo-cli --clean-keyframes KEYFRAMES_IN KEYFRAMES_OUT [-c FILE.yaml] [--device N]\n"
                       "       molahip-lo-cli --build-occupancy-grid KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
+                      "       molahip-lo-cli --build-traversability KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
@@ -382,6 +385,11 @@ int main(int argc, char** argv) {
                       "  --build-occupancy-grid: no sequence is run: every key-frame of KEYFRAMES is ray-traced from its pose into an occupancy map and a\n"
                       "  height band of it is projected to a 2-D grid (the pipeline's occupancy_grid: block; -c or --pipeline, optional), written as\n"
                       "  OUT_PREFIX.pgm and OUT_PREFIX.yaml for a map server; a key-frame file of any plan is taken\n"
+                      "  --build-traversability: no sequence is run: the points of every key-frame of KEYFRAMES are binned into a 2.5-D elevation map (the\n"
+                      "  lowest height per cell), obstacles are marked over that ground, and slope and step give every cell a cost (the pipeline's\n"
+                      "  traversability: block; -c or --pipeline, optional); written as OUT_PREFIX.pgm + OUT_PREFIX.yaml (lethal / free / unknown, for a\n"
+                      "  map server), OUT_PREFIX_cost.pgm (the cost bytes) and OUT_PREFIX_height.f32 (the ground height); run it after --close-loops\n"
+                      "  and --clean-keyframes\n"
                       "  --relocalize-in-keyframes: the vehicle is found in a saved session without a prior pose: place recognition over the\n"
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
@@ -445,6 +453,10 @@ int main(int argc, char** argv) {
         grid_files.push_back(val("--build-occupancy-grid"));
         grid_files.push_back(val("--build-occupancy-grid"));
       }
+      else if (a == "--build-traversability") {
+        trav_files.push_back(val("--build-traversability"));
+        trav_files.push_back(val("--build-traversability"));
+      }
       else if (a == "--relocalize-in-keyframes") opt.relocalize_in_keyframes = true;
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
@@ -454,6 +466,32 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n%s", e.what(), usage);
       return 2;
     }
+  }
+  if (!trav_files.empty()) {  // an elevation map with a traversability cost from a recorded drive's key-frames, no sequence
+    if (trav_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty() || !clean_files.empty() ||
+        !grid_files.empty()) {
+      fprintf(stderr, "--build-traversability takes one key-frame file to read and one output prefix, once, and takes no sequence\n%s", usage);
+      return 2;
+    }
+    try {
+      const mola_hip::TraversabilityOptions topt =
+          mola_hip::TraversabilityOptions::FromConfig(pipeline.empty() ? mp2p_icp_hip::Config::FromYamlText("") : mp2p_icp_hip::Config::FromYamlFile(pipeline));
+      const molahip_host::KeyFrameSet set = molahip_host::read_keyframe_file(trav_files[0]);  // (a missing file is refused before a device is asked for)
+      auto ctx = std::make_shared<mp2p_icp_hip::DeviceContext>(devices.empty() ? 0 : devices[0]);
+      const mola_hip::TraversabilityMap t = mola_hip::build_traversability_map(set, topt, ctx);
+      mola_hip::write_traversability_map(t, trav_files[1]);
+      printf("{\"keyframe_file\": \"%s\", \"traversability\": \"%s\", \"frames\": %llu, \"points\": %llu, \"points_counted\": %llu, "
+             "\"points_left_out\": %llu, \"grid_x0\": %d, \"grid_y0\": %d, \"grid_nx\": %u, \"grid_ny\": %u, \"cells_lethal\": %llu, "
+             "\"cells_free\": %llu, \"cells_unknown\": %llu, \"seconds_bounds\": %.6f, \"seconds_add\": %.6f, \"seconds_mark\": %.6f, "
+             "\"seconds_relief\": %.6f}\n",
+             trav_files[0].c_str(), trav_files[1].c_str(), (unsigned long long)t.frames, (unsigned long long)t.points,
+             (unsigned long long)t.points_counted, (unsigned long long)t.points_left_out, t.x0, t.y0, t.nx, t.ny, (unsigned long long)t.cells_lethal,
+             (unsigned long long)t.cells_free, (unsigned long long)t.cells_unknown, t.seconds_bounds, t.seconds_add, t.seconds_mark, t.seconds_relief);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "molahip-lo-cli: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (!grid_files.empty()) {  // a navigation occupancy grid from a recorded drive's key-frames, no sequence
     if (grid_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty() || !clean_files.empty()) {

@@ -10,6 +10,7 @@
 #include "mola_lidar_odometry_hip/LoopClosure.h"
 #include "mola_lidar_odometry_hip/MapCleaning.h"
 #include "mola_lidar_odometry_hip/OccupancyGrid.h"
+#include "mola_lidar_odometry_hip/Traversability.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 #include "molahip_host/plugin_switches.h"
@@ -1401,6 +1402,88 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
   m.def("write_occupancy_grid", [dict2grid](const py::dict& grid, const std::string& prefix) { mola_hip::write_occupancy_grid(dict2grid(grid), prefix); },
         py::arg("grid"), py::arg("prefix"));
   m.def("read_occupancy_grid", [grid2dict](const std::string& prefix) { return grid2dict(mola_hip::read_occupancy_grid(prefix)); }, py::arg("prefix"));
+  // ---- an elevation map with a traversability cost from key-frames (mola_lidar_odometry_hip/Traversability.h)
+  using mola_hip::TraversabilityMap;
+  using mola_hip::TraversabilityOptions;
+  // `options`: a pipeline Config, or the YAML text of one (its traversability: block is read; absent: the defaults)
+  auto trav_opts = [](const py::object& options) {
+    if (options.is_none()) return TraversabilityOptions::FromConfig(Config::FromYamlText(""));
+    if (py::isinstance<py::str>(options)) return TraversabilityOptions::FromConfig(Config::FromYamlText(options.cast<std::string>()));
+    return TraversabilityOptions::FromConfig(options.cast<const Config&>());
+  };
+  auto plane2array = [](const auto& v, uint32_t ny, uint32_t nx) {
+    using T = typename std::decay_t<decltype(v)>::value_type;
+    py::array_t<T> a({(py::ssize_t)(v.empty() ? 0 : ny), (py::ssize_t)nx});
+    std::copy(v.begin(), v.end(), a.mutable_data());
+    return a;
+  };
+  auto trav2dict = [plane2array](const TraversabilityMap& t) {
+    py::dict d;
+    d["x0"] = t.x0; d["y0"] = t.y0; d["nx"] = t.nx; d["ny"] = t.ny; d["resolution"] = t.resolution; d["z_quantum"] = t.z_quantum;
+    d["clearance_q"] = t.clearance_q; d["step_q"] = t.step_q; d["rise_q"] = t.rise_q;
+    d["min_points_per_cell"] = t.min_points_per_cell; d["min_obstacle_points"] = t.min_obstacle_points;
+    d["ground"] = plane2array(t.ground, t.ny, t.nx); d["top"] = plane2array(t.top, t.ny, t.nx);
+    d["count"] = plane2array(t.count, t.ny, t.nx); d["obstacle_count"] = plane2array(t.obstacle_count, t.ny, t.nx);
+    d["relief1"] = plane2array(t.relief1, t.ny, t.nx); d["reliefR"] = plane2array(t.reliefR, t.ny, t.nx);
+    d["cost"] = plane2array(t.cost, t.ny, t.nx); d["height"] = plane2array(t.height, t.ny, t.nx);
+    d["cells_lethal"] = t.cells_lethal; d["cells_free"] = t.cells_free; d["cells_unknown"] = t.cells_unknown;
+    d["frames"] = t.frames; d["points"] = t.points; d["points_counted"] = t.points_counted; d["points_left_out"] = t.points_left_out;
+    d["points_outside_window"] = t.points_outside_window;
+    d["seconds_bounds"] = t.seconds_bounds; d["seconds_add"] = t.seconds_add; d["seconds_mark"] = t.seconds_mark; d["seconds_relief"] = t.seconds_relief;
+    return d;
+  };
+  m.def("traversability_options", [trav_opts](const py::object& options) {
+    const TraversabilityOptions o = trav_opts(options);
+    py::dict d;
+    d["resolution"] = o.resolution; d["z_quantum"] = o.z_quantum; d["max_range"] = o.max_range; d["vehicle_height"] = o.vehicle_height;
+    d["max_step"] = o.max_step; d["slope_radius_cells"] = o.slope_radius_cells; d["max_slope_deg"] = o.max_slope_deg;
+    d["min_points_per_cell"] = o.min_points_per_cell; d["min_obstacle_points"] = o.min_obstacle_points; d["target_map"] = o.target_map;
+    d["margin_cells"] = o.margin_cells;
+    d["clearance_q"] = o.clearanceQ(); d["step_q"] = o.stepQ(); d["rise_q"] = o.riseQ();
+    return d; }, py::arg("options") = py::none());
+  // the host rule on given planes [ny, nx] -> (uint8 cost, float32 height, lethal, free, unknown)
+  m.def("traversability_classify", [plane2array](py::array_t<int32_t, py::array::c_style | py::array::forcecast> ground,
+                                                 py::array_t<uint32_t, py::array::c_style | py::array::forcecast> count,
+                                                 py::array_t<uint32_t, py::array::c_style | py::array::forcecast> obstacle_count,
+                                                 py::array_t<int32_t, py::array::c_style | py::array::forcecast> relief1,
+                                                 py::array_t<int32_t, py::array::c_style | py::array::forcecast> reliefR, int32_t step_q, int32_t rise_q,
+                                                 uint32_t min_points_per_cell, uint32_t min_obstacle_points, double z_quantum) {
+    if (count.ndim() != 2) throw std::runtime_error("traversability_classify: the planes must be [ny, nx]");
+    TraversabilityMap t;
+    t.ny = (uint32_t)count.shape(0); t.nx = (uint32_t)count.shape(1);
+    t.step_q = step_q; t.rise_q = rise_q; t.min_points_per_cell = min_points_per_cell; t.min_obstacle_points = min_obstacle_points;
+    t.z_quantum = z_quantum;
+    t.ground.assign(ground.data(), ground.data() + ground.size());
+    t.count.assign(count.data(), count.data() + count.size());
+    t.obstacle_count.assign(obstacle_count.data(), obstacle_count.data() + obstacle_count.size());
+    t.relief1.assign(relief1.data(), relief1.data() + relief1.size());
+    t.reliefR.assign(reliefR.data(), reliefR.data() + reliefR.size());
+    mola_hip::traversability_classify(t);
+    return py::make_tuple(plane2array(t.cost, t.ny, t.nx), plane2array(t.height, t.ny, t.nx), t.cells_lethal, t.cells_free, t.cells_unknown); },
+        py::arg("ground"), py::arg("count"), py::arg("obstacle_count"), py::arg("relief1"), py::arg("reliefR"), py::arg("step_q"), py::arg("rise_q"),
+        py::arg("min_points_per_cell") = 2, py::arg("min_obstacle_points") = 2, py::arg("z_quantum") = 0.01);
+  // a key-frame set (a dict, or the path of a key-frame file) -> the map as a dict
+  m.def("build_traversability_map", [dict2kfset, trav_opts, trav2dict](const py::object& frames, const py::object& options, uint64_t max_points_per_pass) {
+    const molahip_host::KeyFrameSet set = py::isinstance<py::str>(frames) ? molahip_host::read_keyframe_file(frames.cast<std::string>())
+                                                                         : dict2kfset(frames.cast<py::dict>());
+    const TraversabilityOptions o = trav_opts(options);
+    TraversabilityMap t;
+    {
+      py::gil_scoped_release nogil;
+      t = mola_hip::build_traversability_map(set, o, nullptr, max_points_per_pass);
+    }
+    return trav2dict(t); }, py::arg("frames"), py::arg("options") = py::none(), py::arg("max_points_per_pass") = 0);
+  m.def("write_traversability_map", [](const py::dict& d, const std::string& prefix) {
+    TraversabilityMap t;
+    t.x0 = d["x0"].cast<int32_t>(); t.y0 = d["y0"].cast<int32_t>(); t.nx = d["nx"].cast<uint32_t>(); t.ny = d["ny"].cast<uint32_t>();
+    t.resolution = d["resolution"].cast<double>(); t.z_quantum = d["z_quantum"].cast<double>();
+    auto c = d["cost"].cast<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>>();
+    auto h = d["height"].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+    t.cost.assign(c.data(), c.data() + c.size());
+    t.height.assign(h.data(), h.data() + h.size());
+    mola_hip::write_traversability_map(t, prefix); }, py::arg("map"), py::arg("prefix"));
+  m.def("read_traversability_map", [trav2dict](const std::string& prefix) { return trav2dict(mola_hip::read_traversability_map(prefix)); },
+        py::arg("prefix"));
   // the pose rules of the driver's online loop closure and the motion model's rebase, on 12-value poses
   auto to_pose = [](const std::vector<double>& T) {
     if (T.size() != 12) throw std::runtime_error("a pose has 12 values");
