@@ -26,6 +26,7 @@ struct Switches {
   bool no_off32 = false;  // the plan / scan matcher's 64-bit-offset instantiation whatever the sizes (flat_off32, mh_k_launch.h)
   long keep_lds = LONG_MAX;  // (clamped to 1..kKeepLds where it is used)
   bool loop16_test_abandon = false, debug_verify_batch = false;
+  bool nav_no_early_stop = false;  // mh_nav_inflate's row pass walks every dx (MH_NAV_NO_EARLY_STOP=1: for measuring what the stop saves; same bits)
 };
 
 inline Switches read_switches() {
@@ -54,6 +55,7 @@ inline Switches read_switches() {
   if ((e = getenv("MH_KEEP_LDS"))) sw.keep_lds = atol(e);
   sw.loop16_test_abandon = on("MH_LOOP16_TEST_ABANDON");
   sw.debug_verify_batch = on("MH_DEBUG_VERIFY_BATCH");
+  sw.nav_no_early_stop = on("MH_NAV_NO_EARLY_STOP");
   return sw;
 }
 

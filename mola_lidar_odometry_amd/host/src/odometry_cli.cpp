@@ -46,6 +46,7 @@
 #include "mola_lidar_odometry_hip/MapCleaning.h"
 #include "mola_lidar_odometry_hip/OccupancyGrid.h"
 #include "mola_lidar_odometry_hip/Traversability.h"
+#include "mola_lidar_odometry_hip/NavCostmap.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "molahip.h"
 
@@ -354,6 +355,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> clean_files;  // --clean-keyframes IN OUT
   std::vector<std::string> grid_files;   // --build-occupancy-grid KEYFRAMES OUT_PREFIX
   std::vector<std::string> trav_files;   // --build-traversability KEYFRAMES OUT_PREFIX
+  std::vector<std::string> cost_files;   // --build-costmap KEYFRAMES OUT_PREFIX
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
                       "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE] [--relocalize-in-keyframes]\n"
@@ -363,6 +365,7 @@ int main(int argc, char** argv) {
                       "       molahip-lo-cli --clean-keyframes KEYFRAMES_IN KEYFRAMES_OUT [-c FILE.yaml] [--device N]\n"
                       "       molahip-lo-cli --build-occupancy-grid KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
                       "       molahip-lo-cli --build-traversability KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
+                      "       molahip-lo-cli --build-costmap KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
@@ -390,6 +393,10 @@ int main(int argc, char** argv) {
                       "  traversability: block; -c or --pipeline, optional); written as OUT_PREFIX.pgm + OUT_PREFIX.yaml (lethal / free / unknown, for a\n"
                       "  map server), OUT_PREFIX_cost.pgm (the cost bytes) and OUT_PREFIX_height.f32 (the ground height); run it after --close-loops\n"
                       "  and --clean-keyframes\n"
+                      "  --build-costmap: no sequence is run: the source map of KEYFRAMES is built (the pipeline's costmap: source, traversability by default,\n"
+                      "  with that map's own block), obstacles are inflated by the vehicle's radius with an exact distance transform, and the cells the\n"
+                      "  vehicle can reach from its key-frames are flooded (the pipeline's costmap: block; -c or --pipeline, optional); written as\n"
+                      "  OUT_PREFIX.pgm + OUT_PREFIX.yaml (for a map server), OUT_PREFIX_cost.pgm and OUT_PREFIX_reach.pgm\n"
                       "  --relocalize-in-keyframes: the vehicle is found in a saved session without a prior pose: place recognition over the\n"
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
@@ -457,6 +464,10 @@ int main(int argc, char** argv) {
         trav_files.push_back(val("--build-traversability"));
         trav_files.push_back(val("--build-traversability"));
       }
+      else if (a == "--build-costmap") {
+        cost_files.push_back(val("--build-costmap"));
+        cost_files.push_back(val("--build-costmap"));
+      }
       else if (a == "--relocalize-in-keyframes") opt.relocalize_in_keyframes = true;
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
@@ -466,6 +477,35 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n%s", e.what(), usage);
       return 2;
     }
+  }
+  if (!cost_files.empty()) {  // an inflated costmap with the reachable region from a recorded drive's key-frames, no sequence
+    if (cost_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty() || !clean_files.empty() ||
+        !grid_files.empty() || !trav_files.empty() || devices.size() > 1) {
+      fprintf(stderr, "--build-costmap takes one key-frame file to read and one output prefix, once, and takes no sequence and one device\n%s", usage);
+      return 2;
+    }
+    try {
+      const mp2p_icp_hip::Config cfg = pipeline.empty() ? mp2p_icp_hip::Config::FromYamlText("") : mp2p_icp_hip::Config::FromYamlFile(pipeline);
+      (void)mola_hip::NavCostmapOptions::FromConfig(cfg);  // (a bad block is refused before the file is read)
+      const molahip_host::KeyFrameSet set = molahip_host::read_keyframe_file(cost_files[0]);  // (a missing file is refused before a device is asked for)
+      auto ctx = std::make_shared<mp2p_icp_hip::DeviceContext>(devices.empty() ? 0 : devices[0]);
+      const mola_hip::NavCostmap c = mola_hip::build_costmap_from_keyframes(set, cfg, ctx);
+      mola_hip::write_costmap(c, cost_files[1]);
+      printf("{\"keyframe_file\": \"%s\", \"costmap\": \"%s\", \"keyframes\": %llu, \"grid_x0\": %d, \"grid_y0\": %d, \"grid_nx\": %u, \"grid_ny\": %u, "
+             "\"max_cells\": %u, \"cells_lethal\": %llu, \"cells_inscribed\": %llu, \"cells_inflated\": %llu, \"cells_free\": %llu, "
+             "\"cells_unknown\": %llu, \"cells_reached\": %llu, \"cells_unreachable_free\": %llu, \"keyframes_blocked\": %llu, "
+             "\"trajectory_min_clearance_m\": %.6f, \"seeds_blocked\": %llu, \"seeds_outside\": %llu, \"sweeps\": %u, "
+             "\"seconds_source\": %.6f, \"seconds_inflate\": %.6f, \"seconds_reach\": %.6f}\n",
+             cost_files[0].c_str(), cost_files[1].c_str(), (unsigned long long)c.keyframe_cost.size(), c.x0, c.y0, c.nx, c.ny, c.max_cells,
+             (unsigned long long)c.cells_lethal, (unsigned long long)c.cells_inscribed, (unsigned long long)c.cells_inflated,
+             (unsigned long long)c.cells_free, (unsigned long long)c.cells_unknown, (unsigned long long)c.cells_reached,
+             (unsigned long long)c.cells_unreachable_free, (unsigned long long)c.keyframes_blocked, c.trajectory_min_clearance_m,
+             (unsigned long long)c.seeds_blocked, (unsigned long long)c.seeds_outside, c.sweeps, c.seconds_source, c.seconds_inflate, c.seconds_reach);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "molahip-lo-cli: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (!trav_files.empty()) {  // an elevation map with a traversability cost from a recorded drive's key-frames, no sequence
     if (trav_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty() || !clean_files.empty() ||

@@ -11,6 +11,7 @@
 #include "mola_lidar_odometry_hip/MapCleaning.h"
 #include "mola_lidar_odometry_hip/OccupancyGrid.h"
 #include "mola_lidar_odometry_hip/Traversability.h"
+#include "mola_lidar_odometry_hip/NavCostmap.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 #include "molahip_host/plugin_switches.h"
@@ -1484,6 +1485,115 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     mola_hip::write_traversability_map(t, prefix); }, py::arg("map"), py::arg("prefix"));
   m.def("read_traversability_map", [trav2dict](const std::string& prefix) { return trav2dict(mola_hip::read_traversability_map(prefix)); },
         py::arg("prefix"));
+  // ---- an inflated costmap with the reachable region (mola_lidar_odometry_hip/NavCostmap.h)
+  using mola_hip::CostmapBase;
+  using mola_hip::NavCostmap;
+  using mola_hip::NavCostmapOptions;
+  using mola_hip::Pose12;
+  // `options`: a pipeline Config, or the YAML text of one (its costmap: block is read; absent: the defaults)
+  auto nav_cfg = [](const py::object& options) {
+    if (options.is_none()) return Config::FromYamlText("");
+    if (py::isinstance<py::str>(options)) return Config::FromYamlText(options.cast<std::string>());
+    return options.cast<Config>();
+  };
+  // a source map as a dict: a traversability map (`cost` uint8) or an occupancy grid (`cells` int8), with x0, y0, nx, ny, resolution
+  auto dict2base = [dict2grid](const py::dict& d) {
+    if (d.contains("cells")) return mola_hip::costmap_base(dict2grid(d));
+    TraversabilityMap t;
+    t.x0 = d["x0"].cast<int32_t>(); t.y0 = d["y0"].cast<int32_t>(); t.nx = d["nx"].cast<uint32_t>(); t.ny = d["ny"].cast<uint32_t>();
+    t.resolution = d["resolution"].cast<double>();
+    auto c = d["cost"].cast<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>>();
+    t.cost.assign(c.data(), c.data() + c.size());
+    return mola_hip::costmap_base(t);
+  };
+  auto to_poses = [](const std::vector<std::vector<double>>& poses) {
+    std::vector<Pose12> out(poses.size());
+    for (size_t k = 0; k < poses.size(); k++) {
+      if (poses[k].size() != 12) throw std::runtime_error("a pose has 12 values");
+      std::copy(poses[k].begin(), poses[k].end(), out[k].begin());
+    }
+    return out;
+  };
+  auto nav2dict = [plane2array](const NavCostmap& c) {
+    py::dict d;
+    d["x0"] = c.x0; d["y0"] = c.y0; d["nx"] = c.nx; d["ny"] = c.ny; d["resolution"] = c.resolution;
+    d["inscribed_radius"] = c.inscribed_radius; d["inflation_radius"] = c.inflation_radius; d["max_cells"] = c.max_cells;
+    d["unknown_is_obstacle"] = c.unknown_is_obstacle;
+    d["d2"] = plane2array(c.d2, c.ny, c.nx); d["cost"] = plane2array(c.cost, c.ny, c.nx); d["reach"] = plane2array(c.reach, c.ny, c.nx);
+    d["cells_lethal"] = c.cells_lethal; d["cells_inscribed"] = c.cells_inscribed; d["cells_inflated"] = c.cells_inflated;
+    d["cells_free"] = c.cells_free; d["cells_unknown"] = c.cells_unknown; d["cells_reached"] = c.cells_reached;
+    d["cells_unreachable_free"] = c.cells_unreachable_free;
+    d["keyframe_d2"] = std::vector<uint32_t>(c.keyframe_d2.begin(), c.keyframe_d2.end());
+    d["keyframe_cost"] = std::vector<uint32_t>(c.keyframe_cost.begin(), c.keyframe_cost.end());
+    d["keyframe_reached"] = std::vector<uint32_t>(c.keyframe_reached.begin(), c.keyframe_reached.end());
+    d["trajectory_min_clearance_m"] = c.trajectory_min_clearance_m; d["keyframes_blocked"] = c.keyframes_blocked;
+    d["seeds"] = c.seeds; d["seeds_blocked"] = c.seeds_blocked; d["seeds_outside"] = c.seeds_outside; d["sweeps"] = c.sweeps;
+    d["seconds_source"] = c.seconds_source; d["seconds_inflate"] = c.seconds_inflate; d["seconds_reach"] = c.seconds_reach;
+    return d;
+  };
+  auto dict2nav = [](const py::dict& d) {
+    NavCostmap c;
+    c.x0 = d["x0"].cast<int32_t>(); c.y0 = d["y0"].cast<int32_t>(); c.nx = d["nx"].cast<uint32_t>(); c.ny = d["ny"].cast<uint32_t>();
+    c.resolution = d["resolution"].cast<double>();
+    c.inscribed_radius = d["inscribed_radius"].cast<double>(); c.inflation_radius = d["inflation_radius"].cast<double>();
+    auto cost = d["cost"].cast<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>>();
+    auto reach = d["reach"].cast<py::array_t<uint8_t, py::array::c_style | py::array::forcecast>>();
+    c.cost.assign(cost.data(), cost.data() + cost.size());
+    c.reach.assign(reach.data(), reach.data() + reach.size());
+    if (d.contains("d2")) {
+      auto d2 = d["d2"].cast<py::array_t<uint16_t, py::array::c_style | py::array::forcecast>>();
+      c.d2.assign(d2.data(), d2.data() + d2.size());
+    }
+    return c;
+  };
+  m.def("costmap_options", [nav_cfg](const py::object& options) {
+    const NavCostmapOptions o = NavCostmapOptions::FromConfig(nav_cfg(options));
+    py::dict d;
+    d["source"] = o.source; d["inscribed_radius"] = o.inscribed_radius; d["inflation_radius"] = o.inflation_radius;
+    d["cost_scaling"] = o.cost_scaling; d["unknown_is_obstacle"] = o.unknown_is_obstacle; d["reach_from"] = o.reach_from;
+    return d; }, py::arg("options") = py::none());
+  // rule 2 -> uint8 [R * R + 1]
+  m.def("inflation_table", [nav_cfg](const py::object& options, double resolution) {
+    const std::vector<uint8_t> t = mola_hip::inflation_table(NavCostmapOptions::FromConfig(nav_cfg(options)), resolution);
+    py::array_t<uint8_t> a((py::ssize_t)t.size());
+    std::copy(t.begin(), t.end(), a.mutable_data());
+    return a; }, py::arg("options") = py::none(), py::arg("resolution") = 0.2);
+  // rule 1 -> uint8 [ny, nx]
+  m.def("costmap_base", [dict2base, plane2array](const py::dict& map) {
+    const CostmapBase b = dict2base(map);
+    return plane2array(b.bytes, b.ny, b.nx); }, py::arg("map"));
+  // rule 3 -> (column, row) pairs relative to the window of `map`
+  m.def("costmap_seeds", [dict2base, to_poses](const py::dict& map, const std::vector<std::vector<double>>& poses, const std::string& reach_from) {
+    return mola_hip::costmap_seeds(dict2base(map), to_poses(poses), reach_from); }, py::arg("map"), py::arg("poses"), py::arg("reach_from") = "keyframes");
+  // rule 4 on given planes (a dict with the window, the resolution, the radii, cost, reach and optionally d2) -> the costmap dict
+  m.def("costmap_summarise", [dict2nav, nav2dict, to_poses](const py::dict& map, const std::vector<std::vector<double>>& poses) {
+    NavCostmap c = dict2nav(map);
+    mola_hip::costmap_summarise(c, to_poses(poses));
+    return nav2dict(c); }, py::arg("map"), py::arg("poses"));
+  m.def("build_costmap", [dict2base, nav_cfg, to_poses, nav2dict](const py::dict& map, const std::vector<std::vector<double>>& poses, const py::object& options) {
+    const CostmapBase b = dict2base(map);
+    const NavCostmapOptions o = NavCostmapOptions::FromConfig(nav_cfg(options));
+    const std::vector<Pose12> p = to_poses(poses);
+    NavCostmap c;
+    {
+      py::gil_scoped_release nogil;
+      c = mola_hip::build_costmap(b, p, o);
+    }
+    return nav2dict(c); }, py::arg("map"), py::arg("poses"), py::arg("options") = py::none());
+  // a key-frame set (a dict, or the path of a key-frame file) -> the costmap as a dict
+  m.def("build_costmap_from_keyframes", [dict2kfset, nav_cfg, nav2dict](const py::object& frames, const py::object& options) {
+    const molahip_host::KeyFrameSet set = py::isinstance<py::str>(frames) ? molahip_host::read_keyframe_file(frames.cast<std::string>())
+                                                                         : dict2kfset(frames.cast<py::dict>());
+    const Config cfg = nav_cfg(options);
+    NavCostmap c;
+    {
+      py::gil_scoped_release nogil;
+      c = mola_hip::build_costmap_from_keyframes(set, cfg);
+    }
+    return nav2dict(c); }, py::arg("frames"), py::arg("options") = py::none());
+  m.def("write_costmap", [dict2nav](const py::dict& d, const std::string& prefix) { mola_hip::write_costmap(dict2nav(d), prefix); }, py::arg("map"),
+        py::arg("prefix"));
+  m.def("read_costmap", [nav2dict](const std::string& prefix) { return nav2dict(mola_hip::read_costmap(prefix)); }, py::arg("prefix"));
   // the pose rules of the driver's online loop closure and the motion model's rebase, on 12-value poses
   auto to_pose = [](const std::vector<double>& T) {
     if (T.size() != 12) throw std::runtime_error("a pose has 12 values");
