@@ -54,14 +54,10 @@ struct MapCleaningOptions {
 };
 
 // ---- what map_cleaning: and online_map_cleaning: (LiveMapCleaning.h) read alike.  `c` is the block, `block` its name in refusals.
-// The keys both hold: n_rings .. win_sectors, max_view_distance, min_through_votes, agree_weight
+// The keys both hold: n_rings .. win_sectors, max_view_distance, min_through_votes, agree_weight.  An absent or null key leaves its
+// option as it is; anything but a number / an integer >= 0 is refused.
 const std::vector<std::string>& cleaning_shared_keys();
 void read_cleaning_shared_keys(const Config& c, const std::string& block, MapCleaningOptions& o);
-// a key that is neither shared nor among own_keys is refused
-void cleaning_block_unknown_keys(const Config& c, const std::string& block, const std::vector<std::string>& own_keys);
-// an absent or null key leaves `v` as it is; anything but a number / an integer >= 0 is refused
-void cleaning_block_number(const Config& c, const std::string& block, const char* key, double& v);
-void cleaning_block_count(const Config& c, const std::string& block, const char* key, uint32_t& v);
 
 // ---- host rules (testable without a device)
 // poses: 12 doubles per frame; has_points: one flag per frame.  out[i]: the neighbours of frame i (rule 1).

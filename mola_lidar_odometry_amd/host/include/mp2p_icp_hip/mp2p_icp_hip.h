@@ -232,6 +232,7 @@ struct PosedFrame {
   size_t n = 0;
   CPose3D pose;
 };
+std::vector<mh_map_frame> to_map_frames(const std::vector<PosedFrame>& frames);  // the same frames as the C ABI takes them
 // mola::HashedVoxelPointCloud stand-in, device resident (NearestNeighborsCapable role only)
 class HashedVoxelPointCloud : public Layer {
  public:

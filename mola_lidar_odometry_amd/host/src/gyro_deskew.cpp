@@ -4,9 +4,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <fstream>
 #include <sstream>
 #include <stdexcept>
+
+#include "config_block.h"
+#include "map_files.h"
 
 namespace mola_hip {
 
@@ -17,38 +19,7 @@ namespace {
 
 const char* const kBlock = "gyro_deskew";
 
-[[noreturn]] void bad(const std::string& key, const std::string& what) { throw std::runtime_error(std::string(kBlock) + ": " + key + " " + what); }
-
-double to_number(const std::string& s, const char* k) {
-  char* end = nullptr;
-  const double v = strtod(s.c_str(), &end);
-  if (end == s.c_str() || *end != '\0') bad(k, "must be a number");
-  return v;
-}
-
-void number(const Config& c, const char* k, double& v) {
-  if (!c.has(k) || c[k].isNull()) return;
-  if (c[k].kind != Config::Kind::Scalar) bad(k, "must be a number");
-  v = to_number(c[k].asString(), k);
-}
-
-void numbers(const Config& c, const char* k, double* v, size_t n) {
-  if (!c.has(k) || c[k].isNull()) return;
-  const Config& s = c[k];
-  if (s.kind != Config::Kind::Seq || s.seq.size() != n) bad(k, "must be a list of " + std::to_string(n) + " numbers");
-  for (size_t i = 0; i < n; i++) {
-    if (s.at(i).kind != Config::Kind::Scalar) bad(k, "must be a list of " + std::to_string(n) + " numbers");
-    v[i] = to_number(s.at(i).asString(), k);
-  }
-}
-
-void boolean(const Config& c, const char* k, bool& v) {
-  if (!c.has(k) || c[k].isNull()) return;
-  const std::string s = c[k].asString();
-  if (s == "true" || s == "True" || s == "1" || s == "yes") v = true;
-  else if (s == "false" || s == "False" || s == "0" || s == "no") v = false;
-  else bad(k, "must be true or false");
-}
+[[noreturn]] void bad(const std::string& key, const std::string& what) { bad_option(kBlock, key, what); }
 
 // 3x3 row-major
 void mul33(const double* a, const double* b, double* c) {
@@ -69,23 +40,20 @@ void exp_so3(const double w[3], double scale, double* R) {
 GyroDeskewOptions GyroDeskewOptions::FromConfig(const Config& cfg) {
   GyroDeskewOptions o;
   if (cfg.has(kBlock) && !cfg[kBlock].isNull()) {
-    const Config& c = cfg[kBlock];
-    if (c.kind != Config::Kind::Map) throw std::runtime_error(std::string(kBlock) + ": the block must be a map of keys");
-    static const char* const keys[] = {"enabled", "window", "segments", "max_gap", "time_zero_offset", "gyro_bias", "sensor_rotation", "buffer_seconds"};
-    for (const auto& kv : c.map)
-      if (std::find_if(std::begin(keys), std::end(keys), [&](const char* k) { return kv.first == k; }) == std::end(keys))
-        bad(kv.first, "is not a key of this block");
-    boolean(c, "enabled", o.enabled);
-    numbers(c, "window", o.window, 2);
+    if (cfg[kBlock].kind != Config::Kind::Map) throw std::runtime_error(std::string(kBlock) + ": the block must be a map of keys");
+    const ConfigBlock c(cfg[kBlock], kBlock);
+    c.knownKeys({"enabled", "window", "segments", "max_gap", "time_zero_offset", "gyro_bias", "sensor_rotation", "buffer_seconds"});
+    c.boolean("enabled", o.enabled);
+    c.numbers("window", o.window, 2);
     double K = o.segments;
-    number(c, "segments", K);
+    c.number("segments", K);
     if (!(K >= 1.0) || !(K <= (double)MH_MOTION_MAX_SEGMENTS) || K != std::floor(K)) bad("segments", "must be an integer in 1 .. 64");
     o.segments = (uint32_t)K;
-    number(c, "max_gap", o.max_gap);
-    number(c, "time_zero_offset", o.time_zero_offset);
-    numbers(c, "gyro_bias", o.gyro_bias, 3);
-    numbers(c, "sensor_rotation", o.sensor_rotation, 9);
-    number(c, "buffer_seconds", o.buffer_seconds);
+    c.number("max_gap", o.max_gap);
+    c.number("time_zero_offset", o.time_zero_offset);
+    c.numbers("gyro_bias", o.gyro_bias, 3);
+    c.numbers("sensor_rotation", o.sensor_rotation, 9);
+    c.number("buffer_seconds", o.buffer_seconds);
   }
   o.validate();
   return o;
@@ -229,12 +197,6 @@ std::vector<GyroSample> parse_gyro_text(const std::string& text) {
   return out;
 }
 
-std::vector<GyroSample> read_gyro_file(const std::string& path) {
-  std::ifstream f(path);
-  if (!f) throw std::runtime_error("gyro file: cannot open '" + path + "'");
-  std::stringstream ss;
-  ss << f.rdbuf();
-  return parse_gyro_text(ss.str());
-}
+std::vector<GyroSample> read_gyro_file(const std::string& path) { return parse_gyro_text(slurp("gyro file", path)); }
 
 }  // namespace mola_hip

@@ -298,13 +298,18 @@ void HashedVoxelPointCloud::insertPointCloud(const DevicePointCloud& pc, const C
   check(st, "mh_map_insert");
 }
 
-void HashedVoxelPointCloud::insertFrames(const std::vector<PosedFrame>& frames, uint64_t max_points_per_pass) {
+std::vector<mh_map_frame> to_map_frames(const std::vector<PosedFrame>& frames) {
   std::vector<mh_map_frame> f(frames.size());
   for (size_t k = 0; k < frames.size(); k++) {
     f[k].x = frames[k].x; f[k].y = frames[k].y; f[k].z = frames[k].z;
     f[k].n = frames[k].n;
     std::copy(frames[k].pose.T, frames[k].pose.T + 12, f[k].T);
   }
+  return f;
+}
+
+void HashedVoxelPointCloud::insertFrames(const std::vector<PosedFrame>& frames, uint64_t max_points_per_pass) {
+  const std::vector<mh_map_frame> f = to_map_frames(frames);
   const mh_status st = mh_map_insert_frames(map_, f.data(), f.size(), MH_MEM_HOST, max_points_per_pass);
   if (st == MH_WARN_PREVIOUS_OUT_OF_RANGE) {  // these frames ARE in the map; an earlier update lost its wild points: log, go on
     fprintf(stderr, "[molahip] warning: %s\n", mh_last_error_string());
@@ -432,12 +437,7 @@ void CVoxelMap::insertFrames(const std::vector<PosedFrame>&, uint64_t) {
                            "(insertPointCloud), not by inserting point layers; it has no batched insertion");
 }
 void CVoxelMap::insertPointCloudFrames(const std::vector<PosedFrame>& frames, uint64_t max_points_per_pass) {
-  std::vector<mh_map_frame> f(frames.size());
-  for (size_t k = 0; k < frames.size(); k++) {
-    f[k].x = frames[k].x; f[k].y = frames[k].y; f[k].z = frames[k].z;
-    f[k].n = frames[k].n;
-    std::copy(frames[k].pose.T, frames[k].pose.T + 12, f[k].T);
-  }
+  const std::vector<mh_map_frame> f = to_map_frames(frames);
   const mh_status st = mh_occmap_insert_frames(occ_, f.data(), f.size(), MH_MEM_HOST, max_points_per_pass);
   prepareSearch(0.0);  // (a failed call may have applied earlier passes: the search map is the occupancy map's present one)
   check(st, "mh_occmap_insert_frames");

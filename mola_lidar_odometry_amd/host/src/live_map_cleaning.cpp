@@ -5,42 +5,36 @@
 #include <algorithm>
 #include <stdexcept>
 
+#include "config_block.h"
+
 namespace mola_hip {
 
 using namespace mp2p_icp_hip;
 
 namespace {
 const char* const kBlock = "online_map_cleaning";
-[[noreturn]] void bad(const std::string& key, const std::string& what) { throw std::runtime_error(std::string(kBlock) + ": " + key + " " + what); }
+[[noreturn]] void bad(const std::string& key, const std::string& what) { bad_option(kBlock, key, what); }
 }  // namespace
 
 // ================================================================== options
 OnlineMapCleaningOptions OnlineMapCleaningOptions::FromConfig(const Config& cfg) {
   OnlineMapCleaningOptions o;
   if (cfg.has(kBlock) && !cfg[kBlock].isNull()) {
-    const Config& c = cfg[kBlock];
-    cleaning_block_unknown_keys(c, kBlock, {"enabled", "max_views", "every_n_updates", "view_layer", "target_maps"});
-    if (c.has("enabled") && !c["enabled"].isNull()) {
-      const std::string s = c["enabled"].asString();
-      if (s == "true" || s == "True" || s == "1" || s == "yes") o.enabled = true;
-      else if (s == "false" || s == "False" || s == "0" || s == "no") o.enabled = false;
-      else bad("enabled", "must be true or false");
-    }
-    read_cleaning_shared_keys(c, kBlock, o);
-    cleaning_block_count(c, kBlock, "max_views", o.max_views);
-    cleaning_block_count(c, kBlock, "every_n_updates", o.every_n_updates);
-    if (c.has("view_layer") && !c["view_layer"].isNull()) {
-      if (c["view_layer"].kind != Config::Kind::Scalar) bad("view_layer", "must be a layer name");
-      o.view_layer = c["view_layer"].asString();
-    }
-    if (c.has("target_maps") && !c["target_maps"].isNull()) {
-      const Config& t = c["target_maps"];
-      if (t.kind != Config::Kind::Seq) bad("target_maps", "must be a list of map names");
-      for (size_t i = 0; i < t.size(); i++) {
-        if (t.at(i).kind != Config::Kind::Scalar || t.at(i).asString().empty()) bad("target_maps", "must be a list of map names");
-        if (std::find(o.target_maps.begin(), o.target_maps.end(), t.at(i).asString()) != o.target_maps.end())
-          bad("target_maps", "names '" + t.at(i).asString() + "' twice");
-        o.target_maps.push_back(t.at(i).asString());
+    const ConfigBlock c(cfg[kBlock], kBlock);
+    c.knownKeys({"enabled", "max_views", "every_n_updates", "view_layer", "target_maps"}, cleaning_shared_keys());
+    c.boolean("enabled", o.enabled);
+    read_cleaning_shared_keys(cfg[kBlock], kBlock, o);
+    c.count("max_views", o.max_views);
+    c.count("every_n_updates", o.every_n_updates);
+    if (c.value("view_layer") && c.value("view_layer")->kind != Config::Kind::Scalar) bad("view_layer", "must be a layer name");
+    c.text("view_layer", o.view_layer);
+    if (const Config* t = c.value("target_maps")) {
+      if (t->kind != Config::Kind::Seq) bad("target_maps", "must be a list of map names");
+      for (size_t i = 0; i < t->size(); i++) {
+        if (t->at(i).kind != Config::Kind::Scalar || t->at(i).asString().empty()) bad("target_maps", "must be a list of map names");
+        if (std::find(o.target_maps.begin(), o.target_maps.end(), t->at(i).asString()) != o.target_maps.end())
+          bad("target_maps", "names '" + t->at(i).asString() + "' twice");
+        o.target_maps.push_back(t->at(i).asString());
       }
     }
   }

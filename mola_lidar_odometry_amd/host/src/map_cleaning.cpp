@@ -10,6 +10,8 @@
 #include <stdexcept>
 #include <utility>
 
+#include "config_block.h"
+
 namespace mola_hip {
 
 using namespace mp2p_icp_hip;
@@ -23,10 +25,6 @@ struct Timer {  // adds the wall time of its scope to a report entry
   Timer(CleaningReport& rep, const char* n) : r(rep), name(n) {}
   ~Timer() { r.seconds[name] += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 };
-
-[[noreturn]] void bad(const std::string& block, const std::string& key, const std::string& what) {
-  throw std::runtime_error(block + ": " + key + " " + what);
-}
 
 bool frame_has_points(const molahip_host::KeyFrame& f) {
   if (!f.has_points) return false;
@@ -50,47 +48,24 @@ const std::vector<std::string>& cleaning_shared_keys() {
   return keys;
 }
 
-void cleaning_block_number(const Config& c, const std::string& block, const char* k, double& v) {
-  if (!c.has(k) || c[k].isNull()) return;
-  const std::string s = c[k].asString();
-  char* end = nullptr;
-  v = strtod(s.c_str(), &end);
-  if (end == s.c_str() || *end != '\0') bad(block, k, "must be a number");
-}
-
-void cleaning_block_count(const Config& c, const std::string& block, const char* k, uint32_t& v) {
-  double d = v;
-  cleaning_block_number(c, block, k, d);
-  if (!(d >= 0.0) || !(d <= 4294967295.0) || d != std::floor(d)) bad(block, k, "must be an integer >= 0");
-  v = (uint32_t)d;
-}
-
-void cleaning_block_unknown_keys(const Config& c, const std::string& block, const std::vector<std::string>& own_keys) {
-  const auto& shared = cleaning_shared_keys();
-  for (const auto& kv : c.map)
-    if (std::find(shared.begin(), shared.end(), kv.first) == shared.end() && std::find(own_keys.begin(), own_keys.end(), kv.first) == own_keys.end())
-      bad(block, kv.first, "is not a key of this block");
-}
-
-void read_cleaning_shared_keys(const Config& c, const std::string& block, MapCleaningOptions& o) {
-  auto num = [&](const char* k, double& v) { cleaning_block_number(c, block, k, v); };
-  auto cnt = [&](const char* k, uint32_t& v) { cleaning_block_count(c, block, k, v); };
-  cnt("n_rings", o.n_rings); cnt("n_sectors", o.n_sectors);
-  num("el_min_deg", o.el_min_deg); num("el_max_deg", o.el_max_deg);
-  num("min_range", o.min_range); num("max_range", o.max_range); num("rel_margin", o.rel_margin);
-  num("origin_x", o.origin[0]); num("origin_y", o.origin[1]); num("origin_z", o.origin[2]);
-  cnt("win_rings", o.win_rings); cnt("win_sectors", o.win_sectors);
-  num("max_view_distance", o.max_view_distance);
-  cnt("min_through_votes", o.min_through_votes); cnt("agree_weight", o.agree_weight);
+void read_cleaning_shared_keys(const Config& block_config, const std::string& block, MapCleaningOptions& o) {
+  const ConfigBlock c(block_config, block);
+  c.count("n_rings", o.n_rings); c.count("n_sectors", o.n_sectors);
+  c.number("el_min_deg", o.el_min_deg); c.number("el_max_deg", o.el_max_deg);
+  c.number("min_range", o.min_range); c.number("max_range", o.max_range); c.number("rel_margin", o.rel_margin);
+  c.number("origin_x", o.origin[0]); c.number("origin_y", o.origin[1]); c.number("origin_z", o.origin[2]);
+  c.count("win_rings", o.win_rings); c.count("win_sectors", o.win_sectors);
+  c.number("max_view_distance", o.max_view_distance);
+  c.count("min_through_votes", o.min_through_votes); c.count("agree_weight", o.agree_weight);
 }
 
 MapCleaningOptions MapCleaningOptions::FromConfig(const Config& cfg) {
   MapCleaningOptions o;
   if (cfg.has("map_cleaning") && !cfg["map_cleaning"].isNull()) {
-    const Config& c = cfg["map_cleaning"];
-    cleaning_block_unknown_keys(c, "map_cleaning", {"max_views_per_frame"});
-    read_cleaning_shared_keys(c, "map_cleaning", o);
-    cleaning_block_count(c, "map_cleaning", "max_views_per_frame", o.max_views_per_frame);
+    const ConfigBlock c(cfg["map_cleaning"], "map_cleaning");
+    c.knownKeys({"max_views_per_frame"}, cleaning_shared_keys());
+    read_cleaning_shared_keys(cfg["map_cleaning"], "map_cleaning", o);
+    c.count("max_views_per_frame", o.max_views_per_frame);
   }
   o.validate();
   return o;
@@ -99,7 +74,7 @@ MapCleaningOptions MapCleaningOptions::FromConfig(const Config& cfg) {
 void MapCleaningOptions::validate() const { validateAs("map_cleaning"); }
 
 void MapCleaningOptions::validateAs(const std::string& block) const {
-  auto bad = [&](const std::string& key, const std::string& what) { mola_hip::bad(block, key, what); };
+  auto bad = [&](const std::string& key, const std::string& what) { bad_option(block, key, what); };
   if (n_rings < 1 || n_rings > MH_CLEAN_MAX_RINGS) bad("n_rings", "must be in 1.." + std::to_string(MH_CLEAN_MAX_RINGS));
   if (n_sectors < 8 || n_sectors > MH_CLEAN_MAX_SECTORS || n_sectors % 8)
     bad("n_sectors", "must be a multiple of 8 in 8.." + std::to_string(MH_CLEAN_MAX_SECTORS));

@@ -7,10 +7,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <sstream>
 #include <stdexcept>
+
+#include "config_block.h"
+#include "map_files.h"
 
 namespace mola_hip {
 
@@ -18,73 +18,15 @@ namespace {
 
 const char* const kBlock = "costmap";
 
-[[noreturn]] void bad(const std::string& key, const std::string& what) { throw std::runtime_error(std::string(kBlock) + ": " + key + " " + what); }
+[[noreturn]] void bad(const std::string& key, const std::string& what) { bad_option(kBlock, key, what); }
 
-void number(const Config& c, const char* k, double& v) {
-  if (!c.has(k) || c[k].isNull()) return;
-  const std::string s = c[k].asString();
-  char* end = nullptr;
-  v = strtod(s.c_str(), &end);
-  if (end == s.c_str() || *end != '\0') bad(k, "must be a number");
-}
+uint8_t reach_byte(uint8_t reached) { return reached ? 255 : 0; }
 
-void boolean(const Config& c, const char* k, bool& v) {
-  if (!c.has(k) || c[k].isNull()) return;
-  const std::string s = c[k].asString();
-  if (s == "true" || s == "True" || s == "1" || s == "yes") v = true;
-  else if (s == "false" || s == "False" || s == "0" || s == "no") v = false;
-  else bad(k, "must be true or false");
-}
-
-std::string g9(double v) {
-  char buf[64];
-  snprintf(buf, sizeof(buf), "%.9g", v);
-  return buf;
-}
-
-std::string base_name(const std::string& path) {
-  const size_t s = path.find_last_of('/');
-  return s == std::string::npos ? path : path.substr(s + 1);
-}
-
-void write_file(const std::string& path, const std::string& bytes, std::ios::openmode mode) {
-  std::ofstream out(path, std::ios::binary | mode);
-  out.write(bytes.data(), (std::streamsize)bytes.size());
-  out.close();
-  if (!out) throw std::runtime_error("write_costmap: cannot write '" + path + "'");
-}
-
-std::string slurp(const std::string& path) {
-  std::ifstream in(path, std::ios::binary);
-  if (!in) throw std::runtime_error("read_costmap: cannot open '" + path + "'");
-  std::stringstream ss;
-  ss << in.rdbuf();
-  return ss.str();
-}
-
-// a plane as a binary PGM, row 0 of the image = the largest y; `reach` maps 1 -> 255
-std::string plane_pgm(const std::vector<uint8_t>& v, uint32_t nx, uint32_t ny, bool reach) {
-  std::string pgm = "P5\n" + std::to_string(nx) + " " + std::to_string(ny) + "\n255\n";
-  const size_t head = pgm.size();
-  pgm.resize(head + (size_t)nx * ny);
-  for (uint32_t r = 0; r < ny; r++) {
-    const uint8_t* src = &v[(size_t)(ny - 1 - r) * nx];
-    for (uint32_t c = 0; c < nx; c++) pgm[head + (size_t)r * nx + c] = (char)(reach ? (src[c] ? 255 : 0) : src[c]);
-  }
-  return pgm;
-}
-
-std::vector<uint8_t> pgm_plane(const std::string& path, uint32_t nx, uint32_t ny, const std::string& prefix) {
-  const std::string s = slurp(path);
-  const size_t n = (size_t)nx * ny;
-  unsigned px = 0, py = 0, maxv = 0;
-  int used = 0;
-  // (no white space behind the last number in the format: it would swallow pixels that happen to be 9 .. 13 or 32)
-  if (sscanf(s.c_str(), "P5\n%u %u\n%u%n", &px, &py, &maxv, &used) != 3 || maxv != 255 || used <= 0 || px != nx || py != ny ||
-      s.size() != (size_t)++used + n || s[(size_t)used - 1] != '\n')
+// a plane of the costmap at `prefix` from its image
+std::vector<uint8_t> window_plane(const std::string& path, uint32_t nx, uint32_t ny, const std::string& prefix) {
+  std::vector<uint8_t> v;
+  if (!pgm_plane(slurp("read_costmap", path), nx, ny, nx, ny, v))
     throw std::runtime_error("read_costmap: '" + path + "' is not an image of the window of '" + prefix + ".pgm'");
-  std::vector<uint8_t> v(n);
-  for (uint32_t r = 0; r < ny; r++) memcpy(&v[(size_t)(ny - 1 - r) * nx], &s[(size_t)used + (size_t)r * nx], nx);
   return v;
 }
 
@@ -118,17 +60,14 @@ void check_base(const CostmapBase& b, const char* who) {
 NavCostmapOptions NavCostmapOptions::FromConfig(const Config& cfg) {
   NavCostmapOptions o;
   if (cfg.has(kBlock) && !cfg[kBlock].isNull()) {
-    const Config& c = cfg[kBlock];
-    static const char* const keys[] = {"source", "inscribed_radius", "inflation_radius", "cost_scaling", "unknown_is_obstacle", "reach_from"};
-    for (const auto& kv : c.map)
-      if (std::find_if(std::begin(keys), std::end(keys), [&](const char* k) { return kv.first == k; }) == std::end(keys))
-        bad(kv.first, "is not a key of this block");
-    if (c.has("source") && !c["source"].isNull()) o.source = c["source"].asString();
-    number(c, "inscribed_radius", o.inscribed_radius);
-    number(c, "inflation_radius", o.inflation_radius);
-    number(c, "cost_scaling", o.cost_scaling);
-    boolean(c, "unknown_is_obstacle", o.unknown_is_obstacle);
-    if (c.has("reach_from") && !c["reach_from"].isNull()) o.reach_from = c["reach_from"].asString();
+    const ConfigBlock c(cfg[kBlock], kBlock);
+    c.knownKeys({"source", "inscribed_radius", "inflation_radius", "cost_scaling", "unknown_is_obstacle", "reach_from"});
+    c.text("source", o.source);
+    c.number("inscribed_radius", o.inscribed_radius);
+    c.number("inflation_radius", o.inflation_radius);
+    c.number("cost_scaling", o.cost_scaling);
+    c.boolean("unknown_is_obstacle", o.unknown_is_obstacle);
+    c.text("reach_from", o.reach_from);
   }
   o.validate();
   return o;
@@ -242,11 +181,12 @@ void write_costmap(const NavCostmap& c, const std::string& prefix) {
   g.cells.resize(n);
   for (size_t i = 0; i < n; i++) g.cells[i] = c.cost[i] == MH_NAV_UNKNOWN ? kGridUnknown : c.cost[i] >= 253 ? kGridOccupied : kGridFree;
   write_occupancy_grid(g, prefix);
+  const char* const who = "write_costmap";
   const std::string name = base_name(prefix);
-  write_file(prefix + ".yaml", "cost_image: " + name + "_cost.pgm\nreach_image: " + name + "_reach.pgm\ninscribed_radius: " + g9(c.inscribed_radius) +
-                                   "\ninflation_radius: " + g9(c.inflation_radius) + "\n", std::ios::app);
-  write_file(prefix + "_cost.pgm", plane_pgm(c.cost, c.nx, c.ny, false), std::ios::trunc);
-  write_file(prefix + "_reach.pgm", plane_pgm(c.reach, c.nx, c.ny, true), std::ios::trunc);
+  write_file(who, prefix + ".yaml", "cost_image: " + name + "_cost.pgm\nreach_image: " + name + "_reach.pgm\ninscribed_radius: " + g9(c.inscribed_radius) +
+                                        "\ninflation_radius: " + g9(c.inflation_radius) + "\n", std::ios::app);
+  write_file(who, prefix + "_cost.pgm", pgm_bytes(c.cost.data(), c.nx, c.ny), std::ios::trunc);
+  write_file(who, prefix + "_reach.pgm", pgm_bytes(c.reach.data(), c.nx, c.ny, reach_byte), std::ios::trunc);
 }
 
 NavCostmap read_costmap(const std::string& prefix) {
@@ -254,24 +194,16 @@ NavCostmap read_costmap(const std::string& prefix) {
   NavCostmap c;
   c.x0 = g.x0; c.y0 = g.y0; c.nx = g.nx; c.ny = g.ny;
   c.resolution = g.resolution;
-  std::string cost_name, reach_name;
-  bool have_a = false, have_b = false;
-  {
-    std::istringstream in(slurp(prefix + ".yaml"));
-    std::string line;
-    while (std::getline(in, line)) {
-      if (line.rfind("cost_image: ", 0) == 0) cost_name = line.substr(12);
-      else if (line.rfind("reach_image: ", 0) == 0) reach_name = line.substr(13);
-      else if (line.rfind("inscribed_radius:", 0) == 0) { c.inscribed_radius = strtod(line.c_str() + 17, nullptr); have_a = true; }
-      else if (line.rfind("inflation_radius:", 0) == 0) { c.inflation_radius = strtod(line.c_str() + 17, nullptr); have_b = true; }
-    }
-  }
-  if (cost_name.empty() || reach_name.empty() || !have_a || !have_b)
+  const std::string yaml = slurp("read_costmap", prefix + ".yaml"), dir = dir_of(prefix);
+  std::string cost_name, reach_name, inscribed, inflation;
+  yaml_line(yaml, "cost_image: ", cost_name);
+  yaml_line(yaml, "reach_image: ", reach_name);
+  if (cost_name.empty() || reach_name.empty() || !yaml_line(yaml, "inscribed_radius:", inscribed) || !yaml_line(yaml, "inflation_radius:", inflation))
     throw std::runtime_error("read_costmap: '" + prefix + ".yaml' lacks cost_image, reach_image, inscribed_radius or inflation_radius");
-  const size_t slash = prefix.find_last_of('/');
-  const std::string dir = slash == std::string::npos ? "" : prefix.substr(0, slash + 1);
-  c.cost = pgm_plane(dir + cost_name, c.nx, c.ny, prefix);
-  c.reach = pgm_plane(dir + reach_name, c.nx, c.ny, prefix);
+  c.inscribed_radius = strtod(inscribed.c_str(), nullptr);
+  c.inflation_radius = strtod(inflation.c_str(), nullptr);
+  c.cost = window_plane(dir + cost_name, c.nx, c.ny, prefix);
+  c.reach = window_plane(dir + reach_name, c.nx, c.ny, prefix);
   for (size_t i = 0; i < c.cost.size(); i++) {
     const int8_t want = c.cost[i] == MH_NAV_UNKNOWN ? kGridUnknown : c.cost[i] >= 253 ? kGridOccupied : kGridFree;
     if (g.cells[i] != want) throw std::runtime_error("read_costmap: '" + dir + cost_name + "' disagrees with the trinary image '" + prefix + ".pgm'");

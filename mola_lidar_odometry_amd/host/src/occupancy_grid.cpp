@@ -7,10 +7,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
-#include <sstream>
 #include <stdexcept>
 
+#include "config_block.h"
+#include "map_files.h"
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
 
 namespace mola_hip {
@@ -19,43 +19,11 @@ namespace {
 
 const char* const kBlock = "occupancy_grid";
 
-[[noreturn]] void bad(const std::string& key, const std::string& what) { throw std::runtime_error(std::string(kBlock) + ": " + key + " " + what); }
-
-void number(const Config& c, const char* k, double& v) {
-  if (!c.has(k) || c[k].isNull()) return;
-  const std::string s = c[k].asString();
-  char* end = nullptr;
-  v = strtod(s.c_str(), &end);
-  if (end == s.c_str() || *end != '\0') bad(k, "must be a number");
-}
-
-void count(const Config& c, const char* k, uint32_t& v) {
-  double d = v;
-  number(c, k, d);
-  if (!(d >= 0.0) || !(d <= 4294967295.0) || d != std::floor(d)) bad(k, "must be an integer >= 0");
-  v = (uint32_t)d;
-}
-
-void boolean(const Config& c, const char* k, bool& v) {
-  if (!c.has(k) || c[k].isNull()) return;
-  const std::string s = c[k].asString();
-  if (s == "true" || s == "True" || s == "1" || s == "yes") v = true;
-  else if (s == "false" || s == "False" || s == "0" || s == "no") v = false;
-  else bad(k, "must be true or false");
-}
+[[noreturn]] void bad(const std::string& key, const std::string& what) { bad_option(kBlock, key, what); }
 
 bool in01(double p) { return p > 0.0 && p < 1.0; }
 
-std::string g9(double v) {
-  char buf[64];
-  snprintf(buf, sizeof(buf), "%.9g", v);
-  return buf;
-}
-
-std::string base_name(const std::string& path) {
-  const size_t s = path.find_last_of('/');
-  return s == std::string::npos ? path : path.substr(s + 1);
-}
+uint8_t trinary_byte(uint8_t cell) { return (int8_t)cell == kGridOccupied ? 0 : (int8_t)cell == kGridFree ? 254 : 205; }
 
 }  // namespace
 
@@ -63,24 +31,20 @@ std::string base_name(const std::string& path) {
 OccupancyGridOptions OccupancyGridOptions::FromConfig(const Config& cfg) {
   OccupancyGridOptions o;
   if (cfg.has(kBlock) && !cfg[kBlock].isNull()) {
-    const Config& c = cfg[kBlock];
-    static const char* const keys[] = {"resolution", "prob_hit", "prob_miss", "clamp_min", "clamp_max", "occupied_threshold",
-                                       "ray_trace_free_space", "max_range", "decimation", "update_rule", "target_map", "z_min", "z_max",
-                                       "margin_cells"};
-    for (const auto& kv : c.map)
-      if (std::find_if(std::begin(keys), std::end(keys), [&](const char* k) { return kv.first == k; }) == std::end(keys))
-        bad(kv.first, "is not a key of this block");
-    number(c, "resolution", o.resolution);
-    number(c, "prob_hit", o.prob_hit); number(c, "prob_miss", o.prob_miss);
-    number(c, "clamp_min", o.clamp_min); number(c, "clamp_max", o.clamp_max);
-    number(c, "occupied_threshold", o.occupied_threshold);
-    boolean(c, "ray_trace_free_space", o.ray_trace_free_space);
-    number(c, "max_range", o.max_range);
-    count(c, "decimation", o.decimation);
-    if (c.has("update_rule") && !c["update_rule"].isNull()) o.update_rule = c["update_rule"].asString();
-    if (c.has("target_map") && !c["target_map"].isNull()) o.target_map = c["target_map"].asString();
-    number(c, "z_min", o.z_min); number(c, "z_max", o.z_max);
-    count(c, "margin_cells", o.margin_cells);
+    const ConfigBlock c(cfg[kBlock], kBlock);
+    c.knownKeys({"resolution", "prob_hit", "prob_miss", "clamp_min", "clamp_max", "occupied_threshold", "ray_trace_free_space", "max_range",
+                 "decimation", "update_rule", "target_map", "z_min", "z_max", "margin_cells"});
+    c.number("resolution", o.resolution);
+    c.number("prob_hit", o.prob_hit); c.number("prob_miss", o.prob_miss);
+    c.number("clamp_min", o.clamp_min); c.number("clamp_max", o.clamp_max);
+    c.number("occupied_threshold", o.occupied_threshold);
+    c.boolean("ray_trace_free_space", o.ray_trace_free_space);
+    c.number("max_range", o.max_range);
+    c.count("decimation", o.decimation);
+    c.text("update_rule", o.update_rule);
+    c.text("target_map", o.target_map);
+    c.number("z_min", o.z_min); c.number("z_max", o.z_max);
+    c.count("margin_cells", o.margin_cells);
   }
   o.validate();
   return o;
@@ -135,70 +99,34 @@ void occupancy_grid_classify(OccupancyGrid& g) {
 void write_occupancy_grid(const OccupancyGrid& g, const std::string& prefix) {
   const size_t n = (size_t)g.nx * g.ny;
   if (g.cells.size() != n || n == 0) throw std::runtime_error("write_occupancy_grid: the grid holds no cells");
-  std::string pgm = "P5\n" + std::to_string(g.nx) + " " + std::to_string(g.ny) + "\n255\n";
-  const size_t head = pgm.size();
-  pgm.resize(head + n);
-  for (uint32_t r = 0; r < g.ny; r++) {  // row 0 of the image is the largest y
-    const int8_t* src = &g.cells[(size_t)(g.ny - 1 - r) * g.nx];
-    for (uint32_t c = 0; c < g.nx; c++)
-      pgm[head + (size_t)r * g.nx + c] = (char)(src[c] == kGridOccupied ? 0 : src[c] == kGridFree ? 254 : 205);
-  }
-  const std::string yaml = "image: " + base_name(prefix) + ".pgm\nresolution: " + g9(g.resolution) + "\norigin: [" +
-                           g9((double)g.x0 * g.resolution) + ", " + g9((double)g.y0 * g.resolution) +
-                           ", 0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n";
-  const std::pair<std::string, const std::string*> files[] = {{prefix + ".pgm", &pgm}, {prefix + ".yaml", &yaml}};
-  for (const auto& f : files) {
-    std::ofstream out(f.first, std::ios::binary | std::ios::trunc);
-    out.write(f.second->data(), (std::streamsize)f.second->size());
-    out.close();
-    if (!out) throw std::runtime_error("write_occupancy_grid: cannot write '" + f.first + "'");
-  }
+  write_file("write_occupancy_grid", prefix + ".pgm", pgm_bytes((const uint8_t*)g.cells.data(), g.nx, g.ny, trinary_byte), std::ios::trunc);
+  write_file("write_occupancy_grid", prefix + ".yaml",
+             "image: " + base_name(prefix) + ".pgm\nresolution: " + g9(g.resolution) + "\norigin: [" + g9((double)g.x0 * g.resolution) + ", " +
+                 g9((double)g.y0 * g.resolution) + ", 0]\nnegate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n",
+             std::ios::trunc);
 }
 
 OccupancyGrid read_occupancy_grid(const std::string& prefix) {
   OccupancyGrid g;
-  {
-    const std::string path = prefix + ".yaml";
-    std::ifstream in(path);
-    if (!in) throw std::runtime_error("read_occupancy_grid: cannot open '" + path + "'");
-    std::string line;
-    double ox = 0, oy = 0;
-    bool have_res = false, have_origin = false;
-    while (std::getline(in, line)) {
-      if (line.rfind("resolution:", 0) == 0) {
-        g.resolution = strtod(line.c_str() + 11, nullptr);
-        have_res = true;
-      } else if (line.rfind("origin:", 0) == 0) {
-        have_origin = sscanf(line.c_str() + 7, " [%lf , %lf", &ox, &oy) == 2;
-      }
-    }
-    if (!have_res || !have_origin || !(g.resolution > 0.0)) throw std::runtime_error("read_occupancy_grid: '" + path + "' lacks resolution or origin");
-    g.x0 = (int32_t)std::llround(ox / g.resolution);
-    g.y0 = (int32_t)std::llround(oy / g.resolution);
-  }
-  const std::string path = prefix + ".pgm";
-  std::ifstream in(path, std::ios::binary);
-  if (!in) throw std::runtime_error("read_occupancy_grid: cannot open '" + path + "'");
-  std::stringstream ss;
-  ss << in.rdbuf();
-  const std::string s = ss.str();
-  unsigned nx = 0, ny = 0, maxv = 0;
-  int used = 0;
-  if (sscanf(s.c_str(), "P5\n%u %u\n%u\n%n", &nx, &ny, &maxv, &used) != 3 || maxv != 255 || used <= 0 || nx == 0 || ny == 0 ||
-      s.size() != (size_t)used + (size_t)nx * ny)
+  const std::string yaml = slurp("read_occupancy_grid", prefix + ".yaml"), path = prefix + ".pgm";
+  std::string res, origin;
+  double ox = 0, oy = 0;
+  if (!yaml_line(yaml, "resolution:", res) || !yaml_line(yaml, "origin:", origin) || sscanf(origin.c_str(), " [%lf , %lf", &ox, &oy) != 2 ||
+      !((g.resolution = strtod(res.c_str(), nullptr)) > 0.0))
+    throw std::runtime_error("read_occupancy_grid: '" + prefix + ".yaml' lacks resolution or origin");
+  g.x0 = (int32_t)std::llround(ox / g.resolution);
+  g.y0 = (int32_t)std::llround(oy / g.resolution);
+  std::vector<uint8_t> bytes;
+  if (!pgm_plane(slurp("read_occupancy_grid", path), 0, 0, g.nx, g.ny, bytes))
     throw std::runtime_error("read_occupancy_grid: '" + path + "' is not a binary PGM written by write_occupancy_grid");
-  g.nx = nx;
-  g.ny = ny;
-  g.cells.resize((size_t)nx * ny);
-  for (uint32_t r = 0; r < ny; r++)
-    for (uint32_t c = 0; c < nx; c++) {
-      const unsigned char v = (unsigned char)s[(size_t)used + (size_t)r * nx + c];
-      int8_t& out = g.cells[(size_t)(ny - 1 - r) * nx + c];
-      if (v == 0) { out = kGridOccupied; g.cells_occupied++; }
-      else if (v == 254) { out = kGridFree; g.cells_free++; }
-      else if (v == 205) { out = kGridUnknown; g.cells_unknown++; }
-      else throw std::runtime_error("read_occupancy_grid: '" + path + "' holds a byte that is neither 0, 254 nor 205");
-    }
+  g.cells.resize(bytes.size());
+  for (size_t i = 0; i < bytes.size(); i++) {
+    const uint8_t v = bytes[i];
+    if (v == 0) { g.cells[i] = kGridOccupied; g.cells_occupied++; }
+    else if (v == 254) { g.cells[i] = kGridFree; g.cells_free++; }
+    else if (v == 205) { g.cells[i] = kGridUnknown; g.cells_unknown++; }
+    else throw std::runtime_error("read_occupancy_grid: '" + path + "' holds a byte that is neither 0, 254 nor 205");
+  }
   return g;
 }
 
@@ -206,13 +134,7 @@ OccupancyGrid read_occupancy_grid(const std::string& prefix) {
 OccupancyGrid build_occupancy_grid(const molahip_host::KeyFrameSet& set, const OccupancyGridOptions& opt, std::shared_ptr<DeviceContext> ctx,
                                    uint64_t max_points_per_pass) {
   opt.validate();
-  if (set.maps.empty()) throw std::runtime_error("build_occupancy_grid: the key-frame set names no target map");
-  size_t map_index = 0;
-  if (!opt.target_map.empty()) {
-    while (map_index < set.maps.size() && set.maps[map_index].name != opt.target_map) map_index++;
-    if (map_index == set.maps.size())
-      throw std::runtime_error("build_occupancy_grid: occupancy_grid: target_map '" + opt.target_map + "' is not a target map of the key-frame set");
-  }
+  const size_t map_index = target_map_index(set, opt.target_map, "build_occupancy_grid", kBlock);
   const std::vector<mp2p_icp_hip::PosedFrame> frames = session_map_frames(set, map_index);
   OccupancyGrid g;
   g.resolution = opt.resolution;

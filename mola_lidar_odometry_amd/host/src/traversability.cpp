@@ -8,11 +8,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <fstream>
 #include <limits>
-#include <sstream>
 #include <stdexcept>
 
+#include "config_block.h"
+#include "map_files.h"
 #include "mola_lidar_odometry_hip/LidarOdometry.h"
 #include "mola_lidar_odometry_hip/OccupancyGrid.h"
 
@@ -23,48 +23,7 @@ namespace {
 const char* const kBlock = "traversability";
 const double kPi = 3.14159265358979323846;
 
-[[noreturn]] void bad(const std::string& key, const std::string& what) { throw std::runtime_error(std::string(kBlock) + ": " + key + " " + what); }
-
-void number(const Config& c, const char* k, double& v) {
-  if (!c.has(k) || c[k].isNull()) return;
-  const std::string s = c[k].asString();
-  char* end = nullptr;
-  v = strtod(s.c_str(), &end);
-  if (end == s.c_str() || *end != '\0') bad(k, "must be a number");
-}
-
-void count(const Config& c, const char* k, uint32_t& v) {
-  double d = v;
-  number(c, k, d);
-  if (!(d >= 0.0) || !(d <= 4294967295.0) || d != std::floor(d)) bad(k, "must be an integer >= 0");
-  v = (uint32_t)d;
-}
-
-std::string g9(double v) {
-  char buf[64];
-  snprintf(buf, sizeof(buf), "%.9g", v);
-  return buf;
-}
-
-std::string base_name(const std::string& path) {
-  const size_t s = path.find_last_of('/');
-  return s == std::string::npos ? path : path.substr(s + 1);
-}
-
-void write_file(const std::string& path, const std::string& bytes, std::ios::openmode mode) {
-  std::ofstream out(path, std::ios::binary | mode);
-  out.write(bytes.data(), (std::streamsize)bytes.size());
-  out.close();
-  if (!out) throw std::runtime_error("write_traversability_map: cannot write '" + path + "'");
-}
-
-std::string slurp(const std::string& path) {
-  std::ifstream in(path, std::ios::binary);
-  if (!in) throw std::runtime_error("read_traversability_map: cannot open '" + path + "'");
-  std::stringstream ss;
-  ss << in.rdbuf();
-  return ss.str();
-}
+[[noreturn]] void bad(const std::string& key, const std::string& what) { bad_option(kBlock, key, what); }
 
 const double kQMax = 1073741824.0;  // 2^30: what a height may reach in quanta (molahip_elevation.h, case 3)
 
@@ -74,23 +33,20 @@ const double kQMax = 1073741824.0;  // 2^30: what a height may reach in quanta (
 TraversabilityOptions TraversabilityOptions::FromConfig(const Config& cfg) {
   TraversabilityOptions o;
   if (cfg.has(kBlock) && !cfg[kBlock].isNull()) {
-    const Config& c = cfg[kBlock];
-    static const char* const keys[] = {"resolution", "z_quantum", "max_range", "vehicle_height", "max_step", "slope_radius_cells",
-                                       "max_slope_deg", "min_points_per_cell", "min_obstacle_points", "target_map", "margin_cells"};
-    for (const auto& kv : c.map)
-      if (std::find_if(std::begin(keys), std::end(keys), [&](const char* k) { return kv.first == k; }) == std::end(keys))
-        bad(kv.first, "is not a key of this block");
-    number(c, "resolution", o.resolution);
-    number(c, "z_quantum", o.z_quantum);
-    number(c, "max_range", o.max_range);
-    number(c, "vehicle_height", o.vehicle_height);
-    number(c, "max_step", o.max_step);
-    count(c, "slope_radius_cells", o.slope_radius_cells);
-    number(c, "max_slope_deg", o.max_slope_deg);
-    count(c, "min_points_per_cell", o.min_points_per_cell);
-    count(c, "min_obstacle_points", o.min_obstacle_points);
-    if (c.has("target_map") && !c["target_map"].isNull()) o.target_map = c["target_map"].asString();
-    count(c, "margin_cells", o.margin_cells);
+    const ConfigBlock c(cfg[kBlock], kBlock);
+    c.knownKeys({"resolution", "z_quantum", "max_range", "vehicle_height", "max_step", "slope_radius_cells", "max_slope_deg",
+                 "min_points_per_cell", "min_obstacle_points", "target_map", "margin_cells"});
+    c.number("resolution", o.resolution);
+    c.number("z_quantum", o.z_quantum);
+    c.number("max_range", o.max_range);
+    c.number("vehicle_height", o.vehicle_height);
+    c.number("max_step", o.max_step);
+    c.count("slope_radius_cells", o.slope_radius_cells);
+    c.number("max_slope_deg", o.max_slope_deg);
+    c.count("min_points_per_cell", o.min_points_per_cell);
+    c.count("min_obstacle_points", o.min_obstacle_points);
+    c.text("target_map", o.target_map);
+    c.count("margin_cells", o.margin_cells);
   }
   o.validate();
   return o;
@@ -155,22 +111,18 @@ void write_traversability_map(const TraversabilityMap& m, const std::string& pre
   g.cells.resize(n);
   for (size_t i = 0; i < n; i++) g.cells[i] = m.cost[i] == kCostLethal ? kGridOccupied : m.cost[i] == kCostUnknown ? kGridUnknown : kGridFree;
   write_occupancy_grid(g, prefix);
+  const char* const who = "write_traversability_map";
   const std::string name = base_name(prefix);
-  write_file(prefix + ".yaml", "cost_image: " + name + "_cost.pgm\nheight_file: " + name + "_height.f32\nz_quantum: " + g9(m.z_quantum) +
-                                   "\nheight_row_order: bottom_up\n", std::ios::app);
-  std::string pgm = "P5\n" + std::to_string(m.nx) + " " + std::to_string(m.ny) + "\n255\n";
-  const size_t head = pgm.size();
-  pgm.resize(head + n);
-  for (uint32_t r = 0; r < m.ny; r++)  // row 0 of the image is the largest y
-    memcpy(&pgm[head + (size_t)r * m.nx], &m.cost[(size_t)(m.ny - 1 - r) * m.nx], m.nx);
-  write_file(prefix + "_cost.pgm", pgm, std::ios::trunc);
+  write_file(who, prefix + ".yaml", "cost_image: " + name + "_cost.pgm\nheight_file: " + name + "_height.f32\nz_quantum: " + g9(m.z_quantum) +
+                                        "\nheight_row_order: bottom_up\n", std::ios::app);
+  write_file(who, prefix + "_cost.pgm", pgm_bytes(m.cost.data(), m.nx, m.ny), std::ios::trunc);
   std::string f32(n * 4, '\0');
   for (size_t i = 0; i < n; i++) {  // little-endian, whatever the host
     uint32_t u;
     memcpy(&u, &m.height[i], 4);
     for (int b = 0; b < 4; b++) f32[4 * i + b] = (char)((u >> (8 * b)) & 0xFF);
   }
-  write_file(prefix + "_height.f32", f32, std::ios::trunc);
+  write_file(who, prefix + "_height.f32", f32, std::ios::trunc);
 }
 
 TraversabilityMap read_traversability_map(const std::string& prefix) {
@@ -179,30 +131,19 @@ TraversabilityMap read_traversability_map(const std::string& prefix) {
   m.x0 = g.x0; m.y0 = g.y0; m.nx = g.nx; m.ny = g.ny;
   m.resolution = g.resolution;
   const size_t n = (size_t)m.nx * m.ny;
-  std::string cost_name, height_name, order;
-  {
-    std::istringstream in(slurp(prefix + ".yaml"));
-    std::string line;
-    while (std::getline(in, line)) {
-      if (line.rfind("cost_image: ", 0) == 0) cost_name = line.substr(12);
-      else if (line.rfind("height_file: ", 0) == 0) height_name = line.substr(13);
-      else if (line.rfind("z_quantum:", 0) == 0) m.z_quantum = strtod(line.c_str() + 10, nullptr);
-      else if (line.rfind("height_row_order: ", 0) == 0) order = line.substr(18);
-    }
-  }
+  const char* const who = "read_traversability_map";
+  const std::string yaml = slurp(who, prefix + ".yaml"), dir = dir_of(prefix);
+  std::string cost_name, height_name, quantum, order;
+  yaml_line(yaml, "cost_image: ", cost_name);
+  yaml_line(yaml, "height_file: ", height_name);
+  if (yaml_line(yaml, "z_quantum:", quantum)) m.z_quantum = strtod(quantum.c_str(), nullptr);
+  yaml_line(yaml, "height_row_order: ", order);
   if (cost_name.empty() || height_name.empty() || !(m.z_quantum > 0.0) || order != "bottom_up")
     throw std::runtime_error("read_traversability_map: '" + prefix + ".yaml' lacks cost_image, height_file, z_quantum or height_row_order: bottom_up");
-  const size_t slash = prefix.find_last_of('/');
-  const std::string dir = slash == std::string::npos ? "" : prefix.substr(0, slash + 1);
   {
-    const std::string path = dir + cost_name, s = slurp(path);
-    unsigned nx = 0, ny = 0, maxv = 0;
-    int used = 0;
-    if (sscanf(s.c_str(), "P5\n%u %u\n%u\n%n", &nx, &ny, &maxv, &used) != 3 || maxv != 255 || used <= 0 || nx != m.nx || ny != m.ny ||
-        s.size() != (size_t)used + n)
+    const std::string path = dir + cost_name;
+    if (!pgm_plane(slurp(who, path), g.nx, g.ny, m.nx, m.ny, m.cost))
       throw std::runtime_error("read_traversability_map: '" + path + "' is not the cost image of '" + prefix + ".pgm'");
-    m.cost.resize(n);
-    for (uint32_t r = 0; r < m.ny; r++) memcpy(&m.cost[(size_t)(m.ny - 1 - r) * m.nx], &s[(size_t)used + (size_t)r * m.nx], m.nx);
     for (size_t i = 0; i < n; i++) {
       const uint8_t c = m.cost[i];
       const int8_t want = c == kCostLethal ? kGridOccupied : c == kCostUnknown ? kGridUnknown : kGridFree;
@@ -212,7 +153,7 @@ TraversabilityMap read_traversability_map(const std::string& prefix) {
     }
   }
   {
-    const std::string path = dir + height_name, s = slurp(path);
+    const std::string path = dir + height_name, s = slurp(who, path);
     if (s.size() != 4 * n) throw std::runtime_error("read_traversability_map: '" + path + "' does not hold ny * nx float32 values");
     m.height.resize(n);
     for (size_t i = 0; i < n; i++) {
@@ -229,13 +170,7 @@ TraversabilityMap build_traversability_map(const molahip_host::KeyFrameSet& set,
                                            std::shared_ptr<DeviceContext> ctx, uint64_t max_points_per_pass) {
   using mp2p_icp_hip::check;
   opt.validate();
-  if (set.maps.empty()) throw std::runtime_error("build_traversability_map: the key-frame set names no target map");
-  size_t map_index = 0;
-  if (!opt.target_map.empty()) {
-    while (map_index < set.maps.size() && set.maps[map_index].name != opt.target_map) map_index++;
-    if (map_index == set.maps.size())
-      throw std::runtime_error("build_traversability_map: traversability: target_map '" + opt.target_map + "' is not a target map of the key-frame set");
-  }
+  const size_t map_index = target_map_index(set, opt.target_map, "build_traversability_map", kBlock);
   const std::vector<mp2p_icp_hip::PosedFrame> posed = session_map_frames(set, map_index);
   TraversabilityMap m;
   m.resolution = opt.resolution;
@@ -246,13 +181,8 @@ TraversabilityMap build_traversability_map(const molahip_host::KeyFrameSet& set,
   m.min_points_per_cell = opt.min_points_per_cell;
   m.min_obstacle_points = opt.min_obstacle_points;
   m.frames = posed.size();
-  std::vector<mh_map_frame> frames(posed.size());
-  for (size_t k = 0; k < posed.size(); k++) {
-    frames[k].x = posed[k].x; frames[k].y = posed[k].y; frames[k].z = posed[k].z;
-    frames[k].n = posed[k].n;
-    std::copy(posed[k].pose.T, posed[k].pose.T + 12, frames[k].T);
-    m.points += posed[k].n;
-  }
+  const std::vector<mh_map_frame> frames = mp2p_icp_hip::to_map_frames(posed);
+  for (const auto& f : posed) m.points += f.n;
   if (!m.points)
     throw std::runtime_error("build_traversability_map: the key-frames hold no points for target map '" + set.maps[map_index].name + "'");
   if (!ctx) ctx = DeviceContext::Default();

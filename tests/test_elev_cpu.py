@@ -134,6 +134,7 @@ def _hand_map(x0=-7, y0=3, q=0.01):
 
 def test_the_four_files_are_the_restatement_s_bytes_and_read_back_to_the_same_bytes(host, tmp_path):
     m, ground, count = _hand_map()
+    m["cost"][-1, :3] = (10, 32, 9)                # the image's first pixels are white space to a careless header parser
     prefix = str(tmp_path / "hill")
     host.write_traversability_map(m, prefix)
     files = {s: open(prefix + s, "rb").read() for s in (".pgm", ".yaml", "_cost.pgm", "_height.f32")}
@@ -155,6 +156,33 @@ def test_the_four_files_are_the_restatement_s_bytes_and_read_back_to_the_same_by
     g = host.read_occupancy_grid(prefix)
     assert (g["x0"], g["y0"], g["nx"], g["ny"]) == (-7, 3, 4, 3)
     assert np.array_equal(g["cells"], np.where(m["cost"] == 254, 100, np.where(m["cost"] == 255, -1, 0)))
+
+
+@pytest.mark.parametrize("v", [9, 10, 11, 12, 13, 32])
+def test_a_cost_image_whose_first_pixel_is_white_space_reads_back(host, tmp_path, v):
+    m, _, _ = _hand_map()
+    m["cost"][-1, 0] = v                           # (the largest y, column 0: the byte behind the header)
+    prefix = str(tmp_path / "m")
+    host.write_traversability_map(m, prefix)
+    raw = open(prefix + "_cost.pgm", "rb").read()
+    assert raw == R.cost_pgm_bytes(m["cost"]) and raw[:11] == b"P5\n4 3\n255\n" and raw[11] == v
+    back = host.read_traversability_map(prefix)
+    assert back["cost"].tobytes() == m["cost"].tobytes() and back["height"].tobytes() == m["height"].tobytes()
+    assert (back["cells_lethal"], back["cells_free"], back["cells_unknown"]) == (2, 8, 2)
+
+
+@pytest.mark.parametrize("header", [b"P5\n4 3\n255 ", b"P5\n4 3\n255\n\n", b"P5\n4 3\n254\n", b"P5\n3 4\n255\n", b"P5\n4 4\n255\n"])
+def test_a_cost_image_whose_header_is_not_the_writer_s_is_refused(host, tmp_path, header):
+    m, _, _ = _hand_map()
+    prefix = str(tmp_path / "m")
+    host.write_traversability_map(m, prefix)
+    raw = open(prefix + "_cost.pgm", "rb").read()
+    assert raw[:11] == b"P5\n4 3\n255\n"
+    open(prefix + "_cost.pgm", "wb").write(header + raw[11:])
+    with pytest.raises(RuntimeError, match="is not the cost image of"):
+        host.read_traversability_map(prefix)
+    open(prefix + "_cost.pgm", "wb").write(raw)
+    assert np.array_equal(host.read_traversability_map(prefix)["cost"], m["cost"])
 
 
 def test_the_reader_and_the_writer_refuse_what_they_cannot_take(host, tmp_path):

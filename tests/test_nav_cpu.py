@@ -213,6 +213,21 @@ def test_the_reader_and_the_writer_refuse_what_they_cannot_take(host, tmp_path):
         host.read_costmap(prefix)
 
 
+@pytest.mark.parametrize("image", ["_cost.pgm", "_reach.pgm"])
+@pytest.mark.parametrize("change", [(b"255\n", b"255 "), (b"255\n", b"255\n\n"), (b"255\n", b"254\n"), (b"23 11", b"11 23"), (b"23 11", b"23 12")])
+def test_an_image_whose_header_is_not_the_writer_s_is_refused(host, tmp_path, image, change):
+    want = _costmap()
+    prefix = str(tmp_path / "m")
+    host.write_costmap(want, prefix)
+    raw = open(prefix + image, "rb").read()
+    assert raw[:13] == b"P5\n23 11\n255\n" and len(raw) == 13 + 23 * 11
+    open(prefix + image, "wb").write(raw[:13].replace(*change) + raw[13:])
+    with pytest.raises(RuntimeError, match="is not an image of the window of"):
+        host.read_costmap(prefix)
+    open(prefix + image, "wb").write(raw)
+    assert np.array_equal(host.read_costmap(prefix)["cost"], want["cost"])
+
+
 # ---- the command line ---------------------------------------------------------------------------------------------------------------
 def test_the_command_line_refuses_before_a_device_is_asked_for(tmp_path):
     run = lambda *a: subprocess.run([CLI, *a], capture_output=True, text=True, timeout=60)

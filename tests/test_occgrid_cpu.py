@@ -142,6 +142,25 @@ def test_a_bad_value_or_an_unknown_key_is_refused_by_name(host, key, value):
         host.occupancy_grid_options("occupancy_grid:\n  %s: %s\n" % (key, value))
 
 
+# the six option blocks that are read alike: (entry point, block, a number key, a count key, a boolean key)
+OPTION_BLOCKS = [("occupancy_grid_options", "occupancy_grid", "resolution", "decimation", "ray_trace_free_space"),
+                 ("traversability_options", "traversability", "resolution", "margin_cells", None),
+                 ("costmap_options", "costmap", "cost_scaling", None, "unknown_is_obstacle"),
+                 ("gyro_deskew_options", "gyro_deskew", "max_gap", None, "enabled"),
+                 ("map_cleaning_options", "map_cleaning", "rel_margin", "n_rings", None),
+                 ("online_map_cleaning_options", "online_map_cleaning", "rel_margin", "max_views", "enabled")]
+
+
+@pytest.mark.parametrize("entry,block,key", [(e, b, k) for e, b, *keys in OPTION_BLOCKS for k in keys if k])
+def test_every_block_refuses_a_list_a_map_and_text_by_name_and_takes_null_as_absent(host, entry, block, key):
+    read = getattr(host, entry)
+    for value in ("[1, 2]", "{a: 1}", "1x"):
+        with pytest.raises(RuntimeError, match=r"%s: %s\b" % (block, key)):
+            read("%s:\n  %s: %s\n" % (block, key, value))
+    for null in ("~", ""):                                     # (this YAML subset's nulls)
+        assert read("%s:\n  %s: %s\n" % (block, key, null)) == read()
+
+
 # ---- the host rules ----------------------------------------------------------------------------------------------------------------
 def test_heights_become_indices_by_the_floor_rule_on_boundaries(host):
     hand = {(0.0, 0.05): 0, (-1e-12, 0.05): -1, (0.05, 0.05): 1, (0.0499999, 0.05): 0, (-0.05, 0.05): -1, (-0.0500001, 0.05): -2,
@@ -210,6 +229,20 @@ def test_the_reader_and_the_writer_refuse_what_they_cannot_take(host, tmp_path):
     open(prefix + ".pgm", "wb").write(raw[:-1] + b"\x07")
     with pytest.raises(RuntimeError, match="neither"):
         host.read_occupancy_grid(prefix)
+
+
+# (this reader has no other image to hold the size against: a size is wrong when it is not the size of what follows the header)
+@pytest.mark.parametrize("header", [b"P5\n7 5\n255 ", b"P5\n7 5\n255\n\n", b"P5\n7 5\n254\n", b"P5\n7 6\n255\n", b"P5\n0 5\n255\n"])
+def test_an_image_whose_header_is_not_the_writer_s_is_refused(host, tmp_path, header):
+    prefix = str(tmp_path / "g")
+    host.write_occupancy_grid(_hand_grid(), prefix)
+    raw = open(prefix + ".pgm", "rb").read()
+    assert raw[:11] == b"P5\n7 5\n255\n"
+    open(prefix + ".pgm", "wb").write(header + raw[11:])
+    with pytest.raises(RuntimeError, match="is not a binary PGM written by write_occupancy_grid"):
+        host.read_occupancy_grid(prefix)
+    open(prefix + ".pgm", "wb").write(raw)
+    assert (host.read_occupancy_grid(prefix)["cells"] == _hand_grid()["cells"]).all()
 
 
 def test_the_cli_refuses_a_missing_file_by_name_and_an_incomplete_form(tmp_path):

@@ -159,6 +159,28 @@ int main(int argc, char** argv) {
       CHECK(refuses([&] { (void)read_traversability_map(dir + "/plain"); }));
     }
   }
+  // ---- a cost image whose first pixels (the largest y, from column 0) are white space to a careless header parser reads back
+  for (int first : {9, 10, 11, 12, 13, 32, -1}) {
+    TraversabilityMap m;
+    m.nx = 4; m.ny = 3;
+    m.resolution = 0.2; m.z_quantum = 0.01;
+    m.x0 = -7; m.y0 = 3;
+    m.cost = {255, 0, 17, 254, 251, 254, 255, 1, 0, 0, 0, 0};
+    if (first >= 0) m.cost[8] = (uint8_t)first;
+    else { m.cost[8] = 10; m.cost[9] = 32; m.cost[10] = 9; }
+    m.height.assign(12, 0.25f);
+    const std::string prefix = dir + "/white" + std::to_string(first + 1);
+    write_traversability_map(m, prefix);
+    const std::string cost = slurp(prefix + "_cost.pgm");
+    CHECK(cost.size() == 11 + 12 && cost.compare(0, 11, "P5\n4 3\n255\n") == 0 && (uint8_t)cost[11] == m.cost[8]);
+    const TraversabilityMap back = read_traversability_map(prefix);
+    CHECK(back.nx == 4 && back.ny == 3 && back.cost == m.cost && back.height == m.height);
+    CHECK(back.cells_lethal == 2 && back.cells_free == 8 && back.cells_unknown == 2);
+    for (const char* head : {"P5\n4 3\n255 ", "P5\n4 3\n255\n\n", "P5\n4 3\n254\n", "P5\n3 4\n255\n", "P5\n4 4\n255\n"}) {  // not the writer's header
+      spit(prefix + "_cost.pgm", head + cost.substr(11));
+      CHECK(refuses([&] { (void)read_traversability_map(prefix); }));
+    }
+  }
   // ---- a set without points is refused before any device is asked for
   molahip_host::KeyFrameSet set;
   CHECK(refuses([&] { (void)build_traversability_map(set, d); }));

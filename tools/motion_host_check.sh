@@ -1,6 +1,6 @@
 #!/bin/bash
 # builds tools/motion_host_check.cpp with AddressSanitizer and UndefinedBehaviorSanitizer -- the host code under test
-# (gyro_deskew.cpp, config.cpp) compiled into the program with them -- and runs it.  No device is needed.  The libraries must be
+# (gyro_deskew.cpp, map_files.cpp, config.cpp) compiled into the program with them -- and runs it.  No device is needed.  The libraries must be
 # built (the program links the rest of the host layer from libmolahip_host.so).
 set -euo pipefail
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -8,6 +8,6 @@ H=$ROOT/mola_lidar_odometry_amd/host
 OUT=$(mktemp -d)
 trap 'rm -rf "$OUT"' EXIT
 g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -pthread -Wall -Wextra \
-    -I"$H/include" -I"$ROOT/include" "$ROOT/tools/motion_host_check.cpp" "$H/src/gyro_deskew.cpp" "$H/src/config.cpp" \
+    -I"$H/include" -I"$ROOT/include" "$ROOT/tools/motion_host_check.cpp" "$H/src/gyro_deskew.cpp" "$H/src/map_files.cpp" "$H/src/config.cpp" \
     -L"$ROOT/mola_lidar_odometry_amd" -lmolahip_host -lmolahip -Wl,-rpath,"$ROOT/mola_lidar_odometry_amd" -o "$OUT/motion_host_check"
 "$OUT/motion_host_check"
