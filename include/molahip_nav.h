@@ -51,8 +51,8 @@
  * seeds_xy included); a bad `mem`; max_cells > 255; n_table != max_cells^2 + 1; a table entry > 253; mh_nav_inflate before
  * mh_nav_set_base; passable_below outside 1 .. 254.
  *
- * NOT BUILT: a planner or a cost-to-go field; footprints other than a disc; 8-connectivity; a distance beyond 255 cells;
- * incremental use while driving (every call works on the whole window); several devices.
+ * NOT BUILT: footprints other than a disc; 8-connectivity; a distance beyond 255 cells; incremental use while driving (every call
+ * works on the whole window); several devices.  (A cost-to-go field and routes over the cost plane: include/molahip_plan.h.)
  *
  * Threads.  As every handle of the library, an mh_nav is not to be used by two calls at once; mh_nav_download and mh_nav_get_info
  * take a const handle because they leave the planes alone. */

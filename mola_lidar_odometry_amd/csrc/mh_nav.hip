@@ -5,28 +5,10 @@
 
 #include "../../include/molahip_nav.h"
 #include "mh_k_nav.h"
+#include "mh_nav_internal.h"
 
 using namespace mh;
 using namespace mh::nav;
-
-struct mh_nav {
-  mh_ctx* ctx = nullptr;
-  uint32_t nx = 0, ny = 0;
-  size_t n_cells = 0;
-  DevBuf bytes;   // base | cost | reach, n_cells bytes each (256-byte aligned sections)
-  DevBuf words;   // d2 | g, n_cells uint16 each
-  DevBuf table;   // the inflation table of the last inflate
-  DevBuf seeds;   // the seeds of the last reach
-  DevBuf ctr;     // uint32 [4]: seeds blocked, seeds placed, cells reached, the sweep's flag
-  PinnedBuf h_ctr;
-  size_t stride = 0;  // of a byte plane
-  mh_nav_info info{};
-  uint8_t* base() const { return bytes.as<uint8_t>(); }
-  uint8_t* cost() const { return bytes.as<uint8_t>() + stride; }
-  uint8_t* reach() const { return bytes.as<uint8_t>() + 2 * stride; }
-  uint16_t* d2() const { return words.as<uint16_t>(); }
-  uint16_t* g() const { return words.as<uint16_t>() + stride; }
-};
 
 namespace {
 inline uint32_t nblk(size_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }

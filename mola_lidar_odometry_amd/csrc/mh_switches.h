@@ -27,6 +27,7 @@ struct Switches {
   long keep_lds = LONG_MAX;  // (clamped to 1..kKeepLds where it is used)
   bool loop16_test_abandon = false, debug_verify_batch = false;
   bool nav_no_early_stop = false;  // mh_nav_inflate's row pass walks every dx (MH_NAV_NO_EARLY_STOP=1: for measuring what the stop saves; same bits)
+  bool plan_all_tiles = false;  // mh_plan_field runs every tile in every sweep (MH_PLAN_ALL_TILES=1: for measuring what the active-tile flags save; same bits)
 };
 
 inline Switches read_switches() {
@@ -56,6 +57,7 @@ inline Switches read_switches() {
   sw.loop16_test_abandon = on("MH_LOOP16_TEST_ABANDON");
   sw.debug_verify_batch = on("MH_DEBUG_VERIFY_BATCH");
   sw.nav_no_early_stop = on("MH_NAV_NO_EARLY_STOP");
+  sw.plan_all_tiles = on("MH_PLAN_ALL_TILES");
   return sw;
 }
 

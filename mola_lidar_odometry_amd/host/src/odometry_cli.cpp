@@ -47,6 +47,7 @@
 #include "mola_lidar_odometry_hip/OccupancyGrid.h"
 #include "mola_lidar_odometry_hip/Traversability.h"
 #include "mola_lidar_odometry_hip/NavCostmap.h"
+#include "mola_lidar_odometry_hip/RoutePlan.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "molahip.h"
 
@@ -356,6 +357,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> grid_files;   // --build-occupancy-grid KEYFRAMES OUT_PREFIX
   std::vector<std::string> trav_files;   // --build-traversability KEYFRAMES OUT_PREFIX
   std::vector<std::string> cost_files;   // --build-costmap KEYFRAMES OUT_PREFIX
+  std::vector<std::string> route_files;  // --plan-route COSTMAP_PREFIX OUT_PREFIX
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
                       "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE] [--relocalize-in-keyframes]\n"
@@ -366,6 +368,7 @@ int main(int argc, char** argv) {
                       "       molahip-lo-cli --build-occupancy-grid KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
                       "       molahip-lo-cli --build-traversability KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
                       "       molahip-lo-cli --build-costmap KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
+                      "       molahip-lo-cli --plan-route COSTMAP_PREFIX OUT_PREFIX -c FILE.yaml [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
@@ -397,6 +400,9 @@ int main(int argc, char** argv) {
                       "  with that map's own block), obstacles are inflated by the vehicle's radius with an exact distance transform, and the cells the\n"
                       "  vehicle can reach from its key-frames are flooded (the pipeline's costmap: block; -c or --pipeline, optional); written as\n"
                       "  OUT_PREFIX.pgm + OUT_PREFIX.yaml (for a map server), OUT_PREFIX_cost.pgm and OUT_PREFIX_reach.pgm\n"
+                      "  --plan-route: no sequence is run: the costmap written by --build-costmap under COSTMAP_PREFIX is read, the cost-to-go field to\n"
+                      "  the goal is computed and the route from the start traced down it (the pipeline's route: block with start_x, start_y, goal_x and\n"
+                      "  goal_y in metres; -c or --pipeline); written as OUT_PREFIX_route.txt (x y per cell) and OUT_PREFIX_route.pgm\n"
                       "  --relocalize-in-keyframes: the vehicle is found in a saved session without a prior pose: place recognition over the\n"
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
@@ -468,6 +474,10 @@ int main(int argc, char** argv) {
         cost_files.push_back(val("--build-costmap"));
         cost_files.push_back(val("--build-costmap"));
       }
+      else if (a == "--plan-route") {
+        route_files.push_back(val("--plan-route"));
+        route_files.push_back(val("--plan-route"));
+      }
       else if (a == "--relocalize-in-keyframes") opt.relocalize_in_keyframes = true;
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
@@ -477,6 +487,29 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n%s", e.what(), usage);
       return 2;
     }
+  }
+  if (!route_files.empty()) {  // a route over a costmap read back from files, no sequence
+    if (route_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty() || !clean_files.empty() ||
+        !grid_files.empty() || !trav_files.empty() || !cost_files.empty() || devices.size() > 1 || pipeline.empty()) {
+      fprintf(stderr, "--plan-route takes one costmap prefix to read and one output prefix, once, with a pipeline file, and takes no sequence and one device\n%s", usage);
+      return 2;
+    }
+    try {
+      const mola_hip::RouteOptions ropt = mola_hip::RouteOptions::FromConfig(mp2p_icp_hip::Config::FromYamlFile(pipeline));
+      (void)mola_hip::route_price_table(ropt);  // (a bad block is refused before the files are read)
+      const mola_hip::NavCostmap c = mola_hip::read_costmap(route_files[0]);  // (missing files are refused before a device is asked for)
+      auto ctx = std::make_shared<mp2p_icp_hip::DeviceContext>(devices.empty() ? 0 : devices[0]);
+      const mola_hip::RoutePlan r = mola_hip::plan_route(c, ropt, ctx);
+      mola_hip::write_route(r, c, route_files[1]);
+      printf("{\"costmap\": \"%s\", \"route\": \"%s\", \"status\": \"%s\", \"cells\": %llu, \"length_m\": %.6f, \"cost_to_go\": %u, \"max_cost\": %u, "
+             "\"min_clearance_m\": %.6f, \"sweeps\": %u, \"tile_runs\": %llu, \"cells_with_field\": %llu, \"seconds_field\": %.6f, \"seconds_trace\": %.6f}\n",
+             route_files[0].c_str(), route_files[1].c_str(), r.status.c_str(), (unsigned long long)(r.cells.size() / 2), r.length_m, r.cost_to_go, r.max_cost,
+             r.min_clearance_m, r.sweeps, (unsigned long long)r.tile_runs, (unsigned long long)r.cells_with_field, r.seconds_field, r.seconds_trace);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "molahip-lo-cli: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (!cost_files.empty()) {  // an inflated costmap with the reachable region from a recorded drive's key-frames, no sequence
     if (cost_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty() || !clean_files.empty() ||

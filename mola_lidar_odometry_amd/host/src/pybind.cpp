@@ -12,6 +12,7 @@
 #include "mola_lidar_odometry_hip/OccupancyGrid.h"
 #include "mola_lidar_odometry_hip/Traversability.h"
 #include "mola_lidar_odometry_hip/NavCostmap.h"
+#include "mola_lidar_odometry_hip/RoutePlan.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
 #include "molahip_host/plugin_switches.h"
@@ -1594,6 +1595,91 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
   m.def("write_costmap", [dict2nav](const py::dict& d, const std::string& prefix) { mola_hip::write_costmap(dict2nav(d), prefix); }, py::arg("map"),
         py::arg("prefix"));
   m.def("read_costmap", [nav2dict](const std::string& prefix) { return nav2dict(mola_hip::read_costmap(prefix)); }, py::arg("prefix"));
+  // ---- a route over a costmap (mola_lidar_odometry_hip/RoutePlan.h)
+  using mola_hip::RouteOptions;
+  using mola_hip::RoutePlan;
+  auto route2dict = [](const RoutePlan& r, uint32_t nx, uint32_t ny) {
+    py::dict d;
+    d["status"] = r.status;
+    d["start_cell"] = py::make_tuple(r.start_col, r.start_row); d["goal_cell"] = py::make_tuple(r.goal_col, r.goal_row);
+    py::array_t<int32_t> cells({(py::ssize_t)(r.cells.size() / 2), (py::ssize_t)2});
+    std::copy(r.cells.begin(), r.cells.end(), cells.mutable_data());
+    py::array_t<double> xy({(py::ssize_t)(r.xy.size() / 2), (py::ssize_t)2});
+    std::copy(r.xy.begin(), r.xy.end(), xy.mutable_data());
+    d["cells"] = cells; d["xy"] = xy;
+    d["length_m"] = r.length_m; d["cost_to_go"] = r.cost_to_go; d["max_cost"] = r.max_cost; d["min_clearance_m"] = r.min_clearance_m;
+    if (r.field.empty()) d["field"] = py::none();
+    else {
+      py::array_t<uint32_t> f({(py::ssize_t)ny, (py::ssize_t)nx});
+      std::copy(r.field.begin(), r.field.end(), f.mutable_data());
+      d["field"] = f;
+    }
+    d["sweeps"] = r.sweeps; d["tile_runs"] = r.tile_runs; d["cells_with_field"] = r.cells_with_field;
+    d["seconds_field"] = r.seconds_field; d["seconds_trace"] = r.seconds_trace;
+    return d;
+  };
+  auto dict2route = [](const py::dict& d) {
+    RoutePlan r;
+    auto cells = d["cells"].cast<py::array_t<int32_t, py::array::c_style | py::array::forcecast>>();
+    r.cells.assign(cells.data(), cells.data() + cells.size());
+    if (d.contains("xy")) {
+      auto xy = d["xy"].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+      r.xy.assign(xy.data(), xy.data() + xy.size());
+    }
+    return r;
+  };
+  m.def("route_options", [nav_cfg](const py::object& options) {
+    const RouteOptions o = RouteOptions::FromConfig(nav_cfg(options));
+    py::dict d;
+    d["start_x"] = o.start_x; d["start_y"] = o.start_y; d["goal_x"] = o.goal_x; d["goal_y"] = o.goal_y;
+    d["start_keyframe"] = o.start_keyframe; d["goal_keyframe"] = o.goal_keyframe; d["neutral_price"] = o.neutral_price;
+    d["cost_factor"] = o.cost_factor; d["max_route_cells"] = o.max_route_cells;
+    return d; }, py::arg("options") = py::none());
+  // rule 1 -> uint16 [253]; with n_cells > 0 the wrap-around bound for a window of that many cells is checked as well
+  m.def("route_price_table", [nav_cfg](const py::object& options, uint64_t n_cells) {
+    const std::vector<uint16_t> t = mola_hip::route_price_table(RouteOptions::FromConfig(nav_cfg(options)));
+    if (n_cells) mola_hip::route_check_window(t, n_cells);
+    py::array_t<uint16_t> a((py::ssize_t)t.size());
+    std::copy(t.begin(), t.end(), a.mutable_data());
+    return a; }, py::arg("options") = py::none(), py::arg("n_cells") = 0);
+  // rule 2 -> (column, row), (-1, -1) for a point without a cell in the window of `map`
+  m.def("route_cell", [dict2nav](const py::dict& map, double x, double y) {
+    int32_t col, row;
+    (void)mola_hip::route_cell(dict2nav(map), x, y, col, row);
+    return py::make_tuple(col, row); }, py::arg("map"), py::arg("x"), py::arg("y"));
+  // rule 3 on given cells (int32 [n, 2]) -> the route dict
+  m.def("route_summarise", [dict2nav, dict2route, route2dict](const py::dict& route, const py::dict& map) {
+    const NavCostmap c = dict2nav(map);
+    RoutePlan r = dict2route(route);
+    mola_hip::route_summarise(r, c);
+    return route2dict(r, c.nx, c.ny); }, py::arg("route"), py::arg("map"));
+  m.def("plan_route", [dict2nav, nav_cfg, route2dict](const py::dict& map, const py::object& options) {
+    const NavCostmap c = dict2nav(map);
+    const RouteOptions o = RouteOptions::FromConfig(nav_cfg(options));
+    RoutePlan r;
+    {
+      py::gil_scoped_release nogil;
+      r = mola_hip::plan_route(c, o);
+    }
+    return route2dict(r, c.nx, c.ny); }, py::arg("map"), py::arg("options") = py::none());
+  // a key-frame set (a dict, or the path of a key-frame file) -> the route dict, with the costmap it was planned on under "costmap"
+  m.def("plan_route_from_keyframes", [dict2kfset, nav_cfg, nav2dict, route2dict](const py::object& frames, const py::object& options) {
+    const molahip_host::KeyFrameSet set = py::isinstance<py::str>(frames) ? molahip_host::read_keyframe_file(frames.cast<std::string>())
+                                                                         : dict2kfset(frames.cast<py::dict>());
+    const Config cfg = nav_cfg(options);
+    mola_hip::RouteFromKeyframes out;
+    {
+      py::gil_scoped_release nogil;
+      out = mola_hip::plan_route_from_keyframes(set, cfg);
+    }
+    py::dict d = route2dict(out.route, out.costmap.nx, out.costmap.ny);
+    d["costmap"] = nav2dict(out.costmap);
+    return d; }, py::arg("frames"), py::arg("options") = py::none());
+  m.def("write_route", [dict2nav, dict2route](const py::dict& route, const py::dict& map, const std::string& prefix) {
+    const NavCostmap c = dict2nav(map);
+    RoutePlan r = dict2route(route);
+    if (r.xy.empty()) mola_hip::route_summarise(r, c);
+    mola_hip::write_route(r, c, prefix); }, py::arg("route"), py::arg("map"), py::arg("prefix"));
   // the pose rules of the driver's online loop closure and the motion model's rebase, on 12-value poses
   auto to_pose = [](const std::vector<double>& T) {
     if (T.size() != 12) throw std::runtime_error("a pose has 12 values");
