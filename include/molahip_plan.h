@@ -70,8 +70,8 @@
  *   passable_below; a price of 0; the wrap-around bound; mh_plan_field before a cost was set; mh_plan_trace or mh_plan_download before
  *   mh_plan_field; cap == 0.
  *
- * NOT BUILT: any-angle or kinematic routes; footprints other than a disc; replanning while driving (every call works on the whole
- * window); several devices.
+ * NOT BUILT: any-angle or kinematic routes; footprints other than a disc; several devices.  (Replanning while driving: every call here
+ * works on the whole window; include/molahip_replan.h repairs the field after the cost of a rectangle of cells changed.)
  *
  * Threads.  As every handle of the library, an mh_plan is not to be used by two calls at once; mh_plan_trace, mh_plan_download and
  * mh_plan_get_info take a const handle where they leave the planes alone. */

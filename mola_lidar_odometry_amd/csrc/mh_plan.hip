@@ -7,36 +7,82 @@
 #include "../../include/molahip_plan.h"
 #include "mh_k_plan.h"
 #include "mh_nav_internal.h"
+#include "mh_plan_internal.h"
 
 using namespace mh;
 using namespace mh::nav;
 using namespace mh::plan;
 
-struct mh_plan {
-  mh_ctx* ctx = nullptr;
-  uint32_t nx = 0, ny = 0;
-  size_t n_cells = 0;
-  uint32_t lw = 0, n_tiles = 0;  // the relax tiles: 2^lw cells wide
-  DevBuf cost;     // n_cells bytes
-  DevBuf field;    // n_cells uint32
-  DevBuf price;    // uint16 [256] of the last field: 0 = impassable
-  DevBuf goals;    // the goals of the last field
-  DevBuf changed;  // two byte planes of n_tiles flags (256-byte aligned sections)
-  DevBuf ctr;      // uint32 [8]: goals blocked, goals placed, cells reached, max field, the sweep's flag, the sweep's tile runs
-  PinnedBuf h_ctr;  // ... their mirror, and the price table on its way up behind them
-  mutable DevBuf t_starts, t_out, t_len;  // mh_plan_trace's scratch
-  size_t tile_stride = 0;
-  mh_plan_info info{};
-};
+namespace mh {
+namespace plan {
 
-namespace {
-inline uint32_t nblk(size_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
-inline void forget_field(mh_plan* p) {
-  p->info.has_field = 0u;
-  p->info.n_reached = p->info.n_goals_blocked = p->info.n_goals_outside = p->info.n_tile_runs = 0;
-  p->info.n_sweeps = p->info.max_field = p->info.passable_below = 0u;
+mh_status relax_to_rest(mh_plan* p, bool all_tiles, uint8_t* first, uint32_t* sweeps, uint64_t* tile_runs) {
+  // Values only fall and are bounded below, so a sweep that changes nothing comes; every sweep is a launch of its own and the
+  // host reads its flag: no workgroup ever waits for another.  `prev` holds the tiles that changed in the sweep before.
+  hipStream_t s = p->ctx->stream;
+  uint32_t* d_ctr = p->ctr.as<uint32_t>();
+  uint32_t* h_ctr = p->h_ctr.as<uint32_t>();
+  uint8_t* prev = first;
+  uint8_t* now = first == p->plane(0) ? p->plane(1) : p->plane(0);
+  uint64_t mine = 0;
+  for (;;) {
+    MH_HIP(hipMemsetAsync(d_ctr + 4, 0, 2 * sizeof(uint32_t), s));
+    MH_HIP(hipMemsetAsync(now, 0, p->n_tiles, s));
+    hipLaunchKernelGGL(k_plan_relax, dim3(p->n_tiles), dim3(256), 0, s, p->cost.as<uint8_t>(), p->price.as<uint16_t>(), p->nx, p->ny, p->lw,
+                       all_tiles ? 1u : 0u, prev, now, p->field.as<uint32_t>(), d_ctr + 4);
+    MH_HIP(hipGetLastError());
+    MH_HIP(hipMemcpyAsync(h_ctr + 4, d_ctr + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    MH_HIP(mh::wait_stream(s));
+    (*sweeps)++;
+    mine++;
+    *tile_runs += h_ctr[5];
+    prev = now;
+    now = now == p->plane(0) ? p->plane(1) : p->plane(0);
+    if (!h_ctr[4]) break;
+    // (Bellman-Ford: after k sweeps every cell whose cheapest route has k steps is final, so more changing sweeps than cells
+    // cannot be)
+    if (mine > (uint64_t)p->n_cells) return fail(MH_ERR_INTERNAL, "mh_plan_field: the sweeps do not come to rest");
+  }
+  return MH_OK;
 }
-}  // namespace
+
+mh_status field_from_goals(mh_plan* p, const Switches& sw, uint32_t passable_below) {
+  hipStream_t s = p->ctx->stream;
+  uint32_t* d_ctr = p->ctr.as<uint32_t>();
+  uint32_t* h_ctr = p->h_ctr.as<uint32_t>();
+  for (uint32_t k = 0; k < 8u; k++) h_ctr[k] = 0u;
+  MH_HIP(hipMemsetAsync(p->field.p, 0xFF, p->n_cells * sizeof(uint32_t), s));
+  MH_HIP(hipMemsetAsync(d_ctr, 0, 8 * sizeof(uint32_t), s));
+  MH_HIP(hipMemsetAsync(p->changed.p, 0, 2 * p->tile_stride, s));
+  uint32_t sweeps = 0;
+  uint64_t tile_runs = 0;
+  if (p->n_goals > p->info.n_goals_outside) {
+    hipLaunchKernelGGL(k_plan_goals, dim3(nblk(p->n_goals, 256)), dim3(256), 0, s, p->goals.as<int>(), (uint32_t)p->n_goals, p->nx, p->ny,
+                       p->cost.as<uint8_t>(), passable_below, p->lw, p->field.as<uint32_t>(), p->plane(0), d_ctr);
+    MH_HIP(hipGetLastError());
+    MH_HIP(hipMemcpyAsync(h_ctr, d_ctr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    MH_HIP(mh::wait_stream(s));
+    if (h_ctr[1]) {
+      MH_TRY(relax_to_rest(p, sw.plan_all_tiles, p->plane(0), &sweeps, &tile_runs));
+      hipLaunchKernelGGL(k_plan_stats, dim3(std::min<uint32_t>(nblk(p->n_cells, 256), 4096u)), dim3(256), 0, s, p->field.as<uint32_t>(),
+                         p->n_cells, d_ctr + 2);
+      MH_HIP(hipGetLastError());
+      MH_HIP(hipMemcpyAsync(h_ctr + 2, d_ctr + 2, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+  }
+  MH_HIP(mh::wait_stream(s));
+  p->info.n_goals_blocked = h_ctr[0];
+  p->info.n_reached = h_ctr[2];
+  p->info.max_field = h_ctr[3];
+  p->info.n_sweeps = sweeps;
+  p->info.n_tile_runs = tile_runs;
+  p->info.passable_below = passable_below;
+  p->info.has_field = 1u;
+  return MH_OK;
+}
+
+}  // namespace plan
+}  // namespace mh
 
 extern "C" {
 
@@ -61,9 +107,9 @@ mh_status mh_plan_create(mh_ctx* ctx, uint32_t nx, uint32_t ny, mh_plan** out) {
   mh_status st = p->cost.reserve(p->n_cells);
   if (st == MH_OK) st = p->field.reserve(p->n_cells * sizeof(uint32_t));
   if (st == MH_OK) st = p->price.reserve(256 * sizeof(uint16_t));
-  if (st == MH_OK) st = p->changed.reserve(2 * p->tile_stride);
-  if (st == MH_OK) st = p->ctr.reserve(8 * sizeof(uint32_t));
-  if (st == MH_OK) st = p->h_ctr.reserve(8 * sizeof(uint32_t) + 256 * sizeof(uint16_t));
+  if (st == MH_OK) st = p->changed.reserve(3 * p->tile_stride);
+  if (st == MH_OK) st = p->ctr.reserve(kCtrs * sizeof(uint32_t));
+  if (st == MH_OK) st = p->h_ctr.reserve(kCtrs * sizeof(uint32_t) + 256 * sizeof(uint16_t));
   if (st != MH_OK) {
     (void)mh_plan_destroy(p);
     return st;
@@ -80,6 +126,7 @@ mh_status mh_plan_destroy(mh_plan* p) {
   p->field.release();
   p->price.release();
   p->goals.release();
+  p->patch.release();
   p->changed.release();
   p->ctr.release();
   p->h_ctr.release();
@@ -142,62 +189,20 @@ mh_status mh_plan_field(mh_plan* p, const int32_t* goals_xy, size_t n_goals, uin
     const int32_t x = goals_xy[2 * k], y = goals_xy[2 * k + 1];
     if (x < 0 || y < 0 || (uint32_t)x >= nx || (uint32_t)y >= ny) outside++;
   }
-  uint32_t* d_ctr = p->ctr.as<uint32_t>();
-  uint32_t* h_ctr = p->h_ctr.as<uint32_t>();
-  uint16_t* h_price = reinterpret_cast<uint16_t*>(h_ctr + 8);  // (behind the counters in the pinned block)
+  uint16_t* h_price = reinterpret_cast<uint16_t*>(p->h_ctr.as<uint32_t>() + kCtrs);  // (behind the counters in the pinned block)
   for (uint32_t k = 0; k < 256u; k++) h_price[k] = k < passable_below ? price[k] : (uint16_t)0;
-  for (uint32_t k = 0; k < 8u; k++) h_ctr[k] = 0u;
   MH_HIP(hipMemcpyAsync(p->price.p, h_price, 256 * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-  MH_HIP(hipMemsetAsync(p->field.p, 0xFF, p->n_cells * sizeof(uint32_t), s));
-  MH_HIP(hipMemsetAsync(d_ctr, 0, 8 * sizeof(uint32_t), s));
-  MH_HIP(hipMemsetAsync(p->changed.p, 0, 2 * p->tile_stride, s));
-  uint32_t sweeps = 0;
-  uint64_t tile_runs = 0;
+  p->n_goals = 0;
   if (n_goals > outside) {
-    uint8_t* plane[2] = {p->changed.as<uint8_t>(), p->changed.as<uint8_t>() + p->tile_stride};
     MH_TRY(p->goals.reserve(n_goals * 2 * sizeof(int32_t)));
     MH_HIP(hipMemcpyAsync(p->goals.p, goals_xy, n_goals * 2 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_plan_goals, dim3(nblk(n_goals, 256)), dim3(256), 0, s, p->goals.as<int>(), (uint32_t)n_goals, nx, ny,
-                       p->cost.as<uint8_t>(), passable_below, lw, p->field.as<uint32_t>(), plane[0], d_ctr);
-    MH_HIP(hipGetLastError());
-    MH_HIP(hipMemcpyAsync(h_ctr, d_ctr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     MH_HIP(mh::wait_stream(s));  // (the caller's goals are free again behind this)
-    if (h_ctr[1]) {
-      // Values only fall and are bounded below, so a sweep that changes nothing comes; every sweep is a launch of its own and the
-      // host reads its flag: no workgroup ever waits for another.  plane[prev] holds the tiles that changed in the sweep before.
-      uint32_t prev = 0;
-      for (;;) {
-        MH_HIP(hipMemsetAsync(d_ctr + 4, 0, 2 * sizeof(uint32_t), s));
-        MH_HIP(hipMemsetAsync(plane[prev ^ 1u], 0, p->n_tiles, s));
-        hipLaunchKernelGGL(k_plan_relax, dim3(p->n_tiles), dim3(256), 0, s, p->cost.as<uint8_t>(), p->price.as<uint16_t>(), nx, ny, lw,
-                           sw.plan_all_tiles ? 1u : 0u, plane[prev], plane[prev ^ 1u], p->field.as<uint32_t>(), d_ctr + 4);
-        MH_HIP(hipGetLastError());
-        MH_HIP(hipMemcpyAsync(h_ctr + 4, d_ctr + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        MH_HIP(mh::wait_stream(s));
-        sweeps++;
-        tile_runs += h_ctr[5];
-        prev ^= 1u;
-        if (!h_ctr[4]) break;
-        // (Bellman-Ford: after k sweeps every cell whose cheapest route has k steps is final, so more changing sweeps than cells
-        // cannot be)
-        if ((uint64_t)sweeps > (uint64_t)p->n_cells) return fail(MH_ERR_INTERNAL, "mh_plan_field: the sweeps do not come to rest");
-      }
-      hipLaunchKernelGGL(k_plan_stats, dim3(std::min<uint32_t>(nblk(p->n_cells, 256), 4096u)), dim3(256), 0, s, p->field.as<uint32_t>(),
-                         p->n_cells, d_ctr + 2);
-      MH_HIP(hipGetLastError());
-      MH_HIP(hipMemcpyAsync(h_ctr + 2, d_ctr + 2, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    }
+    p->n_goals = n_goals;
   }
-  MH_HIP(mh::wait_stream(s));
   p->info.n_goals_outside = outside;
-  p->info.n_goals_blocked = h_ctr[0];
-  p->info.n_reached = h_ctr[2];
-  p->info.max_field = h_ctr[3];
-  p->info.n_sweeps = sweeps;
-  p->info.n_tile_runs = tile_runs;
-  p->info.passable_below = passable_below;
-  p->info.has_field = 1u;
-  return MH_OK;
+  const mh_status st = field_from_goals(p, sw, passable_below);
+  if (st != MH_OK) forget_field(p);
+  return st;
 }
 
 mh_status mh_plan_trace(const mh_plan* p, const int32_t* starts_xy, size_t n_starts, uint32_t cap, int32_t* out_xy, uint32_t* out_len) {

@@ -28,6 +28,7 @@ struct Switches {
   bool loop16_test_abandon = false, debug_verify_batch = false;
   bool nav_no_early_stop = false;  // mh_nav_inflate's row pass walks every dx (MH_NAV_NO_EARLY_STOP=1: for measuring what the stop saves; same bits)
   bool plan_all_tiles = false;  // mh_plan_field runs every tile in every sweep (MH_PLAN_ALL_TILES=1: for measuring what the active-tile flags save; same bits)
+  bool replan_full = false;  // an update of molahip_replan.h patches the bytes and computes the whole field from nothing (MH_REPLAN_FULL=1: for measuring what the repair saves, and as a twin in tests; same bits)
 };
 
 inline Switches read_switches() {
@@ -58,6 +59,7 @@ inline Switches read_switches() {
   sw.debug_verify_batch = on("MH_DEBUG_VERIFY_BATCH");
   sw.nav_no_early_stop = on("MH_NAV_NO_EARLY_STOP");
   sw.plan_all_tiles = on("MH_PLAN_ALL_TILES");
+  sw.replan_full = on("MH_REPLAN_FULL");
   return sw;
 }
 

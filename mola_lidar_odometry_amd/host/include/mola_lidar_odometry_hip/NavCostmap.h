@@ -30,8 +30,9 @@
 //        cost_image: <name>_cost.pgm\nreach_image: <name>_reach.pgm\ninscribed_radius: A\ninflation_radius: B\n   (numbers as %.9g)
 //      read_costmap gives back the window, the resolution, cost, reach, the two radii and the counts that need no d2.
 //
-// NOT BUILT: footprints other than a disc; 8-connectivity; a distance beyond 255 cells; incremental use while driving; a costmap
-// under --devices (one device per call).  (Routes over the costmap: RoutePlan.h.)
+// NOT BUILT: footprints other than a disc; 8-connectivity; a distance beyond 255 cells; an incremental inflation (Replan.h inflates
+// the whole window again after a change of the base and repairs only the route field); a costmap under --devices (one device per
+// call).  (Routes over the costmap: RoutePlan.h; routes while the base changes: Replan.h.)
 #pragma once
 #include <array>
 #include <memory>

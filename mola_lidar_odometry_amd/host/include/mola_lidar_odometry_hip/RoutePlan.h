@@ -27,8 +27,8 @@
 //      (occupied 0 where cost is 253 or 254, unknown 205 where 255, free 254 otherwise) with every route cell drawn as 100; row 0 at
 //      the top is the largest y.
 //
-// NOT BUILT: any-angle or kinematic routes; footprints other than a disc; replanning while driving; a route under --devices (one
-// device per call).
+// NOT BUILT: any-angle or kinematic routes; footprints other than a disc; a route under --devices (one device per call).  (Replanning
+// while the costmap changes: Replan.h.)
 #pragma once
 #include <limits>
 #include <memory>
@@ -77,8 +77,8 @@ void route_check_window(const std::vector<uint16_t>& price, uint64_t n_cells);
 bool route_cell(const NavCostmap& c, double x, double y, int32_t& col, int32_t& row);
 // rule 3: xy, length_m, max_cost and min_clearance_m from r.cells
 void route_summarise(RoutePlan& r, const NavCostmap& c);
-// rule 4
-void write_route(const RoutePlan& r, const NavCostmap& c, const std::string& prefix);
+// rule 4; `stem` stands for "_route" in the two file names (Replan.h writes prefix_route_K.txt / .pgm with it)
+void write_route(const RoutePlan& r, const NavCostmap& c, const std::string& prefix, const std::string& stem = "_route");
 
 // ---- the whole thing.  plan_route needs the four metre keys.
 RoutePlan plan_route(const NavCostmap& c, const RouteOptions& opt, std::shared_ptr<DeviceContext> ctx = nullptr);

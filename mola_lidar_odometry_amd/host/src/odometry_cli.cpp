@@ -47,6 +47,7 @@
 #include "mola_lidar_odometry_hip/OccupancyGrid.h"
 #include "mola_lidar_odometry_hip/Traversability.h"
 #include "mola_lidar_odometry_hip/NavCostmap.h"
+#include "mola_lidar_odometry_hip/Replan.h"
 #include "mola_lidar_odometry_hip/RoutePlan.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "molahip.h"
@@ -358,6 +359,7 @@ int main(int argc, char** argv) {
   std::vector<std::string> trav_files;   // --build-traversability KEYFRAMES OUT_PREFIX
   std::vector<std::string> cost_files;   // --build-costmap KEYFRAMES OUT_PREFIX
   std::vector<std::string> route_files;  // --plan-route COSTMAP_PREFIX OUT_PREFIX
+  std::vector<std::string> replan_files;  // --replan-route KEYFRAMES EVENTS OUT_PREFIX
   const char* usage = "usage: molahip-lo-cli --pipeline FILE.yaml --seq-dir DIR [--seq-dir DIR ...] --out FILE.tum [--device N | --devices 0,1,..|all] "
                       "[--no-prefetch] [--max-scans N] [--profile] [--time-field BYTES] [--intensity-field BYTES] [--scan-log FILE|auto] [--plan-only]\n"
                       "                      [--save-local-map FILE] [--output-simplemap FILE] [--output-session-map FILE] [--relocalize-in-keyframes]\n"
@@ -369,6 +371,7 @@ int main(int argc, char** argv) {
                       "       molahip-lo-cli --build-traversability KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
                       "       molahip-lo-cli --build-costmap KEYFRAMES OUT_PREFIX [-c FILE.yaml] [--device N]\n"
                       "       molahip-lo-cli --plan-route COSTMAP_PREFIX OUT_PREFIX -c FILE.yaml [--device N]\n"
+                      "       molahip-lo-cli --replan-route KEYFRAMES EVENTS OUT_PREFIX [-c FILE.yaml] [--device N]\n"
                       "  several --seq-dir: the sequences run together, one host thread each, the alignments of the sequences that share\n"
                       "  a GPU merged into lock-step batches; trajectories go to FILE_<k>.tum\n"
                       "  --save-local-map: the local maps at the end of the run (FILE_<k> for several sequences); a later run loads one through\n"
@@ -403,6 +406,11 @@ int main(int argc, char** argv) {
                       "  --plan-route: no sequence is run: the costmap written by --build-costmap under COSTMAP_PREFIX is read, the cost-to-go field to\n"
                       "  the goal is computed and the route from the start traced down it (the pipeline's route: block with start_x, start_y, goal_x and\n"
                       "  goal_y in metres; -c or --pipeline); written as OUT_PREFIX_route.txt (x y per cell) and OUT_PREFIX_route.pgm\n"
+                      "  --replan-route: no sequence is run: the costmap of KEYFRAMES is built as by --build-costmap and the cost-to-go field to the goal\n"
+                      "  (the route: block's goal_x and goal_y, or goal_keyframe) is computed once; then the lines of the text file EVENTS are run in\n"
+                      "  order: 'block X0 Y0 X1 Y1' makes a rectangle [m] of the base map lethal, 'clear X0 Y0 X1 Y1' makes it free -- the costmap is\n"
+                      "  inflated again and the field is repaired round the change, not recomputed -- and 'at X Y' traces the route from that point,\n"
+                      "  written as OUT_PREFIX_route_K.txt and OUT_PREFIX_route_K.pgm for the K-th 'at' line (from 0); one summary line per event\n"
                       "  --relocalize-in-keyframes: the vehicle is found in a saved session without a prior pose: place recognition over the\n"
                       "  key-frames of MOLA_LOAD_SM, then a pose search in the map of MOLA_LOAD_MM (run with MOLA_MAPPING_ENABLED=false);\n"
                       "  one sequence per device only\n"
@@ -478,6 +486,9 @@ int main(int argc, char** argv) {
         route_files.push_back(val("--plan-route"));
         route_files.push_back(val("--plan-route"));
       }
+      else if (a == "--replan-route") {
+        for (int k = 0; k < 3; k++) replan_files.push_back(val("--replan-route"));
+      }
       else if (a == "--relocalize-in-keyframes") opt.relocalize_in_keyframes = true;
       else if (a == "--no-prefetch") opt.prefetch = false;
       else if (a == "--profile") print_profile = true;
@@ -487,6 +498,30 @@ int main(int argc, char** argv) {
       fprintf(stderr, "%s\n%s", e.what(), usage);
       return 2;
     }
+  }
+  if (!replan_files.empty()) {  // routes that follow a costmap whose base changes, from a recorded drive's key-frames, no sequence
+    if (replan_files.size() != 3 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty() || !clean_files.empty() ||
+        !grid_files.empty() || !trav_files.empty() || !cost_files.empty() || !route_files.empty() || devices.size() > 1) {
+      fprintf(stderr, "--replan-route takes one key-frame file, one events file and one output prefix, once, and takes no sequence and one device\n%s", usage);
+      return 2;
+    }
+    try {
+      const mp2p_icp_hip::Config cfg = pipeline.empty() ? mp2p_icp_hip::Config::FromYamlText("") : mp2p_icp_hip::Config::FromYamlFile(pipeline);
+      (void)mola_hip::route_price_table(mola_hip::RouteOptions::FromConfig(cfg));  // (bad blocks and a bad events file are refused before the
+      (void)mola_hip::NavCostmapOptions::FromConfig(cfg);                          // key-frames are read and a device is asked for)
+      const std::vector<mola_hip::ReplanEvent> events = mola_hip::read_replan_events(replan_files[1]);
+      const molahip_host::KeyFrameSet set = molahip_host::read_keyframe_file(replan_files[0]);
+      auto ctx = std::make_shared<mp2p_icp_hip::DeviceContext>(devices.empty() ? 0 : devices[0]);
+      const mola_hip::ReplanRun run = mola_hip::replan_route_from_keyframes(set, cfg, events, ctx);
+      mola_hip::write_replan_routes(run, replan_files[2]);
+      for (size_t k = 0; k < run.events.size(); k++) printf("%s\n", mola_hip::replan_event_summary(run, k).c_str());
+      printf("{\"keyframe_file\": \"%s\", \"events_file\": \"%s\", \"prefix\": \"%s\", \"events\": %zu, \"routes\": %zu, \"rects_outside\": %llu}\n",
+             replan_files[0].c_str(), replan_files[1].c_str(), replan_files[2].c_str(), run.events.size(), run.routes.size(), (unsigned long long)run.rects_outside);
+    } catch (const std::exception& e) {
+      fprintf(stderr, "molahip-lo-cli: %s\n", e.what());
+      return 1;
+    }
+    return 0;
   }
   if (!route_files.empty()) {  // a route over a costmap read back from files, no sequence
     if (route_files.size() != 2 || !seq_dirs.empty() || !build_from.empty() || !close_from.empty() || !join_files.empty() || !clean_files.empty() ||

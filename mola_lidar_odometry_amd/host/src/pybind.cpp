@@ -12,6 +12,7 @@
 #include "mola_lidar_odometry_hip/OccupancyGrid.h"
 #include "mola_lidar_odometry_hip/Traversability.h"
 #include "mola_lidar_odometry_hip/NavCostmap.h"
+#include "mola_lidar_odometry_hip/Replan.h"
 #include "mola_lidar_odometry_hip/RoutePlan.h"
 #include "mola_lidar_odometry_hip/SessionJoin.h"
 #include "mp2p_icp_hip/mp2p_icp_hip.h"
@@ -1680,6 +1681,104 @@ PYBIND11_MODULE(_mp2p_icp_hip, m) {
     RoutePlan r = dict2route(route);
     if (r.xy.empty()) mola_hip::route_summarise(r, c);
     mola_hip::write_route(r, c, prefix); }, py::arg("route"), py::arg("map"), py::arg("prefix"));
+  // ---- routes that follow a changing costmap (mola_lidar_odometry_hip/Replan.h)
+  using mola_hip::CellRect;
+  using mola_hip::ReplanEvent;
+  auto rect2py = [](const CellRect& r) -> py::object {
+    if (r.empty) return py::none();
+    return py::make_tuple(r.col0, r.row0, r.w, r.h);
+  };
+  auto update2dict = [rect2py](const mola_hip::ReplanUpdate& u) {
+    py::dict d;
+    d["rect"] = rect2py(u.rect); d["grown"] = rect2py(u.grown);
+    d["cells_changed"] = u.info.n_cells_changed; d["cells_repriced"] = u.info.n_cells_repriced; d["withdrawn"] = u.info.n_withdrawn;
+    d["withdraw_sweeps"] = u.info.n_withdraw_sweeps; d["relax_sweeps"] = u.info.n_relax_sweeps;
+    d["tile_runs_withdraw"] = u.info.n_tile_runs_withdraw; d["tile_runs_relax"] = u.info.n_tile_runs_relax; d["updates"] = u.info.n_updates;
+    d["seconds_inflate"] = u.seconds_inflate; d["seconds_update"] = u.seconds_update;
+    return d;
+  };
+  // rule 8 -> a list of dicts (verb, numbers, line)
+  m.def("replan_parse_events", [](const std::string& text) {
+    py::list out;
+    for (const ReplanEvent& e : mola_hip::parse_replan_events(text)) {
+      py::dict d;
+      d["verb"] = std::string(e.verbName());
+      d["numbers"] = std::vector<double>(e.v, e.v + (e.verb == ReplanEvent::kAt ? 2 : 4));
+      d["line"] = e.line;
+      out.append(d);
+    }
+    return out; }, py::arg("text"));
+  // rule 9 on a window dict (x0, y0, nx, ny, resolution) -> (col0, row0, w, h) or None
+  m.def("replan_metre_rect", [rect2py](const py::dict& win, double xa, double ya, double xb, double yb) {
+    NavCostmap c;
+    c.x0 = win["x0"].cast<int32_t>(); c.y0 = win["y0"].cast<int32_t>(); c.nx = win["nx"].cast<uint32_t>(); c.ny = win["ny"].cast<uint32_t>();
+    c.resolution = win["resolution"].cast<double>();
+    return rect2py(mola_hip::replan_metre_rect(c, xa, ya, xb, yb)); }, py::arg("window"), py::arg("xa"), py::arg("ya"), py::arg("xb"), py::arg("yb"));
+  // rule 5 -> (col0, row0, w, h)
+  m.def("replan_grown_rect", [rect2py](uint32_t col0, uint32_t row0, uint32_t w, uint32_t h, uint32_t max_cells, uint32_t nx, uint32_t ny) {
+    CellRect r;
+    r.empty = false;
+    r.col0 = col0; r.row0 = row0; r.w = w; r.h = h;
+    return rect2py(mola_hip::replan_grown_rect(r, max_cells, nx, ny)); });
+  // a planner that lives across updates: RoutePlanner(map, poses, options) with the source map dict of build_costmap and a pipeline
+  // text with costmap: and route: blocks (goal_x / goal_y needed)
+  py::class_<mola_hip::RoutePlanner>(m, "RoutePlanner")
+      .def(py::init([dict2base, nav_cfg, to_poses](const py::dict& map, const std::vector<std::vector<double>>& poses, const py::object& options) {
+             const Config cfg = nav_cfg(options);
+             return std::make_unique<mola_hip::RoutePlanner>(dict2base(map), to_poses(poses), NavCostmapOptions::FromConfig(cfg), RouteOptions::FromConfig(cfg));
+           }),
+           py::arg("map"), py::arg("poses"), py::arg("options") = py::none())
+      .def("update", [update2dict](mola_hip::RoutePlanner& p, uint32_t col0, uint32_t row0, const py::array_t<uint8_t, py::array::c_style | py::array::forcecast>& bytes) {
+             if (bytes.ndim() != 2) throw std::runtime_error("RoutePlanner.update: bytes is uint8 [h, w]");
+             mola_hip::ReplanUpdate u;
+             const uint32_t h = (uint32_t)bytes.shape(0), w = (uint32_t)bytes.shape(1);
+             const uint8_t* data = bytes.data();
+             {
+               py::gil_scoped_release nogil;
+               u = p.update(col0, row0, w, h, data);
+             }
+             return update2dict(u); }, py::arg("col0"), py::arg("row0"), py::arg("bytes"))
+      .def("route_from", [route2dict](mola_hip::RoutePlanner& p, double x, double y) {
+             RoutePlan r;
+             {
+               py::gil_scoped_release nogil;
+               r = p.routeFrom(x, y);
+             }
+             return route2dict(r, p.base().nx, p.base().ny); }, py::arg("x"), py::arg("y"))
+      .def("costmap", [nav2dict](mola_hip::RoutePlanner& p) { return nav2dict(p.costmap()); })
+      .def("base", [plane2array](mola_hip::RoutePlanner& p) { return plane2array(p.base().bytes, p.base().ny, p.base().nx); })
+      .def_property_readonly("max_cells", &mola_hip::RoutePlanner::maxCells);
+  // a key-frame set (a dict, or the path of a key-frame file), a pipeline and an events text -> a dict: "events" (one dict per event),
+  // "routes" (one route dict per `at`, with the costmap it was traced on under "costmap"), "costmap" (after the last event),
+  // "rects_outside", "summaries" (the command line's one line per event)
+  m.def("replan_route_from_keyframes", [dict2kfset, nav_cfg, nav2dict, route2dict, update2dict](const py::object& frames, const py::object& options,
+                                                                                              const std::string& events) {
+    const molahip_host::KeyFrameSet set = py::isinstance<py::str>(frames) ? molahip_host::read_keyframe_file(frames.cast<std::string>())
+                                                                         : dict2kfset(frames.cast<py::dict>());
+    const Config cfg = nav_cfg(options);
+    const std::vector<ReplanEvent> ev = mola_hip::parse_replan_events(events);
+    mola_hip::ReplanRun run;
+    {
+      py::gil_scoped_release nogil;
+      run = mola_hip::replan_route_from_keyframes(set, cfg, ev);
+    }
+    py::dict out;
+    py::list evs, routes, lines;
+    for (size_t k = 0; k < run.events.size(); k++) {
+      const mola_hip::ReplanEventResult& e = run.events[k];
+      py::dict d = e.event.verb == ReplanEvent::kAt ? py::dict() : update2dict(e.update);
+      d["verb"] = std::string(e.event.verbName()); d["line"] = e.event.line; d["route"] = e.route;
+      evs.append(d);
+      lines.append(mola_hip::replan_event_summary(run, k));
+    }
+    for (size_t k = 0; k < run.routes.size(); k++) {
+      py::dict d = route2dict(run.routes[k], run.costmap.nx, run.costmap.ny);
+      d["costmap"] = nav2dict(run.route_costmaps[k]);
+      routes.append(d);
+    }
+    out["events"] = evs; out["routes"] = routes; out["summaries"] = lines;
+    out["costmap"] = nav2dict(run.costmap); out["rects_outside"] = run.rects_outside;
+    return out; }, py::arg("frames"), py::arg("options"), py::arg("events"));
   // the pose rules of the driver's online loop closure and the motion model's rebase, on 12-value poses
   auto to_pose = [](const std::vector<double>& T) {
     if (T.size() != 12) throw std::runtime_error("a pose has 12 values");

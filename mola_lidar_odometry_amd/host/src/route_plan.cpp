@@ -127,7 +127,7 @@ void route_summarise(RoutePlan& r, const NavCostmap& c) {
   if (best != MH_NAV_FAR) r.min_clearance_m = std::sqrt((double)best) * c.resolution;
 }
 
-void write_route(const RoutePlan& r, const NavCostmap& c, const std::string& prefix) {
+void write_route(const RoutePlan& r, const NavCostmap& c, const std::string& prefix, const std::string& stem) {
   check_costmap(c, "write_route");
   if (r.xy.size() != r.cells.size()) throw std::runtime_error("write_route: the route's cells and its points differ in number");
   const char* const who = "write_route";
@@ -144,8 +144,8 @@ void write_route(const RoutePlan& r, const NavCostmap& c, const std::string& pre
     if (col < 0 || row < 0 || (uint32_t)col >= c.nx || (uint32_t)row >= c.ny) throw std::runtime_error("write_route: a route cell lies outside the window");
     px[(size_t)row * c.nx + (size_t)col] = 100;
   }
-  write_file(who, prefix + "_route.txt", text, std::ios::trunc);
-  write_file(who, prefix + "_route.pgm", pgm_bytes(px.data(), c.nx, c.ny), std::ios::trunc);
+  write_file(who, prefix + stem + ".txt", text, std::ios::trunc);
+  write_file(who, prefix + stem + ".pgm", pgm_bytes(px.data(), c.nx, c.ny), std::ios::trunc);
 }
 
 // ================================================================== the whole thing
